@@ -3,8 +3,25 @@
 N(500,50^2), FR) against an hg38-scale genome (3.1 Gbp; GRCh38 itself is not available offline, so a deterministic synthetic genome
 with repeat families is used and named as such).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
   (N > 1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...)
+
+A plain run measures the headline path alone (below: `value`, or with --no-e2e the resident pipeline): set-up, W warm-up steps, K timed
+steps, one JSON line.  --full adds everything else: the other two timed regions, per-kernel durations, algorithmic counters and the
+roofline, the measured bandwidth ceilings, `other_configs`, the CPU baseline and the in-run SAM parity check.
+
+The synthetic genome and its index are built once into a cache directory ($BWAHIP_BENCH_CACHE, default $XDG_CACHE_HOME/bwahip_bench or
+~/.cache/bwahip_bench); __graft_entry__.build() fills it for the default genome where a GPU is present.  Reads and FASTQ files are generated
+from fixed seeds in every run, so the inputs of two runs with the same arguments are identical.
+
+--dump-outputs DIR writes what the timed path returned in its last timed step (the file-to-file path: that step's SAM goes to a tmpfs file
+instead of /dev/null; the resident paths: the SAM of the last batch each context ran) as float64 arrays:
+  sam_records.npy   one row per read of a fixed, seeded sample of at most 131072 reads, the read's primary SAM line:
+                    [read index, FLAG, RNAME (contig index in the genome, -1 = *), POS, MAPQ, RNEXT (index, -1 = *), PNEXT, TLEN, NM, AS, XS
+                    (-1 when absent), reference bases the CIGAR spans, soft-clipped bases, lines of the read (primary + supplementary and
+                    secondary), 48-bit hash of the whole line]
+  sam_summary.npy   [SAM lines (header excluded), SAM bytes, reads, unmapped reads, supplementary lines, secondary lines]
+  sam_digest.npy    SHA-256 of all the SAM text of that step, as eight 32-bit words
 
 A "step" = one pass of the whole of mem_process_seqs -- hot path (mem_align1_core), insert-size statistics, mate rescue, pairing,
 mark-primary, CIGAR/NM/MD/mapQ, SAM text -- over this rank's read set (default 10 M reads = 5 M pairs, BASELINE configs[2]) in batches of
@@ -28,8 +45,10 @@ import hashlib
 import json
 import os
 import re
+import shutil
 import subprocess
 import sys
+import tempfile
 import threading
 import time
 
@@ -152,9 +171,9 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
-    ap.add_argument("--genome-mbp", type=int, default=int(os.environ.get("BWAHIP_BENCH_MBP", "3100")),
+    ap.add_argument("--genome-mbp", type=int, default=DEFAULT_MBP,
                     help="size of the synthetic genome (GRCh38 itself is not available offline); hg38 is 3.1 Gbp")
-    ap.add_argument("--genome-profile", default=os.environ.get("BWAHIP_BENCH_PROFILE", "default"), choices=["default", "human-like"],
+    ap.add_argument("--genome-profile", default=DEFAULT_PROFILE, choices=["default", "human-like"],
                     help="repeat content of the synthetic genome: default = dispersed families up to 1 400 copies; human-like = 45 %% of the bases in "
                          "Alu/L1-like families of 10^4..10^6 copies at 5-15 %% divergence plus satellite arrays")
     ap.add_argument("--reads", type=int, default=int(os.environ.get("BWAHIP_BENCH_READS", "10000000")),
@@ -172,6 +191,9 @@ def main():
                     help="contexts per GPU taking the batches in turn (double buffering) in gpu_pipeline; 1 = one batch at a time only")
     ap.add_argument("--stream-contexts", type=int, default=int(os.environ.get("BWAHIP_BENCH_STREAM_CONTEXTS", "3")),
                     help="contexts per GPU bwahip_stream_run deals the batches to (file to file: a third context covers the others' host phases)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the other timed regions, per-kernel durations, roofline, other configurations, CPU baseline and parity check")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the timed path computed in its last step to DIR/<name>.npy")
     args = ap.parse_args()
 
     rank = int(os.environ.get("RANK", "0"))
@@ -208,22 +230,18 @@ def main():
     workdir = os.environ.get("BWAHIP_BENCH_DIR", "/dev/shm/bwahip_bench" if os.path.isdir("/dev/shm") else "/tmp/bwahip_bench")
     os.makedirs(workdir, exist_ok=True)
     human = args.genome_profile == "human-like"
-    prefix = os.path.join(workdir, f"g{args.genome_mbp}" + ("h" if human else ""))
+    lens = tp.contig_lengths(args.genome_mbp * 1000000)
+    prefix = index_prefix(args.genome_mbp, args.genome_profile)
     fa = prefix + ".fa"
     t_index = 0.0
-    lens = tp.contig_lengths(args.genome_mbp * 1000000)
     cpus = usable_cpus()
-    # ---------------- genome + index: rank 0 builds (stock bwa format, cached under /dev/shm), the others receive it over RCCL
+    # ---------------- genome + index: rank 0 builds (stock bwa format, kept in the cache directory), the others receive it over RCCL
     genome = None
     if rank == 0:
         t0 = time.time()
-        if not (os.path.exists(prefix + ".sa") and os.path.exists(fa)):
-            genome = tp.make_genome(38, lens, repeats=True, profile=args.genome_profile)
-            tp.write_fasta(fa, genome, lens)
-            log(f"genome {args.genome_mbp} Mbp ({args.genome_profile}) generated and written: {time.time() - t0:.1f}s")
-            bw.make_index(fa, prefix)
+        genome = ensure_index(bw, tp, args.genome_mbp, args.genome_profile)
         t_index = time.time() - t0
-        log(f"genome + index ready: {t_index:.1f}s")
+        log(f"genome + index ready: {t_index:.1f}s ({prefix})")
     if world > 1:
         dist.barrier()
     t0 = time.time()
@@ -278,34 +296,52 @@ def main():
     reads = tp.make_reads(genome, lens, args.reads, args.read_len, sub_ppm=args.sub_ppm, seed=(103 if pe else 102) + rank, paired=pe)
     log(f"rank {rank}: {args.reads} reads generated ({time.time() - t0:.1f}s)")
     rl = args.read_len
-    res = Resident(bw, tp, torch, dev, reads, pe, args.batch)
-    n_batches = res.n_batches
+    full = args.full
+    n_batches = (args.reads + args.batch - 1) // args.batch
+    # the region the headline `value` comes from; a plain run times that one alone, --full all three
+    headline = "stream" if not args.no_e2e else ("pipeline" if args.overlap > 1 and n_batches > 1 else "single")
+    dump = args.dump_outputs if rank == 0 else None
+    res = Resident(bw, tp, torch, dev, reads, pe, args.batch) if full or headline != "stream" else None
     opt = bw.default_opt()
     if pe:
         opt.flag |= 0x2
     opt.n_threads = max(1, int(os.environ.get("BWAHIP_BENCH_HOST_THREADS", cpus // world)))
 
+    def dump_resident(ctxs):
+        """The SAM each context holds after the last timed step: that of the last batch it ran."""
+        pieces = []
+        for t, cx in enumerate(ctxs):
+            ran = range(t, res.n_batches, len(ctxs))
+            if len(ran):
+                pieces.append((cx.batch_sam(), res.bounds(ran[-1])[0]))
+        dump_sam(pieces, prefix, dump)
+
     # ---------------- single_context: one batch at a time on one context (kernel_ms, roofline)
-    for w in range(args.warmup):
+    single, kms = None, []
+    if full or headline == "single":
+        for w in range(args.warmup):
+            kms = []
+            res.step([ctx], opt, kms)
+            log(f"warmup {w}: kernel ms of batch 0 {dict((k, round(v, 2)) for k, v in kms[0].items())}")
+        sync_all()
+        t0 = time.time()
         kms = []
-        res.step([ctx], opt, kms)
-        log(f"warmup {w}: kernel ms of batch 0 {dict((k, round(v, 2)) for k, v in kms[0].items())}")
-    sync_all()
-    t0 = time.time()
-    kms = []
-    for _ in range(args.steps):
-        res.step([ctx], opt, kms)
-    sync_all()
-    elapsed = max_over_ranks(time.time() - t0)
-    single = {"value": round(args.reads * world * args.steps / elapsed, 1), "unit": "reads/s", "ms_per_step": round(elapsed / args.steps * 1e3, 3), "steps": args.steps,
-              "what": "reads resident in HBM, SAM left in HBM, one batch at a time on one context: the timed region `kernel_ms` and `roofline` are measured in"}
+        for _ in range(args.steps):
+            res.step([ctx], opt, kms)
+        sync_all()
+        elapsed = max_over_ranks(time.time() - t0)
+        single = {"value": round(args.reads * world * args.steps / elapsed, 1), "unit": "reads/s", "ms_per_step": round(elapsed / args.steps * 1e3, 3), "steps": args.steps,
+                  "what": "reads resident in HBM, SAM left in HBM, one batch at a time on one context: the timed region `kernel_ms` and `roofline` are measured in"}
+        if dump and headline == "single":
+            dump_resident([ctx])
     # ---------------- gpu_pipeline: the same steps double buffered on --overlap contexts sharing the index
-    clones = [ctx.clone() for _ in range(max(args.overlap, 1 if args.no_e2e else args.stream_contexts) - 1)]
+    n_clones = max(args.overlap if full or headline == "pipeline" else 1, 1 if args.no_e2e else args.stream_contexts) - 1
+    clones = [ctx.clone() for _ in range(n_clones)]
     ctxs = [ctx] + clones[:max(0, args.overlap - 1)]
     sctxs = [ctx] + clones[:max(0, args.stream_contexts - 1)]
     dbuf = None
-    if len(ctxs) > 1 and n_batches > 1:
-        for _ in range(max(1, min(args.warmup, 2))):
+    if (full or headline == "pipeline") and len(ctxs) > 1 and n_batches > 1:
+        for _ in range(max(1, min(args.warmup, 2)) if full else args.warmup):
             res.step(ctxs, opt)
         sync_all()
         t0 = time.time()
@@ -317,11 +353,17 @@ def main():
                 "what": "reads (codes, names, qualities) resident in HBM when the timed region starts, SAM text left in HBM; the batches of a step are taken in turn by "
                         "several contexts on the GPU (bwahip_ctx_clone: shared index, own streams and host thread each), so that one batch's latency-bound kernels and "
                         "serial tails run under another batch's throughput-bound kernels"}
-        log(f"gpu pipeline, double buffered ({len(ctxs)} contexts): {dbuf['value']:.0f} reads/s vs {single['value']:.0f} one batch at a time")
-    counters, sam_resident0 = res.count(ctx, opt)
-    sam_bytes = len(sam_resident0)
-    if pe:
-        log(f"batch 0: insert size FR {ctx.last_pe_stats()[0][1]}; mate rescue {ctx.pe_counters}")
+        if single:
+            log(f"gpu pipeline, double buffered ({len(ctxs)} contexts): {dbuf['value']:.0f} reads/s vs {single['value']:.0f} one batch at a time")
+        else:
+            log(f"gpu pipeline, double buffered ({len(ctxs)} contexts): {dbuf['value']:.0f} reads/s")
+        if dump and headline == "pipeline":
+            dump_resident(ctxs)
+    if full:
+        counters, sam_resident0 = res.count(ctx, opt)
+        sam_bytes = len(sam_resident0)
+        if pe:
+            log(f"batch 0: insert size FR {ctx.last_pe_stats()[0][1]}; mate rescue {ctx.pe_counters}")
 
     # ---------------- value: FASTQ files -> SAM text through the library's batch driver (bwahip_stream_run), this rank's own files
     stream = None
@@ -333,30 +375,36 @@ def main():
         log(f"rank {rank}: FASTQ files written ({time.time() - t0:.1f}s): {' '.join(fqs)}")
         fq2 = fqs[1] if pe else None
         reader_threads = int(os.environ.get("BWAHIP_BENCH_READER_THREADS", max(2, min(8, opt.n_threads // 2))))
-        # untimed pass 0: SAM to a file on tmpfs (kept for the parity check below); buffers grow to the batch size here
-        fd = os.open(stream_sam_path, os.O_WRONLY | os.O_CREAT | os.O_TRUNC, 0o644)
-        try:
-            st0 = bw.stream_run(sctxs, fqs[0], fq2, fd, opt, chunk_bases=K_bases, reader_threads=reader_threads)
-        finally:
-            os.close(fd)
-        log(f"stream pass 0 (to a tmpfs file, buffers growing): {st0.n_reads} reads, {st0.sam_bytes} SAM bytes in {st0.seconds:.3f}s")
         devnull = os.open("/dev/null", os.O_WRONLY)
-        for _ in range(max(0, args.warmup - 1)):
+        n_warm = args.warmup
+        if full:
+            # untimed pass 0: SAM to a file on tmpfs (kept for the parity check below); buffers grow to the batch size here
+            fd = os.open(stream_sam_path, os.O_WRONLY | os.O_CREAT | os.O_TRUNC, 0o644)
+            try:
+                st0 = bw.stream_run(sctxs, fqs[0], fq2, fd, opt, chunk_bases=K_bases, reader_threads=reader_threads)
+            finally:
+                os.close(fd)
+            log(f"stream pass 0 (to a tmpfs file, buffers growing): {st0.n_reads} reads, {st0.sam_bytes} SAM bytes in {st0.seconds:.3f}s")
+            n_warm = max(0, args.warmup - 1)
+        for _ in range(n_warm):
             bw.stream_run(sctxs, fqs[0], fq2, devnull, opt, chunk_bases=K_bases, reader_threads=reader_threads)
+        # with --dump-outputs the last timed step writes its SAM to a tmpfs file instead of /dev/null
+        dump_path = stream_sam_path + ".last"
         sync_all()
         t0 = time.time()
-        sts = [bw.stream_run(sctxs, fqs[0], fq2, devnull, opt, chunk_bases=K_bases, reader_threads=reader_threads) for _ in range(args.steps)]
+        sts = []
+        for i in range(args.steps):
+            out_fd = os.open(dump_path, os.O_WRONLY | os.O_CREAT | os.O_TRUNC, 0o644) if dump and i == args.steps - 1 else devnull
+            try:
+                sts.append(bw.stream_run(sctxs, fqs[0], fq2, out_fd, opt, chunk_bases=K_bases, reader_threads=reader_threads))
+            finally:
+                if out_fd != devnull:
+                    os.close(out_fd)
         sync_all()
         el3 = max_over_ranks(time.time() - t0)
         os.close(devnull)
-        # the same once more with the SAM written to a tmpfs file (one memcpy of 420 bytes per read more, on the writer thread)
-        fd = os.open(stream_sam_path + ".2", os.O_WRONLY | os.O_CREAT | os.O_TRUNC, 0o644)
-        try:
-            st_file = bw.stream_run(sctxs, fqs[0], fq2, fd, opt, chunk_bases=K_bases, reader_threads=reader_threads)
-        finally:
-            os.close(fd)
-            os.unlink(stream_sam_path + ".2")
-        assert all(s.n_reads == args.reads and s.sam_bytes == st0.sam_bytes for s in sts + [st_file])
+        if not full:
+            st0 = sts[0]
         stream = {"value": round(args.reads * world * args.steps / el3, 1), "unit": "reads/s", "ms_per_step": round(el3 / args.steps * 1e3, 3),
                   "contexts_per_gpu": len(sctxs), "reader_threads": reader_threads, "host_threads_per_gpu": opt.n_threads,
                   "sam_bytes_per_step": int(st0.sam_bytes), "batches_per_step": int(st0.n_batches),
@@ -364,17 +412,35 @@ def main():
                   "workers_waiting_for_reader_s": round(sum(s.reader_wait_s for s in sts) / args.steps, 4),
                   "workers_in_process_seqs_s": round(sum(s.gpu_busy_s for s in sts) / args.steps, 4),
                   "writer_in_write_s": round(sum(s.write_s for s in sts) / args.steps, 4),
-                  "to_tmpfs_file_reads_per_s": round(st_file.n_reads / st_file.seconds, 1),
                   "what": "bwahip_stream_run: two FASTQ files on tmpfs (one for --se) -> the library's parallel reader -> whole -K batches with their true n_processed "
                           "on the contexts -> SAM text in input order to /dev/null (to_tmpfs_file_reads_per_s: to a file); opening the files to the last SAM "
                           "byte, PCIe both ways and all host work included"}
-        log(f"file to file: {stream['value']:.0f} reads/s ({el3 / args.steps:.3f}s per step); to a tmpfs file {stream['to_tmpfs_file_reads_per_s']:.0f}")
+        if dump:
+            stream["last_step_to"] = "a tmpfs file (--dump-outputs)"
+        if full:
+            # the same once more with the SAM written to a tmpfs file (one memcpy of 420 bytes per read more, on the writer thread)
+            fd = os.open(stream_sam_path + ".2", os.O_WRONLY | os.O_CREAT | os.O_TRUNC, 0o644)
+            try:
+                st_file = bw.stream_run(sctxs, fqs[0], fq2, fd, opt, chunk_bases=K_bases, reader_threads=reader_threads)
+            finally:
+                os.close(fd)
+                os.unlink(stream_sam_path + ".2")
+            sts.append(st_file)
+            stream["to_tmpfs_file_reads_per_s"] = round(st_file.n_reads / st_file.seconds, 1)
+        assert all(s.n_reads == args.reads and s.sam_bytes == st0.sam_bytes for s in sts)
+        log(f"file to file: {stream['value']:.0f} reads/s ({el3 / args.steps:.3f}s per step)"
+            + (f"; to a tmpfs file {stream['to_tmpfs_file_reads_per_s']:.0f}" if full else ""))
+        if dump:
+            try:
+                dump_sam([(dump_path, 0)], prefix, dump)
+            finally:
+                os.unlink(dump_path)
     for c2 in clones:
         c2.close()
 
     # ---------------- other BASELINE configurations on the same index (rank 0, N = 1)
     other = {}
-    if rank == 0 and world == 1 and not args.no_other_configs and not args.no_cpu_baseline:
+    if full and rank == 0 and world == 1 and not args.no_other_configs and not args.no_cpu_baseline:
         for key, (o_rl, o_sub, o_seed) in (("configs[1]", (150, 10000, 102)), ("configs[4]", (250, 50000, 105))):
             if (not pe) and o_rl == rl and o_sub == args.sub_ppm:
                 continue
@@ -388,14 +454,6 @@ def main():
             value, ms_step, what = dbuf["value"], dbuf["ms_per_step"], "gpu_pipeline (reads resident in HBM)"
         else:
             value, ms_step, what = single["value"], single["ms_per_step"], "single_context (reads resident in HBM)"
-        k1 = float(np.mean([k["k_smem"] for k in kms]))
-        # algorithmic bytes of the BWT-search kernel per launch: 64 B per Occ block touched by bwt_extend +
-        # the read bytes in + 32 B per interval out, counted by the kernel itself (the few reads k_smem hands to
-        # k_smem_heavy, and pass 3 which runs in k_smem3, are counted by those kernels and subtracted)
-        alg_total = (64 * (counters["blocks"] - counters["heavy_blocks"] - counters["pass3_blocks"]) + args.reads * rl +
-                     32 * (counters["intv"] - counters["heavy_intv"] - counters["pass3_intv"]))
-        alg_bytes = alg_total / n_batches
-        achieved = alg_bytes / (k1 * 1e-3) / 1e9
         kind = (f"{args.reads // 2} pairs (2x{rl} bp, FR, insert N(500,50^2) clipped [300,700])" if pe else f"{args.reads} SE reads of {rl} bp")
         gdesc = ("45 % of the bases in Alu/L1-like families of 10^4..10^6 copies at 5-15 % divergence, satellite arrays" if human else "repeat families up to 1 400 copies")
         out = {
@@ -411,43 +469,57 @@ def main():
                        "stages": ctx.stage_names(),
                        "output": ctx.output_description(pe),
                        "index_in_hbm": ctx.index_footprint(), "index_build_s": round(t_index, 1), "index_to_hbm_s": round(t_bcast, 2), "index_distribution": index_distribution, "host_cpus_usable": cpus},
-            "kernel_ms": {k: round(float(np.mean([x[k] for x in kms])), 3) for k in kms[0]},
-            "launches_timed": n_launch, "sam_bytes_per_batch": sam_bytes,
-            "per_read": per_read(counters, args.reads),
-            "tail_us": tails(counters),
-            "tail_counts": {"max_extends_per_read": counters.get("max_extends"), "max_seeds_per_read": counters.get("max_seeds"), "max_chains_per_read": counters.get("max_chains")},
-            "roofline": {"kernel": "k_smem", "bound": "hbm", "achieved": round(achieved, 1), "peak": 8000.0, "unit": "GB/s",
-                         "frac": round(achieved / 8000.0, 4), "traffic": None,
-                         "algorithmic_bytes_per_launch": int(alg_bytes), "avg_launch_ms": round(k1, 3), "reads_per_launch": args.batch},
         }
-        out["single_context"] = single
+        out["full"] = full
+        if single:
+            out["single_context"] = single
         if dbuf:
             out["gpu_pipeline"] = dbuf
-            out["sum_kernel_ms_over_gpu_pipeline_ms_per_batch"] = round(sum(out["kernel_ms"].values()) / (dbuf["ms_per_step"] / n_batches), 3)
         if stream:
             out["file_to_file"] = stream
-        # the other kernels SURVEY.md 8(d) asks figures for: the SA look-up kernels against the same HBM roofline, the integer DP of the
-        # extension in cell updates per second (no roofline fraction: VALU / LDS issue bound, no MFMA work anywhere)
-        out["other_kernels"] = other_kernels(out["kernel_ms"], counters, n_batches)
-        # HBM traffic of the same kernel from the committed PMC passes of this very command (counters cannot be read from
-        # inside the process); quoted only when the per-launch workload (one batch) AND the kernel sources are the ones the
-        # counters were collected on
-        try:
-            pt = json.load(open(os.path.join(ROOT, "profiles", "pmc_traffic.json")))
-            if pt.get("launch_workload") == out["config"]["launch_workload"] and pt.get("kernel_src_sha256") == kernel_src_sha():
-                out["roofline"]["traffic"] = int(pt["fetch_bytes_per_launch"] + pt["write_bytes_per_launch"])
-                out["roofline"]["traffic_source"] = pt["source"]
-        except (OSError, ValueError, KeyError):
-            pass
-        ceil = measured_ceilings() if world == 1 else None
-        if ceil:
-            # what this very device sustains for the kernel's access pattern (dependent random 64-byte gathers, one lane per
-            # block, 3 GB table) and for a plain streaming copy -- SURVEY.md 8(d); `peak` above stays the 8 TB/s spec figure
-            out["roofline"]["measured_gather64_GBps"] = ceil["gather64_GBps"]
-            out["roofline"]["measured_stream_copy_GBps"] = ceil["stream_copy_GBps"]
-            out["roofline"]["frac_of_measured_gather"] = round(achieved / ceil["gather64_GBps"], 4)
         parity_ok = None
-        if not args.no_cpu_baseline and world == 1:               # rank 0 at N = 1 only
+        if full:
+            k1 = float(np.mean([k["k_smem"] for k in kms]))
+            # algorithmic bytes of the BWT-search kernel per launch: 64 B per Occ block touched by bwt_extend +
+            # the read bytes in + 32 B per interval out, counted by the kernel itself (the few reads k_smem hands to
+            # k_smem_heavy, and pass 3 which runs in k_smem3, are counted by those kernels and subtracted)
+            alg_total = (64 * (counters["blocks"] - counters["heavy_blocks"] - counters["pass3_blocks"]) + args.reads * rl +
+                         32 * (counters["intv"] - counters["heavy_intv"] - counters["pass3_intv"]))
+            alg_bytes = alg_total / n_batches
+            achieved = alg_bytes / (k1 * 1e-3) / 1e9
+            out.update({
+                "kernel_ms": {k: round(float(np.mean([x[k] for x in kms])), 3) for k in kms[0]},
+                "launches_timed": n_launch, "sam_bytes_per_batch": sam_bytes,
+                "per_read": per_read(counters, args.reads),
+                "tail_us": tails(counters),
+                "tail_counts": {"max_extends_per_read": counters.get("max_extends"), "max_seeds_per_read": counters.get("max_seeds"), "max_chains_per_read": counters.get("max_chains")},
+                "roofline": {"kernel": "k_smem", "bound": "hbm", "achieved": round(achieved, 1), "peak": 8000.0, "unit": "GB/s",
+                             "frac": round(achieved / 8000.0, 4), "traffic": None,
+                             "algorithmic_bytes_per_launch": int(alg_bytes), "avg_launch_ms": round(k1, 3), "reads_per_launch": args.batch},
+            })
+            if dbuf:
+                out["sum_kernel_ms_over_gpu_pipeline_ms_per_batch"] = round(sum(out["kernel_ms"].values()) / (dbuf["ms_per_step"] / n_batches), 3)
+            # the other kernels SURVEY.md 8(d) asks figures for: the SA look-up kernels against the same HBM roofline, the integer DP of the
+            # extension in cell updates per second (no roofline fraction: VALU / LDS issue bound, no MFMA work anywhere)
+            out["other_kernels"] = other_kernels(out["kernel_ms"], counters, n_batches)
+            # HBM traffic of the same kernel from the committed PMC passes of this very command (counters cannot be read from
+            # inside the process); quoted only when the per-launch workload (one batch) AND the kernel sources are the ones the
+            # counters were collected on
+            try:
+                pt = json.load(open(os.path.join(ROOT, "profiles", "pmc_traffic.json")))
+                if pt.get("launch_workload") == out["config"]["launch_workload"] and pt.get("kernel_src_sha256") == kernel_src_sha():
+                    out["roofline"]["traffic"] = int(pt["fetch_bytes_per_launch"] + pt["write_bytes_per_launch"])
+                    out["roofline"]["traffic_source"] = pt["source"]
+            except (OSError, ValueError, KeyError):
+                pass
+            ceil = measured_ceilings() if world == 1 else None
+            if ceil:
+                # what this very device sustains for the kernel's access pattern (dependent random 64-byte gathers, one lane per
+                # block, 3 GB table) and for a plain streaming copy -- SURVEY.md 8(d); `peak` above stays the 8 TB/s spec figure
+                out["roofline"]["measured_gather64_GBps"] = ceil["gather64_GBps"]
+                out["roofline"]["measured_stream_copy_GBps"] = ceil["stream_copy_GBps"]
+                out["roofline"]["frac_of_measured_gather"] = round(achieved / ceil["gather64_GBps"], 4)
+        if full and not args.no_cpu_baseline and world == 1:      # rank 0 at N = 1 only
             n_s = min(args.cpu_sample, args.reads)
             if pe and n_s < min(args.batch, args.reads):
                 # paired-end: mem_pestat is per batch, so a part of a batch is not the same problem (other insert-size bounds, other rescues)
@@ -485,6 +557,107 @@ def main():
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
+
+
+DEFAULT_MBP = int(os.environ.get("BWAHIP_BENCH_MBP", "3100"))
+DEFAULT_PROFILE = os.environ.get("BWAHIP_BENCH_PROFILE", "default")
+
+
+def prepare(bw):
+    """The default genome and its index into the cache directory (__graft_entry__.build() calls this where a GPU is present)."""
+    import tools_py as tp
+    ensure_index(bw, tp, DEFAULT_MBP, DEFAULT_PROFILE)
+
+
+def cache_dir():
+    d = os.environ.get("BWAHIP_BENCH_CACHE")
+    if not d:
+        d = os.path.join(os.environ.get("XDG_CACHE_HOME") or os.path.join(os.path.expanduser("~"), ".cache"), "bwahip_bench")
+    return d
+
+
+def index_prefix(genome_mbp, profile):
+    return os.path.join(cache_dir(), f"g{genome_mbp}" + ("h" if profile == "human-like" else ""))
+
+
+INDEX_EXTS = (".amb", ".ann", ".bwt", ".pac", ".sa", ".fa")        # .fa last: its presence marks a complete set
+
+
+def ensure_index(bw, tp, genome_mbp, profile="default"):
+    """The synthetic genome (seed 38) as FASTA plus its index in the cache directory, built when missing.  Built in a private directory
+    and moved into place file by file, so that a concurrent run never sees a partial set.  Returns the genome when it was generated."""
+    prefix = index_prefix(genome_mbp, profile)
+    if all(os.path.exists(prefix + e) for e in INDEX_EXTS):
+        return None
+    d, name = os.path.split(prefix)
+    os.makedirs(d, exist_ok=True)
+    t0 = time.time()
+    lens = tp.contig_lengths(genome_mbp * 1000000)
+    genome = tp.make_genome(38, lens, repeats=True, profile=profile)
+    tmp = tempfile.mkdtemp(prefix=name + ".", dir=d)
+    try:
+        tp.write_fasta(os.path.join(tmp, name + ".fa"), genome, lens)
+        log(f"genome {genome_mbp} Mbp ({profile}) generated and written: {time.time() - t0:.1f}s")
+        bw.make_index(os.path.join(tmp, name + ".fa"), os.path.join(tmp, name))
+        for e in INDEX_EXTS:
+            os.replace(os.path.join(tmp, name + e), prefix + e)
+    finally:
+        shutil.rmtree(tmp, ignore_errors=True)
+    return genome
+
+
+def dump_sam(pieces, prefix, out_dir, sample=1 << 17, seed=20261016):
+    """pieces: [(SAM bytes or a path to a SAM file, index of its first read)], the reads of each piece in input order; prefix: the index
+    (contig order from its .ann).  Writes the arrays the module docstring lists (float64) to out_dir."""
+    os.makedirs(out_dir, exist_ok=True)
+    with open(prefix + ".ann", "rb") as f:
+        sq = {ln.split()[1]: i for i, ln in enumerate(f.read().splitlines()[1::2])}
+    digest, rows_all = hashlib.sha256(), []
+    summary = np.zeros(6)
+    for src, first in pieces:
+        buf = np.fromfile(src, dtype=np.uint8) if isinstance(src, str) else np.frombuffer(src, dtype=np.uint8)
+        digest.update(buf)
+        ends = np.flatnonzero(buf == 10)
+        starts = np.concatenate(([0], ends[:-1] + 1)).astype(np.int64)
+        head = buf[starts] == ord("@")
+        starts, ends = starts[~head], ends[~head]
+        # FLAG: the second field; QNAME is fixed width in this benchmark (fixed_names)
+        w = int(np.argmax(buf[starts[0]:starts[0] + 256] == 9)) if len(starts) else 0
+        assert len(starts) == 0 or bool(np.all(buf[starts + w] == 9)), "QNAME of varying width"
+        flag = np.zeros(len(starts), dtype=np.int64)
+        done = np.zeros(len(starts), dtype=bool)
+        for j in range(1, 6):
+            c = buf[np.minimum(starts + w + j, len(buf) - 1)].astype(np.int64)
+            done |= (c < 48) | (c > 57)
+            flag = np.where(done, flag, flag * 10 + c - 48)
+        prim = (flag & 0x900) == 0
+        n_reads = int(prim.sum())
+        summary += [len(starts), len(buf), n_reads, int(((flag & 4) != 0)[prim].sum()), int(((flag & 0x800) != 0).sum()),
+                    int(((flag & 0x100) != 0).sum())]
+        line_of_read = np.flatnonzero(prim)
+        lines_per_read = np.diff(np.append(line_of_read, len(starts)))
+        rows_all.append((buf, starts[line_of_read], ends[line_of_read], lines_per_read, first))
+    total = sum(len(r[1]) for r in rows_all)
+    pick = np.sort(np.random.default_rng(seed).choice(total, min(sample, total), replace=False))
+    recs, base = [], 0
+    for buf, st, en, lpr, first in rows_all:
+        for k in pick[(pick >= base) & (pick < base + len(st))] - base:
+            line = bytes(buf[st[k]:en[k]])
+            f = line.split(b"\t")
+            tags = {t[:2]: t[5:] for t in f[11:]}
+            ref_len = clip = 0
+            for n, op in re.findall(rb"(\d+)([MIDNSHP=X])", f[5]):
+                ref_len += int(n) if op in b"MDN=X" else 0
+                clip += int(n) if op == b"S" else 0
+            rname = sq.get(f[2], -1)
+            recs.append([first + k, int(f[1]), rname, int(f[3]), int(f[4]), rname if f[6] == b"=" else sq.get(f[6], -1), int(f[7]), int(f[8]),
+                         int(tags.get(b"NM", -1)), int(tags.get(b"AS", -1)), int(tags.get(b"XS", -1)), ref_len, clip, int(lpr[k]),
+                         int.from_bytes(hashlib.blake2b(line, digest_size=6).digest(), "little")])
+        base += len(st)
+    np.save(os.path.join(out_dir, "sam_records.npy"), np.asarray(recs, dtype=np.float64).reshape(-1, 15))
+    np.save(os.path.join(out_dir, "sam_summary.npy"), summary)
+    np.save(os.path.join(out_dir, "sam_digest.npy"), np.frombuffer(digest.digest(), dtype=">u4").astype(np.float64))
+    log(f"outputs of the last timed step: {len(recs)} sampled reads of {total} -> {out_dir}")
 
 
 def other_kernels(km, counters, n_batches):

@@ -1,11 +1,11 @@
 #!/usr/bin/env python3
-"""Copy the summaries of a scripts/profile_round.sh run (gpurun_out/<tag>/) into profiles/<round>/ (tracked).
+"""Copy the summaries of a scripts/profile_round.sh run ($BWAHIP_OUT/<tag>/, default bench_out/<tag>/) into profiles/<round>/ (tracked).
 usage: scripts/collect_profiles.py <tag> <round-dir>"""
 import csv, glob, hashlib, json, os, re, shutil, sys, collections
 
 tag, dst = sys.argv[1], sys.argv[2]
-traffic_only = "--traffic-only" in sys.argv       # on the GPU box: only (re)write profiles/pmc_traffic.json
-src = os.path.join("gpurun_out", tag)
+traffic_only = "--traffic-only" in sys.argv       # only (re)write profiles/pmc_traffic.json
+src = os.path.join(os.environ.get("BWAHIP_OUT", "bench_out"), tag)
 os.makedirs(dst, exist_ok=True)
 if not traffic_only:
     if os.path.exists(os.path.join(src, "bench_default.json")):      # the unprofiled run may come from a later call (profile_round.sh bench)
@@ -40,6 +40,6 @@ if key:
         sha.update(open(os.path.join("bwa-mem-gpu_amd", "csrc", f), "rb").read())
     out = {"launch_workload": bench["config"]["launch_workload"], "kernel": key[0], "kernel_src_sha256": sha.hexdigest(),
            "fetch_bytes_per_launch": t["FETCH_SIZE"] / n["FETCH_SIZE"] * 1024, "write_bytes_per_launch": t["WRITE_SIZE"] / n["WRITE_SIZE"] * 1024,
-           "source": f"{dst}/pmc_bench_default.csv (separate rocprofv3 --pmc passes of `python3 bench.py --steps 1 --warmup 0 --reads 2000000 --overlap 1 --no-cpu-baseline --no-e2e`; per launch = per batch of 1 M reads)"}
+           "source": f"{dst}/pmc_bench_default.csv (separate rocprofv3 --pmc passes of `python3 bench.py --full --steps 1 --warmup 0 --reads 2000000 --overlap 1 --no-cpu-baseline --no-e2e`; per launch = per batch of 1 M reads)"}
     json.dump(out, open(os.path.join("profiles", "pmc_traffic.json"), "w"), indent=1)
     print(out)

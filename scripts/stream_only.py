@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""bwahip_stream_run alone on the files a bench.py run left in /dev/shm/bwahip_bench (index g3100, bench_r0_[12].fq): for a kernel trace of the
+"""bwahip_stream_run alone on the files a bench.py run left (FASTQ bench_r0_[12].fq in /dev/shm/bwahip_bench, index g3100 in bench.py's cache
+directory): for a kernel trace of the
 file-to-file path (rocprofv3 --kernel-trace -- python3 scripts/stream_only.py [contexts] [passes]).  Prints reads/s per pass."""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -9,7 +10,8 @@ bw = entry.load_bwahip()
 d = os.environ.get("BWAHIP_BENCH_DIR", "/dev/shm/bwahip_bench")
 n_ctx = int(sys.argv[1]) if len(sys.argv) > 1 else 2
 passes = int(sys.argv[2]) if len(sys.argv) > 2 else 2
-prefix = os.path.join(d, os.environ.get("BWAHIP_BENCH_INDEX", "g3100"))
+cache = os.environ.get("BWAHIP_BENCH_CACHE") or os.path.join(os.environ.get("XDG_CACHE_HOME") or os.path.expanduser("~/.cache"), "bwahip_bench")
+prefix = os.path.join(cache, os.environ.get("BWAHIP_BENCH_INDEX", "g3100"))
 fq1, fq2 = os.path.join(d, "bench_r0_1.fq"), os.path.join(d, "bench_r0_2.fq")
 opt = bw.default_opt(); opt.flag |= 2; opt.n_threads = int(os.environ.get("BWAHIP_BENCH_HOST_THREADS", "16"))
 with bw.Context(prefix, 0) as c0:
