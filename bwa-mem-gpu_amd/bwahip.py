@@ -107,6 +107,16 @@ def lib():
     L.bwahip_ctx_clone_on.argtypes = [vp, C.c_int, C.POINTER(vp)]
     L.bwahip_stream_run.argtypes = [C.POINTER(vp), C.c_int, C.POINTER(Opt), C.POINTER(PeStat), C.c_char_p, C.c_char_p, C.c_int, C.POINTER(StreamStats)]
     L.bwahip_process_seqs_text.argtypes = [vp, C.POINTER(Opt), C.c_int64, C.c_int, C.POINTER(Seq), C.c_void_p, C.POINTER(C.c_char_p), i64p, C.POINTER(i64p)]
+    L.bwahip_process_seqs_bam.argtypes = [vp, C.POINTER(Opt), C.c_int64, C.c_int, C.POINTER(Seq), C.c_void_p, C.POINTER(vp), i64p, C.POINTER(i64p)]
+    L.bwahip_batch_run_bam.argtypes = [vp, C.POINTER(Opt), C.c_int64, C.POINTER(PeStat), C.POINTER(C.c_float), C.c_int]
+    L.bwahip_batch_bam.argtypes = [vp, C.POINTER(vp), i64p, vp]
+    L.bwahip_bam_header.argtypes = [C.POINTER(Bns), C.c_char_p, C.POINTER(vp), i64p]
+    L.bwahip_bgzf_write.argtypes = [C.c_int, vp, C.c_int64, C.c_int, C.c_int]
+    L.bwahip_bgzf_eof.argtypes = [C.c_int]
+    L.bwahip_bns.argtypes = [vp]
+    L.bwahip_bns.restype = C.POINTER(Bns)
+    L.bwahip_stream_run_bam.argtypes = [C.POINTER(vp), C.c_int, C.POINTER(Opt), C.POINTER(PeStat), C.c_char_p, C.c_char_p, C.c_int, C.c_char_p, C.c_int,
+                                        C.POINTER(StreamStats)]
     L.bwahip_fastq_open.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(vp)]
     L.bwahip_fastq_next.argtypes = [vp, C.c_int64, C.c_int, C.POINTER(C.POINTER(Seq)), C.POINTER(C.c_int)]
     L.bwahip_fastq_close.argtypes = [vp]
@@ -158,6 +168,50 @@ def big_bytes(ptr, n):
 def _check(rc, what):
     if rc != 0:
         raise BwahipError(f"{what} failed: {ERRORS.get(rc, rc)}")
+
+
+def _free(ptr):
+    libc = C.CDLL(None)
+    libc.free.argtypes = [C.c_void_p]
+    libc.free(ptr)
+
+
+def seq_array(names, seqs, quals=None, comments=None):
+    """A bseq1_t array of ASCII reads for the process_seqs_*_array calls; returns (array, the buffers it points into).  The library
+    converts the bases in place, so an array serves one call."""
+    n = len(seqs)
+    arr = (Seq * n)()
+    keep = []
+    for i in range(n):
+        sb = C.create_string_buffer(bytes(seqs[i]), len(seqs[i]) + 1)
+        keep.append(sb)
+        arr[i].l_seq, arr[i].id = len(seqs[i]), i
+        arr[i].name = bytes(names[i])
+        arr[i].comment = bytes(comments[i]) if comments is not None and comments[i] is not None else None
+        arr[i].seq = C.cast(sb, C.POINTER(C.c_char))
+        arr[i].qual = bytes(quals[i]) if quals is not None and quals[i] is not None else None
+    return arr, keep
+
+
+def bam_header(bns, hdr_line=None):
+    """bwahip_bam_header: the uncompressed BAM header (magic, text, reference table) of a Bns (or of a Context's index); no device."""
+    if isinstance(bns, Context):
+        bns = lib().bwahip_bns(bns._h).contents
+    out, ln = C.c_void_p(), C.c_int64()
+    if isinstance(hdr_line, str):
+        hdr_line = hdr_line.encode()
+    _check(lib().bwahip_bam_header(C.byref(bns), hdr_line, C.byref(out), C.byref(ln)), "bwahip_bam_header")
+    b = big_bytes(out, ln.value)
+    _free(out)
+    return b
+
+
+def bgzf_write(fd, data, level=1, n_threads=1, eof=False):
+    """bwahip_bgzf_write: data as BGZF blocks on fd; eof: the end-of-file block after them (bwahip_bgzf_eof)."""
+    data = bytes(data)
+    _check(lib().bwahip_bgzf_write(fd, data, len(data), level, n_threads), "bwahip_bgzf_write")
+    if eof:
+        _check(lib().bwahip_bgzf_eof(fd), "bwahip_bgzf_eof")
 
 
 def default_opt():
@@ -331,6 +385,19 @@ class Context:
         text = big_bytes(sam, ln.value)
         return (text, [off[i] for i in range(n + 1)]) if want_offsets else text
 
+    def process_seqs_bam_array(self, arr, n, opt=None, n_processed=0, pes0=None, want_offsets=False):
+        """bwahip_process_seqs_bam on a bseq1_t array: the batch's BAM records (no header, uncompressed) as one bytes object."""
+        opt = opt or default_opt()
+        bam, ln, off = C.c_void_p(), C.c_int64(), C.POINTER(C.c_int64)()
+        _check(lib().bwahip_process_seqs_bam(self._h, C.byref(opt), n_processed, n, arr, pes0, C.byref(bam), C.byref(ln), C.byref(off)), "bwahip_process_seqs_bam")
+        rec = big_bytes(bam, ln.value)
+        return (rec, [off[i] for i in range(n + 1)]) if want_offsets else rec
+
+    def process_seqs_bam(self, names, seqs, quals=None, opt=None, n_processed=0, pes0=None, comments=None, want_offsets=False):
+        """The same from lists of names / ASCII reads (/ qualities, comments)."""
+        arr, keep = seq_array(names, seqs, quals, comments)
+        return self.process_seqs_bam_array(arr, len(seqs), opt, n_processed, pes0, want_offsets)
+
     def last_pe_stats(self):
         """(pestat[4] as dicts, mate-rescue alignments run on the GPU, regions they added) of the last PE batch."""
         pes = (PeStat * 4)()
@@ -367,6 +434,21 @@ class Context:
         libc.free.argtypes = [C.c_void_p]
         libc.free(out)
         return sam
+
+    def batch_run_bam(self, opt=None, n_processed=0, pes0=None):
+        """batch_run_sam with BAM records as the output (the same kernel_ms slots)."""
+        opt = opt or default_opt()
+        nk = lib().bwahip_n_kernels()
+        ms = (C.c_float * nk)()
+        _check(lib().bwahip_batch_run_bam(self._h, C.byref(opt), n_processed, pes0, ms, nk), "bwahip_batch_run_bam")
+        return {lib().bwahip_kernel_name(i).decode(): float(ms[i]) for i in range(nk)}
+
+    def batch_bam(self):
+        out, ln = C.c_void_p(), C.c_int64()
+        _check(lib().bwahip_batch_bam(self._h, C.byref(out), C.byref(ln), None), "bwahip_batch_bam")
+        rec = big_bytes(out, ln.value)
+        _free(out)
+        return rec
 
     def batch_run(self, opt=None):
         opt = opt or default_opt()
@@ -503,6 +585,21 @@ def stream_run(ctxs, fq1, fq2=None, out_fd=-1, opt=None, chunk_bases=0, max_read
     arr = (C.c_void_p * len(ctxs))(*[c._h for c in ctxs])
     _check(lib().bwahip_stream_run(arr, len(ctxs), C.byref(opt), C.byref(pes0) if pes0 is not None else None, os.fsencode(fq1),
                                    os.fsencode(fq2) if fq2 else None, out_fd, C.byref(st)), "bwahip_stream_run")
+    return st
+
+
+def stream_run_bam(ctxs, fq1, fq2=None, out_fd=-1, hdr_line=None, level=1, opt=None, chunk_bases=0, max_reads=0, keep_comments=False,
+                   reader_threads=0, pes0=None):
+    """bwahip_stream_run_bam: FASTQ files -> a BAM file (header, BGZF blocks, EOF block) on out_fd.  Returns the filled StreamStats
+    (sam_bytes = uncompressed bytes of the records)."""
+    opt = opt or default_opt()
+    st = StreamStats()
+    st.chunk_bases, st.max_reads, st.keep_comments, st.reader_threads = chunk_bases, max_reads, int(keep_comments), reader_threads
+    arr = (C.c_void_p * len(ctxs))(*[c._h for c in ctxs])
+    if isinstance(hdr_line, str):
+        hdr_line = hdr_line.encode()
+    _check(lib().bwahip_stream_run_bam(arr, len(ctxs), C.byref(opt), C.byref(pes0) if pes0 is not None else None, os.fsencode(fq1),
+                                       os.fsencode(fq2) if fq2 else None, out_fd, hdr_line, level, C.byref(st)), "bwahip_stream_run_bam")
     return st
 
 

@@ -307,6 +307,9 @@ int launch_matesw_sw(const PairLaunch &a, int n_tasks, int n_tasks8, int max_len
 int launch_pair(const PairLaunch &a, int n_listed, hipStream_t st);   // subset 2: n_listed pairs of resc_list
 size_t matesw_slab_bytes(int64_t window);
 int launch_sam_pe(const FinLaunch &a, bool write, hipStream_t st, int read_lo = 0, int read_hi = -1);
+// k_bam.hip: the same two passes writing BAM records (FinLaunch::sam / sam_len / sam_off hold the records' bytes)
+int launch_bam(const FinLaunch &a, bool write, hipStream_t st, int read_lo = 0, int read_hi = -1);
+int launch_bam_pe(const FinLaunch &a, bool write, hipStream_t st, int read_lo = 0, int read_hi = -1);
 
 // K3b: mem_flt_chained_seeds on the chains k_chain / k_chain_flt left (k_seedsw.hip)
 struct SeedSwLaunch {

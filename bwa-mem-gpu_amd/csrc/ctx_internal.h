@@ -140,5 +140,6 @@ int launch_scan(const int *in, int64_t *out, int n, DevBuf &tmp, hipStream_t st)
 int launch_nt4(uint8_t *seq, int64_t n, hipStream_t st);   // runtime.hip: ASCII / codes -> codes 0..4 in place (nst_nt4_table)
 int dev_upload(DevBuf &b, const void *src, size_t bytes, hipStream_t st);
 int run_pipeline(bwahip_ctx *c, const bwahip_opt_t *opt, bool timed, bool dump);      // the hot path over the uploaded batch
-int run_final(bwahip_ctx *c, const bwahip_opt_t *opt, int64_t n_processed, const bwahip_pestat_t *pes0, bool timed);   // regions in HBM -> SAM text in HBM (SE, or PE when opt->flag has MEM_F_PE)
+int run_final(bwahip_ctx *c, const bwahip_opt_t *opt, int64_t n_processed, const bwahip_pestat_t *pes0, bool timed, bool bam = false);   // regions in HBM -> SAM text (or, bam: BAM records) in HBM (SE, or PE when opt->flag has MEM_F_PE)
+int bam_check_reads(int n, const bwahip_seq_t *seqs);   // bam_host.cpp: BWAHIP_EINVAL (with a message naming the read) for a name or a comment BAM cannot hold
 int final_setup(bwahip_ctx *c);                                                       // contig name tables for the SAM kernels

@@ -183,8 +183,13 @@ static int run_pe_rescue(bwahip_ctx *c, const bwahip_opt_t *opt, const DevOpt &d
 }
 
 // K6 -> K9 over the batch run_pipeline left in HBM.  The text inputs (d_qual, d_names, ...) must be uploaded.
-int run_final(bwahip_ctx *c, const bwahip_opt_t *opt, int64_t n_processed, const bwahip_pestat_t *pes0, bool timed)
+int run_final(bwahip_ctx *c, const bwahip_opt_t *opt, int64_t n_processed, const bwahip_pestat_t *pes0, bool timed, bool bam)
 {
+	// the two output passes in the batch's format: SAM text (k_sam.hip) or BAM records (k_bam.hip)
+	auto launch_out = [&](const FinLaunch &fl, bool write, int lo, int hi) {
+		const bool pe_ = (opt->flag & BWAHIP_F_PE) != 0;
+		return bam ? (pe_ ? launch_bam_pe(fl, write, c->stream, lo, hi) : launch_bam(fl, write, c->stream, lo, hi)) : (pe_ ? launch_sam_pe(fl, write, c->stream, lo, hi) : launch_sam(fl, write, c->stream, lo, hi));
+	};
 	const int n = c->n_reads;
 	const bool pe = (opt->flag & BWAHIP_F_PE) != 0;
 	c->total_sam = 0; c->total_tasks = 0;
@@ -291,7 +296,7 @@ int run_final(bwahip_ctx *c, const bwahip_opt_t *opt, int64_t n_processed, const
 		break;
 	}
 	if (timed) HIP_TRY(hipEventRecord(c->ev[17], c->stream));
-	if ((rc = pe ? launch_sam_pe(f, false, c->stream) : launch_sam(f, false, c->stream))) return rc;
+	if ((rc = launch_out(f, false, 0, -1))) return rc;
 	if ((rc = launch_scan(c->d_sam_len.as<int>(), c->d_sam_off.as<int64_t>(), n, c->d_scan, c->stream))) return rc;
 	if (timed) HIP_TRY(hipEventRecord(c->ev[18], c->stream));
 	int64_t total = 0;
@@ -307,9 +312,9 @@ int run_final(bwahip_ctx *c, const bwahip_opt_t *opt, int64_t n_processed, const
 	// the write pass in two halves (cut at an even read: mates stay together) with an event between them: a caller that downloads the text
 	// (bwahip_process_seqs) starts on the first half while the second is being written
 	c->sam_half_reads = (n / 2) & ~1;
-	if ((rc = pe ? launch_sam_pe(f, true, c->stream, 0, c->sam_half_reads) : launch_sam(f, true, c->stream, 0, c->sam_half_reads))) return rc;
+	if ((rc = launch_out(f, true, 0, c->sam_half_reads))) return rc;
 	HIP_TRY(hipEventRecord(c->ev_sam_half, c->stream));
-	if ((rc = pe ? launch_sam_pe(f, true, c->stream, c->sam_half_reads, n) : launch_sam(f, true, c->stream, c->sam_half_reads, n))) return rc;
+	if ((rc = launch_out(f, true, c->sam_half_reads, n))) return rc;
 	if (timed) {
 		HIP_TRY(hipEventRecord(c->ev[19], c->stream));
 		HIP_TRY(hipStreamSynchronize(c->stream));
@@ -458,7 +463,7 @@ static int stage_text(bwahip_ctx *c, int nt, int n, bwahip_seq_t *seqs, const Ba
 
 // text != nullptr: the batch's SAM stays one piece (in the context's pinned buffer) instead of being cut into per-read strings
 static int process_seqs_impl(bwahip_ctx *ctx, const bwahip_opt_t *opt, int64_t n_processed, int n, bwahip_seq_t *seqs, const bwahip_pestat_t *pes0,
-                             const char **text_out, int64_t *len_out, const int64_t **off_out)
+                             const char **text_out, int64_t *len_out, const int64_t **off_out, bool bam = false)
 {
 	if (!ctx || !opt || n < 0 || (n && !seqs)) return BWAHIP_EINVAL;
 	const bool pe = (opt->flag & BWAHIP_F_PE) != 0;
@@ -471,6 +476,7 @@ static int process_seqs_impl(bwahip_ctx *ctx, const bwahip_opt_t *opt, int64_t n
 	}
 	if (pe) for (int i = 0; i < n; i += 2) if (strcmp(seqs[i].name, seqs[i + 1].name) != 0) { fprintf(stderr, "[bwahip] paired reads have different names\n"); return BWAHIP_EINVAL; }   // err_fatal in the reference (bwamem_pair.c:386)
 	if (n == 0) return 0;
+	if (bam) { const int rc_bam = bam_check_reads(n, seqs); if (rc_bam) return rc_bam; }   // what BAM cannot hold is refused before any launch
 	HIP_TRY(hipSetDevice(ctx->device));
 	const bool verbose = ctx->knobs.verbose != 0;
 	auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
@@ -489,7 +495,7 @@ static int process_seqs_impl(bwahip_ctx *ctx, const bwahip_opt_t *opt, int64_t n
 	if (rc || (rc = rc_text)) return rc;
 	const double t2 = now();
 	ctx->want_host_sam_off = true;
-	rc = run_final(ctx, opt, n_processed, pes0, false);
+	rc = run_final(ctx, opt, n_processed, pes0, false, bam);
 	ctx->want_host_sam_off = false;
 	if (rc) return rc;
 	// SAM text back through the pinned buffer, on the context's stream (a non-blocking stream: a plain hipMemcpy would not wait
@@ -570,6 +576,15 @@ extern "C" int bwahip_process_seqs_text(bwahip_ctx *ctx, const bwahip_opt_t *opt
 {
 	if (!sam || !sam_len) return BWAHIP_EINVAL;
 	return process_seqs_impl(ctx, opt, n_processed, n, seqs, pes0, sam, sam_len, off);
+}
+
+// The same work with the batch as BAM records (k_bam.hip): *bam = the records of all reads in read order, concatenated, without header
+// and uncompressed (bwahip_bam_header / bwahip_bgzf_write make a file of them); the buffers and their lifetime as for the text.
+extern "C" int bwahip_process_seqs_bam(bwahip_ctx *ctx, const bwahip_opt_t *opt, int64_t n_processed, int n, bwahip_seq_t *seqs, const bwahip_pestat_t *pes0,
+                                       const uint8_t **bam, int64_t *bam_len, const int64_t **off)
+{
+	if (!bam || !bam_len) return BWAHIP_EINVAL;
+	return process_seqs_impl(ctx, opt, n_processed, n, seqs, pes0, (const char**)bam, bam_len, off, true);
 }
 
 // Insert-size statistics (mem_pestat_t x 4: FF, FR, RF, RR) and mate-rescue counters ([0] Smith-Waterman alignments run on

@@ -809,6 +809,33 @@ int bwahip_batch_run_sam(bwahip_ctx *c, const bwahip_opt_t *opt, int64_t n_proce
 	return rc;
 }
 
+// bwahip_batch_run_sam with BAM records as the output (k_bam.hip); kernel_ms[14], [15] are the sizing and the write pass of that format.
+// A read name of 255 bytes or more cannot be encoded: checked here from the name offsets (the names themselves are in HBM).
+int bwahip_batch_run_bam(bwahip_ctx *c, const bwahip_opt_t *opt, int64_t n_processed, const bwahip_pestat_t *pes0, float *kernel_ms, int n_ms)
+{
+	if (!c || !opt) return BWAHIP_EINVAL;
+	HIP_TRY(hipSetDevice(c->device));
+	if (c->n_reads > 0) {
+		if (!c->d_name_off.p) return BWAHIP_EINVAL;
+		std::vector<int64_t> noff((size_t)c->n_reads + 1);
+		HIP_TRY(hipMemcpyAsync(noff.data(), c->d_name_off.p, noff.size() * 8, hipMemcpyDeviceToHost, c->stream));
+		HIP_TRY(hipStreamSynchronize(c->stream));
+		for (int i = 0; i < c->n_reads; ++i)
+			if (noff[i + 1] - noff[i] > 255) { fprintf(stderr, "[bwahip] BAM: the name of read %d has %lld bytes (at most 254 fit a record)\n", i, (long long)(noff[i + 1] - noff[i] - 1)); return BWAHIP_EINVAL; }
+	}
+	int rc = run_pipeline(c, opt, true, false);
+	if (!rc) rc = run_final(c, opt, n_processed, pes0, true, true);
+	if (!rc && kernel_ms) {
+		for (int i = 0; i < n_ms && i < 11; ++i) kernel_ms[i] = c->last_ms[i];
+		if (n_ms > 11) kernel_ms[11] = c->final_ms[4];
+		for (int i = 0; i < 4 && 12 + i < n_ms; ++i) kernel_ms[12 + i] = c->final_ms[i];
+	}
+	return rc;
+}
+
+// The records of the last bwahip_batch_run_bam, as bwahip_batch_sam hands out the text (no NUL is meaningful here)
+int bwahip_batch_bam(bwahip_ctx *c, uint8_t **out, int64_t *out_len, int64_t *off) { return bwahip_batch_sam(c, (char**)out, out_len, off); }
+
 // SAM text of the last bwahip_batch_run_sam: *out = malloc()ed buffer of *out_len bytes (reads in order); off (may be NULL):
 // n + 1 offsets of the reads' texts
 int bwahip_batch_sam(bwahip_ctx *c, char **out, int64_t *out_len, int64_t *off)

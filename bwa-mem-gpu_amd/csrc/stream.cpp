@@ -44,6 +44,7 @@ struct Driver {
 	int workers_left = 0;
 	int rc = 0;                                                  // first error (workers and the writer stop on it)
 	int fd = -1;
+	int bam = 0, level = 0, deflate_threads = 1;                 // bwahip_stream_run_bam: the batches' records go through the BGZF writer
 	int64_t sam_bytes = 0;
 	double t_last_write = 0, write_s = 0;
 
@@ -63,6 +64,11 @@ struct Driver {
 			}
 			const double t0 = now_s();
 			int64_t o = 0;
+			if (bam) {
+				const int r = bwahip_bgzf_write(fd, it.p, it.len, level, deflate_threads);
+				if (r) { fail(r); return; }
+				o = it.len;
+			}
 			while (fd >= 0 && o < it.len) {
 				const ssize_t w = write(fd, it.p + o, (size_t)(it.len - o > (1ll << 30) ? (1ll << 30) : it.len - o));
 				if (w < 0) { if (errno == EINTR) continue; fprintf(stderr, "[bwahip] writing the SAM text failed: %s\n", strerror(errno)); fail(BWAHIP_EIO); return; }
@@ -89,18 +95,30 @@ Reaper g_reaper;
 
 } // namespace
 
-extern "C" int bwahip_stream_run(bwahip_ctx *const *ctxs, int n_ctx, const bwahip_opt_t *opt, const bwahip_pestat_t *pes0,
-                                 const char *fq1, const char *fq2, int out_fd, bwahip_stream_t *st)
+// bam: 0 = SAM text as it comes; 1 = BAM: header, every batch's records through the BGZF writer in input order, the EOF block
+static int stream_run(bwahip_ctx *const *ctxs, int n_ctx, const bwahip_opt_t *opt, const bwahip_pestat_t *pes0,
+                      const char *fq1, const char *fq2, int out_fd, bwahip_stream_t *st, int bam, const char *hdr_line, int level)
 {
 	if (!ctxs || n_ctx < 1 || n_ctx > 256 || !opt || !fq1 || !st) return BWAHIP_EINVAL;
 	for (int i = 0; i < n_ctx; ++i) if (!ctxs[i]) return BWAHIP_EINVAL;
+	if (bam && (level < 0 || level > 9)) return BWAHIP_EINVAL;
 	// actual_chunk_size (fastmap.c:304): -K when given, else chunk_size * n_threads
 	const int64_t chunk = st->chunk_bases > 0 ? st->chunk_bases : (int64_t)opt->chunk_size * (opt->n_threads > 0 ? opt->n_threads : 1);
 	bwahip_opt_t o = *opt;
 	if (fq2) o.flag |= BWAHIP_F_PE;
-	o.n_threads = opt->n_threads / n_ctx > 1 ? opt->n_threads / n_ctx : 1;   // opt->n_threads is the host-thread budget of the whole run
+	// opt->n_threads is the host-thread budget of the whole run; BAM: half of it deflates, the other half stages the batches
+	const int n_deflate = bam ? (opt->n_threads / 2 > 1 ? opt->n_threads / 2 : 1) : 0;
+	const int n_stage = bam && opt->n_threads > n_deflate ? opt->n_threads - n_deflate : opt->n_threads;
+	o.n_threads = n_stage / n_ctx > 1 ? n_stage / n_ctx : 1;
 	Driver d;
 	d.fd = out_fd; d.max_reads = st->max_reads;
+	d.bam = bam; d.level = level; d.deflate_threads = n_deflate;
+	if (bam) {
+		uint8_t *hdr = nullptr; int64_t hlen = 0;
+		int hr = bwahip_bam_header(bwahip_bns(ctxs[0]), hdr_line, &hdr, &hlen);
+		if (!hr) { hr = bwahip_bgzf_write(out_fd, hdr, hlen, level, 1); free(hdr); }
+		if (hr) return hr;
+	}
 	const double t_call = now_s();
 	int rc = bwahip_fastq_open_mt(fq1, fq2, st->reader_threads, &d.rd);
 	if (rc) return rc;
@@ -163,7 +181,8 @@ extern "C" int bwahip_stream_run(bwahip_ctx *const *ctxs, int n_ctx, const bwahi
 			if (stop) { bwahip_fastq_batch_release(b); continue; }   // (drain what the fetcher still delivers; it stops at the failure flag)
 			const double t1 = now_s();
 			const char *sam = nullptr; int64_t len = 0;
-			const int r = bwahip_process_seqs_text(ctxs[w], &o, np0, n, seqs, pes0, &sam, &len, nullptr);
+			const int r = bam ? bwahip_process_seqs_bam(ctxs[w], &o, np0, n, seqs, pes0, (const uint8_t**)&sam, &len, nullptr)
+			                  : bwahip_process_seqs_text(ctxs[w], &o, np0, n, seqs, pes0, &sam, &len, nullptr);
 			bwahip_fastq_batch_release(b);                          // names, bases and qualities were staged inside the call
 			busy_s[w] += now_s() - t1;
 			if (r) { d.fail(r); continue; }
@@ -181,6 +200,7 @@ extern "C" int bwahip_stream_run(bwahip_ctx *const *ctxs, int n_ctx, const bwahi
 	for (int w = 0; w < n_ctx; ++w) th.emplace_back(worker, w);
 	for (auto &t : th) t.join();
 	wr.join();
+	if (bam && !d.rc) { const int r = bwahip_bgzf_eof(out_fd); if (r) d.rc = r; d.t_last_write = now_s(); }
 	const double t_joined = now_s();
 	g_reaper.close_later(d.rd);
 	if (getenv("BWAHIP_STREAM_LOG"))
@@ -190,4 +210,17 @@ extern "C" int bwahip_stream_run(bwahip_ctx *const *ctxs, int n_ctx, const bwahi
 	st->seconds = d.t_last_write - t_start; st->write_s = d.write_s;
 	for (int w = 0; w < n_ctx; ++w) { st->reader_wait_s += wait_s[w]; st->gpu_busy_s += busy_s[w]; }
 	return d.rc;
+}
+
+extern "C" int bwahip_stream_run(bwahip_ctx *const *ctxs, int n_ctx, const bwahip_opt_t *opt, const bwahip_pestat_t *pes0,
+                                 const char *fq1, const char *fq2, int out_fd, bwahip_stream_t *st)
+{
+	return stream_run(ctxs, n_ctx, opt, pes0, fq1, fq2, out_fd, st, 0, nullptr, 0);
+}
+
+// FASTQ files in -> a BAM file out: bwahip_stream_run with bwahip_process_seqs_bam in the workers and the BGZF writer behind them
+extern "C" int bwahip_stream_run_bam(bwahip_ctx *const *ctxs, int n_ctx, const bwahip_opt_t *opt, const bwahip_pestat_t *pes0,
+                                     const char *fq1, const char *fq2, int out_fd, const char *hdr_line, int level, bwahip_stream_t *st)
+{
+	return stream_run(ctxs, n_ctx, opt, pes0, fq1, fq2, out_fd, st, 1, hdr_line, level);
 }

@@ -243,6 +243,27 @@ int bwahip_process_seqs(bwahip_ctx *ctx, const bwahip_opt_t *opt, int64_t n_proc
 int  bwahip_process_seqs_text(bwahip_ctx *ctx, const bwahip_opt_t *opt, int64_t n_processed, int n, bwahip_seq_t *seqs,
                               const bwahip_pestat_t *pes0, const char **sam, int64_t *sam_len, const int64_t **off);
 
+/* The same work with the batch as BAM records (SAM specification 4.2) encoded on the GPU: *bam = the records of all reads in read
+ * order, concatenated -- no header, no compression (bwahip_bam_header and bwahip_bgzf_write make a file of them); *off: n + 1
+ * offsets, read i's records are bam[off[i]..off[i+1]).  Buffers and lifetimes as for bwahip_process_seqs_text.  A record says what
+ * the SAM line says: the same flags, positions, CIGAR (BAM's operation codes), tags in the same order; NM / AS / XS as the smallest
+ * integer type that holds the value, pa as the single nearest to the printed "%.3f", the others as Z.  What a record cannot hold
+ * is refused with BWAHIP_EINVAL (and a message naming the read) before anything is launched: a read name of 255 bytes or more,
+ * and a comment (-C) whose tab-separated fields are not all XX:Z:<printable>, XX:A:<char> or XX:i:<integer in [-2^31, 2^32)>. */
+int  bwahip_process_seqs_bam(bwahip_ctx *ctx, const bwahip_opt_t *opt, int64_t n_processed, int n, bwahip_seq_t *seqs,
+                             const bwahip_pestat_t *pes0, const uint8_t **bam, int64_t *bam_len, const int64_t **off);
+
+/* ---- BAM file pieces that need no device -----------------------------------------------------------------------------------
+ * bwahip_bam_header: magic, l_text + text, n_ref, names and lengths in a malloc()ed buffer (free() it).  The text is what
+ * bwa_print_sam_hdr (bwa.c:520) writes for bns and hdr_line: one @SQ line per contig (AH:* for ALT contigs) unless hdr_line
+ * (may be NULL) brings @SQ lines of its own, then hdr_line and a newline.  A @PG line is the caller's to put into hdr_line.
+ * bwahip_bgzf_write: data as BGZF blocks (at most 65 280 input bytes each) on fd (< 0: produced and dropped), deflated by
+ * n_threads workers and written in order -- the bytes do not depend on n_threads.  level 0: stored, 1..9: zlib's levels.
+ * bwahip_bgzf_eof: the 28-byte end-of-file block.  A BAM file = bgzf(header) bgzf(records)... eof. */
+int  bwahip_bam_header(const bwahip_bns_t *bns, const char *hdr_line, uint8_t **out, int64_t *len);
+int  bwahip_bgzf_write(int fd, const void *data, int64_t len, int level, int n_threads);
+int  bwahip_bgzf_eof(int fd);
+
 /* ---- the batch driver: FASTQ files in -> SAM text out -------------------------------------------------------------------
  * What superBatchMain(ktp_aux_t*) (cuda/superbatch_process.h:35, superbatch_process.cpp:133: read || process, double buffered,
  * one GPU) and process()/kt_pipeline (fastmap.c:46,307: bseq_read -> mem_process_seqs -> fputs) are in the reference, for any
@@ -265,6 +286,13 @@ typedef struct {
 } bwahip_stream_t;
 int bwahip_stream_run(bwahip_ctx *const *ctxs, int n_ctx, const bwahip_opt_t *opt, const bwahip_pestat_t *pes0,
                       const char *fq1, const char *fq2, int out_fd, bwahip_stream_t *st);
+
+/* bwahip_stream_run with a BAM file as the output: the header (bwahip_bam_header of the contexts' index and hdr_line) first, every
+ * batch's records (bwahip_process_seqs_bam) through the BGZF writer in input order, the end-of-file block last; out_fd < 0:
+ * produced, deflated and dropped.  st as above, with sam_bytes = the uncompressed bytes of the records (header excluded) and
+ * write_s = deflate + write().  Of opt->n_threads, half deflate and the other half stage the batches. */
+int bwahip_stream_run_bam(bwahip_ctx *const *ctxs, int n_ctx, const bwahip_opt_t *opt, const bwahip_pestat_t *pes0,
+                          const char *fq1, const char *fq2, int out_fd, const char *hdr_line, int level, bwahip_stream_t *st);
 
 /* Insert-size statistics (mem_pestat_t[4]: FF, FR, RF, RR; bwamem_pair.c:72) and mate-rescue counters ([0] local alignments
  * run, [1] regions added, [2] most alignments of one pair, [3] pairs that needed any; bwamem_pair.c:137) of the last
@@ -304,6 +332,10 @@ int bwahip_batch_download(bwahip_ctx *ctx, bwahip_alnreg_v *regs_out);       /* 
 int bwahip_batch_attach_text(bwahip_ctx *ctx, const uint8_t *qual_dev, const int64_t *qual_off_dev, const uint8_t *names_dev, const int64_t *name_off_dev);
 int bwahip_batch_run_sam(bwahip_ctx *ctx, const bwahip_opt_t *opt, int64_t n_processed, const bwahip_pestat_t *pes0, float *kernel_ms, int n_kernel_ms);
 int bwahip_batch_sam(bwahip_ctx *ctx, char **out, int64_t *out_len, int64_t *off);
+/* The same pair with BAM records as the output (see bwahip_process_seqs_bam; a batch is finalised for one format: run again for the
+ * other).  kernel_ms slots as for the SAM passes.  Names of 255 bytes or more: BWAHIP_EINVAL, judged by the name offsets. */
+int bwahip_batch_run_bam(bwahip_ctx *ctx, const bwahip_opt_t *opt, int64_t n_processed, const bwahip_pestat_t *pes0, float *kernel_ms, int n_kernel_ms);
+int bwahip_batch_bam(bwahip_ctx *ctx, uint8_t **out, int64_t *out_len, int64_t *off);
 int bwahip_n_kernels(void);
 const char *bwahip_kernel_name(int i);
 /* Algorithmic work counters of the last bwahip_batch_run, counted on the device by the kernels
