@@ -2,7 +2,12 @@
 // runtime.hip (hot path sequencing, C ABI) and final_rt.hip (finalisation / SAM sequencing).
 #pragma once
 #include "bwahip_internal.h"
+#include <atomic>
 #include <string>
+
+// hipFree / hipMalloc / hipHostMalloc inside a buffer's ensure() synchronise the whole device: counted, so that the stream driver can
+// report how many a pass paid (BWAHIP_STREAM_LOG; a steady pass of equal batches pays none)
+inline std::atomic<long> g_bwahip_reallocs{0};
 
 // ------------------------------------------------------------------ small device helpers
 struct DevBuf {
@@ -13,6 +18,7 @@ struct DevBuf {
 		if (bytes <= cap && !ext) return 0;
 		if (p && !ext) (void)hipFree(p);
 		p = nullptr; cap = 0; ext = false;
+		++g_bwahip_reallocs;
 		size_t want = bytes + bytes / 8 + 256;
 		if (hipMalloc(&p, want) != hipSuccess) { fprintf(stderr, "[bwahip] hipMalloc(%zu) failed\n", want); return BWAHIP_ENOMEM; }
 		cap = want;
@@ -31,6 +37,7 @@ struct HostBuf {
 		if (bytes <= cap) return 0;
 		if (p) (void)hipHostFree(p);
 		p = nullptr; cap = 0;
+		++g_bwahip_reallocs;
 		const size_t want = bytes + bytes / 8 + 4096;
 		if (hipHostMalloc(&p, want, hipHostMallocDefault) != hipSuccess) { fprintf(stderr, "[bwahip] hipHostMalloc(%zu) failed\n", want); p = nullptr; return BWAHIP_ENOMEM; }
 		cap = want;
@@ -77,7 +84,10 @@ struct BatchText {
 	size_t sz_codes = 0, sz_qual = 0, sz_names = 0, sz_comm = 0;
 };
 
+struct StreamPipe;                       // final_rt.hip: the second sets of batch buffers the stream driver's three stages work on
+
 struct bwahip_ctx {
+	StreamPipe *pipe = nullptr;          // made by the first bwahip_stream_run on this context, kept (buffers do not shrink), freed with the context
 	BatchText batch_text;
 	bool want_host_sam_off = false;      // run_final copies the SAM offsets to h_sam_off ahead of the write pass (bwahip_process_seqs)
 	std::vector<int64_t> h_sam_off;      // offsets of the reads' SAM text in h_sam (bwahip_process_seqs / _text)
@@ -142,4 +152,5 @@ int dev_upload(DevBuf &b, const void *src, size_t bytes, hipStream_t st);
 int run_pipeline(bwahip_ctx *c, const bwahip_opt_t *opt, bool timed, bool dump);      // the hot path over the uploaded batch
 int run_final(bwahip_ctx *c, const bwahip_opt_t *opt, int64_t n_processed, const bwahip_pestat_t *pes0, bool timed, bool bam = false);   // regions in HBM -> SAM text (or, bam: BAM records) in HBM (SE, or PE when opt->flag has MEM_F_PE)
 int bam_check_reads(int n, const bwahip_seq_t *seqs);   // bam_host.cpp: BWAHIP_EINVAL (with a message naming the read) for a name or a comment BAM cannot hold
+void pipe_destroy(bwahip_ctx *c);                                                     // final_rt.hip: the stream driver's buffer sets
 int final_setup(bwahip_ctx *c);                                                       // contig name tables for the SAM kernels

@@ -604,3 +604,252 @@ extern "C" int bwahip_last_pe_stats(bwahip_ctx *ctx, bwahip_pestat_t *pes4, uint
 	}
 	return 0;
 }
+
+// ------------------------------------------------------------------ the stream driver's stages (stream_pipe.h)
+#include "stream_pipe.h"
+#include <condition_variable>
+#include <functional>
+#include <mutex>
+
+namespace {
+
+double pipe_now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+
+// the staging threads of one context: run(f) calls f(0 .. n-1), f(0) on the calling thread, and returns when all are back
+struct StagePool {
+	std::vector<std::thread> th;
+	std::mutex mu; std::condition_variable cv, cv_done;
+	const std::function<void(int)> *job = nullptr;
+	long gen = 0; int left = 0; bool quit = false;
+	int size() const { return (int)th.size() + 1; }
+	void start(int n)
+	{
+		for (int t = 1; t < n; ++t) th.emplace_back([this, t] {
+			long seen = 0;
+			for (;;) {
+				const std::function<void(int)> *f;
+				{ std::unique_lock<std::mutex> lk(mu); cv.wait(lk, [&] { return quit || gen != seen; }); if (quit) return; seen = gen; f = job; }
+				(*f)(t);
+				{ std::lock_guard<std::mutex> lk(mu); if (--left == 0) cv_done.notify_all(); }
+			}
+		});
+	}
+	void run(const std::function<void(int)> &f)
+	{
+		if (th.empty()) { f(0); return; }
+		{ std::lock_guard<std::mutex> lk(mu); job = &f; left = (int)th.size(); ++gen; }
+		cv.notify_all();
+		f(0);
+		std::unique_lock<std::mutex> lk(mu);
+		cv_done.wait(lk, [&] { return left == 0; });
+	}
+	void stop()
+	{
+		{ std::lock_guard<std::mutex> lk(mu); quit = true; }
+		cv.notify_all();
+		for (auto &t : th) t.join();
+		th.clear(); quit = false; gen = 0;
+	}
+};
+
+struct PipeIn {
+	DevBuf d_seq, d_off, d_qual, d_qual_off, d_names, d_name_off, d_comments, d_comment_off;
+	HostBuf h_stage;                     // pinned: the four offset tables, then codes | qualities | names | comments
+	hipEvent_t ev = nullptr;             // the copies to HBM are done
+	int n = 0, max_len = 0; int64_t total_bases = 0; bool any_comment = false;
+};
+struct PipeOut {
+	DevBuf d_sam, d_sam_off;
+	HostBuf h_sam;
+	hipEvent_t ev_written = nullptr, ev_copied = nullptr;   // the write pass has ended / the bytes are in h_sam
+	int64_t total = 0;
+};
+
+} // namespace
+
+struct StreamPipe {
+	PipeIn in[PIPE_SETS];
+	PipeOut out[PIPE_SETS];
+	StagePool pool;
+};
+
+long pipe_realloc_count() { return g_bwahip_reallocs.load(); }
+
+int pipe_open(bwahip_ctx *c, int n_threads)
+{
+	if (!c) return BWAHIP_EINVAL;
+	HIP_TRY(hipSetDevice(c->device));
+	if (!c->pipe) {
+		c->pipe = new StreamPipe;
+		for (auto &s : c->pipe->in) HIP_TRY(hipEventCreateWithFlags(&s.ev, hipEventDisableTiming));
+		for (auto &s : c->pipe->out) { HIP_TRY(hipEventCreateWithFlags(&s.ev_written, hipEventDisableTiming)); HIP_TRY(hipEventCreateWithFlags(&s.ev_copied, hipEventDisableTiming)); }
+	}
+	c->pipe->pool.start(n_threads > 1 ? n_threads : 1);
+	return 0;
+}
+
+void pipe_close(bwahip_ctx *c)
+{
+	if (!c || !c->pipe) return;
+	(void)hipSetDevice(c->device);
+	for (hipStream_t s : { c->stream_copy, c->stream2, c->stream3, c->stream }) if (s) (void)hipStreamSynchronize(s);
+	c->pipe->pool.stop();
+}
+
+void pipe_destroy(bwahip_ctx *c)
+{
+	if (!c->pipe) return;
+	for (auto &s : c->pipe->in) {
+		for (DevBuf *b : { &s.d_seq, &s.d_off, &s.d_qual, &s.d_qual_off, &s.d_names, &s.d_name_off, &s.d_comments, &s.d_comment_off }) b->release();
+		s.h_stage.release();
+		if (s.ev) (void)hipEventDestroy(s.ev);
+	}
+	for (auto &s : c->pipe->out) {
+		s.d_sam.release(); s.d_sam_off.release(); s.h_sam.release();
+		if (s.ev_written) (void)hipEventDestroy(s.ev_written);
+		if (s.ev_copied) (void)hipEventDestroy(s.ev_copied);
+	}
+	delete c->pipe;
+	c->pipe = nullptr;
+}
+
+// What stage_codes + stage_text do for bwahip_process_seqs, in two passes of the context's staging threads and without writing to the
+// reader's records: pass 1 the per-chunk totals (two strlen per read), the longest read and the checks; pass 2 the offsets and the gather
+// of bases, qualities, names and comments, all into one pinned buffer.  The bases travel as ASCII and become codes in HBM (k_nt4_conv).
+int pipe_stage_in(bwahip_ctx *c, int in, const bwahip_opt_t *opt, int n, const bwahip_seq_t *seqs, int bam, double *t_copy_begin)
+{
+	if (!c || !c->pipe || in < 0 || in >= PIPE_SETS || !opt || n <= 0 || !seqs) return BWAHIP_EINVAL;
+	const bool pe = (opt->flag & BWAHIP_F_PE) != 0;
+	if (pe && (n & 1)) return BWAHIP_EINVAL;
+	if (!c->knobs.gpu_final || (pe && !c->knobs.gpu_pair)) return BWAHIP_EINVAL;   // the one-piece output exists on the GPU path only
+	if (bam) { const int rc_bam = bam_check_reads(n, seqs); if (rc_bam) return rc_bam; }
+	HIP_TRY(hipSetDevice(c->device));
+	PipeIn &s = c->pipe->in[in];
+	StagePool &pool = c->pipe->pool;
+	const int C = n >= 4096 ? pool.size() : 1;
+	struct Tot { int64_t seq = 0, qual = 0, name = 0, comm = 0; int bad = 0, any_comm = 0, max_len = 0, long_read = -1, name_diff = 0; char pad[12]; };
+	std::vector<Tot> tot(C + 1);
+	auto chunk = [&](int k) { return ((int64_t)n * k / C) & ~(int64_t)1; };   // even: mates stay in one chunk
+	auto chunk_end = [&](int k) { return k + 1 == C ? (int64_t)n : chunk(k + 1); };
+	pool.run([&](int k) {
+		if (k >= C) return;
+		Tot x;
+		for (int64_t i = chunk(k); i < chunk_end(k); ++i) {
+			if (seqs[i].l_seq < 0 || !seqs[i].name || !seqs[i].seq) { x.bad = 1; continue; }
+			const int64_t ln = (int64_t)strlen(seqs[i].name) + 1, lc = seqs[i].comment ? (int64_t)strlen(seqs[i].comment) : 0;
+			if (seqs[i].l_seq > BWAHIP_MAX_READ_LEN && x.long_read < 0) x.long_read = (int)i;
+			if (seqs[i].l_seq > x.max_len) x.max_len = seqs[i].l_seq;
+			if (pe && (i & 1) && seqs[i - 1].name && strcmp(seqs[i - 1].name, seqs[i].name) != 0) x.name_diff = 1;
+			x.seq += seqs[i].l_seq; x.qual += seqs[i].qual ? seqs[i].l_seq : 0; x.name += ln; x.comm += lc ? lc + 1 : 0; x.any_comm |= lc > 0;
+		}
+		tot[k + 1] = x;
+	});
+	s.any_comment = false; s.max_len = 0;
+	for (int k = 1; k <= C; ++k) {
+		if (tot[k].bad) return BWAHIP_EINVAL;
+		if (tot[k].name_diff) { fprintf(stderr, "[bwahip] paired reads have different names\n"); return BWAHIP_EINVAL; }   // err_fatal in the reference (bwamem_pair.c:386)
+		if (tot[k].long_read >= 0) { fprintf(stderr, "[bwahip] read %d is %d bases long (limit %d)\n", tot[k].long_read, seqs[tot[k].long_read].l_seq, BWAHIP_MAX_READ_LEN); return BWAHIP_ECAPACITY; }
+		s.any_comment |= tot[k].any_comm != 0;
+		if (tot[k].max_len > s.max_len) s.max_len = tot[k].max_len;
+		tot[k].seq += tot[k - 1].seq; tot[k].qual += tot[k - 1].qual; tot[k].name += tot[k - 1].name; tot[k].comm += tot[k - 1].comm;
+	}
+	const int64_t n_codes = tot[C].seq, n_qual = tot[C].qual, n_names = tot[C].name, n_comm = tot[C].comm;
+	const size_t sz_off = (((size_t)n + 1) * 8 + 63) & ~(size_t)63;
+	const size_t sz_codes = ((size_t)n_codes + 64) & ~(size_t)63, sz_qual = ((size_t)n_qual + 127) & ~(size_t)63, sz_names = ((size_t)n_names + 127) & ~(size_t)63;
+	const size_t sz_comm = s.any_comment ? ((size_t)n_comm + 127) & ~(size_t)63 : 0;
+	// the set is this stage's alone: its buffers grow here, before anything is queued on them
+	int rc;
+	if ((rc = s.h_stage.ensure(4 * sz_off + sz_codes + sz_qual + sz_names + sz_comm))) return rc;
+	if ((rc = s.d_seq.ensure(sz_codes)) || (rc = s.d_off.ensure(sz_off)) || (rc = s.d_qual.ensure(sz_qual)) || (rc = s.d_qual_off.ensure(sz_off + 16)) || (rc = s.d_names.ensure(sz_names)) ||
+	    (rc = s.d_name_off.ensure(sz_off)) || (rc = s.d_comment_off.ensure(sz_off)) || (s.any_comment && (rc = s.d_comments.ensure(sz_comm)))) return rc;
+	int64_t *off = (int64_t*)s.h_stage.p, *qoff = off + sz_off / 8, *noff = qoff + sz_off / 8, *coff = noff + sz_off / 8;
+	uint8_t *codes = (uint8_t*)(coff + sz_off / 8), *qual = codes + sz_codes, *names = qual + sz_qual, *comments = names + sz_names;
+	off[0] = noff[0] = coff[0] = 0;
+	pool.run([&](int k) {
+		if (k >= C) return;
+		int64_t so = tot[k].seq, qo = tot[k].qual, no = tot[k].name, co = tot[k].comm;
+		for (int64_t i = chunk(k); i < chunk_end(k); ++i) {
+			const int l = seqs[i].l_seq;
+			memcpy(codes + so, seqs[i].seq, (size_t)l);
+			so += l; off[i + 1] = so;
+			if (seqs[i].qual) { memcpy(qual + qo, seqs[i].qual, (size_t)l); qoff[i] = qo; qo += l; } else qoff[i] = -1;
+			const int64_t ln = (int64_t)strlen(seqs[i].name) + 1, lc = seqs[i].comment ? (int64_t)strlen(seqs[i].comment) : 0;
+			memcpy(names + no, seqs[i].name, (size_t)ln);
+			no += ln; noff[i + 1] = no;
+			if (lc) { memcpy(comments + co, seqs[i].comment, (size_t)lc + 1); co += lc + 1; }
+			coff[i + 1] = co;
+		}
+	});
+	memset(codes + n_codes, 0, sz_codes - (size_t)n_codes); memset(qual + n_qual, 0, sz_qual - (size_t)n_qual); memset(names + n_names, 0, sz_names - (size_t)n_names);
+	if (s.any_comment) memset(comments + n_comm, 0, sz_comm - (size_t)n_comm);
+	s.n = n; s.total_bases = n_codes;
+	if (t_copy_begin) *t_copy_begin = pipe_now();
+	hipStream_t st = c->stream_copy;
+	HIP_TRY(hipMemcpyAsync(s.d_seq.p, codes, (size_t)n_codes ? (size_t)n_codes : 1, hipMemcpyHostToDevice, st));
+	HIP_TRY(hipMemcpyAsync(s.d_off.p, off, (size_t)(n + 1) * 8, hipMemcpyHostToDevice, st));
+	HIP_TRY(hipMemcpyAsync(s.d_qual.p, qual, sz_qual, hipMemcpyHostToDevice, st));
+	HIP_TRY(hipMemcpyAsync(s.d_qual_off.p, qoff, (size_t)n * 8, hipMemcpyHostToDevice, st));
+	HIP_TRY(hipMemcpyAsync(s.d_names.p, names, sz_names, hipMemcpyHostToDevice, st));
+	HIP_TRY(hipMemcpyAsync(s.d_name_off.p, noff, (size_t)(n + 1) * 8, hipMemcpyHostToDevice, st));
+	HIP_TRY(hipMemcpyAsync(s.d_comment_off.p, coff, (size_t)(n + 1) * 8, hipMemcpyHostToDevice, st));
+	if (s.any_comment) HIP_TRY(hipMemcpyAsync(s.d_comments.p, comments, sz_comm, hipMemcpyHostToDevice, st));
+	HIP_TRY(hipEventRecord(s.ev, st));
+	HIP_TRY(hipEventSynchronize(s.ev));
+	return 0;
+}
+
+int pipe_compute(bwahip_ctx *c, int in, int out, const bwahip_opt_t *opt, int64_t n_processed, const bwahip_pestat_t *pes0, int bam, double *t_hot_end)
+{
+	if (!c || !c->pipe || in < 0 || in >= PIPE_SETS || out < 0 || out >= PIPE_SETS || !opt) return BWAHIP_EINVAL;
+	HIP_TRY(hipSetDevice(c->device));
+	PipeIn &s = c->pipe->in[in];
+	PipeOut &o = c->pipe->out[out];
+	// run_pipeline and run_final work on the context's own members: the two sets take their place for this batch, and go back whatever happens
+	DevBuf no_comments;
+	auto exchange = [&] {
+		std::swap(c->d_seq, s.d_seq); std::swap(c->d_off, s.d_off); std::swap(c->d_qual, s.d_qual); std::swap(c->d_qual_off, s.d_qual_off);
+		std::swap(c->d_names, s.d_names); std::swap(c->d_name_off, s.d_name_off); std::swap(c->d_comment_off, s.d_comment_off);
+		std::swap(c->d_comments, s.any_comment ? s.d_comments : no_comments);   // a batch without comments: a null pointer tells the kernels
+		std::swap(c->d_sam, o.d_sam); std::swap(c->d_sam_off, o.d_sam_off);
+		std::swap(c->n_reads, s.n); std::swap(c->max_len, s.max_len); std::swap(c->total_bases, s.total_bases);
+	};
+	exchange();
+	int rc = 0;
+	auto body = [&]() -> int {
+		HIP_TRY(hipStreamWaitEvent(c->stream, s.ev, 0));
+		if ((rc = launch_nt4(c->d_seq.as<uint8_t>(), c->total_bases, c->stream))) return rc;
+		if ((rc = run_pipeline(c, opt, false, false))) return rc;
+		if (t_hot_end) *t_hot_end = pipe_now();
+		c->want_host_sam_off = false;
+		if ((rc = run_final(c, opt, n_processed, pes0, false, bam != 0))) return rc;
+		HIP_TRY(hipEventRecord(o.ev_written, c->stream));
+		o.total = c->total_sam;
+		return 0;
+	};
+	rc = body();
+	exchange();
+	return rc;
+}
+
+int pipe_stage_out(bwahip_ctx *c, int out, const char **text, int64_t *len, double *t_kernels_end)
+{
+	if (!c || !c->pipe || out < 0 || out >= PIPE_SETS || !text || !len) return BWAHIP_EINVAL;
+	HIP_TRY(hipSetDevice(c->device));
+	PipeOut &o = c->pipe->out[out];
+	// waiting on the host, not in the copy stream: the next batch's upload is queued there and must not stand behind this batch's kernels
+	HIP_TRY(hipEventSynchronize(o.ev_written));
+	if (t_kernels_end) *t_kernels_end = pipe_now();
+	int rc = o.h_sam.ensure((size_t)o.total + 1);
+	if (rc) return rc;
+	char *p = (char*)o.h_sam.p;
+	// in slices, each awaited before the next is queued: an upload the stager queues meanwhile waits for one slice at the most
+	constexpr int64_t SLICE = 64 << 20;
+	for (int64_t b = 0; b < o.total; b += SLICE) {
+		HIP_TRY(hipMemcpyAsync(p + b, (const char*)o.d_sam.p + b, (size_t)std::min(SLICE, o.total - b), hipMemcpyDeviceToHost, c->stream_copy));
+		HIP_TRY(hipEventRecord(o.ev_copied, c->stream_copy));
+		HIP_TRY(hipEventSynchronize(o.ev_copied));
+	}
+	p[o.total] = 0;
+	*text = p; *len = o.total;
+	return 0;
+}

@@ -3,24 +3,34 @@
 // (read -> mem_process_seqs -> fputs, fastmap.c:46,307) do in the reference, for N GPUs and several batches in flight per GPU:
 //
 //   one reader      bwahip_fastq_* (its own parse / inflate threads) cuts batches exactly as bseq_read does (-K bases);
-//   N workers       one host thread per context (contexts on N devices, or clones sharing one device's index).  A worker takes the
-//                   next batch under the reader's lock -- which also fixes the batch's number and its true n_processed (the global
-//                   index of its first read: hash_64 tie-breaks, bwamem.c:534/1204, and the per-batch mem_pestat then come out as in
-//                   a serial run) -- and runs bwahip_process_seqs_text on its context;
-//   one writer      writes the batches' SAM in batch order to the caller's file descriptor while the workers go on (the text of a
-//                   context stays valid until its next-but-one call: bwahip_process_seqs_text alternates between two pinned buffers).
+//   N contexts      (on N devices, or clones sharing one device's index), each a software pipeline of three threads working on
+//                   three different batches (stream_pipe.h):
+//                     stager   takes the next batch under the reader's lock -- which also fixes the batch's number and its true
+//                              n_processed (the global index of its first read: hash_64 tie-breaks, bwamem.c:534/1204, and the
+//                              per-batch mem_pestat then come out as in a serial run) -- gathers it into a pinned buffer and copies
+//                              it to HBM (batch k+1);
+//                     compute  queues k_nt4_conv, the hot path and the finalisation (batch k);
+//                     drainer  copies the SAM text back and hands it to the writer (batch k-1);
+//   one writer      writes the batches' SAM in batch order to the caller's file descriptor, and gives every buffer back to the
+//                   context it came from once its bytes are on the descriptor.
 //
-// Whole batches are dealt to whichever context is free (on equal devices that is round-robin); results do not depend on which
-// context took a batch (tests/test_gpu_multi.py).  No data-path collective: SURVEY.md 8(e).
+// A context has two sets of input buffers and two of output buffers; a set is reused only when its consumer has said it is done with
+// it (Pipe::in_free / out_free below).  A stager asks for a batch when it has a free input set, so batches go to whichever context
+// frees first and staging runs ahead of a context that still computes; results do not depend on which context took a batch
+// (tests/test_gpu_multi.py).  No data-path collective: SURVEY.md 8(e).
 #include "../../include/bwahip.h"
+#include "stream_pipe.h"
 #include <errno.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 #include <unistd.h>
 #include <chrono>
+#include <atomic>
 #include <condition_variable>
+#include <deque>
 #include <map>
+#include <functional>
 #include <mutex>
 #include <thread>
 #include <vector>
@@ -38,18 +48,21 @@ struct Driver {
 	// writer side
 	std::mutex mu;
 	std::condition_variable cv_item, cv_done;
-	struct Item { const char *p; int64_t len; };
+	struct Item { const char *p; int64_t len; int ctx, out; };   // ctx / out: the output set the bytes sit in
 	std::map<int64_t, Item> ready;                               // finished batches waiting for their turn
 	int64_t written = 0;                                         // batches [0, written) are on the descriptor
 	int workers_left = 0;
-	int rc = 0;                                                  // first error (workers and the writer stop on it)
+	int rc = 0;                                                  // first error (the stages and the writer stop on it)
+	std::atomic<bool> stop{false};                               // rc != 0, readable without the lock
+	std::function<void()> wake_all;                              // wakes every context's threads (failure)
+	std::function<void(const Item&, int64_t, double, double)> on_written;   // gives the output set back to its context
 	int fd = -1;
 	int bam = 0, level = 0, deflate_threads = 1;                 // bwahip_stream_run_bam: the batches' records go through the BGZF writer
 	int64_t sam_bytes = 0;
 	double t_last_write = 0, write_s = 0;
 
-	void fail(int code) { { std::lock_guard<std::mutex> lk(mu); if (!rc) rc = code; } cv_item.notify_all(); cv_done.notify_all(); }
-	bool failed() { std::lock_guard<std::mutex> lk(mu); return rc != 0; }
+	void fail(int code) { { std::lock_guard<std::mutex> lk(mu); if (!rc) rc = code; stop = true; } cv_item.notify_all(); cv_done.notify_all(); if (wake_all) wake_all(); }
+	bool failed() { return stop.load(); }
 
 	void writer()
 	{
@@ -74,11 +87,13 @@ struct Driver {
 				if (w < 0) { if (errno == EINTR) continue; fprintf(stderr, "[bwahip] writing the SAM text failed: %s\n", strerror(errno)); fail(BWAHIP_EIO); return; }
 				o += w;
 			}
+			int64_t seq_no;
 			{
 				std::lock_guard<std::mutex> lk(mu);
-				++written; sam_bytes += it.len; t_last_write = now_s(); write_s += t_last_write - t0;
+				seq_no = written++; sam_bytes += it.len; t_last_write = now_s(); write_s += t_last_write - t0;
 			}
 			cv_done.notify_all();
+			on_written(it, seq_no, t0, t_last_write);
 		}
 	}
 };
@@ -126,88 +141,147 @@ static int stream_run(bwahip_ctx *const *ctxs, int n_ctx, const bwahip_opt_t *op
 	const double t_start = now_s();
 	d.workers_left = n_ctx;
 	d.t_last_write = t_start;
-	std::vector<double> wait_s(n_ctx, 0.), busy_s(n_ctx, 0.);
 	const int keep_comments = st->keep_comments;
-	// Every context has a runner (bwahip_process_seqs_text, batch after batch) and a fetcher that takes the runner's NEXT batch from the
-	// reader meanwhile -- linking a million records into a bseq1_t array, and waiting for the parser, are host work that would otherwise
-	// sit between two batches of the context.
-	struct Slot {
+	const bool log = getenv("BWAHIP_STREAM_LOG") != nullptr;
+	const long reallocs0 = pipe_realloc_count();
+	// One batch on its way through a context, and the context's hand-over state.  The sets are numbered; who holds which is written down
+	// here and nowhere inferred.
+	struct Job { int n = 0; int64_t seq_no = 0, np0 = 0; int in = -1, out = -1; double t_final = 0; };
+	struct Pipe {
 		std::mutex mu; std::condition_variable cv;
-		bool full = false, eof = false;
-		bwahip_fastq_batch *b = nullptr; bwahip_seq_t *seqs = nullptr; int n = 0; int64_t seq_no = 0, np0 = 0;
+		bool in_free[PIPE_SETS], out_free[PIPE_SETS];
+		std::deque<Job> staged, computed;                          // stager -> compute -> drainer
+		bool staged_end = false, computed_end = false;
+		double wait_s = 0, busy_s = 0;
+		Pipe() { for (int i = 0; i < PIPE_SETS; ++i) in_free[i] = out_free[i] = true; }
 	};
-	std::vector<Slot> slots(n_ctx);
-	auto fetcher = [&](int w) {
-		Slot &sl = slots[w];
+	std::vector<Pipe> pipes(n_ctx);
+	// the timeline (BWAHIP_STREAM_LOG): begin and end of every stage of every batch, printed when the pass is over (scripts/stream_timeline.py)
+	struct Span { const char *stage; int64_t batch; int ctx; double t0, t1; };
+	std::mutex mu_log; std::vector<Span> spans;
+	auto span = [&](const char *stage, int64_t batch, int ctx, double t0, double t1) { if (log) { std::lock_guard<std::mutex> lk(mu_log); spans.push_back({ stage, batch, ctx, t0, t1 }); } };
+	d.wake_all = [&] { for (auto &p : pipes) { { std::lock_guard<std::mutex> lk(p.mu); } p.cv.notify_all(); } };
+	d.on_written = [&](const Driver::Item &it, int64_t seq_no, double t0, double t1) {
+		Pipe &p = pipes[it.ctx];
+		{ std::lock_guard<std::mutex> lk(p.mu); p.out_free[it.out] = true; }
+		p.cv.notify_all();
+		span("write", seq_no, it.ctx, t0, t1);
+	};
+	int n_open = 0;
+	for (; n_open < n_ctx; ++n_open) if ((rc = pipe_open(ctxs[n_open], o.n_threads))) break;
+	if (rc) { for (int w = 0; w <= n_open && w < n_ctx; ++w) pipe_close(ctxs[w]); bwahip_fastq_close(d.rd); return rc; }
+	auto take_free = [](bool *f) { for (int i = 0; i < PIPE_SETS; ++i) if (f[i]) { f[i] = false; return i; } return -1; };
+	auto any_free = [](const bool *f) { for (int i = 0; i < PIPE_SETS; ++i) if (f[i]) return true; return false; };
+
+	auto stager = [&](int w) {
+		Pipe &p = pipes[w];
 		for (;;) {
-			{ std::unique_lock<std::mutex> lk(sl.mu); sl.cv.wait(lk, [&] { return !sl.full; }); }
-			bwahip_fastq_batch *b = nullptr; bwahip_seq_t *seqs = nullptr; int n = 0;
-			int64_t seq_no = 0, np0 = 0;
-			bool eof = d.failed();
+			Job j;
+			{
+				std::unique_lock<std::mutex> lk(p.mu);
+				p.cv.wait(lk, [&] { return d.failed() || any_free(p.in_free); });
+				if (d.failed()) break;
+				j.in = take_free(p.in_free);
+			}
+			bwahip_fastq_batch *b = nullptr; bwahip_seq_t *seqs = nullptr;
+			bool eof = false;
 			const double t0 = now_s();
-			if (!eof) {
+			{
 				std::lock_guard<std::mutex> lk(d.mu_read);
-				if (d.eof || (d.max_reads > 0 && d.n_processed >= d.max_reads)) { d.eof = true; eof = true; }
+				if (d.failed() || d.eof || (d.max_reads > 0 && d.n_processed >= d.max_reads)) { d.eof = true; eof = true; }
 				else {
-					const int r = bwahip_fastq_next_batch(d.rd, chunk, keep_comments, &b, &seqs, &n);
+					const int r = bwahip_fastq_next_batch(d.rd, chunk, keep_comments, &b, &seqs, &j.n);
 					if (r) { d.eof = true; eof = true; d.fail(r); }
-					else if (n == 0) { d.eof = true; eof = true; }
-					else { seq_no = d.next_seq++; np0 = d.n_processed; d.n_processed += n; }
+					else if (j.n == 0) { d.eof = true; eof = true; }
+					else { j.seq_no = d.next_seq++; j.np0 = d.n_processed; d.n_processed += j.n; }
 				}
 			}
-			wait_s[w] += now_s() - t0;
-			{ std::lock_guard<std::mutex> lk(sl.mu); sl.b = b; sl.seqs = seqs; sl.n = n; sl.seq_no = seq_no; sl.np0 = np0; sl.eof = eof; sl.full = true; }
-			sl.cv.notify_all();
-			if (eof) return;
-		}
-	};
-	auto worker = [&](int w) {
-		Slot &sl = slots[w];
-		std::thread ft(fetcher, w);
-		int64_t mine[2] = { -1, -1 };                             // the batches whose text sits in this context's two buffers
-		for (int k = 0;; ++k) {
-			bwahip_fastq_batch *b; bwahip_seq_t *seqs; int n; int64_t seq_no, np0; bool eof;
-			{
-				std::unique_lock<std::mutex> lk(sl.mu);
-				sl.cv.wait(lk, [&] { return sl.full; });
-				b = sl.b; seqs = sl.seqs; n = sl.n; seq_no = sl.seq_no; np0 = sl.np0; eof = sl.eof;
-				sl.full = false;
-			}
-			sl.cv.notify_all();
-			if (eof) break;
-			bool stop = d.failed();
-			// this call overwrites the buffer of this context's last-but-one batch: that one must be on the descriptor
-			if (!stop && mine[k & 1] >= 0) { std::unique_lock<std::mutex> lk(d.mu); d.cv_done.wait(lk, [&] { return d.rc || d.written > mine[k & 1]; }); stop = d.rc != 0; }
-			if (stop) { bwahip_fastq_batch_release(b); continue; }   // (drain what the fetcher still delivers; it stops at the failure flag)
 			const double t1 = now_s();
+			p.wait_s += t1 - t0;
+			if (eof) break;
+			span("take", j.seq_no, w, t0, t1);
+			double t_copy = t1;
+			const int r = pipe_stage_in(ctxs[w], j.in, &o, j.n, seqs, bam, &t_copy);
+			bwahip_fastq_batch_release(b);                          // names, bases and qualities are in HBM
+			const double t2 = now_s();
+			if (r) { d.fail(r); break; }
+			span("stage", j.seq_no, w, t1, t_copy); span("h2d", j.seq_no, w, t_copy, t2);
+			{ std::lock_guard<std::mutex> lk(p.mu); p.staged.push_back(j); }
+			p.cv.notify_all();
+		}
+		{ std::lock_guard<std::mutex> lk(p.mu); p.staged_end = true; }
+		p.cv.notify_all();
+	};
+	auto compute = [&](int w) {
+		Pipe &p = pipes[w];
+		for (;;) {
+			Job j;
+			{
+				std::unique_lock<std::mutex> lk(p.mu);
+				p.cv.wait(lk, [&] { return d.failed() || (!p.staged.empty() && any_free(p.out_free)) || (p.staged.empty() && p.staged_end); });
+				if (d.failed() || p.staged.empty()) break;
+				j = p.staged.front(); p.staged.pop_front();
+				j.out = take_free(p.out_free);
+			}
+			const double t0 = now_s();
+			double t_hot = t0;
+			const int r = pipe_compute(ctxs[w], j.in, j.out, &o, j.np0, pes0, bam, &t_hot);
+			if (r) { d.fail(r); break; }
+			span("hot", j.seq_no, w, t0, t_hot);
+			j.t_final = t_hot;
+			p.busy_s += now_s() - t0;
+			{ std::lock_guard<std::mutex> lk(p.mu); p.computed.push_back(j); }
+			p.cv.notify_all();
+		}
+		{ std::lock_guard<std::mutex> lk(p.mu); p.computed_end = true; }
+		p.cv.notify_all();
+	};
+	auto drainer = [&](int w) {
+		Pipe &p = pipes[w];
+		for (;;) {
+			Job j;
+			{
+				std::unique_lock<std::mutex> lk(p.mu);
+				p.cv.wait(lk, [&] { return d.failed() || !p.computed.empty() || p.computed_end; });
+				if (d.failed() || p.computed.empty()) break;
+				j = p.computed.front(); p.computed.pop_front();
+			}
 			const char *sam = nullptr; int64_t len = 0;
-			const int r = bam ? bwahip_process_seqs_bam(ctxs[w], &o, np0, n, seqs, pes0, (const uint8_t**)&sam, &len, nullptr)
-			                  : bwahip_process_seqs_text(ctxs[w], &o, np0, n, seqs, pes0, &sam, &len, nullptr);
-			bwahip_fastq_batch_release(b);                          // names, bases and qualities were staged inside the call
-			busy_s[w] += now_s() - t1;
-			if (r) { d.fail(r); continue; }
-			mine[k & 1] = seq_no;
-			{ std::lock_guard<std::mutex> lk(d.mu); d.ready[seq_no] = { sam, len }; }
+			double t_end = 0;
+			const int r = pipe_stage_out(ctxs[w], j.out, &sam, &len, &t_end);
+			const double t1 = now_s();
+			if (r) { d.fail(r); break; }
+			{ std::lock_guard<std::mutex> lk(p.mu); p.in_free[j.in] = true; }   // the kernels that read the input set have ended
+			p.cv.notify_all();
+			span("final", j.seq_no, w, j.t_final, t_end); span("d2h", j.seq_no, w, t_end, t1);
+			{ std::lock_guard<std::mutex> lk(d.mu); d.ready[j.seq_no] = { sam, len, w, j.out }; }
 			d.cv_item.notify_all();
 		}
-		ft.join();
 		// the buffers must outlive their write
-		{ std::unique_lock<std::mutex> lk(d.mu); d.cv_done.wait(lk, [&] { return d.rc || (d.written > mine[0] && d.written > mine[1]); }); --d.workers_left; }
+		{ std::unique_lock<std::mutex> lk(p.mu); p.cv.wait(lk, [&] { if (d.failed()) return true; for (int i = 0; i < PIPE_SETS; ++i) if (!p.out_free[i]) return false; return true; }); }
+		{ std::lock_guard<std::mutex> lk(d.mu); --d.workers_left; }
 		d.cv_item.notify_all();
 	};
 	std::thread wr([&] { d.writer(); });
 	std::vector<std::thread> th;
-	for (int w = 0; w < n_ctx; ++w) th.emplace_back(worker, w);
+	for (int w = 0; w < n_ctx; ++w) { th.emplace_back(stager, w); th.emplace_back(compute, w); th.emplace_back(drainer, w); }
 	for (auto &t : th) t.join();
 	wr.join();
+	for (int w = 0; w < n_ctx; ++w) pipe_close(ctxs[w]);           // after a failure kernels and copies may still be queued: nothing is left running
+	std::vector<double> wait_s(n_ctx), busy_s(n_ctx);
+	for (int w = 0; w < n_ctx; ++w) { wait_s[w] = pipes[w].wait_s; busy_s[w] = pipes[w].busy_s; }
 	if (bam && !d.rc) { const int r = bwahip_bgzf_eof(out_fd); if (r) d.rc = r; d.t_last_write = now_s(); }
 	const double t_joined = now_s();
 	g_reaper.close_later(d.rd);
-	if (getenv("BWAHIP_STREAM_LOG"))
+	if (log) {
+		for (const Span &x : spans) fprintf(stderr, "[bwahip] span %s batch %lld ctx %d %.3f %.3f\n", x.stage, (long long)x.batch, x.ctx, (x.t0 - t_call) * 1e3, (x.t1 - t_call) * 1e3);
+		fprintf(stderr, "[bwahip] stream: %lld batches on %d contexts, %ld buffer reallocations in this pass\n", (long long)d.next_seq, n_ctx, pipe_realloc_count() - reallocs0);
+	}
+	if (log)
 		fprintf(stderr, "[bwahip] stream: open %.1f ms, first batch in -> last SAM byte out %.1f ms, joining the threads %.1f ms, handing the reader to the closer %.1f ms\n",
 		        (t_start - t_call) * 1e3, (d.t_last_write - t_start) * 1e3, (t_joined - d.t_last_write) * 1e3, (now_s() - t_joined) * 1e3);
 	st->n_reads = d.n_processed; st->n_batches = d.next_seq; st->sam_bytes = d.sam_bytes;
-	st->seconds = d.t_last_write - t_start; st->write_s = d.write_s;
+	st->seconds = d.t_last_write - t_call; st->write_s = d.write_s;
 	for (int w = 0; w < n_ctx; ++w) { st->reader_wait_s += wait_s[w]; st->gpu_busy_s += busy_s[w]; }
 	return d.rc;
 }

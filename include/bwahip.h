@@ -279,9 +279,10 @@ typedef struct {
 	int keep_comments;        /* in: -C */
 	int reader_threads;       /* in: parse threads of the reader; <= 0: default */
 	int64_t n_reads, n_batches, sam_bytes;   /* out */
-	double seconds;           /* out: opening the files -> last SAM byte written */
-	double reader_wait_s;     /* out: summed over the workers: time spent waiting for the reader */
-	double gpu_busy_s;        /* out: summed over the workers: time inside bwahip_process_seqs_text */
+	double seconds;           /* out: the call (opening the files) -> last SAM byte written */
+	double reader_wait_s;     /* out: summed over the contexts: time their stage-in threads spent waiting for the reader */
+	double gpu_busy_s;        /* out: summed over the contexts: time in the compute stage (hot path and finalisation queued and their
+	                           * size read-backs awaited; staging and the copies run beside it and are not counted) */
 	double write_s;           /* out: time the writer spent in write() */
 } bwahip_stream_t;
 int bwahip_stream_run(bwahip_ctx *const *ctxs, int n_ctx, const bwahip_opt_t *opt, const bwahip_pestat_t *pes0,
