@@ -72,6 +72,11 @@ class StreamStats(C.Structure):  # bwahip_stream_t
                 ("reader_wait_s", C.c_double), ("gpu_busy_s", C.c_double), ("write_s", C.c_double)]
 
 
+class SortStats(C.Structure):  # bwahip_sort_t
+    _fields_ = [("tmp_dir", C.c_char_p), ("mem_budget", C.c_int64), ("n_records", C.c_int64), ("n_runs", C.c_int64), ("spilled_bytes", C.c_int64),
+                ("sort_ms", C.c_double), ("merge_s", C.c_double)]
+
+
 ERRORS = {0: "ok", -1: "EINVAL", -2: "ENODEV", -3: "ENOMEM", -4: "EIO", -5: "ECAPACITY", -6: "EINTERNAL"}
 
 STAGE_INTV, STAGE_CHAIN, STAGE_CHAIN_FLT, STAGE_REGS, STAGE_REGS_PRE, STAGE_SEEDS = 1, 2, 3, 4, 5, 6
@@ -117,6 +122,25 @@ def lib():
     L.bwahip_bns.restype = C.POINTER(Bns)
     L.bwahip_stream_run_bam.argtypes = [C.POINTER(vp), C.c_int, C.POINTER(Opt), C.POINTER(PeStat), C.c_char_p, C.c_char_p, C.c_int, C.c_char_p, C.c_int,
                                         C.POINTER(StreamStats)]
+    L.bwahip_process_seqs_bam_sorted.argtypes = [vp, C.POINTER(Opt), C.c_int64, C.c_int, C.POINTER(Seq), C.c_void_p, C.POINTER(vp), i64p, C.POINTER(vp), C.POINTER(vp), i64p]
+    L.bwahip_batch_run_bam_sorted.argtypes = [vp, C.POINTER(Opt), C.c_int64, C.POINTER(PeStat), C.POINTER(C.c_float), C.c_int, C.POINTER(C.c_float)]
+    L.bwahip_batch_bam_sorted.argtypes = [vp, C.POINTER(vp), i64p, C.POINTER(vp), C.POINTER(vp), i64p]
+    L.bwahip_bam_sort_key.argtypes = [C.POINTER(Bns), C.c_int32, C.c_int32, C.c_int]
+    L.bwahip_bam_sort_key.restype = C.c_uint64
+    L.bwahip_bam_sort_key_bits.argtypes = [C.POINTER(Bns)]
+    L.bwahip_bam_sort_key_for.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int]
+    L.bwahip_bam_sort_key_for.restype = C.c_uint64
+    L.bwahip_bam_sort_key_bits_for.argtypes = [C.c_int32, C.c_int32]
+    L.bwahip_bam_header_sorted.argtypes = [C.POINTER(Bns), C.c_char_p, C.POINTER(vp), i64p]
+    L.bwahip_bam_merger_open.argtypes = [C.c_char_p, C.c_int64, C.POINTER(vp)]
+    L.bwahip_bam_merger_add.argtypes = [vp, C.c_int64, vp, C.c_int64, vp, vp, C.c_int64]
+    L.bwahip_bam_merger_finish.argtypes = [vp, C.c_int, C.c_int, C.c_int]
+    L.bwahip_bam_merger_stats.argtypes = [vp, i64p, i64p, i64p, C.POINTER(C.c_double)]
+    L.bwahip_bam_merger_close.argtypes = [vp]
+    L.bwahip_bam_merger_close.restype = None
+    L.bwahip_stream_run_bam_sorted.argtypes = [C.POINTER(vp), C.c_int, C.POINTER(Opt), C.POINTER(PeStat), C.c_char_p, C.c_char_p, C.c_int, C.c_char_p, C.c_int,
+                                               C.POINTER(StreamStats), C.POINTER(SortStats)]
+    L.bwahip_kat_radix_sort.argtypes = [vp, C.c_int64, vp, C.c_int, vp, C.POINTER(C.c_int)]
     L.bwahip_fastq_open.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(vp)]
     L.bwahip_fastq_next.argtypes = [vp, C.c_int64, C.c_int, C.POINTER(C.POINTER(Seq)), C.POINTER(C.c_int)]
     L.bwahip_fastq_close.argtypes = [vp]
@@ -204,6 +228,78 @@ def bam_header(bns, hdr_line=None):
     b = big_bytes(out, ln.value)
     _free(out)
     return b
+
+
+def _bns_of(bns):
+    return lib().bwahip_bns(bns._h).contents if isinstance(bns, Context) else bns
+
+
+def bam_header_sorted(bns, hdr_line=None):
+    """bwahip_bam_header_sorted: bam_header with "@HD\tVN:1.6\tSO:coordinate" as the first line of the text; an @HD line in hdr_line: EINVAL."""
+    out, ln = C.c_void_p(), C.c_int64()
+    if isinstance(hdr_line, str):
+        hdr_line = hdr_line.encode()
+    _check(lib().bwahip_bam_header_sorted(C.byref(_bns_of(bns)), hdr_line, C.byref(out), C.byref(ln)), "bwahip_bam_header_sorted")
+    b = big_bytes(out, ln.value)
+    _free(out)
+    return b
+
+
+def bam_sort_key(bns, ref_id, pos, reverse):
+    """bwahip_bam_sort_key: the coordinate-sort key of a record with this refID, pos and strand under the index's contig table; no device."""
+    return int(lib().bwahip_bam_sort_key(C.byref(_bns_of(bns)), ref_id, pos, int(bool(reverse))))
+
+
+def bam_sort_key_bits(bns):
+    r = lib().bwahip_bam_sort_key_bits(C.byref(_bns_of(bns)))
+    if r < 0:
+        _check(r, "bwahip_bam_sort_key_bits")
+    return r
+
+
+def bam_sort_key_for(n_seqs, longest, ref_id, pos, reverse):
+    """bwahip_bam_sort_key_for: bam_sort_key under any index with n_seqs contigs whose longest has `longest` bases."""
+    return int(lib().bwahip_bam_sort_key_for(n_seqs, longest, ref_id, pos, int(bool(reverse))))
+
+
+def bam_sort_key_bits_for(n_seqs, longest):
+    r = lib().bwahip_bam_sort_key_bits_for(n_seqs, longest)
+    if r < 0:
+        _check(r, "bwahip_bam_sort_key_bits_for")
+    return r
+
+
+class BamMerger:
+    """bwahip_bam_merger_*: sorted runs in (records, keys, record offsets), one coordinate-sorted BGZF stream out; no device."""
+
+    def __init__(self, tmp_dir=None, mem_budget=1 << 30):
+        self._h = C.c_void_p()
+        _check(lib().bwahip_bam_merger_open(os.fsencode(tmp_dir) if tmp_dir is not None else None, mem_budget, C.byref(self._h)), "bwahip_bam_merger_open")
+
+    def add(self, run_no, rec, keys, rec_off):
+        rec = bytes(rec)
+        keys = np.ascontiguousarray(keys, dtype=np.uint64)
+        rec_off = np.ascontiguousarray(rec_off, dtype=np.int64)
+        _check(lib().bwahip_bam_merger_add(self._h, run_no, rec, len(rec), keys.ctypes.data, rec_off.ctypes.data, len(keys)), "bwahip_bam_merger_add")
+
+    def finish(self, fd, level=1, n_threads=1):
+        _check(lib().bwahip_bam_merger_finish(self._h, fd, level, n_threads), "bwahip_bam_merger_finish")
+
+    def stats(self):
+        a, b, c, d = C.c_int64(), C.c_int64(), C.c_int64(), C.c_double()
+        _check(lib().bwahip_bam_merger_stats(self._h, C.byref(a), C.byref(b), C.byref(c), C.byref(d)), "bwahip_bam_merger_stats")
+        return dict(n_records=a.value, n_runs=b.value, spilled_bytes=c.value, merge_s=d.value)
+
+    def close(self):
+        if self._h:
+            lib().bwahip_bam_merger_close(self._h)
+            self._h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
 
 
 def bgzf_write(fd, data, level=1, n_threads=1, eof=False):
@@ -398,6 +494,21 @@ class Context:
         arr, keep = seq_array(names, seqs, quals, comments)
         return self.process_seqs_bam_array(arr, len(seqs), opt, n_processed, pes0, want_offsets)
 
+    def process_seqs_bam_sorted_array(self, arr, n, opt=None, n_processed=0, pes0=None):
+        """bwahip_process_seqs_bam_sorted on a bseq1_t array: (records in coordinate order, keys as uint64 array, record offsets as int64 array)."""
+        opt = opt or default_opt()
+        bam, ln, keys, off, nr = C.c_void_p(), C.c_int64(), C.c_void_p(), C.c_void_p(), C.c_int64()
+        _check(lib().bwahip_process_seqs_bam_sorted(self._h, C.byref(opt), n_processed, n, arr, pes0, C.byref(bam), C.byref(ln), C.byref(keys), C.byref(off), C.byref(nr)),
+               "bwahip_process_seqs_bam_sorted")
+        k = np.frombuffer(big_bytes(keys, nr.value * 8), dtype=np.uint64).copy()
+        o = np.frombuffer(big_bytes(off, (nr.value + 1) * 8), dtype=np.int64).copy()
+        return big_bytes(bam, ln.value), k, o
+
+    def process_seqs_bam_sorted(self, names, seqs, quals=None, opt=None, n_processed=0, pes0=None, comments=None):
+        """The same from lists of names / ASCII reads (/ qualities, comments)."""
+        arr, keep = seq_array(names, seqs, quals, comments)
+        return self.process_seqs_bam_sorted_array(arr, len(seqs), opt, n_processed, pes0)
+
     def last_pe_stats(self):
         """(pestat[4] as dicts, mate-rescue alignments run on the GPU, regions they added) of the last PE batch."""
         pes = (PeStat * 4)()
@@ -449,6 +560,36 @@ class Context:
         rec = big_bytes(out, ln.value)
         _free(out)
         return rec
+
+    def batch_run_bam_sorted(self, opt=None, n_processed=0, pes0=None):
+        """batch_run_bam with the records in coordinate order; the stage milliseconds gain sort_table / sort_radix / sort_gather and
+        sort_passes (the radix passes that ran)."""
+        opt = opt or default_opt()
+        nk = lib().bwahip_n_kernels()
+        ms, sm = (C.c_float * nk)(), (C.c_float * 4)()
+        _check(lib().bwahip_batch_run_bam_sorted(self._h, C.byref(opt), n_processed, pes0, ms, nk, sm), "bwahip_batch_run_bam_sorted")
+        d = {lib().bwahip_kernel_name(i).decode(): float(ms[i]) for i in range(nk)}
+        d.update(sort_table=float(sm[0]), sort_radix=float(sm[1]), sort_gather=float(sm[2]), sort_passes=int(sm[3]))
+        return d
+
+    def batch_bam_sorted(self):
+        """(records, keys, record offsets) of the last batch_run_bam_sorted."""
+        out, ln, keys, off, nr = C.c_void_p(), C.c_int64(), C.c_void_p(), C.c_void_p(), C.c_int64()
+        _check(lib().bwahip_batch_bam_sorted(self._h, C.byref(out), C.byref(ln), C.byref(keys), C.byref(off), C.byref(nr)), "bwahip_batch_bam_sorted")
+        rec = big_bytes(out, ln.value)
+        k = np.frombuffer(big_bytes(keys, nr.value * 8), dtype=np.uint64).copy()
+        o = np.frombuffer(big_bytes(off, (nr.value + 1) * 8), dtype=np.int64).copy()
+        for p in (out, keys, off):
+            _free(p)
+        return rec, k, o
+
+    def kat_radix_sort(self, keys, key_bits=64):
+        """(permutation, tile): the product's stable radix sort on these uint64 keys; tile = items one workgroup ranks per pass."""
+        keys = np.ascontiguousarray(keys, dtype=np.uint64)
+        idx = np.empty(len(keys), dtype=np.uint32)
+        tile = C.c_int()
+        _check(lib().bwahip_kat_radix_sort(self._h, len(keys), keys.ctypes.data, key_bits, idx.ctypes.data, C.byref(tile)), "bwahip_kat_radix_sort")
+        return idx, tile.value
 
     def batch_run(self, opt=None):
         opt = opt or default_opt()
@@ -601,6 +742,21 @@ def stream_run_bam(ctxs, fq1, fq2=None, out_fd=-1, hdr_line=None, level=1, opt=N
     _check(lib().bwahip_stream_run_bam(arr, len(ctxs), C.byref(opt), C.byref(pes0) if pes0 is not None else None, os.fsencode(fq1),
                                        os.fsencode(fq2) if fq2 else None, out_fd, hdr_line, level, C.byref(st)), "bwahip_stream_run_bam")
     return st
+
+
+def stream_run_bam_sorted(ctxs, fq1, fq2=None, out_fd=-1, hdr_line=None, level=1, opt=None, chunk_bases=0, max_reads=0, keep_comments=False,
+                          reader_threads=0, pes0=None, tmp_dir=None, mem_budget=1 << 30):
+    """bwahip_stream_run_bam_sorted: FASTQ files -> a coordinate-sorted BAM file on out_fd.  Returns (StreamStats, SortStats)."""
+    opt = opt or default_opt()
+    st, so = StreamStats(), SortStats()
+    st.chunk_bases, st.max_reads, st.keep_comments, st.reader_threads = chunk_bases, max_reads, int(keep_comments), reader_threads
+    so.tmp_dir, so.mem_budget = os.fsencode(tmp_dir) if tmp_dir is not None else None, mem_budget
+    arr = (C.c_void_p * len(ctxs))(*[c._h for c in ctxs])
+    if isinstance(hdr_line, str):
+        hdr_line = hdr_line.encode()
+    _check(lib().bwahip_stream_run_bam_sorted(arr, len(ctxs), C.byref(opt), C.byref(pes0) if pes0 is not None else None, os.fsencode(fq1),
+                                              os.fsencode(fq2) if fq2 else None, out_fd, hdr_line, level, C.byref(st), C.byref(so)), "bwahip_stream_run_bam_sorted")
+    return st, so
 
 
 def _tool(name):

@@ -84,11 +84,27 @@ struct BatchText {
 	size_t sz_codes = 0, sz_qual = 0, sz_names = 0, sz_comm = 0;
 };
 
+// Working set of the coordinate sort of a batch's BAM records (k_bamsort.hip), one per context.  Per record: two key and two ordinal
+// buffers (the radix passes go back and forth), offset, length and sorted length; per read: record count and base; per pass: the
+// (digit, workgroup) histogram and its scan; `raw`: the batch's records in input order (the sorted ones go to d_sam).
+struct BamSort {
+	DevBuf raw, rec_cnt, rec_base, keys[2], idx[2], off, len, len_sorted, hist, hist_base, bits;
+	float ms[3] = { 0, 0, 0 };           // record table, radix sort, gather of the last timed run
+	int n_passes = 0;                    // radix passes the last sort ran
+	void release() { for (DevBuf *b : { &raw, &rec_cnt, &rec_base, &keys[0], &keys[1], &idx[0], &idx[1], &off, &len, &len_sorted, &hist, &hist_base, &bits }) b->release(); }
+};
+
 struct StreamPipe;                       // final_rt.hip: the second sets of batch buffers the stream driver's three stages work on
 
 struct bwahip_ctx {
 	StreamPipe *pipe = nullptr;          // made by the first bwahip_stream_run on this context, kept (buffers do not shrink), freed with the context
 	BatchText batch_text;
+	bool want_sorted = false;            // run_final (BAM): the records leave in coordinate order (k_bamsort.hip), with their keys and offsets
+	BamSort bs;
+	DevBuf d_skeys, d_rec_off;           // the sorted batch: n_rec keys, n_rec + 1 offsets of the records in d_sam
+	int64_t n_rec = 0;
+	hipEvent_t ev_sort[4] = {};          // begin of the record table, of the radix sort, of the gather, and the end
+	HostBuf h_skeys[2], h_rec_off[2];    // pinned: keys and offsets of bwahip_process_seqs_bam_sorted (taken in turn with h_sam / h_sam2)
 	bool want_host_sam_off = false;      // run_final copies the SAM offsets to h_sam_off ahead of the write pass (bwahip_process_seqs)
 	std::vector<int64_t> h_sam_off;      // offsets of the reads' SAM text in h_sam (bwahip_process_seqs / _text)
 	bool external_index = false;
@@ -151,6 +167,13 @@ int launch_nt4(uint8_t *seq, int64_t n, hipStream_t st);   // runtime.hip: ASCII
 int dev_upload(DevBuf &b, const void *src, size_t bytes, hipStream_t st);
 int run_pipeline(bwahip_ctx *c, const bwahip_opt_t *opt, bool timed, bool dump);      // the hot path over the uploaded batch
 int run_final(bwahip_ctx *c, const bwahip_opt_t *opt, int64_t n_processed, const bwahip_pestat_t *pes0, bool timed, bool bam = false);   // regions in HBM -> SAM text (or, bam: BAM records) in HBM (SE, or PE when opt->flag has MEM_F_PE)
+// k_bamsort.hip: the records of c->bs.raw (per-read offsets c->d_sam_off, n_reads + 1) in coordinate order into c->d_sam, their keys into
+// c->d_skeys, their offsets into c->d_rec_off; sets c->n_rec.  Queued on c->stream (with two small read-backs awaited in between).
+int bam_sort_batch(bwahip_ctx *c, int n_reads, int64_t total);
+// the stable LSD radix sort of bam_sort_batch alone, over c->bs.keys[0] / idx[0] (n items): the result is in keys[*which] / idx[*which]
+int bam_sort_radix(bwahip_ctx *c, int n, int key_bits, int *which);
+int bam_sort_iota(unsigned *idx, int n, hipStream_t st);
+int bam_sort_tile();
 int bam_check_reads(int n, const bwahip_seq_t *seqs);   // bam_host.cpp: BWAHIP_EINVAL (with a message naming the read) for a name or a comment BAM cannot hold
 void pipe_destroy(bwahip_ctx *c);                                                     // final_rt.hip: the stream driver's buffer sets
 int final_setup(bwahip_ctx *c);                                                       // contig name tables for the SAM kernels

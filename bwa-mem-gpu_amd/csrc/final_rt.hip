@@ -192,7 +192,8 @@ int run_final(bwahip_ctx *c, const bwahip_opt_t *opt, int64_t n_processed, const
 	};
 	const int n = c->n_reads;
 	const bool pe = (opt->flag & BWAHIP_F_PE) != 0;
-	c->total_sam = 0; c->total_tasks = 0;
+	c->total_sam = 0; c->total_tasks = 0; c->n_rec = 0;
+	const bool sorted = bam && c->want_sorted;                    // the records leave in coordinate order: written to a scratch buffer, sorted into d_sam
 	if (n == 0) return 0;
 	if (pe && (n & 1)) return BWAHIP_EINVAL;
 	int rc;
@@ -305,6 +306,7 @@ int run_final(bwahip_ctx *c, const bwahip_opt_t *opt, int64_t n_processed, const
 	c->total_sam = total;
 	if ((rc = c->d_sam.ensure((size_t)total + 64))) return rc;
 	f.sam = c->d_sam.as<uint8_t>();
+	if (sorted) { if ((rc = c->bs.raw.ensure((size_t)total + 64))) return rc; f.sam = c->bs.raw.as<uint8_t>(); }
 	if (c->want_host_sam_off) {                                 // bwahip_process_seqs: the offsets travel ahead of the write pass
 		c->h_sam_off.resize((size_t)n + 1);
 		HIP_TRY(hipMemcpyAsync(c->h_sam_off.data(), c->d_sam_off.p, (size_t)(n + 1) * 8, hipMemcpyDeviceToHost, c->stream));
@@ -315,9 +317,11 @@ int run_final(bwahip_ctx *c, const bwahip_opt_t *opt, int64_t n_processed, const
 	if ((rc = launch_out(f, true, 0, c->sam_half_reads))) return rc;
 	HIP_TRY(hipEventRecord(c->ev_sam_half, c->stream));
 	if ((rc = launch_out(f, true, c->sam_half_reads, n))) return rc;
+	if (timed) HIP_TRY(hipEventRecord(c->ev[19], c->stream));
+	if (sorted && (rc = bam_sort_batch(c, n, total))) return rc;
 	if (timed) {
-		HIP_TRY(hipEventRecord(c->ev[19], c->stream));
 		HIP_TRY(hipStreamSynchronize(c->stream));
+		if (sorted) for (int k = 0; k < 3; ++k) HIP_TRY(hipEventElapsedTime(&c->bs.ms[k], c->ev_sort[k], c->ev_sort[k + 1]));
 		HIP_TRY(hipEventElapsedTime(&c->final_ms[0], c->ev[15], c->ev[16]));
 		HIP_TRY(hipEventElapsedTime(&c->final_ms[1], c->ev[16], c->ev[17]));
 		HIP_TRY(hipEventElapsedTime(&c->final_ms[2], c->ev[17], c->ev[18]));
@@ -461,10 +465,15 @@ static int stage_text(bwahip_ctx *c, int nt, int n, bwahip_seq_t *seqs, const Ba
 	return 0;
 }
 
+// what bwahip_process_seqs_bam_sorted hands out beside the record bytes
+struct SortedOut { const uint64_t **keys; const int64_t **rec_off; int64_t *n_rec; };
+
 // text != nullptr: the batch's SAM stays one piece (in the context's pinned buffer) instead of being cut into per-read strings
 static int process_seqs_impl(bwahip_ctx *ctx, const bwahip_opt_t *opt, int64_t n_processed, int n, bwahip_seq_t *seqs, const bwahip_pestat_t *pes0,
-                             const char **text_out, int64_t *len_out, const int64_t **off_out, bool bam = false)
+                             const char **text_out, int64_t *len_out, const int64_t **off_out, bool bam = false, const SortedOut *sorted = nullptr)
 {
+	static const int64_t no_records[1] = { 0 };
+	if (sorted) { *sorted->keys = nullptr; *sorted->rec_off = no_records; *sorted->n_rec = 0; }
 	if (!ctx || !opt || n < 0 || (n && !seqs)) return BWAHIP_EINVAL;
 	const bool pe = (opt->flag & BWAHIP_F_PE) != 0;
 	if (pe && (n & 1)) return BWAHIP_EINVAL;
@@ -494,10 +503,25 @@ static int process_seqs_impl(bwahip_ctx *ctx, const bwahip_opt_t *opt, int64_t n
 	text_thread.join();
 	if (rc || (rc = rc_text)) return rc;
 	const double t2 = now();
-	ctx->want_host_sam_off = true;
+	ctx->want_host_sam_off = true; ctx->want_sorted = sorted != nullptr;
 	rc = run_final(ctx, opt, n_processed, pes0, false, bam);
-	ctx->want_host_sam_off = false;
+	ctx->want_host_sam_off = false; ctx->want_sorted = false;
 	if (rc) return rc;
+	if (sorted) {                                                 // records, keys and offsets in one piece each, through pinned buffers taken in turn
+		const int flip = (ctx->sam_flip ^= 1);
+		HostBuf &hb = flip ? ctx->h_sam2 : ctx->h_sam, &hk = ctx->h_skeys[flip], &ho = ctx->h_rec_off[flip];
+		const int64_t nr = ctx->n_rec;
+		if ((rc = hb.ensure((size_t)ctx->total_sam + 1)) || (rc = hk.ensure((size_t)(nr ? nr : 1) * 8)) || (rc = ho.ensure((size_t)(nr + 1) * 8))) return rc;
+		if (ctx->total_sam) HIP_TRY(hipMemcpyAsync(hb.p, ctx->d_sam.p, (size_t)ctx->total_sam, hipMemcpyDeviceToHost, ctx->stream));
+		if (nr) HIP_TRY(hipMemcpyAsync(hk.p, ctx->d_skeys.p, (size_t)nr * 8, hipMemcpyDeviceToHost, ctx->stream));
+		HIP_TRY(hipMemcpyAsync(ho.p, ctx->d_rec_off.p, (size_t)(nr + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
+		HIP_TRY(hipStreamSynchronize(ctx->stream));
+		HIP_TRY(hipStreamSynchronize(ctx->stream_copy));
+		par_for_chunks(n, nt, [&](int64_t b, int64_t e) { for (int64_t i = b; i < e; ++i) seqs[i].sam = nullptr; });
+		*text_out = (const char*)hb.p; *len_out = ctx->total_sam;
+		*sorted->keys = (const uint64_t*)hk.p; *sorted->rec_off = (const int64_t*)ho.p; *sorted->n_rec = nr;
+		return 0;
+	}
 	// SAM text back through the pinned buffer, on the context's stream (a non-blocking stream: a plain hipMemcpy would not wait
 	// for the SAM kernel), in slices of reads: while slice k+1 travels, the host threads cut slice k into one malloc()ed string
 	// per read, which is what the reference's contract wants (bwamem.c:1054)
@@ -587,6 +611,16 @@ extern "C" int bwahip_process_seqs_bam(bwahip_ctx *ctx, const bwahip_opt_t *opt,
 	return process_seqs_impl(ctx, opt, n_processed, n, seqs, pes0, (const char**)bam, bam_len, off, true);
 }
 
+// The same records in coordinate order (k_bamsort.hip; the key and the order are in include/bwahip.h), with what a merge of several
+// batches needs: the sorted keys and the records' offsets.  Buffers and lifetimes as above.
+extern "C" int bwahip_process_seqs_bam_sorted(bwahip_ctx *ctx, const bwahip_opt_t *opt, int64_t n_processed, int n, bwahip_seq_t *seqs, const bwahip_pestat_t *pes0,
+                                              const uint8_t **bam, int64_t *bam_len, const uint64_t **keys, const int64_t **rec_off, int64_t *n_rec)
+{
+	if (!bam || !bam_len || !keys || !rec_off || !n_rec) return BWAHIP_EINVAL;
+	const SortedOut so = { keys, rec_off, n_rec };
+	return process_seqs_impl(ctx, opt, n_processed, n, seqs, pes0, (const char**)bam, bam_len, nullptr, true, &so);
+}
+
 // Insert-size statistics (mem_pestat_t x 4: FF, FR, RF, RR) and mate-rescue counters ([0] Smith-Waterman alignments run on
 // the GPU, [1] regions they added, [2] most alignments of one pair, [3] pairs that needed any) of the last paired-end batch
 // finalised on the GPU.
@@ -663,6 +697,12 @@ struct PipeOut {
 	HostBuf h_sam;
 	hipEvent_t ev_written = nullptr, ev_copied = nullptr;   // the write pass has ended / the bytes are in h_sam
 	int64_t total = 0;
+	// coordinate-sorted BAM: the keys and offsets of the set's records, and the events around the sort stage that produced them
+	DevBuf d_keys, d_rec_off;
+	HostBuf h_keys, h_rec_off;
+	hipEvent_t ev_sort[4] = {};
+	int64_t n_rec = 0;
+	bool sorted = false;
 };
 
 } // namespace
@@ -706,6 +746,8 @@ void pipe_destroy(bwahip_ctx *c)
 	}
 	for (auto &s : c->pipe->out) {
 		s.d_sam.release(); s.d_sam_off.release(); s.h_sam.release();
+		s.d_keys.release(); s.d_rec_off.release(); s.h_keys.release(); s.h_rec_off.release();
+		for (auto &e : s.ev_sort) if (e) (void)hipEventDestroy(e);
 		if (s.ev_written) (void)hipEventDestroy(s.ev_written);
 		if (s.ev_copied) (void)hipEventDestroy(s.ev_copied);
 	}
@@ -811,6 +853,7 @@ int pipe_compute(bwahip_ctx *c, int in, int out, const bwahip_opt_t *opt, int64_
 		std::swap(c->d_names, s.d_names); std::swap(c->d_name_off, s.d_name_off); std::swap(c->d_comment_off, s.d_comment_off);
 		std::swap(c->d_comments, s.any_comment ? s.d_comments : no_comments);   // a batch without comments: a null pointer tells the kernels
 		std::swap(c->d_sam, o.d_sam); std::swap(c->d_sam_off, o.d_sam_off);
+		std::swap(c->d_skeys, o.d_keys); std::swap(c->d_rec_off, o.d_rec_off); std::swap(c->ev_sort, o.ev_sort);
 		std::swap(c->n_reads, s.n); std::swap(c->max_len, s.max_len); std::swap(c->total_bases, s.total_bases);
 	};
 	exchange();
@@ -820,10 +863,12 @@ int pipe_compute(bwahip_ctx *c, int in, int out, const bwahip_opt_t *opt, int64_
 		if ((rc = launch_nt4(c->d_seq.as<uint8_t>(), c->total_bases, c->stream))) return rc;
 		if ((rc = run_pipeline(c, opt, false, false))) return rc;
 		if (t_hot_end) *t_hot_end = pipe_now();
-		c->want_host_sam_off = false;
-		if ((rc = run_final(c, opt, n_processed, pes0, false, bam != 0))) return rc;
+		c->want_host_sam_off = false; c->want_sorted = bam == 2;
+		rc = run_final(c, opt, n_processed, pes0, false, bam != 0);
+		c->want_sorted = false;
+		if (rc) return rc;
 		HIP_TRY(hipEventRecord(o.ev_written, c->stream));
-		o.total = c->total_sam;
+		o.total = c->total_sam; o.n_rec = c->n_rec; o.sorted = bam == 2;
 		return 0;
 	};
 	rc = body();
@@ -851,5 +896,25 @@ int pipe_stage_out(bwahip_ctx *c, int out, const char **text, int64_t *len, doub
 	}
 	p[o.total] = 0;
 	*text = p; *len = o.total;
+	return 0;
+}
+
+// After pipe_stage_out of a batch computed with bam == 2: the keys and offsets of the set's records in its pinned buffers (valid as long
+// as the text), and the time the sort stage took on the GPU.
+int pipe_stage_out_sorted(bwahip_ctx *c, int out, const uint64_t **keys, const int64_t **rec_off, int64_t *n_rec, double *sort_ms)
+{
+	if (!c || !c->pipe || out < 0 || out >= PIPE_SETS || !keys || !rec_off || !n_rec) return BWAHIP_EINVAL;
+	HIP_TRY(hipSetDevice(c->device));
+	PipeOut &o = c->pipe->out[out];
+	if (!o.sorted) return BWAHIP_EINVAL;
+	int rc;
+	if ((rc = o.h_keys.ensure((size_t)(o.n_rec ? o.n_rec : 1) * 8)) || (rc = o.h_rec_off.ensure((size_t)(o.n_rec + 1) * 8))) return rc;
+	if (o.n_rec) HIP_TRY(hipMemcpyAsync(o.h_keys.p, o.d_keys.p, (size_t)o.n_rec * 8, hipMemcpyDeviceToHost, c->stream_copy));
+	if (o.n_rec) HIP_TRY(hipMemcpyAsync(o.h_rec_off.p, o.d_rec_off.p, (size_t)(o.n_rec + 1) * 8, hipMemcpyDeviceToHost, c->stream_copy));
+	else *(int64_t*)o.h_rec_off.p = 0;
+	HIP_TRY(hipEventRecord(o.ev_copied, c->stream_copy));
+	HIP_TRY(hipEventSynchronize(o.ev_copied));
+	if (sort_ms) { float ms = 0; if (o.n_rec && o.ev_sort[0] && hipEventElapsedTime(&ms, o.ev_sort[0], o.ev_sort[3]) != hipSuccess) ms = 0; *sort_ms = ms; }
+	*keys = (const uint64_t*)o.h_keys.p; *rec_off = (const int64_t*)o.h_rec_off.p; *n_rec = o.n_rec;
 	return 0;
 }

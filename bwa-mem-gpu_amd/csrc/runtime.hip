@@ -365,6 +365,9 @@ void bwahip_destroy(bwahip_ctx *c)
 	if (c->external_index) { c->d_bwt.p = nullptr; c->d_sa.p = nullptr; c->d_pac.p = nullptr; c->d_bwt.cap = c->d_sa.cap = c->d_pac.cap = 0; }
 	for (DevBuf *b : bufs) b->release();
 	c->h_stage.release(); c->h_sam.release(); c->h_sam2.release();
+	c->bs.release(); c->d_skeys.release(); c->d_rec_off.release();
+	for (int k = 0; k < 2; ++k) { c->h_skeys[k].release(); c->h_rec_off[k].release(); }
+	for (auto &e : c->ev_sort) if (e) (void)hipEventDestroy(e);
 	for (auto &e : c->ev) if (e) (void)hipEventDestroy(e);
 	if (c->stream) (void)hipStreamDestroy(c->stream);
 	if (c->stream2) (void)hipStreamDestroy(c->stream2);
@@ -460,6 +463,25 @@ int bwahip_kat_introsort(bwahip_ctx *c, int n, int mode, const int64_t *k64, con
 done:
 	dk.release(); dp.release(); ds.release(); dw.release(); dst.release();
 	return rc;
+}
+
+// The stable radix sort of the coordinate-sorted BAM output (k_bamsort.hip) on caller keys: exactly the product's passes for keys of
+// key_bits significant bits.  idx_out: the permutation (n ordinals: idx_out[i] = input position of the i-th smallest key, ties in input
+// order); tile_out (may be NULL): the items one workgroup ranks per pass.  n = 0 and n = 1 launch nothing.
+int bwahip_kat_radix_sort(bwahip_ctx *c, int64_t n, const uint64_t *keys, int key_bits, uint32_t *idx_out, int *tile_out)
+{
+	if (tile_out) *tile_out = bam_sort_tile();
+	if (!c || n < 0 || n > 0x7fffffff || key_bits < 1 || key_bits > 64 || (n && (!keys || !idx_out))) return BWAHIP_EINVAL;
+	if (n == 0) return 0;
+	HIP_TRY(hipSetDevice(c->device));
+	BamSort &s = c->bs;
+	int rc, cur = 0;
+	if ((rc = s.keys[0].ensure((size_t)n * 8)) || (rc = s.keys[1].ensure((size_t)n * 8)) || (rc = s.idx[0].ensure((size_t)n * 4)) || (rc = s.idx[1].ensure((size_t)n * 4))) return rc;
+	HIP_TRY(hipMemcpyAsync(s.keys[0].p, keys, (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
+	if ((rc = bam_sort_iota(s.idx[0].as<unsigned>(), (int)n, c->stream)) || (rc = bam_sort_radix(c, (int)n, key_bits, &cur))) return rc;
+	HIP_TRY(hipMemcpyAsync(idx_out, s.idx[cur].p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+	HIP_TRY(hipStreamSynchronize(c->stream));
+	return 0;
 }
 
 int bwahip_kat_occ4(bwahip_ctx *c, int n, const uint64_t *k, uint64_t *out)
@@ -832,6 +854,37 @@ int bwahip_batch_run_bam(bwahip_ctx *c, const bwahip_opt_t *opt, int64_t n_proce
 		for (int i = 0; i < 4 && 12 + i < n_ms; ++i) kernel_ms[12 + i] = c->final_ms[i];
 	}
 	return rc;
+}
+
+// bwahip_batch_run_bam with the records in coordinate order.  sort_ms4 (may be NULL): the sort stage of this run on the GPU -- [0] record
+// table, [1] radix sort, [2] gather, in milliseconds, and [3] the number of radix passes that ran.
+int bwahip_batch_run_bam_sorted(bwahip_ctx *c, const bwahip_opt_t *opt, int64_t n_processed, const bwahip_pestat_t *pes0, float *kernel_ms, int n_ms, float *sort_ms4)
+{
+	if (!c || !opt) return BWAHIP_EINVAL;
+	c->want_sorted = true;
+	const int rc = bwahip_batch_run_bam(c, opt, n_processed, pes0, kernel_ms, n_ms);
+	c->want_sorted = false;
+	if (!rc && sort_ms4) { for (int k = 0; k < 3; ++k) sort_ms4[k] = c->n_rec ? c->bs.ms[k] : 0; sort_ms4[3] = (float)c->bs.n_passes; }
+	return rc;
+}
+
+// The sorted records of the last bwahip_batch_run_bam_sorted with their keys (*n_rec) and offsets (*n_rec + 1), each in a malloc()ed buffer
+int bwahip_batch_bam_sorted(bwahip_ctx *c, uint8_t **out, int64_t *out_len, uint64_t **keys, int64_t **rec_off, int64_t *n_rec)
+{
+	if (!c || !out || !out_len || !keys || !rec_off || !n_rec) return BWAHIP_EINVAL;
+	HIP_TRY(hipSetDevice(c->device));
+	const int64_t nr = c->n_rec;
+	uint8_t *buf = (uint8_t*)malloc((size_t)c->total_sam + 1);
+	uint64_t *k = (uint64_t*)malloc((size_t)(nr ? nr : 1) * 8);
+	int64_t *o = (int64_t*)calloc((size_t)nr + 1, 8);
+	auto bad = [&](int code) { free(buf); free(k); free(o); return code; };
+	if (!buf || !k || !o) return bad(BWAHIP_ENOMEM);
+	if (nr && (hipMemcpyAsync(buf, c->d_sam.p, (size_t)c->total_sam, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+	           hipMemcpyAsync(k, c->d_skeys.p, (size_t)nr * 8, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+	           hipMemcpyAsync(o, c->d_rec_off.p, (size_t)(nr + 1) * 8, hipMemcpyDeviceToHost, c->stream) != hipSuccess)) return bad(BWAHIP_ENODEV);
+	if (hipStreamSynchronize(c->stream) != hipSuccess) return bad(BWAHIP_ENODEV);
+	*out = buf; *out_len = nr ? c->total_sam : 0; *keys = k; *rec_off = o; *n_rec = nr;
+	return 0;
 }
 
 // The records of the last bwahip_batch_run_bam, as bwahip_batch_sam hands out the text (no NUL is meaningful here)

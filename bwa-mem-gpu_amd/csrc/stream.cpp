@@ -48,7 +48,7 @@ struct Driver {
 	// writer side
 	std::mutex mu;
 	std::condition_variable cv_item, cv_done;
-	struct Item { const char *p; int64_t len; int ctx, out; };   // ctx / out: the output set the bytes sit in
+	struct Item { const char *p; int64_t len; int ctx, out; const uint64_t *keys; const int64_t *rec_off; int64_t n_rec; };   // ctx / out: the output set the bytes sit in; keys, rec_off: coordinate-sorted BAM
 	std::map<int64_t, Item> ready;                               // finished batches waiting for their turn
 	int64_t written = 0;                                         // batches [0, written) are on the descriptor
 	int workers_left = 0;
@@ -58,6 +58,8 @@ struct Driver {
 	std::function<void(const Item&, int64_t, double, double)> on_written;   // gives the output set back to its context
 	int fd = -1;
 	int bam = 0, level = 0, deflate_threads = 1;                 // bwahip_stream_run_bam: the batches' records go through the BGZF writer
+	bwahip_bam_merger *merger = nullptr;                         // bam == 2 (bwahip_stream_run_bam_sorted): every batch is a sorted run of the merger instead
+	double sort_ms = 0;
 	int64_t sam_bytes = 0;
 	double t_last_write = 0, write_s = 0;
 
@@ -77,7 +79,11 @@ struct Driver {
 			}
 			const double t0 = now_s();
 			int64_t o = 0;
-			if (bam) {
+			if (bam == 2) {                                              // the merger copies (or spills) the run: the set goes back at once
+				const int r = bwahip_bam_merger_add(merger, written, (const uint8_t*)it.p, it.len, it.keys, it.rec_off, it.n_rec);
+				if (r) { fail(r); return; }
+				o = it.len;
+			} else if (bam) {
 				const int r = bwahip_bgzf_write(fd, it.p, it.len, level, deflate_threads);
 				if (r) { fail(r); return; }
 				o = it.len;
@@ -110,11 +116,13 @@ Reaper g_reaper;
 
 } // namespace
 
-// bam: 0 = SAM text as it comes; 1 = BAM: header, every batch's records through the BGZF writer in input order, the EOF block
+// bam: 0 = SAM text as it comes; 1 = BAM: header, every batch's records through the BGZF writer in input order, the EOF block;
+// 2 = coordinate-sorted BAM: every batch leaves its context sorted and becomes a run of the merger (the batch number is the run number);
+// after the last batch: header, the merge of the runs through the BGZF writer, the EOF block
 static int stream_run(bwahip_ctx *const *ctxs, int n_ctx, const bwahip_opt_t *opt, const bwahip_pestat_t *pes0,
-                      const char *fq1, const char *fq2, int out_fd, bwahip_stream_t *st, int bam, const char *hdr_line, int level)
+                      const char *fq1, const char *fq2, int out_fd, bwahip_stream_t *st, int bam, const char *hdr_line, int level, bwahip_sort_t *so = nullptr)
 {
-	if (!ctxs || n_ctx < 1 || n_ctx > 256 || !opt || !fq1 || !st) return BWAHIP_EINVAL;
+	if (!ctxs || n_ctx < 1 || n_ctx > 256 || !opt || !fq1 || !st || (bam == 2 && !so)) return BWAHIP_EINVAL;
 	for (int i = 0; i < n_ctx; ++i) if (!ctxs[i]) return BWAHIP_EINVAL;
 	if (bam && (level < 0 || level > 9)) return BWAHIP_EINVAL;
 	// actual_chunk_size (fastmap.c:304): -K when given, else chunk_size * n_threads
@@ -128,7 +136,18 @@ static int stream_run(bwahip_ctx *const *ctxs, int n_ctx, const bwahip_opt_t *op
 	Driver d;
 	d.fd = out_fd; d.max_reads = st->max_reads;
 	d.bam = bam; d.level = level; d.deflate_threads = n_deflate;
-	if (bam) {
+	struct Sorted {                                              // the header waits for the merge; the merger and its files go whatever happens
+		uint8_t *hdr = nullptr; int64_t hlen = 0; bwahip_bam_merger *m = nullptr;
+		~Sorted() { free(hdr); bwahip_bam_merger_close(m); }
+	} sorted;
+	if (bam == 2) {
+		so->n_records = so->n_runs = so->spilled_bytes = 0; so->sort_ms = so->merge_s = 0;
+		int hr = bwahip_bam_header_sorted(bwahip_bns(ctxs[0]), hdr_line, &sorted.hdr, &sorted.hlen);
+		if (!hr) hr = bwahip_bam_merger_open(so->tmp_dir, so->mem_budget, &sorted.m);
+		if (hr) return hr;
+		d.merger = sorted.m;
+	}
+	if (bam == 1) {
 		uint8_t *hdr = nullptr; int64_t hlen = 0;
 		int hr = bwahip_bam_header(bwahip_bns(ctxs[0]), hdr_line, &hdr, &hlen);
 		if (!hr) { hr = bwahip_bgzf_write(out_fd, hdr, hlen, level, 1); free(hdr); }
@@ -254,7 +273,10 @@ static int stream_run(bwahip_ctx *const *ctxs, int n_ctx, const bwahip_opt_t *op
 			{ std::lock_guard<std::mutex> lk(p.mu); p.in_free[j.in] = true; }   // the kernels that read the input set have ended
 			p.cv.notify_all();
 			span("final", j.seq_no, w, j.t_final, t_end); span("d2h", j.seq_no, w, t_end, t1);
-			{ std::lock_guard<std::mutex> lk(d.mu); d.ready[j.seq_no] = { sam, len, w, j.out }; }
+			const uint64_t *keys = nullptr; const int64_t *rec_off = nullptr; int64_t n_rec = 0;
+			double sort_ms = 0;
+			if (bam == 2) { const int r2 = pipe_stage_out_sorted(ctxs[w], j.out, &keys, &rec_off, &n_rec, &sort_ms); if (r2) { d.fail(r2); break; } }
+			{ std::lock_guard<std::mutex> lk(d.mu); d.ready[j.seq_no] = { sam, len, w, j.out, keys, rec_off, n_rec }; d.sort_ms += sort_ms; }
 			d.cv_item.notify_all();
 		}
 		// the buffers must outlive their write
@@ -270,6 +292,17 @@ static int stream_run(bwahip_ctx *const *ctxs, int n_ctx, const bwahip_opt_t *op
 	for (int w = 0; w < n_ctx; ++w) pipe_close(ctxs[w]);           // after a failure kernels and copies may still be queued: nothing is left running
 	std::vector<double> wait_s(n_ctx), busy_s(n_ctx);
 	for (int w = 0; w < n_ctx; ++w) { wait_s[w] = pipes[w].wait_s; busy_s[w] = pipes[w].busy_s; }
+	if (bam == 2 && !d.rc) {                                     // every run is with the merger: header, merge, end-of-file block
+		const double t0 = now_s();
+		int r = bwahip_bgzf_write(out_fd, sorted.hdr, sorted.hlen, level, 1);
+		// the staging threads have ended, so the merge's BGZF writer gets all host threads, not the n_deflate the unsorted writer
+		// shares the host with them for (the bytes do not depend on the number of threads)
+		if (!r) r = bwahip_bam_merger_finish(sorted.m, out_fd, level, opt->n_threads > 1 ? opt->n_threads : 1);
+		if (r) d.rc = r;
+		d.write_s += now_s() - t0;
+		bwahip_bam_merger_stats(sorted.m, &so->n_records, &so->n_runs, &so->spilled_bytes, &so->merge_s);
+		so->sort_ms = d.sort_ms;
+	}
 	if (bam && !d.rc) { const int r = bwahip_bgzf_eof(out_fd); if (r) d.rc = r; d.t_last_write = now_s(); }
 	const double t_joined = now_s();
 	g_reaper.close_later(d.rd);
@@ -297,4 +330,12 @@ extern "C" int bwahip_stream_run_bam(bwahip_ctx *const *ctxs, int n_ctx, const b
                                      const char *fq1, const char *fq2, int out_fd, const char *hdr_line, int level, bwahip_stream_t *st)
 {
 	return stream_run(ctxs, n_ctx, opt, pes0, fq1, fq2, out_fd, st, 1, hdr_line, level);
+}
+
+// FASTQ files in -> a coordinate-sorted BAM file out: every batch is sorted on its context (bwahip_process_seqs_bam_sorted's kernels) and
+// merged on the host (bwahip_bam_merger_*); the bytes depend on the input and the options alone
+extern "C" int bwahip_stream_run_bam_sorted(bwahip_ctx *const *ctxs, int n_ctx, const bwahip_opt_t *opt, const bwahip_pestat_t *pes0,
+                                            const char *fq1, const char *fq2, int out_fd, const char *hdr_line, int level, bwahip_stream_t *st, bwahip_sort_t *so)
+{
+	return stream_run(ctxs, n_ctx, opt, pes0, fq1, fq2, out_fd, st, 2, hdr_line, level, so);
 }

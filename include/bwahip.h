@@ -295,6 +295,67 @@ int bwahip_stream_run(bwahip_ctx *const *ctxs, int n_ctx, const bwahip_opt_t *op
 int bwahip_stream_run_bam(bwahip_ctx *const *ctxs, int n_ctx, const bwahip_opt_t *opt, const bwahip_pestat_t *pes0,
                           const char *fq1, const char *fq2, int out_fd, const char *hdr_line, int level, bwahip_stream_t *st);
 
+/* ---- coordinate-sorted BAM ---------------------------------------------------------------------------------------------------------
+ * The order is `samtools sort`'s coordinate order with its ties made explicit:
+ *   1. refID as an unsigned number: -1 (no reference) after every contig;
+ *   2. pos, -1 first within a refID (only records without a reference have it);
+ *   3. strand: forward before reverse (flag 0x10);
+ *   4. input order: batch (run) number, then the record's ordinal within the batch's unsorted records -- the sort is stable.
+ * An unmapped read with a mapped mate carries the mate's refID and pos (bwamem.c:842-845) and so sorts next to it.  Rules 1-3 are one
+ * uint64_t whose unsigned order is that order -- part of the ABI, because callers merge on it:
+ *     bit 0                        reverse strand
+ *     bits 1 .. P                  pos + 1                         P = bit length of (longest contig of the index + 1)
+ *     bits P + 1 .. P + R          refID, -1 mapped to n_seqs      R = bit length of n_seqs
+ * and no bit above.  n_seqs and contig lengths are int32 (bntseq.h), so P <= 32, R <= 31 and the key fits 64 bits for any index.
+ * bwahip_bam_sort_key is the host restatement (no device; a refID outside [0, n_seqs) counts as -1), bwahip_bam_sort_key_bits = 1 + P + R.
+ *
+ * bwahip_process_seqs_bam_sorted: bwahip_process_seqs_bam with the batch's records in that order, sorted on the GPU (csrc/k_bamsort.hip: a
+ * record table, a stable radix sort of (key, ordinal) over the key bits that differ, one gather of the record bytes).  *keys: the n_rec
+ * sorted keys; *rec_off: n_rec + 1 offsets, record i is bam[rec_off[i] .. rec_off[i+1]).  Buffers and lifetimes as for
+ * bwahip_process_seqs_bam (*bam and *keys until the next-but-one call on the context, *rec_off likewise). */
+int  bwahip_process_seqs_bam_sorted(bwahip_ctx *ctx, const bwahip_opt_t *opt, int64_t n_processed, int n, bwahip_seq_t *seqs, const bwahip_pestat_t *pes0,
+                                    const uint8_t **bam, int64_t *bam_len, const uint64_t **keys, const int64_t **rec_off, int64_t *n_rec);
+uint64_t bwahip_bam_sort_key(const bwahip_bns_t *bns, int32_t refID, int32_t pos, int reverse);
+int  bwahip_bam_sort_key_bits(const bwahip_bns_t *bns);
+/* the same for any index with n_seqs contigs whose longest has `longest` bases: the key depends on the contig table through these alone */
+uint64_t bwahip_bam_sort_key_for(int32_t n_seqs, int32_t longest, int32_t refID, int32_t pos, int reverse);
+int  bwahip_bam_sort_key_bits_for(int32_t n_seqs, int32_t longest);
+/* bwahip_bam_header with "@HD\tVN:1.6\tSO:coordinate" as the first line of the text; a hdr_line that brings an @HD line of its own:
+ * BWAHIP_EINVAL. */
+int  bwahip_bam_header_sorted(const bwahip_bns_t *bns, const char *hdr_line, uint8_t **out, int64_t *len);
+
+/* Device-free merger of sorted runs (one run = one batch of bwahip_process_seqs_bam_sorted, handed over with its keys and offsets; no
+ * record is ever parsed).  open: runs stay in host memory while their total is within mem_budget bytes; from the first run that would
+ * exceed it, every run goes to a file of its own under tmp_dir (NULL: $TMPDIR or /tmp; mem_budget <= 0: every run) -- raw records, keys
+ * and offsets, uncompressed, private.  tmp_dir must be a directory files can be made in: BWAHIP_EIO otherwise.  add: thread-safe, copies
+ * what it is given (the caller's buffers are free on return); a run_no given twice: BWAHIP_EINVAL; a failed or short write: BWAHIP_EIO.
+ * finish: k-way merge by (key, run_no, position in the run) into BGZF blocks on fd (< 0: produced and dropped) -- no header, no EOF
+ * block; spilled runs are read through bounded windows and the output is deflated in pieces, so the whole is never in memory; the bytes
+ * are those of one bwahip_bgzf_write over all records in order, whatever the budget and however the records were cut into runs.
+ * A spilled run's file is open only while one of its windows
+ * is filled, so the number of runs is not bounded by the limit on open descriptors.
+ * close: frees everything and removes the files (also those of runs whose add failed half way). */
+typedef struct bwahip_bam_merger bwahip_bam_merger;
+int  bwahip_bam_merger_open(const char *tmp_dir, int64_t mem_budget, bwahip_bam_merger **m);
+int  bwahip_bam_merger_add(bwahip_bam_merger *m, int64_t run_no, const uint8_t *rec, int64_t len, const uint64_t *keys, const int64_t *rec_off, int64_t n_rec);
+int  bwahip_bam_merger_finish(bwahip_bam_merger *m, int fd, int level, int n_threads);
+int  bwahip_bam_merger_stats(bwahip_bam_merger *m, int64_t *n_records, int64_t *n_runs, int64_t *spilled_bytes, double *merge_s);   /* any pointer may be NULL */
+void bwahip_bam_merger_close(bwahip_bam_merger *m);
+
+/* bwahip_stream_run_bam with a coordinate-sorted file as the output.  The pipeline per context is the same (stager, compute, drainer);
+ * every batch leaves its context sorted and is handed to a merger with its batch number as the run number; after the last batch the
+ * header (bwahip_bam_header_sorted), the merge and the EOF block are written.  The bytes do not depend on the number of contexts, on
+ * which context took a batch, on mem_budget or on thread counts.  st as for bwahip_stream_run_bam (seconds: to the last byte written;
+ * write_s includes the merge).  so: fill tmp_dir and mem_budget (see bwahip_bam_merger_open); the rest is written on return: records and
+ * runs merged, bytes that went through tmp_dir, sort_ms = GPU time of the sort stage summed over the batches, merge_s = the merge
+ * (deflate and write included).  On failure of any stage every thread ends and the temporary files are gone. */
+typedef struct {
+	const char *tmp_dir; int64_t mem_budget;                                    /* in */
+	int64_t n_records, n_runs, spilled_bytes; double sort_ms, merge_s;         /* out */
+} bwahip_sort_t;
+int bwahip_stream_run_bam_sorted(bwahip_ctx *const *ctxs, int n_ctx, const bwahip_opt_t *opt, const bwahip_pestat_t *pes0, const char *fq1, const char *fq2,
+                                 int out_fd, const char *hdr_line, int level, bwahip_stream_t *st, bwahip_sort_t *so);
+
 /* Insert-size statistics (mem_pestat_t[4]: FF, FR, RF, RR; bwamem_pair.c:72) and mate-rescue counters ([0] local alignments
  * run, [1] regions added, [2] most alignments of one pair, [3] pairs that needed any; bwamem_pair.c:137) of the last
  * paired-end batch finalised on the GPU.  Either pointer may be NULL; counters4 receives 4 values. */
@@ -337,6 +398,11 @@ int bwahip_batch_sam(bwahip_ctx *ctx, char **out, int64_t *out_len, int64_t *off
  * other).  kernel_ms slots as for the SAM passes.  Names of 255 bytes or more: BWAHIP_EINVAL, judged by the name offsets. */
 int bwahip_batch_run_bam(bwahip_ctx *ctx, const bwahip_opt_t *opt, int64_t n_processed, const bwahip_pestat_t *pes0, float *kernel_ms, int n_kernel_ms);
 int bwahip_batch_bam(bwahip_ctx *ctx, uint8_t **out, int64_t *out_len, int64_t *off);
+/* The same pair with the records in coordinate order (bwahip_process_seqs_bam_sorted).  sort_ms4 (may be NULL): the sort stage of the run
+ * measured with HIP events -- [0] record table, [1] radix sort, [2] gather (milliseconds), [3] the number of radix passes that ran.
+ * bwahip_batch_bam_sorted: records, keys (*n_rec) and offsets (*n_rec + 1), each in a malloc()ed buffer. */
+int bwahip_batch_run_bam_sorted(bwahip_ctx *ctx, const bwahip_opt_t *opt, int64_t n_processed, const bwahip_pestat_t *pes0, float *kernel_ms, int n_kernel_ms, float *sort_ms4);
+int bwahip_batch_bam_sorted(bwahip_ctx *ctx, uint8_t **out, int64_t *out_len, uint64_t **keys, int64_t **rec_off, int64_t *n_rec);
 int bwahip_n_kernels(void);
 const char *bwahip_kernel_name(int i);
 /* Algorithmic work counters of the last bwahip_batch_run, counted on the device by the kernels
@@ -367,6 +433,12 @@ int bwahip_kat_ksw_extend(bwahip_ctx *ctx, int n, const int *params /*n x 10*/, 
  * mode 1: score descending, k64, qb).  idx_par / idx_seq: the two permutations; status2[0] = 1 when the parallel form ran to the end
  * (0: the introsort's depth limit -- it hands over to the one-lane form, idx_par is the identity), status2[1] != 0: internal error. */
 int bwahip_kat_introsort(bwahip_ctx *ctx, int n, int mode, const int64_t *k64, const int *score, const int *qb, int *idx_par, int *idx_seq, int *status2);
+
+/* The stable LSD radix sort of the coordinate-sorted BAM output (csrc/k_bamsort.hip) on caller keys: exactly the product's passes for
+ * keys of key_bits (1..64) significant bits -- 8 bits per pass, passes in which all keys agree skipped.  idx_out[i] = input position of
+ * the i-th key in sorted order, equal keys in input order; *tile_out (may be NULL): items one workgroup ranks per pass.  n <= 1 launches
+ * nothing. */
+int bwahip_kat_radix_sort(bwahip_ctx *ctx, int64_t n, const uint64_t *keys, int key_bits, uint32_t *idx_out, int *tile_out);
 
 /* ksw_align2 (ksw.c:343) on the device, byte or word kernel as xtra's KSW_XBYTE says.  params: n x 8 ints
  * (qlen, tlen, xtra, o_del, e_del, o_ins, e_ins, 0); mat25 NULL = the default 1/-4 matrix; out7: n x 7
