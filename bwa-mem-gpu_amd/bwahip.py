@@ -77,6 +77,10 @@ class SortStats(C.Structure):  # bwahip_sort_t
                 ("sort_ms", C.c_double), ("merge_s", C.c_double)]
 
 
+class BgzfStats(C.Structure):  # bwahip_bgzf_stats_t
+    _fields_ = [("raw_bytes", C.c_int64), ("bgzf_bytes", C.c_int64), ("n_blocks", C.c_int64), ("n_stored", C.c_int64), ("deflate_ms", C.c_double)]
+
+
 ERRORS = {0: "ok", -1: "EINVAL", -2: "ENODEV", -3: "ENOMEM", -4: "EIO", -5: "ECAPACITY", -6: "EINTERNAL"}
 
 STAGE_INTV, STAGE_CHAIN, STAGE_CHAIN_FLT, STAGE_REGS, STAGE_REGS_PRE, STAGE_SEEDS = 1, 2, 3, 4, 5, 6
@@ -140,6 +144,12 @@ def lib():
     L.bwahip_bam_merger_close.restype = None
     L.bwahip_stream_run_bam_sorted.argtypes = [C.POINTER(vp), C.c_int, C.POINTER(Opt), C.POINTER(PeStat), C.c_char_p, C.c_char_p, C.c_int, C.c_char_p, C.c_int,
                                                C.POINTER(StreamStats), C.POINTER(SortStats)]
+    L.bwahip_kat_bgzf.argtypes = [vp, vp, C.c_int64, vp, C.c_int64, i64p, i64p, i64p]
+    L.bwahip_process_seqs_bgzf.argtypes = [vp, C.POINTER(Opt), C.c_int64, C.c_int, C.POINTER(Seq), C.c_void_p, C.POINTER(vp), i64p, i64p, i64p]
+    L.bwahip_batch_run_bgzf.argtypes = [vp, C.POINTER(Opt), C.c_int64, C.POINTER(PeStat), C.POINTER(C.c_float), C.c_int, C.POINTER(C.c_float)]
+    L.bwahip_batch_bgzf.argtypes = [vp, C.POINTER(vp), i64p, i64p, i64p, i64p]
+    L.bwahip_stream_run_bam_dev.argtypes = [C.POINTER(vp), C.c_int, C.POINTER(Opt), C.POINTER(PeStat), C.c_char_p, C.c_char_p, C.c_int, C.c_char_p,
+                                            C.POINTER(StreamStats), C.POINTER(BgzfStats)]
     L.bwahip_kat_radix_sort.argtypes = [vp, C.c_int64, vp, C.c_int, vp, C.POINTER(C.c_int)]
     L.bwahip_fastq_open.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(vp)]
     L.bwahip_fastq_next.argtypes = [vp, C.c_int64, C.c_int, C.POINTER(C.POINTER(Seq)), C.POINTER(C.c_int)]
@@ -509,6 +519,20 @@ class Context:
         arr, keep = seq_array(names, seqs, quals, comments)
         return self.process_seqs_bam_sorted_array(arr, len(seqs), opt, n_processed, pes0)
 
+    def process_seqs_bgzf_array(self, arr, n, opt=None, n_processed=0, pes0=None):
+        """bwahip_process_seqs_bgzf on a bseq1_t array: (the BGZF members of the batch's BAM records as one bytes object, the uncompressed
+        bytes of the records, the number of members).  No file header, no end-of-file block."""
+        opt = opt or default_opt()
+        out, ln, raw, nb = C.c_void_p(), C.c_int64(), C.c_int64(), C.c_int64()
+        _check(lib().bwahip_process_seqs_bgzf(self._h, C.byref(opt), n_processed, n, arr, pes0, C.byref(out), C.byref(ln), C.byref(raw), C.byref(nb)),
+               "bwahip_process_seqs_bgzf")
+        return big_bytes(out, ln.value), raw.value, nb.value
+
+    def process_seqs_bgzf(self, names, seqs, quals=None, opt=None, n_processed=0, pes0=None, comments=None):
+        """The same from lists of names / ASCII reads (/ qualities, comments)."""
+        arr, keep = seq_array(names, seqs, quals, comments)
+        return self.process_seqs_bgzf_array(arr, len(seqs), opt, n_processed, pes0)
+
     def last_pe_stats(self):
         """(pestat[4] as dicts, mate-rescue alignments run on the GPU, regions they added) of the last PE batch."""
         pes = (PeStat * 4)()
@@ -582,6 +606,35 @@ class Context:
         for p in (out, keys, off):
             _free(p)
         return rec, k, o
+
+    def batch_run_bgzf(self, opt=None, n_processed=0, pes0=None):
+        """batch_run_bam with the records deflated into BGZF members on the GPU (they stay in HBM); the stage milliseconds gain
+        `deflate`, the deflate stage by HIP events."""
+        opt = opt or default_opt()
+        nk = lib().bwahip_n_kernels()
+        ms, dm = (C.c_float * nk)(), C.c_float()
+        _check(lib().bwahip_batch_run_bgzf(self._h, C.byref(opt), n_processed, pes0, ms, nk, C.byref(dm)), "bwahip_batch_run_bgzf")
+        d = {lib().bwahip_kernel_name(i).decode(): float(ms[i]) for i in range(nk)}
+        d["deflate"] = float(dm.value)
+        return d
+
+    def batch_bgzf(self):
+        """(members, uncompressed bytes, members, stored members) of the last batch_run_bgzf."""
+        out, ln, raw, nb, ns = C.c_void_p(), C.c_int64(), C.c_int64(), C.c_int64(), C.c_int64()
+        _check(lib().bwahip_batch_bgzf(self._h, C.byref(out), C.byref(ln), C.byref(raw), C.byref(nb), C.byref(ns)), "bwahip_batch_bgzf")
+        data = big_bytes(out, ln.value)
+        _free(out)
+        return data, raw.value, nb.value, ns.value
+
+    def kat_bgzf(self, data):
+        """(members, n_blocks, n_stored): the product's deflate stage (csrc/k_bgzf.hip) on these bytes, cut every 65 280."""
+        data = bytes(data)
+        cap = max(1, (len(data) + 65279) // 65280 * 65536)
+        out = np.empty(cap, dtype=np.uint8)
+        src = np.frombuffer(data, dtype=np.uint8) if data else np.zeros(1, dtype=np.uint8)
+        ln, nb, ns = C.c_int64(), C.c_int64(), C.c_int64()
+        _check(lib().bwahip_kat_bgzf(self._h, src.ctypes.data, len(data), out.ctypes.data, cap if data else 0, C.byref(ln), C.byref(nb), C.byref(ns)), "bwahip_kat_bgzf")
+        return out[:ln.value].tobytes(), nb.value, ns.value
 
     def kat_radix_sort(self, keys, key_bits=64):
         """(permutation, tile): the product's stable radix sort on these uint64 keys; tile = items one workgroup ranks per pass."""
@@ -742,6 +795,21 @@ def stream_run_bam(ctxs, fq1, fq2=None, out_fd=-1, hdr_line=None, level=1, opt=N
     _check(lib().bwahip_stream_run_bam(arr, len(ctxs), C.byref(opt), C.byref(pes0) if pes0 is not None else None, os.fsencode(fq1),
                                        os.fsencode(fq2) if fq2 else None, out_fd, hdr_line, level, C.byref(st)), "bwahip_stream_run_bam")
     return st
+
+
+def stream_run_bam_dev(ctxs, fq1, fq2=None, out_fd=-1, hdr_line=None, opt=None, chunk_bases=0, max_reads=0, keep_comments=False,
+                       reader_threads=0, pes0=None):
+    """bwahip_stream_run_bam_dev: FASTQ files -> a BAM file on out_fd whose BGZF blocks are deflated and checksummed on the GPU.
+    Returns (StreamStats, BgzfStats)."""
+    opt = opt or default_opt()
+    st, bs = StreamStats(), BgzfStats()
+    st.chunk_bases, st.max_reads, st.keep_comments, st.reader_threads = chunk_bases, max_reads, int(keep_comments), reader_threads
+    arr = (C.c_void_p * len(ctxs))(*[c._h for c in ctxs])
+    if isinstance(hdr_line, str):
+        hdr_line = hdr_line.encode()
+    _check(lib().bwahip_stream_run_bam_dev(arr, len(ctxs), C.byref(opt), C.byref(pes0) if pes0 is not None else None, os.fsencode(fq1),
+                                           os.fsencode(fq2) if fq2 else None, out_fd, hdr_line, C.byref(st), C.byref(bs)), "bwahip_stream_run_bam_dev")
+    return st, bs
 
 
 def stream_run_bam_sorted(ctxs, fq1, fq2=None, out_fd=-1, hdr_line=None, level=1, opt=None, chunk_bases=0, max_reads=0, keep_comments=False,

@@ -94,6 +94,14 @@ struct BamSort {
 	void release() { for (DevBuf *b : { &raw, &rec_cnt, &rec_base, &keys[0], &keys[1], &idx[0], &idx[1], &off, &len, &len_sorted, &hist, &hist_base, &bits }) b->release(); }
 };
 
+// Working set of the deflate stage (k_bgzf.hip), one per context: a 64 KiB slot per BGZF block for the member as it is formed, the
+// members' lengths and their scan, per workgroup of the grid one word per input position (match candidate, then length and distance),
+// the count of blocks that left stored.
+struct Bgzf {
+	DevBuf slots, mlen, moff, md, cnt;
+	void release() { for (DevBuf *b : { &slots, &mlen, &moff, &md, &cnt }) b->release(); }
+};
+
 struct StreamPipe;                       // final_rt.hip: the second sets of batch buffers the stream driver's three stages work on
 
 struct bwahip_ctx {
@@ -101,6 +109,11 @@ struct bwahip_ctx {
 	BatchText batch_text;
 	bool want_sorted = false;            // run_final (BAM): the records leave in coordinate order (k_bamsort.hip), with their keys and offsets
 	BamSort bs;
+	bool want_bgzf = false;              // run_final (BAM): the records leave as BGZF members (k_bgzf.hip): written to bs.raw, deflated into d_sam
+	Bgzf bz;
+	DevBuf d_bgzf_tot;                   // the deflated batch in d_sam: [0] its bytes, [1] blocks that left stored (int64 each)
+	int64_t n_bgzf_blocks = 0;
+	hipEvent_t ev_bgzf[2] = {};          // around the deflate stage
 	DevBuf d_skeys, d_rec_off;           // the sorted batch: n_rec keys, n_rec + 1 offsets of the records in d_sam
 	int64_t n_rec = 0;
 	hipEvent_t ev_sort[4] = {};          // begin of the record table, of the radix sort, of the gather, and the end
@@ -174,6 +187,11 @@ int bam_sort_batch(bwahip_ctx *c, int n_reads, int64_t total);
 int bam_sort_radix(bwahip_ctx *c, int n, int key_bits, int *which);
 int bam_sort_iota(unsigned *idx, int n, hipStream_t st);
 int bam_sort_tile();
+// k_bgzf.hip: `len` bytes at d_in (HBM) as BGZF members, cut every 65 280 bytes, concatenated into out (grown here to the bound
+// len + 31 per block: a member is never longer than its stored form); tot[0] = the bytes of the members, tot[1] = members that are
+// stored (both int64, in HBM: nothing is awaited).  Queued on st; len == 0 launches nothing but sets tot.
+int bgzf_deflate(bwahip_ctx *c, const uint8_t *d_in, int64_t len, DevBuf &out, int64_t *tot_dev, hipStream_t st);
+inline int64_t bgzf_blocks(int64_t len) { return (len + 65279) / 65280; }
 int bam_check_reads(int n, const bwahip_seq_t *seqs);   // bam_host.cpp: BWAHIP_EINVAL (with a message naming the read) for a name or a comment BAM cannot hold
 void pipe_destroy(bwahip_ctx *c);                                                     // final_rt.hip: the stream driver's buffer sets
 int final_setup(bwahip_ctx *c);                                                       // contig name tables for the SAM kernels

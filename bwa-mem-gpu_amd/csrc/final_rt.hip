@@ -194,6 +194,8 @@ int run_final(bwahip_ctx *c, const bwahip_opt_t *opt, int64_t n_processed, const
 	const bool pe = (opt->flag & BWAHIP_F_PE) != 0;
 	c->total_sam = 0; c->total_tasks = 0; c->n_rec = 0;
 	const bool sorted = bam && c->want_sorted;                    // the records leave in coordinate order: written to a scratch buffer, sorted into d_sam
+	const bool bgzf = bam && c->want_bgzf && !sorted;             // the records leave as BGZF members: written to the same scratch buffer, deflated into d_sam
+	c->n_bgzf_blocks = 0;
 	if (n == 0) return 0;
 	if (pe && (n & 1)) return BWAHIP_EINVAL;
 	int rc;
@@ -304,9 +306,9 @@ int run_final(bwahip_ctx *c, const bwahip_opt_t *opt, int64_t n_processed, const
 	HIP_TRY(hipMemcpyAsync(&total, c->d_sam_off.as<int64_t>() + n, 8, hipMemcpyDeviceToHost, c->stream));
 	HIP_TRY(hipStreamSynchronize(c->stream));
 	c->total_sam = total;
-	if ((rc = c->d_sam.ensure((size_t)total + 64))) return rc;
+	if ((rc = c->d_sam.ensure((size_t)total + (bgzf ? (size_t)bgzf_blocks(total) * 31 : 0) + 64))) return rc;   // bgzf: the bound bgzf_deflate asks for
 	f.sam = c->d_sam.as<uint8_t>();
-	if (sorted) { if ((rc = c->bs.raw.ensure((size_t)total + 64))) return rc; f.sam = c->bs.raw.as<uint8_t>(); }
+	if (sorted || bgzf) { if ((rc = c->bs.raw.ensure((size_t)total + 64))) return rc; f.sam = c->bs.raw.as<uint8_t>(); }
 	if (c->want_host_sam_off) {                                 // bwahip_process_seqs: the offsets travel ahead of the write pass
 		c->h_sam_off.resize((size_t)n + 1);
 		HIP_TRY(hipMemcpyAsync(c->h_sam_off.data(), c->d_sam_off.p, (size_t)(n + 1) * 8, hipMemcpyDeviceToHost, c->stream));
@@ -319,6 +321,13 @@ int run_final(bwahip_ctx *c, const bwahip_opt_t *opt, int64_t n_processed, const
 	if ((rc = launch_out(f, true, c->sam_half_reads, n))) return rc;
 	if (timed) HIP_TRY(hipEventRecord(c->ev[19], c->stream));
 	if (sorted && (rc = bam_sort_batch(c, n, total))) return rc;
+	if (bgzf) {                                                   // the deflate stage, queued behind the write pass
+		for (auto &e : c->ev_bgzf) if (!e) HIP_TRY(hipEventCreate(&e));
+		if ((rc = c->d_bgzf_tot.ensure(16))) return rc;
+		HIP_TRY(hipEventRecord(c->ev_bgzf[0], c->stream));
+		if ((rc = bgzf_deflate(c, c->bs.raw.as<uint8_t>(), total, c->d_sam, c->d_bgzf_tot.as<int64_t>(), c->stream))) return rc;
+		HIP_TRY(hipEventRecord(c->ev_bgzf[1], c->stream));
+	}
 	if (timed) {
 		HIP_TRY(hipStreamSynchronize(c->stream));
 		if (sorted) for (int k = 0; k < 3; ++k) HIP_TRY(hipEventElapsedTime(&c->bs.ms[k], c->ev_sort[k], c->ev_sort[k + 1]));
@@ -467,10 +476,12 @@ static int stage_text(bwahip_ctx *c, int nt, int n, bwahip_seq_t *seqs, const Ba
 
 // what bwahip_process_seqs_bam_sorted hands out beside the record bytes
 struct SortedOut { const uint64_t **keys; const int64_t **rec_off; int64_t *n_rec; };
+// what bwahip_process_seqs_bgzf hands out beside the members
+struct BgzfOut { int64_t *raw_len, *n_blocks; };
 
 // text != nullptr: the batch's SAM stays one piece (in the context's pinned buffer) instead of being cut into per-read strings
 static int process_seqs_impl(bwahip_ctx *ctx, const bwahip_opt_t *opt, int64_t n_processed, int n, bwahip_seq_t *seqs, const bwahip_pestat_t *pes0,
-                             const char **text_out, int64_t *len_out, const int64_t **off_out, bool bam = false, const SortedOut *sorted = nullptr)
+                             const char **text_out, int64_t *len_out, const int64_t **off_out, bool bam = false, const SortedOut *sorted = nullptr, const BgzfOut *bz = nullptr)
 {
 	static const int64_t no_records[1] = { 0 };
 	if (sorted) { *sorted->keys = nullptr; *sorted->rec_off = no_records; *sorted->n_rec = 0; }
@@ -503,10 +514,24 @@ static int process_seqs_impl(bwahip_ctx *ctx, const bwahip_opt_t *opt, int64_t n
 	text_thread.join();
 	if (rc || (rc = rc_text)) return rc;
 	const double t2 = now();
-	ctx->want_host_sam_off = true; ctx->want_sorted = sorted != nullptr;
+	ctx->want_host_sam_off = true; ctx->want_sorted = sorted != nullptr; ctx->want_bgzf = bz != nullptr;
 	rc = run_final(ctx, opt, n_processed, pes0, false, bam);
-	ctx->want_host_sam_off = false; ctx->want_sorted = false;
+	ctx->want_host_sam_off = false; ctx->want_sorted = false; ctx->want_bgzf = false;
 	if (rc) return rc;
+	if (bz) {                                                     // the members in one piece, through the pinned buffers taken in turn
+		int64_t tot[2] = { 0, 0 };
+		HIP_TRY(hipMemcpyAsync(tot, ctx->d_bgzf_tot.p, 16, hipMemcpyDeviceToHost, ctx->stream));
+		HIP_TRY(hipStreamSynchronize(ctx->stream));
+		HostBuf &hb = (ctx->sam_flip ^= 1) ? ctx->h_sam2 : ctx->h_sam;
+		if ((rc = hb.ensure((size_t)tot[0] + 1))) return rc;
+		if (tot[0]) HIP_TRY(hipMemcpyAsync(hb.p, ctx->d_sam.p, (size_t)tot[0], hipMemcpyDeviceToHost, ctx->stream));
+		HIP_TRY(hipStreamSynchronize(ctx->stream));
+		HIP_TRY(hipStreamSynchronize(ctx->stream_copy));
+		par_for_chunks(n, nt, [&](int64_t b, int64_t e) { for (int64_t i = b; i < e; ++i) seqs[i].sam = nullptr; });
+		*text_out = (const char*)hb.p; *len_out = tot[0];
+		*bz->raw_len = ctx->total_sam; *bz->n_blocks = ctx->n_bgzf_blocks;
+		return 0;
+	}
 	if (sorted) {                                                 // records, keys and offsets in one piece each, through pinned buffers taken in turn
 		const int flip = (ctx->sam_flip ^= 1);
 		HostBuf &hb = flip ? ctx->h_sam2 : ctx->h_sam, &hk = ctx->h_skeys[flip], &ho = ctx->h_rec_off[flip];
@@ -621,6 +646,17 @@ extern "C" int bwahip_process_seqs_bam_sorted(bwahip_ctx *ctx, const bwahip_opt_
 	return process_seqs_impl(ctx, opt, n_processed, n, seqs, pes0, (const char**)bam, bam_len, nullptr, true, &so);
 }
 
+// bwahip_process_seqs_bam with the records leaving the GPU as BGZF members (k_bgzf.hip): *bgzf = the members of the batch's records, cut
+// every 65 280 bytes, concatenated -- no file header, no end-of-file block; *raw_len = the bytes of the records, *n_blocks = members.
+extern "C" int bwahip_process_seqs_bgzf(bwahip_ctx *ctx, const bwahip_opt_t *opt, int64_t n_processed, int n, bwahip_seq_t *seqs, const bwahip_pestat_t *pes0,
+                                        const uint8_t **bgzf, int64_t *bgzf_len, int64_t *raw_len, int64_t *n_blocks)
+{
+	if (!bgzf || !bgzf_len || !raw_len || !n_blocks) return BWAHIP_EINVAL;
+	*raw_len = 0; *n_blocks = 0;
+	const BgzfOut bz = { raw_len, n_blocks };
+	return process_seqs_impl(ctx, opt, n_processed, n, seqs, pes0, (const char**)bgzf, bgzf_len, nullptr, true, nullptr, &bz);
+}
+
 // Insert-size statistics (mem_pestat_t x 4: FF, FR, RF, RR) and mate-rescue counters ([0] Smith-Waterman alignments run on
 // the GPU, [1] regions they added, [2] most alignments of one pair, [3] pairs that needed any) of the last paired-end batch
 // finalised on the GPU.
@@ -703,6 +739,11 @@ struct PipeOut {
 	hipEvent_t ev_sort[4] = {};
 	int64_t n_rec = 0;
 	bool sorted = false;
+	// BGZF members (bam == 3): their total and the stored count in HBM, the events around the deflate stage, the records' bytes
+	DevBuf d_tot;
+	hipEvent_t ev_bgzf[2] = {};
+	int64_t raw_total = 0, n_blocks = 0, n_stored = 0;
+	bool bgzf = false;
 };
 
 } // namespace
@@ -748,6 +789,8 @@ void pipe_destroy(bwahip_ctx *c)
 		s.d_sam.release(); s.d_sam_off.release(); s.h_sam.release();
 		s.d_keys.release(); s.d_rec_off.release(); s.h_keys.release(); s.h_rec_off.release();
 		for (auto &e : s.ev_sort) if (e) (void)hipEventDestroy(e);
+		s.d_tot.release();
+		for (auto &e : s.ev_bgzf) if (e) (void)hipEventDestroy(e);
 		if (s.ev_written) (void)hipEventDestroy(s.ev_written);
 		if (s.ev_copied) (void)hipEventDestroy(s.ev_copied);
 	}
@@ -854,6 +897,7 @@ int pipe_compute(bwahip_ctx *c, int in, int out, const bwahip_opt_t *opt, int64_
 		std::swap(c->d_comments, s.any_comment ? s.d_comments : no_comments);   // a batch without comments: a null pointer tells the kernels
 		std::swap(c->d_sam, o.d_sam); std::swap(c->d_sam_off, o.d_sam_off);
 		std::swap(c->d_skeys, o.d_keys); std::swap(c->d_rec_off, o.d_rec_off); std::swap(c->ev_sort, o.ev_sort);
+		std::swap(c->d_bgzf_tot, o.d_tot); std::swap(c->ev_bgzf, o.ev_bgzf);
 		std::swap(c->n_reads, s.n); std::swap(c->max_len, s.max_len); std::swap(c->total_bases, s.total_bases);
 	};
 	exchange();
@@ -863,12 +907,13 @@ int pipe_compute(bwahip_ctx *c, int in, int out, const bwahip_opt_t *opt, int64_
 		if ((rc = launch_nt4(c->d_seq.as<uint8_t>(), c->total_bases, c->stream))) return rc;
 		if ((rc = run_pipeline(c, opt, false, false))) return rc;
 		if (t_hot_end) *t_hot_end = pipe_now();
-		c->want_host_sam_off = false; c->want_sorted = bam == 2;
+		c->want_host_sam_off = false; c->want_sorted = bam == 2; c->want_bgzf = bam == 3;
 		rc = run_final(c, opt, n_processed, pes0, false, bam != 0);
-		c->want_sorted = false;
+		c->want_sorted = false; c->want_bgzf = false;
 		if (rc) return rc;
 		HIP_TRY(hipEventRecord(o.ev_written, c->stream));
 		o.total = c->total_sam; o.n_rec = c->n_rec; o.sorted = bam == 2;
+		o.bgzf = bam == 3; o.raw_total = c->total_sam; o.n_blocks = c->n_bgzf_blocks;
 		return 0;
 	};
 	rc = body();
@@ -884,6 +929,13 @@ int pipe_stage_out(bwahip_ctx *c, int out, const char **text, int64_t *len, doub
 	// waiting on the host, not in the copy stream: the next batch's upload is queued there and must not stand behind this batch's kernels
 	HIP_TRY(hipEventSynchronize(o.ev_written));
 	if (t_kernels_end) *t_kernels_end = pipe_now();
+	if (o.bgzf) {                                                 // what travels is the members: their total was left in HBM by the deflate stage
+		int64_t tot[2] = { 0, 0 };
+		HIP_TRY(hipMemcpyAsync(tot, o.d_tot.p, 16, hipMemcpyDeviceToHost, c->stream_copy));
+		HIP_TRY(hipEventRecord(o.ev_copied, c->stream_copy));
+		HIP_TRY(hipEventSynchronize(o.ev_copied));
+		o.total = tot[0]; o.n_stored = tot[1];
+	}
 	int rc = o.h_sam.ensure((size_t)o.total + 1);
 	if (rc) return rc;
 	char *p = (char*)o.h_sam.p;
@@ -916,5 +968,17 @@ int pipe_stage_out_sorted(bwahip_ctx *c, int out, const uint64_t **keys, const i
 	HIP_TRY(hipEventSynchronize(o.ev_copied));
 	if (sort_ms) { float ms = 0; if (o.n_rec && o.ev_sort[0] && hipEventElapsedTime(&ms, o.ev_sort[0], o.ev_sort[3]) != hipSuccess) ms = 0; *sort_ms = ms; }
 	*keys = (const uint64_t*)o.h_keys.p; *rec_off = (const int64_t*)o.h_rec_off.p; *n_rec = o.n_rec;
+	return 0;
+}
+
+// After pipe_stage_out of a batch computed with bam == 3: the bytes of the records the members hold, the members, those that are stored,
+// and the GPU time of the deflate stage.
+int pipe_stage_out_bgzf(bwahip_ctx *c, int out, int64_t *raw_len, int64_t *n_blocks, int64_t *n_stored, double *deflate_ms)
+{
+	if (!c || !c->pipe || out < 0 || out >= PIPE_SETS || !raw_len || !n_blocks || !n_stored) return BWAHIP_EINVAL;
+	PipeOut &o = c->pipe->out[out];
+	if (!o.bgzf) return BWAHIP_EINVAL;
+	*raw_len = o.raw_total; *n_blocks = o.n_blocks; *n_stored = o.n_stored;
+	if (deflate_ms) { float ms = 0; if (o.ev_bgzf[0] && hipEventElapsedTime(&ms, o.ev_bgzf[0], o.ev_bgzf[1]) != hipSuccess) ms = 0; *deflate_ms = ms; }
 	return 0;
 }

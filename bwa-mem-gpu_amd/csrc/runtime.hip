@@ -368,6 +368,8 @@ void bwahip_destroy(bwahip_ctx *c)
 	c->bs.release(); c->d_skeys.release(); c->d_rec_off.release();
 	for (int k = 0; k < 2; ++k) { c->h_skeys[k].release(); c->h_rec_off[k].release(); }
 	for (auto &e : c->ev_sort) if (e) (void)hipEventDestroy(e);
+	c->bz.release(); c->d_bgzf_tot.release();
+	for (auto &e : c->ev_bgzf) if (e) (void)hipEventDestroy(e);
 	for (auto &e : c->ev) if (e) (void)hipEventDestroy(e);
 	if (c->stream) (void)hipStreamDestroy(c->stream);
 	if (c->stream2) (void)hipStreamDestroy(c->stream2);
@@ -885,6 +887,66 @@ int bwahip_batch_bam_sorted(bwahip_ctx *c, uint8_t **out, int64_t *out_len, uint
 	if (hipStreamSynchronize(c->stream) != hipSuccess) return bad(BWAHIP_ENODEV);
 	*out = buf; *out_len = nr ? c->total_sam : 0; *keys = k; *rec_off = o; *n_rec = nr;
 	return 0;
+}
+
+// bwahip_batch_run_bam with the records deflated into BGZF members on the GPU (k_bgzf.hip); they stay in HBM (bwahip_batch_bgzf downloads
+// them).  deflate_ms (may be NULL): the deflate stage of this run by HIP events.
+int bwahip_batch_run_bgzf(bwahip_ctx *c, const bwahip_opt_t *opt, int64_t n_processed, const bwahip_pestat_t *pes0, float *kernel_ms, int n_ms, float *deflate_ms)
+{
+	if (!c || !opt) return BWAHIP_EINVAL;
+	c->want_bgzf = true;
+	const int rc = bwahip_batch_run_bam(c, opt, n_processed, pes0, kernel_ms, n_ms);
+	c->want_bgzf = false;
+	if (!rc && deflate_ms) {
+		*deflate_ms = 0;
+		if (c->n_reads > 0 && c->ev_bgzf[0]) HIP_TRY(hipEventElapsedTime(deflate_ms, c->ev_bgzf[0], c->ev_bgzf[1]));
+	}
+	return rc;
+}
+
+// The members of the last bwahip_batch_run_bgzf in a malloc()ed buffer; *raw_len: the bytes of the records they hold, *n_blocks: members,
+// *n_stored: those that are stored (any of the three may be NULL)
+int bwahip_batch_bgzf(bwahip_ctx *c, uint8_t **out, int64_t *out_len, int64_t *raw_len, int64_t *n_blocks, int64_t *n_stored)
+{
+	if (!c || !out || !out_len) return BWAHIP_EINVAL;
+	HIP_TRY(hipSetDevice(c->device));
+	int64_t tot[2] = { 0, 0 };
+	if (c->n_reads > 0 && c->d_bgzf_tot.p) {
+		HIP_TRY(hipMemcpyAsync(tot, c->d_bgzf_tot.p, 16, hipMemcpyDeviceToHost, c->stream));
+		HIP_TRY(hipStreamSynchronize(c->stream));
+	}
+	uint8_t *buf = (uint8_t*)malloc((size_t)tot[0] + 1);
+	if (!buf) return BWAHIP_ENOMEM;
+	if (tot[0] && (hipMemcpyAsync(buf, c->d_sam.p, (size_t)tot[0], hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess)) { free(buf); return BWAHIP_ENODEV; }
+	*out = buf; *out_len = tot[0];
+	if (raw_len) *raw_len = c->n_reads > 0 ? c->total_sam : 0;
+	if (n_blocks) *n_blocks = c->n_reads > 0 ? c->n_bgzf_blocks : 0;
+	if (n_stored) *n_stored = tot[1];
+	return 0;
+}
+
+// Exactly the product's deflate stage (k_bgzf.hip) on caller bytes: the members of `len` bytes cut every 65 280, concatenated into out
+// (*out_len bytes); out_cap below n_blocks x 65 536: BWAHIP_ECAPACITY.  len == 0: no member, nothing is launched.
+int bwahip_kat_bgzf(bwahip_ctx *c, const void *data, int64_t len, uint8_t *out, int64_t out_cap, int64_t *out_len, int64_t *n_blocks, int64_t *n_stored)
+{
+	if (!c || len < 0 || (len && !data) || !out_len || !n_blocks || !n_stored) return BWAHIP_EINVAL;
+	*out_len = 0; *n_stored = 0;
+	*n_blocks = bgzf_blocks(len);
+	if (out_cap < *n_blocks * 65536) return BWAHIP_ECAPACITY;
+	if (len == 0) return 0;
+	if (!out) return BWAHIP_EINVAL;
+	HIP_TRY(hipSetDevice(c->device));
+	DevBuf din, dout, dtot;
+	int rc;
+	int64_t tot[2] = { 0, 0 };
+	if ((rc = upload(din, data, (size_t)len, c->stream)) || (rc = dtot.ensure(16)) || (rc = bgzf_deflate(c, din.as<uint8_t>(), len, dout, dtot.as<int64_t>(), c->stream))) goto done;
+	if (hipMemcpyAsync(tot, dtot.p, 16, hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) { rc = BWAHIP_ENODEV; goto done; }
+	if (tot[0] < 0 || tot[0] > out_cap) { rc = BWAHIP_EINTERNAL; goto done; }
+	if (hipMemcpyAsync(out, dout.p, (size_t)tot[0], hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) { rc = BWAHIP_ENODEV; goto done; }
+	*out_len = tot[0]; *n_stored = tot[1];
+done:
+	din.release(); dout.release(); dtot.release();
+	return rc;
 }
 
 // The records of the last bwahip_batch_run_bam, as bwahip_batch_sam hands out the text (no NUL is meaningful here)

@@ -48,7 +48,7 @@ struct Driver {
 	// writer side
 	std::mutex mu;
 	std::condition_variable cv_item, cv_done;
-	struct Item { const char *p; int64_t len; int ctx, out; const uint64_t *keys; const int64_t *rec_off; int64_t n_rec; };   // ctx / out: the output set the bytes sit in; keys, rec_off: coordinate-sorted BAM
+	struct Item { const char *p; int64_t len; int ctx, out; const uint64_t *keys; const int64_t *rec_off; int64_t n_rec; int64_t raw_len; };   // ctx / out: the output set the bytes sit in; keys, rec_off: coordinate-sorted BAM
 	std::map<int64_t, Item> ready;                               // finished batches waiting for their turn
 	int64_t written = 0;                                         // batches [0, written) are on the descriptor
 	int workers_left = 0;
@@ -60,6 +60,7 @@ struct Driver {
 	int bam = 0, level = 0, deflate_threads = 1;                 // bwahip_stream_run_bam: the batches' records go through the BGZF writer
 	bwahip_bam_merger *merger = nullptr;                         // bam == 2 (bwahip_stream_run_bam_sorted): every batch is a sorted run of the merger instead
 	double sort_ms = 0;
+	bwahip_bgzf_stats_t bz = { 0, 0, 0, 0, 0 };                  // bam == 3 (bwahip_stream_run_bam_dev): the batches arrive as BGZF members and are only written
 	int64_t sam_bytes = 0;
 	double t_last_write = 0, write_s = 0;
 
@@ -83,7 +84,7 @@ struct Driver {
 				const int r = bwahip_bam_merger_add(merger, written, (const uint8_t*)it.p, it.len, it.keys, it.rec_off, it.n_rec);
 				if (r) { fail(r); return; }
 				o = it.len;
-			} else if (bam) {
+			} else if (bam == 1) {
 				const int r = bwahip_bgzf_write(fd, it.p, it.len, level, deflate_threads);
 				if (r) { fail(r); return; }
 				o = it.len;
@@ -96,7 +97,7 @@ struct Driver {
 			int64_t seq_no;
 			{
 				std::lock_guard<std::mutex> lk(mu);
-				seq_no = written++; sam_bytes += it.len; t_last_write = now_s(); write_s += t_last_write - t0;
+				seq_no = written++; sam_bytes += bam == 3 ? it.raw_len : it.len; t_last_write = now_s(); write_s += t_last_write - t0;
 			}
 			cv_done.notify_all();
 			on_written(it, seq_no, t0, t_last_write);
@@ -120,9 +121,9 @@ Reaper g_reaper;
 // 2 = coordinate-sorted BAM: every batch leaves its context sorted and becomes a run of the merger (the batch number is the run number);
 // after the last batch: header, the merge of the runs through the BGZF writer, the EOF block
 static int stream_run(bwahip_ctx *const *ctxs, int n_ctx, const bwahip_opt_t *opt, const bwahip_pestat_t *pes0,
-                      const char *fq1, const char *fq2, int out_fd, bwahip_stream_t *st, int bam, const char *hdr_line, int level, bwahip_sort_t *so = nullptr)
+                      const char *fq1, const char *fq2, int out_fd, bwahip_stream_t *st, int bam, const char *hdr_line, int level, bwahip_sort_t *so = nullptr, bwahip_bgzf_stats_t *bs = nullptr)
 {
-	if (!ctxs || n_ctx < 1 || n_ctx > 256 || !opt || !fq1 || !st || (bam == 2 && !so)) return BWAHIP_EINVAL;
+	if (!ctxs || n_ctx < 1 || n_ctx > 256 || !opt || !fq1 || !st || (bam == 2 && !so) || (bam == 3 && !bs)) return BWAHIP_EINVAL;
 	for (int i = 0; i < n_ctx; ++i) if (!ctxs[i]) return BWAHIP_EINVAL;
 	if (bam && (level < 0 || level > 9)) return BWAHIP_EINVAL;
 	// actual_chunk_size (fastmap.c:304): -K when given, else chunk_size * n_threads
@@ -130,7 +131,8 @@ static int stream_run(bwahip_ctx *const *ctxs, int n_ctx, const bwahip_opt_t *op
 	bwahip_opt_t o = *opt;
 	if (fq2) o.flag |= BWAHIP_F_PE;
 	// opt->n_threads is the host-thread budget of the whole run; BAM: half of it deflates, the other half stages the batches
-	const int n_deflate = bam ? (opt->n_threads / 2 > 1 ? opt->n_threads / 2 : 1) : 0;
+	// (bam == 3: the GPU deflates, all of it stages)
+	const int n_deflate = bam && bam != 3 ? (opt->n_threads / 2 > 1 ? opt->n_threads / 2 : 1) : 0;
 	const int n_stage = bam && opt->n_threads > n_deflate ? opt->n_threads - n_deflate : opt->n_threads;
 	o.n_threads = n_stage / n_ctx > 1 ? n_stage / n_ctx : 1;
 	Driver d;
@@ -147,7 +149,7 @@ static int stream_run(bwahip_ctx *const *ctxs, int n_ctx, const bwahip_opt_t *op
 		if (hr) return hr;
 		d.merger = sorted.m;
 	}
-	if (bam == 1) {
+	if (bam == 1 || bam == 3) {
 		uint8_t *hdr = nullptr; int64_t hlen = 0;
 		int hr = bwahip_bam_header(bwahip_bns(ctxs[0]), hdr_line, &hdr, &hlen);
 		if (!hr) { hr = bwahip_bgzf_write(out_fd, hdr, hlen, level, 1); free(hdr); }
@@ -276,7 +278,15 @@ static int stream_run(bwahip_ctx *const *ctxs, int n_ctx, const bwahip_opt_t *op
 			const uint64_t *keys = nullptr; const int64_t *rec_off = nullptr; int64_t n_rec = 0;
 			double sort_ms = 0;
 			if (bam == 2) { const int r2 = pipe_stage_out_sorted(ctxs[w], j.out, &keys, &rec_off, &n_rec, &sort_ms); if (r2) { d.fail(r2); break; } }
-			{ std::lock_guard<std::mutex> lk(d.mu); d.ready[j.seq_no] = { sam, len, w, j.out, keys, rec_off, n_rec }; d.sort_ms += sort_ms; }
+			int64_t raw_len = len, n_blocks = 0, n_stored = 0;
+			double deflate_ms = 0;
+			if (bam == 3) { const int r3 = pipe_stage_out_bgzf(ctxs[w], j.out, &raw_len, &n_blocks, &n_stored, &deflate_ms); if (r3) { d.fail(r3); break; } }
+			{
+				std::lock_guard<std::mutex> lk(d.mu);
+				d.ready[j.seq_no] = { sam, len, w, j.out, keys, rec_off, n_rec, raw_len };
+				d.sort_ms += sort_ms;
+				if (bam == 3) { d.bz.raw_bytes += raw_len; d.bz.bgzf_bytes += len; d.bz.n_blocks += n_blocks; d.bz.n_stored += n_stored; d.bz.deflate_ms += deflate_ms; }
+			}
 			d.cv_item.notify_all();
 		}
 		// the buffers must outlive their write
@@ -313,6 +323,7 @@ static int stream_run(bwahip_ctx *const *ctxs, int n_ctx, const bwahip_opt_t *op
 	if (log)
 		fprintf(stderr, "[bwahip] stream: open %.1f ms, first batch in -> last SAM byte out %.1f ms, joining the threads %.1f ms, handing the reader to the closer %.1f ms\n",
 		        (t_start - t_call) * 1e3, (d.t_last_write - t_start) * 1e3, (t_joined - d.t_last_write) * 1e3, (now_s() - t_joined) * 1e3);
+	if (bs) *bs = d.bz;
 	st->n_reads = d.n_processed; st->n_batches = d.next_seq; st->sam_bytes = d.sam_bytes;
 	st->seconds = d.t_last_write - t_call; st->write_s = d.write_s;
 	for (int w = 0; w < n_ctx; ++w) { st->reader_wait_s += wait_s[w]; st->gpu_busy_s += busy_s[w]; }
@@ -338,4 +349,14 @@ extern "C" int bwahip_stream_run_bam_sorted(bwahip_ctx *const *ctxs, int n_ctx, 
                                             const char *fq1, const char *fq2, int out_fd, const char *hdr_line, int level, bwahip_stream_t *st, bwahip_sort_t *so)
 {
 	return stream_run(ctxs, n_ctx, opt, pes0, fq1, fq2, out_fd, st, 2, hdr_line, level, so);
+}
+
+// FASTQ files in -> a BAM file out with the BGZF blocks of the records made on the GPU (k_bgzf.hip): the header through the host writer,
+// every batch's members written as they come back, the end-of-file block; no deflate workers, all host threads stage
+extern "C" int bwahip_stream_run_bam_dev(bwahip_ctx *const *ctxs, int n_ctx, const bwahip_opt_t *opt, const bwahip_pestat_t *pes0,
+                                         const char *fq1, const char *fq2, int out_fd, const char *hdr_line, bwahip_stream_t *st, bwahip_bgzf_stats_t *bs)
+{
+	if (!bs) return BWAHIP_EINVAL;
+	memset(bs, 0, sizeof *bs);
+	return stream_run(ctxs, n_ctx, opt, pes0, fq1, fq2, out_fd, st, 3, hdr_line, 1, nullptr, bs);
 }

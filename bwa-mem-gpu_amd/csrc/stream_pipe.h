@@ -22,12 +22,15 @@ int pipe_stage_in(bwahip_ctx *c, int in, const bwahip_opt_t *opt, int n, const b
 // k_nt4_conv, the hot path and the finalisation of input set `in` into output set `out`; returns when the write pass is queued
 // (bam == 2: when the gather is queued; the sort stage awaits two small read-backs on the way, the record count and the bits that differ
 // between the keys, so the caller is held until the write pass has ended).
-int pipe_compute(bwahip_ctx *c, int in, int out, const bwahip_opt_t *opt, int64_t n_processed, const bwahip_pestat_t *pes0, int bam, double *t_hot_end);   // bam: 0 SAM text, 1 BAM records, 2 BAM records in coordinate order
+int pipe_compute(bwahip_ctx *c, int in, int out, const bwahip_opt_t *opt, int64_t n_processed, const bwahip_pestat_t *pes0, int bam, double *t_hot_end);   // bam: 0 SAM text, 1 BAM records, 2 BAM records in coordinate order, 3 BAM records as BGZF members (the deflate stage is queued behind the write pass)
 // Waits for the batch's kernels (*t_kernels_end; from here on the input set it used is free), then copies output set `out` to its pinned buffer:
 // *text stays valid until the set is handed to pipe_compute again.
 int pipe_stage_out(bwahip_ctx *c, int out, const char **text, int64_t *len, double *t_kernels_end);
 // After pipe_stage_out of a batch computed with bam == 2 (coordinate-sorted records): the records' keys and offsets, valid as long as the
 // text; *sort_ms: the GPU time of the sort stage (record table, radix sort, gather).
 int pipe_stage_out_sorted(bwahip_ctx *c, int out, const uint64_t **keys, const int64_t **rec_off, int64_t *n_rec, double *sort_ms);
+// After pipe_stage_out of a batch computed with bam == 3 (BGZF members, k_bgzf.hip): the uncompressed bytes of the records, the number of
+// members and of stored ones, and the GPU time of the deflate stage.
+int pipe_stage_out_bgzf(bwahip_ctx *c, int out, int64_t *raw_len, int64_t *n_blocks, int64_t *n_stored, double *deflate_ms);
 // buffers freed and allocated again since the library was loaded (DevBuf / HostBuf ::ensure)
 long pipe_realloc_count();

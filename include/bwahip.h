@@ -253,6 +253,14 @@ int  bwahip_process_seqs_text(bwahip_ctx *ctx, const bwahip_opt_t *opt, int64_t 
 int  bwahip_process_seqs_bam(bwahip_ctx *ctx, const bwahip_opt_t *opt, int64_t n_processed, int n, bwahip_seq_t *seqs,
                              const bwahip_pestat_t *pes0, const uint8_t **bam, int64_t *bam_len, const int64_t **off);
 
+/* bwahip_process_seqs_bam with the records leaving the GPU compressed: *bgzf = BGZF members (SAM specification 4.1) of the batch's
+ * records, deflated and checksummed on the GPU (csrc/k_bgzf.hip), concatenated in order -- the records are cut every 65 280 bytes
+ * exactly as bwahip_bgzf_write cuts them, regardless of record boundaries; no file header, no end-of-file block.  *raw_len = the
+ * bytes of the records, *n_blocks = the number of members.  Buffers, lifetimes and refusals as for bwahip_process_seqs_bam.  The
+ * same input gives the same bytes on every run and every context. */
+int  bwahip_process_seqs_bgzf(bwahip_ctx *ctx, const bwahip_opt_t *opt, int64_t n_processed, int n, bwahip_seq_t *seqs,
+                              const bwahip_pestat_t *pes0, const uint8_t **bgzf, int64_t *bgzf_len, int64_t *raw_len, int64_t *n_blocks);
+
 /* ---- BAM file pieces that need no device -----------------------------------------------------------------------------------
  * bwahip_bam_header: magic, l_text + text, n_ref, names and lengths in a malloc()ed buffer (free() it).  The text is what
  * bwa_print_sam_hdr (bwa.c:520) writes for bns and hdr_line: one @SQ line per contig (AH:* for ALT contigs) unless hdr_line
@@ -294,6 +302,18 @@ int bwahip_stream_run(bwahip_ctx *const *ctxs, int n_ctx, const bwahip_opt_t *op
  * write_s = deflate + write().  Of opt->n_threads, half deflate and the other half stage the batches. */
 int bwahip_stream_run_bam(bwahip_ctx *const *ctxs, int n_ctx, const bwahip_opt_t *opt, const bwahip_pestat_t *pes0,
                           const char *fq1, const char *fq2, int out_fd, const char *hdr_line, int level, bwahip_stream_t *st);
+
+/* bwahip_stream_run_bam with the BGZF blocks of the records made on the GPU: the same three-stage pipeline per context with the
+ * deflate stage queued behind the BAM write pass, so what comes back from a context is a batch's finished members (about a quarter
+ * of the bytes) and the writer only write()s them in input order.  The header goes through bwahip_bgzf_write at level 1, the
+ * end-of-file block last.  There are no deflate workers: all of opt->n_threads stage the batches.  st as for bwahip_stream_run_bam
+ * (sam_bytes = the uncompressed bytes of the records); *bs is written on return: raw_bytes (= st->sam_bytes), bgzf_bytes = the
+ * members' bytes (the file without header member and EOF block), members, members that left stored, and the GPU time of the deflate
+ * stage summed over the batches.  The file's bytes do not depend on the number of contexts or on thread counts.  Coordinate-sorted
+ * output is not offered here: its blocks are cut by the host merge (bwahip_stream_run_bam_sorted). */
+typedef struct { int64_t raw_bytes, bgzf_bytes, n_blocks, n_stored; double deflate_ms; } bwahip_bgzf_stats_t;
+int bwahip_stream_run_bam_dev(bwahip_ctx *const *ctxs, int n_ctx, const bwahip_opt_t *opt, const bwahip_pestat_t *pes0,
+                              const char *fq1, const char *fq2, int out_fd, const char *hdr_line, bwahip_stream_t *st, bwahip_bgzf_stats_t *bs);
 
 /* ---- coordinate-sorted BAM ---------------------------------------------------------------------------------------------------------
  * The order is `samtools sort`'s coordinate order with its ties made explicit:
@@ -403,6 +423,11 @@ int bwahip_batch_bam(bwahip_ctx *ctx, uint8_t **out, int64_t *out_len, int64_t *
  * bwahip_batch_bam_sorted: records, keys (*n_rec) and offsets (*n_rec + 1), each in a malloc()ed buffer. */
 int bwahip_batch_run_bam_sorted(bwahip_ctx *ctx, const bwahip_opt_t *opt, int64_t n_processed, const bwahip_pestat_t *pes0, float *kernel_ms, int n_kernel_ms, float *sort_ms4);
 int bwahip_batch_bam_sorted(bwahip_ctx *ctx, uint8_t **out, int64_t *out_len, uint64_t **keys, int64_t **rec_off, int64_t *n_rec);
+/* The same pair with the records as BGZF members (bwahip_process_seqs_bgzf); they stay in HBM until bwahip_batch_bgzf fetches them
+ * into a malloc()ed buffer.  deflate_ms (may be NULL): the deflate stage of the run measured with HIP events.  raw_len, n_blocks,
+ * n_stored (each may be NULL): the bytes of the records, the members, the members that are stored. */
+int bwahip_batch_run_bgzf(bwahip_ctx *ctx, const bwahip_opt_t *opt, int64_t n_processed, const bwahip_pestat_t *pes0, float *kernel_ms, int n_kernel_ms, float *deflate_ms);
+int bwahip_batch_bgzf(bwahip_ctx *ctx, uint8_t **out, int64_t *out_len, int64_t *raw_len, int64_t *n_blocks, int64_t *n_stored);
 int bwahip_n_kernels(void);
 const char *bwahip_kernel_name(int i);
 /* Algorithmic work counters of the last bwahip_batch_run, counted on the device by the kernels
@@ -439,6 +464,12 @@ int bwahip_kat_introsort(bwahip_ctx *ctx, int n, int mode, const int64_t *k64, c
  * the i-th key in sorted order, equal keys in input order; *tile_out (may be NULL): items one workgroup ranks per pass.  n <= 1 launches
  * nothing. */
 int bwahip_kat_radix_sort(bwahip_ctx *ctx, int64_t n, const uint64_t *keys, int key_bits, uint32_t *idx_out, int *tile_out);
+
+/* The deflate stage of the BGZF output (csrc/k_bgzf.hip) on caller bytes: exactly the product's kernels.  `len` bytes are cut every
+ * 65 280; out receives one complete member per block (18-byte header with BSIZE, a raw deflate stream -- a dynamic block, or the
+ * stored form where that is not larger --, CRC32, ISIZE; never more than 65 536 bytes), concatenated; *n_blocks members, *n_stored of
+ * them stored.  out_cap below n_blocks x 65 536: BWAHIP_ECAPACITY.  len == 0: no member, nothing is launched. */
+int bwahip_kat_bgzf(bwahip_ctx *ctx, const void *data, int64_t len, uint8_t *out, int64_t out_cap, int64_t *out_len, int64_t *n_blocks, int64_t *n_stored);
 
 /* ksw_align2 (ksw.c:343) on the device, byte or word kernel as xtra's KSW_XBYTE says.  params: n x 8 ints
  * (qlen, tlen, xtra, o_del, e_del, o_ins, e_ins, 0); mat25 NULL = the default 1/-4 matrix; out7: n x 7
