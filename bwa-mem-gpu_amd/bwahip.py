@@ -85,6 +85,10 @@ ERRORS = {0: "ok", -1: "EINVAL", -2: "ENODEV", -3: "ENOMEM", -4: "EIO", -5: "ECA
 
 STAGE_INTV, STAGE_CHAIN, STAGE_CHAIN_FLT, STAGE_REGS, STAGE_REGS_PRE, STAGE_SEEDS = 1, 2, 3, 4, 5, 6
 TAG_READ = 100
+# known-answer DP entries (bwahip.h): forms of bwahip_kat_ksw_global, CIGAR words per item, path bits of bwahip_kat_ksw_extend2
+KAT_GLOBAL_AUTO_SMALL, KAT_GLOBAL_AUTO_BIG, KAT_GLOBAL_SCORE_ONLY = 0, 1, 2
+KAT_MAX_CIGAR = 512
+KAT_EXT_ROWS1, KAT_EXT_ROWS2, KAT_EXT_ROWS3, KAT_EXT_ROWS4, KAT_EXT_SHORT, KAT_EXT_WIDE, KAT_EXT_BEYOND16 = 1, 2, 4, 8, 16, 32, 64
 
 
 class BwahipError(RuntimeError):
@@ -180,6 +184,8 @@ def lib():
     L.bwahip_kat_kmer_table.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_uint64)]
     L.bwahip_kat_extend.argtypes = [vp, C.c_int, vp, vp, vp]
     L.bwahip_kat_ksw_extend.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, vp]
+    L.bwahip_kat_ksw_extend2.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, vp, vp]
+    L.bwahip_kat_ksw_global.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp]
     L.bwahip_align_batch.argtypes = [vp, C.POINTER(Opt), C.c_int, C.POINTER(Seq), C.POINTER(AlnRegV)]
     L.bwahip_process_seqs.argtypes = [vp, C.POINTER(Opt), C.c_int64, C.c_int, C.POINTER(Seq), C.POINTER(PeStat)]
     L.bwahip_batch_download.argtypes = [vp, C.POINTER(AlnRegV)]
@@ -713,6 +719,33 @@ class Context:
         _check(lib().bwahip_kat_ksw_extend(self._h, len(params), params.ctypes.data, q.ctypes.data, qoff.ctypes.data, t.ctypes.data,
                                            toff.ctypes.data, out.ctypes.data), "bwahip_kat_ksw_extend")
         return out
+
+    def kat_ksw_extend2(self, params, mat, q, qoff, t, toff):
+        """ksw_extend2 at a given number of columns per lane (bwahip_kat_ksw_extend2); params n x 12 (qlen, tlen, w, h0, zdrop, end_bonus,
+        o_del, e_del, o_ins, e_ins, reverse, cpl), mat n x 25 -> n x 7 (six results, path mask KAT_EXT_*)."""
+        params = np.ascontiguousarray(params, dtype=np.int32).reshape(-1, 12)
+        mat = np.ascontiguousarray(mat, dtype=np.int8).reshape(-1, 25)
+        q, t = np.ascontiguousarray(q, dtype=np.uint8), np.ascontiguousarray(t, dtype=np.uint8)
+        qoff, toff = np.ascontiguousarray(qoff, dtype=np.int64), np.ascontiguousarray(toff, dtype=np.int64)
+        assert len(mat) == len(params) and len(qoff) == len(params) + 1 and len(toff) == len(params) + 1
+        out = np.zeros((len(params), 7), dtype=np.int32)
+        _check(lib().bwahip_kat_ksw_extend2(self._h, len(params), params.ctypes.data, mat.ctypes.data, q.ctypes.data, qoff.ctypes.data, t.ctypes.data,
+                                            toff.ctypes.data, out.ctypes.data), "bwahip_kat_ksw_extend2")
+        return out
+
+    def kat_ksw_global(self, params, mat, q, qoff, t, toff):
+        """ksw_global2 with CIGAR through the kernels' own code (bwahip_kat_ksw_global); params n x 10 (qlen, tlen, w, o_del, e_del, o_ins, e_ins,
+        reverse, form KAT_GLOBAL_*, cpl), mat n x 25 -> (n x 2 (score, n_cigar or -1), n x KAT_MAX_CIGAR words)."""
+        params = np.ascontiguousarray(params, dtype=np.int32).reshape(-1, 10)
+        mat = np.ascontiguousarray(mat, dtype=np.int8).reshape(-1, 25)
+        q, t = np.ascontiguousarray(q, dtype=np.uint8), np.ascontiguousarray(t, dtype=np.uint8)
+        qoff, toff = np.ascontiguousarray(qoff, dtype=np.int64), np.ascontiguousarray(toff, dtype=np.int64)
+        assert len(mat) == len(params) and len(qoff) == len(params) + 1 and len(toff) == len(params) + 1
+        out = np.zeros((len(params), 2), dtype=np.int32)
+        cig = np.zeros((len(params), KAT_MAX_CIGAR), dtype=np.uint32)
+        _check(lib().bwahip_kat_ksw_global(self._h, len(params), params.ctypes.data, mat.ctypes.data, q.ctypes.data, qoff.ctypes.data, t.ctypes.data,
+                                           toff.ctypes.data, out.ctypes.data, cig.ctypes.data), "bwahip_kat_ksw_global")
+        return out, cig
 
     def kat_ksw_align(self, params, q, qoff, t, toff, mat=None):
         """ksw_align2 on the device; params n x 8 (qlen, tlen, xtra, o_del, e_del, o_ins, e_ins, 0) -> n x 7."""

@@ -325,6 +325,15 @@ constexpr int BWAHIP_LOGTAB_N = 65536;
 
 int launch_kat_ksw(const DevOpt &opt, int n, const int *params, const uint8_t *q, const int64_t *qoff, const uint8_t *t, const int64_t *toff,
                    int *out6, hipStream_t st);
+// known-answer kernels of the two DP forms on caller-supplied pairs (bwahip_kat_ksw_global / bwahip_kat_ksw_extend2): the n items listed in
+// `items` of the caller's arrays; params: 10 (global) or 12 (extend) ints per item, mat: 25 bytes per item
+struct KatDp { int n; const int *items, *params; const int8_t *mat; const uint8_t *q; const int64_t *qoff; const uint8_t *t; const int64_t *toff; };
+int launch_kat_global(const KatDp &a, int form, int grid, uint8_t *big_z, unsigned *zslab, int *out2, uint32_t *cig_out, hipStream_t st);   // k_final.hip
+size_t kat_global_zslab_bytes();
+int kat_global_t_cap(int form);
+int launch_kat_global_score(const KatDp &a, int cpl, int *out2, hipStream_t st);   // k_extend.hip: wave_global_score<cpl>
+int launch_kat_ksw2(const KatDp &a, int cpl, int *out7, hipStream_t st);           // k_extend.hip: wave_extend<cpl> beside wave_extend_fit<cpl>
+int kat_ext_t_cap();
 int launch_kat_isort(int n, int mode, const void *keys16, int *idx_par, int *idx_seq, int *work, int *status, hipStream_t st);
 size_t kat_isort_work_ints(int n);
 int launch_kat_occ4(const DevIndex &ix, int n, const uint64_t *k, uint64_t *out, hipStream_t st);

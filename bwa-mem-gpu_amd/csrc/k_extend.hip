@@ -420,12 +420,16 @@ __device__ __forceinline__ int ext_rows(const Sw &sw, const uint8_t *q, int qs, 
 }
 
 // The driver: first row of ksw_extend2 (ksw.c:396-397), band clamp (ksw.c:399-407), then runs of rows in the window that fits.
-// Flanks of fewer than 64 bases keep the plain one-column-per-lane form (nothing to gain there); so do bands wider than WIN_MAX
-// columns (-w above 127) and scores that do not fit 16 bits.
-template <int CPL>
+// Flanks of fewer than 64 bases keep the plain one-column-per-lane form (nothing to gain there); so do bands that can grow wider than WIN_MAX
+// columns (-w above 126 on flanks of 256 bases and more) and scores that do not fit 16 bits.
+// TRACE (the known-answer kernel only; the extension kernels compile it out): *path collects which of the forms below the call went through
+enum { EXT_PATH_ROWS1 = 1, EXT_PATH_ROWS2 = 2, EXT_PATH_ROWS3 = 4, EXT_PATH_ROWS4 = 8, EXT_PATH_SHORT = 16, EXT_PATH_WIDE = 32, EXT_PATH_BEYOND16 = 64 };
+template <int CPL, bool TRACE = false>
 __device__ __forceinline__ int wave_extend_fit(const Sw &sw, const uint8_t *q, int qs, int qlen, const uint8_t *t, int ts, int tlen,
-                                               int w, int end_bonus, int zdrop, int h0, int &qle, int &tle, int &gtle, int &gscore, int &max_off, Work &wk, unsigned *s_he)
+                                               int w, int end_bonus, int zdrop, int h0, int &qle, int &tle, int &gtle, int &gscore, int &max_off, Work &wk, unsigned *s_he,
+                                               unsigned *path = nullptr)
 {
+	if (TRACE && qlen < 64) *path |= EXT_PATH_SHORT;
 	if (qlen < 64) return wave_extend<1>(sw, q, qs, qlen, t, ts, tlen, w, end_bonus, zdrop, h0, qle, tle, gtle, gscore, max_off, wk);
 #ifdef KEXT_NO_WINDOW
 	if (CPL > 2 && qlen < 128) return wave_extend<2>(sw, q, qs, qlen, t, ts, tlen, w, end_bonus, zdrop, h0, qle, tle, gtle, gscore, max_off, wk);
@@ -444,7 +448,13 @@ __device__ __forceinline__ int wave_extend_fit(const Sw &sw, const uint8_t *q, i
 		wc = wc < max_del ? wc : max_del;
 	}
 	const int end0 = qlen < wc + 1 ? qlen : wc + 1;              // row 0 reads columns [0, end0) and writes column end0
-	if (end0 + 1 > WIN_MAX - 8 || h0 + qlen * sw.mx >= 32760)     // (-w above 127, or scores beyond 16 bits: the plain form, every column a register)
+	// the live band of a row lies inside [i - w, i + w + 1] (ksw.c:428-430) and grows by one column on either side per row at most
+	// (ksw.c:466-469): after a row it spans up to 2w + 2 columns beyond its first, or the whole flank.  The widest window must hold that
+	// whatever the scores are -- with the band of the second try (-w doubled, bwamem.c:730) it does not on flanks of 256 bases and more
+	const int span = qlen < 2 * wc + 2 ? qlen : 2 * wc + 2;
+	if (TRACE && (end0 + 1 > WIN_MAX - 8 || span > WIN_MAX - 1)) *path |= EXT_PATH_WIDE;
+	if (TRACE && h0 + qlen * sw.mx >= 32760) *path |= EXT_PATH_BEYOND16;
+	if (end0 + 1 > WIN_MAX - 8 || span > WIN_MAX - 1 || h0 + qlen * sw.mx >= 32760)     // (-w above 126, or scores beyond 16 bits: the plain form, every column a register)
 		return wave_extend<CPL>(sw, q, qs, qlen, t, ts, tlen, w, end_bonus, zdrop, h0, qle, tle, gtle, gscore, max_off, wk);
 	ExtSt S;
 	S.i = 0; S.beg = 0; S.end = end0; S.best = h0; S.best_i = -1; S.best_j = -1; S.best_ie = -1; S.gscore = -1; S.max_off = 0;
@@ -452,6 +462,7 @@ __device__ __forceinline__ int wave_extend_fit(const Sw &sw, const uint8_t *q, i
 	while (S.i < tlen) {
 		const int width = S.end - S.beg + 1;
 		int st;
+		if (TRACE) *path |= width + 8 <= 64 ? EXT_PATH_ROWS1 : width + 8 <= 128 ? EXT_PATH_ROWS2 : (CPL <= 3 || width + 8 <= 192) ? EXT_PATH_ROWS3 : EXT_PATH_ROWS4;
 		if (width + 8 <= 64) st = ext_rows<1>(sw, q, qs, qlen, t, ts, tlen, wc, zdrop, h0, S, s_he, wk);
 		else if (width + 8 <= 128) st = ext_rows<2>(sw, q, qs, qlen, t, ts, tlen, wc, zdrop, h0, S, s_he, wk);
 		else if (CPL <= 3 || width + 8 <= 192) st = ext_rows<3>(sw, q, qs, qlen, t, ts, tlen, wc, zdrop, h0, S, s_he, wk);   // (CPL <= 3: flanks below 192 bases)
@@ -1221,6 +1232,69 @@ __global__ __launch_bounds__(64) void k_kat_ksw(DevOpt opt, int n, const int *pa
 	if (l == 0) { int *o = out6 + 6 * r; o[0] = sc; o[1] = qle; o[2] = tle; o[3] = gtle; o[4] = gscore; o[5] = max_off; }
 }
 
+// known-answer kernel: ksw_extend2 as the extension kernels instantiated for CPL columns per lane run it, on caller-supplied pairs with their own
+// matrix.  params per item: qlen, tlen, w, h0, zdrop, end_bonus, o_del, e_del, o_ins, e_ins, reverse (stride -1 on both sequences, as the left
+// extension reads them, bwamem.c:725-729), cpl.  out7: the six results, and the forms wave_extend_fit went through (EXT_PATH_*).
+template <int CPL>
+__global__ __launch_bounds__(64) void k_kat_ksw2(KatDp a, int *out7)
+{
+	__shared__ uint8_t s_q[MAXQ + 8];
+	__shared__ __attribute__((aligned(16))) uint8_t s_t[MAXT + 8];
+	__shared__ int8_t s_mat[32];
+	__shared__ __attribute__((aligned(16))) unsigned s_he_g[WIN_MAX + 128];   // as in the extension kernels
+	unsigned *const s_he = s_he_g + 64;
+	const int l = lane();
+	if ((int)blockIdx.x >= a.n) return;
+	const int r = a.items[blockIdx.x];
+	const int *p = a.params + 12 * r;
+	const int qlen = p[0], tlen = p[1];
+	if (qlen + 1 > 64 * CPL || qlen > MAXQ || tlen > MAXT) return;   // (the host refuses these)
+	const int8_t *mat = a.mat + 25 * r;
+	if (l < 25) s_mat[l] = mat[l];
+	for (int i = l; i < qlen; i += 64) { const uint8_t c = a.q[a.qoff[r] + i]; s_q[i] = c < 5 ? c : 4; }
+	for (int i = l; i < tlen; i += 64) { const uint8_t c = a.t[a.toff[r] + i]; s_t[i] = c < 5 ? c : 4; }
+	__syncthreads();
+	Sw sw; sw.mat = s_mat; sw.o_del = p[6]; sw.e_del = p[7]; sw.o_ins = p[8]; sw.e_ins = p[9];
+	sw.mx = wmax(l < 25 ? (int)mat[l] : 0); if (sw.mx < 0) sw.mx = 0;
+	const bool rev = p[10] != 0;
+	const uint8_t *qp = rev ? s_q + qlen - 1 : s_q, *tp = rev ? s_t + (tlen > 0 ? tlen - 1 : 0) : s_t;
+	const int st = rev ? -1 : 1;
+	int qle, tle, gtle, gscore, max_off;
+	Work wk = { 0, 0, 0 };
+	int sc = wave_extend<CPL>(sw, qp, st, qlen, tp, st, tlen, p[2], p[5], p[4], p[3], qle, tle, gtle, gscore, max_off, wk);
+	// what the extension kernels run must give the same six numbers as the plain form
+	int qle2, tle2, gtle2, gscore2, max_off2;
+	unsigned path = 0;
+	const int sc2 = wave_extend_fit<CPL, true>(sw, qp, st, qlen, tp, st, tlen, p[2], p[5], p[4], p[3], qle2, tle2, gtle2, gscore2, max_off2, wk, s_he, &path);
+	if (sc2 != sc || qle2 != qle || tle2 != tle || gtle2 != gtle || gscore2 != gscore || max_off2 != max_off) sc = -777777;
+	if (l == 0) { int *o = out7 + 7 * r; o[0] = sc; o[1] = qle; o[2] = tle; o[3] = gtle; o[4] = gscore; o[5] = max_off; o[6] = (int)path; }
+}
+
+// known-answer kernel: the score-only ksw_global2 of mem_patch_reg at CPL columns per lane.  params as for k_kat_global (k_final.hip); out2: score, 0
+template <int CPL>
+__global__ __launch_bounds__(64) void k_kat_global_score(KatDp a, int *out2)
+{
+	__shared__ uint8_t s_q[MAXQ + 8];
+	__shared__ __attribute__((aligned(16))) uint8_t s_t[MAXT + 8];
+	__shared__ int8_t s_mat[32];
+	const int l = lane();
+	if ((int)blockIdx.x >= a.n) return;
+	const int r = a.items[blockIdx.x];
+	const int *p = a.params + 10 * r;
+	const int qlen = p[0], tlen = p[1];
+	if (qlen + 1 > 64 * CPL || qlen > MAXQ || tlen > MAXT) return;   // (the host refuses these)
+	if (l < 25) s_mat[l] = a.mat[25 * r + l];
+	for (int i = l; i < qlen; i += 64) { const uint8_t c = a.q[a.qoff[r] + i]; s_q[i] = c < 5 ? c : 4; }
+	for (int i = l; i < tlen; i += 64) { const uint8_t c = a.t[a.toff[r] + i]; s_t[i] = c < 5 ? c : 4; }
+	__syncthreads();
+	Sw sw; sw.mat = s_mat; sw.o_del = p[3]; sw.e_del = p[4]; sw.o_ins = p[5]; sw.e_ins = p[6]; sw.mx = 0;
+	const bool rev = p[7] != 0;
+	Work wk = { 0, 0, 0 };
+	const int sc = rev ? wave_global_score<CPL>(sw, s_q + qlen - 1, -1, qlen, s_t + tlen - 1, -1, tlen, p[2], wk)
+	                   : wave_global_score<CPL>(sw, s_q, 1, qlen, s_t, 1, tlen, p[2], wk);
+	if (l == 0) { out2[2 * r] = sc; out2[2 * r + 1] = 0; }
+}
+
 // known-answer kernel: the wavefront's exact introsort (regsort_dev.h / isort_dev.h) beside the one-lane restatement of ksort.h on the same keys
 __global__ __launch_bounds__(64) void k_kat_isort(int n, int mode, const RegKey *keys, int *idx_par, int *idx_seq, int *work, int *status)
 {
@@ -1250,6 +1324,28 @@ int launch_kat_ksw(const DevOpt &opt, int n, const int *params, const uint8_t *q
 {
 	if (n <= 0) return 0;
 	hipLaunchKernelGGL(k_kat_ksw, dim3(n), dim3(64), 0, st, opt, n, params, q, qoff, t, toff, out6);
+	return hipGetLastError() == hipSuccess ? 0 : BWAHIP_ENODEV;
+}
+
+int kat_ext_t_cap() { return MAXT; }
+int launch_kat_ksw2(const KatDp &a, int cpl, int *out7, hipStream_t st)
+{
+	if (a.n <= 0) return 0;
+	if (cpl == 3) hipLaunchKernelGGL(k_kat_ksw2<3>, dim3(a.n), dim3(64), 0, st, a, out7);
+	else if (cpl == 4) hipLaunchKernelGGL(k_kat_ksw2<4>, dim3(a.n), dim3(64), 0, st, a, out7);
+	else if (cpl == 5) hipLaunchKernelGGL(k_kat_ksw2<5>, dim3(a.n), dim3(64), 0, st, a, out7);
+	else if (cpl == 11) hipLaunchKernelGGL(k_kat_ksw2<11>, dim3(a.n), dim3(64), 0, st, a, out7);
+	else return BWAHIP_EINVAL;
+	return hipGetLastError() == hipSuccess ? 0 : BWAHIP_ENODEV;
+}
+int launch_kat_global_score(const KatDp &a, int cpl, int *out2, hipStream_t st)
+{
+	if (a.n <= 0) return 0;
+	if (cpl == 3) hipLaunchKernelGGL(k_kat_global_score<3>, dim3(a.n), dim3(64), 0, st, a, out2);
+	else if (cpl == 4) hipLaunchKernelGGL(k_kat_global_score<4>, dim3(a.n), dim3(64), 0, st, a, out2);
+	else if (cpl == 5) hipLaunchKernelGGL(k_kat_global_score<5>, dim3(a.n), dim3(64), 0, st, a, out2);
+	else if (cpl == 11) hipLaunchKernelGGL(k_kat_global_score<11>, dim3(a.n), dim3(64), 0, st, a, out2);
+	else return BWAHIP_EINVAL;
 	return hipGetLastError() == hipSuccess ? 0 : BWAHIP_ENODEV;
 }
 

@@ -544,7 +544,10 @@ struct CigarLds { uint8_t *q, *t, *z; uint32_t *cig; uint8_t *md; int8_t *mat; i
 
 // One task: region `ar` of read r -> DevAln (+ CIGAR words and MD text appended to the pool).  BIG: window / matrix in the
 // workgroup's global slab.  Returns false when the task does not fit this variant (caller lists it for k_cigar_big).
-template <bool BIG, bool NODP = false, int CPLMAX = 11>
+// KAT (the known-answer kernel k_kat_global only; every `if (KAT)` is compiled out of the product's kernels): the caller has put the target into
+// m.t, the band of ksw_global2 is ar.w as it stands, and the task ends after one DP and its backtrack with the score and the number of CIGAR
+// words in *out and the words in m.cig.
+template <bool BIG, bool NODP = false, int CPLMAX = 11, bool KAT = false>
 __device__ __forceinline__ bool reg2aln(const FinLaunch &a, const FinReg &ar, int r, long long task_id, const CigarLds &m, int t_cap, size_t z_cap, DevAln *out)
 {
 	const int l = lane();
@@ -565,7 +568,7 @@ __device__ __forceinline__ bool reg2aln(const FinLaunch &a, const FinReg &ar, in
 	if (bad && l == 0) atomicExch(a.err, 31);
 	// reference span, one base per byte; for a reverse-strand hit query and reference are both read backwards (bwa.c:275-280)
 	__syncthreads();
-	for (int i = l; i < rlen; i += 64) m.t[i] = (uint8_t)ref_base(ix, rb + i);
+	if (!KAT) for (int i = l; i < rlen; i += 64) m.t[i] = (uint8_t)ref_base(ix, rb + i);
 	__syncthreads();
 	const uint8_t *qp = rev ? m.q + qe - 1 : m.q + qb; const int qs = rev ? -1 : 1;
 	const uint8_t *tp = rev ? m.t + rlen - 1 : m.t; const int ts = rev ? -1 : 1;
@@ -598,6 +601,7 @@ __device__ __forceinline__ bool reg2aln(const FinLaunch &a, const FinReg &ar, in
 			w = w < w2 ? w : w2;
 			const int min_w = dl + 3;
 			w = w > min_w ? w : min_w;
+			if (KAT) w = ar.w;
 			const int n_col = lq < 2 * w + 1 ? lq : 2 * w + 1;
 			const bool nib_z = 2 * w + 1 <= 64;                     // band of at most 64 diagonals: 4-bit cells, two rows per byte (wave_band_trace)
 			const bool nib2_z = !nib_z && 2 * w + 1 <= 128;          // up to 128: 4-bit cells, a lane's two diagonals per byte (wave_band_trace2)
@@ -675,11 +679,13 @@ __device__ __forceinline__ bool reg2aln(const FinLaunch &a, const FinReg &ar, in
 			n_cigar = nc;
 			wsync();
 		}
+		if (KAT) break;
 		if (score == last_sc || w2 == opt.w << 2) break;
 		last_sc = score;
 		w2 <<= 1;
 	} while (++it < 3 && score < ar.truesc - opt.a);
 	if (!fits) return false;
+	if (KAT) { if (l == 0) { out->score = score; out->n_cigar = n_cigar; } return true; }
 
 	// ---- NM and MD (bwa.c:309-339) on the raw CIGAR; for a reverse-strand hit the bases come out complemented ("TGCAN")
 	int md_len = 0, NM = 0;
@@ -833,6 +839,56 @@ __global__ __launch_bounds__(64) void k_cigar_big(FinLaunch a)
 	}
 }
 
+// known-answer kernel: ksw_global2 with CIGAR on caller-supplied pairs through reg2aln's own DP forms and backtrack (its KAT mode).  FORM 0: as
+// k_cigar holds a task (sequences in LDS, band cells in the workgroup's global slab; -1 for a band of more than 128 diagonals or a target beyond
+// CG_MAXT); FORM 1: as k_cigar_big does (target and backtrack cells in the workgroup's big slab).  A fixed grid takes the listed items in turn.
+// params per item: qlen, tlen, w, o_del, e_del, o_ins, e_ins, reverse (both sequences read backwards, bwa.c:275-280), form, cpl
+template <int FORM>
+__global__ __launch_bounds__(64) void k_kat_global(KatDp a, uint8_t *big_z, unsigned *zslab, int *out2, uint32_t *cig_out)
+{
+	__shared__ uint8_t s_q[CG_MAXQ + 8];
+	__shared__ uint8_t s_t[CG_MAXT + 8];
+	__shared__ uint8_t s_z[16];
+	__shared__ uint32_t s_cig[CG_MAXC];
+	__shared__ uint8_t s_md[16];
+	__shared__ int8_t s_mat[32];
+	__shared__ DevAln s_al;
+	const int l = lane();
+	uint8_t *slab = FORM == 1 ? big_z + (size_t)blockIdx.x * (CG_BIG_Z + CG_BIG_T + 64) : nullptr;
+	unsigned *zg = FORM == 0 ? zslab + (size_t)blockIdx.x * cigar_zslab_words(CG_MAXT) : nullptr;
+	uint8_t *const tt = FORM == 1 ? slab + CG_BIG_Z : s_t;
+	for (int it = (int)blockIdx.x; it < a.n; it += (int)gridDim.x) {
+		const int r = a.items[it];
+		const int *p = a.params + 10 * r;
+		const int qlen = p[0], tlen = p[1];
+		bool fits = false;
+		__syncthreads();
+		if (qlen >= 1 && qlen <= CG_MAXQ && tlen >= 1 && tlen <= (FORM == 1 ? CG_BIG_T : CG_MAXT)) {
+			for (int i = l; i < qlen; i += 64) { const uint8_t c = a.q[a.qoff[r] + i]; s_q[i] = c < 5 ? c : 4; }
+			for (int i = l; i < tlen; i += 64) { const uint8_t c = a.t[a.toff[r] + i]; tt[i] = c < 5 ? c : 4; }
+			if (l < 25) s_mat[l] = a.mat[25 * r + l];
+			__syncthreads();
+			// what reg2aln reads of its launch and its region: the gap costs, the strand (from rb against l_pac), the span and the band; a
+			// secondary region has no mapping quality to work out, and a score this low keeps the no-DP shortcut away
+			FinLaunch fa;
+			fa.opt.a = 1; fa.opt.w = 100; fa.opt.mat[0] = 1;
+			fa.opt.o_del = p[3]; fa.opt.e_del = p[4]; fa.opt.o_ins = p[5]; fa.opt.e_ins = p[6];
+			fa.ix.l_pac = (int64_t)1 << 40;
+			fa.off = a.qoff; fa.err = out2 + 2 * r; fa.logtab = nullptr;
+			FinReg ar;
+			ar.qb = 0; ar.qe = qlen; ar.rb = p[7] ? fa.ix.l_pac : 0; ar.re = ar.rb + tlen;
+			ar.w = p[2]; ar.truesc = -(1 << 24); ar.secondary = 0;
+			const CigarLds m = { s_q, tt, FORM == 1 ? slab : s_z, s_cig, s_md, s_mat, CG_MAXC, 16, zg };
+			if (FORM == 1) fits = reg2aln<true, false, 11, true>(fa, ar, r, 0, m, CG_BIG_T, CG_BIG_Z, &s_al);
+			else fits = reg2aln<false, false, 11, true>(fa, ar, r, 0, m, CG_MAXT, 0, &s_al);
+			wsync();
+		}
+		const int nc = fits ? s_al.n_cigar : -1;
+		if (l == 0) { out2[2 * r] = fits ? s_al.score : 0; out2[2 * r + 1] = nc; }
+		for (int i = l; i < nc; i += 64) cig_out[(size_t)r * CG_MAXC + i] = s_cig[i];
+	}
+}
+
 } // namespace
 
 int launch_mark_primary(const FinLaunch &a, bool plan, int n_listed, hipStream_t st)
@@ -852,6 +908,18 @@ int launch_task_fill(const FinLaunch &a, hipStream_t st)
 }
 
 size_t cigar_big_slab_bytes() { return CG_BIG_Z + CG_BIG_T + 64; }
+
+// form 0 / 1 (see k_kat_global); grid workgroups, each with a slab of kat_global_zslab_bytes() (form 0) or cigar_big_slab_bytes() (form 1)
+size_t kat_global_zslab_bytes() { return cigar_zslab_words(CG_MAXT) * 4; }
+int kat_global_t_cap(int form) { return form == 1 ? CG_BIG_T : CG_MAXT; }
+int launch_kat_global(const KatDp &a, int form, int grid, uint8_t *big_z, unsigned *zslab, int *out2, uint32_t *cig_out, hipStream_t st)
+{
+	static_assert(CG_MAXC == BWAHIP_KAT_MAX_CIGAR, "the known-answer entry hands out CG_MAXC words per item");
+	if (a.n <= 0) return 0;
+	if (form == 1) hipLaunchKernelGGL(k_kat_global<1>, dim3(grid), dim3(64), 0, st, a, big_z, zslab, out2, cig_out);
+	else hipLaunchKernelGGL(k_kat_global<0>, dim3(grid), dim3(64), 0, st, a, big_z, zslab, out2, cig_out);
+	return hipGetLastError() == hipSuccess ? 0 : BWAHIP_ENODEV;
+}
 
 // the two lists run side by side (st2 forks from st and joins it again): the no-DP tasks wait on memory, the DP tasks compute
 // grid of the DP kernel and the bytes of backtrack slabs it needs (run_final sizes FinLaunch::zslab with it)

@@ -1166,4 +1166,96 @@ done:
 	return rc;
 }
 
+// the sequences of the known-answer DP entries: offsets ascending and consistent with the lengths in params (stride ints per item)
+static bool kat_dp_offsets_ok(int n, const int *params, int stride, const int64_t *qoff, const int64_t *toff)
+{
+	if (qoff[0] < 0 || toff[0] < 0) return false;
+	for (int i = 0; i < n; ++i)
+		if (qoff[i + 1] - qoff[i] < params[stride * i] || toff[i + 1] - toff[i] < params[stride * i + 1]) return false;
+	return true;
+}
+
+int bwahip_kat_ksw_extend2(bwahip_ctx *c, int n, const int *params, const int8_t *mat25, const uint8_t *q, const int64_t *qoff, const uint8_t *t, const int64_t *toff, int *out7)
+{
+	if (!c || n < 0 || (n && (!params || !mat25 || !q || !qoff || !t || !toff || !out7))) return BWAHIP_EINVAL;
+	if (n == 0) return 0;
+	static const int cpls[4] = { 3, 4, 5, 11 };
+	std::vector<int> items[4];
+	for (int i = 0; i < n; ++i) {
+		const int *p = params + 12 * i;
+		int k = 0;
+		while (k < 4 && cpls[k] != p[11]) ++k;
+		if (k == 4 || p[0] < 0 || p[1] < 0 || p[2] < 0 || p[3] <= 0 || p[4] < 0 || p[6] < 0 || p[7] < 1 || p[8] < 0 || p[9] < 1 || (p[10] != 0 && p[10] != 1)) return BWAHIP_EINVAL;
+		if (p[0] > BWAHIP_MAX_READ_LEN || p[0] + 1 > 64 * p[11] || p[1] > kat_ext_t_cap() || p[3] > (1 << 20)) return BWAHIP_ECAPACITY;
+		items[k].push_back(i);
+	}
+	if (!kat_dp_offsets_ok(n, params, 12, qoff, toff)) return BWAHIP_EINVAL;
+	HIP_TRY(hipSetDevice(c->device));
+	DevBuf dp, dm, dq, dqo, dt, dto, dout, dit[4]; int rc;
+	if ((rc = upload(dp, params, (size_t)n * 48, c->stream)) || (rc = upload(dm, mat25, (size_t)n * 25, c->stream)) || (rc = upload(dq, q, (size_t)qoff[n], c->stream)) ||
+	    (rc = upload(dqo, qoff, (size_t)(n + 1) * 8, c->stream)) || (rc = upload(dt, t, (size_t)toff[n], c->stream)) || (rc = upload(dto, toff, (size_t)(n + 1) * 8, c->stream)) ||
+	    (rc = dout.ensure((size_t)n * 28))) goto done;
+	for (int k = 0; k < 4 && !rc; ++k) {
+		if (items[k].empty()) continue;
+		if ((rc = upload(dit[k], items[k].data(), items[k].size() * 4, c->stream))) break;
+		const KatDp a = { (int)items[k].size(), dit[k].as<int>(), dp.as<int>(), dm.as<int8_t>(), dq.as<uint8_t>(), dqo.as<int64_t>(), dt.as<uint8_t>(), dto.as<int64_t>() };
+		rc = launch_kat_ksw2(a, cpls[k], dout.as<int>(), c->stream);
+	}
+	if (!rc && hipMemcpyAsync(out7, dout.p, (size_t)n * 28, hipMemcpyDeviceToHost, c->stream) != hipSuccess) rc = BWAHIP_ENODEV;
+	if (hipStreamSynchronize(c->stream) != hipSuccess) rc = BWAHIP_ENODEV;
+done:
+	dp.release(); dm.release(); dq.release(); dqo.release(); dt.release(); dto.release(); dout.release();
+	for (int k = 0; k < 4; ++k) dit[k].release();
+	return rc;
+}
+
+int bwahip_kat_ksw_global(bwahip_ctx *c, int n, const int *params, const int8_t *mat25, const uint8_t *q, const int64_t *qoff, const uint8_t *t, const int64_t *toff,
+                          int *out2, uint32_t *cigar)
+{
+	if (!c || n < 0 || (n && (!params || !mat25 || !q || !qoff || !t || !toff || !out2 || !cigar))) return BWAHIP_EINVAL;
+	if (n == 0) return 0;
+	static const int cpls[4] = { 3, 4, 5, 11 };
+	std::vector<int> items[6];                               // [0] auto_small, [1] auto_big, [2..5] score_only at CPL 3, 4, 5, 11
+	for (int i = 0; i < n; ++i) {
+		const int *p = params + 10 * i;
+		const int dl = p[0] > p[1] ? p[0] - p[1] : p[1] - p[0];
+		int k = p[8];
+		if (k == BWAHIP_KAT_GLOBAL_SCORE_ONLY) {
+			int j = 0;
+			while (j < 4 && cpls[j] != p[9]) ++j;
+			if (j == 4) return BWAHIP_EINVAL;
+			k = 2 + j;
+		} else if (k != BWAHIP_KAT_GLOBAL_AUTO_SMALL && k != BWAHIP_KAT_GLOBAL_AUTO_BIG) return BWAHIP_EINVAL;
+		// the band forms need w >= |tlen - qlen|, as bwa_gen_cigar2 guarantees (bwa.c:293-300)
+		if (p[0] < 1 || p[1] < 1 || p[2] < 1 || p[2] < dl || p[3] < 0 || p[4] < 1 || p[5] < 0 || p[6] < 1 || (p[7] != 0 && p[7] != 1)) return BWAHIP_EINVAL;
+		if (p[0] > BWAHIP_MAX_READ_LEN || p[2] > (1 << 20) || p[1] > (k >= 2 ? kat_ext_t_cap() : kat_global_t_cap(1)) || (k >= 2 && p[0] + 1 > 64 * p[9])) return BWAHIP_ECAPACITY;
+		items[k].push_back(i);
+	}
+	if (!kat_dp_offsets_ok(n, params, 10, qoff, toff)) return BWAHIP_EINVAL;
+	HIP_TRY(hipSetDevice(c->device));
+	const int grid = 64;
+	DevBuf dp, dm, dq, dqo, dt, dto, dout, dcig, dslab, dit[6]; int rc;
+	if ((rc = upload(dp, params, (size_t)n * 40, c->stream)) || (rc = upload(dm, mat25, (size_t)n * 25, c->stream)) || (rc = upload(dq, q, (size_t)qoff[n], c->stream)) ||
+	    (rc = upload(dqo, qoff, (size_t)(n + 1) * 8, c->stream)) || (rc = upload(dt, t, (size_t)toff[n], c->stream)) || (rc = upload(dto, toff, (size_t)(n + 1) * 8, c->stream)) ||
+	    (rc = dout.ensure((size_t)n * 8)) || (rc = dcig.ensure((size_t)n * BWAHIP_KAT_MAX_CIGAR * 4))) goto done;
+	if (hipMemsetAsync(dcig.p, 0, (size_t)n * BWAHIP_KAT_MAX_CIGAR * 4, c->stream) != hipSuccess) { rc = BWAHIP_ENODEV; goto done; }
+	for (int k = 0; k < 6 && !rc; ++k) {
+		if (items[k].empty()) continue;
+		if ((rc = upload(dit[k], items[k].data(), items[k].size() * 4, c->stream))) break;
+		const KatDp a = { (int)items[k].size(), dit[k].as<int>(), dp.as<int>(), dm.as<int8_t>(), dq.as<uint8_t>(), dqo.as<int64_t>(), dt.as<uint8_t>(), dto.as<int64_t>() };
+		if (k >= 2) { rc = launch_kat_global_score(a, cpls[k - 2], dout.as<int>(), c->stream); continue; }
+		// one slab per workgroup; the two forms run one after the other on the stream, so the larger serves both
+		if ((rc = dslab.ensure((size_t)grid * (k == 1 ? cigar_big_slab_bytes() : kat_global_zslab_bytes())))) break;
+		rc = launch_kat_global(a, k, grid, dslab.as<uint8_t>(), dslab.as<unsigned>(), dout.as<int>(), dcig.as<uint32_t>(), c->stream);
+		if (!rc && hipStreamSynchronize(c->stream) != hipSuccess) rc = BWAHIP_ENODEV;   // (ensure may move the slab before the next form)
+	}
+	if (!rc && hipMemcpyAsync(out2, dout.p, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream) != hipSuccess) rc = BWAHIP_ENODEV;
+	if (!rc && hipMemcpyAsync(cigar, dcig.p, (size_t)n * BWAHIP_KAT_MAX_CIGAR * 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess) rc = BWAHIP_ENODEV;
+	if (hipStreamSynchronize(c->stream) != hipSuccess) rc = BWAHIP_ENODEV;
+done:
+	dp.release(); dm.release(); dq.release(); dqo.release(); dt.release(); dto.release(); dout.release(); dcig.release(); dslab.release();
+	for (int k = 0; k < 6; ++k) dit[k].release();
+	return rc;
+}
+
 } // extern "C"

@@ -453,6 +453,42 @@ int bwahip_kat_extend(bwahip_ctx *ctx, int n, const uint64_t *ik3, const int *is
 int bwahip_kat_ksw_extend(bwahip_ctx *ctx, int n, const int *params /*n x 10*/, const uint8_t *q, const int64_t *qoff,
                           const uint8_t *t, const int64_t *toff, int *out6 /*n x 6*/);
 
+/* ksw_extend2 (ksw.c:380) as the extension kernels compiled for `cpl` columns per lane run it: the plain form and the windowed one,
+ * which must agree (else score = -777777).  params: n x 12 ints (qlen, tlen, w, h0, zdrop, end_bonus, o_del, e_del, o_ins, e_ins,
+ * reverse, cpl); reverse = 1 reads both sequences backwards, as the left extension does; cpl is 3, 4, 5 or 11.  mat25: n x 25, one
+ * 5x5 matrix per item (the largest entry is taken from it as the kernels take it from the options).  out7: n x 7 (score, qle, tle,
+ * gtle, gscore, max_off, path), path = the forms the windowed driver went through, BWAHIP_KAT_EXT_* or-ed.
+ * BWAHIP_EINVAL: h0 <= 0, an unknown cpl, negative lengths or gap costs, an extension cost below 1, offsets shorter than the lengths;
+ * BWAHIP_ECAPACITY: qlen above BWAHIP_MAX_READ_LEN or qlen + 1 above 64 x cpl, tlen above the kernels' window in LDS (2124).  Nothing
+ * is launched then. */
+#define BWAHIP_KAT_EXT_ROWS1    1     /* windowed rows with 1 .. 4 columns per lane */
+#define BWAHIP_KAT_EXT_ROWS2    2
+#define BWAHIP_KAT_EXT_ROWS3    4
+#define BWAHIP_KAT_EXT_ROWS4    8
+#define BWAHIP_KAT_EXT_SHORT    16    /* flank below 64 bases: plain form, one column per lane */
+#define BWAHIP_KAT_EXT_WIDE     32    /* band too wide for the window: plain form */
+#define BWAHIP_KAT_EXT_BEYOND16 64    /* scores beyond 16 bits: plain form */
+int bwahip_kat_ksw_extend2(bwahip_ctx *ctx, int n, const int *params /*n x 12*/, const int8_t *mat25 /*n x 25*/, const uint8_t *q, const int64_t *qoff,
+                           const uint8_t *t, const int64_t *toff, int *out7 /*n x 7*/);
+
+/* ksw_global2 (ksw.c:504) with CIGAR through the code mem_reg2aln's kernels run (DP form by band and length, wavefront backtrack).
+ * params: n x 10 ints (qlen, tlen, w, o_del, e_del, o_ins, e_ins, reverse, form, cpl); reverse = 1 reads both sequences backwards, as
+ * for a reverse-strand hit (bwa.c:275-280).  form: AUTO_SMALL = what the ordinary CIGAR kernel takes (band forms on its global slab);
+ * AUTO_BIG = what the large-task kernel takes (band forms up to 128 diagonals, the row-wise form chosen by qlen above); SCORE_ONLY =
+ * the score-only DP of mem_patch_reg at cpl (3, 4, 5 or 11) columns per lane.  cpl is ignored by the first two.  mat25: n x 25.
+ * out2: n x 2 (score, n_cigar); n_cigar = -1 (score 0) when the item does not fit the form -- AUTO_SMALL: a band of more than 128
+ * diagonals or tlen above 1536; either: more than BWAHIP_KAT_MAX_CIGAR operations -- and 0 for SCORE_ONLY.  cigar: n x
+ * BWAHIP_KAT_MAX_CIGAR words, length << 4 | op as ksw.c:493 packs them, the rest zero.
+ * BWAHIP_EINVAL: an unknown form or (SCORE_ONLY) cpl, a length below 1, w below 1 or below |tlen - qlen| (the band forms rely on what bwa.c:293-300
+ * guarantees), a negative gap cost, an extension cost below 1; BWAHIP_ECAPACITY: qlen above BWAHIP_MAX_READ_LEN, tlen above 8192 (2124
+ * for SCORE_ONLY), or qlen + 1 above 64 x cpl for SCORE_ONLY.  Nothing is launched then. */
+#define BWAHIP_KAT_GLOBAL_AUTO_SMALL 0
+#define BWAHIP_KAT_GLOBAL_AUTO_BIG   1
+#define BWAHIP_KAT_GLOBAL_SCORE_ONLY 2
+#define BWAHIP_KAT_MAX_CIGAR 512
+int bwahip_kat_ksw_global(bwahip_ctx *ctx, int n, const int *params /*n x 10*/, const int8_t *mat25 /*n x 25*/, const uint8_t *q, const int64_t *qoff,
+                          const uint8_t *t, const int64_t *toff, int *out2 /*n x 2*/, uint32_t *cigar /*n x BWAHIP_KAT_MAX_CIGAR*/);
+
 /* The region-list sorts (ks_introsort over mem_ars2 / mem_ars keys, bwamem.c:398-402, ksort.h:176) as the kernels run them: the whole
  * wavefront's exact form (csrc/isort_dev.h) and the one-lane restatement of ksort.h on the same n keys {k64, score, qb} (mode 0: by k64;
  * mode 1: score descending, k64, qb).  idx_par / idx_seq: the two permutations; status2[0] = 1 when the parallel form ran to the end

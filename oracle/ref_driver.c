@@ -20,6 +20,8 @@
  *                                                ksw_global2 / ksw_align2
  *   katalign <out.bin> <n> <seed>                known answers: ksw_align2 under
  *                                                other matrices / gap costs / xtra
+ *   katdp  <out.bin> <n> <seed>                  known answers: ksw_extend2 / ksw_global2 over
+ *                                                the whole range of lengths, bands, matrices
  *
  * Dump format ("i64 records"): a stream of  [tag:i64][n:i64][n x i64].
  */
@@ -410,6 +412,81 @@ static int main_katalign(int argc, char **argv)
 	return 0;
 }
 
+/* ksw_extend2 (ksw.c:380) and ksw_global2 (ksw.c:504) over the whole range the device forms are written for: flanks of 1 to 700
+ * bases (half of the cases above 250, a quarter on the lengths where the device code changes form), bands from 0 to 400, h0 up
+ * to 5000 (with the 50/60 matrix: scores beyond 16 bits), z-drop from 0 to 1000, five matrices, five sets of gap costs (one with a
+ * free gap opening), 0 to 30 % errors, gaps of up to 40 bases, ambiguous bases.
+ * Records: qlen tlen w h0 zdrop end_bonus o_del e_del o_ins e_ins mat[25] q[qlen] t[tlen] | 6 results (TAG_KSW_EXT_W)
+ *          the same with w widened to admit the length difference, h0 = zdrop = end_bonus = 0 | score n_cigar cigar[] (TAG_KSW_GLB_W) */
+enum { TAG_KSW_EXT_W = 24, TAG_KSW_GLB_W = 25 };
+
+static void rand_pair_wide(int qlen, int tlen, int err_pct, int n_pct, uint8_t *q, uint8_t *t)
+{ /* target = copy of the query with substitutions, short indels and now and then a gap of up to 40 bases */
+	int i, j = 0;
+	for (i = 0; i < qlen; ++i) q[i] = (int)(rng() % 100) < n_pct ? 4 : (rng() & 3);
+	for (i = 0; i < tlen; ++i) {
+		int r = rng() % 100;
+		if (j >= qlen) { t[i] = rng() & 3; continue; }
+		if (r < err_pct) {
+			int kind = rng() % 8;
+			if (kind < 4) t[i] = (q[j] + 1 + rng() % 3) & 3, ++j;             /* substitution */
+			else if (kind < 6) t[i] = rng() & 3;                               /* base missing from the query */
+			else if (kind < 7) { j += 1 + rng() % 3; t[i] = j < qlen ? q[j] : (rng() & 3); ++j; }
+			else if ((rng() & 1) && tlen - i > 45) { int g = 1 + rng() % 40; while (g-- > 0 && i < tlen - 1) t[i++] = rng() & 3; t[i] = rng() & 3; } /* long gap in the query */
+			else { j += 1 + rng() % 40; t[i] = j < qlen ? q[j] : (rng() & 3); ++j; }                                                    /* long gap in the target */
+		} else t[i] = q[j++];
+		if ((int)(rng() % 100) < n_pct) t[i] = 4;
+	}
+}
+
+static int main_katdp(int argc, char **argv)
+{
+	static const int ab[5][2] = { {1, 4}, {2, 3}, {1, 1}, {3, 9}, {50, 60} };
+	static const int gaps[5][4] = { {6, 1, 6, 1}, {4, 2, 7, 1}, {1, 1, 1, 1}, {16, 1, 16, 1}, {0, 1, 0, 1} };
+	static const int ws[12] = { 0, 1, 2, 5, 20, 31, 32, 63, 64, 100, 127, 400 };
+	static const int zds[5] = { 0, 1, 10, 100, 1000 }, ebs[3] = { 0, 5, 50 };
+	static const int edge[12] = { 1, 2, 63, 64, 65, 127, 128, 191, 192, 255, 256, 700 };
+	FILE *out;
+	int i, n;
+	if (argc < 4) return 1;
+	out = fopen(argv[1], "wb");
+	n = atoi(argv[2]); rng_state = strtoull(argv[3], 0, 10);
+	for (i = 0; i < n; ++i) {
+		const int *sc = ab[rng() % 5], *g = gaps[rng() % 5];
+		int kind = rng() & 3;
+		int qlen = kind < 2 ? 251 + rng() % 450 : kind == 2 ? 1 + rng() % 250 : edge[rng() % 12];
+		int tlen = qlen - 40 + (int)(rng() % 121), err = (rng() & 3) ? rng() % 8 : rng() % 31, n_pct = (rng() & 7) == 0 ? 3 : 0;
+		int w = ws[rng() % 12], h0 = (rng() & 1) ? 1 + rng() % 5000 : 1 + rng() % 120, zdrop = zds[rng() % 5], end_bonus = ebs[rng() % 3];
+		int j, qle, tle, gtle, gscore, max_off, s, n_cigar = 0, wg;
+		uint32_t *cigar = 0;
+		int8_t mat[25];
+		uint8_t *q, *t;
+		i64v v = {0, 0, 0};
+		if (tlen < 1) tlen = 1;
+		if ((rng() & 31) == 0) n_pct = 100;                           /* nothing but ambiguous bases */
+		bwa_fill_scmat(sc[0], sc[1], mat);
+		q = malloc(qlen); t = malloc(tlen);
+		rand_pair_wide(qlen, tlen, err, n_pct, q, t);
+		push(&v, qlen); push(&v, tlen); push(&v, w); push(&v, h0); push(&v, zdrop); push(&v, end_bonus);
+		push(&v, g[0]); push(&v, g[1]); push(&v, g[2]); push(&v, g[3]);
+		for (j = 0; j < 25; ++j) push(&v, mat[j]);
+		for (j = 0; j < qlen; ++j) push(&v, q[j]);
+		for (j = 0; j < tlen; ++j) push(&v, t[j]);
+		s = ksw_extend2(qlen, q, tlen, t, 5, mat, g[0], g[1], g[2], g[3], w, end_bonus, zdrop, h0, &qle, &tle, &gtle, &gscore, &max_off);
+		push(&v, s); push(&v, qle); push(&v, tle); push(&v, gtle); push(&v, gscore); push(&v, max_off);
+		rec_write(out, TAG_KSW_EXT_W, v.n, v.a);
+		wg = w > abs(tlen - qlen) + 3 ? w : abs(tlen - qlen) + 3;    /* bwa.c:293-300: the band admits the length difference */
+		v.n = 35 + qlen + tlen; v.a[2] = wg; v.a[3] = v.a[4] = v.a[5] = 0;
+		s = ksw_global2(qlen, q, tlen, t, 5, mat, g[0], g[1], g[2], g[3], wg, &n_cigar, &cigar);
+		push(&v, s); push(&v, n_cigar);
+		for (j = 0; j < n_cigar; ++j) push(&v, cigar[j]);
+		rec_write(out, TAG_KSW_GLB_W, v.n, v.a);
+		free(cigar); free(v.a); free(q); free(t);
+	}
+	fclose(out);
+	return 0;
+}
+
 /* readfq <chunk_bases> <in1> [in2]: the batches the reference's bseq_read (bwa.c:191) cuts, one record per line as
  * name TAB comment-or-* TAB seq TAB qual-or-*, a line "#batch <n>" in front of every batch -- golden vectors for the product's
  * FASTA/FASTQ reader (csrc/fastq_reader.cpp) */
@@ -449,6 +526,7 @@ int main(int argc, char **argv)
 	if (strcmp(argv[1], "katfm") == 0) return main_katfm(argc - 1, argv + 1);
 	if (strcmp(argv[1], "katksw") == 0) return main_katksw(argc - 1, argv + 1);
 	if (strcmp(argv[1], "katalign") == 0) return main_katalign(argc - 1, argv + 1);
+	if (strcmp(argv[1], "katdp") == 0) return main_katdp(argc - 1, argv + 1);
 	if (strcmp(argv[1], "readfq") == 0) return main_readfq(argc - 1, argv + 1);
 	fprintf(stderr, "unknown sub-command '%s'\n", argv[1]);
 	return 1;

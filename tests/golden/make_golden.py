@@ -11,6 +11,7 @@ the outputs below are data (inputs + expected outputs), never reference source.
   tests/golden/se.stages.npz       per-read stage dump (intervals, chains, filtered chains, regions)
   tests/golden/kat_fm.npz, kat_ksw.npz   known answers for Occ/SA/extend and ksw_extend2/global2/align2
   tests/golden/kat_ksw_align.npz   ksw_align2 under other matrices / gap costs / xtra (word kernel as mem_seed_sw uses it)
+  tests/golden/kat_dp_wide.npz     ksw_extend2 / ksw_global2 over the whole range of lengths, bands, matrices, gap costs (`make_golden.py dpwide`)
   tests/golden/opt_<set>.sam.gz    SAM bodies of se.fq / pe_[12].fq under non-default options (common.GOLDEN_OPTION_SETS)
 
 `make_golden.py extras` writes only the last two groups (round 2 additions); the older files are left alone.
@@ -127,6 +128,16 @@ def extras():
     sh("ls", "-la", HERE)
 
 
+def dp_wide():
+    """kat_dp_wide.npz: 320 ksw_extend2 and 320 ksw_global2 records of `bwaref katdp` (oracle/ref_driver.c), each with its matrix -- flanks of 1
+    to 700 bases (half of them above 250), bands 0 to 400, h0 up to 5000, five matrices, five sets of gap costs.  Inputs and the
+    reference's outputs only."""
+    assert os.path.exists("/root/reference/bwamem.c") and os.access(REF, os.X_OK), "needs the reference build (make -C oracle ref)"
+    os.makedirs(TMP, exist_ok=True)
+    sh(REF, "katdp", f"{TMP}/kat_dp_wide.bin", "320", "17")
+    records_to_npz(f"{TMP}/kat_dp_wide.bin", f"{HERE}/kat_dp_wide.npz")
+
+
 def fastq_cases():
     """tests/golden/fastq: hand-made FASTA/FASTQ inputs and the batches the REFERENCE's bseq_read / kseq_read cut from them
     (`bwaref readfq`, oracle/ref_driver.c) -- the vectors of the product's reader (csrc/fastq_reader.cpp).  Deterministic: running it again
@@ -162,4 +173,4 @@ def fastq_cases():
 
 
 if __name__ == "__main__":
-    {"extras": extras, "fastq": fastq_cases}.get(sys.argv[1] if len(sys.argv) > 1 else "", main)()
+    {"extras": extras, "fastq": fastq_cases, "dpwide": dp_wide}.get(sys.argv[1] if len(sys.argv) > 1 else "", main)()

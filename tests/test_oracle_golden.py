@@ -138,6 +138,21 @@ def test_ksw_known_answers():
     assert all(c >= 100 for c in counts.values())
 
 
+def test_dp_wide_known_answers(built):
+    """ora_ksw_extend2 (six outputs) and ora_ksw_global2 (score and every CIGAR word) reproduce every reference-made record of
+    kat_dp_wide.npz: flanks up to 700 bases, bands 0 to 400, scores beyond 16 bits, five matrices, five sets of gap costs."""
+    import dp_kat
+    ora = dp_kat.Oracle()
+    ext, glb = dp_kat.load_records("kat_dp_wide.npz")
+    assert len(ext) >= 300 and len(glb) == len(ext)
+    assert sum(c.qlen > 250 for c in ext) * 3 >= len(ext)
+    assert sum(c.h0 + c.qlen * int(c.mat.max()) >= 32760 for c in ext) >= 10          # the device's 16-bit window cannot hold these
+    assert {int(c.mat[0]) for c in ext} == {1, 2, 3, 50} and sum(c.gaps[0] == 0 for c in ext) >= 20
+    assert sum(2 * c.w + 1 <= 64 for c in glb) >= 30 and sum(64 < 2 * c.w + 1 <= 128 for c in glb) >= 30 and sum(2 * c.w + 1 > 128 for c in glb) >= 30
+    for c in ext + glb:
+        assert ora.answer(c) == c.res, c
+
+
 def test_oracle_option_sweep_equals_reference_sam(gold):
     """The restatement under non-default options vs SAM the reference produced with the same options (opt_*.sam.gz),
     incl. -W on 600-700 base reads where mem_flt_chained_seeds (bwamem.c:605) really drops seeds."""

@@ -76,3 +76,23 @@ def test_option_sweep_pe(small_index, sweep_reads, name):
     flags = common.option_flags(name)
     _, f1, f2 = sweep_reads
     assert _sam(common.ORACLE, flags + [small_index["prefix"], f1, f2]) == _sam(common.BWAREF, flags + [small_index["prefix"], f1, f2])
+
+
+def test_dp_random_vs_reference(built, tmp_path):
+    """ora_ksw_extend2 / ora_ksw_global2 against the reference's ksw_extend2 / ksw_global2 on 20 000 random pairs of `bwaref katdp`
+    (flanks up to 700 bases, bands 0 to 400, h0 up to 5000, five matrices, five sets of gap costs, N's, gaps up to 40 bases): all six
+    outputs, the score and every CIGAR word."""
+    import numpy as np
+    import dp_kat
+    out = str(tmp_path / "dp.bin")
+    subprocess.check_call([common.BWAREF, "katdp", out, "20000", "4242"])
+    ora = dp_kat.Oracle()
+    n = {"ext": 0, "glb": 0}
+    beyond16 = 0
+    for tag, v in bw.parse_records(np.fromfile(out, dtype=np.int64)):
+        qlen, tlen = int(v[0]), int(v[1])
+        c = dp_kat.Case("ext" if tag == dp_kat.TAG_EXT_W else "glb", v[35:35 + qlen], v[35 + qlen:35 + qlen + tlen], v[2], v[6:10], v[10:35], v[3], v[4], v[5])
+        assert ora.answer(c) == [int(x) for x in v[35 + qlen + tlen:]], c
+        n[c.kind] += 1
+        beyond16 += c.kind == "ext" and c.h0 + c.qlen * int(c.mat.max()) >= 32760
+    assert n == {"ext": 20000, "glb": 20000} and beyond16 >= 100
