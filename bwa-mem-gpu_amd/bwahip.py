@@ -88,7 +88,7 @@ TAG_READ = 100
 # known-answer DP entries (bwahip.h): forms of bwahip_kat_ksw_global, CIGAR words per item, path bits of bwahip_kat_ksw_extend2
 KAT_GLOBAL_AUTO_SMALL, KAT_GLOBAL_AUTO_BIG, KAT_GLOBAL_SCORE_ONLY = 0, 1, 2
 KAT_MAX_CIGAR = 512
-KAT_EXT_ROWS1, KAT_EXT_ROWS2, KAT_EXT_ROWS3, KAT_EXT_ROWS4, KAT_EXT_SHORT, KAT_EXT_WIDE, KAT_EXT_BEYOND16 = 1, 2, 4, 8, 16, 32, 64
+KAT_EXT_ROWS1, KAT_EXT_ROWS2, KAT_EXT_ROWS3, KAT_EXT_ROWS4, KAT_EXT_SHORT, KAT_EXT_WIDE, KAT_EXT_BEYOND16, KAT_EXT_STOPPED = 1, 2, 4, 8, 16, 32, 64, 128
 
 
 class BwahipError(RuntimeError):
@@ -446,7 +446,9 @@ class Context:
         return parse_records(words)
 
     def tune(self, **kw):
-        """Set hand-off thresholds of the heavy-read kernels (bwahip_ctx_tune): intv_cap, smem_lanes, heavy_mult, ..."""
+        """Set hand-off thresholds of the heavy-read kernels (bwahip_ctx_tune): intv_cap, smem_lanes, heavy_mult, ...; and
+        ext_early_stop (default 1): ksw_extend2 ends once no later row can change its results; 0 = every row to the end, as the
+        reference (same results, more rows)."""
         for k, v in kw.items():
             _check(lib().bwahip_ctx_tune(self._h, k.encode(), int(v)), f"bwahip_ctx_tune({k})")
 
@@ -722,7 +724,8 @@ class Context:
 
     def kat_ksw_extend2(self, params, mat, q, qoff, t, toff):
         """ksw_extend2 at a given number of columns per lane (bwahip_kat_ksw_extend2); params n x 12 (qlen, tlen, w, h0, zdrop, end_bonus,
-        o_del, e_del, o_ins, e_ins, reverse, cpl), mat n x 25 -> n x 7 (six results, path mask KAT_EXT_*)."""
+        o_del, e_del, o_ins, e_ins, reverse, cpl), mat n x 25 -> n x 7 (six results, path mask KAT_EXT_*; KAT_EXT_STOPPED: the early
+        stop ended the loop -- the entry follows the context's ext_early_stop)."""
         params = np.ascontiguousarray(params, dtype=np.int32).reshape(-1, 12)
         mat = np.ascontiguousarray(mat, dtype=np.int8).reshape(-1, 25)
         q, t = np.ascontiguousarray(q, dtype=np.uint8), np.ascontiguousarray(t, dtype=np.uint8)

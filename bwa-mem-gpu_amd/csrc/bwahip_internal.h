@@ -187,6 +187,7 @@ struct ExtLaunch {
 	int subset;                                  // k_extend / k_dedup: 0 all reads, 1 the heavy ones (first two classes of the launch order), 2 the others; k_dedup 3: list 2
 	uint8_t *big_t;                              // BWAHIP_EXT_BIG_GRID slabs of BWAHIP_EXT_BIG_T + 64 bytes
 	int lds_window;                              // largest reference window k_extend keeps in LDS (<= its compiled MAXT)
+	int ext_early_stop;                          // ksw_extend2 ends once no later row can change its results (0: off)
 };
 constexpr int BWAHIP_EXT_BIG_GRID = 128, BWAHIP_EXT_BIG_T = 1 << 16;
 int launch_extend(const ExtLaunch &a, int max_len, hipStream_t st, hipStream_t st2, hipEvent_t fork, hipEvent_t join);
@@ -323,11 +324,11 @@ int launch_kat_align(const DevOpt &opt, int n, int byte_mode, const int *items, 
                      const uint8_t *t, const int64_t *toff, uint8_t *wsp, size_t wsp_stride, int *out7, hipStream_t st);
 constexpr int BWAHIP_LOGTAB_N = 65536;
 
-int launch_kat_ksw(const DevOpt &opt, int n, const int *params, const uint8_t *q, const int64_t *qoff, const uint8_t *t, const int64_t *toff,
+int launch_kat_ksw(const DevOpt &opt, int early_stop, int n, const int *params, const uint8_t *q, const int64_t *qoff, const uint8_t *t, const int64_t *toff,
                    int *out6, hipStream_t st);
 // known-answer kernels of the two DP forms on caller-supplied pairs (bwahip_kat_ksw_global / bwahip_kat_ksw_extend2): the n items listed in
 // `items` of the caller's arrays; params: 10 (global) or 12 (extend) ints per item, mat: 25 bytes per item
-struct KatDp { int n; const int *items, *params; const int8_t *mat; const uint8_t *q; const int64_t *qoff; const uint8_t *t; const int64_t *toff; };
+struct KatDp { int n; const int *items, *params; const int8_t *mat; const uint8_t *q; const int64_t *qoff; const uint8_t *t; const int64_t *toff; int early_stop = 0; };   // early_stop: the context's ext_early_stop (ksw_extend2 only)
 int launch_kat_global(const KatDp &a, int form, int grid, uint8_t *big_z, unsigned *zslab, int *out2, uint32_t *cig_out, hipStream_t st);   // k_final.hip
 size_t kat_global_zslab_bytes();
 int kat_global_t_cap(int form);

@@ -59,6 +59,7 @@ struct Knobs {
 	int rank_sort_min = 2;      // BWAHIP_RANK_SORT_MIN: dedup lists at least this long are sorted by the whole wavefront (shorter: the one-lane restatement of ks_introsort)
 	int spec_min_chains = 16;   // BWAHIP_SPEC_MIN_CHAINS: chains from which k_extend_spec extends ahead of time (0: off)
 	int ext_lds_window = 1 << 30;   // BWAHIP_EXT_LDS_WINDOW: reference windows above this go to k_extend_big (tests; default = the compiled LDS window)
+	int ext_early_stop = 1;     // BWAHIP_EXT_EARLY_STOP: ksw_extend2 ends once no later row can change its results (0: every row to the end, as the reference -- same results, more rows)
 	int gpu_final = 1;          // BWAHIP_GPU_FINAL: 0 = finalisation of single-end batches on host threads (host_final.cpp) instead of the GPU kernels
 	int gpu_pair = 1;           // BWAHIP_GPU_PAIR: 0 = paired-end batches finalised on host threads (mate rescue, pairing, SAM)
 	int verbose = 0;            // BWAHIP_VERBOSE
@@ -68,11 +69,12 @@ struct Knobs {
 	{
 		auto geti = [](const char *k, int &v) { if (const char *e = getenv(k)) v = atoi(e); };
 		geti("BWAHIP_INTV_CAP", intv_cap); geti("BWAHIP_SMEM_LANES", smem_lanes); geti("BWAHIP_HEAVY_MULT", heavy_mult); geti("BWAHIP_SA_INTV", sa_intv); geti("BWAHIP_KMER_K", kmer_k);
-		geti("BWAHIP_CHAIN_BIG_MIN", chain_big_min); geti("BWAHIP_CHAIN_MID_MAX", chain_mid_max); geti("BWAHIP_CHAIN_BIG_MAX", chain_big_max); geti("BWAHIP_CHAIN_GLB_GRID", chain_glb_grid); geti("BWAHIP_RANK_SORT_MIN", rank_sort_min); geti("BWAHIP_SPEC_MIN_CHAINS", spec_min_chains); geti("BWAHIP_EXT_LDS_WINDOW", ext_lds_window); geti("BWAHIP_GPU_FINAL", gpu_final); geti("BWAHIP_GPU_PAIR", gpu_pair);
+		geti("BWAHIP_CHAIN_BIG_MIN", chain_big_min); geti("BWAHIP_CHAIN_MID_MAX", chain_mid_max); geti("BWAHIP_CHAIN_BIG_MAX", chain_big_max); geti("BWAHIP_CHAIN_GLB_GRID", chain_glb_grid); geti("BWAHIP_RANK_SORT_MIN", rank_sort_min); geti("BWAHIP_SPEC_MIN_CHAINS", spec_min_chains); geti("BWAHIP_EXT_LDS_WINDOW", ext_lds_window); geti("BWAHIP_EXT_EARLY_STOP", ext_early_stop); geti("BWAHIP_GPU_FINAL", gpu_final); geti("BWAHIP_GPU_PAIR", gpu_pair);
 		verbose = getenv("BWAHIP_VERBOSE") != nullptr;
 		e2e_log = getenv("BWAHIP_E2E_LOG") != nullptr;
 		dump_ext = getenv("BWAHIP_DUMP_EXT");
 		if (intv_cap < 2) intv_cap = 2;
+		ext_early_stop = ext_early_stop != 0;
 	}
 };
 

@@ -35,15 +35,46 @@ constexpr int MAXT = BWAHIP_MAX_READ_LEN + 2 * 200 + 1024;   // reference window
 
 // per-wavefront work counters (all uniform; lane 0 adds them to the launch counters at the end)
 struct Work { unsigned long long cells; unsigned rows1, rowsN; };
+// which forms a call of wave_extend_fit<CPL, true> went through, and whether the early stop ended its loop (BWAHIP_KAT_EXT_*)
+enum { EXT_PATH_ROWS1 = 1, EXT_PATH_ROWS2 = 2, EXT_PATH_ROWS3 = 4, EXT_PATH_ROWS4 = 8, EXT_PATH_SHORT = 16, EXT_PATH_WIDE = 32, EXT_PATH_BEYOND16 = 64, EXT_PATH_STOPPED = 128 };
 
 // ---------------------------------------------------------------------------------------------------
 // ksw_extend2 (ksw.c:380).  q/t live in LDS and are read with a stride (+1 / -1) so the left extension
 // can run on the reversed sequences (bwamem.c:725-729) without copying.  Collective over the wavefront.
 // ---------------------------------------------------------------------------------------------------
+// Early stop ("ksw_extend2: rows that cannot matter").  After a row's shift Hs[] / E[] hold the reference's eh[].h / eh[].e.  With
+//     phi = max over columns j in [beg, qlen) of  max( eh[j].h ? eh[j].h + mx * (qlen - j) : 0,  eh[j].e ? eh[j].e + mx * (qlen - 1 - j) : 0 )
+// no H of any later row exceeds phi; once end == qlen, gscore >= 0, phi < gscore and phi <= best, no later row changes any of the six
+// results and the loop ends.  ext_stop_try is the scalar part (wavefront-uniform, no vector work): the knob (sw.stop), the two conditions,
+// and a bound phi cannot be below -- the row maximum m of column mj sits in eh[mj + 1].h, so phi >= m + mx * (qlen - 1 - mj) whenever
+// mj + 1 < qlen -- which keeps the reduction out of nearly every row it would fail in (all rows in which the best path is still
+// inside the query).  ext_stop_holds is the vector part: each lane's maximum over its own columns against the two limits, and one
+// ballot (phi is below a limit exactly when every lane's share of it is: no reduction is needed).
+__device__ __forceinline__ bool ext_stop_try(int stop, int end, int qlen, int gscore, int m, int mj, int mx)
+{
+	return stop && end == qlen && gscore >= 0 && (mj + 1 >= qlen || m + mx * (qlen - 1 - mj) < gscore);
+}
 template <int CPL>
+__device__ __forceinline__ bool ext_stop_holds(const int (&Hs)[CPL], const int (&E)[CPL], int j0, int beg, int qlen, int mx, int gscore, int best)
+{
+	int phi = 0;
+	asm volatile("" : "+v"(j0));                                 // the products below are invariant in the row loop: keeps them from being hoisted into registers that would then live through every row
+#pragma unroll
+	for (int c = 0; c < CPL; ++c) {
+		const int j = j0 + c;
+		const int ph = Hs[c] ? Hs[c] + mx * (qlen - j) : 0, pe = E[c] ? E[c] + mx * (qlen - 1 - j) : 0;
+		const int p = ph > pe ? ph : pe;
+		if (j >= beg && j < qlen) phi = phi > p ? phi : p;      // (eh[qlen] is no diagonal source: left out)
+	}
+	const int lim = gscore - 1 < best ? gscore - 1 : best;       // phi < gscore (strictly: a later row with an equal hend would move gtle, ksw.c:451) and phi <= best
+	return __ballot(phi > lim) == 0;
+}
+
+// TRACE (the known-answer kernel only): *path gets EXT_PATH_STOPPED when the early stop ended the loop
+template <int CPL, bool TRACE = false>
 __device__ int wave_extend(const Sw &sw, const uint8_t *q, int qs, int qlen, const uint8_t *t, int ts, int tlen,
                            int w, int end_bonus, int zdrop, int h0, int &qle, int &tle, int &gtle, int &gscore_, int &max_off_,
-                           Work &wk)
+                           Work &wk, unsigned *path = nullptr)
 {
 	const int l = lane(), j0 = l * CPL;
 	// every argument is wavefront-uniform, but it reaches here through per-lane loads: tell the compiler, so that the
@@ -172,6 +203,9 @@ __device__ int wave_extend(const Sw &sw, const uint8_t *q, int qs, int qlen, con
 		if (lz < nbeg) lz = nbeg - 1;
 		beg = nbeg;
 		end = lz + 2 < qlen ? lz + 2 : qlen;
+		if (ext_stop_try(sw.stop, end, qlen, gscore, m, mj, sw.mx)) {
+			if (ext_stop_holds<CPL>(Hs, E, j0, beg, qlen, sw.mx, gscore, best)) { if (TRACE) *path |= EXT_PATH_STOPPED; break; }
+		}
 	}
 	qle = best_j + 1; tle = best_i + 1; gtle = best_ie + 1; gscore_ = gscore; max_off_ = max_off;
 	return best;
@@ -276,9 +310,9 @@ __device__ __forceinline__ int first_row_h(int j, int qlen, int h0, int oe_ins, 
 }
 constexpr int WIN_MAX = 256;                                 // widest live band the windowed form takes (4 columns per lane)
 
-template <int CPL>
+template <int CPL, bool TRACE = false>
 __device__ __forceinline__ int ext_rows(const Sw &sw, const uint8_t *q, int qs, int qlen, const uint8_t *t, int ts, int tlen,
-                                     int w, int zdrop, int h0, ExtSt &S, unsigned *s_he, Work &wk)
+                                     int w, int zdrop, int h0, ExtSt &S, unsigned *s_he, Work &wk, unsigned *path = nullptr)
 {
 	const int l = lane();
 	qlen = __builtin_amdgcn_readfirstlane(qlen); tlen = __builtin_amdgcn_readfirstlane(tlen); w = __builtin_amdgcn_readfirstlane(w);
@@ -397,6 +431,11 @@ __device__ __forceinline__ int ext_rows(const Sw &sw, const uint8_t *q, int qs, 
 		if (lz < nbeg) lz = nbeg - 1;
 		beg = nbeg;
 		end = lz + 2 < qlen ? lz + 2 : qlen;
+		// the early stop, before the hand-over decision (a finished extension is not handed over); only while every column up to qlen - 1
+		// has a lane in this window
+		if (qlen - base <= 64 * CPL && ext_stop_try(sw.stop, end, qlen, gscore, m, mj, sw.mx)) {
+			if (ext_stop_holds<CPL>(Hs, E, j0, beg, qlen, sw.mx, gscore, best)) { if (TRACE) *path |= EXT_PATH_STOPPED; break; }
+		}
 		// the window: column `end` needs a lane (it grows by one column per row at most: old_end was inside), and a band that has become
 		// narrow enough for fewer columns per lane moves on to that instantiation (with slack, so that it does not come straight back)
 		if (end - base > 64 * CPL - 1 || (CPL > 1 && end - beg + 1 <= 64 * (CPL - 1) - 16)) {
@@ -423,14 +462,13 @@ __device__ __forceinline__ int ext_rows(const Sw &sw, const uint8_t *q, int qs, 
 // Flanks of fewer than 64 bases keep the plain one-column-per-lane form (nothing to gain there); so do bands that can grow wider than WIN_MAX
 // columns (-w above 126 on flanks of 256 bases and more) and scores that do not fit 16 bits.
 // TRACE (the known-answer kernel only; the extension kernels compile it out): *path collects which of the forms below the call went through
-enum { EXT_PATH_ROWS1 = 1, EXT_PATH_ROWS2 = 2, EXT_PATH_ROWS3 = 4, EXT_PATH_ROWS4 = 8, EXT_PATH_SHORT = 16, EXT_PATH_WIDE = 32, EXT_PATH_BEYOND16 = 64 };
 template <int CPL, bool TRACE = false>
 __device__ __forceinline__ int wave_extend_fit(const Sw &sw, const uint8_t *q, int qs, int qlen, const uint8_t *t, int ts, int tlen,
                                                int w, int end_bonus, int zdrop, int h0, int &qle, int &tle, int &gtle, int &gscore, int &max_off, Work &wk, unsigned *s_he,
                                                unsigned *path = nullptr)
 {
 	if (TRACE && qlen < 64) *path |= EXT_PATH_SHORT;
-	if (qlen < 64) return wave_extend<1>(sw, q, qs, qlen, t, ts, tlen, w, end_bonus, zdrop, h0, qle, tle, gtle, gscore, max_off, wk);
+	if (qlen < 64) return wave_extend<1, TRACE>(sw, q, qs, qlen, t, ts, tlen, w, end_bonus, zdrop, h0, qle, tle, gtle, gscore, max_off, wk, path);
 #ifdef KEXT_NO_WINDOW
 	if (CPL > 2 && qlen < 128) return wave_extend<2>(sw, q, qs, qlen, t, ts, tlen, w, end_bonus, zdrop, h0, qle, tle, gtle, gscore, max_off, wk);
 	if (CPL > 3 && qlen < 192) return wave_extend<3>(sw, q, qs, qlen, t, ts, tlen, w, end_bonus, zdrop, h0, qle, tle, gtle, gscore, max_off, wk);
@@ -455,7 +493,7 @@ __device__ __forceinline__ int wave_extend_fit(const Sw &sw, const uint8_t *q, i
 	if (TRACE && (end0 + 1 > WIN_MAX - 8 || span > WIN_MAX - 1)) *path |= EXT_PATH_WIDE;
 	if (TRACE && h0 + qlen * sw.mx >= 32760) *path |= EXT_PATH_BEYOND16;
 	if (end0 + 1 > WIN_MAX - 8 || span > WIN_MAX - 1 || h0 + qlen * sw.mx >= 32760)     // (-w above 126, or scores beyond 16 bits: the plain form, every column a register)
-		return wave_extend<CPL>(sw, q, qs, qlen, t, ts, tlen, w, end_bonus, zdrop, h0, qle, tle, gtle, gscore, max_off, wk);
+		return wave_extend<CPL, TRACE>(sw, q, qs, qlen, t, ts, tlen, w, end_bonus, zdrop, h0, qle, tle, gtle, gscore, max_off, wk, path);
 	ExtSt S;
 	S.i = 0; S.beg = 0; S.end = end0; S.best = h0; S.best_i = -1; S.best_j = -1; S.best_ie = -1; S.gscore = -1; S.max_off = 0;
 	S.max_end = -1; S.hi = -1;                                   // nothing in s_he yet: every column starts from the first row (ksw.c:396-397)
@@ -463,10 +501,10 @@ __device__ __forceinline__ int wave_extend_fit(const Sw &sw, const uint8_t *q, i
 		const int width = S.end - S.beg + 1;
 		int st;
 		if (TRACE) *path |= width + 8 <= 64 ? EXT_PATH_ROWS1 : width + 8 <= 128 ? EXT_PATH_ROWS2 : (CPL <= 3 || width + 8 <= 192) ? EXT_PATH_ROWS3 : EXT_PATH_ROWS4;
-		if (width + 8 <= 64) st = ext_rows<1>(sw, q, qs, qlen, t, ts, tlen, wc, zdrop, h0, S, s_he, wk);
-		else if (width + 8 <= 128) st = ext_rows<2>(sw, q, qs, qlen, t, ts, tlen, wc, zdrop, h0, S, s_he, wk);
-		else if (CPL <= 3 || width + 8 <= 192) st = ext_rows<3>(sw, q, qs, qlen, t, ts, tlen, wc, zdrop, h0, S, s_he, wk);   // (CPL <= 3: flanks below 192 bases)
-		else st = ext_rows<(CPL <= 3 ? 3 : 4)>(sw, q, qs, qlen, t, ts, tlen, wc, zdrop, h0, S, s_he, wk);
+		if (width + 8 <= 64) st = ext_rows<1, TRACE>(sw, q, qs, qlen, t, ts, tlen, wc, zdrop, h0, S, s_he, wk, path);
+		else if (width + 8 <= 128) st = ext_rows<2, TRACE>(sw, q, qs, qlen, t, ts, tlen, wc, zdrop, h0, S, s_he, wk, path);
+		else if (CPL <= 3 || width + 8 <= 192) st = ext_rows<3, TRACE>(sw, q, qs, qlen, t, ts, tlen, wc, zdrop, h0, S, s_he, wk, path);   // (CPL <= 3: flanks below 192 bases)
+		else st = ext_rows<(CPL <= 3 ? 3 : 4), TRACE>(sw, q, qs, qlen, t, ts, tlen, wc, zdrop, h0, S, s_he, wk, path);
 		wsync();
 		if (!st) break;
 	}
@@ -598,7 +636,7 @@ __global__ __launch_bounds__(64, (CPL <= 3 ? KEXT_W3 : CPL == 4 ? 4 : 1)) void k
 	const int l = lane();
 	const DevOpt &opt = a.opt;
 	const DevIndex &ix = a.ix;
-	Sw sw; sw.mat = s_mat; sw.o_del = opt.o_del; sw.e_del = opt.e_del; sw.o_ins = opt.o_ins; sw.e_ins = opt.e_ins;
+	Sw sw; sw.mat = s_mat; sw.o_del = opt.o_del; sw.e_del = opt.e_del; sw.o_ins = opt.o_ins; sw.e_ins = opt.e_ins; sw.stop = a.ext_early_stop;
 	if (l < 25) s_mat[l] = opt.mat[l];
 	sw.mx = wmax(l < 25 ? (int)opt.mat[l] : 0); if (sw.mx < 0) sw.mx = 0;
 	Work wk = { 0, 0, 0 };
@@ -749,7 +787,7 @@ __device__ __forceinline__ void extend_read(const ExtLaunch &a, const int r, uin
 	int n_av = 0;
 	Work wk = { 0, 0, 0 };
 	const unsigned long long t_0 = wall_clock64();
-	Sw sw; sw.mat = s_mat; sw.o_del = opt.o_del; sw.e_del = opt.e_del; sw.o_ins = opt.o_ins; sw.e_ins = opt.e_ins;
+	Sw sw; sw.mat = s_mat; sw.o_del = opt.o_del; sw.e_del = opt.e_del; sw.o_ins = opt.o_ins; sw.e_ins = opt.e_ins; sw.stop = a.ext_early_stop;
 	__syncthreads();
 	if (l < 25) s_mat[l] = opt.mat[l];
 	sw.mx = wmax(l < 25 ? (int)opt.mat[l] : 0); if (sw.mx < 0) sw.mx = 0;
@@ -1204,7 +1242,7 @@ __global__ void k_order_place(int n, const int *kept_seeds, int t0, int t1, int 
 }
 
 // known-answer kernel: ksw_extend2 on caller-supplied pairs (params per item: qlen,tlen,w,h0,zdrop,end_bonus,o_del,e_del,o_ins,e_ins)
-__global__ __launch_bounds__(64) void k_kat_ksw(DevOpt opt, int n, const int *params, const uint8_t *q, const int64_t *qoff,
+__global__ __launch_bounds__(64) void k_kat_ksw(DevOpt opt, int early_stop, int n, const int *params, const uint8_t *q, const int64_t *qoff,
                                                 const uint8_t *t, const int64_t *toff, int *out6)
 {
 	__shared__ uint8_t s_q[MAXQ + 8];
@@ -1220,7 +1258,7 @@ __global__ __launch_bounds__(64) void k_kat_ksw(DevOpt opt, int n, const int *pa
 	for (int i = l; i < qlen; i += 64) s_q[i] = q[qoff[r] + i];
 	for (int i = l; i < tlen; i += 64) s_t[i] = t[toff[r] + i];
 	__syncthreads();
-	Sw sw; sw.mat = s_mat; sw.o_del = p[6]; sw.e_del = p[7]; sw.o_ins = p[8]; sw.e_ins = p[9];
+	Sw sw; sw.mat = s_mat; sw.o_del = p[6]; sw.e_del = p[7]; sw.o_ins = p[8]; sw.e_ins = p[9]; sw.stop = early_stop;
 	sw.mx = wmax(l < 25 ? (int)opt.mat[l] : 0); if (sw.mx < 0) sw.mx = 0;
 	int qle, tle, gtle, gscore, max_off;
 	Work wk = { 0, 0, 0 };
@@ -1234,7 +1272,8 @@ __global__ __launch_bounds__(64) void k_kat_ksw(DevOpt opt, int n, const int *pa
 
 // known-answer kernel: ksw_extend2 as the extension kernels instantiated for CPL columns per lane run it, on caller-supplied pairs with their own
 // matrix.  params per item: qlen, tlen, w, h0, zdrop, end_bonus, o_del, e_del, o_ins, e_ins, reverse (stride -1 on both sequences, as the left
-// extension reads them, bwamem.c:725-729), cpl.  out7: the six results, and the forms wave_extend_fit went through (EXT_PATH_*).
+// extension reads them, bwamem.c:725-729), cpl.  out7: the six results, and the forms wave_extend_fit went through (EXT_PATH_*, with
+// EXT_PATH_STOPPED when the early stop ended its loop; a.early_stop = 0 runs both calls to the last row).
 template <int CPL>
 __global__ __launch_bounds__(64) void k_kat_ksw2(KatDp a, int *out7)
 {
@@ -1254,7 +1293,7 @@ __global__ __launch_bounds__(64) void k_kat_ksw2(KatDp a, int *out7)
 	for (int i = l; i < qlen; i += 64) { const uint8_t c = a.q[a.qoff[r] + i]; s_q[i] = c < 5 ? c : 4; }
 	for (int i = l; i < tlen; i += 64) { const uint8_t c = a.t[a.toff[r] + i]; s_t[i] = c < 5 ? c : 4; }
 	__syncthreads();
-	Sw sw; sw.mat = s_mat; sw.o_del = p[6]; sw.e_del = p[7]; sw.o_ins = p[8]; sw.e_ins = p[9];
+	Sw sw; sw.mat = s_mat; sw.o_del = p[6]; sw.e_del = p[7]; sw.o_ins = p[8]; sw.e_ins = p[9]; sw.stop = a.early_stop;
 	sw.mx = wmax(l < 25 ? (int)mat[l] : 0); if (sw.mx < 0) sw.mx = 0;
 	const bool rev = p[10] != 0;
 	const uint8_t *qp = rev ? s_q + qlen - 1 : s_q, *tp = rev ? s_t + (tlen > 0 ? tlen - 1 : 0) : s_t;
@@ -1287,7 +1326,7 @@ __global__ __launch_bounds__(64) void k_kat_global_score(KatDp a, int *out2)
 	for (int i = l; i < qlen; i += 64) { const uint8_t c = a.q[a.qoff[r] + i]; s_q[i] = c < 5 ? c : 4; }
 	for (int i = l; i < tlen; i += 64) { const uint8_t c = a.t[a.toff[r] + i]; s_t[i] = c < 5 ? c : 4; }
 	__syncthreads();
-	Sw sw; sw.mat = s_mat; sw.o_del = p[3]; sw.e_del = p[4]; sw.o_ins = p[5]; sw.e_ins = p[6]; sw.mx = 0;
+	Sw sw; sw.mat = s_mat; sw.o_del = p[3]; sw.e_del = p[4]; sw.o_ins = p[5]; sw.e_ins = p[6]; sw.mx = 0; sw.stop = 0;
 	const bool rev = p[7] != 0;
 	Work wk = { 0, 0, 0 };
 	const int sc = rev ? wave_global_score<CPL>(sw, s_q + qlen - 1, -1, qlen, s_t + tlen - 1, -1, tlen, p[2], wk)
@@ -1319,11 +1358,11 @@ int launch_kat_isort(int n, int mode, const void *keys16, int *idx_par, int *idx
 }
 size_t kat_isort_work_ints(int n) { return 6 * ((size_t)n / 64 + 1) + 2 * ((size_t)n / 2 + 1) + (size_t)n + (size_t)n / 4 + 4; }
 
-int launch_kat_ksw(const DevOpt &opt, int n, const int *params, const uint8_t *q, const int64_t *qoff, const uint8_t *t, const int64_t *toff,
+int launch_kat_ksw(const DevOpt &opt, int early_stop, int n, const int *params, const uint8_t *q, const int64_t *qoff, const uint8_t *t, const int64_t *toff,
                    int *out6, hipStream_t st)
 {
 	if (n <= 0) return 0;
-	hipLaunchKernelGGL(k_kat_ksw, dim3(n), dim3(64), 0, st, opt, n, params, q, qoff, t, toff, out6);
+	hipLaunchKernelGGL(k_kat_ksw, dim3(n), dim3(64), 0, st, opt, early_stop, n, params, q, qoff, t, toff, out6);
 	return hipGetLastError() == hipSuccess ? 0 : BWAHIP_ENODEV;
 }
 

@@ -572,7 +572,7 @@ __device__ __forceinline__ bool reg2aln(const FinLaunch &a, const FinReg &ar, in
 	__syncthreads();
 	const uint8_t *qp = rev ? m.q + qe - 1 : m.q + qb; const int qs = rev ? -1 : 1;
 	const uint8_t *tp = rev ? m.t + rlen - 1 : m.t; const int ts = rev ? -1 : 1;
-	Sw sw; sw.mat = m.mat; sw.o_del = opt.o_del; sw.e_del = opt.e_del; sw.o_ins = opt.o_ins; sw.e_ins = opt.e_ins; sw.mx = 0;
+	Sw sw; sw.mat = m.mat; sw.o_del = opt.o_del; sw.e_del = opt.e_del; sw.o_ins = opt.o_ins; sw.e_ins = opt.e_ins; sw.mx = 0; sw.stop = 0;
 	int w2;
 	{
 		const int tmp = infer_bw(lq, rlen, ar.truesc, opt.a, opt.o_del, opt.e_del);

@@ -401,6 +401,7 @@ int bwahip_ctx_tune(bwahip_ctx *c, const char *key, int value)
 	else if (!strcmp(key, "rank_sort_min")) k.rank_sort_min = value;
 	else if (!strcmp(key, "spec_min_chains")) k.spec_min_chains = value;
 	else if (!strcmp(key, "ext_lds_window")) k.ext_lds_window = value < 1 ? 1 : value;
+	else if (!strcmp(key, "ext_early_stop")) { if (value != 0 && value != 1) return BWAHIP_EINVAL; k.ext_early_stop = value; }
 	else if (!strcmp(key, "gpu_final")) k.gpu_final = value;
 	else if (!strcmp(key, "gpu_pair")) k.gpu_pair = value;
 	else if (!strcmp(key, "verbose")) k.verbose = value;
@@ -748,7 +749,7 @@ int run_pipeline(bwahip_ctx *c, const bwahip_opt_t *opt, bool timed, bool dump)
 		if ((rc = c->d_dedup.ensure(((size_t)3 * n + 4) * 4))) return rc;
 		HIP_TRY(hipMemsetAsync(c->d_dedup.p, 0, 16, c->stream));
 		el.dedup_n = c->d_dedup.as<int>(); el.dedup_list = c->d_dedup.as<int>() + 4;
-		el.redo_n = c->d_redo.as<int>(); el.redo_list = c->d_redo.as<int>() + 4; el.big_t = c->d_big_t.as<uint8_t>(); el.lds_window = c->knobs.ext_lds_window;
+		el.redo_n = c->d_redo.as<int>(); el.redo_list = c->d_redo.as<int>() + 4; el.big_t = c->d_big_t.as<uint8_t>(); el.lds_window = c->knobs.ext_lds_window; el.ext_early_stop = c->knobs.ext_early_stop;
 		el.rank_sort_min = c->knobs.rank_sort_min;
 		const int spec_min = c->knobs.spec_min_chains;           // 0 = no ahead-of-time extension
 		if (spec_min > 0) {
@@ -1158,7 +1159,7 @@ int bwahip_kat_ksw_extend(bwahip_ctx *c, int n, const int *params, const uint8_t
 	DevBuf dp, dq, dqo, dt, dto, dout; int rc;
 	if ((rc = upload(dp, params, (size_t)n * 40, c->stream)) || (rc = upload(dq, q, (size_t)qoff[n], c->stream)) || (rc = upload(dqo, qoff, (size_t)(n + 1) * 8, c->stream)) ||
 	    (rc = upload(dt, t, (size_t)toff[n], c->stream)) || (rc = upload(dto, toff, (size_t)(n + 1) * 8, c->stream)) || (rc = dout.ensure((size_t)n * 24))) goto done;
-	rc = launch_kat_ksw(dopt, n, dp.as<int>(), dq.as<uint8_t>(), dqo.as<int64_t>(), dt.as<uint8_t>(), dto.as<int64_t>(), dout.as<int>(), c->stream);
+	rc = launch_kat_ksw(dopt, c->knobs.ext_early_stop, n, dp.as<int>(), dq.as<uint8_t>(), dqo.as<int64_t>(), dt.as<uint8_t>(), dto.as<int64_t>(), dout.as<int>(), c->stream);
 	if (!rc && hipMemcpyAsync(out6, dout.p, (size_t)n * 24, hipMemcpyDeviceToHost, c->stream) != hipSuccess) rc = BWAHIP_ENODEV;
 	if (hipStreamSynchronize(c->stream) != hipSuccess) rc = BWAHIP_ENODEV;
 done:
@@ -1198,7 +1199,7 @@ int bwahip_kat_ksw_extend2(bwahip_ctx *c, int n, const int *params, const int8_t
 	for (int k = 0; k < 4 && !rc; ++k) {
 		if (items[k].empty()) continue;
 		if ((rc = upload(dit[k], items[k].data(), items[k].size() * 4, c->stream))) break;
-		const KatDp a = { (int)items[k].size(), dit[k].as<int>(), dp.as<int>(), dm.as<int8_t>(), dq.as<uint8_t>(), dqo.as<int64_t>(), dt.as<uint8_t>(), dto.as<int64_t>() };
+		const KatDp a = { (int)items[k].size(), dit[k].as<int>(), dp.as<int>(), dm.as<int8_t>(), dq.as<uint8_t>(), dqo.as<int64_t>(), dt.as<uint8_t>(), dto.as<int64_t>(), c->knobs.ext_early_stop };
 		rc = launch_kat_ksw2(a, cpls[k], dout.as<int>(), c->stream);
 	}
 	if (!rc && hipMemcpyAsync(out7, dout.p, (size_t)n * 28, hipMemcpyDeviceToHost, c->stream) != hipSuccess) rc = BWAHIP_ENODEV;

@@ -457,7 +457,8 @@ int bwahip_kat_ksw_extend(bwahip_ctx *ctx, int n, const int *params /*n x 10*/, 
  * which must agree (else score = -777777).  params: n x 12 ints (qlen, tlen, w, h0, zdrop, end_bonus, o_del, e_del, o_ins, e_ins,
  * reverse, cpl); reverse = 1 reads both sequences backwards, as the left extension does; cpl is 3, 4, 5 or 11.  mat25: n x 25, one
  * 5x5 matrix per item (the largest entry is taken from it as the kernels take it from the options).  out7: n x 7 (score, qle, tle,
- * gtle, gscore, max_off, path), path = the forms the windowed driver went through, BWAHIP_KAT_EXT_* or-ed.
+ * gtle, gscore, max_off, path), path = the forms the windowed driver went through, BWAHIP_KAT_EXT_* or-ed, with
+ * BWAHIP_KAT_EXT_STOPPED when the early stop (knob ext_early_stop of the context, which both calls follow) ended its loop.
  * BWAHIP_EINVAL: h0 <= 0, an unknown cpl, negative lengths or gap costs, an extension cost below 1, offsets shorter than the lengths;
  * BWAHIP_ECAPACITY: qlen above BWAHIP_MAX_READ_LEN or qlen + 1 above 64 x cpl, tlen above the kernels' window in LDS (2124).  Nothing
  * is launched then. */
@@ -468,6 +469,7 @@ int bwahip_kat_ksw_extend(bwahip_ctx *ctx, int n, const int *params /*n x 10*/, 
 #define BWAHIP_KAT_EXT_SHORT    16    /* flank below 64 bases: plain form, one column per lane */
 #define BWAHIP_KAT_EXT_WIDE     32    /* band too wide for the window: plain form */
 #define BWAHIP_KAT_EXT_BEYOND16 64    /* scores beyond 16 bits: plain form */
+#define BWAHIP_KAT_EXT_STOPPED  128   /* the loop ended because no later row could change a result (never with ext_early_stop = 0) */
 int bwahip_kat_ksw_extend2(bwahip_ctx *ctx, int n, const int *params /*n x 12*/, const int8_t *mat25 /*n x 25*/, const uint8_t *q, const int64_t *qoff,
                            const uint8_t *t, const int64_t *toff, int *out7 /*n x 7*/);
 
@@ -514,8 +516,10 @@ int bwahip_kat_ksw_align(bwahip_ctx *ctx, int n, const int *params, const int8_t
                          const uint8_t *t, const int64_t *toff, int *out7);
 
 /* Tuning knobs of the heavy-read hand-off kernels (tests force each one onto ordinary reads): keys intv_cap,
- * smem_lanes, heavy_mult, chain_big_min, rank_sort_min, spec_min_chains, ext_lds_window, verbose.  The same knobs are read from the
- * environment (BWAHIP_<KEY>) once, when the context is created. */
+ * smem_lanes, heavy_mult, chain_big_min, rank_sort_min, spec_min_chains, ext_lds_window, verbose; and ext_early_stop (default 1): every
+ * device form of ksw_extend2 ends its row loop once no later row can change score, qle, tle, gtle, gscore or max_off --
+ * 0 runs every row to the end as the reference does (same results, more rows).
+ * The same knobs are read from the environment (BWAHIP_<KEY>) once, when the context is created. */
 int bwahip_ctx_tune(bwahip_ctx *ctx, const char *key, int value);
 
 const char *bwahip_version(void);
