@@ -81,6 +81,18 @@ class BgzfStats(C.Structure):  # bwahip_bgzf_stats_t
     _fields_ = [("raw_bytes", C.c_int64), ("bgzf_bytes", C.c_int64), ("n_blocks", C.c_int64), ("n_stored", C.c_int64), ("deflate_ms", C.c_double)]
 
 
+class DevMergeStats(C.Structure):  # bwahip_devmerge_stats_t
+    _fields_ = [("n_records", C.c_int64), ("n_runs", C.c_int64), ("raw_bytes", C.c_int64), ("bgzf_bytes", C.c_int64), ("n_blocks", C.c_int64),
+                ("n_stored", C.c_int64), ("hbm_bytes", C.c_int64), ("sort_ms", C.c_double), ("gather_ms", C.c_double), ("deflate_ms", C.c_double),
+                ("finish_s", C.c_double)]
+
+
+class SortDevStats(C.Structure):  # bwahip_sort_dev_t
+    _fields_ = [("tmp_dir", C.c_char_p), ("mem_budget", C.c_int64), ("level", C.c_int), ("hbm_budget", C.c_int64), ("piece_blocks", C.c_int),
+                ("fell_back", C.c_int), ("fell_back_at_run", C.c_int64), ("n_records", C.c_int64), ("n_runs", C.c_int64), ("spilled_bytes", C.c_int64),
+                ("sort_ms", C.c_double), ("merge_s", C.c_double), ("dev", DevMergeStats)]
+
+
 ERRORS = {0: "ok", -1: "EINVAL", -2: "ENODEV", -3: "ENOMEM", -4: "EIO", -5: "ECAPACITY", -6: "EINTERNAL"}
 
 STAGE_INTV, STAGE_CHAIN, STAGE_CHAIN_FLT, STAGE_REGS, STAGE_REGS_PRE, STAGE_SEEDS = 1, 2, 3, 4, 5, 6
@@ -148,6 +160,15 @@ def lib():
     L.bwahip_bam_merger_close.restype = None
     L.bwahip_stream_run_bam_sorted.argtypes = [C.POINTER(vp), C.c_int, C.POINTER(Opt), C.POINTER(PeStat), C.c_char_p, C.c_char_p, C.c_int, C.c_char_p, C.c_int,
                                                C.POINTER(StreamStats), C.POINTER(SortStats)]
+    L.bwahip_bam_devmerger_open.argtypes = [vp, C.c_int, C.POINTER(vp)]
+    L.bwahip_bam_devmerger_add.argtypes = [vp, C.c_int64, vp, C.c_int64, vp, vp, C.c_int64]
+    L.bwahip_bam_devmerger_finish.argtypes = [vp, C.c_int, C.POINTER(DevMergeStats)]
+    L.bwahip_bam_devmerger_close.argtypes = [vp]
+    L.bwahip_bam_devmerger_close.restype = None
+    L.bwahip_bam_devmerge_hbm_need.argtypes = [C.c_int64, C.c_int64, C.c_int64, C.c_int]
+    L.bwahip_bam_devmerge_hbm_need.restype = C.c_int64
+    L.bwahip_stream_run_bam_sorted_dev.argtypes = [C.POINTER(vp), C.c_int, C.POINTER(Opt), C.POINTER(PeStat), C.c_char_p, C.c_char_p, C.c_int, C.c_char_p,
+                                                   C.POINTER(StreamStats), C.POINTER(SortDevStats)]
     L.bwahip_kat_bgzf.argtypes = [vp, vp, C.c_int64, vp, C.c_int64, i64p, i64p, i64p]
     L.bwahip_process_seqs_bgzf.argtypes = [vp, C.POINTER(Opt), C.c_int64, C.c_int, C.POINTER(Seq), C.c_void_p, C.POINTER(vp), i64p, i64p, i64p]
     L.bwahip_batch_run_bgzf.argtypes = [vp, C.POINTER(Opt), C.c_int64, C.POINTER(PeStat), C.POINTER(C.c_float), C.c_int, C.POINTER(C.c_float)]
@@ -316,6 +337,44 @@ class BamMerger:
 
     def __exit__(self, *a):
         self.close()
+
+
+class DevMerger:
+    """bwahip_bam_devmerger_*: BamMerger with the runs in the context's HBM and the merge, the gather and the deflate on its device
+    (csrc/k_bammerge.hip).  piece_blocks: BGZF blocks gathered and deflated at a time (0: the context's sorted_piece_blocks)."""
+
+    def __init__(self, ctx, piece_blocks=0):
+        self._h = C.c_void_p()
+        self._ctx = ctx                                          # the context outlives the merger
+        _check(lib().bwahip_bam_devmerger_open(ctx._h, piece_blocks, C.byref(self._h)), "bwahip_bam_devmerger_open")
+
+    def add(self, run_no, rec, keys, rec_off):
+        rec = bytes(rec)
+        keys = np.ascontiguousarray(keys, dtype=np.uint64)
+        rec_off = np.ascontiguousarray(rec_off, dtype=np.int64)
+        _check(lib().bwahip_bam_devmerger_add(self._h, run_no, rec, len(rec), keys.ctypes.data, rec_off.ctypes.data, len(keys)), "bwahip_bam_devmerger_add")
+
+    def finish(self, fd=-1):
+        """The members of all records on fd (no header, no EOF block); returns the filled DevMergeStats."""
+        st = DevMergeStats()
+        _check(lib().bwahip_bam_devmerger_finish(self._h, fd, C.byref(st)), "bwahip_bam_devmerger_finish")
+        return st
+
+    def close(self):
+        if self._h:
+            lib().bwahip_bam_devmerger_close(self._h)
+            self._h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+
+def bam_devmerge_hbm_need(raw_bytes, n_records, n_runs, piece_blocks):
+    """bwahip_bam_devmerge_hbm_need: the HBM a device merger takes for these runs, finish included (no device)."""
+    return lib().bwahip_bam_devmerge_hbm_need(raw_bytes, n_records, n_runs, piece_blocks)
 
 
 def bgzf_write(fd, data, level=1, n_threads=1, eof=False):
@@ -861,6 +920,23 @@ def stream_run_bam_sorted(ctxs, fq1, fq2=None, out_fd=-1, hdr_line=None, level=1
     _check(lib().bwahip_stream_run_bam_sorted(arr, len(ctxs), C.byref(opt), C.byref(pes0) if pes0 is not None else None, os.fsencode(fq1),
                                               os.fsencode(fq2) if fq2 else None, out_fd, hdr_line, level, C.byref(st), C.byref(so)), "bwahip_stream_run_bam_sorted")
     return st, so
+
+
+def stream_run_bam_sorted_dev(ctxs, fq1, fq2=None, out_fd=-1, hdr_line=None, opt=None, chunk_bases=0, max_reads=0, keep_comments=False,
+                              reader_threads=0, pes0=None, hbm_budget=0, piece_blocks=0, tmp_dir=None, mem_budget=1 << 30, level=1):
+    """bwahip_stream_run_bam_sorted_dev: FASTQ files -> a coordinate-sorted BAM file on out_fd, the runs kept, merged and deflated in HBM;
+    tmp_dir, mem_budget and level are the host merger's after a fall-back.  Returns (StreamStats, SortDevStats)."""
+    opt = opt or default_opt()
+    st, sd = StreamStats(), SortDevStats()
+    st.chunk_bases, st.max_reads, st.keep_comments, st.reader_threads = chunk_bases, max_reads, int(keep_comments), reader_threads
+    sd.tmp_dir, sd.mem_budget, sd.level = os.fsencode(tmp_dir) if tmp_dir is not None else None, mem_budget, level
+    sd.hbm_budget, sd.piece_blocks = hbm_budget, piece_blocks
+    arr = (C.c_void_p * len(ctxs))(*[c._h for c in ctxs])
+    if isinstance(hdr_line, str):
+        hdr_line = hdr_line.encode()
+    _check(lib().bwahip_stream_run_bam_sorted_dev(arr, len(ctxs), C.byref(opt), C.byref(pes0) if pes0 is not None else None, os.fsencode(fq1),
+                                                  os.fsencode(fq2) if fq2 else None, out_fd, hdr_line, C.byref(st), C.byref(sd)), "bwahip_stream_run_bam_sorted_dev")
+    return st, sd
 
 
 def _tool(name):

@@ -4,6 +4,7 @@
 #include "bwahip_internal.h"
 #include <atomic>
 #include <string>
+#include <utility>
 
 // hipFree / hipMalloc / hipHostMalloc inside a buffer's ensure() synchronise the whole device: counted, so that the stream driver can
 // report how many a pass paid (BWAHIP_STREAM_LOG; a steady pass of equal batches pays none)
@@ -60,6 +61,7 @@ struct Knobs {
 	int spec_min_chains = 16;   // BWAHIP_SPEC_MIN_CHAINS: chains from which k_extend_spec extends ahead of time (0: off)
 	int ext_lds_window = 1 << 30;   // BWAHIP_EXT_LDS_WINDOW: reference windows above this go to k_extend_big (tests; default = the compiled LDS window)
 	int ext_early_stop = 1;     // BWAHIP_EXT_EARLY_STOP: ksw_extend2 ends once no later row can change its results (0: every row to the end, as the reference -- same results, more rows)
+	int sorted_piece_blocks = 1024;   // BWAHIP_SORTED_PIECE_BLOCKS: BGZF blocks a device merger (k_bammerge.hip) gathers and deflates at a time (1 .. 4096; the bytes do not depend on it)
 	int gpu_final = 1;          // BWAHIP_GPU_FINAL: 0 = finalisation of single-end batches on host threads (host_final.cpp) instead of the GPU kernels
 	int gpu_pair = 1;           // BWAHIP_GPU_PAIR: 0 = paired-end batches finalised on host threads (mate rescue, pairing, SAM)
 	int verbose = 0;            // BWAHIP_VERBOSE
@@ -75,6 +77,8 @@ struct Knobs {
 		dump_ext = getenv("BWAHIP_DUMP_EXT");
 		if (intv_cap < 2) intv_cap = 2;
 		ext_early_stop = ext_early_stop != 0;
+		geti("BWAHIP_SORTED_PIECE_BLOCKS", sorted_piece_blocks);
+		if (sorted_piece_blocks < 1 || sorted_piece_blocks > 4096) sorted_piece_blocks = 1024;
 	}
 };
 
@@ -194,6 +198,20 @@ int bam_sort_tile();
 // stored (both int64, in HBM: nothing is awaited).  Queued on st; len == 0 launches nothing but sets tot.
 int bgzf_deflate(bwahip_ctx *c, const uint8_t *d_in, int64_t len, DevBuf &out, int64_t *tot_dev, hipStream_t st);
 inline int64_t bgzf_blocks(int64_t len) { return (len + 65279) / 65280; }
+// k_bammerge.hip: one sorted run in device buffers of its own (records, keys, n_rec + 1 offsets), as a device merger holds it.
+// bam_devrun_make allocates them on c's device and copies from device pointers on st (one device-to-device copy each; awaited, so the
+// source is free on return); a failed allocation: BWAHIP_ENOMEM and nothing is held.  bam_devmerger_adopt registers the run under
+// run_no and owns it from then on (refused: the caller still owns it).  bam_devrun_download copies a run to host buffers of at least
+// len, n_rec and n_rec + 1 items.
+struct DevRun { int64_t n_rec = 0, len = 0; uint8_t *rec = nullptr; uint64_t *keys = nullptr; int64_t *off = nullptr; int device = 0; };   // allocated to size: no slack
+int  bam_devrun_make(bwahip_ctx *c, const uint8_t *d_rec, int64_t len, const uint64_t *d_keys, const int64_t *d_rec_off, int64_t n_rec, hipStream_t st, DevRun **out);
+int  bam_devrun_download(const DevRun *r, uint8_t *rec, uint64_t *keys, int64_t *rec_off, hipStream_t st);
+void bam_devrun_free(DevRun *r);
+int  bam_devmerger_adopt(bwahip_bam_devmerger *m, int64_t run_no, DevRun *r);
+// the device-to-device form of bwahip_bam_devmerger_add: make + adopt
+int  bam_devmerger_add_dev(bwahip_bam_devmerger *m, int64_t run_no, const uint8_t *d_rec, int64_t len, const uint64_t *d_keys, const int64_t *d_rec_off, int64_t n_rec, hipStream_t st);
+// the merger's runs in run-number order, handed to the caller (who frees them); the merger is empty afterwards
+int  bam_devmerger_take_runs(bwahip_bam_devmerger *m, std::vector<std::pair<int64_t, DevRun*>> *out);
 int bam_check_reads(int n, const bwahip_seq_t *seqs);   // bam_host.cpp: BWAHIP_EINVAL (with a message naming the read) for a name or a comment BAM cannot hold
 void pipe_destroy(bwahip_ctx *c);                                                     // final_rt.hip: the stream driver's buffer sets
 int final_setup(bwahip_ctx *c);                                                       // contig name tables for the SAM kernels

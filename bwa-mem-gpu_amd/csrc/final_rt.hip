@@ -971,6 +971,23 @@ int pipe_stage_out_sorted(bwahip_ctx *c, int out, const uint64_t **keys, const i
 	return 0;
 }
 
+// Instead of pipe_stage_out + pipe_stage_out_sorted when the run stays in HBM: the set's records, keys and offsets into device buffers of
+// the run's own (k_bammerge.hip), on the copy stream.
+int pipe_stage_out_devrun(bwahip_ctx *c, int out, DevRun **run, int64_t *raw_len, int64_t *n_rec, double *sort_ms, double *t_kernels_end)
+{
+	if (!c || !c->pipe || out < 0 || out >= PIPE_SETS || !run || !raw_len || !n_rec) return BWAHIP_EINVAL;
+	*run = nullptr;
+	HIP_TRY(hipSetDevice(c->device));
+	PipeOut &o = c->pipe->out[out];
+	HIP_TRY(hipEventSynchronize(o.ev_written));
+	if (t_kernels_end) *t_kernels_end = pipe_now();
+	if (!o.sorted) return BWAHIP_EINVAL;
+	if (sort_ms) { float ms = 0; if (o.n_rec && o.ev_sort[0] && hipEventElapsedTime(&ms, o.ev_sort[0], o.ev_sort[3]) != hipSuccess) ms = 0; *sort_ms = ms; }
+	*raw_len = o.total; *n_rec = o.n_rec;
+	const int rc = bam_devrun_make(c, o.d_sam.as<uint8_t>(), o.total, o.d_keys.as<uint64_t>(), o.d_rec_off.as<int64_t>(), o.n_rec, c->stream_copy, run);
+	return rc == BWAHIP_ENOMEM ? 0 : rc;
+}
+
 // After pipe_stage_out of a batch computed with bam == 3: the bytes of the records the members hold, the members, those that are stored,
 // and the GPU time of the deflate stage.
 int pipe_stage_out_bgzf(bwahip_ctx *c, int out, int64_t *raw_len, int64_t *n_blocks, int64_t *n_stored, double *deflate_ms)

@@ -1,0 +1,420 @@
+// K9e -- the merge of sorted runs on the GPU: what bwahip_bam_merger_* (bam_sort_host.cpp) does on one host thread in front of host zlib,
+// for runs that stay in HBM.  A run = the sorted records of one batch, its keys and its n_rec + 1 record offsets, each in a device buffer
+// of its own; no record is ever parsed.  finish():
+//
+//   order          the runs' keys, concatenated in run-number order, through the stable radix sort of k_bamsort.hip with the ordinals
+//                  0 .. n - 1: concatenation order is (run, position in the run), the sort is stable, so the result is the order of the
+//                  host merger's k-way merge -- (key, run_no, position) -- without a merge kernel.  All 64 bits of the key count, as in
+//                  the host merger's comparison (the sort skips the digits that are the same in all keys);
+//   source table   k_src_table: per ordinal the absolute device address of the record and its length (the run by binary search in the
+//                  table of the runs' first ordinals);
+//   output offsets k_sorted_len: the lengths in sorted order; an exclusive scan.  The last offset must be the sum of the runs' bytes;
+//   pieces         the sorted byte stream is never made whole: it is cut every piece_blocks x 65 280 bytes, k_piece_first finds the
+//                  record that holds every cut (binary search over the output offsets), one read-back brings them to the host;
+//   windowed       k_gather_window: k_gather_copy's shape (16 lanes per record, single bytes to the destination's 16-byte boundary,
+//   gather         unaligned 16-byte loads and aligned 16-byte stores, the ragged end), clipped to the piece's byte range at both ends;
+//   deflate        bgzf_deflate (k_bgzf.hip) on the piece as it is.  Pieces are whole multiples of a block's input and blocks are
+//                  independent, so the members are those of one deflate stage over all sorted records.
+//
+// Two piece inputs and two piece outputs: the gather and the deflate of piece k are queued on the context's stream while the 16-byte
+// total and then the members of piece k - 1 come back on the copy stream and are written.  No kernel here uses LDS or atomics.
+#include "ctx_internal.h"
+#include <errno.h>
+#include <unistd.h>
+#include <chrono>
+#include <map>
+#include <mutex>
+
+namespace {
+
+constexpr int64_t BLOCK_IN = 65280;
+constexpr int MAX_PIECE_BLOCKS = 4096;
+
+double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+
+// first[r]: the ordinal of run r's first record (n_runs + 1 entries, the last = n).  Thread = ordinal.  err: offsets that decrease or leave
+// the run's bytes (never expected: add() checked the host's, the sort stage produced the device's); such a record counts as empty.
+__global__ __launch_bounds__(256) void k_src_table(int n, int n_runs, const int64_t *first, const uint8_t *const *run_rec, const int64_t *const *run_off, const int64_t *run_len,
+                                                  const uint8_t **addr, int *len, int *err)
+{
+	const int g = blockIdx.x * 256 + threadIdx.x;
+	if (g >= n) return;
+	int lo = 0, hi = n_runs;                                       // the last run whose first ordinal is <= g: it is not empty, because the next one's is > g
+	while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (first[mid] <= g) lo = mid; else hi = mid; }
+	const int64_t j = g - first[lo];
+	const int64_t o0 = run_off[lo][j], o1 = run_off[lo][j + 1];
+	const bool ok = o0 >= 0 && o1 >= o0 && o1 <= run_len[lo] && o1 - o0 <= 0x7fffffff;
+	if (!ok) *err = 1;                                             // every writer writes 1
+	addr[g] = run_rec[lo] + (ok ? o0 : 0);
+	len[g] = ok ? (int)(o1 - o0) : 0;
+}
+
+__global__ __launch_bounds__(256) void k_sorted_len(const unsigned *idx, const int *len, int n, int *len_sorted)
+{
+	const int i = blockIdx.x * 256 + threadIdx.x;
+	if (i < n) len_sorted[i] = len[idx[i]];
+}
+
+// first_rec[p], p < n_pieces: the last record (in sorted order) whose first byte is at or before byte p * piece_bytes of the sorted stream --
+// the record that holds that byte, or the one that begins there.  out_off: n + 1 offsets, out_off[0] = 0.
+__global__ __launch_bounds__(256) void k_piece_first(const int64_t *out_off, int n, int64_t piece_bytes, int n_pieces, int *first_rec)
+{
+	const int p = blockIdx.x * 256 + threadIdx.x;
+	if (p >= n_pieces) return;
+	const int64_t b = (int64_t)p * piece_bytes;
+	int lo = 0, hi = n;                                            // out_off[lo] <= b < out_off[hi] (b is below the stream's end)
+	while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (out_off[mid] <= b) lo = mid; else hi = mid; }
+	first_rec[p] = lo;
+}
+
+// Records [rec_lo, rec_lo + n_rec) of the sorted order, the bytes of each that fall into [byte_lo, byte_hi) of the sorted stream, to
+// dst + (position - byte_lo).  16 lanes per record.  A record may begin before the piece, end behind it, or cover it whole.
+__global__ __launch_bounds__(256) void k_gather_window(const uint8_t *const *addr, const unsigned *idx, const int64_t *out_off, int rec_lo, int n_rec, int64_t byte_lo, int64_t byte_hi,
+                                                      uint8_t *dst_all)
+{
+	const int64_t g = ((int64_t)blockIdx.x * 256 + threadIdx.x) >> 4;
+	const int l = threadIdx.x & 15;
+	if (g >= n_rec) return;
+	const int64_t o = out_off[rec_lo + g], e = out_off[rec_lo + g + 1];
+	const int64_t a = o > byte_lo ? o : byte_lo, b = e < byte_hi ? e : byte_hi;
+	if (a >= b) return;
+	const uint8_t *src = addr[idx[rec_lo + g]] + (a - o);
+	uint8_t *dst = dst_all + (a - byte_lo);
+	const int len = (int)(b - a);                                  // at most the piece: 4096 x 65 280 bytes
+	int head = (int)((16 - ((uintptr_t)dst & 15)) & 15);
+	if (head > len) head = len;
+	if (l < head) dst[l] = src[l];
+	const int body = (len - head) >> 4;
+	for (int k = l; k < body; k += 16) {
+		uint4 v;
+		__builtin_memcpy(&v, src + head + 16 * k, 16);
+		*reinterpret_cast<uint4*>(dst + head + 16 * k) = v;
+	}
+	for (int k = head + 16 * body + l; k < len; k += 16) dst[k] = src[k];
+}
+
+int launched() { return hipGetLastError() == hipSuccess ? 0 : BWAHIP_ENODEV; }
+
+int dev_alloc(void **p, size_t bytes)
+{
+	*p = nullptr;
+	++g_bwahip_reallocs;
+	if (hipMalloc(p, bytes ? bytes : 1) != hipSuccess) { (void)hipGetLastError(); *p = nullptr; fprintf(stderr, "[bwahip] sorted BAM: hipMalloc(%zu) for a run failed\n", bytes); return BWAHIP_ENOMEM; }
+	return 0;
+}
+
+// finish()'s buffers beside the context's (bs.keys / bs.idx / bs.hist*, bz.*): counted by bwahip_bam_devmerge_hbm_need below
+struct Work {
+	DevBuf first, run_rec, run_off, run_len;                       // per run
+	DevBuf addr, len, len_sorted, out_off, err;                    // per record: 8 + 4 + 4 + 8 bytes
+	DevBuf piece_first;                                            // per piece
+	DevBuf in[2], out[2], tot[2];                                  // per piece of piece_blocks blocks: input, members (input + 31 per block), their total
+	HostBuf h_out[2], h_tot;
+	hipEvent_t ev_gather[2] = {}, ev_deflate[2] = {}, ev_done[2] = {}, ev_down[2] = {}, ev_sort[2] = {};
+	int make_events()
+	{
+		for (auto *set : { ev_gather, ev_deflate, ev_done, ev_down, ev_sort }) for (int k = 0; k < 2; ++k) if (!set[k]) HIP_TRY(hipEventCreate(&set[k]));
+		return 0;
+	}
+	size_t bytes() const
+	{
+		size_t b = 0;
+		for (const DevBuf *d : { &first, &run_rec, &run_off, &run_len, &addr, &len, &len_sorted, &out_off, &err, &piece_first, &in[0], &in[1], &out[0], &out[1], &tot[0], &tot[1] }) b += d->cap;
+		return b;
+	}
+	void release()
+	{
+		for (DevBuf *d : { &first, &run_rec, &run_off, &run_len, &addr, &len, &len_sorted, &out_off, &err, &piece_first, &in[0], &in[1], &out[0], &out[1], &tot[0], &tot[1] }) d->release();
+		h_out[0].release(); h_out[1].release(); h_tot.release();
+		for (auto *set : { ev_gather, ev_deflate, ev_done, ev_down, ev_sort }) for (int k = 0; k < 2; ++k) if (set[k]) { (void)hipEventDestroy(set[k]); set[k] = nullptr; }
+	}
+};
+
+int write_full(int fd, const uint8_t *b, int64_t len)
+{
+	while (len > 0) {
+		const ssize_t w = write(fd, b, (size_t)(len > (1ll << 30) ? (1ll << 30) : len));
+		if (w < 0) { if (errno == EINTR) continue; fprintf(stderr, "[bwahip] sorted BAM: writing the members failed: %s\n", strerror(errno)); return BWAHIP_EIO; }
+		if (w == 0) return BWAHIP_EIO;
+		b += w; len -= w;
+	}
+	return 0;
+}
+
+} // namespace
+
+// The HBM of a device merger: what the runs hold, and what finish() allocates for them -- next to the buffers it counts (Work above, the
+// context's BamSort keys / ordinals and Bgzf slots).  Per record: two key and two ordinal buffers of the sort (24), address, length, sorted
+// length and output offset (24).  Per block of a piece: two inputs, two outputs (input + 31), the slot, the member's length and offset.
+// The deflate stage's per-workgroup words (one workgroup per compute unit, 261 120 bytes each) and the sort's histograms: 64 MiB covers
+// 256 compute units.  The working buffers grow with an eighth of slack (DevBuf::ensure); the runs are allocated to size.
+extern "C" int64_t bwahip_bam_devmerge_hbm_need(int64_t raw_bytes, int64_t n_records, int64_t n_runs, int piece_blocks)
+{
+	if (raw_bytes < 0 || n_records < 0 || n_runs < 0 || piece_blocks < 1 || piece_blocks > MAX_PIECE_BLOCKS) return -1;
+	const int64_t runs = raw_bytes + 16 * n_records + 8 * n_runs;
+	int64_t pb = bgzf_blocks(raw_bytes);
+	if (pb > piece_blocks) pb = piece_blocks;
+	const int64_t work = 48 * n_records + pb * (4 * BLOCK_IN + 2 * 31 + 65536 + 12) + (64ll << 20);
+	return runs + work + work / 8;
+}
+
+struct bwahip_bam_devmerger {
+	bwahip_ctx *c = nullptr;
+	int piece_blocks = 0;
+	std::mutex mu;
+	std::map<int64_t, DevRun*> runs;                               // by run_no: the order of the concatenation
+	int64_t n_records = 0, raw_bytes = 0;
+	Work w;
+};
+
+int bam_devrun_make(bwahip_ctx *c, const uint8_t *d_rec, int64_t len, const uint64_t *d_keys, const int64_t *d_rec_off, int64_t n_rec, hipStream_t st, DevRun **out)
+{
+	if (!c || !out || len < 0 || n_rec < 0 || (n_rec && (!d_rec || !d_keys || !d_rec_off)) || (!n_rec && len)) return BWAHIP_EINVAL;
+	*out = nullptr;
+	HIP_TRY(hipSetDevice(c->device));
+	DevRun *r = new DevRun;
+	r->n_rec = n_rec; r->len = len; r->device = c->device;
+	if (n_rec) {
+		int rc;
+		if ((rc = dev_alloc((void**)&r->rec, (size_t)len)) || (rc = dev_alloc((void**)&r->keys, (size_t)n_rec * 8)) || (rc = dev_alloc((void**)&r->off, (size_t)(n_rec + 1) * 8))) { bam_devrun_free(r); return rc; }
+		hipError_t e = len ? hipMemcpyAsync(r->rec, d_rec, (size_t)len, hipMemcpyDeviceToDevice, st) : hipSuccess;
+		if (e == hipSuccess) e = hipMemcpyAsync(r->keys, d_keys, (size_t)n_rec * 8, hipMemcpyDeviceToDevice, st);
+		if (e == hipSuccess) e = hipMemcpyAsync(r->off, d_rec_off, (size_t)(n_rec + 1) * 8, hipMemcpyDeviceToDevice, st);
+		if (e == hipSuccess) e = hipStreamSynchronize(st);
+		if (e != hipSuccess) { fprintf(stderr, "[bwahip] sorted BAM: copying a run failed: %s\n", hipGetErrorString(e)); bam_devrun_free(r); return BWAHIP_ENODEV; }
+	}
+	*out = r;
+	return 0;
+}
+
+int bam_devrun_download(const DevRun *r, uint8_t *rec, uint64_t *keys, int64_t *rec_off, hipStream_t st)
+{
+	if (!r || !rec_off) return BWAHIP_EINVAL;
+	if (!r->n_rec) { rec_off[0] = 0; return 0; }
+	if (!rec || !keys) return BWAHIP_EINVAL;
+	HIP_TRY(hipSetDevice(r->device));
+	if (r->len) HIP_TRY(hipMemcpyAsync(rec, r->rec, (size_t)r->len, hipMemcpyDeviceToHost, st));
+	HIP_TRY(hipMemcpyAsync(keys, r->keys, (size_t)r->n_rec * 8, hipMemcpyDeviceToHost, st));
+	HIP_TRY(hipMemcpyAsync(rec_off, r->off, (size_t)(r->n_rec + 1) * 8, hipMemcpyDeviceToHost, st));
+	HIP_TRY(hipStreamSynchronize(st));
+	return 0;
+}
+
+void bam_devrun_free(DevRun *r)
+{
+	if (!r) return;
+	(void)hipSetDevice(r->device);
+	for (void *p : { (void*)r->rec, (void*)r->keys, (void*)r->off }) if (p) { (void)hipFree(p); ++g_bwahip_reallocs; }
+	delete r;
+}
+
+int bam_devmerger_adopt(bwahip_bam_devmerger *m, int64_t run_no, DevRun *r)
+{
+	if (!m || !r || run_no < 0 || r->device != m->c->device) return BWAHIP_EINVAL;
+	std::lock_guard<std::mutex> lk(m->mu);
+	if (m->runs.count(run_no)) return BWAHIP_EINVAL;
+	if (m->n_records + r->n_rec > 0x7fffffffll) return BWAHIP_ECAPACITY;   // the sort's ordinals are 32-bit and it takes an int
+	m->runs[run_no] = r;
+	m->n_records += r->n_rec; m->raw_bytes += r->len;
+	return 0;
+}
+
+int bam_devmerger_add_dev(bwahip_bam_devmerger *m, int64_t run_no, const uint8_t *d_rec, int64_t len, const uint64_t *d_keys, const int64_t *d_rec_off, int64_t n_rec, hipStream_t st)
+{
+	if (!m || run_no < 0) return BWAHIP_EINVAL;
+	{
+		std::lock_guard<std::mutex> lk(m->mu);                      // refused before anything is allocated (adopt checks again under the same lock)
+		if (m->runs.count(run_no)) return BWAHIP_EINVAL;
+		if (n_rec >= 0 && m->n_records + n_rec > 0x7fffffffll) return BWAHIP_ECAPACITY;
+	}
+	DevRun *r = nullptr;
+	int rc = bam_devrun_make(m->c, d_rec, len, d_keys, d_rec_off, n_rec, st, &r);
+	if (rc) return rc;
+	if ((rc = bam_devmerger_adopt(m, run_no, r))) bam_devrun_free(r);
+	return rc;
+}
+
+int bam_devmerger_take_runs(bwahip_bam_devmerger *m, std::vector<std::pair<int64_t, DevRun*>> *out)
+{
+	if (!m || !out) return BWAHIP_EINVAL;
+	std::lock_guard<std::mutex> lk(m->mu);
+	out->assign(m->runs.begin(), m->runs.end());
+	m->runs.clear(); m->n_records = 0; m->raw_bytes = 0;
+	return 0;
+}
+
+extern "C" int bwahip_bam_devmerger_open(bwahip_ctx *ctx, int piece_blocks, bwahip_bam_devmerger **out)
+{
+	if (!out) return BWAHIP_EINVAL;
+	*out = nullptr;
+	if (!ctx || piece_blocks > MAX_PIECE_BLOCKS) return BWAHIP_EINVAL;
+	bwahip_bam_devmerger *m = new bwahip_bam_devmerger;
+	m->c = ctx; m->piece_blocks = piece_blocks > 0 ? piece_blocks : ctx->knobs.sorted_piece_blocks;
+	*out = m;
+	return 0;
+}
+
+extern "C" int bwahip_bam_devmerger_add(bwahip_bam_devmerger *m, int64_t run_no, const uint8_t *rec, int64_t len, const uint64_t *keys, const int64_t *rec_off, int64_t n_rec)
+{
+	if (!m || run_no < 0 || len < 0 || n_rec < 0 || (n_rec && (!rec || !keys || !rec_off)) || (!n_rec && len)) return BWAHIP_EINVAL;
+	if (n_rec && (rec_off[0] != 0 || rec_off[n_rec] != len)) return BWAHIP_EINVAL;
+	for (int64_t i = 0; i < n_rec; ++i) {
+		if (rec_off[i + 1] < rec_off[i]) return BWAHIP_EINVAL;
+		if (rec_off[i + 1] - rec_off[i] > 0x7fffffffll) return BWAHIP_ECAPACITY;   // lengths are scanned as int32
+	}
+	bwahip_ctx *c = m->c;
+	{
+		std::lock_guard<std::mutex> lk(m->mu);
+		if (m->runs.count(run_no)) return BWAHIP_EINVAL;
+		if (m->n_records + n_rec > 0x7fffffffll) return BWAHIP_ECAPACITY;
+	}
+	HIP_TRY(hipSetDevice(c->device));
+	DevRun *r = new DevRun;
+	r->n_rec = n_rec; r->len = len; r->device = c->device;
+	int rc = 0;
+	if (n_rec) {
+		if ((rc = dev_alloc((void**)&r->rec, (size_t)len)) || (rc = dev_alloc((void**)&r->keys, (size_t)n_rec * 8)) || (rc = dev_alloc((void**)&r->off, (size_t)(n_rec + 1) * 8))) { bam_devrun_free(r); return rc; }
+		// plain copies: they return when the caller's memory has been read, whatever thread and stream
+		hipError_t e = len ? hipMemcpy(r->rec, rec, (size_t)len, hipMemcpyHostToDevice) : hipSuccess;
+		if (e == hipSuccess) e = hipMemcpy(r->keys, keys, (size_t)n_rec * 8, hipMemcpyHostToDevice);
+		if (e == hipSuccess) e = hipMemcpy(r->off, rec_off, (size_t)(n_rec + 1) * 8, hipMemcpyHostToDevice);
+		if (e == hipSuccess) e = hipDeviceSynchronize();
+		if (e != hipSuccess) { fprintf(stderr, "[bwahip] sorted BAM: uploading a run failed: %s\n", hipGetErrorString(e)); bam_devrun_free(r); return BWAHIP_ENODEV; }
+	}
+	if ((rc = bam_devmerger_adopt(m, run_no, r))) bam_devrun_free(r);
+	return rc;
+}
+
+extern "C" int bwahip_bam_devmerger_finish(bwahip_bam_devmerger *m, int fd, bwahip_devmerge_stats_t *st)
+{
+	if (!m) return BWAHIP_EINVAL;
+	std::lock_guard<std::mutex> lk(m->mu);
+	bwahip_ctx *c = m->c;
+	Work &w = m->w;
+	const double t0 = now_s();
+	bwahip_devmerge_stats_t s;
+	memset(&s, 0, sizeof s);
+	s.n_records = m->n_records; s.n_runs = (int64_t)m->runs.size(); s.raw_bytes = m->raw_bytes;
+	s.n_blocks = bgzf_blocks(m->raw_bytes);
+	for (auto &kv : m->runs) s.hbm_bytes += kv.second->n_rec ? kv.second->len + 16 * kv.second->n_rec + 8 : 0;
+	if (st) *st = s;
+	const int n = (int)m->n_records;
+	const int64_t total = m->raw_bytes;
+	if (n == 0 || total == 0) { s.finish_s = now_s() - t0; if (st) *st = s; return 0; }   // nothing to write: no member
+	HIP_TRY(hipSetDevice(c->device));
+	int rc;
+	if ((rc = w.make_events())) return rc;
+	BamSort &bs = c->bs;
+	const int n_runs = (int)m->runs.size();
+
+	// ---- the order
+	if ((rc = bs.keys[0].ensure((size_t)n * 8)) || (rc = bs.keys[1].ensure((size_t)n * 8)) || (rc = bs.idx[0].ensure((size_t)n * 4)) || (rc = bs.idx[1].ensure((size_t)n * 4))) return rc;
+	std::vector<int64_t> first((size_t)n_runs + 1), run_len((size_t)n_runs);
+	std::vector<const uint8_t*> run_rec((size_t)n_runs);
+	std::vector<const int64_t*> run_off((size_t)n_runs);
+	HIP_TRY(hipEventRecord(w.ev_sort[0], c->stream));
+	{
+		int64_t at = 0; int k = 0;
+		for (auto &kv : m->runs) {
+			const DevRun *r = kv.second;
+			first[(size_t)k] = at; run_rec[(size_t)k] = r->rec; run_off[(size_t)k] = r->off; run_len[(size_t)k] = r->len;
+			if (r->n_rec) HIP_TRY(hipMemcpyAsync(bs.keys[0].as<uint64_t>() + at, r->keys, (size_t)r->n_rec * 8, hipMemcpyDeviceToDevice, c->stream));
+			at += r->n_rec; ++k;
+		}
+		first[(size_t)n_runs] = at;
+	}
+	int cur = 0;
+	if ((rc = bam_sort_iota(bs.idx[0].as<unsigned>(), n, c->stream)) || (rc = bam_sort_radix(c, n, 64, &cur))) return rc;
+	HIP_TRY(hipEventRecord(w.ev_sort[1], c->stream));
+	const unsigned *idx = bs.idx[cur].as<unsigned>();
+
+	// ---- source table, output offsets
+	if ((rc = dev_upload(w.first, first.data(), first.size() * 8, c->stream)) || (rc = dev_upload(w.run_rec, run_rec.data(), run_rec.size() * 8, c->stream)) ||
+	    (rc = dev_upload(w.run_off, run_off.data(), run_off.size() * 8, c->stream)) || (rc = dev_upload(w.run_len, run_len.data(), run_len.size() * 8, c->stream))) return rc;
+	if ((rc = w.addr.ensure((size_t)n * 8)) || (rc = w.len.ensure((size_t)n * 4)) || (rc = w.len_sorted.ensure((size_t)n * 4)) || (rc = w.out_off.ensure(((size_t)n + 1) * 8)) || (rc = w.err.ensure(4))) return rc;
+	HIP_TRY(hipMemsetAsync(w.err.p, 0, 4, c->stream));
+	const int grid_n = (n + 255) / 256;
+	hipLaunchKernelGGL(k_src_table, dim3(grid_n), dim3(256), 0, c->stream, n, n_runs, w.first.as<int64_t>(), w.run_rec.as<const uint8_t*>(), w.run_off.as<const int64_t*>(), w.run_len.as<int64_t>(),
+	                   w.addr.as<const uint8_t*>(), w.len.as<int>(), w.err.as<int>());
+	if ((rc = launched())) return rc;
+	hipLaunchKernelGGL(k_sorted_len, dim3(grid_n), dim3(256), 0, c->stream, idx, w.len.as<int>(), n, w.len_sorted.as<int>());
+	if ((rc = launched()) || (rc = launch_scan(w.len_sorted.as<int>(), w.out_off.as<int64_t>(), n, c->d_scan, c->stream))) return rc;
+
+	// ---- pieces
+	const int64_t piece_bytes = (int64_t)m->piece_blocks * BLOCK_IN;
+	const int64_t n_pieces64 = (total + piece_bytes - 1) / piece_bytes;
+	if (n_pieces64 > 0x7fffffffll / 2) return BWAHIP_ECAPACITY;
+	const int n_pieces = (int)n_pieces64;
+	if ((rc = w.piece_first.ensure((size_t)n_pieces * 4))) return rc;
+	hipLaunchKernelGGL(k_piece_first, dim3((n_pieces + 255) / 256), dim3(256), 0, c->stream, w.out_off.as<int64_t>(), n, piece_bytes, n_pieces, w.piece_first.as<int>());
+	if ((rc = launched())) return rc;
+	std::vector<int> piece_first((size_t)n_pieces);
+	int64_t sum = 0; int err = 0;
+	HIP_TRY(hipMemcpyAsync(piece_first.data(), w.piece_first.p, (size_t)n_pieces * 4, hipMemcpyDeviceToHost, c->stream));
+	HIP_TRY(hipMemcpyAsync(&sum, w.out_off.as<int64_t>() + n, 8, hipMemcpyDeviceToHost, c->stream));
+	HIP_TRY(hipMemcpyAsync(&err, w.err.p, 4, hipMemcpyDeviceToHost, c->stream));
+	HIP_TRY(hipStreamSynchronize(c->stream));
+	if (err || sum != total) { fprintf(stderr, "[bwahip] sorted BAM: the runs' offsets give %lld bytes, the runs hold %lld\n", (long long)sum, (long long)total); return BWAHIP_EINTERNAL; }
+	for (int p = 0; p < n_pieces; ++p) if (piece_first[(size_t)p] < 0 || piece_first[(size_t)p] >= n || (p && piece_first[(size_t)p] < piece_first[(size_t)p - 1])) return BWAHIP_EINTERNAL;
+
+	// ---- the piece buffers, once: input, and the bound of the members ("input + 31 per block", as bgzf_deflate grows its output to)
+	const int64_t in_cap = total < piece_bytes ? total : piece_bytes;
+	const int64_t out_cap = in_cap + bgzf_blocks(in_cap) * 31 + 64;
+	for (int k = 0; k < 2; ++k)
+		if ((rc = w.in[k].ensure((size_t)in_cap)) || (rc = w.out[k].ensure((size_t)out_cap)) || (rc = w.tot[k].ensure(16)) || (rc = w.h_out[k].ensure((size_t)out_cap))) return rc;
+	if ((rc = w.h_tot.ensure(32))) return rc;
+	int64_t *h_tot = (int64_t*)w.h_tot.p;
+
+	// ---- gather and deflate piece k, download and write piece k - 1
+	auto piece_len = [&](int p) { const int64_t lo = (int64_t)p * piece_bytes; return total - lo < piece_bytes ? total - lo : piece_bytes; };
+	for (int k = 0; k <= n_pieces; ++k) {
+		if (k < n_pieces) {
+			const int b = k & 1;
+			if (k >= 2) HIP_TRY(hipStreamWaitEvent(c->stream, w.ev_down[b], 0));   // piece k - 2 has left out[b] (in[b]: the deflate of k - 2 is earlier in this stream)
+			const int64_t lo = (int64_t)k * piece_bytes, hi = lo + piece_len(k);
+			const int rec_lo = piece_first[(size_t)k];
+			const int rec_hi = k + 1 < n_pieces ? piece_first[(size_t)k + 1] : n - 1;   // inclusive: the record that holds the next cut begins in this piece or at the cut
+			const int n_rec = rec_hi - rec_lo + 1;
+			HIP_TRY(hipEventRecord(w.ev_gather[b], c->stream));
+			hipLaunchKernelGGL(k_gather_window, dim3((unsigned)(((int64_t)n_rec * 16 + 255) / 256)), dim3(256), 0, c->stream, w.addr.as<const uint8_t*>(), idx, w.out_off.as<int64_t>(),
+			                   rec_lo, n_rec, lo, hi, w.in[b].as<uint8_t>());
+			if ((rc = launched())) return rc;
+			HIP_TRY(hipEventRecord(w.ev_deflate[b], c->stream));
+			if ((rc = bgzf_deflate(c, w.in[b].as<uint8_t>(), hi - lo, w.out[b], w.tot[b].as<int64_t>(), c->stream))) return rc;
+			HIP_TRY(hipEventRecord(w.ev_done[b], c->stream));
+		}
+		if (k >= 1) {
+			const int b = (k - 1) & 1;
+			HIP_TRY(hipStreamWaitEvent(c->stream_copy, w.ev_done[b], 0));
+			HIP_TRY(hipMemcpyAsync(h_tot + 2 * b, w.tot[b].p, 16, hipMemcpyDeviceToHost, c->stream_copy));
+			HIP_TRY(hipStreamSynchronize(c->stream_copy));
+			const int64_t got = h_tot[2 * b], plen = piece_len(k - 1);
+			if (got < 0 || got > plen + bgzf_blocks(plen) * 31) return BWAHIP_EINTERNAL;
+			if (got) HIP_TRY(hipMemcpyAsync(w.h_out[b].p, w.out[b].p, (size_t)got, hipMemcpyDeviceToHost, c->stream_copy));
+			HIP_TRY(hipEventRecord(w.ev_down[b], c->stream_copy));
+			HIP_TRY(hipEventSynchronize(w.ev_down[b]));
+			float ms = 0;
+			if (hipEventElapsedTime(&ms, w.ev_gather[b], w.ev_deflate[b]) == hipSuccess) s.gather_ms += ms;
+			if (hipEventElapsedTime(&ms, w.ev_deflate[b], w.ev_done[b]) == hipSuccess) s.deflate_ms += ms;
+			s.bgzf_bytes += got; s.n_stored += h_tot[2 * b + 1];
+			if (fd >= 0 && (rc = write_full(fd, (const uint8_t*)w.h_out[b].p, got))) { (void)hipStreamSynchronize(c->stream); return rc; }
+		}
+	}
+	HIP_TRY(hipStreamSynchronize(c->stream));
+	{ float ms = 0; if (hipEventElapsedTime(&ms, w.ev_sort[0], w.ev_sort[1]) == hipSuccess) s.sort_ms = ms; }
+	s.hbm_bytes += (int64_t)(w.bytes() + bs.keys[0].cap + bs.keys[1].cap + bs.idx[0].cap + bs.idx[1].cap + bs.hist.cap + bs.hist_base.cap +
+	                         c->bz.slots.cap + c->bz.mlen.cap + c->bz.moff.cap + c->bz.md.cap + c->bz.cnt.cap);
+	s.finish_s = now_s() - t0;
+	if (st) *st = s;
+	return 0;
+}
+
+extern "C" void bwahip_bam_devmerger_close(bwahip_bam_devmerger *m)
+{
+	if (!m) return;
+	(void)hipSetDevice(m->c->device);
+	for (hipStream_t q : { m->c->stream_copy, m->c->stream }) if (q) (void)hipStreamSynchronize(q);   // after a failed finish work may still be queued on the buffers
+	for (auto &kv : m->runs) bam_devrun_free(kv.second);
+	m->w.release();
+	delete m;
+}

@@ -402,6 +402,7 @@ int bwahip_ctx_tune(bwahip_ctx *c, const char *key, int value)
 	else if (!strcmp(key, "spec_min_chains")) k.spec_min_chains = value;
 	else if (!strcmp(key, "ext_lds_window")) k.ext_lds_window = value < 1 ? 1 : value;
 	else if (!strcmp(key, "ext_early_stop")) { if (value != 0 && value != 1) return BWAHIP_EINVAL; k.ext_early_stop = value; }
+	else if (!strcmp(key, "sorted_piece_blocks")) { if (value < 1 || value > 4096) return BWAHIP_EINVAL; k.sorted_piece_blocks = value; }
 	else if (!strcmp(key, "gpu_final")) k.gpu_final = value;
 	else if (!strcmp(key, "gpu_pair")) k.gpu_pair = value;
 	else if (!strcmp(key, "verbose")) k.verbose = value;

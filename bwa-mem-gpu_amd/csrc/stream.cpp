@@ -20,6 +20,7 @@
 // (tests/test_gpu_multi.py).  No data-path collective: SURVEY.md 8(e).
 #include "../../include/bwahip.h"
 #include "stream_pipe.h"
+#include "ctx_internal.h"                                       // the contexts' devices, the runs a device merger holds (k_bammerge.hip)
 #include <errno.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -48,7 +49,7 @@ struct Driver {
 	// writer side
 	std::mutex mu;
 	std::condition_variable cv_item, cv_done;
-	struct Item { const char *p; int64_t len; int ctx, out; const uint64_t *keys; const int64_t *rec_off; int64_t n_rec; int64_t raw_len; };   // ctx / out: the output set the bytes sit in; keys, rec_off: coordinate-sorted BAM
+	struct Item { const char *p; int64_t len; int ctx, out; const uint64_t *keys; const int64_t *rec_off; int64_t n_rec; int64_t raw_len; DevRun *run; };   // ctx / out: the output set the bytes sit in; keys, rec_off: coordinate-sorted BAM; run (bam == 4): the batch as a run in HBM -- no bytes, and the output set went back to its context already
 	std::map<int64_t, Item> ready;                               // finished batches waiting for their turn
 	int64_t written = 0;                                         // batches [0, written) are on the descriptor
 	int workers_left = 0;
@@ -60,12 +61,50 @@ struct Driver {
 	int bam = 0, level = 0, deflate_threads = 1;                 // bwahip_stream_run_bam: the batches' records go through the BGZF writer
 	bwahip_bam_merger *merger = nullptr;                         // bam == 2 (bwahip_stream_run_bam_sorted): every batch is a sorted run of the merger instead
 	double sort_ms = 0;
+	// bam == 4 (bwahip_stream_run_bam_sorted_dev): every batch is a run of the device merger while the HBM budget holds; from the first run
+	// that does not fit (or came back downloaded because its buffers could not be allocated) every run goes to the host merger
+	bwahip_bam_devmerger *devm = nullptr;
+	bwahip_sort_dev_t *sd = nullptr;
+	bwahip_ctx *ctx0 = nullptr;
+	int64_t hbm_budget = 0, held_raw = 0, held_rec = 0;
+	int piece_blocks = 0;
+	std::atomic<bool> fell_back{false};                          // read by the drainers: from now on they download
+	hipStream_t fb_stream = nullptr;                             // the fall-back's downloads: one pinned buffer each for records, keys and offsets
+	HostBuf fb_rec, fb_keys, fb_off;
 	bwahip_bgzf_stats_t bz = { 0, 0, 0, 0, 0 };                  // bam == 3 (bwahip_stream_run_bam_dev): the batches arrive as BGZF members and are only written
 	int64_t sam_bytes = 0;
 	double t_last_write = 0, write_s = 0;
 
 	void fail(int code) { { std::lock_guard<std::mutex> lk(mu); if (!rc) rc = code; stop = true; } cv_item.notify_all(); cv_done.notify_all(); if (wake_all) wake_all(); }
 	bool failed() { return stop.load(); }
+
+	// a run in HBM -> the host merger, through the pinned buffers; the run is freed whatever happens
+	int run_to_host(int64_t run_no, DevRun *r)
+	{
+		int rc = hipSetDevice(ctx0->device) == hipSuccess ? 0 : BWAHIP_ENODEV;
+		if (!rc && !fb_stream && hipStreamCreateWithFlags(&fb_stream, hipStreamNonBlocking) != hipSuccess) rc = BWAHIP_ENODEV;
+		if (!rc && ((rc = fb_rec.ensure((size_t)r->len + 1)) || (rc = fb_keys.ensure((size_t)(r->n_rec + 1) * 8)) || (rc = fb_off.ensure((size_t)(r->n_rec + 1) * 8)))) {}
+		if (!rc) rc = bam_devrun_download(r, (uint8_t*)fb_rec.p, (uint64_t*)fb_keys.p, (int64_t*)fb_off.p, fb_stream);
+		if (!rc) rc = bwahip_bam_merger_add(merger, run_no, (const uint8_t*)fb_rec.p, r->len, (const uint64_t*)fb_keys.p, (const int64_t*)fb_off.p, r->n_rec);
+		bam_devrun_free(r);
+		return rc;
+	}
+	// run `at` does not fit: the host merger is opened (only now is tmp_dir looked at) and takes the runs held so far, in run order
+	int fall_back(int64_t at)
+	{
+		int rc = bwahip_bam_merger_open(sd->tmp_dir, sd->mem_budget, &merger);
+		std::vector<std::pair<int64_t, DevRun*>> held;
+		bam_devmerger_take_runs(devm, &held);
+		for (auto &h : held) { if (!rc) rc = run_to_host(h.first, h.second); else bam_devrun_free(h.second); }
+		fell_back = true; sd->fell_back = 1; sd->fell_back_at_run = at;
+		return rc;
+	}
+	void fb_release()
+	{
+		if (ctx0) (void)hipSetDevice(ctx0->device);
+		if (fb_stream) { (void)hipStreamDestroy(fb_stream); fb_stream = nullptr; }
+		fb_rec.release(); fb_keys.release(); fb_off.release();
+	}
 
 	void writer()
 	{
@@ -80,7 +119,19 @@ struct Driver {
 			}
 			const double t0 = now_s();
 			int64_t o = 0;
-			if (bam == 2) {                                              // the merger copies (or spills) the run: the set goes back at once
+			if (bam == 4) {
+				int r = 0;
+				if (!fell_back) {                                       // in input order, so the decision depends on the input and the budget alone
+					const bool fits = it.run && bwahip_bam_devmerge_hbm_need(held_raw + it.raw_len, held_rec + it.n_rec, written + 1, piece_blocks) <= hbm_budget;
+					if (!fits) r = fall_back(written);
+				}
+				if (!r && !fell_back) { if (!(r = bam_devmerger_adopt(devm, written, it.run))) { it.run = nullptr; held_raw += it.raw_len; held_rec += it.n_rec; } }
+				else if (!r && it.run) { r = run_to_host(written, it.run); it.run = nullptr; }
+				else if (!r) r = bwahip_bam_merger_add(merger, written, (const uint8_t*)it.p, it.len, it.keys, it.rec_off, it.n_rec);
+				if (it.run) bam_devrun_free(it.run);                    // refused, or the fall-back failed before its turn
+				if (r) { fail(r); return; }
+				o = it.len;
+			} else if (bam == 2) {                                       // the merger copies (or spills) the run: the set goes back at once
 				const int r = bwahip_bam_merger_add(merger, written, (const uint8_t*)it.p, it.len, it.keys, it.rec_off, it.n_rec);
 				if (r) { fail(r); return; }
 				o = it.len;
@@ -121,27 +172,49 @@ Reaper g_reaper;
 // 2 = coordinate-sorted BAM: every batch leaves its context sorted and becomes a run of the merger (the batch number is the run number);
 // after the last batch: header, the merge of the runs through the BGZF writer, the EOF block
 static int stream_run(bwahip_ctx *const *ctxs, int n_ctx, const bwahip_opt_t *opt, const bwahip_pestat_t *pes0,
-                      const char *fq1, const char *fq2, int out_fd, bwahip_stream_t *st, int bam, const char *hdr_line, int level, bwahip_sort_t *so = nullptr, bwahip_bgzf_stats_t *bs = nullptr)
+                      const char *fq1, const char *fq2, int out_fd, bwahip_stream_t *st, int bam, const char *hdr_line, int level, bwahip_sort_t *so = nullptr, bwahip_bgzf_stats_t *bs = nullptr,
+                      bwahip_sort_dev_t *sd = nullptr)
 {
-	if (!ctxs || n_ctx < 1 || n_ctx > 256 || !opt || !fq1 || !st || (bam == 2 && !so) || (bam == 3 && !bs)) return BWAHIP_EINVAL;
+	if (!ctxs || n_ctx < 1 || n_ctx > 256 || !opt || !fq1 || !st || (bam == 2 && !so) || (bam == 3 && !bs) || (bam == 4 && !sd)) return BWAHIP_EINVAL;
 	for (int i = 0; i < n_ctx; ++i) if (!ctxs[i]) return BWAHIP_EINVAL;
 	if (bam && (level < 0 || level > 9)) return BWAHIP_EINVAL;
+	if (bam == 4) {
+		for (int i = 1; i < n_ctx; ++i) if (ctxs[i]->device != ctxs[0]->device) return BWAHIP_EINVAL;   // the runs of all contexts meet in one device's merger
+		if (sd->piece_blocks > 4096 || sd->hbm_budget < 0 || sd->level < 0 || sd->level > 9) return BWAHIP_EINVAL;
+	}
+	const int bam_pipe = bam == 4 ? 2 : bam;                       // what the contexts compute: mode 4 is mode 2 up to the stage-out
 	// actual_chunk_size (fastmap.c:304): -K when given, else chunk_size * n_threads
 	const int64_t chunk = st->chunk_bases > 0 ? st->chunk_bases : (int64_t)opt->chunk_size * (opt->n_threads > 0 ? opt->n_threads : 1);
 	bwahip_opt_t o = *opt;
 	if (fq2) o.flag |= BWAHIP_F_PE;
 	// opt->n_threads is the host-thread budget of the whole run; BAM: half of it deflates, the other half stages the batches
 	// (bam == 3: the GPU deflates, all of it stages)
-	const int n_deflate = bam && bam != 3 ? (opt->n_threads / 2 > 1 ? opt->n_threads / 2 : 1) : 0;
+	const int n_deflate = bam && bam != 3 && bam != 4 ? (opt->n_threads / 2 > 1 ? opt->n_threads / 2 : 1) : 0;
 	const int n_stage = bam && opt->n_threads > n_deflate ? opt->n_threads - n_deflate : opt->n_threads;
 	o.n_threads = n_stage / n_ctx > 1 ? n_stage / n_ctx : 1;
 	Driver d;
 	d.fd = out_fd; d.max_reads = st->max_reads;
 	d.bam = bam; d.level = level; d.deflate_threads = n_deflate;
 	struct Sorted {                                              // the header waits for the merge; the merger and its files go whatever happens
-		uint8_t *hdr = nullptr; int64_t hlen = 0; bwahip_bam_merger *m = nullptr;
-		~Sorted() { free(hdr); bwahip_bam_merger_close(m); }
+		uint8_t *hdr = nullptr; int64_t hlen = 0; bwahip_bam_merger *m = nullptr; bwahip_bam_devmerger *dm = nullptr;
+		~Sorted() { free(hdr); bwahip_bam_merger_close(m); bwahip_bam_devmerger_close(dm); }
 	} sorted;
+	if (bam == 4) {
+		sd->fell_back = 0; sd->fell_back_at_run = 0; sd->n_records = sd->n_runs = sd->spilled_bytes = 0; sd->sort_ms = sd->merge_s = 0;
+		memset(&sd->dev, 0, sizeof sd->dev);
+		int hr = bwahip_bam_header_sorted(bwahip_bns(ctxs[0]), hdr_line, &sorted.hdr, &sorted.hlen);
+		if (!hr) hr = bwahip_bam_devmerger_open(ctxs[0], sd->piece_blocks, &sorted.dm);
+		if (hr) return hr;
+		d.devm = sorted.dm; d.sd = sd; d.ctx0 = ctxs[0];
+		d.piece_blocks = sd->piece_blocks > 0 ? sd->piece_blocks : ctxs[0]->knobs.sorted_piece_blocks;
+		d.hbm_budget = sd->hbm_budget;
+		if (!d.hbm_budget) {                                         // half of what the device has free now
+			size_t mem_free = 0, mem_total = 0;
+			HIP_TRY(hipSetDevice(ctxs[0]->device));
+			HIP_TRY(hipMemGetInfo(&mem_free, &mem_total));
+			d.hbm_budget = (int64_t)(mem_free / 2);
+		}
+	}
 	if (bam == 2) {
 		so->n_records = so->n_runs = so->spilled_bytes = 0; so->sort_ms = so->merge_s = 0;
 		int hr = bwahip_bam_header_sorted(bwahip_bns(ctxs[0]), hdr_line, &sorted.hdr, &sorted.hlen);
@@ -184,8 +257,10 @@ static int stream_run(bwahip_ctx *const *ctxs, int n_ctx, const bwahip_opt_t *op
 	d.wake_all = [&] { for (auto &p : pipes) { { std::lock_guard<std::mutex> lk(p.mu); } p.cv.notify_all(); } };
 	d.on_written = [&](const Driver::Item &it, int64_t seq_no, double t0, double t1) {
 		Pipe &p = pipes[it.ctx];
-		{ std::lock_guard<std::mutex> lk(p.mu); p.out_free[it.out] = true; }
-		p.cv.notify_all();
+		if (it.p) {                                                  // (a run that stayed in HBM: its drainer gave the set back, and it may be in use again)
+			{ std::lock_guard<std::mutex> lk(p.mu); p.out_free[it.out] = true; }
+			p.cv.notify_all();
+		}
 		span("write", seq_no, it.ctx, t0, t1);
 	};
 	int n_open = 0;
@@ -222,7 +297,7 @@ static int stream_run(bwahip_ctx *const *ctxs, int n_ctx, const bwahip_opt_t *op
 			if (eof) break;
 			span("take", j.seq_no, w, t0, t1);
 			double t_copy = t1;
-			const int r = pipe_stage_in(ctxs[w], j.in, &o, j.n, seqs, bam, &t_copy);
+			const int r = pipe_stage_in(ctxs[w], j.in, &o, j.n, seqs, bam_pipe, &t_copy);
 			bwahip_fastq_batch_release(b);                          // names, bases and qualities are in HBM
 			const double t2 = now_s();
 			if (r) { d.fail(r); break; }
@@ -246,7 +321,7 @@ static int stream_run(bwahip_ctx *const *ctxs, int n_ctx, const bwahip_opt_t *op
 			}
 			const double t0 = now_s();
 			double t_hot = t0;
-			const int r = pipe_compute(ctxs[w], j.in, j.out, &o, j.np0, pes0, bam, &t_hot);
+			const int r = pipe_compute(ctxs[w], j.in, j.out, &o, j.np0, pes0, bam_pipe, &t_hot);
 			if (r) { d.fail(r); break; }
 			span("hot", j.seq_no, w, t0, t_hot);
 			j.t_final = t_hot;
@@ -269,6 +344,25 @@ static int stream_run(bwahip_ctx *const *ctxs, int n_ctx, const bwahip_opt_t *op
 			}
 			const char *sam = nullptr; int64_t len = 0;
 			double t_end = 0;
+			if (bam == 4 && !d.fell_back) {                           // the run stays in HBM: no download, the writer gets an item without bytes
+				DevRun *run = nullptr; int64_t raw = 0, nr = 0; double sort_ms = 0;
+				const int r4 = pipe_stage_out_devrun(ctxs[w], j.out, &run, &raw, &nr, &sort_ms, &t_end);
+				if (r4) { d.fail(r4); break; }
+				if (run) {
+					const double t1 = now_s();
+					{ std::lock_guard<std::mutex> lk(p.mu); p.in_free[j.in] = true; p.out_free[j.out] = true; }   // the copies have ended: both sets go back at once
+					p.cv.notify_all();
+					span("final", j.seq_no, w, j.t_final, t_end); span("d2d", j.seq_no, w, t_end, t1);
+					{
+						std::lock_guard<std::mutex> lk(d.mu);
+						if (d.rc) bam_devrun_free(run);                     // the writer has gone: nobody would take it
+						else d.ready[j.seq_no] = { nullptr, raw, w, j.out, nullptr, nullptr, nr, raw, run };
+						d.sort_ms += sort_ms;
+					}
+					d.cv_item.notify_all();
+					continue;
+				}
+			}                                                         // (its buffers could not be allocated: downloaded as any run after a fall-back, which it causes)
 			const int r = pipe_stage_out(ctxs[w], j.out, &sam, &len, &t_end);
 			const double t1 = now_s();
 			if (r) { d.fail(r); break; }
@@ -277,13 +371,13 @@ static int stream_run(bwahip_ctx *const *ctxs, int n_ctx, const bwahip_opt_t *op
 			span("final", j.seq_no, w, j.t_final, t_end); span("d2h", j.seq_no, w, t_end, t1);
 			const uint64_t *keys = nullptr; const int64_t *rec_off = nullptr; int64_t n_rec = 0;
 			double sort_ms = 0;
-			if (bam == 2) { const int r2 = pipe_stage_out_sorted(ctxs[w], j.out, &keys, &rec_off, &n_rec, &sort_ms); if (r2) { d.fail(r2); break; } }
+			if (bam_pipe == 2) { const int r2 = pipe_stage_out_sorted(ctxs[w], j.out, &keys, &rec_off, &n_rec, &sort_ms); if (r2) { d.fail(r2); break; } }
 			int64_t raw_len = len, n_blocks = 0, n_stored = 0;
 			double deflate_ms = 0;
 			if (bam == 3) { const int r3 = pipe_stage_out_bgzf(ctxs[w], j.out, &raw_len, &n_blocks, &n_stored, &deflate_ms); if (r3) { d.fail(r3); break; } }
 			{
 				std::lock_guard<std::mutex> lk(d.mu);
-				d.ready[j.seq_no] = { sam, len, w, j.out, keys, rec_off, n_rec, raw_len };
+				d.ready[j.seq_no] = { sam, len, w, j.out, keys, rec_off, n_rec, raw_len, nullptr };
 				d.sort_ms += sort_ms;
 				if (bam == 3) { d.bz.raw_bytes += raw_len; d.bz.bgzf_bytes += len; d.bz.n_blocks += n_blocks; d.bz.n_stored += n_stored; d.bz.deflate_ms += deflate_ms; }
 			}
@@ -312,6 +406,27 @@ static int stream_run(bwahip_ctx *const *ctxs, int n_ctx, const bwahip_opt_t *op
 		d.write_s += now_s() - t0;
 		bwahip_bam_merger_stats(sorted.m, &so->n_records, &so->n_runs, &so->spilled_bytes, &so->merge_s);
 		so->sort_ms = d.sort_ms;
+	}
+	if (bam == 4) {
+		for (auto &kv : d.ready) if (kv.second.run) bam_devrun_free(kv.second.run);   // after a failure: runs nobody took
+		d.ready.clear();
+		d.fb_release();
+		sorted.m = d.merger;                                        // closed (and its files removed) whatever happens
+	}
+	if (bam == 4 && !d.rc) {                                     // every run is with one of the two mergers: header, merge, end-of-file block
+		const double t0 = now_s();
+		const bool fb = d.fell_back;
+		int r = bwahip_bgzf_write(out_fd, sorted.hdr, sorted.hlen, fb ? sd->level : 1, 1);
+		if (!r && fb) {                                             // from here on this is bwahip_stream_run_bam_sorted at sd->level
+			r = bwahip_bam_merger_finish(sorted.m, out_fd, sd->level, opt->n_threads > 1 ? opt->n_threads : 1);
+			bwahip_bam_merger_stats(sorted.m, &sd->n_records, &sd->n_runs, &sd->spilled_bytes, &sd->merge_s);
+		} else if (!r) {
+			r = bwahip_bam_devmerger_finish(sorted.dm, out_fd, &sd->dev);
+			sd->n_records = sd->dev.n_records; sd->n_runs = sd->dev.n_runs; sd->merge_s = sd->dev.finish_s;
+		}
+		if (r) d.rc = r;
+		d.write_s += now_s() - t0;
+		sd->sort_ms = d.sort_ms;
 	}
 	if (bam && !d.rc) { const int r = bwahip_bgzf_eof(out_fd); if (r) d.rc = r; d.t_last_write = now_s(); }
 	const double t_joined = now_s();
@@ -359,4 +474,14 @@ extern "C" int bwahip_stream_run_bam_dev(bwahip_ctx *const *ctxs, int n_ctx, con
 	if (!bs) return BWAHIP_EINVAL;
 	memset(bs, 0, sizeof *bs);
 	return stream_run(ctxs, n_ctx, opt, pes0, fq1, fq2, out_fd, st, 3, hdr_line, 1, nullptr, bs);
+}
+
+// FASTQ files in -> a coordinate-sorted BAM file out with the runs kept in HBM: every batch is sorted on its context as above, copied device
+// to device into buffers of its own and merged, gathered and deflated on ctxs[0]'s device after the last batch (k_bammerge.hip); when the
+// runs outgrow sd->hbm_budget the run ends as bwahip_stream_run_bam_sorted does, on the host
+extern "C" int bwahip_stream_run_bam_sorted_dev(bwahip_ctx *const *ctxs, int n_ctx, const bwahip_opt_t *opt, const bwahip_pestat_t *pes0,
+                                                const char *fq1, const char *fq2, int out_fd, const char *hdr_line, bwahip_stream_t *st, bwahip_sort_dev_t *sd)
+{
+	if (!sd) return BWAHIP_EINVAL;
+	return stream_run(ctxs, n_ctx, opt, pes0, fq1, fq2, out_fd, st, 4, hdr_line, 1, nullptr, nullptr, sd);
 }

@@ -32,5 +32,11 @@ int pipe_stage_out_sorted(bwahip_ctx *c, int out, const uint64_t **keys, const i
 // After pipe_stage_out of a batch computed with bam == 3 (BGZF members, k_bgzf.hip): the uncompressed bytes of the records, the number of
 // members and of stored ones, and the GPU time of the deflate stage.
 int pipe_stage_out_bgzf(bwahip_ctx *c, int out, int64_t *raw_len, int64_t *n_blocks, int64_t *n_stored, double *deflate_ms);
+// The stage-out of a batch computed with bam == 2 whose run stays in HBM (bwahip_stream_run_bam_sorted_dev): nothing is downloaded.  Waits for
+// the batch's kernels (*t_kernels_end; the input set is free from here on), allocates the run's own device buffers and copies records,
+// keys and offsets device to device on the copy stream (awaited: output set `out` is free on return).  *run == nullptr with a return of 0:
+// the buffers could not be allocated -- the caller downloads the set with pipe_stage_out / pipe_stage_out_sorted instead.
+struct DevRun;
+int pipe_stage_out_devrun(bwahip_ctx *c, int out, DevRun **run, int64_t *raw_len, int64_t *n_rec, double *sort_ms, double *t_kernels_end);
 // buffers freed and allocated again since the library was loaded (DevBuf / HostBuf ::ensure)
 long pipe_realloc_count();

@@ -376,6 +376,53 @@ typedef struct {
 int bwahip_stream_run_bam_sorted(bwahip_ctx *const *ctxs, int n_ctx, const bwahip_opt_t *opt, const bwahip_pestat_t *pes0, const char *fq1, const char *fq2,
                                  int out_fd, const char *hdr_line, int level, bwahip_stream_t *st, bwahip_sort_t *so);
 
+/* Merger of sorted runs that stay in HBM (csrc/k_bammerge.hip): the same contract as bwahip_bam_merger_* -- no record is parsed, a run is
+ * bytes + sorted keys + n_rec + 1 offsets, the order is (key, run_no, position in the run) over all 64 bits of the key -- with the merge,
+ * the gather and the deflate on the context's device.  open: piece_blocks = BGZF blocks gathered and deflated at a time (1 .. 4096;
+ * <= 0: the context's "sorted_piece_blocks", bwahip_ctx_tune).  add: host pointers, uploaded into device buffers of the run's own (the
+ * caller's are free on return); thread-safe; a run_no given twice, offsets that do not start at 0, end at len and never decrease:
+ * BWAHIP_EINVAL; more than 2^31 - 1 records in total (or one record of 2^31 bytes or more): BWAHIP_ECAPACITY; a failed allocation:
+ * BWAHIP_ENOMEM -- after any refused add the merger holds what it held before and stays usable.  finish: one stable radix sort of all keys
+ * in (run_no, position) order, then pieces of piece_blocks x 65 280 bytes of the sorted byte stream are gathered from the runs and
+ * deflated (k_bgzf.hip) while the members of the piece before travel to the host and are written to fd (< 0: produced and dropped) -- no
+ * header, no EOF block.  The members are those of one deflate stage over all records in order (bwahip_kat_bgzf of the sorted
+ * concatenation), whatever piece_blocks, however the records were cut into runs and in whichever order the runs were added.  *st (may be
+ * NULL): records, runs, bytes of the records, of the members, members, members that left stored, HBM held at the end of finish (runs
+ * and working set), GPU time of the sort, the gathers and the deflate stages, and the seconds finish took.  finish runs on the
+ * context's streams: no other call on the context meanwhile.  close (before the context is destroyed) frees everything. */
+typedef struct bwahip_bam_devmerger bwahip_bam_devmerger;
+typedef struct { int64_t n_records, n_runs, raw_bytes, bgzf_bytes, n_blocks, n_stored, hbm_bytes; double sort_ms, gather_ms, deflate_ms, finish_s; } bwahip_devmerge_stats_t;
+int  bwahip_bam_devmerger_open(bwahip_ctx *ctx, int piece_blocks, bwahip_bam_devmerger **m);
+int  bwahip_bam_devmerger_add(bwahip_bam_devmerger *m, int64_t run_no, const uint8_t *rec, int64_t len, const uint64_t *keys, const int64_t *rec_off, int64_t n_rec);
+int  bwahip_bam_devmerger_finish(bwahip_bam_devmerger *m, int fd, bwahip_devmerge_stats_t *st);
+void bwahip_bam_devmerger_close(bwahip_bam_devmerger *m);
+/* HBM a device merger takes for runs of raw_bytes bytes and n_records records in all, finish included (no device is touched): the
+ * runs (raw_bytes + 16 per record + 8 per run), and as working set, counted with the eighth of slack its buffers grow with: the sort's
+ * and the source table's 48 bytes per record, two piece inputs, two piece outputs and the deflate stage's slots (4 x 65 280 + 2 x 31 +
+ * 65 536 + 12 bytes per block of a piece, a piece no longer than the records), and 64 MiB for the deflate stage's per-workgroup words.
+ * An argument < 0 or piece_blocks outside 1 .. 4096: -1. */
+int64_t bwahip_bam_devmerge_hbm_need(int64_t raw_bytes, int64_t n_records, int64_t n_runs, int piece_blocks);
+
+/* bwahip_stream_run_bam_sorted with the runs kept in HBM and merged, gathered and deflated there after the last batch
+ * (bwahip_bam_devmerger_* on ctxs[0]): nothing of a batch travels to the host before the end, and what travels then is BGZF members.
+ * All contexts must be on one device (BWAHIP_EINVAL otherwise, before anything starts).  The header goes through bwahip_bgzf_write at
+ * level 1; the records' members are bwahip_kat_bgzf of the sorted records.  sd in: hbm_budget = bytes of HBM the runs and the finish may
+ * take (bwahip_bam_devmerge_hbm_need of the runs so far, taken in input order; 0: half of the device's free memory when the run
+ * starts), piece_blocks as for bwahip_bam_devmerger_open; tmp_dir, mem_budget and level belong to the host merger and are used only after
+ * a fall-back: when run k would exceed hbm_budget (or its device buffers cannot be allocated), the runs held so far are downloaded into a
+ * host merger in run order, every later run is downloaded as bwahip_stream_run_bam_sorted does, and the file is exactly that entry
+ * point's at `level` (fell_back = 1, fell_back_at_run = k, dev all zero; a tmp_dir that cannot be used: BWAHIP_EIO then, not before).
+ * sd out: n_records, n_runs, spilled_bytes, sort_ms (the batches' sorts), merge_s (the finish, device or host) as bwahip_sort_t. */
+typedef struct {
+	const char *tmp_dir; int64_t mem_budget; int level;                         /* in: the host merger after a fall-back */
+	int64_t hbm_budget; int piece_blocks;                                       /* in */
+	int fell_back; int64_t fell_back_at_run;                                    /* out */
+	int64_t n_records, n_runs, spilled_bytes; double sort_ms, merge_s;         /* out */
+	bwahip_devmerge_stats_t dev;                                                /* out */
+} bwahip_sort_dev_t;
+int bwahip_stream_run_bam_sorted_dev(bwahip_ctx *const *ctxs, int n_ctx, const bwahip_opt_t *opt, const bwahip_pestat_t *pes0, const char *fq1, const char *fq2,
+                                     int out_fd, const char *hdr_line, bwahip_stream_t *st, bwahip_sort_dev_t *sd);
+
 /* Insert-size statistics (mem_pestat_t[4]: FF, FR, RF, RR; bwamem_pair.c:72) and mate-rescue counters ([0] local alignments
  * run, [1] regions added, [2] most alignments of one pair, [3] pairs that needed any; bwamem_pair.c:137) of the last
  * paired-end batch finalised on the GPU.  Either pointer may be NULL; counters4 receives 4 values. */
@@ -518,7 +565,8 @@ int bwahip_kat_ksw_align(bwahip_ctx *ctx, int n, const int *params, const int8_t
 /* Tuning knobs of the heavy-read hand-off kernels (tests force each one onto ordinary reads): keys intv_cap,
  * smem_lanes, heavy_mult, chain_big_min, rank_sort_min, spec_min_chains, ext_lds_window, verbose; and ext_early_stop (default 1): every
  * device form of ksw_extend2 ends its row loop once no later row can change score, qle, tle, gtle, gscore or max_off --
- * 0 runs every row to the end as the reference does (same results, more rows).
+ * 0 runs every row to the end as the reference does (same results, more rows); and sorted_piece_blocks (1 .. 4096, default 1024): the
+ * BGZF blocks a device merger gathers and deflates at a time (bwahip_bam_devmerger_open with piece_blocks <= 0; the bytes do not depend on it).
  * The same knobs are read from the environment (BWAHIP_<KEY>) once, when the context is created. */
 int bwahip_ctx_tune(bwahip_ctx *ctx, const char *key, int value);
 
