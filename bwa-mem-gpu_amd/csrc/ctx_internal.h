@@ -108,14 +108,17 @@ struct Bgzf {
 	void release() { for (DevBuf *b : { &slots, &mlen, &moff, &md, &cnt }) b->release(); }
 };
 
+// The form a batch's output leaves run_final in (d_sam): SAM text; BAM records in read order (k_bam.hip); the records in coordinate order with their
+// keys and offsets (k_bamsort.hip: written to bs.raw, sorted into d_sam); the records as BGZF members (k_bgzf.hip: written to bs.raw, deflated into d_sam)
+enum class OutForm { Sam, Bam, BamSorted, Bgzf };
+inline bool is_bam(OutForm f) { return f != OutForm::Sam; }
+
 struct StreamPipe;                       // final_rt.hip: the second sets of batch buffers the stream driver's three stages work on
 
 struct bwahip_ctx {
 	StreamPipe *pipe = nullptr;          // made by the first bwahip_stream_run on this context, kept (buffers do not shrink), freed with the context
 	BatchText batch_text;
-	bool want_sorted = false;            // run_final (BAM): the records leave in coordinate order (k_bamsort.hip), with their keys and offsets
 	BamSort bs;
-	bool want_bgzf = false;              // run_final (BAM): the records leave as BGZF members (k_bgzf.hip): written to bs.raw, deflated into d_sam
 	Bgzf bz;
 	DevBuf d_bgzf_tot;                   // the deflated batch in d_sam: [0] its bytes, [1] blocks that left stored (int64 each)
 	int64_t n_bgzf_blocks = 0;
@@ -124,7 +127,6 @@ struct bwahip_ctx {
 	int64_t n_rec = 0;
 	hipEvent_t ev_sort[4] = {};          // begin of the record table, of the radix sort, of the gather, and the end
 	HostBuf h_skeys[2], h_rec_off[2];    // pinned: keys and offsets of bwahip_process_seqs_bam_sorted (taken in turn with h_sam / h_sam2)
-	bool want_host_sam_off = false;      // run_final copies the SAM offsets to h_sam_off ahead of the write pass (bwahip_process_seqs)
 	std::vector<int64_t> h_sam_off;      // offsets of the reads' SAM text in h_sam (bwahip_process_seqs / _text)
 	bool external_index = false;
 	bool index_resident = false;         // d_bwt / d_sa / d_pac were filled before ctx_setup (bwahip_init_rccl)
@@ -185,7 +187,7 @@ int launch_scan(const int *in, int64_t *out, int n, DevBuf &tmp, hipStream_t st)
 int launch_nt4(uint8_t *seq, int64_t n, hipStream_t st);   // runtime.hip: ASCII / codes -> codes 0..4 in place (nst_nt4_table)
 int dev_upload(DevBuf &b, const void *src, size_t bytes, hipStream_t st);
 int run_pipeline(bwahip_ctx *c, const bwahip_opt_t *opt, bool timed, bool dump);      // the hot path over the uploaded batch
-int run_final(bwahip_ctx *c, const bwahip_opt_t *opt, int64_t n_processed, const bwahip_pestat_t *pes0, bool timed, bool bam = false);   // regions in HBM -> SAM text (or, bam: BAM records) in HBM (SE, or PE when opt->flag has MEM_F_PE)
+int run_final(bwahip_ctx *c, const bwahip_opt_t *opt, int64_t n_processed, const bwahip_pestat_t *pes0, bool timed, OutForm form, bool host_sam_off = false);   // regions in HBM -> the batch in `form` in HBM (SE, or PE when opt->flag has MEM_F_PE); host_sam_off: the offsets travel to h_sam_off ahead of the write pass (bwahip_process_seqs)
 // k_bamsort.hip: the records of c->bs.raw (per-read offsets c->d_sam_off, n_reads + 1) in coordinate order into c->d_sam, their keys into
 // c->d_skeys, their offsets into c->d_rec_off; sets c->n_rec.  Queued on c->stream (with two small read-backs awaited in between).
 int bam_sort_batch(bwahip_ctx *c, int n_reads, int64_t total);

@@ -183,18 +183,18 @@ static int run_pe_rescue(bwahip_ctx *c, const bwahip_opt_t *opt, const DevOpt &d
 }
 
 // K6 -> K9 over the batch run_pipeline left in HBM.  The text inputs (d_qual, d_names, ...) must be uploaded.
-int run_final(bwahip_ctx *c, const bwahip_opt_t *opt, int64_t n_processed, const bwahip_pestat_t *pes0, bool timed, bool bam)
+int run_final(bwahip_ctx *c, const bwahip_opt_t *opt, int64_t n_processed, const bwahip_pestat_t *pes0, bool timed, OutForm form, bool host_sam_off)
 {
 	// the two output passes in the batch's format: SAM text (k_sam.hip) or BAM records (k_bam.hip)
 	auto launch_out = [&](const FinLaunch &fl, bool write, int lo, int hi) {
 		const bool pe_ = (opt->flag & BWAHIP_F_PE) != 0;
-		return bam ? (pe_ ? launch_bam_pe(fl, write, c->stream, lo, hi) : launch_bam(fl, write, c->stream, lo, hi)) : (pe_ ? launch_sam_pe(fl, write, c->stream, lo, hi) : launch_sam(fl, write, c->stream, lo, hi));
+		return is_bam(form) ? (pe_ ? launch_bam_pe(fl, write, c->stream, lo, hi) : launch_bam(fl, write, c->stream, lo, hi)) : (pe_ ? launch_sam_pe(fl, write, c->stream, lo, hi) : launch_sam(fl, write, c->stream, lo, hi));
 	};
 	const int n = c->n_reads;
 	const bool pe = (opt->flag & BWAHIP_F_PE) != 0;
 	c->total_sam = 0; c->total_tasks = 0; c->n_rec = 0;
-	const bool sorted = bam && c->want_sorted;                    // the records leave in coordinate order: written to a scratch buffer, sorted into d_sam
-	const bool bgzf = bam && c->want_bgzf && !sorted;             // the records leave as BGZF members: written to the same scratch buffer, deflated into d_sam
+	const bool sorted = form == OutForm::BamSorted;               // the records leave in coordinate order: written to a scratch buffer, sorted into d_sam
+	const bool bgzf = form == OutForm::Bgzf;                      // the records leave as BGZF members: written to the same scratch buffer, deflated into d_sam
 	c->n_bgzf_blocks = 0;
 	if (n == 0) return 0;
 	if (pe && (n & 1)) return BWAHIP_EINVAL;
@@ -309,7 +309,7 @@ int run_final(bwahip_ctx *c, const bwahip_opt_t *opt, int64_t n_processed, const
 	if ((rc = c->d_sam.ensure((size_t)total + (bgzf ? (size_t)bgzf_blocks(total) * 31 : 0) + 64))) return rc;   // bgzf: the bound bgzf_deflate asks for
 	f.sam = c->d_sam.as<uint8_t>();
 	if (sorted || bgzf) { if ((rc = c->bs.raw.ensure((size_t)total + 64))) return rc; f.sam = c->bs.raw.as<uint8_t>(); }
-	if (c->want_host_sam_off) {                                 // bwahip_process_seqs: the offsets travel ahead of the write pass
+	if (host_sam_off) {                                         // bwahip_process_seqs: the offsets travel ahead of the write pass
 		c->h_sam_off.resize((size_t)n + 1);
 		HIP_TRY(hipMemcpyAsync(c->h_sam_off.data(), c->d_sam_off.p, (size_t)(n + 1) * 8, hipMemcpyDeviceToHost, c->stream));
 	}
@@ -474,29 +474,48 @@ static int stage_text(bwahip_ctx *c, int nt, int n, bwahip_seq_t *seqs, const Ba
 	return 0;
 }
 
-// what bwahip_process_seqs_bam_sorted hands out beside the record bytes
-struct SortedOut { const uint64_t **keys; const int64_t **rec_off; int64_t *n_rec; };
-// what bwahip_process_seqs_bgzf hands out beside the members
-struct BgzfOut { int64_t *raw_len, *n_blocks; };
+// What a bwahip_process_seqs* entry wants back: the batch in `form`; text != nullptr: in one piece (in the context's pinned buffer) instead
+// of being cut into per-read strings, with the pointers the form fills beside it
+struct SeqsOut {
+	OutForm form = OutForm::Sam;
+	const char **text = nullptr; int64_t *len = nullptr; const int64_t **off = nullptr;   // off: the reads' offsets (optional; SAM text, BAM records)
+	const uint64_t **keys = nullptr; const int64_t **rec_off = nullptr; int64_t *n_rec = nullptr;   // BamSorted
+	int64_t *raw_len = nullptr, *n_blocks = nullptr;                                        // Bgzf
+};
 
-// text != nullptr: the batch's SAM stays one piece (in the context's pinned buffer) instead of being cut into per-read strings
-static int process_seqs_impl(bwahip_ctx *ctx, const bwahip_opt_t *opt, int64_t n_processed, int n, bwahip_seq_t *seqs, const bwahip_pestat_t *pes0,
-                             const char **text_out, int64_t *len_out, const int64_t **off_out, bool bam = false, const SortedOut *sorted = nullptr, const BgzfOut *bz = nullptr)
+// The end of the one-piece forms that do not leave in read order: `bytes` of d_sam into the pinned buffer whose turn it is (valid until the
+// next-but-one call), beside what `more` queues on the context's stream for the buffers of the same turn; both streams awaited, no per-read strings
+template <class More>
+static int download_piece(bwahip_ctx *ctx, int64_t bytes, int n, bwahip_seq_t *seqs, int nt, const SeqsOut &out, More more)
+{
+	HostBuf &hb = (ctx->sam_flip ^= 1) ? ctx->h_sam2 : ctx->h_sam;
+	int rc;
+	if ((rc = hb.ensure((size_t)bytes + 1)) || (rc = more())) return rc;
+	if (bytes) HIP_TRY(hipMemcpyAsync(hb.p, ctx->d_sam.p, (size_t)bytes, hipMemcpyDeviceToHost, ctx->stream));
+	HIP_TRY(hipStreamSynchronize(ctx->stream));
+	HIP_TRY(hipStreamSynchronize(ctx->stream_copy));
+	par_for_chunks(n, nt, [&](int64_t b, int64_t e) { for (int64_t i = b; i < e; ++i) seqs[i].sam = nullptr; });
+	*out.text = (const char*)hb.p; *out.len = bytes;
+	return 0;
+}
+
+static int process_seqs_impl(bwahip_ctx *ctx, const bwahip_opt_t *opt, int64_t n_processed, int n, bwahip_seq_t *seqs, const bwahip_pestat_t *pes0, const SeqsOut &out)
 {
 	static const int64_t no_records[1] = { 0 };
-	if (sorted) { *sorted->keys = nullptr; *sorted->rec_off = no_records; *sorted->n_rec = 0; }
+	const bool sorted = out.form == OutForm::BamSorted, bz = out.form == OutForm::Bgzf;
+	if (sorted) { *out.keys = nullptr; *out.rec_off = no_records; *out.n_rec = 0; }
 	if (!ctx || !opt || n < 0 || (n && !seqs)) return BWAHIP_EINVAL;
 	const bool pe = (opt->flag & BWAHIP_F_PE) != 0;
 	if (pe && (n & 1)) return BWAHIP_EINVAL;
-	if (text_out) { *text_out = ""; *len_out = 0; if (off_out) *off_out = nullptr; }
+	if (out.text) { *out.text = ""; *out.len = 0; if (out.off) *out.off = nullptr; }
 	if (!ctx->knobs.gpu_final || (pe && !ctx->knobs.gpu_pair)) {
-		if (text_out) return BWAHIP_EINVAL;                       // the one-piece output exists on the GPU path only
+		if (out.text) return BWAHIP_EINVAL;                       // the one-piece output exists on the GPU path only
 		host_final_fn hf = load_host_final();
 		return hf ? hf(ctx, opt, n_processed, n, seqs, pes0) : BWAHIP_EINVAL;
 	}
 	if (pe) for (int i = 0; i < n; i += 2) if (strcmp(seqs[i].name, seqs[i + 1].name) != 0) { fprintf(stderr, "[bwahip] paired reads have different names\n"); return BWAHIP_EINVAL; }   // err_fatal in the reference (bwamem_pair.c:386)
 	if (n == 0) return 0;
-	if (bam) { const int rc_bam = bam_check_reads(n, seqs); if (rc_bam) return rc_bam; }   // what BAM cannot hold is refused before any launch
+	if (is_bam(out.form)) { const int rc_bam = bam_check_reads(n, seqs); if (rc_bam) return rc_bam; }   // what BAM cannot hold is refused before any launch
 	HIP_TRY(hipSetDevice(ctx->device));
 	const bool verbose = ctx->knobs.verbose != 0;
 	auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
@@ -514,48 +533,35 @@ static int process_seqs_impl(bwahip_ctx *ctx, const bwahip_opt_t *opt, int64_t n
 	text_thread.join();
 	if (rc || (rc = rc_text)) return rc;
 	const double t2 = now();
-	ctx->want_host_sam_off = true; ctx->want_sorted = sorted != nullptr; ctx->want_bgzf = bz != nullptr;
-	rc = run_final(ctx, opt, n_processed, pes0, false, bam);
-	ctx->want_host_sam_off = false; ctx->want_sorted = false; ctx->want_bgzf = false;
-	if (rc) return rc;
-	if (bz) {                                                     // the members in one piece, through the pinned buffers taken in turn
+	if ((rc = run_final(ctx, opt, n_processed, pes0, false, out.form, true))) return rc;
+	if (bz) {                                                     // the members in one piece: their total was left in HBM by the deflate stage
 		int64_t tot[2] = { 0, 0 };
 		HIP_TRY(hipMemcpyAsync(tot, ctx->d_bgzf_tot.p, 16, hipMemcpyDeviceToHost, ctx->stream));
 		HIP_TRY(hipStreamSynchronize(ctx->stream));
-		HostBuf &hb = (ctx->sam_flip ^= 1) ? ctx->h_sam2 : ctx->h_sam;
-		if ((rc = hb.ensure((size_t)tot[0] + 1))) return rc;
-		if (tot[0]) HIP_TRY(hipMemcpyAsync(hb.p, ctx->d_sam.p, (size_t)tot[0], hipMemcpyDeviceToHost, ctx->stream));
-		HIP_TRY(hipStreamSynchronize(ctx->stream));
-		HIP_TRY(hipStreamSynchronize(ctx->stream_copy));
-		par_for_chunks(n, nt, [&](int64_t b, int64_t e) { for (int64_t i = b; i < e; ++i) seqs[i].sam = nullptr; });
-		*text_out = (const char*)hb.p; *len_out = tot[0];
-		*bz->raw_len = ctx->total_sam; *bz->n_blocks = ctx->n_bgzf_blocks;
+		if ((rc = download_piece(ctx, tot[0], n, seqs, nt, out, [] { return 0; }))) return rc;
+		*out.raw_len = ctx->total_sam; *out.n_blocks = ctx->n_bgzf_blocks;
 		return 0;
 	}
-	if (sorted) {                                                 // records, keys and offsets in one piece each, through pinned buffers taken in turn
-		const int flip = (ctx->sam_flip ^= 1);
-		HostBuf &hb = flip ? ctx->h_sam2 : ctx->h_sam, &hk = ctx->h_skeys[flip], &ho = ctx->h_rec_off[flip];
+	if (sorted) {                                                 // records, keys and offsets in one piece each
 		const int64_t nr = ctx->n_rec;
-		if ((rc = hb.ensure((size_t)ctx->total_sam + 1)) || (rc = hk.ensure((size_t)(nr ? nr : 1) * 8)) || (rc = ho.ensure((size_t)(nr + 1) * 8))) return rc;
-		if (ctx->total_sam) HIP_TRY(hipMemcpyAsync(hb.p, ctx->d_sam.p, (size_t)ctx->total_sam, hipMemcpyDeviceToHost, ctx->stream));
-		if (nr) HIP_TRY(hipMemcpyAsync(hk.p, ctx->d_skeys.p, (size_t)nr * 8, hipMemcpyDeviceToHost, ctx->stream));
-		HIP_TRY(hipMemcpyAsync(ho.p, ctx->d_rec_off.p, (size_t)(nr + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
-		HIP_TRY(hipStreamSynchronize(ctx->stream));
-		HIP_TRY(hipStreamSynchronize(ctx->stream_copy));
-		par_for_chunks(n, nt, [&](int64_t b, int64_t e) { for (int64_t i = b; i < e; ++i) seqs[i].sam = nullptr; });
-		*text_out = (const char*)hb.p; *len_out = ctx->total_sam;
-		*sorted->keys = (const uint64_t*)hk.p; *sorted->rec_off = (const int64_t*)ho.p; *sorted->n_rec = nr;
+		rc = download_piece(ctx, ctx->total_sam, n, seqs, nt, out, [&]() -> int {
+			HostBuf &hk = ctx->h_skeys[ctx->sam_flip], &ho = ctx->h_rec_off[ctx->sam_flip];
+			int r;
+			if ((r = hk.ensure((size_t)(nr ? nr : 1) * 8)) || (r = ho.ensure((size_t)(nr + 1) * 8))) return r;
+			if (nr) HIP_TRY(hipMemcpyAsync(hk.p, ctx->d_skeys.p, (size_t)nr * 8, hipMemcpyDeviceToHost, ctx->stream));
+			HIP_TRY(hipMemcpyAsync(ho.p, ctx->d_rec_off.p, (size_t)(nr + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
+			return 0;
+		});
+		if (rc) return rc;
+		*out.keys = (const uint64_t*)ctx->h_skeys[ctx->sam_flip].p; *out.rec_off = (const int64_t*)ctx->h_rec_off[ctx->sam_flip].p; *out.n_rec = nr;
 		return 0;
 	}
-	// SAM text back through the pinned buffer, on the context's stream (a non-blocking stream: a plain hipMemcpy would not wait
-	// for the SAM kernel), in slices of reads: while slice k+1 travels, the host threads cut slice k into one malloc()ed string
-	// per read, which is what the reference's contract wants (bwamem.c:1054)
 	// SAM text back through the pinned buffer.  run_final wrote it in two halves and sent the offsets ahead: once the first half is written
 	// (ev_sam_half) its download starts on the copy stream, beside the kernel that writes the second half.  Per-read strings: in slices of reads --
 	// while slice k+1 travels, the host threads cut slice k into one malloc()ed string per read, which is what the reference's contract wants
 	// (bwamem.c:1054).  (The context's streams are non-blocking: a plain hipMemcpy would not wait for the SAM kernels.)
 	std::vector<int64_t> &soff = ctx->h_sam_off;
-	HostBuf &hs = text_out && (ctx->sam_flip ^= 1) ? ctx->h_sam2 : ctx->h_sam;   // one-piece callers: the text stays valid until the next-but-one call
+	HostBuf &hs = out.text && (ctx->sam_flip ^= 1) ? ctx->h_sam2 : ctx->h_sam;   // one-piece callers: the text stays valid until the next-but-one call
 	if ((rc = hs.ensure((size_t)ctx->total_sam + 1))) return rc;
 	char *text = (char*)hs.p;
 	HIP_TRY(hipEventSynchronize(ctx->ev_sam_half));               // first half written; the offsets arrived before that
@@ -573,12 +579,12 @@ static int process_seqs_impl(bwahip_ctx *ctx, const bwahip_opt_t *opt, int64_t n
 	for (int k = 0; k < SLICES / 2; ++k) if ((rc = copy_slice(k, ctx->stream_copy))) return rc;
 	for (int k = SLICES / 2; k < SLICES; ++k) if ((rc = copy_slice(k, ctx->stream))) return rc;
 	const int n_sl = SLICES;
-	if (text_out) {                                               // one piece: no per-read strings
+	if (out.text) {                                               // one piece: no per-read strings
 		HIP_TRY(hipStreamSynchronize(ctx->stream_copy));
 		HIP_TRY(hipStreamSynchronize(ctx->stream));
 		const double t4 = now();
 		text[ctx->total_sam] = 0;
-		*text_out = text; *len_out = ctx->total_sam; if (off_out) *off_out = soff.data();
+		*out.text = text; *out.len = ctx->total_sam; if (out.off) *out.off = soff.data();
 		par_for_chunks(n, nt, [&](int64_t b, int64_t e) { for (int64_t i = b; i < e; ++i) seqs[i].sam = nullptr; });
 		if (verbose || ctx->knobs.e2e_log)
 			fprintf(stderr, "[bwahip] process_seqs_text %d reads: codes gather+upload %.1f ms, hot path (text upload beside it) %.1f ms, finalisation+SAM on GPU and download %.1f ms (%lld bytes), rest %.1f ms\n",
@@ -614,7 +620,7 @@ static int process_seqs_impl(bwahip_ctx *ctx, const bwahip_opt_t *opt, int64_t n
 
 extern "C" int bwahip_process_seqs(bwahip_ctx *ctx, const bwahip_opt_t *opt, int64_t n_processed, int n, bwahip_seq_t *seqs, const bwahip_pestat_t *pes0)
 {
-	return process_seqs_impl(ctx, opt, n_processed, n, seqs, pes0, nullptr, nullptr, nullptr);
+	return process_seqs_impl(ctx, opt, n_processed, n, seqs, pes0, SeqsOut());
 }
 
 // The same work with the batch's SAM handed over in one piece -- for a caller whose output step is one fwrite (fastmap.c prints
@@ -624,7 +630,7 @@ extern "C" int bwahip_process_seqs_text(bwahip_ctx *ctx, const bwahip_opt_t *opt
                                         const char **sam, int64_t *sam_len, const int64_t **off)
 {
 	if (!sam || !sam_len) return BWAHIP_EINVAL;
-	return process_seqs_impl(ctx, opt, n_processed, n, seqs, pes0, sam, sam_len, off);
+	return process_seqs_impl(ctx, opt, n_processed, n, seqs, pes0, { OutForm::Sam, sam, sam_len, off });
 }
 
 // The same work with the batch as BAM records (k_bam.hip): *bam = the records of all reads in read order, concatenated, without header
@@ -633,7 +639,7 @@ extern "C" int bwahip_process_seqs_bam(bwahip_ctx *ctx, const bwahip_opt_t *opt,
                                        const uint8_t **bam, int64_t *bam_len, const int64_t **off)
 {
 	if (!bam || !bam_len) return BWAHIP_EINVAL;
-	return process_seqs_impl(ctx, opt, n_processed, n, seqs, pes0, (const char**)bam, bam_len, off, true);
+	return process_seqs_impl(ctx, opt, n_processed, n, seqs, pes0, { OutForm::Bam, (const char**)bam, bam_len, off });
 }
 
 // The same records in coordinate order (k_bamsort.hip; the key and the order are in include/bwahip.h), with what a merge of several
@@ -642,8 +648,7 @@ extern "C" int bwahip_process_seqs_bam_sorted(bwahip_ctx *ctx, const bwahip_opt_
                                               const uint8_t **bam, int64_t *bam_len, const uint64_t **keys, const int64_t **rec_off, int64_t *n_rec)
 {
 	if (!bam || !bam_len || !keys || !rec_off || !n_rec) return BWAHIP_EINVAL;
-	const SortedOut so = { keys, rec_off, n_rec };
-	return process_seqs_impl(ctx, opt, n_processed, n, seqs, pes0, (const char**)bam, bam_len, nullptr, true, &so);
+	return process_seqs_impl(ctx, opt, n_processed, n, seqs, pes0, { OutForm::BamSorted, (const char**)bam, bam_len, nullptr, keys, rec_off, n_rec });
 }
 
 // bwahip_process_seqs_bam with the records leaving the GPU as BGZF members (k_bgzf.hip): *bgzf = the members of the batch's records, cut
@@ -653,8 +658,7 @@ extern "C" int bwahip_process_seqs_bgzf(bwahip_ctx *ctx, const bwahip_opt_t *opt
 {
 	if (!bgzf || !bgzf_len || !raw_len || !n_blocks) return BWAHIP_EINVAL;
 	*raw_len = 0; *n_blocks = 0;
-	const BgzfOut bz = { raw_len, n_blocks };
-	return process_seqs_impl(ctx, opt, n_processed, n, seqs, pes0, (const char**)bgzf, bgzf_len, nullptr, true, nullptr, &bz);
+	return process_seqs_impl(ctx, opt, n_processed, n, seqs, pes0, { OutForm::Bgzf, (const char**)bgzf, bgzf_len, nullptr, nullptr, nullptr, nullptr, raw_len, n_blocks });
 }
 
 // Insert-size statistics (mem_pestat_t x 4: FF, FR, RF, RR) and mate-rescue counters ([0] Smith-Waterman alignments run on
@@ -738,13 +742,15 @@ struct PipeOut {
 	HostBuf h_keys, h_rec_off;
 	hipEvent_t ev_sort[4] = {};
 	int64_t n_rec = 0;
-	bool sorted = false;
-	// BGZF members (bam == 3): their total and the stored count in HBM, the events around the deflate stage, the records' bytes
+	OutForm form = OutForm::Sam;         // what pipe_compute left in the set
+	// BGZF members: their total and the stored count in HBM, the events around the deflate stage, the records' bytes
 	DevBuf d_tot;
 	hipEvent_t ev_bgzf[2] = {};
 	int64_t raw_total = 0, n_blocks = 0, n_stored = 0;
-	bool bgzf = false;
 };
+
+// the GPU time of the sort stage that filled the set (record table, radix sort, gather)
+double sort_stage_ms(const PipeOut &o) { float ms = 0; if (o.n_rec && o.ev_sort[0] && hipEventElapsedTime(&ms, o.ev_sort[0], o.ev_sort[3]) != hipSuccess) ms = 0; return ms; }
 
 } // namespace
 
@@ -801,13 +807,13 @@ void pipe_destroy(bwahip_ctx *c)
 // What stage_codes + stage_text do for bwahip_process_seqs, in two passes of the context's staging threads and without writing to the
 // reader's records: pass 1 the per-chunk totals (two strlen per read), the longest read and the checks; pass 2 the offsets and the gather
 // of bases, qualities, names and comments, all into one pinned buffer.  The bases travel as ASCII and become codes in HBM (k_nt4_conv).
-int pipe_stage_in(bwahip_ctx *c, int in, const bwahip_opt_t *opt, int n, const bwahip_seq_t *seqs, int bam, double *t_copy_begin)
+int pipe_stage_in(bwahip_ctx *c, int in, const bwahip_opt_t *opt, int n, const bwahip_seq_t *seqs, OutForm form, double *t_copy_begin)
 {
 	if (!c || !c->pipe || in < 0 || in >= PIPE_SETS || !opt || n <= 0 || !seqs) return BWAHIP_EINVAL;
 	const bool pe = (opt->flag & BWAHIP_F_PE) != 0;
 	if (pe && (n & 1)) return BWAHIP_EINVAL;
 	if (!c->knobs.gpu_final || (pe && !c->knobs.gpu_pair)) return BWAHIP_EINVAL;   // the one-piece output exists on the GPU path only
-	if (bam) { const int rc_bam = bam_check_reads(n, seqs); if (rc_bam) return rc_bam; }
+	if (is_bam(form)) { const int rc_bam = bam_check_reads(n, seqs); if (rc_bam) return rc_bam; }
 	HIP_TRY(hipSetDevice(c->device));
 	PipeIn &s = c->pipe->in[in];
 	StagePool &pool = c->pipe->pool;
@@ -883,7 +889,7 @@ int pipe_stage_in(bwahip_ctx *c, int in, const bwahip_opt_t *opt, int n, const b
 	return 0;
 }
 
-int pipe_compute(bwahip_ctx *c, int in, int out, const bwahip_opt_t *opt, int64_t n_processed, const bwahip_pestat_t *pes0, int bam, double *t_hot_end)
+int pipe_compute(bwahip_ctx *c, int in, int out, const bwahip_opt_t *opt, int64_t n_processed, const bwahip_pestat_t *pes0, OutForm form, double *t_hot_end)
 {
 	if (!c || !c->pipe || in < 0 || in >= PIPE_SETS || out < 0 || out >= PIPE_SETS || !opt) return BWAHIP_EINVAL;
 	HIP_TRY(hipSetDevice(c->device));
@@ -907,13 +913,10 @@ int pipe_compute(bwahip_ctx *c, int in, int out, const bwahip_opt_t *opt, int64_
 		if ((rc = launch_nt4(c->d_seq.as<uint8_t>(), c->total_bases, c->stream))) return rc;
 		if ((rc = run_pipeline(c, opt, false, false))) return rc;
 		if (t_hot_end) *t_hot_end = pipe_now();
-		c->want_host_sam_off = false; c->want_sorted = bam == 2; c->want_bgzf = bam == 3;
-		rc = run_final(c, opt, n_processed, pes0, false, bam != 0);
-		c->want_sorted = false; c->want_bgzf = false;
-		if (rc) return rc;
+		if ((rc = run_final(c, opt, n_processed, pes0, false, form))) return rc;
 		HIP_TRY(hipEventRecord(o.ev_written, c->stream));
-		o.total = c->total_sam; o.n_rec = c->n_rec; o.sorted = bam == 2;
-		o.bgzf = bam == 3; o.raw_total = c->total_sam; o.n_blocks = c->n_bgzf_blocks;
+		o.total = c->total_sam; o.n_rec = c->n_rec; o.form = form;
+		o.raw_total = c->total_sam; o.n_blocks = c->n_bgzf_blocks;
 		return 0;
 	};
 	rc = body();
@@ -929,7 +932,7 @@ int pipe_stage_out(bwahip_ctx *c, int out, const char **text, int64_t *len, doub
 	// waiting on the host, not in the copy stream: the next batch's upload is queued there and must not stand behind this batch's kernels
 	HIP_TRY(hipEventSynchronize(o.ev_written));
 	if (t_kernels_end) *t_kernels_end = pipe_now();
-	if (o.bgzf) {                                                 // what travels is the members: their total was left in HBM by the deflate stage
+	if (o.form == OutForm::Bgzf) {                                              // what travels is the members: their total was left in HBM by the deflate stage
 		int64_t tot[2] = { 0, 0 };
 		HIP_TRY(hipMemcpyAsync(tot, o.d_tot.p, 16, hipMemcpyDeviceToHost, c->stream_copy));
 		HIP_TRY(hipEventRecord(o.ev_copied, c->stream_copy));
@@ -951,14 +954,14 @@ int pipe_stage_out(bwahip_ctx *c, int out, const char **text, int64_t *len, doub
 	return 0;
 }
 
-// After pipe_stage_out of a batch computed with bam == 2: the keys and offsets of the set's records in its pinned buffers (valid as long
+// After pipe_stage_out of a batch computed as OutForm::BamSorted: the keys and offsets of the set's records in its pinned buffers (valid as long
 // as the text), and the time the sort stage took on the GPU.
 int pipe_stage_out_sorted(bwahip_ctx *c, int out, const uint64_t **keys, const int64_t **rec_off, int64_t *n_rec, double *sort_ms)
 {
 	if (!c || !c->pipe || out < 0 || out >= PIPE_SETS || !keys || !rec_off || !n_rec) return BWAHIP_EINVAL;
 	HIP_TRY(hipSetDevice(c->device));
 	PipeOut &o = c->pipe->out[out];
-	if (!o.sorted) return BWAHIP_EINVAL;
+	if (o.form != OutForm::BamSorted) return BWAHIP_EINVAL;
 	int rc;
 	if ((rc = o.h_keys.ensure((size_t)(o.n_rec ? o.n_rec : 1) * 8)) || (rc = o.h_rec_off.ensure((size_t)(o.n_rec + 1) * 8))) return rc;
 	if (o.n_rec) HIP_TRY(hipMemcpyAsync(o.h_keys.p, o.d_keys.p, (size_t)o.n_rec * 8, hipMemcpyDeviceToHost, c->stream_copy));
@@ -966,7 +969,7 @@ int pipe_stage_out_sorted(bwahip_ctx *c, int out, const uint64_t **keys, const i
 	else *(int64_t*)o.h_rec_off.p = 0;
 	HIP_TRY(hipEventRecord(o.ev_copied, c->stream_copy));
 	HIP_TRY(hipEventSynchronize(o.ev_copied));
-	if (sort_ms) { float ms = 0; if (o.n_rec && o.ev_sort[0] && hipEventElapsedTime(&ms, o.ev_sort[0], o.ev_sort[3]) != hipSuccess) ms = 0; *sort_ms = ms; }
+	if (sort_ms) *sort_ms = sort_stage_ms(o);
 	*keys = (const uint64_t*)o.h_keys.p; *rec_off = (const int64_t*)o.h_rec_off.p; *n_rec = o.n_rec;
 	return 0;
 }
@@ -981,20 +984,20 @@ int pipe_stage_out_devrun(bwahip_ctx *c, int out, DevRun **run, int64_t *raw_len
 	PipeOut &o = c->pipe->out[out];
 	HIP_TRY(hipEventSynchronize(o.ev_written));
 	if (t_kernels_end) *t_kernels_end = pipe_now();
-	if (!o.sorted) return BWAHIP_EINVAL;
-	if (sort_ms) { float ms = 0; if (o.n_rec && o.ev_sort[0] && hipEventElapsedTime(&ms, o.ev_sort[0], o.ev_sort[3]) != hipSuccess) ms = 0; *sort_ms = ms; }
+	if (o.form != OutForm::BamSorted) return BWAHIP_EINVAL;
+	if (sort_ms) *sort_ms = sort_stage_ms(o);
 	*raw_len = o.total; *n_rec = o.n_rec;
 	const int rc = bam_devrun_make(c, o.d_sam.as<uint8_t>(), o.total, o.d_keys.as<uint64_t>(), o.d_rec_off.as<int64_t>(), o.n_rec, c->stream_copy, run);
 	return rc == BWAHIP_ENOMEM ? 0 : rc;
 }
 
-// After pipe_stage_out of a batch computed with bam == 3: the bytes of the records the members hold, the members, those that are stored,
+// After pipe_stage_out of a batch computed as OutForm::Bgzf: the bytes of the records the members hold, the members, those that are stored,
 // and the GPU time of the deflate stage.
 int pipe_stage_out_bgzf(bwahip_ctx *c, int out, int64_t *raw_len, int64_t *n_blocks, int64_t *n_stored, double *deflate_ms)
 {
 	if (!c || !c->pipe || out < 0 || out >= PIPE_SETS || !raw_len || !n_blocks || !n_stored) return BWAHIP_EINVAL;
 	PipeOut &o = c->pipe->out[out];
-	if (!o.bgzf) return BWAHIP_EINVAL;
+	if (o.form != OutForm::Bgzf) return BWAHIP_EINVAL;
 	*raw_len = o.raw_total; *n_blocks = o.n_blocks; *n_stored = o.n_stored;
 	if (deflate_ms) { float ms = 0; if (o.ev_bgzf[0] && hipEventElapsedTime(&ms, o.ev_bgzf[0], o.ev_bgzf[1]) != hipSuccess) ms = 0; *deflate_ms = ms; }
 	return 0;

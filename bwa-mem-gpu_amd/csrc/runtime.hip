@@ -820,29 +820,13 @@ int bwahip_batch_attach_text(bwahip_ctx *c, const uint8_t *qual_dev, const int64
 	return 0;
 }
 
-// mem_process_seqs over the attached batch, everything on the GPU: hot path, then finalisation and SAM text, which stays in HBM
-// (bwahip_batch_sam downloads it).  kernel_ms as bwahip_batch_run, entries 11..15 = the finalisation stages.
-int bwahip_batch_run_sam(bwahip_ctx *c, const bwahip_opt_t *opt, int64_t n_processed, const bwahip_pestat_t *pes0, float *kernel_ms, int n_ms)
+// The three entries below, and bwahip_batch_run_sam: hot path, then the finalisation with the output in `form`.  BAM: a read name of 255
+// bytes or more cannot be encoded: checked here from the name offsets (the names themselves are in HBM).
+static int batch_run_form(bwahip_ctx *c, const bwahip_opt_t *opt, int64_t n_processed, const bwahip_pestat_t *pes0, float *kernel_ms, int n_ms, OutForm form)
 {
 	if (!c || !opt) return BWAHIP_EINVAL;
 	HIP_TRY(hipSetDevice(c->device));
-	int rc = run_pipeline(c, opt, true, false);
-	if (!rc) rc = run_final(c, opt, n_processed, pes0, true);
-	if (!rc && kernel_ms) {
-		for (int i = 0; i < n_ms && i < 11; ++i) kernel_ms[i] = c->last_ms[i];
-		if (n_ms > 11) kernel_ms[11] = c->final_ms[4];
-		for (int i = 0; i < 4 && 12 + i < n_ms; ++i) kernel_ms[12 + i] = c->final_ms[i];
-	}
-	return rc;
-}
-
-// bwahip_batch_run_sam with BAM records as the output (k_bam.hip); kernel_ms[14], [15] are the sizing and the write pass of that format.
-// A read name of 255 bytes or more cannot be encoded: checked here from the name offsets (the names themselves are in HBM).
-int bwahip_batch_run_bam(bwahip_ctx *c, const bwahip_opt_t *opt, int64_t n_processed, const bwahip_pestat_t *pes0, float *kernel_ms, int n_ms)
-{
-	if (!c || !opt) return BWAHIP_EINVAL;
-	HIP_TRY(hipSetDevice(c->device));
-	if (c->n_reads > 0) {
+	if (is_bam(form) && c->n_reads > 0) {
 		if (!c->d_name_off.p) return BWAHIP_EINVAL;
 		std::vector<int64_t> noff((size_t)c->n_reads + 1);
 		HIP_TRY(hipMemcpyAsync(noff.data(), c->d_name_off.p, noff.size() * 8, hipMemcpyDeviceToHost, c->stream));
@@ -851,7 +835,7 @@ int bwahip_batch_run_bam(bwahip_ctx *c, const bwahip_opt_t *opt, int64_t n_proce
 			if (noff[i + 1] - noff[i] > 255) { fprintf(stderr, "[bwahip] BAM: the name of read %d has %lld bytes (at most 254 fit a record)\n", i, (long long)(noff[i + 1] - noff[i] - 1)); return BWAHIP_EINVAL; }
 	}
 	int rc = run_pipeline(c, opt, true, false);
-	if (!rc) rc = run_final(c, opt, n_processed, pes0, true, true);
+	if (!rc) rc = run_final(c, opt, n_processed, pes0, true, form);
 	if (!rc && kernel_ms) {
 		for (int i = 0; i < n_ms && i < 11; ++i) kernel_ms[i] = c->last_ms[i];
 		if (n_ms > 11) kernel_ms[11] = c->final_ms[4];
@@ -860,14 +844,24 @@ int bwahip_batch_run_bam(bwahip_ctx *c, const bwahip_opt_t *opt, int64_t n_proce
 	return rc;
 }
 
+// mem_process_seqs over the attached batch, everything on the GPU: hot path, then finalisation and SAM text, which stays in HBM
+// (bwahip_batch_sam downloads it).  kernel_ms as bwahip_batch_run, entries 11..15 = the finalisation stages.
+int bwahip_batch_run_sam(bwahip_ctx *c, const bwahip_opt_t *opt, int64_t n_processed, const bwahip_pestat_t *pes0, float *kernel_ms, int n_ms)
+{
+	return batch_run_form(c, opt, n_processed, pes0, kernel_ms, n_ms, OutForm::Sam);
+}
+
+// bwahip_batch_run_sam with BAM records as the output (k_bam.hip); kernel_ms[14], [15] are the sizing and the write pass of that format.
+int bwahip_batch_run_bam(bwahip_ctx *c, const bwahip_opt_t *opt, int64_t n_processed, const bwahip_pestat_t *pes0, float *kernel_ms, int n_ms)
+{
+	return batch_run_form(c, opt, n_processed, pes0, kernel_ms, n_ms, OutForm::Bam);
+}
+
 // bwahip_batch_run_bam with the records in coordinate order.  sort_ms4 (may be NULL): the sort stage of this run on the GPU -- [0] record
 // table, [1] radix sort, [2] gather, in milliseconds, and [3] the number of radix passes that ran.
 int bwahip_batch_run_bam_sorted(bwahip_ctx *c, const bwahip_opt_t *opt, int64_t n_processed, const bwahip_pestat_t *pes0, float *kernel_ms, int n_ms, float *sort_ms4)
 {
-	if (!c || !opt) return BWAHIP_EINVAL;
-	c->want_sorted = true;
-	const int rc = bwahip_batch_run_bam(c, opt, n_processed, pes0, kernel_ms, n_ms);
-	c->want_sorted = false;
+	const int rc = batch_run_form(c, opt, n_processed, pes0, kernel_ms, n_ms, OutForm::BamSorted);
 	if (!rc && sort_ms4) { for (int k = 0; k < 3; ++k) sort_ms4[k] = c->n_rec ? c->bs.ms[k] : 0; sort_ms4[3] = (float)c->bs.n_passes; }
 	return rc;
 }
@@ -895,10 +889,7 @@ int bwahip_batch_bam_sorted(bwahip_ctx *c, uint8_t **out, int64_t *out_len, uint
 // them).  deflate_ms (may be NULL): the deflate stage of this run by HIP events.
 int bwahip_batch_run_bgzf(bwahip_ctx *c, const bwahip_opt_t *opt, int64_t n_processed, const bwahip_pestat_t *pes0, float *kernel_ms, int n_ms, float *deflate_ms)
 {
-	if (!c || !opt) return BWAHIP_EINVAL;
-	c->want_bgzf = true;
-	const int rc = bwahip_batch_run_bam(c, opt, n_processed, pes0, kernel_ms, n_ms);
-	c->want_bgzf = false;
+	const int rc = batch_run_form(c, opt, n_processed, pes0, kernel_ms, n_ms, OutForm::Bgzf);
 	if (!rc && deflate_ms) {
 		*deflate_ms = 0;
 		if (c->n_reads > 0 && c->ev_bgzf[0]) HIP_TRY(hipEventElapsedTime(deflate_ms, c->ev_bgzf[0], c->ev_bgzf[1]));

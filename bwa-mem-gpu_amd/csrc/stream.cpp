@@ -1,4 +1,4 @@
-// The batch driver behind the C ABI: FASTQ files in -> SAM text out, over any number of contexts.  What superBatchMain
+// The batch driver behind the C ABI: FASTQ files in -> SAM text or a BAM file out, over any number of contexts.  What superBatchMain
 // (cuda/superbatch_process.cpp:133: read || process, double buffered, one GPU) and process() / kt_pipeline of fastmap.c
 // (read -> mem_process_seqs -> fputs, fastmap.c:46,307) do in the reference, for N GPUs and several batches in flight per GPU:
 //
@@ -10,17 +10,16 @@
 //                              per-batch mem_pestat then come out as in a serial run) -- gathers it into a pinned buffer and copies
 //                              it to HBM (batch k+1);
 //                     compute  queues k_nt4_conv, the hot path and the finalisation (batch k);
-//                     drainer  copies the SAM text back and hands it to the writer (batch k-1);
-//   one writer      writes the batches' SAM in batch order to the caller's file descriptor, and gives every buffer back to the
-//                   context it came from once its bytes are on the descriptor.
+//                     drainer  takes the batch off the context as the run's sink says (a download, mostly) and hands it to the writer (batch k-1);
+//   one writer      hands the batches in batch order to the run's sink (below: SAM text or one of four ways to a BAM file on the caller's
+//                   file descriptor), and gives every buffer back to the context it came from once the sink has taken its bytes.
 //
 // A context has two sets of input buffers and two of output buffers; a set is reused only when its consumer has said it is done with
 // it (Pipe::in_free / out_free below).  A stager asks for a batch when it has a free input set, so batches go to whichever context
 // frees first and staging runs ahead of a context that still computes; results do not depend on which context took a batch
 // (tests/test_gpu_multi.py).  No data-path collective: SURVEY.md 8(e).
 #include "../../include/bwahip.h"
-#include "stream_pipe.h"
-#include "ctx_internal.h"                                       // the contexts' devices, the runs a device merger holds (k_bammerge.hip)
+#include "stream_pipe.h"                                        // with ctx_internal.h: the contexts' devices, the runs a device merger holds (k_bammerge.hip)
 #include <errno.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -40,6 +39,184 @@ namespace {
 
 double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
+// One finished batch on its way from its drainer to the writer
+struct Item {
+	const char *p = nullptr; int64_t len = 0;                    // the bytes, in the pinned buffer of output set `out` of context `ctx`
+	int ctx = 0, out = 0; bool holds_set = true;                 // holds_set: the set is the writer's until the bytes are taken; false: it went back to its context already (a run kept in HBM)
+	const uint64_t *keys = nullptr; const int64_t *rec_off = nullptr; int64_t n_rec = 0;   // coordinate-sorted records
+	int64_t raw_len = 0;                                         // what the batch counts for in st->sam_bytes: the bytes of its text or records, deflated or not
+	DevRun *run = nullptr;                                       // the batch as a run in HBM: no bytes
+	double gpu_ms = 0; int64_t n_blocks = 0, n_stored = 0;       // the sort or the deflate stage on the GPU; BGZF members
+};
+
+// Where the batches of a run go.  The driver is the same for every output: a sink says what the contexts compute, how a drainer takes a
+// batch off its context, and what the writer does with it.  This one is SAM text, written as it comes.
+struct Sink {
+	OutForm form = OutForm::Sam;                                 // what the contexts compute
+	bool host_deflates = false;                                  // half of the host threads deflate for the writer, the other half stages (else: all stage)
+	int fd = -1, n_threads = 1, n_deflate = 0;                   // from the driver, before open: the descriptor, opt->n_threads, the deflating share of it
+	virtual ~Sink() {}                                           // clean-up on every path: mergers, their files, buffers
+	virtual int open(bwahip_ctx *const *ctxs, int n_ctx) { return 0; }   // argument checks and set-up, before the reader is opened
+	// a drainer: batch `out` of context c leaves its context (*t_kernels_end: from here on its input set is free) and becomes an item
+	virtual int stage_out(bwahip_ctx *c, int out, Item &it, double *t_kernels_end) { const int r = pipe_stage_out(c, out, &it.p, &it.len, t_kernels_end); it.raw_len = it.len; return r; }
+	virtual int write(int64_t seq_no, Item &it)                  // the writer: batch seq_no, in batch order
+	{
+		for (int64_t o = 0; fd >= 0 && o < it.len;) {
+			const ssize_t w = ::write(fd, it.p + o, (size_t)(it.len - o > (1ll << 30) ? (1ll << 30) : it.len - o));
+			if (w < 0) { if (errno == EINTR) continue; fprintf(stderr, "[bwahip] writing the SAM text failed: %s\n", strerror(errno)); return BWAHIP_EIO; }
+			o += w;
+		}
+		return 0;
+	}
+	virtual void drop(Item &it) {}                               // an item nobody will write (after a failure)
+	virtual int finish() { return 0; }                           // after the last batch of a run without failure: what the file still lacks
+};
+
+// BAM in input order: the header before the first batch, every batch's records through the host's BGZF writer, the end-of-file block.
+// With bs: the members of the records are made on the GPU (k_bgzf.hip), so the batches arrive deflated and are only written; no host
+// thread deflates, and the header goes through the host writer at level 1.
+struct BamSink : Sink {
+	const char *hdr_line; int level; bwahip_bgzf_stats_t *bs;
+	BamSink(const char *h, int lv, bwahip_bgzf_stats_t *b = nullptr) : hdr_line(h), level(lv), bs(b) { form = bs ? OutForm::Bgzf : OutForm::Bam; host_deflates = !bs; }
+	int open(bwahip_ctx *const *ctxs, int) override
+	{
+		if (level < 0 || level > 9) return BWAHIP_EINVAL;
+		uint8_t *hdr = nullptr; int64_t hlen = 0;
+		int r = bwahip_bam_header(bwahip_bns(ctxs[0]), hdr_line, &hdr, &hlen);
+		if (!r) { r = bwahip_bgzf_write(fd, hdr, hlen, level, 1); free(hdr); }
+		return r;
+	}
+	int stage_out(bwahip_ctx *c, int out, Item &it, double *t_end) override { const int r = Sink::stage_out(c, out, it, t_end); return r || !bs ? r : pipe_stage_out_bgzf(c, out, &it.raw_len, &it.n_blocks, &it.n_stored, &it.gpu_ms); }
+	int write(int64_t seq_no, Item &it) override
+	{
+		if (!bs) return bwahip_bgzf_write(fd, it.p, it.len, level, n_deflate);
+		bs->raw_bytes += it.raw_len; bs->bgzf_bytes += it.len; bs->n_blocks += it.n_blocks; bs->n_stored += it.n_stored; bs->deflate_ms += it.gpu_ms;
+		return Sink::write(seq_no, it);
+	}
+	int finish() override { return bwahip_bgzf_eof(fd); }
+};
+
+// Coordinate-sorted BAM merged on the host: every batch leaves its context sorted and becomes a run of the merger (the batch number is
+// the run number), which copies or spills it; after the last batch: header, the merge of the runs through the BGZF writer, the
+// end-of-file block.  The statistics go to the caller's bwahip_sort_t, or to the same fields of a bwahip_sort_dev_t.
+struct SortedSink : Sink {
+	const char *hdr_line, *tmp_dir; int64_t mem_budget; int level;
+	int64_t *n_records, *n_runs, *spilled_bytes; double *sort_ms_out, *merge_s;
+	uint8_t *hdr = nullptr; int64_t hlen = 0; bwahip_bam_merger *m = nullptr; double sort_ms = 0;
+	template <class S> SortedSink(const char *h, int lv, S *so) : hdr_line(h), tmp_dir(so->tmp_dir), mem_budget(so->mem_budget), level(lv),
+		n_records(&so->n_records), n_runs(&so->n_runs), spilled_bytes(&so->spilled_bytes), sort_ms_out(&so->sort_ms), merge_s(&so->merge_s) { form = OutForm::BamSorted; host_deflates = true; }
+	~SortedSink() { free(hdr); bwahip_bam_merger_close(m); }    // the merger and its files go whatever happens
+	int prepare(bwahip_ctx *c0)                                  // everything but the merger: the header waits for the merge
+	{
+		if (level < 0 || level > 9) return BWAHIP_EINVAL;
+		*n_records = *n_runs = *spilled_bytes = 0; *sort_ms_out = *merge_s = 0;
+		return bwahip_bam_header_sorted(bwahip_bns(c0), hdr_line, &hdr, &hlen);
+	}
+	int open(bwahip_ctx *const *ctxs, int) override { const int r = prepare(ctxs[0]); return r ? r : bwahip_bam_merger_open(tmp_dir, mem_budget, &m); }
+	int stage_out(bwahip_ctx *c, int out, Item &it, double *t_end) override { const int r = Sink::stage_out(c, out, it, t_end); return r ? r : pipe_stage_out_sorted(c, out, &it.keys, &it.rec_off, &it.n_rec, &it.gpu_ms); }
+	int write(int64_t seq_no, Item &it) override { sort_ms += it.gpu_ms; return bwahip_bam_merger_add(m, seq_no, (const uint8_t*)it.p, it.len, it.keys, it.rec_off, it.n_rec); }
+	int finish() override
+	{
+		int r = bwahip_bgzf_write(fd, hdr, hlen, level, 1);
+		// the staging threads have ended, so the merge's BGZF writer gets all host threads (the bytes do not depend on the number of threads)
+		if (!r) r = bwahip_bam_merger_finish(m, fd, level, n_threads > 1 ? n_threads : 1);
+		bwahip_bam_merger_stats(m, n_records, n_runs, spilled_bytes, merge_s);
+		*sort_ms_out = sort_ms;
+		return r ? r : bwahip_bgzf_eof(fd);
+	}
+};
+
+// Coordinate-sorted BAM merged on the device: every batch is a run of the device merger, copied device to device into buffers of its own,
+// while the HBM budget holds; from the first run that does not fit (or came back downloaded because its buffers could not be allocated)
+// the run ends as the host-merged one: the runs held so far go to its merger in run order, every later one is downloaded.  No host thread
+// deflates.  Without a fall-back the header is written at level 1 and the device merger writes the rest (k_bammerge.hip).
+struct DevSortedSink : Sink {
+	bwahip_sort_dev_t *sd; SortedSink host;
+	bwahip_bam_devmerger *dm = nullptr; bwahip_ctx *ctx0 = nullptr;
+	int64_t hbm_budget = 0, held_raw = 0, held_rec = 0; int piece_blocks = 0;
+	std::atomic<bool> fell_back{false};                          // read by the drainers: from now on they download
+	hipStream_t fb_stream = nullptr; HostBuf fb_rec, fb_keys, fb_off;   // the fall-back's downloads: their stream, one pinned buffer each for records, keys and offsets
+	DevSortedSink(const char *h, bwahip_sort_dev_t *s) : sd(s), host(h, s->level, s) { form = OutForm::BamSorted; }
+	~DevSortedSink()
+	{
+		if (ctx0) (void)hipSetDevice(ctx0->device);
+		if (fb_stream) (void)hipStreamDestroy(fb_stream);
+		fb_rec.release(); fb_keys.release(); fb_off.release(); bwahip_bam_devmerger_close(dm);
+	}
+	int open(bwahip_ctx *const *ctxs, int n_ctx) override
+	{
+		for (int i = 1; i < n_ctx; ++i) if (ctxs[i]->device != ctxs[0]->device) return BWAHIP_EINVAL;   // the runs of all contexts meet in one device's merger
+		if (sd->piece_blocks > 4096 || sd->hbm_budget < 0) return BWAHIP_EINVAL;
+		host.fd = fd; host.n_threads = n_threads;
+		int r = host.prepare(ctxs[0]);                              // the host merger itself is opened only at a fall-back: tmp_dir is not looked at before
+		if (r) return r;
+		sd->fell_back = 0; sd->fell_back_at_run = 0; memset(&sd->dev, 0, sizeof sd->dev);
+		if ((r = bwahip_bam_devmerger_open(ctxs[0], sd->piece_blocks, &dm))) return r;
+		ctx0 = ctxs[0]; hbm_budget = sd->hbm_budget;
+		piece_blocks = sd->piece_blocks > 0 ? sd->piece_blocks : ctx0->knobs.sorted_piece_blocks;
+		if (!hbm_budget) {                                          // half of what the device has free now
+			size_t mem_free = 0, mem_total = 0;
+			HIP_TRY(hipSetDevice(ctx0->device));
+			HIP_TRY(hipMemGetInfo(&mem_free, &mem_total));
+			hbm_budget = (int64_t)(mem_free / 2);
+		}
+		return 0;
+	}
+	int stage_out(bwahip_ctx *c, int out, Item &it, double *t_end) override
+	{
+		if (!fell_back) {                                           // the run stays in HBM: no download, the writer gets an item without bytes and both sets go back at once
+			const int r = pipe_stage_out_devrun(c, out, &it.run, &it.raw_len, &it.n_rec, &it.gpu_ms, t_end);
+			if (r || it.run) { it.len = it.raw_len; it.holds_set = false; return r; }
+		}                                                           // (its buffers could not be allocated: downloaded as any run after a fall-back, which it causes)
+		return host.stage_out(c, out, it, t_end);
+	}
+	// a run in HBM -> the host merger, through the pinned buffers; the run is freed whatever happens
+	int run_to_host(int64_t run_no, DevRun *r, double sort_ms)
+	{
+		int rc = hipSetDevice(ctx0->device) == hipSuccess ? 0 : BWAHIP_ENODEV;
+		if (!rc && !fb_stream && hipStreamCreateWithFlags(&fb_stream, hipStreamNonBlocking) != hipSuccess) rc = BWAHIP_ENODEV;
+		if (!rc && ((rc = fb_rec.ensure((size_t)r->len + 1)) || (rc = fb_keys.ensure((size_t)(r->n_rec + 1) * 8)) || (rc = fb_off.ensure((size_t)(r->n_rec + 1) * 8)))) {}
+		if (!rc) rc = bam_devrun_download(r, (uint8_t*)fb_rec.p, (uint64_t*)fb_keys.p, (int64_t*)fb_off.p, fb_stream);
+		Item h; h.p = (const char*)fb_rec.p; h.len = r->len; h.keys = (const uint64_t*)fb_keys.p; h.rec_off = (const int64_t*)fb_off.p; h.n_rec = r->n_rec; h.gpu_ms = sort_ms;
+		if (!rc) rc = host.write(run_no, h);
+		bam_devrun_free(r);
+		return rc;
+	}
+	// run `at` does not fit: the host merger is opened and takes the runs held so far, in run order
+	int fall_back(int64_t at)
+	{
+		int rc = bwahip_bam_merger_open(host.tmp_dir, host.mem_budget, &host.m);
+		std::vector<std::pair<int64_t, DevRun*>> held;
+		bam_devmerger_take_runs(dm, &held);
+		for (auto &h : held) { if (!rc) rc = run_to_host(h.first, h.second, 0); else bam_devrun_free(h.second); }
+		fell_back = true; sd->fell_back = 1; sd->fell_back_at_run = at;
+		return rc;
+	}
+	int write(int64_t seq_no, Item &it) override
+	{
+		int r = 0;
+		if (!fell_back) {                                           // in input order, so the decision depends on the input and the budget alone
+			const bool fits = it.run && bwahip_bam_devmerge_hbm_need(held_raw + it.raw_len, held_rec + it.n_rec, seq_no + 1, piece_blocks) <= hbm_budget;
+			if (!fits) r = fall_back(seq_no);
+		}
+		if (!r && !fell_back) { if (!(r = bam_devmerger_adopt(dm, seq_no, it.run))) { it.run = nullptr; held_raw += it.raw_len; held_rec += it.n_rec; host.sort_ms += it.gpu_ms; } }
+		else if (!r && it.run) { r = run_to_host(seq_no, it.run, it.gpu_ms); it.run = nullptr; }
+		else if (!r) r = host.write(seq_no, it);
+		drop(it);                                                   // refused, or the fall-back failed before its turn
+		return r;
+	}
+	void drop(Item &it) override { if (it.run) bam_devrun_free(it.run); it.run = nullptr; }
+	int finish() override
+	{
+		if (fell_back) return host.finish();                        // from here on this is the host-merged run at sd->level
+		int r = bwahip_bgzf_write(fd, host.hdr, host.hlen, 1, 1);
+		if (!r) r = bwahip_bam_devmerger_finish(dm, fd, &sd->dev);
+		if (!r) { sd->n_records = sd->dev.n_records; sd->n_runs = sd->dev.n_runs; sd->merge_s = sd->dev.finish_s; }
+		sd->sort_ms = host.sort_ms;
+		return r ? r : bwahip_bgzf_eof(fd);
+	}
+};
+
 struct Driver {
 	// reader side
 	std::mutex mu_read;
@@ -48,112 +225,18 @@ struct Driver {
 	bool eof = false;
 	// writer side
 	std::mutex mu;
-	std::condition_variable cv_item, cv_done;
-	struct Item { const char *p; int64_t len; int ctx, out; const uint64_t *keys; const int64_t *rec_off; int64_t n_rec; int64_t raw_len; DevRun *run; };   // ctx / out: the output set the bytes sit in; keys, rec_off: coordinate-sorted BAM; run (bam == 4): the batch as a run in HBM -- no bytes, and the output set went back to its context already
+	std::condition_variable cv_item;
 	std::map<int64_t, Item> ready;                               // finished batches waiting for their turn
-	int64_t written = 0;                                         // batches [0, written) are on the descriptor
+	int64_t written = 0;                                         // batches [0, written) are with the sink
 	int workers_left = 0;
 	int rc = 0;                                                  // first error (the stages and the writer stop on it)
 	std::atomic<bool> stop{false};                               // rc != 0, readable without the lock
 	std::function<void()> wake_all;                              // wakes every context's threads (failure)
-	std::function<void(const Item&, int64_t, double, double)> on_written;   // gives the output set back to its context
-	int fd = -1;
-	int bam = 0, level = 0, deflate_threads = 1;                 // bwahip_stream_run_bam: the batches' records go through the BGZF writer
-	bwahip_bam_merger *merger = nullptr;                         // bam == 2 (bwahip_stream_run_bam_sorted): every batch is a sorted run of the merger instead
-	double sort_ms = 0;
-	// bam == 4 (bwahip_stream_run_bam_sorted_dev): every batch is a run of the device merger while the HBM budget holds; from the first run
-	// that does not fit (or came back downloaded because its buffers could not be allocated) every run goes to the host merger
-	bwahip_bam_devmerger *devm = nullptr;
-	bwahip_sort_dev_t *sd = nullptr;
-	bwahip_ctx *ctx0 = nullptr;
-	int64_t hbm_budget = 0, held_raw = 0, held_rec = 0;
-	int piece_blocks = 0;
-	std::atomic<bool> fell_back{false};                          // read by the drainers: from now on they download
-	hipStream_t fb_stream = nullptr;                             // the fall-back's downloads: one pinned buffer each for records, keys and offsets
-	HostBuf fb_rec, fb_keys, fb_off;
-	bwahip_bgzf_stats_t bz = { 0, 0, 0, 0, 0 };                  // bam == 3 (bwahip_stream_run_bam_dev): the batches arrive as BGZF members and are only written
 	int64_t sam_bytes = 0;
 	double t_last_write = 0, write_s = 0;
 
-	void fail(int code) { { std::lock_guard<std::mutex> lk(mu); if (!rc) rc = code; stop = true; } cv_item.notify_all(); cv_done.notify_all(); if (wake_all) wake_all(); }
+	void fail(int code) { { std::lock_guard<std::mutex> lk(mu); if (!rc) rc = code; stop = true; } cv_item.notify_all(); if (wake_all) wake_all(); }
 	bool failed() { return stop.load(); }
-
-	// a run in HBM -> the host merger, through the pinned buffers; the run is freed whatever happens
-	int run_to_host(int64_t run_no, DevRun *r)
-	{
-		int rc = hipSetDevice(ctx0->device) == hipSuccess ? 0 : BWAHIP_ENODEV;
-		if (!rc && !fb_stream && hipStreamCreateWithFlags(&fb_stream, hipStreamNonBlocking) != hipSuccess) rc = BWAHIP_ENODEV;
-		if (!rc && ((rc = fb_rec.ensure((size_t)r->len + 1)) || (rc = fb_keys.ensure((size_t)(r->n_rec + 1) * 8)) || (rc = fb_off.ensure((size_t)(r->n_rec + 1) * 8)))) {}
-		if (!rc) rc = bam_devrun_download(r, (uint8_t*)fb_rec.p, (uint64_t*)fb_keys.p, (int64_t*)fb_off.p, fb_stream);
-		if (!rc) rc = bwahip_bam_merger_add(merger, run_no, (const uint8_t*)fb_rec.p, r->len, (const uint64_t*)fb_keys.p, (const int64_t*)fb_off.p, r->n_rec);
-		bam_devrun_free(r);
-		return rc;
-	}
-	// run `at` does not fit: the host merger is opened (only now is tmp_dir looked at) and takes the runs held so far, in run order
-	int fall_back(int64_t at)
-	{
-		int rc = bwahip_bam_merger_open(sd->tmp_dir, sd->mem_budget, &merger);
-		std::vector<std::pair<int64_t, DevRun*>> held;
-		bam_devmerger_take_runs(devm, &held);
-		for (auto &h : held) { if (!rc) rc = run_to_host(h.first, h.second); else bam_devrun_free(h.second); }
-		fell_back = true; sd->fell_back = 1; sd->fell_back_at_run = at;
-		return rc;
-	}
-	void fb_release()
-	{
-		if (ctx0) (void)hipSetDevice(ctx0->device);
-		if (fb_stream) { (void)hipStreamDestroy(fb_stream); fb_stream = nullptr; }
-		fb_rec.release(); fb_keys.release(); fb_off.release();
-	}
-
-	void writer()
-	{
-		for (;;) {
-			Item it;
-			{
-				std::unique_lock<std::mutex> lk(mu);
-				cv_item.wait(lk, [&] { return rc || ready.count(written) || (workers_left == 0 && ready.empty()); });
-				if (rc || !ready.count(written)) return;
-				it = ready[written];
-				ready.erase(written);
-			}
-			const double t0 = now_s();
-			int64_t o = 0;
-			if (bam == 4) {
-				int r = 0;
-				if (!fell_back) {                                       // in input order, so the decision depends on the input and the budget alone
-					const bool fits = it.run && bwahip_bam_devmerge_hbm_need(held_raw + it.raw_len, held_rec + it.n_rec, written + 1, piece_blocks) <= hbm_budget;
-					if (!fits) r = fall_back(written);
-				}
-				if (!r && !fell_back) { if (!(r = bam_devmerger_adopt(devm, written, it.run))) { it.run = nullptr; held_raw += it.raw_len; held_rec += it.n_rec; } }
-				else if (!r && it.run) { r = run_to_host(written, it.run); it.run = nullptr; }
-				else if (!r) r = bwahip_bam_merger_add(merger, written, (const uint8_t*)it.p, it.len, it.keys, it.rec_off, it.n_rec);
-				if (it.run) bam_devrun_free(it.run);                    // refused, or the fall-back failed before its turn
-				if (r) { fail(r); return; }
-				o = it.len;
-			} else if (bam == 2) {                                       // the merger copies (or spills) the run: the set goes back at once
-				const int r = bwahip_bam_merger_add(merger, written, (const uint8_t*)it.p, it.len, it.keys, it.rec_off, it.n_rec);
-				if (r) { fail(r); return; }
-				o = it.len;
-			} else if (bam == 1) {
-				const int r = bwahip_bgzf_write(fd, it.p, it.len, level, deflate_threads);
-				if (r) { fail(r); return; }
-				o = it.len;
-			}
-			while (fd >= 0 && o < it.len) {
-				const ssize_t w = write(fd, it.p + o, (size_t)(it.len - o > (1ll << 30) ? (1ll << 30) : it.len - o));
-				if (w < 0) { if (errno == EINTR) continue; fprintf(stderr, "[bwahip] writing the SAM text failed: %s\n", strerror(errno)); fail(BWAHIP_EIO); return; }
-				o += w;
-			}
-			int64_t seq_no;
-			{
-				std::lock_guard<std::mutex> lk(mu);
-				seq_no = written++; sam_bytes += bam == 3 ? it.raw_len : it.len; t_last_write = now_s(); write_s += t_last_write - t0;
-			}
-			cv_done.notify_all();
-			on_written(it, seq_no, t0, t_last_write);
-		}
-	}
 };
 
 // Closing the reader (joining its threads, unmapping gigabytes of input: tens of milliseconds of page-table work) is nobody's critical path:
@@ -168,68 +251,28 @@ Reaper g_reaper;
 
 } // namespace
 
-// bam: 0 = SAM text as it comes; 1 = BAM: header, every batch's records through the BGZF writer in input order, the EOF block;
-// 2 = coordinate-sorted BAM: every batch leaves its context sorted and becomes a run of the merger (the batch number is the run number);
-// after the last batch: header, the merge of the runs through the BGZF writer, the EOF block
+// One run of the driver into `sink` (above: SAM text, BAM through the host's BGZF writer, BAM deflated on the GPU, coordinate-sorted BAM
+// merged on the host or on the device)
 static int stream_run(bwahip_ctx *const *ctxs, int n_ctx, const bwahip_opt_t *opt, const bwahip_pestat_t *pes0,
-                      const char *fq1, const char *fq2, int out_fd, bwahip_stream_t *st, int bam, const char *hdr_line, int level, bwahip_sort_t *so = nullptr, bwahip_bgzf_stats_t *bs = nullptr,
-                      bwahip_sort_dev_t *sd = nullptr)
+                      const char *fq1, const char *fq2, int out_fd, bwahip_stream_t *st, Sink &sink)
 {
-	if (!ctxs || n_ctx < 1 || n_ctx > 256 || !opt || !fq1 || !st || (bam == 2 && !so) || (bam == 3 && !bs) || (bam == 4 && !sd)) return BWAHIP_EINVAL;
+	if (!ctxs || n_ctx < 1 || n_ctx > 256 || !opt || !fq1 || !st) return BWAHIP_EINVAL;
 	for (int i = 0; i < n_ctx; ++i) if (!ctxs[i]) return BWAHIP_EINVAL;
-	if (bam && (level < 0 || level > 9)) return BWAHIP_EINVAL;
-	if (bam == 4) {
-		for (int i = 1; i < n_ctx; ++i) if (ctxs[i]->device != ctxs[0]->device) return BWAHIP_EINVAL;   // the runs of all contexts meet in one device's merger
-		if (sd->piece_blocks > 4096 || sd->hbm_budget < 0 || sd->level < 0 || sd->level > 9) return BWAHIP_EINVAL;
-	}
-	const int bam_pipe = bam == 4 ? 2 : bam;                       // what the contexts compute: mode 4 is mode 2 up to the stage-out
 	// actual_chunk_size (fastmap.c:304): -K when given, else chunk_size * n_threads
 	const int64_t chunk = st->chunk_bases > 0 ? st->chunk_bases : (int64_t)opt->chunk_size * (opt->n_threads > 0 ? opt->n_threads : 1);
 	bwahip_opt_t o = *opt;
 	if (fq2) o.flag |= BWAHIP_F_PE;
-	// opt->n_threads is the host-thread budget of the whole run; BAM: half of it deflates, the other half stages the batches
-	// (bam == 3: the GPU deflates, all of it stages)
-	const int n_deflate = bam && bam != 3 && bam != 4 ? (opt->n_threads / 2 > 1 ? opt->n_threads / 2 : 1) : 0;
-	const int n_stage = bam && opt->n_threads > n_deflate ? opt->n_threads - n_deflate : opt->n_threads;
+	// opt->n_threads is the host-thread budget of the whole run: where the sink deflates on the host, half of it does, and the rest stages the batches
+	const int n_deflate = sink.host_deflates ? (opt->n_threads / 2 > 1 ? opt->n_threads / 2 : 1) : 0;
+	const int n_stage = opt->n_threads > n_deflate ? opt->n_threads - n_deflate : opt->n_threads;
 	o.n_threads = n_stage / n_ctx > 1 ? n_stage / n_ctx : 1;
 	Driver d;
-	d.fd = out_fd; d.max_reads = st->max_reads;
-	d.bam = bam; d.level = level; d.deflate_threads = n_deflate;
-	struct Sorted {                                              // the header waits for the merge; the merger and its files go whatever happens
-		uint8_t *hdr = nullptr; int64_t hlen = 0; bwahip_bam_merger *m = nullptr; bwahip_bam_devmerger *dm = nullptr;
-		~Sorted() { free(hdr); bwahip_bam_merger_close(m); bwahip_bam_devmerger_close(dm); }
-	} sorted;
-	if (bam == 4) {
-		sd->fell_back = 0; sd->fell_back_at_run = 0; sd->n_records = sd->n_runs = sd->spilled_bytes = 0; sd->sort_ms = sd->merge_s = 0;
-		memset(&sd->dev, 0, sizeof sd->dev);
-		int hr = bwahip_bam_header_sorted(bwahip_bns(ctxs[0]), hdr_line, &sorted.hdr, &sorted.hlen);
-		if (!hr) hr = bwahip_bam_devmerger_open(ctxs[0], sd->piece_blocks, &sorted.dm);
-		if (hr) return hr;
-		d.devm = sorted.dm; d.sd = sd; d.ctx0 = ctxs[0];
-		d.piece_blocks = sd->piece_blocks > 0 ? sd->piece_blocks : ctxs[0]->knobs.sorted_piece_blocks;
-		d.hbm_budget = sd->hbm_budget;
-		if (!d.hbm_budget) {                                         // half of what the device has free now
-			size_t mem_free = 0, mem_total = 0;
-			HIP_TRY(hipSetDevice(ctxs[0]->device));
-			HIP_TRY(hipMemGetInfo(&mem_free, &mem_total));
-			d.hbm_budget = (int64_t)(mem_free / 2);
-		}
-	}
-	if (bam == 2) {
-		so->n_records = so->n_runs = so->spilled_bytes = 0; so->sort_ms = so->merge_s = 0;
-		int hr = bwahip_bam_header_sorted(bwahip_bns(ctxs[0]), hdr_line, &sorted.hdr, &sorted.hlen);
-		if (!hr) hr = bwahip_bam_merger_open(so->tmp_dir, so->mem_budget, &sorted.m);
-		if (hr) return hr;
-		d.merger = sorted.m;
-	}
-	if (bam == 1 || bam == 3) {
-		uint8_t *hdr = nullptr; int64_t hlen = 0;
-		int hr = bwahip_bam_header(bwahip_bns(ctxs[0]), hdr_line, &hdr, &hlen);
-		if (!hr) { hr = bwahip_bgzf_write(out_fd, hdr, hlen, level, 1); free(hdr); }
-		if (hr) return hr;
-	}
+	d.max_reads = st->max_reads;
+	sink.fd = out_fd; sink.n_threads = opt->n_threads; sink.n_deflate = n_deflate;
+	int rc = sink.open(ctxs, n_ctx);
+	if (rc) return rc;
 	const double t_call = now_s();
-	int rc = bwahip_fastq_open_mt(fq1, fq2, st->reader_threads, &d.rd);
+	rc = bwahip_fastq_open_mt(fq1, fq2, st->reader_threads, &d.rd);
 	if (rc) return rc;
 	st->n_reads = st->n_batches = st->sam_bytes = 0; st->seconds = st->reader_wait_s = st->write_s = st->gpu_busy_s = 0;
 	const double t_start = now_s();
@@ -255,14 +298,6 @@ static int stream_run(bwahip_ctx *const *ctxs, int n_ctx, const bwahip_opt_t *op
 	std::mutex mu_log; std::vector<Span> spans;
 	auto span = [&](const char *stage, int64_t batch, int ctx, double t0, double t1) { if (log) { std::lock_guard<std::mutex> lk(mu_log); spans.push_back({ stage, batch, ctx, t0, t1 }); } };
 	d.wake_all = [&] { for (auto &p : pipes) { { std::lock_guard<std::mutex> lk(p.mu); } p.cv.notify_all(); } };
-	d.on_written = [&](const Driver::Item &it, int64_t seq_no, double t0, double t1) {
-		Pipe &p = pipes[it.ctx];
-		if (it.p) {                                                  // (a run that stayed in HBM: its drainer gave the set back, and it may be in use again)
-			{ std::lock_guard<std::mutex> lk(p.mu); p.out_free[it.out] = true; }
-			p.cv.notify_all();
-		}
-		span("write", seq_no, it.ctx, t0, t1);
-	};
 	int n_open = 0;
 	for (; n_open < n_ctx; ++n_open) if ((rc = pipe_open(ctxs[n_open], o.n_threads))) break;
 	if (rc) { for (int w = 0; w <= n_open && w < n_ctx; ++w) pipe_close(ctxs[w]); bwahip_fastq_close(d.rd); return rc; }
@@ -297,7 +332,7 @@ static int stream_run(bwahip_ctx *const *ctxs, int n_ctx, const bwahip_opt_t *op
 			if (eof) break;
 			span("take", j.seq_no, w, t0, t1);
 			double t_copy = t1;
-			const int r = pipe_stage_in(ctxs[w], j.in, &o, j.n, seqs, bam_pipe, &t_copy);
+			const int r = pipe_stage_in(ctxs[w], j.in, &o, j.n, seqs, sink.form, &t_copy);
 			bwahip_fastq_batch_release(b);                          // names, bases and qualities are in HBM
 			const double t2 = now_s();
 			if (r) { d.fail(r); break; }
@@ -321,7 +356,7 @@ static int stream_run(bwahip_ctx *const *ctxs, int n_ctx, const bwahip_opt_t *op
 			}
 			const double t0 = now_s();
 			double t_hot = t0;
-			const int r = pipe_compute(ctxs[w], j.in, j.out, &o, j.np0, pes0, bam_pipe, &t_hot);
+			const int r = pipe_compute(ctxs[w], j.in, j.out, &o, j.np0, pes0, sink.form, &t_hot);
 			if (r) { d.fail(r); break; }
 			span("hot", j.seq_no, w, t0, t_hot);
 			j.t_final = t_hot;
@@ -342,45 +377,15 @@ static int stream_run(bwahip_ctx *const *ctxs, int n_ctx, const bwahip_opt_t *op
 				if (d.failed() || p.computed.empty()) break;
 				j = p.computed.front(); p.computed.pop_front();
 			}
-			const char *sam = nullptr; int64_t len = 0;
+			Item it; it.ctx = w; it.out = j.out;
 			double t_end = 0;
-			if (bam == 4 && !d.fell_back) {                           // the run stays in HBM: no download, the writer gets an item without bytes
-				DevRun *run = nullptr; int64_t raw = 0, nr = 0; double sort_ms = 0;
-				const int r4 = pipe_stage_out_devrun(ctxs[w], j.out, &run, &raw, &nr, &sort_ms, &t_end);
-				if (r4) { d.fail(r4); break; }
-				if (run) {
-					const double t1 = now_s();
-					{ std::lock_guard<std::mutex> lk(p.mu); p.in_free[j.in] = true; p.out_free[j.out] = true; }   // the copies have ended: both sets go back at once
-					p.cv.notify_all();
-					span("final", j.seq_no, w, j.t_final, t_end); span("d2d", j.seq_no, w, t_end, t1);
-					{
-						std::lock_guard<std::mutex> lk(d.mu);
-						if (d.rc) bam_devrun_free(run);                     // the writer has gone: nobody would take it
-						else d.ready[j.seq_no] = { nullptr, raw, w, j.out, nullptr, nullptr, nr, raw, run };
-						d.sort_ms += sort_ms;
-					}
-					d.cv_item.notify_all();
-					continue;
-				}
-			}                                                         // (its buffers could not be allocated: downloaded as any run after a fall-back, which it causes)
-			const int r = pipe_stage_out(ctxs[w], j.out, &sam, &len, &t_end);
+			const int r = sink.stage_out(ctxs[w], j.out, it, &t_end);
 			const double t1 = now_s();
 			if (r) { d.fail(r); break; }
-			{ std::lock_guard<std::mutex> lk(p.mu); p.in_free[j.in] = true; }   // the kernels that read the input set have ended
+			{ std::lock_guard<std::mutex> lk(p.mu); p.in_free[j.in] = true; if (!it.holds_set) p.out_free[j.out] = true; }   // the kernels that read the input set have ended; an output set the item does not hold was copied from
 			p.cv.notify_all();
-			span("final", j.seq_no, w, j.t_final, t_end); span("d2h", j.seq_no, w, t_end, t1);
-			const uint64_t *keys = nullptr; const int64_t *rec_off = nullptr; int64_t n_rec = 0;
-			double sort_ms = 0;
-			if (bam_pipe == 2) { const int r2 = pipe_stage_out_sorted(ctxs[w], j.out, &keys, &rec_off, &n_rec, &sort_ms); if (r2) { d.fail(r2); break; } }
-			int64_t raw_len = len, n_blocks = 0, n_stored = 0;
-			double deflate_ms = 0;
-			if (bam == 3) { const int r3 = pipe_stage_out_bgzf(ctxs[w], j.out, &raw_len, &n_blocks, &n_stored, &deflate_ms); if (r3) { d.fail(r3); break; } }
-			{
-				std::lock_guard<std::mutex> lk(d.mu);
-				d.ready[j.seq_no] = { sam, len, w, j.out, keys, rec_off, n_rec, raw_len, nullptr };
-				d.sort_ms += sort_ms;
-				if (bam == 3) { d.bz.raw_bytes += raw_len; d.bz.bgzf_bytes += len; d.bz.n_blocks += n_blocks; d.bz.n_stored += n_stored; d.bz.deflate_ms += deflate_ms; }
-			}
+			span("final", j.seq_no, w, j.t_final, t_end); span(it.holds_set ? "d2h" : "d2d", j.seq_no, w, t_end, t1);
+			{ std::lock_guard<std::mutex> lk(d.mu); if (d.rc) sink.drop(it); else d.ready[j.seq_no] = it; }   // (dropped: the writer has gone, nobody would take it)
 			d.cv_item.notify_all();
 		}
 		// the buffers must outlive their write
@@ -388,74 +393,69 @@ static int stream_run(bwahip_ctx *const *ctxs, int n_ctx, const bwahip_opt_t *op
 		{ std::lock_guard<std::mutex> lk(d.mu); --d.workers_left; }
 		d.cv_item.notify_all();
 	};
-	std::thread wr([&] { d.writer(); });
+	auto writer = [&] {
+		for (;;) {
+			Item it;
+			{
+				std::unique_lock<std::mutex> lk(d.mu);
+				d.cv_item.wait(lk, [&] { return d.rc || d.ready.count(d.written) || (d.workers_left == 0 && d.ready.empty()); });
+				if (d.rc || !d.ready.count(d.written)) return;
+				it = d.ready[d.written];
+				d.ready.erase(d.written);
+			}
+			const double t0 = now_s();
+			const int r = sink.write(d.written, it);
+			if (r) { d.fail(r); return; }
+			int64_t seq_no;
+			{ std::lock_guard<std::mutex> lk(d.mu); seq_no = d.written++; d.sam_bytes += it.raw_len; d.t_last_write = now_s(); d.write_s += d.t_last_write - t0; }
+			if (it.holds_set) {                                        // the bytes are taken: the output set goes back to its context
+				Pipe &p = pipes[it.ctx];
+				{ std::lock_guard<std::mutex> lk(p.mu); p.out_free[it.out] = true; }
+				p.cv.notify_all();
+			}
+			span("write", seq_no, it.ctx, t0, d.t_last_write);
+		}
+	};
+	std::thread wr(writer);
 	std::vector<std::thread> th;
 	for (int w = 0; w < n_ctx; ++w) { th.emplace_back(stager, w); th.emplace_back(compute, w); th.emplace_back(drainer, w); }
 	for (auto &t : th) t.join();
 	wr.join();
 	for (int w = 0; w < n_ctx; ++w) pipe_close(ctxs[w]);           // after a failure kernels and copies may still be queued: nothing is left running
-	std::vector<double> wait_s(n_ctx), busy_s(n_ctx);
-	for (int w = 0; w < n_ctx; ++w) { wait_s[w] = pipes[w].wait_s; busy_s[w] = pipes[w].busy_s; }
-	if (bam == 2 && !d.rc) {                                     // every run is with the merger: header, merge, end-of-file block
+	for (auto &kv : d.ready) sink.drop(kv.second);                 // after a failure: items nobody took
+	if (!d.rc) {                                                  // what the file still lacks: header and merge of a sorted one, the end-of-file block
 		const double t0 = now_s();
-		int r = bwahip_bgzf_write(out_fd, sorted.hdr, sorted.hlen, level, 1);
-		// the staging threads have ended, so the merge's BGZF writer gets all host threads, not the n_deflate the unsorted writer
-		// shares the host with them for (the bytes do not depend on the number of threads)
-		if (!r) r = bwahip_bam_merger_finish(sorted.m, out_fd, level, opt->n_threads > 1 ? opt->n_threads : 1);
-		if (r) d.rc = r;
+		d.rc = sink.finish();
 		d.write_s += now_s() - t0;
-		bwahip_bam_merger_stats(sorted.m, &so->n_records, &so->n_runs, &so->spilled_bytes, &so->merge_s);
-		so->sort_ms = d.sort_ms;
+		if (is_bam(sink.form) && !d.rc) d.t_last_write = now_s();
 	}
-	if (bam == 4) {
-		for (auto &kv : d.ready) if (kv.second.run) bam_devrun_free(kv.second.run);   // after a failure: runs nobody took
-		d.ready.clear();
-		d.fb_release();
-		sorted.m = d.merger;                                        // closed (and its files removed) whatever happens
-	}
-	if (bam == 4 && !d.rc) {                                     // every run is with one of the two mergers: header, merge, end-of-file block
-		const double t0 = now_s();
-		const bool fb = d.fell_back;
-		int r = bwahip_bgzf_write(out_fd, sorted.hdr, sorted.hlen, fb ? sd->level : 1, 1);
-		if (!r && fb) {                                             // from here on this is bwahip_stream_run_bam_sorted at sd->level
-			r = bwahip_bam_merger_finish(sorted.m, out_fd, sd->level, opt->n_threads > 1 ? opt->n_threads : 1);
-			bwahip_bam_merger_stats(sorted.m, &sd->n_records, &sd->n_runs, &sd->spilled_bytes, &sd->merge_s);
-		} else if (!r) {
-			r = bwahip_bam_devmerger_finish(sorted.dm, out_fd, &sd->dev);
-			sd->n_records = sd->dev.n_records; sd->n_runs = sd->dev.n_runs; sd->merge_s = sd->dev.finish_s;
-		}
-		if (r) d.rc = r;
-		d.write_s += now_s() - t0;
-		sd->sort_ms = d.sort_ms;
-	}
-	if (bam && !d.rc) { const int r = bwahip_bgzf_eof(out_fd); if (r) d.rc = r; d.t_last_write = now_s(); }
 	const double t_joined = now_s();
 	g_reaper.close_later(d.rd);
 	if (log) {
 		for (const Span &x : spans) fprintf(stderr, "[bwahip] span %s batch %lld ctx %d %.3f %.3f\n", x.stage, (long long)x.batch, x.ctx, (x.t0 - t_call) * 1e3, (x.t1 - t_call) * 1e3);
 		fprintf(stderr, "[bwahip] stream: %lld batches on %d contexts, %ld buffer reallocations in this pass\n", (long long)d.next_seq, n_ctx, pipe_realloc_count() - reallocs0);
-	}
-	if (log)
 		fprintf(stderr, "[bwahip] stream: open %.1f ms, first batch in -> last SAM byte out %.1f ms, joining the threads %.1f ms, handing the reader to the closer %.1f ms\n",
 		        (t_start - t_call) * 1e3, (d.t_last_write - t_start) * 1e3, (t_joined - d.t_last_write) * 1e3, (now_s() - t_joined) * 1e3);
-	if (bs) *bs = d.bz;
+	}
 	st->n_reads = d.n_processed; st->n_batches = d.next_seq; st->sam_bytes = d.sam_bytes;
 	st->seconds = d.t_last_write - t_call; st->write_s = d.write_s;
-	for (int w = 0; w < n_ctx; ++w) { st->reader_wait_s += wait_s[w]; st->gpu_busy_s += busy_s[w]; }
+	for (const Pipe &p : pipes) { st->reader_wait_s += p.wait_s; st->gpu_busy_s += p.busy_s; }
 	return d.rc;
 }
 
 extern "C" int bwahip_stream_run(bwahip_ctx *const *ctxs, int n_ctx, const bwahip_opt_t *opt, const bwahip_pestat_t *pes0,
                                  const char *fq1, const char *fq2, int out_fd, bwahip_stream_t *st)
 {
-	return stream_run(ctxs, n_ctx, opt, pes0, fq1, fq2, out_fd, st, 0, nullptr, 0);
+	Sink sink;
+	return stream_run(ctxs, n_ctx, opt, pes0, fq1, fq2, out_fd, st, sink);
 }
 
 // FASTQ files in -> a BAM file out: bwahip_stream_run with bwahip_process_seqs_bam in the workers and the BGZF writer behind them
 extern "C" int bwahip_stream_run_bam(bwahip_ctx *const *ctxs, int n_ctx, const bwahip_opt_t *opt, const bwahip_pestat_t *pes0,
                                      const char *fq1, const char *fq2, int out_fd, const char *hdr_line, int level, bwahip_stream_t *st)
 {
-	return stream_run(ctxs, n_ctx, opt, pes0, fq1, fq2, out_fd, st, 1, hdr_line, level);
+	BamSink sink(hdr_line, level);
+	return stream_run(ctxs, n_ctx, opt, pes0, fq1, fq2, out_fd, st, sink);
 }
 
 // FASTQ files in -> a coordinate-sorted BAM file out: every batch is sorted on its context (bwahip_process_seqs_bam_sorted's kernels) and
@@ -463,7 +463,9 @@ extern "C" int bwahip_stream_run_bam(bwahip_ctx *const *ctxs, int n_ctx, const b
 extern "C" int bwahip_stream_run_bam_sorted(bwahip_ctx *const *ctxs, int n_ctx, const bwahip_opt_t *opt, const bwahip_pestat_t *pes0,
                                             const char *fq1, const char *fq2, int out_fd, const char *hdr_line, int level, bwahip_stream_t *st, bwahip_sort_t *so)
 {
-	return stream_run(ctxs, n_ctx, opt, pes0, fq1, fq2, out_fd, st, 2, hdr_line, level, so);
+	if (!so) return BWAHIP_EINVAL;
+	SortedSink sink(hdr_line, level, so);
+	return stream_run(ctxs, n_ctx, opt, pes0, fq1, fq2, out_fd, st, sink);
 }
 
 // FASTQ files in -> a BAM file out with the BGZF blocks of the records made on the GPU (k_bgzf.hip): the header through the host writer,
@@ -473,7 +475,8 @@ extern "C" int bwahip_stream_run_bam_dev(bwahip_ctx *const *ctxs, int n_ctx, con
 {
 	if (!bs) return BWAHIP_EINVAL;
 	memset(bs, 0, sizeof *bs);
-	return stream_run(ctxs, n_ctx, opt, pes0, fq1, fq2, out_fd, st, 3, hdr_line, 1, nullptr, bs);
+	BamSink sink(hdr_line, 1, bs);
+	return stream_run(ctxs, n_ctx, opt, pes0, fq1, fq2, out_fd, st, sink);
 }
 
 // FASTQ files in -> a coordinate-sorted BAM file out with the runs kept in HBM: every batch is sorted on its context as above, copied device
@@ -483,5 +486,6 @@ extern "C" int bwahip_stream_run_bam_sorted_dev(bwahip_ctx *const *ctxs, int n_c
                                                 const char *fq1, const char *fq2, int out_fd, const char *hdr_line, bwahip_stream_t *st, bwahip_sort_dev_t *sd)
 {
 	if (!sd) return BWAHIP_EINVAL;
-	return stream_run(ctxs, n_ctx, opt, pes0, fq1, fq2, out_fd, st, 4, hdr_line, 1, nullptr, nullptr, sd);
+	DevSortedSink sink(hdr_line, sd);
+	return stream_run(ctxs, n_ctx, opt, pes0, fq1, fq2, out_fd, st, sink);
 }

@@ -9,6 +9,7 @@
 // and no stage touches (let alone reallocates) a set another stage holds.  Not part of the C ABI.
 #pragma once
 #include "../../include/bwahip.h"
+#include "ctx_internal.h"                                       // OutForm, DevRun
 
 constexpr int PIPE_SETS = 2;
 
@@ -18,25 +19,24 @@ int pipe_open(bwahip_ctx *c, int n_threads);
 void pipe_close(bwahip_ctx *c);
 // Offsets, longest read, gather into the pinned buffer of input set `in`, asynchronous copies to HBM on the copy stream; returns when the
 // copies are done (the caller is a staging thread with nothing else to do), so `seqs` may be released on return.  Nothing is written to `seqs`.
-int pipe_stage_in(bwahip_ctx *c, int in, const bwahip_opt_t *opt, int n, const bwahip_seq_t *seqs, int bam, double *t_copy_begin);
+int pipe_stage_in(bwahip_ctx *c, int in, const bwahip_opt_t *opt, int n, const bwahip_seq_t *seqs, OutForm form, double *t_copy_begin);
 // k_nt4_conv, the hot path and the finalisation of input set `in` into output set `out`; returns when the write pass is queued
-// (bam == 2: when the gather is queued; the sort stage awaits two small read-backs on the way, the record count and the bits that differ
-// between the keys, so the caller is held until the write pass has ended).
-int pipe_compute(bwahip_ctx *c, int in, int out, const bwahip_opt_t *opt, int64_t n_processed, const bwahip_pestat_t *pes0, int bam, double *t_hot_end);   // bam: 0 SAM text, 1 BAM records, 2 BAM records in coordinate order, 3 BAM records as BGZF members (the deflate stage is queued behind the write pass)
+// (OutForm::BamSorted: when the gather is queued; the sort stage awaits two small read-backs on the way, the record count and the bits that differ
+// between the keys, so the caller is held until the write pass has ended; OutForm::Bgzf: the deflate stage is queued behind the write pass).
+int pipe_compute(bwahip_ctx *c, int in, int out, const bwahip_opt_t *opt, int64_t n_processed, const bwahip_pestat_t *pes0, OutForm form, double *t_hot_end);
 // Waits for the batch's kernels (*t_kernels_end; from here on the input set it used is free), then copies output set `out` to its pinned buffer:
 // *text stays valid until the set is handed to pipe_compute again.
 int pipe_stage_out(bwahip_ctx *c, int out, const char **text, int64_t *len, double *t_kernels_end);
-// After pipe_stage_out of a batch computed with bam == 2 (coordinate-sorted records): the records' keys and offsets, valid as long as the
+// After pipe_stage_out of a batch computed as OutForm::BamSorted (coordinate-sorted records): the records' keys and offsets, valid as long as the
 // text; *sort_ms: the GPU time of the sort stage (record table, radix sort, gather).
 int pipe_stage_out_sorted(bwahip_ctx *c, int out, const uint64_t **keys, const int64_t **rec_off, int64_t *n_rec, double *sort_ms);
-// After pipe_stage_out of a batch computed with bam == 3 (BGZF members, k_bgzf.hip): the uncompressed bytes of the records, the number of
+// After pipe_stage_out of a batch computed as OutForm::Bgzf (BGZF members, k_bgzf.hip): the uncompressed bytes of the records, the number of
 // members and of stored ones, and the GPU time of the deflate stage.
 int pipe_stage_out_bgzf(bwahip_ctx *c, int out, int64_t *raw_len, int64_t *n_blocks, int64_t *n_stored, double *deflate_ms);
-// The stage-out of a batch computed with bam == 2 whose run stays in HBM (bwahip_stream_run_bam_sorted_dev): nothing is downloaded.  Waits for
+// The stage-out of a batch computed as OutForm::BamSorted whose run stays in HBM (bwahip_stream_run_bam_sorted_dev): nothing is downloaded.  Waits for
 // the batch's kernels (*t_kernels_end; the input set is free from here on), allocates the run's own device buffers and copies records,
 // keys and offsets device to device on the copy stream (awaited: output set `out` is free on return).  *run == nullptr with a return of 0:
 // the buffers could not be allocated -- the caller downloads the set with pipe_stage_out / pipe_stage_out_sorted instead.
-struct DevRun;
 int pipe_stage_out_devrun(bwahip_ctx *c, int out, DevRun **run, int64_t *raw_len, int64_t *n_rec, double *sort_ms, double *t_kernels_end);
 // buffers freed and allocated again since the library was loaded (DevBuf / HostBuf ::ensure)
 long pipe_realloc_count();

@@ -8,6 +8,13 @@ import numpy as np
 import common
 from common import bw
 
+def _results(stdout):
+    """every rank's RESULT object, by rank; the ranks and the launcher share one pipe, so a line may hold more than the object"""
+    import json
+    dec = json.JSONDecoder()
+    return sorted((dec.raw_decode(part)[0] for part in stdout.split("RESULT ")[1:]), key=lambda x: x["rank"])
+
+
 WORKER = textwrap.dedent('''
     import os, sys, hashlib, json
     sys.path.insert(0, sys.argv[1]); sys.path.insert(0, os.path.join(sys.argv[1], "bwa-mem-gpu_amd"))
@@ -25,7 +32,7 @@ WORKER = textwrap.dedent('''
     t = torch.tensor([float(rank + 1)], dtype=torch.float64)
     dist.all_reduce(t, op=dist.ReduceOp.MAX)                               # bench.py's max-over-ranks timing
     out["max"] = float(t.item())
-    print("RESULT " + json.dumps(out), flush=True)
+    os.write(1, ("RESULT " + json.dumps(out) + "\\n").encode())          # one write of the whole line: the ranks share the pipe
     dist.barrier(); dist.destroy_process_group()
 ''')
 
@@ -43,7 +50,7 @@ def test_index_broadcast_and_sharding_world_size_2(small_index, tmp_path):
            "--master-port", port, str(script), common.ROOT, small_index["prefix"]]
     r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, env=env, timeout=300)
     assert r.returncode == 0, r.stdout[-2000:]
-    res = sorted((json.loads(l.split("RESULT ", 1)[1]) for l in r.stdout.splitlines() if "RESULT " in l), key=lambda x: x["rank"])
+    res = _results(r.stdout)
     assert [x["rank"] for x in res] == [0, 1]
     assert res[0]["hash"] == res[1]["hash"] and res[0]["meta"] == res[1]["meta"]       # every rank holds the same index
     assert res[0]["reads"] != res[1]["reads"]                                           # but aligns its own reads
@@ -67,7 +74,7 @@ SHARD_WORKER = textwrap.dedent('''
         return ("".join(f"read{i}@{n_processed}\\n" for i in range(b0, b1))).encode()
     sam = tp.align_sharded(dist, rank, world, n, batch, align)
     out = {"rank": rank, "seen": seen, "sam": hashlib.sha256(sam).hexdigest() if sam is not None else None, "n_lines": sam.count(b"\\n") if sam is not None else None}
-    print("RESULT " + json.dumps(out), flush=True)
+    os.write(1, ("RESULT " + json.dumps(out) + "\\n").encode())          # one write of the whole line: the ranks share the pipe
     dist.barrier(); dist.destroy_process_group()
 ''')
 
@@ -86,7 +93,7 @@ def test_round_robin_batches_keep_n_processed_and_input_order(tmp_path):
            "--master-port", port, str(script), common.ROOT]
     r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, env=env, timeout=300)
     assert r.returncode == 0, r.stdout[-2000:]
-    res = sorted((json.loads(l.split("RESULT ", 1)[1]) for l in r.stdout.splitlines() if "RESULT " in l), key=lambda x: x["rank"])
+    res = _results(r.stdout)
     n, batch = 10007, 1000
     want = "".join(f"read{i}@{(i // batch) * batch}\n" for i in range(n)).encode()
     assert res[0]["sam"] == hashlib.sha256(want).hexdigest() and res[0]["n_lines"] == n and res[1]["sam"] is None
