@@ -93,6 +93,11 @@ class SortDevStats(C.Structure):  # bwahip_sort_dev_t
                 ("sort_ms", C.c_double), ("merge_s", C.c_double), ("dev", DevMergeStats)]
 
 
+class BaiStats(C.Structure):  # bwahip_bai_stats_t
+    _fields_ = [("n_chunks", C.c_int64), ("n_windows", C.c_int64), ("n_no_coor", C.c_int64), ("bai_bytes", C.c_int64), ("hbm_bytes", C.c_int64),
+                ("index_ms", C.c_double)]
+
+
 ERRORS = {0: "ok", -1: "EINVAL", -2: "ENODEV", -3: "ENOMEM", -4: "EIO", -5: "ECAPACITY", -6: "EINTERNAL"}
 
 STAGE_INTV, STAGE_CHAIN, STAGE_CHAIN_FLT, STAGE_REGS, STAGE_REGS_PRE, STAGE_SEEDS = 1, 2, 3, 4, 5, 6
@@ -175,6 +180,23 @@ def lib():
     L.bwahip_batch_bgzf.argtypes = [vp, C.POINTER(vp), i64p, i64p, i64p, i64p]
     L.bwahip_stream_run_bam_dev.argtypes = [C.POINTER(vp), C.c_int, C.POINTER(Opt), C.POINTER(PeStat), C.c_char_p, C.c_char_p, C.c_int, C.c_char_p,
                                             C.POINTER(StreamStats), C.POINTER(BgzfStats)]
+    L.bwahip_bai_builder_open.argtypes = [C.c_int32, C.c_int64, C.POINTER(vp)]
+    L.bwahip_bai_builder_add_records.argtypes = [vp, vp, vp, C.c_int64]
+    L.bwahip_bai_builder_add_members.argtypes = [vp, vp, C.c_int64]
+    L.bwahip_bai_builder_finish.argtypes = [vp, C.c_int]
+    L.bwahip_bai_builder_close.argtypes = [vp]
+    L.bwahip_bai_builder_close.restype = None
+    L.bwahip_bai_check_contigs.argtypes = [C.POINTER(Bns)]
+    L.bwahip_bgzf_write_lens.argtypes = [C.c_int, vp, C.c_int64, C.c_int, C.c_int, vp, C.c_int64, i64p]
+    L.bwahip_bam_merger_finish_bai.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp]
+    L.bwahip_bam_devmerger_finish_bai.argtypes = [vp, C.c_int, C.c_int, C.c_int64, C.c_int32, C.POINTER(DevMergeStats), C.POINTER(BaiStats)]
+    L.bwahip_kat_bai.argtypes = [vp, vp, vp, C.c_int64, vp, C.c_int64, C.c_int64, C.c_int32, vp, C.c_int64, i64p]
+    L.bwahip_bam_devmerge_bai_hbm_need.argtypes = [C.c_int64, C.c_int64, C.c_int64, C.c_int64]
+    L.bwahip_bam_devmerge_bai_hbm_need.restype = C.c_int64
+    L.bwahip_stream_run_bam_sorted_bai.argtypes = [C.POINTER(vp), C.c_int, C.POINTER(Opt), C.POINTER(PeStat), C.c_char_p, C.c_char_p, C.c_int, C.c_char_p, C.c_int,
+                                                   C.POINTER(StreamStats), C.POINTER(SortStats), C.c_int]
+    L.bwahip_stream_run_bam_sorted_dev_bai.argtypes = [C.POINTER(vp), C.c_int, C.POINTER(Opt), C.POINTER(PeStat), C.c_char_p, C.c_char_p, C.c_int, C.c_char_p,
+                                                       C.POINTER(StreamStats), C.POINTER(SortDevStats), C.c_int]
     L.bwahip_kat_radix_sort.argtypes = [vp, C.c_int64, vp, C.c_int, vp, C.POINTER(C.c_int)]
     L.bwahip_fastq_open.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(vp)]
     L.bwahip_fastq_next.argtypes = [vp, C.c_int64, C.c_int, C.POINTER(C.POINTER(Seq)), C.POINTER(C.c_int)]
@@ -322,6 +344,10 @@ class BamMerger:
     def finish(self, fd, level=1, n_threads=1):
         _check(lib().bwahip_bam_merger_finish(self._h, fd, level, n_threads), "bwahip_bam_merger_finish")
 
+    def finish_bai(self, fd, builder, level=1, n_threads=1):
+        """bwahip_bam_merger_finish_bai: finish with a BaiBuilder listening (the caller finishes the builder)."""
+        _check(lib().bwahip_bam_merger_finish_bai(self._h, fd, level, n_threads, builder._h), "bwahip_bam_merger_finish_bai")
+
     def stats(self):
         a, b, c, d = C.c_int64(), C.c_int64(), C.c_int64(), C.c_double()
         _check(lib().bwahip_bam_merger_stats(self._h, C.byref(a), C.byref(b), C.byref(c), C.byref(d)), "bwahip_bam_merger_stats")
@@ -360,6 +386,13 @@ class DevMerger:
         _check(lib().bwahip_bam_devmerger_finish(self._h, fd, C.byref(st)), "bwahip_bam_devmerger_finish")
         return st
 
+    def finish_bai(self, fd=-1, bai_fd=-1, first_member_offset=0, n_ref=0):
+        """bwahip_bam_devmerger_finish_bai: finish, and the BAI index of the sorted records on bai_fd (csrc/k_bai.hip); returns
+        (DevMergeStats, BaiStats)."""
+        st, bs = DevMergeStats(), BaiStats()
+        _check(lib().bwahip_bam_devmerger_finish_bai(self._h, fd, bai_fd, first_member_offset, n_ref, C.byref(st), C.byref(bs)), "bwahip_bam_devmerger_finish_bai")
+        return st, bs
+
     def close(self):
         if self._h:
             lib().bwahip_bam_devmerger_close(self._h)
@@ -375,6 +408,58 @@ class DevMerger:
 def bam_devmerge_hbm_need(raw_bytes, n_records, n_runs, piece_blocks):
     """bwahip_bam_devmerge_hbm_need: the HBM a device merger takes for these runs, finish included (no device)."""
     return lib().bwahip_bam_devmerge_hbm_need(raw_bytes, n_records, n_runs, piece_blocks)
+
+
+def bam_devmerge_bai_hbm_need(n_records, n_blocks, n_ref, n_windows):
+    """bwahip_bam_devmerge_bai_hbm_need: the HBM the index stage takes beside bam_devmerge_hbm_need (no device)."""
+    return lib().bwahip_bam_devmerge_bai_hbm_need(n_records, n_blocks, n_ref, n_windows)
+
+
+class BaiBuilder:
+    """bwahip_bai_builder_*: the BAI index of a coordinate-sorted BAM file from its records and the lengths of its BGZF members, fed
+    in file order in any interleaving; no device."""
+
+    def __init__(self, n_ref, first_member_offset=0):
+        self._h = C.c_void_p()
+        _check(lib().bwahip_bai_builder_open(n_ref, first_member_offset, C.byref(self._h)), "bwahip_bai_builder_open")
+
+    def add_records(self, rec, rec_off):
+        rec = bytes(rec)
+        rec_off = np.ascontiguousarray(rec_off, dtype=np.int64)
+        _check(lib().bwahip_bai_builder_add_records(self._h, rec, rec_off.ctypes.data, len(rec_off) - 1), "bwahip_bai_builder_add_records")
+
+    def add_members(self, member_len):
+        member_len = np.ascontiguousarray(member_len, dtype=np.int32)
+        _check(lib().bwahip_bai_builder_add_members(self._h, member_len.ctypes.data, len(member_len)), "bwahip_bai_builder_add_members")
+
+    def finish(self, bai_fd=-1):
+        _check(lib().bwahip_bai_builder_finish(self._h, bai_fd), "bwahip_bai_builder_finish")
+
+    def close(self):
+        if self._h:
+            lib().bwahip_bai_builder_close(self._h)
+            self._h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+
+def bai_check_contigs(bns):
+    """bwahip_bai_check_contigs: ECAPACITY for a contig table BAI cannot index (a contig above 2^29 bases); no device."""
+    _check(lib().bwahip_bai_check_contigs(C.byref(_bns_of(bns))), "bwahip_bai_check_contigs")
+
+
+def bgzf_write_lens(fd, data, level=1, n_threads=1, cap=None):
+    """bwahip_bgzf_write_lens: bgzf_write that returns the lengths of the members it wrote (int32 array)."""
+    data = bytes(data)
+    cap = (len(data) + 65279) // 65280 if cap is None else cap
+    lens = np.zeros(max(cap, 1), dtype=np.int32)
+    n = C.c_int64()
+    _check(lib().bwahip_bgzf_write_lens(fd, data, len(data), level, n_threads, lens.ctypes.data, cap, C.byref(n)), "bwahip_bgzf_write_lens")
+    return lens[:n.value].copy()
 
 
 def bgzf_write(fd, data, level=1, n_threads=1, eof=False):
@@ -703,6 +788,23 @@ class Context:
         _check(lib().bwahip_kat_bgzf(self._h, src.ctypes.data, len(data), out.ctypes.data, cap if data else 0, C.byref(ln), C.byref(nb), C.byref(ns)), "bwahip_kat_bgzf")
         return out[:ln.value].tobytes(), nb.value, ns.value
 
+    def kat_bai(self, rec, rec_off, member_len, first_member_offset, n_ref):
+        """The index stage of the device merger (csrc/k_bai.hip) on these records (file order) and member lengths: the .bai bytes."""
+        rec = bytes(rec)
+        rec_off = np.ascontiguousarray(rec_off, dtype=np.int64)
+        member_len = np.ascontiguousarray(member_len, dtype=np.int32)
+        src = np.frombuffer(rec, dtype=np.uint8) if rec else np.zeros(1, dtype=np.uint8)
+        ln = C.c_int64()
+        out = np.empty(1 << 20, dtype=np.uint8)
+        for _ in range(2):
+            rc = lib().bwahip_kat_bai(self._h, src.ctypes.data, rec_off.ctypes.data, len(rec_off) - 1, member_len.ctypes.data, len(member_len), first_member_offset, n_ref,
+                                      out.ctypes.data, len(out), C.byref(ln))
+            if rc != -5 or ln.value <= len(out):
+                break
+            out = np.empty(ln.value, dtype=np.uint8)                # the first answer said how much it takes
+        _check(rc, "bwahip_kat_bai")
+        return out[:ln.value].tobytes()
+
     def kat_radix_sort(self, keys, key_bits=64):
         """(permutation, tile): the product's stable radix sort on these uint64 keys; tile = items one workgroup ranks per pass."""
         keys = np.ascontiguousarray(keys, dtype=np.uint64)
@@ -936,6 +1038,38 @@ def stream_run_bam_sorted_dev(ctxs, fq1, fq2=None, out_fd=-1, hdr_line=None, opt
         hdr_line = hdr_line.encode()
     _check(lib().bwahip_stream_run_bam_sorted_dev(arr, len(ctxs), C.byref(opt), C.byref(pes0) if pes0 is not None else None, os.fsencode(fq1),
                                                   os.fsencode(fq2) if fq2 else None, out_fd, hdr_line, C.byref(st), C.byref(sd)), "bwahip_stream_run_bam_sorted_dev")
+    return st, sd
+
+
+def stream_run_bam_sorted_bai(ctxs, fq1, fq2=None, out_fd=-1, bai_fd=-1, hdr_line=None, level=1, opt=None, chunk_bases=0, max_reads=0, keep_comments=False,
+                              reader_threads=0, pes0=None, tmp_dir=None, mem_budget=1 << 30):
+    """bwahip_stream_run_bam_sorted_bai: stream_run_bam_sorted with the BAI index of the file on bai_fd.  Returns (StreamStats, SortStats)."""
+    opt = opt or default_opt()
+    st, so = StreamStats(), SortStats()
+    st.chunk_bases, st.max_reads, st.keep_comments, st.reader_threads = chunk_bases, max_reads, int(keep_comments), reader_threads
+    so.tmp_dir, so.mem_budget = os.fsencode(tmp_dir) if tmp_dir is not None else None, mem_budget
+    arr = (C.c_void_p * len(ctxs))(*[c._h for c in ctxs])
+    if isinstance(hdr_line, str):
+        hdr_line = hdr_line.encode()
+    _check(lib().bwahip_stream_run_bam_sorted_bai(arr, len(ctxs), C.byref(opt), C.byref(pes0) if pes0 is not None else None, os.fsencode(fq1),
+                                                  os.fsencode(fq2) if fq2 else None, out_fd, hdr_line, level, C.byref(st), C.byref(so), bai_fd), "bwahip_stream_run_bam_sorted_bai")
+    return st, so
+
+
+def stream_run_bam_sorted_dev_bai(ctxs, fq1, fq2=None, out_fd=-1, bai_fd=-1, hdr_line=None, opt=None, chunk_bases=0, max_reads=0, keep_comments=False,
+                                  reader_threads=0, pes0=None, hbm_budget=0, piece_blocks=0, tmp_dir=None, mem_budget=1 << 30, level=1):
+    """bwahip_stream_run_bam_sorted_dev_bai: stream_run_bam_sorted_dev with the BAI index of the file on bai_fd, built on the device (after
+    a fall-back: by the host builder).  Returns (StreamStats, SortDevStats)."""
+    opt = opt or default_opt()
+    st, sd = StreamStats(), SortDevStats()
+    st.chunk_bases, st.max_reads, st.keep_comments, st.reader_threads = chunk_bases, max_reads, int(keep_comments), reader_threads
+    sd.tmp_dir, sd.mem_budget, sd.level = os.fsencode(tmp_dir) if tmp_dir is not None else None, mem_budget, level
+    sd.hbm_budget, sd.piece_blocks = hbm_budget, piece_blocks
+    arr = (C.c_void_p * len(ctxs))(*[c._h for c in ctxs])
+    if isinstance(hdr_line, str):
+        hdr_line = hdr_line.encode()
+    _check(lib().bwahip_stream_run_bam_sorted_dev_bai(arr, len(ctxs), C.byref(opt), C.byref(pes0) if pes0 is not None else None, os.fsencode(fq1),
+                                                      os.fsencode(fq2) if fq2 else None, out_fd, hdr_line, C.byref(st), C.byref(sd), bai_fd), "bwahip_stream_run_bam_sorted_dev_bai")
     return st, sd
 
 

@@ -139,7 +139,8 @@ int write_all(int fd, const uint8_t *p, int64_t len)
 // data -> BGZF blocks on fd (< 0: compressed and dropped).  The blocks are dealt to n_threads workers in contiguous runs, each run
 // deflated into its own part of one buffer and the parts written in order: the file does not depend on n_threads.  Pieces of at
 // most 256 MiB, so the buffer stays bounded.  level 0: stored, 1..9: zlib's levels.
-extern "C" int bwahip_bgzf_write(int fd, const void *data, int64_t len, int level, int n_threads)
+// lens (may be NULL): receives the length of every member, in file order
+static int bgzf_write_impl(int fd, const void *data, int64_t len, int level, int n_threads, int32_t *lens)
 {
 	if (len < 0 || (len && !data) || level < 0 || level > 9) return BWAHIP_EINVAL;
 	if (n_threads < 1) n_threads = 1;
@@ -170,7 +171,9 @@ extern "C" int bwahip_bgzf_write(int fd, const void *data, int64_t len, int leve
 			uint8_t *o = blocks + nb * t / T * BGZF_SLOT;
 			for (int64_t b = nb * t / T; b < nb * (t + 1) / T; ++b) {
 				const int64_t n = plen - b * BGZF_IN < BGZF_IN ? plen - b * BGZF_IN : BGZF_IN;
-				o += bgzf_block(&zs, in + b * BGZF_IN, (int)n, level, o);
+				const int64_t m = bgzf_block(&zs, in + b * BGZF_IN, (int)n, level, o);
+				if (lens) lens[p0 / BGZF_IN + b] = (int32_t)m;
+				o += m;
 			}
 			part_len[(size_t)t] = o - (blocks + nb * t / T * BGZF_SLOT);
 			if (level > 0) deflateEnd(&zs);
@@ -181,6 +184,21 @@ extern "C" int bwahip_bgzf_write(int fd, const void *data, int64_t len, int leve
 		if (fd >= 0) for (int t = 0; t < T; ++t) { const int rc = write_all(fd, blocks + nb * t / T * BGZF_SLOT, part_len[(size_t)t]); if (rc) return rc; }
 	}
 	return 0;
+}
+
+extern "C" int bwahip_bgzf_write(int fd, const void *data, int64_t len, int level, int n_threads) { return bgzf_write_impl(fd, data, len, level, n_threads, nullptr); }
+
+// bwahip_bgzf_write that also says how long every member is (member_len: room for cap lengths; fewer than the (len + 65279) / 65280
+// members there will be: BWAHIP_ECAPACITY, before anything is written)
+extern "C" int bwahip_bgzf_write_lens(int fd, const void *data, int64_t len, int level, int n_threads, int32_t *member_len, int64_t cap, int64_t *n_members)
+{
+	if (len < 0 || !n_members || cap < 0 || (cap && !member_len)) return BWAHIP_EINVAL;
+	const int64_t nb = (len + BGZF_IN - 1) / BGZF_IN;
+	if (nb > cap) return BWAHIP_ECAPACITY;
+	*n_members = 0;
+	const int rc = bgzf_write_impl(fd, data, len, level, n_threads, nb ? member_len : nullptr);
+	if (!rc) *n_members = nb;
+	return rc;
 }
 
 // the end-of-file marker of the specification: an empty block

@@ -3,6 +3,7 @@
 // and handed over with its keys and record offsets, so that nothing here ever parses a record.
 #include "../../include/bwahip.h"
 #include "bam_sort_key.h"
+#include "bai_tables.h"                                         // MergeHooks: the index builder listens to the merge (bai_host.cpp)
 #include <errno.h>
 #include <fcntl.h>
 #include <stdio.h>
@@ -247,7 +248,8 @@ extern "C" int bwahip_bam_merger_add(bwahip_bam_merger *m, int64_t run_no, const
 	return 0;
 }
 
-extern "C" int bwahip_bam_merger_finish(bwahip_bam_merger *m, int fd, int level, int n_threads)
+// bai (may be NULL): who is told every record as it is emitted and the lengths of a piece's members as the piece leaves the writer
+int bam_merger_finish_hooks(bwahip_bam_merger *m, int fd, int level, int n_threads, const MergeHooks *bai)
 {
 	if (!m || level < 0 || level > 9) return BWAHIP_EINVAL;
 	std::lock_guard<std::mutex> lk(m->mu);
@@ -277,25 +279,35 @@ extern "C" int bwahip_bam_merger_finish(bwahip_bam_merger *m, int fd, int level,
 	std::vector<uint8_t> piece;
 	if (!heap.empty()) piece.resize((size_t)PIECE);
 	int64_t fill = 0;
+	std::vector<int32_t> lens(bai ? (size_t)(PIECE / 65280) : 0);
+	auto flush = [&]() -> int {
+		if (!bai) return bwahip_bgzf_write(fd, piece.data(), fill, level, n_threads);
+		int64_t n_mem = 0;
+		const int r = bwahip_bgzf_write_lens(fd, piece.data(), fill, level, n_threads, lens.data(), (int64_t)lens.size(), &n_mem);
+		return r ? r : bai->members(bai->arg, lens.data(), n_mem);
+	};
 	while (!heap.empty()) {
 		Cursor *c = heap[0];
 		const uint8_t *p; int64_t n;
 		if ((rc = c->record(&p, &n))) return rc;
+		if (bai && (rc = bai->record(bai->arg, p, n))) return rc;
 		while (n > 0) {                                           // a record may straddle two pieces: the BGZF stream is one sequence of bytes
 			const int64_t take = n < PIECE - fill ? n : PIECE - fill;
 			memcpy(piece.data() + fill, p, (size_t)take);
 			fill += take; p += take; n -= take;
-			if (fill == PIECE) { if ((rc = bwahip_bgzf_write(fd, piece.data(), fill, level, n_threads))) return rc; fill = 0; }
+			if (fill == PIECE) { if ((rc = flush())) return rc; fill = 0; }
 		}
 		bool more;
 		if ((rc = c->advance(&more))) return rc;
 		if (!more) { heap[0] = heap.back(); heap.pop_back(); }
 		if (!heap.empty()) sift_down(0);
 	}
-	if (fill && (rc = bwahip_bgzf_write(fd, piece.data(), fill, level, n_threads))) return rc;
+	if (fill && (rc = flush())) return rc;
 	m->merge_s = now_s() - t0;
 	return 0;
 }
+
+extern "C" int bwahip_bam_merger_finish(bwahip_bam_merger *m, int fd, int level, int n_threads) { return bam_merger_finish_hooks(m, fd, level, n_threads, nullptr); }
 
 extern "C" int bwahip_bam_merger_stats(bwahip_bam_merger *m, int64_t *n_records, int64_t *n_runs, int64_t *spilled_bytes, double *merge_s)
 {

@@ -214,6 +214,15 @@ int  bam_devmerger_adopt(bwahip_bam_devmerger *m, int64_t run_no, DevRun *r);
 int  bam_devmerger_add_dev(bwahip_bam_devmerger *m, int64_t run_no, const uint8_t *d_rec, int64_t len, const uint64_t *d_keys, const int64_t *d_rec_off, int64_t n_rec, hipStream_t st);
 // the merger's runs in run-number order, handed to the caller (who frees them); the merger is empty afterwards
 int  bam_devmerger_take_runs(bwahip_bam_devmerger *m, std::vector<std::pair<int64_t, DevRun*>> *out);
+// k_bai.hip: the index stage of a device merger's finish.  bai_stage_members: room for the lengths of n_blocks members (the caller fills
+// them, on c->stream); bai_stage_run: the index of the n records addr[idx[i]] (sorted order; out_off: their n + 1 offsets in the stream of
+// `total` bytes) as the bytes of a .bai file -- queued on c->stream and awaited; the context's sort buffers (bs.keys / bs.idx) are reused
+struct BaiStage;
+BaiStage *bai_stage_new();
+void bai_stage_free(BaiStage *s);
+int  bai_stage_members(BaiStage *s, int64_t n_blocks, int **mlen);
+int  bai_stage_run(BaiStage *s, bwahip_ctx *c, int n, const uint8_t *const *addr, const unsigned *idx, const int64_t *out_off, int64_t total, int64_t n_blocks, int64_t base,
+                   int32_t n_ref, std::vector<uint8_t> *bytes, bwahip_bai_stats_t *bs);
 int bam_check_reads(int n, const bwahip_seq_t *seqs);   // bam_host.cpp: BWAHIP_EINVAL (with a message naming the read) for a name or a comment BAM cannot hold
 void pipe_destroy(bwahip_ctx *c);                                                     // final_rt.hip: the stream driver's buffer sets
 int final_setup(bwahip_ctx *c);                                                       // contig name tables for the SAM kernels

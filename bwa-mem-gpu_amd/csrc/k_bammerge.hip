@@ -19,6 +19,7 @@
 // Two piece inputs and two piece outputs: the gather and the deflate of piece k are queued on the context's stream while the 16-byte
 // total and then the members of piece k - 1 come back on the copy stream and are written.  No kernel here uses LDS or atomics.
 #include "ctx_internal.h"
+#include "bai_tables.h"
 #include <errno.h>
 #include <unistd.h>
 #include <chrono>
@@ -165,7 +166,20 @@ struct bwahip_bam_devmerger {
 	std::map<int64_t, DevRun*> runs;                               // by run_no: the order of the concatenation
 	int64_t n_records = 0, raw_bytes = 0;
 	Work w;
+	BaiStage *bai = nullptr;                                       // the index stage's buffers (k_bai.hip), made by the first finish_bai
 };
+
+namespace {
+struct BaiArgs { int bai_fd; int64_t base; int32_t n_ref; bwahip_bai_stats_t *bs; };
+// the index of what finish wrote: after the last piece, on the context's stream
+int finish_index(bwahip_bam_devmerger *m, const BaiArgs &a, int n, const unsigned *idx, int64_t total)
+{
+	std::vector<uint8_t> bytes;
+	int rc = bai_stage_run(m->bai, m->c, n, m->w.addr.as<const uint8_t*>(), idx, m->w.out_off.as<int64_t>(), total, bgzf_blocks(total), a.base, a.n_ref, &bytes, a.bs);
+	if (!rc) rc = bai_write_fd(a.bai_fd, bytes);
+	return rc;
+}
+} // namespace
 
 int bam_devrun_make(bwahip_ctx *c, const uint8_t *d_rec, int64_t len, const uint64_t *d_keys, const int64_t *d_rec_off, int64_t n_rec, hipStream_t st, DevRun **out)
 {
@@ -285,10 +299,12 @@ extern "C" int bwahip_bam_devmerger_add(bwahip_bam_devmerger *m, int64_t run_no,
 	return rc;
 }
 
-extern "C" int bwahip_bam_devmerger_finish(bwahip_bam_devmerger *m, int fd, bwahip_devmerge_stats_t *st)
+// bai (may be NULL): the index stage after the last piece (bwahip_bam_devmerger_finish_bai); the members do not depend on it
+static int devmerger_finish(bwahip_bam_devmerger *m, int fd, bwahip_devmerge_stats_t *st, const BaiArgs *bai)
 {
 	if (!m) return BWAHIP_EINVAL;
 	std::lock_guard<std::mutex> lk(m->mu);
+	if (bai && !m->bai) m->bai = bai_stage_new();
 	bwahip_ctx *c = m->c;
 	Work &w = m->w;
 	const double t0 = now_s();
@@ -300,7 +316,11 @@ extern "C" int bwahip_bam_devmerger_finish(bwahip_bam_devmerger *m, int fd, bwah
 	if (st) *st = s;
 	const int n = (int)m->n_records;
 	const int64_t total = m->raw_bytes;
-	if (n == 0 || total == 0) { s.finish_s = now_s() - t0; if (st) *st = s; return 0; }   // nothing to write: no member
+	if (n == 0 || total == 0) {                                    // nothing to write: no member
+		const int r = bai ? (n ? BWAHIP_EINVAL : finish_index(m, *bai, 0, nullptr, 0)) : 0;
+		s.finish_s = now_s() - t0; if (st) *st = s;
+		return r;
+	}
 	HIP_TRY(hipSetDevice(c->device));
 	int rc;
 	if ((rc = w.make_events())) return rc;
@@ -364,6 +384,8 @@ extern "C" int bwahip_bam_devmerger_finish(bwahip_bam_devmerger *m, int fd, bwah
 		if ((rc = w.in[k].ensure((size_t)in_cap)) || (rc = w.out[k].ensure((size_t)out_cap)) || (rc = w.tot[k].ensure(16)) || (rc = w.h_out[k].ensure((size_t)out_cap))) return rc;
 	if ((rc = w.h_tot.ensure(32))) return rc;
 	int64_t *h_tot = (int64_t*)w.h_tot.p;
+	int *mlen_all = nullptr;                                       // the whole stream's member lengths, for the index
+	if (bai && (rc = bai_stage_members(m->bai, s.n_blocks, &mlen_all))) return rc;
 
 	// ---- gather and deflate piece k, download and write piece k - 1
 	auto piece_len = [&](int p) { const int64_t lo = (int64_t)p * piece_bytes; return total - lo < piece_bytes ? total - lo : piece_bytes; };
@@ -382,6 +404,8 @@ extern "C" int bwahip_bam_devmerger_finish(bwahip_bam_devmerger *m, int fd, bwah
 			HIP_TRY(hipEventRecord(w.ev_deflate[b], c->stream));
 			if ((rc = bgzf_deflate(c, w.in[b].as<uint8_t>(), hi - lo, w.out[b], w.tot[b].as<int64_t>(), c->stream))) return rc;
 			HIP_TRY(hipEventRecord(w.ev_done[b], c->stream));
+			if (bai)                                                    // the piece's member lengths, before the next piece reuses the deflate stage's buffers: same stream
+				HIP_TRY(hipMemcpyAsync(mlen_all + (int64_t)k * m->piece_blocks, c->bz.mlen.p, (size_t)bgzf_blocks(hi - lo) * 4, hipMemcpyDeviceToDevice, c->stream));
 		}
 		if (k >= 1) {
 			const int b = (k - 1) & 1;
@@ -404,9 +428,20 @@ extern "C" int bwahip_bam_devmerger_finish(bwahip_bam_devmerger *m, int fd, bwah
 	{ float ms = 0; if (hipEventElapsedTime(&ms, w.ev_sort[0], w.ev_sort[1]) == hipSuccess) s.sort_ms = ms; }
 	s.hbm_bytes += (int64_t)(w.bytes() + bs.keys[0].cap + bs.keys[1].cap + bs.idx[0].cap + bs.idx[1].cap + bs.hist.cap + bs.hist_base.cap +
 	                         c->bz.slots.cap + c->bz.mlen.cap + c->bz.moff.cap + c->bz.md.cap + c->bz.cnt.cap);
+	rc = bai ? finish_index(m, *bai, n, idx, total) : 0;
 	s.finish_s = now_s() - t0;
 	if (st) *st = s;
-	return 0;
+	return rc;
+}
+
+extern "C" int bwahip_bam_devmerger_finish(bwahip_bam_devmerger *m, int fd, bwahip_devmerge_stats_t *st) { return devmerger_finish(m, fd, st, nullptr); }
+
+extern "C" int bwahip_bam_devmerger_finish_bai(bwahip_bam_devmerger *m, int fd, int bai_fd, int64_t first_member_offset, int32_t n_ref, bwahip_devmerge_stats_t *st, bwahip_bai_stats_t *bs)
+{
+	if (n_ref < 0 || first_member_offset < 0 || first_member_offset >= (1ll << 48)) return BWAHIP_EINVAL;
+	if (bs) memset(bs, 0, sizeof *bs);
+	const BaiArgs a = { bai_fd, first_member_offset, n_ref, bs };
+	return devmerger_finish(m, fd, st, &a);
 }
 
 extern "C" void bwahip_bam_devmerger_close(bwahip_bam_devmerger *m)
@@ -416,5 +451,6 @@ extern "C" void bwahip_bam_devmerger_close(bwahip_bam_devmerger *m)
 	for (hipStream_t q : { m->c->stream_copy, m->c->stream }) if (q) (void)hipStreamSynchronize(q);   // after a failed finish work may still be queued on the buffers
 	for (auto &kv : m->runs) bam_devrun_free(kv.second);
 	m->w.release();
+	bai_stage_free(m->bai);
 	delete m;
 }

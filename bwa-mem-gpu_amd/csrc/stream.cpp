@@ -103,6 +103,7 @@ struct SortedSink : Sink {
 	const char *hdr_line, *tmp_dir; int64_t mem_budget; int level;
 	int64_t *n_records, *n_runs, *spilled_bytes; double *sort_ms_out, *merge_s;
 	uint8_t *hdr = nullptr; int64_t hlen = 0; bwahip_bam_merger *m = nullptr; double sort_ms = 0;
+	bool with_bai = false; int bai_fd = -1; int32_t n_ref = 0;   // the BAI index beside the file (bwahip_stream_run_bam_sorted_bai): a builder listens to the merge
 	template <class S> SortedSink(const char *h, int lv, S *so) : hdr_line(h), tmp_dir(so->tmp_dir), mem_budget(so->mem_budget), level(lv),
 		n_records(&so->n_records), n_runs(&so->n_runs), spilled_bytes(&so->spilled_bytes), sort_ms_out(&so->sort_ms), merge_s(&so->merge_s) { form = OutForm::BamSorted; host_deflates = true; }
 	~SortedSink() { free(hdr); bwahip_bam_merger_close(m); }    // the merger and its files go whatever happens
@@ -110,19 +111,37 @@ struct SortedSink : Sink {
 	{
 		if (level < 0 || level > 9) return BWAHIP_EINVAL;
 		*n_records = *n_runs = *spilled_bytes = 0; *sort_ms_out = *merge_s = 0;
+		if (with_bai) { const int r = bwahip_bai_check_contigs(bwahip_bns(c0)); if (r) return r; n_ref = bwahip_bns(c0)->n_seqs; }   // a contig BAI cannot hold: before anything starts
 		return bwahip_bam_header_sorted(bwahip_bns(c0), hdr_line, &hdr, &hlen);
+	}
+	// the header's members; with the index their bytes are counted: the offset of the first member of the records
+	int write_header(int lv, int64_t *first_member_offset)
+	{
+		if (!with_bai) return bwahip_bgzf_write(fd, hdr, hlen, lv, 1);
+		std::vector<int32_t> lens((size_t)((hlen + 65279) / 65280));
+		int64_t n_mem = 0;
+		const int r = bwahip_bgzf_write_lens(fd, hdr, hlen, lv, 1, lens.data(), (int64_t)lens.size(), &n_mem);
+		*first_member_offset = 0;
+		for (int64_t k = 0; k < n_mem; ++k) *first_member_offset += lens[(size_t)k];
+		return r;
 	}
 	int open(bwahip_ctx *const *ctxs, int) override { const int r = prepare(ctxs[0]); return r ? r : bwahip_bam_merger_open(tmp_dir, mem_budget, &m); }
 	int stage_out(bwahip_ctx *c, int out, Item &it, double *t_end) override { const int r = Sink::stage_out(c, out, it, t_end); return r ? r : pipe_stage_out_sorted(c, out, &it.keys, &it.rec_off, &it.n_rec, &it.gpu_ms); }
 	int write(int64_t seq_no, Item &it) override { sort_ms += it.gpu_ms; return bwahip_bam_merger_add(m, seq_no, (const uint8_t*)it.p, it.len, it.keys, it.rec_off, it.n_rec); }
 	int finish() override
 	{
-		int r = bwahip_bgzf_write(fd, hdr, hlen, level, 1);
+		int64_t base = 0;
+		int r = write_header(level, &base);
+		bwahip_bai_builder *bb = nullptr;
+		if (!r && with_bai) r = bwahip_bai_builder_open(n_ref, base, &bb);
 		// the staging threads have ended, so the merge's BGZF writer gets all host threads (the bytes do not depend on the number of threads)
-		if (!r) r = bwahip_bam_merger_finish(m, fd, level, n_threads > 1 ? n_threads : 1);
+		if (!r) r = bb ? bwahip_bam_merger_finish_bai(m, fd, level, n_threads > 1 ? n_threads : 1, bb) : bwahip_bam_merger_finish(m, fd, level, n_threads > 1 ? n_threads : 1);
 		bwahip_bam_merger_stats(m, n_records, n_runs, spilled_bytes, merge_s);
 		*sort_ms_out = sort_ms;
-		return r ? r : bwahip_bgzf_eof(fd);
+		if (!r) r = bwahip_bgzf_eof(fd);
+		if (!r && bb) r = bwahip_bai_builder_finish(bb, bai_fd);    // the index last: nothing of it is written unless the file is whole
+		bwahip_bai_builder_close(bb);
+		return r;
 	}
 };
 
@@ -134,6 +153,7 @@ struct DevSortedSink : Sink {
 	bwahip_sort_dev_t *sd; SortedSink host;
 	bwahip_bam_devmerger *dm = nullptr; bwahip_ctx *ctx0 = nullptr;
 	int64_t hbm_budget = 0, held_raw = 0, held_rec = 0; int piece_blocks = 0;
+	int64_t bai_windows = 0;                                     // with the index: the 16 Kbp windows of the contig table, for the stage's share of the budget
 	std::atomic<bool> fell_back{false};                          // read by the drainers: from now on they download
 	hipStream_t fb_stream = nullptr; HostBuf fb_rec, fb_keys, fb_off;   // the fall-back's downloads: their stream, one pinned buffer each for records, keys and offsets
 	DevSortedSink(const char *h, bwahip_sort_dev_t *s) : sd(s), host(h, s->level, s) { form = OutForm::BamSorted; }
@@ -151,6 +171,7 @@ struct DevSortedSink : Sink {
 		int r = host.prepare(ctxs[0]);                              // the host merger itself is opened only at a fall-back: tmp_dir is not looked at before
 		if (r) return r;
 		sd->fell_back = 0; sd->fell_back_at_run = 0; memset(&sd->dev, 0, sizeof sd->dev);
+		if (host.with_bai) { const bwahip_bns_t *bns = bwahip_bns(ctxs[0]); for (int32_t i = 0; i < bns->n_seqs; ++i) bai_windows += ((int64_t)bns->anns[i].len + 16383) >> 14; }
 		if ((r = bwahip_bam_devmerger_open(ctxs[0], sd->piece_blocks, &dm))) return r;
 		ctx0 = ctxs[0]; hbm_budget = sd->hbm_budget;
 		piece_blocks = sd->piece_blocks > 0 ? sd->piece_blocks : ctx0->knobs.sorted_piece_blocks;
@@ -196,7 +217,9 @@ struct DevSortedSink : Sink {
 	{
 		int r = 0;
 		if (!fell_back) {                                           // in input order, so the decision depends on the input and the budget alone
-			const bool fits = it.run && bwahip_bam_devmerge_hbm_need(held_raw + it.raw_len, held_rec + it.n_rec, seq_no + 1, piece_blocks) <= hbm_budget;
+			int64_t need = bwahip_bam_devmerge_hbm_need(held_raw + it.raw_len, held_rec + it.n_rec, seq_no + 1, piece_blocks);
+			if (host.with_bai) need += bwahip_bam_devmerge_bai_hbm_need(held_rec + it.n_rec, bgzf_blocks(held_raw + it.raw_len), host.n_ref, bai_windows);
+			const bool fits = it.run && need <= hbm_budget;
 			if (!fits) r = fall_back(seq_no);
 		}
 		if (!r && !fell_back) { if (!(r = bam_devmerger_adopt(dm, seq_no, it.run))) { it.run = nullptr; held_raw += it.raw_len; held_rec += it.n_rec; host.sort_ms += it.gpu_ms; } }
@@ -209,8 +232,9 @@ struct DevSortedSink : Sink {
 	int finish() override
 	{
 		if (fell_back) return host.finish();                        // from here on this is the host-merged run at sd->level
-		int r = bwahip_bgzf_write(fd, host.hdr, host.hlen, 1, 1);
-		if (!r) r = bwahip_bam_devmerger_finish(dm, fd, &sd->dev);
+		int64_t base = 0;
+		int r = host.write_header(1, &base);
+		if (!r) r = host.with_bai ? bwahip_bam_devmerger_finish_bai(dm, fd, host.bai_fd, base, host.n_ref, &sd->dev, nullptr) : bwahip_bam_devmerger_finish(dm, fd, &sd->dev);
 		if (!r) { sd->n_records = sd->dev.n_records; sd->n_runs = sd->dev.n_runs; sd->merge_s = sd->dev.finish_s; }
 		sd->sort_ms = host.sort_ms;
 		return r ? r : bwahip_bgzf_eof(fd);
@@ -487,5 +511,25 @@ extern "C" int bwahip_stream_run_bam_sorted_dev(bwahip_ctx *const *ctxs, int n_c
 {
 	if (!sd) return BWAHIP_EINVAL;
 	DevSortedSink sink(hdr_line, sd);
+	return stream_run(ctxs, n_ctx, opt, pes0, fq1, fq2, out_fd, st, sink);
+}
+
+// The two coordinate-sorted entry points with the BAI index of the file on bai_fd: the same sinks, which then count the header's member
+// bytes and let a builder listen to the host merge, or run the device merger's index stage (k_bai.hip)
+extern "C" int bwahip_stream_run_bam_sorted_bai(bwahip_ctx *const *ctxs, int n_ctx, const bwahip_opt_t *opt, const bwahip_pestat_t *pes0,
+                                                const char *fq1, const char *fq2, int out_fd, const char *hdr_line, int level, bwahip_stream_t *st, bwahip_sort_t *so, int bai_fd)
+{
+	if (!so) return BWAHIP_EINVAL;
+	SortedSink sink(hdr_line, level, so);
+	sink.with_bai = true; sink.bai_fd = bai_fd;
+	return stream_run(ctxs, n_ctx, opt, pes0, fq1, fq2, out_fd, st, sink);
+}
+
+extern "C" int bwahip_stream_run_bam_sorted_dev_bai(bwahip_ctx *const *ctxs, int n_ctx, const bwahip_opt_t *opt, const bwahip_pestat_t *pes0,
+                                                    const char *fq1, const char *fq2, int out_fd, const char *hdr_line, bwahip_stream_t *st, bwahip_sort_dev_t *sd, int bai_fd)
+{
+	if (!sd) return BWAHIP_EINVAL;
+	DevSortedSink sink(hdr_line, sd);
+	sink.host.with_bai = true; sink.host.bai_fd = bai_fd;
 	return stream_run(ctxs, n_ctx, opt, pes0, fq1, fq2, out_fd, st, sink);
 }

@@ -423,6 +423,73 @@ typedef struct {
 int bwahip_stream_run_bam_sorted_dev(bwahip_ctx *const *ctxs, int n_ctx, const bwahip_opt_t *opt, const bwahip_pestat_t *pes0, const char *fq1, const char *fq2,
                                      int out_fd, const char *hdr_line, bwahip_stream_t *st, bwahip_sort_dev_t *sd);
 
+/* ---- the BAI index beside a coordinate-sorted file (SAM specification 5.2; csrc/bai_host.cpp, csrc/k_bai.hip) ----
+ * The canonical form every path here writes, byte for byte.  Virtual offsets: the record stream is cut every 65 280 bytes into members
+ * 0 .. B - 1 at file offsets c[b]; V(u) = c[u / 65280] << 16 | u % 65280, and V(total) = c[B] << 16, where the end-of-file block goes;
+ * record i spans [V(u_i), V(u_i+1)).  Per record, read from its bytes: rlen = the lengths of its M D N = X operations, e = pos + rlen
+ * when rlen > 0 and 0x4 is clear, else pos + 1; bin = reg2bin(pos, e), never the record's own field.  refID < 0: counted in n_no_coor
+ * only.  A chunk is a maximal run of consecutive records of one (refID, bin); within a bin chunks are in file order and a chunk that
+ * begins in the member in which its predecessor ends is joined to it; bins ascending, then pseudo-bin 37450 (first begin / last end,
+ * records with 0x4 clear / set); a reference without records: n_bin = 0, n_intv = 0.  Linear index: n_intv = 1 + the largest
+ * (e - 1) >> 14, a window holds the smallest begin over the records that overlap it, an empty one the value of the next to its right.
+ * Sparse bins are not moved into their parents, and there is no CSI form.  Any reader that follows the specification can use the index;
+ * that its bytes are those of another writer is not claimed.
+ * Refused, before a byte of the index is written, with the code of the first offending record in file order: BWAHIP_EINVAL for a record
+ * shorter than 36 bytes, whose block_size + 4 is not its length, whose name and CIGAR (36 + l_read_name + 4 x n_cigar_op) exceed it, with
+ * refID >= n_ref or refID >= 0 and pos < 0, or that comes before its predecessor (refID as unsigned, then pos); BWAHIP_ECAPACITY for
+ * e > 2^29.  No byte outside a record is read to find that out.
+ *
+ * Device-free builder.  open: n_ref references, the file offset of the first member of the records.  add_records: whole records in file
+ * order, record i is rec[rec_off[i] .. rec_off[i+1]); add_members: the lengths of the next members in file order (1 .. 65 536 each).
+ * The two may be called in any interleaving; what is held is proportional to the chunks, the windows and the records whose members
+ * are not known yet, not to the records.  finish: members that are not exactly those of the records' bytes: BWAHIP_EINVAL; the index on
+ * bai_fd (< 0: built and dropped).  After a refusal every later call returns the same code. */
+typedef struct bwahip_bai_builder bwahip_bai_builder;
+int  bwahip_bai_builder_open(int32_t n_ref, int64_t first_member_offset, bwahip_bai_builder **b);
+int  bwahip_bai_builder_add_records(bwahip_bai_builder *b, const uint8_t *rec, const int64_t *rec_off, int64_t n_rec);
+int  bwahip_bai_builder_add_members(bwahip_bai_builder *b, const int32_t *member_len, int64_t n);
+int  bwahip_bai_builder_finish(bwahip_bai_builder *b, int bai_fd);
+void bwahip_bai_builder_close(bwahip_bai_builder *b);
+/* BWAHIP_ECAPACITY for a contig table with a contig longer than 2^29 bases: BAI cannot index it (no device is touched) */
+int  bwahip_bai_check_contigs(const bwahip_bns_t *bns);
+/* bwahip_bgzf_write that also returns the length of every member it wrote, in file order (the same bytes on fd).  member_len has room
+ * for cap lengths: fewer than the (len + 65 279) / 65 280 members: BWAHIP_ECAPACITY, nothing is written. */
+int  bwahip_bgzf_write_lens(int fd, const void *data, int64_t len, int level, int n_threads, int32_t *member_len, int64_t cap, int64_t *n_members);
+/* bwahip_bam_merger_finish with the index: the builder is fed every record as it is emitted and the lengths of the members as each
+ * piece leaves the writer; the bytes on fd are bwahip_bam_merger_finish's.  The caller opens, finishes and closes the builder. */
+int  bwahip_bam_merger_finish_bai(bwahip_bam_merger *m, int fd, int level, int n_threads, bwahip_bai_builder *builder);
+
+/* The index stage on the device (csrc/k_bai.hip).  bwahip_bam_devmerger_finish_bai: bwahip_bam_devmerger_finish (the same members on
+ * fd) and, after the last piece, the index of the sorted records on bai_fd (< 0: built and dropped): the records are parsed where the
+ * runs lie, the members' lengths were kept as each piece was deflated; what travels to the host is the compact tables.  n_ref and
+ * first_member_offset as for the builder.  A refusal (above) comes after the members were written and before any byte of the index.
+ * *bs (may be NULL): chunks and linear-index windows written, records without a reference, bytes of the index, HBM the stage held
+ * beside the merger's, GPU time of the stage.
+ * bwahip_kat_bai: exactly that stage on the caller's records (host pointers; record i = rec[rec_off[i] .. rec_off[i+1]), in file
+ * order) and the caller's member lengths, no deflate; the index into out (out_cap too small: BWAHIP_ECAPACITY, *out_len says what it
+ * takes); n_members other than the (bytes + 65 279) / 65 280 of the records: BWAHIP_EINVAL.
+ * bwahip_bam_devmerge_bai_hbm_need: the HBM the stage takes beside bwahip_bam_devmerge_hbm_need, with the eighth of slack its buffers
+ * grow with: 29 bytes per record and, for at most as many chunks, 52 each; 12 per member; 56 per reference (first and last record,
+ * window and 0x4 counts, the linear index's offset, 32 of metadata); 16 per window of the linear index (no device is touched; an
+ * argument < 0: -1). */
+typedef struct { int64_t n_chunks, n_windows, n_no_coor, bai_bytes, hbm_bytes; double index_ms; } bwahip_bai_stats_t;
+int  bwahip_bam_devmerger_finish_bai(bwahip_bam_devmerger *m, int fd, int bai_fd, int64_t first_member_offset, int32_t n_ref, bwahip_devmerge_stats_t *st, bwahip_bai_stats_t *bs);
+int  bwahip_kat_bai(bwahip_ctx *ctx, const uint8_t *rec, const int64_t *rec_off, int64_t n_rec, const int32_t *member_len, int64_t n_members, int64_t first_member_offset,
+                    int32_t n_ref, uint8_t *out, int64_t out_cap, int64_t *out_len);
+int64_t bwahip_bam_devmerge_bai_hbm_need(int64_t n_records, int64_t n_blocks, int64_t n_ref, int64_t n_windows);
+
+/* bwahip_stream_run_bam_sorted and bwahip_stream_run_bam_sorted_dev with the index of the file on bai_fd (< 0: built and dropped); the
+ * BAM file is the one the entry point without index writes.  An index whose longest contig exceeds 2^29 bases: BWAHIP_ECAPACITY before
+ * anything starts.  The header goes through bwahip_bgzf_write_lens, so its members give the offset of the first member of the records.
+ * Host-merged: a builder listens to the merge (bwahip_bam_merger_finish_bai).  Device-merged: hbm_budget counts
+ * bwahip_bam_devmerge_hbm_need and bwahip_bam_devmerge_bai_hbm_need (windows: those of the contig table) together, the finish is
+ * bwahip_bam_devmerger_finish_bai; after a fall-back the index comes from the host path.  On any failure the return code says so and
+ * what may have reached bai_fd is not an index. */
+int bwahip_stream_run_bam_sorted_bai(bwahip_ctx *const *ctxs, int n_ctx, const bwahip_opt_t *opt, const bwahip_pestat_t *pes0, const char *fq1, const char *fq2,
+                                     int out_fd, const char *hdr_line, int level, bwahip_stream_t *st, bwahip_sort_t *so, int bai_fd);
+int bwahip_stream_run_bam_sorted_dev_bai(bwahip_ctx *const *ctxs, int n_ctx, const bwahip_opt_t *opt, const bwahip_pestat_t *pes0, const char *fq1, const char *fq2,
+                                         int out_fd, const char *hdr_line, bwahip_stream_t *st, bwahip_sort_dev_t *sd, int bai_fd);
+
 /* Insert-size statistics (mem_pestat_t[4]: FF, FR, RF, RR; bwamem_pair.c:72) and mate-rescue counters ([0] local alignments
  * run, [1] regions added, [2] most alignments of one pair, [3] pairs that needed any; bwamem_pair.c:137) of the last
  * paired-end batch finalised on the GPU.  Either pointer may be NULL; counters4 receives 4 values. */
