@@ -101,6 +101,9 @@ class BaiStats(C.Structure):  # bwahip_bai_stats_t
 ERRORS = {0: "ok", -1: "EINVAL", -2: "ENODEV", -3: "ENOMEM", -4: "EIO", -5: "ECAPACITY", -6: "EINTERNAL"}
 
 STAGE_INTV, STAGE_CHAIN, STAGE_CHAIN_FLT, STAGE_REGS, STAGE_REGS_PRE, STAGE_SEEDS = 1, 2, 3, 4, 5, 6
+STAGE_PESTAT, STAGE_REGS_PE, STAGE_PAIR = 7, 8, 9        # bwahip_run_pe_stages
+PE_PATHS = ("ahead_byte", "ahead_word", "inline_lds", "inline_slab", "incr_insert", "general_dedup", "big_pairs", "copy_big_pairs",
+            "try_ff", "try_fr", "try_rf", "try_rr", "off_contig", "both_kernels")   # bwahip_last_pe_paths
 TAG_READ = 100
 # known-answer DP entries (bwahip.h): forms of bwahip_kat_ksw_global, CIGAR words per item, path bits of bwahip_kat_ksw_extend2
 KAT_GLOBAL_AUTO_SMALL, KAT_GLOBAL_AUTO_BIG, KAT_GLOBAL_SCORE_ONLY = 0, 1, 2
@@ -233,6 +236,8 @@ def lib():
     L.bwahip_process_seqs.argtypes = [vp, C.POINTER(Opt), C.c_int64, C.c_int, C.POINTER(Seq), C.POINTER(PeStat)]
     L.bwahip_batch_download.argtypes = [vp, C.POINTER(AlnRegV)]
     L.bwahip_last_pe_stats.argtypes = [vp, C.POINTER(PeStat), u64p]
+    L.bwahip_last_pe_paths.argtypes = [vp, u64p, C.c_int]
+    L.bwahip_run_pe_stages.argtypes = [vp, C.POINTER(Opt), C.c_int64, C.c_int, vp, vp, C.POINTER(PeStat), C.c_int, C.POINTER(i64p), i64p]
     L.bwahip_seqs_take_sam.argtypes = [C.POINTER(Seq), C.c_int, C.POINTER(vp), i64p]
     _lib = L
     return L
@@ -588,6 +593,27 @@ class Context:
         words = np.ctypeslib.as_array(out, shape=(n.value,)).copy() if n.value else np.zeros(0, dtype=np.int64)
         C.CDLL(None).free(out)
         return parse_records(words)
+
+    def run_pe_stages(self, codes, off, stages, opt=None, n_processed=0, pes0=None):
+        """bwahip_run_pe_stages: reads 2i, 2i+1 are a pair; -> records (STAGE_PESTAT first, then per read TAG_READ and the stages asked for)."""
+        opt = opt or default_opt()
+        mask = 0
+        for s in stages:
+            mask |= 1 << s
+        out, n = C.POINTER(C.c_int64)(), C.c_int64()
+        codes = np.ascontiguousarray(codes, dtype=np.uint8)
+        off = np.ascontiguousarray(off, dtype=np.int64)
+        _check(lib().bwahip_run_pe_stages(self._h, C.byref(opt), n_processed, len(off) - 1, codes.ctypes.data, off.ctypes.data, pes0, mask,
+                                          C.byref(out), C.byref(n)), "bwahip_run_pe_stages")
+        words = np.ctypeslib.as_array(out, shape=(n.value,)).copy() if n.value else np.zeros(0, dtype=np.int64)
+        C.CDLL(None).free(out)
+        return parse_records(words)
+
+    def last_pe_paths(self):
+        """bwahip_last_pe_paths as a dict over PE_PATHS: which paths the paired-end kernels of the last batch took."""
+        cnt = (C.c_uint64 * len(PE_PATHS))()
+        _check(lib().bwahip_last_pe_paths(self._h, cnt, len(PE_PATHS)), "bwahip_last_pe_paths")
+        return {k: int(cnt[i]) for i, k in enumerate(PE_PATHS)}
 
     def tune(self, **kw):
         """Set hand-off thresholds of the heavy-read kernels (bwahip_ctx_tune): intv_cap, smem_lanes, heavy_mult, ...; and

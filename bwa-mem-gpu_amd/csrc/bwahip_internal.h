@@ -290,6 +290,8 @@ struct PairLaunch {
 	uint8_t *slab; size_t slab_stride;           // k_matesw: per-workgroup global scratch (reference window, column maxima, long-query working set)
 	unsigned int *queue;                         // k_matesw's work-queue heads (one per instantiation)
 	unsigned long long *counters;                // [0] SW calls, [1] rescued regions
+	unsigned long long *paths;                   // which path the rescue kernels took (PE_PATH_*; bwahip_last_pe_paths)
+	int *pair_dbg;                               // stage dump only (else null): per pair mem_pair's return value, sub and n_sub, zeroed by the host
 	// pairing
 	const FinReg *fregs; const int *freg_n; const int *n_pri;   // after k_mark on the pe lists (fregs is written: sub / secondary updates of bwamem_pair.c:347-350, 359-365)
 	FinReg *fregs_w;
@@ -299,6 +301,9 @@ struct PairLaunch {
 	PeRead *pe_read;
 	int *err;
 };
+// PairLaunch::paths: added up in registers, one atomic per workgroup at kernel end (k_pe_copy_big: per listed pair)
+enum { PE_PATH_INLINE_LDS = 0, PE_PATH_INLINE_SLAB, PE_PATH_INCR, PE_PATH_GENERAL, PE_PATH_BIG_PAIRS, PE_PATH_COPY_BIG, PE_PATH_TRY0, PE_PATH_TRY1, PE_PATH_TRY2, PE_PATH_TRY3,
+       PE_PATH_OFF_CONTIG, PE_PATH_BOTH_KERNELS, PE_PATH_N };
 int launch_pestat(const PairLaunch &a, hipStream_t st);
 int launch_pe_prepare(const PairLaunch &a, hipStream_t st);      // nb, pe_cap
 int launch_pe_copy(const PairLaunch &a, hipStream_t st);         // copy lists into pe_regs, list the pairs that need rescue

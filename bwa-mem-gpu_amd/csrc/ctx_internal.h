@@ -164,7 +164,10 @@ struct bwahip_ctx {
 	DevBuf d_hist, d_pair_tab, d_nb, d_pe_cap, d_pe_base, d_pe_regs, d_pe_n, d_pe_tmp, d_pe_keys, d_pe_idx, d_resc, d_ms_slab, d_pe_read, d_sw_cnt, d_sw_base, d_sw_res, d_sw_tasks, d_sw_info;   // paired-end stages
 	bwahip_pestat_t last_pes[4];         // insert-size statistics of the last paired-end batch
 	unsigned long long last_sw_tasks = 0;   // alignments k_matesw_sw ran ahead of the list logic (BWAHIP_PE_LOG)
-	unsigned long long last_pe_counters[9] = { 0, 0, 0, 0, 0, 0, 0, 0, 0 };   // mate-rescue alignments run / regions added / most per pair / pairs rescued
+	unsigned long long last_sw_ahead[2] = { 0, 0 };   // alignments run ahead by the byte / the word kernel (bwahip_last_pe_paths)
+	DevBuf d_pair_dbg;                   // stage dump: PairLaunch::pair_dbg
+	static constexpr int PE_CNT_PATHS = 14, PE_CNT_N = PE_CNT_PATHS + PE_PATH_N;   // d_fmisc[5 .. 5 + PE_CNT_N) in one copy: the 9 counters, 5 words of other use, PairLaunch::paths
+	unsigned long long last_pe_counters[PE_CNT_N] = { 0 };   // [0..3] mate-rescue alignments run / regions added / most per pair / pairs rescued
 	DevBuf d_task_lists;                 // k_cigar's two work lists (no-DP tasks, DP tasks)
 	DevBuf d_resc_flag;                  // one byte per pair: mate rescue works on it (finalised by the second k_mark / k_pair launch)
 	DevBuf d_zslab;                      // k_cigar's backtrack slabs
@@ -187,7 +190,28 @@ int launch_scan(const int *in, int64_t *out, int n, DevBuf &tmp, hipStream_t st)
 int launch_nt4(uint8_t *seq, int64_t n, hipStream_t st);   // runtime.hip: ASCII / codes -> codes 0..4 in place (nst_nt4_table)
 int dev_upload(DevBuf &b, const void *src, size_t bytes, hipStream_t st);
 int run_pipeline(bwahip_ctx *c, const bwahip_opt_t *opt, bool timed, bool dump);      // the hot path over the uploaded batch
-int run_final(bwahip_ctx *c, const bwahip_opt_t *opt, int64_t n_processed, const bwahip_pestat_t *pes0, bool timed, OutForm form, bool host_sam_off = false);   // regions in HBM -> the batch in `form` in HBM (SE, or PE when opt->flag has MEM_F_PE); host_sam_off: the offsets travel to h_sam_off ahead of the write pass (bwahip_process_seqs)
+// one region list as a stage record's words (bwahip_run_stages, bwahip_run_pe_stages): the count, then 19 words per region
+inline void stage_put_regs(std::vector<int64_t> &v, int cnt, const DevReg *rg)
+{
+	auto f2i = [](float f) { uint32_t u; memcpy(&u, &f, 4); return (int64_t)u; };
+	v.push_back(cnt);
+	for (int k = 0; k < cnt; ++k) {
+		const DevReg &p = rg[k];
+		v.push_back(p.rb); v.push_back(p.re); v.push_back(p.qb); v.push_back(p.qe); v.push_back(p.rid);
+		v.push_back(p.score); v.push_back(p.truesc); v.push_back(p.sub); v.push_back(0); v.push_back(p.csub);
+		v.push_back(p.sub_n); v.push_back(p.w); v.push_back(p.seedcov); v.push_back(0);
+		v.push_back(0); v.push_back(p.seedlen0); v.push_back(p.n_comp); v.push_back(p.is_alt);
+		v.push_back(f2i(p.frac_rep));
+	}
+}
+inline void stage_rec(std::vector<int64_t> &o, int64_t tag, const std::vector<int64_t> &v)
+{
+	o.push_back(tag); o.push_back((int64_t)v.size());
+	o.insert(o.end(), v.begin(), v.end());
+}
+// pe_stage_stop: paired end only, for bwahip_run_pe_stages -- return once both k_pair passes are done (the stream is idle then), with mem_pair's
+// results per pair in d_pair_dbg; nothing of the output stages runs
+int run_final(bwahip_ctx *c, const bwahip_opt_t *opt, int64_t n_processed, const bwahip_pestat_t *pes0, bool timed, OutForm form, bool host_sam_off = false, bool pe_stage_stop = false);   // regions in HBM -> the batch in `form` in HBM (SE, or PE when opt->flag has MEM_F_PE); host_sam_off: the offsets travel to h_sam_off ahead of the write pass (bwahip_process_seqs)
 // k_bamsort.hip: the records of c->bs.raw (per-read offsets c->d_sam_off, n_reads + 1) in coordinate order into c->d_sam, their keys into
 // c->d_skeys, their offsets into c->d_rec_off; sets c->n_rec.  Queued on c->stream (with two small read-backs awaited in between).
 int bam_sort_batch(bwahip_ctx *c, int n_reads, int64_t total);

@@ -99,7 +99,7 @@ static int run_pe_rescue(bwahip_ctx *c, const bwahip_opt_t *opt, const DevOpt &d
 	pl.logtab = c->d_logtab.as<double>();
 	pl.regs = c->d_regs.as<DevReg>(); pl.reg_base = c->d_reg_base.as<int64_t>(); pl.reg_n = c->d_reg_n.as<int>();
 	unsigned long long *fm = c->d_fmisc.as<unsigned long long>();
-	pl.err = (int*)(fm + 2); pl.resc_n = (int*)(fm + 4); pl.counters = fm + 5; pl.sw_n = (int*)(fm + 14); pl.queue = (unsigned int*)(fm + 16); pl.sw_n8 = (int*)(fm + 18);
+	pl.err = (int*)(fm + 2); pl.resc_n = (int*)(fm + 4); pl.counters = fm + 5; pl.sw_n = (int*)(fm + 14); pl.queue = (unsigned int*)(fm + 16); pl.sw_n8 = (int*)(fm + 18); pl.paths = fm + 19;   // (PE_PATH_N = 12 slots: up to fm[30] of the 32)
 	bwahip_pestat_t pes[4];
 	if (pes0) memcpy(pes, pes0, sizeof pes);
 	else {
@@ -164,6 +164,7 @@ static int run_pe_rescue(bwahip_ctx *c, const bwahip_opt_t *opt, const DevOpt &d
 	n_resc_out = n_resc;
 	c->last_pe_counters[3] = (unsigned long long)n_resc;
 	c->last_sw_tasks = (unsigned long long)n_sw_tasks + (unsigned long long)n_sw_tasks8;
+	c->last_sw_ahead[0] = (unsigned long long)n_sw_tasks; c->last_sw_ahead[1] = (unsigned long long)n_sw_tasks8;
 	if (n_resc > 0 || n_sw_tasks > 0 || n_sw_tasks8 > 0) {
 		HIP_TRY(hipEventRecord(c->ev_fork, c->stream));
 		HIP_TRY(hipStreamWaitEvent(c->stream2, c->ev_fork, 0));
@@ -183,7 +184,7 @@ static int run_pe_rescue(bwahip_ctx *c, const bwahip_opt_t *opt, const DevOpt &d
 }
 
 // K6 -> K9 over the batch run_pipeline left in HBM.  The text inputs (d_qual, d_names, ...) must be uploaded.
-int run_final(bwahip_ctx *c, const bwahip_opt_t *opt, int64_t n_processed, const bwahip_pestat_t *pes0, bool timed, OutForm form, bool host_sam_off)
+int run_final(bwahip_ctx *c, const bwahip_opt_t *opt, int64_t n_processed, const bwahip_pestat_t *pes0, bool timed, OutForm form, bool host_sam_off, bool pe_stage_stop)
 {
 	// the two output passes in the batch's format: SAM text (k_sam.hip) or BAM records (k_bam.hip)
 	auto launch_out = [&](const FinLaunch &fl, bool write, int lo, int hi) {
@@ -241,6 +242,11 @@ int run_final(bwahip_ctx *c, const bwahip_opt_t *opt, int64_t n_processed, const
 		if ((rc = c->d_pe_read.ensure((size_t)n * sizeof(PeRead)))) return rc;
 		pl.fregs = f.fregs; pl.fregs_w = f.fregs; pl.fregs_tmp = f.fregs2; pl.freg_n = f.freg_n; pl.n_pri = f.n_pri; pl.need = f.need; pl.xa_owner = f.xa_owner;
 		pl.task_n = f.task_n; pl.rec_n = f.rec_n; pl.scr = f.scr; pl.pe_read = c->d_pe_read.as<PeRead>();
+		if (pe_stage_stop) {
+			if ((rc = c->d_pair_dbg.ensure((size_t)(n / 2) * 12))) return rc;
+			HIP_TRY(hipMemsetAsync(c->d_pair_dbg.p, 0, (size_t)(n / 2) * 12, c->stream));
+			pl.pair_dbg = c->d_pair_dbg.as<int>();
+		}
 		pl.subset = 1;
 		if ((rc = launch_pair(pl, 0, c->stream))) return rc;
 		HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_join, 0));      // the rescue kernels (an event not recorded in this batch is complete: no wait)
@@ -250,9 +256,18 @@ int run_final(bwahip_ctx *c, const bwahip_opt_t *opt, int64_t n_processed, const
 			if ((rc = launch_pair(pl, n_resc, c->stream))) return rc;
 		}
 		f.subset = 0; pl.subset = 0;
-		HIP_TRY(hipMemcpyAsync(c->last_pe_counters, pl.counters, 72, hipMemcpyDeviceToHost, c->stream));   // [0..3] as documented; [4..8]: ticks of 10 ns in the window fetch, the alignments and the list clean-up of k_matesw, its longest pair, alignments it ran itself
+		static_assert(bwahip_ctx::PE_CNT_PATHS == 19 - 5, "PairLaunch::paths starts at d_fmisc[19], the counters at [5]");
+		HIP_TRY(hipMemcpyAsync(c->last_pe_counters, pl.counters, bwahip_ctx::PE_CNT_N * 8, hipMemcpyDeviceToHost, c->stream));   // [0..3] as documented; [4..8]: ticks of 10 ns in the window fetch, the alignments and the list clean-up of k_matesw, its longest pair, alignments it ran itself; [14..]: paths
 		f.pe_read = pl.pe_read;
 		memcpy(f.pes, pl.pes, sizeof f.pes);
+	}
+	if (pe_stage_stop) {
+		if (!pe) return BWAHIP_EINVAL;
+		HIP_TRY(hipStreamSynchronize(c->stream));
+		int err = 0;
+		HIP_TRY(hipMemcpy(&err, c->d_fmisc.as<unsigned long long>() + 2, 4, hipMemcpyDeviceToHost));
+		if (err) { fprintf(stderr, "[bwahip] paired-end kernels reported code %d\n", err); return BWAHIP_EINTERNAL; }
+		return 0;
 	}
 	if ((rc = launch_scan(c->d_task_n.as<int>(), c->d_task_base.as<int64_t>(), n, c->d_scan, c->stream))) return rc;
 	if (timed) HIP_TRY(hipEventRecord(c->ev[16], c->stream));
@@ -676,6 +691,79 @@ extern "C" int bwahip_last_pe_stats(bwahip_ctx *ctx, bwahip_pestat_t *pes4, uint
 		fprintf(stderr, "[bwahip] mate rescue: %llu alignments run ahead by k_matesw_sw; mem_matesw used %llu (%llu more inside k_matesw), %llu regions added, %llu pairs; k_matesw summed over its wavefronts: window fetch %.1f ms, alignments %.1f ms, list clean-up %.1f ms; longest pair %.2f ms\n",
 		        ctx->last_sw_tasks, c[0], c[8], c[1], c[3], c[4] / 1e5, c[5] / 1e5, c[6] / 1e5, c[7] / 1e5);
 	}
+	return 0;
+}
+
+// Which paths the paired-end kernels of the last batch took: out[0..n) of
+//   [0] alignments run ahead of the sequential pass by the byte kernel (k_matesw_sw), [1] by the word kernel (k_matesw_sw8),
+//   [2] alignments run inside k_matesw with the reference window in LDS, [3] with the window in the global slab,
+//   [4] rescued regions placed by incr_insert, [5] calls of the general sort_dedup_nopatch,
+//   [6] pairs taken by the BIG instantiations of k_matesw, [7] pairs copied by k_pe_copy_big,
+//   [8..11] alignments attempted per orientation FF, FR, RF, RR, [12] windows rejected because their middle lies in another contig than the
+//   anchor, [13] pairs with one end rescued by a <16> and the other by an <8> instantiation of k_matesw.
+extern "C" int bwahip_last_pe_paths(bwahip_ctx *ctx, uint64_t *out, int n)
+{
+	if (!ctx || !out || n < 0) return BWAHIP_EINVAL;
+	HIP_TRY(hipSetDevice(ctx->device));
+	HIP_TRY(hipStreamSynchronize(ctx->stream));
+	for (int i = 0; i < n; ++i) out[i] = i < 2 ? ctx->last_sw_ahead[i] : i < 2 + PE_PATH_N ? ctx->last_pe_counters[bwahip_ctx::PE_CNT_PATHS + i - 2] : 0;
+	return 0;
+}
+
+// Stage dump of the paired-end path (the counterpart of bwahip_run_stages): upload, run_pipeline, then run_final's paired-end part up to and
+// including both k_pair passes.  Records as bwahip_run_stages writes them: BWAHIP_STAGE_PESTAT once in front, then per read the header
+// (tag 100) and the stages asked for.
+extern "C" int bwahip_run_pe_stages(bwahip_ctx *c, const bwahip_opt_t *opt_in, int64_t n_processed, int n, const uint8_t *seq, const int64_t *off,
+                                    const bwahip_pestat_t *pes0, int stage_mask, int64_t **out, int64_t *out_len)
+{
+	if (!c || !opt_in || !out || !out_len || n < 0 || (n & 1)) return BWAHIP_EINVAL;
+	bwahip_opt_t opt = *opt_in;
+	opt.flag |= BWAHIP_F_PE;
+	int rc = bwahip_batch_upload(c, n, seq, off);
+	if (rc) return rc;
+	std::vector<int64_t> o, v;
+	if (n) {
+		if ((rc = run_pipeline(c, &opt, false, false))) return rc;
+		if ((rc = run_final(c, &opt, n_processed, pes0, false, OutForm::Sam, false, true))) return rc;
+	} else memset(c->last_pes, 0, sizeof c->last_pes);
+	for (int d = 0; d < 4; ++d) {
+		const bwahip_pestat_t &p = c->last_pes[d];
+		int64_t a, s;
+		memcpy(&a, &p.avg, 8); memcpy(&s, &p.std, 8);
+		v.push_back(p.low); v.push_back(p.high); v.push_back(p.failed); v.push_back(a); v.push_back(s);
+	}
+	if (stage_mask & (1 << BWAHIP_STAGE_PESTAT)) stage_rec(o, BWAHIP_STAGE_PESTAT, v);
+	if (n) {
+		const size_t R1 = (size_t)c->total_regs;
+		std::vector<int> n0(n), n1(n), dbg((size_t)(n / 2) * 3);
+		std::vector<int64_t> b0(n + 1), b1(n + 1);
+		std::vector<PeRead> pr(n);
+		HIP_TRY(hipMemcpy(n0.data(), c->d_reg_n.p, (size_t)n * 4, hipMemcpyDeviceToHost));
+		HIP_TRY(hipMemcpy(b0.data(), c->d_reg_base.p, (size_t)(n + 1) * 8, hipMemcpyDeviceToHost));
+		HIP_TRY(hipMemcpy(n1.data(), c->d_pe_n.p, (size_t)n * 4, hipMemcpyDeviceToHost));
+		HIP_TRY(hipMemcpy(b1.data(), c->d_pe_base.p, (size_t)(n + 1) * 8, hipMemcpyDeviceToHost));
+		HIP_TRY(hipMemcpy(pr.data(), c->d_pe_read.p, (size_t)n * sizeof(PeRead), hipMemcpyDeviceToHost));
+		HIP_TRY(hipMemcpy(dbg.data(), c->d_pair_dbg.p, dbg.size() * 4, hipMemcpyDeviceToHost));
+		std::vector<DevReg> r0((size_t)b0[n] + 1), r1(R1 + 1);
+		if (b0[n]) HIP_TRY(hipMemcpy(r0.data(), c->d_regs.p, (size_t)b0[n] * sizeof(DevReg), hipMemcpyDeviceToHost));
+		if (R1) HIP_TRY(hipMemcpy(r1.data(), c->d_pe_regs.p, R1 * sizeof(DevReg), hipMemcpyDeviceToHost));
+		for (int i = 0; i < n; ++i) {
+			v = { (int64_t)i, off[i + 1] - off[i] };
+			stage_rec(o, 100, v);
+			if (stage_mask & (1 << BWAHIP_STAGE_REGS)) { v.clear(); stage_put_regs(v, n0[i], &r0[b0[i]]); stage_rec(o, BWAHIP_STAGE_REGS, v); }
+			if (stage_mask & (1 << BWAHIP_STAGE_REGS_PE)) { v.clear(); stage_put_regs(v, n1[i], &r1[b1[i]]); stage_rec(o, BWAHIP_STAGE_REGS_PE, v); }
+			if (stage_mask & (1 << BWAHIP_STAGE_PAIR)) {
+				const PeRead &q = pr[i];
+				const int *g = &dbg[(size_t)(i >> 1) * 3];
+				v = { q.mode, q.h_reg, q.alt_reg, q.mapq, q.extra_flag, g[0], g[1], g[2] };
+				stage_rec(o, BWAHIP_STAGE_PAIR, v);
+			}
+		}
+	}
+	*out_len = (int64_t)o.size();
+	*out = (int64_t*)malloc(o.size() * 8 + 8);
+	if (!*out) return BWAHIP_ENOMEM;
+	memcpy(*out, o.data(), o.size() * 8);
 	return 0;
 }
 

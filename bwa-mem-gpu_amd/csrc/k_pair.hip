@@ -92,8 +92,9 @@ __global__ void k_pe_prepare(PairLaunch a)
 }
 
 // the reference window of mem_matesw for anchor `an`, orientation r and a mate of l_ms bases (bwamem_pair.c:153-166);
-// true when the alignment is attempted (same contig as the anchor, window at least one seed long)
-__device__ __forceinline__ bool ms_window(const PairLaunch &a, const DevReg &an, int r, int l_ms, int64_t &rb, int64_t &re)
+// 1 when the alignment is attempted (same contig as the anchor, window at least one seed long), -1 when the window's middle lies in
+// another contig than the anchor, else 0
+__device__ __forceinline__ int ms_window(const PairLaunch &a, const DevReg &an, int r, int l_ms, int64_t &rb, int64_t &re)
 {
 	const DevIndex &ix = a.ix;
 	const int64_t l_pac = ix.l_pac;
@@ -117,7 +118,8 @@ __device__ __forceinline__ bool ms_window(const PairLaunch &a, const DevReg &an,
 		rb = rb > far_beg ? rb : far_beg;
 		re = re < far_end ? re : far_end;
 	}
-	return an.rid == rid && re - rb >= a.opt.min_seed_len;
+	if (an.rid == rid && re - rb >= a.opt.min_seed_len) return 1;
+	return rid >= 0 && an.rid != rid ? -1 : 0;
 }
 
 constexpr int SW_TW = 1024;                                  // widest window k_matesw_sw takes (wider ones are aligned inside k_matesw)
@@ -162,7 +164,7 @@ __device__ __forceinline__ void pe_copy_pair(const PairLaunch &a, int p, int l)
 			if (byte_k || l_ms <= SW8_QMAX)
 				for (int o = W > 1 ? l : 0; o < 4; o += W > 1 ? 64 : 1) {
 					int64_t rb, re;
-					if ((sk >> o & 1) || !ms_window(a, src[j], o, l_ms, rb, re) || re - rb > SW_TW) continue;
+					if ((sk >> o & 1) || ms_window(a, src[j], o, l_ms, rb, re) <= 0 || re - rb > SW_TW) continue;
 					const int slot = (int)a.sw_base[r] + 4 * j + o;
 					a.sw_res[slot].state = 1;
 					if (byte_k) a.sw_tasks[atomicAdd(a.sw_n, 1)] = slot;
@@ -186,6 +188,7 @@ __global__ __launch_bounds__(256) void k_pe_copy_big(PairLaunch a)
 	if (p >= a.n_reads >> 1) return;
 	if (a.reg_n[p << 1] + a.reg_n[p << 1 | 1] <= PE_COPY_SMALL) return;
 	pe_copy_pair<64>(a, p, lane());
+	if (lane() == 0) atomicAdd(&a.paths[PE_PATH_COPY_BIG], 1ull);
 }
 
 // ---------------------------------------------------------------------------------------------------- mem_matesw
@@ -407,11 +410,15 @@ __device__ __forceinline__ bool incr_insert(const DevOpt &o, int &n_io, const Li
 	return true;
 }
 
+// what a wavefront of k_matesw counts on its way (PairLaunch::counters and ::paths); tries: attempted alignments per orientation, 32 bits each
+// (r = 0, 1 in tries01; 2, 3 in tries23: no array, an index that is a loop variable would put it into scratch memory)
+struct MsCount { unsigned long long n_sw = 0, n_new = 0, n_inline = 0, tries01 = 0, tries23 = 0; unsigned inline_slab = 0, incr = 0, general = 0, off_contig = 0; };
+
 // mem_matesw (bwamem_pair.c:137-206): anchor `an` (a region of one end), mate read r_m (length l_ms), mate list L (n_ma).
 // P = 16: byte kernel (l_ms * a < 250), P = 8: word kernel.  Returns the new length of the mate list.
 template <int P>
 __device__ __forceinline__ int matesw(const PairLaunch &a, const DevReg an, int slot0, int r_m, int l_ms, const ListRef L, int n_ma, const ListRef tmp, RegKey *keys, int *idx,
-                      const MsLds &m, uint8_t *slab, int l, unsigned long long &n_sw, unsigned long long &n_new, unsigned long long &n_inline, bool &clean)
+                      const MsLds &m, uint8_t *slab, int l, MsCount &cnt, bool &clean)
 {
 	// clean: the list is what a mem_sort_dedup_patch without ties returned (or that plus incr_insert steps): one more call is the identity
 	const DevOpt &opt = a.opt;
@@ -437,7 +444,10 @@ __device__ __forceinline__ int matesw(const PairLaunch &a, const DevReg an, int 
 		bool general = !clean;                                    // this orientation ends with the general mem_sort_dedup_patch
 		const int is_rev = (r >> 1) != (r & 1);
 		int64_t rb, re;
-		if (ms_window(a, an, r, l_ms, rb, re)) {
+		const int win = ms_window(a, an, r, l_ms, rb, re);
+		cnt.off_contig += win < 0 ? 1 : 0;
+		if (win > 0) {
+			cnt.tries01 += r < 2 ? 1ull << (r << 5) : 0ull; cnt.tries23 += r < 2 ? 0ull : 1ull << ((r & 1) << 5);
 			const unsigned long long tk0 = wall_clock64();
 			const int tlen = (int)(re - rb);
 			ssw::Res aln = { 0, -1, -1, -1, -1, -1, -1 };
@@ -465,9 +475,9 @@ __device__ __forceinline__ int matesw(const PairLaunch &a, const DevReg an, int 
 				}
 				aln.score = __shfl(aln.score, 0); aln.te = __shfl(aln.te, 0); aln.qe = __shfl(aln.qe, 0); aln.score2 = __shfl(aln.score2, 0);
 				aln.tb = __shfl(aln.tb, 0); aln.qb = __shfl(aln.qb, 0);
-				++n_inline;
+				++cnt.n_inline; cnt.inline_slab += tlen <= m.tw_cap ? 0 : 1;
 			}
-			++n_sw;
+			++cnt.n_sw;
 			const unsigned long long tk2 = wall_clock64();
 			if (l == 0) { atomicAdd(&a.counters[4], tk1 - tk0); atomicAdd(&a.counters[5], tk2 - tk1); }
 			if (aln.score >= opt.min_seed_len && aln.qb >= 0) {   // something goes wrong if aln.qb < 0 (bwamem_pair.c:178)
@@ -482,7 +492,7 @@ __device__ __forceinline__ int matesw(const PairLaunch &a, const DevReg an, int 
 				b.seedcov = (int)((b.re - b.rb < b.qe - b.qb ? b.re - b.rb : b.qe - b.qb) >> 1);
 				const unsigned long long tki = wall_clock64();
 				const bool done = !general && incr_insert(opt, n_ma, L, tmp, b, idx, l);
-				if (done) { ++n_new; if (l == 0) atomicAdd(&a.counters[6], wall_clock64() - tki); }
+				if (done) { ++cnt.n_new; ++cnt.incr; if (l == 0) atomicAdd(&a.counters[6], wall_clock64() - tki); }
 				else {
 				general = true;
 				// insert b keeping the list sorted by score (bwamem_pair.c:194-199)
@@ -502,13 +512,13 @@ __device__ __forceinline__ int matesw(const PairLaunch &a, const DevReg an, int 
 					wsync();
 				}
 				if (l == 0) L[at] = b;
-				++n_ma; ++n_new;
+				++n_ma; ++cnt.n_new;
 				wsync();
 				}
 			}
 			++n;
 		}
-		if (n && general) { const unsigned long long tk3 = wall_clock64(); bool ties; n_ma = sort_dedup_nopatch(opt, n_ma, L, tmp, keys, idx, m.stk, reinterpret_cast<unsigned*>(m.h + 128), l, a.err, ties); clean = !ties; if (l == 0) atomicAdd(&a.counters[6], wall_clock64() - tk3); }   // (m.h + 128: 256 bytes into the array -- a base register of the sort's table accesses stays inside LDS whatever offset gets folded)
+		if (n && general) { ++cnt.general; const unsigned long long tk3 = wall_clock64(); bool ties; n_ma = sort_dedup_nopatch(opt, n_ma, L, tmp, keys, idx, m.stk, reinterpret_cast<unsigned*>(m.h + 128), l, a.err, ties); clean = !ties; if (l == 0) atomicAdd(&a.counters[6], wall_clock64() - tk3); }   // (m.h + 128: 256 bytes into the array -- a base register of the sort's table accesses stays inside LDS whatever offset gets folded)
 	}
 	return n_ma;
 }
@@ -616,7 +626,9 @@ __global__ __launch_bounds__(64, BIG ? 2 : 1) void k_matesw(PairLaunch a)
 	if (l < 25) s_mat[l] = a.opt.mat[l];
 	__syncthreads();
 	uint8_t *slab = a.slab + (size_t)blockIdx.x * a.slab_stride;
-	unsigned long long n_sw = 0, n_new = 0, max_sw = 0, n_inline = 0;
+	MsCount cnt;
+	unsigned long long max_sw = 0;
+	unsigned n_pairs = 0, n_both = 0;
 	const int n_resc = *a.resc_n;
 	// the pairs come from a queue, the ones with the longest lists first (k_resc_order): a pair inside a repeat family costs a thousand times an
 	// ordinary one, and a fixed share per workgroup left most of the kernel's duration to the unluckiest workgroup
@@ -627,14 +639,17 @@ __global__ __launch_bounds__(64, BIG ? 2 : 1) void k_matesw(PairLaunch a)
 		if (it >= n_resc) break;
 		const int p = a.resc_list[it];
 		if ((a.pe_cap[p << 1] > MS_LIST || a.pe_cap[p << 1 | 1] > MS_LIST) != BIG) continue;   // the other instantiation's pair
-		const unsigned long long sw_before = n_sw, tp0 = wall_clock64();
+		const unsigned long long sw_before = cnt.n_sw, tp0 = wall_clock64();
+		bool mine = false, others = false;                        // ends of this pair rescued here / by the instantiation for the other mate length
+		++n_pairs;
 		int n_list[2] = { a.pe_n[p << 1], a.pe_n[p << 1 | 1] };
 		// sort scratch of a list lives behind its slots' spare copy: tmp list, keys and index arrays sized by the capacity
 		for (int i = 0; i < 2; ++i) {
 			const int r = p << 1 | i, rm = r ^ 1;
 			const int l_ms = (int)(a.off[rm + 1] - a.off[rm]);
-			if ((P == 16) != (l_ms * a.opt.a < 250)) continue;    // the other instantiation takes this mate length
 			if (a.nb[r] == 0) continue;
+			if ((P == 16) != (l_ms * a.opt.a < 250)) { others = true; continue; }   // the other instantiation takes this mate length
+			mine = true;
 			// the mate's list is worked on in LDS when its capacity fits (the insert / sort / dedup steps are chains of dependent
 			// accesses: ~1 ms per rescue through global memory, measured), else in its global slots
 			DevReg *G = a.pe_regs + a.pe_base[rm];
@@ -650,7 +665,7 @@ __global__ __launch_bounds__(64, BIG ? 2 : 1) void k_matesw(PairLaunch a)
 				const MsLds m = { s_q, s_mat, s_prof, s_h, s_keys, s_idx, s_stk, s_tw, 4096, s_cm };
 				bool clean = false;
 				for (int j = 0; j < a.nb[r]; ++j)
-					n_list[i ^ 1] = matesw<P>(a, snap[j], (int)a.sw_base[r] + 4 * j, rm, l_ms, s_list, n_list[i ^ 1], s_tmp, s_keys, s_idx, m, slab, l, n_sw, n_new, n_inline, clean);
+					n_list[i ^ 1] = matesw<P>(a, snap[j], (int)a.sw_base[r] + 4 * j, rm, l_ms, s_list, n_list[i ^ 1], s_tmp, s_keys, s_idx, m, slab, l, cnt, clean);
 			} else {
 				DevReg *tmp = a.pe_tmp + a.pe_base[rm];
 				RegKey *keys = reinterpret_cast<RegKey*>(a.pe_keys) + a.pe_base[rm];
@@ -658,7 +673,7 @@ __global__ __launch_bounds__(64, BIG ? 2 : 1) void k_matesw(PairLaunch a)
 				const MsLds m = { s_q, s_mat, s_prof, s_h, keys, idx, s_stk, s_tw, 4096, s_cm };
 				bool clean = false;
 				for (int j = 0; j < a.nb[r]; ++j)
-					n_list[i ^ 1] = matesw<P>(a, snap[j], (int)a.sw_base[r] + 4 * j, rm, l_ms, ListRef::global(G), n_list[i ^ 1], ListRef::global(tmp), keys, idx, m, slab, l, n_sw, n_new, n_inline, clean);
+					n_list[i ^ 1] = matesw<P>(a, snap[j], (int)a.sw_base[r] + 4 * j, rm, l_ms, ListRef::global(G), n_list[i ^ 1], ListRef::global(tmp), keys, idx, m, slab, l, cnt, clean);
 			}
 			if (in_lds) { wsync(); for (int k = l; k < n_list[i ^ 1]; k += 64) G[k] = s_list[k]; wsync(); }
 		}
@@ -668,11 +683,19 @@ __global__ __launch_bounds__(64, BIG ? 2 : 1) void k_matesw(PairLaunch a)
 			if ((P == 16) == (lm1 * a.opt.a < 250)) a.pe_n[p << 1 | 1] = n_list[1];
 			if ((P == 16) == (lm0 * a.opt.a < 250)) a.pe_n[p << 1] = n_list[0];
 		}
-		max_sw = max_sw > n_sw - sw_before ? max_sw : n_sw - sw_before;
+		max_sw = max_sw > cnt.n_sw - sw_before ? max_sw : cnt.n_sw - sw_before;
+		n_both += P == 8 && mine && others ? 1 : 0;
 		if (l == 0) atomicMax(&a.counters[7], wall_clock64() - tp0);
 		__syncthreads();
 	}
-	if (l == 0) { if (n_sw) { atomicAdd(&a.counters[0], n_sw); atomicAdd(&a.counters[1], n_new); atomicMax(&a.counters[2], max_sw); atomicAdd(&a.counters[8], n_inline); } if (blockIdx.x == 0) atomicMax(&a.counters[3], (unsigned long long)n_resc); }
+	if (l == 0) {
+		if (cnt.n_sw) { atomicAdd(&a.counters[0], cnt.n_sw); atomicAdd(&a.counters[1], cnt.n_new); atomicMax(&a.counters[2], max_sw); atomicAdd(&a.counters[8], cnt.n_inline); }
+		if (blockIdx.x == 0) atomicMax(&a.counters[3], (unsigned long long)n_resc);
+		auto add = [paths = a.paths](int k, unsigned long long v) { if (v) atomicAdd(&paths[k], v); };
+		add(PE_PATH_INLINE_LDS, cnt.n_inline - cnt.inline_slab); add(PE_PATH_INLINE_SLAB, cnt.inline_slab); add(PE_PATH_INCR, cnt.incr); add(PE_PATH_GENERAL, cnt.general);
+		add(PE_PATH_BIG_PAIRS, BIG ? n_pairs : 0); add(PE_PATH_OFF_CONTIG, cnt.off_contig); add(PE_PATH_BOTH_KERNELS, n_both);
+		add(PE_PATH_TRY0, cnt.tries01 & 0xffffffffu); add(PE_PATH_TRY1, cnt.tries01 >> 32); add(PE_PATH_TRY2, cnt.tries23 & 0xffffffffu); add(PE_PATH_TRY3, cnt.tries23 >> 32);
+	}
 }
 
 // ---------------------------------------------------------------------------------------------------- mem_pair + mem_sam_pe decisions
@@ -817,6 +840,7 @@ __global__ __launch_bounds__(64) void k_pair(PairLaunch a)
 #undef FOR_PAIRS
 				n_sub = wsum(c2) - 1;
 			}
+			if (a.pair_dbg && l == 0) { a.pair_dbg[3 * p] = o; a.pair_dbg[3 * p + 1] = subo; a.pair_dbg[3 * p + 2] = n_sub; }   // as mem_pair returned them
 			if (o > 0) {
 				// ---- bwamem_pair.c:312-365
 				int is_multi[2];

@@ -361,7 +361,7 @@ void bwahip_destroy(bwahip_ctx *c)
 	                   &c->d_ctg_names, &c->d_ctg_name_off, &c->d_ctg_anno, &c->d_ctg_anno_off, &c->d_rg, &c->d_qual, &c->d_qual_off, &c->d_names, &c->d_name_off, &c->d_comments, &c->d_comment_off,
 	                   &c->d_fregs, &c->d_fregs2, &c->d_fscr, &c->d_need, &c->d_xa_owner, &c->d_freg_n, &c->d_npri, &c->d_task_n, &c->d_rec_n, &c->d_task_base, &c->d_tasks, &c->d_aln_of_reg, &c->d_alns,
 	                   &c->d_resc_flag, &c->d_zslab, &c->d_resc_ord, &c->d_pool, &c->d_fmisc, &c->d_fredo, &c->d_bigz, &c->d_rec_list, &c->d_xa_list, &c->d_sam_len, &c->d_sam_off, &c->d_sam,
-	                   &c->d_hist, &c->d_pair_tab, &c->d_nb, &c->d_pe_cap, &c->d_pe_base, &c->d_pe_regs, &c->d_pe_n, &c->d_pe_tmp, &c->d_pe_keys, &c->d_pe_idx, &c->d_resc, &c->d_ms_slab, &c->d_pe_read, &c->d_sw_cnt, &c->d_sw_base, &c->d_sw_res, &c->d_sw_tasks, &c->d_sw_info, &c->d_task_lists };
+	                   &c->d_hist, &c->d_pair_tab, &c->d_nb, &c->d_pe_cap, &c->d_pe_base, &c->d_pe_regs, &c->d_pe_n, &c->d_pe_tmp, &c->d_pe_keys, &c->d_pe_idx, &c->d_resc, &c->d_ms_slab, &c->d_pe_read, &c->d_sw_cnt, &c->d_sw_base, &c->d_sw_res, &c->d_sw_tasks, &c->d_sw_info, &c->d_task_lists, &c->d_pair_dbg };
 	if (c->external_index) { c->d_bwt.p = nullptr; c->d_sa.p = nullptr; c->d_pac.p = nullptr; c->d_bwt.cap = c->d_sa.cap = c->d_pac.cap = 0; }
 	for (DevBuf *b : bufs) b->release();
 	c->h_stage.release(); c->h_sam.release(); c->h_sam2.release();
@@ -1011,11 +1011,7 @@ static int batch_download_mt(bwahip_ctx *c, bwahip_alnreg_v *out, int nt)
 int bwahip_batch_download(bwahip_ctx *c, bwahip_alnreg_v *out) { return batch_download_mt(c, out, 1); }
 
 // ------------------------------------------------------------------ stage dump (i64 records)
-static void rec(std::vector<int64_t> &o, int64_t tag, const std::vector<int64_t> &v)
-{
-	o.push_back(tag); o.push_back((int64_t)v.size());
-	o.insert(o.end(), v.begin(), v.end());
-}
+static void rec(std::vector<int64_t> &o, int64_t tag, const std::vector<int64_t> &v) { stage_rec(o, tag, v); }
 
 int bwahip_run_stages(bwahip_ctx *c, const bwahip_opt_t *opt, int n, const uint8_t *seq, const int64_t *off,
                       int stage_mask, int64_t **out, int64_t *out_len)
@@ -1070,17 +1066,7 @@ int bwahip_run_stages(bwahip_ctx *c, const bwahip_opt_t *opt, int n, const uint8
 			for (int t = 0; t < h.n; ++t) { const DevSeed &d = sd[h.seed_off + t]; v.push_back(d.rbeg); v.push_back(d.qbeg); v.push_back(d.len); v.push_back(d.score); }
 		}
 	};
-	auto put_regs = [&](std::vector<int64_t> &v, int cnt, const DevReg *rg) {
-		v.push_back(cnt);
-		for (int k = 0; k < cnt; ++k) {
-			const DevReg &p = rg[k];
-			v.push_back(p.rb); v.push_back(p.re); v.push_back(p.qb); v.push_back(p.qe); v.push_back(p.rid);
-			v.push_back(p.score); v.push_back(p.truesc); v.push_back(p.sub); v.push_back(0); v.push_back(p.csub);
-			v.push_back(p.sub_n); v.push_back(p.w); v.push_back(p.seedcov); v.push_back(0);
-			v.push_back(0); v.push_back(p.seedlen0); v.push_back(p.n_comp); v.push_back(p.is_alt);
-			v.push_back(f2i(p.frac_rep));
-		}
-	};
+	auto put_regs = [&](std::vector<int64_t> &v, int cnt, const DevReg *rg) { stage_put_regs(v, cnt, rg); };
 	for (int i = 0; i < n; ++i) {
 		std::vector<int64_t> v = { (int64_t)i, off[i + 1] - off[i] };
 		rec(o, 100, v);

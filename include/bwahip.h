@@ -510,6 +510,26 @@ int bwahip_seqs_take_sam(bwahip_seq_t *seqs, int n, char **out, int64_t *out_len
 int bwahip_run_stages(bwahip_ctx *ctx, const bwahip_opt_t *opt, int n, const uint8_t *seq, const int64_t *off,
                       int stage_mask, int64_t **out, int64_t *out_len);
 
+/* The same for the paired-end path (reads 2i and 2i+1 are a pair; BWAHIP_F_PE is implied): insert-size statistics, mate rescue and
+ * pairing run exactly as bwahip_process_seqs runs them, up to and including the pairing kernel; no output is made.  pes0 and
+ * n_processed as for bwahip_process_seqs.  Records: BWAHIP_STAGE_PESTAT once, in front of the first read; per read the header and
+ * BWAHIP_STAGE_REGS (the list mem_sam_pe is given), _REGS_PE, _PAIR as asked for. */
+#define BWAHIP_STAGE_PESTAT    7   /* mem_pestat (bwamem_pair.c:72): per direction FF, FR, RF, RR low, high, failed and the bit patterns of avg and std */
+#define BWAHIP_STAGE_REGS_PE   8   /* regions after all mem_matesw calls, before mem_mark_primary_se (bwamem_pair.c:299); layout of BWAHIP_STAGE_REGS */
+#define BWAHIP_STAGE_PAIR      9   /* mem_sam_pe's decisions: paired (bwamem_pair.c:311-384) or not; region of h[i] (paired: z[i]; else the region the
+                                      mate information comes from, -1 none); ALT region printed as supplementary or -1; q_se[i] (0 when not paired);
+                                      extra_flag as mem_sam_pe holds it at that point (the proper-pair bit of an unpaired end is set later, when
+                                      the records are written); and per pair mem_pair's return value, sub and n_sub (0 when mem_pair did not run) */
+int bwahip_run_pe_stages(bwahip_ctx *ctx, const bwahip_opt_t *opt, int64_t n_processed, int n, const uint8_t *seq, const int64_t *off,
+                         const bwahip_pestat_t *pes0, int stage_mask, int64_t **out, int64_t *out_len);
+/* Which paths the paired-end kernels of the last batch took (work counts, kept by the kernels): [0] / [1] mate-rescue alignments run
+ * ahead of the sequential pass by the byte / the word kernel, [2] / [3] alignments run inside the sequential pass with the reference
+ * window in LDS / in global memory, [4] rescued regions placed without sorting the list again, [5] full sort-and-dedup passes,
+ * [6] pairs whose lists stayed in global memory, [7] pairs whose lists were copied by a whole wavefront, [8..11] alignments attempted
+ * per orientation FF, FR, RF, RR, [12] windows dropped because their middle lies in another contig than the anchor, [13] pairs with one
+ * end rescued by the byte and the other by the word kernel's instantiation.  out[i] for i >= 14 is set to 0. */
+int bwahip_last_pe_paths(bwahip_ctx *ctx, uint64_t *out, int n);
+
 /* Device-resident batch for benchmarking: upload once, run the whole hot path (seq codes in HBM ->
  * alignment regions in HBM) any number of times.  kernel_ms (may be NULL) receives the per-kernel
  * durations of the last run measured with HIP events on the launch stream, in launch order

@@ -2,6 +2,7 @@
  * restatement.  Mirrors oracle/ref_driver.c so tests can diff the two:
  *   bwa_oracle mem    [-p] [-t N] [-K bases] [-a] <prefix> <r1.fq> [r2.fq]   SAM body on stdout
  *   bwa_oracle stages <prefix> <reads.fq> <out.bin>                          per-read stage dump
+ *   bwa_oracle stages [options, -I] <prefix> <r1.fq> <r2.fq> <out.bin>       paired-end stage dump (one batch)
  * Batching follows bseq_read (bwa.c:191): reads are taken until the batch holds
  * >= chunk bases and an even number of reads.
  */
@@ -91,7 +92,7 @@ static void rec_write(FILE *fp, int64_t tag, int64_t n, const int64_t *v) { fwri
 typedef struct { int64_t n, m; int64_t *a; } i64v;
 static inline void push(i64v *v, int64_t x) { if (v->n == v->m) { v->m = v->m ? v->m << 1 : 256; v->a = (int64_t*)realloc(v->a, v->m * 8); } v->a[v->n++] = x; }
 static inline int64_t f2i(float f) { uint32_t u; memcpy(&u, &f, 4); return (int64_t)u; }
-enum { TAG_READ = 100, TAG_INTV = 1, TAG_CHAIN = 2, TAG_CHAIN_FLT = 3, TAG_REGS_PRE = 5, TAG_REGS = 4 };
+enum { TAG_READ = 100, TAG_INTV = 1, TAG_CHAIN = 2, TAG_CHAIN_FLT = 3, TAG_REGS_PRE = 5, TAG_REGS = 4, TAG_PESTAT = 7, TAG_REGS_PE = 8, TAG_PAIR = 9 };
 
 static void dump_chains(FILE *fp, int64_t tag, int n, const ora_chain_t *a)
 {
@@ -122,6 +123,47 @@ static void dump_regs(FILE *fp, int64_t tag, int n, const ora_reg_t *a)
 	rec_write(fp, tag, v.n, v.a); free(v.a);
 }
 
+/* Paired-end stages: the whole input as ONE batch through ora_process_seqs with the recording hook of ora.h switched on.
+ * PESTAT once, in front of the reads (per direction low, high, failed and the bit patterns of avg and std); per read REGS (the
+ * list mem_sam_pe is given), REGS_PE (after all mem_matesw calls, bwamem_pair.c:299) and PAIR (see ora_pe_dump_t). */
+static int stages_pe(ora_opt_t *opt, const optparse_t *op, ora_index_t *idx, const char *fq1, const char *fq2, const char *out_fn)
+{
+	fq_t f1 = { 0, 0, 0, 0 }, f2 = { 0, 0, 0, 0 };
+	ora_pe_dump_t rec;
+	ora_read_t *seqs;
+	FILE *out;
+	int64_t ps[20];
+	int n, i, d;
+	f1.fp = gzopen(fq1, "r"); f2.fp = gzopen(fq2, "r");
+	if (!f1.fp || !f2.fp || !(out = fopen(out_fn, "wb"))) return 1;
+	opt->flag |= ORA_F_PE;
+	seqs = read_batch(0x7fffffff, &n, &f1, &f2);
+	memset(&rec, 0, sizeof rec);
+	rec.se = (ora_reg_v*)calloc(n ? n : 1, sizeof(ora_reg_v)); rec.pe = (ora_reg_v*)calloc(n ? n : 1, sizeof(ora_reg_v));
+	rec.pair = (int64_t(*)[8])calloc(n ? n : 1, sizeof(int64_t[8]));
+	ora_pe_dump = &rec;
+	ora_process_seqs(opt, idx, 0, n, seqs, op->has_pes0 ? op->pes : 0);
+	ora_pe_dump = 0;
+	for (d = 0; d < 4; ++d) {
+		ps[5*d] = rec.pes[d].low; ps[5*d+1] = rec.pes[d].high; ps[5*d+2] = rec.pes[d].failed;
+		memcpy(&ps[5*d+3], &rec.pes[d].avg, 8); memcpy(&ps[5*d+4], &rec.pes[d].std, 8);
+	}
+	rec_write(out, TAG_PESTAT, 20, ps);
+	for (i = 0; i < n; ++i) {
+		int64_t hdr[2];
+		hdr[0] = i; hdr[1] = seqs[i].l_seq;
+		rec_write(out, TAG_READ, 2, hdr);
+		dump_regs(out, TAG_REGS, rec.se[i].n, rec.se[i].a);
+		dump_regs(out, TAG_REGS_PE, rec.pe[i].n, rec.pe[i].a);
+		rec_write(out, TAG_PAIR, 8, rec.pair[i]);
+		free(rec.se[i].a); free(rec.pe[i].a);
+		free(seqs[i].name); free(seqs[i].comment); free(seqs[i].seq); free(seqs[i].qual); free(seqs[i].sam);
+	}
+	free(seqs); free(rec.se); free(rec.pe); free(rec.pair);
+	fclose(out); gzclose(f1.fp); gzclose(f2.fp); free(f1.line); free(f2.line);
+	return 0;
+}
+
 static int main_stages(int argc, char **argv)
 {
 	ora_opt_t opt;
@@ -139,6 +181,7 @@ static int main_stages(int argc, char **argv)
 	argv += optind - 1;
 	idx = ora_index_load(argv[1]);
 	if (op.ignore_alt) for (c = 0; c < idx->ref->n_seqs; ++c) idx->ref->anns[c].is_alt = 0;
+	if (optind + 4 <= argc) { c = stages_pe(&opt, &op, idx, argv[2], argv[3], argv[4]); ora_index_destroy(idx); return c; }
 	f.fp = gzopen(argv[2], "r");
 	out = fopen(argv[3], "wb");
 	while (fq_read(&f, &r)) {

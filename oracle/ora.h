@@ -73,6 +73,19 @@ int ora_matesw(const ora_opt_t *opt, const ora_ref_t *r, const ora_pestat_t pes[
 int ora_pair(const ora_opt_t *opt, const ora_ref_t *r, const ora_pestat_t pes[4], ora_read_t s[2], ora_reg_v a[2], int id, int *sub, int *n_sub, int z[2], int n_pri[2]); /* bwamem_pair.c:208 */
 int ora_sam_pe(const ora_opt_t *opt, const ora_ref_t *r, const ora_pestat_t pes[4], uint64_t id, ora_read_t s[2], ora_reg_v a[2]); /* bwamem_pair.c:276 */
 
+/* Stage records of the paired-end path (`bwa_oracle stages` with two read files).  While ora_pe_dump is NULL -- always in `mem`
+ * mode -- nothing is recorded.  Otherwise ora_process_seqs stores the batch's insert-size statistics and ora_sam_pe, per read of the
+ * batch, a copy of the list it was given, of the list after every ora_matesw call, and its decisions.  Each pair writes only its own
+ * slots, so the worker threads need no lock. */
+typedef struct {
+	ora_pestat_t pes[4];
+	int64_t id0;                /* pair id of the batch's first pair (n_processed >> 1) */
+	ora_reg_v *se, *pe;         /* per read: regions as mem_align1_core returned them / after all mem_matesw calls (bwamem_pair.c:299) */
+	int64_t (*pair)[8];         /* per read: paired, z[i] (unpaired: the region of h[i], -1 none), ALT region or -1, q_se[i], extra_flag
+	                               as mem_sam_pe holds it when it decides, and per pair mem_pair's return value, sub, n_sub */
+} ora_pe_dump_t;
+extern ora_pe_dump_t *ora_pe_dump;
+
 /* ora_process.c */
 void ora_process_seqs(const ora_opt_t *opt, const ora_index_t *idx, int64_t n_processed, int n, ora_read_t *seqs, const ora_pestat_t *pes0); /* bwamem.c:1215 */
 

@@ -218,13 +218,35 @@ int ora_pair(const ora_opt_t *opt, const ora_ref_t *ref, const ora_pestat_t pes[
 
 #define RAW_MAPQ(diff, a) ((int)(6.02 * (diff) / (a) + .499))   /* bwamem_pair.c:274 */
 
+/* stage records (ora.h): inert while ora_pe_dump is NULL */
+ora_pe_dump_t *ora_pe_dump = 0;
+static void dump_lists(ora_reg_v *to, uint64_t id, const ora_reg_v a[2])
+{
+	int i;
+	for (i = 0; i < 2; ++i) {
+		ora_reg_v *d = &to[(id - ora_pe_dump->id0) << 1 | i];
+		d->n = d->m = a[i].n;
+		d->a = (ora_reg_t*)malloc((a[i].n ? a[i].n : 1) * sizeof(ora_reg_t));
+		if (a[i].n) memcpy(d->a, a[i].a, a[i].n * sizeof(ora_reg_t));
+	}
+}
+static void dump_pair(uint64_t id, int paired, const int z[2], const int alt[2], const int q_se[2], int extra_flag, int o, int subo, int n_sub)
+{
+	int i;
+	for (i = 0; i < 2; ++i) {
+		int64_t *p = ora_pe_dump->pair[(id - ora_pe_dump->id0) << 1 | i];
+		p[0] = paired; p[1] = z[i]; p[2] = alt[i]; p[3] = q_se[i]; p[4] = extra_flag; p[5] = o; p[6] = subo; p[7] = n_sub;
+	}
+}
+
 int ora_sam_pe(const ora_opt_t *opt, const ora_ref_t *ref, const ora_pestat_t pes[4], uint64_t id, ora_read_t s[2], ora_reg_v a[2])   /* bwamem_pair.c:276 */
 {
-	int n = 0, i, j, z[2], o, subo, n_sub, extra_flag = 1, n_pri[2], n_aa[2];
+	int n = 0, i, j, z[2], o = 0, subo = 0, n_sub = 0, subo_pair = 0, extra_flag = 1, n_pri[2], n_aa[2];
 	ora_str_t str = { 0, 0, 0 };
 	ora_aln_t h[2], g[2], aa[2][2];
 	memset(h, 0, sizeof h); memset(g, 0, sizeof g);
 	n_aa[0] = n_aa[1] = 0;
+	if (ora_pe_dump) dump_lists(ora_pe_dump->se, id, a);
 	if (!(opt->flag & ORA_F_NO_RESCUE)) {
 		ora_reg_v b[2] = { { 0, 0, 0 }, { 0, 0, 0 } };
 		for (i = 0; i < 2; ++i)
@@ -238,6 +260,7 @@ int ora_sam_pe(const ora_opt_t *opt, const ora_ref_t *ref, const ora_pestat_t pe
 				n += ora_matesw(opt, ref, pes, &b[i].a[j], s[!i].l_seq, (uint8_t*)s[!i].seq, &a[!i]);
 		free(b[0].a); free(b[1].a);
 	}
+	if (ora_pe_dump) dump_lists(ora_pe_dump->pe, id, a);
 	n_pri[0] = ora_mark_primary_se(opt, a[0].n, a[0].a, id << 1 | 0);
 	n_pri[1] = ora_mark_primary_se(opt, a[1].n, a[1].a, id << 1 | 1);
 	if (opt->flag & ORA_F_PRIMARY5) { ora_reorder_primary5(opt->T, &a[0]); ora_reorder_primary5(opt->T, &a[1]); }
@@ -245,6 +268,7 @@ int ora_sam_pe(const ora_opt_t *opt, const ora_ref_t *ref, const ora_pestat_t pe
 	if (n_pri[0] && n_pri[1] && (o = ora_pair(opt, ref, pes, s, a, (int)id, &subo, &n_sub, z, n_pri)) > 0) {
 		int is_multi[2], q_pe, score_un, q_se[2];
 		char **XA[2];
+		subo_pair = subo;
 		for (i = 0; i < 2; ++i) {
 			for (j = 1; j < n_pri[i]; ++j)
 				if (a[i].a[j].secondary < 0 && a[i].a[j].score >= opt->T) break;
@@ -284,6 +308,14 @@ int ora_sam_pe(const ora_opt_t *opt, const ora_ref_t *ref, const ora_pestat_t pe
 				a[i].a[z[i]].secondary_all = -1;
 			}
 		}
+		if (ora_pe_dump) {
+			int alt[2];
+			for (i = 0; i < 2; ++i) {
+				const ora_reg_t *p = &a[i].a[n_pri[i]];
+				alt[i] = n_pri[i] < a[i].n && !(p->score < opt->T || p->secondary >= 0 || !p->is_alt) ? n_pri[i] : -1;
+			}
+			dump_pair(id, 1, z, alt, q_se, extra_flag, o, subo_pair, n_sub);
+		}
 		if (!(opt->flag & ORA_F_ALL)) {
 			for (i = 0; i < 2; ++i) XA[i] = ora_gen_alt(opt, ref, &a[i], s[i].l_seq, s[i].seq);
 		} else XA[0] = XA[1] = 0;
@@ -317,15 +349,18 @@ int ora_sam_pe(const ora_opt_t *opt, const ora_ref_t *ref, const ora_pestat_t pe
 	return n;
 
 no_pairing:
+	if (o <= 0) subo_pair = subo;                                /* (else set above, before score_un went into subo) */
 	for (i = 0; i < 2; ++i) {
 		int which = -1;
 		if (a[i].n) {
 			if (a[i].a[0].score >= opt->T) which = 0;
 			else if (n_pri[i] < a[i].n && a[i].a[n_pri[i]].score >= opt->T) which = n_pri[i];
 		}
+		z[i] = which;
 		if (which >= 0) h[i] = ora_reg2aln(opt, ref, s[i].l_seq, s[i].seq, &a[i].a[which]);
 		else h[i] = ora_reg2aln(opt, ref, s[i].l_seq, s[i].seq, 0);
 	}
+	if (ora_pe_dump) { const int none[2] = { -1, -1 }, zero[2] = { 0, 0 }; dump_pair(id, 0, z, none, zero, extra_flag, o, subo_pair, n_sub); }
 	if (!(opt->flag & ORA_F_NOPAIRING) && h[0].rid == h[1].rid && h[0].rid >= 0) {
 		int64_t dist;
 		int d = infer_dir(ref->l_pac, a[0].a[0].rb, a[1].a[0].rb, &dist);

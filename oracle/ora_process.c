@@ -81,6 +81,7 @@ void ora_process_seqs(const ora_opt_t *opt, const ora_index_t *idx, int64_t n_pr
 	if (opt->flag & ORA_F_PE) {
 		if (pes0) memcpy(pes, pes0, sizeof pes);
 		else ora_pestat(opt, idx->ref->l_pac, n, w.regs, pes);
+		if (ora_pe_dump) { memcpy(ora_pe_dump->pes, pes, sizeof pes); ora_pe_dump->id0 = n_processed >> 1; }
 	}
 	run_phase(&w, 2, opt->n_threads);
 	free(w.regs);

@@ -13,6 +13,8 @@ the outputs below are data (inputs + expected outputs), never reference source.
   tests/golden/kat_ksw_align.npz   ksw_align2 under other matrices / gap costs / xtra (word kernel as mem_seed_sw uses it)
   tests/golden/kat_dp_wide.npz     ksw_extend2 / ksw_global2 over the whole range of lengths, bands, matrices, gap costs (`make_golden.py dpwide`)
   tests/golden/opt_<set>.sam.gz    SAM bodies of se.fq / pe_[12].fq under non-default options (common.GOLDEN_OPTION_SETS)
+  tests/golden/pelib_<name>_[12].fq.gz, pelib_<name>.sam.gz   the paired-end libraries of tests/pe_cases.py at pe_cases.GOLDEN_PAIRS pairs over the
+                                   suite's 1 Mb genome (simgen seed 11), and the reference's SAM for them (`make_golden.py pelibs`)
 
 `make_golden.py extras` writes only the last two groups (round 2 additions); the older files are left alone.
 """
@@ -172,5 +174,25 @@ def fastq_cases():
             sh(REF, "readfq", str(chunk), *[f"{d}/{x}" for x in files], stdout=f, stderr=subprocess.DEVNULL)
 
 
+def pe_libraries():
+    """pelib_*: every library of tests/pe_cases.py (orientations other than FR, wide inserts, ragged lengths, contig ends) through the
+    reference's mem_process_seqs.  The genome is the one the suite's small_index fixture makes; only reads and SAM are committed."""
+    import pe_cases
+    assert os.path.exists("/root/reference/bwamem.c") and os.access(REF, os.X_OK), "needs the reference build (make -C oracle ref)"
+    os.makedirs(TMP, exist_ok=True)
+    fa = f"{TMP}/g1.fa"
+    bw.make_genome(fa, 11, [600000, 300000, 100000], repeats=True)
+    sh(REF, "index", fa, f"{TMP}/g1")
+    genome = pe_cases.load_genome(fa)
+    for name in pe_cases.LIBRARIES:
+        fq1, fq2, _, _, _ = pe_cases.write_library(genome, name, TMP, pe_cases.golden_pairs(name))
+        with open(f"{TMP}/pelib.sam", "wb") as f:
+            sh(REF, "mem", f"{TMP}/g1", fq1, fq2, stdout=f, stderr=subprocess.DEVNULL)
+        gz(fq1, f"{HERE}/pelib_{name}_1.fq.gz")
+        gz(fq2, f"{HERE}/pelib_{name}_2.fq.gz")
+        gz(f"{TMP}/pelib.sam", f"{HERE}/pelib_{name}.sam.gz")
+    sh("ls", "-la", HERE)
+
+
 if __name__ == "__main__":
-    {"extras": extras, "fastq": fastq_cases, "dpwide": dp_wide}.get(sys.argv[1] if len(sys.argv) > 1 else "", main)()
+    {"extras": extras, "fastq": fastq_cases, "dpwide": dp_wide, "pelibs": pe_libraries}.get(sys.argv[1] if len(sys.argv) > 1 else "", main)()
