@@ -113,6 +113,53 @@ struct Bgzf {
 enum class OutForm { Sam, Bam, BamSorted, Bgzf };
 inline bool is_bam(OutForm f) { return f != OutForm::Sam; }
 
+// What a batch arrives in: bases (codes 0..4 once k_nt4_conv has run), qualities, names, comments and their offsets in HBM, the pinned buffer they
+// travel through, and the event behind the last copy to HBM (stream path).  One type for the context's own batch and for the stream driver's sets.
+struct BatchIn {
+	DevBuf d_seq, d_off, d_qual, d_qual_off, d_names, d_name_off, d_comments, d_comment_off;
+	HostBuf h_stage;
+	hipEvent_t ev = nullptr;             // the copies to HBM are done
+	int n = 0, max_len = 0; int64_t total_bases = 0; bool any_comment = false;
+	// a batch without comments: a null pointer tells the kernels (d_comments itself is kept from batch to batch)
+	const uint8_t *comments() const { return any_comment ? d_comments.as<uint8_t>() : nullptr; }
+	void release()                       // at the end of the owner: the buffers freed, the events destroyed
+	{
+		for (DevBuf *b : { &d_seq, &d_off, &d_qual, &d_qual_off, &d_names, &d_name_off, &d_comments, &d_comment_off }) b->release();
+		h_stage.release();
+		if (ev) (void)hipEventDestroy(ev);
+	}
+};
+
+// What run_final leaves behind: the batch in `form` in d_sam (`total` bytes of text or records; OutForm::Bgzf: of the records the members hold)
+// with the reads' offsets; BamSorted: n_rec keys and n_rec + 1 offsets of the records, the events at the begin of the record table, of the
+// radix sort, of the gather, and at the end; Bgzf: d_tot = [0] the members' bytes, [1] members that left stored (int64 each, in HBM), n_blocks
+// members, the events around the deflate stage; n_stored: d_tot[1] once it has been read back.
+struct BatchOut {
+	DevBuf d_sam, d_sam_off, d_keys, d_rec_off, d_tot;
+	hipEvent_t ev_sort[4] = {}, ev_bgzf[2] = {};
+	int64_t total = 0, n_rec = 0, n_blocks = 0, n_stored = 0;
+	OutForm form = OutForm::Sam;
+	void release()
+	{
+		for (DevBuf *b : { &d_sam, &d_sam_off, &d_keys, &d_rec_off, &d_tot }) b->release();
+		for (hipEvent_t e : ev_sort) if (e) (void)hipEventDestroy(e);
+		for (hipEvent_t e : ev_bgzf) if (e) (void)hipEventDestroy(e);
+	}
+};
+
+// The pinned buffers a BatchOut comes back into -- one per set of the stream driver, two taken in turn for the context's own set (the one-piece
+// entries of bwahip_process_seqs*) -- and the events of the way back (stream path): the write pass has ended / the bytes are in h_sam
+struct PinnedOut {
+	HostBuf h_sam, h_keys, h_rec_off;
+	hipEvent_t ev_written = nullptr, ev_copied = nullptr;
+	void release()
+	{
+		h_sam.release(); h_keys.release(); h_rec_off.release();
+		if (ev_written) (void)hipEventDestroy(ev_written);
+		if (ev_copied) (void)hipEventDestroy(ev_copied);
+	}
+};
+
 struct StreamPipe;                       // final_rt.hip: the second sets of batch buffers the stream driver's three stages work on
 
 struct bwahip_ctx {
@@ -120,13 +167,14 @@ struct bwahip_ctx {
 	BatchText batch_text;
 	BamSort bs;
 	Bgzf bz;
-	DevBuf d_bgzf_tot;                   // the deflated batch in d_sam: [0] its bytes, [1] blocks that left stored (int64 each)
-	int64_t n_bgzf_blocks = 0;
-	hipEvent_t ev_bgzf[2] = {};          // around the deflate stage
-	DevBuf d_skeys, d_rec_off;           // the sorted batch: n_rec keys, n_rec + 1 offsets of the records in d_sam
-	int64_t n_rec = 0;
-	hipEvent_t ev_sort[4] = {};          // begin of the record table, of the radix sort, of the gather, and the end
-	HostBuf h_skeys[2], h_rec_off[2];    // pinned: keys and offsets of bwahip_process_seqs_bam_sorted (taken in turn with h_sam / h_sam2)
+	// The batch of the direct entry points (bwahip_batch_upload / _attach*, bwahip_process_seqs*, the stage dumps) and what run_final makes of it.
+	// Everything that computes goes through `in` / `out`: they point here, except while pipe_compute has them on two of the stream driver's sets.
+	BatchIn own_in;
+	BatchOut own_out;
+	BatchIn *in = &own_in;
+	BatchOut *out = &own_out;
+	PinnedOut pin[2];                    // one-piece output of bwahip_process_seqs_text / _bam / _bam_sorted / _bgzf: taken in turn (plain bwahip_process_seqs: pin[0])
+	int turn = 0;
 	std::vector<int64_t> h_sam_off;      // offsets of the reads' SAM text in h_sam (bwahip_process_seqs / _text)
 	bool external_index = false;
 	bool index_resident = false;         // d_bwt / d_sa / d_pac were filled before ctx_setup (bwahip_init_rccl)
@@ -147,10 +195,8 @@ struct bwahip_ctx {
 	DevBuf d_kmer;                       // the interval table of the BWT search (launch_kmer_table); clones read their source's
 	const bwahip_ctx *share_from = nullptr;   // bwahip_ctx_clone: the context whose index arrays this one reads
 	DevBuf d_sa_dense;                   // the SA table the kernels read when it is denser than the files' (launch_sa_densify); owned by the context that built it
-	// batch state
-	int n_reads = 0, max_len = 0;
-	int64_t total_bases = 0;
-	DevBuf d_seq, d_off, d_seq4, d_smem_heavy, d_raw, d_raw_n;
+	// working set of the batch
+	DevBuf d_seq4, d_smem_heavy, d_raw, d_raw_n;
 	DevBuf d_intv, d_intv_n, d_seed_cnt, d_lrep, d_seed_base, d_seeds, d_scratch;
 	DevBuf d_misc;                       // CNT_SLOTS rows of CNT_N counters (u64), then queue (4 x u32), err (i32)
 	// K3/K4 working set (sized from the seed count of the batch)
@@ -159,7 +205,6 @@ struct bwahip_ctx {
 	DevBuf d_dbg_chains, d_dbg_seeds, d_dbg_chain_n, d_dbg_regs, d_dbg_reg_n, d_flt, d_heavy, d_perm, d_spec_regs, d_spec_items, d_scan, d_chain_big, d_redo, d_big_t, d_dedup, d_cperm;
 	// finalisation on the GPU (final_rt.hip)
 	DevBuf d_ctg_names, d_ctg_name_off, d_ctg_anno, d_ctg_anno_off, d_rg;      // contig names / annotations (SAM RNAME, XR), read-group id
-	DevBuf d_qual, d_qual_off, d_names, d_name_off, d_comments, d_comment_off; // per-batch text inputs of the SAM kernels
 	DevBuf d_fregs, d_fregs2, d_fscr, d_need, d_xa_owner, d_freg_n, d_npri, d_task_n, d_rec_n, d_task_base, d_tasks, d_aln_of_reg, d_alns;
 	DevBuf d_hist, d_pair_tab, d_nb, d_pe_cap, d_pe_base, d_pe_regs, d_pe_n, d_pe_tmp, d_pe_keys, d_pe_idx, d_resc, d_ms_slab, d_pe_read, d_sw_cnt, d_sw_base, d_sw_res, d_sw_tasks, d_sw_info;   // paired-end stages
 	bwahip_pestat_t last_pes[4];         // insert-size statistics of the last paired-end batch
@@ -172,10 +217,8 @@ struct bwahip_ctx {
 	DevBuf d_resc_flag;                  // one byte per pair: mate rescue works on it (finalised by the second k_mark / k_pair launch)
 	DevBuf d_zslab;                      // k_cigar's backtrack slabs
 	DevBuf d_resc_ord;                   // scratch of the rescue list's ordering
-	DevBuf d_pool, d_fmisc, d_fredo, d_bigz, d_rec_list, d_xa_list, d_sam_len, d_sam_off, d_sam;
-	HostBuf h_stage, h_sam, h_sam2;       // pinned staging: batch text in, SAM text out (two buffers taken in turn by bwahip_process_seqs_text)
-	int sam_flip = 0;
-	int64_t total_tasks = 0, total_sam = 0;
+	DevBuf d_pool, d_fmisc, d_fredo, d_bigz, d_rec_list, d_xa_list, d_sam_len;
+	int64_t total_tasks = 0;
 	size_t pool_cap = 0;
 	float final_ms[8] = { 0 };           // k_mark, k_cigar, k_sam(size), k_sam(write) of the last run
 	int intv_cap = 96;                   // current capacity (starts at knobs.intv_cap, grows on overflow)
@@ -212,8 +255,8 @@ inline void stage_rec(std::vector<int64_t> &o, int64_t tag, const std::vector<in
 // pe_stage_stop: paired end only, for bwahip_run_pe_stages -- return once both k_pair passes are done (the stream is idle then), with mem_pair's
 // results per pair in d_pair_dbg; nothing of the output stages runs
 int run_final(bwahip_ctx *c, const bwahip_opt_t *opt, int64_t n_processed, const bwahip_pestat_t *pes0, bool timed, OutForm form, bool host_sam_off = false, bool pe_stage_stop = false);   // regions in HBM -> the batch in `form` in HBM (SE, or PE when opt->flag has MEM_F_PE); host_sam_off: the offsets travel to h_sam_off ahead of the write pass (bwahip_process_seqs)
-// k_bamsort.hip: the records of c->bs.raw (per-read offsets c->d_sam_off, n_reads + 1) in coordinate order into c->d_sam, their keys into
-// c->d_skeys, their offsets into c->d_rec_off; sets c->n_rec.  Queued on c->stream (with two small read-backs awaited in between).
+// k_bamsort.hip: the records of c->bs.raw (per-read offsets c->out->d_sam_off, n_reads + 1) in coordinate order into c->out->d_sam, their keys
+// into c->out->d_keys, their offsets into c->out->d_rec_off; sets c->out->n_rec.  Queued on c->stream (with two small read-backs awaited in between).
 int bam_sort_batch(bwahip_ctx *c, int n_reads, int64_t total);
 // the stable LSD radix sort of bam_sort_batch alone, over c->bs.keys[0] / idx[0] (n items): the result is in keys[*which] / idx[*which]
 int bam_sort_radix(bwahip_ctx *c, int n, int key_bits, int *which);

@@ -92,10 +92,10 @@ static void pestat_from_hist(const bwahip_opt_t *opt, const std::vector<unsigned
 // under them) go to the second stream and are NOT waited for: run_final finalises all other pairs meanwhile and the rescued ones after ev_join.
 static int run_pe_rescue(bwahip_ctx *c, const bwahip_opt_t *opt, const DevOpt &dopt, int64_t n_processed, const bwahip_pestat_t *pes0, PairLaunch &pl, int &n_resc_out)
 {
-	const int n = c->n_reads;
+	const int n = c->in->n;
 	int rc;
 	memset(&pl, 0, sizeof pl);
-	pl.ix = c->ix; pl.opt = dopt; pl.n_reads = n; pl.seq = c->d_seq.as<uint8_t>(); pl.off = c->d_off.as<int64_t>(); pl.n_processed = n_processed;
+	pl.ix = c->ix; pl.opt = dopt; pl.n_reads = n; pl.seq = c->in->d_seq.as<uint8_t>(); pl.off = c->in->d_off.as<int64_t>(); pl.n_processed = n_processed;
 	pl.logtab = c->d_logtab.as<double>();
 	pl.regs = c->d_regs.as<DevReg>(); pl.reg_base = c->d_reg_base.as<int64_t>(); pl.reg_n = c->d_reg_n.as<int>();
 	unsigned long long *fm = c->d_fmisc.as<unsigned long long>();
@@ -168,11 +168,11 @@ static int run_pe_rescue(bwahip_ctx *c, const bwahip_opt_t *opt, const DevOpt &d
 	if (n_resc > 0 || n_sw_tasks > 0 || n_sw_tasks8 > 0) {
 		HIP_TRY(hipEventRecord(c->ev_fork, c->stream));
 		HIP_TRY(hipStreamWaitEvent(c->stream2, c->ev_fork, 0));
-		if ((rc = launch_matesw_sw(pl, n_sw_tasks, n_sw_tasks8, c->max_len, c->stream2))) return rc;   // the alignments against the unrescued lists, all at once
+		if ((rc = launch_matesw_sw(pl, n_sw_tasks, n_sw_tasks8, c->in->max_len, c->stream2))) return rc;   // the alignments against the unrescued lists, all at once
 		if (n_resc > 0) {
 			if ((rc = c->d_resc_ord.ensure(((size_t)3 * n_resc + 8) * 4)) || (rc = launch_resc_order(pl, n_resc, c->d_resc_ord.as<int>(), c->stream2))) return rc;
 			const int grid = std::min(n_resc, 2048);
-			pl.slab_stride = (matesw_slab_bytes(widest + c->max_len) + 255) & ~(size_t)255;
+			pl.slab_stride = (matesw_slab_bytes(widest + c->in->max_len) + 255) & ~(size_t)255;
 			if ((rc = c->d_ms_slab.ensure(pl.slab_stride * (size_t)grid))) return rc;
 			pl.slab = c->d_ms_slab.as<uint8_t>();
 			HIP_TRY(hipMemsetAsync(pl.queue, 0, 16, c->stream2));
@@ -191,12 +191,12 @@ int run_final(bwahip_ctx *c, const bwahip_opt_t *opt, int64_t n_processed, const
 		const bool pe_ = (opt->flag & BWAHIP_F_PE) != 0;
 		return is_bam(form) ? (pe_ ? launch_bam_pe(fl, write, c->stream, lo, hi) : launch_bam(fl, write, c->stream, lo, hi)) : (pe_ ? launch_sam_pe(fl, write, c->stream, lo, hi) : launch_sam(fl, write, c->stream, lo, hi));
 	};
-	const int n = c->n_reads;
+	const int n = c->in->n;
 	const bool pe = (opt->flag & BWAHIP_F_PE) != 0;
-	c->total_sam = 0; c->total_tasks = 0; c->n_rec = 0;
+	BatchOut &o = *c->out;
+	o.total = 0; o.n_rec = 0; o.n_blocks = 0; o.n_stored = 0; o.form = form; c->total_tasks = 0;
 	const bool sorted = form == OutForm::BamSorted;               // the records leave in coordinate order: written to a scratch buffer, sorted into d_sam
 	const bool bgzf = form == OutForm::Bgzf;                      // the records leave as BGZF members: written to the same scratch buffer, deflated into d_sam
-	c->n_bgzf_blocks = 0;
 	if (n == 0) return 0;
 	if (pe && (n & 1)) return BWAHIP_EINVAL;
 	int rc;
@@ -210,7 +210,7 @@ int run_final(bwahip_ctx *c, const bwahip_opt_t *opt, int64_t n_processed, const
 	if ((rc = c->d_fregs.ensure(R * sizeof(FinReg))) || (rc = c->d_fregs2.ensure(R * sizeof(FinReg))) || (rc = c->d_fscr.ensure(R * 16)) || (rc = c->d_need.ensure(R)) ||
 	    (rc = c->d_xa_owner.ensure(R * 4)) || (rc = c->d_aln_of_reg.ensure(R * 4)) || (rc = c->d_rec_list.ensure(R * 8)) || (rc = c->d_xa_list.ensure(R * 8)) ||
 	    (rc = c->d_freg_n.ensure((size_t)n * 4)) || (rc = c->d_npri.ensure((size_t)n * 4)) || (rc = c->d_task_n.ensure((size_t)n * 4)) || (rc = c->d_rec_n.ensure((size_t)n * 4)) ||
-	    (rc = c->d_task_base.ensure((size_t)(n + 1) * 8)) || (rc = c->d_sam_len.ensure((size_t)n * 4)) || (rc = c->d_sam_off.ensure((size_t)(n + 1) * 8))) return rc;
+	    (rc = c->d_task_base.ensure((size_t)(n + 1) * 8)) || (rc = c->d_sam_len.ensure((size_t)n * 4)) || (rc = o.d_sam_off.ensure((size_t)(n + 1) * 8))) return rc;
 	// rg id
 	{
 		std::string rg = c->rg_id;
@@ -219,7 +219,7 @@ int run_final(bwahip_ctx *c, const bwahip_opt_t *opt, int64_t n_processed, const
 	}
 	FinLaunch f;
 	memset(&f, 0, sizeof f);
-	f.ix = c->ix; f.opt = make_dev_opt(opt); f.n_reads = n; f.seq = c->d_seq.as<uint8_t>(); f.off = c->d_off.as<int64_t>();
+	f.ix = c->ix; f.opt = make_dev_opt(opt); f.n_reads = n; f.seq = c->in->d_seq.as<uint8_t>(); f.off = c->in->d_off.as<int64_t>();
 	f.n_processed = n_processed; f.logtab = c->d_logtab.as<double>();
 	f.regs = c->d_regs.as<DevReg>(); f.reg_base = c->d_reg_base.as<int64_t>(); f.reg_n = c->d_reg_n.as<int>();
 	if (pe) { f.regs = c->d_pe_regs.as<DevReg>(); f.reg_base = c->d_pe_base.as<int64_t>(); f.reg_n = c->d_pe_n.as<int>(); }
@@ -229,11 +229,11 @@ int run_final(bwahip_ctx *c, const bwahip_opt_t *opt, int64_t n_processed, const
 	f.rec_list = c->d_rec_list.as<const DevAln*>(); f.xa_list = c->d_xa_list.as<const DevAln*>();
 	unsigned long long *pool_head = c->d_fmisc.as<unsigned long long>();
 	f.pool_head = pool_head; f.redo_n = (int*)(pool_head + 1); f.err = (int*)(pool_head + 2);
-	f.qual = c->d_qual.as<uint8_t>(); f.qual_off = c->d_qual_off.as<int64_t>(); f.names = c->d_names.as<uint8_t>(); f.name_off = c->d_name_off.as<int64_t>();
-	f.comments = c->d_comments.p ? c->d_comments.as<uint8_t>() : nullptr; f.comment_off = c->d_comment_off.as<int64_t>();
+	f.qual = c->in->d_qual.as<uint8_t>(); f.qual_off = c->in->d_qual_off.as<int64_t>(); f.names = c->in->d_names.as<uint8_t>(); f.name_off = c->in->d_name_off.as<int64_t>();
+	f.comments = c->in->comments(); f.comment_off = c->in->d_comment_off.as<int64_t>();
 	f.ctg_names = c->d_ctg_names.as<uint8_t>(); f.ctg_name_off = c->d_ctg_name_off.as<int>(); f.ctg_anno = c->d_ctg_anno.as<uint8_t>(); f.ctg_anno_off = c->d_ctg_anno_off.as<int>();
 	f.rg_id = c->d_rg.as<uint8_t>(); f.rg_len = (int)c->rg_id.size();
-	f.sam_len = c->d_sam_len.as<int>(); f.sam_off = c->d_sam_off.as<int64_t>();
+	f.sam_len = c->d_sam_len.as<int>(); f.sam_off = o.d_sam_off.as<int64_t>();
 	if (timed) HIP_TRY(hipEventRecord(c->ev[15], c->stream));
 	// paired end: first every pair mate rescue does not touch, while the rescue kernels run on the second stream; then, once those are done, their pairs
 	if (pe) { f.resc_flag = pl.resc_flag; f.resc_pairs = pl.resc_list; f.subset = 1; }
@@ -290,8 +290,8 @@ int run_final(bwahip_ctx *c, const bwahip_opt_t *opt, int64_t n_processed, const
 		f.pool = c->d_pool.as<uint8_t>(); f.pool_cap = want_pool;
 		HIP_TRY(hipMemsetAsync(c->d_fmisc.p, 0, 120, c->stream));   // pool head, redo count, error; the task-list lengths at +120 stay
 		{ const unsigned long long head0 = (unsigned long long)Tn * 64; HIP_TRY(hipMemcpyAsync(c->d_fmisc.p, &head0, 8, hipMemcpyHostToDevice, c->stream)); }   // the shared tail starts behind the slots
-		if (n_list[1] > 0) { if ((rc = c->d_zslab.ensure(cigar_zslab_bytes(c->max_len, n_list[1])))) return rc; f.zslab = c->d_zslab.as<unsigned>(); }
-		if ((rc = launch_cigar(f, n_list[0], n_list[1], c->max_len, c->stream, c->stream2, c->ev_fork, c->ev_join))) return rc;
+		if (n_list[1] > 0) { if ((rc = c->d_zslab.ensure(cigar_zslab_bytes(c->in->max_len, n_list[1])))) return rc; f.zslab = c->d_zslab.as<unsigned>(); }
+		if ((rc = launch_cigar(f, n_list[0], n_list[1], c->in->max_len, c->stream, c->stream2, c->ev_fork, c->ev_join))) return rc;
 		int h[6] = { 0 };
 		HIP_TRY(hipMemcpyAsync(h, c->d_fmisc.p, 24, hipMemcpyDeviceToHost, c->stream));
 		HIP_TRY(hipStreamSynchronize(c->stream));
@@ -315,18 +315,18 @@ int run_final(bwahip_ctx *c, const bwahip_opt_t *opt, int64_t n_processed, const
 	}
 	if (timed) HIP_TRY(hipEventRecord(c->ev[17], c->stream));
 	if ((rc = launch_out(f, false, 0, -1))) return rc;
-	if ((rc = launch_scan(c->d_sam_len.as<int>(), c->d_sam_off.as<int64_t>(), n, c->d_scan, c->stream))) return rc;
+	if ((rc = launch_scan(c->d_sam_len.as<int>(), o.d_sam_off.as<int64_t>(), n, c->d_scan, c->stream))) return rc;
 	if (timed) HIP_TRY(hipEventRecord(c->ev[18], c->stream));
 	int64_t total = 0;
-	HIP_TRY(hipMemcpyAsync(&total, c->d_sam_off.as<int64_t>() + n, 8, hipMemcpyDeviceToHost, c->stream));
+	HIP_TRY(hipMemcpyAsync(&total, o.d_sam_off.as<int64_t>() + n, 8, hipMemcpyDeviceToHost, c->stream));
 	HIP_TRY(hipStreamSynchronize(c->stream));
-	c->total_sam = total;
-	if ((rc = c->d_sam.ensure((size_t)total + (bgzf ? (size_t)bgzf_blocks(total) * 31 : 0) + 64))) return rc;   // bgzf: the bound bgzf_deflate asks for
-	f.sam = c->d_sam.as<uint8_t>();
+	o.total = total; if (bgzf) o.n_blocks = bgzf_blocks(total);
+	if ((rc = o.d_sam.ensure((size_t)total + (bgzf ? (size_t)bgzf_blocks(total) * 31 : 0) + 64))) return rc;   // bgzf: the bound bgzf_deflate asks for
+	f.sam = o.d_sam.as<uint8_t>();
 	if (sorted || bgzf) { if ((rc = c->bs.raw.ensure((size_t)total + 64))) return rc; f.sam = c->bs.raw.as<uint8_t>(); }
 	if (host_sam_off) {                                         // bwahip_process_seqs: the offsets travel ahead of the write pass
 		c->h_sam_off.resize((size_t)n + 1);
-		HIP_TRY(hipMemcpyAsync(c->h_sam_off.data(), c->d_sam_off.p, (size_t)(n + 1) * 8, hipMemcpyDeviceToHost, c->stream));
+		HIP_TRY(hipMemcpyAsync(c->h_sam_off.data(), o.d_sam_off.p, (size_t)(n + 1) * 8, hipMemcpyDeviceToHost, c->stream));
 	}
 	// the write pass in two halves (cut at an even read: mates stay together) with an event between them: a caller that downloads the text
 	// (bwahip_process_seqs) starts on the first half while the second is being written
@@ -337,15 +337,15 @@ int run_final(bwahip_ctx *c, const bwahip_opt_t *opt, int64_t n_processed, const
 	if (timed) HIP_TRY(hipEventRecord(c->ev[19], c->stream));
 	if (sorted && (rc = bam_sort_batch(c, n, total))) return rc;
 	if (bgzf) {                                                   // the deflate stage, queued behind the write pass
-		for (auto &e : c->ev_bgzf) if (!e) HIP_TRY(hipEventCreate(&e));
-		if ((rc = c->d_bgzf_tot.ensure(16))) return rc;
-		HIP_TRY(hipEventRecord(c->ev_bgzf[0], c->stream));
-		if ((rc = bgzf_deflate(c, c->bs.raw.as<uint8_t>(), total, c->d_sam, c->d_bgzf_tot.as<int64_t>(), c->stream))) return rc;
-		HIP_TRY(hipEventRecord(c->ev_bgzf[1], c->stream));
+		for (auto &e : o.ev_bgzf) if (!e) HIP_TRY(hipEventCreate(&e));
+		if ((rc = o.d_tot.ensure(16))) return rc;
+		HIP_TRY(hipEventRecord(o.ev_bgzf[0], c->stream));
+		if ((rc = bgzf_deflate(c, c->bs.raw.as<uint8_t>(), total, o.d_sam, o.d_tot.as<int64_t>(), c->stream))) return rc;
+		HIP_TRY(hipEventRecord(o.ev_bgzf[1], c->stream));
 	}
 	if (timed) {
 		HIP_TRY(hipStreamSynchronize(c->stream));
-		if (sorted) for (int k = 0; k < 3; ++k) HIP_TRY(hipEventElapsedTime(&c->bs.ms[k], c->ev_sort[k], c->ev_sort[k + 1]));
+		if (sorted) for (int k = 0; k < 3; ++k) HIP_TRY(hipEventElapsedTime(&c->bs.ms[k], o.ev_sort[k], o.ev_sort[k + 1]));
 		HIP_TRY(hipEventElapsedTime(&c->final_ms[0], c->ev[15], c->ev[16]));
 		HIP_TRY(hipEventElapsedTime(&c->final_ms[1], c->ev[16], c->ev[17]));
 		HIP_TRY(hipEventElapsedTime(&c->final_ms[2], c->ev[17], c->ev[18]));
@@ -444,29 +444,29 @@ static int stage_codes(bwahip_ctx *c, int nt, int n, bwahip_seq_t *seqs, BatchTe
 	// PCIe speed instead of through pageable memory
 	t.sz_codes = ((size_t)t.off[n] + 64) & ~(size_t)63; t.sz_qual = ((size_t)t.qtot + 127) & ~(size_t)63; t.sz_names = ((size_t)t.noff[n] + 127) & ~(size_t)63;
 	t.sz_comm = t.any_comment ? ((size_t)t.coff[n] + 127) & ~(size_t)63 : 0;
-	int rc = c->h_stage.ensure(t.sz_codes + t.sz_qual + t.sz_names + t.sz_comm);
+	int rc = c->in->h_stage.ensure(t.sz_codes + t.sz_qual + t.sz_names + t.sz_comm);
 	if (rc) return rc;
 	// device buffers of the text are sized here, on the calling thread, so that the helper only copies
-	if ((rc = c->d_qual.ensure(t.sz_qual)) || (rc = c->d_qual_off.ensure((size_t)n * 8 + 16)) || (rc = c->d_names.ensure(t.sz_names)) ||
-	    (rc = c->d_name_off.ensure((size_t)(n + 1) * 8)) || (rc = c->d_comment_off.ensure((size_t)(n + 1) * 8))) return rc;
-	if (t.any_comment) { if ((rc = c->d_comments.ensure(t.sz_comm))) return rc; }
-	else c->d_comments.release();
+	if ((rc = c->in->d_qual.ensure(t.sz_qual)) || (rc = c->in->d_qual_off.ensure((size_t)n * 8 + 16)) || (rc = c->in->d_names.ensure(t.sz_names)) ||
+	    (rc = c->in->d_name_off.ensure((size_t)(n + 1) * 8)) || (rc = c->in->d_comment_off.ensure((size_t)(n + 1) * 8))) return rc;
+	c->in->any_comment = t.any_comment;
+	if (t.any_comment && (rc = c->in->d_comments.ensure(t.sz_comm))) return rc;
 	// the bases travel as the caller wrote them (ASCII or codes) and are turned into codes in HBM (k_nt4: the same table look-up as
 	// bwamem.c:1067-1068); the caller's own arrays are converted in place by the helper thread while the hot path runs
 	const double t2 = now();
-	uint8_t *codes = (uint8_t*)c->h_stage.p;
+	uint8_t *codes = (uint8_t*)c->in->h_stage.p;
 	par_for_chunks(n, nt, [&](int64_t b, int64_t e) { for (int64_t i = b; i < e; ++i) memcpy(codes + t.off[i], seqs[i].seq, (size_t)seqs[i].l_seq); });
 	const double t3 = now();
 	if ((rc = bwahip_batch_upload(c, n, codes, t.off.data()))) return rc;
 	if (c->knobs.e2e_log) fprintf(stderr, "[bwahip] stage_codes: offsets %.1f ms, buffers %.1f ms, gather %.1f ms, upload %.1f ms\n", (t1 - t0) * 1e3, (t2 - t1) * 1e3, (t3 - t2) * 1e3, (now() - t3) * 1e3);
-	return launch_nt4(c->d_seq.as<uint8_t>(), c->total_bases, c->stream);
+	return launch_nt4(c->in->d_seq.as<uint8_t>(), c->in->total_bases, c->stream);
 }
 
 // helper thread: the text of the batch into the pinned buffer and on to HBM (copy stream); returns when the copies are done
 static int stage_text(bwahip_ctx *c, int nt, int n, bwahip_seq_t *seqs, const BatchText &t)
 {
 	HIP_TRY(hipSetDevice(c->device));
-	uint8_t *qual = (uint8_t*)c->h_stage.p + t.sz_codes, *names = qual + t.sz_qual, *comments = names + t.sz_names;
+	uint8_t *qual = (uint8_t*)c->in->h_stage.p + t.sz_codes, *names = qual + t.sz_qual, *comments = names + t.sz_names;
 	memset(qual + (size_t)t.qtot, 0, t.sz_qual - (size_t)t.qtot); memset(names + (size_t)t.noff[n], 0, t.sz_names - (size_t)t.noff[n]);
 	if (t.any_comment) memset(comments + (size_t)t.coff[n], 0, t.sz_comm - (size_t)t.coff[n]);
 	par_for_chunks(n, nt, [&](int64_t b, int64_t e) {
@@ -479,12 +479,12 @@ static int stage_text(bwahip_ctx *c, int nt, int n, bwahip_seq_t *seqs, const Ba
 		}
 	});
 	hipStream_t st = c->stream_copy;
-	HIP_TRY(hipMemcpyAsync(c->d_qual.p, qual, t.sz_qual, hipMemcpyHostToDevice, st));
-	if (n) HIP_TRY(hipMemcpyAsync(c->d_qual_off.p, t.qoff.data(), (size_t)n * 8, hipMemcpyHostToDevice, st));
-	HIP_TRY(hipMemcpyAsync(c->d_names.p, names, t.sz_names, hipMemcpyHostToDevice, st));
-	HIP_TRY(hipMemcpyAsync(c->d_name_off.p, t.noff.data(), (size_t)(n + 1) * 8, hipMemcpyHostToDevice, st));
-	HIP_TRY(hipMemcpyAsync(c->d_comment_off.p, t.coff.data(), (size_t)(n + 1) * 8, hipMemcpyHostToDevice, st));
-	if (t.any_comment) HIP_TRY(hipMemcpyAsync(c->d_comments.p, comments, t.sz_comm, hipMemcpyHostToDevice, st));
+	HIP_TRY(hipMemcpyAsync(c->in->d_qual.p, qual, t.sz_qual, hipMemcpyHostToDevice, st));
+	if (n) HIP_TRY(hipMemcpyAsync(c->in->d_qual_off.p, t.qoff.data(), (size_t)n * 8, hipMemcpyHostToDevice, st));
+	HIP_TRY(hipMemcpyAsync(c->in->d_names.p, names, t.sz_names, hipMemcpyHostToDevice, st));
+	HIP_TRY(hipMemcpyAsync(c->in->d_name_off.p, t.noff.data(), (size_t)(n + 1) * 8, hipMemcpyHostToDevice, st));
+	HIP_TRY(hipMemcpyAsync(c->in->d_comment_off.p, t.coff.data(), (size_t)(n + 1) * 8, hipMemcpyHostToDevice, st));
+	if (t.any_comment) HIP_TRY(hipMemcpyAsync(c->in->d_comments.p, comments, t.sz_comm, hipMemcpyHostToDevice, st));
 	HIP_TRY(hipStreamSynchronize(st));
 	return 0;
 }
@@ -503,10 +503,11 @@ struct SeqsOut {
 template <class More>
 static int download_piece(bwahip_ctx *ctx, int64_t bytes, int n, bwahip_seq_t *seqs, int nt, const SeqsOut &out, More more)
 {
-	HostBuf &hb = (ctx->sam_flip ^= 1) ? ctx->h_sam2 : ctx->h_sam;
+	PinnedOut &pin = ctx->pin[ctx->turn ^= 1];
+	HostBuf &hb = pin.h_sam;
 	int rc;
-	if ((rc = hb.ensure((size_t)bytes + 1)) || (rc = more())) return rc;
-	if (bytes) HIP_TRY(hipMemcpyAsync(hb.p, ctx->d_sam.p, (size_t)bytes, hipMemcpyDeviceToHost, ctx->stream));
+	if ((rc = hb.ensure((size_t)bytes + 1)) || (rc = more(pin))) return rc;
+	if (bytes) HIP_TRY(hipMemcpyAsync(hb.p, ctx->out->d_sam.p, (size_t)bytes, hipMemcpyDeviceToHost, ctx->stream));
 	HIP_TRY(hipStreamSynchronize(ctx->stream));
 	HIP_TRY(hipStreamSynchronize(ctx->stream_copy));
 	par_for_chunks(n, nt, [&](int64_t b, int64_t e) { for (int64_t i = b; i < e; ++i) seqs[i].sam = nullptr; });
@@ -551,24 +552,23 @@ static int process_seqs_impl(bwahip_ctx *ctx, const bwahip_opt_t *opt, int64_t n
 	if ((rc = run_final(ctx, opt, n_processed, pes0, false, out.form, true))) return rc;
 	if (bz) {                                                     // the members in one piece: their total was left in HBM by the deflate stage
 		int64_t tot[2] = { 0, 0 };
-		HIP_TRY(hipMemcpyAsync(tot, ctx->d_bgzf_tot.p, 16, hipMemcpyDeviceToHost, ctx->stream));
+		HIP_TRY(hipMemcpyAsync(tot, ctx->out->d_tot.p, 16, hipMemcpyDeviceToHost, ctx->stream));
 		HIP_TRY(hipStreamSynchronize(ctx->stream));
-		if ((rc = download_piece(ctx, tot[0], n, seqs, nt, out, [] { return 0; }))) return rc;
-		*out.raw_len = ctx->total_sam; *out.n_blocks = ctx->n_bgzf_blocks;
+		if ((rc = download_piece(ctx, tot[0], n, seqs, nt, out, [](PinnedOut&) { return 0; }))) return rc;
+		*out.raw_len = ctx->out->total; *out.n_blocks = ctx->out->n_blocks;
 		return 0;
 	}
 	if (sorted) {                                                 // records, keys and offsets in one piece each
-		const int64_t nr = ctx->n_rec;
-		rc = download_piece(ctx, ctx->total_sam, n, seqs, nt, out, [&]() -> int {
-			HostBuf &hk = ctx->h_skeys[ctx->sam_flip], &ho = ctx->h_rec_off[ctx->sam_flip];
+		const int64_t nr = ctx->out->n_rec;
+		rc = download_piece(ctx, ctx->out->total, n, seqs, nt, out, [&](PinnedOut &pin) -> int {
 			int r;
-			if ((r = hk.ensure((size_t)(nr ? nr : 1) * 8)) || (r = ho.ensure((size_t)(nr + 1) * 8))) return r;
-			if (nr) HIP_TRY(hipMemcpyAsync(hk.p, ctx->d_skeys.p, (size_t)nr * 8, hipMemcpyDeviceToHost, ctx->stream));
-			HIP_TRY(hipMemcpyAsync(ho.p, ctx->d_rec_off.p, (size_t)(nr + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
+			if ((r = pin.h_keys.ensure((size_t)(nr ? nr : 1) * 8)) || (r = pin.h_rec_off.ensure((size_t)(nr + 1) * 8))) return r;
+			if (nr) HIP_TRY(hipMemcpyAsync(pin.h_keys.p, ctx->out->d_keys.p, (size_t)nr * 8, hipMemcpyDeviceToHost, ctx->stream));
+			HIP_TRY(hipMemcpyAsync(pin.h_rec_off.p, ctx->out->d_rec_off.p, (size_t)(nr + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
 			return 0;
 		});
 		if (rc) return rc;
-		*out.keys = (const uint64_t*)ctx->h_skeys[ctx->sam_flip].p; *out.rec_off = (const int64_t*)ctx->h_rec_off[ctx->sam_flip].p; *out.n_rec = nr;
+		*out.keys = (const uint64_t*)ctx->pin[ctx->turn].h_keys.p; *out.rec_off = (const int64_t*)ctx->pin[ctx->turn].h_rec_off.p; *out.n_rec = nr;
 		return 0;
 	}
 	// SAM text back through the pinned buffer.  run_final wrote it in two halves and sent the offsets ahead: once the first half is written
@@ -576,8 +576,8 @@ static int process_seqs_impl(bwahip_ctx *ctx, const bwahip_opt_t *opt, int64_t n
 	// while slice k+1 travels, the host threads cut slice k into one malloc()ed string per read, which is what the reference's contract wants
 	// (bwamem.c:1054).  (The context's streams are non-blocking: a plain hipMemcpy would not wait for the SAM kernels.)
 	std::vector<int64_t> &soff = ctx->h_sam_off;
-	HostBuf &hs = out.text && (ctx->sam_flip ^= 1) ? ctx->h_sam2 : ctx->h_sam;   // one-piece callers: the text stays valid until the next-but-one call
-	if ((rc = hs.ensure((size_t)ctx->total_sam + 1))) return rc;
+	HostBuf &hs = ctx->pin[out.text ? (ctx->turn ^= 1) : 0].h_sam;   // one-piece callers: the text stays valid until the next-but-one call
+	if ((rc = hs.ensure((size_t)ctx->out->total + 1))) return rc;
 	char *text = (char*)hs.p;
 	HIP_TRY(hipEventSynchronize(ctx->ev_sam_half));               // first half written; the offsets arrived before that
 	const int half = ctx->sam_half_reads;
@@ -587,7 +587,7 @@ static int process_seqs_impl(bwahip_ctx *ctx, const bwahip_opt_t *opt, int64_t n
 	for (int k = 0; k <= SLICES / 2; ++k) sl_beg[SLICES / 2 + k] = half + (int64_t)(n - half) * k / (SLICES / 2);
 	auto copy_slice = [&](int k, hipStream_t st) -> int {
 		const int64_t b = soff[sl_beg[k]], e = soff[sl_beg[k + 1]];
-		if (e > b) HIP_TRY(hipMemcpyAsync(text + b, (const char*)ctx->d_sam.p + b, (size_t)(e - b), hipMemcpyDeviceToHost, st));
+		if (e > b) HIP_TRY(hipMemcpyAsync(text + b, (const char*)ctx->out->d_sam.p + b, (size_t)(e - b), hipMemcpyDeviceToHost, st));
 		HIP_TRY(hipEventRecord(ctx->ev_slice[k], st));
 		return 0;
 	};
@@ -598,12 +598,12 @@ static int process_seqs_impl(bwahip_ctx *ctx, const bwahip_opt_t *opt, int64_t n
 		HIP_TRY(hipStreamSynchronize(ctx->stream_copy));
 		HIP_TRY(hipStreamSynchronize(ctx->stream));
 		const double t4 = now();
-		text[ctx->total_sam] = 0;
-		*out.text = text; *out.len = ctx->total_sam; if (out.off) *out.off = soff.data();
+		text[ctx->out->total] = 0;
+		*out.text = text; *out.len = ctx->out->total; if (out.off) *out.off = soff.data();
 		par_for_chunks(n, nt, [&](int64_t b, int64_t e) { for (int64_t i = b; i < e; ++i) seqs[i].sam = nullptr; });
 		if (verbose || ctx->knobs.e2e_log)
 			fprintf(stderr, "[bwahip] process_seqs_text %d reads: codes gather+upload %.1f ms, hot path (text upload beside it) %.1f ms, finalisation+SAM on GPU and download %.1f ms (%lld bytes), rest %.1f ms\n",
-			        n, (t1 - t0) * 1e3, (t2 - t1) * 1e3, (t4 - t2) * 1e3, (long long)ctx->total_sam, (now() - t4) * 1e3);
+			        n, (t1 - t0) * 1e3, (t2 - t1) * 1e3, (t4 - t2) * 1e3, (long long)ctx->out->total, (now() - t4) * 1e3);
 		return 0;
 	}
 	const double t3 = now();
@@ -628,7 +628,7 @@ static int process_seqs_impl(bwahip_ctx *ctx, const bwahip_opt_t *opt, int64_t n
 	HIP_TRY(hipStreamSynchronize(ctx->stream));
 	if (verbose || ctx->knobs.e2e_log)
 		fprintf(stderr, "[bwahip] process_seqs %d reads: codes gather+upload %.1f ms, hot path (text upload beside it) %.1f ms, finalisation+SAM on GPU %.1f ms (%lld bytes), download + per-read strings %.1f ms\n",
-		        n, (t1 - t0) * 1e3, (t2 - t1) * 1e3, (t3 - t2) * 1e3, (long long)ctx->total_sam, (now() - t3) * 1e3);
+		        n, (t1 - t0) * 1e3, (t2 - t1) * 1e3, (t3 - t2) * 1e3, (long long)ctx->out->total, (now() - t3) * 1e3);
 	if (hip_bad) return BWAHIP_ENODEV;
 	return oom ? BWAHIP_ENOMEM : 0;
 }
@@ -814,37 +814,15 @@ struct StagePool {
 	}
 };
 
-struct PipeIn {
-	DevBuf d_seq, d_off, d_qual, d_qual_off, d_names, d_name_off, d_comments, d_comment_off;
-	HostBuf h_stage;                     // pinned: the four offset tables, then codes | qualities | names | comments
-	hipEvent_t ev = nullptr;             // the copies to HBM are done
-	int n = 0, max_len = 0; int64_t total_bases = 0; bool any_comment = false;
-};
-struct PipeOut {
-	DevBuf d_sam, d_sam_off;
-	HostBuf h_sam;
-	hipEvent_t ev_written = nullptr, ev_copied = nullptr;   // the write pass has ended / the bytes are in h_sam
-	int64_t total = 0;
-	// coordinate-sorted BAM: the keys and offsets of the set's records, and the events around the sort stage that produced them
-	DevBuf d_keys, d_rec_off;
-	HostBuf h_keys, h_rec_off;
-	hipEvent_t ev_sort[4] = {};
-	int64_t n_rec = 0;
-	OutForm form = OutForm::Sam;         // what pipe_compute left in the set
-	// BGZF members: their total and the stored count in HBM, the events around the deflate stage, the records' bytes
-	DevBuf d_tot;
-	hipEvent_t ev_bgzf[2] = {};
-	int64_t raw_total = 0, n_blocks = 0, n_stored = 0;
-};
-
 // the GPU time of the sort stage that filled the set (record table, radix sort, gather)
-double sort_stage_ms(const PipeOut &o) { float ms = 0; if (o.n_rec && o.ev_sort[0] && hipEventElapsedTime(&ms, o.ev_sort[0], o.ev_sort[3]) != hipSuccess) ms = 0; return ms; }
+double sort_stage_ms(const BatchOut &o) { float ms = 0; if (o.n_rec && o.ev_sort[0] && hipEventElapsedTime(&ms, o.ev_sort[0], o.ev_sort[3]) != hipSuccess) ms = 0; return ms; }
 
 } // namespace
 
 struct StreamPipe {
-	PipeIn in[PIPE_SETS];
-	PipeOut out[PIPE_SETS];
+	BatchIn in[PIPE_SETS];
+	BatchOut out[PIPE_SETS];
+	PinnedOut pin[PIPE_SETS];
 	StagePool pool;
 };
 
@@ -857,7 +835,7 @@ int pipe_open(bwahip_ctx *c, int n_threads)
 	if (!c->pipe) {
 		c->pipe = new StreamPipe;
 		for (auto &s : c->pipe->in) HIP_TRY(hipEventCreateWithFlags(&s.ev, hipEventDisableTiming));
-		for (auto &s : c->pipe->out) { HIP_TRY(hipEventCreateWithFlags(&s.ev_written, hipEventDisableTiming)); HIP_TRY(hipEventCreateWithFlags(&s.ev_copied, hipEventDisableTiming)); }
+		for (auto &s : c->pipe->pin) { HIP_TRY(hipEventCreateWithFlags(&s.ev_written, hipEventDisableTiming)); HIP_TRY(hipEventCreateWithFlags(&s.ev_copied, hipEventDisableTiming)); }
 	}
 	c->pipe->pool.start(n_threads > 1 ? n_threads : 1);
 	return 0;
@@ -874,20 +852,9 @@ void pipe_close(bwahip_ctx *c)
 void pipe_destroy(bwahip_ctx *c)
 {
 	if (!c->pipe) return;
-	for (auto &s : c->pipe->in) {
-		for (DevBuf *b : { &s.d_seq, &s.d_off, &s.d_qual, &s.d_qual_off, &s.d_names, &s.d_name_off, &s.d_comments, &s.d_comment_off }) b->release();
-		s.h_stage.release();
-		if (s.ev) (void)hipEventDestroy(s.ev);
-	}
-	for (auto &s : c->pipe->out) {
-		s.d_sam.release(); s.d_sam_off.release(); s.h_sam.release();
-		s.d_keys.release(); s.d_rec_off.release(); s.h_keys.release(); s.h_rec_off.release();
-		for (auto &e : s.ev_sort) if (e) (void)hipEventDestroy(e);
-		s.d_tot.release();
-		for (auto &e : s.ev_bgzf) if (e) (void)hipEventDestroy(e);
-		if (s.ev_written) (void)hipEventDestroy(s.ev_written);
-		if (s.ev_copied) (void)hipEventDestroy(s.ev_copied);
-	}
+	for (auto &s : c->pipe->in) s.release();
+	for (auto &s : c->pipe->out) s.release();
+	for (auto &s : c->pipe->pin) s.release();
 	delete c->pipe;
 	c->pipe = nullptr;
 }
@@ -903,7 +870,7 @@ int pipe_stage_in(bwahip_ctx *c, int in, const bwahip_opt_t *opt, int n, const b
 	if (!c->knobs.gpu_final || (pe && !c->knobs.gpu_pair)) return BWAHIP_EINVAL;   // the one-piece output exists on the GPU path only
 	if (is_bam(form)) { const int rc_bam = bam_check_reads(n, seqs); if (rc_bam) return rc_bam; }
 	HIP_TRY(hipSetDevice(c->device));
-	PipeIn &s = c->pipe->in[in];
+	BatchIn &s = c->pipe->in[in];
 	StagePool &pool = c->pipe->pool;
 	const int C = n >= 4096 ? pool.size() : 1;
 	struct Tot { int64_t seq = 0, qual = 0, name = 0, comm = 0; int bad = 0, any_comm = 0, max_len = 0, long_read = -1, name_diff = 0; char pad[12]; };
@@ -981,64 +948,51 @@ int pipe_compute(bwahip_ctx *c, int in, int out, const bwahip_opt_t *opt, int64_
 {
 	if (!c || !c->pipe || in < 0 || in >= PIPE_SETS || out < 0 || out >= PIPE_SETS || !opt) return BWAHIP_EINVAL;
 	HIP_TRY(hipSetDevice(c->device));
-	PipeIn &s = c->pipe->in[in];
-	PipeOut &o = c->pipe->out[out];
-	// run_pipeline and run_final work on the context's own members: the two sets take their place for this batch, and go back whatever happens
-	DevBuf no_comments;
-	auto exchange = [&] {
-		std::swap(c->d_seq, s.d_seq); std::swap(c->d_off, s.d_off); std::swap(c->d_qual, s.d_qual); std::swap(c->d_qual_off, s.d_qual_off);
-		std::swap(c->d_names, s.d_names); std::swap(c->d_name_off, s.d_name_off); std::swap(c->d_comment_off, s.d_comment_off);
-		std::swap(c->d_comments, s.any_comment ? s.d_comments : no_comments);   // a batch without comments: a null pointer tells the kernels
-		std::swap(c->d_sam, o.d_sam); std::swap(c->d_sam_off, o.d_sam_off);
-		std::swap(c->d_skeys, o.d_keys); std::swap(c->d_rec_off, o.d_rec_off); std::swap(c->ev_sort, o.ev_sort);
-		std::swap(c->d_bgzf_tot, o.d_tot); std::swap(c->ev_bgzf, o.ev_bgzf);
-		std::swap(c->n_reads, s.n); std::swap(c->max_len, s.max_len); std::swap(c->total_bases, s.total_bases);
-	};
-	exchange();
-	int rc = 0;
-	auto body = [&]() -> int {
-		HIP_TRY(hipStreamWaitEvent(c->stream, s.ev, 0));
-		if ((rc = launch_nt4(c->d_seq.as<uint8_t>(), c->total_bases, c->stream))) return rc;
-		if ((rc = run_pipeline(c, opt, false, false))) return rc;
-		if (t_hot_end) *t_hot_end = pipe_now();
-		if ((rc = run_final(c, opt, n_processed, pes0, false, form))) return rc;
-		HIP_TRY(hipEventRecord(o.ev_written, c->stream));
-		o.total = c->total_sam; o.n_rec = c->n_rec; o.form = form;
-		o.raw_total = c->total_sam; o.n_blocks = c->n_bgzf_blocks;
-		return 0;
-	};
-	rc = body();
-	exchange();
-	return rc;
+	// run_pipeline and run_final work on what the context points at: the two sets for this batch, its own again whatever happens
+	struct OnSets {
+		bwahip_ctx *c;
+		OnSets(bwahip_ctx *c, BatchIn *in, BatchOut *out) : c(c) { c->in = in; c->out = out; }
+		~OnSets() { c->in = &c->own_in; c->out = &c->own_out; }
+	} on_sets(c, &c->pipe->in[in], &c->pipe->out[out]);
+	int rc;
+	HIP_TRY(hipStreamWaitEvent(c->stream, c->in->ev, 0));
+	if ((rc = launch_nt4(c->in->d_seq.as<uint8_t>(), c->in->total_bases, c->stream))) return rc;
+	if ((rc = run_pipeline(c, opt, false, false))) return rc;
+	if (t_hot_end) *t_hot_end = pipe_now();
+	if ((rc = run_final(c, opt, n_processed, pes0, false, form))) return rc;
+	HIP_TRY(hipEventRecord(c->pipe->pin[out].ev_written, c->stream));
+	return 0;
 }
 
 int pipe_stage_out(bwahip_ctx *c, int out, const char **text, int64_t *len, double *t_kernels_end)
 {
 	if (!c || !c->pipe || out < 0 || out >= PIPE_SETS || !text || !len) return BWAHIP_EINVAL;
 	HIP_TRY(hipSetDevice(c->device));
-	PipeOut &o = c->pipe->out[out];
+	BatchOut &o = c->pipe->out[out];
+	PinnedOut &pin = c->pipe->pin[out];
 	// waiting on the host, not in the copy stream: the next batch's upload is queued there and must not stand behind this batch's kernels
-	HIP_TRY(hipEventSynchronize(o.ev_written));
+	HIP_TRY(hipEventSynchronize(pin.ev_written));
 	if (t_kernels_end) *t_kernels_end = pipe_now();
+	int64_t total = o.total;
 	if (o.form == OutForm::Bgzf) {                                              // what travels is the members: their total was left in HBM by the deflate stage
 		int64_t tot[2] = { 0, 0 };
 		HIP_TRY(hipMemcpyAsync(tot, o.d_tot.p, 16, hipMemcpyDeviceToHost, c->stream_copy));
-		HIP_TRY(hipEventRecord(o.ev_copied, c->stream_copy));
-		HIP_TRY(hipEventSynchronize(o.ev_copied));
-		o.total = tot[0]; o.n_stored = tot[1];
+		HIP_TRY(hipEventRecord(pin.ev_copied, c->stream_copy));
+		HIP_TRY(hipEventSynchronize(pin.ev_copied));
+		total = tot[0]; o.n_stored = tot[1];
 	}
-	int rc = o.h_sam.ensure((size_t)o.total + 1);
+	int rc = pin.h_sam.ensure((size_t)total + 1);
 	if (rc) return rc;
-	char *p = (char*)o.h_sam.p;
+	char *p = (char*)pin.h_sam.p;
 	// in slices, each awaited before the next is queued: an upload the stager queues meanwhile waits for one slice at the most
 	constexpr int64_t SLICE = 64 << 20;
-	for (int64_t b = 0; b < o.total; b += SLICE) {
-		HIP_TRY(hipMemcpyAsync(p + b, (const char*)o.d_sam.p + b, (size_t)std::min(SLICE, o.total - b), hipMemcpyDeviceToHost, c->stream_copy));
-		HIP_TRY(hipEventRecord(o.ev_copied, c->stream_copy));
-		HIP_TRY(hipEventSynchronize(o.ev_copied));
+	for (int64_t b = 0; b < total; b += SLICE) {
+		HIP_TRY(hipMemcpyAsync(p + b, (const char*)o.d_sam.p + b, (size_t)std::min(SLICE, total - b), hipMemcpyDeviceToHost, c->stream_copy));
+		HIP_TRY(hipEventRecord(pin.ev_copied, c->stream_copy));
+		HIP_TRY(hipEventSynchronize(pin.ev_copied));
 	}
-	p[o.total] = 0;
-	*text = p; *len = o.total;
+	p[total] = 0;
+	*text = p; *len = total;
 	return 0;
 }
 
@@ -1048,17 +1002,18 @@ int pipe_stage_out_sorted(bwahip_ctx *c, int out, const uint64_t **keys, const i
 {
 	if (!c || !c->pipe || out < 0 || out >= PIPE_SETS || !keys || !rec_off || !n_rec) return BWAHIP_EINVAL;
 	HIP_TRY(hipSetDevice(c->device));
-	PipeOut &o = c->pipe->out[out];
+	const BatchOut &o = c->pipe->out[out];
+	PinnedOut &pin = c->pipe->pin[out];
 	if (o.form != OutForm::BamSorted) return BWAHIP_EINVAL;
 	int rc;
-	if ((rc = o.h_keys.ensure((size_t)(o.n_rec ? o.n_rec : 1) * 8)) || (rc = o.h_rec_off.ensure((size_t)(o.n_rec + 1) * 8))) return rc;
-	if (o.n_rec) HIP_TRY(hipMemcpyAsync(o.h_keys.p, o.d_keys.p, (size_t)o.n_rec * 8, hipMemcpyDeviceToHost, c->stream_copy));
-	if (o.n_rec) HIP_TRY(hipMemcpyAsync(o.h_rec_off.p, o.d_rec_off.p, (size_t)(o.n_rec + 1) * 8, hipMemcpyDeviceToHost, c->stream_copy));
-	else *(int64_t*)o.h_rec_off.p = 0;
-	HIP_TRY(hipEventRecord(o.ev_copied, c->stream_copy));
-	HIP_TRY(hipEventSynchronize(o.ev_copied));
+	if ((rc = pin.h_keys.ensure((size_t)(o.n_rec ? o.n_rec : 1) * 8)) || (rc = pin.h_rec_off.ensure((size_t)(o.n_rec + 1) * 8))) return rc;
+	if (o.n_rec) HIP_TRY(hipMemcpyAsync(pin.h_keys.p, o.d_keys.p, (size_t)o.n_rec * 8, hipMemcpyDeviceToHost, c->stream_copy));
+	if (o.n_rec) HIP_TRY(hipMemcpyAsync(pin.h_rec_off.p, o.d_rec_off.p, (size_t)(o.n_rec + 1) * 8, hipMemcpyDeviceToHost, c->stream_copy));
+	else *(int64_t*)pin.h_rec_off.p = 0;
+	HIP_TRY(hipEventRecord(pin.ev_copied, c->stream_copy));
+	HIP_TRY(hipEventSynchronize(pin.ev_copied));
 	if (sort_ms) *sort_ms = sort_stage_ms(o);
-	*keys = (const uint64_t*)o.h_keys.p; *rec_off = (const int64_t*)o.h_rec_off.p; *n_rec = o.n_rec;
+	*keys = (const uint64_t*)pin.h_keys.p; *rec_off = (const int64_t*)pin.h_rec_off.p; *n_rec = o.n_rec;
 	return 0;
 }
 
@@ -1069,8 +1024,8 @@ int pipe_stage_out_devrun(bwahip_ctx *c, int out, DevRun **run, int64_t *raw_len
 	if (!c || !c->pipe || out < 0 || out >= PIPE_SETS || !run || !raw_len || !n_rec) return BWAHIP_EINVAL;
 	*run = nullptr;
 	HIP_TRY(hipSetDevice(c->device));
-	PipeOut &o = c->pipe->out[out];
-	HIP_TRY(hipEventSynchronize(o.ev_written));
+	const BatchOut &o = c->pipe->out[out];
+	HIP_TRY(hipEventSynchronize(c->pipe->pin[out].ev_written));
 	if (t_kernels_end) *t_kernels_end = pipe_now();
 	if (o.form != OutForm::BamSorted) return BWAHIP_EINVAL;
 	if (sort_ms) *sort_ms = sort_stage_ms(o);
@@ -1084,9 +1039,9 @@ int pipe_stage_out_devrun(bwahip_ctx *c, int out, DevRun **run, int64_t *raw_len
 int pipe_stage_out_bgzf(bwahip_ctx *c, int out, int64_t *raw_len, int64_t *n_blocks, int64_t *n_stored, double *deflate_ms)
 {
 	if (!c || !c->pipe || out < 0 || out >= PIPE_SETS || !raw_len || !n_blocks || !n_stored) return BWAHIP_EINVAL;
-	PipeOut &o = c->pipe->out[out];
+	const BatchOut &o = c->pipe->out[out];
 	if (o.form != OutForm::Bgzf) return BWAHIP_EINVAL;
-	*raw_len = o.raw_total; *n_blocks = o.n_blocks; *n_stored = o.n_stored;
+	*raw_len = o.total; *n_blocks = o.n_blocks; *n_stored = o.n_stored;
 	if (deflate_ms) { float ms = 0; if (o.ev_bgzf[0] && hipEventElapsedTime(&ms, o.ev_bgzf[0], o.ev_bgzf[1]) != hipSuccess) ms = 0; *deflate_ms = ms; }
 	return 0;
 }

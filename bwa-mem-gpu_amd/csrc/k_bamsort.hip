@@ -223,15 +223,15 @@ int bam_sort_radix(bwahip_ctx *c, int n, int key_bits, int *which)
 int bam_sort_batch(bwahip_ctx *c, int n, int64_t total)
 {
 	BamSort &s = c->bs;
-	c->n_rec = 0; s.n_passes = 0;
+	c->out->n_rec = 0; s.n_passes = 0;
 	if (n <= 0) return 0;
-	for (auto &e : c->ev_sort) if (!e) HIP_TRY(hipEventCreate(&e));
+	for (auto &e : c->out->ev_sort) if (!e) HIP_TRY(hipEventCreate(&e));
 	int rc;
 	if ((rc = s.rec_cnt.ensure((size_t)n * 4)) || (rc = s.rec_base.ensure(((size_t)n + 1) * 8)) || (rc = s.bits.ensure(16))) return rc;
 	const uint8_t *raw = s.raw.as<uint8_t>();
-	const int64_t *off = c->d_sam_off.as<int64_t>();
+	const int64_t *off = c->out->d_sam_off.as<int64_t>();
 	const int grid_n = (n + 255) / 256;
-	HIP_TRY(hipEventRecord(c->ev_sort[0], c->stream));
+	HIP_TRY(hipEventRecord(c->out->ev_sort[0], c->stream));
 	HIP_TRY(hipMemsetAsync(s.bits.p, 0, 16, c->stream));
 	hipLaunchKernelGGL(k_rec_count, dim3(grid_n), dim3(256), 0, c->stream, raw, off, n, s.rec_cnt.as<int>(), s.bits.as<int>());
 	if ((rc = launched()) || (rc = launch_scan(s.rec_cnt.as<int>(), s.rec_base.as<int64_t>(), n, c->d_scan, c->stream))) return rc;
@@ -242,26 +242,26 @@ int bam_sort_batch(bwahip_ctx *c, int n, int64_t total)
 	if (err || n_rec < 0 || n_rec > 0x7fffffff) { fprintf(stderr, "[bwahip] sorted BAM: the records of the batch do not chain (%lld records)\n", (long long)n_rec); return BWAHIP_EINTERNAL; }
 	const size_t R = (size_t)(n_rec ? n_rec : 1);
 	if ((rc = s.keys[0].ensure(R * 8)) || (rc = s.keys[1].ensure(R * 8)) || (rc = s.idx[0].ensure(R * 4)) || (rc = s.idx[1].ensure(R * 4)) || (rc = s.off.ensure(R * 8)) ||
-	    (rc = s.len.ensure(R * 4)) || (rc = s.len_sorted.ensure(R * 4)) || (rc = c->d_skeys.ensure(R * 8)) || (rc = c->d_rec_off.ensure((R + 1) * 8))) return rc;
+	    (rc = s.len.ensure(R * 4)) || (rc = s.len_sorted.ensure(R * 4)) || (rc = c->out->d_keys.ensure(R * 8)) || (rc = c->out->d_rec_off.ensure((R + 1) * 8))) return rc;
 	const bwahip_bns_t *bns = &c->host.bns;
 	hipLaunchKernelGGL(k_rec_fill, dim3(grid_n), dim3(256), 0, c->stream, raw, off, s.rec_base.as<int64_t>(), n, bns->n_seqs, bam_key_pos_bits(bns),
 	                   s.keys[0].as<uint64_t>(), s.idx[0].as<unsigned>(), s.off.as<int64_t>(), s.len.as<int>());
 	if ((rc = launched())) return rc;
-	HIP_TRY(hipEventRecord(c->ev_sort[1], c->stream));
+	HIP_TRY(hipEventRecord(c->out->ev_sort[1], c->stream));
 	int cur = 0;
 	if ((rc = bam_sort_radix(c, (int)n_rec, bam_key_bits(bns), &cur))) return rc;
-	HIP_TRY(hipEventRecord(c->ev_sort[2], c->stream));
+	HIP_TRY(hipEventRecord(c->out->ev_sort[2], c->stream));
 	const int nr = (int)n_rec, grid_r = (nr + 255) / 256;
 	if (nr > 0) {
 		hipLaunchKernelGGL(k_gather_len, dim3(grid_r), dim3(256), 0, c->stream, s.idx[cur].as<unsigned>(), s.len.as<int>(), nr, s.len_sorted.as<int>());
-		if ((rc = launched()) || (rc = launch_scan(s.len_sorted.as<int>(), c->d_rec_off.as<int64_t>(), nr, c->d_scan, c->stream))) return rc;
-		HIP_TRY(hipMemcpyAsync(c->d_skeys.p, s.keys[cur].p, (size_t)nr * 8, hipMemcpyDeviceToDevice, c->stream));
+		if ((rc = launched()) || (rc = launch_scan(s.len_sorted.as<int>(), c->out->d_rec_off.as<int64_t>(), nr, c->d_scan, c->stream))) return rc;
+		HIP_TRY(hipMemcpyAsync(c->out->d_keys.p, s.keys[cur].p, (size_t)nr * 8, hipMemcpyDeviceToDevice, c->stream));
 		hipLaunchKernelGGL(k_gather_copy, dim3((unsigned)(((int64_t)nr * 16 + 255) / 256)), dim3(256), 0, c->stream, raw, s.idx[cur].as<unsigned>(), s.off.as<int64_t>(),
-		                   c->d_rec_off.as<int64_t>(), nr, c->d_sam.as<uint8_t>());
+		                   c->out->d_rec_off.as<int64_t>(), nr, c->out->d_sam.as<uint8_t>());
 		if ((rc = launched())) return rc;
-	} else HIP_TRY(hipMemsetAsync(c->d_rec_off.p, 0, 8, c->stream));
-	HIP_TRY(hipEventRecord(c->ev_sort[3], c->stream));
-	c->n_rec = n_rec;
+	} else HIP_TRY(hipMemsetAsync(c->out->d_rec_off.p, 0, 8, c->stream));
+	HIP_TRY(hipEventRecord(c->out->ev_sort[3], c->stream));
+	c->out->n_rec = n_rec;
 	(void)total;
 	return 0;
 }

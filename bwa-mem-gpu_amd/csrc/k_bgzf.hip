@@ -642,7 +642,6 @@ int bgzf_deflate(bwahip_ctx *c, const uint8_t *d_in, int64_t len, DevBuf &out, i
 	const int64_t nb64 = bgzf_blocks(len);
 	if (nb64 > 0x7fff0000ll / 4) return BWAHIP_ECAPACITY;
 	const int nb = (int)nb64;
-	c->n_bgzf_blocks = nb;
 	if (nb == 0) { HIP_TRY(hipMemsetAsync(tot_dev, 0, 16, st)); return 0; }
 	static int n_cu = 0;
 	if (!n_cu) { hipDeviceProp_t pr; HIP_TRY(hipGetDeviceProperties(&pr, c->device)); n_cu = pr.multiProcessorCount > 0 ? pr.multiProcessorCount : 64; }

@@ -353,23 +353,20 @@ void bwahip_destroy(bwahip_ctx *c)
 	(void)hipSetDevice(c->device);
 	if (c->stream) (void)hipStreamSynchronize(c->stream);
 	pipe_destroy(c);
-	DevBuf *bufs[] = { &c->d_bwt, &c->d_bwtp, &c->d_sa, &c->d_sa_dense, &c->d_kmer, &c->d_pac, &c->d_anns, &c->d_seq, &c->d_off, &c->d_seq4, &c->d_smem_heavy, &c->d_raw, &c->d_raw_n, &c->d_intv, &c->d_intv_n, &c->d_seed_cnt,
+	DevBuf *bufs[] = { &c->d_bwt, &c->d_bwtp, &c->d_sa, &c->d_sa_dense, &c->d_kmer, &c->d_pac, &c->d_anns, &c->d_seq4, &c->d_smem_heavy, &c->d_raw, &c->d_raw_n, &c->d_intv, &c->d_intv_n, &c->d_seed_cnt,
 	                   &c->d_lrep, &c->d_seed_base, &c->d_seeds, &c->d_scratch, &c->d_misc,
 	                   &c->d_cw, &c->d_nxt, &c->d_ord, &c->d_wts, &c->d_kept, &c->d_first, &c->d_keep, &c->d_nodes, &c->d_stack,
 	                   &c->d_chains, &c->d_chain_seeds, &c->d_chain_n, &c->d_kept_seeds, &c->d_reg_base, &c->d_regs, &c->d_tmp_regs,
 	                   &c->d_reg_n, &c->d_srt, &c->d_dbg_chains, &c->d_dbg_seeds, &c->d_dbg_chain_n, &c->d_dbg_regs, &c->d_dbg_reg_n, &c->d_flt, &c->d_heavy, &c->d_perm, &c->d_spec_regs, &c->d_spec_items, &c->d_scan, &c->d_chain_big, &c->d_logtab, &c->d_redo, &c->d_big_t, &c->d_dedup, &c->d_cperm,
-	                   &c->d_ctg_names, &c->d_ctg_name_off, &c->d_ctg_anno, &c->d_ctg_anno_off, &c->d_rg, &c->d_qual, &c->d_qual_off, &c->d_names, &c->d_name_off, &c->d_comments, &c->d_comment_off,
+	                   &c->d_ctg_names, &c->d_ctg_name_off, &c->d_ctg_anno, &c->d_ctg_anno_off, &c->d_rg,
 	                   &c->d_fregs, &c->d_fregs2, &c->d_fscr, &c->d_need, &c->d_xa_owner, &c->d_freg_n, &c->d_npri, &c->d_task_n, &c->d_rec_n, &c->d_task_base, &c->d_tasks, &c->d_aln_of_reg, &c->d_alns,
-	                   &c->d_resc_flag, &c->d_zslab, &c->d_resc_ord, &c->d_pool, &c->d_fmisc, &c->d_fredo, &c->d_bigz, &c->d_rec_list, &c->d_xa_list, &c->d_sam_len, &c->d_sam_off, &c->d_sam,
+	                   &c->d_resc_flag, &c->d_zslab, &c->d_resc_ord, &c->d_pool, &c->d_fmisc, &c->d_fredo, &c->d_bigz, &c->d_rec_list, &c->d_xa_list, &c->d_sam_len,
 	                   &c->d_hist, &c->d_pair_tab, &c->d_nb, &c->d_pe_cap, &c->d_pe_base, &c->d_pe_regs, &c->d_pe_n, &c->d_pe_tmp, &c->d_pe_keys, &c->d_pe_idx, &c->d_resc, &c->d_ms_slab, &c->d_pe_read, &c->d_sw_cnt, &c->d_sw_base, &c->d_sw_res, &c->d_sw_tasks, &c->d_sw_info, &c->d_task_lists, &c->d_pair_dbg };
 	if (c->external_index) { c->d_bwt.p = nullptr; c->d_sa.p = nullptr; c->d_pac.p = nullptr; c->d_bwt.cap = c->d_sa.cap = c->d_pac.cap = 0; }
 	for (DevBuf *b : bufs) b->release();
-	c->h_stage.release(); c->h_sam.release(); c->h_sam2.release();
-	c->bs.release(); c->d_skeys.release(); c->d_rec_off.release();
-	for (int k = 0; k < 2; ++k) { c->h_skeys[k].release(); c->h_rec_off[k].release(); }
-	for (auto &e : c->ev_sort) if (e) (void)hipEventDestroy(e);
-	c->bz.release(); c->d_bgzf_tot.release();
-	for (auto &e : c->ev_bgzf) if (e) (void)hipEventDestroy(e);
+	c->own_in.release(); c->own_out.release();
+	for (auto &p : c->pin) p.release();
+	c->bs.release(); c->bz.release();
 	for (auto &e : c->ev) if (e) (void)hipEventDestroy(e);
 	if (c->stream) (void)hipStreamDestroy(c->stream);
 	if (c->stream2) (void)hipStreamDestroy(c->stream2);
@@ -576,11 +573,11 @@ int bwahip_batch_upload(bwahip_ctx *c, int n, const uint8_t *seq, const int64_t 
 		if (l > BWAHIP_MAX_READ_LEN) { fprintf(stderr, "[bwahip] read %d is %lld bases long (limit %d)\n", i, (long long)l, BWAHIP_MAX_READ_LEN); return BWAHIP_ECAPACITY; }
 		if (l > max_len) max_len = (int)l;
 	}
-	c->n_reads = n; c->max_len = max_len; c->total_bases = n ? off[n] - off[0] : 0;
+	c->in->n = n; c->in->max_len = max_len; c->in->total_bases = n ? off[n] - off[0] : 0;
 	int rc;
 	if (n && off[0] != 0) return BWAHIP_EINVAL;
-	if ((rc = upload(c->d_seq, seq, (size_t)c->total_bases, c->stream))) return rc;
-	if ((rc = upload(c->d_off, off, (size_t)(n + 1) * 8, c->stream))) return rc;
+	if ((rc = upload(c->in->d_seq, seq, (size_t)c->in->total_bases, c->stream))) return rc;
+	if ((rc = upload(c->in->d_off, off, (size_t)(n + 1) * 8, c->stream))) return rc;
 	HIP_TRY(hipStreamSynchronize(c->stream));
 	return 0;
 }
@@ -590,9 +587,9 @@ int bwahip_batch_attach(bwahip_ctx *c, int n, const uint8_t *seq_dev, const int6
 	if (!c || n < 0 || (n && (!seq_dev || !off_dev)) || max_len < 0 || total_bases < 0) return BWAHIP_EINVAL;
 	if (max_len > BWAHIP_MAX_READ_LEN) return BWAHIP_ECAPACITY;
 	HIP_TRY(hipSetDevice(c->device));
-	c->n_reads = n; c->max_len = max_len; c->total_bases = total_bases;
-	c->d_seq.adopt((void*)seq_dev, (size_t)total_bases);
-	c->d_off.adopt((void*)off_dev, (size_t)(n + 1) * 8);
+	c->in->n = n; c->in->max_len = max_len; c->in->total_bases = total_bases;
+	c->in->d_seq.adopt((void*)seq_dev, (size_t)total_bases);
+	c->in->d_off.adopt((void*)off_dev, (size_t)(n + 1) * 8);
 	return 0;
 }
 
@@ -605,16 +602,16 @@ int run_pipeline(bwahip_ctx *c, const bwahip_opt_t *opt, bool timed, bool dump)
 {
 	const bool verbose = c->knobs.verbose != 0;
 #define STAGE_LOG(name) do { if (verbose) { (void)hipStreamSynchronize(c->stream); fprintf(stderr, "[bwahip] %s done (%s)\n", name, hipGetErrorString(hipGetLastError())); fflush(stderr); } } while (0)
-	const int n = c->n_reads;
+	const int n = c->in->n;
 	if (n == 0) return 0;
 	DevOpt dopt = make_dev_opt(opt);
-	if (c->ix.seq_len >= (1ull << 38) || c->max_len >= (1 << 14)) return BWAHIP_EINVAL;   // k_smem packs list entries as 3 x 38 + 14 bits
+	if (c->ix.seq_len >= (1ull << 38) || c->in->max_len >= (1 << 14)) return BWAHIP_EINVAL;   // k_smem packs list entries as 3 x 38 + 14 bits
 	unsigned long long *counters = c->d_misc.as<unsigned long long>();
 	unsigned int *queue = (unsigned int*)(counters + (size_t)CNT_SLOTS * CNT_N);
 	int *err = (int*)(queue + 4);
 	int rc;
 	for (int attempt = 0; attempt < 8; ++attempt) {
-		const int cap = c->intv_cap, lcap = c->max_len + 2;
+		const int cap = c->intv_cap, lcap = c->in->max_len + 2;
 		const int G = c->knobs.smem_lanes;                       // lanes per read in k_smem (1, 2, 4 or 8)
 		const int groups = smem_default_groups(G);
 		if ((rc = c->d_intv.ensure((size_t)n * cap * sizeof(DevIntv))) || (rc = c->d_raw.ensure((size_t)n * cap * sizeof(DevIntv))) || (rc = c->d_raw_n.ensure((size_t)n * 4))) return rc;
@@ -624,16 +621,16 @@ int run_pipeline(bwahip_ctx *c, const bwahip_opt_t *opt, bool timed, bool dump)
 		HIP_TRY(hipMemsetAsync(c->d_misc.p, 0, BWAHIP_MISC_BYTES, c->stream));
 		SmemLaunch sl;
 		memset(&sl, 0, sizeof sl);
-		sl.ix = c->ix; sl.opt = dopt; sl.n_reads = n; sl.seq = c->d_seq.as<uint8_t>(); sl.off = c->d_off.as<int64_t>();
+		sl.ix = c->ix; sl.opt = dopt; sl.n_reads = n; sl.seq = c->in->d_seq.as<uint8_t>(); sl.off = c->in->d_off.as<int64_t>();
 		sl.out = c->d_intv.as<DevIntv>(); sl.out_n = c->d_intv_n.as<int>(); sl.cap = cap;
 		sl.raw = c->d_raw.as<DevIntv>(); sl.raw_n = c->d_raw_n.as<int>();
 		sl.seed_cnt = c->d_seed_cnt.as<int>(); sl.l_rep = c->d_lrep.as<int>();
-		sl.seq4_stride = (c->max_len + 15) / 16 + 1;            // +1: a word of 0xF past the longest read
+		sl.seq4_stride = (c->in->max_len + 15) / 16 + 1;            // +1: a word of 0xF past the longest read
 		if ((rc = c->d_seq4.ensure((size_t)n * sl.seq4_stride * 8))) return rc;
 		sl.seq4 = c->d_seq4.as<uint64_t>();
 		if (attempt == 0 && (rc = launch_pack4(sl, c->stream))) return rc;
 		sl.scratch = c->d_scratch.as<DevIntv>(); sl.lcap = lcap; sl.queue = queue; sl.counters = counters; sl.err = err; sl.groups_total = groups;
-		const int heavy_mult = c->knobs.heavy_mult >= 0 ? c->knobs.heavy_mult : c->max_len <= 200 ? 10 : 30;   // x read length; 0 = never hand off
+		const int heavy_mult = c->knobs.heavy_mult >= 0 ? c->knobs.heavy_mult : c->in->max_len <= 200 ? 10 : 30;   // x read length; 0 = never hand off
 		if ((rc = c->d_smem_heavy.ensure((size_t)n * 4))) return rc;
 		sl.heavy_list = c->d_smem_heavy.as<int>(); sl.heavy_n = queue + 1; sl.heavy_mult = heavy_mult; sl.worst_n = (int*)(queue + 2);
 		if (timed) HIP_TRY(hipEventRecord(c->ev[0], c->stream));
@@ -669,7 +666,7 @@ int run_pipeline(bwahip_ctx *c, const bwahip_opt_t *opt, bool timed, bool dump)
 		if ((rc = c->d_seeds.ensure((size_t)(total ? total : 1) * sizeof(DevSeed)))) return rc;
 		SeedLaunch se;
 		memset(&se, 0, sizeof se);
-		se.ix = c->ix; se.opt = dopt; se.n_reads = n; se.off = c->d_off.as<int64_t>();
+		se.ix = c->ix; se.opt = dopt; se.n_reads = n; se.off = c->in->d_off.as<int64_t>();
 		se.intv = c->d_intv.as<DevIntv>(); se.intv_n = c->d_intv_n.as<int>(); se.cap = cap;
 		se.seed_base = c->d_seed_base.as<int64_t>(); se.seeds = c->d_seeds.as<DevSeed>(); se.counters = counters;
 		if (timed) HIP_TRY(hipEventRecord(c->ev[3], c->stream));
@@ -688,7 +685,7 @@ int run_pipeline(bwahip_ctx *c, const bwahip_opt_t *opt, bool timed, bool dump)
 			return rc;
 		ChainLaunch cl;
 		memset(&cl, 0, sizeof cl);
-		cl.ix = c->ix; cl.opt = dopt; cl.n_reads = n; cl.off = c->d_off.as<int64_t>();
+		cl.ix = c->ix; cl.opt = dopt; cl.n_reads = n; cl.off = c->in->d_off.as<int64_t>();
 		cl.intv = c->d_intv.as<DevIntv>(); cl.intv_n = c->d_intv_n.as<int>(); cl.cap = cap;
 		cl.seed_base = c->d_seed_base.as<int64_t>(); cl.seeds = c->d_seeds.as<DevSeed>();
 		cl.cw_ = c->d_cw.as<ChainWOpaque>(); cl.nxt = c->d_nxt.as<int>(); cl.ord = c->d_ord.as<int>(); cl.wts = c->d_wts.as<int>();
@@ -714,10 +711,10 @@ int run_pipeline(bwahip_ctx *c, const bwahip_opt_t *opt, bool timed, bool dump)
 		if (timed) HIP_TRY(hipEventRecord(c->ev[6], c->stream));
 		// ---- K3b: mem_flt_chained_seeds (bwamem.c:605).  With -W 0 it returns at its first test for every read of 2..700
 		// bases (5.5 ln l > 0.05 l there), so the launch is skipped; the kernel itself repeats the test per read.
-		if (opt->min_chain_weight != 0 || c->max_len > 700) {
+		if (opt->min_chain_weight != 0 || c->in->max_len > 700) {
 			SeedSwLaunch ss;
 			memset(&ss, 0, sizeof ss);
-			ss.ix = c->ix; ss.opt = dopt; ss.n_reads = n; ss.seq = c->d_seq.as<uint8_t>(); ss.off = c->d_off.as<int64_t>();
+			ss.ix = c->ix; ss.opt = dopt; ss.n_reads = n; ss.seq = c->in->d_seq.as<uint8_t>(); ss.off = c->in->d_off.as<int64_t>();
 			ss.seed_base = c->d_seed_base.as<int64_t>(); ss.chains = c->d_chains.as<DevChain>(); ss.chain_seeds = c->d_chain_seeds.as<DevSeed>();
 			ss.chain_n = c->d_chain_n.as<int>(); ss.kept_seeds = c->d_kept_seeds.as<int>(); ss.logtab = c->d_logtab.as<double>();
 			if ((rc = launch_seed_sw(ss, c->stream))) return rc;
@@ -737,7 +734,7 @@ int run_pipeline(bwahip_ctx *c, const bwahip_opt_t *opt, bool timed, bool dump)
 		if (dump && ((rc = c->d_dbg_regs.ensure(R * sizeof(DevReg))) || (rc = c->d_dbg_reg_n.ensure((size_t)n * 4)))) return rc;
 		ExtLaunch el;
 		memset(&el, 0, sizeof el);
-		el.ix = c->ix; el.opt = dopt; el.n_reads = n; el.seq = c->d_seq.as<uint8_t>(); el.off = c->d_off.as<int64_t>();
+		el.ix = c->ix; el.opt = dopt; el.n_reads = n; el.seq = c->in->d_seq.as<uint8_t>(); el.off = c->in->d_off.as<int64_t>();
 		el.seed_base = c->d_seed_base.as<int64_t>(); el.chains = c->d_chains.as<DevChain>(); el.chain_seeds = c->d_chain_seeds.as<DevSeed>();
 		el.chain_n = c->d_chain_n.as<int>(); el.reg_base = c->d_reg_base.as<int64_t>();
 		el.regs = c->d_regs.as<DevReg>(); el.reg_n = c->d_reg_n.as<int>(); el.tmp_regs = c->d_tmp_regs.as<DevReg>(); el.srt = c->d_srt.as<int>();
@@ -759,11 +756,11 @@ int run_pipeline(bwahip_ctx *c, const bwahip_opt_t *opt, bool timed, bool dump)
 			el.spec_min_chains = spec_min;
 		}
 		if (timed) HIP_TRY(hipEventRecord(c->ev[11], c->stream));
-		if ((rc = launch_extend_spec(el, c->max_len, c->stream))) return rc;
+		if ((rc = launch_extend_spec(el, c->in->max_len, c->stream))) return rc;
 		STAGE_LOG("k_extend_spec");
 		if (timed) HIP_TRY(hipEventRecord(c->ev[8], c->stream));
 		if (verbose) fprintf(stderr, "[bwahip] seeds=%lld regs_cap=%lld\n", (long long)total, (long long)total_regs);
-		if ((rc = launch_extend(el, c->max_len, c->stream, c->stream2, c->ev_fork, c->ev_join))) return rc;
+		if ((rc = launch_extend(el, c->in->max_len, c->stream, c->stream2, c->ev_fork, c->ev_join))) return rc;
 		STAGE_LOG("k_extend");
 		if (timed) HIP_TRY(hipEventRecord(c->ev[9], c->stream));
 		int h_err2[2] = { 0, 0 };
@@ -809,14 +806,14 @@ int bwahip_batch_run(bwahip_ctx *c, const bwahip_opt_t *opt, float *kernel_ms, i
 int bwahip_batch_attach_text(bwahip_ctx *c, const uint8_t *qual_dev, const int64_t *qual_off_dev, const uint8_t *names_dev, const int64_t *name_off_dev)
 {
 	if (!c || !names_dev || !name_off_dev || (qual_dev && !qual_off_dev)) return BWAHIP_EINVAL;
-	const int n = c->n_reads;
-	c->d_qual.adopt((void*)qual_dev, 0); c->d_qual_off.adopt((void*)qual_off_dev, (size_t)n * 8);
-	c->d_names.adopt((void*)names_dev, 0); c->d_name_off.adopt((void*)name_off_dev, (size_t)(n + 1) * 8);
-	c->d_comments.release();
-	int rc = c->d_comment_off.ensure((size_t)(n + 1) * 8);
+	const int n = c->in->n;
+	c->in->d_qual.adopt((void*)qual_dev, 0); c->in->d_qual_off.adopt((void*)qual_off_dev, (size_t)n * 8);
+	c->in->d_names.adopt((void*)names_dev, 0); c->in->d_name_off.adopt((void*)name_off_dev, (size_t)(n + 1) * 8);
+	c->in->any_comment = false;
+	int rc = c->in->d_comment_off.ensure((size_t)(n + 1) * 8);
 	if (rc) return rc;
 	HIP_TRY(hipSetDevice(c->device));
-	HIP_TRY(hipMemsetAsync(c->d_comment_off.p, 0, (size_t)(n + 1) * 8, c->stream));
+	HIP_TRY(hipMemsetAsync(c->in->d_comment_off.p, 0, (size_t)(n + 1) * 8, c->stream));
 	return 0;
 }
 
@@ -826,12 +823,12 @@ static int batch_run_form(bwahip_ctx *c, const bwahip_opt_t *opt, int64_t n_proc
 {
 	if (!c || !opt) return BWAHIP_EINVAL;
 	HIP_TRY(hipSetDevice(c->device));
-	if (is_bam(form) && c->n_reads > 0) {
-		if (!c->d_name_off.p) return BWAHIP_EINVAL;
-		std::vector<int64_t> noff((size_t)c->n_reads + 1);
-		HIP_TRY(hipMemcpyAsync(noff.data(), c->d_name_off.p, noff.size() * 8, hipMemcpyDeviceToHost, c->stream));
+	if (is_bam(form) && c->in->n > 0) {
+		if (!c->in->d_name_off.p) return BWAHIP_EINVAL;
+		std::vector<int64_t> noff((size_t)c->in->n + 1);
+		HIP_TRY(hipMemcpyAsync(noff.data(), c->in->d_name_off.p, noff.size() * 8, hipMemcpyDeviceToHost, c->stream));
 		HIP_TRY(hipStreamSynchronize(c->stream));
-		for (int i = 0; i < c->n_reads; ++i)
+		for (int i = 0; i < c->in->n; ++i)
 			if (noff[i + 1] - noff[i] > 255) { fprintf(stderr, "[bwahip] BAM: the name of read %d has %lld bytes (at most 254 fit a record)\n", i, (long long)(noff[i + 1] - noff[i] - 1)); return BWAHIP_EINVAL; }
 	}
 	int rc = run_pipeline(c, opt, true, false);
@@ -862,7 +859,7 @@ int bwahip_batch_run_bam(bwahip_ctx *c, const bwahip_opt_t *opt, int64_t n_proce
 int bwahip_batch_run_bam_sorted(bwahip_ctx *c, const bwahip_opt_t *opt, int64_t n_processed, const bwahip_pestat_t *pes0, float *kernel_ms, int n_ms, float *sort_ms4)
 {
 	const int rc = batch_run_form(c, opt, n_processed, pes0, kernel_ms, n_ms, OutForm::BamSorted);
-	if (!rc && sort_ms4) { for (int k = 0; k < 3; ++k) sort_ms4[k] = c->n_rec ? c->bs.ms[k] : 0; sort_ms4[3] = (float)c->bs.n_passes; }
+	if (!rc && sort_ms4) { for (int k = 0; k < 3; ++k) sort_ms4[k] = c->out->n_rec ? c->bs.ms[k] : 0; sort_ms4[3] = (float)c->bs.n_passes; }
 	return rc;
 }
 
@@ -871,17 +868,17 @@ int bwahip_batch_bam_sorted(bwahip_ctx *c, uint8_t **out, int64_t *out_len, uint
 {
 	if (!c || !out || !out_len || !keys || !rec_off || !n_rec) return BWAHIP_EINVAL;
 	HIP_TRY(hipSetDevice(c->device));
-	const int64_t nr = c->n_rec;
-	uint8_t *buf = (uint8_t*)malloc((size_t)c->total_sam + 1);
+	const int64_t nr = c->out->n_rec;
+	uint8_t *buf = (uint8_t*)malloc((size_t)c->out->total + 1);
 	uint64_t *k = (uint64_t*)malloc((size_t)(nr ? nr : 1) * 8);
 	int64_t *o = (int64_t*)calloc((size_t)nr + 1, 8);
 	auto bad = [&](int code) { free(buf); free(k); free(o); return code; };
 	if (!buf || !k || !o) return bad(BWAHIP_ENOMEM);
-	if (nr && (hipMemcpyAsync(buf, c->d_sam.p, (size_t)c->total_sam, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
-	           hipMemcpyAsync(k, c->d_skeys.p, (size_t)nr * 8, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
-	           hipMemcpyAsync(o, c->d_rec_off.p, (size_t)(nr + 1) * 8, hipMemcpyDeviceToHost, c->stream) != hipSuccess)) return bad(BWAHIP_ENODEV);
+	if (nr && (hipMemcpyAsync(buf, c->out->d_sam.p, (size_t)c->out->total, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+	           hipMemcpyAsync(k, c->out->d_keys.p, (size_t)nr * 8, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+	           hipMemcpyAsync(o, c->out->d_rec_off.p, (size_t)(nr + 1) * 8, hipMemcpyDeviceToHost, c->stream) != hipSuccess)) return bad(BWAHIP_ENODEV);
 	if (hipStreamSynchronize(c->stream) != hipSuccess) return bad(BWAHIP_ENODEV);
-	*out = buf; *out_len = nr ? c->total_sam : 0; *keys = k; *rec_off = o; *n_rec = nr;
+	*out = buf; *out_len = nr ? c->out->total : 0; *keys = k; *rec_off = o; *n_rec = nr;
 	return 0;
 }
 
@@ -892,7 +889,7 @@ int bwahip_batch_run_bgzf(bwahip_ctx *c, const bwahip_opt_t *opt, int64_t n_proc
 	const int rc = batch_run_form(c, opt, n_processed, pes0, kernel_ms, n_ms, OutForm::Bgzf);
 	if (!rc && deflate_ms) {
 		*deflate_ms = 0;
-		if (c->n_reads > 0 && c->ev_bgzf[0]) HIP_TRY(hipEventElapsedTime(deflate_ms, c->ev_bgzf[0], c->ev_bgzf[1]));
+		if (c->in->n > 0 && c->out->ev_bgzf[0]) HIP_TRY(hipEventElapsedTime(deflate_ms, c->out->ev_bgzf[0], c->out->ev_bgzf[1]));
 	}
 	return rc;
 }
@@ -904,16 +901,16 @@ int bwahip_batch_bgzf(bwahip_ctx *c, uint8_t **out, int64_t *out_len, int64_t *r
 	if (!c || !out || !out_len) return BWAHIP_EINVAL;
 	HIP_TRY(hipSetDevice(c->device));
 	int64_t tot[2] = { 0, 0 };
-	if (c->n_reads > 0 && c->d_bgzf_tot.p) {
-		HIP_TRY(hipMemcpyAsync(tot, c->d_bgzf_tot.p, 16, hipMemcpyDeviceToHost, c->stream));
+	if (c->in->n > 0 && c->out->d_tot.p) {
+		HIP_TRY(hipMemcpyAsync(tot, c->out->d_tot.p, 16, hipMemcpyDeviceToHost, c->stream));
 		HIP_TRY(hipStreamSynchronize(c->stream));
 	}
 	uint8_t *buf = (uint8_t*)malloc((size_t)tot[0] + 1);
 	if (!buf) return BWAHIP_ENOMEM;
-	if (tot[0] && (hipMemcpyAsync(buf, c->d_sam.p, (size_t)tot[0], hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess)) { free(buf); return BWAHIP_ENODEV; }
+	if (tot[0] && (hipMemcpyAsync(buf, c->out->d_sam.p, (size_t)tot[0], hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess)) { free(buf); return BWAHIP_ENODEV; }
 	*out = buf; *out_len = tot[0];
-	if (raw_len) *raw_len = c->n_reads > 0 ? c->total_sam : 0;
-	if (n_blocks) *n_blocks = c->n_reads > 0 ? c->n_bgzf_blocks : 0;
+	if (raw_len) *raw_len = c->in->n > 0 ? c->out->total : 0;
+	if (n_blocks) *n_blocks = c->in->n > 0 ? c->out->n_blocks : 0;
 	if (n_stored) *n_stored = tot[1];
 	return 0;
 }
@@ -951,13 +948,13 @@ int bwahip_batch_sam(bwahip_ctx *c, char **out, int64_t *out_len, int64_t *off)
 {
 	if (!c || !out || !out_len) return BWAHIP_EINVAL;
 	HIP_TRY(hipSetDevice(c->device));
-	char *buf = (char*)malloc((size_t)c->total_sam + 1);
+	char *buf = (char*)malloc((size_t)c->out->total + 1);
 	if (!buf) return BWAHIP_ENOMEM;
-	if (c->total_sam) HIP_TRY(hipMemcpyAsync(buf, c->d_sam.p, (size_t)c->total_sam, hipMemcpyDeviceToHost, c->stream));
-	if (off && c->n_reads) HIP_TRY(hipMemcpyAsync(off, c->d_sam_off.p, (size_t)(c->n_reads + 1) * 8, hipMemcpyDeviceToHost, c->stream));
+	if (c->out->total) HIP_TRY(hipMemcpyAsync(buf, c->out->d_sam.p, (size_t)c->out->total, hipMemcpyDeviceToHost, c->stream));
+	if (off && c->in->n) HIP_TRY(hipMemcpyAsync(off, c->out->d_sam_off.p, (size_t)(c->in->n + 1) * 8, hipMemcpyDeviceToHost, c->stream));
 	HIP_TRY(hipStreamSynchronize(c->stream));
-	buf[c->total_sam] = 0;
-	*out = buf; *out_len = c->total_sam;
+	buf[c->out->total] = 0;
+	*out = buf; *out_len = c->out->total;
 	return 0;
 }
 
@@ -982,7 +979,7 @@ static int batch_download_mt(bwahip_ctx *c, bwahip_alnreg_v *out, int nt)
 {
 	if (!c || !out) return BWAHIP_EINVAL;
 	HIP_TRY(hipSetDevice(c->device));
-	const int n = c->n_reads;
+	const int n = c->in->n;
 	if (n == 0) return 0;
 	std::vector<int> h_regn(n);
 	std::vector<int64_t> h_rbase(n + 1);

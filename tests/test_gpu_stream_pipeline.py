@@ -6,6 +6,7 @@ import subprocess
 import sys
 import textwrap
 
+import numpy as np
 import pytest
 
 import common
@@ -261,3 +262,150 @@ def test_back_to_back_passes_on_the_same_contexts(ctx3, pe_inputs, small_index, 
     want_bam = bw.bam_header(ctx3[0], hdr) + bam_ref.sam_to_bam_records(want_pe, bam_ref.contig_names_of(small_index["prefix"]))
     assert gzip.decompress(open(out, "rb").read()) == want_bam
     assert st.n_batches == 7 and st.n_reads == n_reads
+
+
+# ---------------------------------------------------------------------------------------------- the context's own batch beside the sets
+def _interleaved(fq1, fq2):
+    n1, s1, q1 = bw.read_fastq(fq1)
+    n2, s2, q2 = bw.read_fastq(fq2)
+    return [x for p in zip(n1, n2) for x in p], [x for p in zip(s1, s2) for x in p], [x for p in zip(q1, q2) for x in p]
+
+
+def _pe_opt():
+    opt = bw.default_opt()
+    opt.n_threads = 4
+    opt.flag |= 0x2
+    return opt
+
+
+K_100 = 100 * 100
+
+
+@pytest.fixture(scope="module")
+def pe100(small_index, tmp_path_factory):
+    """300 pairs of 2 x 100: six batches of -K 100 * 100"""
+    d = tmp_path_factory.mktemp("pipe_pe100")
+    fq1, fq2 = str(d / "h_1.fq"), str(d / "h_2.fq")
+    bw.make_reads(small_index["fa"], fq1, fq2, 600, 100, 10000, 2000, 500, 651, 20000)
+    assert len(_records(fq1)) == len(_records(fq2)) == 300
+    return fq1, fq2
+
+
+def test_an_uploaded_batch_survives_a_stream_pass(ctx3, pe_inputs, pe100, small_index, tmp_path):
+    """200 reads of 2 x 150 made resident in a context's own buffers (text by a SAM call, bases by bwahip_batch_upload), then stream passes of
+    600 reads of 2 x 100 through that context as one of two: bwahip_batch_run_sam / _bam_sorted over the resident batch give the same bytes
+    before and after, without a new upload."""
+    a, b, n_reads, want = pe_inputs[1]
+    names, seqs, quals = _interleaved(a, b)
+    assert n_reads == len(names) == 200
+    opt = _pe_opt()
+    c = ctx3[0]
+    arr, keep = bw.seq_array(names, seqs, quals)
+    assert c.process_seqs_text_array(arr, 200, opt) == want
+    c.batch_upload(*bw.pack_reads(seqs))
+
+    def resident():
+        c.batch_run_sam(opt)
+        sam = c.batch_sam()
+        c.batch_run_bam_sorted(opt)
+        return sam, c.batch_bam_sorted()
+
+    def same(x, y):
+        assert x[0] == y[0]
+        assert x[1][0] == y[1][0] and np.array_equal(x[1][1], y[1][1]) and np.array_equal(x[1][2], y[1][2])
+    before = resident()
+    assert before[0] == want and len(before[1][1]) > 0 and len(before[1][2]) == len(before[1][1]) + 1 and before[1][2][-1] == len(before[1][0])
+    fq1, fq2 = pe100
+    st, got = _stream(ctx3[:2], fq1, fq2, str(tmp_path / "o.sam"), K_100)
+    assert got == _oracle(small_index["prefix"], [fq1, fq2], K_100) and st.n_batches == 6 and st.n_reads == 600
+    same(resident(), before)
+    fd = os.open(str(tmp_path / "o.bam"), os.O_WRONLY | os.O_CREAT | os.O_TRUNC, 0o644)
+    try:
+        st, so = bw.stream_run_bam_sorted(ctx3[:2], fq1, fq2, fd, "@PG\tID:bwahip", 0, opt, chunk_bases=K_100, reader_threads=2)
+    finally:
+        os.close(fd)
+    assert st.n_batches == 6 and st.n_reads == 600
+    same(resident(), before)
+
+
+FORMS = ["text", "bam", "bam_sorted", "bgzf"]
+
+
+def _one_piece(c, form, reads, np0, opt):
+    """One bwahip_process_seqs_<form> call: the (address, bytes) of every buffer it hands out, and the scalars beside them"""
+    arr, keep = bw.seq_array(*reads)
+    n, L = len(reads[0]), bw.lib()
+    ln = C.c_int64()
+    if form == "text":
+        sam, off = C.c_char_p(), C.POINTER(C.c_int64)()
+        rc = L.bwahip_process_seqs_text(c._h, C.byref(opt), np0, n, arr, None, C.byref(sam), C.byref(ln), C.byref(off))
+        out = [(C.cast(sam, C.c_void_p).value, ln.value)], ()
+    elif form == "bam":
+        p, off = C.c_void_p(), C.POINTER(C.c_int64)()
+        rc = L.bwahip_process_seqs_bam(c._h, C.byref(opt), np0, n, arr, None, C.byref(p), C.byref(ln), C.byref(off))
+        out = [(p.value, ln.value)], ()
+    elif form == "bam_sorted":
+        p, keys, roff, nr = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_int64()
+        rc = L.bwahip_process_seqs_bam_sorted(c._h, C.byref(opt), np0, n, arr, None, C.byref(p), C.byref(ln), C.byref(keys), C.byref(roff), C.byref(nr))
+        out = [(p.value, ln.value), (keys.value, nr.value * 8), (roff.value, (nr.value + 1) * 8)], ()
+    else:
+        p, raw, nb = C.c_void_p(), C.c_int64(), C.c_int64()
+        rc = L.bwahip_process_seqs_bgzf(c._h, C.byref(opt), np0, n, arr, None, C.byref(p), C.byref(ln), C.byref(raw), C.byref(nb))
+        out = [(p.value, ln.value)], (raw.value, nb.value)
+    assert rc == 0
+    return out
+
+
+def _bytes_at(pieces):
+    return [C.string_at(addr, n) for addr, n in pieces]
+
+
+@pytest.fixture(scope="module")
+def two_batches(small_index, pe_inputs):
+    """two different batches of 200 reads (2 x 150) and, per output form, what a fresh context hands out for each (copied at once)"""
+    a, b, n_reads, _ = pe_inputs[2]
+    names, seqs, quals = _interleaved(a, b)
+    assert n_reads == len(names) == 400
+    batches = [(names[lo:lo + 200], seqs[lo:lo + 200], quals[lo:lo + 200]) for lo in (0, 200)]
+    want = {}
+    with bw.Context(small_index["prefix"]) as fresh:
+        for form in FORMS:
+            want[form] = []
+            for k, reads in enumerate(batches):
+                pieces, scalars = _one_piece(fresh, form, reads, 200 * k, _pe_opt())
+                want[form].append((_bytes_at(pieces), scalars))
+    return batches, want
+
+
+@pytest.mark.parametrize("form", FORMS)
+def test_one_piece_calls_take_their_buffers_in_turn(ctx3, two_batches, form):
+    """Every one-piece form keeps the documented lifetime: after the second of two consecutive calls on different batches the first call's
+    bytes still stand at the addresses it returned -- records, and for the sorted form keys and record offsets, which have pinned buffers
+    of their own -- and both equal what a fresh context gives."""
+    batches, want = two_batches
+    opt = _pe_opt()
+    first, scalars1 = _one_piece(ctx3[0], form, batches[0], 0, opt)
+    second, scalars2 = _one_piece(ctx3[0], form, batches[1], 200, opt)
+    assert all(n > 0 for _, n in first + second)
+    assert want[form][0][0] != want[form][1][0]
+    assert (_bytes_at(second), scalars2) == want[form][1]
+    assert (_bytes_at(first), scalars1) == want[form][0]          # still there after the call that followed it
+
+
+def test_comments_come_and_go_on_the_direct_path(ctx3, pe100, small_index, tmp_path):
+    """-C through bwahip_process_seqs_text on one context: a batch with comments, one without, one with -- the comment buffer stays with the
+    context and the kernels are told per batch whether it counts.  Each batch against the oracle's SAM of that batch alone."""
+    r1, r2 = _records(pe100[0]), _records(pe100[1])
+    opt = _pe_opt()
+    for k in range(3):
+        pairs = range(100 * k, 100 * k + 100)
+        cm = [b"BC:Z:" + b"ACGT"[i % 4:i % 4 + 1] * 6 + b"\tXY:i:%d" % i if k != 1 and i % 3 else None for i in pairs]
+        a, b = str(tmp_path / f"c{k}_1.fq"), str(tmp_path / f"c{k}_2.fq")
+        _write(a, [r1[i] for i in pairs]); _write(b, [r2[i] for i in pairs])
+        names, seqs, quals = _interleaved(a, b)
+        for path, recs in ((a, r1), (b, r2)):
+            _write(path, [[recs[i][0] + (b" " + c if c else b"")] + recs[i][1:] for i, c in zip(pairs, cm)])
+        want = _oracle(small_index["prefix"], [a, b], 1 << 30, ["-C"])
+        assert (b"\tBC:Z:" in want) == (k != 1)
+        arr, keep = bw.seq_array(names, seqs, quals, [c for c in cm for _ in (0, 1)])
+        assert ctx3[0].process_seqs_text_array(arr, 200, opt) == want, f"batch {k}"
