@@ -98,6 +98,18 @@ class BaiStats(C.Structure):  # bwahip_bai_stats_t
                 ("index_ms", C.c_double)]
 
 
+class DupDesc(C.Structure):  # bwahip_dup_desc_t
+    _fields_ = [("end", C.c_uint64 * 2), ("score", C.c_uint32), ("kind", C.c_uint32)]
+
+
+DUP_DESC_DTYPE = np.dtype([("end", np.uint64, (2,)), ("score", np.uint32), ("kind", np.uint32)])   # the same 24 bytes as a numpy record
+
+
+class MarkdupStats(C.Structure):  # bwahip_markdup_stats_t
+    _fields_ = [("n_templates", C.c_int64 * 3), ("n_dup_templates", C.c_int64 * 3), ("n_marked", C.c_int64), ("hbm_bytes", C.c_int64),
+                ("markdup_ms", C.c_double), ("decide_ms", C.c_double), ("mark_ms", C.c_double)]
+
+
 ERRORS = {0: "ok", -1: "EINVAL", -2: "ENODEV", -3: "ENOMEM", -4: "EIO", -5: "ECAPACITY", -6: "EINTERNAL"}
 
 STAGE_INTV, STAGE_CHAIN, STAGE_CHAIN_FLT, STAGE_REGS, STAGE_REGS_PRE, STAGE_SEEDS = 1, 2, 3, 4, 5, 6
@@ -200,6 +212,21 @@ def lib():
                                                    C.POINTER(StreamStats), C.POINTER(SortStats), C.c_int]
     L.bwahip_stream_run_bam_sorted_dev_bai.argtypes = [C.POINTER(vp), C.c_int, C.POINTER(Opt), C.POINTER(PeStat), C.c_char_p, C.c_char_p, C.c_int, C.c_char_p,
                                                        C.POINTER(StreamStats), C.POINTER(SortDevStats), C.c_int]
+    L.bwahip_dup_end_word.argtypes = [C.c_int32, C.c_int32, C.c_int]
+    L.bwahip_dup_end_word.restype = C.c_uint64
+    L.bwahip_markdup_decide_host.argtypes = [vp, C.c_int64, vp]
+    L.bwahip_process_seqs_bam_sorted_dup.argtypes = [vp, C.POINTER(Opt), C.c_int64, C.c_int, C.POINTER(Seq), C.c_void_p, C.POINTER(vp), i64p, C.POINTER(vp), C.POINTER(vp), i64p,
+                                                     C.POINTER(vp), C.POINTER(vp), i64p]
+    L.bwahip_bam_devmerger_add_dup.argtypes = [vp, C.c_int64, vp, C.c_int64, vp, vp, C.c_int64, vp, vp, C.c_int64]
+    L.bwahip_bam_devmerger_finish_markdup.argtypes = [vp, C.c_int, C.c_int, C.c_int64, C.c_int32, C.POINTER(DevMergeStats), C.POINTER(BaiStats), C.POINTER(MarkdupStats)]
+    L.bwahip_bam_devmerge_markdup_hbm_need.argtypes = [C.c_int64, C.c_int64]
+    L.bwahip_bam_devmerge_markdup_hbm_need.restype = C.c_int64
+    L.bwahip_stream_run_bam_sorted_dev_markdup.argtypes = [C.POINTER(vp), C.c_int, C.POINTER(Opt), C.POINTER(PeStat), C.c_char_p, C.c_char_p, C.c_int, C.c_char_p,
+                                                           C.POINTER(StreamStats), C.POINTER(SortDevStats), C.c_int, C.POINTER(MarkdupStats)]
+    L.bwahip_kat_dup_desc.argtypes = [vp, vp, vp, C.c_int64, C.c_int, vp]
+    L.bwahip_kat_markdup.argtypes = [vp, vp, C.c_int64, vp]
+    L.bwahip_kat_dup_desc_ms.argtypes = [vp]
+    L.bwahip_kat_dup_desc_ms.restype = C.c_float
     L.bwahip_kat_radix_sort.argtypes = [vp, C.c_int64, vp, C.c_int, vp, C.POINTER(C.c_int)]
     L.bwahip_fastq_open.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(vp)]
     L.bwahip_fastq_next.argtypes = [vp, C.c_int64, C.c_int, C.POINTER(C.POINTER(Seq)), C.POINTER(C.c_int)]
@@ -391,6 +418,24 @@ class DevMerger:
         _check(lib().bwahip_bam_devmerger_finish(self._h, fd, C.byref(st)), "bwahip_bam_devmerger_finish")
         return st
 
+    def add_dup(self, run_no, rec, keys, rec_off, tmpl, desc):
+        """bwahip_bam_devmerger_add_dup: add, with the records' template indices (uint32) and the templates' descriptors (DUP_DESC_DTYPE)."""
+        rec = bytes(rec)
+        keys = np.ascontiguousarray(keys, dtype=np.uint64)
+        rec_off = np.ascontiguousarray(rec_off, dtype=np.int64)
+        tmpl = np.ascontiguousarray(tmpl, dtype=np.uint32)
+        desc = np.ascontiguousarray(desc, dtype=DUP_DESC_DTYPE)
+        _check(lib().bwahip_bam_devmerger_add_dup(self._h, run_no, rec, len(rec), keys.ctypes.data, rec_off.ctypes.data, len(keys), tmpl.ctypes.data, desc.ctypes.data, len(desc)),
+               "bwahip_bam_devmerger_add_dup")
+
+    def finish_markdup(self, fd=-1, bai_fd=-1, first_member_offset=0, n_ref=-1):
+        """bwahip_bam_devmerger_finish_markdup: duplicates marked in HBM (csrc/k_markdup.hip), then finish (n_ref < 0: no index) or
+        finish_bai; returns (DevMergeStats, BaiStats, MarkdupStats)."""
+        st, bs, ms = DevMergeStats(), BaiStats(), MarkdupStats()
+        _check(lib().bwahip_bam_devmerger_finish_markdup(self._h, fd, bai_fd, first_member_offset, n_ref, C.byref(st), C.byref(bs), C.byref(ms)),
+               "bwahip_bam_devmerger_finish_markdup")
+        return st, bs, ms
+
     def finish_bai(self, fd=-1, bai_fd=-1, first_member_offset=0, n_ref=0):
         """bwahip_bam_devmerger_finish_bai: finish, and the BAI index of the sorted records on bai_fd (csrc/k_bai.hip); returns
         (DevMergeStats, BaiStats)."""
@@ -413,6 +458,24 @@ class DevMerger:
 def bam_devmerge_hbm_need(raw_bytes, n_records, n_runs, piece_blocks):
     """bwahip_bam_devmerge_hbm_need: the HBM a device merger takes for these runs, finish included (no device)."""
     return lib().bwahip_bam_devmerge_hbm_need(raw_bytes, n_records, n_runs, piece_blocks)
+
+
+def bam_devmerge_markdup_hbm_need(n_records, n_templates):
+    """bwahip_bam_devmerge_markdup_hbm_need: the HBM duplicate marking adds to bam_devmerge_hbm_need (no device)."""
+    return lib().bwahip_bam_devmerge_markdup_hbm_need(n_records, n_templates)
+
+
+def dup_end_word(ref_id, u5, reverse):
+    """bwahip_dup_end_word: the end word of a mapped primary record (no device)."""
+    return int(lib().bwahip_dup_end_word(ref_id, u5, int(bool(reverse))))
+
+
+def markdup_decide_host(desc):
+    """bwahip_markdup_decide_host: one byte per template, 1 = duplicate (the decision restated on the host; no device)."""
+    desc = np.ascontiguousarray(desc, dtype=DUP_DESC_DTYPE)
+    dup = np.zeros(max(1, len(desc)), dtype=np.uint8)
+    _check(lib().bwahip_markdup_decide_host(desc.ctypes.data if len(desc) else None, len(desc), dup.ctypes.data), "bwahip_markdup_decide_host")
+    return dup[:len(desc)]
 
 
 def bam_devmerge_bai_hbm_need(n_records, n_blocks, n_ref, n_windows):
@@ -697,6 +760,25 @@ class Context:
         arr, keep = seq_array(names, seqs, quals, comments)
         return self.process_seqs_bam_sorted_array(arr, len(seqs), opt, n_processed, pes0)
 
+    def process_seqs_bam_sorted_dup_array(self, arr, n, opt=None, n_processed=0, pes0=None):
+        """bwahip_process_seqs_bam_sorted_dup: process_seqs_bam_sorted_array's three, then the records' template indices (uint32 array) and the
+        templates' descriptors (DUP_DESC_DTYPE array)."""
+        opt = opt or default_opt()
+        bam, ln, keys, off, nr = C.c_void_p(), C.c_int64(), C.c_void_p(), C.c_void_p(), C.c_int64()
+        tmpl, desc, nt = C.c_void_p(), C.c_void_p(), C.c_int64()
+        _check(lib().bwahip_process_seqs_bam_sorted_dup(self._h, C.byref(opt), n_processed, n, arr, pes0, C.byref(bam), C.byref(ln), C.byref(keys), C.byref(off), C.byref(nr),
+                                                        C.byref(tmpl), C.byref(desc), C.byref(nt)), "bwahip_process_seqs_bam_sorted_dup")
+        k = np.frombuffer(big_bytes(keys, nr.value * 8), dtype=np.uint64).copy()
+        o = np.frombuffer(big_bytes(off, (nr.value + 1) * 8), dtype=np.int64).copy()
+        t = np.frombuffer(big_bytes(tmpl, nr.value * 4), dtype=np.uint32).copy()
+        d = np.frombuffer(big_bytes(desc, nt.value * 24), dtype=DUP_DESC_DTYPE).copy()
+        return big_bytes(bam, ln.value), k, o, t, d
+
+    def process_seqs_bam_sorted_dup(self, names, seqs, quals=None, opt=None, n_processed=0, pes0=None, comments=None):
+        """The same from lists of names / ASCII reads (/ qualities, comments)."""
+        arr, keep = seq_array(names, seqs, quals, comments)
+        return self.process_seqs_bam_sorted_dup_array(arr, len(seqs), opt, n_processed, pes0)
+
     def process_seqs_bgzf_array(self, arr, n, opt=None, n_processed=0, pes0=None):
         """bwahip_process_seqs_bgzf on a bseq1_t array: (the BGZF members of the batch's BAM records as one bytes object, the uncompressed
         bytes of the records, the number of members).  No file header, no end-of-file block."""
@@ -830,6 +912,28 @@ class Context:
             out = np.empty(ln.value, dtype=np.uint8)                # the first answer said how much it takes
         _check(rc, "bwahip_kat_bai")
         return out[:ln.value].tobytes()
+
+    def kat_dup_desc(self, rec, off, paired=False):
+        """The batch's descriptor kernel (csrc/k_markdup.hip) on these records in input order: read i = rec[off[i]:off[i+1]]; one
+        descriptor per read, or per two reads (paired), as a DUP_DESC_DTYPE array."""
+        rec = bytes(rec)
+        off = np.ascontiguousarray(off, dtype=np.int64)
+        n = len(off) - 1
+        src = np.frombuffer(rec, dtype=np.uint8) if rec else np.zeros(1, dtype=np.uint8)
+        desc = np.zeros(max(1, n // 2 if paired else n), dtype=DUP_DESC_DTYPE)
+        _check(lib().bwahip_kat_dup_desc(self._h, src.ctypes.data, off.ctypes.data, n, int(bool(paired)), desc.ctypes.data), "bwahip_kat_dup_desc")
+        return desc[:n // 2 if paired else n]
+
+    def kat_dup_desc_ms(self):
+        """The descriptor kernel's GPU milliseconds in the last kat_dup_desc (HIP events around the kernel alone)."""
+        return float(lib().bwahip_kat_dup_desc_ms(self._h))
+
+    def kat_markdup(self, desc):
+        """The decision stage of a marked finish (csrc/k_markdup.hip) on these descriptors: one byte per template, 1 = duplicate."""
+        desc = np.ascontiguousarray(desc, dtype=DUP_DESC_DTYPE)
+        dup = np.zeros(max(1, len(desc)), dtype=np.uint8)
+        _check(lib().bwahip_kat_markdup(self._h, desc.ctypes.data if len(desc) else None, len(desc), dup.ctypes.data), "bwahip_kat_markdup")
+        return dup[:len(desc)]
 
     def kat_radix_sort(self, keys, key_bits=64):
         """(permutation, tile): the product's stable radix sort on these uint64 keys; tile = items one workgroup ranks per pass."""
@@ -1097,6 +1201,25 @@ def stream_run_bam_sorted_dev_bai(ctxs, fq1, fq2=None, out_fd=-1, bai_fd=-1, hdr
     _check(lib().bwahip_stream_run_bam_sorted_dev_bai(arr, len(ctxs), C.byref(opt), C.byref(pes0) if pes0 is not None else None, os.fsencode(fq1),
                                                       os.fsencode(fq2) if fq2 else None, out_fd, hdr_line, C.byref(st), C.byref(sd), bai_fd), "bwahip_stream_run_bam_sorted_dev_bai")
     return st, sd
+
+
+def stream_run_bam_sorted_dev_markdup(ctxs, fq1, fq2=None, out_fd=-1, bai_fd=-1, hdr_line=None, opt=None, chunk_bases=0, max_reads=0, keep_comments=False,
+                                      reader_threads=0, pes0=None, hbm_budget=0, piece_blocks=0):
+    """bwahip_stream_run_bam_sorted_dev_markdup: stream_run_bam_sorted_dev_bai with duplicates marked on the device before the deflate
+    (bai_fd < 0: no index).  No host fall-back: a run that does not fit hbm_budget raises ECAPACITY.  Returns (StreamStats, SortDevStats,
+    MarkdupStats)."""
+    opt = opt or default_opt()
+    st, sd, ms = StreamStats(), SortDevStats(), MarkdupStats()
+    st.chunk_bases, st.max_reads, st.keep_comments, st.reader_threads = chunk_bases, max_reads, int(keep_comments), reader_threads
+    sd.tmp_dir, sd.mem_budget, sd.level = None, 0, 1
+    sd.hbm_budget, sd.piece_blocks = hbm_budget, piece_blocks
+    arr = (C.c_void_p * len(ctxs))(*[c._h for c in ctxs])
+    if isinstance(hdr_line, str):
+        hdr_line = hdr_line.encode()
+    _check(lib().bwahip_stream_run_bam_sorted_dev_markdup(arr, len(ctxs), C.byref(opt), C.byref(pes0) if pes0 is not None else None, os.fsencode(fq1),
+                                                          os.fsencode(fq2) if fq2 else None, out_fd, hdr_line, C.byref(st), C.byref(sd), bai_fd, C.byref(ms)),
+           "bwahip_stream_run_bam_sorted_dev_markdup")
+    return st, sd, ms
 
 
 def _tool(name):

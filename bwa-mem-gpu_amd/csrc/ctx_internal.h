@@ -95,9 +95,10 @@ struct BatchText {
 // (digit, workgroup) histogram and its scan; `raw`: the batch's records in input order (the sorted ones go to d_sam).
 struct BamSort {
 	DevBuf raw, rec_cnt, rec_base, keys[2], idx[2], off, len, len_sorted, hist, hist_base, bits;
+	DevBuf tmpl;                         // OutForm::BamSortedDup: per record in input order the index of its template (k_markdup.hip)
 	float ms[3] = { 0, 0, 0 };           // record table, radix sort, gather of the last timed run
 	int n_passes = 0;                    // radix passes the last sort ran
-	void release() { for (DevBuf *b : { &raw, &rec_cnt, &rec_base, &keys[0], &keys[1], &idx[0], &idx[1], &off, &len, &len_sorted, &hist, &hist_base, &bits }) b->release(); }
+	void release() { for (DevBuf *b : { &raw, &rec_cnt, &rec_base, &keys[0], &keys[1], &idx[0], &idx[1], &off, &len, &len_sorted, &hist, &hist_base, &bits, &tmpl }) b->release(); }
 };
 
 // Working set of the deflate stage (k_bgzf.hip), one per context: a 64 KiB slot per BGZF block for the member as it is formed, the
@@ -110,8 +111,10 @@ struct Bgzf {
 
 // The form a batch's output leaves run_final in (d_sam): SAM text; BAM records in read order (k_bam.hip); the records in coordinate order with their
 // keys and offsets (k_bamsort.hip: written to bs.raw, sorted into d_sam); the records as BGZF members (k_bgzf.hip: written to bs.raw, deflated into d_sam)
-enum class OutForm { Sam, Bam, BamSorted, Bgzf };
+// BamSortedDup: BamSorted, and what duplicate marking in a device merger needs (k_markdup.hip): per record its template's index, per template its descriptor
+enum class OutForm { Sam, Bam, BamSorted, Bgzf, BamSortedDup };
 inline bool is_bam(OutForm f) { return f != OutForm::Sam; }
+inline bool is_sorted(OutForm f) { return f == OutForm::BamSorted || f == OutForm::BamSortedDup; }
 
 // What a batch arrives in: bases (codes 0..4 once k_nt4_conv has run), qualities, names, comments and their offsets in HBM, the pinned buffer they
 // travel through, and the event behind the last copy to HBM (stream path).  One type for the context's own batch and for the stream driver's sets.
@@ -133,15 +136,16 @@ struct BatchIn {
 // What run_final leaves behind: the batch in `form` in d_sam (`total` bytes of text or records; OutForm::Bgzf: of the records the members hold)
 // with the reads' offsets; BamSorted: n_rec keys and n_rec + 1 offsets of the records, the events at the begin of the record table, of the
 // radix sort, of the gather, and at the end; Bgzf: d_tot = [0] the members' bytes, [1] members that left stored (int64 each, in HBM), n_blocks
-// members, the events around the deflate stage; n_stored: d_tot[1] once it has been read back.
+// members, the events around the deflate stage; n_stored: d_tot[1] once it has been read back.  BamSortedDup: beside the keys n_rec template
+// indices in d_tmpl, and n_tmpl descriptors in d_desc (with the descriptor kernel's error word behind them).
 struct BatchOut {
-	DevBuf d_sam, d_sam_off, d_keys, d_rec_off, d_tot;
+	DevBuf d_sam, d_sam_off, d_keys, d_rec_off, d_tot, d_tmpl, d_desc;
 	hipEvent_t ev_sort[4] = {}, ev_bgzf[2] = {};
-	int64_t total = 0, n_rec = 0, n_blocks = 0, n_stored = 0;
+	int64_t total = 0, n_rec = 0, n_blocks = 0, n_stored = 0, n_tmpl = 0;
 	OutForm form = OutForm::Sam;
 	void release()
 	{
-		for (DevBuf *b : { &d_sam, &d_sam_off, &d_keys, &d_rec_off, &d_tot }) b->release();
+		for (DevBuf *b : { &d_sam, &d_sam_off, &d_keys, &d_rec_off, &d_tot, &d_tmpl, &d_desc }) b->release();
 		for (hipEvent_t e : ev_sort) if (e) (void)hipEventDestroy(e);
 		for (hipEvent_t e : ev_bgzf) if (e) (void)hipEventDestroy(e);
 	}
@@ -150,11 +154,11 @@ struct BatchOut {
 // The pinned buffers a BatchOut comes back into -- one per set of the stream driver, two taken in turn for the context's own set (the one-piece
 // entries of bwahip_process_seqs*) -- and the events of the way back (stream path): the write pass has ended / the bytes are in h_sam
 struct PinnedOut {
-	HostBuf h_sam, h_keys, h_rec_off;
+	HostBuf h_sam, h_keys, h_rec_off, h_tmpl, h_desc;
 	hipEvent_t ev_written = nullptr, ev_copied = nullptr;
 	void release()
 	{
-		h_sam.release(); h_keys.release(); h_rec_off.release();
+		h_sam.release(); h_keys.release(); h_rec_off.release(); h_tmpl.release(); h_desc.release();
 		if (ev_written) (void)hipEventDestroy(ev_written);
 		if (ev_copied) (void)hipEventDestroy(ev_copied);
 	}
@@ -220,6 +224,7 @@ struct bwahip_ctx {
 	DevBuf d_pool, d_fmisc, d_fredo, d_bigz, d_rec_list, d_xa_list, d_sam_len;
 	int64_t total_tasks = 0;
 	size_t pool_cap = 0;
+	float dup_desc_ms = 0;               // k_dup_desc in the last bwahip_kat_dup_desc
 	float final_ms[8] = { 0 };           // k_mark, k_cigar, k_sam(size), k_sam(write) of the last run
 	int intv_cap = 96;                   // current capacity (starts at knobs.intv_cap, grows on overflow)
 	int64_t total_seeds = 0, total_regs = 0;
@@ -257,7 +262,8 @@ inline void stage_rec(std::vector<int64_t> &o, int64_t tag, const std::vector<in
 int run_final(bwahip_ctx *c, const bwahip_opt_t *opt, int64_t n_processed, const bwahip_pestat_t *pes0, bool timed, OutForm form, bool host_sam_off = false, bool pe_stage_stop = false);   // regions in HBM -> the batch in `form` in HBM (SE, or PE when opt->flag has MEM_F_PE); host_sam_off: the offsets travel to h_sam_off ahead of the write pass (bwahip_process_seqs)
 // k_bamsort.hip: the records of c->bs.raw (per-read offsets c->out->d_sam_off, n_reads + 1) in coordinate order into c->out->d_sam, their keys
 // into c->out->d_keys, their offsets into c->out->d_rec_off; sets c->out->n_rec.  Queued on c->stream (with two small read-backs awaited in between).
-int bam_sort_batch(bwahip_ctx *c, int n_reads, int64_t total);
+// dup_tmpl: 0, or the reads of a template (1, 2): then also the templates' descriptors into c->out->d_desc and the records' templates into c->out->d_tmpl
+int bam_sort_batch(bwahip_ctx *c, int n_reads, int64_t total, int dup_tmpl = 0);
 // the stable LSD radix sort of bam_sort_batch alone, over c->bs.keys[0] / idx[0] (n items): the result is in keys[*which] / idx[*which]
 int bam_sort_radix(bwahip_ctx *c, int n, int key_bits, int *which);
 int bam_sort_iota(unsigned *idx, int n, hipStream_t st);
@@ -272,10 +278,16 @@ inline int64_t bgzf_blocks(int64_t len) { return (len + 65279) / 65280; }
 // source is free on return); a failed allocation: BWAHIP_ENOMEM and nothing is held.  bam_devmerger_adopt registers the run under
 // run_no and owns it from then on (refused: the caller still owns it).  bam_devrun_download copies a run to host buffers of at least
 // len, n_rec and n_rec + 1 items.
-struct DevRun { int64_t n_rec = 0, len = 0; uint8_t *rec = nullptr; uint64_t *keys = nullptr; int64_t *off = nullptr; int device = 0; };   // allocated to size: no slack
+// With duplicate marking (has_dup): n_rec template indices and n_tmpl descriptors as well.
+struct DevRun {
+	int64_t n_rec = 0, len = 0; uint8_t *rec = nullptr; uint64_t *keys = nullptr; int64_t *off = nullptr; int device = 0;   // allocated to size: no slack
+	bool has_dup = false; int64_t n_tmpl = 0; uint32_t *tmpl = nullptr; bwahip_dup_desc_t *desc = nullptr;
+};
 int  bam_devrun_make(bwahip_ctx *c, const uint8_t *d_rec, int64_t len, const uint64_t *d_keys, const int64_t *d_rec_off, int64_t n_rec, hipStream_t st, DevRun **out);
 int  bam_devrun_download(const DevRun *r, uint8_t *rec, uint64_t *keys, int64_t *rec_off, hipStream_t st);
 void bam_devrun_free(DevRun *r);
+// the run's template indices and descriptors, copied from device pointers on st as bam_devrun_make copies the records (BWAHIP_ENOMEM: the run is as before)
+int  bam_devrun_add_dup(DevRun *r, const uint32_t *d_tmpl, const bwahip_dup_desc_t *d_desc, int64_t n_tmpl, hipStream_t st);
 int  bam_devmerger_adopt(bwahip_bam_devmerger *m, int64_t run_no, DevRun *r);
 // the device-to-device form of bwahip_bam_devmerger_add: make + adopt
 int  bam_devmerger_add_dev(bwahip_bam_devmerger *m, int64_t run_no, const uint8_t *d_rec, int64_t len, const uint64_t *d_keys, const int64_t *d_rec_off, int64_t n_rec, hipStream_t st);
@@ -290,6 +302,23 @@ void bai_stage_free(BaiStage *s);
 int  bai_stage_members(BaiStage *s, int64_t n_blocks, int **mlen);
 int  bai_stage_run(BaiStage *s, bwahip_ctx *c, int n, const uint8_t *const *addr, const unsigned *idx, const int64_t *out_off, int64_t total, int64_t n_blocks, int64_t base,
                    int32_t n_ref, std::vector<uint8_t> *bytes, bwahip_bai_stats_t *bs);
+// k_markdup.hip.  Per batch, from bam_sort_batch: dup_batch_desc after the record table (descriptors, templates in input order), dup_batch_tmpl
+// after the radix sort (templates in sorted order; awaits the descriptor kernel's error word).  The decision stage of a device merger's
+// marked finish: desc = the descriptors of all runs in run order; markdup_decide leaves one byte per template in dup (queued on c->stream, the
+// context's sort buffers are used); markdup_count and markdup_mark_run add to cnt ([0..5] templates and duplicates per kind, [6] records
+// marked, [7] the marking pass's error word), which markdup_counters_reset zeroes.
+struct MarkdupStage {
+	DevBuf desc, head, seg, best, pair_here, dup, cnt;
+	hipEvent_t ev[3] = {};               // begin, decision done, end
+	size_t bytes() const;
+	void release();
+};
+int dup_batch_desc(bwahip_ctx *c, int n_reads, bool paired, int64_t n_rec);
+int dup_batch_tmpl(bwahip_ctx *c, int n_rec, const unsigned *idx);
+int markdup_decide(MarkdupStage *s, bwahip_ctx *c, int64_t n_tmpl);
+int markdup_counters_reset(MarkdupStage *s, bwahip_ctx *c);
+int markdup_count(MarkdupStage *s, bwahip_ctx *c, int64_t n_tmpl);
+int markdup_mark_run(MarkdupStage *s, bwahip_ctx *c, uint8_t *rec, const int64_t *off, int64_t n_rec, int64_t len, const uint32_t *tmpl, int64_t first_tmpl, int64_t n_tmpl);
 int bam_check_reads(int n, const bwahip_seq_t *seqs);   // bam_host.cpp: BWAHIP_EINVAL (with a message naming the read) for a name or a comment BAM cannot hold
 void pipe_destroy(bwahip_ctx *c);                                                     // final_rt.hip: the stream driver's buffer sets
 int final_setup(bwahip_ctx *c);                                                       // contig name tables for the SAM kernels

@@ -194,8 +194,8 @@ int run_final(bwahip_ctx *c, const bwahip_opt_t *opt, int64_t n_processed, const
 	const int n = c->in->n;
 	const bool pe = (opt->flag & BWAHIP_F_PE) != 0;
 	BatchOut &o = *c->out;
-	o.total = 0; o.n_rec = 0; o.n_blocks = 0; o.n_stored = 0; o.form = form; c->total_tasks = 0;
-	const bool sorted = form == OutForm::BamSorted;               // the records leave in coordinate order: written to a scratch buffer, sorted into d_sam
+	o.total = 0; o.n_rec = 0; o.n_blocks = 0; o.n_stored = 0; o.n_tmpl = 0; o.form = form; c->total_tasks = 0;
+	const bool sorted = is_sorted(form);                          // the records leave in coordinate order: written to a scratch buffer, sorted into d_sam
 	const bool bgzf = form == OutForm::Bgzf;                      // the records leave as BGZF members: written to the same scratch buffer, deflated into d_sam
 	if (n == 0) return 0;
 	if (pe && (n & 1)) return BWAHIP_EINVAL;
@@ -335,7 +335,7 @@ int run_final(bwahip_ctx *c, const bwahip_opt_t *opt, int64_t n_processed, const
 	HIP_TRY(hipEventRecord(c->ev_sam_half, c->stream));
 	if ((rc = launch_out(f, true, c->sam_half_reads, n))) return rc;
 	if (timed) HIP_TRY(hipEventRecord(c->ev[19], c->stream));
-	if (sorted && (rc = bam_sort_batch(c, n, total))) return rc;
+	if (sorted && (rc = bam_sort_batch(c, n, total, form == OutForm::BamSortedDup ? (pe ? 2 : 1) : 0))) return rc;
 	if (bgzf) {                                                   // the deflate stage, queued behind the write pass
 		for (auto &e : o.ev_bgzf) if (!e) HIP_TRY(hipEventCreate(&e));
 		if ((rc = o.d_tot.ensure(16))) return rc;
@@ -496,6 +496,7 @@ struct SeqsOut {
 	const char **text = nullptr; int64_t *len = nullptr; const int64_t **off = nullptr;   // off: the reads' offsets (optional; SAM text, BAM records)
 	const uint64_t **keys = nullptr; const int64_t **rec_off = nullptr; int64_t *n_rec = nullptr;   // BamSorted
 	int64_t *raw_len = nullptr, *n_blocks = nullptr;                                        // Bgzf
+	const uint32_t **tmpl = nullptr; const bwahip_dup_desc_t **desc = nullptr; int64_t *n_tmpl = nullptr;   // BamSortedDup
 };
 
 // The end of the one-piece forms that do not leave in read order: `bytes` of d_sam into the pinned buffer whose turn it is (valid until the
@@ -518,8 +519,9 @@ static int download_piece(bwahip_ctx *ctx, int64_t bytes, int n, bwahip_seq_t *s
 static int process_seqs_impl(bwahip_ctx *ctx, const bwahip_opt_t *opt, int64_t n_processed, int n, bwahip_seq_t *seqs, const bwahip_pestat_t *pes0, const SeqsOut &out)
 {
 	static const int64_t no_records[1] = { 0 };
-	const bool sorted = out.form == OutForm::BamSorted, bz = out.form == OutForm::Bgzf;
+	const bool sorted = is_sorted(out.form), bz = out.form == OutForm::Bgzf, dup = out.form == OutForm::BamSortedDup;
 	if (sorted) { *out.keys = nullptr; *out.rec_off = no_records; *out.n_rec = 0; }
+	if (dup) { *out.tmpl = nullptr; *out.desc = nullptr; *out.n_tmpl = 0; }
 	if (!ctx || !opt || n < 0 || (n && !seqs)) return BWAHIP_EINVAL;
 	const bool pe = (opt->flag & BWAHIP_F_PE) != 0;
 	if (pe && (n & 1)) return BWAHIP_EINVAL;
@@ -565,9 +567,16 @@ static int process_seqs_impl(bwahip_ctx *ctx, const bwahip_opt_t *opt, int64_t n
 			if ((r = pin.h_keys.ensure((size_t)(nr ? nr : 1) * 8)) || (r = pin.h_rec_off.ensure((size_t)(nr + 1) * 8))) return r;
 			if (nr) HIP_TRY(hipMemcpyAsync(pin.h_keys.p, ctx->out->d_keys.p, (size_t)nr * 8, hipMemcpyDeviceToHost, ctx->stream));
 			HIP_TRY(hipMemcpyAsync(pin.h_rec_off.p, ctx->out->d_rec_off.p, (size_t)(nr + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
+			if (dup) {
+				const int64_t nt_ = ctx->out->n_tmpl;
+				if ((r = pin.h_tmpl.ensure((size_t)(nr ? nr : 1) * 4)) || (r = pin.h_desc.ensure((size_t)(nt_ ? nt_ : 1) * sizeof(bwahip_dup_desc_t)))) return r;
+				if (nr) HIP_TRY(hipMemcpyAsync(pin.h_tmpl.p, ctx->out->d_tmpl.p, (size_t)nr * 4, hipMemcpyDeviceToHost, ctx->stream));
+				if (nt_) HIP_TRY(hipMemcpyAsync(pin.h_desc.p, ctx->out->d_desc.p, (size_t)nt_ * sizeof(bwahip_dup_desc_t), hipMemcpyDeviceToHost, ctx->stream));
+			}
 			return 0;
 		});
 		if (rc) return rc;
+		if (dup) { *out.tmpl = (const uint32_t*)ctx->pin[ctx->turn].h_tmpl.p; *out.desc = (const bwahip_dup_desc_t*)ctx->pin[ctx->turn].h_desc.p; *out.n_tmpl = ctx->out->n_tmpl; }
 		*out.keys = (const uint64_t*)ctx->pin[ctx->turn].h_keys.p; *out.rec_off = (const int64_t*)ctx->pin[ctx->turn].h_rec_off.p; *out.n_rec = nr;
 		return 0;
 	}
@@ -664,6 +673,18 @@ extern "C" int bwahip_process_seqs_bam_sorted(bwahip_ctx *ctx, const bwahip_opt_
 {
 	if (!bam || !bam_len || !keys || !rec_off || !n_rec) return BWAHIP_EINVAL;
 	return process_seqs_impl(ctx, opt, n_processed, n, seqs, pes0, { OutForm::BamSorted, (const char**)bam, bam_len, nullptr, keys, rec_off, n_rec });
+}
+
+// bwahip_process_seqs_bam_sorted with what duplicate marking in a device merger needs (k_markdup.hip): per record the index of its template,
+// per template its descriptor
+extern "C" int bwahip_process_seqs_bam_sorted_dup(bwahip_ctx *ctx, const bwahip_opt_t *opt, int64_t n_processed, int n, bwahip_seq_t *seqs, const bwahip_pestat_t *pes0,
+                                                  const uint8_t **bam, int64_t *bam_len, const uint64_t **keys, const int64_t **rec_off, int64_t *n_rec,
+                                                  const uint32_t **tmpl, const bwahip_dup_desc_t **desc, int64_t *n_tmpl)
+{
+	if (!bam || !bam_len || !keys || !rec_off || !n_rec || !tmpl || !desc || !n_tmpl) return BWAHIP_EINVAL;
+	SeqsOut so = { OutForm::BamSortedDup, (const char**)bam, bam_len, nullptr, keys, rec_off, n_rec };
+	so.tmpl = tmpl; so.desc = desc; so.n_tmpl = n_tmpl;
+	return process_seqs_impl(ctx, opt, n_processed, n, seqs, pes0, so);
 }
 
 // bwahip_process_seqs_bam with the records leaving the GPU as BGZF members (k_bgzf.hip): *bgzf = the members of the batch's records, cut
@@ -1004,7 +1025,7 @@ int pipe_stage_out_sorted(bwahip_ctx *c, int out, const uint64_t **keys, const i
 	HIP_TRY(hipSetDevice(c->device));
 	const BatchOut &o = c->pipe->out[out];
 	PinnedOut &pin = c->pipe->pin[out];
-	if (o.form != OutForm::BamSorted) return BWAHIP_EINVAL;
+	if (!is_sorted(o.form)) return BWAHIP_EINVAL;
 	int rc;
 	if ((rc = pin.h_keys.ensure((size_t)(o.n_rec ? o.n_rec : 1) * 8)) || (rc = pin.h_rec_off.ensure((size_t)(o.n_rec + 1) * 8))) return rc;
 	if (o.n_rec) HIP_TRY(hipMemcpyAsync(pin.h_keys.p, o.d_keys.p, (size_t)o.n_rec * 8, hipMemcpyDeviceToHost, c->stream_copy));
@@ -1027,10 +1048,11 @@ int pipe_stage_out_devrun(bwahip_ctx *c, int out, DevRun **run, int64_t *raw_len
 	const BatchOut &o = c->pipe->out[out];
 	HIP_TRY(hipEventSynchronize(c->pipe->pin[out].ev_written));
 	if (t_kernels_end) *t_kernels_end = pipe_now();
-	if (o.form != OutForm::BamSorted) return BWAHIP_EINVAL;
+	if (!is_sorted(o.form)) return BWAHIP_EINVAL;
 	if (sort_ms) *sort_ms = sort_stage_ms(o);
 	*raw_len = o.total; *n_rec = o.n_rec;
-	const int rc = bam_devrun_make(c, o.d_sam.as<uint8_t>(), o.total, o.d_keys.as<uint64_t>(), o.d_rec_off.as<int64_t>(), o.n_rec, c->stream_copy, run);
+	int rc = bam_devrun_make(c, o.d_sam.as<uint8_t>(), o.total, o.d_keys.as<uint64_t>(), o.d_rec_off.as<int64_t>(), o.n_rec, c->stream_copy, run);
+	if (!rc && o.form == OutForm::BamSortedDup && (rc = bam_devrun_add_dup(*run, o.d_tmpl.as<uint32_t>(), o.d_desc.as<bwahip_dup_desc_t>(), o.n_tmpl, c->stream_copy))) { bam_devrun_free(*run); *run = nullptr; }
 	return rc == BWAHIP_ENOMEM ? 0 : rc;
 }
 

@@ -18,6 +18,9 @@
 //
 // Two piece inputs and two piece outputs: the gather and the deflate of piece k are queued on the context's stream while the 16-byte
 // total and then the members of piece k - 1 come back on the copy stream and are written.  No kernel here uses LDS or atomics.
+//
+// A marked finish (bwahip_bam_devmerger_finish_markdup) runs the duplicate decision and the marking pass of k_markdup.hip over the runs
+// before the order is made: one bit of a record changes and no key, so everything after it is the unmarked finish.
 #include "ctx_internal.h"
 #include "bai_tables.h"
 #include <errno.h>
@@ -167,6 +170,7 @@ struct bwahip_bam_devmerger {
 	int64_t n_records = 0, raw_bytes = 0;
 	Work w;
 	BaiStage *bai = nullptr;                                       // the index stage's buffers (k_bai.hip), made by the first finish_bai
+	MarkdupStage md;                                               // the marking stage's buffers (k_markdup.hip), grown by the first finish_markdup
 };
 
 namespace {
@@ -218,8 +222,23 @@ void bam_devrun_free(DevRun *r)
 {
 	if (!r) return;
 	(void)hipSetDevice(r->device);
-	for (void *p : { (void*)r->rec, (void*)r->keys, (void*)r->off }) if (p) { (void)hipFree(p); ++g_bwahip_reallocs; }
+	for (void *p : { (void*)r->rec, (void*)r->keys, (void*)r->off, (void*)r->tmpl, (void*)r->desc }) if (p) { (void)hipFree(p); ++g_bwahip_reallocs; }
 	delete r;
+}
+
+int bam_devrun_add_dup(DevRun *r, const uint32_t *d_tmpl, const bwahip_dup_desc_t *d_desc, int64_t n_tmpl, hipStream_t st)
+{
+	if (!r || r->has_dup || n_tmpl < 0 || (r->n_rec && !d_tmpl) || (n_tmpl && !d_desc)) return BWAHIP_EINVAL;
+	HIP_TRY(hipSetDevice(r->device));
+	uint32_t *t = nullptr; bwahip_dup_desc_t *d = nullptr;
+	int rc;
+	if ((r->n_rec && (rc = dev_alloc((void**)&t, (size_t)r->n_rec * 4))) || (n_tmpl && (rc = dev_alloc((void**)&d, (size_t)n_tmpl * sizeof *d)))) { if (t) (void)hipFree(t); return rc; }
+	hipError_t e = r->n_rec ? hipMemcpyAsync(t, d_tmpl, (size_t)r->n_rec * 4, hipMemcpyDeviceToDevice, st) : hipSuccess;
+	if (e == hipSuccess && n_tmpl) e = hipMemcpyAsync(d, d_desc, (size_t)n_tmpl * sizeof *d, hipMemcpyDeviceToDevice, st);
+	if (e == hipSuccess) e = hipStreamSynchronize(st);
+	if (e != hipSuccess) { fprintf(stderr, "[bwahip] sorted BAM: copying a run's templates failed: %s\n", hipGetErrorString(e)); if (t) (void)hipFree(t); if (d) (void)hipFree(d); return BWAHIP_ENODEV; }
+	r->tmpl = t; r->desc = d; r->n_tmpl = n_tmpl; r->has_dup = true;
+	return 0;
 }
 
 int bam_devmerger_adopt(bwahip_bam_devmerger *m, int64_t run_no, DevRun *r)
@@ -268,13 +287,20 @@ extern "C" int bwahip_bam_devmerger_open(bwahip_ctx *ctx, int piece_blocks, bwah
 	return 0;
 }
 
-extern "C" int bwahip_bam_devmerger_add(bwahip_bam_devmerger *m, int64_t run_no, const uint8_t *rec, int64_t len, const uint64_t *keys, const int64_t *rec_off, int64_t n_rec)
+// tmpl / desc / n_tmpl: bwahip_bam_devmerger_add_dup (with_dup)
+static int devmerger_add(bwahip_bam_devmerger *m, int64_t run_no, const uint8_t *rec, int64_t len, const uint64_t *keys, const int64_t *rec_off, int64_t n_rec,
+                         bool with_dup, const uint32_t *tmpl, const bwahip_dup_desc_t *desc, int64_t n_tmpl)
 {
 	if (!m || run_no < 0 || len < 0 || n_rec < 0 || (n_rec && (!rec || !keys || !rec_off)) || (!n_rec && len)) return BWAHIP_EINVAL;
 	if (n_rec && (rec_off[0] != 0 || rec_off[n_rec] != len)) return BWAHIP_EINVAL;
 	for (int64_t i = 0; i < n_rec; ++i) {
 		if (rec_off[i + 1] < rec_off[i]) return BWAHIP_EINVAL;
 		if (rec_off[i + 1] - rec_off[i] > 0x7fffffffll) return BWAHIP_ECAPACITY;   // lengths are scanned as int32
+	}
+	if (with_dup) {                                                // refused before anything is allocated
+		if (n_tmpl < 0 || n_tmpl > 0x3fffffffll || (n_rec && !tmpl) || (n_tmpl && !desc)) return BWAHIP_EINVAL;
+		for (int64_t i = 0; i < n_rec; ++i) if (tmpl[i] >= (uint64_t)n_tmpl) return BWAHIP_EINVAL;
+		for (int64_t i = 0; i < n_tmpl; ++i) if (desc[i].kind > 2) return BWAHIP_EINVAL;
 	}
 	bwahip_ctx *c = m->c;
 	{
@@ -292,22 +318,90 @@ extern "C" int bwahip_bam_devmerger_add(bwahip_bam_devmerger *m, int64_t run_no,
 		hipError_t e = len ? hipMemcpy(r->rec, rec, (size_t)len, hipMemcpyHostToDevice) : hipSuccess;
 		if (e == hipSuccess) e = hipMemcpy(r->keys, keys, (size_t)n_rec * 8, hipMemcpyHostToDevice);
 		if (e == hipSuccess) e = hipMemcpy(r->off, rec_off, (size_t)(n_rec + 1) * 8, hipMemcpyHostToDevice);
+		if (e == hipSuccess && with_dup && (rc = dev_alloc((void**)&r->tmpl, (size_t)n_rec * 4))) { bam_devrun_free(r); return rc; }
+		if (e == hipSuccess && with_dup) e = hipMemcpy(r->tmpl, tmpl, (size_t)n_rec * 4, hipMemcpyHostToDevice);
 		if (e == hipSuccess) e = hipDeviceSynchronize();
 		if (e != hipSuccess) { fprintf(stderr, "[bwahip] sorted BAM: uploading a run failed: %s\n", hipGetErrorString(e)); bam_devrun_free(r); return BWAHIP_ENODEV; }
 	}
+	if (with_dup && n_tmpl) {
+		if ((rc = dev_alloc((void**)&r->desc, (size_t)n_tmpl * sizeof *desc))) { bam_devrun_free(r); return rc; }
+		if (hipMemcpy(r->desc, desc, (size_t)n_tmpl * sizeof *desc, hipMemcpyHostToDevice) != hipSuccess || hipDeviceSynchronize() != hipSuccess) { bam_devrun_free(r); return BWAHIP_ENODEV; }
+	}
+	r->has_dup = with_dup; r->n_tmpl = with_dup ? n_tmpl : 0;
 	if ((rc = bam_devmerger_adopt(m, run_no, r))) bam_devrun_free(r);
 	return rc;
 }
 
+extern "C" int bwahip_bam_devmerger_add(bwahip_bam_devmerger *m, int64_t run_no, const uint8_t *rec, int64_t len, const uint64_t *keys, const int64_t *rec_off, int64_t n_rec)
+{
+	return devmerger_add(m, run_no, rec, len, keys, rec_off, n_rec, false, nullptr, nullptr, 0);
+}
+
+extern "C" int bwahip_bam_devmerger_add_dup(bwahip_bam_devmerger *m, int64_t run_no, const uint8_t *rec, int64_t len, const uint64_t *keys, const int64_t *rec_off, int64_t n_rec,
+                                            const uint32_t *tmpl, const bwahip_dup_desc_t *desc, int64_t n_tmpl)
+{
+	return devmerger_add(m, run_no, rec, len, keys, rec_off, n_rec, true, tmpl, desc, n_tmpl);
+}
+
+// The marked finish's own part, on the context's stream, before the order is made: the runs' descriptors concatenated in run order, the
+// decision, the counts, the marking pass over every run's records.  Awaited at its end (the counters come back).
+static int devmerger_mark(bwahip_bam_devmerger *m, bwahip_markdup_stats_t *ms)
+{
+	bwahip_ctx *c = m->c;
+	MarkdupStage &s = m->md;
+	int64_t T = 0, run_bytes = 0;
+	for (auto &kv : m->runs) { T += kv.second->n_tmpl; run_bytes += 4 * kv.second->n_rec + 24 * kv.second->n_tmpl; }
+	if (T > 0x3fffffffll) return BWAHIP_ECAPACITY;
+	HIP_TRY(hipSetDevice(c->device));
+	for (auto &e : s.ev) if (!e) HIP_TRY(hipEventCreate(&e));
+	int rc;
+	if ((rc = s.desc.ensure((size_t)(T ? T : 1) * sizeof(bwahip_dup_desc_t)))) return rc;
+	HIP_TRY(hipEventRecord(s.ev[0], c->stream));
+	int64_t at = 0;
+	for (auto &kv : m->runs) {
+		const DevRun *r = kv.second;
+		if (r->n_tmpl) HIP_TRY(hipMemcpyAsync(s.desc.as<bwahip_dup_desc_t>() + at, r->desc, (size_t)r->n_tmpl * sizeof(bwahip_dup_desc_t), hipMemcpyDeviceToDevice, c->stream));
+		at += r->n_tmpl;
+	}
+	if ((rc = markdup_decide(&s, c, T))) return rc;
+	HIP_TRY(hipEventRecord(s.ev[1], c->stream));
+	if ((rc = markdup_counters_reset(&s, c)) || (rc = markdup_count(&s, c, T))) return rc;
+	at = 0;
+	for (auto &kv : m->runs) {
+		DevRun *r = kv.second;
+		if ((rc = markdup_mark_run(&s, c, r->rec, r->off, r->n_rec, r->len, r->tmpl, at, r->n_tmpl))) return rc;
+		at += r->n_tmpl;
+	}
+	HIP_TRY(hipEventRecord(s.ev[2], c->stream));
+	unsigned long long cnt[8] = { 0 };
+	HIP_TRY(hipMemcpyAsync(cnt, s.cnt.p, 64, hipMemcpyDeviceToHost, c->stream));
+	HIP_TRY(hipStreamSynchronize(c->stream));
+	if ((int)cnt[7]) { fprintf(stderr, "[bwahip] duplicate marking: a record's offset or template index lies outside its run\n"); return BWAHIP_EINTERNAL; }
+	if (ms) {
+		for (int k = 0; k < 3; ++k) { ms->n_templates[k] = (int64_t)cnt[k]; ms->n_dup_templates[k] = (int64_t)cnt[3 + k]; }
+		ms->n_marked = (int64_t)cnt[6];
+		const BamSort &bs = c->bs;
+		ms->hbm_bytes = run_bytes + (int64_t)(s.bytes() + bs.keys[0].cap + bs.keys[1].cap + bs.idx[0].cap + bs.idx[1].cap);
+		float t = 0;
+		if (hipEventElapsedTime(&t, s.ev[0], s.ev[2]) == hipSuccess) ms->markdup_ms = t;
+		if (hipEventElapsedTime(&t, s.ev[0], s.ev[1]) == hipSuccess) ms->decide_ms = t;
+		if (hipEventElapsedTime(&t, s.ev[1], s.ev[2]) == hipSuccess) ms->mark_ms = t;
+	}
+	return 0;
+}
+
 // bai (may be NULL): the index stage after the last piece (bwahip_bam_devmerger_finish_bai); the members do not depend on it
-static int devmerger_finish(bwahip_bam_devmerger *m, int fd, bwahip_devmerge_stats_t *st, const BaiArgs *bai)
+// mark: the runs are marked first (bwahip_bam_devmerger_finish_markdup; ms may be null)
+static int devmerger_finish(bwahip_bam_devmerger *m, int fd, bwahip_devmerge_stats_t *st, const BaiArgs *bai, bool mark = false, bwahip_markdup_stats_t *ms = nullptr)
 {
 	if (!m) return BWAHIP_EINVAL;
 	std::lock_guard<std::mutex> lk(m->mu);
+	const double t0 = now_s();
+	if (mark) for (auto &kv : m->runs) if (!kv.second->has_dup) return BWAHIP_EINVAL;   // before a byte is written
+	if (mark) { const int r = devmerger_mark(m, ms); if (r) return r; }
 	if (bai && !m->bai) m->bai = bai_stage_new();
 	bwahip_ctx *c = m->c;
 	Work &w = m->w;
-	const double t0 = now_s();
 	bwahip_devmerge_stats_t s;
 	memset(&s, 0, sizeof s);
 	s.n_records = m->n_records; s.n_runs = (int64_t)m->runs.size(); s.raw_bytes = m->raw_bytes;
@@ -444,13 +538,23 @@ extern "C" int bwahip_bam_devmerger_finish_bai(bwahip_bam_devmerger *m, int fd, 
 	return devmerger_finish(m, fd, st, &a);
 }
 
+extern "C" int bwahip_bam_devmerger_finish_markdup(bwahip_bam_devmerger *m, int fd, int bai_fd, int64_t first_member_offset, int32_t n_ref, bwahip_devmerge_stats_t *st,
+                                                   bwahip_bai_stats_t *bs, bwahip_markdup_stats_t *ms)
+{
+	if (first_member_offset < 0 || first_member_offset >= (1ll << 48)) return BWAHIP_EINVAL;
+	if (bs) memset(bs, 0, sizeof *bs);
+	if (ms) memset(ms, 0, sizeof *ms);
+	const BaiArgs a = { bai_fd, first_member_offset, n_ref, bs };
+	return devmerger_finish(m, fd, st, n_ref >= 0 ? &a : nullptr, true, ms);   // n_ref < 0: no index
+}
+
 extern "C" void bwahip_bam_devmerger_close(bwahip_bam_devmerger *m)
 {
 	if (!m) return;
 	(void)hipSetDevice(m->c->device);
 	for (hipStream_t q : { m->c->stream_copy, m->c->stream }) if (q) (void)hipStreamSynchronize(q);   // after a failed finish work may still be queued on the buffers
 	for (auto &kv : m->runs) bam_devrun_free(kv.second);
-	m->w.release();
+	m->w.release(); m->md.release();
 	bai_stage_free(m->bai);
 	delete m;
 }

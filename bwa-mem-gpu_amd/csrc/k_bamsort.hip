@@ -220,7 +220,7 @@ int bam_sort_radix(bwahip_ctx *c, int n, int key_bits, int *which)
 	return 0;
 }
 
-int bam_sort_batch(bwahip_ctx *c, int n, int64_t total)
+int bam_sort_batch(bwahip_ctx *c, int n, int64_t total, int dup_tmpl)
 {
 	BamSort &s = c->bs;
 	c->out->n_rec = 0; s.n_passes = 0;
@@ -247,6 +247,7 @@ int bam_sort_batch(bwahip_ctx *c, int n, int64_t total)
 	hipLaunchKernelGGL(k_rec_fill, dim3(grid_n), dim3(256), 0, c->stream, raw, off, s.rec_base.as<int64_t>(), n, bns->n_seqs, bam_key_pos_bits(bns),
 	                   s.keys[0].as<uint64_t>(), s.idx[0].as<unsigned>(), s.off.as<int64_t>(), s.len.as<int>());
 	if ((rc = launched())) return rc;
+	if (dup_tmpl && (rc = dup_batch_desc(c, n, dup_tmpl == 2, n_rec))) return rc;   // the mates are still neighbours here
 	HIP_TRY(hipEventRecord(c->out->ev_sort[1], c->stream));
 	int cur = 0;
 	if ((rc = bam_sort_radix(c, (int)n_rec, bam_key_bits(bns), &cur))) return rc;
@@ -260,6 +261,7 @@ int bam_sort_batch(bwahip_ctx *c, int n, int64_t total)
 		                   c->out->d_rec_off.as<int64_t>(), nr, c->out->d_sam.as<uint8_t>());
 		if ((rc = launched())) return rc;
 	} else HIP_TRY(hipMemsetAsync(c->out->d_rec_off.p, 0, 8, c->stream));
+	if (dup_tmpl && (rc = dup_batch_tmpl(c, nr, s.idx[cur].as<unsigned>()))) return rc;
 	HIP_TRY(hipEventRecord(c->out->ev_sort[3], c->stream));
 	c->out->n_rec = n_rec;
 	(void)total;

@@ -153,6 +153,8 @@ struct DevSortedSink : Sink {
 	bwahip_sort_dev_t *sd; SortedSink host;
 	bwahip_bam_devmerger *dm = nullptr; bwahip_ctx *ctx0 = nullptr;
 	int64_t hbm_budget = 0, held_raw = 0, held_rec = 0; int piece_blocks = 0;
+	bwahip_markdup_stats_t *ms = nullptr; bool markdup = false;   // bwahip_stream_run_bam_sorted_dev_markdup: the runs carry templates, no fall-back
+	int64_t held_tmpl = 0;
 	int64_t bai_windows = 0;                                     // with the index: the 16 Kbp windows of the contig table, for the stage's share of the budget
 	std::atomic<bool> fell_back{false};                          // read by the drainers: from now on they download
 	hipStream_t fb_stream = nullptr; HostBuf fb_rec, fb_keys, fb_off;   // the fall-back's downloads: their stream, one pinned buffer each for records, keys and offsets
@@ -188,6 +190,7 @@ struct DevSortedSink : Sink {
 		if (!fell_back) {                                           // the run stays in HBM: no download, the writer gets an item without bytes and both sets go back at once
 			const int r = pipe_stage_out_devrun(c, out, &it.run, &it.raw_len, &it.n_rec, &it.gpu_ms, t_end);
 			if (r || it.run) { it.len = it.raw_len; it.holds_set = false; return r; }
+			if (markdup) return BWAHIP_ECAPACITY;                    // the run's buffers could not be allocated, and nothing marks on the host
 		}                                                           // (its buffers could not be allocated: downloaded as any run after a fall-back, which it causes)
 		return host.stage_out(c, out, it, t_end);
 	}
@@ -219,10 +222,11 @@ struct DevSortedSink : Sink {
 		if (!fell_back) {                                           // in input order, so the decision depends on the input and the budget alone
 			int64_t need = bwahip_bam_devmerge_hbm_need(held_raw + it.raw_len, held_rec + it.n_rec, seq_no + 1, piece_blocks);
 			if (host.with_bai) need += bwahip_bam_devmerge_bai_hbm_need(held_rec + it.n_rec, bgzf_blocks(held_raw + it.raw_len), host.n_ref, bai_windows);
+			if (markdup) need += bwahip_bam_devmerge_markdup_hbm_need(held_rec + it.n_rec, held_tmpl + (it.run ? it.run->n_tmpl : 0));
 			const bool fits = it.run && need <= hbm_budget;
-			if (!fits) r = fall_back(seq_no);
+			if (!fits) r = markdup ? BWAHIP_ECAPACITY : fall_back(seq_no);
 		}
-		if (!r && !fell_back) { if (!(r = bam_devmerger_adopt(dm, seq_no, it.run))) { it.run = nullptr; held_raw += it.raw_len; held_rec += it.n_rec; host.sort_ms += it.gpu_ms; } }
+		if (!r && !fell_back) { if (!(r = bam_devmerger_adopt(dm, seq_no, it.run))) { held_tmpl += it.run->n_tmpl; it.run = nullptr; held_raw += it.raw_len; held_rec += it.n_rec; host.sort_ms += it.gpu_ms; } }
 		else if (!r && it.run) { r = run_to_host(seq_no, it.run, it.gpu_ms); it.run = nullptr; }
 		else if (!r) r = host.write(seq_no, it);
 		drop(it);                                                   // refused, or the fall-back failed before its turn
@@ -234,7 +238,8 @@ struct DevSortedSink : Sink {
 		if (fell_back) return host.finish();                        // from here on this is the host-merged run at sd->level
 		int64_t base = 0;
 		int r = host.write_header(1, &base);
-		if (!r) r = host.with_bai ? bwahip_bam_devmerger_finish_bai(dm, fd, host.bai_fd, base, host.n_ref, &sd->dev, nullptr) : bwahip_bam_devmerger_finish(dm, fd, &sd->dev);
+		if (!r && markdup) r = bwahip_bam_devmerger_finish_markdup(dm, fd, host.bai_fd, base, host.with_bai ? host.n_ref : -1, &sd->dev, nullptr, ms);
+		else if (!r) r = host.with_bai ? bwahip_bam_devmerger_finish_bai(dm, fd, host.bai_fd, base, host.n_ref, &sd->dev, nullptr) : bwahip_bam_devmerger_finish(dm, fd, &sd->dev);
 		if (!r) { sd->n_records = sd->dev.n_records; sd->n_runs = sd->dev.n_runs; sd->merge_s = sd->dev.finish_s; }
 		sd->sort_ms = host.sort_ms;
 		return r ? r : bwahip_bgzf_eof(fd);
@@ -531,5 +536,20 @@ extern "C" int bwahip_stream_run_bam_sorted_dev_bai(bwahip_ctx *const *ctxs, int
 	if (!sd) return BWAHIP_EINVAL;
 	DevSortedSink sink(hdr_line, sd);
 	sink.host.with_bai = true; sink.host.bai_fd = bai_fd;
+	return stream_run(ctxs, n_ctx, opt, pes0, fq1, fq2, out_fd, st, sink);
+}
+
+// bwahip_stream_run_bam_sorted_dev_bai with duplicate marking (k_markdup.hip): the batches leave their contexts with templates and descriptors,
+// the finish marks before it gathers; a run that does not fit ends the call (no host fall-back)
+extern "C" int bwahip_stream_run_bam_sorted_dev_markdup(bwahip_ctx *const *ctxs, int n_ctx, const bwahip_opt_t *opt, const bwahip_pestat_t *pes0,
+                                                        const char *fq1, const char *fq2, int out_fd, const char *hdr_line, bwahip_stream_t *st, bwahip_sort_dev_t *sd, int bai_fd,
+                                                        bwahip_markdup_stats_t *ms)
+{
+	if (!sd) return BWAHIP_EINVAL;
+	if (ms) memset(ms, 0, sizeof *ms);
+	DevSortedSink sink(hdr_line, sd);
+	sink.form = OutForm::BamSortedDup; sink.markdup = true; sink.ms = ms;
+	sink.host.level = 1;                                          // sd->level belongs to the fall-back, which does not exist here
+	if (bai_fd >= 0) { sink.host.with_bai = true; sink.host.bai_fd = bai_fd; }
 	return stream_run(ctxs, n_ctx, opt, pes0, fq1, fq2, out_fd, st, sink);
 }

@@ -490,6 +490,80 @@ int bwahip_stream_run_bam_sorted_bai(bwahip_ctx *const *ctxs, int n_ctx, const b
 int bwahip_stream_run_bam_sorted_dev_bai(bwahip_ctx *const *ctxs, int n_ctx, const bwahip_opt_t *opt, const bwahip_pestat_t *pes0, const char *fq1, const char *fq2,
                                          int out_fd, const char *hdr_line, bwahip_stream_t *st, bwahip_sort_dev_t *sd, int bai_fd);
 
+/* ---- Duplicate marking of device-merged, coordinate-sorted BAM (csrc/k_markdup.hip), before the deflate ----
+ * One canonical rule, recomputable from the records of the file alone.  Byte identity with samtools markdup or Picard is not claimed:
+ * one library (read groups are ignored), no optical duplicates, no UMIs.
+ *   Template        the records of one read (single end) or of one pair (reads 2i and 2i + 1 of a batch under BWAHIP_F_PE).
+ *   Primary record  a read's record with flag & 0x900 == 0 (the first one, if there are several; a read without one counts as
+ *                   unmapped); it is mapped when 0x4 is clear.
+ *   u5              the unclipped 5' position of a mapped primary record, with rlen = the lengths of its M D N = X operations:
+ *                   forward strand pos - (lengths of the leading S/H operations); reverse strand (0x10) pos + max(rlen, 1) - 1 +
+ *                   (lengths of the trailing S/H operations); taken as int32.
+ *   End word        (uint64)refID << 33 | (uint64)(u5 + 2^31) << 1 | reverse  -- bwahip_dup_end_word, on the host, no device.
+ *   Score           of a record: the sum of its quality bytes that are >= 15, 0 when the first quality byte is 0xff (no qualities);
+ *                   of a template: the sum over its mapped primary records, as uint32.
+ *   Kind            2 (pair): both primaries mapped; 1 (fragment): exactly one (a single-end read, or a pair with one end unmapped);
+ *                   0: none.
+ *   Signature       of a pair: its two end words, the smaller first; of a fragment: its one end word.
+ *   Input order     (run number, template index within the run).
+ *   Decision        among pairs of equal signature the one with the highest score is kept, equal scores keep the earliest in input
+ *                   order, the rest are duplicates.  A fragment is a duplicate if any pair has the fragment's end word as one of its
+ *                   two; otherwise, among the fragments with that end word the best is kept (score, then input order), the rest
+ *                   are duplicates.
+ *   Marking         every record of a duplicate template that has 0x4 clear gets 0x400 -- primary, secondary and supplementary.
+ *                   Nothing else changes: sort order, record offsets and byte counts are those of the unmarked run.
+ * A template's descriptor: pair end[0] <= end[1]; fragment end[1] = 0; kind 0: all fields zero. */
+typedef struct { uint64_t end[2]; uint32_t score; uint32_t kind; } bwahip_dup_desc_t;   /* 24 bytes */
+typedef struct {
+	int64_t n_templates[3], n_dup_templates[3];   /* by kind 0, 1, 2 (kind 0 is never a duplicate) */
+	int64_t n_marked;                             /* records that got 0x400 */
+	int64_t hbm_bytes;                            /* what the stage held: its own buffers, the concatenated descriptors, the runs' tmpl / desc */
+	double markdup_ms, decide_ms, mark_ms;        /* GPU time of the stage by HIP events: all of it; the decision (with the descriptors' concatenation); the counts and the marking pass */
+} bwahip_markdup_stats_t;
+uint64_t bwahip_dup_end_word(int32_t refID, int32_t u5, int reverse);
+/* The decision restated on the host (csrc/markdup_host.cpp, no HIP): dup_out[i] = 1 for a duplicate template, else 0; input order = index. */
+int  bwahip_markdup_decide_host(const bwahip_dup_desc_t *desc, int64_t n_tmpl, uint8_t *dup_out);
+/* bwahip_process_seqs_bam_sorted, and per record (in sorted order, beside keys and offsets) the index of its template in the batch,
+ * and per template (n / 2 under BWAHIP_F_PE, else n) its descriptor -- made on the GPU while the batch still knows its mates.  Same
+ * buffers and lifetimes. */
+int  bwahip_process_seqs_bam_sorted_dup(bwahip_ctx *ctx, const bwahip_opt_t *opt, int64_t n_processed, int n, bwahip_seq_t *seqs, const bwahip_pestat_t *pes0,
+                                        const uint8_t **bam, int64_t *bam_len, const uint64_t **keys, const int64_t **rec_off, int64_t *n_rec,
+                                        const uint32_t **tmpl, const bwahip_dup_desc_t **desc, int64_t *n_tmpl);
+/* bwahip_bam_devmerger_add with the run's template indices (one per record) and descriptors (one per template); additionally refuses a
+ * tmpl[i] >= n_tmpl with BWAHIP_EINVAL; after a refusal the merger is as before.
+ * bwahip_bam_devmerger_finish_markdup: the decision over the templates of all runs (input order = run number, then index) and the marking
+ * pass over the runs' records in HBM, then bwahip_bam_devmerger_finish (n_ref < 0: no index, bai_fd is not looked at) or
+ * bwahip_bam_devmerger_finish_bai (n_ref >= 0, bai_fd as there).  A merger that holds a run added without descriptors: BWAHIP_EINVAL
+ * before a byte is written.  The runs stay marked: a second finish writes the same bytes.  ms may be NULL. */
+int  bwahip_bam_devmerger_add_dup(bwahip_bam_devmerger *m, int64_t run_no, const uint8_t *rec, int64_t len, const uint64_t *keys, const int64_t *rec_off, int64_t n_rec,
+                                  const uint32_t *tmpl, const bwahip_dup_desc_t *desc, int64_t n_tmpl);
+int  bwahip_bam_devmerger_finish_markdup(bwahip_bam_devmerger *m, int fd, int bai_fd, int64_t first_member_offset, int32_t n_ref, bwahip_devmerge_stats_t *st,
+                                         bwahip_bai_stats_t *bs, bwahip_markdup_stats_t *ms);
+/* The HBM marking adds to bwahip_bam_devmerge_hbm_need (no device; -1 for a negative argument), term by term:
+ *   the runs     4 bytes per record (tmpl) and 24 per template (desc), allocated to size;
+ *   the stage    per template 115 bytes: the descriptors of all runs concatenated (24); the verdict (1); and for the two entries a
+ *                template has in the end-word table 45 each -- the two key and two ordinal buffers of the sort, should they have to
+ *                grow beyond what the merge itself takes (8 + 8 + 4 + 4), the segment head (4), its scan (8), the segment's best
+ *                (8), "a pair is here" (1); plus 4096 for the counters and the scan's last element; grown with an eighth of slack
+ *                (DevBuf::ensure).  The sort's histograms are within the 64 MiB bwahip_bam_devmerge_hbm_need counts. */
+int64_t bwahip_bam_devmerge_markdup_hbm_need(int64_t n_records, int64_t n_templates);
+/* bwahip_stream_run_bam_sorted_dev_bai with marking: every batch leaves its context with tmpl and descriptors, handed device to device to
+ * the merger as the records are; the finish is bwahip_bam_devmerger_finish_markdup.  bai_fd < 0: no index is built.  hbm_budget counts
+ * bwahip_bam_devmerge_hbm_need, _bai_hbm_need (with an index) and _markdup_hbm_need together.  The file does not depend on the number of
+ * contexts, on which context took a batch, or on piece_blocks.  There is NO host fall-back here: when a run does not fit the budget, or
+ * its buffers cannot be allocated, the call returns BWAHIP_ECAPACITY and what reached out_fd is not a file; sd->tmp_dir, mem_budget and
+ * level are ignored. */
+int  bwahip_stream_run_bam_sorted_dev_markdup(bwahip_ctx *const *ctxs, int n_ctx, const bwahip_opt_t *opt, const bwahip_pestat_t *pes0, const char *fq1, const char *fq2,
+                                              int out_fd, const char *hdr_line, bwahip_stream_t *st, bwahip_sort_dev_t *sd, int bai_fd, bwahip_markdup_stats_t *ms);
+/* Known answers.  bwahip_kat_dup_desc: exactly the batch kernel on the caller's records in input order -- read i's records are
+ * rec[off[i] .. off[i+1]) (host pointers, off[0] >= 0, rec holds off[n_reads] bytes); paired: reads 2i and 2i + 1 are one template;
+ * desc_out receives n_reads (or n_reads / 2) descriptors.  A record that does not chain, or whose name + CIGAR + sequence + qualities
+ * exceed its length: BWAHIP_EINVAL, and no byte outside a record is read.
+ * bwahip_kat_markdup: exactly the decision stage on the caller's descriptors, one byte per template; n_tmpl == 0 launches nothing. */
+int  bwahip_kat_dup_desc(bwahip_ctx *ctx, const uint8_t *rec, const int64_t *off, int64_t n_reads, int paired, bwahip_dup_desc_t *desc_out);
+int  bwahip_kat_markdup(bwahip_ctx *ctx, const bwahip_dup_desc_t *desc, int64_t n_tmpl, uint8_t *dup_out);
+float bwahip_kat_dup_desc_ms(bwahip_ctx *ctx);   /* the kernel's milliseconds in the last bwahip_kat_dup_desc, by HIP events (scripts/markdup_rate.py) */
+
 /* Insert-size statistics (mem_pestat_t[4]: FF, FR, RF, RR; bwamem_pair.c:72) and mate-rescue counters ([0] local alignments
  * run, [1] regions added, [2] most alignments of one pair, [3] pairs that needed any; bwamem_pair.c:137) of the last
  * paired-end batch finalised on the GPU.  Either pointer may be NULL; counters4 receives 4 values. */
