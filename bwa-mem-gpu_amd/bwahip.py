@@ -110,6 +110,15 @@ class MarkdupStats(C.Structure):  # bwahip_markdup_stats_t
                 ("markdup_ms", C.c_double), ("decide_ms", C.c_double), ("mark_ms", C.c_double)]
 
 
+class QcOpt(C.Structure):  # bwahip_qc_opt_t
+    _fields_ = [("window_shift", C.c_int), ("exclude_flags", C.c_int), ("min_mapq", C.c_int)]
+
+
+class QcStats(C.Structure):  # bwahip_qc_stats_t
+    _fields_ = [("n_windows", C.c_int64), ("qc_bytes", C.c_int64), ("hbm_bytes", C.c_int64), ("qc_ms", C.c_double), ("record_ms", C.c_double),
+                ("scan_ms", C.c_double)]
+
+
 ERRORS = {0: "ok", -1: "EINVAL", -2: "ENODEV", -3: "ENOMEM", -4: "EIO", -5: "ECAPACITY", -6: "EINTERNAL"}
 
 STAGE_INTV, STAGE_CHAIN, STAGE_CHAIN_FLT, STAGE_REGS, STAGE_REGS_PRE, STAGE_SEEDS = 1, 2, 3, 4, 5, 6
@@ -227,6 +236,19 @@ def lib():
     L.bwahip_kat_markdup.argtypes = [vp, vp, C.c_int64, vp]
     L.bwahip_kat_dup_desc_ms.argtypes = [vp]
     L.bwahip_kat_dup_desc_ms.restype = C.c_float
+    L.bwahip_qc_builder_open.argtypes = [C.c_int32, vp, C.POINTER(QcOpt), C.POINTER(vp)]
+    L.bwahip_qc_builder_add_records.argtypes = [vp, vp, vp, C.c_int64]
+    L.bwahip_qc_builder_finish.argtypes = [vp, C.c_int]
+    L.bwahip_qc_builder_close.argtypes = [vp]
+    L.bwahip_qc_builder_close.restype = None
+    L.bwahip_bam_merger_set_qc.argtypes = [vp, vp]
+    L.bwahip_kat_qc.argtypes = [vp, vp, vp, C.c_int64, C.c_int32, vp, C.POINTER(QcOpt), vp, C.c_int64, i64p]
+    L.bwahip_bam_devmerger_set_qc.argtypes = [vp, C.POINTER(QcOpt), C.c_int32, vp, C.c_int, C.POINTER(QcStats)]
+    L.bwahip_qc_hbm_need.argtypes = [C.c_int64, C.c_int64, C.c_int64, C.c_int64]
+    L.bwahip_qc_hbm_need.restype = C.c_int64
+    L.bwahip_stream_run_bam_sorted_dev_qc.argtypes = [C.POINTER(vp), C.c_int, C.POINTER(Opt), C.POINTER(PeStat), C.c_char_p, C.c_char_p, C.c_int, C.c_char_p,
+                                                      C.POINTER(StreamStats), C.POINTER(SortDevStats), C.c_int, C.POINTER(MarkdupStats), C.c_int, C.POINTER(QcOpt), C.c_int,
+                                                      C.POINTER(QcStats)]
     L.bwahip_kat_radix_sort.argtypes = [vp, C.c_int64, vp, C.c_int, vp, C.POINTER(C.c_int)]
     L.bwahip_fastq_open.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(vp)]
     L.bwahip_fastq_next.argtypes = [vp, C.c_int64, C.c_int, C.POINTER(C.POINTER(Seq)), C.POINTER(C.c_int)]
@@ -380,6 +402,11 @@ class BamMerger:
         """bwahip_bam_merger_finish_bai: finish with a BaiBuilder listening (the caller finishes the builder)."""
         _check(lib().bwahip_bam_merger_finish_bai(self._h, fd, level, n_threads, builder._h), "bwahip_bam_merger_finish_bai")
 
+    def set_qc(self, builder):
+        """bwahip_bam_merger_set_qc: finish and finish_bai feed this QcBuilder every record as it is emitted (None: nobody listens)."""
+        self._qc = builder                                       # the builder outlives the merge
+        _check(lib().bwahip_bam_merger_set_qc(self._h, builder._h if builder is not None else None), "bwahip_bam_merger_set_qc")
+
     def stats(self):
         a, b, c, d = C.c_int64(), C.c_int64(), C.c_int64(), C.c_double()
         _check(lib().bwahip_bam_merger_stats(self._h, C.byref(a), C.byref(b), C.byref(c), C.byref(d)), "bwahip_bam_merger_stats")
@@ -436,6 +463,18 @@ class DevMerger:
                "bwahip_bam_devmerger_finish_markdup")
         return st, bs, ms
 
+    def set_qc(self, ref_len=None, qc_fd=-1, opt=()):
+        """bwahip_bam_devmerger_set_qc: every later finish runs the QC stage (csrc/k_qc.hip) over the runs and writes the summary to qc_fd;
+        opt = (window_shift, exclude_flags, min_mapq), () for the defaults; ref_len None disarms.  Returns the QcStats every armed finish fills."""
+        if ref_len is None or opt is None:
+            self._qc = None
+            _check(lib().bwahip_bam_devmerger_set_qc(self._h, None, 0, None, -1, None), "bwahip_bam_devmerger_set_qc")
+            return None
+        o, lens, qs = qc_opt(*opt), np.ascontiguousarray(ref_len, dtype=np.int64), QcStats()
+        _check(lib().bwahip_bam_devmerger_set_qc(self._h, C.byref(o), len(lens), lens.ctypes.data if len(lens) else None, qc_fd, C.byref(qs)), "bwahip_bam_devmerger_set_qc")
+        self._qc = qs                                            # the merger writes into it
+        return qs
+
     def finish_bai(self, fd=-1, bai_fd=-1, first_member_offset=0, n_ref=0):
         """bwahip_bam_devmerger_finish_bai: finish, and the BAI index of the sorted records on bai_fd (csrc/k_bai.hip); returns
         (DevMergeStats, BaiStats)."""
@@ -481,6 +520,47 @@ def markdup_decide_host(desc):
 def bam_devmerge_bai_hbm_need(n_records, n_blocks, n_ref, n_windows):
     """bwahip_bam_devmerge_bai_hbm_need: the HBM the index stage takes beside bam_devmerge_hbm_need (no device)."""
     return lib().bwahip_bam_devmerge_bai_hbm_need(n_records, n_blocks, n_ref, n_windows)
+
+
+def qc_opt(window_shift=0, exclude_flags=-1, min_mapq=0):
+    """bwahip_qc_opt_t; the defaults resolve to 14, 1796, 0."""
+    o = QcOpt()
+    o.window_shift, o.exclude_flags, o.min_mapq = window_shift, exclude_flags, min_mapq
+    return o
+
+
+def qc_hbm_need(n_ref, sum_len, n_windows, n_records):
+    """bwahip_qc_hbm_need: the HBM the QC stage takes (no device)."""
+    return lib().bwahip_qc_hbm_need(n_ref, sum_len, n_windows, n_records)
+
+
+class QcBuilder:
+    """bwahip_qc_builder_*: the QC summary (BQC\1) of BAM records fed in any cut and any order, for these contig lengths; no device.
+    opt = (window_shift, exclude_flags, min_mapq), () for the defaults."""
+
+    def __init__(self, ref_len, opt=()):
+        self._h = C.c_void_p()
+        lens = np.ascontiguousarray(ref_len, dtype=np.int64)
+        _check(lib().bwahip_qc_builder_open(len(lens), lens.ctypes.data if len(lens) else None, C.byref(qc_opt(*opt)), C.byref(self._h)), "bwahip_qc_builder_open")
+
+    def add_records(self, rec, rec_off):
+        rec = bytes(rec)
+        rec_off = np.ascontiguousarray(rec_off, dtype=np.int64)
+        _check(lib().bwahip_qc_builder_add_records(self._h, rec, rec_off.ctypes.data, len(rec_off) - 1), "bwahip_qc_builder_add_records")
+
+    def finish(self, qc_fd=-1):
+        _check(lib().bwahip_qc_builder_finish(self._h, qc_fd), "bwahip_qc_builder_finish")
+
+    def close(self):
+        if self._h:
+            lib().bwahip_qc_builder_close(self._h)
+            self._h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
 
 
 class BaiBuilder:
@@ -913,6 +993,24 @@ class Context:
         _check(rc, "bwahip_kat_bai")
         return out[:ln.value].tobytes()
 
+    def kat_qc(self, rec, rec_off, ref_len, opt=()):
+        """The QC stage of the device merger (csrc/k_qc.hip) on these records (any order) for these contig lengths: the BQC\1 bytes.
+        opt = (window_shift, exclude_flags, min_mapq), () for the defaults."""
+        rec = bytes(rec)
+        rec_off = np.ascontiguousarray(rec_off, dtype=np.int64)
+        lens = np.ascontiguousarray(ref_len, dtype=np.int64)
+        src = np.frombuffer(rec, dtype=np.uint8) if rec else np.zeros(1, dtype=np.uint8)
+        ln = C.c_int64()
+        out = np.empty(1 << 20, dtype=np.uint8)
+        for _ in range(2):
+            rc = lib().bwahip_kat_qc(self._h, src.ctypes.data, rec_off.ctypes.data, len(rec_off) - 1, len(lens), lens.ctypes.data if len(lens) else None, C.byref(qc_opt(*opt)),
+                                     out.ctypes.data, len(out), C.byref(ln))
+            if rc != -5 or ln.value <= len(out):
+                break
+            out = np.empty(ln.value, dtype=np.uint8)                # the first answer said how much it takes
+        _check(rc, "bwahip_kat_qc")
+        return out[:ln.value].tobytes()
+
     def kat_dup_desc(self, rec, off, paired=False):
         """The batch's descriptor kernel (csrc/k_markdup.hip) on these records in input order: read i = rec[off[i]:off[i+1]]; one
         descriptor per read, or per two reads (paired), as a DUP_DESC_DTYPE array."""
@@ -1220,6 +1318,25 @@ def stream_run_bam_sorted_dev_markdup(ctxs, fq1, fq2=None, out_fd=-1, bai_fd=-1,
                                                           os.fsencode(fq2) if fq2 else None, out_fd, hdr_line, C.byref(st), C.byref(sd), bai_fd, C.byref(ms)),
            "bwahip_stream_run_bam_sorted_dev_markdup")
     return st, sd, ms
+
+
+def stream_run_bam_sorted_dev_qc(ctxs, fq1, fq2=None, out_fd=-1, bai_fd=-1, qc_fd=-1, markdup=False, qc=(), hdr_line=None, opt=None, chunk_bases=0, max_reads=0,
+                                 keep_comments=False, reader_threads=0, pes0=None, hbm_budget=0, piece_blocks=0, tmp_dir=None, mem_budget=1 << 30, level=1):
+    """bwahip_stream_run_bam_sorted_dev_qc: stream_run_bam_sorted_dev_markdup (markdup) or stream_run_bam_sorted_dev_bai with the QC summary of
+    the file on qc_fd (csrc/k_qc.hip; after a fall-back: the host builder).  qc = (window_shift, exclude_flags, min_mapq).  Returns
+    (StreamStats, SortDevStats, MarkdupStats, QcStats)."""
+    opt = opt or default_opt()
+    st, sd, ms, qs = StreamStats(), SortDevStats(), MarkdupStats(), QcStats()
+    st.chunk_bases, st.max_reads, st.keep_comments, st.reader_threads = chunk_bases, max_reads, int(keep_comments), reader_threads
+    sd.tmp_dir, sd.mem_budget, sd.level = os.fsencode(tmp_dir) if tmp_dir is not None else None, mem_budget, level
+    sd.hbm_budget, sd.piece_blocks = hbm_budget, piece_blocks
+    arr = (C.c_void_p * len(ctxs))(*[c._h for c in ctxs])
+    if isinstance(hdr_line, str):
+        hdr_line = hdr_line.encode()
+    _check(lib().bwahip_stream_run_bam_sorted_dev_qc(arr, len(ctxs), C.byref(opt), C.byref(pes0) if pes0 is not None else None, os.fsencode(fq1),
+                                                     os.fsencode(fq2) if fq2 else None, out_fd, hdr_line, C.byref(st), C.byref(sd), bai_fd, C.byref(ms), int(bool(markdup)),
+                                                     C.byref(qc_opt(*qc)), qc_fd, C.byref(qs)), "bwahip_stream_run_bam_sorted_dev_qc")
+    return st, sd, ms, qs
 
 
 def _tool(name):

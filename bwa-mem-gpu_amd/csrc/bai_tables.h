@@ -89,3 +89,5 @@ int bai_write_fd(int fd, const std::vector<uint8_t> &bytes);   // all of them or
 struct MergeHooks { int (*record)(void *arg, const uint8_t *rec, int64_t len); int (*members)(void *arg, const int32_t *member_len, int64_t n); void *arg; };
 struct bwahip_bam_merger;
 int bam_merger_finish_hooks(bwahip_bam_merger *m, int fd, int level, int n_threads, const MergeHooks *hooks);
+// a listener that stays with the merger: every finish tells it every record as it is emitted, beside the hooks (record == nullptr: nobody listens)
+int bam_merger_listen(bwahip_bam_merger *m, int (*record)(void *arg, const uint8_t *rec, int64_t len), void *arg);

@@ -188,6 +188,7 @@ struct bwahip_bam_merger {
 	std::mutex mu;
 	std::map<int64_t, Run> runs;             // by run_no: the tie-break of the merge
 	double merge_s = 0;
+	int (*listen)(void *arg, const uint8_t *rec, int64_t len) = nullptr; void *listen_arg = nullptr;   // bam_merger_listen: told every record as it is emitted
 };
 
 extern "C" int bwahip_bam_merger_open(const char *tmp_dir, int64_t mem_budget, bwahip_bam_merger **out)
@@ -291,6 +292,7 @@ int bam_merger_finish_hooks(bwahip_bam_merger *m, int fd, int level, int n_threa
 		const uint8_t *p; int64_t n;
 		if ((rc = c->record(&p, &n))) return rc;
 		if (bai && (rc = bai->record(bai->arg, p, n))) return rc;
+		if (m->listen && (rc = m->listen(m->listen_arg, p, n))) return rc;
 		while (n > 0) {                                           // a record may straddle two pieces: the BGZF stream is one sequence of bytes
 			const int64_t take = n < PIECE - fill ? n : PIECE - fill;
 			memcpy(piece.data() + fill, p, (size_t)take);
@@ -308,6 +310,14 @@ int bam_merger_finish_hooks(bwahip_bam_merger *m, int fd, int level, int n_threa
 }
 
 extern "C" int bwahip_bam_merger_finish(bwahip_bam_merger *m, int fd, int level, int n_threads) { return bam_merger_finish_hooks(m, fd, level, n_threads, nullptr); }
+
+int bam_merger_listen(bwahip_bam_merger *m, int (*record)(void *arg, const uint8_t *rec, int64_t len), void *arg)
+{
+	if (!m) return BWAHIP_EINVAL;
+	std::lock_guard<std::mutex> lk(m->mu);
+	m->listen = record; m->listen_arg = arg;
+	return 0;
+}
 
 extern "C" int bwahip_bam_merger_stats(bwahip_bam_merger *m, int64_t *n_records, int64_t *n_runs, int64_t *spilled_bytes, double *merge_s)
 {

@@ -319,6 +319,15 @@ int markdup_decide(MarkdupStage *s, bwahip_ctx *c, int64_t n_tmpl);
 int markdup_counters_reset(MarkdupStage *s, bwahip_ctx *c);
 int markdup_count(MarkdupStage *s, bwahip_ctx *c, int64_t n_tmpl);
 int markdup_mark_run(MarkdupStage *s, bwahip_ctx *c, uint8_t *rec, const int64_t *off, int64_t n_rec, int64_t len, const uint32_t *tmpl, int64_t first_tmpl, int64_t n_tmpl);
+// k_qc.hip: the QC stage of a device merger's finish, on c->stream.  begin: the layout for these contigs and (resolved) options, the tables and
+// the difference array cleared; records: the record pass over one run (ord0: the ordinal of its first record in the order given); finish: the
+// scan pass, the one download (awaited) and the summary's bytes -- BWAHIP_EINVAL when a record was refused.  n_records == 0 launches nothing.
+struct QcStage;
+QcStage *qc_stage_new();
+void qc_stage_free(QcStage *s);
+int  qc_stage_begin(QcStage *s, bwahip_ctx *c, int32_t n_ref, const int64_t *ref_len, const bwahip_qc_opt_t &opt, int64_t n_records);
+int  qc_stage_records(QcStage *s, bwahip_ctx *c, const uint8_t *rec, const int64_t *off, int64_t n_rec, int64_t len, int64_t ord0);
+int  qc_stage_finish(QcStage *s, bwahip_ctx *c, std::vector<uint8_t> *bytes, bwahip_qc_stats_t *qs);
 int bam_check_reads(int n, const bwahip_seq_t *seqs);   // bam_host.cpp: BWAHIP_EINVAL (with a message naming the read) for a name or a comment BAM cannot hold
 void pipe_destroy(bwahip_ctx *c);                                                     // final_rt.hip: the stream driver's buffer sets
 int final_setup(bwahip_ctx *c);                                                       // contig name tables for the SAM kernels

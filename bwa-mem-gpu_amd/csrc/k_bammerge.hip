@@ -21,8 +21,12 @@
 //
 // A marked finish (bwahip_bam_devmerger_finish_markdup) runs the duplicate decision and the marking pass of k_markdup.hip over the runs
 // before the order is made: one bit of a record changes and no key, so everything after it is the unmarked finish.
+//
+// An armed merger (bwahip_bam_devmerger_set_qc) runs the QC stage of k_qc.hip over the runs after the marking and before the order: it reads
+// the records and changes nothing, so the members are those of the unarmed finish.
 #include "ctx_internal.h"
 #include "bai_tables.h"
+#include "qc_tables.h"
 #include <errno.h>
 #include <unistd.h>
 #include <chrono>
@@ -171,6 +175,8 @@ struct bwahip_bam_devmerger {
 	Work w;
 	BaiStage *bai = nullptr;                                       // the index stage's buffers (k_bai.hip), made by the first finish_bai
 	MarkdupStage md;                                               // the marking stage's buffers (k_markdup.hip), grown by the first finish_markdup
+	QcStage *qc = nullptr;                                         // the QC stage's buffers (k_qc.hip), made by the first armed finish
+	bool qc_armed = false; bwahip_qc_opt_t qc_opt = { 14, 1796, 0 }; std::vector<int64_t> qc_len; int qc_fd = -1; bwahip_qc_stats_t *qc_stats = nullptr;
 };
 
 namespace {
@@ -390,6 +396,20 @@ static int devmerger_mark(bwahip_bam_devmerger *m, bwahip_markdup_stats_t *ms)
 	return 0;
 }
 
+// The QC stage over the runs in run order, on the context's stream; awaited at its end (the tables come back)
+static int devmerger_qc(bwahip_bam_devmerger *m, std::vector<uint8_t> *bytes)
+{
+	if (!m->qc) m->qc = qc_stage_new();
+	int rc = qc_stage_begin(m->qc, m->c, (int32_t)m->qc_len.size(), m->qc_len.data(), m->qc_opt, m->n_records);
+	int64_t at = 0;
+	for (auto &kv : m->runs) {
+		const DevRun *r = kv.second;
+		if (!rc) rc = qc_stage_records(m->qc, m->c, r->rec, r->off, r->n_rec, r->len, at);
+		at += r->n_rec;
+	}
+	return rc ? rc : qc_stage_finish(m->qc, m->c, bytes, m->qc_stats);
+}
+
 // bai (may be NULL): the index stage after the last piece (bwahip_bam_devmerger_finish_bai); the members do not depend on it
 // mark: the runs are marked first (bwahip_bam_devmerger_finish_markdup; ms may be null)
 static int devmerger_finish(bwahip_bam_devmerger *m, int fd, bwahip_devmerge_stats_t *st, const BaiArgs *bai, bool mark = false, bwahip_markdup_stats_t *ms = nullptr)
@@ -399,6 +419,8 @@ static int devmerger_finish(bwahip_bam_devmerger *m, int fd, bwahip_devmerge_sta
 	const double t0 = now_s();
 	if (mark) for (auto &kv : m->runs) if (!kv.second->has_dup) return BWAHIP_EINVAL;   // before a byte is written
 	if (mark) { const int r = devmerger_mark(m, ms); if (r) return r; }
+	std::vector<uint8_t> qc_bytes;                                 // written once the members are
+	if (m->qc_armed) { const int r = devmerger_qc(m, &qc_bytes); if (r) return r; }
 	if (bai && !m->bai) m->bai = bai_stage_new();
 	bwahip_ctx *c = m->c;
 	Work &w = m->w;
@@ -411,7 +433,8 @@ static int devmerger_finish(bwahip_bam_devmerger *m, int fd, bwahip_devmerge_sta
 	const int n = (int)m->n_records;
 	const int64_t total = m->raw_bytes;
 	if (n == 0 || total == 0) {                                    // nothing to write: no member
-		const int r = bai ? (n ? BWAHIP_EINVAL : finish_index(m, *bai, 0, nullptr, 0)) : 0;
+		int r = bai ? (n ? BWAHIP_EINVAL : finish_index(m, *bai, 0, nullptr, 0)) : 0;
+		if (!r && m->qc_armed) r = qc_write_fd(m->qc_fd, qc_bytes);
 		s.finish_s = now_s() - t0; if (st) *st = s;
 		return r;
 	}
@@ -523,6 +546,7 @@ static int devmerger_finish(bwahip_bam_devmerger *m, int fd, bwahip_devmerge_sta
 	s.hbm_bytes += (int64_t)(w.bytes() + bs.keys[0].cap + bs.keys[1].cap + bs.idx[0].cap + bs.idx[1].cap + bs.hist.cap + bs.hist_base.cap +
 	                         c->bz.slots.cap + c->bz.mlen.cap + c->bz.moff.cap + c->bz.md.cap + c->bz.cnt.cap);
 	rc = bai ? finish_index(m, *bai, n, idx, total) : 0;
+	if (!rc && m->qc_armed) rc = qc_write_fd(m->qc_fd, qc_bytes);
 	s.finish_s = now_s() - t0;
 	if (st) *st = s;
 	return rc;
@@ -548,6 +572,19 @@ extern "C" int bwahip_bam_devmerger_finish_markdup(bwahip_bam_devmerger *m, int 
 	return devmerger_finish(m, fd, st, n_ref >= 0 ? &a : nullptr, true, ms);   // n_ref < 0: no index
 }
 
+extern "C" int bwahip_bam_devmerger_set_qc(bwahip_bam_devmerger *m, const bwahip_qc_opt_t *opt, int32_t n_ref, const int64_t *ref_len, int qc_fd, bwahip_qc_stats_t *qs)
+{
+	if (!m) return BWAHIP_EINVAL;
+	std::lock_guard<std::mutex> lk(m->mu);
+	if (!opt) { m->qc_armed = false; m->qc_stats = nullptr; return 0; }
+	bwahip_qc_opt_t o;
+	int rc;
+	if ((rc = qc_resolve(opt, &o)) || (rc = qc_check_refs(n_ref, ref_len, nullptr))) return rc;   // the merger is as before
+	m->qc_opt = o; m->qc_len.assign(ref_len, ref_len + n_ref); m->qc_fd = qc_fd; m->qc_stats = qs; m->qc_armed = true;
+	if (qs) memset(qs, 0, sizeof *qs);
+	return 0;
+}
+
 extern "C" void bwahip_bam_devmerger_close(bwahip_bam_devmerger *m)
 {
 	if (!m) return;
@@ -555,6 +592,6 @@ extern "C" void bwahip_bam_devmerger_close(bwahip_bam_devmerger *m)
 	for (hipStream_t q : { m->c->stream_copy, m->c->stream }) if (q) (void)hipStreamSynchronize(q);   // after a failed finish work may still be queued on the buffers
 	for (auto &kv : m->runs) bam_devrun_free(kv.second);
 	m->w.release(); m->md.release();
-	bai_stage_free(m->bai);
+	bai_stage_free(m->bai); qc_stage_free(m->qc);
 	delete m;
 }

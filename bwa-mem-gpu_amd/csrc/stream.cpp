@@ -156,6 +156,8 @@ struct DevSortedSink : Sink {
 	bwahip_markdup_stats_t *ms = nullptr; bool markdup = false;   // bwahip_stream_run_bam_sorted_dev_markdup: the runs carry templates, no fall-back
 	int64_t held_tmpl = 0;
 	int64_t bai_windows = 0;                                     // with the index: the 16 Kbp windows of the contig table, for the stage's share of the budget
+	const bwahip_qc_opt_t *qo = nullptr; int qc_fd = -1; bwahip_qc_stats_t *qs = nullptr;   // bwahip_stream_run_bam_sorted_dev_qc: the summary of the file on qc_fd
+	std::vector<int64_t> qc_len; int64_t qc_need = 0, qc_windows = 0; bwahip_qc_builder *qb = nullptr;   // the contigs' lengths, the stage's share of the budget; the fall-back's builder
 	std::atomic<bool> fell_back{false};                          // read by the drainers: from now on they download
 	hipStream_t fb_stream = nullptr; HostBuf fb_rec, fb_keys, fb_off;   // the fall-back's downloads: their stream, one pinned buffer each for records, keys and offsets
 	DevSortedSink(const char *h, bwahip_sort_dev_t *s) : sd(s), host(h, s->level, s) { form = OutForm::BamSorted; }
@@ -164,6 +166,7 @@ struct DevSortedSink : Sink {
 		if (ctx0) (void)hipSetDevice(ctx0->device);
 		if (fb_stream) (void)hipStreamDestroy(fb_stream);
 		fb_rec.release(); fb_keys.release(); fb_off.release(); bwahip_bam_devmerger_close(dm);
+		bwahip_qc_builder_close(qb);
 	}
 	int open(bwahip_ctx *const *ctxs, int n_ctx) override
 	{
@@ -175,6 +178,15 @@ struct DevSortedSink : Sink {
 		sd->fell_back = 0; sd->fell_back_at_run = 0; memset(&sd->dev, 0, sizeof sd->dev);
 		if (host.with_bai) { const bwahip_bns_t *bns = bwahip_bns(ctxs[0]); for (int32_t i = 0; i < bns->n_seqs; ++i) bai_windows += ((int64_t)bns->anns[i].len + 16383) >> 14; }
 		if ((r = bwahip_bam_devmerger_open(ctxs[0], sd->piece_blocks, &dm))) return r;
+		if (qo) {                                                   // bad options are refused here, before anything starts
+			const bwahip_bns_t *bns = bwahip_bns(ctxs[0]);
+			for (int32_t i = 0; i < bns->n_seqs; ++i) qc_len.push_back(bns->anns[i].len);
+			if ((r = bwahip_bam_devmerger_set_qc(dm, qo, (int32_t)qc_len.size(), qc_len.data(), qc_fd, qs))) return r;
+			const int ws = qo->window_shift ? qo->window_shift : 14;
+			int64_t sum = 0;
+			for (int64_t L : qc_len) { sum += L; qc_windows += (L + (1ll << ws) - 1) >> ws; }
+			qc_need = bwahip_qc_hbm_need((int64_t)qc_len.size(), sum, qc_windows, 0);
+		}
 		ctx0 = ctxs[0]; hbm_budget = sd->hbm_budget;
 		piece_blocks = sd->piece_blocks > 0 ? sd->piece_blocks : ctx0->knobs.sorted_piece_blocks;
 		if (!hbm_budget) {                                          // half of what the device has free now
@@ -210,6 +222,7 @@ struct DevSortedSink : Sink {
 	int fall_back(int64_t at)
 	{
 		int rc = bwahip_bam_merger_open(host.tmp_dir, host.mem_budget, &host.m);
+		if (!rc && qo && !(rc = bwahip_qc_builder_open((int32_t)qc_len.size(), qc_len.data(), qo, &qb))) rc = bwahip_bam_merger_set_qc(host.m, qb);   // the host builder listens to the host merge
 		std::vector<std::pair<int64_t, DevRun*>> held;
 		bam_devmerger_take_runs(dm, &held);
 		for (auto &h : held) { if (!rc) rc = run_to_host(h.first, h.second, 0); else bam_devrun_free(h.second); }
@@ -223,6 +236,7 @@ struct DevSortedSink : Sink {
 			int64_t need = bwahip_bam_devmerge_hbm_need(held_raw + it.raw_len, held_rec + it.n_rec, seq_no + 1, piece_blocks);
 			if (host.with_bai) need += bwahip_bam_devmerge_bai_hbm_need(held_rec + it.n_rec, bgzf_blocks(held_raw + it.raw_len), host.n_ref, bai_windows);
 			if (markdup) need += bwahip_bam_devmerge_markdup_hbm_need(held_rec + it.n_rec, held_tmpl + (it.run ? it.run->n_tmpl : 0));
+			need += qc_need;
 			const bool fits = it.run && need <= hbm_budget;
 			if (!fits) r = markdup ? BWAHIP_ECAPACITY : fall_back(seq_no);
 		}
@@ -235,7 +249,12 @@ struct DevSortedSink : Sink {
 	void drop(Item &it) override { if (it.run) bam_devrun_free(it.run); it.run = nullptr; }
 	int finish() override
 	{
-		if (fell_back) return host.finish();                        // from here on this is the host-merged run at sd->level
+		if (fell_back) {                                            // from here on this is the host-merged run at sd->level
+			int r = host.finish();
+			if (!r && qb) r = bwahip_qc_builder_finish(qb, qc_fd);   // the summary last, as the index: nothing of it unless the file is whole
+			if (!r && qb && qs) { memset(qs, 0, sizeof *qs); qs->n_windows = qc_windows; qs->qc_bytes = 12580 + 48 * (int64_t)qc_len.size() + 8 * qc_windows; }
+			return r;
+		}
 		int64_t base = 0;
 		int r = host.write_header(1, &base);
 		if (!r && markdup) r = bwahip_bam_devmerger_finish_markdup(dm, fd, host.bai_fd, base, host.with_bai ? host.n_ref : -1, &sd->dev, nullptr, ms);
@@ -551,5 +570,24 @@ extern "C" int bwahip_stream_run_bam_sorted_dev_markdup(bwahip_ctx *const *ctxs,
 	sink.form = OutForm::BamSortedDup; sink.markdup = true; sink.ms = ms;
 	sink.host.level = 1;                                          // sd->level belongs to the fall-back, which does not exist here
 	if (bai_fd >= 0) { sink.host.with_bai = true; sink.host.bai_fd = bai_fd; }
+	return stream_run(ctxs, n_ctx, opt, pes0, fq1, fq2, out_fd, st, sink);
+}
+
+// The two entry points above with the QC summary of the file on qc_fd (k_qc.hip): the merger is armed, so its finish runs the stage after the
+// marking and before the first gather; after a fall-back (markdup == 0 only) a host builder listens to the host merge
+extern "C" int bwahip_stream_run_bam_sorted_dev_qc(bwahip_ctx *const *ctxs, int n_ctx, const bwahip_opt_t *opt, const bwahip_pestat_t *pes0,
+                                                   const char *fq1, const char *fq2, int out_fd, const char *hdr_line, bwahip_stream_t *st, bwahip_sort_dev_t *sd, int bai_fd,
+                                                   bwahip_markdup_stats_t *ms, int markdup, const bwahip_qc_opt_t *qo, int qc_fd, bwahip_qc_stats_t *qs)
+{
+	if (!sd || !qo) return BWAHIP_EINVAL;
+	if (ms) memset(ms, 0, sizeof *ms);
+	if (qs) memset(qs, 0, sizeof *qs);
+	DevSortedSink sink(hdr_line, sd);
+	sink.qo = qo; sink.qc_fd = qc_fd; sink.qs = qs;
+	if (markdup) {
+		sink.form = OutForm::BamSortedDup; sink.markdup = true; sink.ms = ms;
+		sink.host.level = 1;
+		if (bai_fd >= 0) { sink.host.with_bai = true; sink.host.bai_fd = bai_fd; }
+	} else { sink.host.with_bai = true; sink.host.bai_fd = bai_fd; }
 	return stream_run(ctxs, n_ctx, opt, pes0, fq1, fq2, out_fd, st, sink);
 }

@@ -564,6 +564,82 @@ int  bwahip_kat_dup_desc(bwahip_ctx *ctx, const uint8_t *rec, const int64_t *off
 int  bwahip_kat_markdup(bwahip_ctx *ctx, const bwahip_dup_desc_t *desc, int64_t n_tmpl, uint8_t *dup_out);
 float bwahip_kat_dup_desc_ms(bwahip_ctx *ctx);   /* the kernel's milliseconds in the last bwahip_kat_dup_desc, by HIP events (scripts/markdup_rate.py) */
 
+/* ---- Alignment QC summary and depth of coverage of coordinate-sorted BAM (csrc/k_qc.hip on the device, csrc/qc_host.cpp without one) ----
+ * One canonical summary, recomputable from the records of the file and the contig lengths alone.  All values are integers.  The result
+ * does not depend on the order of the records, on how they are cut into runs or calls, or on the order in which wavefronts run.
+ * Equality with the output of samtools flagstat, samtools idxstats or mosdepth is not claimed; the categories are theirs as restated here.
+ *   Options         window_shift in [4, 29], 0 means 14 (BAI's linear window); exclude_flags in [0, 65535], < 0 means 1796
+ *                   (0x4 | 0x100 | 0x200 | 0x400); min_mapq in [0, 255].  Anything else: BWAHIP_EINVAL before anything is launched.
+ *                   The file holds them as resolved.
+ *   Per record      every field is bounded by the record's length first.  BWAHIP_EINVAL: a record shorter than 36 bytes; a
+ *                   block_size + 4 that is not its length; 36 + l_read_name + 4 * n_cigar_op beyond it; refID >= n_ref; refID >= 0 with
+ *                   pos < 0.  The first offending record in the order given decides.  No byte outside a record is read, and of a record
+ *                   only its first 36 bytes and its CIGAR.
+ *   Counts          count[q][16], q = (flag & 0x200) != 0: [0] total; [1] primary (flag & 0x900 == 0); [2] secondary (0x100);
+ *                   [3] supplementary (0x800 without 0x100); [4] duplicates (0x400); [5] primary duplicates; [6] mapped (0x4 clear);
+ *                   [7] primary mapped.  [8..15] count primary records with 0x1 only: [8] paired; [9] read1 (0x40); [10] read2 (0x80);
+ *                   [11] properly paired (0x2 set, 0x4 clear); [12] itself and mate mapped (0x4 and 0x8 clear); [13] singletons (0x4
+ *                   clear, 0x8 set); [14] of [12], next_refID != refID; [15] of [14], mapq >= 5.
+ *                   n_no_coor: the records with refID < 0.
+ *   Per reference   mapped: the records with that refID and 0x4 clear; placed_unmapped: the same with 0x4 set.
+ *   Histograms      mapq_hist[256] over primary mapped records; isize_hist[1025] over primary records with 0x1 and 0x2 set, 0x4 and
+ *                   0x8 clear and tlen > 0, bin min(tlen, 1024).
+ *   Coverage        a record takes part when refID >= 0, flag & exclude_flags == 0 and mapq >= min_mapq.  Each of its M, =, X and D
+ *                   operations covers [p, p + len), p starting at pos and advancing over M D N = X; the interval is clipped to
+ *                   [0, contig length); N covers nothing; overlapping mates both count.  depth(r, x) = the intervals over base x of
+ *                   reference r.  Per reference: covered = bases of depth >= 1, depth_sum; per reference ceil(len / 2^window_shift)
+ *                   windows, each the sum of depth over its bases (the last one short); depth_hist[256] over all bases of all
+ *                   references, bin min(depth, 255).
+ *   The file        little endian, no padding, 12 580 + 48 * n_ref + 8 * (windows of all references) bytes:
+ *                     char[4] "BQC\1" | int32 n_ref | int32 window_shift, exclude_flags, min_mapq | uint64 n_no_coor |
+ *                     uint64 count[2][16] | uint64 mapq_hist[256] | uint64 isize_hist[1025] | uint64 depth_hist[256] |
+ *                     n_ref x { uint64 len, mapped, placed_unmapped, covered, depth_sum, n_windows } |
+ *                     the windows of reference 0, 1, ... as uint64 each.
+ * Device-free builder (csrc/qc_host.cpp).  open: the contig lengths (0 .. 2^31 - 1 each) and the options (NULL: all defaults).
+ * add_records: whole records, record i is rec[rec_off[i] .. rec_off[i+1]), any cut into calls, any order.  finish: the summary on
+ * qc_fd (< 0: built and dropped).  After a refusal every later call returns the same code.  It holds 4 bytes per base of every reference
+ * that a record has covered (a difference array of len + 1 words, made at the reference's first covering record), 24 bytes per reference
+ * and, during finish, 8 bytes per window. */
+typedef struct { int window_shift, exclude_flags, min_mapq; } bwahip_qc_opt_t;
+typedef struct {
+	int64_t n_windows, qc_bytes;                  /* windows of all references; bytes of the summary */
+	int64_t hbm_bytes;                            /* what the stage held (0 after a host fall-back) */
+	double qc_ms, record_ms, scan_ms;             /* GPU time by HIP events: the stage (with the clearing of its tables and of the difference array); its record pass; its scan pass */
+} bwahip_qc_stats_t;
+typedef struct bwahip_qc_builder bwahip_qc_builder;
+int  bwahip_qc_builder_open(int32_t n_ref, const int64_t *ref_len, const bwahip_qc_opt_t *opt, bwahip_qc_builder **b);
+int  bwahip_qc_builder_add_records(bwahip_qc_builder *b, const uint8_t *rec, const int64_t *rec_off, int64_t n_rec);
+int  bwahip_qc_builder_finish(bwahip_qc_builder *b, int qc_fd);
+void bwahip_qc_builder_close(bwahip_qc_builder *b);
+/* The host merger with a listener: bwahip_bam_merger_finish and _finish_bai feed the builder every record as it is emitted (NULL: nobody
+ * listens, as before); the bytes on fd do not change.  The caller opens, finishes and closes the builder. */
+int  bwahip_bam_merger_set_qc(bwahip_bam_merger *m, bwahip_qc_builder *builder);
+/* The stage on the device (csrc/k_qc.hip): one pass over the records where they lie (counts reduced per wavefront, histograms per
+ * workgroup in LDS, +1 / -1 into a difference array of len + 1 slots per reference, each reference padded to whole tiles of 2048), then
+ * a three-phase prefix sum over the array (tile sums, their scan, the tiles again) that feeds depth histogram, covered bases and
+ * windows; the compact tables come back in one download and go through the host builder's serialiser.
+ * bwahip_kat_qc: exactly that stage on the caller's records (host pointers, any order); the summary into out (out_cap too small:
+ * BWAHIP_ECAPACITY, *out_len says what it takes).
+ * bwahip_bam_devmerger_set_qc arms a device merger: every finish (_finish, _finish_bai, _finish_markdup) then runs the stage over the
+ * runs after the marking, if there is any, and before the order is made, and writes the summary to qc_fd (< 0: built and dropped) once
+ * the members are written.  A refusal comes before a byte of the members is written.  opt == NULL disarms (the other arguments are not
+ * looked at); an unarmed merger queues what it queued before.  *qs (may be NULL) is filled by every armed finish.
+ * bwahip_qc_hbm_need: the HBM the stage takes, with the eighth of slack its buffers grow with (no device; -1 for a negative argument):
+ * with S = sum_len + 2048 * n_ref slots (len + 1 per reference, padded), 4 * S for the difference array, 16 * (S / 2048 + n_ref + 1)
+ * for the tiles (sum, its scan, the tile's reference), 8 * (1570 + 3 * n_ref + n_windows) for the tables, 24 * (n_ref + 1) for length,
+ * first tile and first window of every reference, 4096 for the error word and the scan's own sums.  Nothing is held per record. */
+int  bwahip_kat_qc(bwahip_ctx *ctx, const uint8_t *rec, const int64_t *rec_off, int64_t n_rec, int32_t n_ref, const int64_t *ref_len, const bwahip_qc_opt_t *opt,
+                   uint8_t *out, int64_t out_cap, int64_t *out_len);
+int  bwahip_bam_devmerger_set_qc(bwahip_bam_devmerger *m, const bwahip_qc_opt_t *opt, int32_t n_ref, const int64_t *ref_len, int qc_fd, bwahip_qc_stats_t *qs);
+int64_t bwahip_qc_hbm_need(int64_t n_ref, int64_t sum_len, int64_t n_windows, int64_t n_records);
+/* bwahip_stream_run_bam_sorted_dev_markdup (markdup != 0: its file and rules, no fall-back) or bwahip_stream_run_bam_sorted_dev_bai
+ * (markdup == 0: its file and rules; bai_fd < 0: the index is built and dropped) with the summary of the file on qc_fd.  The contig
+ * lengths are those of the contexts' index.  hbm_budget counts bwahip_qc_hbm_need too.  After a fall-back the host builder listens to
+ * the host merge and writes the same bytes.  qo == NULL: BWAHIP_EINVAL.  ms and qs may be NULL. */
+int  bwahip_stream_run_bam_sorted_dev_qc(bwahip_ctx *const *ctxs, int n_ctx, const bwahip_opt_t *opt, const bwahip_pestat_t *pes0, const char *fq1, const char *fq2,
+                                         int out_fd, const char *hdr_line, bwahip_stream_t *st, bwahip_sort_dev_t *sd, int bai_fd, bwahip_markdup_stats_t *ms,
+                                         int markdup, const bwahip_qc_opt_t *qo, int qc_fd, bwahip_qc_stats_t *qs);
+
 /* Insert-size statistics (mem_pestat_t[4]: FF, FR, RF, RR; bwamem_pair.c:72) and mate-rescue counters ([0] local alignments
  * run, [1] regions added, [2] most alignments of one pair, [3] pairs that needed any; bwamem_pair.c:137) of the last
  * paired-end batch finalised on the GPU.  Either pointer may be NULL; counters4 receives 4 values. */
