@@ -273,6 +273,7 @@ def lib():
     L.bwahip_batch_counters.argtypes = [vp, u64p, C.c_int]
     L.bwahip_kernel_name.restype = C.c_char_p
     L.bwahip_kat_introsort.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp]
+    L.bwahip_kat_mate_insert.argtypes = [vp, C.POINTER(Opt), C.c_int, vp, vp, vp, vp, vp, C.c_int, C.c_int, vp, vp, vp]
     L.bwahip_kat_occ4.argtypes = [vp, C.c_int, vp, vp]
     L.bwahip_index_footprint.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_uint64)]
     L.bwahip_kat_sa.argtypes = [vp, C.c_int, vp, vp]
@@ -761,7 +762,8 @@ class Context:
     def tune(self, **kw):
         """Set hand-off thresholds of the heavy-read kernels (bwahip_ctx_tune): intv_cap, smem_lanes, heavy_mult, ...; and
         ext_early_stop (default 1): ksw_extend2 ends once no later row can change its results; 0 = every row to the end, as the
-        reference (same results, more rows)."""
+        reference (same results, more rows); and incr_insert (default 1): mate rescue places a region into a tie-free list without
+        sorting it again; 0 = every orientation ends in the full sort-and-dedup (same lists, pairing and output)."""
         for k, v in kw.items():
             _check(lib().bwahip_ctx_tune(self._h, k.encode(), int(v)), f"bwahip_ctx_tune({k})")
 
@@ -1076,6 +1078,21 @@ class Context:
         _check(lib().bwahip_kat_introsort(self._h, n, mode, k64.ctypes.data, score.ctypes.data, qb.ctypes.data, a.ctypes.data, b.ctypes.data, st.ctypes.data), "bwahip_kat_introsort")
         assert st[1] == 0
         return a, b, bool(st[0])
+
+    def kat_mate_insert(self, list_off, list_words, step_off, step_hit, step_words, opt=None, mode=0, where=0):
+        """bwahip_kat_mate_insert: the list update of mate rescue on caller lists (19 words per region, the layout of STAGE_REGS_PE).
+        mode 0: as shipped, 1: never incremental; where 0: LDS up to 224 regions of capacity, 1: global memory always.
+        -> (out_words [capacity x 19, item i from row list_off[i] + step_off[i]], out_n, out_cnt [n_items x 3: by incr_insert, by score, full passes])."""
+        opt = opt or default_opt()
+        list_off = np.ascontiguousarray(list_off, dtype=np.int64); step_off = np.ascontiguousarray(step_off, dtype=np.int64)
+        list_words = np.ascontiguousarray(list_words, dtype=np.int64).reshape(-1, 19); step_words = np.ascontiguousarray(step_words, dtype=np.int64).reshape(-1, 19)
+        step_hit = np.ascontiguousarray(step_hit, dtype=np.int32)
+        n = len(list_off) - 1
+        assert len(step_off) == n + 1 and len(list_words) >= list_off.max() and len(step_words) >= step_off.max() and len(step_hit) == len(step_words)
+        out = np.zeros((max(0, int(list_off[-1] + step_off[-1])), 19), dtype=np.int64); out_n = np.zeros(n, dtype=np.int32); cnt = np.zeros((n, 3), dtype=np.int32)
+        _check(lib().bwahip_kat_mate_insert(self._h, C.byref(opt), n, list_off.ctypes.data, list_words.ctypes.data, step_off.ctypes.data, step_hit.ctypes.data, step_words.ctypes.data,
+                                            mode, where, out.ctypes.data, out_n.ctypes.data, cnt.ctypes.data), "bwahip_kat_mate_insert")
+        return out, out_n, cnt
 
     def kat_occ4(self, k):
         k = np.ascontiguousarray(k, dtype=np.uint64)

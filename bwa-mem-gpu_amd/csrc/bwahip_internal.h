@@ -288,6 +288,7 @@ struct PairLaunch {
 	const int64_t *sw_base; int *sw_cnt; SwRes *sw_res; int *sw_tasks; int2 *sw_info; int *sw_n;
 	int *sw_n8; int sw_cap;                      // the word kernel's tasks (mates of 250..256 bases x a): taken from the END of sw_tasks (sw_cap entries)
 	uint8_t *slab; size_t slab_stride;           // k_matesw: per-workgroup global scratch (reference window, column maxima, long-query working set)
+	int incr_insert;                             // knob incr_insert: 0 = a rescued region never goes in by incr_insert, every orientation ends in the full sort-and-dedup (same lists)
 	unsigned int *queue;                         // k_matesw's work-queue heads (one per instantiation)
 	unsigned long long *counters;                // [0] SW calls, [1] rescued regions
 	unsigned long long *paths;                   // which path the rescue kernels took (PE_PATH_*; bwahip_last_pe_paths)
@@ -312,6 +313,19 @@ int launch_resc_order(const PairLaunch &a, int n_resc, int *scratch, hipStream_t
 int launch_matesw_sw(const PairLaunch &a, int n_tasks, int n_tasks8, int max_len, hipStream_t st);   // max_len: longest read of the batch
 int launch_pair(const PairLaunch &a, int n_listed, hipStream_t st);   // subset 2: n_listed pairs of resc_list
 size_t matesw_slab_bytes(int64_t window);
+// known-answer kernel of k_matesw's list update (bwahip_kat_mate_insert): item i owns the slots [base[i], base[i + 1]) of regs / tmp / keys
+// (and twice that range of idx), its start list (n_start[i] regions) in front of them; its steps are step_hit / step_reg[step_off[i] .. step_off[i + 1])
+struct KatMate {
+	DevOpt opt;
+	const int64_t *base, *step_off; const int *n_start;
+	const int *step_hit; const DevReg *step_reg;
+	DevReg *regs, *tmp; void *keys; int *idx;
+	int use_incr;                                // 1: as shipped; 0: never incremental
+	int *out_n, *out_cnt;                        // per item: final length; {steps placed by incr_insert, steps that went the general way, orientations closed by the general path}
+	int *err;
+};
+int launch_kat_mate_insert(const KatMate &a, int n_lds, const int *items_lds, int n_glb, const int *items_glb, hipStream_t st);   // items of capacity <= kat_mate_lds_cap() may go to the LDS form
+int kat_mate_lds_cap();
 int launch_sam_pe(const FinLaunch &a, bool write, hipStream_t st, int read_lo = 0, int read_hi = -1);
 // k_bam.hip: the same two passes writing BAM records (FinLaunch::sam / sam_len / sam_off hold the records' bytes)
 int launch_bam(const FinLaunch &a, bool write, hipStream_t st, int read_lo = 0, int read_hi = -1);

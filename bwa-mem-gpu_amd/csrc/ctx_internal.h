@@ -64,6 +64,7 @@ struct Knobs {
 	int sorted_piece_blocks = 1024;   // BWAHIP_SORTED_PIECE_BLOCKS: BGZF blocks a device merger (k_bammerge.hip) gathers and deflates at a time (1 .. 4096; the bytes do not depend on it)
 	int gpu_final = 1;          // BWAHIP_GPU_FINAL: 0 = finalisation of single-end batches on host threads (host_final.cpp) instead of the GPU kernels
 	int gpu_pair = 1;           // BWAHIP_GPU_PAIR: 0 = paired-end batches finalised on host threads (mate rescue, pairing, SAM)
+	int incr_insert = 1;        // mate rescue places a region into a clean list without sorting it again (k_pair.hip: incr_insert); 0 = every orientation ends in the full sort-and-dedup, as the reference -- same lists, more work (BWAHIP_INCR_INSERT)
 	int verbose = 0;            // BWAHIP_VERBOSE
 	int e2e_log = 0;            // BWAHIP_E2E_LOG: one line of phase timings per bwahip_process_seqs call
 	const char *dump_ext = nullptr;   // BWAHIP_DUMP_EXT (diagnostic)
@@ -77,6 +78,7 @@ struct Knobs {
 		dump_ext = getenv("BWAHIP_DUMP_EXT");
 		if (intv_cap < 2) intv_cap = 2;
 		ext_early_stop = ext_early_stop != 0;
+		geti("BWAHIP_INCR_INSERT", incr_insert); incr_insert = incr_insert != 0;
 		geti("BWAHIP_SORTED_PIECE_BLOCKS", sorted_piece_blocks);
 		if (sorted_piece_blocks < 1 || sorted_piece_blocks > 4096) sorted_piece_blocks = 1024;
 	}

@@ -97,6 +97,7 @@ static int run_pe_rescue(bwahip_ctx *c, const bwahip_opt_t *opt, const DevOpt &d
 	memset(&pl, 0, sizeof pl);
 	pl.ix = c->ix; pl.opt = dopt; pl.n_reads = n; pl.seq = c->in->d_seq.as<uint8_t>(); pl.off = c->in->d_off.as<int64_t>(); pl.n_processed = n_processed;
 	pl.logtab = c->d_logtab.as<double>();
+	pl.incr_insert = c->knobs.incr_insert;
 	pl.regs = c->d_regs.as<DevReg>(); pl.reg_base = c->d_reg_base.as<int64_t>(); pl.reg_n = c->d_reg_n.as<int>();
 	unsigned long long *fm = c->d_fmisc.as<unsigned long long>();
 	pl.err = (int*)(fm + 2); pl.resc_n = (int*)(fm + 4); pl.counters = fm + 5; pl.sw_n = (int*)(fm + 14); pl.queue = (unsigned int*)(fm + 16); pl.sw_n8 = (int*)(fm + 18); pl.paths = fm + 19;   // (PE_PATH_N = 12 slots: up to fm[30] of the 32)

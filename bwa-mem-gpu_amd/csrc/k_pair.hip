@@ -410,6 +410,49 @@ __device__ __forceinline__ bool incr_insert(const DevOpt &o, int &n_io, const Li
 	return true;
 }
 
+// The list update of mem_matesw, in two steps that k_matesw and the known-answer kernel k_kat_mate_insert both call.
+// ms_list_add: a region b that an alignment produced goes into the list (bwamem_pair.c:186-199) -- by incr_insert while this orientation
+// has not turned general (general = !clean on entry of the orientation), else in front of the first entry of lower score, and the
+// orientation then ends in the general path.  Returns true when incr_insert placed it.
+__device__ __forceinline__ bool ms_list_add(const DevOpt &opt, const ListRef L, int &n_ma, const ListRef tmp, const DevReg &b, int *idx, int l, bool &general)
+{
+	if (!general && incr_insert(opt, n_ma, L, tmp, b, idx, l)) return true;
+	general = true;
+	// insert b keeping the list sorted by score (bwamem_pair.c:194-199)
+	int at = n_ma;
+	for (int base = 0; base < n_ma; base += 64) {
+		const unsigned long long lower = __ballot(base + l < n_ma && L[base + l].score < b.score);
+		if (lower) { at = base + __ffsll((long long)lower) - 1; break; }
+	}
+	__syncthreads();
+	for (int hi = n_ma; hi > at; hi -= 64) {           // shift [at, n_ma) up by one, from the top, 64 at a time
+		const int i = hi - 1 - l;
+		DevReg v;
+		const bool mv = i >= at;
+		if (mv) v = L[i];
+		wsync();
+		if (mv) L[i + 1] = v;
+		wsync();
+	}
+	if (l == 0) L[at] = b;
+	++n_ma;
+	wsync();
+	return false;
+}
+// ms_list_close: the end of an orientation (bwamem_pair.c:203: `if (n) mem_sort_dedup_patch`, n = alignments attempted so far for this
+// anchor).  Nothing to do while every region of the orientation went in by incr_insert on a clean list (one more call would be the
+// identity); else the general path, after which the list is clean when no two entries shared `re` -- and never with use_incr == false
+// (the knob incr_insert = 0: every orientation ends in the general path).  Returns true when the general path ran.
+__device__ __forceinline__ bool ms_list_close(const DevOpt &opt, const ListRef L, int &n_ma, const ListRef tmp, RegKey *keys, int *idx, int *stk, unsigned *lds256, int l, int *err,
+                                              int n, bool general, bool use_incr, bool &clean)
+{
+	if (!(n && general)) return false;
+	bool ties;
+	n_ma = sort_dedup_nopatch(opt, n_ma, L, tmp, keys, idx, stk, lds256, l, err, ties);
+	clean = use_incr && !ties;
+	return true;
+}
+
 // what a wavefront of k_matesw counts on its way (PairLaunch::counters and ::paths); tries: attempted alignments per orientation, 32 bits each
 // (r = 0, 1 in tries01; 2, 3 in tries23: no array, an index that is a loop variable would put it into scratch memory)
 struct MsCount { unsigned long long n_sw = 0, n_new = 0, n_inline = 0, tries01 = 0, tries23 = 0; unsigned inline_slab = 0, incr = 0, general = 0, off_contig = 0; };
@@ -491,34 +534,17 @@ __device__ __forceinline__ int matesw(const PairLaunch &a, const DevReg an, int 
 				b.score = aln.score; b.csub = aln.score2;
 				b.seedcov = (int)((b.re - b.rb < b.qe - b.qb ? b.re - b.rb : b.qe - b.qb) >> 1);
 				const unsigned long long tki = wall_clock64();
-				const bool done = !general && incr_insert(opt, n_ma, L, tmp, b, idx, l);
-				if (done) { ++cnt.n_new; ++cnt.incr; if (l == 0) atomicAdd(&a.counters[6], wall_clock64() - tki); }
-				else {
-				general = true;
-				// insert b keeping the list sorted by score (bwamem_pair.c:194-199)
-				int at = n_ma;
-				for (int base = 0; base < n_ma; base += 64) {
-					const unsigned long long lower = __ballot(base + l < n_ma && L[base + l].score < b.score);
-					if (lower) { at = base + __ffsll((long long)lower) - 1; break; }
-				}
-				__syncthreads();
-				for (int hi = n_ma; hi > at; hi -= 64) {           // shift [at, n_ma) up by one, from the top, 64 at a time
-					const int i = hi - 1 - l;
-					DevReg v;
-					const bool mv = i >= at;
-					if (mv) v = L[i];
-					wsync();
-					if (mv) L[i + 1] = v;
-					wsync();
-				}
-				if (l == 0) L[at] = b;
-				++n_ma; ++cnt.n_new;
-				wsync();
-				}
+				++cnt.n_new;
+				if (ms_list_add(opt, L, n_ma, tmp, b, idx, l, general)) { ++cnt.incr; if (l == 0) atomicAdd(&a.counters[6], wall_clock64() - tki); }
 			}
 			++n;
 		}
-		if (n && general) { ++cnt.general; const unsigned long long tk3 = wall_clock64(); bool ties; n_ma = sort_dedup_nopatch(opt, n_ma, L, tmp, keys, idx, m.stk, reinterpret_cast<unsigned*>(m.h + 128), l, a.err, ties); clean = !ties; if (l == 0) atomicAdd(&a.counters[6], wall_clock64() - tk3); }   // (m.h + 128: 256 bytes into the array -- a base register of the sort's table accesses stays inside LDS whatever offset gets folded)
+		const unsigned long long tk3 = n && general ? wall_clock64() : 0ull;
+		// (m.h + 128: 256 bytes into the array -- a base register of the sort's table accesses stays inside LDS whatever offset gets folded)
+		if (ms_list_close(opt, L, n_ma, tmp, keys, idx, m.stk, reinterpret_cast<unsigned*>(m.h + 128), l, a.err, n, general, a.incr_insert != 0, clean)) {
+			++cnt.general;
+			if (l == 0) atomicAdd(&a.counters[6], wall_clock64() - tk3);
+		}
 	}
 	return n_ma;
 }
@@ -696,6 +722,53 @@ __global__ __launch_bounds__(64, BIG ? 2 : 1) void k_matesw(PairLaunch a)
 		add(PE_PATH_BIG_PAIRS, BIG ? n_pairs : 0); add(PE_PATH_OFF_CONTIG, cnt.off_contig); add(PE_PATH_BOTH_KERNELS, n_both);
 		add(PE_PATH_TRY0, cnt.tries01 & 0xffffffffu); add(PE_PATH_TRY1, cnt.tries01 >> 32); add(PE_PATH_TRY2, cnt.tries23 & 0xffffffffu); add(PE_PATH_TRY3, cnt.tries23 >> 32);
 	}
+}
+
+// Known-answer kernel of the list update: one item per wavefront, a start list in any arrangement and a sequence of steps, each one
+// orientation of mem_matesw's loop in which the alignment was attempted (so the reference calls mem_sort_dedup_patch at its end) -- with a
+// region b, or without a hit.  clean starts false, as k_matesw starts it per end.  GLB: the lists in global memory (k_matesw<P, true>'s
+// address space), else in LDS through GuardedLds (k_matesw<P, false>'s); the same two call sites, for the same reason.
+struct KatMateLds { int *stk; unsigned *lds256; };
+struct KatMateCnt { int incr = 0, by_score = 0, closed = 0; };
+__device__ __forceinline__ void kat_mate_steps(const KatMate &a, int it, const ListRef L, int &n, const ListRef tmp, RegKey *keys, int *idx, const KatMateLds &s, int l, KatMateCnt &cnt)
+{
+	bool clean = false;
+	for (int64_t t = a.step_off[it]; t < a.step_off[it + 1]; ++t) {
+		bool general = !clean;
+		if (a.step_hit[t]) {
+			const DevReg b = a.step_reg[t];
+			if (ms_list_add(a.opt, L, n, tmp, b, idx, l, general)) ++cnt.incr; else ++cnt.by_score;
+		}
+		if (ms_list_close(a.opt, L, n, tmp, keys, idx, s.stk, s.lds256, l, a.err, 1, general, a.use_incr != 0, clean)) ++cnt.closed;
+	}
+}
+template <bool GLB>
+__global__ __launch_bounds__(64) void k_kat_mate_insert(KatMate a, const int *items)
+{
+	constexpr int LDS_LIST = GLB ? 1 : MS_LIST;
+	__shared__ int s_stk_g[3 * 80 + 32];
+	__shared__ __attribute__((aligned(16))) unsigned s_lds_g[256 + 128];
+	__shared__ GuardedLds<LDS_LIST> s_list_g, s_tmp_g;
+	__shared__ __attribute__((aligned(16))) RegKey s_keys[LDS_LIST];
+	__shared__ int s_idx[2 * LDS_LIST];
+	const KatMateLds s = { s_stk_g + 16, s_lds_g + 64 };
+	const int l = lane();
+	const int it = items[blockIdx.x];
+	const int64_t base = a.base[it];
+	int n = a.n_start[it];
+	KatMateCnt cnt;
+	DevReg *G = a.regs + base;
+	if (!GLB) {
+		const ListRef s_list = ListRef::lds(s_list_g), s_tmp = ListRef::lds(s_tmp_g);
+		for (int k = l; k < n; k += 64) s_list[k] = G[k];
+		wsync();
+		kat_mate_steps(a, it, s_list, n, s_tmp, s_keys, s_idx, s, l, cnt);
+		wsync();
+		for (int k = l; k < n; k += 64) G[k] = s_list[k];
+	} else {
+		kat_mate_steps(a, it, ListRef::global(G), n, ListRef::global(a.tmp + base), reinterpret_cast<RegKey*>(a.keys) + base, a.idx + 2 * base, s, l, cnt);
+	}
+	if (l == 0) { a.out_n[it] = n; a.out_cnt[3 * it] = cnt.incr; a.out_cnt[3 * it + 1] = cnt.by_score; a.out_cnt[3 * it + 2] = cnt.closed; }
 }
 
 // ---------------------------------------------------------------------------------------------------- mem_pair + mem_sam_pe decisions
@@ -1013,6 +1086,13 @@ int launch_matesw(const PairLaunch &a, int grid, hipStream_t st)
 	hipLaunchKernelGGL((k_matesw<16, false>), dim3(grid), dim3(64), 0, st, a);
 	hipLaunchKernelGGL((k_matesw<8, true>), dim3(grid), dim3(64), 0, st, a);     // longer mates: word kernel (after the byte one: a pair may need both)
 	hipLaunchKernelGGL((k_matesw<8, false>), dim3(grid), dim3(64), 0, st, a);
+	return hipGetLastError() == hipSuccess ? 0 : BWAHIP_ENODEV;
+}
+int kat_mate_lds_cap() { return MS_LIST; }
+int launch_kat_mate_insert(const KatMate &a, int n_lds, const int *items_lds, int n_glb, const int *items_glb, hipStream_t st)
+{
+	if (n_lds > 0) hipLaunchKernelGGL(k_kat_mate_insert<false>, dim3(n_lds), dim3(64), 0, st, a, items_lds);
+	if (n_glb > 0) hipLaunchKernelGGL(k_kat_mate_insert<true>, dim3(n_glb), dim3(64), 0, st, a, items_glb);
 	return hipGetLastError() == hipSuccess ? 0 : BWAHIP_ENODEV;
 }
 int launch_matesw_sw(const PairLaunch &a, int n_tasks, int n_tasks8, int max_len, hipStream_t st)

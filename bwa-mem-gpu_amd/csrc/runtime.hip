@@ -402,6 +402,7 @@ int bwahip_ctx_tune(bwahip_ctx *c, const char *key, int value)
 	else if (!strcmp(key, "sorted_piece_blocks")) { if (value < 1 || value > 4096) return BWAHIP_EINVAL; k.sorted_piece_blocks = value; }
 	else if (!strcmp(key, "gpu_final")) k.gpu_final = value;
 	else if (!strcmp(key, "gpu_pair")) k.gpu_pair = value;
+	else if (!strcmp(key, "incr_insert")) { if (value != 0 && value != 1) return BWAHIP_EINVAL; k.incr_insert = value; }
 	else if (!strcmp(key, "verbose")) k.verbose = value;
 	else return BWAHIP_EINVAL;
 	return 0;
@@ -463,6 +464,76 @@ int bwahip_kat_introsort(bwahip_ctx *c, int n, int mode, const int64_t *k64, con
 	if (hipStreamSynchronize(c->stream) != hipSuccess) rc = BWAHIP_ENODEV;
 done:
 	dk.release(); dp.release(); ds.release(); dw.release(); dst.release();
+	return rc;
+}
+
+// The list update of mate rescue (k_pair.hip: ms_list_add / ms_list_close, the code k_matesw calls) on caller lists; see bwahip.h.
+int bwahip_kat_mate_insert(bwahip_ctx *c, const bwahip_opt_t *opt, int n_items, const int64_t *list_off, const int64_t *list_words, const int64_t *step_off,
+                           const int32_t *step_hit, const int64_t *step_words, int mode, int where, int64_t *out_words, int32_t *out_n, int32_t *out_cnt3)
+{
+	if (!c || !opt || n_items < 0 || (mode != 0 && mode != 1) || (where != 0 && where != 1)) return BWAHIP_EINVAL;
+	if (n_items == 0) return 0;
+	if (!list_off || !step_off || !out_n || !out_cnt3 || list_off[0] != 0 || step_off[0] != 0) return BWAHIP_EINVAL;
+	for (int i = 0; i < n_items; ++i) if (list_off[i + 1] < list_off[i] || step_off[i + 1] < step_off[i]) return BWAHIP_EINVAL;
+	const int64_t n_list = list_off[n_items], n_step = step_off[n_items], total = n_list + n_step;
+	if (total > (1 << 26) || (n_list && !list_words) || (n_step && (!step_hit || !step_words)) || (total && !out_words)) return BWAHIP_EINVAL;
+	HIP_TRY(hipSetDevice(c->device));
+	auto get = [](const int64_t *w) {
+		DevReg r; memset(&r, 0, sizeof r);
+		r.rb = w[0]; r.re = w[1]; r.qb = (int)w[2]; r.qe = (int)w[3]; r.rid = (int)w[4]; r.score = (int)w[5]; r.truesc = (int)w[6]; r.sub = (int)w[7]; r.csub = (int)w[9];
+		r.sub_n = (int)w[10]; r.w = (int)w[11]; r.seedcov = (int)w[12]; r.seedlen0 = (int)w[15]; r.n_comp = (int)w[16]; r.is_alt = (int)w[17];
+		const uint32_t u = (uint32_t)w[18]; memcpy(&r.frac_rep, &u, 4);
+		return r;
+	};
+	// item i owns the slots [base[i], base[i + 1]): its capacity, start length + steps (64 spare slots behind the last item)
+	std::vector<int64_t> base(n_items + 1);
+	std::vector<int> n_start(n_items), items[2];
+	std::vector<DevReg> regs((size_t)total + 64), steps((size_t)n_step + 1);
+	memset(regs.data(), 0, regs.size() * sizeof(DevReg));
+	for (int i = 0; i < n_items; ++i) {
+		base[i] = list_off[i] + step_off[i];
+		n_start[i] = (int)(list_off[i + 1] - list_off[i]);
+		for (int64_t k = list_off[i]; k < list_off[i + 1]; ++k) regs[(size_t)(base[i] + k - list_off[i])] = get(list_words + 19 * k);
+		const int64_t cap = (list_off[i + 1] - list_off[i]) + (step_off[i + 1] - step_off[i]);
+		items[where == 0 && cap <= kat_mate_lds_cap() ? 0 : 1].push_back(i);
+	}
+	base[n_items] = total;
+	for (int64_t t = 0; t < n_step; ++t) steps[(size_t)t] = get(step_words + 19 * t);
+	const size_t slots = (size_t)total + 64;
+	DevBuf db, dso, dns, dsh, dsr, dr, dt, dk, di, don, doc, de, dit0, dit1; int rc;
+	std::vector<DevReg> back((size_t)total + 1);
+	int err = 0;
+	KatMate a;
+	if ((rc = upload(db, base.data(), base.size() * 8, c->stream)) || (rc = upload(dso, step_off, (size_t)(n_items + 1) * 8, c->stream)) || (rc = upload(dns, n_start.data(), (size_t)n_items * 4, c->stream)) ||
+	    (rc = upload(dsh, step_hit, (size_t)n_step * 4, c->stream)) || (rc = upload(dsr, steps.data(), steps.size() * sizeof(DevReg), c->stream)) ||
+	    (rc = upload(dr, regs.data(), slots * sizeof(DevReg), c->stream)) || (rc = dt.ensure(slots * sizeof(DevReg))) || (rc = dk.ensure(slots * 16)) || (rc = di.ensure(slots * 8)) ||
+	    (rc = don.ensure((size_t)n_items * 4)) || (rc = doc.ensure((size_t)n_items * 12)) || (rc = de.ensure(16)) ||
+	    (rc = upload(dit0, items[0].data(), items[0].size() * 4, c->stream)) || (rc = upload(dit1, items[1].data(), items[1].size() * 4, c->stream))) goto done;
+	if (hipMemsetAsync(de.p, 0, 16, c->stream) != hipSuccess) { rc = BWAHIP_ENODEV; goto done; }
+	a.opt = make_dev_opt(opt);
+	a.base = db.as<int64_t>(); a.step_off = dso.as<int64_t>(); a.n_start = dns.as<int>(); a.step_hit = dsh.as<int>(); a.step_reg = dsr.as<DevReg>();
+	a.regs = dr.as<DevReg>(); a.tmp = dt.as<DevReg>(); a.keys = dk.p; a.idx = di.as<int>(); a.use_incr = mode == 0 ? 1 : 0;
+	a.out_n = don.as<int>(); a.out_cnt = doc.as<int>(); a.err = de.as<int>();
+	rc = launch_kat_mate_insert(a, (int)items[0].size(), dit0.as<int>(), (int)items[1].size(), dit1.as<int>(), c->stream);
+	if (!rc && (hipMemcpyAsync(back.data(), dr.p, (size_t)total * sizeof(DevReg), hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+	            hipMemcpyAsync(out_n, don.p, (size_t)n_items * 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+	            hipMemcpyAsync(out_cnt3, doc.p, (size_t)n_items * 12, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+	            hipMemcpyAsync(&err, de.p, 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess)) rc = BWAHIP_ENODEV;
+	if (hipStreamSynchronize(c->stream) != hipSuccess) rc = BWAHIP_ENODEV;
+	if (!rc && err) { fprintf(stderr, "[bwahip] bwahip_kat_mate_insert: device sort error %d\n", err); rc = BWAHIP_EINTERNAL; }
+	if (!rc) {
+		memset(out_words, 0, (size_t)total * 19 * 8);
+		std::vector<int64_t> v;
+		for (int i = 0; i < n_items; ++i) {
+			const int64_t cap = base[i + 1] - base[i];
+			if (out_n[i] < 0 || out_n[i] > cap) { rc = BWAHIP_EINTERNAL; break; }
+			v.clear();
+			stage_put_regs(v, out_n[i], &back[(size_t)base[i]]);
+			if (out_n[i]) memcpy(out_words + 19 * base[i], v.data() + 1, (size_t)out_n[i] * 19 * 8);
+		}
+	}
+done:
+	for (DevBuf *b : { &db, &dso, &dns, &dsh, &dsr, &dr, &dt, &dk, &di, &don, &doc, &de, &dit0, &dit1 }) b->release();
 	return rc;
 }
 

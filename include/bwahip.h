@@ -781,6 +781,21 @@ int bwahip_kat_ksw_global(bwahip_ctx *ctx, int n, const int *params /*n x 10*/, 
  * (0: the introsort's depth limit -- it hands over to the one-lane form, idx_par is the identity), status2[1] != 0: internal error. */
 int bwahip_kat_introsort(bwahip_ctx *ctx, int n, int mode, const int64_t *k64, const int *score, const int *qb, int *idx_par, int *idx_seq, int *status2);
 
+/* The list update of mate rescue (mem_matesw, bwamem_pair.c:186-203) through the code k_matesw runs, on caller lists: n_items independent
+ * items, one wavefront each.  Item i: a start list of list_off[i + 1] - list_off[i] regions in any arrangement (ties and duplicates
+ * allowed) and the steps step_off[i] .. step_off[i + 1]; a step is one orientation in which the alignment was attempted -- step_hit != 0:
+ * it produced the region given, which goes into the list; 0: no hit -- and at whose end the reference calls mem_sort_dedup_patch
+ * (bns == 0).  The item starts as k_matesw starts an end (list not known to be clean).  Regions travel as the 19 words per region of
+ * BWAHIP_STAGE_REGS_PE (the words the device keeps no field for are ignored and come back 0); a step without a hit still owns 19 words.
+ * Of opt only max_chain_gap and mask_level_redun are read.  mode 0: as shipped (incr_insert where its conditions hold); 1: never
+ * incremental, every step ends in the full sort-and-dedup.  where 0: lists of capacity (start length + steps) up to 224 regions are
+ * worked on in LDS, longer ones in global memory, as k_matesw decides; 1: global memory always.  out_words: 19 words per region, item i
+ * from region list_off[i] + step_off[i] on (room for its capacity); out_n[i]: its final length; out_cnt3: per item the regions placed by
+ * incr_insert, the regions placed by score in front of a full pass, and the orientations that ended in a full pass.
+ * BWAHIP_EINVAL: a negative length, offsets that do not start at 0 or do not ascend.  n_items == 0 launches nothing. */
+int bwahip_kat_mate_insert(bwahip_ctx *ctx, const bwahip_opt_t *opt, int n_items, const int64_t *list_off, const int64_t *list_words, const int64_t *step_off,
+                           const int32_t *step_hit, const int64_t *step_words, int mode, int where, int64_t *out_words, int32_t *out_n, int32_t *out_cnt3);
+
 /* The stable LSD radix sort of the coordinate-sorted BAM output (csrc/k_bamsort.hip) on caller keys: exactly the product's passes for
  * keys of key_bits (1..64) significant bits -- 8 bits per pass, passes in which all keys agree skipped.  idx_out[i] = input position of
  * the i-th key in sorted order, equal keys in input order; *tile_out (may be NULL): items one workgroup ranks per pass.  n <= 1 launches
@@ -803,7 +818,10 @@ int bwahip_kat_ksw_align(bwahip_ctx *ctx, int n, const int *params, const int8_t
  * smem_lanes, heavy_mult, chain_big_min, rank_sort_min, spec_min_chains, ext_lds_window, verbose; and ext_early_stop (default 1): every
  * device form of ksw_extend2 ends its row loop once no later row can change score, qle, tle, gtle, gscore or max_off --
  * 0 runs every row to the end as the reference does (same results, more rows); and sorted_piece_blocks (1 .. 4096, default 1024): the
- * BGZF blocks a device merger gathers and deflates at a time (bwahip_bam_devmerger_open with piece_blocks <= 0; the bytes do not depend on it).
+ * BGZF blocks a device merger gathers and deflates at a time (bwahip_bam_devmerger_open with piece_blocks <= 0; the bytes do not depend on it);
+ * and incr_insert (0 or 1, default 1): mate rescue places a rescued region into a list that the last mem_sort_dedup_patch left free of
+ * ties without sorting the list again -- 0 ends every orientation in the full sort-and-dedup, as the reference does.  The knob changes
+ * no result: lists, pairing and output are the same with either value, only bwahip_last_pe_paths [4] and [5] differ.
  * The same knobs are read from the environment (BWAHIP_<KEY>) once, when the context is created. */
 int bwahip_ctx_tune(bwahip_ctx *ctx, const char *key, int value);
 

@@ -70,6 +70,7 @@ extern char ora_rg_id[256];                                                     
 /* ora_pair.c */
 void ora_pestat(const ora_opt_t *opt, int64_t l_pac, int n, const ora_reg_v *regs, ora_pestat_t pes[4]);      /* bwamem_pair.c:72 */
 int ora_matesw(const ora_opt_t *opt, const ora_ref_t *r, const ora_pestat_t pes[4], const ora_reg_t *a, int l_ms, const uint8_t *ms, ora_reg_v *ma); /* bwamem_pair.c:137 */
+int ora_kat_mate_insert(int max_chain_gap, float mask_level_redun, int n, const int64_t *start19, int n_steps, const int *hit, const int64_t *step19, int64_t *out19);   /* test helper: the list update of ora_matesw on a caller's list */
 int ora_pair(const ora_opt_t *opt, const ora_ref_t *r, const ora_pestat_t pes[4], ora_read_t s[2], ora_reg_v a[2], int id, int *sub, int *n_sub, int z[2], int n_pri[2]); /* bwamem_pair.c:208 */
 int ora_sam_pe(const ora_opt_t *opt, const ora_ref_t *r, const ora_pestat_t pes[4], uint64_t id, ora_read_t s[2], ora_reg_v a[2]); /* bwamem_pair.c:276 */
 

@@ -153,6 +153,53 @@ int ora_matesw(const ora_opt_t *opt, const ora_ref_t *ref, const ora_pestat_t pe
 	return n;
 }
 
+static void kat_get(ora_reg_t *p, const int64_t *x)   /* a region from its 19 words (dump_regs' order, main_oracle.c) */
+{
+	uint32_t u = (uint32_t)x[18];
+	memset(p, 0, sizeof(ora_reg_t));
+	p->rb = x[0]; p->re = x[1]; p->qb = (int)x[2]; p->qe = (int)x[3]; p->rid = (int)x[4]; p->score = (int)x[5]; p->truesc = (int)x[6];
+	p->sub = (int)x[7]; p->alt_sc = (int)x[8]; p->csub = (int)x[9]; p->sub_n = (int)x[10]; p->w = (int)x[11]; p->seedcov = (int)x[12];
+	p->secondary = (int)x[13]; p->secondary_all = (int)x[14]; p->seedlen0 = (int)x[15]; p->n_comp = (int)x[16]; p->is_alt = (int)x[17];
+	memcpy(&p->frac_rep, &u, 4);
+}
+
+/* Test helper (tests/mate_insert_cases.py): the list update of ora_matesw above, lines "ma->a[ma->n++] = b" to the call of
+ * ora_sort_dedup_patch, replayed on a caller's list.  start19 / step19 / out19: 19 words per region in dump_regs' order (main_oracle.c);
+ * hit[t] != 0: step t is an orientation whose alignment gave region t of step19, 0: an orientation that was tried without a hit -- the
+ * call at its end is made either way.  out19 has room for n + n_steps regions; returns the final length. */
+int ora_kat_mate_insert(int max_chain_gap, float mask_level_redun, int n, const int64_t *start19, int n_steps, const int *hit, const int64_t *step19, int64_t *out19)
+{
+	ora_opt_t opt;
+	ora_reg_t *a = (ora_reg_t*)calloc((size_t)(n + n_steps + 1), sizeof(ora_reg_t));
+	int i, t, tmp;
+	memset(&opt, 0, sizeof opt);
+	opt.max_chain_gap = max_chain_gap; opt.mask_level_redun = mask_level_redun;
+	for (i = 0; i < n; ++i) kat_get(&a[i], start19 + 19 * i);
+	for (t = 0; t < n_steps; ++t) {
+		if (hit[t]) {
+			ora_reg_t b;
+			kat_get(&b, step19 + 19 * t);
+			a[n++] = b;
+			for (i = 0; i < n - 1; ++i)
+				if (a[i].score < b.score) break;
+			tmp = i;
+			for (i = n - 1; i > tmp; --i) a[i] = a[i-1];
+			a[i] = b;
+		}
+		n = ora_sort_dedup_patch(&opt, 0, 0, n, a);
+	}
+	for (i = 0; i < n; ++i) {
+		const ora_reg_t *p = &a[i];
+		int64_t *w = out19 + 19 * i;
+		uint32_t u;
+		memcpy(&u, &p->frac_rep, 4);
+		w[0] = p->rb; w[1] = p->re; w[2] = p->qb; w[3] = p->qe; w[4] = p->rid; w[5] = p->score; w[6] = p->truesc; w[7] = p->sub; w[8] = p->alt_sc; w[9] = p->csub;
+		w[10] = p->sub_n; w[11] = p->w; w[12] = p->seedcov; w[13] = p->secondary; w[14] = p->secondary_all; w[15] = p->seedlen0; w[16] = p->n_comp; w[17] = p->is_alt; w[18] = u;
+	}
+	free(a);
+	return n;
+}
+
 int ora_pair(const ora_opt_t *opt, const ora_ref_t *ref, const ora_pestat_t pes[4], ora_read_t s[2], ora_reg_v a[2], int id,
              int *sub, int *n_sub, int z[2], int n_pri[2])   /* bwamem_pair.c:208 */
 {

@@ -116,6 +116,77 @@ def test_library_matches_oracle_stage_by_stage(ctx, lib, name, flags):
     assert paths["incr_insert"] + paths["general_dedup"] > 0
 
 
+REPEAT_FLAGS = ("-I", "330,40")                                  # given insert sizes: pairs inside a repeat family give mem_pestat nothing to learn from
+
+
+@pytest.fixture(scope="module")
+def repeat_family(built, tmp_path_factory):
+    """40 FR pairs from a 400-base unit with 1000 copies (2 % diverged, one every 700 bases at most) in a 1 Mbp genome of its own -- the recipe
+    of test_gpu_sam.py::test_reads_inside_a_large_repeat_family, at the smallest size (found with bwa_oracle alone) at which the oracle's lists
+    show both kinds of pair the rescue kernels tell apart: every third fragment reaches the unique flank, the others lie wholly inside the unit."""
+    d = tmp_path_factory.mktemp("repfam")
+    rng = np.random.default_rng(2)
+    n_copies, length = 1000, 1000000
+    g = rng.integers(0, 4, length, dtype=np.uint8)
+    unit = rng.integers(0, 4, 400, dtype=np.uint8)
+    starts = np.sort(rng.choice(np.arange(1000, length - 1400, 700), n_copies, replace=False))
+    for s in starts:
+        c = unit.copy()
+        m = rng.random(400) < 0.02
+        c[m] = (c[m] + rng.integers(1, 4, int(m.sum()))) % 4
+        g[s:s + 400] = c
+    txt = bytes(np.frombuffer(b"ACGT", dtype=np.uint8)[g])
+    fa, prefix = str(d / "rep.fa"), str(d / "rep")
+    with open(fa, "wb") as f:
+        f.write(b">rep\n")
+        for i in range(0, length, 60):
+            f.write(txt[i:i + 60] + b"\n")
+    bw.make_index(fa, prefix)
+    r1, r2 = [], []
+    for i in range(40):
+        s = int(starts[rng.integers(0, n_copies)])
+        if i % 3 == 0:                                              # fragment inside the repeat unit and its unique flank: rescue has something to add
+            a = s + int(rng.integers(0, 200)); frag = txt[a:a + 420]
+        else:                                                       # fragment wholly inside the unit: every copy matches
+            a = s + int(rng.integers(0, 60)); frag = txt[a:a + 330]
+        r1.append(frag[:150]); r2.append(pc.rc(frag[-150:]))
+    fq1, fq2 = str(d / "h_1.fq"), str(d / "h_2.fq")
+    pc.write_fastq(fq1, r1); pc.write_fastq(fq2, r2)
+    seqs = [x for p in zip(r1, r2) for x in p]
+    codes, off = bw.pack_reads(seqs)
+    L = dict(prefix=prefix, seqs=seqs, names=[b"p%d" % (i >> 1) for i in range(len(seqs))], quals=[b"I" * len(s) for s in seqs], codes=codes, off=off)
+    L["ps"], L["reads"] = pc.oracle_pe_stages(prefix, fq1, fq2, str(d / "o.bin"), ["-t", "8", *REPEAT_FLAGS])
+    L["sam"] = pc.oracle_sam(prefix, fq1, fq2, ["-t", "8", *REPEAT_FLAGS])
+    return L
+
+
+def test_repeat_family_lists_with_and_without_incr_insert(repeat_family):
+    """Lists beyond the 224 regions held in LDS and lists of dozens of regions, most of them changed by rescue: with the knob incr_insert at 1
+    (as shipped) and at 0 (every orientation ends in the full sort-and-dedup) statistics, lists, pairing and SAM are the oracle's, and the
+    counters show that the incremental path, the general path, the global-memory instantiation of k_matesw and the wavefront copy all ran."""
+    L = repeat_family
+    n_pe = [int(r[bw.STAGE_REGS_PE][0]) for r in L["reads"]]
+    assert max(n_pe) > 224, "no end with a list beyond the LDS list"
+    assert any(33 <= n_pe[i] + n_pe[i + 1] <= 224 for i in range(0, len(n_pe), 2)), "no pair for the wavefront copy with its lists in LDS"
+    assert len(pc.rescued_reads(L["reads"])) >= 8, "rescue changed too few lists"
+    assert any(int(r[bw.STAGE_REGS_PE][0]) - int(r[bw.STAGE_REGS][0]) >= 20 for r in L["reads"]), "no list that rescue grew by many regions"
+    paths = {}
+    with bw.Context(L["prefix"]) as c:
+        try:
+            for knob in (1, 0):
+                c.tune(incr_insert=knob)
+                _assert_stages(c, L, f"repeat family, incr_insert {knob}", REPEAT_FLAGS)
+                paths[knob] = c.last_pe_paths()
+                print("incr_insert", knob, paths[knob])
+                assert _sam(c, L, REPEAT_FLAGS) == L["sam"], f"repeat family, incr_insert {knob}: SAM"
+        finally:
+            c.tune(incr_insert=1)
+    p1, p0 = paths[1], paths[0]
+    assert p1["incr_insert"] > 0 and p1["general_dedup"] > 0 and p1["big_pairs"] > 0 and p1["copy_big_pairs"] > 0, p1
+    assert p0["incr_insert"] == 0 and p0["general_dedup"] > p1["general_dedup"], (p0, p1)
+    assert p0["big_pairs"] == p1["big_pairs"] and p0["copy_big_pairs"] == p1["copy_big_pairs"]
+
+
 def test_mixed4_with_host_pairing_gives_the_same_sam(ctx, lib):
     L = lib("mixed4")
     try:
