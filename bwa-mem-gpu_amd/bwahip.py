@@ -126,6 +126,11 @@ STAGE_PESTAT, STAGE_REGS_PE, STAGE_PAIR = 7, 8, 9        # bwahip_run_pe_stages
 PE_PATHS = ("ahead_byte", "ahead_word", "inline_lds", "inline_slab", "incr_insert", "general_dedup", "big_pairs", "copy_big_pairs",
             "try_ff", "try_fr", "try_rf", "try_rr", "off_contig", "both_kernels")   # bwahip_last_pe_paths
 TAG_READ = 100
+# bwahip_kat_chain's per-read diagnostics (bwahip.h): columns, who took the read, which sort, which filter
+CHAIN_DIAG_N = 8
+CHAIN_BY_LANE, CHAIN_BY_HELPED = -1, 4                      # 0..3: the class of k_chain_big
+CHAIN_SORT_NONE, CHAIN_SORT_LANE, CHAIN_SORT_WAVE, CHAIN_SORT_LANE_AREA, CHAIN_SORT_LANE_DEPTH = 0, 1, 2, 3, 4
+CHAIN_FLT_NONE, CHAIN_FLT_SEQ, CHAIN_FLT_WAVE = 0, 1, 2
 # known-answer DP entries (bwahip.h): forms of bwahip_kat_ksw_global, CIGAR words per item, path bits of bwahip_kat_ksw_extend2
 KAT_GLOBAL_AUTO_SMALL, KAT_GLOBAL_AUTO_BIG, KAT_GLOBAL_SCORE_ONLY = 0, 1, 2
 KAT_MAX_CIGAR = 512
@@ -274,6 +279,7 @@ def lib():
     L.bwahip_kernel_name.restype = C.c_char_p
     L.bwahip_kat_introsort.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp]
     L.bwahip_kat_mate_insert.argtypes = [vp, C.POINTER(Opt), C.c_int, vp, vp, vp, vp, vp, C.c_int, C.c_int, vp, vp, vp]
+    L.bwahip_kat_chain.argtypes = [vp, C.POINTER(Opt), C.c_int, vp, vp, vp, vp, vp, C.POINTER(i64p), i64p, vp]
     L.bwahip_kat_occ4.argtypes = [vp, C.c_int, vp, vp]
     L.bwahip_index_footprint.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_uint64)]
     L.bwahip_kat_sa.argtypes = [vp, C.c_int, vp, vp]
@@ -737,6 +743,24 @@ class Context:
         words = np.ctypeslib.as_array(out, shape=(n.value,)).copy() if n.value else np.zeros(0, dtype=np.int64)
         C.CDLL(None).free(out)
         return parse_records(words)
+
+    def kat_chain(self, read_len, seed_off, seeds, intv_off, intv, opt=None):
+        """bwahip_kat_chain: chaining and the chain filter on caller seed lists -- seeds [n x 4] (rbeg, qbeg, len, rid) in look-up order,
+        intv [m x 3] (x[2], qbeg, qend), both by offsets per read.  -> (records: per read TAG_READ, STAGE_CHAIN, STAGE_CHAIN_FLT;
+        diag [n_reads x CHAIN_DIAG_N]: who took the read (CHAIN_BY_*), nodes, height, sort (CHAIN_SORT_*), filter (CHAIN_FLT_*), chains)."""
+        opt = opt or default_opt()
+        read_len = np.ascontiguousarray(read_len, dtype=np.int32)
+        seed_off = np.ascontiguousarray(seed_off, dtype=np.int64); intv_off = np.ascontiguousarray(intv_off, dtype=np.int64)
+        seeds = np.ascontiguousarray(seeds, dtype=np.int64).reshape(-1, 4); intv = np.ascontiguousarray(intv, dtype=np.int64).reshape(-1, 3)
+        n = len(read_len)
+        assert len(seed_off) == n + 1 and len(intv_off) == n + 1 and len(seeds) >= seed_off[-1] and len(intv) >= intv_off[-1]
+        diag = np.zeros((n, CHAIN_DIAG_N), dtype=np.int32)
+        out, m = C.POINTER(C.c_int64)(), C.c_int64()
+        _check(lib().bwahip_kat_chain(self._h, C.byref(opt), n, read_len.ctypes.data, seed_off.ctypes.data, seeds.ctypes.data, intv_off.ctypes.data,
+                                      intv.ctypes.data, C.byref(out), C.byref(m), diag.ctypes.data), "bwahip_kat_chain")
+        words = np.ctypeslib.as_array(out, shape=(m.value,)).copy() if m.value else np.zeros(0, dtype=np.int64)
+        C.CDLL(None).free(out)
+        return parse_records(words), diag
 
     def run_pe_stages(self, codes, off, stages, opt=None, n_processed=0, pes0=None):
         """bwahip_run_pe_stages: reads 2i, 2i+1 are a pair; -> records (STAGE_PESTAT first, then per read TAG_READ and the stages asked for)."""

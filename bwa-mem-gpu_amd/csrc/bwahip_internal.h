@@ -163,7 +163,15 @@ struct ChainLaunch {
 	int *heavy_list, *heavy_count;               // reads whose overlap filter is deferred to k_chain_flt
 	const int *seed_cnt; int *perm, *perm_counts;   // k_chain's launch order: reads with many seeds first, like sizes together (nullptr = identity)
 	int *big_list, *big_count; int big_min, big_max, mid_max, glb_grid;   // reads with big_min < seeds <= big_max go to k_chain_big (nullptr: off)
+	int *diag;                                   // bwahip_kat_chain only, nullptr in every production launch: CHAIN_DIAG_N ints per read
 };
+// ChainLaunch::diag of read r, at diag[CHAIN_DIAG_N * r ..]: [0] who took the read (CHAIN_DIAG_LANE: k_chain; 0..3: the class of k_chain_big;
+// CHAIN_DIAG_HELPED: a class 1 / 2 read emptied from its queue by the global-node kernel), [1] B-tree nodes used, [2] tree height (a lone
+// leaf: 1), [3] the sort by weight (CHAIN_SORT_*; 0: fewer than two chains), [4] the overlap filter (CHAIN_FLT_*; 0: no chain reached it),
+// [5] chains before the filter; the rest 0
+enum { CHAIN_DIAG_N = 8, CHAIN_DIAG_LANE = -1, CHAIN_DIAG_HELPED = 4 };
+enum { CHAIN_SORT_LANE = 1, CHAIN_SORT_WAVE = 2, CHAIN_SORT_LANE_AREA = 3, CHAIN_SORT_LANE_DEPTH = 4 };   // k_chain's one-lane sort; the wavefront's; one lane because the area was too small / the depth limit was hit
+enum { CHAIN_FLT_SEQ = 1, CHAIN_FLT_WAVE = 2 };
 int launch_chain(const ChainLaunch &a, hipStream_t st, hipStream_t st2, hipStream_t st3, hipEvent_t fork, hipEvent_t join, hipEvent_t join3);
 int launch_chain_flt(const ChainLaunch &a, hipStream_t st);
 

@@ -382,7 +382,8 @@ constexpr int GLB_LDS = 2048 + 512;                          // reads beyond big
 __device__ __forceinline__ int coop_class(int S, int mid_max, int big_max) { return S <= SMALL_SEEDS ? 0 : S <= mid_max ? 1 : S <= big_max ? 2 : 3; }
 
 template <bool BIG>
-__device__ __forceinline__ void chain_read(const ChainLaunch &a, int r, BtNode *lds_nodes, int lds_node_cap = BIG_NODES, uint8_t *lds_area = nullptr, int lds_bytes = 0)
+__device__ __forceinline__ void chain_read(const ChainLaunch &a, int r, BtNode *lds_nodes, int lds_node_cap = BIG_NODES, uint8_t *lds_area = nullptr, int lds_bytes = 0,
+                                           int taken_by = CHAIN_DIAG_LANE)
 {
 	const int64_t sb = a.seed_base[r];
 	const int S = (int)(a.seed_base[r + 1] - sb), len = (int)(a.off[r + 1] - a.off[r]);
@@ -396,6 +397,9 @@ __device__ __forceinline__ void chain_read(const ChainLaunch &a, int r, BtNode *
 	c.n_chains = 0; c.n_nodes = 0; c.coop = BIG; c.lane = (int)(threadIdx.x & 63); c.glb = BIG && !lds_nodes;
 	a.chain_n[r] = 0; a.kept_seeds[r] = 0;
 	if (a.dbg_chain_n) a.dbg_chain_n[r] = 0;
+	// known-answer entry only (a.diag is nullptr in production; the slot is addressed anew at each use so that nothing stays in registers for it)
+	auto diag_put = [&](int k, int v) { if (a.diag && (!BIG || c.lane == 0)) a.diag[CHAIN_DIAG_N * (size_t)r + k] = v; };
+	diag_put(0, taken_by);
 	if (S == 0) return;
 
 	// frac_rep: union length of the query spans of over-abundant intervals (bwamem.c:272-279)
@@ -437,6 +441,11 @@ __device__ __forceinline__ void chain_read(const ChainLaunch &a, int r, BtNode *
 	}
 	const unsigned long long t_1 = wall_clock64();
 	int n_chn = bt_inorder(c, c.ord);                           // bwamem.c:311-315
+	if (a.diag) {
+		int h = 1;
+		for (int xi = c.root; c.nodes[xi].is_internal; xi = c.nodes[xi].ptr[0]) ++h;
+		diag_put(1, c.n_nodes); diag_put(2, h); diag_put(5, n_chn);
+	}
 	if (a.dbg_chain_n) {                                        // stage dump: chains before filtering
 		a.dbg_chain_n[r] = n_chn;
 		write_chains(c, a.ix, n_chn, c.ord, frac_rep, false, a.dbg_chains + sb, a.dbg_seeds + sb);
@@ -491,12 +500,16 @@ __device__ __forceinline__ void chain_read(const ChainLaunch &a, int r, BtNode *
 				for (int i = c.lane; i < n_chn; i += 64) c.ord[i] = work[i];
 				__threadfence_block(); __syncthreads();
 			}
-		}
+			diag_put(3, sorted ? CHAIN_SORT_WAVE : CHAIN_SORT_LANE_DEPTH);
+		} else if (n_chn >= 2) diag_put(3, CHAIN_SORT_LANE_AREA);
 		if (!sorted && n_chn >= 2) {
 			if (c.lane == 0) isort_weight(c, n_chn, c.ord);
 			__threadfence_block(); __syncthreads();
 		}
-	} else isort_weight(c, n_chn, c.ord);                       // exact unstable introsort
+	} else {
+		isort_weight(c, n_chn, c.ord);                          // exact unstable introsort
+		if (n_chn >= 2) diag_put(3, CHAIN_SORT_LANE);
+	}
 	const unsigned long long t_2 = wall_clock64();
 	if (n_chn > FLT_SEQ_MAX && a.heavy_list) {
 		// many chains: the O(n^2) overlap filter runs wavefront-parallel in k_chain_flt; leave it the per-position data
@@ -513,6 +526,7 @@ __device__ __forceinline__ void chain_read(const ChainLaunch &a, int r, BtNode *
 		return;
 	}
 	// NB: `first` and the kept list hold positions in the sorted array, as in the reference
+	diag_put(4, CHAIN_FLT_SEQ);
 	int n_keep = 0;
 	c.kept[c.ord[0]] = 3;
 	c.keep_list[n_keep++] = 0;
@@ -596,7 +610,7 @@ __global__ __launch_bounds__(64) void k_chain_big(ChainLaunch a)
 		if ((threadIdx.x & 63) == 0) h = atomicAdd(&a.big_count[4 + CLS], 1);
 		h = __shfl(h, 0);
 		if (h >= n_mine) break;
-		chain_read<true>(a, a.big_list[(size_t)CLS * a.n_reads + h], nodes, NODES, s_area, LDS_BYTES);
+		chain_read<true>(a, a.big_list[(size_t)CLS * a.n_reads + h], nodes, NODES, s_area, LDS_BYTES, CLS);
 		__threadfence_block(); __syncthreads();
 	}
 	// The kernel with the nodes in global memory is slower per read but is not held to one or two workgroups per CU by 77 / 150 KB of LDS.
@@ -612,7 +626,7 @@ __global__ __launch_bounds__(64) void k_chain_big(ChainLaunch a)
 				if ((threadIdx.x & 63) == 0) h = atomicAdd(&a.big_count[4 + cls], 1);
 				h = __shfl(h, 0);
 				if (h >= n_cls) break;
-				chain_read<true>(a, a.big_list[(size_t)cls * a.n_reads + h], nullptr, 0, s_area, LDS_BYTES);
+				chain_read<true>(a, a.big_list[(size_t)cls * a.n_reads + h], nullptr, 0, s_area, LDS_BYTES, CHAIN_DIAG_HELPED);
 				__threadfence_block(); __syncthreads();
 			}
 		}
@@ -690,6 +704,7 @@ __global__ __launch_bounds__(64) void k_chain_flt(ChainLaunch a)
 			int n_out = 0, tot = 0;
 			for (i = 0; i < n; ++i) if (kept[i] != 0) { oidx[n_out] = i; ooff[n_out] = tot; tot += cw[ord[i]].n; ++n_out; }
 			a.chain_n[r] = n_out; a.kept_seeds[r] = tot;
+			if (a.diag) a.diag[CHAIN_DIAG_N * (size_t)r + 4] = CHAIN_FLT_WAVE;
 		}
 		__threadfence_block(); __syncthreads();
 		const int n_out = a.chain_n[r];

@@ -395,6 +395,9 @@ int bwahip_ctx_tune(bwahip_ctx *c, const char *key, int value)
 	else if (!strcmp(key, "smem_lanes")) { if (value != 1 && value != 2 && value != 4 && value != 8) return BWAHIP_EINVAL; k.smem_lanes = value; }
 	else if (!strcmp(key, "heavy_mult")) k.heavy_mult = value;
 	else if (!strcmp(key, "chain_big_min")) k.chain_big_min = value;
+	else if (!strcmp(key, "chain_mid_max")) k.chain_mid_max = value;      // the launch clamps these two to the LDS budgets (1536 / 3200 seeds)
+	else if (!strcmp(key, "chain_big_max")) k.chain_big_max = value;
+	else if (!strcmp(key, "chain_glb_grid")) { if (value < 1 || value > 65536) return BWAHIP_EINVAL; k.chain_glb_grid = value; }
 	else if (!strcmp(key, "rank_sort_min")) k.rank_sort_min = value;
 	else if (!strcmp(key, "spec_min_chains")) k.spec_min_chains = value;
 	else if (!strcmp(key, "ext_lds_window")) k.ext_lds_window = value < 1 ? 1 : value;
@@ -669,6 +672,44 @@ const char *bwahip_kernel_name(int i) { return i >= 0 && i < bwahip_n_kernels() 
 
 } // extern "C" (the pipeline itself has C++ linkage: final_rt.hip calls it)
 
+// K3's working storage, sized from the seed count, and its launch record: n reads whose seeds (`total` of them) lie in c->d_seeds by
+// c->d_seed_base and whose intervals lie in c->d_intv (cap per read).  off: the reads' offsets on the device (only the lengths are read).
+// run_pipeline and bwahip_kat_chain both come through here, so that the known-answer entry launches on the product's own layout.
+static int chain_prepare(bwahip_ctx *c, const DevOpt &dopt, int n, int64_t total, const int64_t *off, int cap, bool dump, unsigned long long *counters, ChainLaunch &cl)
+{
+	int rc;
+	const size_t T = (size_t)(total ? total : 1);
+	if ((rc = c->d_cw.ensure(T * sizeof(ChainWOpaque))) || (rc = c->d_nxt.ensure(T * 4)) || (rc = c->d_ord.ensure(T * 4)) ||
+	    (rc = c->d_wts.ensure(T * 4)) || (rc = c->d_kept.ensure(T * 4)) || (rc = c->d_first.ensure(T * 4)) || (rc = c->d_keep.ensure(T * 4)) ||
+	    (rc = c->d_nodes.ensure(((T >> 2) + 4 * (size_t)n + 8) * sizeof(BtNodeOpaque))) || (rc = c->d_stack.ensure((size_t)n * 256 * 4)) ||
+	    (rc = c->d_chains.ensure(T * sizeof(DevChain))) || (rc = c->d_chain_seeds.ensure(T * sizeof(DevSeed))) ||
+	    (rc = c->d_chain_n.ensure((size_t)n * 4)) || (rc = c->d_kept_seeds.ensure((size_t)n * 4)) || (rc = c->d_reg_base.ensure((size_t)(n + 1) * 8)))
+		return rc;
+	if (dump && ((rc = c->d_dbg_chains.ensure(T * sizeof(DevChain))) || (rc = c->d_dbg_seeds.ensure(T * sizeof(DevSeed))) || (rc = c->d_dbg_chain_n.ensure((size_t)n * 4))))
+		return rc;
+	memset(&cl, 0, sizeof cl);
+	cl.ix = c->ix; cl.opt = dopt; cl.n_reads = n; cl.off = off;
+	cl.intv = c->d_intv.as<DevIntv>(); cl.intv_n = c->d_intv_n.as<int>(); cl.cap = cap;
+	cl.seed_base = c->d_seed_base.as<int64_t>(); cl.seeds = c->d_seeds.as<DevSeed>();
+	cl.cw_ = c->d_cw.as<ChainWOpaque>(); cl.nxt = c->d_nxt.as<int>(); cl.ord = c->d_ord.as<int>(); cl.wts = c->d_wts.as<int>();
+	cl.kept = c->d_kept.as<int>(); cl.first = c->d_first.as<int>(); cl.keep_list = c->d_keep.as<int>();
+	cl.nodes_ = c->d_nodes.as<BtNodeOpaque>(); cl.stack = c->d_stack.as<int>();
+	cl.chains = c->d_chains.as<DevChain>(); cl.chain_seeds = c->d_chain_seeds.as<DevSeed>();
+	cl.chain_n = c->d_chain_n.as<int>(); cl.kept_seeds = c->d_kept_seeds.as<int>();
+	cl.counters = counters;
+	if ((rc = c->d_flt.ensure(T * 32)) || (rc = c->d_heavy.ensure((size_t)(n + 4) * 4))) return rc;
+	cl.flt = c->d_flt.as<int>(); cl.heavy_list = c->d_heavy.as<int>() + 4; cl.heavy_count = c->d_heavy.as<int>();
+	const int big_min = c->knobs.chain_big_min;              // seeds; < 0 = off
+	if (big_min >= 0) {
+		if ((rc = c->d_chain_big.ensure(((size_t)4 * n + 8) * 4))) return rc;
+		HIP_TRY(hipMemsetAsync(c->d_chain_big.p, 0, 32, c->stream));
+		cl.big_list = c->d_chain_big.as<int>() + 8; cl.big_count = c->d_chain_big.as<int>(); cl.big_min = big_min; cl.big_max = std::min(c->knobs.chain_big_max, 3200); cl.mid_max = std::min(c->knobs.chain_mid_max, 1536); cl.glb_grid = std::max(c->knobs.chain_glb_grid, 64);   // 800 LDS nodes >= 0.24 x seeds (every node but the root holds >= 5 keys)
+	}
+	HIP_TRY(hipMemsetAsync(c->d_heavy.p, 0, 16, c->stream));
+	if (dump) { cl.dbg_chains = c->d_dbg_chains.as<DevChain>(); cl.dbg_seeds = c->d_dbg_seeds.as<DevSeed>(); cl.dbg_chain_n = c->d_dbg_chain_n.as<int>(); }
+	return 0;
+}
+
 int run_pipeline(bwahip_ctx *c, const bwahip_opt_t *opt, bool timed, bool dump)
 {
 	const bool verbose = c->knobs.verbose != 0;
@@ -746,35 +787,8 @@ int run_pipeline(bwahip_ctx *c, const bwahip_opt_t *opt, bool timed, bool dump)
 		if (timed) HIP_TRY(hipEventRecord(c->ev[4], c->stream));
 		// ---- K3: chaining + chain filter
 		const size_t T = (size_t)(total ? total : 1);
-		if ((rc = c->d_cw.ensure(T * sizeof(ChainWOpaque))) || (rc = c->d_nxt.ensure(T * 4)) || (rc = c->d_ord.ensure(T * 4)) ||
-		    (rc = c->d_wts.ensure(T * 4)) || (rc = c->d_kept.ensure(T * 4)) || (rc = c->d_first.ensure(T * 4)) || (rc = c->d_keep.ensure(T * 4)) ||
-		    (rc = c->d_nodes.ensure(((T >> 2) + 4 * (size_t)n + 8) * sizeof(BtNodeOpaque))) || (rc = c->d_stack.ensure((size_t)n * 256 * 4)) ||
-		    (rc = c->d_chains.ensure(T * sizeof(DevChain))) || (rc = c->d_chain_seeds.ensure(T * sizeof(DevSeed))) ||
-		    (rc = c->d_chain_n.ensure((size_t)n * 4)) || (rc = c->d_kept_seeds.ensure((size_t)n * 4)) || (rc = c->d_reg_base.ensure((size_t)(n + 1) * 8)))
-			return rc;
-		if (dump && ((rc = c->d_dbg_chains.ensure(T * sizeof(DevChain))) || (rc = c->d_dbg_seeds.ensure(T * sizeof(DevSeed))) || (rc = c->d_dbg_chain_n.ensure((size_t)n * 4))))
-			return rc;
 		ChainLaunch cl;
-		memset(&cl, 0, sizeof cl);
-		cl.ix = c->ix; cl.opt = dopt; cl.n_reads = n; cl.off = c->in->d_off.as<int64_t>();
-		cl.intv = c->d_intv.as<DevIntv>(); cl.intv_n = c->d_intv_n.as<int>(); cl.cap = cap;
-		cl.seed_base = c->d_seed_base.as<int64_t>(); cl.seeds = c->d_seeds.as<DevSeed>();
-		cl.cw_ = c->d_cw.as<ChainWOpaque>(); cl.nxt = c->d_nxt.as<int>(); cl.ord = c->d_ord.as<int>(); cl.wts = c->d_wts.as<int>();
-		cl.kept = c->d_kept.as<int>(); cl.first = c->d_first.as<int>(); cl.keep_list = c->d_keep.as<int>();
-		cl.nodes_ = c->d_nodes.as<BtNodeOpaque>(); cl.stack = c->d_stack.as<int>();
-		cl.chains = c->d_chains.as<DevChain>(); cl.chain_seeds = c->d_chain_seeds.as<DevSeed>();
-		cl.chain_n = c->d_chain_n.as<int>(); cl.kept_seeds = c->d_kept_seeds.as<int>();
-		cl.counters = counters;
-		if ((rc = c->d_flt.ensure(T * 32)) || (rc = c->d_heavy.ensure((size_t)(n + 4) * 4))) return rc;
-		cl.flt = c->d_flt.as<int>(); cl.heavy_list = c->d_heavy.as<int>() + 4; cl.heavy_count = c->d_heavy.as<int>();
-		const int big_min = c->knobs.chain_big_min;              // seeds; < 0 = off
-		if (big_min >= 0) {
-			if ((rc = c->d_chain_big.ensure(((size_t)4 * n + 8) * 4))) return rc;
-			HIP_TRY(hipMemsetAsync(c->d_chain_big.p, 0, 32, c->stream));
-			cl.big_list = c->d_chain_big.as<int>() + 8; cl.big_count = c->d_chain_big.as<int>(); cl.big_min = big_min; cl.big_max = std::min(c->knobs.chain_big_max, 3200); cl.mid_max = std::min(c->knobs.chain_mid_max, 1536); cl.glb_grid = std::max(c->knobs.chain_glb_grid, 64);   // 800 LDS nodes >= 0.24 x seeds (every node but the root holds >= 5 keys)
-		}
-		HIP_TRY(hipMemsetAsync(c->d_heavy.p, 0, 16, c->stream));
-		if (dump) { cl.dbg_chains = c->d_dbg_chains.as<DevChain>(); cl.dbg_seeds = c->d_dbg_seeds.as<DevSeed>(); cl.dbg_chain_n = c->d_dbg_chain_n.as<int>(); }
+		if ((rc = chain_prepare(c, dopt, n, total, c->in->d_off.as<int64_t>(), cap, dump, counters, cl))) return rc;
 		if (timed) HIP_TRY(hipEventRecord(c->ev[5], c->stream));
 		if ((rc = launch_chain(cl, c->stream, c->stream2, c->stream3, c->ev_fork, c->ev_join, c->ev_join3))) return rc;
 		if ((rc = launch_chain_flt(cl, c->stream))) return rc;
@@ -1081,6 +1095,97 @@ int bwahip_batch_download(bwahip_ctx *c, bwahip_alnreg_v *out) { return batch_do
 // ------------------------------------------------------------------ stage dump (i64 records)
 static void rec(std::vector<int64_t> &o, int64_t tag, const std::vector<int64_t> &v) { stage_rec(o, tag, v); }
 
+// the words of BWAHIP_STAGE_CHAIN / BWAHIP_STAGE_CHAIN_FLT for one read (bwahip_run_stages, bwahip_kat_chain)
+static void stage_put_chains(std::vector<int64_t> &v, int cnt, const DevChain *ch, const DevSeed *sd)
+{
+	auto f2i = [](float f) { uint32_t u; memcpy(&u, &f, 4); return (int64_t)u; };
+	v.push_back(cnt);
+	for (int k = 0; k < cnt; ++k) {
+		const DevChain &h = ch[k];
+		v.push_back(h.pos); v.push_back(h.rid); v.push_back(h.is_alt); v.push_back(h.w); v.push_back(h.kept);
+		v.push_back(h.first); v.push_back(f2i(h.frac_rep)); v.push_back(h.n);
+		for (int t = 0; t < h.n; ++t) { const DevSeed &d = sd[h.seed_off + t]; v.push_back(d.rbeg); v.push_back(d.qbeg); v.push_back(d.len); v.push_back(d.score); }
+	}
+}
+
+// Chaining and the chain filter (k_chain.hip) on caller seed lists; see bwahip.h.  The buffers, their sizes and the launches are run_pipeline's
+// (chain_prepare, launch_chain, launch_chain_flt) under the context's knobs; only the seeds and intervals come from the caller.
+int bwahip_kat_chain(bwahip_ctx *c, const bwahip_opt_t *opt, int n_reads, const int32_t *read_len, const int64_t *seed_off, const int64_t *seeds4,
+                     const int64_t *intv_off, const int64_t *intv3, int64_t **out, int64_t *out_len, int32_t *diag)
+{
+	if (!c || !opt || n_reads < 0 || !out || !out_len) return BWAHIP_EINVAL;
+	*out = nullptr; *out_len = 0;
+	if (n_reads == 0) return 0;
+	if (!read_len || !seed_off || !intv_off || seed_off[0] != 0 || intv_off[0] != 0) return BWAHIP_EINVAL;
+	const int n = n_reads;
+	int cap = 1;
+	std::vector<int64_t> off((size_t)n + 1, 0);
+	for (int i = 0; i < n; ++i) {
+		if (read_len[i] < 1 || read_len[i] > BWAHIP_MAX_READ_LEN || seed_off[i + 1] < seed_off[i] || intv_off[i + 1] < intv_off[i] || intv_off[i + 1] - intv_off[i] > (1 << 20)) return BWAHIP_EINVAL;
+		off[i + 1] = off[i] + read_len[i];
+		cap = std::max(cap, (int)(intv_off[i + 1] - intv_off[i]));
+	}
+	const int64_t total = seed_off[n], n_intv = intv_off[n];
+	if (total > (1 << 26) || (size_t)n * cap > ((size_t)1 << 26) || (total && !seeds4) || (n_intv && !intv3)) return BWAHIP_EINVAL;
+	std::vector<DevSeed> hs((size_t)total + 1);
+	for (int i = 0; i < n; ++i)
+		for (int64_t t = seed_off[i]; t < seed_off[i + 1]; ++t) {
+			const int64_t *w = seeds4 + 4 * t;
+			// what k_seeds can produce: a seed inside the read and inside the doubled reference, its contig a real one (or none: skipped by mem_chain)
+			if (w[0] < 0 || w[2] < 1 || w[1] < 0 || w[1] + w[2] > read_len[i] || w[0] + w[2] > 2 * c->ix.l_pac || w[3] < -1 || w[3] >= c->ix.n_seqs) return BWAHIP_EINVAL;
+			hs[(size_t)t] = DevSeed{ w[0], (int32_t)w[1], (int32_t)w[2], (int32_t)w[2], (int32_t)w[3] };
+		}
+	std::vector<DevIntv> hi((size_t)n * cap);
+	std::vector<int> hin(n);
+	for (int i = 0; i < n; ++i) {
+		hin[i] = (int)(intv_off[i + 1] - intv_off[i]);
+		for (int t = 0; t < hin[i]; ++t) {
+			const int64_t *w = intv3 + 3 * (intv_off[i] + t);
+			if (w[0] < 0 || w[1] < 0 || w[2] < w[1] || w[2] > read_len[i]) return BWAHIP_EINVAL;
+			hi[(size_t)i * cap + t] = DevIntv{ 0, 0, (uint64_t)w[0], (uint64_t)w[1] << 32 | (uint64_t)w[2] };
+		}
+	}
+	HIP_TRY(hipSetDevice(c->device));
+	DevBuf d_off, d_diag; int rc;
+	ChainLaunch cl;
+	const size_t T = (size_t)total + 1;
+	std::vector<DevChain> h_ch(T), h_dch(T);
+	std::vector<DevSeed> h_cs(T), h_dcs(T);
+	std::vector<int> h_chn(n), h_dchn(n);
+	std::vector<int64_t> o, v;
+	if ((rc = upload(d_off, off.data(), off.size() * 8, c->stream)) || (rc = upload(c->d_seed_base, seed_off, (size_t)(n + 1) * 8, c->stream)) ||
+	    (rc = upload(c->d_seeds, hs.data(), hs.size() * sizeof(DevSeed), c->stream)) || (rc = upload(c->d_intv, hi.data(), hi.size() * sizeof(DevIntv), c->stream)) ||
+	    (rc = upload(c->d_intv_n, hin.data(), (size_t)n * 4, c->stream)) || (rc = d_diag.ensure((size_t)n * CHAIN_DIAG_N * 4))) goto done;
+	if ((rc = chain_prepare(c, make_dev_opt(opt), n, total, d_off.as<int64_t>(), cap, true, nullptr, cl))) goto done;
+	if (hipMemsetAsync(d_diag.p, 0, (size_t)n * CHAIN_DIAG_N * 4, c->stream) != hipSuccess) { rc = BWAHIP_ENODEV; goto done; }
+	cl.diag = d_diag.as<int>();
+	if ((rc = launch_chain(cl, c->stream, c->stream2, c->stream3, c->ev_fork, c->ev_join, c->ev_join3)) || (rc = launch_chain_flt(cl, c->stream))) goto done;
+	if ((total && (hipMemcpyAsync(h_ch.data(), c->d_chains.p, (size_t)total * sizeof(DevChain), hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+	               hipMemcpyAsync(h_cs.data(), c->d_chain_seeds.p, (size_t)total * sizeof(DevSeed), hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+	               hipMemcpyAsync(h_dch.data(), c->d_dbg_chains.p, (size_t)total * sizeof(DevChain), hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+	               hipMemcpyAsync(h_dcs.data(), c->d_dbg_seeds.p, (size_t)total * sizeof(DevSeed), hipMemcpyDeviceToHost, c->stream) != hipSuccess)) ||
+	    hipMemcpyAsync(h_chn.data(), c->d_chain_n.p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+	    hipMemcpyAsync(h_dchn.data(), c->d_dbg_chain_n.p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+	    (diag && hipMemcpyAsync(diag, d_diag.p, (size_t)n * CHAIN_DIAG_N * 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess)) rc = BWAHIP_ENODEV;
+done:
+	if (hipStreamSynchronize(c->stream) != hipSuccess && !rc) rc = BWAHIP_ENODEV;
+	d_off.release(); d_diag.release();
+	if (rc) return rc;
+	for (int i = 0; i < n; ++i) {
+		const int64_t S = seed_off[i + 1] - seed_off[i];
+		if (h_chn[i] < 0 || h_chn[i] > S || h_dchn[i] < 0 || h_dchn[i] > S) return BWAHIP_EINTERNAL;
+		v = { (int64_t)i, (int64_t)read_len[i] };
+		rec(o, 100, v);
+		v.clear(); stage_put_chains(v, h_dchn[i], &h_dch[(size_t)seed_off[i]], &h_dcs[(size_t)seed_off[i]]); rec(o, BWAHIP_STAGE_CHAIN, v);
+		v.clear(); stage_put_chains(v, h_chn[i], &h_ch[(size_t)seed_off[i]], &h_cs[(size_t)seed_off[i]]); rec(o, BWAHIP_STAGE_CHAIN_FLT, v);
+	}
+	*out = (int64_t*)malloc(o.size() * 8 + 8);
+	if (!*out) return BWAHIP_ENOMEM;
+	memcpy(*out, o.data(), o.size() * 8);
+	*out_len = (int64_t)o.size();
+	return 0;
+}
+
 int bwahip_run_stages(bwahip_ctx *c, const bwahip_opt_t *opt, int n, const uint8_t *seq, const int64_t *off,
                       int stage_mask, int64_t **out, int64_t *out_len)
 {
@@ -1101,7 +1206,6 @@ int bwahip_run_stages(bwahip_ctx *c, const bwahip_opt_t *opt, int n, const uint8
 		HIP_TRY(hipMemcpy(h_base.data(), c->d_seed_base.p, (size_t)(n + 1) * 8, hipMemcpyDeviceToHost));
 		if (c->total_seeds) HIP_TRY(hipMemcpy(h_seeds.data(), c->d_seeds.p, (size_t)c->total_seeds * sizeof(DevSeed), hipMemcpyDeviceToHost));
 	}
-	auto f2i = [](float f) { uint32_t u; memcpy(&u, &f, 4); return (int64_t)u; };
 	const size_t T = (size_t)c->total_seeds + 1, R = (size_t)c->total_regs + 1;
 	std::vector<DevChain> h_ch(T), h_dch(T);
 	std::vector<DevSeed> h_cs(T), h_dcs(T);
@@ -1125,15 +1229,7 @@ int bwahip_run_stages(bwahip_ctx *c, const bwahip_opt_t *opt, int n, const uint8
 			HIP_TRY(hipMemcpy(h_dregs.data(), c->d_dbg_regs.p, (size_t)c->total_regs * sizeof(DevReg), hipMemcpyDeviceToHost));
 		}
 	}
-	auto put_chains = [&](std::vector<int64_t> &v, int cnt, const DevChain *ch, const DevSeed *sd) {
-		v.push_back(cnt);
-		for (int k = 0; k < cnt; ++k) {
-			const DevChain &h = ch[k];
-			v.push_back(h.pos); v.push_back(h.rid); v.push_back(h.is_alt); v.push_back(h.w); v.push_back(h.kept);
-			v.push_back(h.first); v.push_back(f2i(h.frac_rep)); v.push_back(h.n);
-			for (int t = 0; t < h.n; ++t) { const DevSeed &d = sd[h.seed_off + t]; v.push_back(d.rbeg); v.push_back(d.qbeg); v.push_back(d.len); v.push_back(d.score); }
-		}
-	};
+	auto put_chains = [&](std::vector<int64_t> &v, int cnt, const DevChain *ch, const DevSeed *sd) { stage_put_chains(v, cnt, ch, sd); };
 	auto put_regs = [&](std::vector<int64_t> &v, int cnt, const DevReg *rg) { stage_put_regs(v, cnt, rg); };
 	for (int i = 0; i < n; ++i) {
 		std::vector<int64_t> v = { (int64_t)i, off[i + 1] - off[i] };

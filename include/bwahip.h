@@ -796,6 +796,23 @@ int bwahip_kat_introsort(bwahip_ctx *ctx, int n, int mode, const int64_t *k64, c
 int bwahip_kat_mate_insert(bwahip_ctx *ctx, const bwahip_opt_t *opt, int n_items, const int64_t *list_off, const int64_t *list_words, const int64_t *step_off,
                            const int32_t *step_hit, const int64_t *step_words, int mode, int where, int64_t *out_words, int32_t *out_n, int32_t *out_cnt3);
 
+/* Chaining and the chain filter (mem_chain's seed loop bwamem.c:280-317, mem_chain_flt bwamem.c:334-392) through the kernels of
+ * csrc/k_chain.hip, on caller seed lists: the buffers, their sizes and the launches are those of the stage chain, under the context's
+ * knobs (chain_big_min, chain_mid_max, chain_big_max, chain_glb_grid).  Read i: read_len[i] bases (1 .. BWAHIP_MAX_READ_LEN); its seeds
+ * seeds4[4 * seed_off[i] .. 4 * seed_off[i + 1]) as (rbeg, qbeg, len, rid) in look-up order -- rid the contig of bns_intv2rid, -1 for a
+ * seed mem_chain skips; its intervals intv3[3 * intv_off[i] ..) as (x[2], qbeg, qend) in sorted order, read only for frac_rep.
+ * *out: a malloc()ed stream of i64 records, per read [100: i, len], BWAHIP_STAGE_CHAIN (the chains before the filter; w, kept, first 0),
+ * BWAHIP_STAGE_CHAIN_FLT.  diag (may be NULL): BWAHIP_CHAIN_DIAG_N ints per read -- [0] who took the read: -1 k_chain (one read per lane),
+ * 0..3 the class of k_chain_big (B-tree in 14 / 77 / 150 KB of LDS, in global memory), 4 a class 1 / 2 read that the global-memory kernel
+ * took off the queue; [1] B-tree nodes used; [2] tree height; [3] the sort by weight: 0 fewer than two chains, 1 k_chain's one-lane
+ * introsort, 2 the wavefront's, 3 one lane because the sort area was too small, 4 one lane because the depth limit was hit; [4] the
+ * overlap filter: 0 none, 1 sequential, 2 k_chain_flt; [5] chains before the filter.
+ * BWAHIP_EINVAL: offsets that do not start at 0 or do not ascend, a seed outside its read or the reference, a contig that does not
+ * exist.  n_reads == 0 launches nothing. */
+#define BWAHIP_CHAIN_DIAG_N 8
+int bwahip_kat_chain(bwahip_ctx *ctx, const bwahip_opt_t *opt, int n_reads, const int32_t *read_len, const int64_t *seed_off, const int64_t *seeds4,
+                     const int64_t *intv_off, const int64_t *intv3, int64_t **out, int64_t *out_len, int32_t *diag);
+
 /* The stable LSD radix sort of the coordinate-sorted BAM output (csrc/k_bamsort.hip) on caller keys: exactly the product's passes for
  * keys of key_bits (1..64) significant bits -- 8 bits per pass, passes in which all keys agree skipped.  idx_out[i] = input position of
  * the i-th key in sorted order, equal keys in input order; *tile_out (may be NULL): items one workgroup ranks per pass.  n <= 1 launches
@@ -821,7 +838,11 @@ int bwahip_kat_ksw_align(bwahip_ctx *ctx, int n, const int *params, const int8_t
  * BGZF blocks a device merger gathers and deflates at a time (bwahip_bam_devmerger_open with piece_blocks <= 0; the bytes do not depend on it);
  * and incr_insert (0 or 1, default 1): mate rescue places a rescued region into a list that the last mem_sort_dedup_patch left free of
  * ties without sorting the list again -- 0 ends every orientation in the full sort-and-dedup, as the reference does.  The knob changes
- * no result: lists, pairing and output are the same with either value, only bwahip_last_pe_paths [4] and [5] differ.
+ * no result: lists, pairing and output are the same with either value, only bwahip_last_pe_paths [4] and [5] differ;
+ * and chain_mid_max / chain_big_max (defaults 1536 / 3200, larger values are held to these): the seeds up to which a read taken by a
+ * wavefront (more than chain_big_min seeds, and more than 256) keeps its B-tree in 77 KB / 150 KB of LDS, beyond chain_big_max in
+ * global memory; chain_glb_grid (1 .. 65536, default 2048, at least 64 are launched): the workgroups of that last kernel.  None of
+ * the three changes a result.
  * The same knobs are read from the environment (BWAHIP_<KEY>) once, when the context is created. */
 int bwahip_ctx_tune(bwahip_ctx *ctx, const char *key, int value);
 

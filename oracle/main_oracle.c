@@ -3,6 +3,7 @@
  *   bwa_oracle mem    [-p] [-t N] [-K bases] [-a] <prefix> <r1.fq> [r2.fq]   SAM body on stdout
  *   bwa_oracle stages <prefix> <reads.fq> <out.bin>                          per-read stage dump
  *   bwa_oracle stages [options, -I] <prefix> <r1.fq> <r2.fq> <out.bin>       paired-end stage dump (one batch)
+ *   bwa_oracle katchain [options] <prefix> <cases.bin> <out.bin>             chains of caller-supplied seed lists
  * Batching follows bseq_read (bwa.c:191): reads are taken until the batch holds
  * >= chunk bases and an even number of reads.
  */
@@ -220,6 +221,57 @@ static int main_stages(int argc, char **argv)
 	return 0;
 }
 
+/* katchain [options] <prefix> <cases.bin> <out.bin>: ora_kat_chain on caller seeds.  cases.bin, per read: TAG_READ [id, len], record 6
+ * [(rbeg, qbeg, len, rid) per seed, look-up order], TAG_INTV [(x[2], qbeg, qend) per interval].  out.bin, per read: TAG_READ, TAG_CHAIN,
+ * TAG_CHAIN_FLT as `stages` writes them, and TAG_CHAIN_STAT [B-tree nodes, tree height, chains sorted, depth limit reached] (ours only:
+ * ref_driver.c's katchain stops at TAG_CHAIN_FLT). */
+enum { TAG_SEEDS = 6, TAG_CHAIN_STAT = 30 };
+static int main_katchain(int argc, char **argv)
+{
+	ora_opt_t opt;
+	ora_index_t *idx;
+	optparse_t op;
+	FILE *in, *out;
+	int64_t hdr[2], *rd[3] = { 0, 0, 0 }, rn[3] = { 0, 0, 0 };
+	int c, k, rc = 0;
+	ora_opt_init(&opt);
+	optparse_init(&op, &opt);
+	while ((c = getopt(argc, argv, OPT_GETOPT_STRING)) >= 0) if (optparse_one(&op, c, optarg)) return 1;
+	if (optparse_finish(&op) || optind + 3 > argc) return 1;
+	idx = ora_index_load(argv[optind]);
+	if (!idx) return 1;
+	if (op.ignore_alt) for (c = 0; c < idx->ref->n_seqs; ++c) idx->ref->anns[c].is_alt = 0;
+	in = fopen(argv[optind + 1], "rb"); out = fopen(argv[optind + 2], "wb");
+	if (!in || !out) return 1;
+	while (fread(hdr, 8, 2, in) == 2) {
+		static const int64_t want[3] = { TAG_READ, TAG_SEEDS, TAG_INTV };
+		ora_chain_v un, flt;
+		int stat[4], i;
+		int64_t st[4];
+		for (k = 0; k < 3; ++k) {                              /* the three records of a read, in this order */
+			if (k && fread(hdr, 8, 2, in) != 2) { rc = 1; break; }
+			if (hdr[0] != want[k] || hdr[1] < 0) { rc = 1; break; }
+			rn[k] = hdr[1]; rd[k] = (int64_t*)realloc(rd[k], (hdr[1] + 1) * 8);
+			if (hdr[1] && fread(rd[k], 8, hdr[1], in) != (size_t)hdr[1]) { rc = 1; break; }
+		}
+		if (rc || rn[0] != 2 || rn[1] % 4 || rn[2] % 3) { rc = 1; break; }
+		ora_kat_chain(&opt, idx, (int)rd[0][1], (int)(rn[1] / 4), rd[1], (int)(rn[2] / 3), rd[2], &un, &flt, stat);
+		rec_write(out, TAG_READ, 2, rd[0]);
+		dump_chains(out, TAG_CHAIN, un.n, un.a);
+		dump_chains(out, TAG_CHAIN_FLT, flt.n, flt.a);
+		for (i = 0; i < 4; ++i) st[i] = stat[i];
+		rec_write(out, TAG_CHAIN_STAT, 4, st);
+		for (i = 0; i < un.n; ++i) free(un.a[i].seeds);
+		for (i = 0; i < flt.n; ++i) free(flt.a[i].seeds);
+		free(un.a); free(flt.a);
+	}
+	for (k = 0; k < 3; ++k) free(rd[k]);
+	fclose(in); fclose(out);
+	ora_index_destroy(idx);
+	if (rc) fprintf(stderr, "[bwa_oracle] katchain: malformed case file\n");
+	return rc;
+}
+
 static int main_mem(int argc, char **argv)
 {
 	ora_opt_t opt;
@@ -265,6 +317,7 @@ int main(int argc, char **argv)
 {
 	if (argc >= 2 && strcmp(argv[1], "mem") == 0) return main_mem(argc - 1, argv + 1);
 	if (argc >= 2 && strcmp(argv[1], "stages") == 0) return main_stages(argc - 1, argv + 1);
-	fprintf(stderr, "usage: bwa_oracle <mem|stages> ...\n");
+	if (argc >= 2 && strcmp(argv[1], "katchain") == 0) return main_katchain(argc - 1, argv + 1);
+	fprintf(stderr, "usage: bwa_oracle <mem|stages|katchain> ...\n");
 	return 1;
 }

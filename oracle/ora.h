@@ -46,6 +46,8 @@ void ora_opt_init(ora_opt_t *o);                                                
 void ora_fill_scmat(int a, int b, int8_t mat[25]);                                                    /* bwa.c:249 */
 void ora_collect_intv(const ora_opt_t *opt, const ora_fmi_t *f, int len, const uint8_t *seq, ora_aux_t *a);   /* bwamem.c:137 */
 ora_chain_v ora_chain(const ora_opt_t *opt, const ora_index_t *idx, int len, const uint8_t *seq, ora_aux_t *aux); /* bwamem.c:258 */
+void ora_kat_chain(const ora_opt_t *opt, const ora_index_t *idx, int len, int n_seeds, const int64_t *seeds4, int n_intv, const int64_t *intv3,
+                   ora_chain_v *unfiltered, ora_chain_v *filtered, int stat4[4]);   /* test helper: the seed loop of ora_chain + ora_chain_flt on a caller's seeds */
 int ora_chain_weight(const ora_chain_t *c);                                                           /* bwamem.c:220 */
 int ora_chain_flt(const ora_opt_t *opt, int n_chn, ora_chain_t *a);                                   /* bwamem.c:334 */
 void ora_flt_chained_seeds(const ora_opt_t *opt, const ora_ref_t *r, int l_query, const uint8_t *query, int n_chn, ora_chain_t *a); /* bwamem.c:605 */

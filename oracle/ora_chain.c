@@ -116,7 +116,8 @@ typedef struct bt_node {
 } bt_node;
 typedef struct { bt_node *root; int n_keys; ora_chain_t *pool; int n_pool, m_pool; } btree;
 
-static bt_node *bt_newnode(void) { return (bt_node*)calloc(1, sizeof(bt_node)); }
+static __thread int bt_nodes_made;                        /* counted for ora_kat_chain's statistics */
+static bt_node *bt_newnode(void) { ++bt_nodes_made; return (bt_node*)calloc(1, sizeof(bt_node)); }
 static void bt_free(bt_node *x) { int i; if (!x) return; if (x->is_internal) for (i = 0; i <= x->n; ++i) bt_free(x->ptr[i]); free(x); }
 
 /* kbtree.h:119 __kb_getp_aux: index of the first key >= pos if it equals pos
@@ -254,12 +255,49 @@ int ora_chain_weight(const ora_chain_t *c)              /* bwamem.c:220 */
 	return w < 1 << 30 ? w : (1 << 30) - 1;
 }
 
+/* bwamem.c:295-306: one seed of a contig (rid >= 0) goes into the chain with the greatest pos <= rbeg, or opens a chain */
+static void chain_add_seed(const ora_opt_t *opt, const ora_ref_t *ref, btree *tree, const ora_seed_t *s, int rid)
+{
+	int to_add = 0, lower;
+	if (tree->n_keys) {
+		lower = bt_lower(tree, s->rbeg);
+		if (lower < 0 || !try_merge(opt, ref->l_pac, &tree->pool[lower], s, rid)) to_add = 1;
+	} else to_add = 1;
+	if (to_add) {
+		ora_chain_t *c;
+		if (tree->n_pool == tree->m_pool) {
+			tree->m_pool = tree->m_pool ? tree->m_pool << 1 : 16;
+			tree->pool = (ora_chain_t*)realloc(tree->pool, tree->m_pool * sizeof(ora_chain_t));
+		}
+		c = &tree->pool[tree->n_pool];
+		memset(c, 0, sizeof(*c));
+		c->n = 1; c->m = 4;
+		c->seeds = (ora_seed_t*)calloc(c->m, sizeof(ora_seed_t));
+		c->seeds[0] = *s;
+		c->pos = s->rbeg;
+		c->rid = rid;
+		c->is_alt = !!ref->anns[rid].is_alt;
+		bt_put(tree, tree->n_pool++);
+	}
+}
+
+/* bwamem.c:311-320: the chains in B-tree order; the tree is freed */
+static ora_chain_v chain_collect(btree *tree, int l_rep, int len)
+{
+	ora_chain_v chain = { 0, 0, 0 };
+	int i;
+	chain.m = tree->n_keys; chain.a = (ora_chain_t*)malloc(sizeof(ora_chain_t) * (tree->n_keys ? tree->n_keys : 1));
+	bt_inorder(tree->root, tree->pool, &chain);
+	for (i = 0; i < chain.n; ++i) chain.a[i].frac_rep = (float)l_rep / len;
+	bt_free(tree->root); free(tree->pool);
+	return chain;
+}
+
 ora_chain_v ora_chain(const ora_opt_t *opt, const ora_index_t *idx, int len, const uint8_t *seq, ora_aux_t *aux)   /* bwamem.c:258 */
 {
 	const ora_fmi_t *f = idx->fmi;
 	const ora_ref_t *ref = idx->ref;
 	int i, b, e, l_rep;
-	int64_t l_pac = ref->l_pac;
 	ora_chain_v chain = { 0, 0, 0 };
 	btree tree;
 	if (len < opt->min_seed_len) return chain;
@@ -281,40 +319,64 @@ ora_chain_v ora_chain(const ora_opt_t *opt, const ora_index_t *idx, int len, con
 		step = p->x[2] > (uint64_t)opt->max_occ ? (int)(p->x[2] / opt->max_occ) : 1;
 		for (k = count = 0; k < (int64_t)p->x[2] && count < opt->max_occ; k += step, ++count) {
 			ora_seed_t s;
-			int rid, to_add = 0, lower;
-			int64_t pos;
-			s.rbeg = pos = (int64_t)ora_sa(f, p->x[0] + k);
+			int rid;
+			s.rbeg = (int64_t)ora_sa(f, p->x[0] + k);
 			s.qbeg = p->info >> 32;
 			s.score = s.len = slen;
 			rid = ora_intv2rid(ref, s.rbeg, s.rbeg + s.len);
 			if (rid < 0) continue;
-			if (tree.n_keys) {
-				lower = bt_lower(&tree, pos);
-				if (lower < 0 || !try_merge(opt, l_pac, &tree.pool[lower], &s, rid)) to_add = 1;
-			} else to_add = 1;
-			if (to_add) {
-				ora_chain_t *c;
-				if (tree.n_pool == tree.m_pool) {
-					tree.m_pool = tree.m_pool ? tree.m_pool << 1 : 16;
-					tree.pool = (ora_chain_t*)realloc(tree.pool, tree.m_pool * sizeof(ora_chain_t));
-				}
-				c = &tree.pool[tree.n_pool];
-				memset(c, 0, sizeof(*c));
-				c->n = 1; c->m = 4;
-				c->seeds = (ora_seed_t*)calloc(c->m, sizeof(ora_seed_t));
-				c->seeds[0] = s;
-				c->pos = pos;
-				c->rid = rid;
-				c->is_alt = !!ref->anns[rid].is_alt;
-				bt_put(&tree, tree.n_pool++);
-			}
+			chain_add_seed(opt, ref, &tree, &s, rid);
 		}
 	}
-	chain.m = tree.n_keys; chain.a = (ora_chain_t*)malloc(sizeof(ora_chain_t) * (tree.n_keys ? tree.n_keys : 1));
-	bt_inorder(tree.root, tree.pool, &chain);
-	for (i = 0; i < chain.n; ++i) chain.a[i].frac_rep = (float)l_rep / len;
-	bt_free(tree.root); free(tree.pool);
-	return chain;
+	return chain_collect(&tree, l_rep, len);
+}
+
+/* Test helper: the seed loop of ora_chain and ora_chain_flt on a caller's seeds -- seeds4: (rbeg, qbeg, len, rid) per seed in look-up
+ * order, a seed with rid < 0 skipped as bwamem.c:294 skips it; intv3: (x[2], qbeg, qend) per interval in sorted order, read for frac_rep
+ * only.  *unfiltered: the chains in B-tree order (own copies of the seeds; w, kept, first 0); *filtered: what ora_chain_flt keeps.
+ * stat4 (may be NULL): B-tree nodes made, tree height (a lone leaf: 1), chains that reached the sort, and whether the sort reached the
+ * introsort's depth limit. */
+__thread int ora_sort_comb_calls;
+void ora_kat_chain(const ora_opt_t *opt, const ora_index_t *idx, int len, int n_seeds, const int64_t *seeds4, int n_intv, const int64_t *intv3,
+                   ora_chain_v *unfiltered, ora_chain_v *filtered, int stat4[4])
+{
+	const ora_ref_t *ref = idx->ref;
+	int i, b, e, l_rep, height = 1;
+	const bt_node *x;
+	btree tree;
+	memset(&tree, 0, sizeof tree);
+	bt_nodes_made = 0;
+	tree.root = bt_newnode();
+	for (i = 0, b = e = l_rep = 0; i < n_intv; ++i) {
+		int sb = (int)intv3[3 * i + 1], se = (int)intv3[3 * i + 2];
+		if ((uint64_t)intv3[3 * i] <= (uint64_t)opt->max_occ) continue;
+		if (sb > e) l_rep += e - b, b = sb, e = se;
+		else e = e > se ? e : se;
+	}
+	l_rep += e - b;
+	for (i = 0; i < n_seeds; ++i) {
+		ora_seed_t s;
+		s.rbeg = seeds4[4 * i]; s.qbeg = (int)seeds4[4 * i + 1]; s.score = s.len = (int)seeds4[4 * i + 2];
+		if (seeds4[4 * i + 3] < 0) continue;
+		chain_add_seed(opt, ref, &tree, &s, (int)seeds4[4 * i + 3]);
+	}
+	for (x = tree.root; x->is_internal; x = x->ptr[0]) ++height;
+	*filtered = chain_collect(&tree, l_rep, len);
+	unfiltered->n = unfiltered->m = filtered->n;
+	unfiltered->a = (ora_chain_t*)malloc(sizeof(ora_chain_t) * (filtered->n ? filtered->n : 1));
+	for (i = 0; i < filtered->n; ++i) {
+		ora_chain_t *c = &unfiltered->a[i];
+		*c = filtered->a[i];
+		c->seeds = (ora_seed_t*)malloc(sizeof(ora_seed_t) * c->m);
+		memcpy(c->seeds, filtered->a[i].seeds, sizeof(ora_seed_t) * c->n);
+	}
+	ora_sort_comb_calls = 0;
+	if (stat4) {
+		stat4[0] = bt_nodes_made; stat4[1] = height; stat4[2] = 0;
+		for (i = 0; i < filtered->n; ++i) stat4[2] += ora_chain_weight(&filtered->a[i]) >= opt->min_chain_weight;
+	}
+	filtered->n = ora_chain_flt(opt, filtered->n, filtered->a);
+	if (stat4) stat4[3] = ora_sort_comb_calls != 0;
 }
 
 #define CHN_BEG(ch) ((ch).seeds->qbeg)

@@ -13,6 +13,8 @@
 #define ORA_SORT_H
 #include <stdlib.h>
 
+extern __thread int ora_sort_comb_calls;   /* times a sort of this thread reached the depth limit (ora_chain.c; read by ora_kat_chain) */
+
 #define ORA_SORT_DEFINE(name, type_t, LT)                                                     \
 static void ora_insertion_##name(type_t *s, type_t *t)                                        \
 {                                                                                             \
@@ -26,6 +28,7 @@ static void ora_comb_##name(size_t n, type_t *a)                                
 	int swapped;                                                                              \
 	size_t gap = n;                                                                           \
 	type_t tmp, *i, *j;                                                                       \
+	++ora_sort_comb_calls;                                                                    \
 	do {                                                                                      \
 		if (gap > 2) {                                                                        \
 			gap = (size_t)(gap / shrink);                                                     \

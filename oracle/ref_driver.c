@@ -22,6 +22,7 @@
  *                                                other matrices / gap costs / xtra
  *   katdp  <out.bin> <n> <seed>                  known answers: ksw_extend2 / ksw_global2 over
  *                                                the whole range of lengths, bands, matrices
+ *   katchain [options] <prefix> <cases.bin> <out.bin>   known answers: chains and filtered chains of given seed lists
  *
  * Dump format ("i64 records"): a stream of  [tag:i64][n:i64][n x i64].
  */
@@ -206,6 +207,9 @@ static int main_stages(int argc, char **argv)
 		free(v.a);
 		/* stage 2: chains (bwamem.c:258) */
 		chn = mem_chain(opt, idx->bwt, idx->bns, l_seq, (uint8_t*)seq, aux);
+		/* w, kept and first are not set before mem_chain_flt (mem_chain's `tmp` is a stack variable, bwamem.c:287): what they hold depends
+		 * on how this file was compiled.  Dumped as 0, as the restatement has them; mem_chain_flt sets all three before it reads them. */
+		for (i = 0; i < chn.n; ++i) { chn.a[i].w = 0; chn.a[i].kept = 0; chn.a[i].first = 0; }
 		dump_chains(out, TAG_CHAIN, chn.n, chn.a);
 		/* stage 3: filtered chains (bwamem.c:334, 605) */
 		chn.n = mem_chain_flt(opt, chn.n, chn.a);
@@ -487,6 +491,92 @@ static int main_katdp(int argc, char **argv)
 	return 0;
 }
 
+/* katchain [options] <prefix> <cases.bin> <out.bin>: the reference's chaining on caller-supplied seeds -- its kbtree instantiation
+ * (bwamem.c:194), test_and_merge, and mem_chain_flt (with mem_chain_weight inside), driven the way mem_chain drives them from bwamem.c:286
+ * on.  cases.bin per read: TAG_READ [id, len], record 6 [(rbeg, qbeg, len, rid) per seed in look-up order; the rid given is ignored, the
+ * reference's bns_intv2rid decides], TAG_INTV [(x[2], qbeg, qend) per interval, for frac_rep].  out.bin per read: TAG_READ, TAG_CHAIN
+ * (w, kept, first as the tree holds them: not meaningful), TAG_CHAIN_FLT. */
+static int main_katchain(int argc, char **argv)
+{
+	mem_opt_t *opt = mem_opt_init();
+	bwaidx_t *idx;
+	optparse_t op;
+	FILE *in, *out;
+	int64_t hdr[2], *rd[3] = { 0, 0, 0 }, rn[3] = { 0, 0, 0 };
+	int c, k, rc = 0;
+	bwa_verbose = 1;
+	optparse_init(&op, opt);
+	while ((c = getopt(argc, argv, OPT_GETOPT_STRING)) >= 0) if (optparse_one(&op, c, optarg)) return 1;
+	if (optparse_finish(&op) || optind + 3 > argc) return 1;
+	idx = bwa_idx_load(argv[optind], BWA_IDX_BNS);
+	if (idx == 0) return 1;
+	if (op.ignore_alt) for (c = 0; c < idx->bns->n_seqs; ++c) idx->bns->anns[c].is_alt = 0;
+	in = fopen(argv[optind + 1], "rb"); out = fopen(argv[optind + 2], "wb");
+	if (!in || !out) return 1;
+	while (fread(hdr, 8, 2, in) == 2) {
+		static const int64_t want[3] = { TAG_READ, 6, TAG_INTV };
+		kbtree_t(chn) *tree;
+		mem_chain_v chain;
+		int64_t t;
+		int i, len, l_rep = 0, rb = 0, re = 0;
+		for (k = 0; k < 3; ++k) {
+			if (k && fread(hdr, 8, 2, in) != 2) { rc = 1; break; }
+			if (hdr[0] != want[k] || hdr[1] < 0) { rc = 1; break; }
+			rn[k] = hdr[1]; rd[k] = realloc(rd[k], (hdr[1] + 1) * 8);
+			if (hdr[1] && fread(rd[k], 8, hdr[1], in) != (size_t)hdr[1]) { rc = 1; break; }
+		}
+		if (rc || rn[0] != 2 || rn[1] % 4 || rn[2] % 3) { rc = 1; break; }
+		len = (int)rd[0][1];
+		for (t = 0; t < rn[2]; t += 3) {                       /* query bases under over-abundant intervals (bwamem.c:272-279) */
+			int qb = (int)rd[2][t + 1], qe = (int)rd[2][t + 2];
+			if ((uint64_t)rd[2][t] <= (uint64_t)opt->max_occ) continue;
+			if (qb > re) { l_rep += re - rb; rb = qb; re = qe; }
+			else if (qe > re) re = qe;
+		}
+		l_rep += re - rb;
+		tree = kb_init(chn, KB_DEFAULT_SIZE);
+		for (t = 0; t < rn[1]; t += 4) {
+			mem_chain_t key, *lower = 0, *upper = 0;
+			mem_seed_t s;
+			int rid, merged = 0;
+			s.rbeg = key.pos = rd[1][t]; s.qbeg = (int)rd[1][t + 1]; s.score = s.len = (int)rd[1][t + 2];
+			rid = bns_intv2rid(idx->bns, s.rbeg, s.rbeg + s.len);
+			if (rid < 0) continue;
+			if (kb_size(tree)) {
+				kb_intervalp(chn, tree, &key, &lower, &upper);
+				merged = lower && test_and_merge(opt, idx->bns->l_pac, lower, &s, rid);
+			}
+			if (!merged) {
+				memset(&key, 0, sizeof key);                   /* the reference leaves w / kept / first as they are; the tests mask them */
+				key.pos = s.rbeg; key.n = 1; key.m = 4;
+				key.seeds = calloc(key.m, sizeof(mem_seed_t));
+				key.seeds[0] = s;
+				key.rid = rid; key.is_alt = !!idx->bns->anns[rid].is_alt;
+				kb_putp(chn, tree, &key);
+			}
+		}
+		kv_init(chain);
+		kv_resize(mem_chain_t, chain, kb_size(tree) + 1);
+#define katchain_take(p_) (chain.a[chain.n++] = *(p_))
+		__kb_traverse(mem_chain_t, tree, katchain_take);
+#undef katchain_take
+		for (i = 0; i < chain.n; ++i) chain.a[i].frac_rep = (float)l_rep / len;
+		kb_destroy(chn, tree);
+		rec_write(out, TAG_READ, 2, rd[0]);
+		dump_chains(out, TAG_CHAIN, chain.n, chain.a);
+		chain.n = mem_chain_flt(opt, chain.n, chain.a);
+		dump_chains(out, TAG_CHAIN_FLT, chain.n, chain.a);
+		for (i = 0; i < chain.n; ++i) free(chain.a[i].seeds);
+		free(chain.a);
+	}
+	for (k = 0; k < 3; ++k) free(rd[k]);
+	fclose(in); fclose(out);
+	bwa_idx_destroy(idx);
+	free(opt);
+	if (rc) fprintf(stderr, "[bwaref] katchain: malformed case file\n");
+	return rc;
+}
+
 /* readfq <chunk_bases> <in1> [in2]: the batches the reference's bseq_read (bwa.c:191) cuts, one record per line as
  * name TAB comment-or-* TAB seq TAB qual-or-*, a line "#batch <n>" in front of every batch -- golden vectors for the product's
  * FASTA/FASTQ reader (csrc/fastq_reader.cpp) */
@@ -527,6 +617,7 @@ int main(int argc, char **argv)
 	if (strcmp(argv[1], "katksw") == 0) return main_katksw(argc - 1, argv + 1);
 	if (strcmp(argv[1], "katalign") == 0) return main_katalign(argc - 1, argv + 1);
 	if (strcmp(argv[1], "katdp") == 0) return main_katdp(argc - 1, argv + 1);
+	if (strcmp(argv[1], "katchain") == 0) return main_katchain(argc - 1, argv + 1);
 	if (strcmp(argv[1], "readfq") == 0) return main_readfq(argc - 1, argv + 1);
 	fprintf(stderr, "unknown sub-command '%s'\n", argv[1]);
 	return 1;

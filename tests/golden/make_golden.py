@@ -15,6 +15,7 @@ the outputs below are data (inputs + expected outputs), never reference source.
   tests/golden/opt_<set>.sam.gz    SAM bodies of se.fq / pe_[12].fq under non-default options (common.GOLDEN_OPTION_SETS)
   tests/golden/pelib_<name>_[12].fq.gz, pelib_<name>.sam.gz   the paired-end libraries of tests/pe_cases.py at pe_cases.GOLDEN_PAIRS pairs over the
                                    suite's 1 Mb genome (simgen seed 11), and the reference's SAM for them (`make_golden.py pelibs`)
+  tests/golden/kat_chain.npz       the reference's chains and filtered chains for the seed lists of tests/chain_cases.py (`make_golden.py chain`)
 
 `make_golden.py extras` writes only the last two groups (round 2 additions); the older files are left alone.
 """
@@ -194,5 +195,37 @@ def pe_libraries():
     sh("ls", "-la", HERE)
 
 
+def chain_kat():
+    """kat_chain.npz: the core sets of tests/chain_cases.py (every set but the two floods) through `bwaref katchain` (oracle/ref_driver.c: the
+    reference's kbtree instantiation, test_and_merge and mem_chain_flt on the given seeds), over the suite's 1 Mb genome with ctg3 declared
+    ALT.  Per set: <set>.inputs, the sha256 of the generated case file (a changed generator is caught before anything is compared);
+    <set>.sha [cases x 2], the sha256 of each case's two records (chains before the filter with w / kept / first zeroed; filtered chains);
+    <set>.words / <set>.off, the two records themselves for the cases of at most 64 seeds.  Results only, no inputs."""
+    import chain_cases as cc
+    assert os.path.exists("/root/reference/bwamem.c") and os.access(REF, os.X_OK), "needs the reference build (make -C oracle ref)"
+    os.makedirs(TMP, exist_ok=True)
+    fa = f"{TMP}/g1.fa"
+    bw.make_genome(fa, 11, [600000, 300000, 100000], repeats=True)
+    bw.make_index(fa, f"{TMP}/g1")
+    for e in ("amb", "ann", "bwt", "pac", "sa", "alt"):
+        if os.path.lexists(f"{TMP}/alt.{e}"):
+            os.remove(f"{TMP}/alt.{e}")
+    alt = cc.alt_index({"prefix": f"{TMP}/g1"}, TMP)
+    out = {}
+    for name, (flags, _, _, core) in cc.SETS.items():
+        if not core:
+            continue
+        cases = cc.cases_of(name)
+        reads, _ = cc.run_checker(REF, alt, cases, flags, TMP, "golden")
+        m = cc.masked(reads)
+        small = [np.concatenate([m[i][bw.STAGE_CHAIN], m[i][bw.STAGE_CHAIN_FLT]]) for i, c in enumerate(cases) if len(c.seeds) <= 64]
+        out[f"{name}.inputs"] = np.array(cc.input_digest(cases))
+        out[f"{name}.sha"] = cc.digests(reads)
+        out[f"{name}.words"] = np.concatenate(small) if small else np.zeros(0, np.int64)
+        out[f"{name}.off"] = np.cumsum([0] + [len(x) for x in small]).astype(np.int64)
+    np.savez_compressed(f"{HERE}/kat_chain.npz", **out)
+    print("kat_chain.npz:", os.path.getsize(f"{HERE}/kat_chain.npz"), "bytes")
+
+
 if __name__ == "__main__":
-    {"extras": extras, "fastq": fastq_cases, "dpwide": dp_wide, "pelibs": pe_libraries}.get(sys.argv[1] if len(sys.argv) > 1 else "", main)()
+    {"extras": extras, "fastq": fastq_cases, "dpwide": dp_wide, "pelibs": pe_libraries, "chain": chain_kat}.get(sys.argv[1] if len(sys.argv) > 1 else "", main)()

@@ -17,7 +17,8 @@ def ctx(small_index):
 
 
 # the shipped defaults (csrc/ctx_internal.h: Knobs); heavy_mult -1 = 10 x length for reads up to 200 bases, 30 x above
-KNOB_DEFAULTS = dict(intv_cap=96, smem_lanes=1, heavy_mult=-1, chain_big_min=512, rank_sort_min=2, spec_min_chains=16, ext_lds_window=1 << 30)
+KNOB_DEFAULTS = dict(intv_cap=96, smem_lanes=1, heavy_mult=-1, chain_big_min=512, chain_mid_max=1536, chain_big_max=3200, chain_glb_grid=2048,
+                     rank_sort_min=2, spec_min_chains=16, ext_lds_window=1 << 30)
 
 
 @pytest.fixture
