@@ -134,6 +134,7 @@ CHAIN_FLT_NONE, CHAIN_FLT_SEQ, CHAIN_FLT_WAVE = 0, 1, 2
 # known-answer DP entries (bwahip.h): forms of bwahip_kat_ksw_global, CIGAR words per item, path bits of bwahip_kat_ksw_extend2
 KAT_GLOBAL_AUTO_SMALL, KAT_GLOBAL_AUTO_BIG, KAT_GLOBAL_SCORE_ONLY = 0, 1, 2
 KAT_MAX_CIGAR = 512
+KAT_MARK_TAG, KAT_MARK_WORDS = 41, 25                       # bwahip_kat_mark's record: 4 header words, then 25 per region
 KAT_EXT_ROWS1, KAT_EXT_ROWS2, KAT_EXT_ROWS3, KAT_EXT_ROWS4, KAT_EXT_SHORT, KAT_EXT_WIDE, KAT_EXT_BEYOND16, KAT_EXT_STOPPED = 1, 2, 4, 8, 16, 32, 64, 128
 
 
@@ -280,6 +281,7 @@ def lib():
     L.bwahip_kat_introsort.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp]
     L.bwahip_kat_mate_insert.argtypes = [vp, C.POINTER(Opt), C.c_int, vp, vp, vp, vp, vp, C.c_int, C.c_int, vp, vp, vp]
     L.bwahip_kat_chain.argtypes = [vp, C.POINTER(Opt), C.c_int, vp, vp, vp, vp, vp, C.POINTER(i64p), i64p, vp]
+    L.bwahip_kat_mark.argtypes = [vp, C.POINTER(Opt), C.c_int64, C.c_int, vp, vp, C.c_int, vp, C.c_int, C.POINTER(i64p), i64p]
     L.bwahip_kat_occ4.argtypes = [vp, C.c_int, vp, vp]
     L.bwahip_index_footprint.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_uint64)]
     L.bwahip_kat_sa.argtypes = [vp, C.c_int, vp, vp]
@@ -761,6 +763,25 @@ class Context:
         words = np.ctypeslib.as_array(out, shape=(m.value,)).copy() if m.value else np.zeros(0, dtype=np.int64)
         C.CDLL(None).free(out)
         return parse_records(words), diag
+
+    def kat_mark(self, reg_off, regs, opt=None, n_processed=0, plan=1, pairs=None):
+        """bwahip_kat_mark: primary marking, -5, the selection and mapQ on caller region lists -- regs [m x 19] in the layout of STAGE_REGS,
+        by offsets per read; plan 1 / 0: k_mark as the single-end / the paired-end path launches it; pairs: the pair indices the second of
+        the paired-end path's two launches takes.  -> records: per read TAG_READ [i, n] and KAT_MARK_TAG [n, n_pri, tasks, records, then
+        KAT_MARK_WORDS per region: the 19 words as marked, hash, input index, need, XA owner, mapQ, bad]."""
+        opt = opt or default_opt()
+        reg_off = np.ascontiguousarray(reg_off, dtype=np.int64)
+        regs = np.ascontiguousarray(regs, dtype=np.int64).reshape(-1, 19)
+        n = len(reg_off) - 1
+        assert n >= 0 and (n == 0 or len(regs) >= reg_off[-1])
+        n_pairs = 0 if pairs is None else len(pairs)
+        pl = None if pairs is None else np.ascontiguousarray(list(pairs) + [0], dtype=np.int32)      # (never an empty array: its pointer says "a list was given")
+        out, m = C.POINTER(C.c_int64)(), C.c_int64()
+        _check(lib().bwahip_kat_mark(self._h, C.byref(opt), n_processed, n, reg_off.ctypes.data, regs.ctypes.data, plan,
+                                     None if pl is None else pl.ctypes.data, n_pairs, C.byref(out), C.byref(m)), "bwahip_kat_mark")
+        words = np.ctypeslib.as_array(out, shape=(m.value,)).copy() if m.value else np.zeros(0, dtype=np.int64)
+        C.CDLL(None).free(out)
+        return parse_records(words)
 
     def run_pe_stages(self, codes, off, stages, opt=None, n_processed=0, pes0=None):
         """bwahip_run_pe_stages: reads 2i, 2i+1 are a pair; -> records (STAGE_PESTAT first, then per read TAG_READ and the stages asked for)."""

@@ -258,6 +258,7 @@ struct FinLaunch {
 	int *err;
 };
 int launch_mark_primary(const FinLaunch &a, bool plan, int n_listed, hipStream_t st);   // subset 2: n_listed pairs of resc_pairs
+int launch_kat_mapq(const FinLaunch &a, int64_t n_slots, int *out2, hipStream_t st);   // bwahip_kat_mark: fin::approx_mapq_se of fregs[0 .. n_slots) -> (mapQ, bad) per slot
 int launch_task_fill(const FinLaunch &a, hipStream_t st);
 int launch_cigar(const FinLaunch &a, int n_fast, int n_dp, int max_len, hipStream_t st, hipStream_t st2, hipEvent_t fork, hipEvent_t join);
 int launch_cigar_big(const FinLaunch &a, int grid, hipStream_t st);   // the tasks k_cigar listed in redo_list; big_z: grid slabs of cigar_big_slab_bytes()

@@ -184,6 +184,27 @@ static int run_pe_rescue(bwahip_ctx *c, const bwahip_opt_t *opt, const DevOpt &d
 	return 0;
 }
 
+// What k_mark works in and reads, for n reads over c->total_regs region slots: the marked regions and their spare copy, the 16 bytes of scratch
+// per slot, the selection, the per-read counts; the launch record with the options, the read id base, the log table and the region lists
+// (pe_lists: the ones mate rescue left in d_pe_*, otherwise k_extend's).  run_final and bwahip_kat_mark both come through here, so that the
+// known-answer entry launches on the product's own layout; everything else of `f` is zero when this returns.
+static int mark_prepare(bwahip_ctx *c, const bwahip_opt_t *opt, int n, int64_t n_processed, bool pe_lists, FinLaunch &f)
+{
+	int rc;
+	const size_t R = (size_t)(c->total_regs ? c->total_regs : 1);
+	if ((rc = c->d_fregs.ensure(R * sizeof(FinReg))) || (rc = c->d_fregs2.ensure(R * sizeof(FinReg))) || (rc = c->d_fscr.ensure(R * 16)) || (rc = c->d_need.ensure(R)) ||
+	    (rc = c->d_xa_owner.ensure(R * 4)) || (rc = c->d_freg_n.ensure((size_t)n * 4)) || (rc = c->d_npri.ensure((size_t)n * 4)) || (rc = c->d_task_n.ensure((size_t)n * 4)) ||
+	    (rc = c->d_rec_n.ensure((size_t)n * 4))) return rc;
+	memset(&f, 0, sizeof f);
+	f.ix = c->ix; f.opt = make_dev_opt(opt); f.n_reads = n;
+	f.n_processed = n_processed; f.logtab = c->d_logtab.as<double>();
+	f.regs = c->d_regs.as<DevReg>(); f.reg_base = c->d_reg_base.as<int64_t>(); f.reg_n = c->d_reg_n.as<int>();
+	if (pe_lists) { f.regs = c->d_pe_regs.as<DevReg>(); f.reg_base = c->d_pe_base.as<int64_t>(); f.reg_n = c->d_pe_n.as<int>(); }
+	f.fregs = c->d_fregs.as<FinReg>(); f.fregs2 = c->d_fregs2.as<FinReg>(); f.freg_n = c->d_freg_n.as<int>(); f.n_pri = c->d_npri.as<int>(); f.scr = c->d_fscr.as<int>();
+	f.need = c->d_need.as<uint8_t>(); f.xa_owner = c->d_xa_owner.as<int>(); f.task_n = c->d_task_n.as<int>(); f.rec_n = c->d_rec_n.as<int>();
+	return 0;
+}
+
 // K6 -> K9 over the batch run_pipeline left in HBM.  The text inputs (d_qual, d_names, ...) must be uploaded.
 int run_final(bwahip_ctx *c, const bwahip_opt_t *opt, int64_t n_processed, const bwahip_pestat_t *pes0, bool timed, OutForm form, bool host_sam_off, bool pe_stage_stop)
 {
@@ -207,10 +228,10 @@ int run_final(bwahip_ctx *c, const bwahip_opt_t *opt, int64_t n_processed, const
 	const DevOpt dopt_pe = make_dev_opt(opt);
 	int n_resc = 0;
 	if (pe && (rc = run_pe_rescue(c, opt, dopt_pe, n_processed, pes0, pl, n_resc))) return rc;
+	FinLaunch f;
+	if ((rc = mark_prepare(c, opt, n, n_processed, pe, f))) return rc;
 	const size_t R = (size_t)(c->total_regs ? c->total_regs : 1);
-	if ((rc = c->d_fregs.ensure(R * sizeof(FinReg))) || (rc = c->d_fregs2.ensure(R * sizeof(FinReg))) || (rc = c->d_fscr.ensure(R * 16)) || (rc = c->d_need.ensure(R)) ||
-	    (rc = c->d_xa_owner.ensure(R * 4)) || (rc = c->d_aln_of_reg.ensure(R * 4)) || (rc = c->d_rec_list.ensure(R * 8)) || (rc = c->d_xa_list.ensure(R * 8)) ||
-	    (rc = c->d_freg_n.ensure((size_t)n * 4)) || (rc = c->d_npri.ensure((size_t)n * 4)) || (rc = c->d_task_n.ensure((size_t)n * 4)) || (rc = c->d_rec_n.ensure((size_t)n * 4)) ||
+	if ((rc = c->d_aln_of_reg.ensure(R * 4)) || (rc = c->d_rec_list.ensure(R * 8)) || (rc = c->d_xa_list.ensure(R * 8)) ||
 	    (rc = c->d_task_base.ensure((size_t)(n + 1) * 8)) || (rc = c->d_sam_len.ensure((size_t)n * 4)) || (rc = o.d_sam_off.ensure((size_t)(n + 1) * 8))) return rc;
 	// rg id
 	{
@@ -218,14 +239,7 @@ int run_final(bwahip_ctx *c, const bwahip_opt_t *opt, int64_t n_processed, const
 		rg.resize(rg.size() + 64, 0);
 		if ((rc = dev_upload(c->d_rg, rg.data(), rg.size(), c->stream))) return rc;
 	}
-	FinLaunch f;
-	memset(&f, 0, sizeof f);
-	f.ix = c->ix; f.opt = make_dev_opt(opt); f.n_reads = n; f.seq = c->in->d_seq.as<uint8_t>(); f.off = c->in->d_off.as<int64_t>();
-	f.n_processed = n_processed; f.logtab = c->d_logtab.as<double>();
-	f.regs = c->d_regs.as<DevReg>(); f.reg_base = c->d_reg_base.as<int64_t>(); f.reg_n = c->d_reg_n.as<int>();
-	if (pe) { f.regs = c->d_pe_regs.as<DevReg>(); f.reg_base = c->d_pe_base.as<int64_t>(); f.reg_n = c->d_pe_n.as<int>(); }
-	f.fregs = c->d_fregs.as<FinReg>(); f.fregs2 = c->d_fregs2.as<FinReg>(); f.freg_n = c->d_freg_n.as<int>(); f.n_pri = c->d_npri.as<int>(); f.scr = c->d_fscr.as<int>();
-	f.need = c->d_need.as<uint8_t>(); f.xa_owner = c->d_xa_owner.as<int>(); f.task_n = c->d_task_n.as<int>(); f.rec_n = c->d_rec_n.as<int>();
+	f.seq = c->in->d_seq.as<uint8_t>(); f.off = c->in->d_off.as<int64_t>();
 	f.task_base = c->d_task_base.as<int64_t>(); f.aln_of_reg = c->d_aln_of_reg.as<int>();
 	f.rec_list = c->d_rec_list.as<const DevAln*>(); f.xa_list = c->d_xa_list.as<const DevAln*>();
 	unsigned long long *pool_head = c->d_fmisc.as<unsigned long long>();
@@ -786,6 +800,116 @@ extern "C" int bwahip_run_pe_stages(bwahip_ctx *c, const bwahip_opt_t *opt_in, i
 	*out = (int64_t*)malloc(o.size() * 8 + 8);
 	if (!*out) return BWAHIP_ENOMEM;
 	memcpy(*out, o.data(), o.size() * 8);
+	return 0;
+}
+
+// Primary marking, -5, the selection and mapQ (k_mark, fin::select_records, fin::approx_mapq_se) on caller region lists; see bwahip.h.  The
+// buffers and the launch record are run_final's (mark_prepare), the launches are launch_mark_primary as run_final calls it -- one launch, or
+// with `pairs` the two of the paired-end path -- and only the region lists come from the caller.
+extern "C" int bwahip_kat_mark(bwahip_ctx *c, const bwahip_opt_t *opt, int64_t n_processed, int n_reads, const int64_t *reg_off, const int64_t *reg_words,
+                               int plan, const int32_t *pairs, int n_pairs, int64_t **out, int64_t *out_len)
+{
+	if (!c || !opt || n_reads < 0 || !out || !out_len || (plan != 0 && plan != 1) || n_pairs < 0 || n_processed < 0) return BWAHIP_EINVAL;
+	*out = nullptr; *out_len = 0;
+	if (n_reads == 0) return 0;
+	const int n = n_reads;
+	if (!reg_off || reg_off[0] != 0) return BWAHIP_EINVAL;
+	if (((opt->flag & BWAHIP_F_PE) || pairs) && (n & 1)) return BWAHIP_EINVAL;
+	for (int i = 0; i < n; ++i) if (reg_off[i + 1] < reg_off[i] || reg_off[i + 1] - reg_off[i] > (1 << 24)) return BWAHIP_EINVAL;
+	const int64_t total = reg_off[n];
+	if (total > (1 << 26) || (total && !reg_words) || (n_pairs && !pairs)) return BWAHIP_EINVAL;
+	std::vector<DevReg> regs((size_t)total + 1);
+	std::vector<int> regn(n);
+	for (int i = 0; i < n; ++i) regn[i] = (int)(reg_off[i + 1] - reg_off[i]);
+	for (int64_t k = 0; k < total; ++k) {
+		const int64_t *w = reg_words + 19 * k;
+		if (w[3] < w[2] || w[1] < w[0] || w[4] < 0 || w[4] >= c->ix.n_seqs) return BWAHIP_EINVAL;
+		DevReg r; memset(&r, 0, sizeof r);
+		r.rb = w[0]; r.re = w[1]; r.qb = (int)w[2]; r.qe = (int)w[3]; r.rid = (int)w[4]; r.score = (int)w[5]; r.truesc = (int)w[6]; r.sub = (int)w[7]; r.csub = (int)w[9];
+		r.sub_n = (int)w[10]; r.w = (int)w[11]; r.seedcov = (int)w[12]; r.seedlen0 = (int)w[15]; r.n_comp = (int)w[16]; r.is_alt = (int)w[17];
+		const uint32_t u = (uint32_t)w[18]; memcpy(&r.frac_rep, &u, 4);
+		regs[(size_t)k] = r;
+	}
+	std::vector<uint8_t> flag((size_t)(n / 2 + 4), 0);
+	std::vector<int> list(pairs ? (size_t)n_pairs + 1 : 1, 0);
+	for (int k = 0; pairs && k < n_pairs; ++k) {
+		if (pairs[k] < 0 || pairs[k] >= n / 2 || flag[pairs[k]]) return BWAHIP_EINVAL;    // (a pair named twice would be marked by two workgroups at once)
+		flag[pairs[k]] = 1; list[k] = pairs[k];
+	}
+	HIP_TRY(hipSetDevice(c->device));
+	const size_t R = (size_t)(total ? total : 1);
+	std::vector<FinReg> h_f(R);
+	std::vector<uint8_t> h_need(R);
+	std::vector<int> h_own(R), h_mq(2 * R), h_fn(n), h_np(n), h_tn(n), h_rn(n);
+	DevBuf d_mq;
+	FinLaunch f;
+	int rc;
+	const int sel0 = plan ? 0xff : 0;
+	c->total_regs = total;
+	if ((rc = dev_upload(c->d_regs, regs.data(), regs.size() * sizeof(DevReg), c->stream)) || (rc = dev_upload(c->d_reg_base, reg_off, (size_t)(n + 1) * 8, c->stream)) ||
+	    (rc = dev_upload(c->d_reg_n, regn.data(), (size_t)n * 4, c->stream)) || (rc = d_mq.ensure(R * 8)) || (rc = mark_prepare(c, opt, n, n_processed, false, f))) goto done;
+	// what k_mark<false> leaves alone comes back as zero; what a launch must write starts as 0xff, so that nothing a call before this one
+	// left in the context's buffers can pass for an answer
+	if (hipMemsetAsync(c->d_fregs.p, 0xff, R * sizeof(FinReg), c->stream) != hipSuccess || hipMemsetAsync(c->d_freg_n.p, 0xff, (size_t)n * 4, c->stream) != hipSuccess ||
+	    hipMemsetAsync(c->d_npri.p, 0xff, (size_t)n * 4, c->stream) != hipSuccess ||
+	    hipMemsetAsync(c->d_need.p, sel0, R, c->stream) != hipSuccess || hipMemsetAsync(c->d_xa_owner.p, sel0, R * 4, c->stream) != hipSuccess ||
+	    hipMemsetAsync(c->d_task_n.p, sel0, (size_t)n * 4, c->stream) != hipSuccess || hipMemsetAsync(c->d_rec_n.p, sel0, (size_t)n * 4, c->stream) != hipSuccess) { rc = BWAHIP_ENODEV; goto done; }
+	if (pairs) {                                                 // as run_final does for a paired-end batch: all pairs but the listed ones, then the listed ones
+		if ((rc = dev_upload(c->d_resc, list.data(), list.size() * 4, c->stream)) || (rc = dev_upload(c->d_resc_flag, flag.data(), flag.size(), c->stream))) goto done;
+		f.resc_flag = c->d_resc_flag.as<uint8_t>(); f.resc_pairs = c->d_resc.as<int>(); f.subset = 1;
+		if ((rc = launch_mark_primary(f, plan != 0, 0, c->stream))) goto done;
+		if (n_pairs > 0) {
+			f.subset = 2;
+			if ((rc = launch_mark_primary(f, plan != 0, n_pairs, c->stream))) goto done;
+		}
+		f.subset = 0;
+	} else if ((rc = launch_mark_primary(f, plan != 0, 0, c->stream))) goto done;
+	if ((rc = launch_kat_mapq(f, total, d_mq.as<int>(), c->stream))) goto done;
+	if ((total && (hipMemcpyAsync(h_f.data(), c->d_fregs.p, (size_t)total * sizeof(FinReg), hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+	               hipMemcpyAsync(h_need.data(), c->d_need.p, (size_t)total, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+	               hipMemcpyAsync(h_own.data(), c->d_xa_owner.p, (size_t)total * 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+	               hipMemcpyAsync(h_mq.data(), d_mq.p, (size_t)total * 8, hipMemcpyDeviceToHost, c->stream) != hipSuccess)) ||
+	    hipMemcpyAsync(h_fn.data(), c->d_freg_n.p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+	    hipMemcpyAsync(h_np.data(), c->d_npri.p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+	    hipMemcpyAsync(h_tn.data(), c->d_task_n.p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+	    hipMemcpyAsync(h_rn.data(), c->d_rec_n.p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess) rc = BWAHIP_ENODEV;
+done:
+	if (hipStreamSynchronize(c->stream) != hipSuccess && !rc) rc = BWAHIP_ENODEV;
+	d_mq.release();
+	if (rc) return rc;
+	auto hash_64 = [](uint64_t key) {                             // utils.h:97
+		key += ~(key << 32); key ^= (key >> 22); key += ~(key << 13); key ^= (key >> 8);
+		key += (key << 3); key ^= (key >> 15); key += ~(key << 27); key ^= (key >> 31);
+		return key;
+	};
+	std::vector<int64_t> o, v;
+	std::vector<std::pair<uint64_t, int>> by_hash;
+	for (int i = 0; i < n; ++i) {
+		const int m = regn[i];
+		if (h_fn[i] != m) return BWAHIP_EINTERNAL;
+		const uint64_t id = (opt->flag & BWAHIP_F_PE) ? ((((uint64_t)n_processed >> 1) + (uint64_t)(i >> 1)) << 1 | (uint64_t)(i & 1)) : (uint64_t)n_processed + (uint64_t)i;
+		by_hash.clear();
+		for (int k = 0; k < m; ++k) by_hash.emplace_back(hash_64(id + (uint64_t)k), k);
+		std::sort(by_hash.begin(), by_hash.end());
+		v = { (int64_t)i, (int64_t)m };
+		stage_rec(o, 100, v);
+		v = { (int64_t)m, (int64_t)h_np[i], (int64_t)h_tn[i], (int64_t)h_rn[i] };
+		for (int k = 0; k < m; ++k) {
+			const size_t s = (size_t)reg_off[i] + k;
+			const FinReg &p = h_f[s];
+			uint32_t u; memcpy(&u, &p.frac_rep, 4);
+			const auto it = std::lower_bound(by_hash.begin(), by_hash.end(), std::make_pair(p.hash, 0));
+			const int64_t w[BWAHIP_KAT_MARK_WORDS] = { p.rb, p.re, p.qb, p.qe, p.rid, p.score, p.truesc, p.sub, p.alt_sc, p.csub, p.sub_n, p.w, p.seedcov, p.secondary, p.secondary_all,
+			                                           p.seedlen0, p.n_comp, p.is_alt, (int64_t)u, (int64_t)p.hash, it != by_hash.end() && it->first == p.hash ? it->second : -1,
+			                                           h_need[s], h_own[s], h_mq[2 * s], h_mq[2 * s + 1] };
+			v.insert(v.end(), w, w + BWAHIP_KAT_MARK_WORDS);
+		}
+		stage_rec(o, BWAHIP_KAT_MARK_TAG, v);
+	}
+	*out = (int64_t*)malloc(o.size() * 8 + 8);
+	if (!*out) return BWAHIP_ENOMEM;
+	memcpy(*out, o.data(), o.size() * 8);
+	*out_len = (int64_t)o.size();
 	return 0;
 }
 

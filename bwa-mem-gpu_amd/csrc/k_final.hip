@@ -253,6 +253,17 @@ __global__ __launch_bounds__(64) void k_mark(FinLaunch a)
 	}
 }
 
+// known-answer kernel (bwahip_kat_mark): mem_approx_mapq_se of every marked region, one lane per region slot -- the function reg2aln calls
+// for the regions it aligns, with the same log table; a region it cannot answer for comes back with bad = 1
+__global__ __launch_bounds__(256) void k_kat_mapq(FinLaunch a, int64_t n_slots, int *out2)
+{
+	const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+	if (t >= n_slots) return;
+	int bad = 0;
+	const int mapq = approx_mapq_se(a.opt, a.logtab, a.fregs[t], &bad);
+	out2[2 * t] = mapq; out2[2 * t + 1] = bad;
+}
+
 __device__ __forceinline__ int infer_bw(int l1, int l2, int score, int a, int q, int r)   // bwamem.c:799
 {
 	if (l1 == l2 && l1 * a - score < (q + r - a) << 1) return 0;
@@ -897,6 +908,13 @@ int launch_mark_primary(const FinLaunch &a, bool plan, int n_listed, hipStream_t
 	if (grid <= 0) return 0;
 	if (plan) hipLaunchKernelGGL(k_mark<true>, dim3(grid), dim3(64), 0, st, a);
 	else hipLaunchKernelGGL(k_mark<false>, dim3(grid), dim3(64), 0, st, a);
+	return hipGetLastError() == hipSuccess ? 0 : BWAHIP_ENODEV;
+}
+
+int launch_kat_mapq(const FinLaunch &a, int64_t n_slots, int *out2, hipStream_t st)
+{
+	if (n_slots <= 0) return 0;
+	hipLaunchKernelGGL(k_kat_mapq, dim3((unsigned)((n_slots + 255) / 256)), dim3(256), 0, st, a, n_slots, out2);
 	return hipGetLastError() == hipSuccess ? 0 : BWAHIP_ENODEV;
 }
 

@@ -813,6 +813,28 @@ int bwahip_kat_mate_insert(bwahip_ctx *ctx, const bwahip_opt_t *opt, int n_items
 int bwahip_kat_chain(bwahip_ctx *ctx, const bwahip_opt_t *opt, int n_reads, const int32_t *read_len, const int64_t *seed_off, const int64_t *seeds4,
                      const int64_t *intv_off, const int64_t *intv3, int64_t **out, int64_t *out_len, int32_t *diag);
 
+/* The stage between the region list and the output (mem_mark_primary_se bwamem.c:528, mem_reorder_primary5 bwamem.c:988 under
+ * BWAHIP_F_PRIMARY5, the record filter of mem_reg2sam bwamem.c:1025-1031, the XA membership of mem_gen_alt bwamem_extra.c:131-145,
+ * mem_approx_mapq_se bwamem.c:962) through k_mark of csrc/k_final.hip, on caller region lists: the finalisation's own buffers, sizes and
+ * launch, only the lists come from the caller.  Read i of the batch (its id for the tie-breaking hash follows from n_processed, i and
+ * BWAHIP_F_PE as in mem_process_seqs) has the regions reg_words[19 * reg_off[i] .. 19 * reg_off[i + 1]), 19 words per region in the
+ * layout of BWAHIP_STAGE_REGS (sub, alt_sc, secondary, secondary_all are not read).  plan 1: k_mark as the single-end path launches it,
+ * with the selection; 0: as the paired-end path does, without.  pairs (may be NULL): n_pairs distinct pair indices (reads 2p, 2p + 1);
+ * the batch is then marked by the two launches of the paired-end path -- every pair but the listed ones, then the listed ones -- instead
+ * of one.
+ * *out: a malloc()ed stream of i64 records, per read [100: i, n] and [BWAHIP_KAT_MARK_TAG: n, n_pri, regions with an alignment task,
+ * regions with a record, then BWAHIP_KAT_MARK_WORDS words per region in the final order: the 19 words of a stage record with sub,
+ * alt_sc, secondary, secondary_all as marked; hash; the index the region had in the input list; need (1: prints a record, 2: listed in
+ * an XA tag); the region whose XA tag lists it, or -1; mem_approx_mapq_se of the region (of every region, secondary or not); 1 where
+ * that needs a logarithm beyond the table (a span, sub_n + 1 or seedcov of 65536 and more: the output path reports an error), mapQ 0
+ * then].  With plan 0 need, the XA region and the two counts are 0.
+ * BWAHIP_EINVAL: offsets that do not start at 0 or descend, qe < qb, re < rb, a contig that does not exist, an odd n_reads with
+ * BWAHIP_F_PE or with pairs, a pair index out of range or given twice.  n_reads == 0 launches nothing. */
+#define BWAHIP_KAT_MARK_TAG   41
+#define BWAHIP_KAT_MARK_WORDS 25
+int bwahip_kat_mark(bwahip_ctx *ctx, const bwahip_opt_t *opt, int64_t n_processed, int n_reads, const int64_t *reg_off, const int64_t *reg_words,
+                    int plan, const int32_t *pairs, int n_pairs, int64_t **out, int64_t *out_len);
+
 /* The stable LSD radix sort of the coordinate-sorted BAM output (csrc/k_bamsort.hip) on caller keys: exactly the product's passes for
  * keys of key_bits (1..64) significant bits -- 8 bits per pass, passes in which all keys agree skipped.  idx_out[i] = input position of
  * the i-th key in sorted order, equal keys in input order; *tile_out (may be NULL): items one workgroup ranks per pass.  n <= 1 launches

@@ -4,6 +4,7 @@
  *   bwa_oracle stages <prefix> <reads.fq> <out.bin>                          per-read stage dump
  *   bwa_oracle stages [options, -I] <prefix> <r1.fq> <r2.fq> <out.bin>       paired-end stage dump (one batch)
  *   bwa_oracle katchain [options] <prefix> <cases.bin> <out.bin>             chains of caller-supplied seed lists
+ *   bwa_oracle katmark [options] <prefix> <cases.bin> <out.bin>              primary marking, selection and mapQ of caller-supplied region lists
  * Batching follows bseq_read (bwa.c:191): reads are taken until the batch holds
  * >= chunk bases and an even number of reads.
  */
@@ -21,6 +22,7 @@ static double now_s(void) { struct timeval tv; gettimeofday(&tv, 0); return tv.t
 #define OPT_FILL_SCMAT(a, b, mat) ora_fill_scmat((a), (b), (mat))
 #define OPT_LOG(x) log(x)
 #include "opt_parse.h"
+#include "kat_mark_io.h"
 
 /* ---- minimal FASTA/FASTQ reader with kseq.h's field semantics ---- */
 typedef struct { gzFile fp; char *line; size_t m; int peeked; } fq_t;
@@ -272,6 +274,37 @@ static int main_katchain(int argc, char **argv)
 	return rc;
 }
 
+/* katmark [options] <prefix> <cases.bin> <out.bin>: ora_kat_mark on caller region lists (kat_mark_io.h has both file formats).  The index
+ * is not read: <prefix> is there so that the command line is the one of the other sub-commands. */
+static int main_katmark(int argc, char **argv)
+{
+	ora_opt_t opt;
+	optparse_t op;
+	km_file_t k;
+	FILE *in, *out;
+	const int64_t *regs;
+	int64_t i, *rec = 0;
+	int c, n, rc;
+	ora_opt_init(&opt);
+	optparse_init(&op, &opt);
+	while ((c = getopt(argc, argv, OPT_GETOPT_STRING)) >= 0) if (optparse_one(&op, c, optarg)) return 1;
+	if (optparse_finish(&op) || optind + 3 > argc) return 1;
+	in = fopen(argv[optind + 1], "rb"); out = fopen(argv[optind + 2], "wb");
+	if (!in || !out || km_read_opt(in, &opt, &k)) { fprintf(stderr, "[bwa_oracle] katmark: cannot open the files, or no option record\n"); return 1; }
+	while ((rc = km_next_read(in, &k, &i, &n, &regs)) > 0) {
+		int64_t hdr[2];
+		rec = (int64_t*)realloc(rec, (4 + (size_t)KM_OUT_WORDS * n) * 8);
+		ora_kat_mark(&opt, n, regs, km_read_id(&k, i), rec);
+		hdr[0] = i; hdr[1] = n;
+		rec_write(out, TAG_READ, 2, hdr);
+		rec_write(out, KM_TAG_MARK, 4 + (int64_t)KM_OUT_WORDS * n, rec);
+	}
+	free(rec); free(k.buf);
+	fclose(in); fclose(out);
+	if (rc) fprintf(stderr, "[bwa_oracle] katmark: malformed case file\n");
+	return rc ? 1 : 0;
+}
+
 static int main_mem(int argc, char **argv)
 {
 	ora_opt_t opt;
@@ -318,6 +351,7 @@ int main(int argc, char **argv)
 	if (argc >= 2 && strcmp(argv[1], "mem") == 0) return main_mem(argc - 1, argv + 1);
 	if (argc >= 2 && strcmp(argv[1], "stages") == 0) return main_stages(argc - 1, argv + 1);
 	if (argc >= 2 && strcmp(argv[1], "katchain") == 0) return main_katchain(argc - 1, argv + 1);
-	fprintf(stderr, "usage: bwa_oracle <mem|stages|katchain> ...\n");
+	if (argc >= 2 && strcmp(argv[1], "katmark") == 0) return main_katmark(argc - 1, argv + 1);
+	fprintf(stderr, "usage: bwa_oracle <mem|stages|katchain|katmark> ...\n");
 	return 1;
 }

@@ -66,6 +66,9 @@ void ora_reorder_primary5(int T, ora_reg_v *a);                                 
 ora_aln_t ora_reg2aln(const ora_opt_t *opt, const ora_ref_t *r, int l_query, const char *query, const ora_reg_t *ar); /* bwamem.c:1099 */
 void ora_aln2sam(const ora_opt_t *opt, const ora_ref_t *r, ora_str_t *str, ora_read_t *s, int n, const ora_aln_t *list, int which, const ora_aln_t *m); /* bwamem.c:832 */
 void ora_reg2sam(const ora_opt_t *opt, const ora_ref_t *r, ora_read_t *s, ora_reg_v *a, int extra_flag, const ora_aln_t *m); /* bwamem.c:1013 */
+enum { ORA_NEED_REC = 1, ORA_NEED_XA = 2 };
+void ora_select(const ora_opt_t *opt, int n, const ora_reg_t *a, int want_xa, uint8_t *need, int *owner);   /* the record filter of bwamem.c:1025-1031 and the XA membership of bwamem_extra.c:131-145 */
+void ora_kat_mark(const ora_opt_t *opt, int n, const int64_t *regs19, int64_t id, int64_t *out);       /* test helper: mark primary, -5, selection and mapQ on a caller's region list */
 char **ora_gen_alt(const ora_opt_t *opt, const ora_ref_t *r, const ora_reg_v *a, int l_query, const char *query); /* bwamem_extra.c:124 */
 extern char ora_rg_id[256];                                                                            /* bwa.c:44 */
 

@@ -344,26 +344,56 @@ static inline int pri_idx(double XA_drop_ratio, const ora_reg_t *a, int i)   /* 
 	return -1;
 }
 
+/* The selection on a read's marked regions, in one place for ora_gen_alt, ora_reg2sam and ora_kat_mark: need[i] & ORA_NEED_REC for the
+ * regions mem_reg2sam prints a record for (bwamem.c:1025-1031); with want_xa, need[i] & ORA_NEED_XA and owner[i] = its primary for the
+ * regions mem_gen_alt lists in an XA tag (bwamem_extra.c:131-145), owner[i] = -1 for every other region. */
+void ora_select(const ora_opt_t *opt, int n, const ora_reg_t *a, int want_xa, uint8_t *need, int *owner)
+{
+	int i, r, *cnt;
+	char *has_alt;
+	for (i = 0; i < n; ++i) { need[i] = 0; owner[i] = -1; }
+	if (want_xa) {
+		cnt = (int*)calloc(n > 0 ? n : 1, sizeof(int));
+		has_alt = (char*)calloc(n > 0 ? n : 1, 1);
+		for (i = 0; i < n; ++i) {
+			r = pri_idx(opt->XA_drop_ratio, a, i);
+			if (r >= 0) {
+				++cnt[r];
+				if (a[i].is_alt) has_alt[r] = 1;
+			}
+		}
+		for (i = 0; i < n; ++i) {
+			if ((r = pri_idx(opt->XA_drop_ratio, a, i)) < 0) continue;
+			if (cnt[r] > opt->max_XA_hits_alt || (!has_alt[r] && cnt[r] > opt->max_XA_hits)) continue;
+			need[i] |= ORA_NEED_XA; owner[i] = r;
+		}
+		free(has_alt); free(cnt);
+	}
+	for (i = 0; i < n; ++i) {
+		const ora_reg_t *p = &a[i];
+		if (p->score < opt->T) continue;
+		if (p->secondary >= 0 && (p->is_alt || !(opt->flag & ORA_F_ALL))) continue;
+		if (p->secondary >= 0 && p->secondary < INT_MAX && p->score < a[p->secondary].score * opt->drop_ratio) continue;
+		need[i] |= ORA_NEED_REC;
+	}
+}
+
 char **ora_gen_alt(const ora_opt_t *opt, const ora_ref_t *ref, const ora_reg_v *a, int l_query, const char *query)   /* bwamem_extra.c:124 */
 {
-	int i, k, r, *cnt, tot;
+	int i, k, r, tot, *owner;
 	ora_str_t *aln = 0, str = { 0, 0, 0 };
-	char **XA = 0, *has_alt;
-	cnt = (int*)calloc(a->n ? a->n : 1, sizeof(int));
-	has_alt = (char*)calloc(a->n ? a->n : 1, 1);
-	for (i = 0, tot = 0; i < a->n; ++i) {
-		r = pri_idx(opt->XA_drop_ratio, a->a, i);
-		if (r >= 0) {
-			++cnt[r]; ++tot;
-			if (a->a[i].is_alt) has_alt[r] = 1;
-		}
-	}
+	char **XA = 0;
+	uint8_t *need;
+	need = (uint8_t*)calloc(a->n ? a->n : 1, 1);
+	owner = (int*)calloc(a->n ? a->n : 1, sizeof(int));
+	ora_select(opt, a->n, a->a, 1, need, owner);
+	for (i = 0, tot = 0; i < a->n; ++i) if (pri_idx(opt->XA_drop_ratio, a->a, i) >= 0) ++tot;
 	if (tot == 0) goto end;
 	aln = (ora_str_t*)calloc(a->n, sizeof(ora_str_t));
 	for (i = 0; i < a->n; ++i) {
 		ora_aln_t t;
-		if ((r = pri_idx(opt->XA_drop_ratio, a->a, i)) < 0) continue;
-		if (cnt[r] > opt->max_XA_hits_alt || (!has_alt[r] && cnt[r] > opt->max_XA_hits)) continue;
+		if (!(need[i] & ORA_NEED_XA)) continue;
+		r = owner[i];
 		t = ora_reg2aln(opt, ref, l_query, query, &a->a[i]);
 		str.l = 0;
 		ora_str_puts(&str, ref->anns[t.rid].name);
@@ -379,7 +409,7 @@ char **ora_gen_alt(const ora_opt_t *opt, const ora_ref_t *ref, const ora_reg_v *
 	XA = (char**)calloc(a->n, sizeof(char*));
 	for (k = 0; k < a->n; ++k) XA[k] = aln[k].s;
 end:
-	free(has_alt); free(cnt); free(aln); free(str.s);
+	free(need); free(owner); free(aln); free(str.s);
 	return XA;
 }
 
@@ -389,13 +419,14 @@ void ora_reg2sam(const ora_opt_t *opt, const ora_ref_t *ref, ora_read_t *s, ora_
 	struct { int n, m; ora_aln_t *a; } aa = { 0, 0, 0 };
 	int k, l;
 	char **XA = 0;
+	uint8_t *need = (uint8_t*)calloc(a->n ? a->n : 1, 1);
+	int *owner = (int*)calloc(a->n ? a->n : 1, sizeof(int));
 	if (!(opt->flag & ORA_F_ALL)) XA = ora_gen_alt(opt, ref, a, s->l_seq, s->seq);
+	ora_select(opt, a->n, a->a, 0, need, owner);
 	for (k = l = 0; k < a->n; ++k) {
 		ora_reg_t *p = &a->a[k];
 		ora_aln_t *q;
-		if (p->score < opt->T) continue;
-		if (p->secondary >= 0 && (p->is_alt || !(opt->flag & ORA_F_ALL))) continue;
-		if (p->secondary >= 0 && p->secondary < INT_MAX && p->score < a->a[p->secondary].score * opt->drop_ratio) continue;
+		if (!(need[k] & ORA_NEED_REC)) continue;
 		if (aa.n == aa.m) { aa.m = aa.m ? aa.m << 1 : 2; aa.a = (ora_aln_t*)realloc(aa.a, sizeof(ora_aln_t) * aa.m); }
 		q = &aa.a[aa.n++];
 		*q = ora_reg2aln(opt, ref, s->l_seq, s->seq, p);
@@ -418,4 +449,46 @@ void ora_reg2sam(const ora_opt_t *opt, const ora_ref_t *ref, ora_read_t *s, ora_
 	}
 	s->sam = str.s;
 	if (XA) { for (k = 0; k < a->n; ++k) free(XA[k]); free(XA); }
+	free(need); free(owner);
+}
+
+/* Test helper (`bwa_oracle katmark`): what the finalisation decides about one caller-supplied region list without aligning anything --
+ * ora_mark_primary_se, ora_reorder_primary5 under -5, ora_select, and ora_approx_mapq_se of EVERY region (the function is defined for
+ * any region; the output path asks it of primaries only).  regs19: n regions in the 19-word layout of the stage records.  out: 4 + 25 n
+ * words -- [n, n_pri, regions with a task, regions with a record], then per region in the final order the 19 words, the hash, the index
+ * the region had in regs19 (found through the hash, a bijection of it; -1: a hash no input region owns), need, XA owner, mapQ, 0. */
+void ora_kat_mark(const ora_opt_t *opt, int n, const int64_t *regs19, int64_t id, int64_t *out)
+{
+	ora_reg_v v;
+	uint8_t *need = (uint8_t*)calloc(n ? n : 1, 1);
+	int *owner = (int*)calloc(n ? n : 1, sizeof(int));
+	int i, j, n_pri, n_task = 0, n_rec = 0;
+	v.n = v.m = n; v.a = (ora_reg_t*)calloc(n ? n : 1, sizeof(ora_reg_t));
+	for (i = 0; i < n; ++i) {
+		const int64_t *w = regs19 + 19 * i;
+		ora_reg_t *p = &v.a[i];
+		uint32_t u = (uint32_t)w[18];
+		p->rb = w[0]; p->re = w[1]; p->qb = (int)w[2]; p->qe = (int)w[3]; p->rid = (int)w[4]; p->score = (int)w[5]; p->truesc = (int)w[6];
+		p->sub = (int)w[7]; p->alt_sc = (int)w[8]; p->csub = (int)w[9]; p->sub_n = (int)w[10]; p->w = (int)w[11]; p->seedcov = (int)w[12];
+		p->secondary = (int)w[13]; p->secondary_all = (int)w[14]; p->seedlen0 = (int)w[15]; p->n_comp = (int)w[16]; p->is_alt = (int)w[17];
+		memcpy(&p->frac_rep, &u, 4);
+	}
+	n_pri = ora_mark_primary_se(opt, n, v.a, id);
+	if (opt->flag & ORA_F_PRIMARY5) ora_reorder_primary5(opt->T, &v);
+	ora_select(opt, n, v.a, !(opt->flag & ORA_F_ALL), need, owner);
+	for (i = 0; i < n; ++i) {
+		const ora_reg_t *p = &v.a[i];
+		int64_t *w = out + 4 + 25 * i;
+		uint32_t u;
+		memcpy(&u, &p->frac_rep, 4);
+		w[0] = p->rb; w[1] = p->re; w[2] = p->qb; w[3] = p->qe; w[4] = p->rid; w[5] = p->score; w[6] = p->truesc; w[7] = p->sub; w[8] = p->alt_sc;
+		w[9] = p->csub; w[10] = p->sub_n; w[11] = p->w; w[12] = p->seedcov; w[13] = p->secondary; w[14] = p->secondary_all; w[15] = p->seedlen0;
+		w[16] = p->n_comp; w[17] = p->is_alt; w[18] = u; w[19] = (int64_t)p->hash;
+		for (j = 0; j < n && ora_hash64((uint64_t)id + j) != p->hash; ++j);
+		w[20] = j < n ? j : -1;
+		w[21] = need[i]; w[22] = owner[i]; w[23] = ora_approx_mapq_se(opt, p); w[24] = 0;
+		n_task += need[i] != 0; n_rec += (need[i] & ORA_NEED_REC) != 0;
+	}
+	out[0] = n; out[1] = n_pri; out[2] = n_task; out[3] = n_rec;
+	free(v.a); free(need); free(owner);
 }

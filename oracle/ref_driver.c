@@ -23,6 +23,7 @@
  *   katdp  <out.bin> <n> <seed>                  known answers: ksw_extend2 / ksw_global2 over
  *                                                the whole range of lengths, bands, matrices
  *   katchain [options] <prefix> <cases.bin> <out.bin>   known answers: chains and filtered chains of given seed lists
+ *   katmark [options] <prefix> <cases.bin> <out.bin>    known answers: primary marking and mapQ of given region lists
  *
  * Dump format ("i64 records"): a stream of  [tag:i64][n:i64][n x i64].
  */
@@ -40,6 +41,7 @@ extern int bwa_idx_build(const char *fa, const char *prefix, int algo_type, int 
 #define OPT_FILL_SCMAT(a, b, mat) bwa_fill_scmat((a), (b), (mat))
 #define OPT_LOG(x) log(x)
 #include "opt_parse.h"
+#include "kat_mark_io.h"
 
 /* ---------------------------------------------------------------- records */
 static void rec_write(FILE *fp, int64_t tag, int64_t n, const int64_t *v)
@@ -577,6 +579,65 @@ static int main_katchain(int argc, char **argv)
 	return rc;
 }
 
+/* katmark [options] <prefix> <cases.bin> <out.bin>: the reference's own mem_mark_primary_se, mem_reorder_primary5 (under -5) and
+ * mem_approx_mapq_se -- of every region: the function is defined for any region -- on caller-supplied region lists; kat_mark_io.h has both
+ * file formats.  need, XA owner and the two counts are written as 0: the reference cannot give the selection without real alignments,
+ * because mem_gen_alt and mem_reg2sam call mem_reg2aln as they go (a region here has no bases behind it).  The selection of the known
+ * answers is ora_select, which the SAM goldens pin to the reference through ora_reg2sam / ora_gen_alt.  <prefix> is not read. */
+static int main_katmark(int argc, char **argv)
+{
+	mem_opt_t *opt = mem_opt_init();
+	optparse_t op;
+	km_file_t k;
+	FILE *in, *out;
+	const int64_t *regs;
+	int64_t i, *rec = 0;
+	int c, n, rc, j, t;
+	bwa_verbose = 1;
+	optparse_init(&op, opt);
+	while ((c = getopt(argc, argv, OPT_GETOPT_STRING)) >= 0) if (optparse_one(&op, c, optarg)) return 1;
+	if (optparse_finish(&op) || optind + 3 > argc) return 1;
+	in = fopen(argv[optind + 1], "rb"); out = fopen(argv[optind + 2], "wb");
+	if (!in || !out || km_read_opt(in, opt, &k)) { fprintf(stderr, "[bwaref] katmark: cannot open the files, or no option record\n"); return 1; }
+	while ((rc = km_next_read(in, &k, &i, &n, &regs)) > 0) {
+		mem_alnreg_v v;
+		int64_t hdr[2], id = km_read_id(&k, i);
+		int n_pri;
+		v.n = v.m = n; v.a = calloc(n ? n : 1, sizeof(mem_alnreg_t));
+		for (j = 0; j < n; ++j) {
+			const int64_t *w = regs + KM_REG_WORDS * j;
+			mem_alnreg_t *p = &v.a[j];
+			p->rb = w[0]; p->re = w[1]; p->qb = (int)w[2]; p->qe = (int)w[3]; p->rid = (int)w[4]; p->score = (int)w[5]; p->truesc = (int)w[6];
+			p->sub = (int)w[7]; p->alt_sc = (int)w[8]; p->csub = (int)w[9]; p->sub_n = (int)w[10]; p->w = (int)w[11]; p->seedcov = (int)w[12];
+			p->secondary = (int)w[13]; p->secondary_all = (int)w[14]; p->seedlen0 = (int)w[15]; p->n_comp = (int)w[16]; p->is_alt = (int)w[17];
+			p->frac_rep = km_i2f(w[18]);
+		}
+		n_pri = mem_mark_primary_se(opt, n, v.a, id);
+		if (opt->flag & MEM_F_PRIMARY5) mem_reorder_primary5(opt->T, &v);
+		rec = realloc(rec, (4 + (size_t)KM_OUT_WORDS * n) * 8);
+		rec[0] = n; rec[1] = n_pri; rec[2] = rec[3] = 0;
+		for (j = 0; j < n; ++j) {
+			const mem_alnreg_t *p = &v.a[j];
+			int64_t *w = rec + 4 + KM_OUT_WORDS * j;
+			w[0] = p->rb; w[1] = p->re; w[2] = p->qb; w[3] = p->qe; w[4] = p->rid; w[5] = p->score; w[6] = p->truesc; w[7] = p->sub; w[8] = p->alt_sc;
+			w[9] = p->csub; w[10] = p->sub_n; w[11] = p->w; w[12] = p->seedcov; w[13] = p->secondary; w[14] = p->secondary_all; w[15] = p->seedlen0;
+			w[16] = p->n_comp; w[17] = p->is_alt; w[18] = f2i(p->frac_rep); w[19] = (int64_t)p->hash;
+			for (t = 0; t < n && hash_64((uint64_t)id + t) != p->hash; ++t);
+			w[20] = t < n ? t : -1;
+			w[21] = w[22] = 0; w[23] = mem_approx_mapq_se(opt, p); w[24] = 0;
+		}
+		hdr[0] = i; hdr[1] = n;
+		rec_write(out, TAG_READ, 2, hdr);
+		rec_write(out, KM_TAG_MARK, 4 + (int64_t)KM_OUT_WORDS * n, rec);
+		free(v.a);
+	}
+	free(rec); free(k.buf);
+	fclose(in); fclose(out);
+	free(opt);
+	if (rc) fprintf(stderr, "[bwaref] katmark: malformed case file\n");
+	return rc ? 1 : 0;
+}
+
 /* readfq <chunk_bases> <in1> [in2]: the batches the reference's bseq_read (bwa.c:191) cuts, one record per line as
  * name TAB comment-or-* TAB seq TAB qual-or-*, a line "#batch <n>" in front of every batch -- golden vectors for the product's
  * FASTA/FASTQ reader (csrc/fastq_reader.cpp) */
@@ -618,6 +679,7 @@ int main(int argc, char **argv)
 	if (strcmp(argv[1], "katalign") == 0) return main_katalign(argc - 1, argv + 1);
 	if (strcmp(argv[1], "katdp") == 0) return main_katdp(argc - 1, argv + 1);
 	if (strcmp(argv[1], "katchain") == 0) return main_katchain(argc - 1, argv + 1);
+	if (strcmp(argv[1], "katmark") == 0) return main_katmark(argc - 1, argv + 1);
 	if (strcmp(argv[1], "readfq") == 0) return main_readfq(argc - 1, argv + 1);
 	fprintf(stderr, "unknown sub-command '%s'\n", argv[1]);
 	return 1;

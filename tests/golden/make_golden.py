@@ -16,6 +16,7 @@ the outputs below are data (inputs + expected outputs), never reference source.
   tests/golden/pelib_<name>_[12].fq.gz, pelib_<name>.sam.gz   the paired-end libraries of tests/pe_cases.py at pe_cases.GOLDEN_PAIRS pairs over the
                                    suite's 1 Mb genome (simgen seed 11), and the reference's SAM for them (`make_golden.py pelibs`)
   tests/golden/kat_chain.npz       the reference's chains and filtered chains for the seed lists of tests/chain_cases.py (`make_golden.py chain`)
+  tests/golden/kat_mark.npz        digests of the reference's primary marking and mapQ for the region lists of tests/mark_cases.py (`make_golden.py mark`)
 
 `make_golden.py extras` writes only the last two groups (round 2 additions); the older files are left alone.
 """
@@ -227,5 +228,21 @@ def chain_kat():
     print("kat_chain.npz:", os.path.getsize(f"{HERE}/kat_chain.npz"), "bytes")
 
 
+def mark_kat():
+    """kat_mark.npz: every set of tests/mark_cases.py through `bwaref katmark` (oracle/ref_driver.c: the reference's mem_mark_primary_se,
+    mem_reorder_primary5 and mem_approx_mapq_se on the given region lists).  Per set: <set>.inputs, the sha256 of the generated case file
+    and its flags (a changed generator is caught before anything is compared); <set>.sha [reads], the sha256 of each read's record.
+    Digests only: no inputs, no records."""
+    import mark_cases as mc
+    assert os.path.exists("/root/reference/bwamem.c") and os.access(REF, os.X_OK), "needs the reference build (make -C oracle ref)"
+    os.makedirs(TMP, exist_ok=True)
+    out = {}
+    for name in mc.SETS:
+        out[f"{name}.inputs"] = np.array(mc.input_digest(name))
+        out[f"{name}.sha"] = mc.digests(mc.run_checker(REF, name, TMP, "golden"))
+    np.savez_compressed(f"{HERE}/kat_mark.npz", **out)
+    print("kat_mark.npz:", os.path.getsize(f"{HERE}/kat_mark.npz"), "bytes")
+
+
 if __name__ == "__main__":
-    {"extras": extras, "fastq": fastq_cases, "dpwide": dp_wide, "pelibs": pe_libraries, "chain": chain_kat}.get(sys.argv[1] if len(sys.argv) > 1 else "", main)()
+    {"extras": extras, "fastq": fastq_cases, "dpwide": dp_wide, "pelibs": pe_libraries, "chain": chain_kat, "mark": mark_kat}.get(sys.argv[1] if len(sys.argv) > 1 else "", main)()
