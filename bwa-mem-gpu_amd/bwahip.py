@@ -119,6 +119,12 @@ class QcStats(C.Structure):  # bwahip_qc_stats_t
                 ("scan_ms", C.c_double)]
 
 
+class SpillStats(C.Structure):  # bwahip_spill_t
+    _fields_ = [("host_budget", C.c_int64), ("tmp_dir", C.c_char_p), ("window_pieces", C.c_int), ("n_spilled_runs", C.c_int64), ("first_spilled_run", C.c_int64),
+                ("host_bytes", C.c_int64), ("file_bytes", C.c_int64), ("n_windows", C.c_int64), ("window_hbm_bytes", C.c_int64), ("download_s", C.c_double),
+                ("upload_ms", C.c_double)]
+
+
 ERRORS = {0: "ok", -1: "EINVAL", -2: "ENODEV", -3: "ENOMEM", -4: "EIO", -5: "ECAPACITY", -6: "EINTERNAL"}
 
 STAGE_INTV, STAGE_CHAIN, STAGE_CHAIN_FLT, STAGE_REGS, STAGE_REGS_PRE, STAGE_SEEDS = 1, 2, 3, 4, 5, 6
@@ -255,6 +261,14 @@ def lib():
     L.bwahip_stream_run_bam_sorted_dev_qc.argtypes = [C.POINTER(vp), C.c_int, C.POINTER(Opt), C.POINTER(PeStat), C.c_char_p, C.c_char_p, C.c_int, C.c_char_p,
                                                       C.POINTER(StreamStats), C.POINTER(SortDevStats), C.c_int, C.POINTER(MarkdupStats), C.c_int, C.POINTER(QcOpt), C.c_int,
                                                       C.POINTER(QcStats)]
+    L.bwahip_bam_devmerger_set_spill.argtypes = [vp, C.POINTER(SpillStats)]
+    L.bwahip_bam_devmerger_add_spilled.argtypes = [vp, C.c_int64, vp, C.c_int64, vp, vp, C.c_int64, vp, vp, C.c_int64]
+    L.bwahip_bam_devmerger_spill_stats.argtypes = [vp, C.POINTER(SpillStats)]
+    L.bwahip_bam_devmerge_spill_hbm_need.argtypes = [C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_int]
+    L.bwahip_bam_devmerge_spill_hbm_need.restype = C.c_int64
+    L.bwahip_stream_run_bam_sorted_dev_spill.argtypes = [C.POINTER(vp), C.c_int, C.POINTER(Opt), C.POINTER(PeStat), C.c_char_p, C.c_char_p, C.c_int, C.c_char_p,
+                                                         C.POINTER(StreamStats), C.POINTER(SortDevStats), C.POINTER(SpillStats), C.c_int, C.c_int, C.POINTER(MarkdupStats),
+                                                         C.POINTER(QcOpt), C.c_int, C.POINTER(QcStats)]
     L.bwahip_kat_radix_sort.argtypes = [vp, C.c_int64, vp, C.c_int, vp, C.POINTER(C.c_int)]
     L.bwahip_fastq_open.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(vp)]
     L.bwahip_fastq_next.argtypes = [vp, C.c_int64, C.c_int, C.POINTER(C.POINTER(Seq)), C.POINTER(C.c_int)]
@@ -491,6 +505,30 @@ class DevMerger:
         _check(lib().bwahip_bam_devmerger_finish_bai(self._h, fd, bai_fd, first_member_offset, n_ref, C.byref(st), C.byref(bs)), "bwahip_bam_devmerger_finish_bai")
         return st, bs
 
+    def set_spill(self, host_budget=0, tmp_dir=None, window_pieces=0):
+        """bwahip_bam_devmerger_set_spill: before the first add; runs added with add_spilled keep their record bytes in a host-side store
+        (pinned memory up to host_budget bytes, otherwise unlinked files in tmp_dir) and every finish stages them window by window
+        (csrc/k_bamspill.hip); window_pieces <= 0: the default, 8."""
+        sp = SpillStats()
+        sp.host_budget, sp.tmp_dir, sp.window_pieces = host_budget, os.fsencode(tmp_dir) if tmp_dir is not None else None, window_pieces
+        _check(lib().bwahip_bam_devmerger_set_spill(self._h, C.byref(sp)), "bwahip_bam_devmerger_set_spill")
+
+    def add_spilled(self, run_no, rec, keys, rec_off, tmpl=None, desc=None):
+        """bwahip_bam_devmerger_add_spilled: add (tmpl and desc None) or add_dup, the run held spilled."""
+        rec = bytes(rec)
+        keys = np.ascontiguousarray(keys, dtype=np.uint64)
+        rec_off = np.ascontiguousarray(rec_off, dtype=np.int64)
+        t = np.ascontiguousarray(tmpl, dtype=np.uint32) if tmpl is not None else None
+        d = np.ascontiguousarray(desc, dtype=DUP_DESC_DTYPE) if desc is not None else None
+        _check(lib().bwahip_bam_devmerger_add_spilled(self._h, run_no, rec, len(rec), keys.ctypes.data, rec_off.ctypes.data, len(keys), t.ctypes.data if t is not None else None,
+                                                      d.ctypes.data if d is not None else None, len(d) if d is not None else 0), "bwahip_bam_devmerger_add_spilled")
+
+    def spill_stats(self):
+        """bwahip_bam_devmerger_spill_stats: the SpillStats of the runs held and of the last finish."""
+        sp = SpillStats()
+        _check(lib().bwahip_bam_devmerger_spill_stats(self._h, C.byref(sp)), "bwahip_bam_devmerger_spill_stats")
+        return sp
+
     def close(self):
         if self._h:
             lib().bwahip_bam_devmerger_close(self._h)
@@ -506,6 +544,11 @@ class DevMerger:
 def bam_devmerge_hbm_need(raw_bytes, n_records, n_runs, piece_blocks):
     """bwahip_bam_devmerge_hbm_need: the HBM a device merger takes for these runs, finish included (no device)."""
     return lib().bwahip_bam_devmerge_hbm_need(raw_bytes, n_records, n_runs, piece_blocks)
+
+
+def bam_devmerge_spill_hbm_need(resident_raw_bytes, spilled_raw_bytes, longest_record, n_records, n_runs, piece_blocks, window_pieces):
+    """bwahip_bam_devmerge_spill_hbm_need: the HBM a device merger with spilled runs takes, finish included (no device)."""
+    return lib().bwahip_bam_devmerge_spill_hbm_need(resident_raw_bytes, spilled_raw_bytes, longest_record, n_records, n_runs, piece_blocks, window_pieces)
 
 
 def bam_devmerge_markdup_hbm_need(n_records, n_templates):
@@ -1399,6 +1442,28 @@ def stream_run_bam_sorted_dev_qc(ctxs, fq1, fq2=None, out_fd=-1, bai_fd=-1, qc_f
                                                      os.fsencode(fq2) if fq2 else None, out_fd, hdr_line, C.byref(st), C.byref(sd), bai_fd, C.byref(ms), int(bool(markdup)),
                                                      C.byref(qc_opt(*qc)), qc_fd, C.byref(qs)), "bwahip_stream_run_bam_sorted_dev_qc")
     return st, sd, ms, qs
+
+
+def stream_run_bam_sorted_dev_spill(ctxs, fq1, fq2=None, out_fd=-1, bai_fd=-1, qc_fd=-1, markdup=False, qc=None, hdr_line=None, opt=None, chunk_bases=0, max_reads=0,
+                                    keep_comments=False, reader_threads=0, pes0=None, hbm_budget=0, piece_blocks=0, host_budget=0, tmp_dir=None, window_pieces=0):
+    """bwahip_stream_run_bam_sorted_dev_spill: the device-merged sorted BAM file for samples whose record bytes outgrow HBM -- runs that do
+    not fit hbm_budget keep their record bytes in a host-side store (host_budget, tmp_dir) and the finish stages them window by window.
+    bai_fd >= 0: the index; markdup: duplicates marked; qc = (window_shift, exclude_flags, min_mapq) or (): the QC summary on qc_fd.
+    Returns (StreamStats, SortDevStats, SpillStats, MarkdupStats, QcStats)."""
+    opt = opt or default_opt()
+    st, sd, sp, ms, qs = StreamStats(), SortDevStats(), SpillStats(), MarkdupStats(), QcStats()
+    st.chunk_bases, st.max_reads, st.keep_comments, st.reader_threads = chunk_bases, max_reads, int(keep_comments), reader_threads
+    sd.tmp_dir, sd.mem_budget, sd.level = None, 0, 1
+    sd.hbm_budget, sd.piece_blocks = hbm_budget, piece_blocks
+    sp.host_budget, sp.tmp_dir, sp.window_pieces = host_budget, os.fsencode(tmp_dir) if tmp_dir is not None else None, window_pieces
+    arr = (C.c_void_p * len(ctxs))(*[c._h for c in ctxs])
+    if isinstance(hdr_line, str):
+        hdr_line = hdr_line.encode()
+    _check(lib().bwahip_stream_run_bam_sorted_dev_spill(arr, len(ctxs), C.byref(opt), C.byref(pes0) if pes0 is not None else None, os.fsencode(fq1),
+                                                        os.fsencode(fq2) if fq2 else None, out_fd, hdr_line, C.byref(st), C.byref(sd), C.byref(sp), bai_fd, int(bool(markdup)),
+                                                        C.byref(ms), C.byref(qc_opt(*qc)) if qc is not None else None, qc_fd, C.byref(qs)),
+           "bwahip_stream_run_bam_sorted_dev_spill")
+    return st, sd, sp, ms, qs
 
 
 def _tool(name):

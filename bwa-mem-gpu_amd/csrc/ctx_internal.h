@@ -284,6 +284,7 @@ inline int64_t bgzf_blocks(int64_t len) { return (len + 65279) / 65280; }
 struct DevRun {
 	int64_t n_rec = 0, len = 0; uint8_t *rec = nullptr; uint64_t *keys = nullptr; int64_t *off = nullptr; int device = 0;   // allocated to size: no slack
 	bool has_dup = false; int64_t n_tmpl = 0; uint32_t *tmpl = nullptr; bwahip_dup_desc_t *desc = nullptr;
+	bool spilled = false; std::vector<int64_t> h_off;               // a spilled run (k_bamspill.hip): rec stays null, the bytes are in the merger's store; the offsets on the host as well
 };
 int  bam_devrun_make(bwahip_ctx *c, const uint8_t *d_rec, int64_t len, const uint64_t *d_keys, const int64_t *d_rec_off, int64_t n_rec, hipStream_t st, DevRun **out);
 int  bam_devrun_download(const DevRun *r, uint8_t *rec, uint64_t *keys, int64_t *rec_off, hipStream_t st);
@@ -291,9 +292,14 @@ void bam_devrun_free(DevRun *r);
 // the run's template indices and descriptors, copied from device pointers on st as bam_devrun_make copies the records (BWAHIP_ENOMEM: the run is as before)
 int  bam_devrun_add_dup(DevRun *r, const uint32_t *d_tmpl, const bwahip_dup_desc_t *d_desc, int64_t n_tmpl, hipStream_t st);
 int  bam_devmerger_adopt(bwahip_bam_devmerger *m, int64_t run_no, DevRun *r);
+// adopt, with the run held spilled (the merger is armed): its record bytes go device -> store on st and leave HBM, its offsets are kept on
+// the host as well; *longest (may be null): its longest record.  Refused: the caller still owns the run, whole
+int  bam_devmerger_window_pieces(const bwahip_bam_devmerger *m);   // of an armed merger: what set_spill resolved (0: not armed)
+int  bam_devmerger_adopt_spilled(bwahip_bam_devmerger *m, int64_t run_no, DevRun *r, hipStream_t st, int64_t *longest);
 // the device-to-device form of bwahip_bam_devmerger_add: make + adopt
 int  bam_devmerger_add_dev(bwahip_bam_devmerger *m, int64_t run_no, const uint8_t *d_rec, int64_t len, const uint64_t *d_keys, const int64_t *d_rec_off, int64_t n_rec, hipStream_t st);
-// the merger's runs in run-number order, handed to the caller (who frees them); the merger is empty afterwards
+// the merger's runs in run-number order, handed to the caller (who frees them); the merger is empty afterwards.  A merger that holds a
+// spilled run is refused (BWAHIP_EINVAL) and keeps its runs: their record bytes are in its store
 int  bam_devmerger_take_runs(bwahip_bam_devmerger *m, std::vector<std::pair<int64_t, DevRun*>> *out);
 // k_bai.hip: the index stage of a device merger's finish.  bai_stage_members: room for the lengths of n_blocks members (the caller fills
 // them, on c->stream); bai_stage_run: the index of the n records addr[idx[i]] (sorted order; out_off: their n + 1 offsets in the stream of
@@ -303,7 +309,11 @@ BaiStage *bai_stage_new();
 void bai_stage_free(BaiStage *s);
 int  bai_stage_members(BaiStage *s, int64_t n_blocks, int **mlen);
 int  bai_stage_run(BaiStage *s, bwahip_ctx *c, int n, const uint8_t *const *addr, const unsigned *idx, const int64_t *out_off, int64_t total, int64_t n_blocks, int64_t base,
-                   int32_t n_ref, std::vector<uint8_t> *bytes, bwahip_bai_stats_t *bs);
+                   int32_t n_ref, std::vector<uint8_t> *bytes, bwahip_bai_stats_t *bs, bool parsed = false);
+// the parse alone, for a merger with spilled runs: bai_stage_parse_begin once (buffers, cleared tables), bai_stage_parse over the sorted
+// ordinals [lo, hi) while their records -- and that of ordinal lo - 1 -- can be read; bai_stage_run(parsed = true) does the rest
+int  bai_stage_parse_begin(BaiStage *s, bwahip_ctx *c, int n, int64_t n_blocks, int32_t n_ref);
+int  bai_stage_parse(BaiStage *s, bwahip_ctx *c, int lo, int hi, const uint8_t *const *addr, const unsigned *idx, const int64_t *out_off, int32_t n_ref);
 // k_markdup.hip.  Per batch, from bam_sort_batch: dup_batch_desc after the record table (descriptors, templates in input order), dup_batch_tmpl
 // after the radix sort (templates in sorted order; awaits the descriptor kernel's error word).  The decision stage of a device merger's
 // marked finish: desc = the descriptors of all runs in run order; markdup_decide leaves one byte per template in dup (queued on c->stream, the
@@ -320,7 +330,13 @@ int dup_batch_tmpl(bwahip_ctx *c, int n_rec, const unsigned *idx);
 int markdup_decide(MarkdupStage *s, bwahip_ctx *c, int64_t n_tmpl);
 int markdup_counters_reset(MarkdupStage *s, bwahip_ctx *c);
 int markdup_count(MarkdupStage *s, bwahip_ctx *c, int64_t n_tmpl);
-int markdup_mark_run(MarkdupStage *s, bwahip_ctx *c, uint8_t *rec, const int64_t *off, int64_t n_rec, int64_t len, const uint32_t *tmpl, int64_t first_tmpl, int64_t n_tmpl);
+// marked_to: where the records marked are counted (null: cnt[6]; a spilled run's record staged a second time counts elsewhere)
+int markdup_mark_run(MarkdupStage *s, bwahip_ctx *c, uint8_t *rec, const int64_t *off, int64_t n_rec, int64_t len, const uint32_t *tmpl, int64_t first_tmpl, int64_t n_tmpl,
+                     unsigned long long *marked_to = nullptr);
+// k_bamspill.hip: the window cuts of a merger with spilled runs (cut: n_windows rows of n_runs + 1 cells) and a window's source addresses
+int spill_window_cuts(hipStream_t st, int n, int n_runs, const int64_t *first, const uint8_t *spilled, const unsigned *idx, const int *piece_first, int window_pieces, int n_windows, int *cut);
+int spill_window_addr(hipStream_t st, int rec_lo, int n_rec, int n_runs, const int64_t *first, const int64_t *const *run_off, const uint8_t *spilled, const int64_t *base,
+                      const unsigned *idx, const uint8_t **addr);
 // k_qc.hip: the QC stage of a device merger's finish, on c->stream.  begin: the layout for these contigs and (resolved) options, the tables and
 // the difference array cleared; records: the record pass over one run (ord0: the ordinal of its first record in the order given); finish: the
 // scan pass, the one download (awaited) and the summary's bytes -- BWAHIP_EINVAL when a record was refused.  n_records == 0 launches nothing.

@@ -34,10 +34,11 @@ __global__ __launch_bounds__(256) void k_bai_addr(int n, const uint8_t *rec, con
 	if (i < n) addr[i] = rec + rec_off[i];
 }
 
-__global__ __launch_bounds__(256) void k_bai_parse(int n, const uint8_t *const *addr, const unsigned *idx, const int64_t *out_off, int n_ref,
+// the sorted records [lo, n)
+__global__ __launch_bounds__(256) void k_bai_parse(int lo, int n, const uint8_t *const *addr, const unsigned *idx, const int64_t *out_off, int n_ref,
                                                    uint64_t *rk, int *pos, int *end, uint8_t *unm, unsigned long long *err, int *top, unsigned *n_unm)
 {
-	const int i = blockIdx.x * 256 + threadIdx.x;
+	const int i = lo + blockIdx.x * 256 + threadIdx.x;
 	if (i >= n) return;
 	const uint8_t *p = addr[idx[i]];
 	const int64_t len = out_off[i + 1] - out_off[i];
@@ -175,8 +176,38 @@ int bai_stage_members(BaiStage *s, int64_t n_blocks, int **mlen)
 	return rc;
 }
 
+// what the parse writes and what it adds to, cleared: queued on c->stream
+int bai_stage_parse_begin(BaiStage *s, bwahip_ctx *c, int n, int64_t n_blocks, int32_t n_ref)
+{
+	if (!s || !c || n <= 0 || n_ref < 0) return BWAHIP_EINVAL;
+	HIP_TRY(hipSetDevice(c->device));
+	for (auto &e : s->ev) if (!e) HIP_TRY(hipEventCreate(&e));
+	hipStream_t q = c->stream;
+	const size_t N = (size_t)n, R = (size_t)(n_ref ? n_ref : 1);
+	int rc;
+	if ((rc = s->rk.ensure(N * 8)) || (rc = s->pos.ensure(N * 4)) || (rc = s->end.ensure(N * 4)) || (rc = s->unm.ensure(N)) || (rc = s->head.ensure(N * 4)) ||
+	    (rc = s->hscan.ensure((N + 1) * 8)) || (rc = s->coff.ensure(((size_t)n_blocks + 1) * 8)) || (rc = s->first.ensure(R * 4)) || (rc = s->last.ensure(R * 4)) ||
+	    (rc = s->top.ensure(R * 4)) || (rc = s->n_unm.ensure(R * 4)) || (rc = s->err.ensure(16)) || (rc = s->h_top.ensure(R * 4 + 32))) return rc;
+	HIP_TRY(hipEventRecord(s->ev[0], q));
+	HIP_TRY(hipMemsetAsync(s->err.p, 0xff, 8, q));
+	HIP_TRY(hipMemsetAsync(s->err.as<uint8_t>() + 8, 0, 8, q));   // n_coor
+	HIP_TRY(hipMemsetAsync(s->first.p, 0xff, R * 4, q));
+	HIP_TRY(hipMemsetAsync(s->last.p, 0xff, R * 4, q));
+	HIP_TRY(hipMemsetAsync(s->top.p, 0x7f, R * 4, q));             // above every window
+	HIP_TRY(hipMemsetAsync(s->n_unm.p, 0, R * 4, q));
+	return 0;
+}
+
+int bai_stage_parse(BaiStage *s, bwahip_ctx *c, int lo, int hi, const uint8_t *const *addr, const unsigned *idx, const int64_t *out_off, int32_t n_ref)
+{
+	if (hi <= lo) return 0;
+	hipLaunchKernelGGL(k_bai_parse, dim3(grid_of((int64_t)hi - lo)), dim3(256), 0, c->stream, lo, hi, addr, idx, out_off, (int)n_ref, s->rk.as<uint64_t>(), s->pos.as<int>(), s->end.as<int>(),
+	                   s->unm.as<uint8_t>(), s->err.as<unsigned long long>(), s->top.as<int>(), s->n_unm.as<unsigned>());
+	return launched();
+}
+
 int bai_stage_run(BaiStage *s, bwahip_ctx *c, int n, const uint8_t *const *addr, const unsigned *idx, const int64_t *out_off, int64_t total, int64_t n_blocks, int64_t base,
-                  int32_t n_ref, std::vector<uint8_t> *bytes, bwahip_bai_stats_t *bs)
+                  int32_t n_ref, std::vector<uint8_t> *bytes, bwahip_bai_stats_t *bs, bool parsed)
 {
 	if (!s || !c || !bytes || n < 0 || n_ref < 0 || base < 0 || n_blocks != bgzf_blocks(total) || n_blocks > 0x7fffffffll) return BWAHIP_EINVAL;
 	bwahip_bai_stats_t st;
@@ -194,24 +225,9 @@ int bai_stage_run(BaiStage *s, bwahip_ctx *c, int n, const uint8_t *const *addr,
 		if (bs) *bs = st;
 		return 0;
 	}
-	HIP_TRY(hipSetDevice(c->device));
-	for (auto &e : s->ev) if (!e) HIP_TRY(hipEventCreate(&e));
 	hipStream_t q = c->stream;
-	const size_t N = (size_t)n, R = (size_t)(n_ref ? n_ref : 1);
-	if ((rc = s->rk.ensure(N * 8)) || (rc = s->pos.ensure(N * 4)) || (rc = s->end.ensure(N * 4)) || (rc = s->unm.ensure(N)) || (rc = s->head.ensure(N * 4)) ||
-	    (rc = s->hscan.ensure((N + 1) * 8)) || (rc = s->coff.ensure(((size_t)n_blocks + 1) * 8)) || (rc = s->first.ensure(R * 4)) || (rc = s->last.ensure(R * 4)) ||
-	    (rc = s->top.ensure(R * 4)) || (rc = s->n_unm.ensure(R * 4)) || (rc = s->err.ensure(16)) || (rc = s->h_top.ensure(R * 4 + 32))) return rc;
-	HIP_TRY(hipEventRecord(s->ev[0], q));
-	HIP_TRY(hipMemsetAsync(s->err.p, 0xff, 8, q));
-	HIP_TRY(hipMemsetAsync(s->err.as<uint8_t>() + 8, 0, 8, q));   // n_coor
-	HIP_TRY(hipMemsetAsync(s->first.p, 0xff, R * 4, q));
-	HIP_TRY(hipMemsetAsync(s->last.p, 0xff, R * 4, q));
-	HIP_TRY(hipMemsetAsync(s->top.p, 0x7f, R * 4, q));             // above every window
-	HIP_TRY(hipMemsetAsync(s->n_unm.p, 0, R * 4, q));
+	if (!parsed && ((rc = bai_stage_parse_begin(s, c, n, n_blocks, n_ref)) || (rc = bai_stage_parse(s, c, 0, n, addr, idx, out_off, n_ref)))) return rc;
 	int *n_coor_dev = (int*)(s->err.as<uint8_t>() + 8);
-	hipLaunchKernelGGL(k_bai_parse, dim3(grid_of(n)), dim3(256), 0, q, n, addr, idx, out_off, (int)n_ref, s->rk.as<uint64_t>(), s->pos.as<int>(), s->end.as<int>(), s->unm.as<uint8_t>(),
-	                   s->err.as<unsigned long long>(), s->top.as<int>(), s->n_unm.as<unsigned>());
-	if ((rc = launched())) return rc;
 	hipLaunchKernelGGL(k_bai_heads, dim3(grid_of(n)), dim3(256), 0, q, n, s->rk.as<uint64_t>(), s->head.as<int>(), s->first.as<int>(), s->last.as<int>(), n_coor_dev);
 	if ((rc = launched()) || (rc = launch_scan(s->head.as<int>(), s->hscan.as<int64_t>(), n, c->d_scan, q)) ||
 	    (rc = launch_scan(s->mlen.as<int>(), s->coff.as<int64_t>(), (int)n_blocks, c->d_scan, q))) return rc;

@@ -22,11 +22,17 @@
 // A marked finish (bwahip_bam_devmerger_finish_markdup) runs the duplicate decision and the marking pass of k_markdup.hip over the runs
 // before the order is made: one bit of a record changes and no key, so everything after it is the unmarked finish.
 //
+// A merger with spilled runs (bwahip_bam_devmerger_set_spill, k_bamspill.hip) keeps those runs' record bytes in a host-side store and
+// stages them one window of pieces at a time: the order, the output offsets, the piece cuts and the deflate are the same, the gather finds
+// a spilled record in the window's staging buffer, and the stages that read records (marking pass, QC record pass, index parse) run per
+// window on the staged slices.  A merger without a spilled run queues exactly what is described above.
+//
 // An armed merger (bwahip_bam_devmerger_set_qc) runs the QC stage of k_qc.hip over the runs after the marking and before the order: it reads
 // the records and changes nothing, so the members are those of the unarmed finish.
 #include "ctx_internal.h"
 #include "bai_tables.h"
 #include "qc_tables.h"
+#include "spill_store.h"
 #include <errno.h>
 #include <unistd.h>
 #include <chrono>
@@ -149,6 +155,36 @@ int write_full(int fd, const uint8_t *b, int64_t len)
 	return 0;
 }
 
+// a merger with spilled runs: the staging of the windows (counted by bwahip_bam_devmerge_spill_hbm_need, k_bamspill.hip)
+struct SpillWork {
+	DevBuf stage[2], cut, base, flags, scratch;                    // two windows' slices; per run and window: the cuts, the slices' bases; per run: spilled or not; a counter nobody reads
+	HostBuf bounce[2];                                             // file-backed runs: pread lands here, at the slice's place in the window
+	hipEvent_t ev_up0[2] = {}, ev_up[2] = {}, ev_used[2] = {};     // a window's upload begun / done (copy stream); its last reader queued (context's stream)
+	int make_events()
+	{
+		for (auto *set : { ev_up0, ev_up, ev_used }) for (int k = 0; k < 2; ++k) if (!set[k]) HIP_TRY(hipEventCreate(&set[k]));
+		return 0;
+	}
+	size_t bytes() const { size_t b = 0; for (const DevBuf *d : { &stage[0], &stage[1], &cut, &base, &flags, &scratch }) b += d->cap; return b; }
+	void release()
+	{
+		for (DevBuf *d : { &stage[0], &stage[1], &cut, &base, &flags, &scratch }) d->release();
+		bounce[0].release(); bounce[1].release();
+		for (auto *set : { ev_up0, ev_up, ev_used }) for (int k = 0; k < 2; ++k) if (set[k]) { (void)hipEventDestroy(set[k]); set[k] = nullptr; }
+	}
+};
+
+constexpr int DEFAULT_WINDOW_PIECES = 8;                          // with 1 024 blocks a piece: windows of 535 MB, two staging buffers of that
+
+void *pinned_alloc(size_t bytes, void *ctx)
+{
+	void *p = nullptr;
+	if (hipSetDevice(((bwahip_ctx*)ctx)->device) != hipSuccess || hipHostMalloc(&p, bytes ? bytes : 1, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
+	++g_bwahip_reallocs;
+	return p;
+}
+void pinned_free(void *p, size_t, void *) { if (p) { (void)hipHostFree(p); ++g_bwahip_reallocs; } }
+
 } // namespace
 
 // The HBM of a device merger: what the runs hold, and what finish() allocates for them -- next to the buffers it counts (Work above, the
@@ -176,16 +212,20 @@ struct bwahip_bam_devmerger {
 	BaiStage *bai = nullptr;                                       // the index stage's buffers (k_bai.hip), made by the first finish_bai
 	MarkdupStage md;                                               // the marking stage's buffers (k_markdup.hip), grown by the first finish_markdup
 	QcStage *qc = nullptr;                                         // the QC stage's buffers (k_qc.hip), made by the first armed finish
+	// spilled runs (bwahip_bam_devmerger_set_spill): the store of their record bytes, the windows' staging
+	HostBuf dl_bounce;                                             // bam_devmerger_adopt_spilled: a file-backed run's bytes on their way from HBM
+	bool spill_armed = false, added = false; int window_pieces = 0; SpillStore *store = nullptr; SpillWork sw;
+	int64_t n_spilled = 0, n_windows = 0; double download_s = 0, upload_ms = 0;
 	bool qc_armed = false; bwahip_qc_opt_t qc_opt = { 14, 1796, 0 }; std::vector<int64_t> qc_len; int qc_fd = -1; bwahip_qc_stats_t *qc_stats = nullptr;
 };
 
 namespace {
 struct BaiArgs { int bai_fd; int64_t base; int32_t n_ref; bwahip_bai_stats_t *bs; };
 // the index of what finish wrote: after the last piece, on the context's stream
-int finish_index(bwahip_bam_devmerger *m, const BaiArgs &a, int n, const unsigned *idx, int64_t total)
+int finish_index(bwahip_bam_devmerger *m, const BaiArgs &a, int n, const unsigned *idx, int64_t total, bool parsed = false)
 {
 	std::vector<uint8_t> bytes;
-	int rc = bai_stage_run(m->bai, m->c, n, m->w.addr.as<const uint8_t*>(), idx, m->w.out_off.as<int64_t>(), total, bgzf_blocks(total), a.base, a.n_ref, &bytes, a.bs);
+	int rc = bai_stage_run(m->bai, m->c, n, m->w.addr.as<const uint8_t*>(), idx, m->w.out_off.as<int64_t>(), total, bgzf_blocks(total), a.base, a.n_ref, &bytes, a.bs, parsed);
 	if (!rc) rc = bai_write_fd(a.bai_fd, bytes);
 	return rc;
 }
@@ -254,7 +294,48 @@ int bam_devmerger_adopt(bwahip_bam_devmerger *m, int64_t run_no, DevRun *r)
 	if (m->runs.count(run_no)) return BWAHIP_EINVAL;
 	if (m->n_records + r->n_rec > 0x7fffffffll) return BWAHIP_ECAPACITY;   // the sort's ordinals are 32-bit and it takes an int
 	m->runs[run_no] = r;
-	m->n_records += r->n_rec; m->raw_bytes += r->len;
+	m->n_records += r->n_rec; m->raw_bytes += r->len; m->added = true;
+	if (r->spilled) ++m->n_spilled;
+	return 0;
+}
+
+int bam_devmerger_window_pieces(const bwahip_bam_devmerger *m) { return m && m->spill_armed ? m->window_pieces : 0; }
+
+int bam_devmerger_adopt_spilled(bwahip_bam_devmerger *m, int64_t run_no, DevRun *r, hipStream_t st, int64_t *longest)
+{
+	if (!m || !r || run_no < 0 || r->spilled || r->device != m->c->device || !m->spill_armed) return BWAHIP_EINVAL;
+	{
+		std::lock_guard<std::mutex> lk(m->mu);
+		if (m->runs.count(run_no)) return BWAHIP_EINVAL;
+	}
+	HIP_TRY(hipSetDevice(r->device));
+	const double t0 = now_s();
+	uint8_t *mem = nullptr;
+	int rc = spill_store_reserve(m->store, run_no, r->len, &mem);
+	if (rc) return rc;
+	std::vector<int64_t> h_off((size_t)(r->n_rec ? r->n_rec + 1 : 0));
+	hipError_t e = r->n_rec ? hipMemcpyAsync(h_off.data(), r->off, h_off.size() * 8, hipMemcpyDeviceToHost, st) : hipSuccess;
+	if (e == hipSuccess && mem) e = hipMemcpyAsync(mem, r->rec, (size_t)r->len, hipMemcpyDeviceToHost, st);
+	if (e == hipSuccess) e = hipStreamSynchronize(st);
+	if (e == hipSuccess && !mem && r->len) {                       // a file: through the pinned bounce buffer, 64 MiB at a time
+		const int64_t step = 64ll << 20;
+		if (!(rc = m->dl_bounce.ensure((size_t)(r->len < step ? r->len : step))))
+			for (int64_t at = 0; at < r->len && !rc && e == hipSuccess; at += step) {
+				const int64_t part = r->len - at < step ? r->len - at : step;
+				e = hipMemcpyAsync(m->dl_bounce.p, r->rec + at, (size_t)part, hipMemcpyDeviceToHost, st);
+				if (e == hipSuccess) e = hipStreamSynchronize(st);
+				if (e == hipSuccess) rc = spill_store_write(m->store, run_no, at, (const uint8_t*)m->dl_bounce.p, part);
+			}
+	}
+	if (e != hipSuccess) { fprintf(stderr, "[bwahip] sorted BAM: downloading a spilled run failed: %s\n", hipGetErrorString(e)); rc = BWAHIP_ENODEV; }
+	if (rc) { (void)spill_store_drop(m->store, run_no); return rc; }
+	uint8_t *d_rec = r->rec;
+	r->rec = nullptr; r->spilled = true; r->h_off.swap(h_off);
+	if ((rc = bam_devmerger_adopt(m, run_no, r))) { r->rec = d_rec; r->spilled = false; r->h_off.clear(); (void)spill_store_drop(m->store, run_no); return rc; }
+	if (d_rec) { (void)hipFree(d_rec); ++g_bwahip_reallocs; }
+	if (longest) { *longest = 0; for (int64_t i = 0; i < r->n_rec; ++i) if (r->h_off[(size_t)i + 1] - r->h_off[(size_t)i] > *longest) *longest = r->h_off[(size_t)i + 1] - r->h_off[(size_t)i]; }
+	std::lock_guard<std::mutex> lk(m->mu);
+	m->download_s += now_s() - t0;
 	return 0;
 }
 
@@ -277,6 +358,7 @@ int bam_devmerger_take_runs(bwahip_bam_devmerger *m, std::vector<std::pair<int64
 {
 	if (!m || !out) return BWAHIP_EINVAL;
 	std::lock_guard<std::mutex> lk(m->mu);
+	if (m->n_spilled) return BWAHIP_EINVAL;
 	out->assign(m->runs.begin(), m->runs.end());
 	m->runs.clear(); m->n_records = 0; m->raw_bytes = 0;
 	return 0;
@@ -295,7 +377,7 @@ extern "C" int bwahip_bam_devmerger_open(bwahip_ctx *ctx, int piece_blocks, bwah
 
 // tmpl / desc / n_tmpl: bwahip_bam_devmerger_add_dup (with_dup)
 static int devmerger_add(bwahip_bam_devmerger *m, int64_t run_no, const uint8_t *rec, int64_t len, const uint64_t *keys, const int64_t *rec_off, int64_t n_rec,
-                         bool with_dup, const uint32_t *tmpl, const bwahip_dup_desc_t *desc, int64_t n_tmpl)
+                         bool with_dup, const uint32_t *tmpl, const bwahip_dup_desc_t *desc, int64_t n_tmpl, bool spill = false)
 {
 	if (!m || run_no < 0 || len < 0 || n_rec < 0 || (n_rec && (!rec || !keys || !rec_off)) || (!n_rec && len)) return BWAHIP_EINVAL;
 	if (n_rec && (rec_off[0] != 0 || rec_off[n_rec] != len)) return BWAHIP_EINVAL;
@@ -315,13 +397,21 @@ static int devmerger_add(bwahip_bam_devmerger *m, int64_t run_no, const uint8_t 
 		if (m->n_records + n_rec > 0x7fffffffll) return BWAHIP_ECAPACITY;
 	}
 	HIP_TRY(hipSetDevice(c->device));
-	DevRun *r = new DevRun;
-	r->n_rec = n_rec; r->len = len; r->device = c->device;
 	int rc = 0;
+	if (spill) {                                                   // the record bytes to the store first: an unusable tmp_dir is refused before anything is allocated
+		const double t0 = now_s();
+		if ((rc = spill_store_put(m->store, run_no, rec, len))) return rc;
+		std::lock_guard<std::mutex> lk(m->mu);
+		m->download_s += now_s() - t0;
+	}
+	DevRun *r = new DevRun;
+	r->n_rec = n_rec; r->len = len; r->device = c->device; r->spilled = spill;
+	if (spill) r->h_off.assign(rec_off, rec_off + (n_rec ? n_rec + 1 : 0));
+	struct Undo { bwahip_bam_devmerger *m; int64_t id; bool on; ~Undo() { if (on) (void)spill_store_drop(m->store, id); } } undo = { m, run_no, spill };   // a refused run leaves the store as it was
 	if (n_rec) {
-		if ((rc = dev_alloc((void**)&r->rec, (size_t)len)) || (rc = dev_alloc((void**)&r->keys, (size_t)n_rec * 8)) || (rc = dev_alloc((void**)&r->off, (size_t)(n_rec + 1) * 8))) { bam_devrun_free(r); return rc; }
+		if ((!spill && (rc = dev_alloc((void**)&r->rec, (size_t)len))) || (rc = dev_alloc((void**)&r->keys, (size_t)n_rec * 8)) || (rc = dev_alloc((void**)&r->off, (size_t)(n_rec + 1) * 8))) { bam_devrun_free(r); return rc; }
 		// plain copies: they return when the caller's memory has been read, whatever thread and stream
-		hipError_t e = len ? hipMemcpy(r->rec, rec, (size_t)len, hipMemcpyHostToDevice) : hipSuccess;
+		hipError_t e = len && !spill ? hipMemcpy(r->rec, rec, (size_t)len, hipMemcpyHostToDevice) : hipSuccess;
 		if (e == hipSuccess) e = hipMemcpy(r->keys, keys, (size_t)n_rec * 8, hipMemcpyHostToDevice);
 		if (e == hipSuccess) e = hipMemcpy(r->off, rec_off, (size_t)(n_rec + 1) * 8, hipMemcpyHostToDevice);
 		if (e == hipSuccess && with_dup && (rc = dev_alloc((void**)&r->tmpl, (size_t)n_rec * 4))) { bam_devrun_free(r); return rc; }
@@ -335,6 +425,7 @@ static int devmerger_add(bwahip_bam_devmerger *m, int64_t run_no, const uint8_t 
 	}
 	r->has_dup = with_dup; r->n_tmpl = with_dup ? n_tmpl : 0;
 	if ((rc = bam_devmerger_adopt(m, run_no, r))) bam_devrun_free(r);
+	else undo.on = false;
 	return rc;
 }
 
@@ -349,14 +440,48 @@ extern "C" int bwahip_bam_devmerger_add_dup(bwahip_bam_devmerger *m, int64_t run
 	return devmerger_add(m, run_no, rec, len, keys, rec_off, n_rec, true, tmpl, desc, n_tmpl);
 }
 
+extern "C" int bwahip_bam_devmerger_set_spill(bwahip_bam_devmerger *m, const bwahip_spill_t *in)
+{
+	if (!m || !in || in->host_budget < 0 || in->window_pieces > 65536) return BWAHIP_EINVAL;
+	std::lock_guard<std::mutex> lk(m->mu);
+	if (m->added || m->spill_armed) return BWAHIP_EINVAL;           // before the first add, once
+	if (!(m->store = spill_store_new(in->host_budget, in->tmp_dir, pinned_alloc, pinned_free, m->c))) return BWAHIP_ENOMEM;
+	m->window_pieces = in->window_pieces > 0 ? in->window_pieces : DEFAULT_WINDOW_PIECES;
+	m->spill_armed = true;
+	return 0;
+}
+
+// tmpl == NULL && desc == NULL: a run without descriptors (bwahip_bam_devmerger_add); otherwise bwahip_bam_devmerger_add_dup
+extern "C" int bwahip_bam_devmerger_add_spilled(bwahip_bam_devmerger *m, int64_t run_no, const uint8_t *rec, int64_t len, const uint64_t *keys, const int64_t *rec_off, int64_t n_rec,
+                                                const uint32_t *tmpl, const bwahip_dup_desc_t *desc, int64_t n_tmpl)
+{
+	if (!m || !m->spill_armed) return BWAHIP_EINVAL;
+	const bool with_dup = tmpl || desc;
+	if (!with_dup && n_tmpl) return BWAHIP_EINVAL;
+	return devmerger_add(m, run_no, rec, len, keys, rec_off, n_rec, with_dup, tmpl, desc, n_tmpl, true);
+}
+
+extern "C" int bwahip_bam_devmerger_spill_stats(bwahip_bam_devmerger *m, bwahip_spill_t *out)
+{
+	if (!m || !out) return BWAHIP_EINVAL;
+	std::lock_guard<std::mutex> lk(m->mu);
+	out->n_spilled_runs = m->n_spilled; out->first_spilled_run = -1;
+	for (auto &kv : m->runs) if (kv.second->spilled) { out->first_spilled_run = kv.first; break; }
+	out->host_bytes = spill_store_host_bytes(m->store); out->file_bytes = spill_store_file_bytes(m->store);
+	out->n_windows = m->n_windows; out->window_hbm_bytes = (int64_t)m->sw.bytes();
+	out->download_s = m->download_s; out->upload_ms = m->upload_ms;
+	return 0;
+}
+
 // The marked finish's own part, on the context's stream, before the order is made: the runs' descriptors concatenated in run order, the
-// decision, the counts, the marking pass over every run's records.  Awaited at its end (the counters come back).
-static int devmerger_mark(bwahip_bam_devmerger *m, bwahip_markdup_stats_t *ms)
+// decision, the counts, the marking pass over every resident run's records (devmerger_mark_begin; a spilled run's records are marked in
+// the windows that stage them).  devmerger_mark_end awaits the stream: the counters come back.
+static int devmerger_mark_begin(bwahip_bam_devmerger *m)
 {
 	bwahip_ctx *c = m->c;
 	MarkdupStage &s = m->md;
-	int64_t T = 0, run_bytes = 0;
-	for (auto &kv : m->runs) { T += kv.second->n_tmpl; run_bytes += 4 * kv.second->n_rec + 24 * kv.second->n_tmpl; }
+	int64_t T = 0;
+	for (auto &kv : m->runs) T += kv.second->n_tmpl;
 	if (T > 0x3fffffffll) return BWAHIP_ECAPACITY;
 	HIP_TRY(hipSetDevice(c->device));
 	for (auto &e : s.ev) if (!e) HIP_TRY(hipEventCreate(&e));
@@ -375,9 +500,18 @@ static int devmerger_mark(bwahip_bam_devmerger *m, bwahip_markdup_stats_t *ms)
 	at = 0;
 	for (auto &kv : m->runs) {
 		DevRun *r = kv.second;
-		if ((rc = markdup_mark_run(&s, c, r->rec, r->off, r->n_rec, r->len, r->tmpl, at, r->n_tmpl))) return rc;
+		if (!r->spilled && (rc = markdup_mark_run(&s, c, r->rec, r->off, r->n_rec, r->len, r->tmpl, at, r->n_tmpl))) return rc;
 		at += r->n_tmpl;
 	}
+	return 0;
+}
+
+static int devmerger_mark_end(bwahip_bam_devmerger *m, bwahip_markdup_stats_t *ms)
+{
+	bwahip_ctx *c = m->c;
+	MarkdupStage &s = m->md;
+	int64_t run_bytes = 0;
+	for (auto &kv : m->runs) run_bytes += 4 * kv.second->n_rec + 24 * kv.second->n_tmpl;
 	HIP_TRY(hipEventRecord(s.ev[2], c->stream));
 	unsigned long long cnt[8] = { 0 };
 	HIP_TRY(hipMemcpyAsync(cnt, s.cnt.p, 64, hipMemcpyDeviceToHost, c->stream));
@@ -396,18 +530,19 @@ static int devmerger_mark(bwahip_bam_devmerger *m, bwahip_markdup_stats_t *ms)
 	return 0;
 }
 
-// The QC stage over the runs in run order, on the context's stream; awaited at its end (the tables come back)
-static int devmerger_qc(bwahip_bam_devmerger *m, std::vector<uint8_t> *bytes)
+// The QC stage over the resident runs in run order, on the context's stream (a spilled run's records pass in the windows that stage
+// them); qc_stage_finish awaits the stream: the tables come back
+static int devmerger_qc_begin(bwahip_bam_devmerger *m)
 {
 	if (!m->qc) m->qc = qc_stage_new();
 	int rc = qc_stage_begin(m->qc, m->c, (int32_t)m->qc_len.size(), m->qc_len.data(), m->qc_opt, m->n_records);
 	int64_t at = 0;
 	for (auto &kv : m->runs) {
 		const DevRun *r = kv.second;
-		if (!rc) rc = qc_stage_records(m->qc, m->c, r->rec, r->off, r->n_rec, r->len, at);
+		if (!rc && !r->spilled) rc = qc_stage_records(m->qc, m->c, r->rec, r->off, r->n_rec, r->len, at);
 		at += r->n_rec;
 	}
-	return rc ? rc : qc_stage_finish(m->qc, m->c, bytes, m->qc_stats);
+	return rc;
 }
 
 // bai (may be NULL): the index stage after the last piece (bwahip_bam_devmerger_finish_bai); the members do not depend on it
@@ -418,9 +553,10 @@ static int devmerger_finish(bwahip_bam_devmerger *m, int fd, bwahip_devmerge_sta
 	std::lock_guard<std::mutex> lk(m->mu);
 	const double t0 = now_s();
 	if (mark) for (auto &kv : m->runs) if (!kv.second->has_dup) return BWAHIP_EINVAL;   // before a byte is written
-	if (mark) { const int r = devmerger_mark(m, ms); if (r) return r; }
+	const bool spill = m->n_spilled > 0;                           // then the counters and the tables come back after the last window
+	if (mark) { int r = devmerger_mark_begin(m); if (!r && !spill) r = devmerger_mark_end(m, ms); if (r) return r; }
 	std::vector<uint8_t> qc_bytes;                                 // written once the members are
-	if (m->qc_armed) { const int r = devmerger_qc(m, &qc_bytes); if (r) return r; }
+	if (m->qc_armed) { int r = devmerger_qc_begin(m); if (!r && !spill) r = qc_stage_finish(m->qc, m->c, &qc_bytes, m->qc_stats); if (r) return r; }
 	if (bai && !m->bai) m->bai = bai_stage_new();
 	bwahip_ctx *c = m->c;
 	Work &w = m->w;
@@ -428,12 +564,14 @@ static int devmerger_finish(bwahip_bam_devmerger *m, int fd, bwahip_devmerge_sta
 	memset(&s, 0, sizeof s);
 	s.n_records = m->n_records; s.n_runs = (int64_t)m->runs.size(); s.raw_bytes = m->raw_bytes;
 	s.n_blocks = bgzf_blocks(m->raw_bytes);
-	for (auto &kv : m->runs) s.hbm_bytes += kv.second->n_rec ? kv.second->len + 16 * kv.second->n_rec + 8 : 0;
+	for (auto &kv : m->runs) s.hbm_bytes += kv.second->n_rec ? (kv.second->spilled ? 0 : kv.second->len) + 16 * kv.second->n_rec + 8 : 0;
 	if (st) *st = s;
 	const int n = (int)m->n_records;
 	const int64_t total = m->raw_bytes;
 	if (n == 0 || total == 0) {                                    // nothing to write: no member
-		int r = bai ? (n ? BWAHIP_EINVAL : finish_index(m, *bai, 0, nullptr, 0)) : 0;
+		int r = mark && spill ? devmerger_mark_end(m, ms) : 0;         // (spilled runs without a record)
+		if (!r && m->qc_armed && spill) r = qc_stage_finish(m->qc, m->c, &qc_bytes, m->qc_stats);
+		if (!r && bai) r = n ? BWAHIP_EINVAL : finish_index(m, *bai, 0, nullptr, 0);
 		if (!r && m->qc_armed) r = qc_write_fd(m->qc_fd, qc_bytes);
 		s.finish_s = now_s() - t0; if (st) *st = s;
 		return r;
@@ -504,6 +642,133 @@ static int devmerger_finish(bwahip_bam_devmerger *m, int fd, bwahip_devmerge_sta
 	int *mlen_all = nullptr;                                       // the whole stream's member lengths, for the index
 	if (bai && (rc = bai_stage_members(m->bai, s.n_blocks, &mlen_all))) return rc;
 
+	// ---- spilled runs: the windows' cuts, the slices every window stages, the staging buffers
+	SpillWork &sw = m->sw;
+	const int wp = m->window_pieces > 0 ? m->window_pieces : 1;
+	const int n_windows = spill ? (n_pieces + wp - 1) / wp : 0;
+	const size_t NR = (size_t)n_runs;
+	std::vector<DevRun*> runv; std::vector<int64_t> run_id, tmpl_at;   // by index in run order
+	std::vector<int64_t> S, slice_at, base;                        // [window][run]: first position needed (n_windows + 1 rows), the slice's place in the staging buffer, its base
+	std::vector<int> owner;                                        // per window: the run of its first record
+	auto win_first = [&](int w) { return w < n_windows ? piece_first[(size_t)w * wp] : n; };
+	// the positions [lo, hi) of run r window w stages; counted: those it handles (the others are handled by the next window as well)
+	auto slice = [&](int w, size_t r, int64_t *lo, int64_t *hi, int64_t *counted) {
+		*lo = S[(size_t)w * NR + r]; *counted = S[((size_t)w + 1) * NR + r];
+		*hi = *counted + (w + 1 < n_windows && (size_t)owner[(size_t)w + 1] == r ? 1 : 0);
+	};
+	if (spill) {
+		if ((rc = sw.make_events())) return rc;
+		std::vector<uint8_t> flags(NR);
+		{ int64_t t_at = 0; for (auto &kv : m->runs) { runv.push_back(kv.second); run_id.push_back(kv.first); tmpl_at.push_back(t_at); t_at += kv.second->n_tmpl; } }
+		for (size_t r = 0; r < NR; ++r) flags[r] = runv[r]->spilled;
+		for (size_t r = 0; r < NR; ++r) if (flags[r] && runv[r]->n_rec >= 0x7f7f7f7f) return BWAHIP_ECAPACITY;   // the cut table's cells are preset to that value
+		const size_t cells = (size_t)n_windows * (NR + 1);
+		if ((rc = dev_upload(sw.flags, flags.data(), NR, c->stream)) || (rc = sw.cut.ensure(cells * 4)) || (rc = sw.scratch.ensure(8)) ||
+		    (rc = spill_window_cuts(c->stream, n, n_runs, w.first.as<int64_t>(), sw.flags.as<uint8_t>(), idx, w.piece_first.as<int>(), wp, n_windows, sw.cut.as<int>()))) return rc;
+		std::vector<int> cut(cells);
+		HIP_TRY(hipMemcpyAsync(cut.data(), sw.cut.p, cells * 4, hipMemcpyDeviceToHost, c->stream));
+		HIP_TRY(hipStreamSynchronize(c->stream));
+		S.assign(((size_t)n_windows + 1) * NR, 0); owner.assign((size_t)n_windows, 0);
+		for (size_t r = 0; r < NR; ++r) S[(size_t)n_windows * NR + r] = runv[r]->n_rec;
+		for (int wd = n_windows - 1; wd >= 0; --wd) {
+			const int *row = cut.data() + (size_t)wd * (NR + 1);
+			if (row[NR] < 0 || row[NR] >= n_runs) return BWAHIP_EINTERNAL;
+			owner[(size_t)wd] = row[NR];
+			for (size_t r = 0; r < NR; ++r) {                           // a window without a record of the run takes the next window's start
+				const int64_t next = S[((size_t)wd + 1) * NR + r];
+				if (row[r] < 0 || (row[r] != 0x7f7f7f7f && row[r] >= runv[r]->n_rec)) return BWAHIP_EINTERNAL;
+				S[(size_t)wd * NR + r] = flags[r] && row[r] < next ? row[r] : next;
+			}
+		}
+		for (size_t r = 0; r < NR; ++r) if (flags[r] && S[r] != 0) return BWAHIP_EINTERNAL;   // every ordinal lies in or behind window 0
+		// every window's exact staging need, from the runs' offsets
+		slice_at.assign((size_t)n_windows * NR, 0); base.assign((size_t)n_windows * NR, 0);
+		int64_t cap = 0;
+		for (int wd = 0; wd < n_windows; ++wd) {
+			int64_t at = 0;
+			for (size_t r = 0; r < NR; ++r) {
+				if (!flags[r]) continue;
+				int64_t lo, hi, counted;
+				slice(wd, r, &lo, &hi, &counted);
+				slice_at[(size_t)wd * NR + r] = at;
+				if (hi > lo) at += runv[r]->h_off[(size_t)hi] - runv[r]->h_off[(size_t)lo];
+			}
+			if (at > cap) cap = at;
+		}
+		bool files = false;
+		for (size_t r = 0; r < NR; ++r) if (flags[r] && runv[r]->len && !spill_store_mem(m->store, run_id[r])) files = true;
+		for (int k = 0; k < 2; ++k) if ((rc = sw.stage[k].ensure((size_t)(cap ? cap : 1))) || (files && (rc = sw.bounce[k].ensure((size_t)(cap ? cap : 1))))) return rc;
+		for (int wd = 0; wd < n_windows; ++wd)
+			for (size_t r = 0; r < NR; ++r) {
+				if (!flags[r] || !runv[r]->n_rec) continue;
+				const int64_t lo = S[(size_t)wd * NR + r];
+				base[(size_t)wd * NR + r] = (int64_t)(uintptr_t)sw.stage[wd & 1].p + slice_at[(size_t)wd * NR + r] - runv[r]->h_off[(size_t)lo];
+			}
+		if ((rc = dev_upload(sw.base, base.data(), base.size() * 8, c->stream))) return rc;
+		if (bai && (rc = bai_stage_parse_begin(m->bai, c, n, s.n_blocks, bai->n_ref))) return rc;
+		m->n_windows = n_windows; m->upload_ms = 0;
+	}
+	// window wd's slices to its staging buffer, on the copy stream: memory-backed runs from their (pinned) memory, file-backed ones through the bounce buffer
+	auto upload_window = [&](int wd) -> int {
+		const int b = wd & 1;
+		float t = 0;
+		if (wd >= 2) {
+			HIP_TRY(hipStreamWaitEvent(c->stream_copy, sw.ev_used[b], 0));   // window wd - 2 has been read
+			HIP_TRY(hipEventSynchronize(sw.ev_up[b]));                       // and has left the bounce buffer
+			if (hipEventElapsedTime(&t, sw.ev_up0[b], sw.ev_up[b]) == hipSuccess) m->upload_ms += t;
+		}
+		HIP_TRY(hipEventRecord(sw.ev_up0[b], c->stream_copy));
+		for (size_t r = 0; r < NR; ++r) {
+			if (!runv[r]->spilled) continue;
+			int64_t lo, hi, counted;
+			slice(wd, r, &lo, &hi, &counted);
+			if (hi <= lo) continue;
+			const int64_t from = runv[r]->h_off[(size_t)lo], bytes = runv[r]->h_off[(size_t)hi] - from, at = slice_at[(size_t)wd * NR + r];
+			if (!bytes) continue;
+			const uint8_t *src = spill_store_mem(m->store, run_id[r]);
+			if (src) src += from;
+			else {
+				uint8_t *bounce = (uint8_t*)sw.bounce[b].p + at;
+				const int rc2 = spill_store_get(m->store, run_id[r], from, bytes, bounce);
+				if (rc2) return rc2;
+				src = bounce;
+			}
+			HIP_TRY(hipMemcpyAsync(sw.stage[b].as<uint8_t>() + at, src, (size_t)bytes, hipMemcpyHostToDevice, c->stream_copy));
+		}
+		HIP_TRY(hipEventRecord(sw.ev_up[b], c->stream_copy));
+		return 0;
+	};
+	// window wd begins, on the context's stream: its slices are marked and pass the QC stage, its records' source addresses are rebuilt
+	auto window_begin = [&](int wd) -> int {
+		const int b = wd & 1;
+		HIP_TRY(hipStreamWaitEvent(c->stream, sw.ev_up[b], 0));
+		int64_t rec_at = 0;
+		for (size_t r = 0; r < NR; ++r) {
+			DevRun *run = runv[r];
+			const int64_t at0 = rec_at;
+			rec_at += run->n_rec;
+			if (!run->spilled) continue;
+			int64_t lo, hi, counted;
+			slice(wd, r, &lo, &hi, &counted);
+			if (hi <= lo) continue;
+			uint8_t *vrec = reinterpret_cast<uint8_t*>((uintptr_t)base[(size_t)wd * NR + r]);   // + an offset of the run = the record in the staging buffer
+			int rc2;
+			if (mark && ((rc2 = markdup_mark_run(&m->md, c, vrec, run->off + lo, counted - lo, run->len, run->tmpl + lo, tmpl_at[r], run->n_tmpl)) ||
+			             (rc2 = markdup_mark_run(&m->md, c, vrec, run->off + counted, hi - counted, run->len, run->tmpl + counted, tmpl_at[r], run->n_tmpl, sw.scratch.as<unsigned long long>())))) return rc2;
+			if (m->qc_armed && (rc2 = qc_stage_records(m->qc, c, vrec, run->off + lo, counted - lo, run->len, at0 + lo))) return rc2;
+		}
+		const int f = win_first(wd), l = wd + 1 < n_windows ? win_first(wd + 1) : n - 1;
+		return spill_window_addr(c->stream, f, l - f + 1, n_runs, w.first.as<int64_t>(), w.run_off.as<const int64_t*>(), sw.flags.as<uint8_t>(), sw.base.as<int64_t>() + (size_t)wd * NR, idx,
+		                         w.addr.as<const uint8_t*>());
+	};
+	// window wd's last piece is queued: the index parse of the records it holds whole with their predecessors; the staging buffer is free behind it
+	auto window_end = [&](int wd) -> int {
+		int rc2;
+		if (bai && (rc2 = bai_stage_parse(m->bai, c, win_first(wd) + (wd > 0), wd + 1 < n_windows ? win_first(wd + 1) + 1 : n, w.addr.as<const uint8_t*>(), idx, w.out_off.as<int64_t>(), bai->n_ref))) return rc2;
+		HIP_TRY(hipEventRecord(sw.ev_used[wd & 1], c->stream));
+		return 0;
+	};
+
 	// ---- gather and deflate piece k, download and write piece k - 1
 	auto piece_len = [&](int p) { const int64_t lo = (int64_t)p * piece_bytes; return total - lo < piece_bytes ? total - lo : piece_bytes; };
 	for (int k = 0; k <= n_pieces; ++k) {
@@ -514,6 +779,10 @@ static int devmerger_finish(bwahip_bam_devmerger *m, int fd, bwahip_devmerge_sta
 			const int rec_lo = piece_first[(size_t)k];
 			const int rec_hi = k + 1 < n_pieces ? piece_first[(size_t)k + 1] : n - 1;   // inclusive: the record that holds the next cut begins in this piece or at the cut
 			const int n_rec = rec_hi - rec_lo + 1;
+			if (spill && k % wp == 0) {
+				if (k == 0 && (rc = upload_window(0))) return rc;
+				if ((rc = window_begin(k / wp))) return rc;
+			}
 			HIP_TRY(hipEventRecord(w.ev_gather[b], c->stream));
 			hipLaunchKernelGGL(k_gather_window, dim3((unsigned)(((int64_t)n_rec * 16 + 255) / 256)), dim3(256), 0, c->stream, w.addr.as<const uint8_t*>(), idx, w.out_off.as<int64_t>(),
 			                   rec_lo, n_rec, lo, hi, w.in[b].as<uint8_t>());
@@ -523,6 +792,8 @@ static int devmerger_finish(bwahip_bam_devmerger *m, int fd, bwahip_devmerge_sta
 			HIP_TRY(hipEventRecord(w.ev_done[b], c->stream));
 			if (bai)                                                    // the piece's member lengths, before the next piece reuses the deflate stage's buffers: same stream
 				HIP_TRY(hipMemcpyAsync(mlen_all + (int64_t)k * m->piece_blocks, c->bz.mlen.p, (size_t)bgzf_blocks(hi - lo) * 4, hipMemcpyDeviceToDevice, c->stream));
+			if (spill && (k % wp == wp - 1 || k == n_pieces - 1) && (rc = window_end(k / wp))) return rc;
+			if (spill && k % wp == 0 && k / wp + 1 < n_windows && (rc = upload_window(k / wp + 1))) return rc;   // the next window travels while this one is gathered and deflated
 		}
 		if (k >= 1) {
 			const int b = (k - 1) & 1;
@@ -545,7 +816,13 @@ static int devmerger_finish(bwahip_bam_devmerger *m, int fd, bwahip_devmerge_sta
 	{ float ms = 0; if (hipEventElapsedTime(&ms, w.ev_sort[0], w.ev_sort[1]) == hipSuccess) s.sort_ms = ms; }
 	s.hbm_bytes += (int64_t)(w.bytes() + bs.keys[0].cap + bs.keys[1].cap + bs.idx[0].cap + bs.idx[1].cap + bs.hist.cap + bs.hist_base.cap +
 	                         c->bz.slots.cap + c->bz.mlen.cap + c->bz.moff.cap + c->bz.md.cap + c->bz.cnt.cap);
-	rc = bai ? finish_index(m, *bai, n, idx, total) : 0;
+	rc = 0;
+	if (spill) {                                                   // what the resident finish awaits before the order
+		for (int k = 0; k < 2 && k < n_windows; ++k) { float t = 0; if (hipEventElapsedTime(&t, sw.ev_up0[(n_windows - 1 - k) & 1], sw.ev_up[(n_windows - 1 - k) & 1]) == hipSuccess) m->upload_ms += t; }
+		if (mark) rc = devmerger_mark_end(m, ms);
+		if (!rc && m->qc_armed) rc = qc_stage_finish(m->qc, c, &qc_bytes, m->qc_stats);
+	}
+	if (!rc && bai) rc = finish_index(m, *bai, n, idx, total, spill);
 	if (!rc && m->qc_armed) rc = qc_write_fd(m->qc_fd, qc_bytes);
 	s.finish_s = now_s() - t0;
 	if (st) *st = s;
@@ -591,7 +868,8 @@ extern "C" void bwahip_bam_devmerger_close(bwahip_bam_devmerger *m)
 	(void)hipSetDevice(m->c->device);
 	for (hipStream_t q : { m->c->stream_copy, m->c->stream }) if (q) (void)hipStreamSynchronize(q);   // after a failed finish work may still be queued on the buffers
 	for (auto &kv : m->runs) bam_devrun_free(kv.second);
-	m->w.release(); m->md.release();
+	m->w.release(); m->md.release(); m->sw.release(); m->dl_bounce.release();
+	spill_store_free(m->store);
 	bai_stage_free(m->bai); qc_stage_free(m->qc);
 	delete m;
 }

@@ -286,11 +286,12 @@ int markdup_count(MarkdupStage *s, bwahip_ctx *c, int64_t n_tmpl)
 	return launched();
 }
 
-int markdup_mark_run(MarkdupStage *s, bwahip_ctx *c, uint8_t *rec, const int64_t *off, int64_t n_rec, int64_t len, const uint32_t *tmpl, int64_t first_tmpl, int64_t n_tmpl)
+int markdup_mark_run(MarkdupStage *s, bwahip_ctx *c, uint8_t *rec, const int64_t *off, int64_t n_rec, int64_t len, const uint32_t *tmpl, int64_t first_tmpl, int64_t n_tmpl,
+                     unsigned long long *marked_to)
 {
 	if (!n_rec) return 0;
 	hipLaunchKernelGGL(k_md_mark, grid_of(n_rec), dim3(256), 0, c->stream, rec, off, n_rec, len, tmpl, n_tmpl, s->dup.as<uint8_t>() + first_tmpl,
-	                   s->cnt.as<unsigned long long>() + 6, (int*)(s->cnt.as<unsigned long long>() + 7));
+	                   marked_to ? marked_to : s->cnt.as<unsigned long long>() + 6, (int*)(s->cnt.as<unsigned long long>() + 7));
 	return launched();
 }
 

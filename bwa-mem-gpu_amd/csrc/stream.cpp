@@ -265,6 +265,78 @@ struct DevSortedSink : Sink {
 	}
 };
 
+// DevSortedSink for samples whose record bytes outgrow HBM (k_bamspill.hip): no fall-back.  Runs are decided in input order: a run stays
+// resident while bwahip_bam_devmerge_spill_hbm_need of the resident bytes so far -- with one full window of staging reserved as spilled
+// bytes, longest_record 0 -- plus the enabled stages' needs is within the budget; from the first run that is not, every run is held
+// spilled: its record bytes travel device -> host store on the sink's copy stream, its small arrays stay where the drainer put them.
+// A spilled run after which the need of what is held (now with the real spilled bytes and longest record) exceeds the budget ends the call
+// with BWAHIP_ECAPACITY; nothing of the records has been written then (the merger writes at the finish).
+struct SpillSortedSink : DevSortedSink {
+	bwahip_spill_t *sp; bool spilling = false;
+	int64_t spilled_raw = 0, longest = 0, all_rec = 0, all_tmpl = 0; int wp = 0;
+	SpillSortedSink(const char *h, bwahip_sort_dev_t *s, bwahip_spill_t *p) : DevSortedSink(h, s), sp(p) {}
+	int open(bwahip_ctx *const *ctxs, int n_ctx) override
+	{
+		if (sp->host_budget < 0 || sp->window_pieces > 65536) return BWAHIP_EINVAL;
+		int r = DevSortedSink::open(ctxs, n_ctx);
+		if (!r) r = bwahip_bam_devmerger_set_spill(dm, sp);
+		if (!r) r = hipSetDevice(ctx0->device) == hipSuccess && hipStreamCreateWithFlags(&fb_stream, hipStreamNonBlocking) == hipSuccess ? 0 : BWAHIP_ENODEV;
+		if (!r) wp = bam_devmerger_window_pieces(dm);               // the merger resolves the default
+		return r;
+	}
+	int stage_out(bwahip_ctx *c, int out, Item &it, double *t_end) override
+	{
+		const int r = pipe_stage_out_devrun(c, out, &it.run, &it.raw_len, &it.n_rec, &it.gpu_ms, t_end);
+		it.len = it.raw_len; it.holds_set = false;
+		return r ? r : it.run ? 0 : BWAHIP_ECAPACITY;               // not even one batch's run fits beside what is held
+	}
+	int64_t stages_need(int64_t n_rec, int64_t raw, int64_t n_tmpl) const
+	{
+		int64_t need = qc_need;
+		if (host.with_bai) need += bwahip_bam_devmerge_bai_hbm_need(n_rec, bgzf_blocks(raw), host.n_ref, bai_windows);
+		if (markdup) need += bwahip_bam_devmerge_markdup_hbm_need(n_rec, n_tmpl);
+		return need;
+	}
+	int write(int64_t seq_no, Item &it) override
+	{
+		int r = it.run ? 0 : BWAHIP_ECAPACITY;
+		if (!r) {
+			const int64_t n_rec = all_rec + it.n_rec, n_tmpl = all_tmpl + it.run->n_tmpl, raw = held_raw + spilled_raw + it.raw_len;
+			if (!spilling) {
+				const int64_t need = bwahip_bam_devmerge_spill_hbm_need(held_raw + it.raw_len, (int64_t)wp * piece_blocks * 65280, 0, n_rec, seq_no + 1, piece_blocks, wp) + stages_need(n_rec, raw, n_tmpl);
+				if (need > hbm_budget) spilling = true;
+			}
+			if (!spilling) { if (!(r = bam_devmerger_adopt(dm, seq_no, it.run))) held_raw += it.raw_len; }
+			else {
+				int64_t run_longest = 0;
+				if (!(r = bam_devmerger_adopt_spilled(dm, seq_no, it.run, fb_stream, &run_longest))) {
+					spilled_raw += it.raw_len;
+					if (run_longest > longest) longest = run_longest;
+					if (bwahip_bam_devmerge_spill_hbm_need(held_raw, spilled_raw, longest, n_rec, seq_no + 1, piece_blocks, wp) + stages_need(n_rec, raw, n_tmpl) > hbm_budget) {
+						fprintf(stderr, "[bwahip] sorted BAM: what stays in HBM of %lld records exceeds the budget of %lld bytes\n", (long long)n_rec, (long long)hbm_budget);
+						it.run = nullptr;                                   // the merger owns it
+						return BWAHIP_ECAPACITY;
+					}
+				}
+			}
+			if (!r) { all_rec = n_rec; all_tmpl = n_tmpl; it.run = nullptr; host.sort_ms += it.gpu_ms; }
+		}
+		drop(it);
+		return r;
+	}
+	int finish() override
+	{
+		int64_t base = 0;
+		int r = host.write_header(1, &base);
+		if (!r && markdup) r = bwahip_bam_devmerger_finish_markdup(dm, fd, host.bai_fd, base, host.with_bai ? host.n_ref : -1, &sd->dev, nullptr, ms);
+		else if (!r) r = host.with_bai ? bwahip_bam_devmerger_finish_bai(dm, fd, host.bai_fd, base, host.n_ref, &sd->dev, nullptr) : bwahip_bam_devmerger_finish(dm, fd, &sd->dev);
+		if (!r) { sd->n_records = sd->dev.n_records; sd->n_runs = sd->dev.n_runs; sd->merge_s = sd->dev.finish_s; }
+		sd->sort_ms = host.sort_ms;
+		(void)bwahip_bam_devmerger_spill_stats(dm, sp);
+		return r ? r : bwahip_bgzf_eof(fd);
+	}
+};
+
 struct Driver {
 	// reader side
 	std::mutex mu_read;
@@ -589,5 +661,23 @@ extern "C" int bwahip_stream_run_bam_sorted_dev_qc(bwahip_ctx *const *ctxs, int 
 		sink.host.level = 1;
 		if (bai_fd >= 0) { sink.host.with_bai = true; sink.host.bai_fd = bai_fd; }
 	} else { sink.host.with_bai = true; sink.host.bai_fd = bai_fd; }
+	return stream_run(ctxs, n_ctx, opt, pes0, fq1, fq2, out_fd, st, sink);
+}
+
+// The device-merged entry points in one, for samples whose record bytes outgrow HBM: runs that do not fit sd->hbm_budget are held spilled
+// (SpillSortedSink); mark, bai_fd >= 0 and qc != NULL choose the stages.  Never a host fall-back: sd->tmp_dir, mem_budget and level are
+// not looked at
+extern "C" int bwahip_stream_run_bam_sorted_dev_spill(bwahip_ctx *const *ctxs, int n_ctx, const bwahip_opt_t *opt, const bwahip_pestat_t *pes0,
+                                                      const char *fq1, const char *fq2, int out_fd, const char *hdr_line, bwahip_stream_t *st, bwahip_sort_dev_t *sd, bwahip_spill_t *sp,
+                                                      int bai_fd, int mark, bwahip_markdup_stats_t *ms, const bwahip_qc_opt_t *qc, int qc_fd, bwahip_qc_stats_t *qs)
+{
+	if (!sd || !sp) return BWAHIP_EINVAL;
+	if (ms) memset(ms, 0, sizeof *ms);
+	if (qs) memset(qs, 0, sizeof *qs);
+	SpillSortedSink sink(hdr_line, sd, sp);
+	sink.host.level = 1;
+	if (mark) { sink.form = OutForm::BamSortedDup; sink.markdup = true; sink.ms = ms; }
+	if (bai_fd >= 0) { sink.host.with_bai = true; sink.host.bai_fd = bai_fd; }
+	if (qc) { sink.qo = qc; sink.qc_fd = qc_fd; sink.qs = qs; }
 	return stream_run(ctxs, n_ctx, opt, pes0, fq1, fq2, out_fd, st, sink);
 }

@@ -640,6 +640,70 @@ int  bwahip_stream_run_bam_sorted_dev_qc(bwahip_ctx *const *ctxs, int n_ctx, con
                                          int out_fd, const char *hdr_line, bwahip_stream_t *st, bwahip_sort_dev_t *sd, int bai_fd, bwahip_markdup_stats_t *ms,
                                          int markdup, const bwahip_qc_opt_t *qo, int qc_fd, bwahip_qc_stats_t *qs);
 
+/* Runs whose record bytes outgrow HBM (csrc/k_bamspill.hip, csrc/spill_store.cpp).  A device merger armed with
+ * bwahip_bam_devmerger_set_spill may hold a run spilled: keys, offsets, template indices and descriptors in HBM as for any run, the record
+ * bytes in a host-side store -- pinned host memory while host_budget holds, otherwise the whole run in an unlinked file of tmp_dir (its
+ * name is gone before a byte is written).  Every finish brings them back one window of window_pieces pieces at a time, through two
+ * staging buffers: window w + 1 is uploaded on the copy stream while window w is gathered and deflated.  The order, the output offsets,
+ * the piece cuts and the deflate are those of a merger with all runs resident, so for any mix of resident and spilled runs the members,
+ * the index, the QC summary and every count of the stats are the same; only hbm_bytes and the timings differ.  The stages that read
+ * records run per window on the staged slices -- the marking pass (the store stays unmarked: every finish marks again), the QC record
+ * pass, the index parse -- and each record counts once, in the window that holds its first byte or, for the record a window begins
+ * with, in that window; their read-backs come after the last window, so a refusal of the QC stage or the index comes after the members
+ * are written.  The limit of 2^31 - 1 records per merger stands: all keys are sorted at once; a finish over a spilled run of 0x7f7f7f7f
+ * records or more: BWAHIP_ECAPACITY (the cut table's empty cell).
+ * set_spill: before the first add (later, or twice: BWAHIP_EINVAL); host_budget < 0 or window_pieces > 65 536: BWAHIP_EINVAL;
+ * window_pieces <= 0: 8 (with 1 024 blocks a piece, windows of 535 MB).  The out fields are not touched.  host_budget bounds the store's
+ * memory alone.  Beside it a merger that holds a file-backed run pins two bounce buffers of one window each at its finish (what pread
+ * fills before the upload: 1.07 GB at the default shapes, also with host_budget 0), and the stream entry point 64 MiB more for the way
+ * from HBM to a file; choose window_pieces with that in mind where pinned memory is scarce.
+ * add_spilled: bwahip_bam_devmerger_add (tmpl == NULL and desc == NULL) or _add_dup with the run held spilled; the same validation and
+ * the same refusals, which leave merger and store as they were; an unarmed merger: BWAHIP_EINVAL; a run that needs a file while tmp_dir
+ * is NULL or no directory files can be made in: BWAHIP_EIO.  Resident and spilled runs mix freely; run numbers are shared.
+ * spill_stats: the out fields (the in fields are not touched): spilled runs held and the lowest run number among them, the store's
+ * bytes by placement, and of the last finish the windows, the HBM of the staging (two buffers, the cut table) and the time its uploads
+ * took on the copy stream; download_s: the time the record bytes took to reach the store, over all adds.
+ * bwahip_bam_devmerge_spill_hbm_need (no device; -1 for a negative argument, piece_blocks outside 1 .. 4 096 or window_pieces outside
+ * 1 .. 65 536): bwahip_bam_devmerge_hbm_need(resident_raw_bytes, n_records, n_runs, piece_blocks) -- the resident record bytes and all
+ * records' metadata -- and, with the eighth of slack the working buffers grow with,
+ *   staging    2 x min(window_pieces x piece_blocks x 65 280 + 2 x longest_record, spilled_raw_bytes): a window and the two records
+ *              that straddle its ends;
+ *   pieces     326 730 x (P(resident + spilled) - P(resident)), P(b) = min(blocks of b bytes, piece_blocks): the piece buffers the
+ *              resident bytes alone do not count;
+ *   cut table  16 x (n_runs + 1) x blocks of (resident + spilled) bytes: a cut and a slice base per run and window, counted for the most
+ *              windows any shape gives (one per block), so that the need never falls as piece_blocks or window_pieces grows. */
+typedef struct {
+	int64_t host_budget;      /* in: bytes of pinned host memory spilled records may take; a run that would exceed it goes whole
+	                             to an unlinked file in tmp_dir.  0: every spilled run is a file.  < 0: BWAHIP_EINVAL */
+	const char *tmp_dir;      /* in: may be NULL while no run needs a file; unusable when one does: BWAHIP_EIO, merger as before */
+	int window_pieces;        /* in: pieces (of piece_blocks x 65 280 bytes) staged per window, 1 .. 65 536; <= 0: 8 */
+	/* out */
+	int64_t n_spilled_runs, first_spilled_run /* -1: none */, host_bytes, file_bytes, n_windows, window_hbm_bytes;
+	double download_s, upload_ms;
+} bwahip_spill_t;
+int  bwahip_bam_devmerger_set_spill(bwahip_bam_devmerger *m, const bwahip_spill_t *in);
+int  bwahip_bam_devmerger_add_spilled(bwahip_bam_devmerger *m, int64_t run_no, const uint8_t *rec, int64_t len, const uint64_t *keys,
+                                      const int64_t *rec_off, int64_t n_rec, const uint32_t *tmpl, const bwahip_dup_desc_t *desc, int64_t n_tmpl);
+int  bwahip_bam_devmerger_spill_stats(bwahip_bam_devmerger *m, bwahip_spill_t *out);
+int64_t bwahip_bam_devmerge_spill_hbm_need(int64_t resident_raw_bytes, int64_t spilled_raw_bytes, int64_t longest_record,
+                                           int64_t n_records, int64_t n_runs, int piece_blocks, int window_pieces);
+/* The device-merged entry points in one, for samples whose record bytes outgrow HBM: bai_fd >= 0 writes the index, mark != 0 marks
+ * duplicates (ms may be NULL), qc != NULL writes the QC summary to qc_fd (qs may be NULL); with none of them the file is that of
+ * bwahip_stream_run_bam_sorted_dev.  sd: hbm_budget (0: half of the free HBM) and piece_blocks in, fell_back stays 0, tmp_dir, mem_budget
+ * and level are not looked at: there is never a host fall-back.  sp: in as for set_spill, out as from spill_stats.  Runs are decided in
+ * input order: a run stays resident while bwahip_bam_devmerge_spill_hbm_need(resident bytes with it, one window of window_pieces x
+ * piece_blocks x 65 280 bytes reserved as spilled, longest_record 0, all records and runs so far) plus the enabled stages' needs
+ * (_bai_hbm_need, _markdup_hbm_need, bwahip_qc_hbm_need) is within hbm_budget; from the first run that is not, every run is held spilled
+ * (first_spilled_run), its record bytes travelling device -> host store.  The split depends on the input and the budgets alone, not on
+ * n_ctx, and the files do not depend on the split.  When what stays in HBM of the runs held -- the need with the real spilled bytes and
+ * longest record -- exceeds hbm_budget, or a batch's own buffers cannot be allocated: BWAHIP_ECAPACITY, and nothing of the records has
+ * been written. */
+int  bwahip_stream_run_bam_sorted_dev_spill(bwahip_ctx *const *ctxs, int n_ctx, const bwahip_opt_t *opt, const bwahip_pestat_t *pes0,
+                                            const char *fq1, const char *fq2, int out_fd, const char *hdr_line, bwahip_stream_t *st,
+                                            bwahip_sort_dev_t *sd, bwahip_spill_t *sp, int bai_fd /* < 0: none */,
+                                            int mark, bwahip_markdup_stats_t *ms,
+                                            const bwahip_qc_opt_t *qc /* NULL: none */, int qc_fd, bwahip_qc_stats_t *qs);
+
 /* Insert-size statistics (mem_pestat_t[4]: FF, FR, RF, RR; bwamem_pair.c:72) and mate-rescue counters ([0] local alignments
  * run, [1] regions added, [2] most alignments of one pair, [3] pairs that needed any; bwamem_pair.c:137) of the last
  * paired-end batch finalised on the GPU.  Either pointer may be NULL; counters4 receives 4 values. */
