@@ -14,8 +14,9 @@
 
 namespace {
 
-void put32(std::vector<uint8_t> &o, uint32_t v) { for (int k = 0; k < 4; ++k) o.push_back((uint8_t)(v >> (8 * k))); }
-void put64(std::vector<uint8_t> &o, uint64_t v) { for (int k = 0; k < 8; ++k) o.push_back((uint8_t)(v >> (8 * k))); }
+// a word at a time into reserved room: byte-wise push_back took 3.5 or 4.4 ms for a 4.5 MB index, depending on where the linker put the loop
+void put32(std::vector<uint8_t> &o, uint32_t v) { uint8_t b[4]; for (int k = 0; k < 4; ++k) b[k] = (uint8_t)(v >> (8 * k)); o.insert(o.end(), b, b + 4); }
+void put64(std::vector<uint8_t> &o, uint64_t v) { uint8_t b[8]; for (int k = 0; k < 8; ++k) b[k] = (uint8_t)(v >> (8 * k)); o.insert(o.end(), b, b + 8); }
 
 } // namespace
 
@@ -24,6 +25,7 @@ int bai_serialise(const BaiTables &t, std::vector<uint8_t> *out)
 	if (!out || t.n_ref < 0 || t.n_chunks < 0 || (t.n_ref && (!t.meta || !t.lin_off)) || (t.n_chunks && (!t.ckey || !t.cbeg || !t.cend))) return BWAHIP_EINVAL;
 	std::vector<uint8_t> &o = *out;
 	o.clear();
+	o.reserve(16 + 48 * (size_t)t.n_ref + 24 * (size_t)t.n_chunks + (t.n_ref ? 8 * (size_t)t.lin_off[t.n_ref] : 0));   // a bound: every chunk with a bin header of its own
 	o.insert(o.end(), { 'B', 'A', 'I', 1 });
 	put32(o, (uint32_t)t.n_ref);
 	int64_t k = 0;

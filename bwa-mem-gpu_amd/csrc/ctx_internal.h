@@ -301,6 +301,15 @@ int  bam_devmerger_add_dev(bwahip_bam_devmerger *m, int64_t run_no, const uint8_
 // the merger's runs in run-number order, handed to the caller (who frees them); the merger is empty afterwards.  A merger that holds a
 // spilled run is refused (BWAHIP_EINVAL) and keeps its runs: their record bytes are in its store
 int  bam_devmerger_take_runs(bwahip_bam_devmerger *m, std::vector<std::pair<int64_t, DevRun*>> *out);
+// What one finish of a device merger runs beside the members, and where the stages' outputs go: resolved once, by the three
+// bwahip_bam_devmerger_finish* entry points or by a sink of the stream driver.  The QC stage is the merger's armed state
+// (bwahip_bam_devmerger_set_qc), the windowed path follows from its runs: the finish fills both in.
+struct FinishPlan {
+	bool index = false; int bai_fd = -1; int64_t base = 0; int32_t n_ref = 0; bwahip_bai_stats_t *bs = nullptr;   // the .bai of what is written (base: the first member's offset in the file)
+	bool mark = false; bwahip_markdup_stats_t *ms = nullptr;       // duplicates marked before anything is gathered (ms may be null)
+	bool qc = false, spill = false;                                // filled in by the finish
+};
+int  bam_devmerger_finish(bwahip_bam_devmerger *m, int fd, bwahip_devmerge_stats_t *st, FinishPlan plan);
 // k_bai.hip: the index stage of a device merger's finish.  bai_stage_members: room for the lengths of n_blocks members (the caller fills
 // them, on c->stream); bai_stage_run: the index of the n records addr[idx[i]] (sorted order; out_off: their n + 1 offsets in the stream of
 // `total` bytes) as the bytes of a .bai file -- queued on c->stream and awaited; the context's sort buffers (bs.keys / bs.idx) are reused

@@ -19,19 +19,19 @@
 // Two piece inputs and two piece outputs: the gather and the deflate of piece k are queued on the context's stream while the 16-byte
 // total and then the members of piece k - 1 come back on the copy stream and are written.  No kernel here uses LDS or atomics.
 //
-// A marked finish (bwahip_bam_devmerger_finish_markdup) runs the duplicate decision and the marking pass of k_markdup.hip over the runs
-// before the order is made: one bit of a record changes and no key, so everything after it is the unmarked finish.
-//
-// A merger with spilled runs (bwahip_bam_devmerger_set_spill, k_bamspill.hip) keeps those runs' record bytes in a host-side store and
-// stages them one window of pieces at a time: the order, the output offsets, the piece cuts and the deflate are the same, the gather finds
-// a spilled record in the window's staging buffer, and the stages that read records (marking pass, QC record pass, index parse) run per
-// window on the staged slices.  A merger without a spilled run queues exactly what is described above.
-//
-// An armed merger (bwahip_bam_devmerger_set_qc) runs the QC stage of k_qc.hip over the runs after the marking and before the order: it reads
-// the records and changes nothing, so the members are those of the unarmed finish.
+// Beside the members a finish runs the stages its FinishPlan names (ctx_internal.h): duplicate marking (k_markdup.hip: one bit of a record
+// changes and no key), the QC summary (k_qc.hip: it reads and changes nothing), the BAI index (k_bai.hip, after the last piece).  Marking and
+// QC read every record.  That is the records pass: a resident run's records pass before the order is made, one stage after the other over
+// all runs, and each stage is awaited there.  A spilled run (bwahip_bam_devmerger_set_spill, k_bamspill.hip) keeps its record bytes in a
+// host-side store; they are staged one window of pieces at a time (spill_plan.h), the gather finds them in the staging buffer, and the slices
+// pass the stages -- and the index parse -- in their window, so the await is deferred behind the last window.  A merger without a stage
+// and without a spilled run queues exactly what is described above.  Finish::run is the list of steps, each a function of its own: the
+// checks; the records pass over resident runs; the order; the source table and output offsets; the piece cuts; the piece buffers; the window
+// plan, if spilled; the piece loop; the deferred await; the index; the QC file; the stats (an empty merger: the first two, the last four).
 #include "ctx_internal.h"
 #include "bai_tables.h"
 #include "qc_tables.h"
+#include "spill_plan.h"
 #include "spill_store.h"
 #include <errno.h>
 #include <unistd.h>
@@ -209,27 +209,15 @@ struct bwahip_bam_devmerger {
 	std::map<int64_t, DevRun*> runs;                               // by run_no: the order of the concatenation
 	int64_t n_records = 0, raw_bytes = 0;
 	Work w;
-	BaiStage *bai = nullptr;                                       // the index stage's buffers (k_bai.hip), made by the first finish_bai
-	MarkdupStage md;                                               // the marking stage's buffers (k_markdup.hip), grown by the first finish_markdup
-	QcStage *qc = nullptr;                                         // the QC stage's buffers (k_qc.hip), made by the first armed finish
+	BaiStage *bai = nullptr;                                       // the stages' buffers (k_bai.hip, k_markdup.hip, k_qc.hip): each made by the first finish that runs the stage
+	MarkdupStage *md = nullptr;
+	QcStage *qc = nullptr;
 	// spilled runs (bwahip_bam_devmerger_set_spill): the store of their record bytes, the windows' staging
 	HostBuf dl_bounce;                                             // bam_devmerger_adopt_spilled: a file-backed run's bytes on their way from HBM
 	bool spill_armed = false, added = false; int window_pieces = 0; SpillStore *store = nullptr; SpillWork sw;
 	int64_t n_spilled = 0, n_windows = 0; double download_s = 0, upload_ms = 0;
 	bool qc_armed = false; bwahip_qc_opt_t qc_opt = { 14, 1796, 0 }; std::vector<int64_t> qc_len; int qc_fd = -1; bwahip_qc_stats_t *qc_stats = nullptr;
 };
-
-namespace {
-struct BaiArgs { int bai_fd; int64_t base; int32_t n_ref; bwahip_bai_stats_t *bs; };
-// the index of what finish wrote: after the last piece, on the context's stream
-int finish_index(bwahip_bam_devmerger *m, const BaiArgs &a, int n, const unsigned *idx, int64_t total, bool parsed = false)
-{
-	std::vector<uint8_t> bytes;
-	int rc = bai_stage_run(m->bai, m->c, n, m->w.addr.as<const uint8_t*>(), idx, m->w.out_off.as<int64_t>(), total, bgzf_blocks(total), a.base, a.n_ref, &bytes, a.bs, parsed);
-	if (!rc) rc = bai_write_fd(a.bai_fd, bytes);
-	return rc;
-}
-} // namespace
 
 int bam_devrun_make(bwahip_ctx *c, const uint8_t *d_rec, int64_t len, const uint64_t *d_keys, const int64_t *d_rec_off, int64_t n_rec, hipStream_t st, DevRun **out)
 {
@@ -473,13 +461,15 @@ extern "C" int bwahip_bam_devmerger_spill_stats(bwahip_bam_devmerger *m, bwahip_
 	return 0;
 }
 
-// The marked finish's own part, on the context's stream, before the order is made: the runs' descriptors concatenated in run order, the
-// decision, the counts, the marking pass over every resident run's records (devmerger_mark_begin; a spilled run's records are marked in
-// the windows that stage them).  devmerger_mark_end awaits the stream: the counters come back.
-static int devmerger_mark_begin(bwahip_bam_devmerger *m)
+// ---- finish ---------------------------------------------------------------------------------------------------------------------------
+namespace {
+
+// ---- the stages that read records: marking (k_markdup.hip), then QC (k_qc.hip)
+// Marking's own beginning, on the context's stream: the runs' descriptors concatenated in run order, the decision, the counts
+int mark_decide(bwahip_bam_devmerger *m)
 {
 	bwahip_ctx *c = m->c;
-	MarkdupStage &s = m->md;
+	MarkdupStage &s = *m->md;
 	int64_t T = 0;
 	for (auto &kv : m->runs) T += kv.second->n_tmpl;
 	if (T > 0x3fffffffll) return BWAHIP_ECAPACITY;
@@ -496,20 +486,15 @@ static int devmerger_mark_begin(bwahip_bam_devmerger *m)
 	}
 	if ((rc = markdup_decide(&s, c, T))) return rc;
 	HIP_TRY(hipEventRecord(s.ev[1], c->stream));
-	if ((rc = markdup_counters_reset(&s, c)) || (rc = markdup_count(&s, c, T))) return rc;
-	at = 0;
-	for (auto &kv : m->runs) {
-		DevRun *r = kv.second;
-		if (!r->spilled && (rc = markdup_mark_run(&s, c, r->rec, r->off, r->n_rec, r->len, r->tmpl, at, r->n_tmpl))) return rc;
-		at += r->n_tmpl;
-	}
-	return 0;
+	if ((rc = markdup_counters_reset(&s, c))) return rc;
+	return markdup_count(&s, c, T);
 }
 
-static int devmerger_mark_end(bwahip_bam_devmerger *m, bwahip_markdup_stats_t *ms)
+// marking's end: the stream is awaited, the counters come back
+int mark_end(bwahip_bam_devmerger *m, bwahip_markdup_stats_t *ms)
 {
 	bwahip_ctx *c = m->c;
-	MarkdupStage &s = m->md;
+	MarkdupStage &s = *m->md;
 	int64_t run_bytes = 0;
 	for (auto &kv : m->runs) run_bytes += 4 * kv.second->n_rec + 24 * kv.second->n_tmpl;
 	HIP_TRY(hipEventRecord(s.ev[2], c->stream));
@@ -530,186 +515,186 @@ static int devmerger_mark_end(bwahip_bam_devmerger *m, bwahip_markdup_stats_t *m
 	return 0;
 }
 
-// The QC stage over the resident runs in run order, on the context's stream (a spilled run's records pass in the windows that stage
-// them); qc_stage_finish awaits the stream: the tables come back
-static int devmerger_qc_begin(bwahip_bam_devmerger *m)
-{
-	if (!m->qc) m->qc = qc_stage_new();
-	int rc = qc_stage_begin(m->qc, m->c, (int32_t)m->qc_len.size(), m->qc_len.data(), m->qc_opt, m->n_records);
-	int64_t at = 0;
-	for (auto &kv : m->runs) {
-		const DevRun *r = kv.second;
-		if (!rc && !r->spilled) rc = qc_stage_records(m->qc, m->c, r->rec, r->off, r->n_rec, r->len, at);
-		at += r->n_rec;
-	}
-	return rc;
-}
+enum { RS_MARK = 1, RS_QC = 2 };                                  // the stages that read every record, in the order they run
 
-// bai (may be NULL): the index stage after the last piece (bwahip_bam_devmerger_finish_bai); the members do not depend on it
-// mark: the runs are marked first (bwahip_bam_devmerger_finish_markdup; ms may be null)
-static int devmerger_finish(bwahip_bam_devmerger *m, int fd, bwahip_devmerge_stats_t *st, const BaiArgs *bai, bool mark = false, bwahip_markdup_stats_t *ms = nullptr)
-{
-	if (!m) return BWAHIP_EINVAL;
-	std::lock_guard<std::mutex> lk(m->mu);
-	const double t0 = now_s();
-	if (mark) for (auto &kv : m->runs) if (!kv.second->has_dup) return BWAHIP_EINVAL;   // before a byte is written
-	const bool spill = m->n_spilled > 0;                           // then the counters and the tables come back after the last window
-	if (mark) { int r = devmerger_mark_begin(m); if (!r && !spill) r = devmerger_mark_end(m, ms); if (r) return r; }
-	std::vector<uint8_t> qc_bytes;                                 // written once the members are
-	if (m->qc_armed) { int r = devmerger_qc_begin(m); if (!r && !spill) r = qc_stage_finish(m->qc, m->c, &qc_bytes, m->qc_stats); if (r) return r; }
-	if (bai && !m->bai) m->bai = bai_stage_new();
-	bwahip_ctx *c = m->c;
-	Work &w = m->w;
+// One finish: the merger, the plan, the locals the steps hand on, and the steps themselves -- run() at the end is their list
+struct Finish {
+	bwahip_bam_devmerger *const m; FinishPlan plan; const int fd; const double t0 = now_s();
+	bwahip_ctx *const c = m->c; Work &w = m->w; SpillWork &sw = m->sw;
 	bwahip_devmerge_stats_t s;
-	memset(&s, 0, sizeof s);
-	s.n_records = m->n_records; s.n_runs = (int64_t)m->runs.size(); s.raw_bytes = m->raw_bytes;
-	s.n_blocks = bgzf_blocks(m->raw_bytes);
-	for (auto &kv : m->runs) s.hbm_bytes += kv.second->n_rec ? (kv.second->spilled ? 0 : kv.second->len) + 16 * kv.second->n_rec + 8 : 0;
-	if (st) *st = s;
-	const int n = (int)m->n_records;
-	const int64_t total = m->raw_bytes;
-	if (n == 0 || total == 0) {                                    // nothing to write: no member
-		int r = mark && spill ? devmerger_mark_end(m, ms) : 0;         // (spilled runs without a record)
-		if (!r && m->qc_armed && spill) r = qc_stage_finish(m->qc, m->c, &qc_bytes, m->qc_stats);
-		if (!r && bai) r = n ? BWAHIP_EINVAL : finish_index(m, *bai, 0, nullptr, 0);
-		if (!r && m->qc_armed) r = qc_write_fd(m->qc_fd, qc_bytes);
-		s.finish_s = now_s() - t0; if (st) *st = s;
-		return r;
-	}
-	HIP_TRY(hipSetDevice(c->device));
-	int rc;
-	if ((rc = w.make_events())) return rc;
-	BamSort &bs = c->bs;
-	const int n_runs = (int)m->runs.size();
-
-	// ---- the order
-	if ((rc = bs.keys[0].ensure((size_t)n * 8)) || (rc = bs.keys[1].ensure((size_t)n * 8)) || (rc = bs.idx[0].ensure((size_t)n * 4)) || (rc = bs.idx[1].ensure((size_t)n * 4))) return rc;
-	std::vector<int64_t> first((size_t)n_runs + 1), run_len((size_t)n_runs);
-	std::vector<const uint8_t*> run_rec((size_t)n_runs);
-	std::vector<const int64_t*> run_off((size_t)n_runs);
-	HIP_TRY(hipEventRecord(w.ev_sort[0], c->stream));
+	int n = 0, n_runs = 0; int64_t total = 0;                      // records, runs, bytes of the sorted stream
+	std::vector<int64_t> first, run_len;                           // per run, for k_src_table: the first ordinal (n_runs + 1 entries), the bytes
+	std::vector<const uint8_t*> run_rec; std::vector<const int64_t*> run_off;
+	const unsigned *idx = nullptr;                                 // the order: the ordinal at every sorted place
+	int64_t piece_bytes = 0; int n_pieces = 0; std::vector<int> piece_first;
+	int *mlen_all = nullptr;                                       // the whole stream's member lengths, for the index
+	std::vector<uint8_t> qc_bytes;                                 // written once the members are
+	// spilled runs: the window plan; by index in run order the run, its number, its first ordinal and template; [window][run] the slices' bases
+	SpillPlan sp; int wp = 1; bool parsed = false;                 // parsed: the index parse ran window by window
+	std::vector<DevRun*> runv; std::vector<int64_t> run_id, rec_at, tmpl_at, base; std::vector<uint8_t> flags;
+	Finish(bwahip_bam_devmerger *m_, const FinishPlan &p, int fd_) : m(m_), plan(p), fd(fd_) { plan.qc = m->qc_armed; plan.spill = m->n_spilled > 0; }
+	int stages() const { return (plan.mark ? RS_MARK : 0) | (plan.qc ? RS_QC : 0); }
+	int64_t piece_len(int p) const { const int64_t lo = (int64_t)p * piece_bytes; return total - lo < piece_bytes ? total - lo : piece_bytes; }
+	// The records pass: positions [lo, hi) of run r through the stages `which`, on the context's stream.  rec + r->off[i] is record i: rec is the
+	// run's bytes, or the base of a staged slice.  [lo, counted) are counted; a record in [counted, hi) -- the next window stages it again -- is
+	// marked too, into a counter nobody reads, and passes no other stage.  ord0 / tmpl0: the run's first record and template among all runs'
+	int records_pass(int which, const DevRun *r, uint8_t *rec, int64_t lo, int64_t counted, int64_t hi, int64_t ord0, int64_t tmpl0)
 	{
-		int64_t at = 0; int k = 0;
+		int rc;
+		if (which & RS_MARK) {
+			if ((rc = markdup_mark_run(m->md, c, rec, r->off + lo, counted - lo, r->len, r->tmpl + lo, tmpl0, r->n_tmpl))) return rc;
+			if (hi > counted && (rc = markdup_mark_run(m->md, c, rec, r->off + counted, hi - counted, r->len, r->tmpl + counted, tmpl0, r->n_tmpl, sw.scratch.as<unsigned long long>()))) return rc;
+		}
+		return which & RS_QC ? qc_stage_records(m->qc, c, rec, r->off + lo, counted - lo, r->len, ord0 + lo) : 0;
+	}
+	// The records pass is over for the stages `which`: each awaits the stream, the counters and the tables come back.  Without a spilled run that is
+	// before the order, stage by stage (resident_pass); with one, after the last window (tail)
+	int records_done(int which)
+	{
+		int rc = which & RS_MARK ? mark_end(m, plan.ms) : 0;
+		if (!rc && (which & RS_QC)) rc = qc_stage_finish(m->qc, c, &qc_bytes, m->qc_stats);
+		return rc;
+	}
+	int checks()
+	{
+		if (plan.mark) for (auto &kv : m->runs) if (!kv.second->has_dup) return BWAHIP_EINVAL;   // before a byte is written
+		if (plan.mark && !m->md) m->md = new MarkdupStage;
+		if (plan.qc && !m->qc) m->qc = qc_stage_new();
+		if (plan.index && !m->bai) m->bai = bai_stage_new();
+		memset(&s, 0, sizeof s);
+		s.n_records = m->n_records; s.n_runs = (int64_t)m->runs.size(); s.raw_bytes = m->raw_bytes; s.n_blocks = bgzf_blocks(m->raw_bytes);
+		for (auto &kv : m->runs) s.hbm_bytes += kv.second->n_rec ? (kv.second->spilled ? 0 : kv.second->len) + 16 * kv.second->n_rec + 8 : 0;
+		n = (int)m->n_records; n_runs = (int)m->runs.size(); total = m->raw_bytes;
+		return 0;
+	}
+	// the resident runs' records pass, one stage after the other over all runs (a spilled run's records pass in the windows that stage them)
+	int resident_pass()
+	{
+		for (int stage : { RS_MARK, RS_QC }) {
+			if (!(stages() & stage)) continue;
+			int rc = stage == RS_MARK ? mark_decide(m) : qc_stage_begin(m->qc, c, (int32_t)m->qc_len.size(), m->qc_len.data(), m->qc_opt, m->n_records);
+			int64_t ord = 0, tmpl = 0;
+			for (auto &kv : m->runs) {
+				const DevRun *r = kv.second;
+				if (!rc && !r->spilled) rc = records_pass(stage, r, r->rec, 0, r->n_rec, r->n_rec, ord, tmpl);
+				ord += r->n_rec; tmpl += r->n_tmpl;
+			}
+			if (!rc && !plan.spill) rc = records_done(stage);
+			if (rc) return rc;
+		}
+		return 0;
+	}
+	// the order: the runs' keys in run order through the stable radix sort, with the ordinals 0 .. n - 1
+	int order()
+	{
+		BamSort &bs = c->bs;
+		HIP_TRY(hipSetDevice(c->device));
+		int rc;
+		if ((rc = w.make_events())) return rc;
+		if ((rc = bs.keys[0].ensure((size_t)n * 8)) || (rc = bs.keys[1].ensure((size_t)n * 8)) || (rc = bs.idx[0].ensure((size_t)n * 4)) || (rc = bs.idx[1].ensure((size_t)n * 4))) return rc;
+		HIP_TRY(hipEventRecord(w.ev_sort[0], c->stream));
+		int64_t at = 0;
 		for (auto &kv : m->runs) {
 			const DevRun *r = kv.second;
-			first[(size_t)k] = at; run_rec[(size_t)k] = r->rec; run_off[(size_t)k] = r->off; run_len[(size_t)k] = r->len;
+			first.push_back(at); run_rec.push_back(r->rec); run_off.push_back(r->off); run_len.push_back(r->len);
 			if (r->n_rec) HIP_TRY(hipMemcpyAsync(bs.keys[0].as<uint64_t>() + at, r->keys, (size_t)r->n_rec * 8, hipMemcpyDeviceToDevice, c->stream));
-			at += r->n_rec; ++k;
+			at += r->n_rec;
 		}
-		first[(size_t)n_runs] = at;
+		first.push_back(at);
+		int cur = 0;
+		if ((rc = bam_sort_iota(bs.idx[0].as<unsigned>(), n, c->stream)) || (rc = bam_sort_radix(c, n, 64, &cur))) return rc;
+		HIP_TRY(hipEventRecord(w.ev_sort[1], c->stream));
+		idx = bs.idx[cur].as<unsigned>();
+		return 0;
 	}
-	int cur = 0;
-	if ((rc = bam_sort_iota(bs.idx[0].as<unsigned>(), n, c->stream)) || (rc = bam_sort_radix(c, n, 64, &cur))) return rc;
-	HIP_TRY(hipEventRecord(w.ev_sort[1], c->stream));
-	const unsigned *idx = bs.idx[cur].as<unsigned>();
-
-	// ---- source table, output offsets
-	if ((rc = dev_upload(w.first, first.data(), first.size() * 8, c->stream)) || (rc = dev_upload(w.run_rec, run_rec.data(), run_rec.size() * 8, c->stream)) ||
-	    (rc = dev_upload(w.run_off, run_off.data(), run_off.size() * 8, c->stream)) || (rc = dev_upload(w.run_len, run_len.data(), run_len.size() * 8, c->stream))) return rc;
-	if ((rc = w.addr.ensure((size_t)n * 8)) || (rc = w.len.ensure((size_t)n * 4)) || (rc = w.len_sorted.ensure((size_t)n * 4)) || (rc = w.out_off.ensure(((size_t)n + 1) * 8)) || (rc = w.err.ensure(4))) return rc;
-	HIP_TRY(hipMemsetAsync(w.err.p, 0, 4, c->stream));
-	const int grid_n = (n + 255) / 256;
-	hipLaunchKernelGGL(k_src_table, dim3(grid_n), dim3(256), 0, c->stream, n, n_runs, w.first.as<int64_t>(), w.run_rec.as<const uint8_t*>(), w.run_off.as<const int64_t*>(), w.run_len.as<int64_t>(),
-	                   w.addr.as<const uint8_t*>(), w.len.as<int>(), w.err.as<int>());
-	if ((rc = launched())) return rc;
-	hipLaunchKernelGGL(k_sorted_len, dim3(grid_n), dim3(256), 0, c->stream, idx, w.len.as<int>(), n, w.len_sorted.as<int>());
-	if ((rc = launched()) || (rc = launch_scan(w.len_sorted.as<int>(), w.out_off.as<int64_t>(), n, c->d_scan, c->stream))) return rc;
-
-	// ---- pieces
-	const int64_t piece_bytes = (int64_t)m->piece_blocks * BLOCK_IN;
-	const int64_t n_pieces64 = (total + piece_bytes - 1) / piece_bytes;
-	if (n_pieces64 > 0x7fffffffll / 2) return BWAHIP_ECAPACITY;
-	const int n_pieces = (int)n_pieces64;
-	if ((rc = w.piece_first.ensure((size_t)n_pieces * 4))) return rc;
-	hipLaunchKernelGGL(k_piece_first, dim3((n_pieces + 255) / 256), dim3(256), 0, c->stream, w.out_off.as<int64_t>(), n, piece_bytes, n_pieces, w.piece_first.as<int>());
-	if ((rc = launched())) return rc;
-	std::vector<int> piece_first((size_t)n_pieces);
-	int64_t sum = 0; int err = 0;
-	HIP_TRY(hipMemcpyAsync(piece_first.data(), w.piece_first.p, (size_t)n_pieces * 4, hipMemcpyDeviceToHost, c->stream));
-	HIP_TRY(hipMemcpyAsync(&sum, w.out_off.as<int64_t>() + n, 8, hipMemcpyDeviceToHost, c->stream));
-	HIP_TRY(hipMemcpyAsync(&err, w.err.p, 4, hipMemcpyDeviceToHost, c->stream));
-	HIP_TRY(hipStreamSynchronize(c->stream));
-	if (err || sum != total) { fprintf(stderr, "[bwahip] sorted BAM: the runs' offsets give %lld bytes, the runs hold %lld\n", (long long)sum, (long long)total); return BWAHIP_EINTERNAL; }
-	for (int p = 0; p < n_pieces; ++p) if (piece_first[(size_t)p] < 0 || piece_first[(size_t)p] >= n || (p && piece_first[(size_t)p] < piece_first[(size_t)p - 1])) return BWAHIP_EINTERNAL;
-
-	// ---- the piece buffers, once: input, and the bound of the members ("input + 31 per block", as bgzf_deflate grows its output to)
-	const int64_t in_cap = total < piece_bytes ? total : piece_bytes;
-	const int64_t out_cap = in_cap + bgzf_blocks(in_cap) * 31 + 64;
-	for (int k = 0; k < 2; ++k)
-		if ((rc = w.in[k].ensure((size_t)in_cap)) || (rc = w.out[k].ensure((size_t)out_cap)) || (rc = w.tot[k].ensure(16)) || (rc = w.h_out[k].ensure((size_t)out_cap))) return rc;
-	if ((rc = w.h_tot.ensure(32))) return rc;
-	int64_t *h_tot = (int64_t*)w.h_tot.p;
-	int *mlen_all = nullptr;                                       // the whole stream's member lengths, for the index
-	if (bai && (rc = bai_stage_members(m->bai, s.n_blocks, &mlen_all))) return rc;
-
-	// ---- spilled runs: the windows' cuts, the slices every window stages, the staging buffers
-	SpillWork &sw = m->sw;
-	const int wp = m->window_pieces > 0 ? m->window_pieces : 1;
-	const int n_windows = spill ? (n_pieces + wp - 1) / wp : 0;
-	const size_t NR = (size_t)n_runs;
-	std::vector<DevRun*> runv; std::vector<int64_t> run_id, tmpl_at;   // by index in run order
-	std::vector<int64_t> S, slice_at, base;                        // [window][run]: first position needed (n_windows + 1 rows), the slice's place in the staging buffer, its base
-	std::vector<int> owner;                                        // per window: the run of its first record
-	auto win_first = [&](int w) { return w < n_windows ? piece_first[(size_t)w * wp] : n; };
-	// the positions [lo, hi) of run r window w stages; counted: those it handles (the others are handled by the next window as well)
-	auto slice = [&](int w, size_t r, int64_t *lo, int64_t *hi, int64_t *counted) {
-		*lo = S[(size_t)w * NR + r]; *counted = S[((size_t)w + 1) * NR + r];
-		*hi = *counted + (w + 1 < n_windows && (size_t)owner[(size_t)w + 1] == r ? 1 : 0);
-	};
-	if (spill) {
+	// the source table (per ordinal the record's address and length) and the records' offsets in the sorted stream
+	int offsets()
+	{
+		int rc;
+		if ((rc = dev_upload(w.first, first.data(), first.size() * 8, c->stream)) || (rc = dev_upload(w.run_rec, run_rec.data(), run_rec.size() * 8, c->stream)) ||
+		    (rc = dev_upload(w.run_off, run_off.data(), run_off.size() * 8, c->stream)) || (rc = dev_upload(w.run_len, run_len.data(), run_len.size() * 8, c->stream))) return rc;
+		if ((rc = w.addr.ensure((size_t)n * 8)) || (rc = w.len.ensure((size_t)n * 4)) || (rc = w.len_sorted.ensure((size_t)n * 4)) || (rc = w.out_off.ensure(((size_t)n + 1) * 8)) || (rc = w.err.ensure(4))) return rc;
+		HIP_TRY(hipMemsetAsync(w.err.p, 0, 4, c->stream));
+		const int grid_n = (n + 255) / 256;
+		hipLaunchKernelGGL(k_src_table, dim3(grid_n), dim3(256), 0, c->stream, n, n_runs, w.first.as<int64_t>(), w.run_rec.as<const uint8_t*>(), w.run_off.as<const int64_t*>(), w.run_len.as<int64_t>(),
+		                   w.addr.as<const uint8_t*>(), w.len.as<int>(), w.err.as<int>());
+		if ((rc = launched())) return rc;
+		hipLaunchKernelGGL(k_sorted_len, dim3(grid_n), dim3(256), 0, c->stream, idx, w.len.as<int>(), n, w.len_sorted.as<int>());
+		if ((rc = launched())) return rc;
+		return launch_scan(w.len_sorted.as<int>(), w.out_off.as<int64_t>(), n, c->d_scan, c->stream);
+	}
+	// the piece cuts: the record that holds every cut, read back with the stream's length and the source table's error word, and verified
+	int cuts()
+	{
+		piece_bytes = (int64_t)m->piece_blocks * BLOCK_IN;
+		const int64_t n_pieces64 = (total + piece_bytes - 1) / piece_bytes;
+		if (n_pieces64 > 0x7fffffffll / 2) return BWAHIP_ECAPACITY;
+		n_pieces = (int)n_pieces64;
+		int rc;
+		if ((rc = w.piece_first.ensure((size_t)n_pieces * 4))) return rc;
+		hipLaunchKernelGGL(k_piece_first, dim3((n_pieces + 255) / 256), dim3(256), 0, c->stream, w.out_off.as<int64_t>(), n, piece_bytes, n_pieces, w.piece_first.as<int>());
+		if ((rc = launched())) return rc;
+		piece_first.resize((size_t)n_pieces);
+		int64_t sum = 0; int err = 0;
+		HIP_TRY(hipMemcpyAsync(piece_first.data(), w.piece_first.p, (size_t)n_pieces * 4, hipMemcpyDeviceToHost, c->stream));
+		HIP_TRY(hipMemcpyAsync(&sum, w.out_off.as<int64_t>() + n, 8, hipMemcpyDeviceToHost, c->stream));
+		HIP_TRY(hipMemcpyAsync(&err, w.err.p, 4, hipMemcpyDeviceToHost, c->stream));
+		HIP_TRY(hipStreamSynchronize(c->stream));
+		if (err || sum != total) { fprintf(stderr, "[bwahip] sorted BAM: the runs' offsets give %lld bytes, the runs hold %lld\n", (long long)sum, (long long)total); return BWAHIP_EINTERNAL; }
+		for (int p = 0; p < n_pieces; ++p) if (piece_first[(size_t)p] < 0 || piece_first[(size_t)p] >= n || (p && piece_first[(size_t)p] < piece_first[(size_t)p - 1])) return BWAHIP_EINTERNAL;
+		return 0;
+	}
+	// the piece buffers, once: input, and the bound of the members ("input + 31 per block", as bgzf_deflate grows its output to)
+	int buffers()
+	{
+		const int64_t in_cap = total < piece_bytes ? total : piece_bytes, out_cap = in_cap + bgzf_blocks(in_cap) * 31 + 64;
+		int rc;
+		for (int k = 0; k < 2; ++k)
+			if ((rc = w.in[k].ensure((size_t)in_cap)) || (rc = w.out[k].ensure((size_t)out_cap)) || (rc = w.tot[k].ensure(16)) || (rc = w.h_out[k].ensure((size_t)out_cap))) return rc;
+		if ((rc = w.h_tot.ensure(32))) return rc;
+		return plan.index ? bai_stage_members(m->bai, s.n_blocks, &mlen_all) : 0;
+	}
+	// spilled runs: the windows' cuts, the plan of the slices every window stages, the staging buffers and the slices' bases
+	int windows()
+	{
+		const size_t NR = (size_t)n_runs;
+		int rc;
 		if ((rc = sw.make_events())) return rc;
-		std::vector<uint8_t> flags(NR);
-		{ int64_t t_at = 0; for (auto &kv : m->runs) { runv.push_back(kv.second); run_id.push_back(kv.first); tmpl_at.push_back(t_at); t_at += kv.second->n_tmpl; } }
-		for (size_t r = 0; r < NR; ++r) flags[r] = runv[r]->spilled;
-		for (size_t r = 0; r < NR; ++r) if (flags[r] && runv[r]->n_rec >= 0x7f7f7f7f) return BWAHIP_ECAPACITY;   // the cut table's cells are preset to that value
-		const size_t cells = (size_t)n_windows * (NR + 1);
+		std::vector<SpillRun> runs;
+		int64_t ord = 0, tmpl = 0;
+		for (auto &kv : m->runs) {
+			DevRun *r = kv.second;
+			runv.push_back(r); run_id.push_back(kv.first); rec_at.push_back(ord); tmpl_at.push_back(tmpl); flags.push_back(r->spilled);
+			runs.push_back({ r->spilled, r->n_rec, r->h_off.data() });
+			ord += r->n_rec; tmpl += r->n_tmpl;
+		}
+		wp = m->window_pieces > 0 ? m->window_pieces : 1;
+		if ((rc = spill_plan_begin(&sp, runs, n_pieces, wp, piece_first.data(), n))) return rc;
+		const size_t cells = (size_t)sp.n_windows * (NR + 1);
 		if ((rc = dev_upload(sw.flags, flags.data(), NR, c->stream)) || (rc = sw.cut.ensure(cells * 4)) || (rc = sw.scratch.ensure(8)) ||
-		    (rc = spill_window_cuts(c->stream, n, n_runs, w.first.as<int64_t>(), sw.flags.as<uint8_t>(), idx, w.piece_first.as<int>(), wp, n_windows, sw.cut.as<int>()))) return rc;
+		    (rc = spill_window_cuts(c->stream, n, n_runs, w.first.as<int64_t>(), sw.flags.as<uint8_t>(), idx, w.piece_first.as<int>(), wp, sp.n_windows, sw.cut.as<int>()))) return rc;
 		std::vector<int> cut(cells);
 		HIP_TRY(hipMemcpyAsync(cut.data(), sw.cut.p, cells * 4, hipMemcpyDeviceToHost, c->stream));
 		HIP_TRY(hipStreamSynchronize(c->stream));
-		S.assign(((size_t)n_windows + 1) * NR, 0); owner.assign((size_t)n_windows, 0);
-		for (size_t r = 0; r < NR; ++r) S[(size_t)n_windows * NR + r] = runv[r]->n_rec;
-		for (int wd = n_windows - 1; wd >= 0; --wd) {
-			const int *row = cut.data() + (size_t)wd * (NR + 1);
-			if (row[NR] < 0 || row[NR] >= n_runs) return BWAHIP_EINTERNAL;
-			owner[(size_t)wd] = row[NR];
-			for (size_t r = 0; r < NR; ++r) {                           // a window without a record of the run takes the next window's start
-				const int64_t next = S[((size_t)wd + 1) * NR + r];
-				if (row[r] < 0 || (row[r] != 0x7f7f7f7f && row[r] >= runv[r]->n_rec)) return BWAHIP_EINTERNAL;
-				S[(size_t)wd * NR + r] = flags[r] && row[r] < next ? row[r] : next;
-			}
-		}
-		for (size_t r = 0; r < NR; ++r) if (flags[r] && S[r] != 0) return BWAHIP_EINTERNAL;   // every ordinal lies in or behind window 0
-		// every window's exact staging need, from the runs' offsets
-		slice_at.assign((size_t)n_windows * NR, 0); base.assign((size_t)n_windows * NR, 0);
-		int64_t cap = 0;
-		for (int wd = 0; wd < n_windows; ++wd) {
-			int64_t at = 0;
-			for (size_t r = 0; r < NR; ++r) {
-				if (!flags[r]) continue;
-				int64_t lo, hi, counted;
-				slice(wd, r, &lo, &hi, &counted);
-				slice_at[(size_t)wd * NR + r] = at;
-				if (hi > lo) at += runv[r]->h_off[(size_t)hi] - runv[r]->h_off[(size_t)lo];
-			}
-			if (at > cap) cap = at;
-		}
+		if ((rc = spill_plan_cuts(&sp, cut.data()))) return rc;
 		bool files = false;
 		for (size_t r = 0; r < NR; ++r) if (flags[r] && runv[r]->len && !spill_store_mem(m->store, run_id[r])) files = true;
-		for (int k = 0; k < 2; ++k) if ((rc = sw.stage[k].ensure((size_t)(cap ? cap : 1))) || (files && (rc = sw.bounce[k].ensure((size_t)(cap ? cap : 1))))) return rc;
-		for (int wd = 0; wd < n_windows; ++wd)
+		for (int k = 0; k < 2; ++k) if ((rc = sw.stage[k].ensure((size_t)(sp.cap ? sp.cap : 1))) || (files && (rc = sw.bounce[k].ensure((size_t)(sp.cap ? sp.cap : 1))))) return rc;
+		base.assign((size_t)sp.n_windows * NR, 0);                   // + an offset of the run = the record in the staging buffer
+		for (int wd = 0; wd < sp.n_windows; ++wd)
 			for (size_t r = 0; r < NR; ++r) {
 				if (!flags[r] || !runv[r]->n_rec) continue;
-				const int64_t lo = S[(size_t)wd * NR + r];
-				base[(size_t)wd * NR + r] = (int64_t)(uintptr_t)sw.stage[wd & 1].p + slice_at[(size_t)wd * NR + r] - runv[r]->h_off[(size_t)lo];
+				const int64_t lo = sp.S[(size_t)wd * NR + r];
+				base[(size_t)wd * NR + r] = (int64_t)(uintptr_t)sw.stage[wd & 1].p + sp.slice_at[(size_t)wd * NR + r] - runv[r]->h_off[(size_t)lo];
 			}
 		if ((rc = dev_upload(sw.base, base.data(), base.size() * 8, c->stream))) return rc;
-		if (bai && (rc = bai_stage_parse_begin(m->bai, c, n, s.n_blocks, bai->n_ref))) return rc;
-		m->n_windows = n_windows; m->upload_ms = 0;
+		if (plan.index) { if ((rc = bai_stage_parse_begin(m->bai, c, n, s.n_blocks, plan.n_ref))) return rc; parsed = true; }
+		m->n_windows = sp.n_windows; m->upload_ms = 0;
+		return 0;
 	}
 	// window wd's slices to its staging buffer, on the copy stream: memory-backed runs from their (pinned) memory, file-backed ones through the bounce buffer
-	auto upload_window = [&](int wd) -> int {
+	int window_upload(int wd)
+	{
 		const int b = wd & 1;
 		float t = 0;
 		if (wd >= 2) {
@@ -718,125 +703,154 @@ static int devmerger_finish(bwahip_bam_devmerger *m, int fd, bwahip_devmerge_sta
 			if (hipEventElapsedTime(&t, sw.ev_up0[b], sw.ev_up[b]) == hipSuccess) m->upload_ms += t;
 		}
 		HIP_TRY(hipEventRecord(sw.ev_up0[b], c->stream_copy));
-		for (size_t r = 0; r < NR; ++r) {
-			if (!runv[r]->spilled) continue;
-			int64_t lo, hi, counted;
-			slice(wd, r, &lo, &hi, &counted);
-			if (hi <= lo) continue;
-			const int64_t from = runv[r]->h_off[(size_t)lo], bytes = runv[r]->h_off[(size_t)hi] - from, at = slice_at[(size_t)wd * NR + r];
+		for (size_t r = 0; r < runv.size(); ++r) {
+			const int64_t bytes = sp.slice_bytes(wd, r), at = sp.slice_at[(size_t)wd * runv.size() + r];
 			if (!bytes) continue;
+			const int64_t from = runv[r]->h_off[(size_t)sp.S[(size_t)wd * runv.size() + r]];
 			const uint8_t *src = spill_store_mem(m->store, run_id[r]);
 			if (src) src += from;
 			else {
 				uint8_t *bounce = (uint8_t*)sw.bounce[b].p + at;
-				const int rc2 = spill_store_get(m->store, run_id[r], from, bytes, bounce);
-				if (rc2) return rc2;
+				const int rc = spill_store_get(m->store, run_id[r], from, bytes, bounce);
+				if (rc) return rc;
 				src = bounce;
 			}
 			HIP_TRY(hipMemcpyAsync(sw.stage[b].as<uint8_t>() + at, src, (size_t)bytes, hipMemcpyHostToDevice, c->stream_copy));
 		}
 		HIP_TRY(hipEventRecord(sw.ev_up[b], c->stream_copy));
 		return 0;
-	};
-	// window wd begins, on the context's stream: its slices are marked and pass the QC stage, its records' source addresses are rebuilt
-	auto window_begin = [&](int wd) -> int {
-		const int b = wd & 1;
-		HIP_TRY(hipStreamWaitEvent(c->stream, sw.ev_up[b], 0));
-		int64_t rec_at = 0;
+	}
+	// window wd begins, on the context's stream: its slices pass the record-reading stages, its records' source addresses are rebuilt
+	int window_begin(int wd)
+	{
+		const size_t NR = runv.size();
+		HIP_TRY(hipStreamWaitEvent(c->stream, sw.ev_up[wd & 1], 0));
 		for (size_t r = 0; r < NR; ++r) {
-			DevRun *run = runv[r];
-			const int64_t at0 = rec_at;
-			rec_at += run->n_rec;
-			if (!run->spilled) continue;
-			int64_t lo, hi, counted;
-			slice(wd, r, &lo, &hi, &counted);
-			if (hi <= lo) continue;
-			uint8_t *vrec = reinterpret_cast<uint8_t*>((uintptr_t)base[(size_t)wd * NR + r]);   // + an offset of the run = the record in the staging buffer
-			int rc2;
-			if (mark && ((rc2 = markdup_mark_run(&m->md, c, vrec, run->off + lo, counted - lo, run->len, run->tmpl + lo, tmpl_at[r], run->n_tmpl)) ||
-			             (rc2 = markdup_mark_run(&m->md, c, vrec, run->off + counted, hi - counted, run->len, run->tmpl + counted, tmpl_at[r], run->n_tmpl, sw.scratch.as<unsigned long long>())))) return rc2;
-			if (m->qc_armed && (rc2 = qc_stage_records(m->qc, c, vrec, run->off + lo, counted - lo, run->len, at0 + lo))) return rc2;
+			int64_t lo, counted, hi;
+			sp.slice(wd, r, &lo, &counted, &hi);
+			if (!runv[r]->spilled || hi <= lo) continue;
+			const int rc = records_pass(stages(), runv[r], reinterpret_cast<uint8_t*>((uintptr_t)base[(size_t)wd * NR + r]), lo, counted, hi, rec_at[r], tmpl_at[r]);
+			if (rc) return rc;
 		}
-		const int f = win_first(wd), l = wd + 1 < n_windows ? win_first(wd + 1) : n - 1;
-		return spill_window_addr(c->stream, f, l - f + 1, n_runs, w.first.as<int64_t>(), w.run_off.as<const int64_t*>(), sw.flags.as<uint8_t>(), sw.base.as<int64_t>() + (size_t)wd * NR, idx,
+		const int rec_lo = sp.first[(size_t)wd], rec_hi = wd + 1 < sp.n_windows ? sp.first[(size_t)wd + 1] : n - 1;
+		return spill_window_addr(c->stream, rec_lo, rec_hi - rec_lo + 1, n_runs, w.first.as<int64_t>(), w.run_off.as<const int64_t*>(), sw.flags.as<uint8_t>(), sw.base.as<int64_t>() + (size_t)wd * NR, idx,
 		                         w.addr.as<const uint8_t*>());
-	};
+	}
 	// window wd's last piece is queued: the index parse of the records it holds whole with their predecessors; the staging buffer is free behind it
-	auto window_end = [&](int wd) -> int {
-		int rc2;
-		if (bai && (rc2 = bai_stage_parse(m->bai, c, win_first(wd) + (wd > 0), wd + 1 < n_windows ? win_first(wd + 1) + 1 : n, w.addr.as<const uint8_t*>(), idx, w.out_off.as<int64_t>(), bai->n_ref))) return rc2;
+	int window_end(int wd)
+	{
+		int rc;
+		if (plan.index && (rc = bai_stage_parse(m->bai, c, sp.first[(size_t)wd] + (wd > 0), wd + 1 < sp.n_windows ? sp.first[(size_t)wd + 1] + 1 : n, w.addr.as<const uint8_t*>(), idx,
+		                                        w.out_off.as<int64_t>(), plan.n_ref))) return rc;
 		HIP_TRY(hipEventRecord(sw.ev_used[wd & 1], c->stream));
 		return 0;
-	};
+	}
+	// piece k: gathered and deflated on the context's stream; the windows begin, end and travel around their pieces
+	int piece_queue(int k)
+	{
+		const int b = k & 1, wd = k / wp;
+		int rc;
+		if (k >= 2) HIP_TRY(hipStreamWaitEvent(c->stream, w.ev_down[b], 0));   // piece k - 2 has left out[b] (in[b]: the deflate of k - 2 is earlier in this stream)
+		const int64_t lo = (int64_t)k * piece_bytes, hi = lo + piece_len(k);
+		const int rec_lo = piece_first[(size_t)k];
+		const int rec_hi = k + 1 < n_pieces ? piece_first[(size_t)k + 1] : n - 1;   // inclusive: the record that holds the next cut begins in this piece or at the cut
+		const int n_rec = rec_hi - rec_lo + 1;
+		if (plan.spill && k % wp == 0) {
+			if (k == 0 && (rc = window_upload(0))) return rc;
+			if ((rc = window_begin(wd))) return rc;
+		}
+		HIP_TRY(hipEventRecord(w.ev_gather[b], c->stream));
+		hipLaunchKernelGGL(k_gather_window, dim3((unsigned)(((int64_t)n_rec * 16 + 255) / 256)), dim3(256), 0, c->stream, w.addr.as<const uint8_t*>(), idx, w.out_off.as<int64_t>(),
+		                   rec_lo, n_rec, lo, hi, w.in[b].as<uint8_t>());
+		if ((rc = launched())) return rc;
+		HIP_TRY(hipEventRecord(w.ev_deflate[b], c->stream));
+		if ((rc = bgzf_deflate(c, w.in[b].as<uint8_t>(), hi - lo, w.out[b], w.tot[b].as<int64_t>(), c->stream))) return rc;
+		HIP_TRY(hipEventRecord(w.ev_done[b], c->stream));
+		if (plan.index)                                             // the piece's member lengths, before the next piece reuses the deflate stage's buffers: same stream
+			HIP_TRY(hipMemcpyAsync(mlen_all + (int64_t)k * m->piece_blocks, c->bz.mlen.p, (size_t)bgzf_blocks(hi - lo) * 4, hipMemcpyDeviceToDevice, c->stream));
+		if (plan.spill && (k % wp == wp - 1 || k == n_pieces - 1) && (rc = window_end(wd))) return rc;
+		if (plan.spill && k % wp == 0 && wd + 1 < sp.n_windows && (rc = window_upload(wd + 1))) return rc;   // the next window travels while this one is gathered and deflated
+		return 0;
+	}
+	// piece k: its total, then its members, come back on the copy stream and are written
+	int piece_write(int k)
+	{
+		const int b = k & 1;
+		int64_t *h_tot = (int64_t*)w.h_tot.p;
+		HIP_TRY(hipStreamWaitEvent(c->stream_copy, w.ev_done[b], 0));
+		HIP_TRY(hipMemcpyAsync(h_tot + 2 * b, w.tot[b].p, 16, hipMemcpyDeviceToHost, c->stream_copy));
+		HIP_TRY(hipStreamSynchronize(c->stream_copy));
+		const int64_t got = h_tot[2 * b], plen = piece_len(k);
+		if (got < 0 || got > plen + bgzf_blocks(plen) * 31) return BWAHIP_EINTERNAL;
+		if (got) HIP_TRY(hipMemcpyAsync(w.h_out[b].p, w.out[b].p, (size_t)got, hipMemcpyDeviceToHost, c->stream_copy));
+		HIP_TRY(hipEventRecord(w.ev_down[b], c->stream_copy));
+		HIP_TRY(hipEventSynchronize(w.ev_down[b]));
+		float ms = 0;
+		if (hipEventElapsedTime(&ms, w.ev_gather[b], w.ev_deflate[b]) == hipSuccess) s.gather_ms += ms;
+		if (hipEventElapsedTime(&ms, w.ev_deflate[b], w.ev_done[b]) == hipSuccess) s.deflate_ms += ms;
+		s.bgzf_bytes += got; s.n_stored += h_tot[2 * b + 1];
+		int rc;
+		if (fd >= 0 && (rc = write_full(fd, (const uint8_t*)w.h_out[b].p, got))) { (void)hipStreamSynchronize(c->stream); return rc; }
+		return 0;
+	}
+	// the piece loop: piece k is queued while piece k - 1 comes back and is written; then what the events and the buffers say
+	int pieces()
+	{
+		int rc = 0;
+		for (int k = 0; k <= n_pieces; ++k)
+			if ((k < n_pieces && (rc = piece_queue(k))) || (k >= 1 && (rc = piece_write(k - 1)))) return rc;
+		HIP_TRY(hipStreamSynchronize(c->stream));
+		const BamSort &bs = c->bs;
+		float ms = 0;
+		if (hipEventElapsedTime(&ms, w.ev_sort[0], w.ev_sort[1]) == hipSuccess) s.sort_ms = ms;
+		s.hbm_bytes += (int64_t)(w.bytes() + bs.keys[0].cap + bs.keys[1].cap + bs.idx[0].cap + bs.idx[1].cap + bs.hist.cap + bs.hist_base.cap +
+		                           c->bz.slots.cap + c->bz.mlen.cap + c->bz.moff.cap + c->bz.md.cap + c->bz.cnt.cap);
+		for (int k = 0, nw = sp.n_windows; plan.spill && k < 2 && k < nw; ++k)   // the last two windows' uploads: no later one has read their events
+			if (hipEventElapsedTime(&ms, sw.ev_up0[(nw - 1 - k) & 1], sw.ev_up[(nw - 1 - k) & 1]) == hipSuccess) m->upload_ms += ms;
+		return 0;
+	}
+	// What follows the members, for the empty merger as well: the deferred end of the records pass, the index, the QC file, the stats
+	int tail(bwahip_devmerge_stats_t *st)
+	{
+		int rc = plan.spill ? records_done(stages()) : 0;    // what the resident finish awaits before the order
+		if (!rc && plan.index) {
+			std::vector<uint8_t> bytes;
+			if (!total && n) rc = BWAHIP_EINVAL;                    // records without a byte cannot be indexed
+			else rc = bai_stage_run(m->bai, c, n, w.addr.as<const uint8_t*>(), idx, w.out_off.as<int64_t>(), total, bgzf_blocks(total), plan.base, plan.n_ref, &bytes, plan.bs, parsed);
+			if (!rc) rc = bai_write_fd(plan.bai_fd, bytes);
+		}
+		if (!rc && plan.qc) rc = qc_write_fd(m->qc_fd, qc_bytes);
+		s.finish_s = now_s() - t0;
+		if (st) *st = s;
+		return rc;
+	}
+	int run(bwahip_devmerge_stats_t *st)
+	{
+		int rc;
+		if ((rc = checks()) || (rc = resident_pass())) return rc;
+		if (st) *st = s;
+		if (n == 0 || total == 0) return tail(st);                  // nothing to write: no member
+		if ((rc = order()) || (rc = offsets()) || (rc = cuts()) || (rc = buffers()) || (plan.spill && (rc = windows())) || (rc = pieces())) return rc;
+		return tail(st);
+	}
+};
 
-	// ---- gather and deflate piece k, download and write piece k - 1
-	auto piece_len = [&](int p) { const int64_t lo = (int64_t)p * piece_bytes; return total - lo < piece_bytes ? total - lo : piece_bytes; };
-	for (int k = 0; k <= n_pieces; ++k) {
-		if (k < n_pieces) {
-			const int b = k & 1;
-			if (k >= 2) HIP_TRY(hipStreamWaitEvent(c->stream, w.ev_down[b], 0));   // piece k - 2 has left out[b] (in[b]: the deflate of k - 2 is earlier in this stream)
-			const int64_t lo = (int64_t)k * piece_bytes, hi = lo + piece_len(k);
-			const int rec_lo = piece_first[(size_t)k];
-			const int rec_hi = k + 1 < n_pieces ? piece_first[(size_t)k + 1] : n - 1;   // inclusive: the record that holds the next cut begins in this piece or at the cut
-			const int n_rec = rec_hi - rec_lo + 1;
-			if (spill && k % wp == 0) {
-				if (k == 0 && (rc = upload_window(0))) return rc;
-				if ((rc = window_begin(k / wp))) return rc;
-			}
-			HIP_TRY(hipEventRecord(w.ev_gather[b], c->stream));
-			hipLaunchKernelGGL(k_gather_window, dim3((unsigned)(((int64_t)n_rec * 16 + 255) / 256)), dim3(256), 0, c->stream, w.addr.as<const uint8_t*>(), idx, w.out_off.as<int64_t>(),
-			                   rec_lo, n_rec, lo, hi, w.in[b].as<uint8_t>());
-			if ((rc = launched())) return rc;
-			HIP_TRY(hipEventRecord(w.ev_deflate[b], c->stream));
-			if ((rc = bgzf_deflate(c, w.in[b].as<uint8_t>(), hi - lo, w.out[b], w.tot[b].as<int64_t>(), c->stream))) return rc;
-			HIP_TRY(hipEventRecord(w.ev_done[b], c->stream));
-			if (bai)                                                    // the piece's member lengths, before the next piece reuses the deflate stage's buffers: same stream
-				HIP_TRY(hipMemcpyAsync(mlen_all + (int64_t)k * m->piece_blocks, c->bz.mlen.p, (size_t)bgzf_blocks(hi - lo) * 4, hipMemcpyDeviceToDevice, c->stream));
-			if (spill && (k % wp == wp - 1 || k == n_pieces - 1) && (rc = window_end(k / wp))) return rc;
-			if (spill && k % wp == 0 && k / wp + 1 < n_windows && (rc = upload_window(k / wp + 1))) return rc;   // the next window travels while this one is gathered and deflated
-		}
-		if (k >= 1) {
-			const int b = (k - 1) & 1;
-			HIP_TRY(hipStreamWaitEvent(c->stream_copy, w.ev_done[b], 0));
-			HIP_TRY(hipMemcpyAsync(h_tot + 2 * b, w.tot[b].p, 16, hipMemcpyDeviceToHost, c->stream_copy));
-			HIP_TRY(hipStreamSynchronize(c->stream_copy));
-			const int64_t got = h_tot[2 * b], plen = piece_len(k - 1);
-			if (got < 0 || got > plen + bgzf_blocks(plen) * 31) return BWAHIP_EINTERNAL;
-			if (got) HIP_TRY(hipMemcpyAsync(w.h_out[b].p, w.out[b].p, (size_t)got, hipMemcpyDeviceToHost, c->stream_copy));
-			HIP_TRY(hipEventRecord(w.ev_down[b], c->stream_copy));
-			HIP_TRY(hipEventSynchronize(w.ev_down[b]));
-			float ms = 0;
-			if (hipEventElapsedTime(&ms, w.ev_gather[b], w.ev_deflate[b]) == hipSuccess) s.gather_ms += ms;
-			if (hipEventElapsedTime(&ms, w.ev_deflate[b], w.ev_done[b]) == hipSuccess) s.deflate_ms += ms;
-			s.bgzf_bytes += got; s.n_stored += h_tot[2 * b + 1];
-			if (fd >= 0 && (rc = write_full(fd, (const uint8_t*)w.h_out[b].p, got))) { (void)hipStreamSynchronize(c->stream); return rc; }
-		}
-	}
-	HIP_TRY(hipStreamSynchronize(c->stream));
-	{ float ms = 0; if (hipEventElapsedTime(&ms, w.ev_sort[0], w.ev_sort[1]) == hipSuccess) s.sort_ms = ms; }
-	s.hbm_bytes += (int64_t)(w.bytes() + bs.keys[0].cap + bs.keys[1].cap + bs.idx[0].cap + bs.idx[1].cap + bs.hist.cap + bs.hist_base.cap +
-	                         c->bz.slots.cap + c->bz.mlen.cap + c->bz.moff.cap + c->bz.md.cap + c->bz.cnt.cap);
-	rc = 0;
-	if (spill) {                                                   // what the resident finish awaits before the order
-		for (int k = 0; k < 2 && k < n_windows; ++k) { float t = 0; if (hipEventElapsedTime(&t, sw.ev_up0[(n_windows - 1 - k) & 1], sw.ev_up[(n_windows - 1 - k) & 1]) == hipSuccess) m->upload_ms += t; }
-		if (mark) rc = devmerger_mark_end(m, ms);
-		if (!rc && m->qc_armed) rc = qc_stage_finish(m->qc, c, &qc_bytes, m->qc_stats);
-	}
-	if (!rc && bai) rc = finish_index(m, *bai, n, idx, total, spill);
-	if (!rc && m->qc_armed) rc = qc_write_fd(m->qc_fd, qc_bytes);
-	s.finish_s = now_s() - t0;
-	if (st) *st = s;
-	return rc;
+} // namespace
+
+int bam_devmerger_finish(bwahip_bam_devmerger *m, int fd, bwahip_devmerge_stats_t *st, FinishPlan plan)
+{
+	if (!m) return BWAHIP_EINVAL;
+	std::lock_guard<std::mutex> lk(m->mu);
+	return Finish(m, plan, fd).run(st);
 }
 
-extern "C" int bwahip_bam_devmerger_finish(bwahip_bam_devmerger *m, int fd, bwahip_devmerge_stats_t *st) { return devmerger_finish(m, fd, st, nullptr); }
+extern "C" int bwahip_bam_devmerger_finish(bwahip_bam_devmerger *m, int fd, bwahip_devmerge_stats_t *st) { return bam_devmerger_finish(m, fd, st, FinishPlan()); }
 
 extern "C" int bwahip_bam_devmerger_finish_bai(bwahip_bam_devmerger *m, int fd, int bai_fd, int64_t first_member_offset, int32_t n_ref, bwahip_devmerge_stats_t *st, bwahip_bai_stats_t *bs)
 {
 	if (n_ref < 0 || first_member_offset < 0 || first_member_offset >= (1ll << 48)) return BWAHIP_EINVAL;
 	if (bs) memset(bs, 0, sizeof *bs);
-	const BaiArgs a = { bai_fd, first_member_offset, n_ref, bs };
-	return devmerger_finish(m, fd, st, &a);
+	return bam_devmerger_finish(m, fd, st, FinishPlan{ true, bai_fd, first_member_offset, n_ref, bs });
 }
 
 extern "C" int bwahip_bam_devmerger_finish_markdup(bwahip_bam_devmerger *m, int fd, int bai_fd, int64_t first_member_offset, int32_t n_ref, bwahip_devmerge_stats_t *st,
@@ -845,8 +859,7 @@ extern "C" int bwahip_bam_devmerger_finish_markdup(bwahip_bam_devmerger *m, int 
 	if (first_member_offset < 0 || first_member_offset >= (1ll << 48)) return BWAHIP_EINVAL;
 	if (bs) memset(bs, 0, sizeof *bs);
 	if (ms) memset(ms, 0, sizeof *ms);
-	const BaiArgs a = { bai_fd, first_member_offset, n_ref, bs };
-	return devmerger_finish(m, fd, st, n_ref >= 0 ? &a : nullptr, true, ms);   // n_ref < 0: no index
+	return bam_devmerger_finish(m, fd, st, FinishPlan{ n_ref >= 0, bai_fd, first_member_offset, n_ref, bs, true, ms });   // n_ref < 0: no index
 }
 
 extern "C" int bwahip_bam_devmerger_set_qc(bwahip_bam_devmerger *m, const bwahip_qc_opt_t *opt, int32_t n_ref, const int64_t *ref_len, int qc_fd, bwahip_qc_stats_t *qs)
@@ -868,8 +881,9 @@ extern "C" void bwahip_bam_devmerger_close(bwahip_bam_devmerger *m)
 	(void)hipSetDevice(m->c->device);
 	for (hipStream_t q : { m->c->stream_copy, m->c->stream }) if (q) (void)hipStreamSynchronize(q);   // after a failed finish work may still be queued on the buffers
 	for (auto &kv : m->runs) bam_devrun_free(kv.second);
-	m->w.release(); m->md.release(); m->sw.release(); m->dl_bounce.release();
+	m->w.release(); m->sw.release(); m->dl_bounce.release();
 	spill_store_free(m->store);
 	bai_stage_free(m->bai); qc_stage_free(m->qc);
+	if (m->md) { m->md->release(); delete m->md; }
 	delete m;
 }

@@ -161,6 +161,15 @@ struct DevSortedSink : Sink {
 	std::atomic<bool> fell_back{false};                          // read by the drainers: from now on they download
 	hipStream_t fb_stream = nullptr; HostBuf fb_rec, fb_keys, fb_off;   // the fall-back's downloads: their stream, one pinned buffer each for records, keys and offsets
 	DevSortedSink(const char *h, bwahip_sort_dev_t *s) : sd(s), host(h, s->level, s) { form = OutForm::BamSorted; }
+	// What an entry point asks of the sink: mark (the runs carry templates), qo_ != NULL (the QC summary on qc_fd_).  no_fallback: a run that
+	// does not fit ends the call, sd->level has no reader, the index is written only for bai_fd >= 0; a sink that may fall back always indexes
+	void configure(int bai_fd, bool mark, bwahip_markdup_stats_t *ms_, const bwahip_qc_opt_t *qo_, int qc_fd_, bwahip_qc_stats_t *qs_, bool no_fallback)
+	{
+		if (mark) { form = OutForm::BamSortedDup; markdup = true; ms = ms_; }
+		if (no_fallback) host.level = 1;
+		if (!no_fallback || bai_fd >= 0) { host.with_bai = true; host.bai_fd = bai_fd; }
+		if (qo_) { qo = qo_; qc_fd = qc_fd_; qs = qs_; }
+	}
 	~DevSortedSink()
 	{
 		if (ctx0) (void)hipSetDevice(ctx0->device);
@@ -206,6 +215,14 @@ struct DevSortedSink : Sink {
 		}                                                           // (its buffers could not be allocated: downloaded as any run after a fall-back, which it causes)
 		return host.stage_out(c, out, it, t_end);
 	}
+	// the HBM the enabled stages take beside the merger's own, for this many records, raw bytes and templates
+	int64_t stages_need(int64_t n_rec, int64_t raw, int64_t n_tmpl) const
+	{
+		int64_t need = qc_need;
+		if (host.with_bai) need += bwahip_bam_devmerge_bai_hbm_need(n_rec, bgzf_blocks(raw), host.n_ref, bai_windows);
+		if (markdup) need += bwahip_bam_devmerge_markdup_hbm_need(n_rec, n_tmpl);
+		return need;
+	}
 	// a run in HBM -> the host merger, through the pinned buffers; the run is freed whatever happens
 	int run_to_host(int64_t run_no, DevRun *r, double sort_ms)
 	{
@@ -233,10 +250,8 @@ struct DevSortedSink : Sink {
 	{
 		int r = 0;
 		if (!fell_back) {                                           // in input order, so the decision depends on the input and the budget alone
-			int64_t need = bwahip_bam_devmerge_hbm_need(held_raw + it.raw_len, held_rec + it.n_rec, seq_no + 1, piece_blocks);
-			if (host.with_bai) need += bwahip_bam_devmerge_bai_hbm_need(held_rec + it.n_rec, bgzf_blocks(held_raw + it.raw_len), host.n_ref, bai_windows);
-			if (markdup) need += bwahip_bam_devmerge_markdup_hbm_need(held_rec + it.n_rec, held_tmpl + (it.run ? it.run->n_tmpl : 0));
-			need += qc_need;
+			const int64_t need = bwahip_bam_devmerge_hbm_need(held_raw + it.raw_len, held_rec + it.n_rec, seq_no + 1, piece_blocks) +
+			                     stages_need(held_rec + it.n_rec, held_raw + it.raw_len, held_tmpl + (it.run ? it.run->n_tmpl : 0));
 			const bool fits = it.run && need <= hbm_budget;
 			if (!fits) r = markdup ? BWAHIP_ECAPACITY : fall_back(seq_no);
 		}
@@ -255,10 +270,17 @@ struct DevSortedSink : Sink {
 			if (!r && qb && qs) { memset(qs, 0, sizeof *qs); qs->n_windows = qc_windows; qs->qc_bytes = 12580 + 48 * (int64_t)qc_len.size() + 8 * qc_windows; }
 			return r;
 		}
-		int64_t base = 0;
-		int r = host.write_header(1, &base);
-		if (!r && markdup) r = bwahip_bam_devmerger_finish_markdup(dm, fd, host.bai_fd, base, host.with_bai ? host.n_ref : -1, &sd->dev, nullptr, ms);
-		else if (!r) r = host.with_bai ? bwahip_bam_devmerger_finish_bai(dm, fd, host.bai_fd, base, host.n_ref, &sd->dev, nullptr) : bwahip_bam_devmerger_finish(dm, fd, &sd->dev);
+		return finish_on_device();
+	}
+	// the header at level 1, the device merger's finish with the stages the sink was configured for, the end-of-file block.  The plan goes
+	// straight to the internal finish: what the C entry points check or clear holds here already (n_ref is the contig table's, base the
+	// header's bytes, ms was cleared by the entry point, no index stats are asked for)
+	int finish_on_device()
+	{
+		FinishPlan plan;
+		plan.index = host.with_bai; plan.bai_fd = host.bai_fd; plan.n_ref = host.n_ref; plan.mark = markdup; plan.ms = ms;
+		int r = host.write_header(1, &plan.base);
+		if (!r) r = bam_devmerger_finish(dm, fd, &sd->dev, plan);
 		if (!r) { sd->n_records = sd->dev.n_records; sd->n_runs = sd->dev.n_runs; sd->merge_s = sd->dev.finish_s; }
 		sd->sort_ms = host.sort_ms;
 		return r ? r : bwahip_bgzf_eof(fd);
@@ -290,13 +312,6 @@ struct SpillSortedSink : DevSortedSink {
 		it.len = it.raw_len; it.holds_set = false;
 		return r ? r : it.run ? 0 : BWAHIP_ECAPACITY;               // not even one batch's run fits beside what is held
 	}
-	int64_t stages_need(int64_t n_rec, int64_t raw, int64_t n_tmpl) const
-	{
-		int64_t need = qc_need;
-		if (host.with_bai) need += bwahip_bam_devmerge_bai_hbm_need(n_rec, bgzf_blocks(raw), host.n_ref, bai_windows);
-		if (markdup) need += bwahip_bam_devmerge_markdup_hbm_need(n_rec, n_tmpl);
-		return need;
-	}
 	int write(int64_t seq_no, Item &it) override
 	{
 		int r = it.run ? 0 : BWAHIP_ECAPACITY;
@@ -324,17 +339,7 @@ struct SpillSortedSink : DevSortedSink {
 		drop(it);
 		return r;
 	}
-	int finish() override
-	{
-		int64_t base = 0;
-		int r = host.write_header(1, &base);
-		if (!r && markdup) r = bwahip_bam_devmerger_finish_markdup(dm, fd, host.bai_fd, base, host.with_bai ? host.n_ref : -1, &sd->dev, nullptr, ms);
-		else if (!r) r = host.with_bai ? bwahip_bam_devmerger_finish_bai(dm, fd, host.bai_fd, base, host.n_ref, &sd->dev, nullptr) : bwahip_bam_devmerger_finish(dm, fd, &sd->dev);
-		if (!r) { sd->n_records = sd->dev.n_records; sd->n_runs = sd->dev.n_runs; sd->merge_s = sd->dev.finish_s; }
-		sd->sort_ms = host.sort_ms;
-		(void)bwahip_bam_devmerger_spill_stats(dm, sp);
-		return r ? r : bwahip_bgzf_eof(fd);
-	}
+	int finish() override { const int r = finish_on_device(); (void)bwahip_bam_devmerger_spill_stats(dm, sp); return r; }
 };
 
 struct Driver {
@@ -626,7 +631,7 @@ extern "C" int bwahip_stream_run_bam_sorted_dev_bai(bwahip_ctx *const *ctxs, int
 {
 	if (!sd) return BWAHIP_EINVAL;
 	DevSortedSink sink(hdr_line, sd);
-	sink.host.with_bai = true; sink.host.bai_fd = bai_fd;
+	sink.configure(bai_fd, false, nullptr, nullptr, -1, nullptr, false);
 	return stream_run(ctxs, n_ctx, opt, pes0, fq1, fq2, out_fd, st, sink);
 }
 
@@ -639,9 +644,7 @@ extern "C" int bwahip_stream_run_bam_sorted_dev_markdup(bwahip_ctx *const *ctxs,
 	if (!sd) return BWAHIP_EINVAL;
 	if (ms) memset(ms, 0, sizeof *ms);
 	DevSortedSink sink(hdr_line, sd);
-	sink.form = OutForm::BamSortedDup; sink.markdup = true; sink.ms = ms;
-	sink.host.level = 1;                                          // sd->level belongs to the fall-back, which does not exist here
-	if (bai_fd >= 0) { sink.host.with_bai = true; sink.host.bai_fd = bai_fd; }
+	sink.configure(bai_fd, true, ms, nullptr, -1, nullptr, true);
 	return stream_run(ctxs, n_ctx, opt, pes0, fq1, fq2, out_fd, st, sink);
 }
 
@@ -655,12 +658,7 @@ extern "C" int bwahip_stream_run_bam_sorted_dev_qc(bwahip_ctx *const *ctxs, int 
 	if (ms) memset(ms, 0, sizeof *ms);
 	if (qs) memset(qs, 0, sizeof *qs);
 	DevSortedSink sink(hdr_line, sd);
-	sink.qo = qo; sink.qc_fd = qc_fd; sink.qs = qs;
-	if (markdup) {
-		sink.form = OutForm::BamSortedDup; sink.markdup = true; sink.ms = ms;
-		sink.host.level = 1;
-		if (bai_fd >= 0) { sink.host.with_bai = true; sink.host.bai_fd = bai_fd; }
-	} else { sink.host.with_bai = true; sink.host.bai_fd = bai_fd; }
+	sink.configure(bai_fd, markdup != 0, ms, qo, qc_fd, qs, markdup != 0);   // unmarked, the run may end on the host: it always indexes
 	return stream_run(ctxs, n_ctx, opt, pes0, fq1, fq2, out_fd, st, sink);
 }
 
@@ -675,9 +673,6 @@ extern "C" int bwahip_stream_run_bam_sorted_dev_spill(bwahip_ctx *const *ctxs, i
 	if (ms) memset(ms, 0, sizeof *ms);
 	if (qs) memset(qs, 0, sizeof *qs);
 	SpillSortedSink sink(hdr_line, sd, sp);
-	sink.host.level = 1;
-	if (mark) { sink.form = OutForm::BamSortedDup; sink.markdup = true; sink.ms = ms; }
-	if (bai_fd >= 0) { sink.host.with_bai = true; sink.host.bai_fd = bai_fd; }
-	if (qc) { sink.qo = qc; sink.qc_fd = qc_fd; sink.qs = qs; }
+	sink.configure(bai_fd, mark != 0, ms, qc, qc_fd, qs, true);
 	return stream_run(ctxs, n_ctx, opt, pes0, fq1, fq2, out_fd, st, sink);
 }

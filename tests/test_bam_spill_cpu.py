@@ -1,6 +1,7 @@
 """Spilled runs of the device merger, the parts that need no device: bwahip_bam_devmerge_spill_hbm_need against hand-computed cases, the
-layout of bwahip_spill_t against a compiled C probe, and the host-side store (bwa-mem-gpu_amd/csrc/spill_store.cpp) through a stand-alone
-program (tests/spill_store_check.cpp) built with the address and undefined-behaviour sanitizers and run as a child process."""
+layout of bwahip_spill_t against a compiled C probe, and the host-side store (bwa-mem-gpu_amd/csrc/spill_store.cpp) and the finish's window
+plan (bwa-mem-gpu_amd/csrc/spill_plan.h), each through a stand-alone program (tests/spill_store_check.cpp, tests/spill_plan_check.cpp) built
+with the address and undefined-behaviour sanitizers and run as a child process."""
 import ctypes as C
 import os
 import shutil
@@ -100,3 +101,15 @@ def test_store_round_trips_under_the_sanitizers(built, tmp_path):
     r = subprocess.run([str(exe), str(d), str(f)], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
     assert r.returncode == 0 and r.stdout.strip() == "ok", r.stdout + r.stderr
     assert os.listdir(d) == []
+
+
+def test_window_plan_holds_under_the_sanitizers(built, tmp_path):
+    """tests/spill_plan_check.cpp: 1, 3 and 7 runs with every subset spilled, window_pieces 1, 2 and beyond the pieces, an empty run, a run
+    inside one window, a tie block and a record over three windows, and every malformed cut table the plan refuses."""
+    cxx = shutil.which("g++") or shutil.which("clang++")
+    assert cxx, "no C++ compiler"
+    exe = tmp_path / "spill_plan_check"
+    subprocess.check_call([cxx, "-std=c++17", "-O1", "-g", "-Wall", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-I" + INC, "-I" + CSRC,
+                           os.path.join(common.ROOT, "tests", "spill_plan_check.cpp"), "-o", str(exe)])
+    r = subprocess.run([str(exe)], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
+    assert r.returncode == 0 and r.stdout.strip() == "ok", r.stdout + r.stderr

@@ -380,8 +380,101 @@ def test_refusals_leave_the_merger_usable(ctx, plain, marked_sets, tmp_path):
             m.finish_markdup(-1)
 
 
-# ---------------------------------------------------------------------------------------------------------------- 7. the stream driver
-K = 1800 * 150                                                                          # batches of 900 pairs (or 1800 single reads): three runs, or two
+# ---------------------------------------------------------------------------------------------------------------- 7. finish after finish
+LEAK_BASE = 4321                                                                        # any first_member_offset: both mergers get the same
+
+
+@pytest.fixture(scope="module")
+def leak_runs():
+    """Three runs of about 1 000 records of 100 to 300 bytes with templates and descriptors: markdup_cases' paired templates, every record
+    lengthened by a trailing Z tag (nothing the stages read), cut into runs as marked_sets cuts them."""
+    c = mcases.record_set(True, n_tmpl=1250, seed=21)
+    rng = random.Random(21)
+    def pad(x):
+        n = rng.randrange(max(len(x) + 4, 100), 301)
+        x += b"XPZ" + b"p" * (n - len(x) - 4) + b"\0"
+        return struct.pack("<i", len(x) - 4) + x[4:]
+    c["templates"] = [(name, [[pad(x) for x in r] for r in rr]) for name, rr in c["templates"] if all(_indexable(x) for r in rr for x in r)]
+    descs = mcases.judge_descs(c)
+    n = len(c["templates"])
+    b = [0, 3 * n // 10, 13 * n // 20, n]
+    key_of = lambda r: sref.packed_key(r, mcases.N_SEQS, mcases.LONGEST)
+    runs = []
+    for k in range(3):
+        recs = [(x, t) for t, (_, reads) in enumerate(c["templates"][b[k]:b[k + 1]]) for r in reads for x in r]
+        recs.sort(key=lambda p: sref.order_key(p[0]))
+        assert all(100 <= len(x) <= 300 for x, _ in recs) and len(recs) > 800
+        runs.append((*sref.run_arrays([x for x, _ in recs], key_of), np.array([t for _, t in recs], dtype=np.uint32), mcases.as_desc_array(descs[b[k]:b[k + 1]])))
+    assert 2500 < sum(len(r[1]) for r in runs) < 3800 and sum(len(r[0]) for r in runs) > 3 * BLOCK
+    return runs
+
+
+def _leak_merger(ctx, runs, spilled):
+    m = bw.DevMerger(ctx, 1)
+    m.set_spill(1 << 30, None, 1)
+    for k in (1, 2, 0):
+        m.add_spilled(k, *runs[k]) if spilled else m.add_dup(k, *runs[k])
+    return m
+
+
+def _leak_step(m, k, d):
+    """Step k of the five finishes on merger m: the three files' bytes and every count the call reports."""
+    paths = [os.path.join(d, n) for n in ("m.bin", "m.bai", "m.bqc")]
+    fd, fb, fq = (os.open(p, os.O_WRONLY | os.O_CREAT | os.O_TRUNC, 0o644) for p in paths)
+    bs = ms = qs = None
+    try:
+        if k == 0:
+            st = m.finish(fd)
+        elif k == 1:
+            st, bs = m.finish_bai(fd, fb, LEAK_BASE, N_SEQS)
+        elif k == 2:
+            qs = m.set_qc(QC_LENS, fq, QC_OPT)
+            st = m.finish(fd)
+        elif k == 3:
+            m.set_qc(None)
+            st = m.finish(fd)
+        else:
+            st, bs, ms = m.finish_markdup(fd, fb, LEAK_BASE, N_SEQS)
+        sp = m.spill_stats()
+    finally:
+        for x in (fd, fb, fq):
+            os.close(x)
+    counts = dict(dev=_counts(st), bai=bs and (bs.n_chunks, bs.n_windows, bs.n_no_coor), qc=qs and (qs.n_windows, qs.qc_bytes),
+                  markdup=ms and (list(ms.n_templates), list(ms.n_dup_templates), ms.n_marked),
+                  spill=(sp.n_spilled_runs, sp.first_spilled_run, sp.host_bytes, sp.file_bytes, sp.n_windows))
+    return [open(p, "rb").read() for p in paths], counts
+
+
+LEAK_STEPS = ("finish", "finish_bai", "set_qc, finish", "set_qc(None), finish", "finish_markdup with the index")
+
+
+@pytest.mark.parametrize("spilled", [False, True])
+def test_no_stage_state_leaks_from_one_finish_into_the_next(ctx, leak_runs, tmp_path, spilled):
+    """One merger finished five times -- plain, indexed, armed, disarmed, marked and indexed -- writes at every step what a fresh merger
+    with the same runs writes when that step is its only call (the marked finish last: it changes resident records in place)."""
+    d_one, d_fresh = tmp_path / "one", tmp_path / "fresh"
+    d_one.mkdir()
+    d_fresh.mkdir()
+    files = []
+    with _leak_merger(ctx, leak_runs, spilled) as one:
+        for k, name in enumerate(LEAK_STEPS):
+            what = f"{'spilled' if spilled else 'resident'}, step {k + 1} ({name})"
+            got, got_counts = _leak_step(one, k, str(d_one))
+            with _leak_merger(ctx, leak_runs, spilled) as fresh:
+                want, want_counts = _leak_step(fresh, k, str(d_fresh))
+            for part, a, b in zip(("members", "index", "QC summary"), got, want):
+                assert a == b, f"{what}: {part} differ from a fresh merger's ({len(a)} and {len(b)} bytes)"
+            assert got_counts == want_counts, what
+            files.append(got)
+    n_pieces = (sum(len(r[0]) for r in leak_runs) + BLOCK - 1) // BLOCK
+    assert n_pieces >= 3 and got_counts["spill"][4] == (n_pieces if spilled else 0)
+    members, bai, qc = zip(*files)
+    assert members[0] == members[1] == members[2] == members[3] != members[4] and got_counts["markdup"][2] > 0
+    assert [bool(x) for x in bai] == [False, True, False, False, True] and [bool(x) for x in qc] == [False, False, True, False, False]
+
+
+# ---------------------------------------------------------------------------------------------------------------- 8. the stream driver
+K = 1800 * 150                                                                        # batches of 900 pairs (or 1800 single reads): three runs, or two
 PER_BATCH = 1800
 HDR = "@RG\tID:g1\tSM:s\n@PG\tID:bwahip"
 STREAM_QC = (8, -1, 0)
