@@ -248,6 +248,7 @@ def lib():
     L.bwahip_kat_markdup.argtypes = [vp, vp, C.c_int64, vp]
     L.bwahip_kat_dup_desc_ms.argtypes = [vp]
     L.bwahip_kat_dup_desc_ms.restype = C.c_float
+    L.bwahip_live_resources.argtypes = [i64p]
     L.bwahip_qc_builder_open.argtypes = [C.c_int32, vp, C.POINTER(QcOpt), C.POINTER(vp)]
     L.bwahip_qc_builder_add_records.argtypes = [vp, vp, vp, C.c_int64]
     L.bwahip_qc_builder_finish.argtypes = [vp, C.c_int]
@@ -668,6 +669,13 @@ def bgzf_write(fd, data, level=1, n_threads=1, eof=False):
     _check(lib().bwahip_bgzf_write(fd, data, len(data), level, n_threads), "bwahip_bgzf_write")
     if eof:
         _check(lib().bwahip_bgzf_eof(fd), "bwahip_bgzf_eof")
+
+
+def live_resources():
+    """(device buffers, device bytes, pinned buffers, pinned bytes, events, streams) the library owns in this process right now."""
+    out = (C.c_int64 * 6)()
+    _check(lib().bwahip_live_resources(out), "bwahip_live_resources")
+    return tuple(out)
 
 
 def default_opt():

@@ -2,49 +2,80 @@
 // runtime.hip (hot path sequencing, C ABI) and final_rt.hip (finalisation / SAM sequencing).
 #pragma once
 #include "bwahip_internal.h"
+#include "own.h"
 #include <atomic>
+#include <memory>
 #include <string>
 #include <utility>
 
-// hipFree / hipMalloc / hipHostMalloc inside a buffer's ensure() synchronise the whole device: counted, so that the stream driver can
-// report how many a pass paid (BWAHIP_STREAM_LOG; a steady pass of equal batches pays none)
+// hipFree / hipMalloc / hipHostMalloc synchronise the whole device: counted, so that the stream driver can report how many a pass paid
+// (BWAHIP_STREAM_LOG; a steady pass of equal batches pays none)
 inline std::atomic<long> g_bwahip_reallocs{0};
+// what the library owns in this process (bwahip_live_resources): device buffers, their bytes, pinned buffers, their bytes, events, streams
+inline std::atomic<int64_t> g_bwahip_live[6];
 
-// ------------------------------------------------------------------ small device helpers
-struct DevBuf {
-	void *p = nullptr; size_t cap = 0; bool ext = false;   // ext: caller-owned device memory (bwahip_batch_attach)
-	void adopt(void *dev, size_t bytes) { release(); p = dev; cap = bytes; ext = true; }
-	int ensure(size_t bytes)
+// ------------------------------------------------------------------ owners of HIP resources (own.h: the buffer type itself)
+struct DevMem {
+	static constexpr size_t slack = 256;
+	static constexpr const char *what = "hipMalloc";
+	static void *alloc(size_t bytes)
 	{
-		if (bytes <= cap && !ext) return 0;
-		if (p && !ext) (void)hipFree(p);
-		p = nullptr; cap = 0; ext = false;
-		++g_bwahip_reallocs;
-		size_t want = bytes + bytes / 8 + 256;
-		if (hipMalloc(&p, want) != hipSuccess) { fprintf(stderr, "[bwahip] hipMalloc(%zu) failed\n", want); return BWAHIP_ENOMEM; }
-		cap = want;
-		return 0;
+		void *p = nullptr;
+		if (hipMalloc(&p, bytes ? bytes : 1) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
+		++g_bwahip_live[0]; g_bwahip_live[1] += (int64_t)bytes;
+		return p;
 	}
-	void release() { if (p && !ext) (void)hipFree(p); p = nullptr; cap = 0; ext = false; }
-	template <class T> T *as() const { return (T*)p; }
+	static void free(void *p, size_t bytes) { (void)hipFree(p); --g_bwahip_live[0]; g_bwahip_live[1] -= (int64_t)bytes; }
+	static void count_sync() { ++g_bwahip_reallocs; }
 };
-
-
-// pinned host staging buffer (grows, never shrinks)
-struct HostBuf {
-	void *p = nullptr; size_t cap = 0;
-	int ensure(size_t bytes)
+struct PinnedMem {
+	static constexpr size_t slack = 4096;
+	static constexpr const char *what = "hipHostMalloc";
+	static void *alloc(size_t bytes)
 	{
-		if (bytes <= cap) return 0;
-		if (p) (void)hipHostFree(p);
-		p = nullptr; cap = 0;
-		++g_bwahip_reallocs;
-		const size_t want = bytes + bytes / 8 + 4096;
-		if (hipHostMalloc(&p, want, hipHostMallocDefault) != hipSuccess) { fprintf(stderr, "[bwahip] hipHostMalloc(%zu) failed\n", want); p = nullptr; return BWAHIP_ENOMEM; }
-		cap = want;
+		void *p = nullptr;
+		if (hipHostMalloc(&p, bytes ? bytes : 1, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
+		++g_bwahip_live[2]; g_bwahip_live[3] += (int64_t)bytes;
+		return p;
+	}
+	static void free(void *p, size_t bytes) { (void)hipHostFree(p); --g_bwahip_live[2]; g_bwahip_live[3] -= (int64_t)bytes; }
+	static void count_sync() { ++g_bwahip_reallocs; }
+};
+using DevBuf = Buf<DevMem>;              // device memory; adopt(): caller-owned (bwahip_batch_attach, bwahip_init_device)
+using HostBuf = Buf<PinnedMem>;          // pinned host staging buffer
+
+// An event / a stream the library made: move-only, destroyed with its owner, passed wherever HIP takes the handle
+struct Event {
+	hipEvent_t e = nullptr;
+	Event() = default;
+	Event(Event &&o) noexcept : e(o.e) { o.e = nullptr; }
+	Event &operator=(Event &&o) noexcept { if (this != &o) { reset(); e = o.e; o.e = nullptr; } return *this; }
+	~Event() { reset(); }
+	int make(unsigned flags = hipEventDefault)
+	{
+		reset();
+		if (hipEventCreateWithFlags(&e, flags) != hipSuccess) { (void)hipGetLastError(); e = nullptr; return BWAHIP_ENODEV; }
+		++g_bwahip_live[4];
 		return 0;
 	}
-	void release() { if (p) (void)hipHostFree(p); p = nullptr; cap = 0; }
+	void reset() { if (e) { (void)hipEventDestroy(e); --g_bwahip_live[4]; e = nullptr; } }
+	operator hipEvent_t() const { return e; }
+};
+struct Stream {
+	hipStream_t s = nullptr;
+	Stream() = default;
+	Stream(Stream &&o) noexcept : s(o.s) { o.s = nullptr; }
+	Stream &operator=(Stream &&o) noexcept { if (this != &o) { reset(); s = o.s; o.s = nullptr; } return *this; }
+	~Stream() { reset(); }
+	int make(unsigned flags = hipStreamNonBlocking)
+	{
+		reset();
+		if (hipStreamCreateWithFlags(&s, flags) != hipSuccess) { (void)hipGetLastError(); s = nullptr; return BWAHIP_ENODEV; }
+		++g_bwahip_live[5];
+		return 0;
+	}
+	void reset() { if (s) { (void)hipStreamDestroy(s); --g_bwahip_live[5]; s = nullptr; } }
+	operator hipStream_t() const { return s; }
 };
 
 // Tuning knobs (hand-off thresholds of the heavy-read kernels).  Read from the environment ONCE, when the context is
@@ -100,7 +131,6 @@ struct BamSort {
 	DevBuf tmpl;                         // OutForm::BamSortedDup: per record in input order the index of its template (k_markdup.hip)
 	float ms[3] = { 0, 0, 0 };           // record table, radix sort, gather of the last timed run
 	int n_passes = 0;                    // radix passes the last sort ran
-	void release() { for (DevBuf *b : { &raw, &rec_cnt, &rec_base, &keys[0], &keys[1], &idx[0], &idx[1], &off, &len, &len_sorted, &hist, &hist_base, &bits, &tmpl }) b->release(); }
 };
 
 // Working set of the deflate stage (k_bgzf.hip), one per context: a 64 KiB slot per BGZF block for the member as it is formed, the
@@ -108,7 +138,6 @@ struct BamSort {
 // the count of blocks that left stored.
 struct Bgzf {
 	DevBuf slots, mlen, moff, md, cnt;
-	void release() { for (DevBuf *b : { &slots, &mlen, &moff, &md, &cnt }) b->release(); }
 };
 
 // The form a batch's output leaves run_final in (d_sam): SAM text; BAM records in read order (k_bam.hip); the records in coordinate order with their
@@ -123,16 +152,10 @@ inline bool is_sorted(OutForm f) { return f == OutForm::BamSorted || f == OutFor
 struct BatchIn {
 	DevBuf d_seq, d_off, d_qual, d_qual_off, d_names, d_name_off, d_comments, d_comment_off;
 	HostBuf h_stage;
-	hipEvent_t ev = nullptr;             // the copies to HBM are done
+	Event ev;                            // the copies to HBM are done
 	int n = 0, max_len = 0; int64_t total_bases = 0; bool any_comment = false;
 	// a batch without comments: a null pointer tells the kernels (d_comments itself is kept from batch to batch)
 	const uint8_t *comments() const { return any_comment ? d_comments.as<uint8_t>() : nullptr; }
-	void release()                       // at the end of the owner: the buffers freed, the events destroyed
-	{
-		for (DevBuf *b : { &d_seq, &d_off, &d_qual, &d_qual_off, &d_names, &d_name_off, &d_comments, &d_comment_off }) b->release();
-		h_stage.release();
-		if (ev) (void)hipEventDestroy(ev);
-	}
 };
 
 // What run_final leaves behind: the batch in `form` in d_sam (`total` bytes of text or records; OutForm::Bgzf: of the records the members hold)
@@ -142,28 +165,16 @@ struct BatchIn {
 // indices in d_tmpl, and n_tmpl descriptors in d_desc (with the descriptor kernel's error word behind them).
 struct BatchOut {
 	DevBuf d_sam, d_sam_off, d_keys, d_rec_off, d_tot, d_tmpl, d_desc;
-	hipEvent_t ev_sort[4] = {}, ev_bgzf[2] = {};
+	Event ev_sort[4], ev_bgzf[2];
 	int64_t total = 0, n_rec = 0, n_blocks = 0, n_stored = 0, n_tmpl = 0;
 	OutForm form = OutForm::Sam;
-	void release()
-	{
-		for (DevBuf *b : { &d_sam, &d_sam_off, &d_keys, &d_rec_off, &d_tot, &d_tmpl, &d_desc }) b->release();
-		for (hipEvent_t e : ev_sort) if (e) (void)hipEventDestroy(e);
-		for (hipEvent_t e : ev_bgzf) if (e) (void)hipEventDestroy(e);
-	}
 };
 
 // The pinned buffers a BatchOut comes back into -- one per set of the stream driver, two taken in turn for the context's own set (the one-piece
 // entries of bwahip_process_seqs*) -- and the events of the way back (stream path): the write pass has ended / the bytes are in h_sam
 struct PinnedOut {
 	HostBuf h_sam, h_keys, h_rec_off, h_tmpl, h_desc;
-	hipEvent_t ev_written = nullptr, ev_copied = nullptr;
-	void release()
-	{
-		h_sam.release(); h_keys.release(); h_rec_off.release(); h_tmpl.release(); h_desc.release();
-		if (ev_written) (void)hipEventDestroy(ev_written);
-		if (ev_copied) (void)hipEventDestroy(ev_copied);
-	}
+	Event ev_written, ev_copied;
 };
 
 struct StreamPipe;                       // final_rt.hip: the second sets of batch buffers the stream driver's three stages work on
@@ -188,11 +199,11 @@ struct bwahip_ctx {
 	std::string rg_id;                   // read-group id appended as RG:Z: to every record (bwa_rg_id, bwa.c:44); empty = none
 	DevBuf d_logtab;                     // log(i), i < BWAHIP_LOGTAB_N, from the host's libm (bwamem.c:607, 974-981)         // index arrays live in caller-owned HBM (bwahip_init_device)
 	int device = 0;
-	hipStream_t stream_copy = nullptr;   // uploads that run beside the kernels (bwahip_process_seqs: names / qualities during the hot path)
-	hipEvent_t ev_sam_half = nullptr; int sam_half_reads = 0;   // run_final: recorded when the SAM text of reads [0, sam_half_reads) is written
-	hipEvent_t ev_slice[8] = {};         // bwahip_process_seqs: one per slice of the SAM download
-	hipStream_t stream = nullptr, stream2 = nullptr, stream3 = nullptr;   // stream2/3: kernels that run beside the main one (k_chain_big)
-	hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_join3 = nullptr;
+	Stream stream_copy;                  // uploads that run beside the kernels (bwahip_process_seqs: names / qualities during the hot path)
+	Event ev_sam_half; int sam_half_reads = 0;   // run_final: recorded when the SAM text of reads [0, sam_half_reads) is written
+	Event ev_slice[8];                   // bwahip_process_seqs: one per slice of the SAM download
+	Stream stream, stream2, stream3;   // stream2/3: kernels that run beside the main one (k_chain_big)
+	Event ev_fork, ev_join, ev_join3;
 	HostIndex host = {};                 // host copy: contig table + packed reference (always owned); FM-index arrays only when loaded from files
 	DevIndex ix;
 	DevBuf d_bwt, d_sa, d_pac, d_anns;
@@ -230,7 +241,7 @@ struct bwahip_ctx {
 	float final_ms[8] = { 0 };           // k_mark, k_cigar, k_sam(size), k_sam(write) of the last run
 	int intv_cap = 96;                   // current capacity (starts at knobs.intv_cap, grows on overflow)
 	int64_t total_seeds = 0, total_regs = 0;
-	hipEvent_t ev[24];
+	Event ev[24];
 	float last_ms[24];
 };
 
@@ -282,9 +293,14 @@ inline int64_t bgzf_blocks(int64_t len) { return (len + 65279) / 65280; }
 // len, n_rec and n_rec + 1 items.
 // With duplicate marking (has_dup): n_rec template indices and n_tmpl descriptors as well.
 struct DevRun {
-	int64_t n_rec = 0, len = 0; uint8_t *rec = nullptr; uint64_t *keys = nullptr; int64_t *off = nullptr; int device = 0;   // allocated to size: no slack
-	bool has_dup = false; int64_t n_tmpl = 0; uint32_t *tmpl = nullptr; bwahip_dup_desc_t *desc = nullptr;
-	bool spilled = false; std::vector<int64_t> h_off;               // a spilled run (k_bamspill.hip): rec stays null, the bytes are in the merger's store; the offsets on the host as well
+	int64_t n_rec = 0, len = 0; DevBuf d_rec, d_keys, d_off; int device = 0;   // allocated to size: no slack
+	bool has_dup = false; int64_t n_tmpl = 0; DevBuf d_tmpl, d_desc;
+	bool spilled = false; std::vector<int64_t> h_off;               // a spilled run (k_bamspill.hip): d_rec stays empty, the bytes are in the merger's store; the offsets on the host as well
+	uint8_t *rec() const { return d_rec.as<uint8_t>(); }
+	uint64_t *keys() const { return d_keys.as<uint64_t>(); }
+	int64_t *off() const { return d_off.as<int64_t>(); }
+	uint32_t *tmpl() const { return d_tmpl.as<uint32_t>(); }
+	bwahip_dup_desc_t *desc() const { return d_desc.as<bwahip_dup_desc_t>(); }
 };
 int  bam_devrun_make(bwahip_ctx *c, const uint8_t *d_rec, int64_t len, const uint64_t *d_keys, const int64_t *d_rec_off, int64_t n_rec, hipStream_t st, DevRun **out);
 int  bam_devrun_download(const DevRun *r, uint8_t *rec, uint64_t *keys, int64_t *rec_off, hipStream_t st);
@@ -329,10 +345,9 @@ int  bai_stage_parse(BaiStage *s, bwahip_ctx *c, int lo, int hi, const uint8_t *
 // context's sort buffers are used); markdup_count and markdup_mark_run add to cnt ([0..5] templates and duplicates per kind, [6] records
 // marked, [7] the marking pass's error word), which markdup_counters_reset zeroes.
 struct MarkdupStage {
-	DevBuf desc, head, seg, best, pair_here, dup, cnt;
-	hipEvent_t ev[3] = {};               // begin, decision done, end
-	size_t bytes() const;
-	void release();
+	Tally hbm;
+	DevBuf desc{hbm}, head{hbm}, seg{hbm}, best{hbm}, pair_here{hbm}, dup{hbm}, cnt{hbm};
+	Event ev[3];                         // begin, decision done, end
 };
 int dup_batch_desc(bwahip_ctx *c, int n_reads, bool paired, int64_t n_rec);
 int dup_batch_tmpl(bwahip_ctx *c, int n_rec, const unsigned *idx);

@@ -352,7 +352,7 @@ int run_final(bwahip_ctx *c, const bwahip_opt_t *opt, int64_t n_processed, const
 	if (timed) HIP_TRY(hipEventRecord(c->ev[19], c->stream));
 	if (sorted && (rc = bam_sort_batch(c, n, total, form == OutForm::BamSortedDup ? (pe ? 2 : 1) : 0))) return rc;
 	if (bgzf) {                                                   // the deflate stage, queued behind the write pass
-		for (auto &e : o.ev_bgzf) if (!e) HIP_TRY(hipEventCreate(&e));
+		for (auto &e : o.ev_bgzf) if (!e && (rc = e.make())) return rc;
 		if ((rc = o.d_tot.ensure(16))) return rc;
 		HIP_TRY(hipEventRecord(o.ev_bgzf[0], c->stream));
 		if ((rc = bgzf_deflate(c, c->bs.raw.as<uint8_t>(), total, o.d_sam, o.d_tot.as<int64_t>(), c->stream))) return rc;
@@ -846,36 +846,38 @@ extern "C" int bwahip_kat_mark(bwahip_ctx *c, const bwahip_opt_t *opt, int64_t n
 	int rc;
 	const int sel0 = plan ? 0xff : 0;
 	c->total_regs = total;
-	if ((rc = dev_upload(c->d_regs, regs.data(), regs.size() * sizeof(DevReg), c->stream)) || (rc = dev_upload(c->d_reg_base, reg_off, (size_t)(n + 1) * 8, c->stream)) ||
-	    (rc = dev_upload(c->d_reg_n, regn.data(), (size_t)n * 4, c->stream)) || (rc = d_mq.ensure(R * 8)) || (rc = mark_prepare(c, opt, n, n_processed, false, f))) goto done;
-	// what k_mark<false> leaves alone comes back as zero; what a launch must write starts as 0xff, so that nothing a call before this one
-	// left in the context's buffers can pass for an answer
-	if (hipMemsetAsync(c->d_fregs.p, 0xff, R * sizeof(FinReg), c->stream) != hipSuccess || hipMemsetAsync(c->d_freg_n.p, 0xff, (size_t)n * 4, c->stream) != hipSuccess ||
-	    hipMemsetAsync(c->d_npri.p, 0xff, (size_t)n * 4, c->stream) != hipSuccess ||
-	    hipMemsetAsync(c->d_need.p, sel0, R, c->stream) != hipSuccess || hipMemsetAsync(c->d_xa_owner.p, sel0, R * 4, c->stream) != hipSuccess ||
-	    hipMemsetAsync(c->d_task_n.p, sel0, (size_t)n * 4, c->stream) != hipSuccess || hipMemsetAsync(c->d_rec_n.p, sel0, (size_t)n * 4, c->stream) != hipSuccess) { rc = BWAHIP_ENODEV; goto done; }
-	if (pairs) {                                                 // as run_final does for a paired-end batch: all pairs but the listed ones, then the listed ones
-		if ((rc = dev_upload(c->d_resc, list.data(), list.size() * 4, c->stream)) || (rc = dev_upload(c->d_resc_flag, flag.data(), flag.size(), c->stream))) goto done;
-		f.resc_flag = c->d_resc_flag.as<uint8_t>(); f.resc_pairs = c->d_resc.as<int>(); f.subset = 1;
-		if ((rc = launch_mark_primary(f, plan != 0, 0, c->stream))) goto done;
-		if (n_pairs > 0) {
-			f.subset = 2;
-			if ((rc = launch_mark_primary(f, plan != 0, n_pairs, c->stream))) goto done;
-		}
-		f.subset = 0;
-	} else if ((rc = launch_mark_primary(f, plan != 0, 0, c->stream))) goto done;
-	if ((rc = launch_kat_mapq(f, total, d_mq.as<int>(), c->stream))) goto done;
-	if ((total && (hipMemcpyAsync(h_f.data(), c->d_fregs.p, (size_t)total * sizeof(FinReg), hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
-	               hipMemcpyAsync(h_need.data(), c->d_need.p, (size_t)total, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
-	               hipMemcpyAsync(h_own.data(), c->d_xa_owner.p, (size_t)total * 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
-	               hipMemcpyAsync(h_mq.data(), d_mq.p, (size_t)total * 8, hipMemcpyDeviceToHost, c->stream) != hipSuccess)) ||
-	    hipMemcpyAsync(h_fn.data(), c->d_freg_n.p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
-	    hipMemcpyAsync(h_np.data(), c->d_npri.p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
-	    hipMemcpyAsync(h_tn.data(), c->d_task_n.p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
-	    hipMemcpyAsync(h_rn.data(), c->d_rec_n.p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess) rc = BWAHIP_ENODEV;
-done:
+	auto queue = [&]() -> int {                                  // the uploads, the launches, the copies back: the stream is awaited whatever this returns
+		if ((rc = dev_upload(c->d_regs, regs.data(), regs.size() * sizeof(DevReg), c->stream)) || (rc = dev_upload(c->d_reg_base, reg_off, (size_t)(n + 1) * 8, c->stream)) ||
+		    (rc = dev_upload(c->d_reg_n, regn.data(), (size_t)n * 4, c->stream)) || (rc = d_mq.ensure(R * 8)) || (rc = mark_prepare(c, opt, n, n_processed, false, f))) return rc;
+		// what k_mark<false> leaves alone comes back as zero; what a launch must write starts as 0xff, so that nothing a call before this one
+		// left in the context's buffers can pass for an answer
+		if (hipMemsetAsync(c->d_fregs.p, 0xff, R * sizeof(FinReg), c->stream) != hipSuccess || hipMemsetAsync(c->d_freg_n.p, 0xff, (size_t)n * 4, c->stream) != hipSuccess ||
+		    hipMemsetAsync(c->d_npri.p, 0xff, (size_t)n * 4, c->stream) != hipSuccess ||
+		    hipMemsetAsync(c->d_need.p, sel0, R, c->stream) != hipSuccess || hipMemsetAsync(c->d_xa_owner.p, sel0, R * 4, c->stream) != hipSuccess ||
+		    hipMemsetAsync(c->d_task_n.p, sel0, (size_t)n * 4, c->stream) != hipSuccess || hipMemsetAsync(c->d_rec_n.p, sel0, (size_t)n * 4, c->stream) != hipSuccess) return BWAHIP_ENODEV;
+		if (pairs) {                                                 // as run_final does for a paired-end batch: all pairs but the listed ones, then the listed ones
+			if ((rc = dev_upload(c->d_resc, list.data(), list.size() * 4, c->stream)) || (rc = dev_upload(c->d_resc_flag, flag.data(), flag.size(), c->stream))) return rc;
+			f.resc_flag = c->d_resc_flag.as<uint8_t>(); f.resc_pairs = c->d_resc.as<int>(); f.subset = 1;
+			if ((rc = launch_mark_primary(f, plan != 0, 0, c->stream))) return rc;
+			if (n_pairs > 0) {
+				f.subset = 2;
+				if ((rc = launch_mark_primary(f, plan != 0, n_pairs, c->stream))) return rc;
+			}
+			f.subset = 0;
+		} else if ((rc = launch_mark_primary(f, plan != 0, 0, c->stream))) return rc;
+		if ((rc = launch_kat_mapq(f, total, d_mq.as<int>(), c->stream))) return rc;
+		if ((total && (hipMemcpyAsync(h_f.data(), c->d_fregs.p, (size_t)total * sizeof(FinReg), hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+		               hipMemcpyAsync(h_need.data(), c->d_need.p, (size_t)total, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+		               hipMemcpyAsync(h_own.data(), c->d_xa_owner.p, (size_t)total * 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+		               hipMemcpyAsync(h_mq.data(), d_mq.p, (size_t)total * 8, hipMemcpyDeviceToHost, c->stream) != hipSuccess)) ||
+		    hipMemcpyAsync(h_fn.data(), c->d_freg_n.p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+		    hipMemcpyAsync(h_np.data(), c->d_npri.p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+		    hipMemcpyAsync(h_tn.data(), c->d_task_n.p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+		    hipMemcpyAsync(h_rn.data(), c->d_rec_n.p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess) return BWAHIP_ENODEV;
+		return 0;
+	};
+	rc = queue();
 	if (hipStreamSynchronize(c->stream) != hipSuccess && !rc) rc = BWAHIP_ENODEV;
-	d_mq.release();
 	if (rc) return rc;
 	auto hash_64 = [](uint64_t key) {                             // utils.h:97
 		key += ~(key << 32); key ^= (key >> 22); key += ~(key << 13); key ^= (key >> 8);
@@ -979,9 +981,11 @@ int pipe_open(bwahip_ctx *c, int n_threads)
 	if (!c) return BWAHIP_EINVAL;
 	HIP_TRY(hipSetDevice(c->device));
 	if (!c->pipe) {
-		c->pipe = new StreamPipe;
-		for (auto &s : c->pipe->in) HIP_TRY(hipEventCreateWithFlags(&s.ev, hipEventDisableTiming));
-		for (auto &s : c->pipe->pin) { HIP_TRY(hipEventCreateWithFlags(&s.ev_written, hipEventDisableTiming)); HIP_TRY(hipEventCreateWithFlags(&s.ev_copied, hipEventDisableTiming)); }
+		std::unique_ptr<StreamPipe> p(new StreamPipe);              // the context's only once all of it exists
+		int rc;
+		for (auto &s : p->in) if ((rc = s.ev.make(hipEventDisableTiming))) return rc;
+		for (auto &s : p->pin) if ((rc = s.ev_written.make(hipEventDisableTiming)) || (rc = s.ev_copied.make(hipEventDisableTiming))) return rc;
+		c->pipe = p.release();
 	}
 	c->pipe->pool.start(n_threads > 1 ? n_threads : 1);
 	return 0;
@@ -991,16 +995,12 @@ void pipe_close(bwahip_ctx *c)
 {
 	if (!c || !c->pipe) return;
 	(void)hipSetDevice(c->device);
-	for (hipStream_t s : { c->stream_copy, c->stream2, c->stream3, c->stream }) if (s) (void)hipStreamSynchronize(s);
+	for (const Stream *s : { &c->stream_copy, &c->stream2, &c->stream3, &c->stream }) if (*s) (void)hipStreamSynchronize(*s);
 	c->pipe->pool.stop();
 }
 
 void pipe_destroy(bwahip_ctx *c)
 {
-	if (!c->pipe) return;
-	for (auto &s : c->pipe->in) s.release();
-	for (auto &s : c->pipe->out) s.release();
-	for (auto &s : c->pipe->pin) s.release();
 	delete c->pipe;
 	c->pipe = nullptr;
 }

@@ -140,23 +140,16 @@ unsigned grid_of(int64_t n) { return (unsigned)((n + 255) / 256); }
 
 // The stage's buffers beside the context's sort buffers: counted by bwahip_bam_devmerge_bai_hbm_need below
 struct BaiStage {
-	DevBuf mlen, coff;                                             // per member: 4 + 8
-	DevBuf rk, pos, end, unm, head, hscan;                         // per record: 8 + 4 + 4 + 1 + 4 + 8
-	DevBuf cbeg, cend, keep, kscan;                                // per chunk before the join: 8 + 8 + 4 + 8 (and 24 of tab)
-	DevBuf first, last, top, n_unm, lin_off;                       // per reference: 4 + 4 + 4 + 4 + 8 (and 32 of tab)
-	DevBuf lin;                                                    // per window: 8 (and 8 of tab)
-	DevBuf err, tab;                                               // tab: what is downloaded -- chunk count | metadata | linear index | chunk keys, begins, ends
-	DevBuf addr, idx, off, rec;                                    // bwahip_kat_bai alone: the caller's records as a merger would hold them
+	Tally hbm;
+	DevBuf mlen{hbm}, coff{hbm};                                   // per member: 4 + 8
+	DevBuf rk{hbm}, pos{hbm}, end{hbm}, unm{hbm}, head{hbm}, hscan{hbm};   // per record: 8 + 4 + 4 + 1 + 4 + 8
+	DevBuf cbeg{hbm}, cend{hbm}, keep{hbm}, kscan{hbm};            // per chunk before the join: 8 + 8 + 4 + 8 (and 24 of tab)
+	DevBuf first{hbm}, last{hbm}, top{hbm}, n_unm{hbm}, lin_off{hbm};   // per reference: 4 + 4 + 4 + 4 + 8 (and 32 of tab)
+	DevBuf lin{hbm};                                               // per window: 8 (and 8 of tab)
+	DevBuf err{hbm}, tab{hbm};                                     // tab: what is downloaded -- chunk count | metadata | linear index | chunk keys, begins, ends
+	DevBuf addr{hbm}, idx{hbm}, off{hbm}, rec{hbm};                // bwahip_kat_bai alone: the caller's records as a merger would hold them
 	HostBuf h_tab, h_top;
-	hipEvent_t ev[2] = {};
-	std::vector<DevBuf*> all() { return { &mlen, &coff, &rk, &pos, &end, &unm, &head, &hscan, &cbeg, &cend, &keep, &kscan, &first, &last, &top, &n_unm, &lin_off, &lin, &err, &tab, &addr, &idx, &off, &rec }; }
-	size_t bytes() { size_t b = 0; for (DevBuf *d : all()) b += d->cap; return b; }
-	~BaiStage()
-	{
-		for (DevBuf *d : all()) d->release();
-		h_tab.release(); h_top.release();
-		for (auto &e : ev) if (e) (void)hipEventDestroy(e);
-	}
+	Event ev[2];
 };
 
 extern "C" int64_t bwahip_bam_devmerge_bai_hbm_need(int64_t n_records, int64_t n_blocks, int64_t n_ref, int64_t n_windows)
@@ -181,10 +174,10 @@ int bai_stage_parse_begin(BaiStage *s, bwahip_ctx *c, int n, int64_t n_blocks, i
 {
 	if (!s || !c || n <= 0 || n_ref < 0) return BWAHIP_EINVAL;
 	HIP_TRY(hipSetDevice(c->device));
-	for (auto &e : s->ev) if (!e) HIP_TRY(hipEventCreate(&e));
 	hipStream_t q = c->stream;
 	const size_t N = (size_t)n, R = (size_t)(n_ref ? n_ref : 1);
 	int rc;
+	for (auto &e : s->ev) if (!e && (rc = e.make())) return rc;
 	if ((rc = s->rk.ensure(N * 8)) || (rc = s->pos.ensure(N * 4)) || (rc = s->end.ensure(N * 4)) || (rc = s->unm.ensure(N)) || (rc = s->head.ensure(N * 4)) ||
 	    (rc = s->hscan.ensure((N + 1) * 8)) || (rc = s->coff.ensure(((size_t)n_blocks + 1) * 8)) || (rc = s->first.ensure(R * 4)) || (rc = s->last.ensure(R * 4)) ||
 	    (rc = s->top.ensure(R * 4)) || (rc = s->n_unm.ensure(R * 4)) || (rc = s->err.ensure(16)) || (rc = s->h_top.ensure(R * 4 + 32))) return rc;
@@ -293,7 +286,7 @@ int bai_stage_run(BaiStage *s, bwahip_ctx *c, int n, const uint8_t *const *addr,
 	if ((rc = bai_serialise(t, bytes))) return rc == BWAHIP_EINVAL ? BWAHIP_EINTERNAL : rc;
 	float ms = 0;
 	if (hipEventElapsedTime(&ms, s->ev[0], s->ev[1]) == hipSuccess) st.index_ms = ms;
-	st.n_chunks = t.n_chunks; st.n_windows = n_win; st.n_no_coor = (int64_t)t.n_no_coor; st.bai_bytes = (int64_t)bytes->size(); st.hbm_bytes = (int64_t)s->bytes();
+	st.n_chunks = t.n_chunks; st.n_windows = n_win; st.n_no_coor = (int64_t)t.n_no_coor; st.bai_bytes = (int64_t)bytes->size(); st.hbm_bytes = (int64_t)s->hbm.bytes;
 	if (bs) *bs = st;
 	return 0;
 }

@@ -109,38 +109,20 @@ __global__ __launch_bounds__(256) void k_gather_window(const uint8_t *const *add
 
 int launched() { return hipGetLastError() == hipSuccess ? 0 : BWAHIP_ENODEV; }
 
-int dev_alloc(void **p, size_t bytes)
-{
-	*p = nullptr;
-	++g_bwahip_reallocs;
-	if (hipMalloc(p, bytes ? bytes : 1) != hipSuccess) { (void)hipGetLastError(); *p = nullptr; fprintf(stderr, "[bwahip] sorted BAM: hipMalloc(%zu) for a run failed\n", bytes); return BWAHIP_ENOMEM; }
-	return 0;
-}
-
 // finish()'s buffers beside the context's (bs.keys / bs.idx / bs.hist*, bz.*): counted by bwahip_bam_devmerge_hbm_need below
 struct Work {
-	DevBuf first, run_rec, run_off, run_len;                       // per run
-	DevBuf addr, len, len_sorted, out_off, err;                    // per record: 8 + 4 + 4 + 8 bytes
-	DevBuf piece_first;                                            // per piece
-	DevBuf in[2], out[2], tot[2];                                  // per piece of piece_blocks blocks: input, members (input + 31 per block), their total
+	Tally hbm;
+	DevBuf first{hbm}, run_rec{hbm}, run_off{hbm}, run_len{hbm};   // per run
+	DevBuf addr{hbm}, len{hbm}, len_sorted{hbm}, out_off{hbm}, err{hbm};   // per record: 8 + 4 + 4 + 8 bytes
+	DevBuf piece_first{hbm};                                       // per piece
+	DevBuf in[2] = { DevBuf{hbm}, DevBuf{hbm} }, out[2] = { DevBuf{hbm}, DevBuf{hbm} }, tot[2] = { DevBuf{hbm}, DevBuf{hbm} };   // per piece of piece_blocks blocks: input, members (input + 31 per block), their total
 	HostBuf h_out[2], h_tot;
-	hipEvent_t ev_gather[2] = {}, ev_deflate[2] = {}, ev_done[2] = {}, ev_down[2] = {}, ev_sort[2] = {};
+	Event ev_gather[2], ev_deflate[2], ev_done[2], ev_down[2], ev_sort[2];
 	int make_events()
 	{
-		for (auto *set : { ev_gather, ev_deflate, ev_done, ev_down, ev_sort }) for (int k = 0; k < 2; ++k) if (!set[k]) HIP_TRY(hipEventCreate(&set[k]));
+		int rc;
+		for (Event *set : { ev_gather, ev_deflate, ev_done, ev_down, ev_sort }) for (int k = 0; k < 2; ++k) if (!set[k] && (rc = set[k].make())) return rc;
 		return 0;
-	}
-	size_t bytes() const
-	{
-		size_t b = 0;
-		for (const DevBuf *d : { &first, &run_rec, &run_off, &run_len, &addr, &len, &len_sorted, &out_off, &err, &piece_first, &in[0], &in[1], &out[0], &out[1], &tot[0], &tot[1] }) b += d->cap;
-		return b;
-	}
-	void release()
-	{
-		for (DevBuf *d : { &first, &run_rec, &run_off, &run_len, &addr, &len, &len_sorted, &out_off, &err, &piece_first, &in[0], &in[1], &out[0], &out[1], &tot[0], &tot[1] }) d->release();
-		h_out[0].release(); h_out[1].release(); h_tot.release();
-		for (auto *set : { ev_gather, ev_deflate, ev_done, ev_down, ev_sort }) for (int k = 0; k < 2; ++k) if (set[k]) { (void)hipEventDestroy(set[k]); set[k] = nullptr; }
 	}
 };
 
@@ -157,20 +139,15 @@ int write_full(int fd, const uint8_t *b, int64_t len)
 
 // a merger with spilled runs: the staging of the windows (counted by bwahip_bam_devmerge_spill_hbm_need, k_bamspill.hip)
 struct SpillWork {
-	DevBuf stage[2], cut, base, flags, scratch;                    // two windows' slices; per run and window: the cuts, the slices' bases; per run: spilled or not; a counter nobody reads
+	Tally hbm;
+	DevBuf stage[2] = { DevBuf{hbm}, DevBuf{hbm} }, cut{hbm}, base{hbm}, flags{hbm}, scratch{hbm};   // two windows' slices; per run and window: the cuts, the slices' bases; per run: spilled or not; a counter nobody reads
 	HostBuf bounce[2];                                             // file-backed runs: pread lands here, at the slice's place in the window
-	hipEvent_t ev_up0[2] = {}, ev_up[2] = {}, ev_used[2] = {};     // a window's upload begun / done (copy stream); its last reader queued (context's stream)
+	Event ev_up0[2], ev_up[2], ev_used[2];                         // a window's upload begun / done (copy stream); its last reader queued (context's stream)
 	int make_events()
 	{
-		for (auto *set : { ev_up0, ev_up, ev_used }) for (int k = 0; k < 2; ++k) if (!set[k]) HIP_TRY(hipEventCreate(&set[k]));
+		int rc;
+		for (Event *set : { ev_up0, ev_up, ev_used }) for (int k = 0; k < 2; ++k) if (!set[k] && (rc = set[k].make())) return rc;
 		return 0;
-	}
-	size_t bytes() const { size_t b = 0; for (const DevBuf *d : { &stage[0], &stage[1], &cut, &base, &flags, &scratch }) b += d->cap; return b; }
-	void release()
-	{
-		for (DevBuf *d : { &stage[0], &stage[1], &cut, &base, &flags, &scratch }) d->release();
-		bounce[0].release(); bounce[1].release();
-		for (auto *set : { ev_up0, ev_up, ev_used }) for (int k = 0; k < 2; ++k) if (set[k]) { (void)hipEventDestroy(set[k]); set[k] = nullptr; }
 	}
 };
 
@@ -178,12 +155,11 @@ constexpr int DEFAULT_WINDOW_PIECES = 8;                          // with 1 024 
 
 void *pinned_alloc(size_t bytes, void *ctx)
 {
-	void *p = nullptr;
-	if (hipSetDevice(((bwahip_ctx*)ctx)->device) != hipSuccess || hipHostMalloc(&p, bytes ? bytes : 1, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
-	++g_bwahip_reallocs;
+	void *p = hipSetDevice(((bwahip_ctx*)ctx)->device) == hipSuccess ? PinnedMem::alloc(bytes) : nullptr;
+	if (p) PinnedMem::count_sync();
 	return p;
 }
-void pinned_free(void *p, size_t, void *) { if (p) { (void)hipHostFree(p); ++g_bwahip_reallocs; } }
+void pinned_free(void *p, size_t bytes, void *) { if (p) { PinnedMem::free(p, bytes); PinnedMem::count_sync(); } }
 
 } // namespace
 
@@ -209,9 +185,9 @@ struct bwahip_bam_devmerger {
 	std::map<int64_t, DevRun*> runs;                               // by run_no: the order of the concatenation
 	int64_t n_records = 0, raw_bytes = 0;
 	Work w;
-	BaiStage *bai = nullptr;                                       // the stages' buffers (k_bai.hip, k_markdup.hip, k_qc.hip): each made by the first finish that runs the stage
-	MarkdupStage *md = nullptr;
-	QcStage *qc = nullptr;
+	std::unique_ptr<BaiStage, void (*)(BaiStage*)> bai{ nullptr, bai_stage_free };   // the stages' buffers (k_bai.hip, k_markdup.hip, k_qc.hip): each made by the first finish that runs the stage
+	std::unique_ptr<MarkdupStage> md;
+	std::unique_ptr<QcStage, void (*)(QcStage*)> qc{ nullptr, qc_stage_free };
 	// spilled runs (bwahip_bam_devmerger_set_spill): the store of their record bytes, the windows' staging
 	HostBuf dl_bounce;                                             // bam_devmerger_adopt_spilled: a file-backed run's bytes on their way from HBM
 	bool spill_armed = false, added = false; int window_pieces = 0; SpillStore *store = nullptr; SpillWork sw;
@@ -228,10 +204,10 @@ int bam_devrun_make(bwahip_ctx *c, const uint8_t *d_rec, int64_t len, const uint
 	r->n_rec = n_rec; r->len = len; r->device = c->device;
 	if (n_rec) {
 		int rc;
-		if ((rc = dev_alloc((void**)&r->rec, (size_t)len)) || (rc = dev_alloc((void**)&r->keys, (size_t)n_rec * 8)) || (rc = dev_alloc((void**)&r->off, (size_t)(n_rec + 1) * 8))) { bam_devrun_free(r); return rc; }
-		hipError_t e = len ? hipMemcpyAsync(r->rec, d_rec, (size_t)len, hipMemcpyDeviceToDevice, st) : hipSuccess;
-		if (e == hipSuccess) e = hipMemcpyAsync(r->keys, d_keys, (size_t)n_rec * 8, hipMemcpyDeviceToDevice, st);
-		if (e == hipSuccess) e = hipMemcpyAsync(r->off, d_rec_off, (size_t)(n_rec + 1) * 8, hipMemcpyDeviceToDevice, st);
+		if ((rc = r->d_rec.alloc_exact((size_t)len)) || (rc = r->d_keys.alloc_exact((size_t)n_rec * 8)) || (rc = r->d_off.alloc_exact((size_t)(n_rec + 1) * 8))) { bam_devrun_free(r); return rc; }
+		hipError_t e = len ? hipMemcpyAsync(r->rec(), d_rec, (size_t)len, hipMemcpyDeviceToDevice, st) : hipSuccess;
+		if (e == hipSuccess) e = hipMemcpyAsync(r->keys(), d_keys, (size_t)n_rec * 8, hipMemcpyDeviceToDevice, st);
+		if (e == hipSuccess) e = hipMemcpyAsync(r->off(), d_rec_off, (size_t)(n_rec + 1) * 8, hipMemcpyDeviceToDevice, st);
 		if (e == hipSuccess) e = hipStreamSynchronize(st);
 		if (e != hipSuccess) { fprintf(stderr, "[bwahip] sorted BAM: copying a run failed: %s\n", hipGetErrorString(e)); bam_devrun_free(r); return BWAHIP_ENODEV; }
 	}
@@ -245,9 +221,9 @@ int bam_devrun_download(const DevRun *r, uint8_t *rec, uint64_t *keys, int64_t *
 	if (!r->n_rec) { rec_off[0] = 0; return 0; }
 	if (!rec || !keys) return BWAHIP_EINVAL;
 	HIP_TRY(hipSetDevice(r->device));
-	if (r->len) HIP_TRY(hipMemcpyAsync(rec, r->rec, (size_t)r->len, hipMemcpyDeviceToHost, st));
-	HIP_TRY(hipMemcpyAsync(keys, r->keys, (size_t)r->n_rec * 8, hipMemcpyDeviceToHost, st));
-	HIP_TRY(hipMemcpyAsync(rec_off, r->off, (size_t)(r->n_rec + 1) * 8, hipMemcpyDeviceToHost, st));
+	if (r->len) HIP_TRY(hipMemcpyAsync(rec, r->rec(), (size_t)r->len, hipMemcpyDeviceToHost, st));
+	HIP_TRY(hipMemcpyAsync(keys, r->keys(), (size_t)r->n_rec * 8, hipMemcpyDeviceToHost, st));
+	HIP_TRY(hipMemcpyAsync(rec_off, r->off(), (size_t)(r->n_rec + 1) * 8, hipMemcpyDeviceToHost, st));
 	HIP_TRY(hipStreamSynchronize(st));
 	return 0;
 }
@@ -256,7 +232,6 @@ void bam_devrun_free(DevRun *r)
 {
 	if (!r) return;
 	(void)hipSetDevice(r->device);
-	for (void *p : { (void*)r->rec, (void*)r->keys, (void*)r->off, (void*)r->tmpl, (void*)r->desc }) if (p) { (void)hipFree(p); ++g_bwahip_reallocs; }
 	delete r;
 }
 
@@ -264,14 +239,14 @@ int bam_devrun_add_dup(DevRun *r, const uint32_t *d_tmpl, const bwahip_dup_desc_
 {
 	if (!r || r->has_dup || n_tmpl < 0 || (r->n_rec && !d_tmpl) || (n_tmpl && !d_desc)) return BWAHIP_EINVAL;
 	HIP_TRY(hipSetDevice(r->device));
-	uint32_t *t = nullptr; bwahip_dup_desc_t *d = nullptr;
+	DevBuf t, d;                                                   // the run's once both are filled
 	int rc;
-	if ((r->n_rec && (rc = dev_alloc((void**)&t, (size_t)r->n_rec * 4))) || (n_tmpl && (rc = dev_alloc((void**)&d, (size_t)n_tmpl * sizeof *d)))) { if (t) (void)hipFree(t); return rc; }
-	hipError_t e = r->n_rec ? hipMemcpyAsync(t, d_tmpl, (size_t)r->n_rec * 4, hipMemcpyDeviceToDevice, st) : hipSuccess;
-	if (e == hipSuccess && n_tmpl) e = hipMemcpyAsync(d, d_desc, (size_t)n_tmpl * sizeof *d, hipMemcpyDeviceToDevice, st);
+	if ((r->n_rec && (rc = t.alloc_exact((size_t)r->n_rec * 4))) || (n_tmpl && (rc = d.alloc_exact((size_t)n_tmpl * sizeof *d_desc)))) return rc;
+	hipError_t e = r->n_rec ? hipMemcpyAsync(t.p, d_tmpl, (size_t)r->n_rec * 4, hipMemcpyDeviceToDevice, st) : hipSuccess;
+	if (e == hipSuccess && n_tmpl) e = hipMemcpyAsync(d.p, d_desc, (size_t)n_tmpl * sizeof *d_desc, hipMemcpyDeviceToDevice, st);
 	if (e == hipSuccess) e = hipStreamSynchronize(st);
-	if (e != hipSuccess) { fprintf(stderr, "[bwahip] sorted BAM: copying a run's templates failed: %s\n", hipGetErrorString(e)); if (t) (void)hipFree(t); if (d) (void)hipFree(d); return BWAHIP_ENODEV; }
-	r->tmpl = t; r->desc = d; r->n_tmpl = n_tmpl; r->has_dup = true;
+	if (e != hipSuccess) { fprintf(stderr, "[bwahip] sorted BAM: copying a run's templates failed: %s\n", hipGetErrorString(e)); return BWAHIP_ENODEV; }
+	r->d_tmpl = std::move(t); r->d_desc = std::move(d); r->n_tmpl = n_tmpl; r->has_dup = true;
 	return 0;
 }
 
@@ -302,25 +277,24 @@ int bam_devmerger_adopt_spilled(bwahip_bam_devmerger *m, int64_t run_no, DevRun 
 	int rc = spill_store_reserve(m->store, run_no, r->len, &mem);
 	if (rc) return rc;
 	std::vector<int64_t> h_off((size_t)(r->n_rec ? r->n_rec + 1 : 0));
-	hipError_t e = r->n_rec ? hipMemcpyAsync(h_off.data(), r->off, h_off.size() * 8, hipMemcpyDeviceToHost, st) : hipSuccess;
-	if (e == hipSuccess && mem) e = hipMemcpyAsync(mem, r->rec, (size_t)r->len, hipMemcpyDeviceToHost, st);
+	hipError_t e = r->n_rec ? hipMemcpyAsync(h_off.data(), r->off(), h_off.size() * 8, hipMemcpyDeviceToHost, st) : hipSuccess;
+	if (e == hipSuccess && mem) e = hipMemcpyAsync(mem, r->rec(), (size_t)r->len, hipMemcpyDeviceToHost, st);
 	if (e == hipSuccess) e = hipStreamSynchronize(st);
 	if (e == hipSuccess && !mem && r->len) {                       // a file: through the pinned bounce buffer, 64 MiB at a time
 		const int64_t step = 64ll << 20;
 		if (!(rc = m->dl_bounce.ensure((size_t)(r->len < step ? r->len : step))))
 			for (int64_t at = 0; at < r->len && !rc && e == hipSuccess; at += step) {
 				const int64_t part = r->len - at < step ? r->len - at : step;
-				e = hipMemcpyAsync(m->dl_bounce.p, r->rec + at, (size_t)part, hipMemcpyDeviceToHost, st);
+				e = hipMemcpyAsync(m->dl_bounce.p, r->rec() + at, (size_t)part, hipMemcpyDeviceToHost, st);
 				if (e == hipSuccess) e = hipStreamSynchronize(st);
 				if (e == hipSuccess) rc = spill_store_write(m->store, run_no, at, (const uint8_t*)m->dl_bounce.p, part);
 			}
 	}
 	if (e != hipSuccess) { fprintf(stderr, "[bwahip] sorted BAM: downloading a spilled run failed: %s\n", hipGetErrorString(e)); rc = BWAHIP_ENODEV; }
 	if (rc) { (void)spill_store_drop(m->store, run_no); return rc; }
-	uint8_t *d_rec = r->rec;
-	r->rec = nullptr; r->spilled = true; r->h_off.swap(h_off);
-	if ((rc = bam_devmerger_adopt(m, run_no, r))) { r->rec = d_rec; r->spilled = false; r->h_off.clear(); (void)spill_store_drop(m->store, run_no); return rc; }
-	if (d_rec) { (void)hipFree(d_rec); ++g_bwahip_reallocs; }
+	r->spilled = true; r->h_off.swap(h_off);
+	if ((rc = bam_devmerger_adopt(m, run_no, r))) { r->spilled = false; r->h_off.clear(); (void)spill_store_drop(m->store, run_no); return rc; }
+	r->d_rec.release();                                            // adopted: only now do the record bytes leave HBM
 	if (longest) { *longest = 0; for (int64_t i = 0; i < r->n_rec; ++i) if (r->h_off[(size_t)i + 1] - r->h_off[(size_t)i] > *longest) *longest = r->h_off[(size_t)i + 1] - r->h_off[(size_t)i]; }
 	std::lock_guard<std::mutex> lk(m->mu);
 	m->download_s += now_s() - t0;
@@ -397,19 +371,19 @@ static int devmerger_add(bwahip_bam_devmerger *m, int64_t run_no, const uint8_t 
 	if (spill) r->h_off.assign(rec_off, rec_off + (n_rec ? n_rec + 1 : 0));
 	struct Undo { bwahip_bam_devmerger *m; int64_t id; bool on; ~Undo() { if (on) (void)spill_store_drop(m->store, id); } } undo = { m, run_no, spill };   // a refused run leaves the store as it was
 	if (n_rec) {
-		if ((!spill && (rc = dev_alloc((void**)&r->rec, (size_t)len))) || (rc = dev_alloc((void**)&r->keys, (size_t)n_rec * 8)) || (rc = dev_alloc((void**)&r->off, (size_t)(n_rec + 1) * 8))) { bam_devrun_free(r); return rc; }
+		if ((!spill && (rc = r->d_rec.alloc_exact((size_t)len))) || (rc = r->d_keys.alloc_exact((size_t)n_rec * 8)) || (rc = r->d_off.alloc_exact((size_t)(n_rec + 1) * 8))) { bam_devrun_free(r); return rc; }
 		// plain copies: they return when the caller's memory has been read, whatever thread and stream
-		hipError_t e = len && !spill ? hipMemcpy(r->rec, rec, (size_t)len, hipMemcpyHostToDevice) : hipSuccess;
-		if (e == hipSuccess) e = hipMemcpy(r->keys, keys, (size_t)n_rec * 8, hipMemcpyHostToDevice);
-		if (e == hipSuccess) e = hipMemcpy(r->off, rec_off, (size_t)(n_rec + 1) * 8, hipMemcpyHostToDevice);
-		if (e == hipSuccess && with_dup && (rc = dev_alloc((void**)&r->tmpl, (size_t)n_rec * 4))) { bam_devrun_free(r); return rc; }
-		if (e == hipSuccess && with_dup) e = hipMemcpy(r->tmpl, tmpl, (size_t)n_rec * 4, hipMemcpyHostToDevice);
+		hipError_t e = len && !spill ? hipMemcpy(r->rec(), rec, (size_t)len, hipMemcpyHostToDevice) : hipSuccess;
+		if (e == hipSuccess) e = hipMemcpy(r->keys(), keys, (size_t)n_rec * 8, hipMemcpyHostToDevice);
+		if (e == hipSuccess) e = hipMemcpy(r->off(), rec_off, (size_t)(n_rec + 1) * 8, hipMemcpyHostToDevice);
+		if (e == hipSuccess && with_dup && (rc = r->d_tmpl.alloc_exact((size_t)n_rec * 4))) { bam_devrun_free(r); return rc; }
+		if (e == hipSuccess && with_dup) e = hipMemcpy(r->tmpl(), tmpl, (size_t)n_rec * 4, hipMemcpyHostToDevice);
 		if (e == hipSuccess) e = hipDeviceSynchronize();
 		if (e != hipSuccess) { fprintf(stderr, "[bwahip] sorted BAM: uploading a run failed: %s\n", hipGetErrorString(e)); bam_devrun_free(r); return BWAHIP_ENODEV; }
 	}
 	if (with_dup && n_tmpl) {
-		if ((rc = dev_alloc((void**)&r->desc, (size_t)n_tmpl * sizeof *desc))) { bam_devrun_free(r); return rc; }
-		if (hipMemcpy(r->desc, desc, (size_t)n_tmpl * sizeof *desc, hipMemcpyHostToDevice) != hipSuccess || hipDeviceSynchronize() != hipSuccess) { bam_devrun_free(r); return BWAHIP_ENODEV; }
+		if ((rc = r->d_desc.alloc_exact((size_t)n_tmpl * sizeof *desc))) { bam_devrun_free(r); return rc; }
+		if (hipMemcpy(r->desc(), desc, (size_t)n_tmpl * sizeof *desc, hipMemcpyHostToDevice) != hipSuccess || hipDeviceSynchronize() != hipSuccess) { bam_devrun_free(r); return BWAHIP_ENODEV; }
 	}
 	r->has_dup = with_dup; r->n_tmpl = with_dup ? n_tmpl : 0;
 	if ((rc = bam_devmerger_adopt(m, run_no, r))) bam_devrun_free(r);
@@ -456,7 +430,7 @@ extern "C" int bwahip_bam_devmerger_spill_stats(bwahip_bam_devmerger *m, bwahip_
 	out->n_spilled_runs = m->n_spilled; out->first_spilled_run = -1;
 	for (auto &kv : m->runs) if (kv.second->spilled) { out->first_spilled_run = kv.first; break; }
 	out->host_bytes = spill_store_host_bytes(m->store); out->file_bytes = spill_store_file_bytes(m->store);
-	out->n_windows = m->n_windows; out->window_hbm_bytes = (int64_t)m->sw.bytes();
+	out->n_windows = m->n_windows; out->window_hbm_bytes = (int64_t)m->sw.hbm.bytes;
 	out->download_s = m->download_s; out->upload_ms = m->upload_ms;
 	return 0;
 }
@@ -474,14 +448,14 @@ int mark_decide(bwahip_bam_devmerger *m)
 	for (auto &kv : m->runs) T += kv.second->n_tmpl;
 	if (T > 0x3fffffffll) return BWAHIP_ECAPACITY;
 	HIP_TRY(hipSetDevice(c->device));
-	for (auto &e : s.ev) if (!e) HIP_TRY(hipEventCreate(&e));
 	int rc;
+	for (auto &e : s.ev) if (!e && (rc = e.make())) return rc;
 	if ((rc = s.desc.ensure((size_t)(T ? T : 1) * sizeof(bwahip_dup_desc_t)))) return rc;
 	HIP_TRY(hipEventRecord(s.ev[0], c->stream));
 	int64_t at = 0;
 	for (auto &kv : m->runs) {
 		const DevRun *r = kv.second;
-		if (r->n_tmpl) HIP_TRY(hipMemcpyAsync(s.desc.as<bwahip_dup_desc_t>() + at, r->desc, (size_t)r->n_tmpl * sizeof(bwahip_dup_desc_t), hipMemcpyDeviceToDevice, c->stream));
+		if (r->n_tmpl) HIP_TRY(hipMemcpyAsync(s.desc.as<bwahip_dup_desc_t>() + at, r->desc(), (size_t)r->n_tmpl * sizeof(bwahip_dup_desc_t), hipMemcpyDeviceToDevice, c->stream));
 		at += r->n_tmpl;
 	}
 	if ((rc = markdup_decide(&s, c, T))) return rc;
@@ -506,7 +480,7 @@ int mark_end(bwahip_bam_devmerger *m, bwahip_markdup_stats_t *ms)
 		for (int k = 0; k < 3; ++k) { ms->n_templates[k] = (int64_t)cnt[k]; ms->n_dup_templates[k] = (int64_t)cnt[3 + k]; }
 		ms->n_marked = (int64_t)cnt[6];
 		const BamSort &bs = c->bs;
-		ms->hbm_bytes = run_bytes + (int64_t)(s.bytes() + bs.keys[0].cap + bs.keys[1].cap + bs.idx[0].cap + bs.idx[1].cap);
+		ms->hbm_bytes = run_bytes + (int64_t)(s.hbm.bytes + bs.keys[0].cap + bs.keys[1].cap + bs.idx[0].cap + bs.idx[1].cap);
 		float t = 0;
 		if (hipEventElapsedTime(&t, s.ev[0], s.ev[2]) == hipSuccess) ms->markdup_ms = t;
 		if (hipEventElapsedTime(&t, s.ev[0], s.ev[1]) == hipSuccess) ms->decide_ms = t;
@@ -542,25 +516,25 @@ struct Finish {
 	{
 		int rc;
 		if (which & RS_MARK) {
-			if ((rc = markdup_mark_run(m->md, c, rec, r->off + lo, counted - lo, r->len, r->tmpl + lo, tmpl0, r->n_tmpl))) return rc;
-			if (hi > counted && (rc = markdup_mark_run(m->md, c, rec, r->off + counted, hi - counted, r->len, r->tmpl + counted, tmpl0, r->n_tmpl, sw.scratch.as<unsigned long long>()))) return rc;
+			if ((rc = markdup_mark_run(m->md.get(), c, rec, r->off() + lo, counted - lo, r->len, r->tmpl() + lo, tmpl0, r->n_tmpl))) return rc;
+			if (hi > counted && (rc = markdup_mark_run(m->md.get(), c, rec, r->off() + counted, hi - counted, r->len, r->tmpl() + counted, tmpl0, r->n_tmpl, sw.scratch.as<unsigned long long>()))) return rc;
 		}
-		return which & RS_QC ? qc_stage_records(m->qc, c, rec, r->off + lo, counted - lo, r->len, ord0 + lo) : 0;
+		return which & RS_QC ? qc_stage_records(m->qc.get(), c, rec, r->off() + lo, counted - lo, r->len, ord0 + lo) : 0;
 	}
 	// The records pass is over for the stages `which`: each awaits the stream, the counters and the tables come back.  Without a spilled run that is
 	// before the order, stage by stage (resident_pass); with one, after the last window (tail)
 	int records_done(int which)
 	{
 		int rc = which & RS_MARK ? mark_end(m, plan.ms) : 0;
-		if (!rc && (which & RS_QC)) rc = qc_stage_finish(m->qc, c, &qc_bytes, m->qc_stats);
+		if (!rc && (which & RS_QC)) rc = qc_stage_finish(m->qc.get(), c, &qc_bytes, m->qc_stats);
 		return rc;
 	}
 	int checks()
 	{
 		if (plan.mark) for (auto &kv : m->runs) if (!kv.second->has_dup) return BWAHIP_EINVAL;   // before a byte is written
-		if (plan.mark && !m->md) m->md = new MarkdupStage;
-		if (plan.qc && !m->qc) m->qc = qc_stage_new();
-		if (plan.index && !m->bai) m->bai = bai_stage_new();
+		if (plan.mark && !m->md) m->md.reset(new MarkdupStage);
+		if (plan.qc && !m->qc) m->qc.reset(qc_stage_new());
+		if (plan.index && !m->bai) m->bai.reset(bai_stage_new());
 		memset(&s, 0, sizeof s);
 		s.n_records = m->n_records; s.n_runs = (int64_t)m->runs.size(); s.raw_bytes = m->raw_bytes; s.n_blocks = bgzf_blocks(m->raw_bytes);
 		for (auto &kv : m->runs) s.hbm_bytes += kv.second->n_rec ? (kv.second->spilled ? 0 : kv.second->len) + 16 * kv.second->n_rec + 8 : 0;
@@ -572,11 +546,11 @@ struct Finish {
 	{
 		for (int stage : { RS_MARK, RS_QC }) {
 			if (!(stages() & stage)) continue;
-			int rc = stage == RS_MARK ? mark_decide(m) : qc_stage_begin(m->qc, c, (int32_t)m->qc_len.size(), m->qc_len.data(), m->qc_opt, m->n_records);
+			int rc = stage == RS_MARK ? mark_decide(m) : qc_stage_begin(m->qc.get(), c, (int32_t)m->qc_len.size(), m->qc_len.data(), m->qc_opt, m->n_records);
 			int64_t ord = 0, tmpl = 0;
 			for (auto &kv : m->runs) {
 				const DevRun *r = kv.second;
-				if (!rc && !r->spilled) rc = records_pass(stage, r, r->rec, 0, r->n_rec, r->n_rec, ord, tmpl);
+				if (!rc && !r->spilled) rc = records_pass(stage, r, r->rec(), 0, r->n_rec, r->n_rec, ord, tmpl);
 				ord += r->n_rec; tmpl += r->n_tmpl;
 			}
 			if (!rc && !plan.spill) rc = records_done(stage);
@@ -596,8 +570,8 @@ struct Finish {
 		int64_t at = 0;
 		for (auto &kv : m->runs) {
 			const DevRun *r = kv.second;
-			first.push_back(at); run_rec.push_back(r->rec); run_off.push_back(r->off); run_len.push_back(r->len);
-			if (r->n_rec) HIP_TRY(hipMemcpyAsync(bs.keys[0].as<uint64_t>() + at, r->keys, (size_t)r->n_rec * 8, hipMemcpyDeviceToDevice, c->stream));
+			first.push_back(at); run_rec.push_back(r->rec()); run_off.push_back(r->off()); run_len.push_back(r->len);
+			if (r->n_rec) HIP_TRY(hipMemcpyAsync(bs.keys[0].as<uint64_t>() + at, r->keys(), (size_t)r->n_rec * 8, hipMemcpyDeviceToDevice, c->stream));
 			at += r->n_rec;
 		}
 		first.push_back(at);
@@ -652,7 +626,7 @@ struct Finish {
 		for (int k = 0; k < 2; ++k)
 			if ((rc = w.in[k].ensure((size_t)in_cap)) || (rc = w.out[k].ensure((size_t)out_cap)) || (rc = w.tot[k].ensure(16)) || (rc = w.h_out[k].ensure((size_t)out_cap))) return rc;
 		if ((rc = w.h_tot.ensure(32))) return rc;
-		return plan.index ? bai_stage_members(m->bai, s.n_blocks, &mlen_all) : 0;
+		return plan.index ? bai_stage_members(m->bai.get(), s.n_blocks, &mlen_all) : 0;
 	}
 	// spilled runs: the windows' cuts, the plan of the slices every window stages, the staging buffers and the slices' bases
 	int windows()
@@ -688,7 +662,7 @@ struct Finish {
 				base[(size_t)wd * NR + r] = (int64_t)(uintptr_t)sw.stage[wd & 1].p + sp.slice_at[(size_t)wd * NR + r] - runv[r]->h_off[(size_t)lo];
 			}
 		if ((rc = dev_upload(sw.base, base.data(), base.size() * 8, c->stream))) return rc;
-		if (plan.index) { if ((rc = bai_stage_parse_begin(m->bai, c, n, s.n_blocks, plan.n_ref))) return rc; parsed = true; }
+		if (plan.index) { if ((rc = bai_stage_parse_begin(m->bai.get(), c, n, s.n_blocks, plan.n_ref))) return rc; parsed = true; }
 		m->n_windows = sp.n_windows; m->upload_ms = 0;
 		return 0;
 	}
@@ -740,7 +714,7 @@ struct Finish {
 	int window_end(int wd)
 	{
 		int rc;
-		if (plan.index && (rc = bai_stage_parse(m->bai, c, sp.first[(size_t)wd] + (wd > 0), wd + 1 < sp.n_windows ? sp.first[(size_t)wd + 1] + 1 : n, w.addr.as<const uint8_t*>(), idx,
+		if (plan.index && (rc = bai_stage_parse(m->bai.get(), c, sp.first[(size_t)wd] + (wd > 0), wd + 1 < sp.n_windows ? sp.first[(size_t)wd + 1] + 1 : n, w.addr.as<const uint8_t*>(), idx,
 		                                        w.out_off.as<int64_t>(), plan.n_ref))) return rc;
 		HIP_TRY(hipEventRecord(sw.ev_used[wd & 1], c->stream));
 		return 0;
@@ -803,7 +777,7 @@ struct Finish {
 		const BamSort &bs = c->bs;
 		float ms = 0;
 		if (hipEventElapsedTime(&ms, w.ev_sort[0], w.ev_sort[1]) == hipSuccess) s.sort_ms = ms;
-		s.hbm_bytes += (int64_t)(w.bytes() + bs.keys[0].cap + bs.keys[1].cap + bs.idx[0].cap + bs.idx[1].cap + bs.hist.cap + bs.hist_base.cap +
+		s.hbm_bytes += (int64_t)(w.hbm.bytes + bs.keys[0].cap + bs.keys[1].cap + bs.idx[0].cap + bs.idx[1].cap + bs.hist.cap + bs.hist_base.cap +
 		                           c->bz.slots.cap + c->bz.mlen.cap + c->bz.moff.cap + c->bz.md.cap + c->bz.cnt.cap);
 		for (int k = 0, nw = sp.n_windows; plan.spill && k < 2 && k < nw; ++k)   // the last two windows' uploads: no later one has read their events
 			if (hipEventElapsedTime(&ms, sw.ev_up0[(nw - 1 - k) & 1], sw.ev_up[(nw - 1 - k) & 1]) == hipSuccess) m->upload_ms += ms;
@@ -816,7 +790,7 @@ struct Finish {
 		if (!rc && plan.index) {
 			std::vector<uint8_t> bytes;
 			if (!total && n) rc = BWAHIP_EINVAL;                    // records without a byte cannot be indexed
-			else rc = bai_stage_run(m->bai, c, n, w.addr.as<const uint8_t*>(), idx, w.out_off.as<int64_t>(), total, bgzf_blocks(total), plan.base, plan.n_ref, &bytes, plan.bs, parsed);
+			else rc = bai_stage_run(m->bai.get(), c, n, w.addr.as<const uint8_t*>(), idx, w.out_off.as<int64_t>(), total, bgzf_blocks(total), plan.base, plan.n_ref, &bytes, plan.bs, parsed);
 			if (!rc) rc = bai_write_fd(plan.bai_fd, bytes);
 		}
 		if (!rc && plan.qc) rc = qc_write_fd(m->qc_fd, qc_bytes);
@@ -879,11 +853,8 @@ extern "C" void bwahip_bam_devmerger_close(bwahip_bam_devmerger *m)
 {
 	if (!m) return;
 	(void)hipSetDevice(m->c->device);
-	for (hipStream_t q : { m->c->stream_copy, m->c->stream }) if (q) (void)hipStreamSynchronize(q);   // after a failed finish work may still be queued on the buffers
+	for (const Stream *q : { &m->c->stream_copy, &m->c->stream }) if (*q) (void)hipStreamSynchronize(*q);   // after a failed finish work may still be queued on the buffers
 	for (auto &kv : m->runs) bam_devrun_free(kv.second);
-	m->w.release(); m->sw.release(); m->dl_bounce.release();
 	spill_store_free(m->store);
-	bai_stage_free(m->bai); qc_stage_free(m->qc);
-	if (m->md) { m->md->release(); delete m->md; }
-	delete m;
+	delete m;                                                      // the stages, the work buffers and their events go with it
 }

@@ -225,8 +225,8 @@ int bam_sort_batch(bwahip_ctx *c, int n, int64_t total, int dup_tmpl)
 	BamSort &s = c->bs;
 	c->out->n_rec = 0; s.n_passes = 0;
 	if (n <= 0) return 0;
-	for (auto &e : c->out->ev_sort) if (!e) HIP_TRY(hipEventCreate(&e));
 	int rc;
+	for (auto &e : c->out->ev_sort) if (!e && (rc = e.make())) return rc;
 	if ((rc = s.rec_cnt.ensure((size_t)n * 4)) || (rc = s.rec_base.ensure(((size_t)n + 1) * 8)) || (rc = s.bits.ensure(16))) return rc;
 	const uint8_t *raw = s.raw.as<uint8_t>();
 	const int64_t *off = c->out->d_sam_off.as<int64_t>();

@@ -244,13 +244,6 @@ extern "C" int64_t bwahip_bam_devmerge_markdup_hbm_need(int64_t n_records, int64
 	return runs + work + work / 8;
 }
 
-size_t MarkdupStage::bytes() const { size_t b = 0; for (const DevBuf *d : { &desc, &head, &seg, &best, &pair_here, &dup, &cnt }) b += d->cap; return b; }
-void MarkdupStage::release()
-{
-	for (DevBuf *d : { &desc, &head, &seg, &best, &pair_here, &dup, &cnt }) d->release();
-	for (auto &e : ev) if (e) { (void)hipEventDestroy(e); e = nullptr; }
-}
-
 // s->desc holds n_tmpl descriptors in input order; the verdicts into s->dup (one byte per template).  Queued on c->stream (the sorts
 // await a small read-back each); the context's sort buffers are used.
 int markdup_decide(MarkdupStage *s, bwahip_ctx *c, int64_t n_tmpl)
@@ -341,10 +334,9 @@ extern "C" int bwahip_kat_dup_desc(bwahip_ctx *c, const uint8_t *rec, const int6
 	HIP_TRY(hipSetDevice(c->device));
 	const int64_t n_tmpl = paired ? n_reads / 2 : n_reads, len = off[n_reads];
 	DevBuf d_rec, d_off, d_desc;
-	hipEvent_t ev[2] = {};
-	for (auto &x : ev) HIP_TRY(hipEventCreate(&x));
+	Event ev[2];
 	int rc, err = 0;
-	if (!(rc = d_rec.ensure((size_t)len + 1)) && !(rc = d_off.ensure((size_t)(n_reads + 1) * 8)) && !(rc = d_desc.ensure((size_t)n_tmpl * sizeof(bwahip_dup_desc_t) + 16))) {
+	if (!(rc = ev[0].make()) && !(rc = ev[1].make()) && !(rc = d_rec.ensure((size_t)len + 1)) && !(rc = d_off.ensure((size_t)(n_reads + 1) * 8)) && !(rc = d_desc.ensure((size_t)n_tmpl * sizeof(bwahip_dup_desc_t) + 16))) {
 		int *d_err = (int*)(d_desc.as<bwahip_dup_desc_t>() + n_tmpl);
 		hipError_t e = len ? hipMemcpyAsync(d_rec.p, rec, (size_t)len, hipMemcpyHostToDevice, c->stream) : hipSuccess;
 		if (e == hipSuccess) e = hipMemcpyAsync(d_off.p, off, (size_t)(n_reads + 1) * 8, hipMemcpyHostToDevice, c->stream);
@@ -361,8 +353,6 @@ extern "C" int bwahip_kat_dup_desc(bwahip_ctx *c, const uint8_t *rec, const int6
 		if (!rc && (e != hipSuccess || e2 != hipSuccess)) rc = BWAHIP_ENODEV;
 		if (rc || hipEventElapsedTime(&c->dup_desc_ms, ev[0], ev[1]) != hipSuccess) c->dup_desc_ms = 0;
 	}
-	for (auto &x : ev) (void)hipEventDestroy(x);
-	d_rec.release(); d_off.release(); d_desc.release();
 	return rc ? rc : err ? BWAHIP_EINVAL : 0;
 }
 
@@ -380,6 +370,5 @@ extern "C" int bwahip_kat_markdup(bwahip_ctx *c, const bwahip_dup_desc_t *desc, 
 	if (!rc) rc = markdup_decide(&s, c, n_tmpl);
 	if (!rc && hipMemcpyAsync(dup_out, s.dup.p, (size_t)n_tmpl, hipMemcpyDeviceToHost, c->stream) != hipSuccess) rc = BWAHIP_ENODEV;
 	if (hipStreamSynchronize(c->stream) != hipSuccess && !rc) rc = BWAHIP_ENODEV;
-	s.release();
 	return rc;
 }

@@ -182,28 +182,21 @@ int launched() { return hipGetLastError() == hipSuccess ? 0 : BWAHIP_ENODEV; }
 
 // The stage's buffers: counted by bwahip_qc_hbm_need (qc_host.cpp)
 struct QcStage {
-	DevBuf diff, tile_sum, tile_pref, tile_ref, ref_tab, tab, err;
-	DevBuf rec, off;                                               // bwahip_kat_qc alone: the caller's records
+	Tally hbm;
+	DevBuf diff{hbm}, tile_sum{hbm}, tile_pref{hbm}, tile_ref{hbm}, ref_tab{hbm}, tab{hbm}, err{hbm};
+	DevBuf rec{hbm}, off{hbm};                                     // bwahip_kat_qc alone: the caller's records
 	HostBuf h_tab;
-	hipEvent_t ev[4] = {};                                         // begin, cleared, records done, end
+	Event ev[4];                                                   // begin, cleared, records done, end
 	// the layout of the call in flight
 	bwahip_qc_opt_t opt = { 14, 1796, 0 };
 	std::vector<int64_t> ref_len, h_ref_tab;                       // h_ref_tab: lengths | first tile (n_ref + 1) | first window (n_ref + 1)
 	std::vector<int> h_tile_ref;
 	int32_t n_ref = 0; int64_t n_tiles = 0, n_win = 0, n_records = 0;
-	std::vector<DevBuf*> all() { return { &diff, &tile_sum, &tile_pref, &tile_ref, &ref_tab, &tab, &err, &rec, &off }; }
-	size_t bytes() { size_t b = 0; for (DevBuf *d : all()) b += d->cap; return b; }
 	const int64_t *d_len() const { return ref_tab.as<int64_t>(); }
 	const int64_t *d_tile0() const { return ref_tab.as<int64_t>() + n_ref; }
 	const int64_t *d_win_off() const { return ref_tab.as<int64_t>() + 2 * (size_t)n_ref + 1; }
 	unsigned long long *d_win() const { return tab.as<unsigned long long>() + QC_FIXED + QC_PER_REF * (size_t)n_ref; }
 	size_t tab_words() const { return (size_t)QC_FIXED + QC_PER_REF * (size_t)n_ref + (size_t)n_win; }
-	~QcStage()
-	{
-		for (DevBuf *d : all()) d->release();
-		h_tab.release();
-		for (auto &e : ev) if (e) (void)hipEventDestroy(e);
-	}
 };
 
 QcStage *qc_stage_new() { return new QcStage; }
@@ -229,7 +222,7 @@ int qc_stage_begin(QcStage *s, bwahip_ctx *c, int32_t n_ref, const int64_t *ref_
 	s->h_tile_ref.resize((size_t)s->n_tiles);
 	for (int32_t r = 0; r < n_ref; ++r) for (int64_t k = tile0[r]; k < tile0[r + 1]; ++k) s->h_tile_ref[(size_t)k] = r;
 	HIP_TRY(hipSetDevice(c->device));
-	for (auto &e : s->ev) if (!e) HIP_TRY(hipEventCreate(&e));
+	for (auto &e : s->ev) if (!e && (rc = e.make())) return rc;
 	hipStream_t q = c->stream;
 	const size_t T = (size_t)s->n_tiles;                           // (0 without a reference: the records are still judged and counted)
 	if ((rc = s->diff.ensure((T ? T : 1) * QC_TILE * 4)) || (rc = s->tile_sum.ensure(T * 4)) || (rc = s->tile_pref.ensure((T + 1) * 8)) || (rc = s->tab.ensure(s->tab_words() * 8)) ||
@@ -291,7 +284,7 @@ int qc_stage_finish(QcStage *s, bwahip_ctx *c, std::vector<uint8_t> *bytes, bwah
 		if (hipEventElapsedTime(&ms, s->ev[0], s->ev[3]) == hipSuccess) st.qc_ms = ms;
 		if (hipEventElapsedTime(&ms, s->ev[1], s->ev[2]) == hipSuccess) st.record_ms = ms;
 		if (hipEventElapsedTime(&ms, s->ev[2], s->ev[3]) == hipSuccess) st.scan_ms = ms;
-		st.hbm_bytes = (int64_t)s->bytes();
+		st.hbm_bytes = (int64_t)s->hbm.bytes;
 	}
 	st.n_windows = s->n_win; st.qc_bytes = (int64_t)bytes->size();
 	if (qs) *qs = st;

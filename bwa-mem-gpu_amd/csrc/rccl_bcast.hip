@@ -101,7 +101,7 @@ extern "C" int bwahip_init_rccl(const char *prefix, int rank, int world, const v
 	HIP_TRY(hipSetDevice(device));
 	int rc = 0;
 	Comm comm = nullptr;
-	hipStream_t st = nullptr;
+	Stream st;
 	bwahip_ctx *c = new bwahip_ctx();
 	c->device = device; c->index_resident = true;
 	HostIndex full;                                             // rank 0: the loaded files (FM-index arrays freed after the upload)
@@ -112,7 +112,7 @@ extern "C" int bwahip_init_rccl(const char *prefix, int rank, int world, const v
 	bool collective_failure = false;                           // every rank leaves together: the communicator can be destroyed normally
 	UniqueId id;
 	memcpy(&id, id128, 128);
-	if (hipStreamCreateWithFlags(&st, hipStreamNonBlocking) != hipSuccess) { rc = BWAHIP_ENODEV; goto done; }
+	if ((rc = st.make())) goto done;
 	// rank 0 reads and packs the index BEFORE the communicator exists: whatever can fail on one rank alone (files, host memory) has then
 	// either happened or not, and the first thing broadcast is rank 0's verdict -- the metadata length, 0 = "rank 0 failed" -- so that
 	// every rank returns BWAHIP_EIO together instead of waiting in a broadcast that never comes
@@ -161,12 +161,10 @@ extern "C" int bwahip_init_rccl(const char *prefix, int rank, int world, const v
 	}
 	rc = ctx_setup(c, &c->host.bwt, &c->host.bns, c->host.pac);
 done:
-	d_meta.release();
 	bwahip_free_host_index(&full);
 	// a failure of THIS rank alone after the communicator exists would leave the others waiting in their next broadcast: abort the
 	// communicator (its peers' pending operations then fail) instead of destroying it quietly
 	if (comm) { if (rc && !collective_failure && g_rccl.CommAbort) g_rccl.CommAbort(comm); else g_rccl.CommDestroy(comm); }
-	if (st) (void)hipStreamDestroy(st);
 	if (rc) { bwahip_destroy(c); return rc; }
 	*out = c;
 	return 0;

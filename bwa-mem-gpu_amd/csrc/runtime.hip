@@ -153,16 +153,11 @@ extern "C" {
 int ctx_setup(bwahip_ctx *c, const bwahip_bwt_t *bwt, const bwahip_bns_t *bns, const uint8_t *pac)
 {
 	HIP_TRY(hipSetDevice(c->device));
-	HIP_TRY(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
-	HIP_TRY(hipStreamCreateWithFlags(&c->stream2, hipStreamNonBlocking));
-	HIP_TRY(hipStreamCreateWithFlags(&c->stream3, hipStreamNonBlocking));
-	HIP_TRY(hipStreamCreateWithFlags(&c->stream_copy, hipStreamNonBlocking));
-	for (auto &e : c->ev_slice) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-	HIP_TRY(hipEventCreateWithFlags(&c->ev_sam_half, hipEventDisableTiming));
-	HIP_TRY(hipEventCreateWithFlags(&c->ev_join3, hipEventDisableTiming));
-	HIP_TRY(hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming)); HIP_TRY(hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming));
-	for (auto &e : c->ev) HIP_TRY(hipEventCreate(&e));
 	int rc;
+	for (Stream *q : { &c->stream, &c->stream2, &c->stream3, &c->stream_copy }) if ((rc = q->make())) return rc;
+	for (auto &e : c->ev_slice) if ((rc = e.make(hipEventDisableTiming))) return rc;
+	for (Event *e : { &c->ev_sam_half, &c->ev_join3, &c->ev_fork, &c->ev_join }) if ((rc = e->make(hipEventDisableTiming))) return rc;
+	for (auto &e : c->ev) if ((rc = e.make())) return rc;
 	c->knobs.from_env();
 	c->intv_cap = c->knobs.intv_cap;
 	{
@@ -172,7 +167,7 @@ int ctx_setup(bwahip_ctx *c, const bwahip_bwt_t *bwt, const bwahip_bns_t *bns, c
 		HIP_TRY(hipStreamSynchronize(c->stream));
 	}
 	if (c->external_index) {             // adopt caller-owned device arrays (e.g. received over RCCL)
-		c->d_bwt.p = bwt->bwt; c->d_sa.p = bwt->sa; c->d_pac.p = (void*)pac;
+		c->d_bwt.adopt(bwt->bwt, (size_t)bwt->bwt_size * 4); c->d_sa.adopt(bwt->sa, (size_t)bwt->n_sa * 8); c->d_pac.adopt((void*)pac, (size_t)bns->l_pac / 4 + 1);
 	} else if (c->index_resident) {      // bwahip_init_rccl: the context's own buffers were filled by the broadcast
 	} else {
 		if ((rc = upload(c->d_bwt, bwt->bwt, bwt->bwt_size * 4, c->stream))) return rc;
@@ -351,34 +346,17 @@ void bwahip_destroy(bwahip_ctx *c)
 {
 	if (!c) return;
 	(void)hipSetDevice(c->device);
-	if (c->stream) (void)hipStreamSynchronize(c->stream);
+	for (const Stream *q : { &c->stream, &c->stream2, &c->stream3, &c->stream_copy }) if (*q) (void)hipStreamSynchronize(*q);
 	pipe_destroy(c);
-	DevBuf *bufs[] = { &c->d_bwt, &c->d_bwtp, &c->d_sa, &c->d_sa_dense, &c->d_kmer, &c->d_pac, &c->d_anns, &c->d_seq4, &c->d_smem_heavy, &c->d_raw, &c->d_raw_n, &c->d_intv, &c->d_intv_n, &c->d_seed_cnt,
-	                   &c->d_lrep, &c->d_seed_base, &c->d_seeds, &c->d_scratch, &c->d_misc,
-	                   &c->d_cw, &c->d_nxt, &c->d_ord, &c->d_wts, &c->d_kept, &c->d_first, &c->d_keep, &c->d_nodes, &c->d_stack,
-	                   &c->d_chains, &c->d_chain_seeds, &c->d_chain_n, &c->d_kept_seeds, &c->d_reg_base, &c->d_regs, &c->d_tmp_regs,
-	                   &c->d_reg_n, &c->d_srt, &c->d_dbg_chains, &c->d_dbg_seeds, &c->d_dbg_chain_n, &c->d_dbg_regs, &c->d_dbg_reg_n, &c->d_flt, &c->d_heavy, &c->d_perm, &c->d_spec_regs, &c->d_spec_items, &c->d_scan, &c->d_chain_big, &c->d_logtab, &c->d_redo, &c->d_big_t, &c->d_dedup, &c->d_cperm,
-	                   &c->d_ctg_names, &c->d_ctg_name_off, &c->d_ctg_anno, &c->d_ctg_anno_off, &c->d_rg,
-	                   &c->d_fregs, &c->d_fregs2, &c->d_fscr, &c->d_need, &c->d_xa_owner, &c->d_freg_n, &c->d_npri, &c->d_task_n, &c->d_rec_n, &c->d_task_base, &c->d_tasks, &c->d_aln_of_reg, &c->d_alns,
-	                   &c->d_resc_flag, &c->d_zslab, &c->d_resc_ord, &c->d_pool, &c->d_fmisc, &c->d_fredo, &c->d_bigz, &c->d_rec_list, &c->d_xa_list, &c->d_sam_len,
-	                   &c->d_hist, &c->d_pair_tab, &c->d_nb, &c->d_pe_cap, &c->d_pe_base, &c->d_pe_regs, &c->d_pe_n, &c->d_pe_tmp, &c->d_pe_keys, &c->d_pe_idx, &c->d_resc, &c->d_ms_slab, &c->d_pe_read, &c->d_sw_cnt, &c->d_sw_base, &c->d_sw_res, &c->d_sw_tasks, &c->d_sw_info, &c->d_task_lists, &c->d_pair_dbg };
-	if (c->external_index) { c->d_bwt.p = nullptr; c->d_sa.p = nullptr; c->d_pac.p = nullptr; c->d_bwt.cap = c->d_sa.cap = c->d_pac.cap = 0; }
-	for (DevBuf *b : bufs) b->release();
-	c->own_in.release(); c->own_out.release();
-	for (auto &p : c->pin) p.release();
-	c->bs.release(); c->bz.release();
-	for (auto &e : c->ev) if (e) (void)hipEventDestroy(e);
-	if (c->stream) (void)hipStreamDestroy(c->stream);
-	if (c->stream2) (void)hipStreamDestroy(c->stream2);
-	if (c->stream3) (void)hipStreamDestroy(c->stream3);
-	if (c->stream_copy) (void)hipStreamDestroy(c->stream_copy);
-	for (auto &e : c->ev_slice) if (e) (void)hipEventDestroy(e);
-	if (c->ev_sam_half) (void)hipEventDestroy(c->ev_sam_half);
-	if (c->ev_join3) (void)hipEventDestroy(c->ev_join3);
-	if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
-	if (c->ev_join) (void)hipEventDestroy(c->ev_join);
 	bwahip_free_host_index(&c->host);
 	delete c;
+}
+
+int bwahip_live_resources(int64_t out[6])
+{
+	if (!out) return BWAHIP_EINVAL;
+	for (int k = 0; k < 6; ++k) out[k] = g_bwahip_live[k].load();
+	return 0;
 }
 
 int bwahip_ctx_set_rg_id(bwahip_ctx *c, const char *id) { if (!c) return BWAHIP_EINVAL; c->rg_id = id ? id : ""; return 0; }
@@ -434,7 +412,7 @@ int bwahip_kat_ksw_align(bwahip_ctx *c, int n, const int *params, const int8_t *
 	DevBuf dp, dq, dqo, dt, dto, dout, dit, dw; int rc;
 	if ((rc = upload(dp, params, (size_t)n * 32, c->stream)) || (rc = upload(dq, q, (size_t)qoff[n], c->stream)) || (rc = upload(dqo, qoff, (size_t)(n + 1) * 8, c->stream)) ||
 	    (rc = upload(dt, t, (size_t)toff[n], c->stream)) || (rc = upload(dto, toff, (size_t)(n + 1) * 8, c->stream)) || (rc = dout.ensure((size_t)n * 28)) ||
-	    (rc = dw.ensure(stride * (size_t)n))) goto done;
+	    (rc = dw.ensure(stride * (size_t)n))) return rc;
 	for (int m = 0; m < 2 && !rc; ++m) {
 		if (items[m].empty()) continue;
 		if ((rc = upload(dit, items[m].data(), items[m].size() * 4, c->stream))) break;
@@ -443,8 +421,6 @@ int bwahip_kat_ksw_align(bwahip_ctx *c, int n, const int *params, const int8_t *
 		if (hipStreamSynchronize(c->stream) != hipSuccess) rc = BWAHIP_ENODEV;
 	}
 	if (!rc && hipMemcpy(out7, dout.p, (size_t)n * 28, hipMemcpyDeviceToHost) != hipSuccess) rc = BWAHIP_ENODEV;
-done:
-	dp.release(); dq.release(); dqo.release(); dt.release(); dto.release(); dout.release(); dit.release(); dw.release();
 	return rc;
 }
 
@@ -460,13 +436,11 @@ int bwahip_kat_introsort(bwahip_ctx *c, int n, int mode, const int64_t *k64, con
 	for (int i = 0; i < n; ++i) keys[i] = { k64[i], score[i], qb[i] };
 	DevBuf dk, dp, ds, dw, dst; int rc;
 	if ((rc = upload(dk, keys.data(), (size_t)n * 16, c->stream)) || (rc = dp.ensure((size_t)n * 8)) || (rc = ds.ensure((size_t)n * 8)) ||
-	    (rc = dw.ensure(kat_isort_work_ints(n) * 4 + 64)) || (rc = dst.ensure(16))) goto done;
+	    (rc = dw.ensure(kat_isort_work_ints(n) * 4 + 64)) || (rc = dst.ensure(16))) return rc;
 	rc = launch_kat_isort(n, mode, dk.p, dp.as<int>(), ds.as<int>(), dw.as<int>(), dst.as<int>(), c->stream);
 	if (!rc && (hipMemcpyAsync(idx_par, dp.p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipMemcpyAsync(idx_seq, ds.p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
 	            hipMemcpyAsync(status2, dst.p, 8, hipMemcpyDeviceToHost, c->stream) != hipSuccess)) rc = BWAHIP_ENODEV;
 	if (hipStreamSynchronize(c->stream) != hipSuccess) rc = BWAHIP_ENODEV;
-done:
-	dk.release(); dp.release(); ds.release(); dw.release(); dst.release();
 	return rc;
 }
 
@@ -511,8 +485,8 @@ int bwahip_kat_mate_insert(bwahip_ctx *c, const bwahip_opt_t *opt, int n_items, 
 	    (rc = upload(dsh, step_hit, (size_t)n_step * 4, c->stream)) || (rc = upload(dsr, steps.data(), steps.size() * sizeof(DevReg), c->stream)) ||
 	    (rc = upload(dr, regs.data(), slots * sizeof(DevReg), c->stream)) || (rc = dt.ensure(slots * sizeof(DevReg))) || (rc = dk.ensure(slots * 16)) || (rc = di.ensure(slots * 8)) ||
 	    (rc = don.ensure((size_t)n_items * 4)) || (rc = doc.ensure((size_t)n_items * 12)) || (rc = de.ensure(16)) ||
-	    (rc = upload(dit0, items[0].data(), items[0].size() * 4, c->stream)) || (rc = upload(dit1, items[1].data(), items[1].size() * 4, c->stream))) goto done;
-	if (hipMemsetAsync(de.p, 0, 16, c->stream) != hipSuccess) { rc = BWAHIP_ENODEV; goto done; }
+	    (rc = upload(dit0, items[0].data(), items[0].size() * 4, c->stream)) || (rc = upload(dit1, items[1].data(), items[1].size() * 4, c->stream))) return rc;
+	HIP_TRY(hipMemsetAsync(de.p, 0, 16, c->stream));
 	a.opt = make_dev_opt(opt);
 	a.base = db.as<int64_t>(); a.step_off = dso.as<int64_t>(); a.n_start = dns.as<int>(); a.step_hit = dsh.as<int>(); a.step_reg = dsr.as<DevReg>();
 	a.regs = dr.as<DevReg>(); a.tmp = dt.as<DevReg>(); a.keys = dk.p; a.idx = di.as<int>(); a.use_incr = mode == 0 ? 1 : 0;
@@ -535,8 +509,6 @@ int bwahip_kat_mate_insert(bwahip_ctx *c, const bwahip_opt_t *opt, int n_items, 
 			if (out_n[i]) memcpy(out_words + 19 * base[i], v.data() + 1, (size_t)out_n[i] * 19 * 8);
 		}
 	}
-done:
-	for (DevBuf *b : { &db, &dso, &dns, &dsh, &dsr, &dr, &dt, &dk, &di, &don, &doc, &de, &dit0, &dit1 }) b->release();
 	return rc;
 }
 
@@ -565,11 +537,10 @@ int bwahip_kat_occ4(bwahip_ctx *c, int n, const uint64_t *k, uint64_t *out)
 	if (n == 0) return 0;
 	HIP_TRY(hipSetDevice(c->device));
 	DevBuf dk, dout; int rc;
-	if ((rc = upload(dk, k, (size_t)n * 8, c->stream)) || (rc = dout.ensure((size_t)n * 32))) { dk.release(); dout.release(); return rc; }
+	if ((rc = upload(dk, k, (size_t)n * 8, c->stream)) || (rc = dout.ensure((size_t)n * 32))) return rc;
 	rc = launch_kat_occ4(c->ix, n, dk.as<uint64_t>(), dout.as<uint64_t>(), c->stream);
 	if (!rc && hipMemcpyAsync(out, dout.p, (size_t)n * 32, hipMemcpyDeviceToHost, c->stream) != hipSuccess) rc = BWAHIP_ENODEV;
 	if (hipStreamSynchronize(c->stream) != hipSuccess) rc = BWAHIP_ENODEV;
-	dk.release(); dout.release();
 	return rc;
 }
 
@@ -579,11 +550,10 @@ int bwahip_kat_sa(bwahip_ctx *c, int n, const uint64_t *k, uint64_t *out)
 	if (n == 0) return 0;
 	HIP_TRY(hipSetDevice(c->device));
 	DevBuf dk, dout; int rc;
-	if ((rc = upload(dk, k, (size_t)n * 8, c->stream)) || (rc = dout.ensure((size_t)n * 8))) { dk.release(); dout.release(); return rc; }
+	if ((rc = upload(dk, k, (size_t)n * 8, c->stream)) || (rc = dout.ensure((size_t)n * 8))) return rc;
 	rc = launch_kat_sa(c->ix, n, dk.as<uint64_t>(), dout.as<uint64_t>(), c->stream);
 	if (!rc && hipMemcpyAsync(out, dout.p, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream) != hipSuccess) rc = BWAHIP_ENODEV;
 	if (hipStreamSynchronize(c->stream) != hipSuccess) rc = BWAHIP_ENODEV;
-	dk.release(); dout.release();
 	return rc;
 }
 
@@ -614,7 +584,6 @@ int bwahip_kat_kmer_table(bwahip_ctx *c, int *k_out, uint64_t *bad_out)
 	unsigned long long bad = 0;
 	if (!rc && hipMemcpyAsync(&bad, d.p, 8, hipMemcpyDeviceToHost, c->stream) != hipSuccess) rc = BWAHIP_ENODEV;
 	if (hipStreamSynchronize(c->stream) != hipSuccess) rc = BWAHIP_ENODEV;
-	d.release();
 	*bad_out = bad;
 	return rc;
 }
@@ -625,13 +594,10 @@ int bwahip_kat_extend(bwahip_ctx *c, int n, const uint64_t *ik3, const int *is_b
 	if (n == 0) return 0;
 	HIP_TRY(hipSetDevice(c->device));
 	DevBuf dk, db, dout; int rc;
-	if ((rc = upload(dk, ik3, (size_t)n * 24, c->stream)) || (rc = upload(db, is_back, (size_t)n * 4, c->stream)) || (rc = dout.ensure((size_t)n * 96))) {
-		dk.release(); db.release(); dout.release(); return rc;
-	}
+	if ((rc = upload(dk, ik3, (size_t)n * 24, c->stream)) || (rc = upload(db, is_back, (size_t)n * 4, c->stream)) || (rc = dout.ensure((size_t)n * 96))) return rc;
 	rc = launch_kat_extend(c->ix, n, dk.as<uint64_t>(), db.as<int>(), dout.as<uint64_t>(), c->stream);
 	if (!rc && hipMemcpyAsync(ok12, dout.p, (size_t)n * 96, hipMemcpyDeviceToHost, c->stream) != hipSuccess) rc = BWAHIP_ENODEV;
 	if (hipStreamSynchronize(c->stream) != hipSuccess) rc = BWAHIP_ENODEV;
-	dk.release(); db.release(); dout.release();
 	return rc;
 }
 
@@ -1014,14 +980,12 @@ int bwahip_kat_bgzf(bwahip_ctx *c, const void *data, int64_t len, uint8_t *out, 
 	DevBuf din, dout, dtot;
 	int rc;
 	int64_t tot[2] = { 0, 0 };
-	if ((rc = upload(din, data, (size_t)len, c->stream)) || (rc = dtot.ensure(16)) || (rc = bgzf_deflate(c, din.as<uint8_t>(), len, dout, dtot.as<int64_t>(), c->stream))) goto done;
-	if (hipMemcpyAsync(tot, dtot.p, 16, hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) { rc = BWAHIP_ENODEV; goto done; }
-	if (tot[0] < 0 || tot[0] > out_cap) { rc = BWAHIP_EINTERNAL; goto done; }
-	if (hipMemcpyAsync(out, dout.p, (size_t)tot[0], hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) { rc = BWAHIP_ENODEV; goto done; }
+	if ((rc = upload(din, data, (size_t)len, c->stream)) || (rc = dtot.ensure(16)) || (rc = bgzf_deflate(c, din.as<uint8_t>(), len, dout, dtot.as<int64_t>(), c->stream))) return rc;
+	if (hipMemcpyAsync(tot, dtot.p, 16, hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) return BWAHIP_ENODEV;
+	if (tot[0] < 0 || tot[0] > out_cap) return BWAHIP_EINTERNAL;
+	if (hipMemcpyAsync(out, dout.p, (size_t)tot[0], hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) return BWAHIP_ENODEV;
 	*out_len = tot[0]; *n_stored = tot[1];
-done:
-	din.release(); dout.release(); dtot.release();
-	return rc;
+	return 0;
 }
 
 // The records of the last bwahip_batch_run_bam, as bwahip_batch_sam hands out the text (no NUL is meaningful here)
@@ -1155,21 +1119,20 @@ int bwahip_kat_chain(bwahip_ctx *c, const bwahip_opt_t *opt, int n_reads, const 
 	std::vector<int64_t> o, v;
 	if ((rc = upload(d_off, off.data(), off.size() * 8, c->stream)) || (rc = upload(c->d_seed_base, seed_off, (size_t)(n + 1) * 8, c->stream)) ||
 	    (rc = upload(c->d_seeds, hs.data(), hs.size() * sizeof(DevSeed), c->stream)) || (rc = upload(c->d_intv, hi.data(), hi.size() * sizeof(DevIntv), c->stream)) ||
-	    (rc = upload(c->d_intv_n, hin.data(), (size_t)n * 4, c->stream)) || (rc = d_diag.ensure((size_t)n * CHAIN_DIAG_N * 4))) goto done;
-	if ((rc = chain_prepare(c, make_dev_opt(opt), n, total, d_off.as<int64_t>(), cap, true, nullptr, cl))) goto done;
-	if (hipMemsetAsync(d_diag.p, 0, (size_t)n * CHAIN_DIAG_N * 4, c->stream) != hipSuccess) { rc = BWAHIP_ENODEV; goto done; }
+	    (rc = upload(c->d_intv_n, hin.data(), (size_t)n * 4, c->stream)) || (rc = d_diag.ensure((size_t)n * CHAIN_DIAG_N * 4))) return rc;
+	rc = chain_prepare(c, make_dev_opt(opt), n, total, d_off.as<int64_t>(), cap, true, nullptr, cl);
+	if (!rc && hipMemsetAsync(d_diag.p, 0, (size_t)n * CHAIN_DIAG_N * 4, c->stream) != hipSuccess) rc = BWAHIP_ENODEV;
 	cl.diag = d_diag.as<int>();
-	if ((rc = launch_chain(cl, c->stream, c->stream2, c->stream3, c->ev_fork, c->ev_join, c->ev_join3)) || (rc = launch_chain_flt(cl, c->stream))) goto done;
-	if ((total && (hipMemcpyAsync(h_ch.data(), c->d_chains.p, (size_t)total * sizeof(DevChain), hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+	if (!rc) rc = launch_chain(cl, c->stream, c->stream2, c->stream3, c->ev_fork, c->ev_join, c->ev_join3);
+	if (!rc) rc = launch_chain_flt(cl, c->stream);
+	if (!rc && ((total && (hipMemcpyAsync(h_ch.data(), c->d_chains.p, (size_t)total * sizeof(DevChain), hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
 	               hipMemcpyAsync(h_cs.data(), c->d_chain_seeds.p, (size_t)total * sizeof(DevSeed), hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
 	               hipMemcpyAsync(h_dch.data(), c->d_dbg_chains.p, (size_t)total * sizeof(DevChain), hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
 	               hipMemcpyAsync(h_dcs.data(), c->d_dbg_seeds.p, (size_t)total * sizeof(DevSeed), hipMemcpyDeviceToHost, c->stream) != hipSuccess)) ||
 	    hipMemcpyAsync(h_chn.data(), c->d_chain_n.p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
 	    hipMemcpyAsync(h_dchn.data(), c->d_dbg_chain_n.p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
-	    (diag && hipMemcpyAsync(diag, d_diag.p, (size_t)n * CHAIN_DIAG_N * 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess)) rc = BWAHIP_ENODEV;
-done:
+	    (diag && hipMemcpyAsync(diag, d_diag.p, (size_t)n * CHAIN_DIAG_N * 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess))) rc = BWAHIP_ENODEV;
 	if (hipStreamSynchronize(c->stream) != hipSuccess && !rc) rc = BWAHIP_ENODEV;
-	d_off.release(); d_diag.release();
 	if (rc) return rc;
 	for (int i = 0; i < n; ++i) {
 		const int64_t S = seed_off[i + 1] - seed_off[i];
@@ -1300,12 +1263,10 @@ int bwahip_kat_ksw_extend(bwahip_ctx *c, int n, const int *params, const uint8_t
 	DevOpt dopt = make_dev_opt(&o);
 	DevBuf dp, dq, dqo, dt, dto, dout; int rc;
 	if ((rc = upload(dp, params, (size_t)n * 40, c->stream)) || (rc = upload(dq, q, (size_t)qoff[n], c->stream)) || (rc = upload(dqo, qoff, (size_t)(n + 1) * 8, c->stream)) ||
-	    (rc = upload(dt, t, (size_t)toff[n], c->stream)) || (rc = upload(dto, toff, (size_t)(n + 1) * 8, c->stream)) || (rc = dout.ensure((size_t)n * 24))) goto done;
+	    (rc = upload(dt, t, (size_t)toff[n], c->stream)) || (rc = upload(dto, toff, (size_t)(n + 1) * 8, c->stream)) || (rc = dout.ensure((size_t)n * 24))) return rc;
 	rc = launch_kat_ksw(dopt, c->knobs.ext_early_stop, n, dp.as<int>(), dq.as<uint8_t>(), dqo.as<int64_t>(), dt.as<uint8_t>(), dto.as<int64_t>(), dout.as<int>(), c->stream);
 	if (!rc && hipMemcpyAsync(out6, dout.p, (size_t)n * 24, hipMemcpyDeviceToHost, c->stream) != hipSuccess) rc = BWAHIP_ENODEV;
 	if (hipStreamSynchronize(c->stream) != hipSuccess) rc = BWAHIP_ENODEV;
-done:
-	dp.release(); dq.release(); dqo.release(); dt.release(); dto.release(); dout.release();
 	return rc;
 }
 
@@ -1337,7 +1298,7 @@ int bwahip_kat_ksw_extend2(bwahip_ctx *c, int n, const int *params, const int8_t
 	DevBuf dp, dm, dq, dqo, dt, dto, dout, dit[4]; int rc;
 	if ((rc = upload(dp, params, (size_t)n * 48, c->stream)) || (rc = upload(dm, mat25, (size_t)n * 25, c->stream)) || (rc = upload(dq, q, (size_t)qoff[n], c->stream)) ||
 	    (rc = upload(dqo, qoff, (size_t)(n + 1) * 8, c->stream)) || (rc = upload(dt, t, (size_t)toff[n], c->stream)) || (rc = upload(dto, toff, (size_t)(n + 1) * 8, c->stream)) ||
-	    (rc = dout.ensure((size_t)n * 28))) goto done;
+	    (rc = dout.ensure((size_t)n * 28))) return rc;
 	for (int k = 0; k < 4 && !rc; ++k) {
 		if (items[k].empty()) continue;
 		if ((rc = upload(dit[k], items[k].data(), items[k].size() * 4, c->stream))) break;
@@ -1346,9 +1307,6 @@ int bwahip_kat_ksw_extend2(bwahip_ctx *c, int n, const int *params, const int8_t
 	}
 	if (!rc && hipMemcpyAsync(out7, dout.p, (size_t)n * 28, hipMemcpyDeviceToHost, c->stream) != hipSuccess) rc = BWAHIP_ENODEV;
 	if (hipStreamSynchronize(c->stream) != hipSuccess) rc = BWAHIP_ENODEV;
-done:
-	dp.release(); dm.release(); dq.release(); dqo.release(); dt.release(); dto.release(); dout.release();
-	for (int k = 0; k < 4; ++k) dit[k].release();
 	return rc;
 }
 
@@ -1380,8 +1338,8 @@ int bwahip_kat_ksw_global(bwahip_ctx *c, int n, const int *params, const int8_t 
 	DevBuf dp, dm, dq, dqo, dt, dto, dout, dcig, dslab, dit[6]; int rc;
 	if ((rc = upload(dp, params, (size_t)n * 40, c->stream)) || (rc = upload(dm, mat25, (size_t)n * 25, c->stream)) || (rc = upload(dq, q, (size_t)qoff[n], c->stream)) ||
 	    (rc = upload(dqo, qoff, (size_t)(n + 1) * 8, c->stream)) || (rc = upload(dt, t, (size_t)toff[n], c->stream)) || (rc = upload(dto, toff, (size_t)(n + 1) * 8, c->stream)) ||
-	    (rc = dout.ensure((size_t)n * 8)) || (rc = dcig.ensure((size_t)n * BWAHIP_KAT_MAX_CIGAR * 4))) goto done;
-	if (hipMemsetAsync(dcig.p, 0, (size_t)n * BWAHIP_KAT_MAX_CIGAR * 4, c->stream) != hipSuccess) { rc = BWAHIP_ENODEV; goto done; }
+	    (rc = dout.ensure((size_t)n * 8)) || (rc = dcig.ensure((size_t)n * BWAHIP_KAT_MAX_CIGAR * 4))) return rc;
+	HIP_TRY(hipMemsetAsync(dcig.p, 0, (size_t)n * BWAHIP_KAT_MAX_CIGAR * 4, c->stream));
 	for (int k = 0; k < 6 && !rc; ++k) {
 		if (items[k].empty()) continue;
 		if ((rc = upload(dit[k], items[k].data(), items[k].size() * 4, c->stream))) break;
@@ -1395,9 +1353,6 @@ int bwahip_kat_ksw_global(bwahip_ctx *c, int n, const int *params, const int8_t 
 	if (!rc && hipMemcpyAsync(out2, dout.p, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream) != hipSuccess) rc = BWAHIP_ENODEV;
 	if (!rc && hipMemcpyAsync(cigar, dcig.p, (size_t)n * BWAHIP_KAT_MAX_CIGAR * 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess) rc = BWAHIP_ENODEV;
 	if (hipStreamSynchronize(c->stream) != hipSuccess) rc = BWAHIP_ENODEV;
-done:
-	dp.release(); dm.release(); dq.release(); dqo.release(); dt.release(); dto.release(); dout.release(); dcig.release(); dslab.release();
-	for (int k = 0; k < 6; ++k) dit[k].release();
 	return rc;
 }
 

@@ -159,7 +159,7 @@ struct DevSortedSink : Sink {
 	const bwahip_qc_opt_t *qo = nullptr; int qc_fd = -1; bwahip_qc_stats_t *qs = nullptr;   // bwahip_stream_run_bam_sorted_dev_qc: the summary of the file on qc_fd
 	std::vector<int64_t> qc_len; int64_t qc_need = 0, qc_windows = 0; bwahip_qc_builder *qb = nullptr;   // the contigs' lengths, the stage's share of the budget; the fall-back's builder
 	std::atomic<bool> fell_back{false};                          // read by the drainers: from now on they download
-	hipStream_t fb_stream = nullptr; HostBuf fb_rec, fb_keys, fb_off;   // the fall-back's downloads: their stream, one pinned buffer each for records, keys and offsets
+	Stream fb_stream; HostBuf fb_rec, fb_keys, fb_off;   // the fall-back's downloads: their stream, one pinned buffer each for records, keys and offsets
 	DevSortedSink(const char *h, bwahip_sort_dev_t *s) : sd(s), host(h, s->level, s) { form = OutForm::BamSorted; }
 	// What an entry point asks of the sink: mark (the runs carry templates), qo_ != NULL (the QC summary on qc_fd_).  no_fallback: a run that
 	// does not fit ends the call, sd->level has no reader, the index is written only for bai_fd >= 0; a sink that may fall back always indexes
@@ -173,8 +173,7 @@ struct DevSortedSink : Sink {
 	~DevSortedSink()
 	{
 		if (ctx0) (void)hipSetDevice(ctx0->device);
-		if (fb_stream) (void)hipStreamDestroy(fb_stream);
-		fb_rec.release(); fb_keys.release(); fb_off.release(); bwahip_bam_devmerger_close(dm);
+		bwahip_bam_devmerger_close(dm);
 		bwahip_qc_builder_close(qb);
 	}
 	int open(bwahip_ctx *const *ctxs, int n_ctx) override
@@ -227,7 +226,7 @@ struct DevSortedSink : Sink {
 	int run_to_host(int64_t run_no, DevRun *r, double sort_ms)
 	{
 		int rc = hipSetDevice(ctx0->device) == hipSuccess ? 0 : BWAHIP_ENODEV;
-		if (!rc && !fb_stream && hipStreamCreateWithFlags(&fb_stream, hipStreamNonBlocking) != hipSuccess) rc = BWAHIP_ENODEV;
+		if (!rc && !fb_stream) rc = fb_stream.make();
 		if (!rc && ((rc = fb_rec.ensure((size_t)r->len + 1)) || (rc = fb_keys.ensure((size_t)(r->n_rec + 1) * 8)) || (rc = fb_off.ensure((size_t)(r->n_rec + 1) * 8)))) {}
 		if (!rc) rc = bam_devrun_download(r, (uint8_t*)fb_rec.p, (uint64_t*)fb_keys.p, (int64_t*)fb_off.p, fb_stream);
 		Item h; h.p = (const char*)fb_rec.p; h.len = r->len; h.keys = (const uint64_t*)fb_keys.p; h.rec_off = (const int64_t*)fb_off.p; h.n_rec = r->n_rec; h.gpu_ms = sort_ms;
@@ -302,7 +301,7 @@ struct SpillSortedSink : DevSortedSink {
 		if (sp->host_budget < 0 || sp->window_pieces > 65536) return BWAHIP_EINVAL;
 		int r = DevSortedSink::open(ctxs, n_ctx);
 		if (!r) r = bwahip_bam_devmerger_set_spill(dm, sp);
-		if (!r) r = hipSetDevice(ctx0->device) == hipSuccess && hipStreamCreateWithFlags(&fb_stream, hipStreamNonBlocking) == hipSuccess ? 0 : BWAHIP_ENODEV;
+		if (!r) r = hipSetDevice(ctx0->device) == hipSuccess ? fb_stream.make() : BWAHIP_ENODEV;
 		if (!r) wp = bam_devmerger_window_pieces(dm);               // the merger resolves the default
 		return r;
 	}

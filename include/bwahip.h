@@ -563,6 +563,10 @@ int  bwahip_stream_run_bam_sorted_dev_markdup(bwahip_ctx *const *ctxs, int n_ctx
 int  bwahip_kat_dup_desc(bwahip_ctx *ctx, const uint8_t *rec, const int64_t *off, int64_t n_reads, int paired, bwahip_dup_desc_t *desc_out);
 int  bwahip_kat_markdup(bwahip_ctx *ctx, const bwahip_dup_desc_t *desc, int64_t n_tmpl, uint8_t *dup_out);
 float bwahip_kat_dup_desc_ms(bwahip_ctx *ctx);   /* the kernel's milliseconds in the last bwahip_kat_dup_desc, by HIP events (scripts/markdup_rate.py) */
+/* Test instrumentation: what the library owns in this process right now -- out[0] device buffers, [1] their bytes, [2] pinned host
+ * buffers, [3] their bytes, [4] HIP events, [5] HIP streams.  Memory of the caller's that a context reads (bwahip_init_device,
+ * bwahip_batch_attach) does not count.  After the last context and merger are gone the figures are those from before the first. */
+int  bwahip_live_resources(int64_t out[6]);
 
 /* ---- Alignment QC summary and depth of coverage of coordinate-sorted BAM (csrc/k_qc.hip on the device, csrc/qc_host.cpp without one) ----
  * One canonical summary, recomputable from the records of the file and the contig lengths alone.  All values are integers.  The result
