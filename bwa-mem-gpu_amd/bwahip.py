@@ -119,6 +119,15 @@ class QcStats(C.Structure):  # bwahip_qc_stats_t
                 ("scan_ms", C.c_double)]
 
 
+class PileupOpt(C.Structure):  # bwahip_pileup_opt_t
+    _fields_ = [("min_mapq", C.c_int), ("min_baseq", C.c_int), ("exclude_flags", C.c_int), ("min_alt", C.c_int)]
+
+
+class PileupStats(C.Structure):  # bwahip_pileup_stats_t
+    _fields_ = [("n_sites", C.c_int64), ("n_alleles", C.c_int64), ("n_obs", C.c_int64 * 3), ("pu_bytes", C.c_int64), ("hbm_bytes", C.c_int64),
+                ("pileup_ms", C.c_double), ("observe_ms", C.c_double), ("sort_ms", C.c_double), ("evidence_ms", C.c_double)]
+
+
 class SpillStats(C.Structure):  # bwahip_spill_t
     _fields_ = [("host_budget", C.c_int64), ("tmp_dir", C.c_char_p), ("window_pieces", C.c_int), ("n_spilled_runs", C.c_int64), ("first_spilled_run", C.c_int64),
                 ("host_bytes", C.c_int64), ("file_bytes", C.c_int64), ("n_windows", C.c_int64), ("window_hbm_bytes", C.c_int64), ("download_s", C.c_double),
@@ -259,6 +268,18 @@ def lib():
     L.bwahip_bam_devmerger_set_qc.argtypes = [vp, C.POINTER(QcOpt), C.c_int32, vp, C.c_int, C.POINTER(QcStats)]
     L.bwahip_qc_hbm_need.argtypes = [C.c_int64, C.c_int64, C.c_int64, C.c_int64]
     L.bwahip_qc_hbm_need.restype = C.c_int64
+    L.bwahip_pileup_builder_open.argtypes = [C.c_int32, vp, vp, C.POINTER(PileupOpt), C.POINTER(vp)]
+    L.bwahip_pileup_builder_add_records.argtypes = [vp, vp, vp, C.c_int64]
+    L.bwahip_pileup_builder_finish.argtypes = [vp, C.c_int]
+    L.bwahip_pileup_builder_close.argtypes = [vp]
+    L.bwahip_pileup_builder_close.restype = None
+    L.bwahip_kat_pileup.argtypes = [vp, vp, vp, C.c_int64, C.c_int32, vp, vp, C.POINTER(PileupOpt), vp, C.c_int64, i64p]
+    L.bwahip_bam_devmerger_set_pileup.argtypes = [vp, C.POINTER(PileupOpt), C.c_int32, vp, vp, C.c_int, C.POINTER(PileupStats)]
+    L.bwahip_pileup_hbm_need.argtypes = [C.c_int64]
+    L.bwahip_pileup_hbm_need.restype = C.c_int64
+    L.bwahip_stream_run_bam_sorted_dev_pileup.argtypes = [C.POINTER(vp), C.c_int, C.POINTER(Opt), C.POINTER(PeStat), C.c_char_p, C.c_char_p, C.c_int, C.c_char_p,
+                                                          C.POINTER(StreamStats), C.POINTER(SortDevStats), C.c_int, C.c_int, C.POINTER(MarkdupStats), C.POINTER(QcOpt), C.c_int,
+                                                          C.POINTER(QcStats), C.POINTER(PileupOpt), C.c_int, C.POINTER(PileupStats)]
     L.bwahip_stream_run_bam_sorted_dev_qc.argtypes = [C.POINTER(vp), C.c_int, C.POINTER(Opt), C.POINTER(PeStat), C.c_char_p, C.c_char_p, C.c_int, C.c_char_p,
                                                       C.POINTER(StreamStats), C.POINTER(SortDevStats), C.c_int, C.POINTER(MarkdupStats), C.c_int, C.POINTER(QcOpt), C.c_int,
                                                       C.POINTER(QcStats)]
@@ -499,6 +520,21 @@ class DevMerger:
         self._qc = qs                                            # the merger writes into it
         return qs
 
+    def set_pileup(self, ref_len=None, pac=None, pu_fd=-1, opt=()):
+        """bwahip_bam_devmerger_set_pileup: every later finish runs the pileup stage (csrc/k_pileup.hip) over the runs and writes the file to
+        pu_fd; pac: the packed reference of these contigs (bytes), None for the context's index; opt = (min_mapq, min_baseq, exclude_flags,
+        min_alt), () for the defaults; ref_len None disarms.  Returns the PileupStats every armed finish fills."""
+        if ref_len is None or opt is None:
+            self._pu = None
+            _check(lib().bwahip_bam_devmerger_set_pileup(self._h, None, 0, None, None, -1, None), "bwahip_bam_devmerger_set_pileup")
+            return None
+        o, lens, ps = pileup_opt(*opt), np.ascontiguousarray(ref_len, dtype=np.int64), PileupStats()
+        pac = bytes(pac) if pac is not None else None
+        _check(lib().bwahip_bam_devmerger_set_pileup(self._h, C.byref(o), len(lens), lens.ctypes.data if len(lens) else None, pac, pu_fd, C.byref(ps)),
+               "bwahip_bam_devmerger_set_pileup")
+        self._pu = ps                                            # the merger writes into it
+        return ps
+
     def finish_bai(self, fd=-1, bai_fd=-1, first_member_offset=0, n_ref=0):
         """bwahip_bam_devmerger_finish_bai: finish, and the BAI index of the sorted records on bai_fd (csrc/k_bai.hip); returns
         (DevMergeStats, BaiStats)."""
@@ -607,6 +643,48 @@ class QcBuilder:
     def close(self):
         if self._h:
             lib().bwahip_qc_builder_close(self._h)
+            self._h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+
+def pileup_opt(min_mapq=0, min_baseq=0, exclude_flags=-1, min_alt=0):
+    """bwahip_pileup_opt_t; the defaults resolve to 0, 0, 1796, 2."""
+    o = PileupOpt()
+    o.min_mapq, o.min_baseq, o.exclude_flags, o.min_alt = min_mapq, min_baseq, exclude_flags, min_alt
+    return o
+
+
+def pileup_hbm_need(n_records):
+    """bwahip_pileup_hbm_need: what is known of the pileup stage's HBM before the data (no device)."""
+    return lib().bwahip_pileup_hbm_need(n_records)
+
+
+class PileupBuilder:
+    """bwahip_pileup_builder_*: the pileup (BPU\1) of BAM records fed in any cut and any order, for these contig lengths and this packed
+    reference; no device.  opt = (min_mapq, min_baseq, exclude_flags, min_alt), () for the defaults."""
+
+    def __init__(self, ref_len, pac, opt=()):
+        self._h = C.c_void_p()
+        lens = np.ascontiguousarray(ref_len, dtype=np.int64)
+        _check(lib().bwahip_pileup_builder_open(len(lens), lens.ctypes.data if len(lens) else None, bytes(pac) if pac is not None else None, C.byref(pileup_opt(*opt)),
+                                                C.byref(self._h)), "bwahip_pileup_builder_open")
+
+    def add_records(self, rec, rec_off):
+        rec = bytes(rec)
+        rec_off = np.ascontiguousarray(rec_off, dtype=np.int64)
+        _check(lib().bwahip_pileup_builder_add_records(self._h, rec, rec_off.ctypes.data, len(rec_off) - 1), "bwahip_pileup_builder_add_records")
+
+    def finish(self, pu_fd=-1):
+        _check(lib().bwahip_pileup_builder_finish(self._h, pu_fd), "bwahip_pileup_builder_finish")
+
+    def close(self):
+        if self._h:
+            lib().bwahip_pileup_builder_close(self._h)
             self._h = C.c_void_p()
 
     def __enter__(self):
@@ -1109,6 +1187,24 @@ class Context:
         _check(rc, "bwahip_kat_qc")
         return out[:ln.value].tobytes()
 
+    def kat_pileup(self, rec, rec_off, ref_len, pac, opt=()):
+        """The pileup stage of the device merger (csrc/k_pileup.hip) on these records (any order) for these contig lengths and this packed
+        reference: the BPU\1 bytes.  opt = (min_mapq, min_baseq, exclude_flags, min_alt), () for the defaults."""
+        rec = bytes(rec)
+        rec_off = np.ascontiguousarray(rec_off, dtype=np.int64)
+        lens = np.ascontiguousarray(ref_len, dtype=np.int64)
+        src = np.frombuffer(rec, dtype=np.uint8) if rec else np.zeros(1, dtype=np.uint8)
+        ln = C.c_int64()
+        out = np.empty(1 << 20, dtype=np.uint8)
+        for _ in range(2):
+            rc = lib().bwahip_kat_pileup(self._h, src.ctypes.data, rec_off.ctypes.data, len(rec_off) - 1, len(lens), lens.ctypes.data if len(lens) else None,
+                                         bytes(pac) if pac is not None else None, C.byref(pileup_opt(*opt)), out.ctypes.data, len(out), C.byref(ln))
+            if rc != -5 or ln.value <= len(out):
+                break
+            out = np.empty(ln.value, dtype=np.uint8)                # the first answer said how much it takes
+        _check(rc, "bwahip_kat_pileup")
+        return out[:ln.value].tobytes()
+
     def kat_dup_desc(self, rec, off, paired=False):
         """The batch's descriptor kernel (csrc/k_markdup.hip) on these records in input order: read i = rec[off[i]:off[i+1]]; one
         descriptor per read, or per two reads (paired), as a DUP_DESC_DTYPE array."""
@@ -1450,6 +1546,28 @@ def stream_run_bam_sorted_dev_qc(ctxs, fq1, fq2=None, out_fd=-1, bai_fd=-1, qc_f
                                                      os.fsencode(fq2) if fq2 else None, out_fd, hdr_line, C.byref(st), C.byref(sd), bai_fd, C.byref(ms), int(bool(markdup)),
                                                      C.byref(qc_opt(*qc)), qc_fd, C.byref(qs)), "bwahip_stream_run_bam_sorted_dev_qc")
     return st, sd, ms, qs
+
+
+def stream_run_bam_sorted_dev_pileup(ctxs, fq1, fq2=None, out_fd=-1, bai_fd=-1, qc_fd=-1, pu_fd=-1, markdup=False, qc=None, pileup=(), hdr_line=None, opt=None,
+                                     chunk_bases=0, max_reads=0, keep_comments=False, reader_threads=0, pes0=None, hbm_budget=0, piece_blocks=0):
+    """bwahip_stream_run_bam_sorted_dev_pileup: the device-merged sorted BAM file with the pileup of the file on pu_fd (csrc/k_pileup.hip), over
+    the contexts' reference.  bai_fd >= 0: the index; markdup: duplicates marked; qc = (window_shift, exclude_flags, min_mapq) or (): the QC
+    summary on qc_fd; pileup = (min_mapq, min_baseq, exclude_flags, min_alt), None to pass no options.  No host fall-back.  Returns
+    (StreamStats, SortDevStats, MarkdupStats, QcStats, PileupStats)."""
+    opt = opt or default_opt()
+    st, sd, ms, qs, ps = StreamStats(), SortDevStats(), MarkdupStats(), QcStats(), PileupStats()
+    st.chunk_bases, st.max_reads, st.keep_comments, st.reader_threads = chunk_bases, max_reads, int(keep_comments), reader_threads
+    sd.tmp_dir, sd.mem_budget, sd.level = None, 0, 1
+    sd.hbm_budget, sd.piece_blocks = hbm_budget, piece_blocks
+    arr = (C.c_void_p * len(ctxs))(*[c._h for c in ctxs])
+    if isinstance(hdr_line, str):
+        hdr_line = hdr_line.encode()
+    _check(lib().bwahip_stream_run_bam_sorted_dev_pileup(arr, len(ctxs), C.byref(opt), C.byref(pes0) if pes0 is not None else None, os.fsencode(fq1),
+                                                         os.fsencode(fq2) if fq2 else None, out_fd, hdr_line, C.byref(st), C.byref(sd), bai_fd, int(bool(markdup)), C.byref(ms),
+                                                         C.byref(qc_opt(*qc)) if qc is not None else None, qc_fd, C.byref(qs),
+                                                         C.byref(pileup_opt(*pileup)) if pileup is not None else None, pu_fd, C.byref(ps)),
+           "bwahip_stream_run_bam_sorted_dev_pileup")
+    return st, sd, ms, qs, ps
 
 
 def stream_run_bam_sorted_dev_spill(ctxs, fq1, fq2=None, out_fd=-1, bai_fd=-1, qc_fd=-1, markdup=False, qc=None, hdr_line=None, opt=None, chunk_bases=0, max_reads=0,

@@ -318,12 +318,12 @@ int  bam_devmerger_add_dev(bwahip_bam_devmerger *m, int64_t run_no, const uint8_
 // spilled run is refused (BWAHIP_EINVAL) and keeps its runs: their record bytes are in its store
 int  bam_devmerger_take_runs(bwahip_bam_devmerger *m, std::vector<std::pair<int64_t, DevRun*>> *out);
 // What one finish of a device merger runs beside the members, and where the stages' outputs go: resolved once, by the three
-// bwahip_bam_devmerger_finish* entry points or by a sink of the stream driver.  The QC stage is the merger's armed state
-// (bwahip_bam_devmerger_set_qc), the windowed path follows from its runs: the finish fills both in.
+// bwahip_bam_devmerger_finish* entry points or by a sink of the stream driver.  The QC stage and the pileup are the merger's armed state
+// (bwahip_bam_devmerger_set_qc, _set_pileup), the windowed path follows from its runs: the finish fills them in.
 struct FinishPlan {
 	bool index = false; int bai_fd = -1; int64_t base = 0; int32_t n_ref = 0; bwahip_bai_stats_t *bs = nullptr;   // the .bai of what is written (base: the first member's offset in the file)
 	bool mark = false; bwahip_markdup_stats_t *ms = nullptr;       // duplicates marked before anything is gathered (ms may be null)
-	bool qc = false, spill = false;                                // filled in by the finish
+	bool qc = false, pileup = false, spill = false;                // filled in by the finish
 };
 int  bam_devmerger_finish(bwahip_bam_devmerger *m, int fd, bwahip_devmerge_stats_t *st, FinishPlan plan);
 // k_bai.hip: the index stage of a device merger's finish.  bai_stage_members: room for the lengths of n_blocks members (the caller fills
@@ -370,6 +370,17 @@ void qc_stage_free(QcStage *s);
 int  qc_stage_begin(QcStage *s, bwahip_ctx *c, int32_t n_ref, const int64_t *ref_len, const bwahip_qc_opt_t &opt, int64_t n_records);
 int  qc_stage_records(QcStage *s, bwahip_ctx *c, const uint8_t *rec, const int64_t *off, int64_t n_rec, int64_t len, int64_t ord0);
 int  qc_stage_finish(QcStage *s, bwahip_ctx *c, std::vector<uint8_t> *bytes, bwahip_qc_stats_t *qs);
+// k_pileup.hip: the pileup stage of a device merger's finish, on c->stream.  begin: these contigs, the packed reference (d_pac: where it lies
+// in HBM; or h_pac: uploaded here, once per non-zero h_pac_gen) and the (resolved) options, the per-record words; records: the observations of one run are counted -- the
+// run is read again by finish and stays where it is until then; finish: the keys, their sort, alleles, sites and evidence, the one download
+// (awaited) and the file's bytes -- BWAHIP_EINVAL when a record was refused.  n_records == 0 launches nothing.
+struct PileupStage;
+PileupStage *pu_stage_new();
+void pu_stage_free(PileupStage *s);
+int  pu_stage_begin(PileupStage *s, bwahip_ctx *c, int32_t n_ref, const int64_t *ref_len, const uint8_t *d_pac, const uint8_t *h_pac, uint64_t h_pac_gen, const bwahip_pileup_opt_t &opt,
+                     int64_t n_records);
+int  pu_stage_records(PileupStage *s, bwahip_ctx *c, const uint8_t *rec, const int64_t *off, int64_t n_rec, int64_t len, int64_t ord0);
+int  pu_stage_finish(PileupStage *s, bwahip_ctx *c, std::vector<uint8_t> *bytes, bwahip_pileup_stats_t *ps);
 int bam_check_reads(int n, const bwahip_seq_t *seqs);   // bam_host.cpp: BWAHIP_EINVAL (with a message naming the read) for a name or a comment BAM cannot hold
 void pipe_destroy(bwahip_ctx *c);                                                     // final_rt.hip: the stream driver's buffer sets
 int final_setup(bwahip_ctx *c);                                                       // contig name tables for the SAM kernels

@@ -20,17 +20,19 @@
 // total and then the members of piece k - 1 come back on the copy stream and are written.  No kernel here uses LDS or atomics.
 //
 // Beside the members a finish runs the stages its FinishPlan names (ctx_internal.h): duplicate marking (k_markdup.hip: one bit of a record
-// changes and no key), the QC summary (k_qc.hip: it reads and changes nothing), the BAI index (k_bai.hip, after the last piece).  Marking and
-// QC read every record.  That is the records pass: a resident run's records pass before the order is made, one stage after the other over
+// changes and no key), the QC summary (k_qc.hip: it reads and changes nothing), the pileup (k_pileup.hip: the same; resident runs only), the
+// BAI index (k_bai.hip, after the last piece).  Marking, QC and the pileup read every record.  That is the records pass: a resident run's records pass before the order is made, one stage after the other over
 // all runs, and each stage is awaited there.  A spilled run (bwahip_bam_devmerger_set_spill, k_bamspill.hip) keeps its record bytes in a
 // host-side store; they are staged one window of pieces at a time (spill_plan.h), the gather finds them in the staging buffer, and the slices
 // pass the stages -- and the index parse -- in their window, so the await is deferred behind the last window.  A merger without a stage
 // and without a spilled run queues exactly what is described above.  Finish::run is the list of steps, each a function of its own: the
 // checks; the records pass over resident runs; the order; the source table and output offsets; the piece cuts; the piece buffers; the window
-// plan, if spilled; the piece loop; the deferred await; the index; the QC file; the stats (an empty merger: the first two, the last four).
+// plan, if spilled; the piece loop; the deferred await; the index; the QC file; the pileup file; the stats (an empty merger: the first
+// two, the last five).
 #include "ctx_internal.h"
 #include "bai_tables.h"
 #include "qc_tables.h"
+#include "pileup_tables.h"
 #include "spill_plan.h"
 #include "spill_store.h"
 #include <errno.h>
@@ -193,6 +195,10 @@ struct bwahip_bam_devmerger {
 	bool spill_armed = false, added = false; int window_pieces = 0; SpillStore *store = nullptr; SpillWork sw;
 	int64_t n_spilled = 0, n_windows = 0; double download_s = 0, upload_ms = 0;
 	bool qc_armed = false; bwahip_qc_opt_t qc_opt = { 14, 1796, 0 }; std::vector<int64_t> qc_len; int qc_fd = -1; bwahip_qc_stats_t *qc_stats = nullptr;
+	// the pileup (bwahip_bam_devmerger_set_pileup): pu_pac empty = the context's packed reference, where it lies in HBM
+	std::unique_ptr<PileupStage, void (*)(PileupStage*)> pu{ nullptr, pu_stage_free };
+	bool pu_armed = false; bwahip_pileup_opt_t pu_opt = { 0, 0, 1796, 2 }; std::vector<int64_t> pu_len; std::vector<uint8_t> pu_pac; bool pu_own_pac = false; uint64_t pu_gen = 0; int pu_fd = -1;
+	bwahip_pileup_stats_t *pu_stats = nullptr;
 };
 
 int bam_devrun_make(bwahip_ctx *c, const uint8_t *d_rec, int64_t len, const uint64_t *d_keys, const int64_t *d_rec_off, int64_t n_rec, hipStream_t st, DevRun **out)
@@ -406,7 +412,7 @@ extern "C" int bwahip_bam_devmerger_set_spill(bwahip_bam_devmerger *m, const bwa
 {
 	if (!m || !in || in->host_budget < 0 || in->window_pieces > 65536) return BWAHIP_EINVAL;
 	std::lock_guard<std::mutex> lk(m->mu);
-	if (m->added || m->spill_armed) return BWAHIP_EINVAL;           // before the first add, once
+	if (m->added || m->spill_armed || m->pu_armed) return BWAHIP_EINVAL;   // before the first add, once; the pileup reads resident runs only
 	if (!(m->store = spill_store_new(in->host_budget, in->tmp_dir, pinned_alloc, pinned_free, m->c))) return BWAHIP_ENOMEM;
 	m->window_pieces = in->window_pieces > 0 ? in->window_pieces : DEFAULT_WINDOW_PIECES;
 	m->spill_armed = true;
@@ -417,7 +423,7 @@ extern "C" int bwahip_bam_devmerger_set_spill(bwahip_bam_devmerger *m, const bwa
 extern "C" int bwahip_bam_devmerger_add_spilled(bwahip_bam_devmerger *m, int64_t run_no, const uint8_t *rec, int64_t len, const uint64_t *keys, const int64_t *rec_off, int64_t n_rec,
                                                 const uint32_t *tmpl, const bwahip_dup_desc_t *desc, int64_t n_tmpl)
 {
-	if (!m || !m->spill_armed) return BWAHIP_EINVAL;
+	if (!m || !m->spill_armed || m->pu_armed) return BWAHIP_EINVAL;
 	const bool with_dup = tmpl || desc;
 	if (!with_dup && n_tmpl) return BWAHIP_EINVAL;
 	return devmerger_add(m, run_no, rec, len, keys, rec_off, n_rec, with_dup, tmpl, desc, n_tmpl, true);
@@ -438,7 +444,7 @@ extern "C" int bwahip_bam_devmerger_spill_stats(bwahip_bam_devmerger *m, bwahip_
 // ---- finish ---------------------------------------------------------------------------------------------------------------------------
 namespace {
 
-// ---- the stages that read records: marking (k_markdup.hip), then QC (k_qc.hip)
+// ---- the stages that read records: marking (k_markdup.hip), then QC (k_qc.hip), then the pileup (k_pileup.hip)
 // Marking's own beginning, on the context's stream: the runs' descriptors concatenated in run order, the decision, the counts
 int mark_decide(bwahip_bam_devmerger *m)
 {
@@ -489,7 +495,7 @@ int mark_end(bwahip_bam_devmerger *m, bwahip_markdup_stats_t *ms)
 	return 0;
 }
 
-enum { RS_MARK = 1, RS_QC = 2 };                                  // the stages that read every record, in the order they run
+enum { RS_MARK = 1, RS_QC = 2, RS_PILEUP = 4 };                   // the stages that read every record, in the order they run
 
 // One finish: the merger, the plan, the locals the steps hand on, and the steps themselves -- run() at the end is their list
 struct Finish {
@@ -502,12 +508,12 @@ struct Finish {
 	const unsigned *idx = nullptr;                                 // the order: the ordinal at every sorted place
 	int64_t piece_bytes = 0; int n_pieces = 0; std::vector<int> piece_first;
 	int *mlen_all = nullptr;                                       // the whole stream's member lengths, for the index
-	std::vector<uint8_t> qc_bytes;                                 // written once the members are
+	std::vector<uint8_t> qc_bytes, pu_bytes;                       // written once the members are
 	// spilled runs: the window plan; by index in run order the run, its number, its first ordinal and template; [window][run] the slices' bases
 	SpillPlan sp; int wp = 1; bool parsed = false;                 // parsed: the index parse ran window by window
 	std::vector<DevRun*> runv; std::vector<int64_t> run_id, rec_at, tmpl_at, base; std::vector<uint8_t> flags;
-	Finish(bwahip_bam_devmerger *m_, const FinishPlan &p, int fd_) : m(m_), plan(p), fd(fd_) { plan.qc = m->qc_armed; plan.spill = m->n_spilled > 0; }
-	int stages() const { return (plan.mark ? RS_MARK : 0) | (plan.qc ? RS_QC : 0); }
+	Finish(bwahip_bam_devmerger *m_, const FinishPlan &p, int fd_) : m(m_), plan(p), fd(fd_) { plan.qc = m->qc_armed; plan.pileup = m->pu_armed; plan.spill = m->n_spilled > 0; }
+	int stages() const { return (plan.mark ? RS_MARK : 0) | (plan.qc ? RS_QC : 0) | (plan.pileup ? RS_PILEUP : 0); }
 	int64_t piece_len(int p) const { const int64_t lo = (int64_t)p * piece_bytes; return total - lo < piece_bytes ? total - lo : piece_bytes; }
 	// The records pass: positions [lo, hi) of run r through the stages `which`, on the context's stream.  rec + r->off[i] is record i: rec is the
 	// run's bytes, or the base of a staged slice.  [lo, counted) are counted; a record in [counted, hi) -- the next window stages it again -- is
@@ -519,7 +525,8 @@ struct Finish {
 			if ((rc = markdup_mark_run(m->md.get(), c, rec, r->off() + lo, counted - lo, r->len, r->tmpl() + lo, tmpl0, r->n_tmpl))) return rc;
 			if (hi > counted && (rc = markdup_mark_run(m->md.get(), c, rec, r->off() + counted, hi - counted, r->len, r->tmpl() + counted, tmpl0, r->n_tmpl, sw.scratch.as<unsigned long long>()))) return rc;
 		}
-		return which & RS_QC ? qc_stage_records(m->qc.get(), c, rec, r->off() + lo, counted - lo, r->len, ord0 + lo) : 0;
+		if ((which & RS_QC) && (rc = qc_stage_records(m->qc.get(), c, rec, r->off() + lo, counted - lo, r->len, ord0 + lo))) return rc;
+		return which & RS_PILEUP ? pu_stage_records(m->pu.get(), c, rec, r->off() + lo, counted - lo, r->len, ord0 + lo) : 0;
 	}
 	// The records pass is over for the stages `which`: each awaits the stream, the counters and the tables come back.  Without a spilled run that is
 	// before the order, stage by stage (resident_pass); with one, after the last window (tail)
@@ -527,6 +534,7 @@ struct Finish {
 	{
 		int rc = which & RS_MARK ? mark_end(m, plan.ms) : 0;
 		if (!rc && (which & RS_QC)) rc = qc_stage_finish(m->qc.get(), c, &qc_bytes, m->qc_stats);
+		if (!rc && (which & RS_PILEUP)) rc = pu_stage_finish(m->pu.get(), c, &pu_bytes, m->pu_stats);
 		return rc;
 	}
 	int checks()
@@ -534,6 +542,8 @@ struct Finish {
 		if (plan.mark) for (auto &kv : m->runs) if (!kv.second->has_dup) return BWAHIP_EINVAL;   // before a byte is written
 		if (plan.mark && !m->md) m->md.reset(new MarkdupStage);
 		if (plan.qc && !m->qc) m->qc.reset(qc_stage_new());
+		if (plan.pileup && plan.spill) return BWAHIP_EINVAL;         // (the setters keep the two apart)
+		if (plan.pileup && !m->pu) m->pu.reset(pu_stage_new());
 		if (plan.index && !m->bai) m->bai.reset(bai_stage_new());
 		memset(&s, 0, sizeof s);
 		s.n_records = m->n_records; s.n_runs = (int64_t)m->runs.size(); s.raw_bytes = m->raw_bytes; s.n_blocks = bgzf_blocks(m->raw_bytes);
@@ -544,9 +554,11 @@ struct Finish {
 	// the resident runs' records pass, one stage after the other over all runs (a spilled run's records pass in the windows that stage them)
 	int resident_pass()
 	{
-		for (int stage : { RS_MARK, RS_QC }) {
+		for (int stage : { RS_MARK, RS_QC, RS_PILEUP }) {
 			if (!(stages() & stage)) continue;
-			int rc = stage == RS_MARK ? mark_decide(m) : qc_stage_begin(m->qc.get(), c, (int32_t)m->qc_len.size(), m->qc_len.data(), m->qc_opt, m->n_records);
+			int rc = stage == RS_MARK ? mark_decide(m) : stage == RS_QC ? qc_stage_begin(m->qc.get(), c, (int32_t)m->qc_len.size(), m->qc_len.data(), m->qc_opt, m->n_records) :
+			         pu_stage_begin(m->pu.get(), c, (int32_t)m->pu_len.size(), m->pu_len.data(), m->pu_own_pac ? nullptr : c->d_pac.as<uint8_t>(), m->pu_own_pac ? m->pu_pac.data() : nullptr,
+			                        m->pu_gen, m->pu_opt, m->n_records);
 			int64_t ord = 0, tmpl = 0;
 			for (auto &kv : m->runs) {
 				const DevRun *r = kv.second;
@@ -794,6 +806,7 @@ struct Finish {
 			if (!rc) rc = bai_write_fd(plan.bai_fd, bytes);
 		}
 		if (!rc && plan.qc) rc = qc_write_fd(m->qc_fd, qc_bytes);
+		if (!rc && plan.pileup) rc = pu_write_fd(m->pu_fd, pu_bytes);
 		s.finish_s = now_s() - t0;
 		if (st) *st = s;
 		return rc;
@@ -846,6 +859,30 @@ extern "C" int bwahip_bam_devmerger_set_qc(bwahip_bam_devmerger *m, const bwahip
 	if ((rc = qc_resolve(opt, &o)) || (rc = qc_check_refs(n_ref, ref_len, nullptr))) return rc;   // the merger is as before
 	m->qc_opt = o; m->qc_len.assign(ref_len, ref_len + n_ref); m->qc_fd = qc_fd; m->qc_stats = qs; m->qc_armed = true;
 	if (qs) memset(qs, 0, sizeof *qs);
+	return 0;
+}
+
+extern "C" int bwahip_bam_devmerger_set_pileup(bwahip_bam_devmerger *m, const bwahip_pileup_opt_t *opt, int32_t n_ref, const int64_t *ref_len, const uint8_t *pac, int pu_fd,
+                                               bwahip_pileup_stats_t *ps)
+{
+	if (!m) return BWAHIP_EINVAL;
+	std::lock_guard<std::mutex> lk(m->mu);
+	if (!opt) { m->pu_armed = false; m->pu_stats = nullptr; return 0; }
+	if (m->spill_armed) return BWAHIP_EINVAL;                       // the evidence pass reads resident runs only
+	bwahip_pileup_opt_t o;
+	int64_t sum = 0;
+	int rc;
+	if ((rc = pu_resolve(opt, &o)) || (rc = pu_check_refs(n_ref, ref_len, &sum))) return rc;   // the merger is as before
+	if (!pac) {                                                    // the context's index: these must be its contigs
+		const bwahip_bns_t &bns = m->c->host.bns;
+		if (n_ref != bns.n_seqs || sum != bns.l_pac || !m->c->d_pac.p) return BWAHIP_EINVAL;
+		for (int32_t r = 0; r < n_ref; ++r) if (ref_len[r] != bns.anns[r].len) return BWAHIP_EINVAL;
+	}
+	m->pu_opt = o; m->pu_len.assign(ref_len, ref_len + n_ref); m->pu_fd = pu_fd; m->pu_stats = ps; m->pu_own_pac = pac != nullptr;
+	if (pac) m->pu_pac.assign(pac, pac + (sum + 3) / 4); else m->pu_pac.clear();
+	++m->pu_gen;                                                   // the stage uploads the copy once
+	m->pu_armed = true;
+	if (ps) memset(ps, 0, sizeof *ps);
 	return 0;
 }
 

@@ -158,6 +158,9 @@ struct DevSortedSink : Sink {
 	int64_t bai_windows = 0;                                     // with the index: the 16 Kbp windows of the contig table, for the stage's share of the budget
 	const bwahip_qc_opt_t *qo = nullptr; int qc_fd = -1; bwahip_qc_stats_t *qs = nullptr;   // bwahip_stream_run_bam_sorted_dev_qc: the summary of the file on qc_fd
 	std::vector<int64_t> qc_len; int64_t qc_need = 0, qc_windows = 0; bwahip_qc_builder *qb = nullptr;   // the contigs' lengths, the stage's share of the budget; the fall-back's builder
+	const bwahip_pileup_opt_t *po = nullptr; int pu_fd = -1; bwahip_pileup_stats_t *ps = nullptr;   // bwahip_stream_run_bam_sorted_dev_pileup: the pileup of the file on pu_fd, no fall-back
+	std::vector<int64_t> pu_len;
+	bool no_host = false;                                        // a run that does not fit ends the call: nothing marks, or piles up, on the host
 	std::atomic<bool> fell_back{false};                          // read by the drainers: from now on they download
 	Stream fb_stream; HostBuf fb_rec, fb_keys, fb_off;   // the fall-back's downloads: their stream, one pinned buffer each for records, keys and offsets
 	DevSortedSink(const char *h, bwahip_sort_dev_t *s) : sd(s), host(h, s->level, s) { form = OutForm::BamSorted; }
@@ -165,11 +168,13 @@ struct DevSortedSink : Sink {
 	// does not fit ends the call, sd->level has no reader, the index is written only for bai_fd >= 0; a sink that may fall back always indexes
 	void configure(int bai_fd, bool mark, bwahip_markdup_stats_t *ms_, const bwahip_qc_opt_t *qo_, int qc_fd_, bwahip_qc_stats_t *qs_, bool no_fallback)
 	{
-		if (mark) { form = OutForm::BamSortedDup; markdup = true; ms = ms_; }
+		if (mark) { form = OutForm::BamSortedDup; markdup = true; ms = ms_; no_host = true; }
 		if (no_fallback) host.level = 1;
 		if (!no_fallback || bai_fd >= 0) { host.with_bai = true; host.bai_fd = bai_fd; }
 		if (qo_) { qo = qo_; qc_fd = qc_fd_; qs = qs_; }
 	}
+	// beside configure(..., no_fallback = true): the pileup of the file on pu_fd_ (k_pileup.hip), over the contexts' reference
+	void configure_pileup(const bwahip_pileup_opt_t *po_, int pu_fd_, bwahip_pileup_stats_t *ps_) { po = po_; pu_fd = pu_fd_; ps = ps_; no_host = true; }
 	~DevSortedSink()
 	{
 		if (ctx0) (void)hipSetDevice(ctx0->device);
@@ -195,6 +200,11 @@ struct DevSortedSink : Sink {
 			for (int64_t L : qc_len) { sum += L; qc_windows += (L + (1ll << ws) - 1) >> ws; }
 			qc_need = bwahip_qc_hbm_need((int64_t)qc_len.size(), sum, qc_windows, 0);
 		}
+		if (po) {                                                   // as the QC options: refused here
+			const bwahip_bns_t *bns = bwahip_bns(ctxs[0]);
+			for (int32_t i = 0; i < bns->n_seqs; ++i) pu_len.push_back(bns->anns[i].len);
+			if ((r = bwahip_bam_devmerger_set_pileup(dm, po, (int32_t)pu_len.size(), pu_len.data(), nullptr, pu_fd, ps))) return r;
+		}
 		ctx0 = ctxs[0]; hbm_budget = sd->hbm_budget;
 		piece_blocks = sd->piece_blocks > 0 ? sd->piece_blocks : ctx0->knobs.sorted_piece_blocks;
 		if (!hbm_budget) {                                          // half of what the device has free now
@@ -210,7 +220,7 @@ struct DevSortedSink : Sink {
 		if (!fell_back) {                                           // the run stays in HBM: no download, the writer gets an item without bytes and both sets go back at once
 			const int r = pipe_stage_out_devrun(c, out, &it.run, &it.raw_len, &it.n_rec, &it.gpu_ms, t_end);
 			if (r || it.run) { it.len = it.raw_len; it.holds_set = false; return r; }
-			if (markdup) return BWAHIP_ECAPACITY;                    // the run's buffers could not be allocated, and nothing marks on the host
+			if (no_host) return BWAHIP_ECAPACITY;                    // the run's buffers could not be allocated, and nothing marks on the host
 		}                                                           // (its buffers could not be allocated: downloaded as any run after a fall-back, which it causes)
 		return host.stage_out(c, out, it, t_end);
 	}
@@ -220,6 +230,7 @@ struct DevSortedSink : Sink {
 		int64_t need = qc_need;
 		if (host.with_bai) need += bwahip_bam_devmerge_bai_hbm_need(n_rec, bgzf_blocks(raw), host.n_ref, bai_windows);
 		if (markdup) need += bwahip_bam_devmerge_markdup_hbm_need(n_rec, n_tmpl);
+		if (po) need += bwahip_pileup_hbm_need(n_rec);
 		return need;
 	}
 	// a run in HBM -> the host merger, through the pinned buffers; the run is freed whatever happens
@@ -252,7 +263,7 @@ struct DevSortedSink : Sink {
 			const int64_t need = bwahip_bam_devmerge_hbm_need(held_raw + it.raw_len, held_rec + it.n_rec, seq_no + 1, piece_blocks) +
 			                     stages_need(held_rec + it.n_rec, held_raw + it.raw_len, held_tmpl + (it.run ? it.run->n_tmpl : 0));
 			const bool fits = it.run && need <= hbm_budget;
-			if (!fits) r = markdup ? BWAHIP_ECAPACITY : fall_back(seq_no);
+			if (!fits) r = no_host ? BWAHIP_ECAPACITY : fall_back(seq_no);
 		}
 		if (!r && !fell_back) { if (!(r = bam_devmerger_adopt(dm, seq_no, it.run))) { held_tmpl += it.run->n_tmpl; it.run = nullptr; held_raw += it.raw_len; held_rec += it.n_rec; host.sort_ms += it.gpu_ms; } }
 		else if (!r && it.run) { r = run_to_host(seq_no, it.run, it.gpu_ms); it.run = nullptr; }
@@ -658,6 +669,23 @@ extern "C" int bwahip_stream_run_bam_sorted_dev_qc(bwahip_ctx *const *ctxs, int 
 	if (qs) memset(qs, 0, sizeof *qs);
 	DevSortedSink sink(hdr_line, sd);
 	sink.configure(bai_fd, markdup != 0, ms, qo, qc_fd, qs, markdup != 0);   // unmarked, the run may end on the host: it always indexes
+	return stream_run(ctxs, n_ctx, opt, pes0, fq1, fq2, out_fd, st, sink);
+}
+
+// The device-merged entry points with the pileup of the file on pu_fd (k_pileup.hip): the sink as _dev_markdup or _dev_qc configure it, without a
+// fall-back, its merger armed for the pileup over the contexts' reference
+extern "C" int bwahip_stream_run_bam_sorted_dev_pileup(bwahip_ctx *const *ctxs, int n_ctx, const bwahip_opt_t *opt, const bwahip_pestat_t *pes0,
+                                                       const char *fq1, const char *fq2, int out_fd, const char *hdr_line, bwahip_stream_t *st, bwahip_sort_dev_t *sd, int bai_fd,
+                                                       int mark, bwahip_markdup_stats_t *ms, const bwahip_qc_opt_t *qc, int qc_fd, bwahip_qc_stats_t *qs,
+                                                       const bwahip_pileup_opt_t *pu, int pu_fd, bwahip_pileup_stats_t *ps)
+{
+	if (!sd || !pu) return BWAHIP_EINVAL;
+	if (ms) memset(ms, 0, sizeof *ms);
+	if (qs) memset(qs, 0, sizeof *qs);
+	if (ps) memset(ps, 0, sizeof *ps);
+	DevSortedSink sink(hdr_line, sd);
+	sink.configure(bai_fd, mark != 0, ms, qc, qc_fd, qs, true);
+	sink.configure_pileup(pu, pu_fd, ps);
 	return stream_run(ctxs, n_ctx, opt, pes0, fq1, fq2, out_fd, st, sink);
 }
 

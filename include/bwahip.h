@@ -644,6 +644,98 @@ int  bwahip_stream_run_bam_sorted_dev_qc(bwahip_ctx *const *ctxs, int n_ctx, con
                                          int out_fd, const char *hdr_line, bwahip_stream_t *st, bwahip_sort_dev_t *sd, int bai_fd, bwahip_markdup_stats_t *ms,
                                          int markdup, const bwahip_qc_opt_t *qo, int qc_fd, bwahip_qc_stats_t *qs);
 
+/* ---- Pileup of candidate variant sites of coordinate-sorted BAM (csrc/k_pileup.hip on the device, csrc/pileup_host.cpp without one) ----
+ * Where the reads disagree with the reference, and how strongly: one canonical table, recomputable from the records of the file, the
+ * contig lengths and the packed reference alone.  All values are integers.  The result does not depend on the order of the records, on
+ * how they are cut into runs or calls, or on the order in which wavefronts run.  No indel is normalised or left-aligned.  Equality with
+ * the output of samtools mpileup or bcftools is not claimed.
+ *   Options         min_mapq in [0, 255]; min_baseq in [0, 93]; exclude_flags in [0, 65535], < 0 means 1796 (0x4 | 0x100 | 0x200 |
+ *                   0x400); min_alt in [1, 65535], 0 means 2.  Anything else: BWAHIP_EINVAL before anything is launched.  The file holds
+ *                   them as resolved.
+ *   Reference       n_ref contigs of ref_len[r] bases (0 .. 2^31 - 1 each); contig r begins at base ref_off[r] = the sum of the earlier
+ *                   lengths of the packed sequence, which has .pac's layout: 2 bits per base (A C G T = 0 1 2 3), base i in byte i >> 2
+ *                   at shift (~i & 3) << 1; (sum of the lengths + 3) / 4 bytes are read.  A sum of 2^40 or more: BWAHIP_ECAPACITY.
+ *                   Inside an ambiguity hole the reference base is whatever .pac holds there, as for the MD tag: there is no hole table.
+ *   Per record      the checks of the QC summary above, and two more, both BWAHIP_EINVAL: l_seq < 0; 36 + l_read_name +
+ *                   4 * n_cigar_op + (l_seq + 1) / 2 + l_seq beyond the record.  The first offending record in the order given decides.
+ *                   No byte outside a record is read.
+ *   Taking part     a record takes part when refID >= 0, flag & exclude_flags == 0, mapq >= min_mapq, l_seq > 0 and the query length
+ *                   of its CIGAR (the lengths of M I S = X) equals l_seq.  Any other record contributes nothing and is not refused.
+ *   Walk            p starts at pos, q at 0.  M = X advance both, I and S advance q, D and N advance p, H, P and the operation codes
+ *                   9 .. 15 advance neither; an operation of length 0 gives nothing.  Base q is the BAM code in the high (q even) or
+ *                   low nibble of seq[q >> 1].  A base passes when the record's first quality byte is 0xff or its own quality is >=
+ *                   min_baseq.  Everything at a p outside [0, contig length) is dropped.
+ *   Observations    kind 0, SNV: an M = X base that is one of A C G T (codes 1 2 4 8), passes and differs from the reference base; at
+ *                           its own p; len 1, bases = the base as 0 .. 3.
+ *                   kind 1, DEL: each D operation; at p = its first base; len = min(length, 2^21 - 1), bases 0.
+ *                   kind 2, INS: each I operation whose bases are all A C G T (qualities are not looked at); at p = the reference base
+ *                           that follows (dropped when that is the contig's end); len = min(length, 31), bases = its first
+ *                           min(length, 8) bases at 2 bits each, the first base lowest.  Longer insertions that agree in these merge.
+ *                   Bases other than A C G T are never evidence.  Each observation counts under the record's strand (flag & 0x10).
+ *   Sites           an allele is a (refID, p, kind, len, bases) with fwd and rev observations; it is kept when fwd + rev >= min_alt.  A
+ *                   site is a (refID, p) with at least one kept allele.  Per site: ref_base (0 .. 3); n_alleles, its kept alleles;
+ *                   n_cov, the records taking part whose M = X or D operations cover p (overlapping mates both count); n_ref_fwd and
+ *                   n_ref_rev, the M = X bases at p that are one of A C G T, pass and equal the reference base, by strand.
+ *   The file        little endian, no padding, 64 + 28 * n_sites + 20 * n_alleles bytes.  Sites ascend by (refID, pos); the alleles
+ *                   follow in site order and within a site ascend by (kind, len, bases):
+ *                     char[4] "BPU\1" | int32 n_ref | int32 min_mapq, min_baseq, exclude_flags, min_alt | uint64 n_sites, n_alleles |
+ *                     uint64 n_obs[3] (all observations by kind, before min_alt) |
+ *                     n_sites x { int32 refID, pos; uint32 ref_base, n_alleles, n_cov, n_ref_fwd, n_ref_rev } |
+ *                     n_alleles x { uint32 kind, len, bases, fwd, rev }.
+ * Device-free builder (csrc/pileup_host.cpp): a judge and a library for small inputs, not wired into the host merger and no fall-back
+ * of anything.  open: the contig lengths, the packed reference (copied) and the options (NULL: all defaults).  add_records: whole
+ * records, record i is rec[rec_off[i] .. rec_off[i+1]), any cut into calls, any order.  finish: the file on pu_fd (< 0: built and
+ * dropped).  After a refusal every later call returns the same code.  It holds 12 bytes per base of every reference that a record has
+ * covered (n_cov, n_ref_fwd, n_ref_rev, made at the reference's first covering record), 8 bytes per observation, and its copy of the
+ * packed reference. */
+typedef struct { int min_mapq, min_baseq, exclude_flags, min_alt; } bwahip_pileup_opt_t;
+typedef struct {
+	int64_t n_sites, n_alleles, n_obs[3];         /* as in the file */
+	int64_t pu_bytes;                             /* bytes of the file */
+	int64_t hbm_bytes;                            /* what the stage held, the observation buffers and its share of the context's sort buffers included */
+	double pileup_ms, observe_ms, sort_ms, evidence_ms;   /* GPU time by HIP events: the stage; counting and writing the observations; the sort, the alleles and the sites; the evidence pass */
+} bwahip_pileup_stats_t;
+typedef struct bwahip_pileup_builder bwahip_pileup_builder;
+int  bwahip_pileup_builder_open(int32_t n_ref, const int64_t *ref_len, const uint8_t *pac, const bwahip_pileup_opt_t *opt, bwahip_pileup_builder **b);
+int  bwahip_pileup_builder_add_records(bwahip_pileup_builder *b, const uint8_t *rec, const int64_t *rec_off, int64_t n_rec);
+int  bwahip_pileup_builder_finish(bwahip_pileup_builder *b, int pu_fd);
+void bwahip_pileup_builder_close(bwahip_pileup_builder *b);
+/* The stage on the device (csrc/k_pileup.hip), 16 lanes per record: the observations of every record are counted and, after a prefix
+ * sum, written as 64-bit keys -- position among all contigs' bases (40 bits) | kind (2) | allele (21) | strand (1); the keys go through
+ * the stable radix sort of the coordinate sort; alleles and their strand counts are segment lengths of the sorted keys; the kept alleles
+ * and the distinct sites are compacted by prefix sums; a second pass over the records adds n_cov and n_ref to the sites inside each
+ * record's span (integer atomics); the compact tables come back in one awaited download and go through the host builder's serialiser.
+ * More than 2^31 - 1 observations: BWAHIP_ECAPACITY.
+ * bwahip_kat_pileup: exactly that stage on the caller's records (host pointers, any order) and the caller's packed reference; the file
+ * into out (out_cap too small: BWAHIP_ECAPACITY, *out_len says what it takes).  opt == NULL: all defaults.
+ * bwahip_bam_devmerger_set_pileup arms a device merger: every finish (_finish, _finish_bai, _finish_markdup) then runs the stage over the
+ * runs after the marking and the QC summary, if there are any, and before the order is made, and writes the file to pu_fd (< 0: built
+ * and dropped) once the members are written.  A refusal comes before a byte of the members is written.  pac == NULL: the reference is
+ * the context's index, where it lies in HBM; n_ref and ref_len must then equal its contig table (BWAHIP_EINVAL).  Otherwise the merger
+ * copies the packed reference and uploads it at the first armed finish that follows.  opt == NULL disarms (the other arguments are not looked at); an
+ * unarmed merger queues what it queued before.  *ps (may be NULL) is filled by every armed finish.  The evidence pass would need a
+ * second round of windows over spilled runs, so the two do not mix: a merger armed for spilling refuses set_pileup, and once armed for
+ * the pileup set_spill and add_spilled are refused, all with BWAHIP_EINVAL.
+ * bwahip_pileup_hbm_need: what is known of the stage's HBM before the data, with the eighth of slack its buffers grow with (no device;
+ * -1 for a negative argument): 12 bytes per record (its observations' count and their first slot) and 4 096 for the error word, the
+ * counters and the contig table's first entries.  The observation buffers -- 24 bytes per observation in the context's sort buffers, 12
+ * for the segment flags and their prefix sums, 32 per allele and per site -- are allocated at the finish, when their number is known;
+ * hbm_budget does not count them, and a failed allocation there is BWAHIP_ENOMEM before a byte of the members is written. */
+int  bwahip_kat_pileup(bwahip_ctx *ctx, const uint8_t *rec, const int64_t *rec_off, int64_t n_rec, int32_t n_ref, const int64_t *ref_len, const uint8_t *pac,
+                       const bwahip_pileup_opt_t *opt, uint8_t *out, int64_t out_cap, int64_t *out_len);
+int  bwahip_bam_devmerger_set_pileup(bwahip_bam_devmerger *m, const bwahip_pileup_opt_t *opt, int32_t n_ref, const int64_t *ref_len, const uint8_t *pac, int pu_fd,
+                                     bwahip_pileup_stats_t *ps);
+int64_t bwahip_pileup_hbm_need(int64_t n_records);
+/* bwahip_stream_run_bam_sorted_dev_markdup (mark != 0) or the device-merged sorted file without marking (mark == 0), with the index for
+ * bai_fd >= 0, the QC summary for qc != NULL and the pileup of the file on pu_fd; the reference is the contexts' index.  The BAM file,
+ * the index and the QC summary are those of the entry points without the pileup.  Never a host fall-back and never a spilled run: a run
+ * that does not fit hbm_budget (which counts bwahip_pileup_hbm_need too) ends the call with BWAHIP_ECAPACITY, as _dev_markdup does;
+ * sd->tmp_dir, mem_budget and level are not looked at.  pu == NULL: BWAHIP_EINVAL.  ms, qs and ps may be NULL. */
+int  bwahip_stream_run_bam_sorted_dev_pileup(bwahip_ctx *const *ctxs, int n_ctx, const bwahip_opt_t *opt, const bwahip_pestat_t *pes0, const char *fq1, const char *fq2,
+                                             int out_fd, const char *hdr_line, bwahip_stream_t *st, bwahip_sort_dev_t *sd, int bai_fd /* < 0: none */,
+                                             int mark, bwahip_markdup_stats_t *ms, const bwahip_qc_opt_t *qc /* NULL: none */, int qc_fd, bwahip_qc_stats_t *qs,
+                                             const bwahip_pileup_opt_t *pu, int pu_fd, bwahip_pileup_stats_t *ps);
+
 /* Runs whose record bytes outgrow HBM (csrc/k_bamspill.hip, csrc/spill_store.cpp).  A device merger armed with
  * bwahip_bam_devmerger_set_spill may hold a run spilled: keys, offsets, template indices and descriptors in HBM as for any run, the record
  * bytes in a host-side store -- pinned host memory while host_budget holds, otherwise the whole run in an unlinked file of tmp_dir (its
