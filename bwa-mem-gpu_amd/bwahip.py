@@ -150,6 +150,11 @@ CHAIN_FLT_NONE, CHAIN_FLT_SEQ, CHAIN_FLT_WAVE = 0, 1, 2
 KAT_GLOBAL_AUTO_SMALL, KAT_GLOBAL_AUTO_BIG, KAT_GLOBAL_SCORE_ONLY = 0, 1, 2
 KAT_MAX_CIGAR = 512
 KAT_MARK_TAG, KAT_MARK_WORDS = 41, 25                       # bwahip_kat_mark's record: 4 header words, then 25 per region
+# bwahip_kat_dedup (bwahip.h): forms, and the diag word -- who finished the read, handed over, one-lane sorts, why k_dedup_fast refused, counts
+KAT_DEDUP_PRODUCT, KAT_DEDUP_FULL, KAT_DEDUP_SLAB = 0, 1, 2
+KAT_DEDUP_FAST, KAT_DEDUP_STAGED, KAT_DEDUP_GLOBAL, KAT_DEDUP_SLABBED, KAT_DEDUP_HANDED, KAT_DEDUP_LANE1, KAT_DEDUP_LANE2 = 1, 2, 4, 8, 16, 32, 64
+KAT_DEDUP_WHY_SHIFT, KAT_DEDUP_ALN_SHIFT, KAT_DEDUP_MRG_SHIFT = 7, 9, 20
+KAT_DEDUP_WHY_TIE1, KAT_DEDUP_WHY_PATCH, KAT_DEDUP_WHY_TIE2 = 1, 2, 3
 KAT_EXT_ROWS1, KAT_EXT_ROWS2, KAT_EXT_ROWS3, KAT_EXT_ROWS4, KAT_EXT_SHORT, KAT_EXT_WIDE, KAT_EXT_BEYOND16, KAT_EXT_STOPPED = 1, 2, 4, 8, 16, 32, 64, 128
 
 
@@ -317,6 +322,7 @@ def lib():
     L.bwahip_kat_introsort.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp]
     L.bwahip_kat_mate_insert.argtypes = [vp, C.POINTER(Opt), C.c_int, vp, vp, vp, vp, vp, C.c_int, C.c_int, vp, vp, vp]
     L.bwahip_kat_chain.argtypes = [vp, C.POINTER(Opt), C.c_int, vp, vp, vp, vp, vp, C.POINTER(i64p), i64p, vp]
+    L.bwahip_kat_dedup.argtypes = [vp, C.POINTER(Opt), C.c_int, vp, vp, vp, vp, vp, C.c_int, C.c_int, vp, vp, vp, C.POINTER(C.c_int32)]
     L.bwahip_kat_mark.argtypes = [vp, C.POINTER(Opt), C.c_int64, C.c_int, vp, vp, C.c_int, vp, C.c_int, C.POINTER(i64p), i64p]
     L.bwahip_kat_occ4.argtypes = [vp, C.c_int, vp, vp]
     L.bwahip_index_footprint.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_uint64)]
@@ -911,6 +917,28 @@ class Context:
         words = np.ctypeslib.as_array(out, shape=(m.value,)).copy() if m.value else np.zeros(0, dtype=np.int64)
         C.CDLL(None).free(out)
         return parse_records(words)
+
+    def kat_dedup(self, codes, off, reg_off, regs, opt=None, heavy=None, form=KAT_DEDUP_PRODUCT, diag=True):
+        """bwahip_kat_dedup: mem_sort_dedup_patch and the is_alt marking through the dedup kernels on caller region lists -- reads as codes by
+        offsets, regs [m x 19] in the layout of STAGE_REGS by offsets per read (at least two per read), heavy[i]: read i enters the heavy
+        reads' list; form KAT_DEDUP_*; diag False: the product's own instantiations.  -> (per read its final regions [n x 19], diag words
+        [n_reads], number of reads handed over to the slab kernel)."""
+        opt = opt or default_opt()
+        codes = np.ascontiguousarray(codes, dtype=np.uint8)
+        off = np.ascontiguousarray(off, dtype=np.int64)
+        reg_off = np.ascontiguousarray(reg_off, dtype=np.int64)
+        regs = np.ascontiguousarray(regs, dtype=np.int64).reshape(-1, 19)
+        n = len(reg_off) - 1
+        assert n >= 0 and len(off) == n + 1 and (n == 0 or (len(regs) >= reg_off[-1] and len(codes) >= off[-1]))
+        hv = None if heavy is None else np.ascontiguousarray(heavy, dtype=np.uint8)
+        assert hv is None or len(hv) == n
+        out_n, dg = np.zeros(n + 1, dtype=np.int32), np.zeros(n + 1, dtype=np.int32)
+        out = np.zeros((len(regs) + 1, 19), dtype=np.int64)
+        handed = C.c_int32(0)
+        _check(lib().bwahip_kat_dedup(self._h, C.byref(opt), n, codes.ctypes.data, off.ctypes.data, reg_off.ctypes.data, regs.ctypes.data,
+                                      None if hv is None else hv.ctypes.data, form, 1 if diag else 0, out_n.ctypes.data, out.ctypes.data, dg.ctypes.data,
+                                      C.byref(handed)), "bwahip_kat_dedup")
+        return [out[reg_off[i]:reg_off[i] + out_n[i]] for i in range(n)], dg[:n], handed.value
 
     def run_pe_stages(self, codes, off, stages, opt=None, n_processed=0, pes0=None):
         """bwahip_run_pe_stages: reads 2i, 2i+1 are a pair; -> records (STAGE_PESTAT first, then per read TAG_READ and the stages asked for)."""

@@ -196,9 +196,15 @@ struct ExtLaunch {
 	uint8_t *big_t;                              // BWAHIP_EXT_BIG_GRID slabs of BWAHIP_EXT_BIG_T + 64 bytes
 	int lds_window;                              // largest reference window k_extend keeps in LDS (<= its compiled MAXT)
 	int ext_early_stop;                          // ksw_extend2 ends once no later row can change its results (0: off)
+	int *diag;                                   // bwahip_kat_dedup only (its own instantiations of the dedup kernels): one word per read, BWAHIP_KAT_DEDUP_* of bwahip.h; nullptr in every production launch
 };
 constexpr int BWAHIP_EXT_BIG_GRID = 128, BWAHIP_EXT_BIG_T = 1 << 16;
 int launch_extend(const ExtLaunch &a, int max_len, hipStream_t st, hipStream_t st2, hipEvent_t fork, hipEvent_t join);
+// mem_sort_dedup_patch of the reads on a.dedup_list, as launch_extend queues it behind k_extend: the heavy reads' list through k_dedup, the
+// bulk's through k_dedup_fast and what that passes on through k_dedup (use_fast false: the bulk's list straight through k_dedup).  diag: the
+// instantiations that fill a.diag.  bwahip_kat_dedup calls this; launch_extend makes the same launches (one function, launch_dedup_part).
+int launch_dedup(const ExtLaunch &a, int max_len, bool use_fast, bool diag, hipStream_t st);
+int launch_kat_dedup_slab(const ExtLaunch &a, hipStream_t st);   // bwahip_kat_dedup: k_extend_big's dedup body (window in the slab) on the reads of a.redo_list
 int launch_order(int n, const int *keys, int t0, int t1, int t2, int *perm, int *counts, hipStream_t st);   // launch order by classes of keys[r], heaviest first
 int launch_extend_spec(const ExtLaunch &a, int max_len, hipStream_t st);
 

@@ -690,7 +690,9 @@ constexpr int BIG_T = BWAHIP_EXT_BIG_T;
 // regions that mem_patch_reg would align -- in a lean kernel of its own (k_dedup_fast): the list lives in LDS, the sorts are counts of smaller keys by shuffle
 // (without ties every correct sort is the reference's), the dedup pass runs on one lane.  Anything else (a tie, a patch candidate) returns -1
 // with the global list untouched, and the read goes to k_dedup.  Returns the new length; the finished list is written back.
+// DIAG (bwahip_kat_dedup's instantiation only): a refusal names its reason -- -1 a tie in the first sort, -2 a patch candidate, -3 a tie in the second.
 constexpr int FAST_N = 8;
+template <bool DIAG = false>
 __device__ __forceinline__ int fast_dedup(const DevOpt &opt, const DevIndex &ix, DevReg *gav, int n, DevReg *s_a, DevReg *s_b, int l)
 {
 	const int64_t l_pac = ix.l_pac;
@@ -740,7 +742,7 @@ __device__ __forceinline__ int fast_dedup(const DevOpt &opt, const DevIndex &ix,
 		}
 	}
 	__threadfence_block(); __syncthreads();
-	if (__shfl(bail, 0)) return -1;
+	if (__shfl(bail, 0)) return DIAG ? -2 : -1;
 	// drop the excluded entries (order kept), then sort by (score desc, rb, qb) (ks_introsort(mem_ars)); equal keys = identical hits: the full path's
 	const bool keep = l < n && s_a[l].qe > s_a[l].qb;
 	const unsigned long long km = __ballot(keep);
@@ -760,7 +762,7 @@ __device__ __forceinline__ int fast_dedup(const DevOpt &opt, const DevIndex &ix,
 		tie2 |= su == sc && ru == rb && qu == qb && u != l;
 	}
 	(void)pos;
-	if (__ballot(keep && tie2)) return -1;
+	if (__ballot(keep && tie2)) return DIAG ? -3 : -1;
 	if (keep) { if (mine.rid >= 0 && ix.anns[mine.rid].is_alt) mine.is_alt = 1; gav[rank2] = mine; }   // (bwamem.c:1091-1095 on the way out)
 	__threadfence_block(); __syncthreads();
 	return m;
@@ -768,7 +770,8 @@ __device__ __forceinline__ int fast_dedup(const DevOpt &opt, const DevIndex &ix,
 
 // PHASE 0: both parts (k_extend_big); 1: the mem_chain2aln calls only -- a read left with more than one region is listed for k_dedup (its
 // sorts and the dedup pass want other registers and run as their own launch); 2: mem_sort_dedup_patch of a listed read.
-template <int CPL, bool BIGT, int PHASE>
+// DIAG (bwahip_kat_dedup's instantiations only): what the dedup pass did goes to a.diag[r]; the product's instantiations compile it out.
+template <int CPL, bool BIGT, int PHASE, bool DIAG = false>
 __device__ __forceinline__ void extend_read(const ExtLaunch &a, const int r, uint8_t *s_q, uint8_t *s_t, int8_t *s_mat, int *s_stk, unsigned *s_he, unsigned *s_v = nullptr, int v_cap = 0)
 {
 	const int T_CAP = BIGT ? BIG_T : (a.lds_window < MAXT ? a.lds_window : MAXT);   // lds_window: test knob, forces the hand-over onto ordinary reads
@@ -916,6 +919,7 @@ __device__ __forceinline__ void extend_read(const ExtLaunch &a, const int r, uin
 	// in every lane (identical reads of av[]), stores are done by lane 0; the rare banded global alignment is
 	// collective.  The sort permutes an index array; the list is then gathered into that order.
 	int n = n_av;
+	int dg = 0, dg_aln = 0, dg_mrg = 0;                         // (DIAG)
 	unsigned long long t_s1 = t_1, t_lp = t_1;
 	// k_dedup, lists of up to 32 regions (nearly all): the list, its spare copy, the keys and the index array live in LDS for the whole
 	// pass -- some fifteen dependent round trips per read otherwise go to global memory -- and the result is written back once
@@ -940,6 +944,7 @@ __device__ __forceinline__ void extend_read(const ExtLaunch &a, const int r, uin
 		// only when the introsort's depth limit is reached (or the test knob asks for it).  Scratch: behind the keys in the spare list.
 		if (n < a.rank_sort_min || !wave_sort_exact(RegSort{keys, 0}, n, idx, stage ? work_lds : reinterpret_cast<int*>(keys + n), s_stk, s_he, l, stage ? nullptr : s_v, stage ? 0 : v_cap)) {
 			__threadfence_block(); __syncthreads();
+			if (DIAG) dg |= BWAHIP_KAT_DEDUP_LANE1;
 			if (l == 0) { int bad = 0; rs_introsort(RegSort{keys, 0}, n, idx, s_stk, &bad); if (bad) atomicExch(a.err, 10 + bad); }
 		}
 		__threadfence_block(); __syncthreads();
@@ -1006,10 +1011,12 @@ __device__ __forceinline__ void extend_read(const ExtLaunch &a, const int r, uin
 										if (BIGT) { atomicExch(a.err, 4); atomicExch(a.err + 1, r); }
 										else a.redo_list[atomicAdd(a.redo_n, 1)] = r;
 										a.reg_n[r] = 0;
+										if (DIAG) a.diag[r] |= BWAHIP_KAT_DEDUP_HANDED;
 									}
 									return;
 								}
 							if (have) {
+								if (DIAG) ++dg_aln;
 								__syncthreads();
 								if (!have_q) { for (int t = l; t < l_query; t += 64) s_q[t] = query[t]; have_q = true; }
 								for (int t = l; t < rlen; t += 64) s_t[t] = (uint8_t)ref_base(ix, grb + t);
@@ -1051,6 +1058,7 @@ __device__ __forceinline__ void extend_read(const ExtLaunch &a, const int r, uin
 						p.w = wband;
 						q.qb = q.qe;
 						p_dirty = true;
+						if (DIAG) ++dg_mrg;
 						if (l == 0) av[j].qb = q.qb;
 						__threadfence_block(); __syncthreads();
 					}
@@ -1086,6 +1094,7 @@ __device__ __forceinline__ void extend_read(const ExtLaunch &a, const int r, uin
 		__threadfence_block(); __syncthreads();
 		if (n < a.rank_sort_min || !wave_sort_exact(RegSort{keys, 1}, n, idx, stage ? work_lds : reinterpret_cast<int*>(keys + n), s_stk, s_he, l, stage ? nullptr : s_v, stage ? 0 : v_cap)) {
 			__threadfence_block(); __syncthreads();
+			if (DIAG) dg |= BWAHIP_KAT_DEDUP_LANE2;
 			if (l == 0) { int bad = 0; rs_introsort(RegSort{keys, 1}, n, idx, s_stk, &bad); if (bad) atomicExch(a.err, 20 + bad); }
 		}
 		__threadfence_block(); __syncthreads();
@@ -1116,6 +1125,9 @@ __device__ __forceinline__ void extend_read(const ExtLaunch &a, const int r, uin
 		__threadfence_block(); __syncthreads();
 		for (int i = l; i < n * 5; i += 64) reinterpret_cast<uint4*>(gav)[i] = reinterpret_cast<const uint4*>(av)[i];
 	}
+	if (DIAG && l == 0)                                          // (k_dedup_fast's word, if it refused the read, is in place: its launch came first)
+		a.diag[r] |= (BIGT ? BWAHIP_KAT_DEDUP_SLABBED : stage ? BWAHIP_KAT_DEDUP_STAGED : BWAHIP_KAT_DEDUP_GLOBAL) | dg |
+		             (dg_aln < 2047 ? dg_aln : 2047) << BWAHIP_KAT_DEDUP_ALN_SHIFT | (dg_mrg < 2047 ? dg_mrg : 2047) << BWAHIP_KAT_DEDUP_MRG_SHIFT;
 	if (l == 0) {
 		a.reg_n[r] = n;
 		if (wk.cells) { atomicAdd(&cnt_row(a.counters)[CNT_CELLS], wk.cells); atomicAdd(&cnt_row(a.counters)[CNT_ROWS1], (unsigned long long)wk.rows1); atomicAdd(&cnt_row(a.counters)[CNT_ROWSN], (unsigned long long)wk.rowsN); }
@@ -1149,6 +1161,7 @@ __global__ __launch_bounds__(64, (CPL <= 3 ? KEXT_W3 : CPL == 4 ? 4 : 1)) void k
 
 // The bulk's lists first go through fast_dedup, one read per wavefront: a quarter of all reads has two or three regions, and the full
 // k_dedup spends some fifteen dependent round trips on each.  What fast_dedup does not take goes on to list 2 for k_dedup.
+template <bool DIAG = false>
 __global__ __launch_bounds__(64) void k_dedup_fast(ExtLaunch a)
 {
 	__shared__ __attribute__((aligned(16))) DevReg s_g[2 * FAST_N + 8];   // (4 unused records at either end: the lists are reached through generic pointers)
@@ -1158,7 +1171,8 @@ __global__ __launch_bounds__(64) void k_dedup_fast(ExtLaunch a)
 		const int r = a.dedup_list[it];
 		const int n = a.reg_n[r];
 		int m = -1;
-		if (n <= FAST_N) m = fast_dedup(a.opt, a.ix, a.regs + a.reg_base[r], n, s_g + 4, s_g + 4 + FAST_N, l);
+		if (n <= FAST_N) m = fast_dedup<DIAG>(a.opt, a.ix, a.regs + a.reg_base[r], n, s_g + 4, s_g + 4 + FAST_N, l);
+		if (DIAG && l == 0) a.diag[r] = m >= 0 ? BWAHIP_KAT_DEDUP_FAST : n > FAST_N ? 0 : -m << BWAHIP_KAT_DEDUP_WHY_SHIFT;
 		if (l == 0) {
 			if (m >= 0) a.reg_n[r] = m;
 			else a.dedup_list[(size_t)2 * a.n_reads + atomicAdd(&a.dedup_n[2], 1)] = r;
@@ -1168,7 +1182,7 @@ __global__ __launch_bounds__(64) void k_dedup_fast(ExtLaunch a)
 }
 
 // mem_sort_dedup_patch of the reads k_extend listed (more than one region), one read per wavefront
-template <int CPL>
+template <int CPL, bool DIAG = false>
 __global__ __launch_bounds__(64) void k_dedup(ExtLaunch a)
 {
 	__shared__ uint8_t s_q[MAXQ + 8];
@@ -1186,7 +1200,7 @@ __global__ __launch_bounds__(64) void k_dedup(ExtLaunch a)
 	const int li = a.subset == 1 ? 1 : a.subset == 3 ? 2 : 0;   // the heavy reads' list, the list k_dedup_fast passed on, or all of the bulk
 	const int n_list = a.dedup_n[li];
 	for (int it = (int)blockIdx.x; it < n_list; it += (int)gridDim.x) {
-		extend_read<CPL, false, 2>(a, a.dedup_list[(size_t)li * a.n_reads + n_list - 1 - it], s_q, s_t, s_mat, s_stk, s_he, s_v, 2048);   // from the end of the list: the reads k_extend finished last are the ones with the longest lists
+		extend_read<CPL, false, 2, DIAG>(a, a.dedup_list[(size_t)li * a.n_reads + n_list - 1 - it], s_q, s_t, s_mat, s_stk, s_he, s_v, 2048);   // from the end of the list: the reads k_extend finished last are the ones with the longest lists
 		__syncthreads();
 	}
 }
@@ -1205,6 +1219,24 @@ __global__ __launch_bounds__(64) void k_extend_big(ExtLaunch a)
 	const int n_redo = *a.redo_n;
 	for (int it = (int)blockIdx.x; it < n_redo; it += (int)gridDim.x) {
 		extend_read<CPL, true, 0>(a, a.redo_list[it], s_q, s_t, s_mat, s_stk, s_he);
+		__syncthreads();
+	}
+}
+
+// known-answer kernel (bwahip_kat_dedup): the dedup body of k_extend_big -- window in the slab, list in global memory whatever its length,
+// query fetched when a patch needs it -- on the region lists that are already in a.regs, for the reads of a.redo_list
+__global__ __launch_bounds__(64) void k_kat_dedup_slab(ExtLaunch a)
+{
+	__shared__ uint8_t s_q[MAXQ + 8];
+	__shared__ int8_t s_mat[32];
+	__shared__ int s_stk_g[3 * 80 + 32];
+	int *const s_stk = s_stk_g + 16;
+	__shared__ __attribute__((aligned(16))) unsigned s_he_g[WIN_MAX + 128];
+	unsigned *const s_he = s_he_g + 64;
+	uint8_t *s_t = a.big_t + (size_t)blockIdx.x * (BIG_T + 64);
+	const int n_redo = *a.redo_n;
+	for (int it = (int)blockIdx.x; it < n_redo; it += (int)gridDim.x) {
+		extend_read<11, true, 2, true>(a, a.redo_list[it], s_q, s_t, s_mat, s_stk, s_he);
 		__syncthreads();
 	}
 }
@@ -1411,19 +1443,57 @@ int launch_extend_spec(const ExtLaunch &a, int max_len, hipStream_t st)
 	return hipGetLastError() == hipSuccess ? 0 : BWAHIP_ENODEV;
 }
 
+// The dedup launches, for launch_extend_cpl and launch_dedup (bwahip_kat_dedup) alike.  heavy: the heavy reads' list (list 1) through k_dedup;
+// otherwise the bulk's (list 0) through k_dedup_fast, and what that passes on (list 2) through k_dedup -- or, with use_fast false, list 0 straight
+// through k_dedup.  DIAG: the instantiations that fill a.diag.
+template <int CPL, bool DIAG> static void launch_dedup_part(ExtLaunch a, bool heavy, bool use_fast, hipStream_t st)
+{
+	if (heavy) {
+		a.subset = 1;
+		hipLaunchKernelGGL((k_dedup<CPL, DIAG>), dim3(a.n_reads < 4096 ? a.n_reads : 4096), dim3(64), 0, st, a);
+		return;
+	}
+	const int dgrid = a.n_reads < 32768 ? a.n_reads : 32768;
+	if (use_fast) {
+		hipLaunchKernelGGL(k_dedup_fast<DIAG>, dim3(dgrid), dim3(64), 0, st, a);   // the ordinary short lists; the rest goes on to list 2
+		a.subset = 3;
+	} else a.subset = 0;
+	hipLaunchKernelGGL((k_dedup<CPL, DIAG>), dim3(dgrid), dim3(64), 0, st, a);
+}
+
 template <int CPL> static void launch_extend_cpl(ExtLaunch a, hipStream_t st, hipStream_t st2)
 {
-	const int dgrid = a.n_reads < 32768 ? a.n_reads : 32768;
 	if (a.perm && st2) {
 		a.subset = 1;                                            // the heavy reads: extension, then their lists, on the second stream
 		hipLaunchKernelGGL(k_extend<CPL>, dim3(a.n_reads < 4096 ? a.n_reads : 4096), dim3(64), 0, st2, a);
-		hipLaunchKernelGGL(k_dedup<CPL>, dim3(a.n_reads < 4096 ? a.n_reads : 4096), dim3(64), 0, st2, a);
+		launch_dedup_part<CPL, false>(a, true, true, st2);
 		a.subset = 2;
 	} else a.subset = 0;
 	hipLaunchKernelGGL(k_extend<CPL>, dim3(a.n_reads), dim3(64), 0, st, a);
-	hipLaunchKernelGGL(k_dedup_fast, dim3(dgrid), dim3(64), 0, st, a);   // the ordinary short lists; the rest goes on to list 2
-	a.subset = 3;
-	hipLaunchKernelGGL(k_dedup<CPL>, dim3(dgrid), dim3(64), 0, st, a);
+	launch_dedup_part<CPL, false>(a, false, true, st);
+}
+
+template <int CPL> static void launch_dedup_cpl(const ExtLaunch &a, bool use_fast, bool diag, hipStream_t st)
+{
+	if (diag) { launch_dedup_part<CPL, true>(a, true, use_fast, st); launch_dedup_part<CPL, true>(a, false, use_fast, st); }
+	else { launch_dedup_part<CPL, false>(a, true, use_fast, st); launch_dedup_part<CPL, false>(a, false, use_fast, st); }
+}
+int launch_dedup(const ExtLaunch &a, int max_len, bool use_fast, bool diag, hipStream_t st)
+{
+	if (a.n_reads <= 0) return 0;
+	if (diag && !a.diag) return BWAHIP_EINVAL;
+	if (max_len + 1 <= 64 * 3) launch_dedup_cpl<3>(a, use_fast, diag, st);        // CPL as launch_extend chooses it
+	else if (max_len + 1 <= 64 * 4) launch_dedup_cpl<4>(a, use_fast, diag, st);
+	else if (max_len + 1 <= 64 * 5) launch_dedup_cpl<5>(a, use_fast, diag, st);
+	else launch_dedup_cpl<11>(a, use_fast, diag, st);
+	return hipGetLastError() == hipSuccess ? 0 : BWAHIP_ENODEV;
+}
+int launch_kat_dedup_slab(const ExtLaunch &a, hipStream_t st)
+{
+	if (a.n_reads <= 0) return 0;
+	if (!a.diag || !a.big_t) return BWAHIP_EINVAL;
+	hipLaunchKernelGGL(k_kat_dedup_slab, dim3(BWAHIP_EXT_BIG_GRID), dim3(64), 0, st, a);
+	return hipGetLastError() == hipSuccess ? 0 : BWAHIP_ENODEV;
 }
 
 // st2 / fork / join: a second stream (and two events) of the context; nullptr = everything on st

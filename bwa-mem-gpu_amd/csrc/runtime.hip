@@ -676,6 +676,42 @@ static int chain_prepare(bwahip_ctx *c, const DevOpt &dopt, int n, int64_t total
 	return 0;
 }
 
+// K4 / K5's working storage, sized from the seed and region-slot counts, and their launch record: the batch attached to the context, its
+// chains in c->d_chains by c->d_seed_base (`total` seed slots), its region slots by c->d_reg_base (`total_regs` of them).  run_pipeline and
+// bwahip_kat_dedup both come through here, so that the known-answer entry launches on the product's own layout.
+static int ext_prepare(bwahip_ctx *c, const DevOpt &dopt, int n, int64_t total, int64_t total_regs, bool dump, unsigned long long *counters, int *err, ExtLaunch &el)
+{
+	int rc;
+	const size_t T = (size_t)(total ? total : 1);
+	const size_t R = (size_t)(total_regs ? total_regs : 1);
+	if ((rc = c->d_regs.ensure(R * sizeof(DevReg))) || (rc = c->d_tmp_regs.ensure(R * sizeof(DevReg))) || (rc = c->d_reg_n.ensure((size_t)n * 4)) ||
+	    (rc = c->d_srt.ensure(T * 8))) return rc;
+	if (dump && ((rc = c->d_dbg_regs.ensure(R * sizeof(DevReg))) || (rc = c->d_dbg_reg_n.ensure((size_t)n * 4)))) return rc;
+	memset(&el, 0, sizeof el);
+	el.ix = c->ix; el.opt = dopt; el.n_reads = n; el.seq = c->in->d_seq.as<uint8_t>(); el.off = c->in->d_off.as<int64_t>();
+	el.seed_base = c->d_seed_base.as<int64_t>(); el.chains = c->d_chains.as<DevChain>(); el.chain_seeds = c->d_chain_seeds.as<DevSeed>();
+	el.chain_n = c->d_chain_n.as<int>(); el.reg_base = c->d_reg_base.as<int64_t>();
+	el.regs = c->d_regs.as<DevReg>(); el.reg_n = c->d_reg_n.as<int>(); el.tmp_regs = c->d_tmp_regs.as<DevReg>(); el.srt = c->d_srt.as<int>();
+	if (dump) { el.dbg_regs = c->d_dbg_regs.as<DevReg>(); el.dbg_reg_n = c->d_dbg_reg_n.as<int>(); }
+	if ((rc = c->d_perm.ensure((size_t)(n + 8) * 4))) return rc;
+	el.kept_seeds = c->d_kept_seeds.as<int>(); el.perm = c->d_perm.as<int>() + 8; el.perm_counts = c->d_perm.as<int>();
+	el.counters = counters; el.err = err;
+	if ((rc = c->d_redo.ensure((size_t)(n + 4) * 4)) || (rc = c->d_big_t.ensure((size_t)BWAHIP_EXT_BIG_GRID * (BWAHIP_EXT_BIG_T + 64)))) return rc;
+	HIP_TRY(hipMemsetAsync(c->d_redo.p, 0, 16, c->stream));
+	if ((rc = c->d_dedup.ensure(((size_t)3 * n + 4) * 4))) return rc;
+	HIP_TRY(hipMemsetAsync(c->d_dedup.p, 0, 16, c->stream));
+	el.dedup_n = c->d_dedup.as<int>(); el.dedup_list = c->d_dedup.as<int>() + 4;
+	el.redo_n = c->d_redo.as<int>(); el.redo_list = c->d_redo.as<int>() + 4; el.big_t = c->d_big_t.as<uint8_t>(); el.lds_window = c->knobs.ext_lds_window; el.ext_early_stop = c->knobs.ext_early_stop;
+	el.rank_sort_min = c->knobs.rank_sort_min;
+	const int spec_min = c->knobs.spec_min_chains;           // 0 = no ahead-of-time extension
+	if (spec_min > 0) {
+		if ((rc = c->d_spec_regs.ensure(T * sizeof(DevReg))) || (rc = c->d_spec_items.ensure(T * 8 + 16))) return rc;
+		el.spec_regs = c->d_spec_regs.as<DevReg>(); el.spec_n = c->d_spec_items.as<int>(); el.spec_items = (int2*)(c->d_spec_items.as<int>() + 4);
+		el.spec_min_chains = spec_min;
+	}
+	return 0;
+}
+
 int run_pipeline(bwahip_ctx *c, const bwahip_opt_t *opt, bool timed, bool dump)
 {
 	const bool verbose = c->knobs.verbose != 0;
@@ -752,7 +788,6 @@ int run_pipeline(bwahip_ctx *c, const bwahip_opt_t *opt, bool timed, bool dump)
 		STAGE_LOG("k_seeds");
 		if (timed) HIP_TRY(hipEventRecord(c->ev[4], c->stream));
 		// ---- K3: chaining + chain filter
-		const size_t T = (size_t)(total ? total : 1);
 		ChainLaunch cl;
 		if ((rc = chain_prepare(c, dopt, n, total, c->in->d_off.as<int64_t>(), cap, dump, counters, cl))) return rc;
 		if (timed) HIP_TRY(hipEventRecord(c->ev[5], c->stream));
@@ -779,33 +814,8 @@ int run_pipeline(bwahip_ctx *c, const bwahip_opt_t *opt, bool timed, bool dump)
 		HIP_TRY(hipStreamSynchronize(c->stream));
 		c->total_regs = total_regs;
 		// ---- K4/K5: extension + sort/dedup/patch
-		const size_t R = (size_t)(total_regs ? total_regs : 1);
-		if ((rc = c->d_regs.ensure(R * sizeof(DevReg))) || (rc = c->d_tmp_regs.ensure(R * sizeof(DevReg))) || (rc = c->d_reg_n.ensure((size_t)n * 4)) ||
-		    (rc = c->d_srt.ensure(T * 8))) return rc;
-		if (dump && ((rc = c->d_dbg_regs.ensure(R * sizeof(DevReg))) || (rc = c->d_dbg_reg_n.ensure((size_t)n * 4)))) return rc;
 		ExtLaunch el;
-		memset(&el, 0, sizeof el);
-		el.ix = c->ix; el.opt = dopt; el.n_reads = n; el.seq = c->in->d_seq.as<uint8_t>(); el.off = c->in->d_off.as<int64_t>();
-		el.seed_base = c->d_seed_base.as<int64_t>(); el.chains = c->d_chains.as<DevChain>(); el.chain_seeds = c->d_chain_seeds.as<DevSeed>();
-		el.chain_n = c->d_chain_n.as<int>(); el.reg_base = c->d_reg_base.as<int64_t>();
-		el.regs = c->d_regs.as<DevReg>(); el.reg_n = c->d_reg_n.as<int>(); el.tmp_regs = c->d_tmp_regs.as<DevReg>(); el.srt = c->d_srt.as<int>();
-		if (dump) { el.dbg_regs = c->d_dbg_regs.as<DevReg>(); el.dbg_reg_n = c->d_dbg_reg_n.as<int>(); }
-		if ((rc = c->d_perm.ensure((size_t)(n + 8) * 4))) return rc;
-		el.kept_seeds = c->d_kept_seeds.as<int>(); el.perm = c->d_perm.as<int>() + 8; el.perm_counts = c->d_perm.as<int>();
-		el.counters = counters; el.err = err;
-		if ((rc = c->d_redo.ensure((size_t)(n + 4) * 4)) || (rc = c->d_big_t.ensure((size_t)BWAHIP_EXT_BIG_GRID * (BWAHIP_EXT_BIG_T + 64)))) return rc;
-		HIP_TRY(hipMemsetAsync(c->d_redo.p, 0, 16, c->stream));
-		if ((rc = c->d_dedup.ensure(((size_t)3 * n + 4) * 4))) return rc;
-		HIP_TRY(hipMemsetAsync(c->d_dedup.p, 0, 16, c->stream));
-		el.dedup_n = c->d_dedup.as<int>(); el.dedup_list = c->d_dedup.as<int>() + 4;
-		el.redo_n = c->d_redo.as<int>(); el.redo_list = c->d_redo.as<int>() + 4; el.big_t = c->d_big_t.as<uint8_t>(); el.lds_window = c->knobs.ext_lds_window; el.ext_early_stop = c->knobs.ext_early_stop;
-		el.rank_sort_min = c->knobs.rank_sort_min;
-		const int spec_min = c->knobs.spec_min_chains;           // 0 = no ahead-of-time extension
-		if (spec_min > 0) {
-			if ((rc = c->d_spec_regs.ensure(T * sizeof(DevReg))) || (rc = c->d_spec_items.ensure(T * 8 + 16))) return rc;
-			el.spec_regs = c->d_spec_regs.as<DevReg>(); el.spec_n = c->d_spec_items.as<int>(); el.spec_items = (int2*)(c->d_spec_items.as<int>() + 4);
-			el.spec_min_chains = spec_min;
-		}
+		if ((rc = ext_prepare(c, dopt, n, total, total_regs, dump, counters, err, el))) return rc;
 		if (timed) HIP_TRY(hipEventRecord(c->ev[11], c->stream));
 		if ((rc = launch_extend_spec(el, c->in->max_len, c->stream))) return rc;
 		STAGE_LOG("k_extend_spec");
@@ -850,6 +860,117 @@ int bwahip_batch_run(bwahip_ctx *c, const bwahip_opt_t *opt, float *kernel_ms, i
 	int rc = run_pipeline(c, opt, true, false);
 	if (!rc && kernel_ms) for (int i = 0; i < n_ms && i < bwahip_n_kernels(); ++i) kernel_ms[i] = c->last_ms[i];
 	return rc;
+}
+
+// mem_sort_dedup_patch through the dedup kernels on caller region lists; see bwahip.h.  The batch is uploaded as any batch; the buffers and the
+// launch record are run_pipeline's (ext_prepare), with as many seed slots as region slots -- the sort's index array lives in the seed-slot
+// scratch and needs n ints per read; the launches are launch_extend's (launch_dedup).  Only the lists, reg_n and the dedup lists, which
+// k_extend would have written, come from the caller.
+int bwahip_kat_dedup(bwahip_ctx *c, const bwahip_opt_t *opt, int n_reads, const uint8_t *seq, const int64_t *off, const int64_t *reg_off,
+                     const int64_t *reg_words, const uint8_t *heavy, int form, int with_diag, int32_t *out_n, int64_t *out_words, int32_t *diag, int32_t *n_handed)
+{
+	if (!c || !opt || n_reads < 0 || form < BWAHIP_KAT_DEDUP_PRODUCT || form > BWAHIP_KAT_DEDUP_SLAB) return BWAHIP_EINVAL;
+	if (n_handed) *n_handed = 0;
+	if (n_reads == 0) return 0;
+	const int n = n_reads;
+	if (!seq || !off || !reg_off || !reg_words || !out_n || !out_words || !diag || !n_handed || off[0] != 0 || reg_off[0] != 0) return BWAHIP_EINVAL;
+	const bwahip_bns_t &bns = c->host.bns;
+	for (int i = 0; i < n; ++i) {
+		const int64_t len = off[i + 1] - off[i], m = reg_off[i + 1] - reg_off[i];
+		if (len < 0 || m < 2 || m > (1 << 24)) return BWAHIP_EINVAL;
+		for (int64_t k = reg_off[i]; k < reg_off[i + 1]; ++k) {
+			const int64_t *w = reg_words + 19 * k;
+			if (w[3] < w[2] || w[1] < w[0] || w[2] < 0 || w[3] > len || w[4] < 0 || w[4] >= bns.n_seqs) return BWAHIP_EINVAL;
+			// [rb, re) inside its contig on the forward strand, or inside the contig's mirror image on the reverse strand
+			const int64_t c0 = bns.anns[w[4]].offset, c1 = c0 + bns.anns[w[4]].len;
+			const bool fwd = w[0] >= c0 && w[1] <= c1, rev = w[0] >= 2 * bns.l_pac - c1 && w[1] <= 2 * bns.l_pac - c0;
+			if (!fwd && !rev) return BWAHIP_EINVAL;
+		}
+	}
+	const int64_t total = reg_off[n];
+	if (total > (1 << 26)) return BWAHIP_EINVAL;
+	int rc;
+	if ((rc = bwahip_batch_upload(c, n, seq, off))) return rc;
+	if (c->in->max_len >= (1 << 14)) return BWAHIP_EINVAL;
+	HIP_TRY(hipSetDevice(c->device));
+	std::vector<DevReg> regs((size_t)total);
+	for (int64_t k = 0; k < total; ++k) {
+		const int64_t *w = reg_words + 19 * k;
+		DevReg r; memset(&r, 0, sizeof r);
+		r.rb = w[0]; r.re = w[1]; r.qb = (int)w[2]; r.qe = (int)w[3]; r.rid = (int)w[4]; r.score = (int)w[5]; r.truesc = (int)w[6]; r.sub = (int)w[7]; r.csub = (int)w[9];
+		r.sub_n = (int)w[10]; r.w = (int)w[11]; r.seedcov = (int)w[12]; r.seedlen0 = (int)w[15]; r.n_comp = (int)w[16]; r.is_alt = (int)w[17];
+		const uint32_t u = (uint32_t)w[18]; memcpy(&r.frac_rep, &u, 4);
+		regs[(size_t)k] = r;
+	}
+	// what k_extend leaves behind: reg_n, and every read on the bulk's list or the heavy reads' (three lists of n behind four counts)
+	std::vector<int> regn(n), lists((size_t)3 * n + 4, 0), redo((size_t)n + 4, 0);
+	for (int i = 0; i < n; ++i) {
+		regn[i] = (int)(reg_off[i + 1] - reg_off[i]);
+		const int li = heavy && heavy[i] ? 1 : 0;
+		lists[4 + (size_t)li * n + lists[li]++] = i;
+	}
+	DevOpt dopt = make_dev_opt(opt);
+	unsigned long long *counters = c->d_misc.as<unsigned long long>();
+	unsigned int *queue = (unsigned int*)(counters + (size_t)CNT_SLOTS * CNT_N);
+	int *err = (int*)(queue + 4);
+	DevBuf d_diag;
+	ExtLaunch el;
+	std::vector<DevReg> back((size_t)total);
+	int h_err[2] = { 0, 0 };
+	c->total_seeds = total; c->total_regs = total;
+	auto fetch = [&](void *dst, const void *src, size_t bytes) { return hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream) == hipSuccess ? 0 : BWAHIP_ENODEV; };
+	auto queue1 = [&]() -> int {                                 // uploads, launches, copies back: the stream is awaited whatever this returns
+		int r2;
+		if (hipMemsetAsync(c->d_misc.p, 0, BWAHIP_MISC_BYTES, c->stream) != hipSuccess) return BWAHIP_ENODEV;
+		if ((r2 = dev_upload(c->d_seed_base, reg_off, (size_t)(n + 1) * 8, c->stream)) || (r2 = dev_upload(c->d_reg_base, reg_off, (size_t)(n + 1) * 8, c->stream)) ||
+		    (r2 = c->d_chain_n.ensure((size_t)n * 4)) || (r2 = d_diag.ensure((size_t)n * 4)) || (r2 = ext_prepare(c, dopt, n, total, total, false, counters, err, el))) return r2;
+		if (hipMemsetAsync(c->d_chain_n.p, 0, (size_t)n * 4, c->stream) != hipSuccess || hipMemsetAsync(d_diag.p, 0, (size_t)n * 4, c->stream) != hipSuccess) return BWAHIP_ENODEV;
+		if ((r2 = dev_upload(c->d_regs, regs.data(), regs.size() * sizeof(DevReg), c->stream)) || (r2 = dev_upload(c->d_reg_n, regn.data(), (size_t)n * 4, c->stream))) return r2;
+		el.perm = nullptr; el.perm_counts = nullptr;              // (no launch order: k_extend does not run)
+		el.diag = d_diag.as<int>();
+		if (form == BWAHIP_KAT_DEDUP_SLAB) {
+			redo[0] = n;
+			for (int i = 0; i < n; ++i) redo[4 + i] = i;
+			if ((r2 = dev_upload(c->d_redo, redo.data(), redo.size() * 4, c->stream)) || (r2 = launch_kat_dedup_slab(el, c->stream))) return r2;
+		} else {
+			if ((r2 = dev_upload(c->d_dedup, lists.data(), lists.size() * 4, c->stream)) ||
+			    (r2 = launch_dedup(el, c->in->max_len, form == BWAHIP_KAT_DEDUP_PRODUCT, with_diag != 0, c->stream))) return r2;
+		}
+		return fetch(h_err, err, 8) || fetch(redo.data(), c->d_redo.p, redo.size() * 4);
+	};
+	rc = queue1();
+	if (hipStreamSynchronize(c->stream) != hipSuccess && !rc) rc = BWAHIP_ENODEV;
+	if (rc) return rc;
+	if (h_err[0]) { fprintf(stderr, "[bwahip] bwahip_kat_dedup: the dedup kernels reported code %d (read %d)\n", h_err[0], h_err[1]); return h_err[0] == 4 ? BWAHIP_ECAPACITY : BWAHIP_EINTERNAL; }
+	const int handed = form == BWAHIP_KAT_DEDUP_SLAB ? 0 : redo[0];
+	if (handed < 0 || handed > n) return BWAHIP_EINTERNAL;
+	auto queue2 = [&]() -> int {                                 // the handed-over reads: their original lists again, then the slab kernel on the redo list as it stands
+		int r2;
+		for (int k = 0; k < handed; ++k) {
+			const int i = redo[4 + k];
+			if (i < 0 || i >= n) return BWAHIP_EINTERNAL;
+			if (hipMemcpyAsync(c->d_regs.as<DevReg>() + reg_off[i], regs.data() + reg_off[i], (size_t)regn[i] * sizeof(DevReg), hipMemcpyHostToDevice, c->stream) != hipSuccess ||
+			    hipMemcpyAsync(c->d_reg_n.as<int>() + i, &regn[i], 4, hipMemcpyHostToDevice, c->stream) != hipSuccess) return BWAHIP_ENODEV;
+		}
+		if (handed && (r2 = launch_kat_dedup_slab(el, c->stream))) return r2;
+		return fetch(h_err, err, 8) || (total && fetch(back.data(), c->d_regs.p, (size_t)total * sizeof(DevReg))) || fetch(out_n, c->d_reg_n.p, (size_t)n * 4) ||
+		       fetch(diag, d_diag.p, (size_t)n * 4);
+	};
+	rc = queue2();
+	if (hipStreamSynchronize(c->stream) != hipSuccess && !rc) rc = BWAHIP_ENODEV;
+	if (rc) return rc;
+	if (h_err[0]) { fprintf(stderr, "[bwahip] bwahip_kat_dedup: the slab kernel reported code %d (read %d)\n", h_err[0], h_err[1]); return h_err[0] == 4 ? BWAHIP_ECAPACITY : BWAHIP_EINTERNAL; }
+	for (int k = 0; k < handed; ++k) diag[redo[4 + k]] |= BWAHIP_KAT_DEDUP_HANDED;   // (the product's instantiations do not write it)
+	memset(out_words, 0, (size_t)total * 19 * 8);
+	std::vector<int64_t> v;
+	for (int i = 0; i < n; ++i) {
+		if (out_n[i] < 0 || out_n[i] > regn[i]) return BWAHIP_EINTERNAL;
+		v.clear();
+		stage_put_regs(v, out_n[i], &back[(size_t)reg_off[i]]);
+		if (out_n[i]) memcpy(out_words + 19 * reg_off[i], v.data() + 1, (size_t)out_n[i] * 19 * 8);
+	}
+	*n_handed = handed;
+	return 0;
 }
 
 // The text the SAM stage prints for the attached batch, already in HBM: qualities (read r at qual_dev + qual_off_dev[r], < 0: none),

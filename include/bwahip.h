@@ -995,6 +995,43 @@ int bwahip_kat_chain(bwahip_ctx *ctx, const bwahip_opt_t *opt, int n_reads, cons
 int bwahip_kat_mark(bwahip_ctx *ctx, const bwahip_opt_t *opt, int64_t n_processed, int n_reads, const int64_t *reg_off, const int64_t *reg_words,
                     int plan, const int32_t *pairs, int n_pairs, int64_t **out, int64_t *out_len);
 
+/* mem_sort_dedup_patch (bwamem.c:444-496, with mem_patch_reg bwamem.c:413) and the is_alt marking of bwamem.c:1091-1095 through the
+ * dedup kernels of csrc/k_extend.hip, on caller region lists.  Read i has the bases seq[off[i] .. off[i + 1]) (codes 0..4; mem_patch_reg
+ * aligns the query) and the regions reg_words[19 * reg_off[i] .. 19 * reg_off[i + 1]), 19 words per region in the layout of
+ * BWAHIP_STAGE_REGS (alt_sc, secondary, secondary_all are not carried: they come back 0); heavy (may be NULL): heavy[i] != 0 puts read i
+ * on the heavy reads' list instead of the bulk's.  The lists are laid into the extension stage's own buffers as k_extend leaves them --
+ * the sizing and the launch record are the ones of the hot path (one function for both), slots from an exclusive scan with exactly n
+ * slots per read, reg_n and the dedup lists filled -- and the launches are those that follow k_extend (one function for both); the
+ * kernel for the longest read, ext_lds_window and rank_sort_min are chosen as in the product.
+ * form BWAHIP_KAT_DEDUP_PRODUCT: heavy list through k_dedup, bulk through k_dedup_fast, what that refuses through k_dedup;
+ * BWAHIP_KAT_DEDUP_FULL: both lists straight through k_dedup; BWAHIP_KAT_DEDUP_SLAB: every read through a known-answer kernel that runs
+ * k_extend_big's dedup body (window in the global-memory slab, list in global memory whatever its length, query fetched on demand).
+ * with_diag != 0: the instantiations of the kernels that also fill diag (the product's compile the diagnostics out); 0: the product's own
+ * instantiations: diag comes back 0 but for the reads handed over, which the slab kernel -- it always fills diag -- describes.
+ * A read whose patch window exceeds the LDS window is handed over by k_dedup, which has permuted (longer than 32 regions) its list in
+ * place by then: the entry uploads the ORIGINAL list of every such read again, runs those reads through the slab kernel and counts them in
+ * *n_handed.  This differs from the product, where k_extend_big rebuilds such a read's list from its chains before the same dedup body.
+ * out_n[i]: the final length; out_words: the final regions of read i at 19 * reg_off[i]; diag[i]: the BWAHIP_KAT_DEDUP_* word below.
+ * BWAHIP_EINVAL: offsets that do not start at 0 or descend, a list of fewer than 2 regions (k_extend finishes those itself), qe < qb,
+ * re < rb, qb < 0, qe beyond the read, a contig that does not exist, a region that leaves its contig (or, on the reverse strand, the
+ * contig's mirror image) and so any region across l_pac.  n_reads == 0 launches nothing. */
+#define BWAHIP_KAT_DEDUP_PRODUCT 0
+#define BWAHIP_KAT_DEDUP_FULL    1
+#define BWAHIP_KAT_DEDUP_SLAB    2
+/* diag word: who finished the read (one of the first four bits) */
+#define BWAHIP_KAT_DEDUP_FAST    0x1        /* k_dedup_fast */
+#define BWAHIP_KAT_DEDUP_STAGED  0x2        /* k_dedup, list in LDS (at most 32 regions) */
+#define BWAHIP_KAT_DEDUP_GLOBAL  0x4        /* k_dedup, list in global memory */
+#define BWAHIP_KAT_DEDUP_SLABBED 0x8        /* the slab kernel */
+#define BWAHIP_KAT_DEDUP_HANDED  0x10       /* k_dedup handed the read over (patch window beyond the LDS window) */
+#define BWAHIP_KAT_DEDUP_LANE1   0x20       /* the sort by re ran as the one-lane introsort (else the wavefront's sort) */
+#define BWAHIP_KAT_DEDUP_LANE2   0x40       /* the same for the sort by (score, rb, qb) */
+#define BWAHIP_KAT_DEDUP_WHY_SHIFT 7        /* 2 bits: why k_dedup_fast refused a list of at most 8 -- 1 tie in the first sort, 2 patch candidate, 3 tie in the second */
+#define BWAHIP_KAT_DEDUP_ALN_SHIFT 9        /* 11 bits: patch alignments run by whoever finished the read (held at 2047) */
+#define BWAHIP_KAT_DEDUP_MRG_SHIFT 20       /* 11 bits: of these, merged */
+int bwahip_kat_dedup(bwahip_ctx *ctx, const bwahip_opt_t *opt, int n_reads, const uint8_t *seq, const int64_t *off, const int64_t *reg_off,
+                     const int64_t *reg_words, const uint8_t *heavy, int form, int with_diag, int32_t *out_n, int64_t *out_words, int32_t *diag, int32_t *n_handed);
+
 /* The stable LSD radix sort of the coordinate-sorted BAM output (csrc/k_bamsort.hip) on caller keys: exactly the product's passes for
  * keys of key_bits (1..64) significant bits -- 8 bits per pass, passes in which all keys agree skipped.  idx_out[i] = input position of
  * the i-th key in sorted order, equal keys in input order; *tile_out (may be NULL): items one workgroup ranks per pass.  n <= 1 launches

@@ -4,6 +4,7 @@
  *   bwa_oracle stages <prefix> <reads.fq> <out.bin>                          per-read stage dump
  *   bwa_oracle stages [options, -I] <prefix> <r1.fq> <r2.fq> <out.bin>       paired-end stage dump (one batch)
  *   bwa_oracle katchain [options] <prefix> <cases.bin> <out.bin>             chains of caller-supplied seed lists
+ *   bwa_oracle katdedup [options] <prefix> <cases.bin> <out.bin>             mem_sort_dedup_patch and the is_alt marking of caller-supplied region lists
  *   bwa_oracle katmark [options] <prefix> <cases.bin> <out.bin>              primary marking, selection and mapQ of caller-supplied region lists
  * Batching follows bseq_read (bwa.c:191): reads are taken until the batch holds
  * >= chunk bases and an even number of reads.
@@ -23,6 +24,7 @@ static double now_s(void) { struct timeval tv; gettimeofday(&tv, 0); return tv.t
 #define OPT_LOG(x) log(x)
 #include "opt_parse.h"
 #include "kat_mark_io.h"
+#include "kat_dedup_io.h"
 
 /* ---- minimal FASTA/FASTQ reader with kseq.h's field semantics ---- */
 typedef struct { gzFile fp; char *line; size_t m; int peeked; } fq_t;
@@ -305,6 +307,44 @@ static int main_katmark(int argc, char **argv)
 	return rc ? 1 : 0;
 }
 
+/* katdedup [options] <prefix> <cases.bin> <out.bin>: ora_kat_dedup on caller region lists over the index's reference (kat_dedup_io.h has
+ * both file formats). */
+static int main_katdedup(int argc, char **argv)
+{
+	ora_opt_t opt;
+	ora_index_t *idx;
+	optparse_t op;
+	kd_file_t k;
+	FILE *in, *out;
+	const int64_t *regs;
+	uint8_t *seq;
+	int64_t i, *rec = 0;
+	int c, n, l, m, rc;
+	ora_opt_init(&opt);
+	optparse_init(&op, &opt);
+	while ((c = getopt(argc, argv, OPT_GETOPT_STRING)) >= 0) if (optparse_one(&op, c, optarg)) return 1;
+	if (optparse_finish(&op) || optind + 3 > argc) return 1;
+	idx = ora_index_load(argv[optind]);
+	if (!idx) return 1;
+	if (op.ignore_alt) for (c = 0; c < idx->ref->n_seqs; ++c) idx->ref->anns[c].is_alt = 0;
+	in = fopen(argv[optind + 1], "rb"); out = fopen(argv[optind + 2], "wb");
+	if (!in || !out || kd_read_opt(in, &opt, &k)) { fprintf(stderr, "[bwa_oracle] katdedup: cannot open the files, or no option record\n"); return 1; }
+	while ((rc = kd_next_read(in, &k, &i, &l, &seq, &n, &regs)) > 0) {
+		int64_t hdr[2];
+		rec = (int64_t*)realloc(rec, (1 + KD_STAT_WORDS + (size_t)KD_REG_WORDS * n) * 8);
+		m = ora_kat_dedup(&opt, idx->ref, l, seq, n, regs, rec + 1 + KD_STAT_WORDS, rec + 1);
+		rec[0] = m;
+		hdr[0] = i; hdr[1] = m;
+		rec_write(out, TAG_READ, 2, hdr);
+		rec_write(out, KD_TAG_OUT, 1 + KD_STAT_WORDS + (int64_t)KD_REG_WORDS * m, rec);
+	}
+	free(rec); free(k.buf); free(k.seq);
+	fclose(in); fclose(out);
+	ora_index_destroy(idx);
+	if (rc) fprintf(stderr, "[bwa_oracle] katdedup: malformed case file\n");
+	return rc ? 1 : 0;
+}
+
 static int main_mem(int argc, char **argv)
 {
 	ora_opt_t opt;
@@ -352,6 +392,7 @@ int main(int argc, char **argv)
 	if (argc >= 2 && strcmp(argv[1], "stages") == 0) return main_stages(argc - 1, argv + 1);
 	if (argc >= 2 && strcmp(argv[1], "katchain") == 0) return main_katchain(argc - 1, argv + 1);
 	if (argc >= 2 && strcmp(argv[1], "katmark") == 0) return main_katmark(argc - 1, argv + 1);
-	fprintf(stderr, "usage: bwa_oracle <mem|stages|katchain|katmark> ...\n");
+	if (argc >= 2 && strcmp(argv[1], "katdedup") == 0) return main_katdedup(argc - 1, argv + 1);
+	fprintf(stderr, "usage: bwa_oracle <mem|stages|katchain|katmark|katdedup> ...\n");
 	return 1;
 }

@@ -57,6 +57,13 @@ void ora_chain2aln(const ora_opt_t *opt, const ora_ref_t *r, int l_query, const 
 int ora_sort_dedup_patch(const ora_opt_t *opt, const ora_ref_t *r, uint8_t *query, int n, ora_reg_t *a);                          /* bwamem.c:444 */
 uint32_t *ora_gen_cigar2(const int8_t mat[25], int o_del, int e_del, int o_ins, int e_ins, int w_, int64_t l_pac, const uint8_t *pac,
                          int l_query, uint8_t *query, int64_t rb, int64_t re, int *score, int *n_cigar, int *NM);                 /* bwa.c:261 */
+/* test helper: ora_sort_dedup_patch and the is_alt marking on a caller's region list; stat: what the function did -- regions excluded as p /
+ * as q, patch alignments run, merged, failed on the score ratio, regions left for the second sort, identical hits dropped, ORA_DF_* flags
+ * (an introsort reached its depth limit, the first sort met equal keys), ORA_DW_* mask of the reasons mem_patch_reg gave for a refusal */
+enum { ORA_DS_EXCL_P, ORA_DS_EXCL_Q, ORA_DS_ALIGN, ORA_DS_MERGE, ORA_DS_RATIO, ORA_DS_KEPT, ORA_DS_IDENT, ORA_DS_FLAGS, ORA_DS_WHY, ORA_DEDUP_STAT_N };
+enum { ORA_DF_COMB1 = 1, ORA_DF_COMB2 = 2, ORA_DF_TIE1 = 4 };
+enum { ORA_DW_STRAND = 1, ORA_DW_QB = 2, ORA_DW_QE = 4, ORA_DW_RE = 8, ORA_DW_GAP_W = 16, ORA_DW_GAP_R = 32, ORA_DW_OVL_W = 64, ORA_DW_OVL_R = 128, ORA_DW_RATIO = 256 };
+int ora_kat_dedup(const ora_opt_t *opt, const ora_ref_t *r, int l_query, const uint8_t *query, int n, const int64_t *regs19, int64_t *out19, int64_t *stat);
 ora_reg_v ora_align1_core(const ora_opt_t *opt, const ora_index_t *idx, int l_seq, char *seq, ora_aux_t *aux);                    /* bwamem.c:1061 */
 
 /* ora_final.c */

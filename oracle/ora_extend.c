@@ -265,28 +265,37 @@ ORA_SORT_DEFINE(reg_end, ora_reg_t, REG_END_LT)
 #define REG_SC_LT(a, b) ((a).score > (b).score || ((a).score == (b).score && ((a).rb < (b).rb || ((a).rb == (b).rb && (a).qb < (b).qb))))
 ORA_SORT_DEFINE(reg_sc, ora_reg_t, REG_SC_LT)
 
+/* While ora_dedup_stat points at ORA_DEDUP_STAT_N words (ora_kat_dedup sets it), ora_sort_dedup_patch counts into them what it did;
+ * NULL -- always, outside that helper -- nothing is counted. */
+static __thread int64_t *ora_dedup_stat = 0;
+#define DSTAT(i, v) do { if (ora_dedup_stat) ora_dedup_stat[i] v; } while (0)
+
 static int patch_reg(const ora_opt_t *opt, const ora_ref_t *ref, uint8_t *query, const ora_reg_t *a, const ora_reg_t *b, int *w_)   /* bwamem.c:413 */
 {
 	int w, score, q_s, r_s;
 	double r;
 	if (ref == 0 || query == 0) return 0;
 	assert(a->rid == b->rid && a->rb <= b->rb);
-	if (a->rb < ref->l_pac && b->rb >= ref->l_pac) return 0;
-	if (a->qb >= b->qb || a->qe >= b->qe || a->re >= b->re) return 0;
+	if (a->rb < ref->l_pac && b->rb >= ref->l_pac) { DSTAT(ORA_DS_WHY, |= ORA_DW_STRAND); return 0; }
+	if (a->qb >= b->qb || a->qe >= b->qe || a->re >= b->re) {
+		DSTAT(ORA_DS_WHY, |= a->qb >= b->qb ? ORA_DW_QB : a->qe >= b->qe ? ORA_DW_QE : ORA_DW_RE);
+		return 0;
+	}
 	w = (int)((a->re - b->rb) - (a->qe - b->qb));
 	w = w > 0 ? w : -w;
 	r = (double)(a->re - b->rb) / (b->re - a->rb) - (double)(a->qe - b->qb) / (b->qe - a->qb);
 	r = r > 0. ? r : -r;
 	if (a->re < b->rb || a->qe < b->qb) {
-		if (w > opt->w << 1 || r >= 0.05f) return 0;             /* PATCH_MAX_R_BW */
-	} else if (w > opt->w << 2 || r >= 0.05f * 2) return 0;
+		if (w > opt->w << 1 || r >= 0.05f) { DSTAT(ORA_DS_WHY, |= w > opt->w << 1 ? ORA_DW_GAP_W : ORA_DW_GAP_R); return 0; }   /* PATCH_MAX_R_BW */
+	} else if (w > opt->w << 2 || r >= 0.05f * 2) { DSTAT(ORA_DS_WHY, |= w > opt->w << 2 ? ORA_DW_OVL_W : ORA_DW_OVL_R); return 0; }
 	w += a->w + b->w;
 	w = w < opt->w << 2 ? w : opt->w << 2;
+	DSTAT(ORA_DS_ALIGN, += 1);
 	ora_gen_cigar2(opt->mat, opt->o_del, opt->e_del, opt->o_ins, opt->e_ins, w, ref->l_pac, ref->pac,
 	               b->qe - a->qb, query + a->qb, a->rb, b->re, &score, 0, 0);
 	q_s = (int)((double)(b->qe - a->qb) / ((b->qe - b->qb) + (a->qe - a->qb)) * (b->score + a->score) + .499);
 	r_s = (int)((double)(b->re - a->rb) / ((b->re - b->rb) + (a->re - a->rb)) * (b->score + a->score) + .499);
-	if ((double)score / (q_s > r_s ? q_s : r_s) < 0.90f) return 0;   /* PATCH_MIN_SC_RATIO */
+	if ((double)score / (q_s > r_s ? q_s : r_s) < 0.90f) { DSTAT(ORA_DS_WHY, |= ORA_DW_RATIO); DSTAT(ORA_DS_RATIO, += 1); return 0; }   /* PATCH_MIN_SC_RATIO */
 	*w_ = w;
 	return score;
 }
@@ -295,7 +304,12 @@ int ora_sort_dedup_patch(const ora_opt_t *opt, const ora_ref_t *ref, uint8_t *qu
 {
 	int m, i, j;
 	if (n <= 1) return n;
+	m = ora_sort_comb_calls;
 	ora_isort_reg_end(n, a);
+	if (ora_dedup_stat) {
+		if (ora_sort_comb_calls != m) ora_dedup_stat[ORA_DS_FLAGS] |= ORA_DF_COMB1;
+		for (i = 1; i < n; ++i) if (a[i].re == a[i-1].re) ora_dedup_stat[ORA_DS_FLAGS] |= ORA_DF_TIE1;
+	}
 	for (i = 0; i < n; ++i) a[i].n_comp = 1;
 	for (i = 1; i < n; ++i) {
 		ora_reg_t *p = &a[i];
@@ -310,9 +324,10 @@ int ora_sort_dedup_patch(const ora_opt_t *opt, const ora_ref_t *ref, uint8_t *qu
 			mr = q->re - q->rb < p->re - p->rb ? q->re - q->rb : p->re - p->rb;
 			mq = q->qe - q->qb < p->qe - p->qb ? q->qe - q->qb : p->qe - p->qb;
 			if (orr > opt->mask_level_redun * mr && oq > opt->mask_level_redun * mq) {
-				if (p->score < q->score) { p->qe = p->qb; break; }
-				else q->qe = q->qb;
+				if (p->score < q->score) { p->qe = p->qb; DSTAT(ORA_DS_EXCL_P, += 1); break; }
+				else { q->qe = q->qb; DSTAT(ORA_DS_EXCL_Q, += 1); }
 			} else if (q->rb < p->rb && (score = patch_reg(opt, ref, query, q, p, &w)) > 0) {
+				DSTAT(ORA_DS_MERGE, += 1);
 				p->n_comp += q->n_comp + 1;
 				p->seedcov = p->seedcov > q->seedcov ? p->seedcov : q->seedcov;
 				p->sub = p->sub > q->sub ? p->sub : q->sub;
@@ -327,9 +342,12 @@ int ora_sort_dedup_patch(const ora_opt_t *opt, const ora_ref_t *ref, uint8_t *qu
 	for (i = 0, m = 0; i < n; ++i)
 		if (a[i].qe > a[i].qb) { if (m != i) a[m++] = a[i]; else ++m; }
 	n = m;
+	j = ora_sort_comb_calls;
 	ora_isort_reg_sc(n, a);
+	if (ora_dedup_stat && ora_sort_comb_calls != j) ora_dedup_stat[ORA_DS_FLAGS] |= ORA_DF_COMB2;
+	DSTAT(ORA_DS_KEPT, = n);
 	for (i = 1; i < n; ++i)
-		if (a[i].score == a[i-1].score && a[i].rb == a[i-1].rb && a[i].qb == a[i-1].qb) a[i].qe = a[i].qb;
+		if (a[i].score == a[i-1].score && a[i].rb == a[i-1].rb && a[i].qb == a[i-1].qb) { a[i].qe = a[i].qb; DSTAT(ORA_DS_IDENT, += 1); }
 	for (i = 1, m = 1; i < n; ++i)
 		if (a[i].qe > a[i].qb) { if (m != i) a[m++] = a[i]; else ++m; }
 	return m;
@@ -355,4 +373,39 @@ ora_reg_v ora_align1_core(const ora_opt_t *opt, const ora_index_t *idx, int l_se
 		if (p->rid >= 0 && idx->ref->anns[p->rid].is_alt) p->is_alt = 1;
 	}
 	return regs;
+}
+
+/* Test helper (`bwa_oracle katdedup`, tests/dedup_cases.py): ora_sort_dedup_patch with the index's reference and the query, then the is_alt
+ * marking of ora_align1_core (bwamem.c:1091-1095), on a caller's region list of n >= 2 regions, 19 words per region in dump_regs' order
+ * (main_oracle.c).  out19 has room for n regions; stat: ORA_DEDUP_STAT_N words, what the function did (ora.h).  Returns the final length. */
+int ora_kat_dedup(const ora_opt_t *opt, const ora_ref_t *ref, int l_query, const uint8_t *query, int n, const int64_t *regs19, int64_t *out19, int64_t *stat)
+{
+	ora_reg_t *a = (ora_reg_t*)calloc((size_t)n + 1, sizeof(ora_reg_t));
+	uint8_t *q = (uint8_t*)malloc((size_t)l_query + 1);
+	int i;
+	memcpy(q, query, (size_t)l_query);
+	for (i = 0; i < n; ++i) {
+		const int64_t *x = regs19 + 19 * i;
+		ora_reg_t *p = &a[i];
+		uint32_t u = (uint32_t)x[18];
+		p->rb = x[0]; p->re = x[1]; p->qb = (int)x[2]; p->qe = (int)x[3]; p->rid = (int)x[4]; p->score = (int)x[5]; p->truesc = (int)x[6];
+		p->sub = (int)x[7]; p->alt_sc = (int)x[8]; p->csub = (int)x[9]; p->sub_n = (int)x[10]; p->w = (int)x[11]; p->seedcov = (int)x[12];
+		p->secondary = (int)x[13]; p->secondary_all = (int)x[14]; p->seedlen0 = (int)x[15]; p->n_comp = (int)x[16]; p->is_alt = (int)x[17];
+		memcpy(&p->frac_rep, &u, 4);
+	}
+	memset(stat, 0, ORA_DEDUP_STAT_N * 8);
+	ora_dedup_stat = stat;
+	n = ora_sort_dedup_patch(opt, ref, q, n, a);
+	ora_dedup_stat = 0;
+	for (i = 0; i < n; ++i) {
+		ora_reg_t *p = &a[i];
+		int64_t *w = out19 + 19 * i;
+		uint32_t u;
+		if (p->rid >= 0 && ref->anns[p->rid].is_alt) p->is_alt = 1;
+		memcpy(&u, &p->frac_rep, 4);
+		w[0] = p->rb; w[1] = p->re; w[2] = p->qb; w[3] = p->qe; w[4] = p->rid; w[5] = p->score; w[6] = p->truesc; w[7] = p->sub; w[8] = p->alt_sc; w[9] = p->csub;
+		w[10] = p->sub_n; w[11] = p->w; w[12] = p->seedcov; w[13] = p->secondary; w[14] = p->secondary_all; w[15] = p->seedlen0; w[16] = p->n_comp; w[17] = p->is_alt; w[18] = u;
+	}
+	free(a); free(q);
+	return n;
 }

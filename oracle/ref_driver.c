@@ -23,6 +23,7 @@
  *   katdp  <out.bin> <n> <seed>                  known answers: ksw_extend2 / ksw_global2 over
  *                                                the whole range of lengths, bands, matrices
  *   katchain [options] <prefix> <cases.bin> <out.bin>   known answers: chains and filtered chains of given seed lists
+ *   katdedup [options] <prefix> <cases.bin> <out.bin>   known answers: mem_sort_dedup_patch of given region lists
  *   katmark [options] <prefix> <cases.bin> <out.bin>    known answers: primary marking and mapQ of given region lists
  *
  * Dump format ("i64 records"): a stream of  [tag:i64][n:i64][n x i64].
@@ -42,6 +43,7 @@ extern int bwa_idx_build(const char *fa, const char *prefix, int algo_type, int 
 #define OPT_LOG(x) log(x)
 #include "opt_parse.h"
 #include "kat_mark_io.h"
+#include "kat_dedup_io.h"
 
 /* ---------------------------------------------------------------- records */
 static void rec_write(FILE *fp, int64_t tag, int64_t n, const int64_t *v)
@@ -638,6 +640,66 @@ static int main_katmark(int argc, char **argv)
 	return rc ? 1 : 0;
 }
 
+/* katdedup [options] <prefix> <cases.bin> <out.bin>: the reference's own mem_sort_dedup_patch(opt, bns, pac, query, n, a) and the is_alt
+ * loop of mem_align1_core (bwamem.c:1091-1095) on caller-supplied region lists over the index's reference; kat_dedup_io.h has both file
+ * formats.  The words of what the function did are written as 0: the reference does not count. */
+static int main_katdedup(int argc, char **argv)
+{
+	mem_opt_t *opt = mem_opt_init();
+	optparse_t op;
+	bwaidx_t *idx;
+	kd_file_t k;
+	FILE *in, *out;
+	const int64_t *regs;
+	uint8_t *seq;
+	int64_t i, *rec = 0;
+	int c, n, l, rc, j;
+	bwa_verbose = 1;
+	optparse_init(&op, opt);
+	while ((c = getopt(argc, argv, OPT_GETOPT_STRING)) >= 0) if (optparse_one(&op, c, optarg)) return 1;
+	if (optparse_finish(&op) || optind + 3 > argc) return 1;
+	idx = bwa_idx_load(argv[optind], BWA_IDX_BNS | BWA_IDX_PAC);
+	if (!idx) return 1;
+	if (op.ignore_alt) for (c = 0; c < idx->bns->n_seqs; ++c) idx->bns->anns[c].is_alt = 0;
+	in = fopen(argv[optind + 1], "rb"); out = fopen(argv[optind + 2], "wb");
+	if (!in || !out || kd_read_opt(in, opt, &k)) { fprintf(stderr, "[bwaref] katdedup: cannot open the files, or no option record\n"); return 1; }
+	while ((rc = kd_next_read(in, &k, &i, &l, &seq, &n, &regs)) > 0) {
+		mem_alnreg_t *a = calloc(n, sizeof(mem_alnreg_t));
+		int64_t hdr[2];
+		(void)l;
+		for (j = 0; j < n; ++j) {
+			const int64_t *w = regs + KD_REG_WORDS * j;
+			mem_alnreg_t *p = &a[j];
+			p->rb = w[0]; p->re = w[1]; p->qb = (int)w[2]; p->qe = (int)w[3]; p->rid = (int)w[4]; p->score = (int)w[5]; p->truesc = (int)w[6];
+			p->sub = (int)w[7]; p->alt_sc = (int)w[8]; p->csub = (int)w[9]; p->sub_n = (int)w[10]; p->w = (int)w[11]; p->seedcov = (int)w[12];
+			p->secondary = (int)w[13]; p->secondary_all = (int)w[14]; p->seedlen0 = (int)w[15]; p->n_comp = (int)w[16]; p->is_alt = (int)w[17];
+			p->frac_rep = km_i2f(w[18]);
+		}
+		n = mem_sort_dedup_patch(opt, idx->bns, idx->pac, seq, n, a);
+		rec = realloc(rec, (1 + KD_STAT_WORDS + (size_t)KD_REG_WORDS * n) * 8);
+		memset(rec, 0, (1 + KD_STAT_WORDS) * 8);
+		rec[0] = n;
+		for (j = 0; j < n; ++j) {
+			mem_alnreg_t *p = &a[j];
+			int64_t *w = rec + 1 + KD_STAT_WORDS + KD_REG_WORDS * j;
+			if (p->rid >= 0 && idx->bns->anns[p->rid].is_alt) p->is_alt = 1;
+			w[0] = p->rb; w[1] = p->re; w[2] = p->qb; w[3] = p->qe; w[4] = p->rid; w[5] = p->score; w[6] = p->truesc; w[7] = p->sub; w[8] = p->alt_sc;
+			w[9] = p->csub; w[10] = p->sub_n; w[11] = p->w; w[12] = p->seedcov; w[13] = p->secondary; w[14] = p->secondary_all; w[15] = p->seedlen0;
+			w[16] = p->n_comp; w[17] = p->is_alt; w[18] = f2i(p->frac_rep);
+		}
+		hdr[0] = i; hdr[1] = n;
+		rec_write(out, TAG_READ, 2, hdr);
+		rec_write(out, KD_TAG_OUT, 1 + KD_STAT_WORDS + (int64_t)KD_REG_WORDS * n, rec);
+		free(a);
+	}
+	free(rec); free(k.buf); free(k.seq);
+	fclose(in); fclose(out);
+	bwa_idx_destroy(idx);
+	free(opt);
+	if (rc) fprintf(stderr, "[bwaref] katdedup: malformed case file\n");
+	return rc ? 1 : 0;
+}
+
 /* readfq <chunk_bases> <in1> [in2]: the batches the reference's bseq_read (bwa.c:191) cuts, one record per line as
  * name TAB comment-or-* TAB seq TAB qual-or-*, a line "#batch <n>" in front of every batch -- golden vectors for the product's
  * FASTA/FASTQ reader (csrc/fastq_reader.cpp) */
@@ -680,6 +742,7 @@ int main(int argc, char **argv)
 	if (strcmp(argv[1], "katdp") == 0) return main_katdp(argc - 1, argv + 1);
 	if (strcmp(argv[1], "katchain") == 0) return main_katchain(argc - 1, argv + 1);
 	if (strcmp(argv[1], "katmark") == 0) return main_katmark(argc - 1, argv + 1);
+	if (strcmp(argv[1], "katdedup") == 0) return main_katdedup(argc - 1, argv + 1);
 	if (strcmp(argv[1], "readfq") == 0) return main_readfq(argc - 1, argv + 1);
 	fprintf(stderr, "unknown sub-command '%s'\n", argv[1]);
 	return 1;

@@ -16,6 +16,7 @@ the outputs below are data (inputs + expected outputs), never reference source.
   tests/golden/pelib_<name>_[12].fq.gz, pelib_<name>.sam.gz   the paired-end libraries of tests/pe_cases.py at pe_cases.GOLDEN_PAIRS pairs over the
                                    suite's 1 Mb genome (simgen seed 11), and the reference's SAM for them (`make_golden.py pelibs`)
   tests/golden/kat_chain.npz       the reference's chains and filtered chains for the seed lists of tests/chain_cases.py (`make_golden.py chain`)
+  tests/golden/kat_dedup.npz       digests of the reference's mem_sort_dedup_patch for the region lists of tests/dedup_cases.py (`make_golden.py dedup`)
   tests/golden/kat_mark.npz        digests of the reference's primary marking and mapQ for the region lists of tests/mark_cases.py (`make_golden.py mark`)
 
 `make_golden.py extras` writes only the last two groups (round 2 additions); the older files are left alone.
@@ -244,5 +245,25 @@ def mark_kat():
     print("kat_mark.npz:", os.path.getsize(f"{HERE}/kat_mark.npz"), "bytes")
 
 
+def dedup_kat():
+    """kat_dedup.npz: every set of tests/dedup_cases.py through `bwaref katdedup` (oracle/ref_driver.c: the reference's own
+    mem_sort_dedup_patch and the is_alt loop of mem_align1_core on the given region lists) over g60k.fa.gz with g60k.alt.  Per set:
+    <set>.inputs, the sha256 of the generated case file and its flags; <set>.sha [reads], the sha256 of each read's final list; for the
+    small hand-made sets (at most 200 regions) <set>.words, the final lists themselves.  Results only, no inputs."""
+    import dedup_cases as dc
+    assert os.path.exists("/root/reference/bwamem.c") and os.access(REF, os.X_OK), "needs the reference build (make -C oracle ref)"
+    os.makedirs(TMP, exist_ok=True)
+    prefix = dc.make_index(TMP)
+    out = {}
+    for name in dc.SETS:
+        got = [x[0] for x in dc.run_checker(REF, name, prefix, TMP, "golden")]
+        out[f"{name}.inputs"] = np.array(dc.input_digest(name))
+        out[f"{name}.sha"] = dc.digests(got)
+        if sum(len(c.regs) for c in dc.cases_of(name)) <= 200:
+            out[f"{name}.words"] = np.concatenate([x.ravel() for x in got])
+    np.savez_compressed(f"{HERE}/kat_dedup.npz", **out)
+    print("kat_dedup.npz:", os.path.getsize(f"{HERE}/kat_dedup.npz"), "bytes")
+
+
 if __name__ == "__main__":
-    {"extras": extras, "fastq": fastq_cases, "dpwide": dp_wide, "pelibs": pe_libraries, "chain": chain_kat, "mark": mark_kat}.get(sys.argv[1] if len(sys.argv) > 1 else "", main)()
+    {"dedup": dedup_kat, "extras": extras, "fastq": fastq_cases, "dpwide": dp_wide, "pelibs": pe_libraries, "chain": chain_kat, "mark": mark_kat}.get(sys.argv[1] if len(sys.argv) > 1 else "", main)()

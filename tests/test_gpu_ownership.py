@@ -12,6 +12,7 @@ import bai_ref
 import bam_sort_ref as sref
 import bgzf_ref
 import common
+import dedup_cases
 import dp_kat
 import mark_cases
 import markdup_cases as mcases
@@ -123,6 +124,8 @@ def _known_answers(ctx, s, members, bai, qc):
     recs, _ = ctx.kat_chain([700], [0, 1], [[5000, 10, 20, 0]], [0, 0], np.zeros((0, 3)))
     assert int(common.by_read(recs)[0][bw.STAGE_CHAIN_FLT][0]) == 1
     assert len(ctx.kat_mark([0, 1], [mark_cases.reg(0, 100, 90)])) > 0
+    dcs = [dedup_cases.Case("own", np.zeros(150, np.uint8), [dedup_cases.reg(100 + k, 200 + k, 0, 100, 50, rid=0), dedup_cases.reg(5000, 5100, 10, 110, 60, rid=0)]) for k in range(2)]
+    assert [len(x) for x in ctx.kat_dedup(*dedup_cases.pack(dcs)[:4])[0]] == [2, 2]
     buf = b"".join(s["records"])
     off = np.concatenate(([0], np.cumsum([len(r) for r in s["records"]]))).astype(np.int64)
     assert ctx.kat_bai(buf, off, _member_lens(members), len(s["hdr"]), N_REF) == bai
