@@ -160,6 +160,7 @@ KAT_DEDUP_FAST, KAT_DEDUP_STAGED, KAT_DEDUP_GLOBAL, KAT_DEDUP_SLABBED, KAT_DEDUP
 KAT_DEDUP_WHY_SHIFT, KAT_DEDUP_ALN_SHIFT, KAT_DEDUP_MRG_SHIFT = 7, 9, 20
 KAT_DEDUP_WHY_TIE1, KAT_DEDUP_WHY_PATCH, KAT_DEDUP_WHY_TIE2 = 1, 2, 3
 KAT_EXT_ROWS1, KAT_EXT_ROWS2, KAT_EXT_ROWS3, KAT_EXT_ROWS4, KAT_EXT_SHORT, KAT_EXT_WIDE, KAT_EXT_BEYOND16, KAT_EXT_STOPPED = 1, 2, 4, 8, 16, 32, 64, 128
+KAT_EXT_DIAG = 256
 
 
 class BwahipError(RuntimeError):
@@ -340,6 +341,7 @@ def lib():
     L.bwahip_kat_extend.argtypes = [vp, C.c_int, vp, vp, vp]
     L.bwahip_kat_ksw_extend.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, vp]
     L.bwahip_kat_ksw_extend2.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, vp, vp]
+    L.bwahip_kat_ksw_extend2_diag.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, vp, vp]
     L.bwahip_kat_ksw_global.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp]
     L.bwahip_align_batch.argtypes = [vp, C.POINTER(Opt), C.c_int, C.POINTER(Seq), C.POINTER(AlnRegV)]
     L.bwahip_process_seqs.argtypes = [vp, C.POINTER(Opt), C.c_int64, C.c_int, C.POINTER(Seq), C.POINTER(PeStat)]
@@ -1011,7 +1013,8 @@ class Context:
     def tune(self, **kw):
         """Set hand-off thresholds of the heavy-read kernels (bwahip_ctx_tune): intv_cap, smem_lanes, heavy_mult, ...; and
         ext_early_stop (default 1): ksw_extend2 ends once no later row can change its results; 0 = every row to the end, as the
-        reference (same results, more rows); and incr_insert (default 1): mate rescue places a region into a tie-free list without
+        reference (same results, more rows); and ext_diag (default 1): ksw_extend2 answers a flank of at most K mismatches (1 at the default
+        scores) from its main diagonal, without a DP row; 0 = every call runs its rows (same results); and incr_insert (default 1): mate rescue places a region into a tie-free list without
         sorting it again; 0 = every orientation ends in the full sort-and-dedup (same lists, pairing and output)."""
         for k, v in kw.items():
             _check(lib().bwahip_ctx_tune(self._h, k.encode(), int(v)), f"bwahip_ctx_tune({k})")
@@ -1334,7 +1337,7 @@ class Context:
         names = ["extend", "blocks", "sa", "lf", "intv", "seeds", "cells", "max_extends", "chain_build_max", "chain_sort_max", "chain_flt_max",
                  "chain_write_max", "max_seeds", "max_chains", "ext_max", "ext_dedup_max", "heavy_blocks", "heavy_intv", "heavy_reads",
                  "dp_rows_1col", "dp_rows_ncol", "dedup_sort1_max", "dedup_loop_max", "dedup_sort2_max",
-                 "pass3_blocks", "pass3_intv", "pass3_jumped", "_27", "_28", "_29", "_30", "_31"]
+                 "pass3_blocks", "pass3_intv", "pass3_jumped", "ext_calls", "ext_diag", "_29", "_30", "_31"]
         return {k: int(buf[i]) for i, k in enumerate(names)}
 
     def kat_introsort(self, k64, score, qb, mode):
@@ -1395,18 +1398,20 @@ class Context:
                                            toff.ctypes.data, out.ctypes.data), "bwahip_kat_ksw_extend")
         return out
 
-    def kat_ksw_extend2(self, params, mat, q, qoff, t, toff):
+    def kat_ksw_extend2(self, params, mat, q, qoff, t, toff, diag=False):
         """ksw_extend2 at a given number of columns per lane (bwahip_kat_ksw_extend2); params n x 12 (qlen, tlen, w, h0, zdrop, end_bonus,
         o_del, e_del, o_ins, e_ins, reverse, cpl), mat n x 25 -> n x 7 (six results, path mask KAT_EXT_*; KAT_EXT_STOPPED: the early
-        stop ended the loop -- the entry follows the context's ext_early_stop)."""
+        stop ended the loop -- the entry follows the context's ext_early_stop).  diag: bwahip_kat_ksw_extend2_diag, the call as the
+        extension kernels make it -- the diagonal rule first (knob ext_diag), KAT_EXT_DIAG alone in the mask of a call it answered."""
         params = np.ascontiguousarray(params, dtype=np.int32).reshape(-1, 12)
         mat = np.ascontiguousarray(mat, dtype=np.int8).reshape(-1, 25)
         q, t = np.ascontiguousarray(q, dtype=np.uint8), np.ascontiguousarray(t, dtype=np.uint8)
         qoff, toff = np.ascontiguousarray(qoff, dtype=np.int64), np.ascontiguousarray(toff, dtype=np.int64)
         assert len(mat) == len(params) and len(qoff) == len(params) + 1 and len(toff) == len(params) + 1
         out = np.zeros((len(params), 7), dtype=np.int32)
-        _check(lib().bwahip_kat_ksw_extend2(self._h, len(params), params.ctypes.data, mat.ctypes.data, q.ctypes.data, qoff.ctypes.data, t.ctypes.data,
-                                            toff.ctypes.data, out.ctypes.data), "bwahip_kat_ksw_extend2")
+        fn = lib().bwahip_kat_ksw_extend2_diag if diag else lib().bwahip_kat_ksw_extend2
+        _check(fn(self._h, len(params), params.ctypes.data, mat.ctypes.data, q.ctypes.data, qoff.ctypes.data, t.ctypes.data,
+                  toff.ctypes.data, out.ctypes.data), "bwahip_kat_ksw_extend2_diag" if diag else "bwahip_kat_ksw_extend2")
         return out
 
     def kat_ksw_global(self, params, mat, q, qoff, t, toff):

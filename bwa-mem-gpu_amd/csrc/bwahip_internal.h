@@ -46,7 +46,8 @@ struct DevOpt {
 // Work counters kept in HBM, bumped once per wavefront at kernel exit (bwahip_batch_counters).
 enum { CNT_EXTEND = 0, CNT_BLOCKS, CNT_SA, CNT_LF, CNT_INTV, CNT_SEEDS, CNT_CELLS, CNT_MAX_EXT /* most bwt_extend calls of one read */,
        CNT_HEAVY_BLOCKS = 16, CNT_HEAVY_INTV, CNT_HEAVY_READS, CNT_ROWS1 /* DP rows, 1 column per lane */, CNT_ROWSN /* DP rows, CPL columns per lane */,
-       CNT_P3_BLOCKS = 24, CNT_P3_INTV, CNT_P3_JUMPED /* pass-3 extensions the interval table stood in for */, CNT_N = 32 };
+       CNT_P3_BLOCKS = 24, CNT_P3_INTV, CNT_P3_JUMPED /* pass-3 extensions the interval table stood in for */,
+       CNT_EXT_CALLS /* ksw_extend2 calls of the extension kernels */, CNT_EXT_DIAG /* those the diagonal rule answered without a row */, CNT_N = 32 };
 // The counters are kept in CNT_SLOTS copies (rows of CNT_N); a wavefront updates the row picked by its position in the
 // launch and the host folds the rows (sum, or max for the *_max entries).  One shared row made every wavefront's
 // end-of-work atomics queue up on the same L2 line: with a million wavefronts that alone cost tens of milliseconds.
@@ -196,6 +197,7 @@ struct ExtLaunch {
 	uint8_t *big_t;                              // BWAHIP_EXT_BIG_GRID slabs of BWAHIP_EXT_BIG_T + 64 bytes
 	int lds_window;                              // largest reference window k_extend keeps in LDS (<= its compiled MAXT)
 	int ext_early_stop;                          // ksw_extend2 ends once no later row can change its results (0: off)
+	int ext_diag;                                // ksw_extend2 answers a flank of at most K mismatches from its diagonal, without a row (0: off)
 	int *diag;                                   // bwahip_kat_dedup only (its own instantiations of the dedup kernels): one word per read, BWAHIP_KAT_DEDUP_* of bwahip.h; nullptr in every production launch
 };
 constexpr int BWAHIP_EXT_BIG_GRID = 128, BWAHIP_EXT_BIG_T = 1 << 16;
@@ -362,7 +364,7 @@ int launch_kat_ksw(const DevOpt &opt, int early_stop, int n, const int *params, 
                    int *out6, hipStream_t st);
 // known-answer kernels of the two DP forms on caller-supplied pairs (bwahip_kat_ksw_global / bwahip_kat_ksw_extend2): the n items listed in
 // `items` of the caller's arrays; params: 10 (global) or 12 (extend) ints per item, mat: 25 bytes per item
-struct KatDp { int n; const int *items, *params; const int8_t *mat; const uint8_t *q; const int64_t *qoff; const uint8_t *t; const int64_t *toff; int early_stop = 0; };   // early_stop: the context's ext_early_stop (ksw_extend2 only)
+struct KatDp { int n; const int *items, *params; const int8_t *mat; const uint8_t *q; const int64_t *qoff; const uint8_t *t; const int64_t *toff; int early_stop = 0, diag = 0; };   // early_stop: the context's ext_early_stop (ksw_extend2 only); diag: its ext_diag (bwahip_kat_ksw_extend2_diag only)
 int launch_kat_global(const KatDp &a, int form, int grid, uint8_t *big_z, unsigned *zslab, int *out2, uint32_t *cig_out, hipStream_t st);   // k_final.hip
 size_t kat_global_zslab_bytes();
 int kat_global_t_cap(int form);

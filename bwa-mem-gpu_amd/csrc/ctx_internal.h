@@ -92,6 +92,7 @@ struct Knobs {
 	int spec_min_chains = 16;   // BWAHIP_SPEC_MIN_CHAINS: chains from which k_extend_spec extends ahead of time (0: off)
 	int ext_lds_window = 1 << 30;   // BWAHIP_EXT_LDS_WINDOW: reference windows above this go to k_extend_big (tests; default = the compiled LDS window)
 	int ext_early_stop = 1;     // BWAHIP_EXT_EARLY_STOP: ksw_extend2 ends once no later row can change its results (0: every row to the end, as the reference -- same results, more rows)
+	int ext_diag = 1;           // BWAHIP_EXT_DIAG: ksw_extend2 answers a flank of ACGT bases with at most K mismatches (1 at the default scores) from its main diagonal, without a DP row (0: every call runs its rows -- same results)
 	int sorted_piece_blocks = 1024;   // BWAHIP_SORTED_PIECE_BLOCKS: BGZF blocks a device merger (k_bammerge.hip) gathers and deflates at a time (1 .. 4096; the bytes do not depend on it)
 	int gpu_final = 1;          // BWAHIP_GPU_FINAL: 0 = finalisation of single-end batches on host threads (host_final.cpp) instead of the GPU kernels
 	int gpu_pair = 1;           // BWAHIP_GPU_PAIR: 0 = paired-end batches finalised on host threads (mate rescue, pairing, SAM)
@@ -103,12 +104,12 @@ struct Knobs {
 	{
 		auto geti = [](const char *k, int &v) { if (const char *e = getenv(k)) v = atoi(e); };
 		geti("BWAHIP_INTV_CAP", intv_cap); geti("BWAHIP_SMEM_LANES", smem_lanes); geti("BWAHIP_HEAVY_MULT", heavy_mult); geti("BWAHIP_SA_INTV", sa_intv); geti("BWAHIP_KMER_K", kmer_k);
-		geti("BWAHIP_CHAIN_BIG_MIN", chain_big_min); geti("BWAHIP_CHAIN_MID_MAX", chain_mid_max); geti("BWAHIP_CHAIN_BIG_MAX", chain_big_max); geti("BWAHIP_CHAIN_GLB_GRID", chain_glb_grid); geti("BWAHIP_RANK_SORT_MIN", rank_sort_min); geti("BWAHIP_SPEC_MIN_CHAINS", spec_min_chains); geti("BWAHIP_EXT_LDS_WINDOW", ext_lds_window); geti("BWAHIP_EXT_EARLY_STOP", ext_early_stop); geti("BWAHIP_GPU_FINAL", gpu_final); geti("BWAHIP_GPU_PAIR", gpu_pair);
+		geti("BWAHIP_CHAIN_BIG_MIN", chain_big_min); geti("BWAHIP_CHAIN_MID_MAX", chain_mid_max); geti("BWAHIP_CHAIN_BIG_MAX", chain_big_max); geti("BWAHIP_CHAIN_GLB_GRID", chain_glb_grid); geti("BWAHIP_RANK_SORT_MIN", rank_sort_min); geti("BWAHIP_SPEC_MIN_CHAINS", spec_min_chains); geti("BWAHIP_EXT_LDS_WINDOW", ext_lds_window); geti("BWAHIP_EXT_EARLY_STOP", ext_early_stop); geti("BWAHIP_EXT_DIAG", ext_diag); geti("BWAHIP_GPU_FINAL", gpu_final); geti("BWAHIP_GPU_PAIR", gpu_pair);
 		verbose = getenv("BWAHIP_VERBOSE") != nullptr;
 		e2e_log = getenv("BWAHIP_E2E_LOG") != nullptr;
 		dump_ext = getenv("BWAHIP_DUMP_EXT");
 		if (intv_cap < 2) intv_cap = 2;
-		ext_early_stop = ext_early_stop != 0;
+		ext_early_stop = ext_early_stop != 0; ext_diag = ext_diag != 0;
 		geti("BWAHIP_INCR_INSERT", incr_insert); incr_insert = incr_insert != 0;
 		geti("BWAHIP_SORTED_PIECE_BLOCKS", sorted_piece_blocks);
 		if (sorted_piece_blocks < 1 || sorted_piece_blocks > 4096) sorted_piece_blocks = 1024;

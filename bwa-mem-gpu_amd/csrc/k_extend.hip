@@ -35,8 +35,27 @@ constexpr int MAXT = BWAHIP_MAX_READ_LEN + 2 * 200 + 1024;   // reference window
 
 // per-wavefront work counters (all uniform; lane 0 adds them to the launch counters at the end)
 struct Work { unsigned long long cells; unsigned rows1, rowsN; };
-// which forms a call of wave_extend_fit<CPL, true> went through, and whether the early stop ended its loop (BWAHIP_KAT_EXT_*)
-enum { EXT_PATH_ROWS1 = 1, EXT_PATH_ROWS2 = 2, EXT_PATH_ROWS3 = 4, EXT_PATH_ROWS4 = 8, EXT_PATH_SHORT = 16, EXT_PATH_WIDE = 32, EXT_PATH_BEYOND16 = 64, EXT_PATH_STOPPED = 128 };
+// which forms a call of wave_extend_fit<CPL, true> went through, and whether the early stop ended its loop (BWAHIP_KAT_EXT_*);
+// EXT_PATH_DIAG alone: the diagonal rule answered the call, no form ran
+enum { EXT_PATH_ROWS1 = 1, EXT_PATH_ROWS2 = 2, EXT_PATH_ROWS3 = 4, EXT_PATH_ROWS4 = 8, EXT_PATH_SHORT = 16, EXT_PATH_WIDE = 32, EXT_PATH_BEYOND16 = 64, EXT_PATH_STOPPED = 128,
+       EXT_PATH_DIAG = 256 };
+// The calls of wave_extend_fit ([0]) and those the diagonal rule answered ([1]) are counted in LDS, by lane 0 with an add that returns nothing:
+// as two more members of Work they lived in registers through every row loop, which cost k_extend<5> a wavefront of occupancy and
+// k_extend<3> eight more spilled dwords.  One wavefront per workgroup; lane 0 zeroes, adds and reads them, in program order.
+__device__ __forceinline__ unsigned *ext_calls_lds() { __shared__ unsigned s_ext_calls[2]; return s_ext_calls; }
+__device__ __forceinline__ void count_ext_call(int which)
+{
+	if (lane() == 0) __hip_atomic_fetch_add(&ext_calls_lds()[which], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+}
+__device__ __forceinline__ void zero_ext_calls() { if (lane() == 0) { ext_calls_lds()[0] = 0; ext_calls_lds()[1] = 0; } }
+// lane 0, at the end of a wavefront's work
+__device__ __forceinline__ void report_ext_calls(unsigned long long *counters)
+{
+	const unsigned calls = __hip_atomic_load(&ext_calls_lds()[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+	const unsigned diag = __hip_atomic_load(&ext_calls_lds()[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+	if (calls) atomicAdd(&cnt_row(counters)[CNT_EXT_CALLS], (unsigned long long)calls);
+	if (diag) atomicAdd(&cnt_row(counters)[CNT_EXT_DIAG], (unsigned long long)diag);
+}
 
 // ---------------------------------------------------------------------------------------------------
 // ksw_extend2 (ksw.c:380).  q/t live in LDS and are read with a stride (+1 / -1) so the left extension
@@ -458,6 +477,58 @@ __device__ __forceinline__ int ext_rows(const Sw &sw, const uint8_t *q, int qs, 
 	return status;
 }
 
+// ---------------------------------------------------------------------------------------------------
+// The diagonal rule ("ksw_extend2: flanks the diagonal answers").  With a matrix of bwa_fill_scmat(a, b), g = min(o_del + e_del,
+// o_ins + e_ins) and K the largest integer with K * (a + b) < g: a flank of ACGT bases with at most K mismatches against the first qlen
+// target bases, whose diagonal value d(j) = h0 + a * matches(0..j) - b * mismatches(0..j) never falls below 1, has all six results of
+// ksw_extend2 on the main diagonal -- no row is run.
+// ext_diag_k: once per kernel.  K, or 0 when the knob is off, the matrix has another form or no mismatch is affordable.
+__device__ __forceinline__ int ext_diag_k(int knob, const int8_t *mat, int o_del, int e_del, int o_ins, int e_ins)
+{
+	const int l = lane();
+	const int a = mat[0], b = -(int)mat[1];
+	const bool other = l < 16 && mat[(l >> 2) * 5 + (l & 3)] != ((l >> 2) == (l & 3) ? a : -b);
+	if (!knob || __ballot(other) || a < 1 || b < 0) return 0;
+	const int g = o_del + e_del < o_ins + e_ins ? o_del + e_del : o_ins + e_ins;
+	return g < 1 ? 0 : (g - 1) / (a + b);
+}
+// One call: collective over the wavefront.  Lane l compares q[j] with t[j] for j = l, l + 64, ...; two ballots per chunk of 64 bases give
+// the N's and the mismatches, the scalar unit walks the mismatches (at most K) and keeps the diagonal's value and its first maximum.
+// Leaves with false -- the DP forms take the call -- at the first chunk that shows an N, mismatch K + 1 or a diagonal value below 1.
+__device__ __forceinline__ bool ext_diag_answer(const Sw &sw, const uint8_t *q, int qs, int qlen, const uint8_t *t, int ts, int tlen, int zdrop, int h0,
+                                                int &score, int &qle, int &tle, int &gtle, int &gscore, int &max_off)
+{
+	const int K = __builtin_amdgcn_readfirstlane(sw.diag);
+	qlen = __builtin_amdgcn_readfirstlane(qlen); tlen = __builtin_amdgcn_readfirstlane(tlen);
+	zdrop = __builtin_amdgcn_readfirstlane(zdrop); h0 = __builtin_amdgcn_readfirstlane(h0);
+	if (K < 1 || qlen < 1 || tlen < qlen || h0 < 1) return false;
+	const int a = __builtin_amdgcn_readfirstlane((int)sw.mat[0]), b = -__builtin_amdgcn_readfirstlane((int)sw.mat[1]);
+	if (zdrop > 0 && K * b > zdrop) return false;                // (on the diagonal best - rowmax <= K * b: no z-drop break)
+	const int l = lane();
+	int left = K, prev = 0, d = h0, best = h0, best_j = -1;      // prev: first base after the last mismatch; d: the diagonal's value before it
+	for (int j0 = 0; j0 < qlen; j0 += 64) {
+		const int j = j0 + l;
+		const int qc = j < qlen ? q[j * qs] : 0, tc = j < qlen ? t[j * ts] : 0;
+		if (__ballot(qc > 3 || tc > 3)) return false;
+		unsigned long long mm = __ballot(qc != tc);
+		left -= __popcll(mm);
+		if (left < 0) return false;
+		while (mm) {
+			const int p = j0 + __ffsll((long long)mm) - 1;
+			mm &= mm - 1;
+			d += a * (p - prev);                                  // the matches before the mismatch: the value rises to d(p - 1)
+			if (d > best) { best = d; best_j = p - 1; }
+			d -= b;
+			if (d < 1) return false;                              // (a cell of value 0 restarts nothing in ksw_extend2: the diagonal would die)
+			prev = p + 1;
+		}
+	}
+	d += a * (qlen - prev);
+	if (d > best) { best = d; best_j = qlen - 1; }
+	score = best; qle = tle = best_j + 1; gscore = d; gtle = qlen; max_off = 0;
+	return true;
+}
+
 // The driver: first row of ksw_extend2 (ksw.c:396-397), band clamp (ksw.c:399-407), then runs of rows in the window that fits.
 // Flanks of fewer than 64 bases keep the plain one-column-per-lane form (nothing to gain there); so do bands that can grow wider than WIN_MAX
 // columns (-w above 126 on flanks of 256 bases and more) and scores that do not fit 16 bits.
@@ -467,6 +538,15 @@ __device__ __forceinline__ int wave_extend_fit(const Sw &sw, const uint8_t *q, i
                                                int w, int end_bonus, int zdrop, int h0, int &qle, int &tle, int &gtle, int &gscore, int &max_off, Work &wk, unsigned *s_he,
                                                unsigned *path = nullptr)
 {
+	if (!TRACE) count_ext_call(0);                               // (the known-answer kernel reports a path mask, not counts)
+	if (sw.diag) {                                               // the diagonal rule first: an answered call runs no row and counts no cell
+		int sc;
+		if (ext_diag_answer(sw, q, qs, qlen, t, ts, tlen, zdrop, h0, sc, qle, tle, gtle, gscore, max_off)) {
+			if (!TRACE) count_ext_call(1);
+			if (TRACE) *path |= EXT_PATH_DIAG;
+			return sc;
+		}
+	}
 	if (TRACE && qlen < 64) *path |= EXT_PATH_SHORT;
 	if (qlen < 64) return wave_extend<1, TRACE>(sw, q, qs, qlen, t, ts, tlen, w, end_bonus, zdrop, h0, qle, tle, gtle, gscore, max_off, wk, path);
 #ifdef KEXT_NO_WINDOW
@@ -639,7 +719,9 @@ __global__ __launch_bounds__(64, (CPL <= 3 ? KEXT_W3 : CPL == 4 ? 4 : 1)) void k
 	Sw sw; sw.mat = s_mat; sw.o_del = opt.o_del; sw.e_del = opt.e_del; sw.o_ins = opt.o_ins; sw.e_ins = opt.e_ins; sw.stop = a.ext_early_stop;
 	if (l < 25) s_mat[l] = opt.mat[l];
 	sw.mx = wmax(l < 25 ? (int)opt.mat[l] : 0); if (sw.mx < 0) sw.mx = 0;
+	sw.diag = ext_diag_k(a.ext_diag, opt.mat, opt.o_del, opt.e_del, opt.o_ins, opt.e_ins);
 	Work wk = { 0, 0, 0 };
+	zero_ext_calls();
 	const int n_items = *a.spec_n;
 	for (int it = (int)blockIdx.x; it < n_items; it += (int)gridDim.x) {
 		const int2 item = a.spec_items[it];
@@ -668,6 +750,7 @@ __global__ __launch_bounds__(64, (CPL <= 3 ? KEXT_W3 : CPL == 4 ? 4 : 1)) void k
 		if (l == 0) a.spec_regs[sb + ci] = reg;
 	}
 	if (l == 0 && wk.cells) { atomicAdd(&cnt_row(a.counters)[CNT_CELLS], wk.cells); atomicAdd(&cnt_row(a.counters)[CNT_ROWS1], (unsigned long long)wk.rows1); atomicAdd(&cnt_row(a.counters)[CNT_ROWSN], (unsigned long long)wk.rowsN); }
+	if (l == 0) report_ext_calls(a.counters);
 }
 
 // work list of k_extend_spec: (read, chain) for every chain of a read with at least min_chains chains
@@ -789,11 +872,13 @@ __device__ __forceinline__ void extend_read(const ExtLaunch &a, const int r, uin
 	int *srt = a.srt + 2 * sb;                                  // [0..n): seed index in ascending (score,idx) order; [n..2n): skipped flag
 	int n_av = 0;
 	Work wk = { 0, 0, 0 };
+	zero_ext_calls();
 	const unsigned long long t_0 = wall_clock64();
 	Sw sw; sw.mat = s_mat; sw.o_del = opt.o_del; sw.e_del = opt.e_del; sw.o_ins = opt.o_ins; sw.e_ins = opt.e_ins; sw.stop = a.ext_early_stop;
 	__syncthreads();
 	if (l < 25) s_mat[l] = opt.mat[l];
 	sw.mx = wmax(l < 25 ? (int)opt.mat[l] : 0); if (sw.mx < 0) sw.mx = 0;
+	sw.diag = ext_diag_k(a.ext_diag, opt.mat, opt.o_del, opt.e_del, opt.o_ins, opt.e_ins);
 	bool have_q = PHASE != 2;                                   // the dedup pass needs the query only for mem_patch_reg's alignment (rare): fetched then
 	if (have_q) for (int i = l; i < l_query; i += 64) s_q[i] = query[i];
 	__syncthreads();
@@ -911,6 +996,7 @@ __device__ __forceinline__ void extend_read(const ExtLaunch &a, const int r, uin
 			const int li = a.subset == 1 ? 1 : 0;                   // the heavy reads' list is the second one
 			a.dedup_list[(size_t)li * a.n_reads + atomicAdd(&a.dedup_n[li], 1)] = r;
 			if (wk.cells) { atomicAdd(&cnt_row(a.counters)[CNT_CELLS], wk.cells); atomicAdd(&cnt_row(a.counters)[CNT_ROWS1], (unsigned long long)wk.rows1); atomicAdd(&cnt_row(a.counters)[CNT_ROWSN], (unsigned long long)wk.rowsN); }
+			report_ext_calls(a.counters);
 			atomicMax(&cnt_row(a.counters)[14], t_1 - t_0);
 		}
 		return;
@@ -1131,6 +1217,7 @@ __device__ __forceinline__ void extend_read(const ExtLaunch &a, const int r, uin
 	if (l == 0) {
 		a.reg_n[r] = n;
 		if (wk.cells) { atomicAdd(&cnt_row(a.counters)[CNT_CELLS], wk.cells); atomicAdd(&cnt_row(a.counters)[CNT_ROWS1], (unsigned long long)wk.rows1); atomicAdd(&cnt_row(a.counters)[CNT_ROWSN], (unsigned long long)wk.rowsN); }
+		report_ext_calls(a.counters);
 		if (PHASE != 2) atomicMax(&cnt_row(a.counters)[14], t_1 - t_0);
 		atomicMax(&cnt_row(a.counters)[15], wall_clock64() - t_1);
 		atomicMax(&cnt_row(a.counters)[21], t_s1 - t_1); atomicMax(&cnt_row(a.counters)[22], t_lp - t_s1); atomicMax(&cnt_row(a.counters)[23], wall_clock64() - t_lp);
@@ -1305,7 +1392,8 @@ __global__ __launch_bounds__(64) void k_kat_ksw(DevOpt opt, int early_stop, int 
 // known-answer kernel: ksw_extend2 as the extension kernels instantiated for CPL columns per lane run it, on caller-supplied pairs with their own
 // matrix.  params per item: qlen, tlen, w, h0, zdrop, end_bonus, o_del, e_del, o_ins, e_ins, reverse (stride -1 on both sequences, as the left
 // extension reads them, bwamem.c:725-729), cpl.  out7: the six results, and the forms wave_extend_fit went through (EXT_PATH_*, with
-// EXT_PATH_STOPPED when the early stop ended its loop; a.early_stop = 0 runs both calls to the last row).
+// EXT_PATH_STOPPED when the early stop ended its loop; a.early_stop = 0 runs both calls to the last row).  a.diag = 1 (bwahip_kat_ksw_extend2_diag): wave_extend_fit
+// applies the diagonal rule as in the extension kernels, and reports EXT_PATH_DIAG alone for a call it answered.
 template <int CPL>
 __global__ __launch_bounds__(64) void k_kat_ksw2(KatDp a, int *out7)
 {
@@ -1327,6 +1415,7 @@ __global__ __launch_bounds__(64) void k_kat_ksw2(KatDp a, int *out7)
 	__syncthreads();
 	Sw sw; sw.mat = s_mat; sw.o_del = p[6]; sw.e_del = p[7]; sw.o_ins = p[8]; sw.e_ins = p[9]; sw.stop = a.early_stop;
 	sw.mx = wmax(l < 25 ? (int)mat[l] : 0); if (sw.mx < 0) sw.mx = 0;
+	sw.diag = ext_diag_k(a.diag, mat, p[6], p[7], p[8], p[9]);   // the plain form below never looks at it
 	const bool rev = p[10] != 0;
 	const uint8_t *qp = rev ? s_q + qlen - 1 : s_q, *tp = rev ? s_t + (tlen > 0 ? tlen - 1 : 0) : s_t;
 	const int st = rev ? -1 : 1;

@@ -380,6 +380,7 @@ int bwahip_ctx_tune(bwahip_ctx *c, const char *key, int value)
 	else if (!strcmp(key, "spec_min_chains")) k.spec_min_chains = value;
 	else if (!strcmp(key, "ext_lds_window")) k.ext_lds_window = value < 1 ? 1 : value;
 	else if (!strcmp(key, "ext_early_stop")) { if (value != 0 && value != 1) return BWAHIP_EINVAL; k.ext_early_stop = value; }
+	else if (!strcmp(key, "ext_diag")) { if (value != 0 && value != 1) return BWAHIP_EINVAL; k.ext_diag = value; }
 	else if (!strcmp(key, "sorted_piece_blocks")) { if (value < 1 || value > 4096) return BWAHIP_EINVAL; k.sorted_piece_blocks = value; }
 	else if (!strcmp(key, "gpu_final")) k.gpu_final = value;
 	else if (!strcmp(key, "gpu_pair")) k.gpu_pair = value;
@@ -701,7 +702,7 @@ static int ext_prepare(bwahip_ctx *c, const DevOpt &dopt, int n, int64_t total, 
 	if ((rc = c->d_dedup.ensure(((size_t)3 * n + 4) * 4))) return rc;
 	HIP_TRY(hipMemsetAsync(c->d_dedup.p, 0, 16, c->stream));
 	el.dedup_n = c->d_dedup.as<int>(); el.dedup_list = c->d_dedup.as<int>() + 4;
-	el.redo_n = c->d_redo.as<int>(); el.redo_list = c->d_redo.as<int>() + 4; el.big_t = c->d_big_t.as<uint8_t>(); el.lds_window = c->knobs.ext_lds_window; el.ext_early_stop = c->knobs.ext_early_stop;
+	el.redo_n = c->d_redo.as<int>(); el.redo_list = c->d_redo.as<int>() + 4; el.big_t = c->d_big_t.as<uint8_t>(); el.lds_window = c->knobs.ext_lds_window; el.ext_early_stop = c->knobs.ext_early_stop; el.ext_diag = c->knobs.ext_diag;
 	el.rank_sort_min = c->knobs.rank_sort_min;
 	const int spec_min = c->knobs.spec_min_chains;           // 0 = no ahead-of-time extension
 	if (spec_min > 0) {
@@ -1400,7 +1401,8 @@ static bool kat_dp_offsets_ok(int n, const int *params, int stride, const int64_
 	return true;
 }
 
-int bwahip_kat_ksw_extend2(bwahip_ctx *c, int n, const int *params, const int8_t *mat25, const uint8_t *q, const int64_t *qoff, const uint8_t *t, const int64_t *toff, int *out7)
+// diag: what the diagonal rule follows -- 0 in bwahip_kat_ksw_extend2 (every call runs its rows), the context's ext_diag in bwahip_kat_ksw_extend2_diag
+static int kat_ksw_extend2(bwahip_ctx *c, int n, const int *params, const int8_t *mat25, const uint8_t *q, const int64_t *qoff, const uint8_t *t, const int64_t *toff, int *out7, bool follow_diag)
 {
 	if (!c || n < 0 || (n && (!params || !mat25 || !q || !qoff || !t || !toff || !out7))) return BWAHIP_EINVAL;
 	if (n == 0) return 0;
@@ -1423,12 +1425,21 @@ int bwahip_kat_ksw_extend2(bwahip_ctx *c, int n, const int *params, const int8_t
 	for (int k = 0; k < 4 && !rc; ++k) {
 		if (items[k].empty()) continue;
 		if ((rc = upload(dit[k], items[k].data(), items[k].size() * 4, c->stream))) break;
-		const KatDp a = { (int)items[k].size(), dit[k].as<int>(), dp.as<int>(), dm.as<int8_t>(), dq.as<uint8_t>(), dqo.as<int64_t>(), dt.as<uint8_t>(), dto.as<int64_t>(), c->knobs.ext_early_stop };
+		const KatDp a = { (int)items[k].size(), dit[k].as<int>(), dp.as<int>(), dm.as<int8_t>(), dq.as<uint8_t>(), dqo.as<int64_t>(), dt.as<uint8_t>(), dto.as<int64_t>(), c->knobs.ext_early_stop,
+		                  follow_diag ? c->knobs.ext_diag : 0 };
 		rc = launch_kat_ksw2(a, cpls[k], dout.as<int>(), c->stream);
 	}
 	if (!rc && hipMemcpyAsync(out7, dout.p, (size_t)n * 28, hipMemcpyDeviceToHost, c->stream) != hipSuccess) rc = BWAHIP_ENODEV;
 	if (hipStreamSynchronize(c->stream) != hipSuccess) rc = BWAHIP_ENODEV;
 	return rc;
+}
+int bwahip_kat_ksw_extend2(bwahip_ctx *c, int n, const int *params, const int8_t *mat25, const uint8_t *q, const int64_t *qoff, const uint8_t *t, const int64_t *toff, int *out7)
+{
+	return kat_ksw_extend2(c, n, params, mat25, q, qoff, t, toff, out7, false);
+}
+int bwahip_kat_ksw_extend2_diag(bwahip_ctx *c, int n, const int *params, const int8_t *mat25, const uint8_t *q, const int64_t *qoff, const uint8_t *t, const int64_t *toff, int *out7)
+{
+	return kat_ksw_extend2(c, n, params, mat25, q, qoff, t, toff, out7, true);
 }
 
 int bwahip_kat_ksw_global(bwahip_ctx *c, int n, const int *params, const int8_t *mat25, const uint8_t *q, const int64_t *qoff, const uint8_t *t, const int64_t *toff,

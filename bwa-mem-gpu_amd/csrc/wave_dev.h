@@ -56,7 +56,9 @@ __device__ __forceinline__ int div_plus1_trunc(int x, int e)
 	return y >= 0 ? y / e : -((-y) / e);
 }
 
-struct Sw { const int8_t *mat; int o_del, e_del, o_ins, e_ins, mx, stop; };   // mx = largest entry of mat (ksw.c:399); stop: early stop of ksw_extend2 (0: off)
+// mx = largest entry of mat (ksw.c:399); stop: early stop of ksw_extend2 (0: off); diag: K of the diagonal rule of ksw_extend2 -- the
+// mismatches a flank it answers may hold (k_extend.hip, ext_diag_k) -- 0: off
+struct Sw { const int8_t *mat; int o_del, e_del, o_ins, e_ins, mx, stop, diag = 0; };
 
 __device__ __forceinline__ int dev_pos2rid(const DevIndex &ix, int64_t pos_f)   // bntseq.c:354
 {

@@ -925,7 +925,8 @@ const char *bwahip_kernel_name(int i);
  * calls of one read; [8..15] per-phase maxima over reads (10 ns ticks) and the largest seed / chain
  * counts of one read; [16,17] Occ blocks / intervals of k_smem_heavy, [24,25] of k_smem3 (both are
  * included in [1] and [4]; bench.py subtracts them to attribute bytes to k_smem); [19,20] DP rows
- * with one / several columns per lane; [21..23] dedup phase maxima.  n <= 32. */
+ * with one / several columns per lane; [21..23] dedup phase maxima; [27] ksw_extend2 calls of the extension
+ * kernels, [28] those the diagonal rule (knob ext_diag) answered without a DP row.  n <= 32. */
 int bwahip_batch_counters(bwahip_ctx *ctx, uint64_t *counters, int n);
 
 /* Known-answer helpers used by the parity tests: device Occ/extend/SA on arrays of inputs. */
@@ -961,6 +962,12 @@ int bwahip_kat_ksw_extend(bwahip_ctx *ctx, int n, const int *params /*n x 10*/, 
 #define BWAHIP_KAT_EXT_STOPPED  128   /* the loop ended because no later row could change a result (never with ext_early_stop = 0) */
 int bwahip_kat_ksw_extend2(bwahip_ctx *ctx, int n, const int *params /*n x 12*/, const int8_t *mat25 /*n x 25*/, const uint8_t *q, const int64_t *qoff,
                            const uint8_t *t, const int64_t *toff, int *out7 /*n x 7*/);
+/* The same call as the extension kernels make it: the windowed driver first tries the diagonal rule (knob ext_diag of the context, DESIGN.md
+ * section 4.6), which bwahip_kat_ksw_extend2 never applies -- its path bits and stop counts are those of the DP forms.  A call the rule
+ * answered reports BWAHIP_KAT_EXT_DIAG and no other path bit; with ext_diag = 0 no call reports it.  Arguments, results and errors as above. */
+#define BWAHIP_KAT_EXT_DIAG     256   /* the diagonal rule answered the call: no DP row ran (never with ext_diag = 0) */
+int bwahip_kat_ksw_extend2_diag(bwahip_ctx *ctx, int n, const int *params /*n x 12*/, const int8_t *mat25 /*n x 25*/, const uint8_t *q, const int64_t *qoff,
+                                const uint8_t *t, const int64_t *toff, int *out7 /*n x 7*/);
 
 /* ksw_global2 (ksw.c:504) with CIGAR through the code mem_reg2aln's kernels run (DP form by band and length, wavefront backtrack).
  * params: n x 10 ints (qlen, tlen, w, o_del, e_del, o_ins, e_ins, reverse, form, cpl); reverse = 1 reads both sequences backwards, as
@@ -1098,7 +1105,9 @@ int bwahip_kat_ksw_align(bwahip_ctx *ctx, int n, const int *params, const int8_t
 /* Tuning knobs of the heavy-read hand-off kernels (tests force each one onto ordinary reads): keys intv_cap,
  * smem_lanes, heavy_mult, chain_big_min, rank_sort_min, spec_min_chains, ext_lds_window, verbose; and ext_early_stop (default 1): every
  * device form of ksw_extend2 ends its row loop once no later row can change score, qle, tle, gtle, gscore or max_off --
- * 0 runs every row to the end as the reference does (same results, more rows); and sorted_piece_blocks (1 .. 4096, default 1024): the
+ * 0 runs every row to the end as the reference does (same results, more rows); and ext_diag (0 or 1, default 1): the extension kernels
+ * answer a ksw_extend2 call whose flank holds only ACGT and at most K mismatches (K = 1 at the default scores) from the main diagonal,
+ * without a DP row -- 0 runs the rows of every call (same results); and sorted_piece_blocks (1 .. 4096, default 1024): the
  * BGZF blocks a device merger gathers and deflates at a time (bwahip_bam_devmerger_open with piece_blocks <= 0; the bytes do not depend on it);
  * and incr_insert (0 or 1, default 1): mate rescue places a rescued region into a list that the last mem_sort_dedup_patch left free of
  * ties without sorting the list again -- 0 ends every orientation in the full sort-and-dedup, as the reference does.  The knob changes
