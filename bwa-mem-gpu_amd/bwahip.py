@@ -154,6 +154,7 @@ CHAIN_FLT_NONE, CHAIN_FLT_SEQ, CHAIN_FLT_WAVE = 0, 1, 2
 KAT_GLOBAL_AUTO_SMALL, KAT_GLOBAL_AUTO_BIG, KAT_GLOBAL_SCORE_ONLY = 0, 1, 2
 KAT_MAX_CIGAR = 512
 KAT_MARK_TAG, KAT_MARK_WORDS = 41, 25                       # bwahip_kat_mark's record: 4 header words, then 25 per region
+KAT_PAIR_TAG, KAT_PAIR_WORDS = 43, 22                       # bwahip_kat_pair's record: 12 header words, then 22 per region
 # bwahip_kat_dedup (bwahip.h): forms, and the diag word -- who finished the read, handed over, one-lane sorts, why k_dedup_fast refused, counts
 KAT_DEDUP_PRODUCT, KAT_DEDUP_FULL, KAT_DEDUP_SLAB = 0, 1, 2
 KAT_DEDUP_FAST, KAT_DEDUP_STAGED, KAT_DEDUP_GLOBAL, KAT_DEDUP_SLABBED, KAT_DEDUP_HANDED, KAT_DEDUP_LANE1, KAT_DEDUP_LANE2 = 1, 2, 4, 8, 16, 32, 64
@@ -334,6 +335,7 @@ def lib():
     L.bwahip_kat_chain.argtypes = [vp, C.POINTER(Opt), C.c_int, vp, vp, vp, vp, vp, C.POINTER(i64p), i64p, vp]
     L.bwahip_kat_dedup.argtypes = [vp, C.POINTER(Opt), C.c_int, vp, vp, vp, vp, vp, C.c_int, C.c_int, vp, vp, vp, C.POINTER(C.c_int32)]
     L.bwahip_kat_mark.argtypes = [vp, C.POINTER(Opt), C.c_int64, C.c_int, vp, vp, C.c_int, vp, C.c_int, C.POINTER(i64p), i64p]
+    L.bwahip_kat_pair.argtypes = [vp, C.POINTER(Opt), C.c_int64, C.c_int, vp, vp, C.POINTER(PeStat), vp, C.c_int, C.POINTER(i64p), i64p]
     L.bwahip_kat_occ4.argtypes = [vp, C.c_int, vp, vp]
     L.bwahip_index_footprint.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_uint64)]
     L.bwahip_kat_sa.argtypes = [vp, C.c_int, vp, vp]
@@ -963,6 +965,25 @@ class Context:
         out, m = C.POINTER(C.c_int64)(), C.c_int64()
         _check(lib().bwahip_kat_mark(self._h, C.byref(opt), n_processed, n, reg_off.ctypes.data, regs.ctypes.data, plan,
                                      None if pl is None else pl.ctypes.data, n_pairs, C.byref(out), C.byref(m)), "bwahip_kat_mark")
+        words = np.ctypeslib.as_array(out, shape=(m.value,)).copy() if m.value else np.zeros(0, dtype=np.int64)
+        C.CDLL(None).free(out)
+        return parse_records(words)
+
+    def kat_pair(self, reg_off, regs, pes, opt=None, n_processed=0, pairs=None):
+        """bwahip_kat_pair: mem_pair and the decisions of mem_sam_pe (k_pair) on caller region lists, reads 2p and 2p + 1 a pair -- regs
+        [m x 19] as for kat_mark, pes: (PeStat * 4) or None, pairs: the pair indices the second of the two launches takes.  -> records: per
+        read TAG_READ [i, n] and KAT_PAIR_TAG [the 8 words of STAGE_PAIR, n, n_pri, tasks, records, then KAT_PAIR_WORDS per region: the 19
+        words as k_pair left them, input index, need, XA owner]."""
+        opt = opt or default_opt()
+        reg_off = np.ascontiguousarray(reg_off, dtype=np.int64)
+        regs = np.ascontiguousarray(regs, dtype=np.int64).reshape(-1, 19)
+        n = len(reg_off) - 1
+        assert n >= 0 and (n == 0 or len(regs) >= reg_off[-1])
+        n_pairs = 0 if pairs is None else len(pairs)
+        pl = None if pairs is None else np.ascontiguousarray(list(pairs) + [0], dtype=np.int32)      # (never an empty array: its pointer says "a list was given")
+        out, m = C.POINTER(C.c_int64)(), C.c_int64()
+        _check(lib().bwahip_kat_pair(self._h, C.byref(opt), n_processed, n, reg_off.ctypes.data, regs.ctypes.data, pes,
+                                     None if pl is None else pl.ctypes.data, n_pairs, C.byref(out), C.byref(m)), "bwahip_kat_pair")
         words = np.ctypeslib.as_array(out, shape=(m.value,)).copy() if m.value else np.zeros(0, dtype=np.int64)
         C.CDLL(None).free(out)
         return parse_records(words)

@@ -87,6 +87,31 @@ static void pestat_from_hist(const bwahip_opt_t *opt, const std::vector<unsigned
 	for (int d = 0; d < 4; ++d) if (pes[d].failed == 0 && cnt[d] < (int)mx * 0.05) pes[d].failed = 1;   // MIN_DIR_RATIO
 }
 
+// The insert-size statistics as k_matesw and k_pair read them (PairLaunch::pes) and, per direction, .721 * log(2 * erfc(|ns| / sqrt 2)) for
+// every admissible distance (bwamem_pair.c:243-244), by the host's libm, uploaded as PairLaunch::pair_tab / tab_off.  widest: the largest
+// high - low of a live direction.  run_pe_rescue and bwahip_kat_pair both come through here.
+static int pair_stats(bwahip_ctx *c, const bwahip_pestat_t pes[4], PairLaunch &pl, int64_t &widest)
+{
+	std::vector<double> tab;
+	widest = 0;
+	for (int d = 0; d < 4; ++d) {
+		pl.pes[d].low = pes[d].low; pl.pes[d].high = pes[d].high; pl.pes[d].failed = pes[d].failed; pl.pes[d].pad = 0; pl.pes[d].avg = pes[d].avg; pl.pes[d].std = pes[d].std;
+		pl.tab_off[d] = (int)tab.size();
+		if (pes[d].failed || pes[d].high < pes[d].low) continue;
+		if ((int64_t)pes[d].high - pes[d].low > (1 << 26)) return BWAHIP_EINVAL;
+		widest = std::max<int64_t>(widest, (int64_t)pes[d].high - pes[d].low);
+		for (int64_t dist = pes[d].low; dist <= pes[d].high; ++dist) {
+			const double ns = (dist - pes[d].avg) / pes[d].std;
+			tab.push_back(.721 * log(2. * erfc(fabs(ns) * M_SQRT1_2)));
+		}
+	}
+	tab.push_back(0.);
+	const int rc = dev_upload(c->d_pair_tab, tab.data(), tab.size() * 8, c->stream);
+	if (rc) return rc;
+	pl.pair_tab = c->d_pair_tab.as<double>();
+	return 0;
+}
+
 // The paired-end stages before mark-primary: insert-size statistics, mate rescue.  Leaves the per-read lists in d_pe_regs.
 // Insert sizes, the lists of both ends, and mate rescue.  The rescue kernels (a handful of pairs, long dependent chains: the GPU is nearly idle
 // under them) go to the second stream and are NOT waited for: run_final finalises all other pairs meanwhile and the rescued ones after ev_join.
@@ -116,23 +141,8 @@ static int run_pe_rescue(bwahip_ctx *c, const bwahip_opt_t *opt, const DevOpt &d
 		pestat_from_hist(opt, h, pes);
 	}
 	memcpy(c->last_pes, pes, sizeof pes);
-	// per direction: .721 * log(2 * erfc(|ns| / sqrt 2)) for every admissible distance (bwamem_pair.c:243-244), by the host's libm
-	std::vector<double> tab;
 	int64_t widest = 0;
-	for (int d = 0; d < 4; ++d) {
-		pl.pes[d].low = pes[d].low; pl.pes[d].high = pes[d].high; pl.pes[d].failed = pes[d].failed; pl.pes[d].pad = 0; pl.pes[d].avg = pes[d].avg; pl.pes[d].std = pes[d].std;
-		pl.tab_off[d] = (int)tab.size();
-		if (pes[d].failed || pes[d].high < pes[d].low) continue;
-		if ((int64_t)pes[d].high - pes[d].low > (1 << 26)) return BWAHIP_EINVAL;
-		widest = std::max<int64_t>(widest, (int64_t)pes[d].high - pes[d].low);
-		for (int64_t dist = pes[d].low; dist <= pes[d].high; ++dist) {
-			const double ns = (dist - pes[d].avg) / pes[d].std;
-			tab.push_back(.721 * log(2. * erfc(fabs(ns) * M_SQRT1_2)));
-		}
-	}
-	tab.push_back(0.);
-	if ((rc = dev_upload(c->d_pair_tab, tab.data(), tab.size() * 8, c->stream))) return rc;
-	pl.pair_tab = c->d_pair_tab.as<double>();
+	if ((rc = pair_stats(c, pes, pl, widest))) return rc;
 	// list capacities after rescue
 	if ((rc = c->d_nb.ensure((size_t)n * 4)) || (rc = c->d_pe_cap.ensure((size_t)n * 4)) || (rc = c->d_pe_base.ensure((size_t)(n + 1) * 8)) || (rc = c->d_pe_n.ensure((size_t)n * 4)) ||
 	    (rc = c->d_resc.ensure((size_t)(n / 2 + 4) * 4)) || (rc = c->d_resc_flag.ensure((size_t)(n / 2 + 4))) || (rc = c->d_sw_cnt.ensure((size_t)n * 4)) || (rc = c->d_sw_base.ensure((size_t)(n + 1) * 8))) return rc;
@@ -205,6 +215,23 @@ static int mark_prepare(bwahip_ctx *c, const bwahip_opt_t *opt, int n, int64_t n
 	return 0;
 }
 
+// k_pair's view of the lists k_mark marked (`f`, after mark_prepare): the regions it updates, the spare array its bitonic sort borrows, the
+// scratch that holds v, the selection and the per-read answers; with dbg the per-pair record of mem_pair's results (zeroed here: a pair whose
+// u is empty leaves it alone).  run_final and bwahip_kat_pair both come through here.
+static int pair_wire(bwahip_ctx *c, const FinLaunch &f, int n, bool dbg, PairLaunch &pl)
+{
+	int rc;
+	if ((rc = c->d_pe_read.ensure((size_t)n * sizeof(PeRead)))) return rc;
+	pl.fregs = f.fregs; pl.fregs_w = f.fregs; pl.fregs_tmp = f.fregs2; pl.freg_n = f.freg_n; pl.n_pri = f.n_pri; pl.need = f.need; pl.xa_owner = f.xa_owner;
+	pl.task_n = f.task_n; pl.rec_n = f.rec_n; pl.scr = f.scr; pl.pe_read = c->d_pe_read.as<PeRead>();
+	if (dbg) {
+		if ((rc = c->d_pair_dbg.ensure((size_t)(n / 2) * 12))) return rc;
+		HIP_TRY(hipMemsetAsync(c->d_pair_dbg.p, 0, (size_t)(n / 2) * 12, c->stream));
+		pl.pair_dbg = c->d_pair_dbg.as<int>();
+	}
+	return 0;
+}
+
 // K6 -> K9 over the batch run_pipeline left in HBM.  The text inputs (d_qual, d_names, ...) must be uploaded.
 int run_final(bwahip_ctx *c, const bwahip_opt_t *opt, int64_t n_processed, const bwahip_pestat_t *pes0, bool timed, OutForm form, bool host_sam_off, bool pe_stage_stop)
 {
@@ -254,14 +281,7 @@ int run_final(bwahip_ctx *c, const bwahip_opt_t *opt, int64_t n_processed, const
 	if (pe) { f.resc_flag = pl.resc_flag; f.resc_pairs = pl.resc_list; f.subset = 1; }
 	if ((rc = launch_mark_primary(f, !pe, 0, c->stream))) return rc;
 	if (pe) {                                                     // mem_pair + the decisions of mem_sam_pe
-		if ((rc = c->d_pe_read.ensure((size_t)n * sizeof(PeRead)))) return rc;
-		pl.fregs = f.fregs; pl.fregs_w = f.fregs; pl.fregs_tmp = f.fregs2; pl.freg_n = f.freg_n; pl.n_pri = f.n_pri; pl.need = f.need; pl.xa_owner = f.xa_owner;
-		pl.task_n = f.task_n; pl.rec_n = f.rec_n; pl.scr = f.scr; pl.pe_read = c->d_pe_read.as<PeRead>();
-		if (pe_stage_stop) {
-			if ((rc = c->d_pair_dbg.ensure((size_t)(n / 2) * 12))) return rc;
-			HIP_TRY(hipMemsetAsync(c->d_pair_dbg.p, 0, (size_t)(n / 2) * 12, c->stream));
-			pl.pair_dbg = c->d_pair_dbg.as<int>();
-		}
+		if ((rc = pair_wire(c, f, n, pe_stage_stop, pl))) return rc;
 		pl.subset = 1;
 		if ((rc = launch_pair(pl, 0, c->stream))) return rc;
 		HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_join, 0));      // the rescue kernels (an event not recorded in this batch is complete: no wait)
@@ -803,6 +823,76 @@ extern "C" int bwahip_run_pe_stages(bwahip_ctx *c, const bwahip_opt_t *opt_in, i
 	return 0;
 }
 
+// The part bwahip_kat_mark and bwahip_kat_pair share: caller region lists checked, turned into DevReg and uploaded with exactly n slots per
+// read -- into k_extend's list buffers (pe_lists false) or into the paired-end list buffers mate rescue leaves (true) --, the marking buffers
+// and the launch record made by mark_prepare, and k_mark launched as run_final launches it: once, or with `pairs` twice (every pair but the
+// listed ones, then the listed ones; the pair list and its flags stay in d_resc / d_resc_flag for launch_pair).
+struct KatLists {
+	std::vector<DevReg> regs; std::vector<int> regn; std::vector<uint8_t> flag; std::vector<int> list;
+	int64_t total = 0;
+};
+static int kat_lists_check(const bwahip_ctx *c, int n, const int64_t *reg_off, const int64_t *reg_words, const int32_t *pairs, int n_pairs, KatLists &L)
+{
+	if (!reg_off || reg_off[0] != 0) return BWAHIP_EINVAL;
+	for (int i = 0; i < n; ++i) if (reg_off[i + 1] < reg_off[i] || reg_off[i + 1] - reg_off[i] > (1 << 24)) return BWAHIP_EINVAL;
+	const int64_t total = L.total = reg_off[n];
+	if (total > (1 << 26) || (total && !reg_words) || (n_pairs && !pairs)) return BWAHIP_EINVAL;
+	L.regs.assign((size_t)total + 1, DevReg());
+	L.regn.resize(n);
+	for (int i = 0; i < n; ++i) L.regn[i] = (int)(reg_off[i + 1] - reg_off[i]);
+	for (int64_t k = 0; k < total; ++k) {
+		const int64_t *w = reg_words + 19 * k;
+		if (w[3] < w[2] || w[1] < w[0] || w[4] < 0 || w[4] >= c->ix.n_seqs) return BWAHIP_EINVAL;
+		DevReg r; memset(&r, 0, sizeof r);
+		r.rb = w[0]; r.re = w[1]; r.qb = (int)w[2]; r.qe = (int)w[3]; r.rid = (int)w[4]; r.score = (int)w[5]; r.truesc = (int)w[6]; r.sub = (int)w[7]; r.csub = (int)w[9];
+		r.sub_n = (int)w[10]; r.w = (int)w[11]; r.seedcov = (int)w[12]; r.seedlen0 = (int)w[15]; r.n_comp = (int)w[16]; r.is_alt = (int)w[17];
+		const uint32_t u = (uint32_t)w[18]; memcpy(&r.frac_rep, &u, 4);
+		L.regs[(size_t)k] = r;
+	}
+	L.flag.assign((size_t)(n / 2 + 4), 0);
+	L.list.assign(pairs ? (size_t)n_pairs + 1 : 1, 0);
+	for (int k = 0; pairs && k < n_pairs; ++k) {
+		if (pairs[k] < 0 || pairs[k] >= n / 2 || L.flag[pairs[k]]) return BWAHIP_EINVAL;    // (a pair named twice would be marked by two workgroups at once)
+		L.flag[pairs[k]] = 1; L.list[k] = pairs[k];
+	}
+	return 0;
+}
+// queues on c->stream; sel0: the byte the selection's buffers start as (0xff where the launches must write them)
+static int kat_upload_mark(bwahip_ctx *c, const bwahip_opt_t *opt, int n, int64_t n_processed, const int64_t *reg_off, const KatLists &L, bool pe_lists, bool plan, int sel0,
+                           bool listed, int n_pairs, FinLaunch &f)
+{
+	int rc;
+	const size_t R = (size_t)(L.total ? L.total : 1);
+	c->total_regs = L.total;
+	DevBuf &d_r = pe_lists ? c->d_pe_regs : c->d_regs, &d_b = pe_lists ? c->d_pe_base : c->d_reg_base, &d_n = pe_lists ? c->d_pe_n : c->d_reg_n;
+	if ((rc = dev_upload(d_r, L.regs.data(), L.regs.size() * sizeof(DevReg), c->stream)) || (rc = dev_upload(d_b, reg_off, (size_t)(n + 1) * 8, c->stream)) ||
+	    (rc = dev_upload(d_n, L.regn.data(), (size_t)n * 4, c->stream)) || (rc = mark_prepare(c, opt, n, n_processed, pe_lists, f))) return rc;
+	// what k_mark<false> leaves alone comes back as zero; what a launch must write starts as 0xff, so that nothing a call before this one
+	// left in the context's buffers can pass for an answer
+	if (hipMemsetAsync(c->d_fregs.p, 0xff, R * sizeof(FinReg), c->stream) != hipSuccess || hipMemsetAsync(c->d_freg_n.p, 0xff, (size_t)n * 4, c->stream) != hipSuccess ||
+	    hipMemsetAsync(c->d_npri.p, 0xff, (size_t)n * 4, c->stream) != hipSuccess ||
+	    hipMemsetAsync(c->d_need.p, sel0, R, c->stream) != hipSuccess || hipMemsetAsync(c->d_xa_owner.p, sel0, R * 4, c->stream) != hipSuccess ||
+	    hipMemsetAsync(c->d_task_n.p, sel0, (size_t)n * 4, c->stream) != hipSuccess || hipMemsetAsync(c->d_rec_n.p, sel0, (size_t)n * 4, c->stream) != hipSuccess) return BWAHIP_ENODEV;
+	if (listed) {                                                // as run_final does for a paired-end batch: all pairs but the listed ones, then the listed ones
+		if ((rc = dev_upload(c->d_resc, L.list.data(), L.list.size() * 4, c->stream)) || (rc = dev_upload(c->d_resc_flag, L.flag.data(), L.flag.size(), c->stream))) return rc;
+		f.resc_flag = c->d_resc_flag.as<uint8_t>(); f.resc_pairs = c->d_resc.as<int>(); f.subset = 1;
+		if ((rc = launch_mark_primary(f, plan, 0, c->stream))) return rc;
+		if (n_pairs > 0) {
+			f.subset = 2;
+			if ((rc = launch_mark_primary(f, plan, n_pairs, c->stream))) return rc;
+		}
+		f.subset = 0;
+	} else if ((rc = launch_mark_primary(f, plan, 0, c->stream))) return rc;
+	return 0;
+}
+// hash -> index in the input list of read `id` (k_mark gives region k of the input the hash of id + k: a bijection)
+static inline uint64_t kat_hash_64(uint64_t key)                    // utils.h:97
+{
+	key += ~(key << 32); key ^= (key >> 22); key += ~(key << 13); key ^= (key >> 8);
+	key += (key << 3); key ^= (key >> 15); key += ~(key << 27); key ^= (key >> 31);
+	return key;
+}
+
 // Primary marking, -5, the selection and mapQ (k_mark, fin::select_records, fin::approx_mapq_se) on caller region lists; see bwahip.h.  The
 // buffers and the launch record are run_final's (mark_prepare), the launches are launch_mark_primary as run_final calls it -- one launch, or
 // with `pairs` the two of the paired-end path -- and only the region lists come from the caller.
@@ -813,29 +903,12 @@ extern "C" int bwahip_kat_mark(bwahip_ctx *c, const bwahip_opt_t *opt, int64_t n
 	*out = nullptr; *out_len = 0;
 	if (n_reads == 0) return 0;
 	const int n = n_reads;
-	if (!reg_off || reg_off[0] != 0) return BWAHIP_EINVAL;
 	if (((opt->flag & BWAHIP_F_PE) || pairs) && (n & 1)) return BWAHIP_EINVAL;
-	for (int i = 0; i < n; ++i) if (reg_off[i + 1] < reg_off[i] || reg_off[i + 1] - reg_off[i] > (1 << 24)) return BWAHIP_EINVAL;
-	const int64_t total = reg_off[n];
-	if (total > (1 << 26) || (total && !reg_words) || (n_pairs && !pairs)) return BWAHIP_EINVAL;
-	std::vector<DevReg> regs((size_t)total + 1);
-	std::vector<int> regn(n);
-	for (int i = 0; i < n; ++i) regn[i] = (int)(reg_off[i + 1] - reg_off[i]);
-	for (int64_t k = 0; k < total; ++k) {
-		const int64_t *w = reg_words + 19 * k;
-		if (w[3] < w[2] || w[1] < w[0] || w[4] < 0 || w[4] >= c->ix.n_seqs) return BWAHIP_EINVAL;
-		DevReg r; memset(&r, 0, sizeof r);
-		r.rb = w[0]; r.re = w[1]; r.qb = (int)w[2]; r.qe = (int)w[3]; r.rid = (int)w[4]; r.score = (int)w[5]; r.truesc = (int)w[6]; r.sub = (int)w[7]; r.csub = (int)w[9];
-		r.sub_n = (int)w[10]; r.w = (int)w[11]; r.seedcov = (int)w[12]; r.seedlen0 = (int)w[15]; r.n_comp = (int)w[16]; r.is_alt = (int)w[17];
-		const uint32_t u = (uint32_t)w[18]; memcpy(&r.frac_rep, &u, 4);
-		regs[(size_t)k] = r;
-	}
-	std::vector<uint8_t> flag((size_t)(n / 2 + 4), 0);
-	std::vector<int> list(pairs ? (size_t)n_pairs + 1 : 1, 0);
-	for (int k = 0; pairs && k < n_pairs; ++k) {
-		if (pairs[k] < 0 || pairs[k] >= n / 2 || flag[pairs[k]]) return BWAHIP_EINVAL;    // (a pair named twice would be marked by two workgroups at once)
-		flag[pairs[k]] = 1; list[k] = pairs[k];
-	}
+	KatLists L;
+	int rc;
+	if ((rc = kat_lists_check(c, n, reg_off, reg_words, pairs, n_pairs, L))) return rc;
+	const int64_t total = L.total;
+	const std::vector<int> &regn = L.regn;
 	HIP_TRY(hipSetDevice(c->device));
 	const size_t R = (size_t)(total ? total : 1);
 	std::vector<FinReg> h_f(R);
@@ -843,28 +916,8 @@ extern "C" int bwahip_kat_mark(bwahip_ctx *c, const bwahip_opt_t *opt, int64_t n
 	std::vector<int> h_own(R), h_mq(2 * R), h_fn(n), h_np(n), h_tn(n), h_rn(n);
 	DevBuf d_mq;
 	FinLaunch f;
-	int rc;
-	const int sel0 = plan ? 0xff : 0;
-	c->total_regs = total;
 	auto queue = [&]() -> int {                                  // the uploads, the launches, the copies back: the stream is awaited whatever this returns
-		if ((rc = dev_upload(c->d_regs, regs.data(), regs.size() * sizeof(DevReg), c->stream)) || (rc = dev_upload(c->d_reg_base, reg_off, (size_t)(n + 1) * 8, c->stream)) ||
-		    (rc = dev_upload(c->d_reg_n, regn.data(), (size_t)n * 4, c->stream)) || (rc = d_mq.ensure(R * 8)) || (rc = mark_prepare(c, opt, n, n_processed, false, f))) return rc;
-		// what k_mark<false> leaves alone comes back as zero; what a launch must write starts as 0xff, so that nothing a call before this one
-		// left in the context's buffers can pass for an answer
-		if (hipMemsetAsync(c->d_fregs.p, 0xff, R * sizeof(FinReg), c->stream) != hipSuccess || hipMemsetAsync(c->d_freg_n.p, 0xff, (size_t)n * 4, c->stream) != hipSuccess ||
-		    hipMemsetAsync(c->d_npri.p, 0xff, (size_t)n * 4, c->stream) != hipSuccess ||
-		    hipMemsetAsync(c->d_need.p, sel0, R, c->stream) != hipSuccess || hipMemsetAsync(c->d_xa_owner.p, sel0, R * 4, c->stream) != hipSuccess ||
-		    hipMemsetAsync(c->d_task_n.p, sel0, (size_t)n * 4, c->stream) != hipSuccess || hipMemsetAsync(c->d_rec_n.p, sel0, (size_t)n * 4, c->stream) != hipSuccess) return BWAHIP_ENODEV;
-		if (pairs) {                                                 // as run_final does for a paired-end batch: all pairs but the listed ones, then the listed ones
-			if ((rc = dev_upload(c->d_resc, list.data(), list.size() * 4, c->stream)) || (rc = dev_upload(c->d_resc_flag, flag.data(), flag.size(), c->stream))) return rc;
-			f.resc_flag = c->d_resc_flag.as<uint8_t>(); f.resc_pairs = c->d_resc.as<int>(); f.subset = 1;
-			if ((rc = launch_mark_primary(f, plan != 0, 0, c->stream))) return rc;
-			if (n_pairs > 0) {
-				f.subset = 2;
-				if ((rc = launch_mark_primary(f, plan != 0, n_pairs, c->stream))) return rc;
-			}
-			f.subset = 0;
-		} else if ((rc = launch_mark_primary(f, plan != 0, 0, c->stream))) return rc;
+		if ((rc = d_mq.ensure(R * 8)) || (rc = kat_upload_mark(c, opt, n, n_processed, reg_off, L, false, plan != 0, plan ? 0xff : 0, pairs != nullptr, n_pairs, f))) return rc;
 		if ((rc = launch_kat_mapq(f, total, d_mq.as<int>(), c->stream))) return rc;
 		if ((total && (hipMemcpyAsync(h_f.data(), c->d_fregs.p, (size_t)total * sizeof(FinReg), hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
 		               hipMemcpyAsync(h_need.data(), c->d_need.p, (size_t)total, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
@@ -879,11 +932,7 @@ extern "C" int bwahip_kat_mark(bwahip_ctx *c, const bwahip_opt_t *opt, int64_t n
 	rc = queue();
 	if (hipStreamSynchronize(c->stream) != hipSuccess && !rc) rc = BWAHIP_ENODEV;
 	if (rc) return rc;
-	auto hash_64 = [](uint64_t key) {                             // utils.h:97
-		key += ~(key << 32); key ^= (key >> 22); key += ~(key << 13); key ^= (key >> 8);
-		key += (key << 3); key ^= (key >> 15); key += ~(key << 27); key ^= (key >> 31);
-		return key;
-	};
+	auto hash_64 = kat_hash_64;
 	std::vector<int64_t> o, v;
 	std::vector<std::pair<uint64_t, int>> by_hash;
 	for (int i = 0; i < n; ++i) {
@@ -907,6 +956,100 @@ extern "C" int bwahip_kat_mark(bwahip_ctx *c, const bwahip_opt_t *opt, int64_t n
 			v.insert(v.end(), w, w + BWAHIP_KAT_MARK_WORDS);
 		}
 		stage_rec(o, BWAHIP_KAT_MARK_TAG, v);
+	}
+	*out = (int64_t*)malloc(o.size() * 8 + 8);
+	if (!*out) return BWAHIP_ENOMEM;
+	memcpy(*out, o.data(), o.size() * 8);
+	*out_len = (int64_t)o.size();
+	return 0;
+}
+
+// mem_pair and the decisions of mem_sam_pe (k_pair) on caller region lists; see bwahip.h.  The lists go into the paired-end list buffers,
+// are marked as the paired-end path marks them (kat_upload_mark) and paired by launch_pair with the same subsets; the statistics, the penalty
+// table (pair_stats) and the wiring of the launch record (pair_wire) are run_final's.
+extern "C" int bwahip_kat_pair(bwahip_ctx *c, const bwahip_opt_t *opt0, int64_t n_processed, int n_reads, const int64_t *reg_off, const int64_t *reg_words,
+                               const bwahip_pestat_t *pes, const int32_t *pairs, int n_pairs, int64_t **out, int64_t *out_len)
+{
+	if (!c || !opt0 || n_reads < 0 || !out || !out_len || n_pairs < 0 || n_processed < 0 || !pes) return BWAHIP_EINVAL;
+	*out = nullptr; *out_len = 0;
+	if (n_reads == 0) return 0;
+	const int n = n_reads;
+	if (n & 1) return BWAHIP_EINVAL;
+	bwahip_opt_t opt = *opt0;
+	opt.flag |= BWAHIP_F_PE;
+	for (int d = 0; d < 4; ++d) if (!pes[d].failed && pes[d].high >= pes[d].low && (int64_t)pes[d].high - pes[d].low > (1 << 26)) return BWAHIP_EINVAL;
+	KatLists L;
+	int rc;
+	if ((rc = kat_lists_check(c, n, reg_off, reg_words, pairs, n_pairs, L))) return rc;
+	const int64_t total = L.total;
+	HIP_TRY(hipSetDevice(c->device));
+	const size_t R = (size_t)(total ? total : 1);
+	std::vector<FinReg> h_f(R);
+	std::vector<uint8_t> h_need(R);
+	std::vector<int> h_own(R), h_fn(n), h_np(n), h_tn(n), h_rn(n), h_dbg((size_t)(n / 2) * 3);
+	std::vector<PeRead> h_pr(n);
+	FinLaunch f;
+	PairLaunch pl;
+	int err = 0;
+	auto queue = [&]() -> int {                                  // the uploads, the launches, the copies back: the stream is awaited whatever this returns
+		if (hipMemsetAsync(c->d_fmisc.p, 0, 256, c->stream) != hipSuccess) return BWAHIP_ENODEV;
+		if ((rc = kat_upload_mark(c, &opt, n, n_processed, reg_off, L, true, false, 0xff, pairs != nullptr, n_pairs, f))) return rc;
+		memset(&pl, 0, sizeof pl);
+		pl.ix = c->ix; pl.opt = make_dev_opt(&opt); pl.n_reads = n; pl.n_processed = n_processed; pl.logtab = c->d_logtab.as<double>();
+		pl.pe_base = c->d_pe_base.as<int64_t>(); pl.pe_regs = c->d_pe_regs.as<DevReg>(); pl.pe_n = c->d_pe_n.as<int>();
+		pl.err = (int*)(c->d_fmisc.as<unsigned long long>() + 2);
+		int64_t widest;
+		if ((rc = pair_stats(c, pes, pl, widest)) || (rc = pair_wire(c, f, n, true, pl))) return rc;
+		if (hipMemsetAsync(c->d_pe_read.p, 0xff, (size_t)n * sizeof(PeRead), c->stream) != hipSuccess) return BWAHIP_ENODEV;
+		if (pairs) {
+			pl.resc_flag = c->d_resc_flag.as<uint8_t>(); pl.resc_list = c->d_resc.as<int>(); pl.subset = 1;
+			if ((rc = launch_pair(pl, 0, c->stream))) return rc;
+			if (n_pairs > 0) {
+				pl.subset = 2;
+				if ((rc = launch_pair(pl, n_pairs, c->stream))) return rc;
+			}
+			pl.subset = 0;
+		} else if ((rc = launch_pair(pl, 0, c->stream))) return rc;
+		if ((total && (hipMemcpyAsync(h_f.data(), c->d_fregs.p, (size_t)total * sizeof(FinReg), hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+		               hipMemcpyAsync(h_need.data(), c->d_need.p, (size_t)total, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+		               hipMemcpyAsync(h_own.data(), c->d_xa_owner.p, (size_t)total * 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess)) ||
+		    hipMemcpyAsync(h_fn.data(), c->d_freg_n.p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+		    hipMemcpyAsync(h_np.data(), c->d_npri.p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+		    hipMemcpyAsync(h_tn.data(), c->d_task_n.p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+		    hipMemcpyAsync(h_rn.data(), c->d_rec_n.p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+		    hipMemcpyAsync(h_pr.data(), c->d_pe_read.p, (size_t)n * sizeof(PeRead), hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+		    hipMemcpyAsync(h_dbg.data(), c->d_pair_dbg.p, h_dbg.size() * 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+		    hipMemcpyAsync(&err, pl.err, 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess) return BWAHIP_ENODEV;
+		return 0;
+	};
+	rc = queue();
+	if (hipStreamSynchronize(c->stream) != hipSuccess && !rc) rc = BWAHIP_ENODEV;
+	if (rc) return rc;
+	if (err) { fprintf(stderr, "[bwahip] paired-end kernels reported code %d\n", err); return BWAHIP_EINTERNAL; }
+	std::vector<int64_t> o, v;
+	std::vector<std::pair<uint64_t, int>> by_hash;
+	for (int i = 0; i < n; ++i) {
+		const int m = L.regn[i];
+		if (h_fn[i] != m) return BWAHIP_EINTERNAL;
+		const uint64_t id = (((uint64_t)n_processed >> 1) + (uint64_t)(i >> 1)) << 1 | (uint64_t)(i & 1);
+		by_hash.clear();
+		for (int k = 0; k < m; ++k) by_hash.emplace_back(kat_hash_64(id + (uint64_t)k), k);
+		std::sort(by_hash.begin(), by_hash.end());
+		v = { (int64_t)i, (int64_t)m };
+		stage_rec(o, 100, v);
+		const PeRead &q = h_pr[i];
+		const int *g = &h_dbg[(size_t)(i >> 1) * 3];
+		v = { q.mode, q.h_reg, q.alt_reg, q.mapq, q.extra_flag, g[0], g[1], g[2], (int64_t)m, (int64_t)h_np[i], (int64_t)h_tn[i], (int64_t)h_rn[i] };
+		for (int k = 0; k < m; ++k) {
+			const size_t s = (size_t)reg_off[i] + k;
+			const FinReg &p = h_f[s];
+			uint32_t u; memcpy(&u, &p.frac_rep, 4);
+			const auto it = std::lower_bound(by_hash.begin(), by_hash.end(), std::make_pair(p.hash, 0));
+			const int64_t w[BWAHIP_KAT_PAIR_WORDS] = { p.rb, p.re, p.qb, p.qe, p.rid, p.score, p.truesc, p.sub, p.alt_sc, p.csub, p.sub_n, p.w, p.seedcov, p.secondary, p.secondary_all,
+			                                           p.seedlen0, p.n_comp, p.is_alt, (int64_t)u, it != by_hash.end() && it->first == p.hash ? it->second : -1, h_need[s], h_own[s] };
+			v.insert(v.end(), w, w + BWAHIP_KAT_PAIR_WORDS);
+		}
+		stage_rec(o, BWAHIP_KAT_PAIR_TAG, v);
 	}
 	*out = (int64_t*)malloc(o.size() * 8 + 8);
 	if (!*out) return BWAHIP_ENOMEM;

@@ -1047,6 +1047,24 @@ int bwahip_kat_chain(bwahip_ctx *ctx, const bwahip_opt_t *opt, int n_reads, cons
 int bwahip_kat_mark(bwahip_ctx *ctx, const bwahip_opt_t *opt, int64_t n_processed, int n_reads, const int64_t *reg_off, const int64_t *reg_words,
                     int plan, const int32_t *pairs, int n_pairs, int64_t **out, int64_t *out_len);
 
+/* mem_pair (bwamem_pair.c:208-272) and the decisions of mem_sam_pe (bwamem_pair.c:303-365, 397-411) through k_pair of csrc/k_pair.hip, on
+ * caller region lists.  Reads 2p and 2p + 1 form pair p (id n_processed / 2 + p); BWAHIP_F_PE is implied.  The lists (as for
+ * bwahip_kat_mark) are laid into the paired-end list buffers with exactly n slots per read -- the tightest layout: the 16 bytes of scratch
+ * per slot hold v, the spare region array the keys of the bitonic sort --, marked by k_mark exactly as the paired-end path marks them (one
+ * launch; with pairs the two launches: every pair but the listed ones, then the listed ones) and paired by k_pair with the same subsets.
+ * pes[4]: the insert-size statistics per orientation as mem_pestat would give them; the penalty table is made from them as in the product.
+ * *out: a malloc()ed stream of i64 records, per read [100: i, n] and [BWAHIP_KAT_PAIR_TAG: the 8 words of BWAHIP_STAGE_PAIR, n, n_pri,
+ * regions with an alignment task, regions with a record, then BWAHIP_KAT_PAIR_WORDS words per region in the final order: the 19 words of
+ * a stage record as k_pair left them (sub, secondary, secondary_all), the index the region had in the input list, need (1: prints a
+ * record, 2: listed in the XA tag of a printed record, 4: only the mate information of the other end), the region whose XA tag lists it
+ * or -1].  Everything a launch must write starts as 0xff.
+ * BWAHIP_EINVAL: what bwahip_kat_mark refuses, pes == NULL, an odd n_reads, a live orientation with high - low above 2^26.
+ * BWAHIP_EINTERNAL: an error code from the kernels (61: n_sub + 1 beyond the log table, 62: a span beyond it).  n_reads == 0 launches nothing. */
+#define BWAHIP_KAT_PAIR_TAG   43
+#define BWAHIP_KAT_PAIR_WORDS 22
+int bwahip_kat_pair(bwahip_ctx *ctx, const bwahip_opt_t *opt, int64_t n_processed, int n_reads, const int64_t *reg_off, const int64_t *reg_words,
+                    const bwahip_pestat_t pes[4], const int32_t *pairs, int n_pairs, int64_t **out, int64_t *out_len);
+
 /* mem_sort_dedup_patch (bwamem.c:444-496, with mem_patch_reg bwamem.c:413) and the is_alt marking of bwamem.c:1091-1095 through the
  * dedup kernels of csrc/k_extend.hip, on caller region lists.  Read i has the bases seq[off[i] .. off[i + 1]) (codes 0..4; mem_patch_reg
  * aligns the query) and the regions reg_words[19 * reg_off[i] .. 19 * reg_off[i + 1]), 19 words per region in the layout of

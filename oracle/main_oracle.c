@@ -6,6 +6,7 @@
  *   bwa_oracle katchain [options] <prefix> <cases.bin> <out.bin>             chains of caller-supplied seed lists
  *   bwa_oracle katdedup [options] <prefix> <cases.bin> <out.bin>             mem_sort_dedup_patch and the is_alt marking of caller-supplied region lists
  *   bwa_oracle katmark [options] <prefix> <cases.bin> <out.bin>              primary marking, selection and mapQ of caller-supplied region lists
+ *   bwa_oracle katpair [options] <prefix> <cases.bin> <out.bin>              mem_pair and mem_sam_pe's decisions on caller-supplied pairs of region lists
  * Batching follows bseq_read (bwa.c:191): reads are taken until the batch holds
  * >= chunk bases and an even number of reads.
  */
@@ -25,6 +26,7 @@ static double now_s(void) { struct timeval tv; gettimeofday(&tv, 0); return tv.t
 #include "opt_parse.h"
 #include "kat_mark_io.h"
 #include "kat_dedup_io.h"
+#include "kat_pair_io.h"
 
 /* ---- minimal FASTA/FASTQ reader with kseq.h's field semantics ---- */
 typedef struct { gzFile fp; char *line; size_t m; int peeked; } fq_t;
@@ -345,6 +347,52 @@ static int main_katdedup(int argc, char **argv)
 	return rc ? 1 : 0;
 }
 
+/* katpair [options] <prefix> <cases.bin> <out.bin>: ora_kat_pair on caller pairs of region lists over the contig table of the index
+ * (kat_pair_io.h has both file formats). */
+static int main_katpair(int argc, char **argv)
+{
+	ora_opt_t opt;
+	ora_index_t *idx;
+	optparse_t op;
+	kp_file_t k;
+	FILE *in, *out;
+	const int64_t *regs[2];
+	int64_t i[2], *marked[2] = { 0, 0 }, *rec[2] = { 0, 0 }, pair5[5], extra[ORA_KAT_PAIR_EXTRA];
+	int c, n[2], rc, e;
+	ora_opt_init(&opt);
+	optparse_init(&op, &opt);
+	while ((c = getopt(argc, argv, OPT_GETOPT_STRING)) >= 0) if (optparse_one(&op, c, optarg)) return 1;
+	if (optparse_finish(&op) || optind + 3 > argc) return 1;
+	idx = ora_index_load(argv[optind]);
+	if (!idx) return 1;
+	in = fopen(argv[optind + 1], "rb"); out = fopen(argv[optind + 2], "wb");
+	if (!in || !out || kp_read_opt(in, &opt, &k)) { fprintf(stderr, "[bwa_oracle] katpair: cannot open the files, or no option record\n"); return 1; }
+	while ((rc = kp_next_pair(in, &k, i, n, regs)) > 0) {
+		for (e = 0; e < 2; ++e) {
+			int j;
+			marked[e] = (int64_t*)realloc(marked[e], (2 + (size_t)KM_REG_WORDS * n[e]) * 8);
+			rec[e] = (int64_t*)realloc(rec[e], (KP_OUT_HDR + (size_t)KP_OUT_WORDS * n[e]) * 8);
+			for (j = 0; j < n[e]; ++j) if (regs[e][KM_REG_WORDS * j + 4] < 0 || regs[e][KM_REG_WORDS * j + 4] >= idx->ref->n_seqs) rc = -1;
+		}
+		if (rc < 0) break;
+		ora_kat_pair(&opt, idx->ref, k.pes, (k.n_processed >> 1) + (i[0] >> 1), n, regs, marked, rec, pair5, extra);
+		for (e = 0; e < 2; ++e) {
+			int64_t hdr[2];
+			hdr[0] = i[e]; hdr[1] = n[e];
+			rec_write(out, TAG_READ, 2, hdr);
+			rec_write(out, KP_TAG_MARKED, 2 + (int64_t)KM_REG_WORDS * n[e], marked[e]);
+			rec_write(out, KP_TAG_PAIR, KP_OUT_HDR + (int64_t)KP_OUT_WORDS * n[e], rec[e]);
+			if (e == 0) { rec_write(out, KP_TAG_MEMPAIR, 5, pair5); rec_write(out, KP_TAG_EXTRA, ORA_KAT_PAIR_EXTRA, extra); }
+		}
+	}
+	for (e = 0; e < 2; ++e) { free(marked[e]); free(rec[e]); }
+	kp_free(&k);
+	fclose(in); fclose(out);
+	ora_index_destroy(idx);
+	if (rc) fprintf(stderr, "[bwa_oracle] katpair: malformed case file\n");
+	return rc ? 1 : 0;
+}
+
 static int main_mem(int argc, char **argv)
 {
 	ora_opt_t opt;
@@ -393,6 +441,7 @@ int main(int argc, char **argv)
 	if (argc >= 2 && strcmp(argv[1], "katchain") == 0) return main_katchain(argc - 1, argv + 1);
 	if (argc >= 2 && strcmp(argv[1], "katmark") == 0) return main_katmark(argc - 1, argv + 1);
 	if (argc >= 2 && strcmp(argv[1], "katdedup") == 0) return main_katdedup(argc - 1, argv + 1);
-	fprintf(stderr, "usage: bwa_oracle <mem|stages|katchain|katmark|katdedup> ...\n");
+	if (argc >= 2 && strcmp(argv[1], "katpair") == 0) return main_katpair(argc - 1, argv + 1);
+	fprintf(stderr, "usage: bwa_oracle <mem|stages|katchain|katmark|katdedup|katpair> ...\n");
 	return 1;
 }

@@ -85,6 +85,18 @@ int ora_matesw(const ora_opt_t *opt, const ora_ref_t *r, const ora_pestat_t pes[
 int ora_kat_mate_insert(int max_chain_gap, float mask_level_redun, int n, const int64_t *start19, int n_steps, const int *hit, const int64_t *step19, int64_t *out19);   /* test helper: the list update of ora_matesw on a caller's list */
 int ora_pair(const ora_opt_t *opt, const ora_ref_t *r, const ora_pestat_t pes[4], ora_read_t s[2], ora_reg_v a[2], int id, int *sub, int *n_sub, int z[2], int n_pri[2]); /* bwamem_pair.c:208 */
 int ora_sam_pe(const ora_opt_t *opt, const ora_ref_t *r, const ora_pestat_t pes[4], uint64_t id, ora_read_t s[2], ora_reg_v a[2]); /* bwamem_pair.c:276 */
+typedef struct { int nv, n_u, zraw[2], best[2], second[2]; } ora_pair_stat_t;    /* sizes of v and u, z[] as mem_pair set it (-1: not), (k, i) of u's two largest (-1: none) */
+int ora_pair_ex(const ora_opt_t *opt, const ora_ref_t *r, const ora_pestat_t pes[4], ora_read_t s[2], ora_reg_v a[2], int id, int *sub, int *n_sub, int z[2], int n_pri[2], ora_pair_stat_t *st);
+typedef struct {
+	int paired, z[2], alt[2], q_se[2], extra_flag;          /* paired: z[i] and the ALT hit print, with q_se[i]; else z[i] is the region h[i] is made of (-1: none) */
+	int ran, o, subo, n_sub;                                /* mem_pair ran; what it returned (0 when it did not run) */
+	int has_un, o_un, is_multi, n_reparent;                 /* o - score_un where it was compared; is_multi[0] | is_multi[1] << 1; ends whose secondary_all was re-parented */
+	ora_pair_stat_t st;
+} ora_pe_dec_t;
+void ora_pe_decide(const ora_opt_t *opt, const ora_ref_t *r, const ora_pestat_t pes[4], uint64_t id, ora_reg_v a[2], int n_pri[2], ora_pe_dec_t *d);   /* the decisions of bwamem_pair.c:311-365, 397-411 */
+enum { ORA_KAT_PAIR_EXTRA = 10 };
+void ora_kat_pair(const ora_opt_t *opt, const ora_ref_t *r, const ora_pestat_t pes[4], int64_t pair_id, const int n[2], const int64_t *const regs19[2],
+                  int64_t *marked[2], int64_t *out[2], int64_t pair5[5], int64_t extra[ORA_KAT_PAIR_EXTRA]);   /* test helper: marking, mem_pair and mem_sam_pe's decisions on two callers' region lists */
 
 /* Stage records of the paired-end path (`bwa_oracle stages` with two read files).  While ora_pe_dump is NULL -- always in `mem`
  * mode -- nothing is recorded.  Otherwise ora_process_seqs stores the batch's insert-size statistics and ora_sam_pe, per read of the

@@ -200,8 +200,9 @@ int ora_kat_mate_insert(int max_chain_gap, float mask_level_redun, int n, const 
 	return n;
 }
 
-int ora_pair(const ora_opt_t *opt, const ora_ref_t *ref, const ora_pestat_t pes[4], ora_read_t s[2], ora_reg_v a[2], int id,
-             int *sub, int *n_sub, int z[2], int n_pri[2])   /* bwamem_pair.c:208 */
+/* st (may be NULL): what a test wants to know beyond mem_pair's results -- the sizes of v and u, the (k, i) of u's two largest elements */
+int ora_pair_ex(const ora_opt_t *opt, const ora_ref_t *ref, const ora_pestat_t pes[4], ora_read_t s[2], ora_reg_v a[2], int id,
+                int *sub, int *n_sub, int z[2], int n_pri[2], ora_pair_stat_t *st)   /* bwamem_pair.c:208 */
 {
 	struct { size_t n, m; ora_pair64_t *a; } v = { 0, 0, 0 }, u = { 0, 0, 0 };
 	int r, i, k, y[4], ret;
@@ -251,6 +252,10 @@ int ora_pair(const ora_opt_t *opt, const ora_ref_t *ref, const ora_pestat_t pes[
 		tmp = tmp > opt->o_del + opt->e_del ? tmp : opt->o_del + opt->e_del;
 		tmp = tmp > opt->o_ins + opt->e_ins ? tmp : opt->o_ins + opt->e_ins;
 		ora_sort_pair64(u.n, u.a);
+		if (st) {
+			st->best[0] = (int)(u.a[u.n-1].y >> 32); st->best[1] = (int)(u.a[u.n-1].y & 0xffffffffU);
+			if (u.n > 1) { st->second[0] = (int)(u.a[u.n-2].y >> 32); st->second[1] = (int)(u.a[u.n-2].y & 0xffffffffU); }
+		}
 		i = u.a[u.n-1].y >> 32; k = u.a[u.n-1].y << 32 >> 32;
 		z[v.a[i].y & 1] = v.a[i].y << 32 >> 34;
 		z[v.a[k].y & 1] = v.a[k].y << 32 >> 34;
@@ -259,8 +264,15 @@ int ora_pair(const ora_opt_t *opt, const ora_ref_t *ref, const ora_pestat_t pes[
 		for (i = (long)u.n - 2, *n_sub = 0; i >= 0; --i)
 			if (*sub - (int)(u.a[i].x >> 32) <= tmp) ++*n_sub;
 	} else ret = 0, *sub = 0, *n_sub = 0;
+	if (st) { st->nv = (int)v.n; st->n_u = (int)u.n; }
 	free(u.a); free(v.a);
 	return ret;
+}
+
+int ora_pair(const ora_opt_t *opt, const ora_ref_t *ref, const ora_pestat_t pes[4], ora_read_t s[2], ora_reg_v a[2], int id,
+             int *sub, int *n_sub, int z[2], int n_pri[2])   /* bwamem_pair.c:208 */
+{
+	return ora_pair_ex(opt, ref, pes, s, a, id, sub, n_sub, z, n_pri, 0);
 }
 
 #define RAW_MAPQ(diff, a) ((int)(6.02 * (diff) / (a) + .499))   /* bwamem_pair.c:274 */
@@ -286,11 +298,93 @@ static void dump_pair(uint64_t id, int paired, const int z[2], const int alt[2],
 	}
 }
 
+/* The decisions of mem_sam_pe between the marked lists and the records (bwamem_pair.c:311-365, 397-411), in one place for ora_sam_pe and
+ * ora_kat_pair: mem_pair, is_multi, score_un, q_pe, q_se, the sub adopted from a secondary z[i], the re-parenting of secondary_all, the
+ * ALT hit printed beside z[i], and the no-pairing branch's choice of h[i].  a[]: marked (and, under -5, reordered) lists; updated as
+ * mem_sam_pe updates them. */
+void ora_pe_decide(const ora_opt_t *opt, const ora_ref_t *ref, const ora_pestat_t pes[4], uint64_t id, ora_reg_v a[2], int n_pri[2], ora_pe_dec_t *d)
+{
+	int i, j, z[2];
+	memset(d, 0, sizeof *d);
+	d->extra_flag = 1;
+	d->alt[0] = d->alt[1] = -1;
+	d->st.zraw[0] = d->st.zraw[1] = -1;
+	d->st.best[0] = d->st.best[1] = d->st.second[0] = d->st.second[1] = -1;
+	if (!(opt->flag & ORA_F_NOPAIRING) && n_pri[0] && n_pri[1]) {
+		int subo, is_multi[2];
+		z[0] = z[1] = -1;
+		d->ran = 1;
+		d->o = ora_pair_ex(opt, ref, pes, 0, a, (int)id, &d->subo, &d->n_sub, z, n_pri, &d->st);
+		d->st.zraw[0] = z[0]; d->st.zraw[1] = z[1];
+		subo = d->subo;
+		for (i = 0; i < 2; ++i) {
+			for (j = 1; j < n_pri[i]; ++j)
+				if (a[i].a[j].secondary < 0 && a[i].a[j].score >= opt->T) break;
+			is_multi[i] = j < n_pri[i] ? 1 : 0;
+		}
+		d->is_multi = is_multi[0] | is_multi[1] << 1;
+		if (d->o > 0 && !is_multi[0] && !is_multi[1]) {
+			int q_pe, score_un, q_se[2], o = d->o, n_sub = d->n_sub;
+			d->paired = 1;
+			score_un = a[0].a[0].score + a[1].a[0].score - opt->pen_unpaired;
+			d->has_un = 1; d->o_un = o - score_un;
+			subo = subo > score_un ? subo : score_un;
+			q_pe = RAW_MAPQ(o - subo, opt->a);
+			if (n_sub > 0) q_pe -= (int)(4.343 * log(n_sub + 1) + .499);
+			if (q_pe < 0) q_pe = 0;
+			if (q_pe > 60) q_pe = 60;
+			q_pe = (int)(q_pe * (1. - .5 * (a[0].a[0].frac_rep + a[1].a[0].frac_rep)) + .499);
+			if (o > score_un) {
+				ora_reg_t *c[2];
+				c[0] = &a[0].a[z[0]]; c[1] = &a[1].a[z[1]];
+				for (i = 0; i < 2; ++i) {
+					if (c[i]->secondary >= 0) c[i]->sub = a[i].a[c[i]->secondary].score, c[i]->secondary = -2;
+					q_se[i] = ora_approx_mapq_se(opt, c[i]);
+				}
+				q_se[0] = q_se[0] > q_pe ? q_se[0] : q_pe < q_se[0] + 40 ? q_pe : q_se[0] + 40;
+				q_se[1] = q_se[1] > q_pe ? q_se[1] : q_pe < q_se[1] + 40 ? q_pe : q_se[1] + 40;
+				d->extra_flag |= 2;
+				q_se[0] = q_se[0] < RAW_MAPQ(c[0]->score - c[0]->csub, opt->a) ? q_se[0] : RAW_MAPQ(c[0]->score - c[0]->csub, opt->a);
+				q_se[1] = q_se[1] < RAW_MAPQ(c[1]->score - c[1]->csub, opt->a) ? q_se[1] : RAW_MAPQ(c[1]->score - c[1]->csub, opt->a);
+			} else {
+				z[0] = z[1] = 0;
+				q_se[0] = ora_approx_mapq_se(opt, &a[0].a[0]);
+				q_se[1] = ora_approx_mapq_se(opt, &a[1].a[0]);
+			}
+			for (i = 0; i < 2; ++i) {
+				int k = a[i].a[z[i]].secondary_all;
+				if (k >= 0 && k < n_pri[i]) {
+					assert(a[i].a[k].secondary_all < 0);
+					for (j = 0; j < a[i].n; ++j)
+						if (a[i].a[j].secondary_all == k || j == k) a[i].a[j].secondary_all = z[i];
+					a[i].a[z[i]].secondary_all = -1;
+					++d->n_reparent;
+				}
+			}
+			for (i = 0; i < 2; ++i) {
+				const ora_reg_t *p = &a[i].a[n_pri[i]];
+				d->alt[i] = n_pri[i] < a[i].n && !(p->score < opt->T || p->secondary >= 0 || !p->is_alt) ? n_pri[i] : -1;
+				d->z[i] = z[i]; d->q_se[i] = q_se[i];
+			}
+			return;
+		}
+	}
+	for (i = 0; i < 2; ++i) {                                   /* no pairing (bwamem_pair.c:397-411): the region h[i] is made of */
+		int which = -1;
+		if (a[i].n) {
+			if (a[i].a[0].score >= opt->T) which = 0;
+			else if (n_pri[i] < a[i].n && a[i].a[n_pri[i]].score >= opt->T) which = n_pri[i];
+		}
+		d->z[i] = which;
+	}
+}
+
 int ora_sam_pe(const ora_opt_t *opt, const ora_ref_t *ref, const ora_pestat_t pes[4], uint64_t id, ora_read_t s[2], ora_reg_v a[2])   /* bwamem_pair.c:276 */
 {
-	int n = 0, i, j, z[2], o = 0, subo = 0, n_sub = 0, subo_pair = 0, extra_flag = 1, n_pri[2], n_aa[2];
+	int n = 0, i, j, n_pri[2], n_aa[2];
 	ora_str_t str = { 0, 0, 0 };
 	ora_aln_t h[2], g[2], aa[2][2];
+	ora_pe_dec_t d;
 	memset(h, 0, sizeof h); memset(g, 0, sizeof g);
 	n_aa[0] = n_aa[1] = 0;
 	if (ora_pe_dump) dump_lists(ora_pe_dump->se, id, a);
@@ -311,73 +405,23 @@ int ora_sam_pe(const ora_opt_t *opt, const ora_ref_t *ref, const ora_pestat_t pe
 	n_pri[0] = ora_mark_primary_se(opt, a[0].n, a[0].a, id << 1 | 0);
 	n_pri[1] = ora_mark_primary_se(opt, a[1].n, a[1].a, id << 1 | 1);
 	if (opt->flag & ORA_F_PRIMARY5) { ora_reorder_primary5(opt->T, &a[0]); ora_reorder_primary5(opt->T, &a[1]); }
-	if (opt->flag & ORA_F_NOPAIRING) goto no_pairing;
-	if (n_pri[0] && n_pri[1] && (o = ora_pair(opt, ref, pes, s, a, (int)id, &subo, &n_sub, z, n_pri)) > 0) {
-		int is_multi[2], q_pe, score_un, q_se[2];
+	ora_pe_decide(opt, ref, pes, id, a, n_pri, &d);
+	if (d.paired) {
 		char **XA[2];
-		subo_pair = subo;
-		for (i = 0; i < 2; ++i) {
-			for (j = 1; j < n_pri[i]; ++j)
-				if (a[i].a[j].secondary < 0 && a[i].a[j].score >= opt->T) break;
-			is_multi[i] = j < n_pri[i] ? 1 : 0;
-		}
-		if (is_multi[0] || is_multi[1]) goto no_pairing;
-		score_un = a[0].a[0].score + a[1].a[0].score - opt->pen_unpaired;
-		subo = subo > score_un ? subo : score_un;
-		q_pe = RAW_MAPQ(o - subo, opt->a);
-		if (n_sub > 0) q_pe -= (int)(4.343 * log(n_sub + 1) + .499);
-		if (q_pe < 0) q_pe = 0;
-		if (q_pe > 60) q_pe = 60;
-		q_pe = (int)(q_pe * (1. - .5 * (a[0].a[0].frac_rep + a[1].a[0].frac_rep)) + .499);
-		if (o > score_un) {
-			ora_reg_t *c[2];
-			c[0] = &a[0].a[z[0]]; c[1] = &a[1].a[z[1]];
-			for (i = 0; i < 2; ++i) {
-				if (c[i]->secondary >= 0) c[i]->sub = a[i].a[c[i]->secondary].score, c[i]->secondary = -2;
-				q_se[i] = ora_approx_mapq_se(opt, c[i]);
-			}
-			q_se[0] = q_se[0] > q_pe ? q_se[0] : q_pe < q_se[0] + 40 ? q_pe : q_se[0] + 40;
-			q_se[1] = q_se[1] > q_pe ? q_se[1] : q_pe < q_se[1] + 40 ? q_pe : q_se[1] + 40;
-			extra_flag |= 2;
-			q_se[0] = q_se[0] < RAW_MAPQ(c[0]->score - c[0]->csub, opt->a) ? q_se[0] : RAW_MAPQ(c[0]->score - c[0]->csub, opt->a);
-			q_se[1] = q_se[1] < RAW_MAPQ(c[1]->score - c[1]->csub, opt->a) ? q_se[1] : RAW_MAPQ(c[1]->score - c[1]->csub, opt->a);
-		} else {
-			z[0] = z[1] = 0;
-			q_se[0] = ora_approx_mapq_se(opt, &a[0].a[0]);
-			q_se[1] = ora_approx_mapq_se(opt, &a[1].a[0]);
-		}
-		for (i = 0; i < 2; ++i) {
-			int k = a[i].a[z[i]].secondary_all;
-			if (k >= 0 && k < n_pri[i]) {
-				assert(a[i].a[k].secondary_all < 0);
-				for (j = 0; j < a[i].n; ++j)
-					if (a[i].a[j].secondary_all == k || j == k) a[i].a[j].secondary_all = z[i];
-				a[i].a[z[i]].secondary_all = -1;
-			}
-		}
-		if (ora_pe_dump) {
-			int alt[2];
-			for (i = 0; i < 2; ++i) {
-				const ora_reg_t *p = &a[i].a[n_pri[i]];
-				alt[i] = n_pri[i] < a[i].n && !(p->score < opt->T || p->secondary >= 0 || !p->is_alt) ? n_pri[i] : -1;
-			}
-			dump_pair(id, 1, z, alt, q_se, extra_flag, o, subo_pair, n_sub);
-		}
+		if (ora_pe_dump) dump_pair(id, 1, d.z, d.alt, d.q_se, d.extra_flag, d.o, d.subo, d.n_sub);
 		if (!(opt->flag & ORA_F_ALL)) {
 			for (i = 0; i < 2; ++i) XA[i] = ora_gen_alt(opt, ref, &a[i], s[i].l_seq, s[i].seq);
 		} else XA[0] = XA[1] = 0;
 		for (i = 0; i < 2; ++i) {
-			h[i] = ora_reg2aln(opt, ref, s[i].l_seq, s[i].seq, &a[i].a[z[i]]);
-			h[i].mapq = (uint32_t)q_se[i] & 0xff;
-			h[i].flag |= 0x40 << i | extra_flag;
-			h[i].XA = XA[i] ? XA[i][z[i]] : 0;
+			h[i] = ora_reg2aln(opt, ref, s[i].l_seq, s[i].seq, &a[i].a[d.z[i]]);
+			h[i].mapq = (uint32_t)d.q_se[i] & 0xff;
+			h[i].flag |= 0x40 << i | d.extra_flag;
+			h[i].XA = XA[i] ? XA[i][d.z[i]] : 0;
 			aa[i][n_aa[i]++] = h[i];
-			if (n_pri[i] < a[i].n) {
-				ora_reg_t *p = &a[i].a[n_pri[i]];
-				if (p->score < opt->T || p->secondary >= 0 || !p->is_alt) continue;
-				g[i] = ora_reg2aln(opt, ref, s[i].l_seq, s[i].seq, p);
-				g[i].flag |= 0x800 | 0x40 << i | extra_flag;
-				g[i].XA = XA[i] ? XA[i][n_pri[i]] : 0;
+			if (d.alt[i] >= 0) {
+				g[i] = ora_reg2aln(opt, ref, s[i].l_seq, s[i].seq, &a[i].a[d.alt[i]]);
+				g[i].flag |= 0x800 | 0x40 << i | d.extra_flag;
+				g[i].XA = XA[i] ? XA[i][d.alt[i]] : 0;
 				aa[i][n_aa[i]++] = g[i];
 			}
 		}
@@ -392,30 +436,95 @@ int ora_sam_pe(const ora_opt_t *opt, const ora_ref_t *ref, const ora_pestat_t pe
 			for (j = 0; j < a[i].n; ++j) free(XA[i][j]);
 			free(XA[i]);
 		}
-	} else goto no_pairing;
-	return n;
-
-no_pairing:
-	if (o <= 0) subo_pair = subo;                                /* (else set above, before score_un went into subo) */
-	for (i = 0; i < 2; ++i) {
-		int which = -1;
-		if (a[i].n) {
-			if (a[i].a[0].score >= opt->T) which = 0;
-			else if (n_pri[i] < a[i].n && a[i].a[n_pri[i]].score >= opt->T) which = n_pri[i];
+	} else {
+		int extra_flag = d.extra_flag;
+		for (i = 0; i < 2; ++i) {
+			if (d.z[i] >= 0) h[i] = ora_reg2aln(opt, ref, s[i].l_seq, s[i].seq, &a[i].a[d.z[i]]);
+			else h[i] = ora_reg2aln(opt, ref, s[i].l_seq, s[i].seq, 0);
 		}
-		z[i] = which;
-		if (which >= 0) h[i] = ora_reg2aln(opt, ref, s[i].l_seq, s[i].seq, &a[i].a[which]);
-		else h[i] = ora_reg2aln(opt, ref, s[i].l_seq, s[i].seq, 0);
+		if (ora_pe_dump) { const int none[2] = { -1, -1 }, zero[2] = { 0, 0 }; dump_pair(id, 0, d.z, none, zero, extra_flag, d.o, d.subo, d.n_sub); }
+		if (!(opt->flag & ORA_F_NOPAIRING) && h[0].rid == h[1].rid && h[0].rid >= 0) {
+			int64_t dist;
+			int dir = infer_dir(ref->l_pac, a[0].a[0].rb, a[1].a[0].rb, &dist);
+			if (!pes[dir].failed && dist >= pes[dir].low && dist <= pes[dir].high) extra_flag |= 2;
+		}
+		ora_reg2sam(opt, ref, &s[0], &a[0], 0x41 | extra_flag, &h[1]);
+		ora_reg2sam(opt, ref, &s[1], &a[1], 0x81 | extra_flag, &h[0]);
+		if (strcmp(s[0].name, s[1].name) != 0) { fprintf(stderr, "[ora] paired reads have different names: \"%s\", \"%s\"\n", s[0].name, s[1].name); exit(1); }
+		free(h[0].cigar); free(h[1].cigar);
 	}
-	if (ora_pe_dump) { const int none[2] = { -1, -1 }, zero[2] = { 0, 0 }; dump_pair(id, 0, z, none, zero, extra_flag, o, subo_pair, n_sub); }
-	if (!(opt->flag & ORA_F_NOPAIRING) && h[0].rid == h[1].rid && h[0].rid >= 0) {
-		int64_t dist;
-		int d = infer_dir(ref->l_pac, a[0].a[0].rb, a[1].a[0].rb, &dist);
-		if (!pes[d].failed && dist >= pes[d].low && dist <= pes[d].high) extra_flag |= 2;
-	}
-	ora_reg2sam(opt, ref, &s[0], &a[0], 0x41 | extra_flag, &h[1]);
-	ora_reg2sam(opt, ref, &s[1], &a[1], 0x81 | extra_flag, &h[0]);
-	if (strcmp(s[0].name, s[1].name) != 0) { fprintf(stderr, "[ora] paired reads have different names: \"%s\", \"%s\"\n", s[0].name, s[1].name); exit(1); }
-	free(h[0].cigar); free(h[1].cigar);
 	return n;
+}
+
+static void kat_put(int64_t *w, const ora_reg_t *p)   /* a region as its 19 words */
+{
+	uint32_t u;
+	memcpy(&u, &p->frac_rep, 4);
+	w[0] = p->rb; w[1] = p->re; w[2] = p->qb; w[3] = p->qe; w[4] = p->rid; w[5] = p->score; w[6] = p->truesc; w[7] = p->sub; w[8] = p->alt_sc; w[9] = p->csub;
+	w[10] = p->sub_n; w[11] = p->w; w[12] = p->seedcov; w[13] = p->secondary; w[14] = p->secondary_all; w[15] = p->seedlen0; w[16] = p->n_comp; w[17] = p->is_alt; w[18] = u;
+}
+
+/* Test helper (`bwa_oracle katpair`): what mem_sam_pe decides about one pair of caller-supplied region lists without aligning anything --
+ * ora_mark_primary_se of both ends (ids pair_id << 1 | end), ora_reorder_primary5 under -5, ora_pe_decide, and the selection as
+ * mem_sam_pe uses it: paired, ora_select's XA membership (what ora_gen_alt lists) kept for the records of z[i] and the ALT hit; not
+ * paired, ora_select as ora_reg2sam uses it and need 4 for the region of h[i] where it prints nothing itself.
+ * regs19[e]: n[e] regions in the 19-word layout of the stage records.
+ * marked[e]: 2 + 19 n[e] words -- n, n_pri, the lists as marked, before any decision (what `bwaref katpair` can give);
+ * out[e]: 12 + 22 n[e] words -- the 8 words of the paired-end stage record, n, n_pri, regions with a task, regions with a record, then per
+ *   region in the final order the 19 words as mem_sam_pe left them, the index the region had in regs19 (through the hash), need, XA owner;
+ * pair5: mem_pair's ret, sub, n_sub and raw z[2] (-1: not set; 0 0 0 -1 -1 when it did not run);
+ * extra: nv, the size of u, (k, i) of the best and of the second element of u (-1: none), 1 and o - score_un where that was compared
+ *   (else 0 0), the is_multi bits, the number of ends re-parented. */
+void ora_kat_pair(const ora_opt_t *opt, const ora_ref_t *ref, const ora_pestat_t pes[4], int64_t pair_id, const int n[2], const int64_t *const regs19[2],
+                  int64_t *marked[2], int64_t *out[2], int64_t pair5[5], int64_t extra[ORA_KAT_PAIR_EXTRA])
+{
+	ora_reg_v a[2];
+	ora_pe_dec_t d;
+	int e, i, j, n_pri[2];
+	for (e = 0; e < 2; ++e) {
+		a[e].n = a[e].m = n[e]; a[e].a = (ora_reg_t*)calloc(n[e] ? n[e] : 1, sizeof(ora_reg_t));
+		for (i = 0; i < n[e]; ++i) kat_get(&a[e].a[i], regs19[e] + 19 * i);
+		n_pri[e] = ora_mark_primary_se(opt, n[e], a[e].a, pair_id << 1 | e);
+	}
+	if (opt->flag & ORA_F_PRIMARY5) { ora_reorder_primary5(opt->T, &a[0]); ora_reorder_primary5(opt->T, &a[1]); }
+	for (e = 0; e < 2; ++e) {
+		marked[e][0] = n[e]; marked[e][1] = n_pri[e];
+		for (i = 0; i < n[e]; ++i) kat_put(marked[e] + 2 + 19 * i, &a[e].a[i]);
+	}
+	ora_pe_decide(opt, ref, pes, (uint64_t)pair_id, a, n_pri, &d);
+	pair5[0] = d.o; pair5[1] = d.subo; pair5[2] = d.n_sub; pair5[3] = d.st.zraw[0]; pair5[4] = d.st.zraw[1];
+	extra[0] = d.st.nv; extra[1] = d.st.n_u; extra[2] = d.st.best[0]; extra[3] = d.st.best[1]; extra[4] = d.st.second[0]; extra[5] = d.st.second[1];
+	extra[6] = d.has_un; extra[7] = d.o_un; extra[8] = d.is_multi; extra[9] = d.n_reparent;
+	for (e = 0; e < 2; ++e) {
+		const int m = n[e];
+		uint8_t *need = (uint8_t*)calloc(m ? m : 1, 1);
+		int *owner = (int*)calloc(m ? m : 1, sizeof(int));
+		int n_task = 0, n_rec = 0;
+		int64_t *o = out[e];
+		if (d.paired) {
+			ora_select(opt, m, a[e].a, !(opt->flag & ORA_F_ALL), need, owner);
+			for (i = 0; i < m; ++i) {
+				int nd = 0;
+				if (i == d.z[e] || i == d.alt[e]) nd |= ORA_NEED_REC;
+				if ((need[i] & ORA_NEED_XA) && (owner[i] == d.z[e] || owner[i] == d.alt[e])) nd |= ORA_NEED_XA; else owner[i] = -1;
+				need[i] = (uint8_t)nd;
+			}
+			n_rec = 1 + (d.alt[e] >= 0);
+		} else if (m > 0) {
+			ora_select(opt, m, a[e].a, !(opt->flag & ORA_F_ALL), need, owner);
+			for (i = 0; i < m; ++i) n_rec += (need[i] & ORA_NEED_REC) != 0;
+			if (d.z[e] >= 0 && need[d.z[e]] == 0) need[d.z[e]] = 4;
+		}
+		for (i = 0; i < m; ++i) n_task += need[i] != 0;
+		o[0] = d.paired; o[1] = d.z[e]; o[2] = d.alt[e]; o[3] = d.paired ? d.q_se[e] : 0; o[4] = d.paired ? d.extra_flag : 1; o[5] = d.o; o[6] = d.subo; o[7] = d.n_sub;
+		o[8] = m; o[9] = n_pri[e]; o[10] = n_task; o[11] = n_rec;
+		for (i = 0; i < m; ++i) {
+			int64_t *w = o + 12 + 22 * i;
+			const uint64_t id = (uint64_t)pair_id << 1 | e;
+			kat_put(w, &a[e].a[i]);
+			for (j = 0; j < m && ora_hash64(id + j) != a[e].a[i].hash; ++j);
+			w[19] = j < m ? j : -1; w[20] = need[i]; w[21] = owner[i];
+		}
+		free(need); free(owner); free(a[e].a);
+	}
 }

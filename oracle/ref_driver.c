@@ -25,6 +25,7 @@
  *   katchain [options] <prefix> <cases.bin> <out.bin>   known answers: chains and filtered chains of given seed lists
  *   katdedup [options] <prefix> <cases.bin> <out.bin>   known answers: mem_sort_dedup_patch of given region lists
  *   katmark [options] <prefix> <cases.bin> <out.bin>    known answers: primary marking and mapQ of given region lists
+ *   katpair [options] <prefix> <cases.bin> <out.bin>    known answers: mem_pair on given pairs of region lists
  *
  * Dump format ("i64 records"): a stream of  [tag:i64][n:i64][n x i64].
  */
@@ -44,6 +45,7 @@ extern int bwa_idx_build(const char *fa, const char *prefix, int algo_type, int 
 #include "opt_parse.h"
 #include "kat_mark_io.h"
 #include "kat_dedup_io.h"
+#include "kat_pair_io.h"
 
 /* ---------------------------------------------------------------- records */
 static void rec_write(FILE *fp, int64_t tag, int64_t n, const int64_t *v)
@@ -700,6 +702,82 @@ static int main_katdedup(int argc, char **argv)
 	return rc ? 1 : 0;
 }
 
+/* katpair [options] <prefix> <cases.bin> <out.bin>: per pair of caller-supplied region lists the reference's own mem_mark_primary_se of
+ * both ends (and mem_reorder_primary5 under -5), then -- where mem_sam_pe would call it: pairing not switched off, a primary-assembly hit
+ * on both ends -- its exported mem_pair over the contig table of the index, z[] set to -1 beforehand; kat_pair_io.h has both file formats.
+ * mem_sam_pe's own decisions cannot be called without aligning and printing: for those the oracle is the judge. */
+static int main_katpair(int argc, char **argv)
+{
+	extern int mem_pair(const mem_opt_t *opt, const bntseq_t *bns, const uint8_t *pac, const mem_pestat_t pes[4], bseq1_t s[2], mem_alnreg_v a[2], int id, int *sub, int *n_sub, int z[2], int n_pri[2]);
+	mem_opt_t *opt = mem_opt_init();
+	optparse_t op;
+	bwaidx_t *idx;
+	kp_file_t k;
+	FILE *in, *out;
+	const int64_t *regs[2];
+	int64_t i[2], *rec = 0;
+	int c, n[2], rc, e, j;
+	bwa_verbose = 1;
+	optparse_init(&op, opt);
+	while ((c = getopt(argc, argv, OPT_GETOPT_STRING)) >= 0) if (optparse_one(&op, c, optarg)) return 1;
+	if (optparse_finish(&op) || optind + 3 > argc) return 1;
+	idx = bwa_idx_load(argv[optind], BWA_IDX_BNS);
+	if (!idx) return 1;
+	in = fopen(argv[optind + 1], "rb"); out = fopen(argv[optind + 2], "wb");
+	if (!in || !out || kp_read_opt(in, opt, &k)) { fprintf(stderr, "[bwaref] katpair: cannot open the files, or no option record\n"); return 1; }
+	while ((rc = kp_next_pair(in, &k, i, n, regs)) > 0) {
+		mem_alnreg_v a[2];
+		bseq1_t s[2];
+		const int64_t id = (k.n_processed >> 1) + (i[0] >> 1);
+		int n_pri[2], z[2] = { -1, -1 }, ret = 0, sub = 0, n_sub = 0;
+		int64_t pair5[5];
+		memset(s, 0, sizeof s);
+		for (e = 0; e < 2; ++e) {
+			a[e].n = a[e].m = n[e]; a[e].a = calloc(n[e] ? n[e] : 1, sizeof(mem_alnreg_t));
+			for (j = 0; j < n[e]; ++j) {
+				const int64_t *w = regs[e] + KM_REG_WORDS * j;
+				mem_alnreg_t *p = &a[e].a[j];
+				if (w[4] < 0 || w[4] >= idx->bns->n_seqs) rc = -1;
+				p->rb = w[0]; p->re = w[1]; p->qb = (int)w[2]; p->qe = (int)w[3]; p->rid = (int)w[4]; p->score = (int)w[5]; p->truesc = (int)w[6];
+				p->sub = (int)w[7]; p->alt_sc = (int)w[8]; p->csub = (int)w[9]; p->sub_n = (int)w[10]; p->w = (int)w[11]; p->seedcov = (int)w[12];
+				p->secondary = (int)w[13]; p->secondary_all = (int)w[14]; p->seedlen0 = (int)w[15]; p->n_comp = (int)w[16]; p->is_alt = (int)w[17];
+				p->frac_rep = km_i2f(w[18]);
+			}
+		}
+		if (rc < 0) break;
+		for (e = 0; e < 2; ++e) n_pri[e] = mem_mark_primary_se(opt, n[e], a[e].a, id << 1 | e);
+		if (opt->flag & MEM_F_PRIMARY5) { mem_reorder_primary5(opt->T, &a[0]); mem_reorder_primary5(opt->T, &a[1]); }
+		for (e = 0; e < 2; ++e) {
+			int64_t hdr[2];
+			rec = realloc(rec, (2 + (size_t)KM_REG_WORDS * n[e]) * 8);
+			rec[0] = n[e]; rec[1] = n_pri[e];
+			for (j = 0; j < n[e]; ++j) {
+				const mem_alnreg_t *p = &a[e].a[j];
+				int64_t *w = rec + 2 + KM_REG_WORDS * j;
+				w[0] = p->rb; w[1] = p->re; w[2] = p->qb; w[3] = p->qe; w[4] = p->rid; w[5] = p->score; w[6] = p->truesc; w[7] = p->sub; w[8] = p->alt_sc;
+				w[9] = p->csub; w[10] = p->sub_n; w[11] = p->w; w[12] = p->seedcov; w[13] = p->secondary; w[14] = p->secondary_all; w[15] = p->seedlen0;
+				w[16] = p->n_comp; w[17] = p->is_alt; w[18] = f2i(p->frac_rep);
+			}
+			hdr[0] = i[e]; hdr[1] = n[e];
+			rec_write(out, TAG_READ, 2, hdr);
+			rec_write(out, KP_TAG_MARKED, 2 + (int64_t)KM_REG_WORDS * n[e], rec);
+			if (e == 0) {
+				if (!(opt->flag & MEM_F_NOPAIRING) && n_pri[0] && n_pri[1])
+					ret = mem_pair(opt, idx->bns, 0, k.pes, s, a, (int)id, &sub, &n_sub, z, n_pri);
+				pair5[0] = ret; pair5[1] = sub; pair5[2] = n_sub; pair5[3] = z[0]; pair5[4] = z[1];
+				rec_write(out, KP_TAG_MEMPAIR, 5, pair5);
+			}
+		}
+		free(a[0].a); free(a[1].a);
+	}
+	free(rec); kp_free(&k);
+	fclose(in); fclose(out);
+	bwa_idx_destroy(idx);
+	free(opt);
+	if (rc) fprintf(stderr, "[bwaref] katpair: malformed case file\n");
+	return rc ? 1 : 0;
+}
+
 /* readfq <chunk_bases> <in1> [in2]: the batches the reference's bseq_read (bwa.c:191) cuts, one record per line as
  * name TAB comment-or-* TAB seq TAB qual-or-*, a line "#batch <n>" in front of every batch -- golden vectors for the product's
  * FASTA/FASTQ reader (csrc/fastq_reader.cpp) */
@@ -743,6 +821,7 @@ int main(int argc, char **argv)
 	if (strcmp(argv[1], "katchain") == 0) return main_katchain(argc - 1, argv + 1);
 	if (strcmp(argv[1], "katmark") == 0) return main_katmark(argc - 1, argv + 1);
 	if (strcmp(argv[1], "katdedup") == 0) return main_katdedup(argc - 1, argv + 1);
+	if (strcmp(argv[1], "katpair") == 0) return main_katpair(argc - 1, argv + 1);
 	if (strcmp(argv[1], "readfq") == 0) return main_readfq(argc - 1, argv + 1);
 	fprintf(stderr, "unknown sub-command '%s'\n", argv[1]);
 	return 1;

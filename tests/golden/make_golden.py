@@ -18,6 +18,7 @@ the outputs below are data (inputs + expected outputs), never reference source.
   tests/golden/kat_chain.npz       the reference's chains and filtered chains for the seed lists of tests/chain_cases.py (`make_golden.py chain`)
   tests/golden/kat_dedup.npz       digests of the reference's mem_sort_dedup_patch for the region lists of tests/dedup_cases.py (`make_golden.py dedup`)
   tests/golden/kat_mark.npz        digests of the reference's primary marking and mapQ for the region lists of tests/mark_cases.py (`make_golden.py mark`)
+  tests/golden/kat_pair.npz        digests of the reference's marked lists and mem_pair results for the pairs of tests/pair_cases.py (`make_golden.py pair`)
 
 `make_golden.py extras` writes only the last two groups (round 2 additions); the older files are left alone.
 """
@@ -245,6 +246,30 @@ def mark_kat():
     print("kat_mark.npz:", os.path.getsize(f"{HERE}/kat_mark.npz"), "bytes")
 
 
+def pair_kat():
+    """kat_pair.npz: every set of tests/pair_cases.py through `bwaref katpair` (oracle/ref_driver.c: the reference's mem_mark_primary_se,
+    mem_reorder_primary5 and mem_pair on the given pairs of region lists), over the contig table of the suite's 1 Mb genome with ctg3
+    declared ALT.  Per set: <set>.inputs, the sha256 of the generated case file and its flags; <set>.sha [pairs], the sha256 of what the
+    reference wrote of each pair (pair_cases.shared_words).  Digests only: no inputs, no records."""
+    import chain_cases as cc
+    import pair_cases as pc
+    assert os.path.exists("/root/reference/bwamem.c") and os.access(REF, os.X_OK), "needs the reference build (make -C oracle ref)"
+    os.makedirs(TMP, exist_ok=True)
+    fa = f"{TMP}/g1.fa"
+    bw.make_genome(fa, 11, [600000, 300000, 100000], repeats=True)
+    bw.make_index(fa, f"{TMP}/g1")
+    for e in ("amb", "ann", "bwt", "pac", "sa", "alt"):
+        if os.path.lexists(f"{TMP}/alt.{e}"):
+            os.remove(f"{TMP}/alt.{e}")
+    alt = cc.alt_index({"prefix": f"{TMP}/g1"}, TMP)
+    out = {}
+    for name in pc.SETS:
+        out[f"{name}.inputs"] = np.array(pc.input_digest(name))
+        out[f"{name}.sha"] = pc.digests_of_checker(pc.run_checker(REF, name, alt, TMP, "golden"))
+    np.savez_compressed(f"{HERE}/kat_pair.npz", **out)
+    print("kat_pair.npz:", os.path.getsize(f"{HERE}/kat_pair.npz"), "bytes")
+
+
 def dedup_kat():
     """kat_dedup.npz: every set of tests/dedup_cases.py through `bwaref katdedup` (oracle/ref_driver.c: the reference's own
     mem_sort_dedup_patch and the is_alt loop of mem_align1_core on the given region lists) over g60k.fa.gz with g60k.alt.  Per set:
@@ -266,4 +291,4 @@ def dedup_kat():
 
 
 if __name__ == "__main__":
-    {"dedup": dedup_kat, "extras": extras, "fastq": fastq_cases, "dpwide": dp_wide, "pelibs": pe_libraries, "chain": chain_kat, "mark": mark_kat}.get(sys.argv[1] if len(sys.argv) > 1 else "", main)()
+    {"dedup": dedup_kat, "extras": extras, "fastq": fastq_cases, "dpwide": dp_wide, "pelibs": pe_libraries, "chain": chain_kat, "mark": mark_kat, "pair": pair_kat}.get(sys.argv[1] if len(sys.argv) > 1 else "", main)()
