@@ -619,28 +619,25 @@ def recal_opt(min_mapq=0, min_baseq=0, exclude_flags=-1, max_cycle=0):
     return o
 
 
-class RecalBuilder:
-    """bwahip_recal_builder_*: the recalibration table (BRC\1) of BAM records fed in any cut and any order, for these contig lengths, this
-    packed reference and this mask of known sites (None: none); no device.  opt = (min_mapq, min_baseq, exclude_flags, max_cycle), () for
-    the defaults."""
+class _Builder:
+    """What the builders of the files beside a sorted BAM file share: bwahip_<_what>_builder_add_records, _finish and _close on self._h."""
+    _what = None
 
-    def __init__(self, ref_len, pac, mask=None, opt=()):
-        self._h = C.c_void_p()
-        lens = np.ascontiguousarray(ref_len, dtype=np.int64)
-        _check(lib().bwahip_recal_builder_open(len(lens), lens.ctypes.data if len(lens) else None, bytes(pac) if pac is not None else None,
-                                               bytes(mask) if mask is not None else None, C.byref(recal_opt(*opt)), C.byref(self._h)), "bwahip_recal_builder_open")
+    def _call(self, name, *args):
+        name = f"bwahip_{self._what}_builder_{name}"
+        return getattr(lib(), name)(*args), name
 
     def add_records(self, rec, rec_off):
         rec = bytes(rec)
         rec_off = np.ascontiguousarray(rec_off, dtype=np.int64)
-        _check(lib().bwahip_recal_builder_add_records(self._h, rec, rec_off.ctypes.data, len(rec_off) - 1), "bwahip_recal_builder_add_records")
+        _check(*self._call("add_records", self._h, rec, rec_off.ctypes.data, len(rec_off) - 1))
 
-    def finish(self, rc_fd=-1):
-        _check(lib().bwahip_recal_builder_finish(self._h, rc_fd), "bwahip_recal_builder_finish")
+    def finish(self, fd=-1):
+        _check(*self._call("finish", self._h, fd))
 
     def close(self):
         if self._h:
-            lib().bwahip_recal_builder_close(self._h)
+            self._call("close", self._h)
             self._h = C.c_void_p()
 
     def __enter__(self):
@@ -648,6 +645,20 @@ class RecalBuilder:
 
     def __exit__(self, *a):
         self.close()
+
+
+class RecalBuilder(_Builder):
+    """bwahip_recal_builder_*: the recalibration table (BRC\1) of BAM records fed in any cut and any order, for these contig lengths, this
+    packed reference and this mask of known sites (None: none); no device.  opt = (min_mapq, min_baseq, exclude_flags, max_cycle), () for
+    the defaults."""
+
+    _what = "recal"
+
+    def __init__(self, ref_len, pac, mask=None, opt=()):
+        self._h = C.c_void_p()
+        lens = np.ascontiguousarray(ref_len, dtype=np.int64)
+        _check(lib().bwahip_recal_builder_open(len(lens), lens.ctypes.data if len(lens) else None, bytes(pac) if pac is not None else None,
+                                               bytes(mask) if mask is not None else None, C.byref(recal_opt(*opt)), C.byref(self._h)), "bwahip_recal_builder_open")
 
 
 def dup_end_word(ref_id, u5, reverse):
@@ -680,33 +691,16 @@ def qc_hbm_need(n_ref, sum_len, n_windows, n_records):
     return lib().bwahip_qc_hbm_need(n_ref, sum_len, n_windows, n_records)
 
 
-class QcBuilder:
+class QcBuilder(_Builder):
     """bwahip_qc_builder_*: the QC summary (BQC\1) of BAM records fed in any cut and any order, for these contig lengths; no device.
     opt = (window_shift, exclude_flags, min_mapq), () for the defaults."""
+
+    _what = "qc"
 
     def __init__(self, ref_len, opt=()):
         self._h = C.c_void_p()
         lens = np.ascontiguousarray(ref_len, dtype=np.int64)
         _check(lib().bwahip_qc_builder_open(len(lens), lens.ctypes.data if len(lens) else None, C.byref(qc_opt(*opt)), C.byref(self._h)), "bwahip_qc_builder_open")
-
-    def add_records(self, rec, rec_off):
-        rec = bytes(rec)
-        rec_off = np.ascontiguousarray(rec_off, dtype=np.int64)
-        _check(lib().bwahip_qc_builder_add_records(self._h, rec, rec_off.ctypes.data, len(rec_off) - 1), "bwahip_qc_builder_add_records")
-
-    def finish(self, qc_fd=-1):
-        _check(lib().bwahip_qc_builder_finish(self._h, qc_fd), "bwahip_qc_builder_finish")
-
-    def close(self):
-        if self._h:
-            lib().bwahip_qc_builder_close(self._h)
-            self._h = C.c_void_p()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
 
 
 def pileup_opt(min_mapq=0, min_baseq=0, exclude_flags=-1, min_alt=0):
@@ -721,9 +715,11 @@ def pileup_hbm_need(n_records):
     return lib().bwahip_pileup_hbm_need(n_records)
 
 
-class PileupBuilder:
+class PileupBuilder(_Builder):
     """bwahip_pileup_builder_*: the pileup (BPU\1) of BAM records fed in any cut and any order, for these contig lengths and this packed
     reference; no device.  opt = (min_mapq, min_baseq, exclude_flags, min_alt), () for the defaults."""
+
+    _what = "pileup"
 
     def __init__(self, ref_len, pac, opt=()):
         self._h = C.c_void_p()
@@ -731,56 +727,20 @@ class PileupBuilder:
         _check(lib().bwahip_pileup_builder_open(len(lens), lens.ctypes.data if len(lens) else None, bytes(pac) if pac is not None else None, C.byref(pileup_opt(*opt)),
                                                 C.byref(self._h)), "bwahip_pileup_builder_open")
 
-    def add_records(self, rec, rec_off):
-        rec = bytes(rec)
-        rec_off = np.ascontiguousarray(rec_off, dtype=np.int64)
-        _check(lib().bwahip_pileup_builder_add_records(self._h, rec, rec_off.ctypes.data, len(rec_off) - 1), "bwahip_pileup_builder_add_records")
 
-    def finish(self, pu_fd=-1):
-        _check(lib().bwahip_pileup_builder_finish(self._h, pu_fd), "bwahip_pileup_builder_finish")
-
-    def close(self):
-        if self._h:
-            lib().bwahip_pileup_builder_close(self._h)
-            self._h = C.c_void_p()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
-
-
-class BaiBuilder:
+class BaiBuilder(_Builder):
     """bwahip_bai_builder_*: the BAI index of a coordinate-sorted BAM file from its records and the lengths of its BGZF members, fed
     in file order in any interleaving; no device."""
+
+    _what = "bai"
 
     def __init__(self, n_ref, first_member_offset=0):
         self._h = C.c_void_p()
         _check(lib().bwahip_bai_builder_open(n_ref, first_member_offset, C.byref(self._h)), "bwahip_bai_builder_open")
 
-    def add_records(self, rec, rec_off):
-        rec = bytes(rec)
-        rec_off = np.ascontiguousarray(rec_off, dtype=np.int64)
-        _check(lib().bwahip_bai_builder_add_records(self._h, rec, rec_off.ctypes.data, len(rec_off) - 1), "bwahip_bai_builder_add_records")
-
     def add_members(self, member_len):
         member_len = np.ascontiguousarray(member_len, dtype=np.int32)
-        _check(lib().bwahip_bai_builder_add_members(self._h, member_len.ctypes.data, len(member_len)), "bwahip_bai_builder_add_members")
-
-    def finish(self, bai_fd=-1):
-        _check(lib().bwahip_bai_builder_finish(self._h, bai_fd), "bwahip_bai_builder_finish")
-
-    def close(self):
-        if self._h:
-            lib().bwahip_bai_builder_close(self._h)
-            self._h = C.c_void_p()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
+        _check(*self._call("add_members", self._h, member_len.ctypes.data, len(member_len)))
 
 
 def bai_check_contigs(bns):

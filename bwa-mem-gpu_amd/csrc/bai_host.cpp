@@ -6,19 +6,9 @@
 // the next one to its right.  No relocation of sparse bins into their parents.
 #include "../../include/bwahip.h"
 #include "bai_tables.h"
-#include <errno.h>
-#include <stdio.h>
-#include <unistd.h>
+#include "sidecar_host.h"
 #include <algorithm>
 #include <deque>
-
-namespace {
-
-// a word at a time into reserved room: byte-wise push_back took 3.5 or 4.4 ms for a 4.5 MB index, depending on where the linker put the loop
-void put32(std::vector<uint8_t> &o, uint32_t v) { uint8_t b[4]; for (int k = 0; k < 4; ++k) b[k] = (uint8_t)(v >> (8 * k)); o.insert(o.end(), b, b + 4); }
-void put64(std::vector<uint8_t> &o, uint64_t v) { uint8_t b[8]; for (int k = 0; k < 8; ++k) b[k] = (uint8_t)(v >> (8 * k)); o.insert(o.end(), b, b + 8); }
-
-} // namespace
 
 int bai_serialise(const BaiTables &t, std::vector<uint8_t> *out)
 {
@@ -53,25 +43,13 @@ int bai_serialise(const BaiTables &t, std::vector<uint8_t> *out)
 	return 0;
 }
 
-int bai_write_fd(int fd, const std::vector<uint8_t> &b)
-{
-	for (size_t o = 0; fd >= 0 && o < b.size();) {
-		const ssize_t w = write(fd, b.data() + o, b.size() - o);
-		if (w < 0) { if (errno == EINTR) continue; fprintf(stderr, "[bwahip] writing the BAI index failed: %s\n", strerror(errno)); return BWAHIP_EIO; }
-		if (w == 0) return BWAHIP_EIO;
-		o += (size_t)w;
-	}
-	return 0;
-}
-
 // ---- builder ------------------------------------------------------------------------------------------------------------------------
 // Records and member lengths arrive in file order, interleaved in any proportion.  A record waits (ten words) until the member that
 // holds its begin and the one that holds the begin of its successor are known; the last record ends at V(total), known at finish.  What
 // is kept beyond that tail: one entry per run of records of one (refID, bin), a word per 16 Kbp window reached, four words per reference,
 // and the offsets of the members no resolved record needs any more are dropped.
-struct bwahip_bai_builder {
-	int32_t n_ref = 0; int64_t base = 0;
-	int err = 0; bool finished = false;
+struct bwahip_bai_builder : SidecarBuilder {                      // (of its contigs it keeps the count alone)
+	int64_t base = 0;
 	int64_t u = 0; bool have_prev = false; uint64_t prev_key = 0;
 	std::deque<int64_t> coff{ 0 }; int64_t coff_first = 0, n_members = 0;   // coff[b - coff_first] = offset of member b, up to b = n_members
 	struct Pend { BaiRec r; int64_t u0; };
@@ -130,7 +108,7 @@ extern "C" int bwahip_bai_builder_add_records(bwahip_bai_builder *b, const uint8
 		bwahip_bai_builder::Pend p;
 		int bad = rec_off[i] < 0 || len < 0 ? BAI_BAD : bai_parse(rec + rec_off[i], len, b->n_ref, &p.r);
 		if (bad != BAI_BAD) {                                       // the order is judged before the capacity: both fields were read within the record
-			const int32_t ref = (int32_t)bai_ld32(rec + rec_off[i] + 4), pos = (int32_t)bai_ld32(rec + rec_off[i] + 8);
+			const int32_t ref = (int32_t)bam_ld32(rec + rec_off[i] + 4), pos = (int32_t)bam_ld32(rec + rec_off[i] + 8);
 			const uint64_t key = bai_order_key(ref, pos);
 			if (b->have_prev && key < b->prev_key) bad = BAI_BAD;
 			b->prev_key = key; b->have_prev = true;
@@ -156,14 +134,11 @@ extern "C" int bwahip_bai_builder_add_members(bwahip_bai_builder *b, const int32
 	return 0;
 }
 
-extern "C" int bwahip_bai_builder_finish(bwahip_bai_builder *b, int bai_fd)
+static int bai_builder_bytes(bwahip_bai_builder *b, std::vector<uint8_t> *bytes)
 {
-	if (!b || b->finished) return BWAHIP_EINVAL;
-	if (b->err) return b->err;
-	b->finished = true;
-	if (b->n_members != (b->u + BAI_BLOCK_IN - 1) / BAI_BLOCK_IN) return b->err = BWAHIP_EINVAL;   // the members are not those of these records
+	if (b->n_members != (b->u + BAI_BLOCK_IN - 1) / BAI_BLOCK_IN) return BWAHIP_EINVAL;   // the members are not those of these records
 	b->drain();
-	if (b->pend.size() > 1) return b->err = BWAHIP_EINTERNAL;
+	if (b->pend.size() > 1) return BWAHIP_EINTERNAL;
 	if (!b->pend.empty()) { b->emit(b->pend[0].r, b->voff(b->pend[0].u0), (uint64_t)(b->base + b->coff.back()) << 16); b->pend.clear(); }
 	b->close_run();
 	std::vector<bwahip_bai_builder::Chunk> &c = b->chunks;
@@ -184,11 +159,10 @@ extern "C" int bwahip_bai_builder_finish(bwahip_bai_builder *b, int bai_fd)
 	BaiTables t;
 	t.n_ref = b->n_ref; t.n_chunks = (int64_t)ckey.size(); t.ckey = ckey.data(); t.cbeg = cbeg.data(); t.cend = cend.data();
 	t.meta = b->meta.data(); t.lin_off = lin_off.data(); t.lin = lin.data(); t.n_no_coor = b->n_no_coor;
-	std::vector<uint8_t> bytes;
-	int rc = bai_serialise(t, &bytes);
-	if (!rc) rc = bai_write_fd(bai_fd, bytes);
-	return b->err = rc;
+	return bai_serialise(t, bytes);
 }
+
+extern "C" int bwahip_bai_builder_finish(bwahip_bai_builder *b, int bai_fd) { return builder_finish(b, bai_fd, "writing the BAI index", bai_builder_bytes); }
 
 extern "C" void bwahip_bai_builder_close(bwahip_bai_builder *b) { delete b; }
 

@@ -2,15 +2,12 @@
 // the device stage (k_bai.hip) share: how one record is read and judged, the virtual offset of a position of the uncompressed record
 // stream, and the compact tables that both hand to the one serialiser.  Plain C++; __host__ __device__ where a HIP compiler reads it.
 #pragma once
+#include "bam_rec.h"
 #include <stdint.h>
 #include <string.h>
 #include <vector>
 
-#ifdef __HIPCC__
-#define BAI_HD __host__ __device__
-#else
-#define BAI_HD
-#endif
+#define BAI_HD BAM_HD
 
 constexpr int64_t BAI_BLOCK_IN = 65280;          // the record stream is cut into BGZF members every 65 280 bytes
 constexpr int32_t BAI_MAX_END = 1 << 29;         // the last position the binning scheme of BAI holds
@@ -19,27 +16,14 @@ constexpr int BAI_BAD = 1, BAI_TOO_FAR = 2;      // what bai_parse says of a rec
 
 struct BaiRec { int32_t ref, pos, e; uint32_t bin; int unm; };
 
-BAI_HD inline uint32_t bai_ld32(const uint8_t *p) { uint32_t v; __builtin_memcpy(&v, p, 4); return v; }   // records begin at any address
-
-BAI_HD inline uint32_t bai_reg2bin(int64_t beg, int64_t end)
-{
-	--end;
-	if (beg >> 14 == end >> 14) return (uint32_t)(((1 << 15) - 1) / 7 + (beg >> 14));
-	if (beg >> 17 == end >> 17) return (uint32_t)(((1 << 12) - 1) / 7 + (beg >> 17));
-	if (beg >> 20 == end >> 20) return (uint32_t)(((1 << 9) - 1) / 7 + (beg >> 20));
-	if (beg >> 23 == end >> 23) return (uint32_t)(((1 << 6) - 1) / 7 + (beg >> 23));
-	if (beg >> 26 == end >> 26) return (uint32_t)(((1 << 3) - 1) / 7 + (beg >> 26));
-	return 0;
-}
-
 // One record of `len` bytes at p.  No byte beyond p + len is read: every field is bounded by the length first.  0: *r is filled (a record
 // without a reference: ref < 0, nothing else means anything); BAI_BAD: not a BAM record of n_ref references; BAI_TOO_FAR: it ends beyond 2^29.
 BAI_HD inline int bai_parse(const uint8_t *p, int64_t len, int32_t n_ref, BaiRec *r)
 {
 	if (len < 36) return BAI_BAD;
-	if ((int64_t)(int32_t)bai_ld32(p) + 4 != len) return BAI_BAD;
-	const int32_t ref = (int32_t)bai_ld32(p + 4), pos = (int32_t)bai_ld32(p + 8);
-	const uint32_t w3 = bai_ld32(p + 12), w4 = bai_ld32(p + 16);
+	if ((int64_t)(int32_t)bam_ld32(p) + 4 != len) return BAI_BAD;
+	const int32_t ref = (int32_t)bam_ld32(p + 4), pos = (int32_t)bam_ld32(p + 8);
+	const uint32_t w3 = bam_ld32(p + 12), w4 = bam_ld32(p + 16);
 	const int64_t l_read_name = w3 & 0xff, n_cigar = w4 & 0xffff;
 	if (36 + l_read_name + 4 * n_cigar > len) return BAI_BAD;
 	if (ref >= n_ref || (ref >= 0 && pos < 0)) return BAI_BAD;
@@ -48,12 +32,12 @@ BAI_HD inline int bai_parse(const uint8_t *p, int64_t len, int32_t n_ref, BaiRec
 	int64_t rlen = 0;
 	const uint8_t *cig = p + 36 + l_read_name;
 	for (int64_t k = 0; k < n_cigar; ++k) {
-		const uint32_t w = bai_ld32(cig + 4 * k), op = w & 15;
+		const uint32_t w = bam_ld32(cig + 4 * k), op = w & 15;
 		if (op == 0 || op == 2 || op == 3 || op == 7 || op == 8) rlen += w >> 4;   // M D N = X
 	}
 	const int64_t e = rlen > 0 && !r->unm ? (int64_t)pos + rlen : (int64_t)pos + 1;
 	if (e > BAI_MAX_END) return BAI_TOO_FAR;
-	r->e = (int32_t)e; r->bin = bai_reg2bin(pos, e);
+	r->e = (int32_t)e; r->bin = bam_reg2bin(pos, e);
 	return 0;
 }
 
@@ -82,7 +66,6 @@ struct BaiTables {
 };
 // bai_host.cpp: the tables as the bytes of a .bai file; BWAHIP_EINVAL for tables that do not fit together
 int bai_serialise(const BaiTables &t, std::vector<uint8_t> *out);
-int bai_write_fd(int fd, const std::vector<uint8_t> &bytes);   // all of them or BWAHIP_EIO; fd < 0: nothing
 
 // bam_sort_host.cpp: bwahip_bam_merger_finish with a listener -- every record as it is emitted (whole, in file order), the lengths of
 // the members of every piece as it leaves the BGZF writer; a hook's non-zero return ends the merge with that code

@@ -5,6 +5,7 @@
 // included, goes last -- lanes 0..35 store one byte each of nine words held in registers.
 #pragma once
 #include "sam_dev.h"
+#include "bam_rec.h"
 
 namespace samdev {
 
@@ -17,18 +18,6 @@ __device__ __forceinline__ void bam_tag_int(Emit &e, char t0, char t1, long long
 	e.word((unsigned long long)(uint8_t)t0 | (unsigned long long)(uint8_t)t1 << 8 | (unsigned long long)(uint8_t)ty << 16 | ((unsigned long long)v & 0xffffffffull) << 24, 3 + nb);
 }
 __device__ __forceinline__ void bam_tag_head(Emit &e, char t0, char t1, char ty) { e.word((unsigned long long)(uint8_t)t0 | (unsigned long long)(uint8_t)t1 << 8 | (unsigned long long)(uint8_t)ty << 16, 3); }
-
-// reg2bin of the specification (section 5.3) on signed values: pos = -1, end = 0 gives 4680
-__device__ __forceinline__ int bam_reg2bin(int64_t beg, int64_t end)
-{
-	--end;
-	if (beg >> 14 == end >> 14) return (int)(((1 << 15) - 1) / 7 + (beg >> 14));
-	if (beg >> 17 == end >> 17) return (int)(((1 << 12) - 1) / 7 + (beg >> 17));
-	if (beg >> 20 == end >> 20) return (int)(((1 << 9) - 1) / 7 + (beg >> 20));
-	if (beg >> 23 == end >> 23) return (int)(((1 << 6) - 1) / 7 + (beg >> 23));
-	if (beg >> 26 == end >> 26) return (int)(((1 << 3) - 1) / 7 + (beg >> 26));
-	return 0;
-}
 
 // The -C comment as tags.  The host has checked (bam_check_reads) that every tab-separated field is XX:Z:<printable>, XX:A:<char>
 // or XX:i:<integer in [-2^31, 2^32)>.  All lanes scan the same bytes (uniform loads); the values are copied one byte per lane.
@@ -130,7 +119,7 @@ __device__ void emit_bam_record(Emit &e, const Tables &t, const ReadText &s, int
 		const int64_t pos = R.placed() ? p.pos : -1;
 		int64_t end = pos + 1;
 		if (R.placed() && !(p.flag & 0x4) && p.n_cigar) { const int rl = get_rlen(t, p); if (rl) end = pos + rl; }
-		const uint32_t bin = (uint32_t)bam_reg2bin(pos, end) & 0xffff, mapq = R.placed() ? p.mapq & 0xff : 0;
+		const uint32_t bin = bam_reg2bin(pos, end) & 0xffff, mapq = R.placed() ? p.mapq & 0xff : 0;
 		const uint32_t w0 = (uint32_t)(e.pos - rec0 - 4), w1 = (uint32_t)(R.placed() ? p.rid : -1), w2 = (uint32_t)(int32_t)pos,
 		               w3 = (uint32_t)l_read_name | mapq << 8 | bin << 16, w4 = (uint32_t)n_cigar | (uint32_t)R.out_flag() << 16, w5 = (uint32_t)l_seq,
 		               w6 = (uint32_t)(R.mate_placed() ? mt.rid : -1), w7 = (uint32_t)(int32_t)(R.mate_placed() ? mt.pos : -1),

@@ -4,6 +4,7 @@
 #include "../../include/bwahip.h"
 #include "bam_sort_key.h"
 #include "bai_tables.h"                                         // MergeHooks: the index builder listens to the merge (bai_host.cpp)
+#include "sidecar_host.h"
 #include <errno.h>
 #include <fcntl.h>
 #include <stdio.h>
@@ -89,18 +90,6 @@ struct Run {
 	std::vector<uint8_t> rec; std::vector<uint64_t> keys; std::vector<int64_t> off;   // in memory
 	std::string path;                                                                // spilled
 };
-
-int write_full(int fd, const void *p, int64_t len)
-{
-	const uint8_t *b = (const uint8_t*)p;
-	while (len > 0) {
-		const ssize_t w = write(fd, b, (size_t)(len > (1ll << 30) ? (1ll << 30) : len));
-		if (w < 0) { if (errno == EINTR) continue; return BWAHIP_EIO; }
-		if (w == 0) return BWAHIP_EIO;
-		b += w; len -= w;
-	}
-	return 0;
-}
 
 int pread_full(int fd, void *p, int64_t len, int64_t at)
 {
@@ -234,7 +223,7 @@ extern "C" int bwahip_bam_merger_add(bwahip_bam_merger *m, int64_t run_no, const
 	}
 	const int fd = open(r->path.c_str(), O_WRONLY | O_CREAT | O_EXCL, 0600);
 	int rc = fd < 0 ? BWAHIP_EIO : 0;
-	if (!rc && ((rc = write_full(fd, keys, n_rec * 8)) || (rc = write_full(fd, rec_off, (n_rec + 1) * 8)) || (rc = write_full(fd, rec, len)))) {}
+	if (!rc && ((rc = write_all(fd, keys, n_rec * 8, nullptr)) || (rc = write_all(fd, rec_off, (n_rec + 1) * 8, nullptr)) || (rc = write_all(fd, rec, len, nullptr)))) {}
 	if (fd >= 0 && close(fd) != 0 && !rc) rc = BWAHIP_EIO;
 	if (rc) {
 		fprintf(stderr, "[bwahip] sorted BAM: writing %s failed: %s\n", r->path.c_str(), strerror(errno));

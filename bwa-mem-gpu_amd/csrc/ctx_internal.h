@@ -319,12 +319,12 @@ int  bam_devmerger_add_dev(bwahip_bam_devmerger *m, int64_t run_no, const uint8_
 // spilled run is refused (BWAHIP_EINVAL) and keeps its runs: their record bytes are in its store
 int  bam_devmerger_take_runs(bwahip_bam_devmerger *m, std::vector<std::pair<int64_t, DevRun*>> *out);
 // What one finish of a device merger runs beside the members, and where the stages' outputs go: resolved once, by the three
-// bwahip_bam_devmerger_finish* entry points or by a sink of the stream driver.  The QC stage and the pileup are the merger's armed state
-// (bwahip_bam_devmerger_set_qc, _set_pileup), the windowed path follows from its runs: the finish fills them in.
+// bwahip_bam_devmerger_finish* entry points or by a sink of the stream driver.  The record stages (below) are the merger's armed state
+// (bwahip_bam_devmerger_set_qc, _set_pileup), the windowed path follows from its runs: the finish fills it in.
 struct FinishPlan {
 	bool index = false; int bai_fd = -1; int64_t base = 0; int32_t n_ref = 0; bwahip_bai_stats_t *bs = nullptr;   // the .bai of what is written (base: the first member's offset in the file)
 	bool mark = false; bwahip_markdup_stats_t *ms = nullptr;       // duplicates marked before anything is gathered (ms may be null)
-	bool qc = false, pileup = false, spill = false;                // filled in by the finish
+	bool spill = false;                                            // filled in by the finish
 };
 int  bam_devmerger_finish(bwahip_bam_devmerger *m, int fd, bwahip_devmerge_stats_t *st, FinishPlan plan);
 // k_bai.hip: the index stage of a device merger's finish.  bai_stage_members: room for the lengths of n_blocks members (the caller fills
@@ -362,26 +362,31 @@ int markdup_mark_run(MarkdupStage *s, bwahip_ctx *c, uint8_t *rec, const int64_t
 int spill_window_cuts(hipStream_t st, int n, int n_runs, const int64_t *first, const uint8_t *spilled, const unsigned *idx, const int *piece_first, int window_pieces, int n_windows, int *cut);
 int spill_window_addr(hipStream_t st, int rec_lo, int n_rec, int n_runs, const int64_t *first, const int64_t *const *run_off, const uint8_t *spilled, const int64_t *base,
                       const unsigned *idx, const uint8_t **addr);
-// k_qc.hip: the QC stage of a device merger's finish, on c->stream.  begin: the layout for these contigs and (resolved) options, the tables and
-// the difference array cleared; records: the record pass over one run (ord0: the ordinal of its first record in the order given); finish: the
-// scan pass, the one download (awaited) and the summary's bytes -- BWAHIP_EINVAL when a record was refused.  n_records == 0 launches nothing.
-struct QcStage;
-QcStage *qc_stage_new();
-void qc_stage_free(QcStage *s);
-int  qc_stage_begin(QcStage *s, bwahip_ctx *c, int32_t n_ref, const int64_t *ref_len, const bwahip_qc_opt_t &opt, int64_t n_records);
-int  qc_stage_records(QcStage *s, bwahip_ctx *c, const uint8_t *rec, const int64_t *off, int64_t n_rec, int64_t len, int64_t ord0);
-int  qc_stage_finish(QcStage *s, bwahip_ctx *c, std::vector<uint8_t> *bytes, bwahip_qc_stats_t *qs);
-// k_pileup.hip: the pileup stage of a device merger's finish, on c->stream.  begin: these contigs, the packed reference (d_pac: where it lies
-// in HBM; or h_pac: uploaded here, once per non-zero h_pac_gen) and the (resolved) options, the per-record words; records: the observations of one run are counted -- the
-// run is read again by finish and stays where it is until then; finish: the keys, their sort, alleles, sites and evidence, the one download
-// (awaited) and the file's bytes -- BWAHIP_EINVAL when a record was refused.  n_records == 0 launches nothing.
-struct PileupStage;
-PileupStage *pu_stage_new();
-void pu_stage_free(PileupStage *s);
-int  pu_stage_begin(PileupStage *s, bwahip_ctx *c, int32_t n_ref, const int64_t *ref_len, const uint8_t *d_pac, const uint8_t *h_pac, uint64_t h_pac_gen, const bwahip_pileup_opt_t &opt,
-                     int64_t n_records);
-int  pu_stage_records(PileupStage *s, bwahip_ctx *c, const uint8_t *rec, const int64_t *off, int64_t n_rec, int64_t len, int64_t ord0);
-int  pu_stage_finish(PileupStage *s, bwahip_ctx *c, std::vector<uint8_t> *bytes, bwahip_pileup_stats_t *ps);
+// A stage of a device merger's finish that reads every record once, run by run, on c->stream, changes none, and leaves a file of its own.  It
+// holds what it was configured with (resolved options, checked contig lengths, where its reference comes from, the caller's stats struct) and
+// its buffers, which later finishes use again.  begin: the layout, the tables cleared; records: one run, or one staged slice of one -- record i
+// = rec[off[i] .. off[i + 1]) within the run's `len` bytes, ord0: the ordinal of its first record among all runs'; done: the rest of the work,
+// the one download (awaited), the file's bytes into `bytes` and the stats -- BWAHIP_EINVAL when a record was refused; write: the bytes to fd
+// (fd < 0: nowhere).  n_records == 0 launches nothing.  takes_windows: a spilled run's slices may pass window by window, each gone when
+// the next arrives -- not so for a stage whose done reads the runs again.
+struct RecordStage {
+	bool armed = false; int fd = -1;
+	std::vector<uint8_t> bytes;
+	virtual ~RecordStage() = default;
+	virtual int begin(bwahip_ctx *c, int64_t n_records) = 0;
+	virtual int records(bwahip_ctx *c, const uint8_t *rec, const int64_t *off, int64_t n_rec, int64_t len, int64_t ord0) = 0;
+	virtual int done(bwahip_ctx *c) = 0;
+	virtual int write() = 0;
+	virtual bool takes_windows() const = 0;
+};
+// k_qc.hip: the QC summary.  k_pileup.hip: the pileup -- pac: the packed reference of these contigs, copied and uploaded once per call of
+// pu_stage_set (null: the context's, where it lies in HBM).  *_set: resolved options and checked lengths; the stats struct may be null
+RecordStage *qc_stage_new();
+void qc_stage_set(RecordStage *s, const bwahip_qc_opt_t &opt, int32_t n_ref, const int64_t *ref_len, int fd, bwahip_qc_stats_t *qs);
+RecordStage *pu_stage_new();
+void pu_stage_set(RecordStage *s, const bwahip_pileup_opt_t &opt, int32_t n_ref, const int64_t *ref_len, const uint8_t *pac, int fd, bwahip_pileup_stats_t *ps);
+// k_bammerge.hip: exactly a configured stage on the caller's records, uploaded as one run (bwahip_kat_qc, bwahip_kat_pileup); the file's bytes to out
+int  record_stage_kat(RecordStage *s, bwahip_ctx *c, const uint8_t *rec, const int64_t *rec_off, int64_t n_rec, uint8_t *out, int64_t out_cap, int64_t *out_len);
 int bam_check_reads(int n, const bwahip_seq_t *seqs);   // bam_host.cpp: BWAHIP_EINVAL (with a message naming the read) for a name or a comment BAM cannot hold
 void pipe_destroy(bwahip_ctx *c);                                                     // final_rt.hip: the stream driver's buffer sets
 int final_setup(bwahip_ctx *c);                                                       // contig name tables for the SAM kernels

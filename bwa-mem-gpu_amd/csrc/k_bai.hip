@@ -46,7 +46,7 @@ __global__ __launch_bounds__(256) void k_bai_parse(int lo, int n, const uint8_t 
 	int bad = bai_parse(p, len, n_ref, &r);
 	if (bad != BAI_BAD && i > 0 && out_off[i] - out_off[i - 1] >= 12) {   // the order, from fields both records hold within their lengths
 		const uint8_t *q = addr[idx[i - 1]];
-		if (bai_order_key((int32_t)bai_ld32(p + 4), (int32_t)bai_ld32(p + 8)) < bai_order_key((int32_t)bai_ld32(q + 4), (int32_t)bai_ld32(q + 8))) bad = BAI_BAD;
+		if (bai_order_key((int32_t)bam_ld32(p + 4), (int32_t)bam_ld32(p + 8)) < bai_order_key((int32_t)bam_ld32(q + 4), (int32_t)bam_ld32(q + 8))) bad = BAI_BAD;
 	}
 	if (bad) atomicMin(err, (unsigned long long)i << 8 | (unsigned)bad);   // the first offending record decides
 	const bool coor = !bad && r.ref >= 0;

@@ -19,24 +19,24 @@
 // Two piece inputs and two piece outputs: the gather and the deflate of piece k are queued on the context's stream while the 16-byte
 // total and then the members of piece k - 1 come back on the copy stream and are written.  No kernel here uses LDS or atomics.
 //
-// Beside the members a finish runs the stages its FinishPlan names (ctx_internal.h): duplicate marking (k_markdup.hip: one bit of a record
-// changes and no key), the QC summary (k_qc.hip: it reads and changes nothing), the pileup (k_pileup.hip: the same; resident runs only), the
-// BAI index (k_bai.hip, after the last piece).  Marking, QC and the pileup read every record.  That is the records pass: a resident run's records pass before the order is made, one stage after the other over
+// Beside the members a finish runs the stages its FinishPlan names (ctx_internal.h) -- duplicate marking (k_markdup.hip: one bit of a record
+// changes and no key), the BAI index (k_bai.hip, after the last piece) -- and the merger's armed record stages (RecordStage, ctx_internal.h: the
+// QC summary, k_qc.hip, then the pileup, k_pileup.hip, resident runs only; they read and change nothing).  Marking and the record stages read
+// every record.  That is the records pass: a resident run's records pass before the order is made, marking first, one stage after the other over
 // all runs, and each stage is awaited there.  A spilled run (bwahip_bam_devmerger_set_spill, k_bamspill.hip) keeps its record bytes in a
 // host-side store; they are staged one window of pieces at a time (spill_plan.h), the gather finds them in the staging buffer, and the slices
 // pass the stages -- and the index parse -- in their window, so the await is deferred behind the last window.  A merger without a stage
 // and without a spilled run queues exactly what is described above.  Finish::run is the list of steps, each a function of its own: the
 // checks; the records pass over resident runs; the order; the source table and output offsets; the piece cuts; the piece buffers; the window
-// plan, if spilled; the piece loop; the deferred await; the index; the QC file; the pileup file; the stats (an empty merger: the first
-// two, the last five).
+// plan, if spilled; the piece loop; the deferred await; the index; the record stages' files; the stats (an empty merger: the first two and
+// what follows the piece loop).
 #include "ctx_internal.h"
 #include "bai_tables.h"
 #include "qc_tables.h"
 #include "pileup_tables.h"
 #include "spill_plan.h"
 #include "spill_store.h"
-#include <errno.h>
-#include <unistd.h>
+#include "sidecar_host.h"
 #include <chrono>
 #include <map>
 #include <mutex>
@@ -128,17 +128,6 @@ struct Work {
 	}
 };
 
-int write_full(int fd, const uint8_t *b, int64_t len)
-{
-	while (len > 0) {
-		const ssize_t w = write(fd, b, (size_t)(len > (1ll << 30) ? (1ll << 30) : len));
-		if (w < 0) { if (errno == EINTR) continue; fprintf(stderr, "[bwahip] sorted BAM: writing the members failed: %s\n", strerror(errno)); return BWAHIP_EIO; }
-		if (w == 0) return BWAHIP_EIO;
-		b += w; len -= w;
-	}
-	return 0;
-}
-
 // a merger with spilled runs: the staging of the windows (counted by bwahip_bam_devmerge_spill_hbm_need, k_bamspill.hip)
 struct SpillWork {
 	Tally hbm;
@@ -187,18 +176,17 @@ struct bwahip_bam_devmerger {
 	std::map<int64_t, DevRun*> runs;                               // by run_no: the order of the concatenation
 	int64_t n_records = 0, raw_bytes = 0;
 	Work w;
-	std::unique_ptr<BaiStage, void (*)(BaiStage*)> bai{ nullptr, bai_stage_free };   // the stages' buffers (k_bai.hip, k_markdup.hip, k_qc.hip): each made by the first finish that runs the stage
+	std::unique_ptr<BaiStage, void (*)(BaiStage*)> bai{ nullptr, bai_stage_free };   // the stages' buffers (k_bai.hip, k_markdup.hip): each made by the first finish that runs the stage
 	std::unique_ptr<MarkdupStage> md;
-	std::unique_ptr<QcStage, void (*)(QcStage*)> qc{ nullptr, qc_stage_free };
+	// The record stages (bwahip_bam_devmerger_set_qc, _set_pileup), in the order a finish runs the armed ones.  They live as long as the merger:
+	// what a setter configured and the buffers a finish made stay for the next finish
+	std::unique_ptr<RecordStage> qc{ qc_stage_new() }, pu{ pu_stage_new() };
+	RecordStage *const stages[2] = { qc.get(), pu.get() };
+	bool all_take_windows() const { for (const RecordStage *s : stages) if (s->armed && !s->takes_windows()) return false; return true; }
 	// spilled runs (bwahip_bam_devmerger_set_spill): the store of their record bytes, the windows' staging
 	HostBuf dl_bounce;                                             // bam_devmerger_adopt_spilled: a file-backed run's bytes on their way from HBM
 	bool spill_armed = false, added = false; int window_pieces = 0; SpillStore *store = nullptr; SpillWork sw;
 	int64_t n_spilled = 0, n_windows = 0; double download_s = 0, upload_ms = 0;
-	bool qc_armed = false; bwahip_qc_opt_t qc_opt = { 14, 1796, 0 }; std::vector<int64_t> qc_len; int qc_fd = -1; bwahip_qc_stats_t *qc_stats = nullptr;
-	// the pileup (bwahip_bam_devmerger_set_pileup): pu_pac empty = the context's packed reference, where it lies in HBM
-	std::unique_ptr<PileupStage, void (*)(PileupStage*)> pu{ nullptr, pu_stage_free };
-	bool pu_armed = false; bwahip_pileup_opt_t pu_opt = { 0, 0, 1796, 2 }; std::vector<int64_t> pu_len; std::vector<uint8_t> pu_pac; bool pu_own_pac = false; uint64_t pu_gen = 0; int pu_fd = -1;
-	bwahip_pileup_stats_t *pu_stats = nullptr;
 };
 
 int bam_devrun_make(bwahip_ctx *c, const uint8_t *d_rec, int64_t len, const uint64_t *d_keys, const int64_t *d_rec_off, int64_t n_rec, hipStream_t st, DevRun **out)
@@ -412,7 +400,7 @@ extern "C" int bwahip_bam_devmerger_set_spill(bwahip_bam_devmerger *m, const bwa
 {
 	if (!m || !in || in->host_budget < 0 || in->window_pieces > 65536) return BWAHIP_EINVAL;
 	std::lock_guard<std::mutex> lk(m->mu);
-	if (m->added || m->spill_armed || m->pu_armed) return BWAHIP_EINVAL;   // before the first add, once; the pileup reads resident runs only
+	if (m->added || m->spill_armed || !m->all_take_windows()) return BWAHIP_EINVAL;   // before the first add, once; the pileup reads resident runs only
 	if (!(m->store = spill_store_new(in->host_budget, in->tmp_dir, pinned_alloc, pinned_free, m->c))) return BWAHIP_ENOMEM;
 	m->window_pieces = in->window_pieces > 0 ? in->window_pieces : DEFAULT_WINDOW_PIECES;
 	m->spill_armed = true;
@@ -423,7 +411,7 @@ extern "C" int bwahip_bam_devmerger_set_spill(bwahip_bam_devmerger *m, const bwa
 extern "C" int bwahip_bam_devmerger_add_spilled(bwahip_bam_devmerger *m, int64_t run_no, const uint8_t *rec, int64_t len, const uint64_t *keys, const int64_t *rec_off, int64_t n_rec,
                                                 const uint32_t *tmpl, const bwahip_dup_desc_t *desc, int64_t n_tmpl)
 {
-	if (!m || !m->spill_armed || m->pu_armed) return BWAHIP_EINVAL;
+	if (!m || !m->spill_armed || !m->all_take_windows()) return BWAHIP_EINVAL;
 	const bool with_dup = tmpl || desc;
 	if (!with_dup && n_tmpl) return BWAHIP_EINVAL;
 	return devmerger_add(m, run_no, rec, len, keys, rec_off, n_rec, with_dup, tmpl, desc, n_tmpl, true);
@@ -444,7 +432,7 @@ extern "C" int bwahip_bam_devmerger_spill_stats(bwahip_bam_devmerger *m, bwahip_
 // ---- finish ---------------------------------------------------------------------------------------------------------------------------
 namespace {
 
-// ---- the stages that read records: marking (k_markdup.hip), then QC (k_qc.hip), then the pileup (k_pileup.hip)
+// ---- the stages that read records: marking (k_markdup.hip), then the armed record stages
 // Marking's own beginning, on the context's stream: the runs' descriptors concatenated in run order, the decision, the counts
 int mark_decide(bwahip_bam_devmerger *m)
 {
@@ -495,8 +483,6 @@ int mark_end(bwahip_bam_devmerger *m, bwahip_markdup_stats_t *ms)
 	return 0;
 }
 
-enum { RS_MARK = 1, RS_QC = 2, RS_PILEUP = 4 };                   // the stages that read every record, in the order they run
-
 // One finish: the merger, the plan, the locals the steps hand on, and the steps themselves -- run() at the end is their list
 struct Finish {
 	bwahip_bam_devmerger *const m; FinishPlan plan; const int fd; const double t0 = now_s();
@@ -508,42 +494,31 @@ struct Finish {
 	const unsigned *idx = nullptr;                                 // the order: the ordinal at every sorted place
 	int64_t piece_bytes = 0; int n_pieces = 0; std::vector<int> piece_first;
 	int *mlen_all = nullptr;                                       // the whole stream's member lengths, for the index
-	std::vector<uint8_t> qc_bytes, pu_bytes;                       // written once the members are
+	std::vector<RecordStage*> rs;                                  // the armed record stages, in the order they run (after marking)
 	// spilled runs: the window plan; by index in run order the run, its number, its first ordinal and template; [window][run] the slices' bases
 	SpillPlan sp; int wp = 1; bool parsed = false;                 // parsed: the index parse ran window by window
 	std::vector<DevRun*> runv; std::vector<int64_t> run_id, rec_at, tmpl_at, base; std::vector<uint8_t> flags;
-	Finish(bwahip_bam_devmerger *m_, const FinishPlan &p, int fd_) : m(m_), plan(p), fd(fd_) { plan.qc = m->qc_armed; plan.pileup = m->pu_armed; plan.spill = m->n_spilled > 0; }
-	int stages() const { return (plan.mark ? RS_MARK : 0) | (plan.qc ? RS_QC : 0) | (plan.pileup ? RS_PILEUP : 0); }
+	Finish(bwahip_bam_devmerger *m_, const FinishPlan &p, int fd_) : m(m_), plan(p), fd(fd_)
+	{
+		plan.spill = m->n_spilled > 0;
+		for (RecordStage *s : m->stages) if (s->armed) rs.push_back(s);
+	}
 	int64_t piece_len(int p) const { const int64_t lo = (int64_t)p * piece_bytes; return total - lo < piece_bytes ? total - lo : piece_bytes; }
-	// The records pass: positions [lo, hi) of run r through the stages `which`, on the context's stream.  rec + r->off[i] is record i: rec is the
-	// run's bytes, or the base of a staged slice.  [lo, counted) are counted; a record in [counted, hi) -- the next window stages it again -- is
-	// marked too, into a counter nobody reads, and passes no other stage.  ord0 / tmpl0: the run's first record and template among all runs'
-	int records_pass(int which, const DevRun *r, uint8_t *rec, int64_t lo, int64_t counted, int64_t hi, int64_t ord0, int64_t tmpl0)
+	// The records pass: positions [lo, hi) of run r, on the context's stream.  rec + r->off[i] is record i: rec is the run's bytes, or the base of a
+	// staged slice.  [lo, counted) are counted; a record in [counted, hi) -- the next window stages it again -- is marked too, into a counter
+	// nobody reads, and passes no record stage.  ord0 / tmpl0: the run's first record and template among all runs'
+	int mark_pass(const DevRun *r, uint8_t *rec, int64_t lo, int64_t counted, int64_t hi, int64_t tmpl0)
 	{
 		int rc;
-		if (which & RS_MARK) {
-			if ((rc = markdup_mark_run(m->md.get(), c, rec, r->off() + lo, counted - lo, r->len, r->tmpl() + lo, tmpl0, r->n_tmpl))) return rc;
-			if (hi > counted && (rc = markdup_mark_run(m->md.get(), c, rec, r->off() + counted, hi - counted, r->len, r->tmpl() + counted, tmpl0, r->n_tmpl, sw.scratch.as<unsigned long long>()))) return rc;
-		}
-		if ((which & RS_QC) && (rc = qc_stage_records(m->qc.get(), c, rec, r->off() + lo, counted - lo, r->len, ord0 + lo))) return rc;
-		return which & RS_PILEUP ? pu_stage_records(m->pu.get(), c, rec, r->off() + lo, counted - lo, r->len, ord0 + lo) : 0;
+		if ((rc = markdup_mark_run(m->md.get(), c, rec, r->off() + lo, counted - lo, r->len, r->tmpl() + lo, tmpl0, r->n_tmpl))) return rc;
+		return hi > counted ? markdup_mark_run(m->md.get(), c, rec, r->off() + counted, hi - counted, r->len, r->tmpl() + counted, tmpl0, r->n_tmpl, sw.scratch.as<unsigned long long>()) : 0;
 	}
-	// The records pass is over for the stages `which`: each awaits the stream, the counters and the tables come back.  Without a spilled run that is
-	// before the order, stage by stage (resident_pass); with one, after the last window (tail)
-	int records_done(int which)
-	{
-		int rc = which & RS_MARK ? mark_end(m, plan.ms) : 0;
-		if (!rc && (which & RS_QC)) rc = qc_stage_finish(m->qc.get(), c, &qc_bytes, m->qc_stats);
-		if (!rc && (which & RS_PILEUP)) rc = pu_stage_finish(m->pu.get(), c, &pu_bytes, m->pu_stats);
-		return rc;
-	}
+	int stage_pass(RecordStage *s, const DevRun *r, const uint8_t *rec, int64_t lo, int64_t counted, int64_t ord0) { return s->records(c, rec, r->off() + lo, counted - lo, r->len, ord0 + lo); }
 	int checks()
 	{
 		if (plan.mark) for (auto &kv : m->runs) if (!kv.second->has_dup) return BWAHIP_EINVAL;   // before a byte is written
 		if (plan.mark && !m->md) m->md.reset(new MarkdupStage);
-		if (plan.qc && !m->qc) m->qc.reset(qc_stage_new());
-		if (plan.pileup && plan.spill) return BWAHIP_EINVAL;         // (the setters keep the two apart)
-		if (plan.pileup && !m->pu) m->pu.reset(pu_stage_new());
+		if (plan.spill) for (const RecordStage *s : rs) if (!s->takes_windows()) return BWAHIP_EINVAL;   // (the setters keep the two apart)
 		if (plan.index && !m->bai) m->bai.reset(bai_stage_new());
 		memset(&s, 0, sizeof s);
 		s.n_records = m->n_records; s.n_runs = (int64_t)m->runs.size(); s.raw_bytes = m->raw_bytes; s.n_blocks = bgzf_blocks(m->raw_bytes);
@@ -551,24 +526,32 @@ struct Finish {
 		n = (int)m->n_records; n_runs = (int)m->runs.size(); total = m->raw_bytes;
 		return 0;
 	}
-	// the resident runs' records pass, one stage after the other over all runs (a spilled run's records pass in the windows that stage them)
+	// One stage over all resident runs: it begins, every run passes (ord / tmpl: the run's first record and template among all runs'), and
+	// without a spilled run it ends here -- it awaits the stream, its counters or tables come back; with one, after the last window (tail)
+	template <class Begin, class Pass, class End> int resident_stage(Begin begin, Pass pass, End end)
+	{
+		int rc = begin();
+		int64_t ord = 0, tmpl = 0;
+		for (auto &kv : m->runs) {
+			const DevRun *r = kv.second;
+			if (!rc && !r->spilled) rc = pass(r, ord, tmpl);
+			ord += r->n_rec; tmpl += r->n_tmpl;
+		}
+		if (!rc && !plan.spill) rc = end();
+		return rc;
+	}
+	// the resident runs' records pass, one stage after the other over all runs: marking, which writes into the records, then the record stages
+	// (a spilled run's records pass in the windows that stage them)
 	int resident_pass()
 	{
-		for (int stage : { RS_MARK, RS_QC, RS_PILEUP }) {
-			if (!(stages() & stage)) continue;
-			int rc = stage == RS_MARK ? mark_decide(m) : stage == RS_QC ? qc_stage_begin(m->qc.get(), c, (int32_t)m->qc_len.size(), m->qc_len.data(), m->qc_opt, m->n_records) :
-			         pu_stage_begin(m->pu.get(), c, (int32_t)m->pu_len.size(), m->pu_len.data(), m->pu_own_pac ? nullptr : c->d_pac.as<uint8_t>(), m->pu_own_pac ? m->pu_pac.data() : nullptr,
-			                        m->pu_gen, m->pu_opt, m->n_records);
-			int64_t ord = 0, tmpl = 0;
-			for (auto &kv : m->runs) {
-				const DevRun *r = kv.second;
-				if (!rc && !r->spilled) rc = records_pass(stage, r, r->rec(), 0, r->n_rec, r->n_rec, ord, tmpl);
-				ord += r->n_rec; tmpl += r->n_tmpl;
-			}
-			if (!rc && !plan.spill) rc = records_done(stage);
-			if (rc) return rc;
-		}
-		return 0;
+		int rc = 0;
+		if (plan.mark)
+			rc = resident_stage([&] { return mark_decide(m); }, [&](const DevRun *r, int64_t, int64_t tmpl) { return mark_pass(r, r->rec(), 0, r->n_rec, r->n_rec, tmpl); },
+			                    [&] { return mark_end(m, plan.ms); });
+		for (RecordStage *s : rs)
+			if (!rc) rc = resident_stage([&] { return s->begin(c, m->n_records); }, [&](const DevRun *r, int64_t ord, int64_t) { return stage_pass(s, r, r->rec(), 0, r->n_rec, ord); },
+			                             [&] { return s->done(c); });
+		return rc;
 	}
 	// the order: the runs' keys in run order through the stable radix sort, with the ordinals 0 .. n - 1
 	int order()
@@ -715,7 +698,9 @@ struct Finish {
 			int64_t lo, counted, hi;
 			sp.slice(wd, r, &lo, &counted, &hi);
 			if (!runv[r]->spilled || hi <= lo) continue;
-			const int rc = records_pass(stages(), runv[r], reinterpret_cast<uint8_t*>((uintptr_t)base[(size_t)wd * NR + r]), lo, counted, hi, rec_at[r], tmpl_at[r]);
+			uint8_t *rec = reinterpret_cast<uint8_t*>((uintptr_t)base[(size_t)wd * NR + r]);
+			int rc = plan.mark ? mark_pass(runv[r], rec, lo, counted, hi, tmpl_at[r]) : 0;
+			for (RecordStage *s : rs) if (!rc) rc = stage_pass(s, runv[r], rec, lo, counted, rec_at[r]);
 			if (rc) return rc;
 		}
 		const int rec_lo = sp.first[(size_t)wd], rec_hi = wd + 1 < sp.n_windows ? sp.first[(size_t)wd + 1] : n - 1;
@@ -776,7 +761,7 @@ struct Finish {
 		if (hipEventElapsedTime(&ms, w.ev_deflate[b], w.ev_done[b]) == hipSuccess) s.deflate_ms += ms;
 		s.bgzf_bytes += got; s.n_stored += h_tot[2 * b + 1];
 		int rc;
-		if (fd >= 0 && (rc = write_full(fd, (const uint8_t*)w.h_out[b].p, got))) { (void)hipStreamSynchronize(c->stream); return rc; }
+		if ((rc = write_all(fd, w.h_out[b].p, got, "sorted BAM: writing the members"))) { (void)hipStreamSynchronize(c->stream); return rc; }
 		return 0;
 	}
 	// the piece loop: piece k is queued while piece k - 1 comes back and is written; then what the events and the buffers say
@@ -795,18 +780,18 @@ struct Finish {
 			if (hipEventElapsedTime(&ms, sw.ev_up0[(nw - 1 - k) & 1], sw.ev_up[(nw - 1 - k) & 1]) == hipSuccess) m->upload_ms += ms;
 		return 0;
 	}
-	// What follows the members, for the empty merger as well: the deferred end of the records pass, the index, the QC file, the stats
+	// What follows the members, for the empty merger as well: the deferred end of the records pass, the index, the record stages' files, the stats
 	int tail(bwahip_devmerge_stats_t *st)
 	{
-		int rc = plan.spill ? records_done(stages()) : 0;    // what the resident finish awaits before the order
+		int rc = plan.spill && plan.mark ? mark_end(m, plan.ms) : 0;   // what the resident finish awaits before the order
+		for (RecordStage *s : rs) if (!rc && plan.spill) rc = s->done(c);
 		if (!rc && plan.index) {
 			std::vector<uint8_t> bytes;
 			if (!total && n) rc = BWAHIP_EINVAL;                    // records without a byte cannot be indexed
 			else rc = bai_stage_run(m->bai.get(), c, n, w.addr.as<const uint8_t*>(), idx, w.out_off.as<int64_t>(), total, bgzf_blocks(total), plan.base, plan.n_ref, &bytes, plan.bs, parsed);
-			if (!rc) rc = bai_write_fd(plan.bai_fd, bytes);
+			if (!rc) rc = write_all(plan.bai_fd, bytes.data(), (int64_t)bytes.size(), "writing the BAI index");
 		}
-		if (!rc && plan.qc) rc = qc_write_fd(m->qc_fd, qc_bytes);
-		if (!rc && plan.pileup) rc = pu_write_fd(m->pu_fd, pu_bytes);
+		for (RecordStage *s : rs) if (!rc) rc = s->write();
 		s.finish_s = now_s() - t0;
 		if (st) *st = s;
 		return rc;
@@ -849,15 +834,39 @@ extern "C" int bwahip_bam_devmerger_finish_markdup(bwahip_bam_devmerger *m, int 
 	return bam_devmerger_finish(m, fd, st, FinishPlan{ n_ref >= 0, bai_fd, first_member_offset, n_ref, bs, true, ms });   // n_ref < 0: no index
 }
 
+int record_stage_kat(RecordStage *s, bwahip_ctx *c, const uint8_t *rec, const int64_t *rec_off, int64_t n_rec, uint8_t *out, int64_t out_cap, int64_t *out_len)
+{
+	for (int64_t i = 0; i < n_rec; ++i) if (rec_off[i] < 0 || rec_off[i + 1] < rec_off[i]) return BWAHIP_EINVAL;
+	HIP_TRY(hipSetDevice(c->device));
+	DevBuf d_rec, d_off;                                           // the caller's records
+	int rc = s->begin(c, n_rec);
+	if (!rc && n_rec) {
+		const size_t len = (size_t)rec_off[n_rec];
+		if (!(rc = d_rec.ensure(len + 1)) && !(rc = d_off.ensure(((size_t)n_rec + 1) * 8))) {
+			if ((len && hipMemcpyAsync(d_rec.p, rec, len, hipMemcpyHostToDevice, c->stream) != hipSuccess) ||
+			    hipMemcpyAsync(d_off.p, rec_off, ((size_t)n_rec + 1) * 8, hipMemcpyHostToDevice, c->stream) != hipSuccess) rc = BWAHIP_ENODEV;
+			if (!rc) rc = s->records(c, d_rec.as<uint8_t>(), d_off.as<int64_t>(), n_rec, (int64_t)len, 0);
+		}
+	}
+	if (!rc) rc = s->done(c);
+	(void)hipStreamSynchronize(c->stream);                         // nothing of the stage's buffers, or of these, is in use when they go
+	if (rc) return rc;
+	*out_len = (int64_t)s->bytes.size();
+	if (*out_len > out_cap) return BWAHIP_ECAPACITY;
+	memcpy(out, s->bytes.data(), s->bytes.size());
+	return 0;
+}
+
 extern "C" int bwahip_bam_devmerger_set_qc(bwahip_bam_devmerger *m, const bwahip_qc_opt_t *opt, int32_t n_ref, const int64_t *ref_len, int qc_fd, bwahip_qc_stats_t *qs)
 {
 	if (!m) return BWAHIP_EINVAL;
 	std::lock_guard<std::mutex> lk(m->mu);
-	if (!opt) { m->qc_armed = false; m->qc_stats = nullptr; return 0; }
+	if (!opt) { m->qc->armed = false; return 0; }
 	bwahip_qc_opt_t o;
 	int rc;
-	if ((rc = qc_resolve(opt, &o)) || (rc = qc_check_refs(n_ref, ref_len, nullptr))) return rc;   // the merger is as before
-	m->qc_opt = o; m->qc_len.assign(ref_len, ref_len + n_ref); m->qc_fd = qc_fd; m->qc_stats = qs; m->qc_armed = true;
+	if ((rc = qc_resolve(opt, &o)) || (rc = check_refs(n_ref, ref_len, nullptr, NO_SUM_CAP))) return rc;   // the merger is as before
+	qc_stage_set(m->qc.get(), o, n_ref, ref_len, qc_fd, qs);
+	m->qc->armed = true;
 	if (qs) memset(qs, 0, sizeof *qs);
 	return 0;
 }
@@ -867,21 +876,19 @@ extern "C" int bwahip_bam_devmerger_set_pileup(bwahip_bam_devmerger *m, const bw
 {
 	if (!m) return BWAHIP_EINVAL;
 	std::lock_guard<std::mutex> lk(m->mu);
-	if (!opt) { m->pu_armed = false; m->pu_stats = nullptr; return 0; }
-	if (m->spill_armed) return BWAHIP_EINVAL;                       // the evidence pass reads resident runs only
+	if (!opt) { m->pu->armed = false; return 0; }
+	if (m->spill_armed && !m->pu->takes_windows()) return BWAHIP_EINVAL;   // the evidence pass reads resident runs only
 	bwahip_pileup_opt_t o;
 	int64_t sum = 0;
 	int rc;
-	if ((rc = pu_resolve(opt, &o)) || (rc = pu_check_refs(n_ref, ref_len, &sum))) return rc;   // the merger is as before
+	if ((rc = pu_resolve(opt, &o)) || (rc = check_refs(n_ref, ref_len, &sum, PU_MAX_SUM))) return rc;   // the merger is as before
 	if (!pac) {                                                    // the context's index: these must be its contigs
 		const bwahip_bns_t &bns = m->c->host.bns;
 		if (n_ref != bns.n_seqs || sum != bns.l_pac || !m->c->d_pac.p) return BWAHIP_EINVAL;
 		for (int32_t r = 0; r < n_ref; ++r) if (ref_len[r] != bns.anns[r].len) return BWAHIP_EINVAL;
 	}
-	m->pu_opt = o; m->pu_len.assign(ref_len, ref_len + n_ref); m->pu_fd = pu_fd; m->pu_stats = ps; m->pu_own_pac = pac != nullptr;
-	if (pac) m->pu_pac.assign(pac, pac + (sum + 3) / 4); else m->pu_pac.clear();
-	++m->pu_gen;                                                   // the stage uploads the copy once
-	m->pu_armed = true;
+	pu_stage_set(m->pu.get(), o, n_ref, ref_len, pac, pu_fd, ps);   // (the stage copies pac and uploads the copy once)
+	m->pu->armed = true;
 	if (ps) memset(ps, 0, sizeof *ps);
 	return 0;
 }

@@ -29,6 +29,7 @@
 // is inside `if`s without a ballot -- and groups of one wavefront that are in different operations meet in the same ballot with their own bits.
 #include "ctx_internal.h"
 #include "pileup_tables.h"
+#include "sidecar_host.h"
 
 namespace {
 
@@ -58,7 +59,7 @@ template <bool EMIT> __device__ __forceinline__ uint32_t pu_walk16(const PuRec &
 	int64_t p = r.q.pos, q = 0;
 	uint32_t n_out = 0;
 	for (int32_t k = 0; k < r.q.n_cigar; ++k) {
-		const uint32_t w = qc_ld32(r.q.cig + 4 * k), op = w & 15;
+		const uint32_t w = bam_ld32(r.q.cig + 4 * k), op = w & 15;
 		const int64_t n = w >> 4;
 		if (pu_is_match(op)) {
 			const int64_t m = L - p < n ? (L - p > 0 ? L - p : 0) : n;   // the bases inside the contig
@@ -224,7 +225,7 @@ __global__ __launch_bounds__(256) void k_pu_evidence(const uint8_t *rec, const i
 	const bool all_pass = r.qual[0] == 0xff;
 	const uint32_t strand = r.q.flag >> 4 & 1;
 	for (int32_t k = 0; k < r.q.n_cigar && s < n_sites && p < L; ++k) {
-		const uint32_t w = qc_ld32(r.q.cig + 4 * k), op = w & 15;
+		const uint32_t w = bam_ld32(r.q.cig + 4 * k), op = w & 15;
 		const int64_t n = w >> 4;
 		const bool match = pu_is_match(op);
 		if (match || op == 2 || op == 3) {
@@ -249,90 +250,107 @@ inline unsigned blocks(int64_t threads) { return (unsigned)((threads + 255) / 25
 } // namespace
 
 // The stage's buffers.  cnt and obs_off are what bwahip_pileup_hbm_need counts; the others are made at the finish, when their sizes are known
-struct PileupStage {
+struct PileupStage final : RecordStage {
 	Tally hbm;
 	DevBuf cnt{hbm}, obs_off{hbm}, ref_tab{hbm}, tab{hbm}, pac{hbm};
 	DevBuf flag{hbm}, pos{hbm}, astart{hbm}, fr{hbm}, alleles{hbm}, sites{hbm};
-	DevBuf rec{hbm}, off{hbm};                                     // bwahip_kat_pileup alone: the caller's records
 	HostBuf h_tab;
 	Event ev[4];                                                   // begin, the keys written, the sites made, end
-	// the call in flight
+	// what pu_stage_set gave.  h_pac: the caller's packed reference (own_pac; otherwise the context's is read where it lies), h_pac_gen: counts the calls
 	bwahip_pileup_opt_t opt = { 0, 0, 1796, 2 };
-	std::vector<int64_t> ref_len, h_ref_tab;                       // h_ref_tab: lengths | first base (n_ref + 1)
-	int32_t n_ref = 0; int64_t n_records = 0;
+	std::vector<int64_t> ref_len;
+	int32_t n_ref = 0;
+	std::vector<uint8_t> h_pac; bool own_pac = false; uint64_t h_pac_gen = 0;
+	bwahip_pileup_stats_t *stats = nullptr;
+	// the call in flight
+	std::vector<int64_t> h_ref_tab;                                // lengths | first base (n_ref + 1)
+	int64_t n_records = 0;
 	const uint8_t *d_pac = nullptr; int64_t pac_bytes = 0;         // the packed reference in HBM: the context's, or `pac`
 	uint64_t pac_gen = 0;                                          // which of the caller's references `pac` holds (0: none)
 	struct Run { const uint8_t *rec; const int64_t *off; int64_t n_rec, ord0; };
 	std::vector<Run> runs;                                         // the runs that passed k_pu_count: emit and evidence read them again
 	const int64_t *d_len() const { return ref_tab.as<int64_t>(); }
 	const int64_t *d_off() const { return ref_tab.as<int64_t>() + n_ref; }
+	int begin(bwahip_ctx *c, int64_t n_records) override;
+	int records(bwahip_ctx *c, const uint8_t *rec, const int64_t *off, int64_t n_rec, int64_t len, int64_t ord0) override;
+	int done(bwahip_ctx *c) override;
+	int write() override { return write_all(fd, bytes.data(), (int64_t)bytes.size(), "writing the pileup"); }
+	bool takes_windows() const override { return false; }          // emit and evidence read the runs again
 };
 
-PileupStage *pu_stage_new() { return new PileupStage; }
-void pu_stage_free(PileupStage *s) { delete s; }
+RecordStage *pu_stage_new() { return new PileupStage; }
 
-int pu_stage_begin(PileupStage *s, bwahip_ctx *c, int32_t n_ref, const int64_t *ref_len, const uint8_t *d_pac, const uint8_t *h_pac, uint64_t h_pac_gen, const bwahip_pileup_opt_t &opt,
-                   int64_t n_records)
+void pu_stage_set(RecordStage *rs, const bwahip_pileup_opt_t &opt, int32_t n_ref, const int64_t *ref_len, const uint8_t *pac, int fd, bwahip_pileup_stats_t *ps)
 {
-	if (!s || !c || n_records < 0 || n_records > 0x7fffffffll) return BWAHIP_EINVAL;
+	PileupStage *s = static_cast<PileupStage*>(rs);
+	s->opt = opt; s->n_ref = n_ref; s->ref_len.assign(ref_len, ref_len + n_ref); s->fd = fd; s->stats = ps;
 	int64_t sum = 0;
+	for (int32_t r = 0; r < n_ref; ++r) sum += ref_len[r];
+	s->own_pac = pac != nullptr;
+	if (pac) s->h_pac.assign(pac, pac + (sum + 3) / 4); else s->h_pac.clear();
+	++s->h_pac_gen;                                                // begin uploads the copy once
+}
+
+int PileupStage::begin(bwahip_ctx *c, int64_t n_records_)
+{
+	if (!c || n_records_ < 0 || n_records_ > 0x7fffffffll) return BWAHIP_EINVAL;
 	int rc;
-	if ((rc = pu_check_refs(n_ref, ref_len, &sum))) return rc;
-	if (sum && !d_pac && !h_pac) return BWAHIP_EINVAL;
-	s->opt = opt; s->n_ref = n_ref; s->n_records = n_records;
-	s->ref_len.assign(ref_len, ref_len + n_ref);
-	s->h_ref_tab.assign(2 * (size_t)n_ref + 1, 0);
-	for (int32_t r = 0; r < n_ref; ++r) { s->h_ref_tab[(size_t)r] = ref_len[r]; s->h_ref_tab[(size_t)n_ref + r + 1] = s->h_ref_tab[(size_t)n_ref + r] + ref_len[r]; }
-	s->runs.clear();
-	s->pac_bytes = (sum + 3) / 4; s->d_pac = d_pac;
+	n_records = n_records_;
+	h_ref_tab.assign(2 * (size_t)n_ref + 1, 0);
+	for (int32_t r = 0; r < n_ref; ++r) { h_ref_tab[(size_t)r] = ref_len[(size_t)r]; h_ref_tab[(size_t)n_ref + r + 1] = h_ref_tab[(size_t)n_ref + r] + ref_len[(size_t)r]; }
+	const int64_t sum = h_ref_tab[2 * (size_t)n_ref];
+	d_pac = own_pac ? nullptr : c->d_pac.as<uint8_t>();
+	if (sum && !d_pac && !own_pac) return BWAHIP_EINVAL;
+	runs.clear();
+	pac_bytes = (sum + 3) / 4;
 	if (!n_records) return 0;                                      // no record: nothing to launch, finish writes the file of no site
 	HIP_TRY(hipSetDevice(c->device));
-	for (auto &e : s->ev) if (!e && (rc = e.make())) return rc;
+	for (auto &e : ev) if (!e && (rc = e.make())) return rc;
 	hipStream_t q = c->stream;
-	if ((rc = s->cnt.ensure(((size_t)n_records + 1) * 4)) || (rc = s->obs_off.ensure(((size_t)n_records + 1) * 8)) || (rc = s->tab.ensure(PU_T_WORDS * 8))) return rc;
-	HIP_TRY(hipEventRecord(s->ev[0], q));
-	if ((rc = dev_upload(s->ref_tab, s->h_ref_tab.data(), s->h_ref_tab.size() * 8, q))) return rc;
-	if (h_pac) {                                                   // uploaded once per generation (0: every time)
-		if (!h_pac_gen || h_pac_gen != s->pac_gen) { s->pac_gen = 0; if ((rc = dev_upload(s->pac, h_pac, (size_t)s->pac_bytes, q))) return rc; s->pac_gen = h_pac_gen; }
-		s->d_pac = s->pac.as<uint8_t>();
+	if ((rc = cnt.ensure(((size_t)n_records + 1) * 4)) || (rc = obs_off.ensure(((size_t)n_records + 1) * 8)) || (rc = tab.ensure(PU_T_WORDS * 8))) return rc;
+	HIP_TRY(hipEventRecord(ev[0], q));
+	if ((rc = dev_upload(ref_tab, h_ref_tab.data(), h_ref_tab.size() * 8, q))) return rc;
+	if (own_pac) {                                                 // uploaded once per generation
+		if (h_pac_gen != pac_gen) { pac_gen = 0; if ((rc = dev_upload(pac, h_pac.data(), (size_t)pac_bytes, q))) return rc; pac_gen = h_pac_gen; }
+		d_pac = pac.as<uint8_t>();
 	}
-	HIP_TRY(hipMemsetAsync(s->tab.p, 0, PU_T_WORDS * 8, q));
-	HIP_TRY(hipMemsetAsync(s->tab.as<unsigned long long>() + PU_T_ERR, 0xff, 8, q));
+	HIP_TRY(hipMemsetAsync(tab.p, 0, PU_T_WORDS * 8, q));
+	HIP_TRY(hipMemsetAsync(tab.as<unsigned long long>() + PU_T_ERR, 0xff, 8, q));
 	return 0;
 }
 
 // n_rec records of one run: record i = rec[off[i] .. off[i+1]) within the run's `len` bytes; ord0: the ordinal of its first record in the order
 // given.  The run is counted here and read again by the finish: it stays where it is until then
-int pu_stage_records(PileupStage *s, bwahip_ctx *c, const uint8_t *rec, const int64_t *off, int64_t n_rec, int64_t len, int64_t ord0)
+int PileupStage::records(bwahip_ctx *c, const uint8_t *rec, const int64_t *off, int64_t n_rec, int64_t len, int64_t ord0)
 {
 	if (!n_rec) return 0;
-	if (ord0 < 0 || ord0 + n_rec > s->n_records) return BWAHIP_EINTERNAL;
-	hipLaunchKernelGGL(k_pu_count, dim3(blocks(n_rec * 16)), dim3(256), 0, c->stream, rec, off, n_rec, len, ord0, (int)s->n_ref, s->d_len(), s->d_off(), s->d_pac, s->pac_bytes, s->opt,
-	                   s->cnt.as<int>(), s->tab.as<unsigned long long>());
-	s->runs.push_back({ rec, off, n_rec, ord0 });
+	if (ord0 < 0 || ord0 + n_rec > n_records) return BWAHIP_EINTERNAL;
+	hipLaunchKernelGGL(k_pu_count, dim3(blocks(n_rec * 16)), dim3(256), 0, c->stream, rec, off, n_rec, len, ord0, (int)n_ref, d_len(), d_off(), d_pac, pac_bytes, opt,
+	                   cnt.as<int>(), tab.as<unsigned long long>());
+	runs.push_back({ rec, off, n_rec, ord0 });
 	return launched();
 }
 
 // everything behind the count, the download (awaited) and the file's bytes; BWAHIP_EINVAL when a record was refused
-int pu_stage_finish(PileupStage *s, bwahip_ctx *c, std::vector<uint8_t> *bytes, bwahip_pileup_stats_t *ps)
+int PileupStage::done(bwahip_ctx *c)
 {
 	bwahip_pileup_stats_t st;
 	memset(&st, 0, sizeof st);
 	PuTables t;
-	t.n_ref = s->n_ref; t.ref_len = s->ref_len.data(); t.opt = s->opt;
+	t.n_ref = n_ref; t.ref_len = ref_len.data(); t.opt = opt;
 	int rc;
-	if (s->n_records) {
+	if (n_records) {
 		hipStream_t q = c->stream;
 		BamSort &bs = c->bs;
 		int64_t counted = 0;
-		for (const auto &r : s->runs) counted += r.n_rec;
-		if (counted != s->n_records) return BWAHIP_EINTERNAL;        // a record nobody counted has no slot
-		const int R = (int)s->n_records;
-		if ((rc = launch_scan(s->cnt.as<int>(), s->obs_off.as<int64_t>(), R, c->d_scan, q))) return rc;
+		for (const auto &r : runs) counted += r.n_rec;
+		if (counted != n_records) return BWAHIP_EINTERNAL;        // a record nobody counted has no slot
+		const int R = (int)n_records;
+		if ((rc = launch_scan(cnt.as<int>(), obs_off.as<int64_t>(), R, c->d_scan, q))) return rc;
 		unsigned long long tab[PU_T_WORDS];
 		int64_t N = 0;
-		HIP_TRY(hipMemcpyAsync(&N, s->obs_off.as<int64_t>() + R, 8, hipMemcpyDeviceToHost, q));
-		HIP_TRY(hipMemcpyAsync(tab, s->tab.p, sizeof tab, hipMemcpyDeviceToHost, q));
+		HIP_TRY(hipMemcpyAsync(&N, obs_off.as<int64_t>() + R, 8, hipMemcpyDeviceToHost, q));
+		HIP_TRY(hipMemcpyAsync(tab, this->tab.p, sizeof tab, hipMemcpyDeviceToHost, q));
 		HIP_TRY(hipStreamSynchronize(q));
 		if (tab[PU_T_ERR] != ~0ull) return BWAHIP_EINVAL;
 		if (N < 0 || N > PU_MAX_OBS) return BWAHIP_ECAPACITY;
@@ -340,31 +358,31 @@ int pu_stage_finish(PileupStage *s, bwahip_ctx *c, std::vector<uint8_t> *bytes, 
 		int n_all = 0, n_kept = 0, n_sites = 0, cur = 0;            // cur: which of the sort's two key buffers holds the sorted keys
 		if (n) {
 			if ((rc = bs.keys[0].ensure((size_t)n * 8)) || (rc = bs.keys[1].ensure((size_t)n * 8)) || (rc = bs.idx[0].ensure((size_t)n * 4)) || (rc = bs.idx[1].ensure((size_t)n * 4)) ||
-			    (rc = s->flag.ensure((size_t)n * 4)) || (rc = s->pos.ensure(((size_t)n + 1) * 8))) return rc;
-			for (const auto &r : s->runs) {
-				hipLaunchKernelGGL(k_pu_emit, dim3(blocks(r.n_rec * 16)), dim3(256), 0, q, r.rec, r.off, r.n_rec, r.ord0, (int)s->n_ref, s->d_len(), s->d_off(), s->d_pac, s->pac_bytes, s->opt,
-				                   s->obs_off.as<int64_t>(), bs.keys[0].as<unsigned long long>(), s->tab.as<unsigned long long>());
+			    (rc = this->flag.ensure((size_t)n * 4)) || (rc = this->pos.ensure(((size_t)n + 1) * 8))) return rc;
+			for (const auto &r : runs) {
+				hipLaunchKernelGGL(k_pu_emit, dim3(blocks(r.n_rec * 16)), dim3(256), 0, q, r.rec, r.off, r.n_rec, r.ord0, (int)n_ref, d_len(), d_off(), d_pac, pac_bytes, opt,
+				                   obs_off.as<int64_t>(), bs.keys[0].as<unsigned long long>(), this->tab.as<unsigned long long>());
 				if ((rc = launched())) return rc;
 			}
-			hipLaunchKernelGGL(k_pu_kinds, dim3(blocks(n) < 1024 ? blocks(n) : 1024), dim3(256), 0, q, bs.keys[0].as<unsigned long long>(), n, s->tab.as<unsigned long long>());
+			hipLaunchKernelGGL(k_pu_kinds, dim3(blocks(n) < 1024 ? blocks(n) : 1024), dim3(256), 0, q, bs.keys[0].as<unsigned long long>(), n, this->tab.as<unsigned long long>());
 			if ((rc = launched())) return rc;
 		}
-		HIP_TRY(hipEventRecord(s->ev[1], q));
+		HIP_TRY(hipEventRecord(ev[1], q));
 		if (n) {
 			if ((rc = bam_sort_radix(c, n, 64, &cur))) return rc;       // the ordinals in bs.idx are moved along and never read
 			const unsigned long long *keys = bs.keys[cur].as<unsigned long long>();
-			int *flag = s->flag.as<int>();
-			int64_t *pos = s->pos.as<int64_t>(), got = 0;
+			int *flag = this->flag.as<int>();
+			int64_t *pos = this->pos.as<int64_t>(), got = 0;
 			hipLaunchKernelGGL(k_pu_heads, dim3(blocks(n)), dim3(256), 0, q, keys, n, flag);
 			if ((rc = launched()) || (rc = launch_scan(flag, pos, n, c->d_scan, q))) return rc;
 			HIP_TRY(hipMemcpyAsync(&got, pos + n, 8, hipMemcpyDeviceToHost, q));
 			HIP_TRY(hipStreamSynchronize(q));
 			if (got < 1 || got > n) return BWAHIP_EINTERNAL;
 			n_all = (int)got;
-			if ((rc = s->astart.ensure(((size_t)n_all + 1) * 4)) || (rc = s->fr.ensure((size_t)n_all * 8))) return rc;
-			hipLaunchKernelGGL(k_pu_starts, dim3(blocks(n)), dim3(256), 0, q, flag, pos, n, s->astart.as<int>());
+			if ((rc = astart.ensure(((size_t)n_all + 1) * 4)) || (rc = fr.ensure((size_t)n_all * 8))) return rc;
+			hipLaunchKernelGGL(k_pu_starts, dim3(blocks(n)), dim3(256), 0, q, flag, pos, n, astart.as<int>());
 			if ((rc = launched())) return rc;
-			hipLaunchKernelGGL(k_pu_alleles, dim3(blocks(n_all)), dim3(256), 0, q, keys, s->astart.as<int>(), n_all, s->opt.min_alt, s->fr.as<uint2>(), flag);   // flag: now `keep`
+			hipLaunchKernelGGL(k_pu_alleles, dim3(blocks(n_all)), dim3(256), 0, q, keys, astart.as<int>(), n_all, opt.min_alt, fr.as<uint2>(), flag);   // flag: now `keep`
 			if ((rc = launched()) || (rc = launch_scan(flag, pos, n_all, c->d_scan, q))) return rc;
 			HIP_TRY(hipMemcpyAsync(&got, pos + n_all, 8, hipMemcpyDeviceToHost, q));
 			HIP_TRY(hipStreamSynchronize(q));
@@ -372,51 +390,51 @@ int pu_stage_finish(PileupStage *s, bwahip_ctx *c, std::vector<uint8_t> *bytes, 
 			n_kept = (int)got;
 		}
 		if (n_kept) {
-			if ((rc = s->alleles.ensure((size_t)n_kept * sizeof(PuAllele)))) return rc;
+			if ((rc = alleles.ensure((size_t)n_kept * sizeof(PuAllele)))) return rc;
 			const unsigned long long *keys = bs.keys[cur].as<unsigned long long>();
-			int *flag = s->flag.as<int>();
-			int64_t *pos = s->pos.as<int64_t>(), got = 0;
-			hipLaunchKernelGGL(k_pu_compact, dim3(blocks(n_all)), dim3(256), 0, q, keys, s->astart.as<int>(), s->fr.as<uint2>(), flag, pos, n_all, s->alleles.as<PuAllele>());
+			int *flag = this->flag.as<int>();
+			int64_t *pos = this->pos.as<int64_t>(), got = 0;
+			hipLaunchKernelGGL(k_pu_compact, dim3(blocks(n_all)), dim3(256), 0, q, keys, astart.as<int>(), fr.as<uint2>(), flag, pos, n_all, alleles.as<PuAllele>());
 			if ((rc = launched())) return rc;
-			hipLaunchKernelGGL(k_pu_site_heads, dim3(blocks(n_kept)), dim3(256), 0, q, s->alleles.as<PuAllele>(), n_kept, flag);   // flag: now the sites' heads
+			hipLaunchKernelGGL(k_pu_site_heads, dim3(blocks(n_kept)), dim3(256), 0, q, alleles.as<PuAllele>(), n_kept, flag);   // flag: now the sites' heads
 			if ((rc = launched()) || (rc = launch_scan(flag, pos, n_kept, c->d_scan, q))) return rc;
 			HIP_TRY(hipMemcpyAsync(&got, pos + n_kept, 8, hipMemcpyDeviceToHost, q));
 			HIP_TRY(hipStreamSynchronize(q));
 			if (got < 1 || got > n_kept) return BWAHIP_EINTERNAL;
 			n_sites = (int)got;
-			if ((rc = s->sites.ensure((size_t)n_sites * sizeof(PuSite)))) return rc;
-			hipLaunchKernelGGL(k_pu_sites, dim3(blocks(n_kept)), dim3(256), 0, q, s->alleles.as<PuAllele>(), flag, pos, n_kept, s->d_pac, s->pac_bytes, s->sites.as<PuSite>());
+			if ((rc = sites.ensure((size_t)n_sites * sizeof(PuSite)))) return rc;
+			hipLaunchKernelGGL(k_pu_sites, dim3(blocks(n_kept)), dim3(256), 0, q, alleles.as<PuAllele>(), flag, pos, n_kept, d_pac, pac_bytes, sites.as<PuSite>());
 			if ((rc = launched())) return rc;
 		}
-		HIP_TRY(hipEventRecord(s->ev[2], q));
-		for (size_t k = 0; n_sites && k < s->runs.size(); ++k) {
-			const auto &r = s->runs[k];
-			hipLaunchKernelGGL(k_pu_evidence, dim3(blocks(r.n_rec)), dim3(256), 0, q, r.rec, r.off, r.n_rec, (int)s->n_ref, s->d_len(), s->d_off(), s->opt, s->sites.as<PuSite>(), n_sites);
+		HIP_TRY(hipEventRecord(ev[2], q));
+		for (size_t k = 0; n_sites && k < runs.size(); ++k) {
+			const auto &r = runs[k];
+			hipLaunchKernelGGL(k_pu_evidence, dim3(blocks(r.n_rec)), dim3(256), 0, q, r.rec, r.off, r.n_rec, (int)n_ref, d_len(), d_off(), opt, sites.as<PuSite>(), n_sites);
 			if ((rc = launched())) return rc;
 		}
-		HIP_TRY(hipEventRecord(s->ev[3], q));
+		HIP_TRY(hipEventRecord(ev[3], q));
 		const size_t a_bytes = (size_t)n_kept * sizeof(PuAllele), s_bytes = (size_t)n_sites * sizeof(PuSite);
-		if ((rc = s->h_tab.ensure(a_bytes + s_bytes + 8))) return rc;
-		uint8_t *h = (uint8_t*)s->h_tab.p;
-		if (a_bytes) HIP_TRY(hipMemcpyAsync(h, s->alleles.p, a_bytes, hipMemcpyDeviceToHost, q));
-		if (s_bytes) HIP_TRY(hipMemcpyAsync(h + a_bytes, s->sites.p, s_bytes, hipMemcpyDeviceToHost, q));
-		HIP_TRY(hipMemcpyAsync(tab, s->tab.p, sizeof tab, hipMemcpyDeviceToHost, q));
+		if ((rc = h_tab.ensure(a_bytes + s_bytes + 8))) return rc;
+		uint8_t *h = (uint8_t*)h_tab.p;
+		if (a_bytes) HIP_TRY(hipMemcpyAsync(h, alleles.p, a_bytes, hipMemcpyDeviceToHost, q));
+		if (s_bytes) HIP_TRY(hipMemcpyAsync(h + a_bytes, sites.p, s_bytes, hipMemcpyDeviceToHost, q));
+		HIP_TRY(hipMemcpyAsync(tab, this->tab.p, sizeof tab, hipMemcpyDeviceToHost, q));
 		HIP_TRY(hipStreamSynchronize(q));
 		if (tab[PU_T_SLOTS] || (uint64_t)N != tab[0] + tab[1] + tab[2]) { fprintf(stderr, "[bwahip] pileup: a record's observations were counted and written differently\n"); return BWAHIP_EINTERNAL; }
 		for (int k = 0; k < 3; ++k) t.n_obs[k] = tab[k];
 		t.n_alleles = n_kept; t.alleles = (const PuAllele*)h; t.n_sites = n_sites; t.sites = (const PuSite*)(h + a_bytes);
-		if ((rc = pu_serialise(t, bytes))) return rc == BWAHIP_EINVAL ? BWAHIP_EINTERNAL : rc;
+		if ((rc = pu_serialise(t, &bytes))) return rc == BWAHIP_EINVAL ? BWAHIP_EINTERNAL : rc;
 		float ms = 0;
-		if (hipEventElapsedTime(&ms, s->ev[0], s->ev[3]) == hipSuccess) st.pileup_ms = ms;
-		if (hipEventElapsedTime(&ms, s->ev[0], s->ev[1]) == hipSuccess) st.observe_ms = ms;
-		if (hipEventElapsedTime(&ms, s->ev[1], s->ev[2]) == hipSuccess) st.sort_ms = ms;
-		if (hipEventElapsedTime(&ms, s->ev[2], s->ev[3]) == hipSuccess) st.evidence_ms = ms;
-		st.hbm_bytes = (int64_t)(s->hbm.bytes + (n ? bs.keys[0].cap + bs.keys[1].cap + bs.idx[0].cap + bs.idx[1].cap : 0));
-	} else if ((rc = pu_serialise(t, bytes))) return rc;
+		if (hipEventElapsedTime(&ms, ev[0], ev[3]) == hipSuccess) st.pileup_ms = ms;
+		if (hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess) st.observe_ms = ms;
+		if (hipEventElapsedTime(&ms, ev[1], ev[2]) == hipSuccess) st.sort_ms = ms;
+		if (hipEventElapsedTime(&ms, ev[2], ev[3]) == hipSuccess) st.evidence_ms = ms;
+		st.hbm_bytes = (int64_t)(hbm.bytes + (n ? bs.keys[0].cap + bs.keys[1].cap + bs.idx[0].cap + bs.idx[1].cap : 0));
+	} else if ((rc = pu_serialise(t, &bytes))) return rc;
 	st.n_sites = t.n_sites; st.n_alleles = t.n_alleles;
 	for (int k = 0; k < 3; ++k) st.n_obs[k] = (int64_t)t.n_obs[k];
-	st.pu_bytes = (int64_t)bytes->size();
-	if (ps) *ps = st;
+	st.pu_bytes = (int64_t)bytes.size();
+	if (stats) *stats = st;
 	return 0;
 }
 
@@ -429,26 +447,9 @@ extern "C" int bwahip_kat_pileup(bwahip_ctx *c, const uint8_t *rec, const int64_
 	bwahip_pileup_opt_t o;
 	int64_t sum = 0;
 	int rc;
-	if ((rc = pu_resolve(opt, &o)) || (rc = pu_check_refs(n_ref, ref_len, &sum))) return rc;
+	if ((rc = pu_resolve(opt, &o)) || (rc = check_refs(n_ref, ref_len, &sum, PU_MAX_SUM))) return rc;
 	if (sum && !pac) return BWAHIP_EINVAL;
-	for (int64_t i = 0; i < n_rec; ++i) if (rec_off[i] < 0 || rec_off[i + 1] < rec_off[i]) return BWAHIP_EINVAL;
-	HIP_TRY(hipSetDevice(c->device));
 	PileupStage s;
-	std::vector<uint8_t> bytes;
-	rc = pu_stage_begin(&s, c, n_ref, ref_len, nullptr, sum ? pac : nullptr, 0, o, n_rec);
-	if (!rc && n_rec) {
-		const size_t len = (size_t)rec_off[n_rec];
-		if (!(rc = s.rec.ensure(len + 1)) && !(rc = s.off.ensure(((size_t)n_rec + 1) * 8))) {
-			if ((len && hipMemcpyAsync(s.rec.p, rec, len, hipMemcpyHostToDevice, c->stream) != hipSuccess) ||
-			    hipMemcpyAsync(s.off.p, rec_off, ((size_t)n_rec + 1) * 8, hipMemcpyHostToDevice, c->stream) != hipSuccess) rc = BWAHIP_ENODEV;
-			if (!rc) rc = pu_stage_records(&s, c, s.rec.as<uint8_t>(), s.off.as<int64_t>(), n_rec, (int64_t)len, 0);
-		}
-	}
-	if (!rc) rc = pu_stage_finish(&s, c, &bytes, nullptr);
-	(void)hipStreamSynchronize(c->stream);                         // nothing of the stage's buffers is in use when they go
-	if (rc) return rc;
-	*out_len = (int64_t)bytes.size();
-	if (*out_len > out_cap) return BWAHIP_ECAPACITY;
-	memcpy(out, bytes.data(), bytes.size());
-	return 0;
+	pu_stage_set(&s, o, n_ref, ref_len, sum ? pac : nullptr, -1, nullptr);
+	return record_stage_kat(&s, c, rec, rec_off, n_rec, out, out_cap, out_len);
 }

@@ -21,6 +21,7 @@
 // that declares them; no pointer into LDS is passed on.
 #include "ctx_internal.h"
 #include "qc_tables.h"
+#include "sidecar_host.h"
 
 namespace {
 
@@ -181,113 +182,124 @@ int launched() { return hipGetLastError() == hipSuccess ? 0 : BWAHIP_ENODEV; }
 } // namespace
 
 // The stage's buffers: counted by bwahip_qc_hbm_need (qc_host.cpp)
-struct QcStage {
+struct QcStage final : RecordStage {
 	Tally hbm;
 	DevBuf diff{hbm}, tile_sum{hbm}, tile_pref{hbm}, tile_ref{hbm}, ref_tab{hbm}, tab{hbm}, err{hbm};
-	DevBuf rec{hbm}, off{hbm};                                     // bwahip_kat_qc alone: the caller's records
 	HostBuf h_tab;
 	Event ev[4];                                                   // begin, cleared, records done, end
-	// the layout of the call in flight
+	// what qc_stage_set gave
 	bwahip_qc_opt_t opt = { 14, 1796, 0 };
-	std::vector<int64_t> ref_len, h_ref_tab;                       // h_ref_tab: lengths | first tile (n_ref + 1) | first window (n_ref + 1)
+	std::vector<int64_t> ref_len;
+	int32_t n_ref = 0;
+	bwahip_qc_stats_t *stats = nullptr;
+	// the layout of the call in flight
+	std::vector<int64_t> h_ref_tab;                                // lengths | first tile (n_ref + 1) | first window (n_ref + 1)
 	std::vector<int> h_tile_ref;
-	int32_t n_ref = 0; int64_t n_tiles = 0, n_win = 0, n_records = 0;
+	int64_t n_tiles = 0, n_win = 0, n_records = 0;
 	const int64_t *d_len() const { return ref_tab.as<int64_t>(); }
 	const int64_t *d_tile0() const { return ref_tab.as<int64_t>() + n_ref; }
 	const int64_t *d_win_off() const { return ref_tab.as<int64_t>() + 2 * (size_t)n_ref + 1; }
 	unsigned long long *d_win() const { return tab.as<unsigned long long>() + QC_FIXED + QC_PER_REF * (size_t)n_ref; }
 	size_t tab_words() const { return (size_t)QC_FIXED + QC_PER_REF * (size_t)n_ref + (size_t)n_win; }
+	int begin(bwahip_ctx *c, int64_t n_records) override;
+	int records(bwahip_ctx *c, const uint8_t *rec, const int64_t *off, int64_t n_rec, int64_t len, int64_t ord0) override;
+	int done(bwahip_ctx *c) override;
+	int write() override { return write_all(fd, bytes.data(), (int64_t)bytes.size(), "writing the QC summary"); }
+	bool takes_windows() const override { return true; }
 };
 
-QcStage *qc_stage_new() { return new QcStage; }
-void qc_stage_free(QcStage *s) { delete s; }
+RecordStage *qc_stage_new() { return new QcStage; }
 
-int qc_stage_begin(QcStage *s, bwahip_ctx *c, int32_t n_ref, const int64_t *ref_len, const bwahip_qc_opt_t &opt, int64_t n_records)
+void qc_stage_set(RecordStage *rs, const bwahip_qc_opt_t &opt, int32_t n_ref, const int64_t *ref_len, int fd, bwahip_qc_stats_t *qs)
 {
-	if (!s || !c || n_records < 0) return BWAHIP_EINVAL;
+	QcStage *s = static_cast<QcStage*>(rs);
+	s->opt = opt; s->n_ref = n_ref; s->ref_len.assign(ref_len, ref_len + n_ref); s->fd = fd; s->stats = qs;
+}
+
+int QcStage::begin(bwahip_ctx *c, int64_t n_records_)
+{
+	if (!c || n_records_ < 0) return BWAHIP_EINVAL;
 	int rc;
-	if ((rc = qc_check_refs(n_ref, ref_len, nullptr))) return rc;
-	s->opt = opt; s->n_ref = n_ref; s->n_records = n_records;
-	s->ref_len.assign(ref_len, ref_len + n_ref);
-	s->h_ref_tab.assign(3 * (size_t)n_ref + 2, 0);
-	int64_t *tile0 = s->h_ref_tab.data() + n_ref, *win_off = tile0 + n_ref + 1;
+	n_records = n_records_;
+	h_ref_tab.assign(3 * (size_t)n_ref + 2, 0);
+	int64_t *tile0 = h_ref_tab.data() + n_ref, *win_off = tile0 + n_ref + 1;
 	for (int32_t r = 0; r < n_ref; ++r) {
-		s->h_ref_tab[(size_t)r] = ref_len[r];
+		h_ref_tab[(size_t)r] = ref_len[r];
 		tile0[r + 1] = tile0[r] + (ref_len[r] + 1 + QC_TILE - 1) / QC_TILE;
 		win_off[r + 1] = win_off[r] + qc_windows(ref_len[r], opt.window_shift);
 	}
-	s->n_tiles = tile0[n_ref]; s->n_win = win_off[n_ref];
-	if (s->n_tiles > 0x7fffffffll) return BWAHIP_ECAPACITY;         // the scan of the tile sums takes an int
+	n_tiles = tile0[n_ref]; n_win = win_off[n_ref];
+	if (n_tiles > 0x7fffffffll) return BWAHIP_ECAPACITY;         // the scan of the tile sums takes an int
 	if (!n_records) return 0;                                      // no record: nothing to launch, finish writes the empty summary
-	s->h_tile_ref.resize((size_t)s->n_tiles);
-	for (int32_t r = 0; r < n_ref; ++r) for (int64_t k = tile0[r]; k < tile0[r + 1]; ++k) s->h_tile_ref[(size_t)k] = r;
+	h_tile_ref.resize((size_t)n_tiles);
+	for (int32_t r = 0; r < n_ref; ++r) for (int64_t k = tile0[r]; k < tile0[r + 1]; ++k) h_tile_ref[(size_t)k] = r;
 	HIP_TRY(hipSetDevice(c->device));
-	for (auto &e : s->ev) if (!e && (rc = e.make())) return rc;
+	for (auto &e : ev) if (!e && (rc = e.make())) return rc;
 	hipStream_t q = c->stream;
-	const size_t T = (size_t)s->n_tiles;                           // (0 without a reference: the records are still judged and counted)
-	if ((rc = s->diff.ensure((T ? T : 1) * QC_TILE * 4)) || (rc = s->tile_sum.ensure(T * 4)) || (rc = s->tile_pref.ensure((T + 1) * 8)) || (rc = s->tab.ensure(s->tab_words() * 8)) ||
-	    (rc = s->err.ensure(8)) || (rc = s->h_tab.ensure(s->tab_words() * 8 + 8))) return rc;
-	HIP_TRY(hipEventRecord(s->ev[0], q));
-	if ((rc = dev_upload(s->ref_tab, s->h_ref_tab.data(), s->h_ref_tab.size() * 8, q)) || (rc = dev_upload(s->tile_ref, s->h_tile_ref.data(), T * 4, q))) return rc;
-	if (T) HIP_TRY(hipMemsetAsync(s->diff.p, 0, T * QC_TILE * 4, q));
-	HIP_TRY(hipMemsetAsync(s->tab.p, 0, s->tab_words() * 8, q));
-	HIP_TRY(hipMemsetAsync(s->err.p, 0xff, 8, q));
-	HIP_TRY(hipEventRecord(s->ev[1], q));
+	const size_t T = (size_t)n_tiles;                           // (0 without a reference: the records are still judged and counted)
+	if ((rc = diff.ensure((T ? T : 1) * QC_TILE * 4)) || (rc = tile_sum.ensure(T * 4)) || (rc = tile_pref.ensure((T + 1) * 8)) || (rc = tab.ensure(tab_words() * 8)) ||
+	    (rc = err.ensure(8)) || (rc = h_tab.ensure(tab_words() * 8 + 8))) return rc;
+	HIP_TRY(hipEventRecord(ev[0], q));
+	if ((rc = dev_upload(ref_tab, h_ref_tab.data(), h_ref_tab.size() * 8, q)) || (rc = dev_upload(tile_ref, h_tile_ref.data(), T * 4, q))) return rc;
+	if (T) HIP_TRY(hipMemsetAsync(diff.p, 0, T * QC_TILE * 4, q));
+	HIP_TRY(hipMemsetAsync(tab.p, 0, tab_words() * 8, q));
+	HIP_TRY(hipMemsetAsync(err.p, 0xff, 8, q));
+	HIP_TRY(hipEventRecord(ev[1], q));
 	return 0;
 }
 
 // n_rec records of one run: record i = rec[off[i] .. off[i+1]) within the run's `len` bytes; ord0: the ordinal of its first record in the order given
-int qc_stage_records(QcStage *s, bwahip_ctx *c, const uint8_t *rec, const int64_t *off, int64_t n_rec, int64_t len, int64_t ord0)
+int QcStage::records(bwahip_ctx *c, const uint8_t *rec, const int64_t *off, int64_t n_rec, int64_t len, int64_t ord0)
 {
 	if (!n_rec) return 0;
 	if (n_rec > 0x7fffffffll) return BWAHIP_ECAPACITY;
-	hipLaunchKernelGGL(k_qc_rec, dim3((unsigned)((n_rec + 255) / 256)), dim3(256), 0, c->stream, rec, off, n_rec, len, ord0, (int)s->n_ref, s->d_len(), s->d_tile0(), s->opt,
-	                   s->tab.as<unsigned long long>(), s->diff.as<int>(), s->err.as<unsigned long long>());
+	hipLaunchKernelGGL(k_qc_rec, dim3((unsigned)((n_rec + 255) / 256)), dim3(256), 0, c->stream, rec, off, n_rec, len, ord0, (int)n_ref, d_len(), d_tile0(), opt,
+	                   tab.as<unsigned long long>(), diff.as<int>(), err.as<unsigned long long>());
 	return launched();
 }
 
 // the scan, the download (awaited) and the summary's bytes; BWAHIP_EINVAL when a record was refused
-int qc_stage_finish(QcStage *s, bwahip_ctx *c, std::vector<uint8_t> *bytes, bwahip_qc_stats_t *qs)
+int QcStage::done(bwahip_ctx *c)
 {
 	bwahip_qc_stats_t st;
 	memset(&st, 0, sizeof st);
 	QcTables t;
-	t.n_ref = s->n_ref; t.ref_len = s->ref_len.data(); t.opt = s->opt;
+	t.n_ref = n_ref; t.ref_len = ref_len.data(); t.opt = opt;
 	int rc;
-	if (!s->n_records) {                                           // every base has depth 0
-		std::vector<uint64_t> z(s->tab_words(), 0);
-		for (int64_t L : s->ref_len) z[QC_DEPTH] += (uint64_t)L;
-		t.fixed = z.data(); t.per_ref = z.data() + QC_FIXED; t.win = z.data() + QC_FIXED + QC_PER_REF * (size_t)s->n_ref;
-		if ((rc = qc_serialise(t, bytes))) return rc;
+	if (!n_records) {                                           // every base has depth 0
+		std::vector<uint64_t> z(tab_words(), 0);
+		for (int64_t L : ref_len) z[QC_DEPTH] += (uint64_t)L;
+		t.fixed = z.data(); t.per_ref = z.data() + QC_FIXED; t.win = z.data() + QC_FIXED + QC_PER_REF * (size_t)n_ref;
+		if ((rc = qc_serialise(t, &bytes))) return rc;
 	} else {
 		hipStream_t q = c->stream;
-		HIP_TRY(hipEventRecord(s->ev[2], q));
-		const unsigned T = (unsigned)s->n_tiles;
+		HIP_TRY(hipEventRecord(ev[2], q));
+		const unsigned T = (unsigned)n_tiles;
 		if (T) {
 			const int chunk = T > 4 * 8192 ? (int)((T + 8191) / 8192) : 4;   // up to 8192 workgroups, each at least four tiles
 			const unsigned grid = (T + (unsigned)chunk - 1) / (unsigned)chunk;
-			hipLaunchKernelGGL(k_qc_tile_sum, dim3(grid), dim3(256), 0, q, s->diff.as<int>(), s->tile_sum.as<int>(), (int)T, chunk);
-			if ((rc = launched()) || (rc = launch_scan(s->tile_sum.as<int>(), s->tile_pref.as<int64_t>(), (int)T, c->d_scan, q))) return rc;
-			hipLaunchKernelGGL(k_qc_tile_scan, dim3(grid), dim3(256), 0, q, s->diff.as<int>(), s->tile_pref.as<int64_t>(), s->tile_ref.as<int>(), s->d_len(), s->d_tile0(), s->d_win_off(),
-			                   s->opt.window_shift, s->tab.as<unsigned long long>(), s->d_win(), (int)T, chunk);
+			hipLaunchKernelGGL(k_qc_tile_sum, dim3(grid), dim3(256), 0, q, diff.as<int>(), tile_sum.as<int>(), (int)T, chunk);
+			if ((rc = launched()) || (rc = launch_scan(tile_sum.as<int>(), tile_pref.as<int64_t>(), (int)T, c->d_scan, q))) return rc;
+			hipLaunchKernelGGL(k_qc_tile_scan, dim3(grid), dim3(256), 0, q, diff.as<int>(), tile_pref.as<int64_t>(), tile_ref.as<int>(), d_len(), d_tile0(), d_win_off(),
+			                   opt.window_shift, tab.as<unsigned long long>(), d_win(), (int)T, chunk);
 			if ((rc = launched())) return rc;
 		}
-		HIP_TRY(hipEventRecord(s->ev[3], q));
-		uint64_t *h = (uint64_t*)s->h_tab.p;
-		HIP_TRY(hipMemcpyAsync(h, s->tab.p, s->tab_words() * 8, hipMemcpyDeviceToHost, q));
-		HIP_TRY(hipMemcpyAsync(h + s->tab_words(), s->err.p, 8, hipMemcpyDeviceToHost, q));
+		HIP_TRY(hipEventRecord(ev[3], q));
+		uint64_t *h = (uint64_t*)h_tab.p;
+		HIP_TRY(hipMemcpyAsync(h, tab.p, tab_words() * 8, hipMemcpyDeviceToHost, q));
+		HIP_TRY(hipMemcpyAsync(h + tab_words(), err.p, 8, hipMemcpyDeviceToHost, q));
 		HIP_TRY(hipStreamSynchronize(q));
-		if (h[s->tab_words()] != ~0ull) return BWAHIP_EINVAL;
-		t.fixed = h; t.per_ref = h + QC_FIXED; t.win = h + QC_FIXED + QC_PER_REF * (size_t)s->n_ref;
-		if ((rc = qc_serialise(t, bytes))) return rc == BWAHIP_EINVAL ? BWAHIP_EINTERNAL : rc;
+		if (h[tab_words()] != ~0ull) return BWAHIP_EINVAL;
+		t.fixed = h; t.per_ref = h + QC_FIXED; t.win = h + QC_FIXED + QC_PER_REF * (size_t)n_ref;
+		if ((rc = qc_serialise(t, &bytes))) return rc == BWAHIP_EINVAL ? BWAHIP_EINTERNAL : rc;
 		float ms = 0;
-		if (hipEventElapsedTime(&ms, s->ev[0], s->ev[3]) == hipSuccess) st.qc_ms = ms;
-		if (hipEventElapsedTime(&ms, s->ev[1], s->ev[2]) == hipSuccess) st.record_ms = ms;
-		if (hipEventElapsedTime(&ms, s->ev[2], s->ev[3]) == hipSuccess) st.scan_ms = ms;
-		st.hbm_bytes = (int64_t)s->hbm.bytes;
+		if (hipEventElapsedTime(&ms, ev[0], ev[3]) == hipSuccess) st.qc_ms = ms;
+		if (hipEventElapsedTime(&ms, ev[1], ev[2]) == hipSuccess) st.record_ms = ms;
+		if (hipEventElapsedTime(&ms, ev[2], ev[3]) == hipSuccess) st.scan_ms = ms;
+		st.hbm_bytes = (int64_t)hbm.bytes;
 	}
-	st.n_windows = s->n_win; st.qc_bytes = (int64_t)bytes->size();
-	if (qs) *qs = st;
+	st.n_windows = n_win; st.qc_bytes = (int64_t)bytes.size();
+	if (stats) *stats = st;
 	return 0;
 }
 
@@ -299,25 +311,8 @@ extern "C" int bwahip_kat_qc(bwahip_ctx *c, const uint8_t *rec, const int64_t *r
 	*out_len = 0;
 	bwahip_qc_opt_t o;
 	int rc;
-	if ((rc = qc_resolve(opt, &o)) || (rc = qc_check_refs(n_ref, ref_len, nullptr))) return rc;
-	for (int64_t i = 0; i < n_rec; ++i) if (rec_off[i] < 0 || rec_off[i + 1] < rec_off[i]) return BWAHIP_EINVAL;
-	HIP_TRY(hipSetDevice(c->device));
+	if ((rc = qc_resolve(opt, &o)) || (rc = check_refs(n_ref, ref_len, nullptr, NO_SUM_CAP))) return rc;
 	QcStage s;
-	std::vector<uint8_t> bytes;
-	rc = qc_stage_begin(&s, c, n_ref, ref_len, o, n_rec);
-	if (!rc && n_rec) {
-		const size_t len = (size_t)rec_off[n_rec];
-		if (!(rc = s.rec.ensure(len + 1)) && !(rc = s.off.ensure(((size_t)n_rec + 1) * 8))) {
-			if ((len && hipMemcpyAsync(s.rec.p, rec, len, hipMemcpyHostToDevice, c->stream) != hipSuccess) ||
-			    hipMemcpyAsync(s.off.p, rec_off, ((size_t)n_rec + 1) * 8, hipMemcpyHostToDevice, c->stream) != hipSuccess) rc = BWAHIP_ENODEV;
-			if (!rc) rc = qc_stage_records(&s, c, s.rec.as<uint8_t>(), s.off.as<int64_t>(), n_rec, (int64_t)len, 0);
-		}
-	}
-	if (!rc) rc = qc_stage_finish(&s, c, &bytes, nullptr);
-	(void)hipStreamSynchronize(c->stream);                         // nothing of the stage's buffers is in use when they go
-	if (rc) return rc;
-	*out_len = (int64_t)bytes.size();
-	if (*out_len > out_cap) return BWAHIP_ECAPACITY;
-	memcpy(out, bytes.data(), bytes.size());
-	return 0;
+	qc_stage_set(&s, o, n_ref, ref_len, -1, nullptr);
+	return record_stage_kat(&s, c, rec, rec_off, n_rec, out, out_cap, out_len);
 }

@@ -4,17 +4,8 @@
 // per base, made at the first such record), every observation as its 64-bit key, and a copy of the packed reference; finish() sorts the
 // keys, and alleles, strand counts and sites are runs of the sorted keys.  A judge and a library for small inputs: nothing falls back on it.
 #include "pileup_tables.h"
-#include <errno.h>
-#include <stdio.h>
-#include <unistd.h>
+#include "sidecar_host.h"
 #include <algorithm>
-
-namespace {
-
-void put32(std::vector<uint8_t> &o, uint32_t v) { for (int k = 0; k < 4; ++k) o.push_back((uint8_t)(v >> (8 * k))); }
-void put64(std::vector<uint8_t> &o, uint64_t v) { for (int k = 0; k < 8; ++k) o.push_back((uint8_t)(v >> (8 * k))); }
-
-} // namespace
 
 int pu_resolve(const bwahip_pileup_opt_t *in, bwahip_pileup_opt_t *out)
 {
@@ -26,16 +17,6 @@ int pu_resolve(const bwahip_pileup_opt_t *in, bwahip_pileup_opt_t *out)
 		if (in->min_alt) o.min_alt = in->min_alt;
 	}
 	*out = o;
-	return 0;
-}
-
-int pu_check_refs(int32_t n_ref, const int64_t *ref_len, int64_t *sum_len)
-{
-	if (n_ref < 0 || (n_ref && !ref_len)) return BWAHIP_EINVAL;
-	int64_t s = 0;
-	for (int32_t r = 0; r < n_ref; ++r) { if (ref_len[r] < 0 || ref_len[r] > 0x7fffffffll) return BWAHIP_EINVAL; s += ref_len[r]; }
-	if (s >= PU_MAX_SUM) return BWAHIP_ECAPACITY;
-	if (sum_len) *sum_len = s;
 	return 0;
 }
 
@@ -66,22 +47,8 @@ int pu_serialise(const PuTables &t, std::vector<uint8_t> *out)
 	return 0;
 }
 
-int pu_write_fd(int fd, const std::vector<uint8_t> &b)
-{
-	for (size_t o = 0; fd >= 0 && o < b.size();) {
-		const ssize_t w = write(fd, b.data() + o, b.size() - o);
-		if (w < 0) { if (errno == EINTR) continue; fprintf(stderr, "[bwahip] writing the pileup failed: %s\n", strerror(errno)); return BWAHIP_EIO; }
-		if (w == 0) return BWAHIP_EIO;
-		o += (size_t)w;
-	}
-	return 0;
-}
-
-struct bwahip_pileup_builder {
-	int32_t n_ref = 0; bwahip_pileup_opt_t opt = { 0, 0, 1796, 2 };
-	int err = 0; bool finished = false;
-	std::vector<int64_t> ref_len, ref_off;
-	std::vector<uint8_t> pac;
+struct bwahip_pileup_builder : SidecarBuilder {
+	bwahip_pileup_opt_t opt = { 0, 0, 1796, 2 };
 	std::vector<std::vector<uint32_t>> ev;                         // per reference 3 words per base (n_cov, n_ref_fwd, n_ref_rev), empty until a record covers it
 	std::vector<uint64_t> keys;                                    // the observations
 };
@@ -93,14 +60,10 @@ extern "C" int bwahip_pileup_builder_open(int32_t n_ref, const int64_t *ref_len,
 	bwahip_pileup_opt_t o;
 	int64_t sum = 0;
 	int rc;
-	if ((rc = pu_check_refs(n_ref, ref_len, &sum)) || (rc = pu_resolve(opt, &o))) return rc;
+	if ((rc = check_refs(n_ref, ref_len, &sum, PU_MAX_SUM)) || (rc = pu_resolve(opt, &o))) return rc;
 	if (sum && !pac) return BWAHIP_EINVAL;
 	bwahip_pileup_builder *b = new bwahip_pileup_builder;
-	b->n_ref = n_ref; b->opt = o;
-	b->ref_len.assign(ref_len, ref_len + n_ref);
-	b->ref_off.assign((size_t)n_ref + 1, 0);
-	for (int32_t r = 0; r < n_ref; ++r) b->ref_off[(size_t)r + 1] = b->ref_off[(size_t)r] + ref_len[r];
-	if (sum) b->pac.assign(pac, pac + (sum + 3) / 4);
+	b->set_refs(n_ref, ref_len, sum ? pac : nullptr); b->opt = o;
 	b->ev.resize((size_t)n_ref);
 	*out = b;
 	return 0;
@@ -109,7 +72,7 @@ extern "C" int bwahip_pileup_builder_open(int32_t n_ref, const int64_t *ref_len,
 static int pu_builder_add_one(bwahip_pileup_builder *b, const uint8_t *rec, int64_t len)
 {
 	PuRec r;
-	if (len < 0 || !pu_parse(rec, len, b->n_ref, &r)) return b->err = BWAHIP_EINVAL;
+	if (!pu_parse(rec, len, b->n_ref, &r)) return BWAHIP_EINVAL;
 	if (!pu_takes_part(r, b->opt)) return 0;
 	const int64_t L = b->ref_len[(size_t)r.q.ref], g0 = b->ref_off[(size_t)r.q.ref];
 	std::vector<uint32_t> &e = b->ev[(size_t)r.q.ref];
@@ -119,26 +82,16 @@ static int pu_builder_add_one(bwahip_pileup_builder *b, const uint8_t *rec, int6
 	        [&](int64_t p) { if (e.empty()) e.assign(3 * (size_t)L, 0); ++e[3 * (size_t)p]; },
 	        [&](int64_t p) { ++e[3 * (size_t)p + 1 + strand]; },
 	        [&](int64_t p, int kind, uint32_t allele) { if ((int64_t)b->keys.size() >= PU_MAX_OBS) full = true; else b->keys.push_back(pu_key(g0 + p, kind, allele, strand)); });
-	return full ? (b->err = BWAHIP_ECAPACITY) : 0;
+	return full ? BWAHIP_ECAPACITY : 0;
 }
 
 extern "C" int bwahip_pileup_builder_add_records(bwahip_pileup_builder *b, const uint8_t *rec, const int64_t *rec_off, int64_t n_rec)
 {
-	if (!b || n_rec < 0 || (n_rec && (!rec || !rec_off)) || b->finished) return BWAHIP_EINVAL;
-	if (b->err) return b->err;
-	for (int64_t i = 0; i < n_rec; ++i) {
-		if (rec_off[i] < 0 || rec_off[i + 1] < rec_off[i]) return b->err = BWAHIP_EINVAL;
-		const int rc = pu_builder_add_one(b, rec + rec_off[i], rec_off[i + 1] - rec_off[i]);
-		if (rc) return rc;
-	}
-	return 0;
+	return builder_feed(b, rec, rec_off, n_rec, pu_builder_add_one);
 }
 
-extern "C" int bwahip_pileup_builder_finish(bwahip_pileup_builder *b, int pu_fd)
+static int pu_builder_bytes(bwahip_pileup_builder *b, std::vector<uint8_t> *bytes)
 {
-	if (!b || b->finished) return BWAHIP_EINVAL;
-	if (b->err) return b->err;
-	b->finished = true;
 	std::vector<uint64_t> &k = b->keys;
 	std::sort(k.begin(), k.end());
 	PuTables t;
@@ -166,11 +119,10 @@ extern "C" int bwahip_pileup_builder_finish(bwahip_pileup_builder *b, int pu_fd)
 		i = j;
 	}
 	t.n_alleles = (int64_t)alleles.size(); t.alleles = alleles.data(); t.n_sites = (int64_t)sites.size(); t.sites = sites.data();
-	std::vector<uint8_t> bytes;
-	int rc = pu_serialise(t, &bytes);
-	if (!rc) rc = pu_write_fd(pu_fd, bytes);
-	return b->err = rc;
+	return pu_serialise(t, bytes);
 }
+
+extern "C" int bwahip_pileup_builder_finish(bwahip_pileup_builder *b, int pu_fd) { return builder_finish(b, pu_fd, "writing the pileup", pu_builder_bytes); }
 
 extern "C" void bwahip_pileup_builder_close(bwahip_pileup_builder *b) { delete b; }
 

@@ -9,7 +9,7 @@
 
 constexpr int PU_SNV = 0, PU_DEL = 1, PU_INS = 2;
 constexpr uint32_t PU_DEL_CAP = (1u << 21) - 1;                   // a deletion's length in its allele
-constexpr int64_t PU_MAX_SUM = 1ll << 40;                        // the sum of the contig lengths stays below it: a global position takes 40 bits
+constexpr int64_t PU_MAX_SUM = 1ll << 40;                        // the sum of the contig lengths stays below it (check_refs, sidecar_host.h): a global position takes 40 bits
 constexpr int64_t PU_MAX_OBS = 0x7fffffffll;
 
 // a record that passed qc_parse and the two checks of the bases
@@ -18,9 +18,9 @@ struct PuRec { QcRec q; int32_t l_seq; const uint8_t *seq, *qual; };
 PU_HD inline bool pu_parse(const uint8_t *p, int64_t len, int32_t n_ref, PuRec *r)
 {
 	if (!qc_parse(p, len, n_ref, &r->q)) return false;
-	const int32_t l_seq = (int32_t)qc_ld32(p + 20);
+	const int32_t l_seq = (int32_t)bam_ld32(p + 20);
 	if (l_seq < 0) return false;
-	const int64_t at = 36 + (int64_t)(qc_ld32(p + 12) & 0xff) + 4 * (int64_t)r->q.n_cigar;
+	const int64_t at = 36 + (int64_t)(bam_ld32(p + 12) & 0xff) + 4 * (int64_t)r->q.n_cigar;
 	if (at + ((int64_t)l_seq + 1) / 2 + l_seq > len) return false;
 	r->l_seq = l_seq; r->seq = p + at; r->qual = r->seq + ((int64_t)l_seq + 1) / 2;
 	return true;
@@ -33,7 +33,7 @@ PU_HD inline int64_t pu_query_len(const PuRec &r)
 {
 	int64_t n = 0;
 	for (int32_t k = 0; k < r.q.n_cigar; ++k) {
-		const uint32_t w = qc_ld32(r.q.cig + 4 * k), op = w & 15;
+		const uint32_t w = bam_ld32(r.q.cig + 4 * k), op = w & 15;
 		if (pu_is_match(op) || op == 1 || op == 4) n += w >> 4;
 	}
 	return n;
@@ -74,7 +74,7 @@ template <class Cover, class Match, class Obs> PU_HD inline void pu_walk(const P
 	const bool all_pass = r.qual[0] == 0xff;
 	int64_t p = r.q.pos, q = 0;
 	for (int32_t k = 0; k < r.q.n_cigar; ++k) {
-		const uint32_t w = qc_ld32(r.q.cig + 4 * k), op = w & 15;
+		const uint32_t w = bam_ld32(r.q.cig + 4 * k), op = w & 15;
 		const int64_t n = w >> 4;
 		if (pu_is_match(op)) {
 			for (int64_t j = 0; j < n && p + j < L; ++j) {
@@ -113,6 +113,4 @@ struct PuTables {
 };
 // pileup_host.cpp
 int pu_resolve(const bwahip_pileup_opt_t *in, bwahip_pileup_opt_t *out);        // NULL: the defaults; BWAHIP_EINVAL for a value out of range
-int pu_check_refs(int32_t n_ref, const int64_t *ref_len, int64_t *sum_len);     // BWAHIP_EINVAL as qc_check_refs; BWAHIP_ECAPACITY for a sum of 2^40 or more
 int pu_serialise(const PuTables &t, std::vector<uint8_t> *out);
-int pu_write_fd(int fd, const std::vector<uint8_t> &bytes);                     // all of them or BWAHIP_EIO; fd < 0: nothing

@@ -3,16 +3,7 @@
 // include/bwahip.h.  The builder keeps a difference array per reference that a record has covered (4 bytes per base), made at the first
 // such record; finish() turns each into depths by one prefix sum.
 #include "qc_tables.h"
-#include <errno.h>
-#include <stdio.h>
-#include <unistd.h>
-
-namespace {
-
-void put32(std::vector<uint8_t> &o, uint32_t v) { for (int k = 0; k < 4; ++k) o.push_back((uint8_t)(v >> (8 * k))); }
-void put64(std::vector<uint8_t> &o, uint64_t v) { for (int k = 0; k < 8; ++k) o.push_back((uint8_t)(v >> (8 * k))); }
-
-} // namespace
+#include "sidecar_host.h"
 
 int qc_resolve(const bwahip_qc_opt_t *in, bwahip_qc_opt_t *out)
 {
@@ -25,15 +16,6 @@ int qc_resolve(const bwahip_qc_opt_t *in, bwahip_qc_opt_t *out)
 		o.min_mapq = in->min_mapq;
 	}
 	*out = o;
-	return 0;
-}
-
-int qc_check_refs(int32_t n_ref, const int64_t *ref_len, int64_t *sum_len)
-{
-	if (n_ref < 0 || (n_ref && !ref_len)) return BWAHIP_EINVAL;
-	int64_t s = 0;
-	for (int32_t r = 0; r < n_ref; ++r) { if (ref_len[r] < 0 || ref_len[r] > 0x7fffffffll) return BWAHIP_EINVAL; s += ref_len[r]; }
-	if (sum_len) *sum_len = s;
 	return 0;
 }
 
@@ -63,21 +45,8 @@ int qc_serialise(const QcTables &t, std::vector<uint8_t> *out)
 	return 0;
 }
 
-int qc_write_fd(int fd, const std::vector<uint8_t> &b)
-{
-	for (size_t o = 0; fd >= 0 && o < b.size();) {
-		const ssize_t w = write(fd, b.data() + o, b.size() - o);
-		if (w < 0) { if (errno == EINTR) continue; fprintf(stderr, "[bwahip] writing the QC summary failed: %s\n", strerror(errno)); return BWAHIP_EIO; }
-		if (w == 0) return BWAHIP_EIO;
-		o += (size_t)w;
-	}
-	return 0;
-}
-
-struct bwahip_qc_builder {
-	int32_t n_ref = 0; bwahip_qc_opt_t opt = { 14, 1796, 0 };
-	int err = 0; bool finished = false;
-	std::vector<int64_t> ref_len;
+struct bwahip_qc_builder : SidecarBuilder {
+	bwahip_qc_opt_t opt = { 14, 1796, 0 };
 	std::vector<uint64_t> fixed, per_ref;
 	std::vector<std::vector<int32_t>> diff;                        // per reference len + 1 words, empty until a record covers it
 };
@@ -88,10 +57,9 @@ extern "C" int bwahip_qc_builder_open(int32_t n_ref, const int64_t *ref_len, con
 	*out = nullptr;
 	bwahip_qc_opt_t o;
 	int rc;
-	if ((rc = qc_check_refs(n_ref, ref_len, nullptr)) || (rc = qc_resolve(opt, &o))) return rc;
+	if ((rc = check_refs(n_ref, ref_len, nullptr, NO_SUM_CAP)) || (rc = qc_resolve(opt, &o))) return rc;
 	bwahip_qc_builder *b = new bwahip_qc_builder;
-	b->n_ref = n_ref; b->opt = o;
-	b->ref_len.assign(ref_len, ref_len + n_ref);
+	b->set_refs(n_ref, ref_len, nullptr); b->opt = o;
 	b->fixed.assign(QC_FIXED, 0); b->per_ref.assign(QC_PER_REF * (size_t)n_ref, 0); b->diff.resize((size_t)n_ref);
 	*out = b;
 	return 0;
@@ -100,7 +68,7 @@ extern "C" int bwahip_qc_builder_open(int32_t n_ref, const int64_t *ref_len, con
 static int qc_builder_add_one(bwahip_qc_builder *b, const uint8_t *rec, int64_t len)
 {
 	QcRec r;
-	if (len < 0 || !qc_parse(rec, len, b->n_ref, &r)) return b->err = BWAHIP_EINVAL;
+	if (!qc_parse(rec, len, b->n_ref, &r)) return BWAHIP_EINVAL;
 	uint64_t *f = b->fixed.data();
 	const uint32_t cat = qc_categories(r);
 	uint64_t *cnt = f + QC_COUNT + ((r.flag & 0x200) ? 16 : 0);
@@ -121,21 +89,11 @@ static int qc_builder_add_one(bwahip_qc_builder *b, const uint8_t *rec, int64_t 
 
 extern "C" int bwahip_qc_builder_add_records(bwahip_qc_builder *b, const uint8_t *rec, const int64_t *rec_off, int64_t n_rec)
 {
-	if (!b || n_rec < 0 || (n_rec && (!rec || !rec_off)) || b->finished) return BWAHIP_EINVAL;
-	if (b->err) return b->err;
-	for (int64_t i = 0; i < n_rec; ++i) {
-		if (rec_off[i] < 0 || rec_off[i + 1] < rec_off[i]) return b->err = BWAHIP_EINVAL;
-		const int rc = qc_builder_add_one(b, rec + rec_off[i], rec_off[i + 1] - rec_off[i]);
-		if (rc) return rc;
-	}
-	return 0;
+	return builder_feed(b, rec, rec_off, n_rec, qc_builder_add_one);
 }
 
-extern "C" int bwahip_qc_builder_finish(bwahip_qc_builder *b, int qc_fd)
+static int qc_builder_bytes(bwahip_qc_builder *b, std::vector<uint8_t> *bytes)
 {
-	if (!b || b->finished) return BWAHIP_EINVAL;
-	if (b->err) return b->err;
-	b->finished = true;
 	const int ws = b->opt.window_shift;
 	std::vector<uint64_t> win;
 	uint64_t *hist = b->fixed.data() + QC_DEPTH;
@@ -156,11 +114,10 @@ extern "C" int bwahip_qc_builder_finish(bwahip_qc_builder *b, int qc_fd)
 	}
 	QcTables t;
 	t.n_ref = b->n_ref; t.ref_len = b->ref_len.data(); t.opt = b->opt; t.fixed = b->fixed.data(); t.per_ref = b->per_ref.data(); t.win = win.data();
-	std::vector<uint8_t> bytes;
-	int rc = qc_serialise(t, &bytes);
-	if (!rc) rc = qc_write_fd(qc_fd, bytes);
-	return b->err = rc;
+	return qc_serialise(t, bytes);
 }
+
+extern "C" int bwahip_qc_builder_finish(bwahip_qc_builder *b, int qc_fd) { return builder_finish(b, qc_fd, "writing the QC summary", qc_builder_bytes); }
 
 extern "C" void bwahip_qc_builder_close(bwahip_qc_builder *b) { delete b; }
 

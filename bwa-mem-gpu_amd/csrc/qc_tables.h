@@ -3,15 +3,12 @@
 // hand to the one serialiser.  Plain C++; __host__ __device__ where a HIP compiler reads it.
 #pragma once
 #include "../../include/bwahip.h"
+#include "bam_rec.h"
 #include <stdint.h>
 #include <string.h>
 #include <vector>
 
-#ifdef __HIPCC__
-#define QC_HD __host__ __device__
-#else
-#define QC_HD
-#endif
+#define QC_HD BAM_HD
 
 constexpr int QC_TILE = 2048;                    // slots of the difference array one workgroup scans; a reference's slots are padded to whole tiles
 // the fixed part of the tables, in 64-bit words: records without a reference, count[2][16], the three histograms
@@ -20,20 +17,18 @@ constexpr int QC_PER_REF = 3;                    // then per reference: mapped, 
 
 struct QcRec { int32_t ref, pos, next_ref, tlen; uint32_t flag, mapq; const uint8_t *cig; int32_t n_cigar; };
 
-QC_HD inline uint32_t qc_ld32(const uint8_t *p) { uint32_t v; __builtin_memcpy(&v, p, 4); return v; }   // records begin at any address
-
 // One record of `len` bytes at p: the checks of bai_parse (bai_tables.h), no byte beyond p + len is read.  false: not a BAM record of n_ref references.
 QC_HD inline bool qc_parse(const uint8_t *p, int64_t len, int32_t n_ref, QcRec *r)
 {
 	if (len < 36) return false;
-	if ((int64_t)(int32_t)qc_ld32(p) + 4 != len) return false;
-	const uint32_t w3 = qc_ld32(p + 12), w4 = qc_ld32(p + 16);
+	if ((int64_t)(int32_t)bam_ld32(p) + 4 != len) return false;
+	const uint32_t w3 = bam_ld32(p + 12), w4 = bam_ld32(p + 16);
 	const int64_t l_read_name = w3 & 0xff, n_cigar = w4 & 0xffff;
 	if (36 + l_read_name + 4 * n_cigar > len) return false;
-	r->ref = (int32_t)qc_ld32(p + 4); r->pos = (int32_t)qc_ld32(p + 8);
+	r->ref = (int32_t)bam_ld32(p + 4); r->pos = (int32_t)bam_ld32(p + 8);
 	if (r->ref >= n_ref || (r->ref >= 0 && r->pos < 0)) return false;
 	r->mapq = w3 >> 8 & 0xff; r->flag = w4 >> 16; r->n_cigar = (int32_t)n_cigar;
-	r->next_ref = (int32_t)qc_ld32(p + 24); r->tlen = (int32_t)qc_ld32(p + 32);
+	r->next_ref = (int32_t)bam_ld32(p + 24); r->tlen = (int32_t)bam_ld32(p + 32);
 	r->cig = p + 36 + l_read_name;
 	return true;
 }
@@ -74,7 +69,7 @@ template <class Put> QC_HD inline void qc_intervals(const QcRec &r, int64_t L, P
 {
 	int64_t p = r.pos, a = -1;
 	for (int32_t k = 0; k <= r.n_cigar; ++k) {
-		const uint32_t w = k < r.n_cigar ? qc_ld32(r.cig + 4 * k) : 3u, op = w & 15;   // behind the last operation: an N of no length
+		const uint32_t w = k < r.n_cigar ? bam_ld32(r.cig + 4 * k) : 3u, op = w & 15;   // behind the last operation: an N of no length
 		const int64_t n = w >> 4;
 		if (op == 0 || op == 2 || op == 7 || op == 8) { if (a < 0) a = p; p += n; }
 		else if (op == 3) {
@@ -96,6 +91,4 @@ struct QcTables {
 };
 // qc_host.cpp
 int qc_resolve(const bwahip_qc_opt_t *in, bwahip_qc_opt_t *out);               // NULL: the defaults; BWAHIP_EINVAL for a value out of range
-int qc_check_refs(int32_t n_ref, const int64_t *ref_len, int64_t *sum_len);    // BWAHIP_EINVAL for n_ref < 0, a missing table, a length outside [0, 2^31 - 1]
 int qc_serialise(const QcTables &t, std::vector<uint8_t> *out);
-int qc_write_fd(int fd, const std::vector<uint8_t> &bytes);                    // all of them or BWAHIP_EIO; fd < 0: nothing

@@ -3,16 +3,7 @@
 // rule is in include/bwahip.h.  The builder keeps the dense tables of recal_tables.h (16 bytes a cell, 3 MB at the default max_cycle, made
 // at the first record that takes part) and copies of the packed reference and the mask.  A judge's twin and a library for small inputs: nothing falls back on it.
 #include "recal_tables.h"
-#include <errno.h>
-#include <stdio.h>
-#include <unistd.h>
-
-namespace {
-
-void put32(std::vector<uint8_t> &o, uint32_t v) { for (int k = 0; k < 4; ++k) o.push_back((uint8_t)(v >> (8 * k))); }
-void put64(std::vector<uint8_t> &o, uint64_t v) { for (int k = 0; k < 8; ++k) o.push_back((uint8_t)(v >> (8 * k))); }
-
-} // namespace
+#include "sidecar_host.h"
 
 int rc_resolve(const bwahip_recal_opt_t *in, bwahip_recal_opt_t *out)
 {
@@ -61,22 +52,10 @@ int rc_serialise(const RcTables &t, std::vector<uint8_t> *out)
 	return 0;
 }
 
-int rc_write_fd(int fd, const std::vector<uint8_t> &b)
-{
-	for (size_t o = 0; fd >= 0 && o < b.size();) {
-		const ssize_t w = write(fd, b.data() + o, b.size() - o);
-		if (w < 0) { if (errno == EINTR) continue; fprintf(stderr, "[bwahip] writing the recalibration table failed: %s\n", strerror(errno)); return BWAHIP_EIO; }
-		if (w == 0) return BWAHIP_EIO;
-		o += (size_t)w;
-	}
-	return 0;
-}
-
-struct bwahip_recal_builder {
-	int32_t n_ref = 0; bwahip_recal_opt_t opt = { 0, 0, RC_DEFAULT_EXCLUDE, RC_DEFAULT_CYCLE };
-	int err = 0; bool finished = false, with_mask = false;
-	std::vector<int64_t> ref_len, ref_off;
-	std::vector<uint8_t> pac, mask;
+struct bwahip_recal_builder : SidecarBuilder {
+	bwahip_recal_opt_t opt = { 0, 0, RC_DEFAULT_EXCLUDE, RC_DEFAULT_CYCLE };
+	bool with_mask = false;
+	std::vector<uint8_t> mask;
 	std::vector<uint64_t> tab;                                     // the dense tables, made at the first record that takes part
 	uint64_t n_records = 0, n_masked = 0;
 };
@@ -88,14 +67,10 @@ extern "C" int bwahip_recal_builder_open(int32_t n_ref, const int64_t *ref_len, 
 	bwahip_recal_opt_t o;
 	int64_t sum = 0;
 	int rc;
-	if ((rc = pu_check_refs(n_ref, ref_len, &sum)) || (rc = rc_resolve(opt, &o))) return rc;
+	if ((rc = check_refs(n_ref, ref_len, &sum, PU_MAX_SUM)) || (rc = rc_resolve(opt, &o))) return rc;
 	if (sum && !pac) return BWAHIP_EINVAL;
 	bwahip_recal_builder *b = new bwahip_recal_builder;
-	b->n_ref = n_ref; b->opt = o;
-	b->ref_len.assign(ref_len, ref_len + n_ref);
-	b->ref_off.assign((size_t)n_ref + 1, 0);
-	for (int32_t r = 0; r < n_ref; ++r) b->ref_off[(size_t)r + 1] = b->ref_off[(size_t)r] + ref_len[r];
-	if (sum) b->pac.assign(pac, pac + (sum + 3) / 4);
+	b->set_refs(n_ref, ref_len, sum ? pac : nullptr); b->opt = o;
 	if (sum && mask) { b->mask.assign(mask, mask + (sum + 7) / 8); b->with_mask = true; }
 	*out = b;
 	return 0;
@@ -104,9 +79,9 @@ extern "C" int bwahip_recal_builder_open(int32_t n_ref, const int64_t *ref_len, 
 static int rc_builder_add_one(bwahip_recal_builder *b, const uint8_t *rec, int64_t len)
 {
 	PuRec r;
-	if (len < 0 || !pu_parse(rec, len, b->n_ref, &r)) return b->err = BWAHIP_EINVAL;
+	if (!pu_parse(rec, len, b->n_ref, &r)) return BWAHIP_EINVAL;
 	if (!rc_takes_part(r, b->opt)) return 0;
-	if (r.l_seq > b->opt.max_cycle) return b->err = BWAHIP_ECAPACITY;
+	if (r.l_seq > b->opt.max_cycle) return BWAHIP_ECAPACITY;
 	const int mc = b->opt.max_cycle;
 	if (b->tab.empty()) b->tab.assign((size_t)rc_table_words(mc), 0);
 	uint64_t *tab = b->tab.data();
@@ -121,28 +96,17 @@ static int rc_builder_add_one(bwahip_recal_builder *b, const uint8_t *rec, int64
 
 extern "C" int bwahip_recal_builder_add_records(bwahip_recal_builder *b, const uint8_t *rec, const int64_t *rec_off, int64_t n_rec)
 {
-	if (!b || n_rec < 0 || (n_rec && (!rec || !rec_off)) || b->finished) return BWAHIP_EINVAL;
-	if (b->err) return b->err;
-	for (int64_t i = 0; i < n_rec; ++i) {
-		if (rec_off[i] < 0 || rec_off[i + 1] < rec_off[i]) return b->err = BWAHIP_EINVAL;
-		const int rc = rc_builder_add_one(b, rec + rec_off[i], rec_off[i + 1] - rec_off[i]);
-		if (rc) return rc;
-	}
-	return 0;
+	return builder_feed(b, rec, rec_off, n_rec, rc_builder_add_one);
 }
 
-extern "C" int bwahip_recal_builder_finish(bwahip_recal_builder *b, int rc_fd)
+static int rc_builder_bytes(bwahip_recal_builder *b, std::vector<uint8_t> *bytes)
 {
-	if (!b || b->finished) return BWAHIP_EINVAL;
-	if (b->err) return b->err;
-	b->finished = true;
 	if (b->tab.empty()) b->tab.assign((size_t)rc_table_words(b->opt.max_cycle), 0);
 	RcTables t;
 	t.n_ref = b->n_ref; t.opt = b->opt; t.n_records = b->n_records; t.n_masked = b->n_masked; t.tab = b->tab.data();
-	std::vector<uint8_t> bytes;
-	int rc = rc_serialise(t, &bytes);
-	if (!rc) rc = rc_write_fd(rc_fd, bytes);
-	return b->err = rc;
+	return rc_serialise(t, bytes);
 }
+
+extern "C" int bwahip_recal_builder_finish(bwahip_recal_builder *b, int rc_fd) { return builder_finish(b, rc_fd, "writing the recalibration table", rc_builder_bytes); }
 
 extern "C" void bwahip_recal_builder_close(bwahip_recal_builder *b) { delete b; }

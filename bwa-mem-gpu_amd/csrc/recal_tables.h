@@ -44,7 +44,7 @@ template <class Count, class Masked> RC_HD inline void rc_walk(const PuRec &r, i
 	const uint32_t mate = r.q.flag >> 7 & 1;
 	int64_t p = r.q.pos, q = 0;
 	for (int32_t k = 0; k < r.q.n_cigar; ++k) {
-		const uint32_t w = qc_ld32(r.q.cig + 4 * k), op = w & 15;
+		const uint32_t w = bam_ld32(r.q.cig + 4 * k), op = w & 15;
 		const int64_t n = w >> 4;
 		if (pu_is_match(op)) {
 			for (int64_t j = 0; j < n && p + j < L; ++j) {
@@ -73,4 +73,3 @@ struct RcTables {
 // recal_host.cpp
 int rc_resolve(const bwahip_recal_opt_t *in, bwahip_recal_opt_t *out);           // NULL: the defaults; BWAHIP_EINVAL for a value out of range
 int rc_serialise(const RcTables &t, std::vector<uint8_t> *out);
-int rc_write_fd(int fd, const std::vector<uint8_t> &bytes);                       // all of them or BWAHIP_EIO; fd < 0: nothing

@@ -4,17 +4,20 @@ reference, written from the rule in include/bwahip.h.  Every comparison is byte 
 import gzip
 import os
 import random
+import struct
 
 import numpy as np
 import pytest
 
 import bai_ref
 import bam_sort_ref as sref
+import bgzf_ref
 import common
 import markdup_cases as mcases
 import markdup_ref as mref
 import pileup_cases as cases
 import pileup_ref as ref
+import qc_ref
 from common import bw
 
 pytestmark = pytest.mark.gpu
@@ -230,6 +233,72 @@ def test_armed_marked_finish_sees_the_duplicate_flag(ctx, tmp_path, n_runs):
     _same(pu, want, f"{n_runs} runs added as {order}, marked")
     got, pu, _ = _finish(ctx, runs, order, str(tmp_path / "unmarked.bin"), (lens, pac, opt), "finish", with_dup=True)
     _same(pu, want_unmarked, f"{n_runs} runs, the unmarked finish of the same runs")
+
+
+def test_marking_index_qc_and_pileup_in_one_finish(ctx, tmp_path):
+    """Three resident runs of about a thousand records at piece_blocks 1 (several pieces); one finish with marking, the index, the QC summary
+    and the pileup all armed writes the members and the three files that the same merger writes with each product armed alone, and the
+    files are the judges' on the marked records.  With QC disarmed again the pileup is still the same: no stage moved or went missing."""
+    c = mcases.record_set(True, n_tmpl=1250, seed=33)
+    n_seqs = mcases.N_SEQS
+    rng = random.Random(33)
+    def pad(x):                                                                            # 100 to 300 bytes a record, by a trailing Z tag: several pieces
+        n = rng.randrange(max(len(x) + 4, 100), 301)
+        x += b"XPZ" + b"p" * (n - len(x) - 4) + b"\0"
+        return struct.pack("<i", len(x) - 4) + x[4:]
+    c["templates"] = [(name, [[pad(x) for x in r] for r in rr]) for name, rr in c["templates"]
+                      if all(bai_ref.fields(x, n_seqs)[2] <= bai_ref.MAX_END for r in rr for x in r)]   # what BAI can index
+    c["names"] = [n for n, _ in c["templates"]]
+    descs = mcases.judge_descs(c)
+    lens = [5000, 100000, 1000, 3000, 64]                                                  # the set's five references; what lies beyond a contig is clipped
+    pac = ref.pack_reference([[rng.randrange(4) for _ in range(n)] for n in lens])
+    n = len(c["templates"])
+    b = [0, 3 * n // 10, 13 * n // 20, n]
+    key_of = lambda r: sref.packed_key(r, n_seqs, mcases.LONGEST)
+    runs = []
+    for k in range(3):
+        recs = [(x, t) for t, (_, reads) in enumerate(c["templates"][b[k]:b[k + 1]]) for r in reads for x in r]
+        recs.sort(key=lambda p: sref.order_key(p[0]))
+        assert len(recs) > 600
+        runs.append((*sref.run_arrays([x for x, _ in recs], key_of), np.array([t for _, t in recs], dtype=np.uint32), mcases.as_desc_array(descs[b[k]:b[k + 1]])))
+    assert 2500 < sum(len(r[1]) for r in runs) < 3800 and sum(len(r[0]) for r in runs) > 3 * 65280
+    qc_opt, pu_opt, base = (8, 0x400, 0), (0, 15, 0x400, 2), 4321
+    paths = [str(tmp_path / x) for x in ("m.bin", "m.bai", "m.bqc", "m.bpu")]
+
+    def finish(m, index, qc, pileup):
+        """A marked finish of merger m with these products armed: the four files' bytes (b"" for a product that is not armed)."""
+        fds = [os.open(p, os.O_WRONLY | os.O_CREAT | os.O_TRUNC, 0o644) for p in paths]
+        try:
+            m.set_qc(lens, fds[2], qc_opt) if qc else m.set_qc(None)
+            m.set_pileup(lens, pac, fds[3], pu_opt) if pileup else m.set_pileup(None)
+            m.finish_markdup(fds[0], fds[1], base, n_seqs if index else -1)
+        finally:
+            for fd in fds:
+                os.close(fd)
+        return [open(p, "rb").read() for p in paths]
+
+    with bw.DevMerger(ctx, 1) as m:
+        for k in (1, 2, 0):
+            m.add_dup(k, *runs[k])
+        alone = [finish(m, False, False, False), finish(m, True, False, False), finish(m, False, True, False), finish(m, False, False, True)]
+        members, bai, qc, pu = finish(m, True, True, True)                                 # (set_qc before set_pileup here; the stages' order is the merger's)
+        for k, part in enumerate(("members", "index", "QC summary", "pileup")):
+            assert [bool(x) for x in alone[k]] == [True] + [j == k for j in range(1, 4)], part
+            assert (members, bai, qc, pu)[k] == alone[k][k], f"all four armed: the {part} differs from the one the merger writes with it armed alone"
+            assert alone[k][0] == members, part
+        again = finish(m, False, False, True)
+        assert again[3] == pu and again[0] == members and again[1] == again[2] == b"", "QC disarmed, the pileup still armed"
+    unmarked = sref.stable_sort([x for _, rr in c["templates"] for r in rr for x in r])
+    marked = mref.mark(unmarked, c["names"], True)["records"]
+    assert bgzf_ref.inflate(members) == b"".join(marked) and marked != unmarked
+    offs = [base]
+    for mem in bgzf_ref.parse(members):
+        offs.append(offs[-1] + mem["size"])
+    assert len(offs) > 3
+    assert bai == bai_ref.build(marked, offs, n_seqs), "the index is not the judge's"
+    assert qc == qc_ref.build(marked, lens, qc_opt), qc_ref.first_difference(qc, qc_ref.build(marked, lens, qc_opt))
+    _same(pu, ref.build(marked, lens, pac, pu_opt), "all four armed")
+    assert len(ref.parse(pu)["sites"]) > 50
 
 
 # ---------------------------------------------------------------------------------------------------------------- 3. the stream driver
