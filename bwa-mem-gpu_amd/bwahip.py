@@ -996,7 +996,8 @@ class Context:
         ext_early_stop (default 1): ksw_extend2 ends once no later row can change its results; 0 = every row to the end, as the
         reference (same results, more rows); and ext_diag (default 1): ksw_extend2 answers a flank of at most K mismatches (1 at the default
         scores) from its main diagonal, without a DP row; 0 = every call runs its rows (same results); and incr_insert (default 1): mate rescue places a region into a tie-free list without
-        sorting it again; 0 = every orientation ends in the full sort-and-dedup (same lists, pairing and output)."""
+        sorting it again; 0 = every orientation ends in the full sort-and-dedup (same lists, pairing and output); and smem_skip (default -1):
+        depth of k_smem's table jump, -1 = derived from the text length, 0 = off, n >= 2 = that depth (same intervals)."""
         for k, v in kw.items():
             _check(lib().bwahip_ctx_tune(self._h, k.encode(), int(v)), f"bwahip_ctx_tune({k})")
 
@@ -1318,7 +1319,7 @@ class Context:
         names = ["extend", "blocks", "sa", "lf", "intv", "seeds", "cells", "max_extends", "chain_build_max", "chain_sort_max", "chain_flt_max",
                  "chain_write_max", "max_seeds", "max_chains", "ext_max", "ext_dedup_max", "heavy_blocks", "heavy_intv", "heavy_reads",
                  "dp_rows_1col", "dp_rows_ncol", "dedup_sort1_max", "dedup_loop_max", "dedup_sort2_max",
-                 "pass3_blocks", "pass3_intv", "pass3_jumped", "ext_calls", "ext_diag", "_29", "_30", "_31"]
+                 "pass3_blocks", "pass3_intv", "pass3_jumped", "ext_calls", "ext_diag", "smem_lookups", "smem_fallbacks", "_31"]
         return {k: int(buf[i]) for i, k in enumerate(names)}
 
     def kat_introsort(self, k64, score, qb, mode):

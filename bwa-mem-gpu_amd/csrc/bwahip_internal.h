@@ -47,7 +47,8 @@ struct DevOpt {
 enum { CNT_EXTEND = 0, CNT_BLOCKS, CNT_SA, CNT_LF, CNT_INTV, CNT_SEEDS, CNT_CELLS, CNT_MAX_EXT /* most bwt_extend calls of one read */,
        CNT_HEAVY_BLOCKS = 16, CNT_HEAVY_INTV, CNT_HEAVY_READS, CNT_ROWS1 /* DP rows, 1 column per lane */, CNT_ROWSN /* DP rows, CPL columns per lane */,
        CNT_P3_BLOCKS = 24, CNT_P3_INTV, CNT_P3_JUMPED /* pass-3 extensions the interval table stood in for */,
-       CNT_EXT_CALLS /* ksw_extend2 calls of the extension kernels */, CNT_EXT_DIAG /* those the diagonal rule answered without a row */, CNT_N = 32 };
+       CNT_EXT_CALLS /* ksw_extend2 calls of the extension kernels */, CNT_EXT_DIAG /* those the diagonal rule answered without a row */,
+       CNT_SMEM_LOOKUPS /* look-ups of the interval table by k_smem's table jump */, CNT_SMEM_FALLBACKS /* calls it abandoned and ran again plainly */, CNT_N = 32 };
 // The counters are kept in CNT_SLOTS copies (rows of CNT_N); a wavefront updates the row picked by its position in the
 // launch and the host folds the rows (sum, or max for the *_max entries).  One shared row made every wavefront's
 // end-of-work atomics queue up on the same L2 line: with a million wavefronts that alone cost tens of milliseconds.
@@ -123,6 +124,7 @@ struct SmemLaunch {
 	int groups_total;
 	int *worst_n;                               // largest interval count of a read whose list overflowed `cap`
 	int *heavy_list; unsigned int *heavy_n; int heavy_mult;   // reads handed to k_smem_heavy after heavy_mult*len extends (0: never)
+	int smem_skip;                              // k_smem: depth of the table jump, clamped to the table's depth and to min_seed_len (0: every call runs plain)
 };
 int launch_smem(const SmemLaunch &a, int group_lanes, hipStream_t st);
 int launch_pack4(const SmemLaunch &a, hipStream_t st);

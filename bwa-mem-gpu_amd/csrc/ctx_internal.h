@@ -85,6 +85,7 @@ struct Knobs {
 	int smem_lanes = 1;         // BWAHIP_SMEM_LANES: lanes per read in k_smem (1, 2, 4, 8)
 	int sa_intv = 1;            // BWAHIP_SA_INTV: interval of the SA table in HBM (1: every row, 8 bytes each; the index files' own interval or more: the files' table as it is); a table that would take over a quarter of the free HBM is built at the next interval that fits
 	int kmer_k = 14;            // BWAHIP_KMER_K: the interval table holds the bi-intervals of all strings of up to kmer_k bases (16 bytes each, 4^k of them per length: 14 -> 5.7 GB, 15 -> 23 GB, 16 -> 92 GB; 0 or 1: no table); never longer than log4 of the text, nor than a quarter of the free HBM
+	int smem_skip = -1;         // BWAHIP_SMEM_SKIP: depth J of k_smem's table jump -- a bwt_smem1a call starts at the table entry of its first J bases and materialises the J - 1 shorter ends by look-ups (same intervals).  -1: the largest J <= the table's depth with 4^J <= text length / 16 (3.1 Gbp: 14); 0: off; n >= 2: that depth.  Always clamped to the table's depth and, per batch, to min_seed_len
 	int heavy_mult = -1;        // BWAHIP_HEAVY_MULT: hand a read to k_smem_heavy after heavy_mult x len extends (0: never; -1: 10 for reads up to 200 bases, 30 above -- a 250 bp read at 5 % error needs 2 500 extends on average, and the hand-off is for the outliers)
 	int chain_mid_max = 1536, chain_big_max = 3200, chain_glb_grid = 2048;   // BWAHIP_CHAIN_MID_MAX / _BIG_MAX / _GLB_GRID: seeds up to which a read's B-tree lives in 77 KB / 150 KB of LDS (beyond: in global memory), and the workgroups of that last kernel
 	int chain_big_min = 512;    // BWAHIP_CHAIN_BIG_MIN: seeds above which a wavefront-per-read chaining kernel takes the read (< 0: off)
@@ -103,7 +104,7 @@ struct Knobs {
 	void from_env()
 	{
 		auto geti = [](const char *k, int &v) { if (const char *e = getenv(k)) v = atoi(e); };
-		geti("BWAHIP_INTV_CAP", intv_cap); geti("BWAHIP_SMEM_LANES", smem_lanes); geti("BWAHIP_HEAVY_MULT", heavy_mult); geti("BWAHIP_SA_INTV", sa_intv); geti("BWAHIP_KMER_K", kmer_k);
+		geti("BWAHIP_INTV_CAP", intv_cap); geti("BWAHIP_SMEM_LANES", smem_lanes); geti("BWAHIP_HEAVY_MULT", heavy_mult); geti("BWAHIP_SMEM_SKIP", smem_skip); geti("BWAHIP_SA_INTV", sa_intv); geti("BWAHIP_KMER_K", kmer_k);
 		geti("BWAHIP_CHAIN_BIG_MIN", chain_big_min); geti("BWAHIP_CHAIN_MID_MAX", chain_mid_max); geti("BWAHIP_CHAIN_BIG_MAX", chain_big_max); geti("BWAHIP_CHAIN_GLB_GRID", chain_glb_grid); geti("BWAHIP_RANK_SORT_MIN", rank_sort_min); geti("BWAHIP_SPEC_MIN_CHAINS", spec_min_chains); geti("BWAHIP_EXT_LDS_WINDOW", ext_lds_window); geti("BWAHIP_EXT_EARLY_STOP", ext_early_stop); geti("BWAHIP_EXT_DIAG", ext_diag); geti("BWAHIP_GPU_FINAL", gpu_final); geti("BWAHIP_GPU_PAIR", gpu_pair);
 		verbose = getenv("BWAHIP_VERBOSE") != nullptr;
 		e2e_log = getenv("BWAHIP_E2E_LOG") != nullptr;

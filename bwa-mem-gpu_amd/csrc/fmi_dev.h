@@ -196,7 +196,10 @@ __device__ __forceinline__ void lane_occ4(const DevIndex &ix, uint64_t p, bool l
 }
 // occ4 of k and of l by one lane; when both fall into the same 64-byte block (two out of five extends) the block is fetched once:
 // four load instructions fewer for those lanes (k_smem 28.9 -> 26.6 ms)
-__device__ __forceinline__ void lane_occ4_pair(const DevIndex &ix, uint64_t pk, uint64_t pl, bool live, uint64_t ck[4], uint64_t cl[4])
+// `other` (k_smem's table jump; null in every other caller): a lane that is not live may fetch these 16 bytes instead, through the very load
+// that brings a live lane the first quarter of its block -- a second source at no cost in registers; *first receives what that load brought.
+__device__ __forceinline__ void lane_occ4_pair(const DevIndex &ix, uint64_t pk, uint64_t pl, bool live, uint64_t ck[4], uint64_t cl[4],
+                                               const uint4 *other = nullptr, uint4 *first = nullptr)
 {
 	const bool nk = (pk == ~0ull);
 	const uint64_t kk = pk - (pk >= ix.primary), ll = pl - (pl >= ix.primary);
@@ -204,6 +207,13 @@ __device__ __forceinline__ void lane_occ4_pair(const DevIndex &ix, uint64_t pk, 
 	// the second 64 bases of a block are fetched only by the lanes whose position lies there
 	const bool same = !nk && (kk >> 7) == (ll >> 7);
 	const bool k_hi = (kk & 127) >= 64, l_hi = (ll & 127) >= 64;
+	if (first) {
+		const bool lk = live && !nk;
+		const uint4 *b = lk ? ix.bwt + (kk >> 7) * 4 : other;
+		if (lk || other) a0 = b[0];
+		if (lk) { a1 = b[1]; a2 = b[2]; if (k_hi || (same && l_hi)) a3 = b[3]; }
+		*first = a0;
+	} else
 	if (live && !nk) { const uint4 *b = ix.bwt + (kk >> 7) * 4; a0 = b[0]; a1 = b[1]; a2 = b[2]; if (k_hi || (same && l_hi)) a3 = b[3]; }
 	uint4 b0 = a0, b1 = a1, b2 = a2, b3 = a3;
 	if (live && !same && pl != ~0ull) { const uint4 *b = ix.bwt + (ll >> 7) * 4; b0 = b[0]; b1 = b[1]; b2 = b[2]; if (l_hi) b3 = b[3]; }   // (l = -1: the counts are zeroed below, nothing to fetch)
@@ -224,13 +234,14 @@ __device__ __forceinline__ void lane_occ4_pair(const DevIndex &ix, uint64_t pk, 
 }
 
 // bwt_extend by ONE lane (64 reads per wavefront): 2 x 64 B per lane in flight, no cross-lane traffic at all.
-__device__ __forceinline__ int lane_extend_c(const DevIndex &ix, const Bi &ik, int is_back, int c, bool live, Bi &o)
+// (other, first: see lane_occ4_pair)
+__device__ __forceinline__ int lane_extend_c(const DevIndex &ix, const Bi &ik, int is_back, int c, bool live, Bi &o, const uint4 *other = nullptr, uint4 *first = nullptr)
 {
 	uint64_t xa = is_back ? ik.x0 : ik.x1;
 	uint64_t xb = is_back ? ik.x1 : ik.x0;
 	uint64_t k = xa - 1, l = k + ik.x2;
 	uint64_t tk[4], tl[4];
-	lane_occ4_pair(ix, k, l, live, tk, tl);
+	lane_occ4_pair(ix, k, l, live, tk, tl, other, first);
 	uint64_t s1 = tl[1] - tk[1], s2 = tl[2] - tk[2], s3 = tl[3] - tk[3];
 	uint64_t lo = L2_at(ix, c) + 1 + sel4(c, tk[0], tk[1], tk[2], tk[3]);
 	uint64_t sz = sel4(c, tl[0] - tk[0], s1, s2, s3);

@@ -24,11 +24,21 @@
 // lists is moved to a per-group HBM area as the forward pass overwrites the ring.  The per-call `mem`
 // vector of bwt_smem1a is not materialised: only its last start coordinate is needed (bwt.c:333).
 // Every lane of a group keeps an identical copy of the state; lane 0 of the group writes the LDS entries.
+//
+// The table jump (knob smem_skip; G = 1 only).  Half of the plain machine's turns produce strings shorter than the interval
+// table's depth: the first forward steps of every bwt_smem1a call and the triangle of the backward sweep in which those short prefixes have
+// not yet collapsed.  With a depth J, a call whose J bases from x on are ACGT starts its forward phase at the table entry of that string
+// (ST_JUMP, one look-up) and stores no entry for the ends x + 1 .. x + J - 1: they are dormant, presumed alive.  The backward step at i,
+// after the active entries, materialises the dormant entry with end i + J -- its string read[i..i+J) has exactly J bases, one look-up --
+// and it joins curr as its shortest entry.  A jumped or materialised string that occurs fewer than min_intv times shows the presumption
+// wrong (ABANDON): the call is dropped and run again from its start in the plain way.  A string found often enough proves every shorter
+// dormant entry alive at that step, and the size tests of bwt.c:311,338 only drop entries that die together with a longer one, so the
+// output is the plain machine's.  The look-up is a request at the same convergent site as the extends, never inside the run-up.
 #include "fmi_dev.h"
 
 namespace {
 
-enum : int { ST_IDLE = 0, ST_NEXT, ST_FWD, ST_BWD, ST_FINISH };
+enum : int { ST_IDLE = 0, ST_NEXT, ST_JUMP, ST_FWD, ST_BWD, ST_FINISH };
 
 __device__ __forceinline__ void put(DevIntv *p, uint64_t x0, uint64_t x1, uint64_t x2, uint64_t info)
 {
@@ -72,6 +82,24 @@ __device__ __forceinline__ int qbase(const uint64_t *row, int p, uint64_t &qw, i
 	if (wi != qwi) { qw = row[wi]; qwi = wi; }
 	const uint32_t half = (p & 8) ? (uint32_t)(qw >> 32) : (uint32_t)qw;
 	return (int)(half >> ((p & 7) * 4)) & 15;
+}
+
+// The J bases from position x on as the interval table's code (base t at bits 2t; J <= 16), straight from the 4-bit row: false when one of
+// them is ambiguous or lies past the read's end (0xF there).  Two words cover any 16 positions; the row has a word past the longest read.
+__device__ __forceinline__ bool kmer_code(const uint64_t *row, int x, int J, uint32_t &code)
+{
+	const int wi = x >> 4, sh = (x & 15) * 4;
+	const uint64_t w0 = row[wi], w1 = row[wi + 1];
+	uint64_t w = sh ? (w0 >> sh | w1 << (64 - sh)) : w0;
+	if (J < 16) w &= (1ull << 4 * J) - 1;
+	const bool acgt = (w & 0xCCCCCCCCCCCCCCCCull) == 0;
+	w = (w | w >> 2) & 0x0F0F0F0F0F0F0F0Full;                 // 2 bits of every 4, squeezed together
+	w = (w | w >> 4) & 0x00FF00FF00FF00FFull;
+	w = (w | w >> 8) & 0x0000FFFF0000FFFFull;
+	w = (w | w >> 16);
+	code = (uint32_t)w;
+	asm volatile("" : "+v"(code));                           // squeezed here: left to the compiler, the 64-bit word waits for its use across the caller's branches
+	return acgt;
 }
 
 __global__ __launch_bounds__(256) void k_pack4(int n_reads, const uint8_t *seq, const int64_t *off, uint64_t *seq4, int stride)
@@ -125,7 +153,9 @@ __device__ __forceinline__ void finish_pass12(const SmemLaunch &a, int rd, int n
 {
 	a.raw_n[rd] = n_emit;
 	a.l_rep[rd] = n_ext;                                     // diagnostic: bwt_extend calls passes 1-2 of this read needed
-	if ((unsigned long long)n_ext > cnt_row(a.counters)[CNT_MAX_EXT]) atomicMax(&cnt_row(a.counters)[CNT_MAX_EXT], (unsigned long long)n_ext);
+	// (the host takes the largest over the rows, so any row serves: the read's own, which costs k_smem's loop no register for the wavefront's)
+	unsigned long long *const mx = a.counters + (size_t)(rd & (CNT_SLOTS - 1)) * CNT_N + CNT_MAX_EXT;
+	if ((unsigned long long)n_ext > *mx) atomicMax(mx, (unsigned long long)n_ext);
 }
 
 __device__ __forceinline__ int base_or_minus1(int b) { return b > 3 ? -1 : b; }
@@ -137,8 +167,9 @@ __device__ __forceinline__ int base_or_minus1(int b) { return b > 3 ? -1 : b; }
 // level with the very same extension (4^L lanes, one block pair each); a string that does not occur has size 0 and so do all its extensions,
 // exactly as bwt_extend returns them (only the size of such a result is ever looked at).
 // Who reads it: k_smem3 (bwt_seed_strategy1 looks at no result before min_seed_len bases, so the first K - 1 extensions of every start
-// are ONE look-up: 3.4 -> 1.6 ms per 1 M reads at K = 14).  k_smem does NOT: answering its short-string extensions from the table (half of
-// all its calls: the first forward steps and the triangle of the backward sweep) was measured twice on the 3.1 Gbp index -- as a second
+// are ONE look-up: 3.4 -> 1.6 ms per 1 M reads at K = 14), and k_smem's table jump, which likewise SKIPS extensions (header comment).
+// ANSWERING k_smem's short-string extensions one by one from the table (half of all its calls: the first forward steps and the triangle
+// of the backward sweep) does not pay; it was measured twice on the 3.1 Gbp index -- as a second
 // source at the convergent step 30.4 -> 28.5 ms against 26.2 ms without the extra code (the kernel is bound by the instructions of an
 // iteration, not by its Occ requests, and the iterations stay), and answered inside the run-up, one dependent gather after the other while
 // the other lanes of the wavefront wait, 46 ms.
@@ -195,27 +226,42 @@ __global__ __launch_bounds__(256, 4) void k_smem(SmemLaunch a)
 	const int group = (int)((blockIdx.x * blockDim.x + threadIdx.x) / G);
 	const DevIndex &ix = a.ix;
 	const int min_seed_len = a.opt.min_seed_len, cap = a.cap, lcap = a.lcap;
+	// the table jump (header comment): depth J, 0 = every call runs plain.  The launch clamps it to the table's depth and to min_seed_len.
+	// One read per lane only: the variants with G > 1 run plain (the look-up rides on the lane's own block fetch, lane_occ4_pair).
+	const int J = G == 1 ? a.smem_skip : 0;
+	const uint32_t jmask = J >= 16 ? ~0u : (1u << 2 * J) - 1;
+	const uint4 *const jtab = ix.kmer + kmer_off(J);
 
 	constexpr int LL = 8 * G;                                // list entries kept in LDS per read (a power of two: ring index)
 	__shared__ uint4 lds_list[(256 / G) * (LL + 1)];         // +1: rows start on different banks
 	uint4 *const lrow = lds_list + (threadIdx.x / G) * (LL + 1);
 	uint4 *const spill = reinterpret_cast<uint4*>(a.scratch) + (size_t)group * lcap;   // list entries by physical index (lcap of them)
 	DevIntv *U = a.raw;                                      // unsorted accumulated intervals of the current read (its raw row)
+	// look-ups and abandoned calls of this wavefront, counted in LDS by adds that return nothing (as registers they would live through the
+	// whole loop); lane 0 zeroes and reads them, in program order
+	__shared__ unsigned skip_cnt[4][4];
+	unsigned *const my_cnt = skip_cnt[threadIdx.x >> 6];
+	if (lane == 0) { my_cnt[0] = 0; my_cnt[1] = 0; my_cnt[2] = 0; my_cnt[3] = 0; }
+	__builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 
 	// ---- per-group state (identical in every lane of the group; plain scalars so it stays in registers) ----
 	int st = ST_IDLE, rd = -1, len = 0, pass = 0;
 	const uint64_t *qrow = nullptr; uint64_t qw = 0; int qwi = -1;
 	int x = 0, i = 0, j = 0, c = 0, min_intv = 1, ret = 0, p2k = 0, old_n = 0, out_n = 0;
-	int prev_n = 0, curr_n = 0, base = 0, top = 0, mem_n = 0, mem_last_start = 0;
-	uint64_t curr_last_x2 = 0, p_info = 0;
+	int prev_n = 0, curr_n = 0, base = 0, top = 0, mem_last_start = 0;
+	uint64_t curr_last_x2 = 0; uint32_t p_info = 0;
 	Bi ik = { 0, 0, 0 };
 	uint32_t ik_end = 0, last_push_end = 0;
-	int guard = 0, guard_max = 0;
+	int guard = 0;
+	// the table jump: dormant entries left (-1 between an abandoned call and its plain restart) and the code of the J bases from i + 1 on
+	// (from x on before the first backward step); out_n at the start of the call waits in the pad entry of the LDS row, read only by ABANDON
+	int dorm = 0;
 	bool exhausted = false;
-	unsigned int n_ext = 0, n_blk = 0, n_out = 0;
+	unsigned int n_blk = 0;
 
 	// Where list entry P (physical index) lives.  The backward sweep always works on the top of the region the forward pass
-	// filled -- [base, top) with top fixed -- so LDS is a ring over the physical index that ends up holding the LL highest
+	// filled -- [base, top) with top fixed; a call that jumped starts at base = J - 1, the room its dormant entries take when the backward
+	// sweep materialises them below the active ones -- so LDS is a ring over the physical index that ends up holding the LL highest
 	// entries: the forward pass writes entry P to ring slot P % LL and, from P = LL on, first moves the entry it displaces
 	// (P - LL) to its HBM slot; afterwards entry P is in LDS iff P >= top - LL.  Lists of up to LL entries never touch HBM.
 #define LDS_SLOT(P) ((P) & (LL - 1))
@@ -233,7 +279,7 @@ __global__ __launch_bounds__(256, 4) void k_smem(SmemLaunch a)
 	// backward phase: prev[jj] is read last-pushed-first (bwt.c:321-324 reverses curr) and stays that way in place
 #define PREV_AT(jj) (base + prev_n - 1 - (jj))
 #define FWD_PUSH(X0, X1, X2, END) do { \
-		const int p_ = curr_n; const uint4 v_ = pack_entry((X0), (X1), (X2), (uint32_t)(END)); \
+		const int p_ = base + curr_n; const uint4 v_ = pack_entry((X0), (X1), (X2), (uint32_t)(END)); \
 		if (p_ >= LL) { uint4 ev_ = lrow[LDS_SLOT(p_)]; asm volatile("" : "+v"(ev_.x), "+v"(ev_.y), "+v"(ev_.z), "+v"(ev_.w)); spill[p_ - LL] = ev_; } \
 		if (gl == 0) lrow[LDS_SLOT(p_)] = v_; \
 		++curr_n; curr_last_x2 = (X2); } while (0)
@@ -242,22 +288,36 @@ __global__ __launch_bounds__(256, 4) void k_smem(SmemLaunch a)
 #define EMIT(X0, X1, X2, INFO) do { if (out_n < cap) put(U + out_n, (X0), (X1), (X2), (INFO)); ++out_n; } while (0)
 	// a MEM ends at start coordinate START (bwt.c:332-336); only those >= min_seed_len are kept (bwamem.c:150,163)
 #define FOUND_MEM(X0, X1, X2, FWD_END, START) do { \
-		if (mem_n == 0 || (START) < mem_last_start) { \
-			++mem_n; mem_last_start = (START); \
+		if ((START) < mem_last_start) { \
+			mem_last_start = (START); \
 			if ((int)(uint32_t)(FWD_END) - (START) >= min_seed_len) EMIT((X0), (X1), (X2), (uint64_t)(START) << 32 | (uint32_t)(FWD_END)); \
 		} } while (0)
 #define QB(p) qbase(qrow, (p), qw, qwi)
 #define BASE_AT(p) ((p) < 0 ? -1 : base_or_minus1(QB(p)))
-	// bwt.c:289-303: start bwt_smem1a(X_, MI)
+	// bwt.c:289-303: start bwt_smem1a(X_, MI).  With J bases of ACGT inside the read from x on, the forward phase starts at the table entry
+	// of that string (one look-up, ST_JUMP) and the ends x + 1 .. x + J - 1 are dormant; not in the plain restart of an abandoned call.
 #define START_SMEM(X_, MI) do { \
 		x = (X_); min_intv = (MI) < 1 ? 1 : (MI); \
-		mem_n = 0; curr_n = 0; base = 0; curr_last_x2 = 0; \
-		set_intv(ix, QB(x), ik); ik_end = (uint32_t)(x + 1); i = x + 1; st = ST_FWD; } while (0)
+		mem_last_start = 0x7fffffff; curr_n = 0; curr_last_x2 = 0; \
+		uint32_t code_ = 0; \
+		const bool jump_ = J && dorm >= 0 && kmer_code(qrow, x, J, code_); \
+		if (jump_) { lrow[LL].y = code_; dorm = J - 1; base = J - 1; ik_end = (uint32_t)(x + J); i = x + J; st = ST_JUMP; lrow[LL].x = (uint32_t)out_n; } \
+		else { dorm = 0; base = 0; set_intv(ix, QB(x), ik); ik_end = (uint32_t)(x + 1); i = x + 1; st = ST_FWD; } } while (0)
+	// a jumped or materialised string occurs fewer than min_intv times: a dormant entry died at a step nobody saw (or here).  The call is
+	// abandoned -- what it emitted is dropped -- and ST_NEXT starts it again, plain, from the same x (pass 2: from the same list entry).
+#define ABANDON() do { \
+		out_n = (int)lrow[LL].x; dorm = -1; if (pass == 2) --p2k; st = ST_NEXT; \
+		if (gl == 0) __hip_atomic_fetch_add(&my_cnt[1], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); } while (0)
+	// bwt.c:340 swap, in place; a materialised entry made curr one longer than prev, and base one lower
+#define BWD_SWAP() do { \
+		__builtin_amdgcn_wave_barrier(); \
+		base += prev_n - curr_n; prev_n = curr_n; curr_n = 0; \
+		--i; j = 0; c = BASE_AT(i); } while (0)
 	// bwt.c:321-324: curr reversed becomes prev; its first entry is the last one pushed
 #define FWD_FINISH() do { \
 		ret = (int)last_push_end; \
 		__builtin_amdgcn_wave_barrier(); \
-		prev_n = curr_n; top = curr_n; base = 0; curr_n = 0; \
+		prev_n = curr_n; top = base + curr_n; curr_n = 0; \
 		i = x - 1; j = 0; c = BASE_AT(i); st = ST_BWD; } while (0)
 	// bwt.c:343 break; pass 1 continues at the forward end (bwamem.c:146)
 #define BWD_FINISH() do { st = ST_NEXT; if (pass == 1) x = ret; } while (0)
@@ -272,14 +332,13 @@ __global__ __launch_bounds__(256, 4) void k_smem(SmemLaunch a)
 			else {
 				rd = (int)t; qrow = a.seq4 + (size_t)t * a.seq4_stride; qwi = -1; U = a.raw + (size_t)t * cap; len = (int)(a.off[t + 1] - a.off[t]);
 				out_n = 0; pass = 1; x = 0; guard = 0;
-				guard_max = a.heavy_mult > 0 ? a.heavy_mult * len + 64 : 64 * BWAHIP_MAX_READ_LEN;
 				st = len < min_seed_len ? ST_FINISH : ST_NEXT;   // bwamem.c:267
 			}
 		}
 		if (__ballot(st != ST_IDLE) == 0) break;               // the whole wavefront is out of work
 
 		// ---------------------------------------------------------------- run to the next bwt_extend
-		bool need = false; int is_back = 0, cb = 0; Bi req = { 0, 0, 0 };
+		bool need = false, is_tab = false; int is_back = 0, cb = 0; Bi req = { 0, 0, 0 };
 		for (int spin = 0; spin < 8192 && !need && st != ST_IDLE && st != ST_FINISH; ++spin) {
 			if (st == ST_NEXT) {
 				if (pass == 1) {
@@ -302,6 +361,7 @@ __global__ __launch_bounds__(256, 4) void k_smem(SmemLaunch a)
 			}
 			// (no `else`: a start falls through to its first forward step, the end of the forward phase to the first backward one, in the same
 			// turn -- the wavefront takes as many turns as its slowest lane has transitions)
+			if (J && st == ST_JUMP) { need = true; is_tab = true; }
 			if (st == ST_FWD) {
 				const int bq = i < len ? QB(i) : 4;
 				if (bq < 4) { need = true; is_back = 0; req = ik; cb = 3 - bq; }
@@ -318,8 +378,11 @@ __global__ __launch_bounds__(256, 4) void k_smem(SmemLaunch a)
 						FOUND_MEM(x0, x1, x2, info, i + 1);
 					}
 					BWD_FINISH();
+				} else if (J && j == prev_n) {                      // after the active entries: the dormant one with end i + J, the string read[i..i+J)
+					lrow[LL].y = (lrow[LL].y << 2 | (uint32_t)c) & jmask;
+					need = true; is_tab = true;
 				} else {
-					LIST_GET(PREV_AT(j), req.x0, req.x1, req.x2, p_info);
+					{ uint64_t e64_; LIST_GET(PREV_AT(j), req.x0, req.x1, req.x2, e64_); p_info = (uint32_t)e64_; }
 					need = true; is_back = 1; cb = c;
 				}
 			}
@@ -327,29 +390,40 @@ __global__ __launch_bounds__(256, 4) void k_smem(SmemLaunch a)
 
 		// ---------------------------------------------------------------- passes 1-2 of a read are done
 		if (st == ST_FINISH) {
-			if (gl == 0) { finish_pass12(a, rd, out_n, guard); n_out += out_n < cap ? out_n : cap; }
+			if (gl == 0) { finish_pass12(a, rd, out_n, guard); __hip_atomic_fetch_add(&my_cnt[2], (unsigned)(out_n < cap ? out_n : cap), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+				__hip_atomic_fetch_add(&my_cnt[3], (unsigned)guard, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
 			st = ST_IDLE; rd = -1;
 		}
 
-		// ---------------------------------------------------------------- the one convergent bwt_extend
+		// ---------------------------------------------------------------- the one convergent request: a bwt_extend or a table look-up
 		Bi o;
-		const bool live = need;
+		const bool live = need && !is_tab;
+		uint4 tv = make_uint4(0, 0, 0, 0);                       // a look-up: one 16-byte gather, through the load that brings the others their Occ blocks
 		int nb = G == 8 ? group8_extend_c(ix, req, is_back, cb, live, o) : G == 4 ? quad_extend_c(ix, req, is_back, cb, live, o) : G == 2 ? pair_extend_c(ix, req, is_back, cb, live, o)
-		                                                                        : lane_extend_c(ix, req, is_back, cb, live, o);
-		if (need && gl == 0) { ++n_ext; n_blk += nb; }
+		                                                                        : lane_extend_c(ix, req, is_back, cb, live, o, is_tab ? jtab + lrow[LL].y : nullptr, &tv);
+		if (live && gl == 0) n_blk += nb;
+		if (is_tab) {
+			uint64_t e_;
+			unpack_entry(tv, o.x0, o.x1, o.x2, e_);
+			if (gl == 0) __hip_atomic_fetch_add(&my_cnt[0], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+		}
 
 		// ---------------------------------------------------------------- consume the result
 		if (need) {
-			if (++guard > guard_max) {
+			// (the bound is worked out here each turn: kept per read it was one more register across the whole loop; look-ups count as turns)
+			if (++guard > (a.heavy_mult > 0 ? a.heavy_mult * len + 64 : 64 * BWAHIP_MAX_READ_LEN)) {
 				// a read deep inside a repeat: thousands of dependent steps would make it the critical path of the whole
 				// launch, so it is handed to k_smem_heavy, which runs each backward step across a wavefront
 				if (a.heavy_mult > 0) {
-					if (gl == 0) { unsigned h = atomicAdd(a.heavy_n, 1u); a.heavy_list[h] = rd; }
+					if (gl == 0) { unsigned h = atomicAdd(a.heavy_n, 1u); a.heavy_list[h] = rd; __hip_atomic_fetch_add(&my_cnt[3], (unsigned)guard, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
 					st = ST_IDLE; rd = -1;
 				} else {                                             // cannot happen; guarantees the grid drains
 					if (gl == 0) atomicExch(a.err, 1);
 					out_n = 0; st = ST_FINISH;
 				}
+			} else if (J && st == ST_JUMP) {
+				if (o.x2 < (uint64_t)min_intv) ABANDON();
+				else { ik = o; st = ST_FWD; }
 			} else if (st == ST_FWD) {                             // bwt.c:308-315
 				bool stop = false;
 				if (o.x2 != ik.x2) {
@@ -358,29 +432,42 @@ __global__ __launch_bounds__(256, 4) void k_smem(SmemLaunch a)
 				}
 				if (stop) FWD_FINISH();
 				else { ik = o; ik_end = (uint32_t)(i + 1); ++i; }
+			} else if (J && st == ST_BWD && is_tab) {                   // the materialised entry goes through the two tests an extended one does
+				if (o.x2 < (uint64_t)min_intv) ABANDON();
+				else {
+					if (curr_n == 0 || o.x2 != curr_last_x2) BWD_PUSH(o.x0, o.x1, o.x2, (uint32_t)(i + J));
+					--dorm;
+					BWD_SWAP();                                          // (curr is not empty: this entry is alive)
+				}
 			} else if (st == ST_BWD) {                             // bwt.c:328-342
 				if (o.x2 < (uint64_t)min_intv) {
 					if (curr_n == 0) FOUND_MEM(req.x0, req.x1, req.x2, p_info, i + 1);
 				} else if (curr_n == 0 || o.x2 != curr_last_x2) {
 					BWD_PUSH(o.x0, o.x1, o.x2, p_info);
 				}
-				if (++j == prev_n) {
+				if (++j == prev_n && dorm <= 0) {                    // (dormant entries left: the next turn materialises one, then swaps)
 					if (curr_n == 0) BWD_FINISH();
-					else {
-						__builtin_amdgcn_wave_barrier();
-						base += prev_n - curr_n; prev_n = curr_n; curr_n = 0;   // bwt.c:340 swap, in place
-						--i; j = 0; c = BASE_AT(i);
-					}
+					else BWD_SWAP();
 				}
 			}
 		}
 	}
 	{                                                        // one set of counter updates per wavefront
-		unsigned long long e = gl == 0 ? n_ext : 0, b = gl == 0 ? n_blk : 0, o = gl == 0 ? n_out : 0;
-		for (int m = 32; m; m >>= 1) { e += __shfl_xor(e, m); b += __shfl_xor(b, m); o += __shfl_xor(o, m); }
-		if (lane == 0 && (e | o)) {
-			unsigned long long *cnt = cnt_row(a.counters);
-			atomicAdd(&cnt[CNT_EXTEND], e); atomicAdd(&cnt[CNT_BLOCKS], b); atomicAdd(&cnt[CNT_INTV], o);
+		unsigned long long b = gl == 0 ? n_blk : 0;
+		for (int m = 32; m; m >>= 1) b += __shfl_xor(b, m);
+		__builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+		if (lane == 0) {
+			const unsigned lk = __hip_atomic_load(&my_cnt[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+			const unsigned fb = __hip_atomic_load(&my_cnt[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+			const unsigned long long o = __hip_atomic_load(&my_cnt[2], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+			const unsigned long long e = __hip_atomic_load(&my_cnt[3], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) - lk;   // turns that were no look-up
+			// (the row from a laundered wavefront index: computed here, not kept in a register through the loop above)
+			unsigned wv = threadIdx.x >> 6;
+			asm volatile("" : "+v"(wv));
+			unsigned long long *cnt = a.counters + (size_t)((blockIdx.x * (blockDim.x >> 6) + wv) & (CNT_SLOTS - 1)) * CNT_N;
+			if (e | o) { atomicAdd(&cnt[CNT_EXTEND], e); atomicAdd(&cnt[CNT_BLOCKS], b); atomicAdd(&cnt[CNT_INTV], o); }
+			if (lk) atomicAdd(&cnt[CNT_SMEM_LOOKUPS], (unsigned long long)lk);
+			if (fb) atomicAdd(&cnt[CNT_SMEM_FALLBACKS], (unsigned long long)fb);
 		}
 	}
 #undef PREV_AT
@@ -396,6 +483,8 @@ __global__ __launch_bounds__(256, 4) void k_smem(SmemLaunch a)
 #undef START_SMEM
 #undef FWD_FINISH
 #undef BWD_FINISH
+#undef ABANDON
+#undef BWD_SWAP
 }
 
 // ---------------------------------------------------------------------------------------------------------------

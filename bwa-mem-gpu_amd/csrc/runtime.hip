@@ -372,6 +372,7 @@ int bwahip_ctx_tune(bwahip_ctx *c, const char *key, int value)
 	if (!strcmp(key, "intv_cap")) { k.intv_cap = value < 2 ? 2 : value; c->intv_cap = k.intv_cap; }
 	else if (!strcmp(key, "smem_lanes")) { if (value != 1 && value != 2 && value != 4 && value != 8) return BWAHIP_EINVAL; k.smem_lanes = value; }
 	else if (!strcmp(key, "heavy_mult")) k.heavy_mult = value;
+	else if (!strcmp(key, "smem_skip")) { if (value < -1 || value == 1) return BWAHIP_EINVAL; k.smem_skip = value; }
 	else if (!strcmp(key, "chain_big_min")) k.chain_big_min = value;
 	else if (!strcmp(key, "chain_mid_max")) k.chain_mid_max = value;      // the launch clamps these two to the LDS budgets (1536 / 3200 seeds)
 	else if (!strcmp(key, "chain_big_max")) k.chain_big_max = value;
@@ -713,6 +714,19 @@ static int ext_prepare(bwahip_ctx *c, const DevOpt &dopt, int n, int64_t total, 
 	return 0;
 }
 
+// Depth of k_smem's table jump for one batch (knob smem_skip).  -1: the largest J with 4^J <= text length / 16 -- a string of J bases then
+// occurs 16 times on average, above the min_intv of nearly every pass-2 call (split_width + 1 = 11 at most), so a jump is rarely abandoned.
+// Never deeper than the table, nor than min_seed_len (a dormant entry is shorter than J, so it never ends a kept seed); below 2 there is
+// nothing to skip.
+static int smem_skip_depth(const DevIndex &ix, int knob, int min_seed_len)
+{
+	int J = knob;
+	if (J < 0) for (J = 0; J < 16 && (1ull << 2 * (J + 1)) <= ix.seq_len / 16; ++J);
+	if (J > ix.kmer_k) J = ix.kmer_k;
+	if (J > min_seed_len) J = min_seed_len;
+	return J < 2 ? 0 : J;
+}
+
 int run_pipeline(bwahip_ctx *c, const bwahip_opt_t *opt, bool timed, bool dump)
 {
 	const bool verbose = c->knobs.verbose != 0;
@@ -748,6 +762,7 @@ int run_pipeline(bwahip_ctx *c, const bwahip_opt_t *opt, bool timed, bool dump)
 		const int heavy_mult = c->knobs.heavy_mult >= 0 ? c->knobs.heavy_mult : c->in->max_len <= 200 ? 10 : 30;   // x read length; 0 = never hand off
 		if ((rc = c->d_smem_heavy.ensure((size_t)n * 4))) return rc;
 		sl.heavy_list = c->d_smem_heavy.as<int>(); sl.heavy_n = queue + 1; sl.heavy_mult = heavy_mult; sl.worst_n = (int*)(queue + 2);
+		sl.smem_skip = smem_skip_depth(c->ix, c->knobs.smem_skip, dopt.min_seed_len);
 		if (timed) HIP_TRY(hipEventRecord(c->ev[0], c->stream));
 		if ((rc = launch_smem(sl, G, c->stream))) return rc;
 		STAGE_LOG("k_smem");

@@ -926,7 +926,9 @@ const char *bwahip_kernel_name(int i);
  * counts of one read; [16,17] Occ blocks / intervals of k_smem_heavy, [24,25] of k_smem3 (both are
  * included in [1] and [4]; bench.py subtracts them to attribute bytes to k_smem); [19,20] DP rows
  * with one / several columns per lane; [21..23] dedup phase maxima; [27] ksw_extend2 calls of the extension
- * kernels, [28] those the diagonal rule (knob ext_diag) answered without a DP row.  n <= 32. */
+ * kernels, [28] those the diagonal rule (knob ext_diag) answered without a DP row; [29] look-ups of the interval
+ * table by k_smem's table jump (knob smem_skip; the bwt_extend calls they stand in for are not in [0]), [30] bwt_smem1a calls the
+ * jump abandoned and ran again plainly.  n <= 32. */
 int bwahip_batch_counters(bwahip_ctx *ctx, uint64_t *counters, int n);
 
 /* Known-answer helpers used by the parity tests: device Occ/extend/SA on arrays of inputs. */
@@ -1125,7 +1127,10 @@ int bwahip_kat_ksw_align(bwahip_ctx *ctx, int n, const int *params, const int8_t
  * device form of ksw_extend2 ends its row loop once no later row can change score, qle, tle, gtle, gscore or max_off --
  * 0 runs every row to the end as the reference does (same results, more rows); and ext_diag (0 or 1, default 1): the extension kernels
  * answer a ksw_extend2 call whose flank holds only ACGT and at most K mismatches (K = 1 at the default scores) from the main diagonal,
- * without a DP row -- 0 runs the rows of every call (same results); and sorted_piece_blocks (1 .. 4096, default 1024): the
+ * without a DP row -- 0 runs the rows of every call (same results); and smem_skip (-1, 0 or >= 2, default -1): the
+ * depth J of k_smem's table jump -- a bwt_smem1a call of passes 1-2 starts at the interval table's entry of its
+ * first J bases and materialises the J - 1 shorter ends by one look-up each; -1 takes the largest J with 4^J <= text length / 16, 0 runs
+ * every call plainly, and any depth is held to the table's and to min_seed_len (same intervals; 1 is refused); and sorted_piece_blocks (1 .. 4096, default 1024): the
  * BGZF blocks a device merger gathers and deflates at a time (bwahip_bam_devmerger_open with piece_blocks <= 0; the bytes do not depend on it);
  * and incr_insert (0 or 1, default 1): mate rescue places a rescued region into a list that the last mem_sort_dedup_patch left free of
  * ties without sorting the list again -- 0 ends every orientation in the full sort-and-dedup, as the reference does.  The knob changes
