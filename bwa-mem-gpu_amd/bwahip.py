@@ -132,6 +132,11 @@ class RecalOpt(C.Structure):  # bwahip_recal_opt_t
     _fields_ = [("min_mapq", C.c_int), ("min_baseq", C.c_int), ("exclude_flags", C.c_int), ("max_cycle", C.c_int)]
 
 
+class RecalStats(C.Structure):  # bwahip_recal_stats_t
+    _fields_ = [("n_records", C.c_int64), ("n_bases", C.c_int64), ("n_err", C.c_int64), ("n_masked", C.c_int64), ("n_rows", C.c_int64 * 3), ("rc_bytes", C.c_int64),
+                ("hbm_bytes", C.c_int64), ("recal_ms", C.c_double)]
+
+
 class SpillStats(C.Structure):  # bwahip_spill_t
     _fields_ = [("host_budget", C.c_int64), ("tmp_dir", C.c_char_p), ("window_pieces", C.c_int), ("n_spilled_runs", C.c_int64), ("first_spilled_run", C.c_int64),
                 ("host_bytes", C.c_int64), ("file_bytes", C.c_int64), ("n_windows", C.c_int64), ("window_hbm_bytes", C.c_int64), ("download_s", C.c_double),
@@ -307,6 +312,13 @@ def lib():
     L.bwahip_recal_builder_finish.argtypes = [vp, C.c_int]
     L.bwahip_recal_builder_close.argtypes = [vp]
     L.bwahip_recal_builder_close.restype = None
+    L.bwahip_kat_recal.argtypes = [vp, vp, vp, C.c_int64, C.c_int32, vp, vp, vp, C.POINTER(RecalOpt), vp, C.c_int64, i64p]
+    L.bwahip_bam_devmerger_set_recal.argtypes = [vp, C.POINTER(RecalOpt), C.c_int32, vp, vp, vp, C.c_int, C.POINTER(RecalStats)]
+    L.bwahip_recal_hbm_need.argtypes = [C.c_int64, C.c_int, C.c_int]
+    L.bwahip_recal_hbm_need.restype = C.c_int64
+    L.bwahip_stream_run_bam_sorted_dev_recal.argtypes = [C.POINTER(vp), C.c_int, C.POINTER(Opt), C.POINTER(PeStat), C.c_char_p, C.c_char_p, C.c_int, C.c_char_p,
+                                                         C.POINTER(StreamStats), C.POINTER(SortDevStats), C.POINTER(SpillStats), C.c_int, C.c_int, C.POINTER(MarkdupStats),
+                                                         C.POINTER(QcOpt), C.c_int, C.POINTER(QcStats), C.POINTER(RecalOpt), vp, C.c_int, C.POINTER(RecalStats)]
     L.bwahip_kat_radix_sort.argtypes = [vp, C.c_int64, vp, C.c_int, vp, C.POINTER(C.c_int)]
     L.bwahip_fastq_open.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(vp)]
     L.bwahip_fastq_next.argtypes = [vp, C.c_int64, C.c_int, C.POINTER(C.POINTER(Seq)), C.POINTER(C.c_int)]
@@ -554,6 +566,21 @@ class DevMerger:
         self._pu = ps                                            # the merger writes into it
         return ps
 
+    def set_recal(self, ref_len=None, pac=None, mask=None, rc_fd=-1, opt=()):
+        """bwahip_bam_devmerger_set_recal: every later finish runs the recalibration-table stage (csrc/k_recal.hip) over the records and writes
+        the file to rc_fd; pac: the packed reference of these contigs (bytes), None for the context's index; mask: the known sites (bytes), None
+        for none; opt = (min_mapq, min_baseq, exclude_flags, max_cycle), () for the defaults; ref_len None disarms.  Returns the RecalStats
+        every armed finish fills."""
+        if ref_len is None or opt is None:
+            self._rc = None
+            _check(lib().bwahip_bam_devmerger_set_recal(self._h, None, 0, None, None, None, -1, None), "bwahip_bam_devmerger_set_recal")
+            return None
+        o, lens, rs = recal_opt(*opt), np.ascontiguousarray(ref_len, dtype=np.int64), RecalStats()
+        _check(lib().bwahip_bam_devmerger_set_recal(self._h, C.byref(o), len(lens), lens.ctypes.data if len(lens) else None, bytes(pac) if pac is not None else None,
+                                                    bytes(mask) if mask is not None else None, rc_fd, C.byref(rs)), "bwahip_bam_devmerger_set_recal")
+        self._rc = rs                                            # the merger writes into it
+        return rs
+
     def finish_bai(self, fd=-1, bai_fd=-1, first_member_offset=0, n_ref=0):
         """bwahip_bam_devmerger_finish_bai: finish, and the BAI index of the sorted records on bai_fd (csrc/k_bai.hip); returns
         (DevMergeStats, BaiStats)."""
@@ -617,6 +644,11 @@ def recal_opt(min_mapq=0, min_baseq=0, exclude_flags=-1, max_cycle=0):
     o = RecalOpt()
     o.min_mapq, o.min_baseq, o.exclude_flags, o.max_cycle = min_mapq, min_baseq, exclude_flags, max_cycle
     return o
+
+
+def recal_hbm_need(sum_len, max_cycle=0, with_mask=False):
+    """bwahip_recal_hbm_need: the HBM of the recalibration-table stage for contigs of sum_len bases in all (no device)."""
+    return lib().bwahip_recal_hbm_need(sum_len, max_cycle, int(bool(with_mask)))
 
 
 class _Builder:
@@ -1265,6 +1297,26 @@ class Context:
         _check(rc, "bwahip_kat_pileup")
         return out[:ln.value].tobytes()
 
+    def kat_recal(self, rec, rec_off, ref_len, pac, mask=None, opt=()):
+        """The recalibration-table stage of the device merger (csrc/k_recal.hip) on these records (any order) for these contig lengths, this
+        packed reference and this mask of known sites (None: none): the BRC\1 bytes.  opt = (min_mapq, min_baseq, exclude_flags, max_cycle),
+        () for the defaults."""
+        rec = bytes(rec)
+        rec_off = np.ascontiguousarray(rec_off, dtype=np.int64)
+        lens = np.ascontiguousarray(ref_len, dtype=np.int64)
+        src = np.frombuffer(rec, dtype=np.uint8) if rec else np.zeros(1, dtype=np.uint8)
+        ln = C.c_int64()
+        out = np.empty(1 << 20, dtype=np.uint8)
+        for _ in range(2):
+            rc = lib().bwahip_kat_recal(self._h, src.ctypes.data, rec_off.ctypes.data, len(rec_off) - 1, len(lens), lens.ctypes.data if len(lens) else None,
+                                        bytes(pac) if pac is not None else None, bytes(mask) if mask is not None else None, C.byref(recal_opt(*opt)), out.ctypes.data,
+                                        len(out), C.byref(ln))
+            if rc != -5 or ln.value <= len(out):
+                break
+            out = np.empty(ln.value, dtype=np.uint8)                # the first answer said how much it takes
+        _check(rc, "bwahip_kat_recal")
+        return out[:ln.value].tobytes()
+
     def kat_dup_desc(self, rec, off, paired=False):
         """The batch's descriptor kernel (csrc/k_markdup.hip) on these records in input order: read i = rec[off[i]:off[i+1]]; one
         descriptor per read, or per two reads (paired), as a DUP_DESC_DTYPE array."""
@@ -1652,6 +1704,29 @@ def stream_run_bam_sorted_dev_spill(ctxs, fq1, fq2=None, out_fd=-1, bai_fd=-1, q
                                                         C.byref(ms), C.byref(qc_opt(*qc)) if qc is not None else None, qc_fd, C.byref(qs)),
            "bwahip_stream_run_bam_sorted_dev_spill")
     return st, sd, sp, ms, qs
+
+
+def stream_run_bam_sorted_dev_recal(ctxs, fq1, fq2=None, out_fd=-1, bai_fd=-1, qc_fd=-1, rc_fd=-1, markdup=False, qc=None, recal=(), mask=None, hdr_line=None, opt=None,
+                                    chunk_bases=0, max_reads=0, keep_comments=False, reader_threads=0, pes0=None, hbm_budget=0, piece_blocks=0, host_budget=0, tmp_dir=None,
+                                    window_pieces=0):
+    """bwahip_stream_run_bam_sorted_dev_recal: stream_run_bam_sorted_dev_spill with the recalibration table of the file on rc_fd
+    (csrc/k_recal.hip), over the contexts' reference and this mask of known sites (bytes, None: none).  recal = (min_mapq, min_baseq,
+    exclude_flags, max_cycle), None to pass no options.  Returns (StreamStats, SortDevStats, SpillStats, MarkdupStats, QcStats, RecalStats)."""
+    opt = opt or default_opt()
+    st, sd, sp, ms, qs, rs = StreamStats(), SortDevStats(), SpillStats(), MarkdupStats(), QcStats(), RecalStats()
+    st.chunk_bases, st.max_reads, st.keep_comments, st.reader_threads = chunk_bases, max_reads, int(keep_comments), reader_threads
+    sd.tmp_dir, sd.mem_budget, sd.level = None, 0, 1
+    sd.hbm_budget, sd.piece_blocks = hbm_budget, piece_blocks
+    sp.host_budget, sp.tmp_dir, sp.window_pieces = host_budget, os.fsencode(tmp_dir) if tmp_dir is not None else None, window_pieces
+    arr = (C.c_void_p * len(ctxs))(*[c._h for c in ctxs])
+    if isinstance(hdr_line, str):
+        hdr_line = hdr_line.encode()
+    _check(lib().bwahip_stream_run_bam_sorted_dev_recal(arr, len(ctxs), C.byref(opt), C.byref(pes0) if pes0 is not None else None, os.fsencode(fq1),
+                                                        os.fsencode(fq2) if fq2 else None, out_fd, hdr_line, C.byref(st), C.byref(sd), C.byref(sp), bai_fd, int(bool(markdup)),
+                                                        C.byref(ms), C.byref(qc_opt(*qc)) if qc is not None else None, qc_fd, C.byref(qs),
+                                                        C.byref(recal_opt(*recal)) if recal is not None else None, bytes(mask) if mask is not None else None, rc_fd, C.byref(rs)),
+           "bwahip_stream_run_bam_sorted_dev_recal")
+    return st, sd, sp, ms, qs, rs
 
 
 def _tool(name):

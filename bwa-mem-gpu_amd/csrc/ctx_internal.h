@@ -321,7 +321,7 @@ int  bam_devmerger_add_dev(bwahip_bam_devmerger *m, int64_t run_no, const uint8_
 int  bam_devmerger_take_runs(bwahip_bam_devmerger *m, std::vector<std::pair<int64_t, DevRun*>> *out);
 // What one finish of a device merger runs beside the members, and where the stages' outputs go: resolved once, by the three
 // bwahip_bam_devmerger_finish* entry points or by a sink of the stream driver.  The record stages (below) are the merger's armed state
-// (bwahip_bam_devmerger_set_qc, _set_pileup), the windowed path follows from its runs: the finish fills it in.
+// (bwahip_bam_devmerger_set_qc, _set_pileup, _set_recal), the windowed path follows from its runs: the finish fills it in.
 struct FinishPlan {
 	bool index = false; int bai_fd = -1; int64_t base = 0; int32_t n_ref = 0; bwahip_bai_stats_t *bs = nullptr;   // the .bai of what is written (base: the first member's offset in the file)
 	bool mark = false; bwahip_markdup_stats_t *ms = nullptr;       // duplicates marked before anything is gathered (ms may be null)
@@ -381,12 +381,15 @@ struct RecordStage {
 	virtual bool takes_windows() const = 0;
 };
 // k_qc.hip: the QC summary.  k_pileup.hip: the pileup -- pac: the packed reference of these contigs, copied and uploaded once per call of
-// pu_stage_set (null: the context's, where it lies in HBM).  *_set: resolved options and checked lengths; the stats struct may be null
+// pu_stage_set (null: the context's, where it lies in HBM).  k_recal.hip: the recalibration table -- pac as for the pileup, mask: the known
+// sites over these contigs' bases, copied and uploaded likewise (null: none).  *_set: resolved options and checked lengths; the stats struct may be null
 RecordStage *qc_stage_new();
 void qc_stage_set(RecordStage *s, const bwahip_qc_opt_t &opt, int32_t n_ref, const int64_t *ref_len, int fd, bwahip_qc_stats_t *qs);
 RecordStage *pu_stage_new();
 void pu_stage_set(RecordStage *s, const bwahip_pileup_opt_t &opt, int32_t n_ref, const int64_t *ref_len, const uint8_t *pac, int fd, bwahip_pileup_stats_t *ps);
-// k_bammerge.hip: exactly a configured stage on the caller's records, uploaded as one run (bwahip_kat_qc, bwahip_kat_pileup); the file's bytes to out
+RecordStage *recal_stage_new();
+void recal_stage_set(RecordStage *s, const bwahip_recal_opt_t &opt, int32_t n_ref, const int64_t *ref_len, const uint8_t *pac, const uint8_t *mask, int fd, bwahip_recal_stats_t *st);
+// k_bammerge.hip: exactly a configured stage on the caller's records, uploaded as one run (bwahip_kat_qc, bwahip_kat_pileup, bwahip_kat_recal); the file's bytes to out
 int  record_stage_kat(RecordStage *s, bwahip_ctx *c, const uint8_t *rec, const int64_t *rec_off, int64_t n_rec, uint8_t *out, int64_t out_cap, int64_t *out_len);
 int bam_check_reads(int n, const bwahip_seq_t *seqs);   // bam_host.cpp: BWAHIP_EINVAL (with a message naming the read) for a name or a comment BAM cannot hold
 void pipe_destroy(bwahip_ctx *c);                                                     // final_rt.hip: the stream driver's buffer sets

@@ -21,7 +21,7 @@
 //
 // Beside the members a finish runs the stages its FinishPlan names (ctx_internal.h) -- duplicate marking (k_markdup.hip: one bit of a record
 // changes and no key), the BAI index (k_bai.hip, after the last piece) -- and the merger's armed record stages (RecordStage, ctx_internal.h: the
-// QC summary, k_qc.hip, then the pileup, k_pileup.hip, resident runs only; they read and change nothing).  Marking and the record stages read
+// QC summary, k_qc.hip, then the pileup, k_pileup.hip, resident runs only, then the recalibration table, k_recal.hip; they read and change nothing).  Marking and the record stages read
 // every record.  That is the records pass: a resident run's records pass before the order is made, marking first, one stage after the other over
 // all runs, and each stage is awaited there.  A spilled run (bwahip_bam_devmerger_set_spill, k_bamspill.hip) keeps its record bytes in a
 // host-side store; they are staged one window of pieces at a time (spill_plan.h), the gather finds them in the staging buffer, and the slices
@@ -34,6 +34,7 @@
 #include "bai_tables.h"
 #include "qc_tables.h"
 #include "pileup_tables.h"
+#include "recal_tables.h"
 #include "spill_plan.h"
 #include "spill_store.h"
 #include "sidecar_host.h"
@@ -178,10 +179,10 @@ struct bwahip_bam_devmerger {
 	Work w;
 	std::unique_ptr<BaiStage, void (*)(BaiStage*)> bai{ nullptr, bai_stage_free };   // the stages' buffers (k_bai.hip, k_markdup.hip): each made by the first finish that runs the stage
 	std::unique_ptr<MarkdupStage> md;
-	// The record stages (bwahip_bam_devmerger_set_qc, _set_pileup), in the order a finish runs the armed ones.  They live as long as the merger:
+	// The record stages (bwahip_bam_devmerger_set_qc, _set_pileup, _set_recal), in the order a finish runs the armed ones.  They live as long as the merger:
 	// what a setter configured and the buffers a finish made stay for the next finish
-	std::unique_ptr<RecordStage> qc{ qc_stage_new() }, pu{ pu_stage_new() };
-	RecordStage *const stages[2] = { qc.get(), pu.get() };
+	std::unique_ptr<RecordStage> qc{ qc_stage_new() }, pu{ pu_stage_new() }, rc{ recal_stage_new() };
+	RecordStage *const stages[3] = { qc.get(), pu.get(), rc.get() };
 	bool all_take_windows() const { for (const RecordStage *s : stages) if (s->armed && !s->takes_windows()) return false; return true; }
 	// spilled runs (bwahip_bam_devmerger_set_spill): the store of their record bytes, the windows' staging
 	HostBuf dl_bounce;                                             // bam_devmerger_adopt_spilled: a file-backed run's bytes on their way from HBM
@@ -890,6 +891,28 @@ extern "C" int bwahip_bam_devmerger_set_pileup(bwahip_bam_devmerger *m, const bw
 	pu_stage_set(m->pu.get(), o, n_ref, ref_len, pac, pu_fd, ps);   // (the stage copies pac and uploads the copy once)
 	m->pu->armed = true;
 	if (ps) memset(ps, 0, sizeof *ps);
+	return 0;
+}
+
+// As set_pileup, with the mask of known sites (copied; null: none).  The stage takes windows: armed for spilling or not, the merger takes it
+extern "C" int bwahip_bam_devmerger_set_recal(bwahip_bam_devmerger *m, const bwahip_recal_opt_t *opt, int32_t n_ref, const int64_t *ref_len, const uint8_t *pac, const uint8_t *mask,
+                                              int rc_fd, bwahip_recal_stats_t *rs)
+{
+	if (!m) return BWAHIP_EINVAL;
+	std::lock_guard<std::mutex> lk(m->mu);
+	if (!opt) { m->rc->armed = false; return 0; }
+	bwahip_recal_opt_t o;
+	int64_t sum = 0;
+	int rc;
+	if ((rc = rc_resolve(opt, &o)) || (rc = check_refs(n_ref, ref_len, &sum, PU_MAX_SUM))) return rc;   // the merger is as before
+	if (!pac) {                                                    // the context's index: these must be its contigs
+		const bwahip_bns_t &bns = m->c->host.bns;
+		if (n_ref != bns.n_seqs || sum != bns.l_pac || !m->c->d_pac.p) return BWAHIP_EINVAL;
+		for (int32_t r = 0; r < n_ref; ++r) if (ref_len[r] != bns.anns[r].len) return BWAHIP_EINVAL;
+	}
+	recal_stage_set(m->rc.get(), o, n_ref, ref_len, pac, mask, rc_fd, rs);   // (the stage copies pac and the mask and uploads the copies once)
+	m->rc->armed = true;
+	if (rs) memset(rs, 0, sizeof *rs);
 	return 0;
 }
 

@@ -1,5 +1,5 @@
 // The base-quality recalibration table of a coordinate-sorted BAM file, the parts that need no device: a builder that is fed the records
-// in any cut and any order, and the serialiser of the dense tables (one serialiser: a device stage would hand its own tables to it).  The
+// in any cut and any order, and the serialiser of the dense tables (one serialiser: the device stage, k_recal.hip, hands its own tables to it).  The
 // rule is in include/bwahip.h.  The builder keeps the dense tables of recal_tables.h (16 bytes a cell, 3 MB at the default max_cycle, made
 // at the first record that takes part) and copies of the packed reference and the mask.  A judge's twin and a library for small inputs: nothing falls back on it.
 #include "recal_tables.h"
@@ -110,3 +110,11 @@ static int rc_builder_bytes(bwahip_recal_builder *b, std::vector<uint8_t> *bytes
 extern "C" int bwahip_recal_builder_finish(bwahip_recal_builder *b, int rc_fd) { return builder_finish(b, rc_fd, "writing the recalibration table", rc_builder_bytes); }
 
 extern "C" void bwahip_recal_builder_close(bwahip_recal_builder *b) { delete b; }
+
+// what the device stage (k_recal.hip) holds: the dense tables, the mask, and 4 096 for the counters, the error word and the contig table's first entries
+extern "C" int64_t bwahip_recal_hbm_need(int64_t sum_len, int max_cycle, int with_mask)
+{
+	if (sum_len < 0 || sum_len >= PU_MAX_SUM || max_cycle < 0 || max_cycle > RC_MAX_CYCLE) return -1;
+	const int64_t work = 8 * rc_table_words(max_cycle ? max_cycle : RC_DEFAULT_CYCLE) + (with_mask ? (sum_len + 7) / 8 : 0) + 4096;
+	return work + work / 8;
+}

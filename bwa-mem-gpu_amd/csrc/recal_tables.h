@@ -1,7 +1,9 @@
 // The base-quality recalibration table of a coordinate-sorted BAM file (include/bwahip.h), the parts that the device-free
-// builder (recal_host.cpp) shares with a device stage (none yet): how the options resolve, which record takes part, the covariates of a
-// base, the mask, the dense tables and their one serialiser.  A record is read and judged as for the pileup (pileup_tables.h).  Plain C++;
-// __host__ __device__ where a HIP compiler reads it.
+// builder (recal_host.cpp) shares with the device stage (k_recal.hip): how the options resolve, which record takes part, the covariates of a
+// base, the mask, the dense tables and their one serialiser, and the whole of the device stage's private counting -- which cell of a workgroup's LDS a base
+// goes to, how a quality claims a slot there, how the claimed slots are flushed -- so that a CPU program (tests/recal_slots_check.cpp) runs the
+// same lines the kernel does.  A record is read and judged as for the pileup (pileup_tables.h).  Plain C++; __host__ __device__ where a HIP
+// compiler reads it.
 #pragma once
 #include "pileup_tables.h"
 
@@ -59,6 +61,71 @@ template <class Count, class Masked> RC_HD inline void rc_walk(const PuRec &r, i
 			p += n; q += n;
 		} else if (op == 2 || op == 3) p += n;
 		else if (op == 1 || op == 4) q += n;
+	}
+}
+
+// ---- The private counting of the device stage (k_recal.hip).  A workgroup counts a share of RC_SHARE consecutive records in 32-bit cells
+// of its LDS and adds every non-zero cell to the dense tables once, at its end.  Two arrays of pairs (n_obs, n_err): the context table
+// whole (RC_NQ x RC_NCTX), and the cycle table for the cycles below RC_LDS_CYCLES of RC_LDS_SLOTS qualities.  A quality gets its slot at
+// its first base: tag[slot] goes from RC_SLOT_EMPTY to Q by compare-and-swap and never changes again.  A base whose cycle or quality has
+// no cell there goes straight to the dense table.  The kernel body holds none of this: it hands in functors over its arrays.
+// 32 bits hold a cell: it counts at most one base per cycle and record (the context table: one per base), a record that is counted has
+// at most RC_MAX_CYCLE bases (a longer one is refused before its walk), so a cell stays below RC_SHARE x RC_MAX_CYCLE = 2^25.
+constexpr int RC_SHARE = 512, RC_LDS_SLOTS = 8, RC_LDS_CYCLES = 256;
+constexpr int RC_LDS_CTX_WORDS = 2 * RC_NQ * RC_NCTX, RC_LDS_CYC_WORDS = 2 * RC_LDS_SLOTS * 2 * RC_LDS_CYCLES;
+constexpr uint32_t RC_SLOT_EMPTY = 0xffffffffu;                   // no quality: as one it lies outside the dense table
+static_assert(RC_SLOT_EMPTY >= (uint32_t)RC_NQ && (int64_t)RC_SHARE * RC_MAX_CYCLE < (1ll << 32), "the empty tag is no quality; a cell holds a share");
+RC_HD inline int rc_lds_ctx_cell(uint32_t Q, uint32_t x) { return 2 * (int)(Q * RC_NCTX + x); }                                   // Q < RC_NQ, x < RC_NCTX
+RC_HD inline int rc_lds_cyc_cell(int slot, uint32_t mate, uint32_t c) { return 2 * (int)(((uint32_t)slot * 2 + mate) * RC_LDS_CYCLES + c); }   // 0 <= slot < RC_LDS_SLOTS, mate < 2, c < RC_LDS_CYCLES
+
+// The slot of quality Q < RC_NQ, claimed here if it has none and one is empty; -1: every slot holds another quality.  load(s): tag[s];
+// cas(s, expected, desired): the compare-and-swap on tag[s], returns what was there.  A tag only ever goes from RC_SLOT_EMPTY to a quality,
+// and a slot is passed only when it holds another quality, so a quality never has two slots, whoever else claims meanwhile.
+template <class Load, class Cas> RC_HD inline int rc_slot_claim(uint32_t Q, Load load, Cas cas)
+{
+	for (int s = 0; s < RC_LDS_SLOTS; ++s) {
+		uint32_t t = load(s);
+		if (t == RC_SLOT_EMPTY) { t = cas(s, RC_SLOT_EMPTY, Q); if (t == RC_SLOT_EMPTY) return s; }
+		if (t == Q) return s;
+	}
+	return -1;
+}
+
+// One counted base.  ctx_add(cell, error) and cyc_add(cell, error) add (1, error) to the pair at that cell of the two LDS arrays,
+// tab_add(word, error) to the pair at that word of the dense tables
+template <class Load, class Cas, class CtxAdd, class CycAdd, class TabAdd>
+RC_HD inline void rc_count_base(int max_cycle, uint32_t Q, uint32_t mate, uint32_t c, uint32_t x, bool error, Load load, Cas cas, CtxAdd ctx_add, CycAdd cyc_add, TabAdd tab_add)
+{
+	ctx_add(rc_lds_ctx_cell(Q, x), error);
+	const int slot = c < (uint32_t)RC_LDS_CYCLES ? rc_slot_claim(Q, load, cas) : -1;
+	if (slot >= 0) cyc_add(rc_lds_cyc_cell(slot, mate, c), error);
+	else tab_add(rc_cell(max_cycle, Q, rc_col_cycle(max_cycle, mate, c)), error);
+}
+
+// The flush of a share, by `step` workers of which this is worker `first`: flush(word, n_obs, n_err) for every non-zero pair, `word` its
+// place in the dense tables.  The quality column gets the context table's row sums.  An unclaimed slot is skipped before anything is
+// formed from its tag; so is a cycle the table has no column for (nothing was counted there: a counted record has at most max_cycle bases).
+// load(s): tag[s]; ctx(i), cyc(i): word i of the two LDS arrays
+template <class Load, class Ctx, class Cyc, class Flush> RC_HD inline void rc_flush(int max_cycle, int first, int step, Load load, Ctx ctx, Cyc cyc, Flush flush)
+{
+	for (int i = first; i < RC_NQ * RC_NCTX; i += step) {
+		const uint32_t Q = (uint32_t)i / RC_NCTX, x = (uint32_t)i % RC_NCTX;
+		const int cell = rc_lds_ctx_cell(Q, x);
+		const uint32_t n = ctx(cell), e = ctx(cell + 1);
+		if (n) flush(rc_cell(max_cycle, Q, rc_col_context(max_cycle, x)), n, e);
+	}
+	for (int i = first; i < RC_NQ; i += step) {
+		uint64_t n = 0, e = 0;
+		for (uint32_t x = 0; x < (uint32_t)RC_NCTX; ++x) { n += ctx(rc_lds_ctx_cell((uint32_t)i, x)); e += ctx(rc_lds_ctx_cell((uint32_t)i, x) + 1); }
+		if (n) flush(rc_cell(max_cycle, (uint32_t)i, 0), n, e);
+	}
+	for (int i = first; i < RC_LDS_SLOTS * 2 * RC_LDS_CYCLES; i += step) {
+		const int slot = i / (2 * RC_LDS_CYCLES);
+		const uint32_t mate = (uint32_t)i / RC_LDS_CYCLES & 1, c = (uint32_t)i % RC_LDS_CYCLES, Q = load(slot);
+		if (Q >= (uint32_t)RC_NQ || c >= (uint32_t)max_cycle) continue;   // nobody claimed the slot
+		const int cell = rc_lds_cyc_cell(slot, mate, c);
+		const uint32_t n = cyc(cell), e = cyc(cell + 1);
+		if (n) flush(rc_cell(max_cycle, Q, rc_col_cycle(max_cycle, mate, c)), n, e);
 	}
 }
 

@@ -160,6 +160,8 @@ struct DevSortedSink : Sink {
 	std::vector<int64_t> qc_len; int64_t qc_need = 0, qc_windows = 0; bwahip_qc_builder *qb = nullptr;   // the contigs' lengths, the stage's share of the budget; the fall-back's builder
 	const bwahip_pileup_opt_t *po = nullptr; int pu_fd = -1; bwahip_pileup_stats_t *ps = nullptr;   // bwahip_stream_run_bam_sorted_dev_pileup: the pileup of the file on pu_fd, no fall-back
 	std::vector<int64_t> pu_len;
+	const bwahip_recal_opt_t *ro = nullptr; const uint8_t *rc_mask = nullptr; int rc_fd = -1; bwahip_recal_stats_t *rcs = nullptr;   // bwahip_stream_run_bam_sorted_dev_recal: the table of the file on rc_fd
+	int64_t rc_need = 0;
 	bool no_host = false;                                        // a run that does not fit ends the call: nothing marks, or piles up, on the host
 	std::atomic<bool> fell_back{false};                          // read by the drainers: from now on they download
 	Stream fb_stream; HostBuf fb_rec, fb_keys, fb_off;   // the fall-back's downloads: their stream, one pinned buffer each for records, keys and offsets
@@ -175,6 +177,8 @@ struct DevSortedSink : Sink {
 	}
 	// beside configure(..., no_fallback = true): the pileup of the file on pu_fd_ (k_pileup.hip), over the contexts' reference
 	void configure_pileup(const bwahip_pileup_opt_t *po_, int pu_fd_, bwahip_pileup_stats_t *ps_) { po = po_; pu_fd = pu_fd_; ps = ps_; no_host = true; }
+	// likewise the recalibration table of the file on rc_fd_ (k_recal.hip), over the contexts' reference and this mask
+	void configure_recal(const bwahip_recal_opt_t *ro_, const uint8_t *mask_, int rc_fd_, bwahip_recal_stats_t *rs_) { ro = ro_; rc_mask = mask_; rc_fd = rc_fd_; rcs = rs_; no_host = true; }
 	~DevSortedSink()
 	{
 		if (ctx0) (void)hipSetDevice(ctx0->device);
@@ -205,6 +209,13 @@ struct DevSortedSink : Sink {
 			for (int32_t i = 0; i < bns->n_seqs; ++i) pu_len.push_back(bns->anns[i].len);
 			if ((r = bwahip_bam_devmerger_set_pileup(dm, po, (int32_t)pu_len.size(), pu_len.data(), nullptr, pu_fd, ps))) return r;
 		}
+		if (ro) {                                                   // likewise
+			const bwahip_bns_t *bns = bwahip_bns(ctxs[0]);
+			std::vector<int64_t> len;
+			for (int32_t i = 0; i < bns->n_seqs; ++i) len.push_back(bns->anns[i].len);
+			if ((r = bwahip_bam_devmerger_set_recal(dm, ro, (int32_t)len.size(), len.data(), nullptr, rc_mask, rc_fd, rcs))) return r;
+			rc_need = bwahip_recal_hbm_need(bns->l_pac, ro->max_cycle, rc_mask != nullptr);
+		}
 		ctx0 = ctxs[0]; hbm_budget = sd->hbm_budget;
 		piece_blocks = sd->piece_blocks > 0 ? sd->piece_blocks : ctx0->knobs.sorted_piece_blocks;
 		if (!hbm_budget) {                                          // half of what the device has free now
@@ -227,7 +238,7 @@ struct DevSortedSink : Sink {
 	// the HBM the enabled stages take beside the merger's own, for this many records, raw bytes and templates
 	int64_t stages_need(int64_t n_rec, int64_t raw, int64_t n_tmpl) const
 	{
-		int64_t need = qc_need;
+		int64_t need = qc_need + rc_need;
 		if (host.with_bai) need += bwahip_bam_devmerge_bai_hbm_need(n_rec, bgzf_blocks(raw), host.n_ref, bai_windows);
 		if (markdup) need += bwahip_bam_devmerge_markdup_hbm_need(n_rec, n_tmpl);
 		if (po) need += bwahip_pileup_hbm_need(n_rec);
@@ -701,5 +712,22 @@ extern "C" int bwahip_stream_run_bam_sorted_dev_spill(bwahip_ctx *const *ctxs, i
 	if (qs) memset(qs, 0, sizeof *qs);
 	SpillSortedSink sink(hdr_line, sd, sp);
 	sink.configure(bai_fd, mark != 0, ms, qc, qc_fd, qs, true);
+	return stream_run(ctxs, n_ctx, opt, pes0, fq1, fq2, out_fd, st, sink);
+}
+
+// bwahip_stream_run_bam_sorted_dev_spill with the recalibration table of the file on rc_fd (k_recal.hip): the same sink, its merger armed for the
+// table over the contexts' reference and the caller's mask
+extern "C" int bwahip_stream_run_bam_sorted_dev_recal(bwahip_ctx *const *ctxs, int n_ctx, const bwahip_opt_t *opt, const bwahip_pestat_t *pes0,
+                                                      const char *fq1, const char *fq2, int out_fd, const char *hdr_line, bwahip_stream_t *st, bwahip_sort_dev_t *sd, bwahip_spill_t *sp,
+                                                      int bai_fd, int mark, bwahip_markdup_stats_t *ms, const bwahip_qc_opt_t *qc, int qc_fd, bwahip_qc_stats_t *qs,
+                                                      const bwahip_recal_opt_t *rc, const uint8_t *mask, int rc_fd, bwahip_recal_stats_t *rs)
+{
+	if (!sd || !sp || !rc) return BWAHIP_EINVAL;
+	if (ms) memset(ms, 0, sizeof *ms);
+	if (qs) memset(qs, 0, sizeof *qs);
+	if (rs) memset(rs, 0, sizeof *rs);
+	SpillSortedSink sink(hdr_line, sd, sp);
+	sink.configure(bai_fd, mark != 0, ms, qc, qc_fd, qs, true);
+	sink.configure_recal(rc, mask, rc_fd, rs);
 	return stream_run(ctxs, n_ctx, opt, pes0, fq1, fq2, out_fd, st, sink);
 }

@@ -800,7 +800,7 @@ int  bwahip_stream_run_bam_sorted_dev_spill(bwahip_ctx *const *ctxs, int n_ctx, 
                                             int mark, bwahip_markdup_stats_t *ms,
                                             const bwahip_qc_opt_t *qc /* NULL: none */, int qc_fd, bwahip_qc_stats_t *qs);
 
-/* ---- Base-quality recalibration table of coordinate-sorted BAM (csrc/recal_host.cpp: without a device; no device stage yet) ----
+/* ---- Base-quality recalibration table of coordinate-sorted BAM (csrc/k_recal.hip on the device, csrc/recal_host.cpp without one) ----
  * How often a base disagrees with the reference, by reported quality, machine cycle and dinucleotide context, with known variant sites
  * kept out: one canonical table, recomputable from the records of the file, the contig lengths, the packed reference and the mask alone.
  * All values are integers.  The bytes do not depend on the order of the records, on how they are cut into runs, calls or windows, or on
@@ -832,7 +832,7 @@ int  bwahip_stream_run_bam_sorted_dev_spill(bwahip_ctx *const *ctxs, int n_ctx, 
  *                   Only rows with n_obs > 0, ascending by (Q, x); x = 0 in the quality table, mate << 31 | c in the cycle table, the
  *                   context in the context table.  Every table's n_obs sum to n_bases and its n_err to n_err.
  * Device-free builder (csrc/recal_host.cpp): the judge's twin and the one serialiser, a library for small inputs and no fall-back of
- * anything; a stage of the device merger's finish that hands its tables to the same serialiser is not part of the library yet.
+ * anything; the stage of the device merger's finish (below) hands its tables to the same serialiser.
  * open: the contig lengths, the packed reference and the mask (both copied; mask NULL: none) and the options (NULL: all defaults).
  * add_records: whole records, record i is rec[rec_off[i] .. rec_off[i+1]), any cut into calls, any order.  finish: the file on rc_fd
  * (< 0: built and dropped).  After a refusal every later call returns the same code.  It holds dense tables of 64-bit words -- 94 rows
@@ -844,6 +844,48 @@ int  bwahip_recal_builder_open(int32_t n_ref, const int64_t *ref_len, const uint
 int  bwahip_recal_builder_add_records(bwahip_recal_builder *b, const uint8_t *rec, const int64_t *rec_off, int64_t n_rec);
 int  bwahip_recal_builder_finish(bwahip_recal_builder *b, int rc_fd);
 void bwahip_recal_builder_close(bwahip_recal_builder *b);
+/* The stage on the device (csrc/k_recal.hip), one pass over the records, 16 lanes per record: a workgroup counts a share of 512
+ * consecutive records in its LDS -- the context table whole, the cycle table for the cycles below 256 of eight qualities that claim
+ * their slots on first use; every other base goes to the dense tables in HBM by 64-bit atomic adds -- and adds its non-zero cells to the
+ * dense tables once (the quality table: the context table's row sums); the dense tables come back in one awaited download and go through
+ * the host builder's serialiser.  Integers only: the bytes do not depend on scheduling.
+ * bwahip_kat_recal: exactly that stage on the caller's records (host pointers, any order), the caller's packed reference and the
+ * caller's mask (NULL: none); the file into out (out_cap too small: BWAHIP_ECAPACITY, *out_len says what it takes).  opt == NULL: all
+ * defaults.
+ * bwahip_bam_devmerger_set_recal arms a device merger: every finish (_finish, _finish_bai, _finish_markdup) then runs the stage over the
+ * records last of the record stages, after the marking -- the default exclude_flags hold 0x400, so the table of a marked finish does not
+ * count what that finish marked -- and writes the file to rc_fd (< 0: built and dropped) once the members are written.  With all runs
+ * resident a refusal comes before a byte of the members is written; the stage reads every record once, so over spilled runs it runs per
+ * window as the QC summary does, and a refusal then comes after the members.  It is not interlocked with set_spill.  pac == NULL: the
+ * reference is the context's index, where it lies in HBM; n_ref and ref_len must then equal its contig table (BWAHIP_EINVAL).  Otherwise
+ * the merger copies the packed reference; the mask is always copied (NULL: nothing is masked); the copies are uploaded at the first armed
+ * finish that follows.  opt == NULL disarms (the other arguments are not looked at); an unarmed merger queues what it queued before.
+ * *rs (may be NULL) is filled by every armed finish.
+ * bwahip_recal_hbm_need: the stage's HBM, with the eighth of slack its buffers grow with (no device; -1 for a negative argument, a sum
+ * of 2^40 or more or max_cycle > 65 536; max_cycle 0: 1 024): the dense tables -- 16 x 94 x (1 + 2 x max_cycle + 17) bytes --, the mask's
+ * (sum_len + 7) / 8 bytes when with_mask != 0, and 4 096 for the counters, the error word and the contig table's first entries.  A packed
+ * reference of the caller's is not counted. */
+typedef struct {
+	int64_t n_records, n_bases, n_err, n_masked, n_rows[3];   /* as in the file */
+	int64_t rc_bytes;                             /* bytes of the file */
+	int64_t hbm_bytes;                            /* what the stage held */
+	double recal_ms;                              /* GPU time by HIP events: the tables cleared, the records' passes */
+} bwahip_recal_stats_t;
+int  bwahip_kat_recal(bwahip_ctx *ctx, const uint8_t *rec, const int64_t *rec_off, int64_t n_rec, int32_t n_ref, const int64_t *ref_len, const uint8_t *pac, const uint8_t *mask,
+                      const bwahip_recal_opt_t *opt, uint8_t *out, int64_t out_cap, int64_t *out_len);
+int  bwahip_bam_devmerger_set_recal(bwahip_bam_devmerger *m, const bwahip_recal_opt_t *opt, int32_t n_ref, const int64_t *ref_len, const uint8_t *pac, const uint8_t *mask,
+                                    int rc_fd, bwahip_recal_stats_t *rs);
+int64_t bwahip_recal_hbm_need(int64_t sum_len, int max_cycle, int with_mask);
+/* bwahip_stream_run_bam_sorted_dev_spill with the recalibration table of the file on rc_fd: the reference is the contexts' index, mask
+ * (NULL: none) covers its contigs' bases.  The BAM file, the index and the QC summary are byte for byte those of _dev_spill with the
+ * same arguments; hbm_budget counts bwahip_recal_hbm_need too.  rc == NULL: BWAHIP_EINVAL; bad options are refused before anything
+ * starts.  ms, qs and rs may be NULL. */
+int  bwahip_stream_run_bam_sorted_dev_recal(bwahip_ctx *const *ctxs, int n_ctx, const bwahip_opt_t *opt, const bwahip_pestat_t *pes0,
+                                            const char *fq1, const char *fq2, int out_fd, const char *hdr_line, bwahip_stream_t *st,
+                                            bwahip_sort_dev_t *sd, bwahip_spill_t *sp, int bai_fd /* < 0: none */,
+                                            int mark, bwahip_markdup_stats_t *ms,
+                                            const bwahip_qc_opt_t *qc /* NULL: none */, int qc_fd, bwahip_qc_stats_t *qs,
+                                            const bwahip_recal_opt_t *rc, const uint8_t *mask, int rc_fd, bwahip_recal_stats_t *rs);
 
 /* Insert-size statistics (mem_pestat_t[4]: FF, FR, RF, RR; bwamem_pair.c:72) and mate-rescue counters ([0] local alignments
  * run, [1] regions added, [2] most alignments of one pair, [3] pairs that needed any; bwamem_pair.c:137) of the last
