@@ -233,8 +233,9 @@ def lib():
     L.bwahip_bam_devmerger_close.restype = None
     L.bwahip_bam_devmerge_hbm_need.argtypes = [C.c_int64, C.c_int64, C.c_int64, C.c_int]
     L.bwahip_bam_devmerge_hbm_need.restype = C.c_int64
-    L.bwahip_stream_run_bam_sorted_dev.argtypes = [C.POINTER(vp), C.c_int, C.POINTER(Opt), C.POINTER(PeStat), C.c_char_p, C.c_char_p, C.c_int, C.c_char_p,
-                                                   C.POINTER(StreamStats), C.POINTER(SortDevStats)]
+    # the ten leading arguments of every device-merged sorted entry point: contexts, options, files, header, the two stats structs
+    sorted_dev = [C.POINTER(vp), C.c_int, C.POINTER(Opt), C.POINTER(PeStat), C.c_char_p, C.c_char_p, C.c_int, C.c_char_p, C.POINTER(StreamStats), C.POINTER(SortDevStats)]
+    L.bwahip_stream_run_bam_sorted_dev.argtypes = sorted_dev
     L.bwahip_kat_bgzf.argtypes = [vp, vp, C.c_int64, vp, C.c_int64, i64p, i64p, i64p]
     L.bwahip_process_seqs_bgzf.argtypes = [vp, C.POINTER(Opt), C.c_int64, C.c_int, C.POINTER(Seq), C.c_void_p, C.POINTER(vp), i64p, i64p, i64p]
     L.bwahip_batch_run_bgzf.argtypes = [vp, C.POINTER(Opt), C.c_int64, C.POINTER(PeStat), C.POINTER(C.c_float), C.c_int, C.POINTER(C.c_float)]
@@ -256,8 +257,7 @@ def lib():
     L.bwahip_bam_devmerge_bai_hbm_need.restype = C.c_int64
     L.bwahip_stream_run_bam_sorted_bai.argtypes = [C.POINTER(vp), C.c_int, C.POINTER(Opt), C.POINTER(PeStat), C.c_char_p, C.c_char_p, C.c_int, C.c_char_p, C.c_int,
                                                    C.POINTER(StreamStats), C.POINTER(SortStats), C.c_int]
-    L.bwahip_stream_run_bam_sorted_dev_bai.argtypes = [C.POINTER(vp), C.c_int, C.POINTER(Opt), C.POINTER(PeStat), C.c_char_p, C.c_char_p, C.c_int, C.c_char_p,
-                                                       C.POINTER(StreamStats), C.POINTER(SortDevStats), C.c_int]
+    L.bwahip_stream_run_bam_sorted_dev_bai.argtypes = sorted_dev + [C.c_int]
     L.bwahip_dup_end_word.argtypes = [C.c_int32, C.c_int32, C.c_int]
     L.bwahip_dup_end_word.restype = C.c_uint64
     L.bwahip_markdup_decide_host.argtypes = [vp, C.c_int64, vp]
@@ -267,8 +267,7 @@ def lib():
     L.bwahip_bam_devmerger_finish_markdup.argtypes = [vp, C.c_int, C.c_int, C.c_int64, C.c_int32, C.POINTER(DevMergeStats), C.POINTER(BaiStats), C.POINTER(MarkdupStats)]
     L.bwahip_bam_devmerge_markdup_hbm_need.argtypes = [C.c_int64, C.c_int64]
     L.bwahip_bam_devmerge_markdup_hbm_need.restype = C.c_int64
-    L.bwahip_stream_run_bam_sorted_dev_markdup.argtypes = [C.POINTER(vp), C.c_int, C.POINTER(Opt), C.POINTER(PeStat), C.c_char_p, C.c_char_p, C.c_int, C.c_char_p,
-                                                           C.POINTER(StreamStats), C.POINTER(SortDevStats), C.c_int, C.POINTER(MarkdupStats)]
+    L.bwahip_stream_run_bam_sorted_dev_markdup.argtypes = sorted_dev + [C.c_int, C.POINTER(MarkdupStats)]
     L.bwahip_kat_dup_desc.argtypes = [vp, vp, vp, C.c_int64, C.c_int, vp]
     L.bwahip_kat_markdup.argtypes = [vp, vp, C.c_int64, vp]
     L.bwahip_kat_dup_desc_ms.argtypes = [vp]
@@ -293,19 +292,16 @@ def lib():
     L.bwahip_bam_devmerger_set_pileup.argtypes = [vp, C.POINTER(PileupOpt), C.c_int32, vp, vp, C.c_int, C.POINTER(PileupStats)]
     L.bwahip_pileup_hbm_need.argtypes = [C.c_int64]
     L.bwahip_pileup_hbm_need.restype = C.c_int64
-    L.bwahip_stream_run_bam_sorted_dev_pileup.argtypes = [C.POINTER(vp), C.c_int, C.POINTER(Opt), C.POINTER(PeStat), C.c_char_p, C.c_char_p, C.c_int, C.c_char_p,
-                                                          C.POINTER(StreamStats), C.POINTER(SortDevStats), C.c_int, C.c_int, C.POINTER(MarkdupStats), C.POINTER(QcOpt), C.c_int,
+    L.bwahip_stream_run_bam_sorted_dev_pileup.argtypes = sorted_dev + [C.c_int, C.c_int, C.POINTER(MarkdupStats), C.POINTER(QcOpt), C.c_int,
                                                           C.POINTER(QcStats), C.POINTER(PileupOpt), C.c_int, C.POINTER(PileupStats)]
-    L.bwahip_stream_run_bam_sorted_dev_qc.argtypes = [C.POINTER(vp), C.c_int, C.POINTER(Opt), C.POINTER(PeStat), C.c_char_p, C.c_char_p, C.c_int, C.c_char_p,
-                                                      C.POINTER(StreamStats), C.POINTER(SortDevStats), C.c_int, C.POINTER(MarkdupStats), C.c_int, C.POINTER(QcOpt), C.c_int,
+    L.bwahip_stream_run_bam_sorted_dev_qc.argtypes = sorted_dev + [C.c_int, C.POINTER(MarkdupStats), C.c_int, C.POINTER(QcOpt), C.c_int,
                                                       C.POINTER(QcStats)]
     L.bwahip_bam_devmerger_set_spill.argtypes = [vp, C.POINTER(SpillStats)]
     L.bwahip_bam_devmerger_add_spilled.argtypes = [vp, C.c_int64, vp, C.c_int64, vp, vp, C.c_int64, vp, vp, C.c_int64]
     L.bwahip_bam_devmerger_spill_stats.argtypes = [vp, C.POINTER(SpillStats)]
     L.bwahip_bam_devmerge_spill_hbm_need.argtypes = [C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_int]
     L.bwahip_bam_devmerge_spill_hbm_need.restype = C.c_int64
-    L.bwahip_stream_run_bam_sorted_dev_spill.argtypes = [C.POINTER(vp), C.c_int, C.POINTER(Opt), C.POINTER(PeStat), C.c_char_p, C.c_char_p, C.c_int, C.c_char_p,
-                                                         C.POINTER(StreamStats), C.POINTER(SortDevStats), C.POINTER(SpillStats), C.c_int, C.c_int, C.POINTER(MarkdupStats),
+    L.bwahip_stream_run_bam_sorted_dev_spill.argtypes = sorted_dev + [C.POINTER(SpillStats), C.c_int, C.c_int, C.POINTER(MarkdupStats),
                                                          C.POINTER(QcOpt), C.c_int, C.POINTER(QcStats)]
     L.bwahip_recal_builder_open.argtypes = [C.c_int32, vp, vp, vp, C.POINTER(RecalOpt), C.POINTER(vp)]
     L.bwahip_recal_builder_add_records.argtypes = [vp, vp, vp, C.c_int64]
@@ -316,8 +312,7 @@ def lib():
     L.bwahip_bam_devmerger_set_recal.argtypes = [vp, C.POINTER(RecalOpt), C.c_int32, vp, vp, vp, C.c_int, C.POINTER(RecalStats)]
     L.bwahip_recal_hbm_need.argtypes = [C.c_int64, C.c_int, C.c_int]
     L.bwahip_recal_hbm_need.restype = C.c_int64
-    L.bwahip_stream_run_bam_sorted_dev_recal.argtypes = [C.POINTER(vp), C.c_int, C.POINTER(Opt), C.POINTER(PeStat), C.c_char_p, C.c_char_p, C.c_int, C.c_char_p,
-                                                         C.POINTER(StreamStats), C.POINTER(SortDevStats), C.POINTER(SpillStats), C.c_int, C.c_int, C.POINTER(MarkdupStats),
+    L.bwahip_stream_run_bam_sorted_dev_recal.argtypes = sorted_dev + [C.POINTER(SpillStats), C.c_int, C.c_int, C.POINTER(MarkdupStats),
                                                          C.POINTER(QcOpt), C.c_int, C.POINTER(QcStats), C.POINTER(RecalOpt), vp, C.c_int, C.POINTER(RecalStats)]
     L.bwahip_kat_radix_sort.argtypes = [vp, C.c_int64, vp, C.c_int, vp, C.POINTER(C.c_int)]
     L.bwahip_fastq_open.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(vp)]
@@ -1575,20 +1570,44 @@ def stream_run_bam_sorted(ctxs, fq1, fq2=None, out_fd=-1, hdr_line=None, level=1
     return st, so
 
 
-def stream_run_bam_sorted_dev(ctxs, fq1, fq2=None, out_fd=-1, hdr_line=None, opt=None, chunk_bases=0, max_reads=0, keep_comments=False,
-                              reader_threads=0, pes0=None, hbm_budget=0, piece_blocks=0, tmp_dir=None, mem_budget=1 << 30, level=1):
-    """bwahip_stream_run_bam_sorted_dev: FASTQ files -> a coordinate-sorted BAM file on out_fd, the runs kept, merged and deflated in HBM;
-    tmp_dir, mem_budget and level are the host merger's after a fall-back.  Returns (StreamStats, SortDevStats)."""
+def _sorted_dev(name, ctxs, fq1, fq2, out_fd, hdr_line, opt, pes0, reader, hbm_budget, piece_blocks, tmp_dir=None, mem_budget=0, level=1):
+    """What the stream_run_bam_sorted_dev* wrappers share: StreamStats filled from reader = (chunk_bases, max_reads, keep_comments,
+    reader_threads), SortDevStats from the budgets (tmp_dir, mem_budget and level are the host merger's after a fall-back), the context
+    array and the encoded header.  Returns (st, sd, call): call(*rest) runs entry point `name` with the ten leading arguments all of them
+    take, then rest, and raises on an error."""
     opt = opt or default_opt()
     st, sd = StreamStats(), SortDevStats()
-    st.chunk_bases, st.max_reads, st.keep_comments, st.reader_threads = chunk_bases, max_reads, int(keep_comments), reader_threads
+    st.chunk_bases, st.max_reads, st.keep_comments, st.reader_threads = reader[0], reader[1], int(reader[2]), reader[3]
     sd.tmp_dir, sd.mem_budget, sd.level = os.fsencode(tmp_dir) if tmp_dir is not None else None, mem_budget, level
     sd.hbm_budget, sd.piece_blocks = hbm_budget, piece_blocks
     arr = (C.c_void_p * len(ctxs))(*[c._h for c in ctxs])
     if isinstance(hdr_line, str):
         hdr_line = hdr_line.encode()
-    _check(lib().bwahip_stream_run_bam_sorted_dev(arr, len(ctxs), C.byref(opt), C.byref(pes0) if pes0 is not None else None, os.fsencode(fq1),
-                                                  os.fsencode(fq2) if fq2 else None, out_fd, hdr_line, C.byref(st), C.byref(sd)), "bwahip_stream_run_bam_sorted_dev")
+
+    def call(*rest):
+        _check(getattr(lib(), name)(arr, len(ctxs), C.byref(opt), C.byref(pes0) if pes0 is not None else None, os.fsencode(fq1), os.fsencode(fq2) if fq2 else None,
+                                    out_fd, hdr_line, C.byref(st), C.byref(sd), *rest), name)
+    return st, sd, call
+
+
+def _spill_stats(host_budget, tmp_dir, window_pieces):
+    sp = SpillStats()
+    sp.host_budget, sp.tmp_dir, sp.window_pieces = host_budget, os.fsencode(tmp_dir) if tmp_dir is not None else None, window_pieces
+    return sp
+
+
+def _opt_ref(make, values):
+    """byref of the options struct made of `values`, or None to pass no options"""
+    return C.byref(make(*values)) if values is not None else None
+
+
+def stream_run_bam_sorted_dev(ctxs, fq1, fq2=None, out_fd=-1, hdr_line=None, opt=None, chunk_bases=0, max_reads=0, keep_comments=False,
+                              reader_threads=0, pes0=None, hbm_budget=0, piece_blocks=0, tmp_dir=None, mem_budget=1 << 30, level=1):
+    """bwahip_stream_run_bam_sorted_dev: FASTQ files -> a coordinate-sorted BAM file on out_fd, the runs kept, merged and deflated in HBM;
+    tmp_dir, mem_budget and level are the host merger's after a fall-back.  Returns (StreamStats, SortDevStats)."""
+    st, sd, call = _sorted_dev("bwahip_stream_run_bam_sorted_dev", ctxs, fq1, fq2, out_fd, hdr_line, opt, pes0, (chunk_bases, max_reads, keep_comments, reader_threads),
+                               hbm_budget, piece_blocks, tmp_dir, mem_budget, level)
+    call()
     return st, sd
 
 
@@ -1611,16 +1630,9 @@ def stream_run_bam_sorted_dev_bai(ctxs, fq1, fq2=None, out_fd=-1, bai_fd=-1, hdr
                                   reader_threads=0, pes0=None, hbm_budget=0, piece_blocks=0, tmp_dir=None, mem_budget=1 << 30, level=1):
     """bwahip_stream_run_bam_sorted_dev_bai: stream_run_bam_sorted_dev with the BAI index of the file on bai_fd, built on the device (after
     a fall-back: by the host builder).  Returns (StreamStats, SortDevStats)."""
-    opt = opt or default_opt()
-    st, sd = StreamStats(), SortDevStats()
-    st.chunk_bases, st.max_reads, st.keep_comments, st.reader_threads = chunk_bases, max_reads, int(keep_comments), reader_threads
-    sd.tmp_dir, sd.mem_budget, sd.level = os.fsencode(tmp_dir) if tmp_dir is not None else None, mem_budget, level
-    sd.hbm_budget, sd.piece_blocks = hbm_budget, piece_blocks
-    arr = (C.c_void_p * len(ctxs))(*[c._h for c in ctxs])
-    if isinstance(hdr_line, str):
-        hdr_line = hdr_line.encode()
-    _check(lib().bwahip_stream_run_bam_sorted_dev_bai(arr, len(ctxs), C.byref(opt), C.byref(pes0) if pes0 is not None else None, os.fsencode(fq1),
-                                                      os.fsencode(fq2) if fq2 else None, out_fd, hdr_line, C.byref(st), C.byref(sd), bai_fd), "bwahip_stream_run_bam_sorted_dev_bai")
+    st, sd, call = _sorted_dev("bwahip_stream_run_bam_sorted_dev_bai", ctxs, fq1, fq2, out_fd, hdr_line, opt, pes0, (chunk_bases, max_reads, keep_comments, reader_threads),
+                               hbm_budget, piece_blocks, tmp_dir, mem_budget, level)
+    call(bai_fd)
     return st, sd
 
 
@@ -1629,17 +1641,10 @@ def stream_run_bam_sorted_dev_markdup(ctxs, fq1, fq2=None, out_fd=-1, bai_fd=-1,
     """bwahip_stream_run_bam_sorted_dev_markdup: stream_run_bam_sorted_dev_bai with duplicates marked on the device before the deflate
     (bai_fd < 0: no index).  No host fall-back: a run that does not fit hbm_budget raises ECAPACITY.  Returns (StreamStats, SortDevStats,
     MarkdupStats)."""
-    opt = opt or default_opt()
-    st, sd, ms = StreamStats(), SortDevStats(), MarkdupStats()
-    st.chunk_bases, st.max_reads, st.keep_comments, st.reader_threads = chunk_bases, max_reads, int(keep_comments), reader_threads
-    sd.tmp_dir, sd.mem_budget, sd.level = None, 0, 1
-    sd.hbm_budget, sd.piece_blocks = hbm_budget, piece_blocks
-    arr = (C.c_void_p * len(ctxs))(*[c._h for c in ctxs])
-    if isinstance(hdr_line, str):
-        hdr_line = hdr_line.encode()
-    _check(lib().bwahip_stream_run_bam_sorted_dev_markdup(arr, len(ctxs), C.byref(opt), C.byref(pes0) if pes0 is not None else None, os.fsencode(fq1),
-                                                          os.fsencode(fq2) if fq2 else None, out_fd, hdr_line, C.byref(st), C.byref(sd), bai_fd, C.byref(ms)),
-           "bwahip_stream_run_bam_sorted_dev_markdup")
+    st, sd, call = _sorted_dev("bwahip_stream_run_bam_sorted_dev_markdup", ctxs, fq1, fq2, out_fd, hdr_line, opt, pes0, (chunk_bases, max_reads, keep_comments, reader_threads),
+                               hbm_budget, piece_blocks)
+    ms = MarkdupStats()
+    call(bai_fd, C.byref(ms))
     return st, sd, ms
 
 
@@ -1648,17 +1653,10 @@ def stream_run_bam_sorted_dev_qc(ctxs, fq1, fq2=None, out_fd=-1, bai_fd=-1, qc_f
     """bwahip_stream_run_bam_sorted_dev_qc: stream_run_bam_sorted_dev_markdup (markdup) or stream_run_bam_sorted_dev_bai with the QC summary of
     the file on qc_fd (csrc/k_qc.hip; after a fall-back: the host builder).  qc = (window_shift, exclude_flags, min_mapq).  Returns
     (StreamStats, SortDevStats, MarkdupStats, QcStats)."""
-    opt = opt or default_opt()
-    st, sd, ms, qs = StreamStats(), SortDevStats(), MarkdupStats(), QcStats()
-    st.chunk_bases, st.max_reads, st.keep_comments, st.reader_threads = chunk_bases, max_reads, int(keep_comments), reader_threads
-    sd.tmp_dir, sd.mem_budget, sd.level = os.fsencode(tmp_dir) if tmp_dir is not None else None, mem_budget, level
-    sd.hbm_budget, sd.piece_blocks = hbm_budget, piece_blocks
-    arr = (C.c_void_p * len(ctxs))(*[c._h for c in ctxs])
-    if isinstance(hdr_line, str):
-        hdr_line = hdr_line.encode()
-    _check(lib().bwahip_stream_run_bam_sorted_dev_qc(arr, len(ctxs), C.byref(opt), C.byref(pes0) if pes0 is not None else None, os.fsencode(fq1),
-                                                     os.fsencode(fq2) if fq2 else None, out_fd, hdr_line, C.byref(st), C.byref(sd), bai_fd, C.byref(ms), int(bool(markdup)),
-                                                     C.byref(qc_opt(*qc)), qc_fd, C.byref(qs)), "bwahip_stream_run_bam_sorted_dev_qc")
+    st, sd, call = _sorted_dev("bwahip_stream_run_bam_sorted_dev_qc", ctxs, fq1, fq2, out_fd, hdr_line, opt, pes0, (chunk_bases, max_reads, keep_comments, reader_threads),
+                               hbm_budget, piece_blocks, tmp_dir, mem_budget, level)
+    ms, qs = MarkdupStats(), QcStats()
+    call(bai_fd, C.byref(ms), int(bool(markdup)), C.byref(qc_opt(*qc)), qc_fd, C.byref(qs))
     return st, sd, ms, qs
 
 
@@ -1668,19 +1666,10 @@ def stream_run_bam_sorted_dev_pileup(ctxs, fq1, fq2=None, out_fd=-1, bai_fd=-1, 
     the contexts' reference.  bai_fd >= 0: the index; markdup: duplicates marked; qc = (window_shift, exclude_flags, min_mapq) or (): the QC
     summary on qc_fd; pileup = (min_mapq, min_baseq, exclude_flags, min_alt), None to pass no options.  No host fall-back.  Returns
     (StreamStats, SortDevStats, MarkdupStats, QcStats, PileupStats)."""
-    opt = opt or default_opt()
-    st, sd, ms, qs, ps = StreamStats(), SortDevStats(), MarkdupStats(), QcStats(), PileupStats()
-    st.chunk_bases, st.max_reads, st.keep_comments, st.reader_threads = chunk_bases, max_reads, int(keep_comments), reader_threads
-    sd.tmp_dir, sd.mem_budget, sd.level = None, 0, 1
-    sd.hbm_budget, sd.piece_blocks = hbm_budget, piece_blocks
-    arr = (C.c_void_p * len(ctxs))(*[c._h for c in ctxs])
-    if isinstance(hdr_line, str):
-        hdr_line = hdr_line.encode()
-    _check(lib().bwahip_stream_run_bam_sorted_dev_pileup(arr, len(ctxs), C.byref(opt), C.byref(pes0) if pes0 is not None else None, os.fsencode(fq1),
-                                                         os.fsencode(fq2) if fq2 else None, out_fd, hdr_line, C.byref(st), C.byref(sd), bai_fd, int(bool(markdup)), C.byref(ms),
-                                                         C.byref(qc_opt(*qc)) if qc is not None else None, qc_fd, C.byref(qs),
-                                                         C.byref(pileup_opt(*pileup)) if pileup is not None else None, pu_fd, C.byref(ps)),
-           "bwahip_stream_run_bam_sorted_dev_pileup")
+    st, sd, call = _sorted_dev("bwahip_stream_run_bam_sorted_dev_pileup", ctxs, fq1, fq2, out_fd, hdr_line, opt, pes0, (chunk_bases, max_reads, keep_comments, reader_threads),
+                               hbm_budget, piece_blocks)
+    ms, qs, ps = MarkdupStats(), QcStats(), PileupStats()
+    call(bai_fd, int(bool(markdup)), C.byref(ms), _opt_ref(qc_opt, qc), qc_fd, C.byref(qs), _opt_ref(pileup_opt, pileup), pu_fd, C.byref(ps))
     return st, sd, ms, qs, ps
 
 
@@ -1690,19 +1679,10 @@ def stream_run_bam_sorted_dev_spill(ctxs, fq1, fq2=None, out_fd=-1, bai_fd=-1, q
     not fit hbm_budget keep their record bytes in a host-side store (host_budget, tmp_dir) and the finish stages them window by window.
     bai_fd >= 0: the index; markdup: duplicates marked; qc = (window_shift, exclude_flags, min_mapq) or (): the QC summary on qc_fd.
     Returns (StreamStats, SortDevStats, SpillStats, MarkdupStats, QcStats)."""
-    opt = opt or default_opt()
-    st, sd, sp, ms, qs = StreamStats(), SortDevStats(), SpillStats(), MarkdupStats(), QcStats()
-    st.chunk_bases, st.max_reads, st.keep_comments, st.reader_threads = chunk_bases, max_reads, int(keep_comments), reader_threads
-    sd.tmp_dir, sd.mem_budget, sd.level = None, 0, 1
-    sd.hbm_budget, sd.piece_blocks = hbm_budget, piece_blocks
-    sp.host_budget, sp.tmp_dir, sp.window_pieces = host_budget, os.fsencode(tmp_dir) if tmp_dir is not None else None, window_pieces
-    arr = (C.c_void_p * len(ctxs))(*[c._h for c in ctxs])
-    if isinstance(hdr_line, str):
-        hdr_line = hdr_line.encode()
-    _check(lib().bwahip_stream_run_bam_sorted_dev_spill(arr, len(ctxs), C.byref(opt), C.byref(pes0) if pes0 is not None else None, os.fsencode(fq1),
-                                                        os.fsencode(fq2) if fq2 else None, out_fd, hdr_line, C.byref(st), C.byref(sd), C.byref(sp), bai_fd, int(bool(markdup)),
-                                                        C.byref(ms), C.byref(qc_opt(*qc)) if qc is not None else None, qc_fd, C.byref(qs)),
-           "bwahip_stream_run_bam_sorted_dev_spill")
+    st, sd, call = _sorted_dev("bwahip_stream_run_bam_sorted_dev_spill", ctxs, fq1, fq2, out_fd, hdr_line, opt, pes0, (chunk_bases, max_reads, keep_comments, reader_threads),
+                               hbm_budget, piece_blocks)
+    sp, ms, qs = _spill_stats(host_budget, tmp_dir, window_pieces), MarkdupStats(), QcStats()
+    call(C.byref(sp), bai_fd, int(bool(markdup)), C.byref(ms), _opt_ref(qc_opt, qc), qc_fd, C.byref(qs))
     return st, sd, sp, ms, qs
 
 
@@ -1712,20 +1692,11 @@ def stream_run_bam_sorted_dev_recal(ctxs, fq1, fq2=None, out_fd=-1, bai_fd=-1, q
     """bwahip_stream_run_bam_sorted_dev_recal: stream_run_bam_sorted_dev_spill with the recalibration table of the file on rc_fd
     (csrc/k_recal.hip), over the contexts' reference and this mask of known sites (bytes, None: none).  recal = (min_mapq, min_baseq,
     exclude_flags, max_cycle), None to pass no options.  Returns (StreamStats, SortDevStats, SpillStats, MarkdupStats, QcStats, RecalStats)."""
-    opt = opt or default_opt()
-    st, sd, sp, ms, qs, rs = StreamStats(), SortDevStats(), SpillStats(), MarkdupStats(), QcStats(), RecalStats()
-    st.chunk_bases, st.max_reads, st.keep_comments, st.reader_threads = chunk_bases, max_reads, int(keep_comments), reader_threads
-    sd.tmp_dir, sd.mem_budget, sd.level = None, 0, 1
-    sd.hbm_budget, sd.piece_blocks = hbm_budget, piece_blocks
-    sp.host_budget, sp.tmp_dir, sp.window_pieces = host_budget, os.fsencode(tmp_dir) if tmp_dir is not None else None, window_pieces
-    arr = (C.c_void_p * len(ctxs))(*[c._h for c in ctxs])
-    if isinstance(hdr_line, str):
-        hdr_line = hdr_line.encode()
-    _check(lib().bwahip_stream_run_bam_sorted_dev_recal(arr, len(ctxs), C.byref(opt), C.byref(pes0) if pes0 is not None else None, os.fsencode(fq1),
-                                                        os.fsencode(fq2) if fq2 else None, out_fd, hdr_line, C.byref(st), C.byref(sd), C.byref(sp), bai_fd, int(bool(markdup)),
-                                                        C.byref(ms), C.byref(qc_opt(*qc)) if qc is not None else None, qc_fd, C.byref(qs),
-                                                        C.byref(recal_opt(*recal)) if recal is not None else None, bytes(mask) if mask is not None else None, rc_fd, C.byref(rs)),
-           "bwahip_stream_run_bam_sorted_dev_recal")
+    st, sd, call = _sorted_dev("bwahip_stream_run_bam_sorted_dev_recal", ctxs, fq1, fq2, out_fd, hdr_line, opt, pes0, (chunk_bases, max_reads, keep_comments, reader_threads),
+                               hbm_budget, piece_blocks)
+    sp, ms, qs, rs = _spill_stats(host_budget, tmp_dir, window_pieces), MarkdupStats(), QcStats(), RecalStats()
+    call(C.byref(sp), bai_fd, int(bool(markdup)), C.byref(ms), _opt_ref(qc_opt, qc), qc_fd, C.byref(qs), _opt_ref(recal_opt, recal), bytes(mask) if mask is not None else None,
+         rc_fd, C.byref(rs))
     return st, sd, sp, ms, qs, rs
 
 

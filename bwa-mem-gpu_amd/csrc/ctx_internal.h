@@ -3,6 +3,7 @@
 #pragma once
 #include "bwahip_internal.h"
 #include "own.h"
+#include "upload_once.h"
 #include <atomic>
 #include <memory>
 #include <string>
@@ -365,24 +366,62 @@ int spill_window_addr(hipStream_t st, int rec_lo, int n_rec, int n_runs, const i
                       const unsigned *idx, const uint8_t **addr);
 // A stage of a device merger's finish that reads every record once, run by run, on c->stream, changes none, and leaves a file of its own.  It
 // holds what it was configured with (resolved options, checked contig lengths, where its reference comes from, the caller's stats struct) and
-// its buffers, which later finishes use again.  begin: the layout, the tables cleared; records: one run, or one staged slice of one -- record i
-// = rec[off[i] .. off[i + 1]) within the run's `len` bytes, ord0: the ordinal of its first record among all runs'; done: the rest of the work,
-// the one download (awaited), the file's bytes into `bytes` and the stats -- BWAHIP_EINVAL when a record was refused; write: the bytes to fd
-// (fd < 0: nowhere).  n_records == 0 launches nothing.  takes_windows: a spilled run's slices may pass window by window, each gone when
-// the next arrives -- not so for a stage whose done reads the runs again.
+// its buffers, which later finishes use again.  hbm_need: the HBM it will allocate for that many records, as configured -- the public
+// bwahip_*_hbm_need of its own resolved configuration, so whoever budgets for the stage (the stream driver's sinks, through
+// bam_devmerger_record_stages_need) asks the stage that allocates.  begin: the layout, the tables cleared; records: one run, or one staged
+// slice of one -- record i = rec[off[i] .. off[i + 1]) within the run's `len` bytes, ord0: the ordinal of its first record among all runs';
+// done: the rest of the work, the one download (awaited), the file's bytes into `bytes` and the stats -- BWAHIP_EINVAL when a record was
+// refused; write: the bytes to fd (fd < 0: nowhere).  n_records == 0 launches nothing.  takes_windows: a spilled run's slices may pass
+// window by window, each gone when the next arrives -- not so for a stage whose done reads the runs again.
+// A new stage: implement this, hbm_need included; give the merger a setter (k_bammerge.hip); give the stream driver's request its fields
+// (SortedDevReq, stream.cpp).
 struct RecordStage {
 	bool armed = false; int fd = -1;
 	std::vector<uint8_t> bytes;
 	virtual ~RecordStage() = default;
+	virtual int64_t hbm_need(int64_t n_records) const = 0;
 	virtual int begin(bwahip_ctx *c, int64_t n_records) = 0;
 	virtual int records(bwahip_ctx *c, const uint8_t *rec, const int64_t *off, int64_t n_rec, int64_t len, int64_t ord0) = 0;
 	virtual int done(bwahip_ctx *c) = 0;
 	virtual int write() = 0;
 	virtual bool takes_windows() const = 0;
 };
-// k_qc.hip: the QC summary.  k_pileup.hip: the pileup -- pac: the packed reference of these contigs, copied and uploaded once per call of
-// pu_stage_set (null: the context's, where it lies in HBM).  k_recal.hip: the recalibration table -- pac as for the pileup, mask: the known
-// sites over these contigs' bases, copied and uploaded likewise (null: none).  *_set: resolved options and checked lengths; the stats struct may be null
+// the sum of hbm_need over the merger's armed record stages
+int64_t bam_devmerger_record_stages_need(bwahip_bam_devmerger *m, int64_t n_records);
+// The reference of a stage that reads one (the pileup, the recalibration table): the contigs' lengths and the table `lengths | first base
+// (n_ref + 1)` on the host and in HBM, and the packed reference -- the caller's, copied by set() and uploaded once per set(), or (pac null)
+// the context's, read where it lies.  The buffers count in the stage's tally.  A call in flight: begin(c), which says where the packed
+// reference will come from (BWAHIP_EINVAL: bases, and no packed reference anywhere), then, when there are records, upload(q): the table and,
+// if it is due, the caller's reference, in that order on q.  d_pac is good from then on.
+struct DevUpload { static int upload(DevBuf &b, const void *src, size_t bytes, hipStream_t q) { return dev_upload(b, src, bytes, q); } };
+using DevOnce = UploadOnce<DevBuf, DevUpload>;
+struct StageRef {
+	std::vector<int64_t> len, h_tab;
+	int32_t n_ref = 0; int64_t sum = 0, pac_bytes = 0;
+	DevBuf tab; DevOnce own;
+	const uint8_t *d_pac = nullptr;
+	explicit StageRef(Tally &t) : tab(t), own(t) {}
+	const int64_t *d_len() const { return tab.as<int64_t>(); }
+	const int64_t *d_off() const { return tab.as<int64_t>() + n_ref; }
+	void set(int32_t n, const int64_t *ref_len, const uint8_t *pac)
+	{
+		n_ref = n; len.assign(ref_len, ref_len + n);
+		h_tab.assign(2 * (size_t)n + 1, 0);
+		for (int32_t r = 0; r < n; ++r) { h_tab[(size_t)r] = ref_len[r]; h_tab[(size_t)n + r + 1] = h_tab[(size_t)n + r] + ref_len[r]; }
+		sum = h_tab[2 * (size_t)n]; pac_bytes = (sum + 3) / 4;
+		own.set(pac, (size_t)pac_bytes);
+	}
+	int begin(const bwahip_ctx *c) { d_pac = own.held ? nullptr : c->d_pac.as<uint8_t>(); return sum && !d_pac && !own.held ? BWAHIP_EINVAL : 0; }
+	int upload(hipStream_t q)
+	{
+		int rc = dev_upload(tab, h_tab.data(), h_tab.size() * 8, q);
+		if (!rc && !(rc = own.begin(q)) && own.held) d_pac = own.d.as<uint8_t>();
+		return rc;
+	}
+};
+// k_qc.hip: the QC summary.  k_pileup.hip: the pileup -- pac: the packed reference of these contigs (StageRef: null is the context's).
+// k_recal.hip: the recalibration table -- pac as for the pileup, mask: the known sites over these contigs' bases, copied and uploaded
+// likewise (null: none).  *_set: resolved options and checked lengths; the stats struct may be null
 RecordStage *qc_stage_new();
 void qc_stage_set(RecordStage *s, const bwahip_qc_opt_t &opt, int32_t n_ref, const int64_t *ref_len, int fd, bwahip_qc_stats_t *qs);
 RecordStage *pu_stage_new();

@@ -872,6 +872,26 @@ extern "C" int bwahip_bam_devmerger_set_qc(bwahip_bam_devmerger *m, const bwahip
 	return 0;
 }
 
+int64_t bam_devmerger_record_stages_need(bwahip_bam_devmerger *m, int64_t n_records)
+{
+	std::lock_guard<std::mutex> lk(m->mu);
+	int64_t need = 0;
+	for (const RecordStage *s : m->stages) if (s->armed) need += s->hbm_need(n_records);
+	return need;
+}
+
+// the contig lengths of a stage that reads the reference; pac null: the context's index, so these must be its contigs
+static int check_stage_ref(const bwahip_ctx *c, int32_t n_ref, const int64_t *ref_len, const uint8_t *pac)
+{
+	int64_t sum = 0;
+	const int rc = check_refs(n_ref, ref_len, &sum, PU_MAX_SUM);
+	if (rc || pac) return rc;
+	const bwahip_bns_t &bns = c->host.bns;
+	if (n_ref != bns.n_seqs || sum != bns.l_pac || !c->d_pac.p) return BWAHIP_EINVAL;
+	for (int32_t r = 0; r < n_ref; ++r) if (ref_len[r] != bns.anns[r].len) return BWAHIP_EINVAL;
+	return 0;
+}
+
 extern "C" int bwahip_bam_devmerger_set_pileup(bwahip_bam_devmerger *m, const bwahip_pileup_opt_t *opt, int32_t n_ref, const int64_t *ref_len, const uint8_t *pac, int pu_fd,
                                                bwahip_pileup_stats_t *ps)
 {
@@ -880,14 +900,8 @@ extern "C" int bwahip_bam_devmerger_set_pileup(bwahip_bam_devmerger *m, const bw
 	if (!opt) { m->pu->armed = false; return 0; }
 	if (m->spill_armed && !m->pu->takes_windows()) return BWAHIP_EINVAL;   // the evidence pass reads resident runs only
 	bwahip_pileup_opt_t o;
-	int64_t sum = 0;
 	int rc;
-	if ((rc = pu_resolve(opt, &o)) || (rc = check_refs(n_ref, ref_len, &sum, PU_MAX_SUM))) return rc;   // the merger is as before
-	if (!pac) {                                                    // the context's index: these must be its contigs
-		const bwahip_bns_t &bns = m->c->host.bns;
-		if (n_ref != bns.n_seqs || sum != bns.l_pac || !m->c->d_pac.p) return BWAHIP_EINVAL;
-		for (int32_t r = 0; r < n_ref; ++r) if (ref_len[r] != bns.anns[r].len) return BWAHIP_EINVAL;
-	}
+	if ((rc = pu_resolve(opt, &o)) || (rc = check_stage_ref(m->c, n_ref, ref_len, pac))) return rc;   // the merger is as before
 	pu_stage_set(m->pu.get(), o, n_ref, ref_len, pac, pu_fd, ps);   // (the stage copies pac and uploads the copy once)
 	m->pu->armed = true;
 	if (ps) memset(ps, 0, sizeof *ps);
@@ -902,14 +916,8 @@ extern "C" int bwahip_bam_devmerger_set_recal(bwahip_bam_devmerger *m, const bwa
 	std::lock_guard<std::mutex> lk(m->mu);
 	if (!opt) { m->rc->armed = false; return 0; }
 	bwahip_recal_opt_t o;
-	int64_t sum = 0;
 	int rc;
-	if ((rc = rc_resolve(opt, &o)) || (rc = check_refs(n_ref, ref_len, &sum, PU_MAX_SUM))) return rc;   // the merger is as before
-	if (!pac) {                                                    // the context's index: these must be its contigs
-		const bwahip_bns_t &bns = m->c->host.bns;
-		if (n_ref != bns.n_seqs || sum != bns.l_pac || !m->c->d_pac.p) return BWAHIP_EINVAL;
-		for (int32_t r = 0; r < n_ref; ++r) if (ref_len[r] != bns.anns[r].len) return BWAHIP_EINVAL;
-	}
+	if ((rc = rc_resolve(opt, &o)) || (rc = check_stage_ref(m->c, n_ref, ref_len, pac))) return rc;   // the merger is as before
 	recal_stage_set(m->rc.get(), o, n_ref, ref_len, pac, mask, rc_fd, rs);   // (the stage copies pac and the mask and uploads the copies once)
 	m->rc->armed = true;
 	if (rs) memset(rs, 0, sizeof *rs);

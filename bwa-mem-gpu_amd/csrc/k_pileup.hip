@@ -252,25 +252,19 @@ inline unsigned blocks(int64_t threads) { return (unsigned)((threads + 255) / 25
 // The stage's buffers.  cnt and obs_off are what bwahip_pileup_hbm_need counts; the others are made at the finish, when their sizes are known
 struct PileupStage final : RecordStage {
 	Tally hbm;
-	DevBuf cnt{hbm}, obs_off{hbm}, ref_tab{hbm}, tab{hbm}, pac{hbm};
+	DevBuf cnt{hbm}, obs_off{hbm}, tab{hbm};
 	DevBuf flag{hbm}, pos{hbm}, astart{hbm}, fr{hbm}, alleles{hbm}, sites{hbm};
 	HostBuf h_tab;
 	Event ev[4];                                                   // begin, the keys written, the sites made, end
-	// what pu_stage_set gave.  h_pac: the caller's packed reference (own_pac; otherwise the context's is read where it lies), h_pac_gen: counts the calls
+	// what pu_stage_set gave
 	bwahip_pileup_opt_t opt = { 0, 0, 1796, 2 };
-	std::vector<int64_t> ref_len;
-	int32_t n_ref = 0;
-	std::vector<uint8_t> h_pac; bool own_pac = false; uint64_t h_pac_gen = 0;
+	StageRef ref{hbm};
 	bwahip_pileup_stats_t *stats = nullptr;
 	// the call in flight
-	std::vector<int64_t> h_ref_tab;                                // lengths | first base (n_ref + 1)
 	int64_t n_records = 0;
-	const uint8_t *d_pac = nullptr; int64_t pac_bytes = 0;         // the packed reference in HBM: the context's, or `pac`
-	uint64_t pac_gen = 0;                                          // which of the caller's references `pac` holds (0: none)
 	struct Run { const uint8_t *rec; const int64_t *off; int64_t n_rec, ord0; };
 	std::vector<Run> runs;                                         // the runs that passed k_pu_count: emit and evidence read them again
-	const int64_t *d_len() const { return ref_tab.as<int64_t>(); }
-	const int64_t *d_off() const { return ref_tab.as<int64_t>() + n_ref; }
+	int64_t hbm_need(int64_t n) const override { return bwahip_pileup_hbm_need(n); }
 	int begin(bwahip_ctx *c, int64_t n_records) override;
 	int records(bwahip_ctx *c, const uint8_t *rec, const int64_t *off, int64_t n_rec, int64_t len, int64_t ord0) override;
 	int done(bwahip_ctx *c) override;
@@ -283,12 +277,8 @@ RecordStage *pu_stage_new() { return new PileupStage; }
 void pu_stage_set(RecordStage *rs, const bwahip_pileup_opt_t &opt, int32_t n_ref, const int64_t *ref_len, const uint8_t *pac, int fd, bwahip_pileup_stats_t *ps)
 {
 	PileupStage *s = static_cast<PileupStage*>(rs);
-	s->opt = opt; s->n_ref = n_ref; s->ref_len.assign(ref_len, ref_len + n_ref); s->fd = fd; s->stats = ps;
-	int64_t sum = 0;
-	for (int32_t r = 0; r < n_ref; ++r) sum += ref_len[r];
-	s->own_pac = pac != nullptr;
-	if (pac) s->h_pac.assign(pac, pac + (sum + 3) / 4); else s->h_pac.clear();
-	++s->h_pac_gen;                                                // begin uploads the copy once
+	s->opt = opt; s->fd = fd; s->stats = ps;
+	s->ref.set(n_ref, ref_len, pac);
 }
 
 int PileupStage::begin(bwahip_ctx *c, int64_t n_records_)
@@ -296,24 +286,15 @@ int PileupStage::begin(bwahip_ctx *c, int64_t n_records_)
 	if (!c || n_records_ < 0 || n_records_ > 0x7fffffffll) return BWAHIP_EINVAL;
 	int rc;
 	n_records = n_records_;
-	h_ref_tab.assign(2 * (size_t)n_ref + 1, 0);
-	for (int32_t r = 0; r < n_ref; ++r) { h_ref_tab[(size_t)r] = ref_len[(size_t)r]; h_ref_tab[(size_t)n_ref + r + 1] = h_ref_tab[(size_t)n_ref + r] + ref_len[(size_t)r]; }
-	const int64_t sum = h_ref_tab[2 * (size_t)n_ref];
-	d_pac = own_pac ? nullptr : c->d_pac.as<uint8_t>();
-	if (sum && !d_pac && !own_pac) return BWAHIP_EINVAL;
+	if ((rc = ref.begin(c))) return rc;
 	runs.clear();
-	pac_bytes = (sum + 3) / 4;
 	if (!n_records) return 0;                                      // no record: nothing to launch, finish writes the file of no site
 	HIP_TRY(hipSetDevice(c->device));
 	for (auto &e : ev) if (!e && (rc = e.make())) return rc;
 	hipStream_t q = c->stream;
 	if ((rc = cnt.ensure(((size_t)n_records + 1) * 4)) || (rc = obs_off.ensure(((size_t)n_records + 1) * 8)) || (rc = tab.ensure(PU_T_WORDS * 8))) return rc;
 	HIP_TRY(hipEventRecord(ev[0], q));
-	if ((rc = dev_upload(ref_tab, h_ref_tab.data(), h_ref_tab.size() * 8, q))) return rc;
-	if (own_pac) {                                                 // uploaded once per generation
-		if (h_pac_gen != pac_gen) { pac_gen = 0; if ((rc = dev_upload(pac, h_pac.data(), (size_t)pac_bytes, q))) return rc; pac_gen = h_pac_gen; }
-		d_pac = pac.as<uint8_t>();
-	}
+	if ((rc = ref.upload(q))) return rc;
 	HIP_TRY(hipMemsetAsync(tab.p, 0, PU_T_WORDS * 8, q));
 	HIP_TRY(hipMemsetAsync(tab.as<unsigned long long>() + PU_T_ERR, 0xff, 8, q));
 	return 0;
@@ -325,7 +306,7 @@ int PileupStage::records(bwahip_ctx *c, const uint8_t *rec, const int64_t *off, 
 {
 	if (!n_rec) return 0;
 	if (ord0 < 0 || ord0 + n_rec > n_records) return BWAHIP_EINTERNAL;
-	hipLaunchKernelGGL(k_pu_count, dim3(blocks(n_rec * 16)), dim3(256), 0, c->stream, rec, off, n_rec, len, ord0, (int)n_ref, d_len(), d_off(), d_pac, pac_bytes, opt,
+	hipLaunchKernelGGL(k_pu_count, dim3(blocks(n_rec * 16)), dim3(256), 0, c->stream, rec, off, n_rec, len, ord0, (int)ref.n_ref, ref.d_len(), ref.d_off(), ref.d_pac, ref.pac_bytes, opt,
 	                   cnt.as<int>(), tab.as<unsigned long long>());
 	runs.push_back({ rec, off, n_rec, ord0 });
 	return launched();
@@ -337,7 +318,7 @@ int PileupStage::done(bwahip_ctx *c)
 	bwahip_pileup_stats_t st;
 	memset(&st, 0, sizeof st);
 	PuTables t;
-	t.n_ref = n_ref; t.ref_len = ref_len.data(); t.opt = opt;
+	t.n_ref = ref.n_ref; t.ref_len = ref.len.data(); t.opt = opt;
 	int rc;
 	if (n_records) {
 		hipStream_t q = c->stream;
@@ -360,7 +341,7 @@ int PileupStage::done(bwahip_ctx *c)
 			if ((rc = bs.keys[0].ensure((size_t)n * 8)) || (rc = bs.keys[1].ensure((size_t)n * 8)) || (rc = bs.idx[0].ensure((size_t)n * 4)) || (rc = bs.idx[1].ensure((size_t)n * 4)) ||
 			    (rc = this->flag.ensure((size_t)n * 4)) || (rc = this->pos.ensure(((size_t)n + 1) * 8))) return rc;
 			for (const auto &r : runs) {
-				hipLaunchKernelGGL(k_pu_emit, dim3(blocks(r.n_rec * 16)), dim3(256), 0, q, r.rec, r.off, r.n_rec, r.ord0, (int)n_ref, d_len(), d_off(), d_pac, pac_bytes, opt,
+				hipLaunchKernelGGL(k_pu_emit, dim3(blocks(r.n_rec * 16)), dim3(256), 0, q, r.rec, r.off, r.n_rec, r.ord0, (int)ref.n_ref, ref.d_len(), ref.d_off(), ref.d_pac, ref.pac_bytes, opt,
 				                   obs_off.as<int64_t>(), bs.keys[0].as<unsigned long long>(), this->tab.as<unsigned long long>());
 				if ((rc = launched())) return rc;
 			}
@@ -403,13 +384,13 @@ int PileupStage::done(bwahip_ctx *c)
 			if (got < 1 || got > n_kept) return BWAHIP_EINTERNAL;
 			n_sites = (int)got;
 			if ((rc = sites.ensure((size_t)n_sites * sizeof(PuSite)))) return rc;
-			hipLaunchKernelGGL(k_pu_sites, dim3(blocks(n_kept)), dim3(256), 0, q, alleles.as<PuAllele>(), flag, pos, n_kept, d_pac, pac_bytes, sites.as<PuSite>());
+			hipLaunchKernelGGL(k_pu_sites, dim3(blocks(n_kept)), dim3(256), 0, q, alleles.as<PuAllele>(), flag, pos, n_kept, ref.d_pac, ref.pac_bytes, sites.as<PuSite>());
 			if ((rc = launched())) return rc;
 		}
 		HIP_TRY(hipEventRecord(ev[2], q));
 		for (size_t k = 0; n_sites && k < runs.size(); ++k) {
 			const auto &r = runs[k];
-			hipLaunchKernelGGL(k_pu_evidence, dim3(blocks(r.n_rec)), dim3(256), 0, q, r.rec, r.off, r.n_rec, (int)n_ref, d_len(), d_off(), opt, sites.as<PuSite>(), n_sites);
+			hipLaunchKernelGGL(k_pu_evidence, dim3(blocks(r.n_rec)), dim3(256), 0, q, r.rec, r.off, r.n_rec, (int)ref.n_ref, ref.d_len(), ref.d_off(), opt, sites.as<PuSite>(), n_sites);
 			if ((rc = launched())) return rc;
 		}
 		HIP_TRY(hipEventRecord(ev[3], q));

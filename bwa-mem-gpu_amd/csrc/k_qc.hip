@@ -201,6 +201,12 @@ struct QcStage final : RecordStage {
 	const int64_t *d_win_off() const { return ref_tab.as<int64_t>() + 2 * (size_t)n_ref + 1; }
 	unsigned long long *d_win() const { return tab.as<unsigned long long>() + QC_FIXED + QC_PER_REF * (size_t)n_ref; }
 	size_t tab_words() const { return (size_t)QC_FIXED + QC_PER_REF * (size_t)n_ref + (size_t)n_win; }
+	int64_t hbm_need(int64_t) const override
+	{
+		int64_t sum = 0, windows = 0;
+		for (int64_t L : ref_len) { sum += L; windows += qc_windows(L, opt.window_shift); }
+		return bwahip_qc_hbm_need(n_ref, sum, windows, 0);
+	}
 	int begin(bwahip_ctx *c, int64_t n_records) override;
 	int records(bwahip_ctx *c, const uint8_t *rec, const int64_t *off, int64_t n_rec, int64_t len, int64_t ord0) override;
 	int done(bwahip_ctx *c) override;

@@ -156,24 +156,17 @@ inline uint64_t get64(const uint8_t *p) { uint64_t v = 0; for (int k = 7; k >= 0
 // The stage's buffers: counted by bwahip_recal_hbm_need (recal_host.cpp), but for a packed reference of the caller's
 struct RecalStage final : RecordStage {
 	Tally hbm;
-	DevBuf tab{hbm}, cnt{hbm}, ref_tab{hbm}, pac{hbm}, mask{hbm};
+	DevBuf tab{hbm}, cnt{hbm};
 	HostBuf h_tab;
 	Event ev[2];                                                   // begin, end
-	// what recal_stage_set gave.  h_pac: the caller's packed reference (own_pac; otherwise the context's is read where it lies); h_mask: the
-	// caller's mask (with_mask); gen: counts the calls
+	// what recal_stage_set gave.  mask: the caller's mask, uploaded once per call as the reference is (held: with a mask)
 	bwahip_recal_opt_t opt = { 0, 0, RC_DEFAULT_EXCLUDE, RC_DEFAULT_CYCLE };
-	std::vector<int64_t> ref_len;
-	int32_t n_ref = 0;
-	std::vector<uint8_t> h_pac, h_mask; bool own_pac = false, with_mask = false; uint64_t gen = 0;
+	StageRef ref{hbm}; DevOnce mask{hbm};
 	bwahip_recal_stats_t *stats = nullptr;
 	// the call in flight
-	std::vector<int64_t> h_ref_tab;                                // lengths | first base (n_ref + 1)
 	int64_t n_records = 0;
-	const uint8_t *d_pac = nullptr; int64_t pac_bytes = 0, mask_bytes = 0;
-	uint64_t pac_gen = 0, mask_gen = 0;                            // which of the caller's references and masks the buffers hold (0: none)
 	size_t tab_words() const { return (size_t)rc_table_words(opt.max_cycle); }
-	const int64_t *d_len() const { return ref_tab.as<int64_t>(); }
-	const int64_t *d_off() const { return ref_tab.as<int64_t>() + n_ref; }
+	int64_t hbm_need(int64_t) const override { return bwahip_recal_hbm_need(ref.sum, opt.max_cycle, mask.held); }
 	int begin(bwahip_ctx *c, int64_t n_records) override;
 	int records(bwahip_ctx *c, const uint8_t *rec, const int64_t *off, int64_t n_rec, int64_t len, int64_t ord0) override;
 	int done(bwahip_ctx *c) override;
@@ -186,13 +179,9 @@ RecordStage *recal_stage_new() { return new RecalStage; }
 void recal_stage_set(RecordStage *rs, const bwahip_recal_opt_t &opt, int32_t n_ref, const int64_t *ref_len, const uint8_t *pac, const uint8_t *mask, int fd, bwahip_recal_stats_t *st)
 {
 	RecalStage *s = static_cast<RecalStage*>(rs);
-	s->opt = opt; s->n_ref = n_ref; s->ref_len.assign(ref_len, ref_len + n_ref); s->fd = fd; s->stats = st;
-	int64_t sum = 0;
-	for (int32_t r = 0; r < n_ref; ++r) sum += ref_len[r];
-	s->own_pac = pac != nullptr; s->with_mask = mask != nullptr && sum > 0;
-	if (pac) s->h_pac.assign(pac, pac + (sum + 3) / 4); else s->h_pac.clear();
-	if (s->with_mask) s->h_mask.assign(mask, mask + (sum + 7) / 8); else s->h_mask.clear();
-	++s->gen;                                                      // begin uploads the copies once
+	s->opt = opt; s->fd = fd; s->stats = st;
+	s->ref.set(n_ref, ref_len, pac);
+	s->mask.set(s->ref.sum > 0 ? mask : nullptr, (size_t)((s->ref.sum + 7) / 8));   // a mask over no base: none
 }
 
 int RecalStage::begin(bwahip_ctx *c, int64_t n_records_)
@@ -200,24 +189,14 @@ int RecalStage::begin(bwahip_ctx *c, int64_t n_records_)
 	if (!c || n_records_ < 0) return BWAHIP_EINVAL;
 	int rc;
 	n_records = n_records_;
-	h_ref_tab.assign(2 * (size_t)n_ref + 1, 0);
-	for (int32_t r = 0; r < n_ref; ++r) { h_ref_tab[(size_t)r] = ref_len[(size_t)r]; h_ref_tab[(size_t)n_ref + r + 1] = h_ref_tab[(size_t)n_ref + r] + ref_len[(size_t)r]; }
-	const int64_t sum = h_ref_tab[2 * (size_t)n_ref];
-	d_pac = own_pac ? nullptr : c->d_pac.as<uint8_t>();
-	if (sum && !d_pac && !own_pac) return BWAHIP_EINVAL;
-	pac_bytes = (sum + 3) / 4; mask_bytes = with_mask ? (sum + 7) / 8 : 0;
+	if ((rc = ref.begin(c))) return rc;
 	if (!n_records) return 0;                                      // no record: nothing to launch, done writes the header alone
 	HIP_TRY(hipSetDevice(c->device));
 	for (auto &e : ev) if (!e && (rc = e.make())) return rc;
 	hipStream_t q = c->stream;
 	if ((rc = tab.ensure(tab_words() * 8)) || (rc = cnt.ensure(RC_T_WORDS * 8)) || (rc = h_tab.ensure((tab_words() + RC_T_WORDS) * 8))) return rc;
 	HIP_TRY(hipEventRecord(ev[0], q));
-	if ((rc = dev_upload(ref_tab, h_ref_tab.data(), h_ref_tab.size() * 8, q))) return rc;
-	if (own_pac) {                                                 // uploaded once per call of recal_stage_set
-		if (gen != pac_gen) { pac_gen = 0; if ((rc = dev_upload(pac, h_pac.data(), (size_t)pac_bytes, q))) return rc; pac_gen = gen; }
-		d_pac = pac.as<uint8_t>();
-	}
-	if (with_mask && gen != mask_gen) { mask_gen = 0; if ((rc = dev_upload(mask, h_mask.data(), (size_t)mask_bytes, q))) return rc; mask_gen = gen; }
+	if ((rc = ref.upload(q)) || (rc = mask.begin(q))) return rc;
 	HIP_TRY(hipMemsetAsync(tab.p, 0, tab_words() * 8, q));
 	HIP_TRY(hipMemsetAsync(cnt.p, 0, RC_T_WORDS * 8, q));
 	HIP_TRY(hipMemsetAsync(cnt.as<unsigned long long>() + RC_T_ERR, 0xff, 8, q));
@@ -229,8 +208,8 @@ int RecalStage::records(bwahip_ctx *c, const uint8_t *rec, const int64_t *off, i
 {
 	if (!n_rec) return 0;
 	if (n_rec > 0x7fffffffll) return BWAHIP_ECAPACITY;
-	hipLaunchKernelGGL(k_rc_count, dim3((unsigned)((n_rec + RC_SHARE - 1) / RC_SHARE)), dim3(256), 0, c->stream, rec, off, n_rec, len, ord0, (int)n_ref, d_len(), d_off(), d_pac, pac_bytes,
-	                   with_mask ? mask.as<uint8_t>() : nullptr, mask_bytes, opt, tab.as<unsigned long long>(), cnt.as<unsigned long long>());
+	hipLaunchKernelGGL(k_rc_count, dim3((unsigned)((n_rec + RC_SHARE - 1) / RC_SHARE)), dim3(256), 0, c->stream, rec, off, n_rec, len, ord0, (int)ref.n_ref, ref.d_len(), ref.d_off(), ref.d_pac,
+	                   ref.pac_bytes, mask.held ? mask.d.as<uint8_t>() : nullptr, (int64_t)mask.h.size(), opt, tab.as<unsigned long long>(), cnt.as<unsigned long long>());
 	return launched();
 }
 
@@ -240,7 +219,7 @@ int RecalStage::done(bwahip_ctx *c)
 	bwahip_recal_stats_t st;
 	memset(&st, 0, sizeof st);
 	RcTables t;
-	t.n_ref = n_ref; t.opt = opt;
+	t.n_ref = ref.n_ref; t.opt = opt;
 	int rc;
 	if (!n_records) {
 		const std::vector<uint64_t> z(tab_words(), 0);

@@ -27,7 +27,7 @@ int qc_serialise(const QcTables &t, std::vector<uint8_t> *out)
 	if (n_win && !t.win) return BWAHIP_EINVAL;
 	std::vector<uint8_t> &o = *out;
 	o.clear();
-	o.reserve((size_t)(28 + 8 * (QC_FIXED - 1) + 48 * (int64_t)t.n_ref + 8 * n_win));
+	o.reserve((size_t)qc_file_bytes(t.n_ref, n_win));
 	o.insert(o.end(), { 'B', 'Q', 'C', 1 });
 	put32(o, (uint32_t)t.n_ref);
 	put32(o, (uint32_t)t.opt.window_shift); put32(o, (uint32_t)t.opt.exclude_flags); put32(o, (uint32_t)t.opt.min_mapq);
@@ -42,7 +42,7 @@ int qc_serialise(const QcTables &t, std::vector<uint8_t> *out)
 		w0 += nw;
 	}
 	for (int64_t w = 0; w < n_win; ++w) put64(o, t.win[w]);
-	return 0;
+	return (int64_t)o.size() == qc_file_bytes(t.n_ref, n_win) ? 0 : BWAHIP_EINTERNAL;   // (what the stream driver reports after a fall-back)
 }
 
 struct bwahip_qc_builder : SidecarBuilder {

@@ -80,6 +80,8 @@ template <class Put> QC_HD inline void qc_intervals(const QcRec &r, int64_t L, P
 }
 
 inline int64_t qc_windows(int64_t len, int shift) { return (len + (1ll << shift) - 1) >> shift; }
+// the bytes of a summary's file: magic, n_ref and the three options, the fixed words, six words per reference, the windows
+inline int64_t qc_file_bytes(int64_t n_ref, int64_t n_windows) { return 20 + 8 * QC_FIXED + 48 * n_ref + 8 * n_windows; }
 
 // The compact tables of a summary.  fixed: QC_FIXED words; per_ref: QC_PER_REF words per reference; win: the windows of all references one
 // after the other, reference r has qc_windows(ref_len[r], opt.window_shift) of them.  opt: as resolved.

@@ -19,6 +19,7 @@
 // frees first and staging runs ahead of a context that still computes; results do not depend on which context took a batch
 // (tests/test_gpu_multi.py).  No data-path collective: SURVEY.md 8(e).
 #include "../../include/bwahip.h"
+#include "qc_tables.h"                                          // the size of a QC summary
 #include "stream_pipe.h"                                        // with ctx_internal.h: the contexts' devices, the runs a device merger holds (k_bammerge.hip)
 #include <errno.h>
 #include <stdio.h>
@@ -145,40 +146,39 @@ struct SortedSink : Sink {
 	}
 };
 
+// What a device-merged entry point asks of its sink: the products beside the file (an options pointer arms the product, its stats struct may
+// be null) and the two things that are no product.
+//   fall_back  a run that does not fit sd->hbm_budget ends the call on the host, as bwahip_stream_run_bam_sorted does, at sd->level.  Only
+//              what the host can also make may ask for it: _dev, _dev_bai, and _dev_qc unmarked.  Without it the header is written at level 1,
+//              sd->level has no reader, and such a run ends the call (BWAHIP_ECAPACITY) or, with sp, is held spilled: _dev_markdup,
+//              _dev_qc marked, _dev_pileup (even unmarked), _dev_spill, _dev_recal.
+//   index      with_index(bai_fd), for every entry point that takes a bai_fd: a run that may fall back indexes whatever bai_fd is (the
+//              host-merged run would); one that may not, if and only if bai_fd >= 0.  _dev takes none and does not index.
+struct SortedDevReq {
+	bwahip_sort_dev_t *sd = nullptr;
+	bool fall_back = false, index = false; int bai_fd = -1;
+	bool mark = false; bwahip_markdup_stats_t *ms = nullptr;       // the runs carry templates (OutForm::BamSortedDup), the finish marks
+	const bwahip_qc_opt_t *qc = nullptr; int qc_fd = -1; bwahip_qc_stats_t *qs = nullptr;
+	const bwahip_pileup_opt_t *pu = nullptr; int pu_fd = -1; bwahip_pileup_stats_t *ps = nullptr;
+	const bwahip_recal_opt_t *rc = nullptr; const uint8_t *mask = nullptr; int rc_fd = -1; bwahip_recal_stats_t *rs = nullptr;
+	bwahip_spill_t *sp = nullptr;                                  // SpillSortedSink (null: DevSortedSink)
+	void with_index(int fd) { bai_fd = fd; index = fall_back || fd >= 0; }
+};
+
 // Coordinate-sorted BAM merged on the device: every batch is a run of the device merger, copied device to device into buffers of its own,
 // while the HBM budget holds; from the first run that does not fit (or came back downloaded because its buffers could not be allocated)
 // the run ends as the host-merged one: the runs held so far go to its merger in run order, every later one is downloaded.  No host thread
 // deflates.  Without a fall-back the header is written at level 1 and the device merger writes the rest (k_bammerge.hip).
 struct DevSortedSink : Sink {
-	bwahip_sort_dev_t *sd; SortedSink host;
+	const SortedDevReq rq; bwahip_sort_dev_t *sd; SortedSink host;
 	bwahip_bam_devmerger *dm = nullptr; bwahip_ctx *ctx0 = nullptr;
-	int64_t hbm_budget = 0, held_raw = 0, held_rec = 0; int piece_blocks = 0;
-	bwahip_markdup_stats_t *ms = nullptr; bool markdup = false;   // bwahip_stream_run_bam_sorted_dev_markdup: the runs carry templates, no fall-back
-	int64_t held_tmpl = 0;
+	int64_t hbm_budget = 0, held_raw = 0, held_rec = 0, held_tmpl = 0; int piece_blocks = 0;
 	int64_t bai_windows = 0;                                     // with the index: the 16 Kbp windows of the contig table, for the stage's share of the budget
-	const bwahip_qc_opt_t *qo = nullptr; int qc_fd = -1; bwahip_qc_stats_t *qs = nullptr;   // bwahip_stream_run_bam_sorted_dev_qc: the summary of the file on qc_fd
-	std::vector<int64_t> qc_len; int64_t qc_need = 0, qc_windows = 0; bwahip_qc_builder *qb = nullptr;   // the contigs' lengths, the stage's share of the budget; the fall-back's builder
-	const bwahip_pileup_opt_t *po = nullptr; int pu_fd = -1; bwahip_pileup_stats_t *ps = nullptr;   // bwahip_stream_run_bam_sorted_dev_pileup: the pileup of the file on pu_fd, no fall-back
-	std::vector<int64_t> pu_len;
-	const bwahip_recal_opt_t *ro = nullptr; const uint8_t *rc_mask = nullptr; int rc_fd = -1; bwahip_recal_stats_t *rcs = nullptr;   // bwahip_stream_run_bam_sorted_dev_recal: the table of the file on rc_fd
-	int64_t rc_need = 0;
-	bool no_host = false;                                        // a run that does not fit ends the call: nothing marks, or piles up, on the host
+	std::vector<int64_t> ref_len; bwahip_qc_builder *qb = nullptr;   // the contigs' lengths; the fall-back's QC builder
 	std::atomic<bool> fell_back{false};                          // read by the drainers: from now on they download
 	Stream fb_stream; HostBuf fb_rec, fb_keys, fb_off;   // the fall-back's downloads: their stream, one pinned buffer each for records, keys and offsets
-	DevSortedSink(const char *h, bwahip_sort_dev_t *s) : sd(s), host(h, s->level, s) { form = OutForm::BamSorted; }
-	// What an entry point asks of the sink: mark (the runs carry templates), qo_ != NULL (the QC summary on qc_fd_).  no_fallback: a run that
-	// does not fit ends the call, sd->level has no reader, the index is written only for bai_fd >= 0; a sink that may fall back always indexes
-	void configure(int bai_fd, bool mark, bwahip_markdup_stats_t *ms_, const bwahip_qc_opt_t *qo_, int qc_fd_, bwahip_qc_stats_t *qs_, bool no_fallback)
-	{
-		if (mark) { form = OutForm::BamSortedDup; markdup = true; ms = ms_; no_host = true; }
-		if (no_fallback) host.level = 1;
-		if (!no_fallback || bai_fd >= 0) { host.with_bai = true; host.bai_fd = bai_fd; }
-		if (qo_) { qo = qo_; qc_fd = qc_fd_; qs = qs_; }
-	}
-	// beside configure(..., no_fallback = true): the pileup of the file on pu_fd_ (k_pileup.hip), over the contexts' reference
-	void configure_pileup(const bwahip_pileup_opt_t *po_, int pu_fd_, bwahip_pileup_stats_t *ps_) { po = po_; pu_fd = pu_fd_; ps = ps_; no_host = true; }
-	// likewise the recalibration table of the file on rc_fd_ (k_recal.hip), over the contexts' reference and this mask
-	void configure_recal(const bwahip_recal_opt_t *ro_, const uint8_t *mask_, int rc_fd_, bwahip_recal_stats_t *rs_) { ro = ro_; rc_mask = mask_; rc_fd = rc_fd_; rcs = rs_; no_host = true; }
+	DevSortedSink(const char *h, const SortedDevReq &r) : rq(r), sd(r.sd), host(h, r.fall_back ? r.sd->level : 1, r.sd)
+	{ form = rq.mark ? OutForm::BamSortedDup : OutForm::BamSorted; host.with_bai = rq.index; host.bai_fd = rq.bai_fd; }
 	~DevSortedSink()
 	{
 		if (ctx0) (void)hipSetDevice(ctx0->device);
@@ -193,29 +193,15 @@ struct DevSortedSink : Sink {
 		int r = host.prepare(ctxs[0]);                              // the host merger itself is opened only at a fall-back: tmp_dir is not looked at before
 		if (r) return r;
 		sd->fell_back = 0; sd->fell_back_at_run = 0; memset(&sd->dev, 0, sizeof sd->dev);
-		if (host.with_bai) { const bwahip_bns_t *bns = bwahip_bns(ctxs[0]); for (int32_t i = 0; i < bns->n_seqs; ++i) bai_windows += ((int64_t)bns->anns[i].len + 16383) >> 14; }
+		const bwahip_bns_t *bns = bwahip_bns(ctxs[0]);
+		for (int32_t i = 0; i < bns->n_seqs; ++i) ref_len.push_back(bns->anns[i].len);
+		if (host.with_bai) for (int64_t L : ref_len) bai_windows += (L + 16383) >> 14;
 		if ((r = bwahip_bam_devmerger_open(ctxs[0], sd->piece_blocks, &dm))) return r;
-		if (qo) {                                                   // bad options are refused here, before anything starts
-			const bwahip_bns_t *bns = bwahip_bns(ctxs[0]);
-			for (int32_t i = 0; i < bns->n_seqs; ++i) qc_len.push_back(bns->anns[i].len);
-			if ((r = bwahip_bam_devmerger_set_qc(dm, qo, (int32_t)qc_len.size(), qc_len.data(), qc_fd, qs))) return r;
-			const int ws = qo->window_shift ? qo->window_shift : 14;
-			int64_t sum = 0;
-			for (int64_t L : qc_len) { sum += L; qc_windows += (L + (1ll << ws) - 1) >> ws; }
-			qc_need = bwahip_qc_hbm_need((int64_t)qc_len.size(), sum, qc_windows, 0);
-		}
-		if (po) {                                                   // as the QC options: refused here
-			const bwahip_bns_t *bns = bwahip_bns(ctxs[0]);
-			for (int32_t i = 0; i < bns->n_seqs; ++i) pu_len.push_back(bns->anns[i].len);
-			if ((r = bwahip_bam_devmerger_set_pileup(dm, po, (int32_t)pu_len.size(), pu_len.data(), nullptr, pu_fd, ps))) return r;
-		}
-		if (ro) {                                                   // likewise
-			const bwahip_bns_t *bns = bwahip_bns(ctxs[0]);
-			std::vector<int64_t> len;
-			for (int32_t i = 0; i < bns->n_seqs; ++i) len.push_back(bns->anns[i].len);
-			if ((r = bwahip_bam_devmerger_set_recal(dm, ro, (int32_t)len.size(), len.data(), nullptr, rc_mask, rc_fd, rcs))) return r;
-			rc_need = bwahip_recal_hbm_need(bns->l_pac, ro->max_cycle, rc_mask != nullptr);
-		}
+		// the merger is armed for what was asked: bad options are refused here, before anything starts.  Pileup and table read the contexts' reference
+		const int32_t n_ref = (int32_t)ref_len.size();
+		if (rq.qc && (r = bwahip_bam_devmerger_set_qc(dm, rq.qc, n_ref, ref_len.data(), rq.qc_fd, rq.qs))) return r;
+		if (rq.pu && (r = bwahip_bam_devmerger_set_pileup(dm, rq.pu, n_ref, ref_len.data(), nullptr, rq.pu_fd, rq.ps))) return r;
+		if (rq.rc && (r = bwahip_bam_devmerger_set_recal(dm, rq.rc, n_ref, ref_len.data(), nullptr, rq.mask, rq.rc_fd, rq.rs))) return r;
 		ctx0 = ctxs[0]; hbm_budget = sd->hbm_budget;
 		piece_blocks = sd->piece_blocks > 0 ? sd->piece_blocks : ctx0->knobs.sorted_piece_blocks;
 		if (!hbm_budget) {                                          // half of what the device has free now
@@ -231,17 +217,17 @@ struct DevSortedSink : Sink {
 		if (!fell_back) {                                           // the run stays in HBM: no download, the writer gets an item without bytes and both sets go back at once
 			const int r = pipe_stage_out_devrun(c, out, &it.run, &it.raw_len, &it.n_rec, &it.gpu_ms, t_end);
 			if (r || it.run) { it.len = it.raw_len; it.holds_set = false; return r; }
-			if (no_host) return BWAHIP_ECAPACITY;                    // the run's buffers could not be allocated, and nothing marks on the host
+			if (!rq.fall_back) return BWAHIP_ECAPACITY;              // the run's buffers could not be allocated, and this run does not end on the host
 		}                                                           // (its buffers could not be allocated: downloaded as any run after a fall-back, which it causes)
 		return host.stage_out(c, out, it, t_end);
 	}
-	// the HBM the enabled stages take beside the merger's own, for this many records, raw bytes and templates
+	// the HBM the enabled stages take beside the merger's own, for this many records, raw bytes and templates: what the armed record stages
+	// say they will take, and the shares of the index and of the marking, which are the finish plan's and no record stages
 	int64_t stages_need(int64_t n_rec, int64_t raw, int64_t n_tmpl) const
 	{
-		int64_t need = qc_need + rc_need;
+		int64_t need = bam_devmerger_record_stages_need(dm, n_rec);
 		if (host.with_bai) need += bwahip_bam_devmerge_bai_hbm_need(n_rec, bgzf_blocks(raw), host.n_ref, bai_windows);
-		if (markdup) need += bwahip_bam_devmerge_markdup_hbm_need(n_rec, n_tmpl);
-		if (po) need += bwahip_pileup_hbm_need(n_rec);
+		if (rq.mark) need += bwahip_bam_devmerge_markdup_hbm_need(n_rec, n_tmpl);
 		return need;
 	}
 	// a run in HBM -> the host merger, through the pinned buffers; the run is freed whatever happens
@@ -260,7 +246,7 @@ struct DevSortedSink : Sink {
 	int fall_back(int64_t at)
 	{
 		int rc = bwahip_bam_merger_open(host.tmp_dir, host.mem_budget, &host.m);
-		if (!rc && qo && !(rc = bwahip_qc_builder_open((int32_t)qc_len.size(), qc_len.data(), qo, &qb))) rc = bwahip_bam_merger_set_qc(host.m, qb);   // the host builder listens to the host merge
+		if (!rc && rq.qc && !(rc = bwahip_qc_builder_open((int32_t)ref_len.size(), ref_len.data(), rq.qc, &qb))) rc = bwahip_bam_merger_set_qc(host.m, qb);   // the host builder listens to the host merge
 		std::vector<std::pair<int64_t, DevRun*>> held;
 		bam_devmerger_take_runs(dm, &held);
 		for (auto &h : held) { if (!rc) rc = run_to_host(h.first, h.second, 0); else bam_devrun_free(h.second); }
@@ -274,7 +260,7 @@ struct DevSortedSink : Sink {
 			const int64_t need = bwahip_bam_devmerge_hbm_need(held_raw + it.raw_len, held_rec + it.n_rec, seq_no + 1, piece_blocks) +
 			                     stages_need(held_rec + it.n_rec, held_raw + it.raw_len, held_tmpl + (it.run ? it.run->n_tmpl : 0));
 			const bool fits = it.run && need <= hbm_budget;
-			if (!fits) r = no_host ? BWAHIP_ECAPACITY : fall_back(seq_no);
+			if (!fits) r = rq.fall_back ? fall_back(seq_no) : BWAHIP_ECAPACITY;
 		}
 		if (!r && !fell_back) { if (!(r = bam_devmerger_adopt(dm, seq_no, it.run))) { held_tmpl += it.run->n_tmpl; it.run = nullptr; held_raw += it.raw_len; held_rec += it.n_rec; host.sort_ms += it.gpu_ms; } }
 		else if (!r && it.run) { r = run_to_host(seq_no, it.run, it.gpu_ms); it.run = nullptr; }
@@ -287,19 +273,25 @@ struct DevSortedSink : Sink {
 	{
 		if (fell_back) {                                            // from here on this is the host-merged run at sd->level
 			int r = host.finish();
-			if (!r && qb) r = bwahip_qc_builder_finish(qb, qc_fd);   // the summary last, as the index: nothing of it unless the file is whole
-			if (!r && qb && qs) { memset(qs, 0, sizeof *qs); qs->n_windows = qc_windows; qs->qc_bytes = 12580 + 48 * (int64_t)qc_len.size() + 8 * qc_windows; }
+			if (!r && qb) r = bwahip_qc_builder_finish(qb, rq.qc_fd);   // the summary last, as the index: nothing of it unless the file is whole
+			if (!r && qb && rq.qs) {
+				bwahip_qc_opt_t o;
+				(void)qc_resolve(rq.qc, &o);                             // (the builder took them)
+				memset(rq.qs, 0, sizeof *rq.qs);
+				for (int64_t L : ref_len) rq.qs->n_windows += qc_windows(L, o.window_shift);
+				rq.qs->qc_bytes = qc_file_bytes((int64_t)ref_len.size(), rq.qs->n_windows);
+			}
 			return r;
 		}
 		return finish_on_device();
 	}
-	// the header at level 1, the device merger's finish with the stages the sink was configured for, the end-of-file block.  The plan goes
+	// the header at level 1, the device merger's finish with the stages the request names, the end-of-file block.  The plan goes
 	// straight to the internal finish: what the C entry points check or clear holds here already (n_ref is the contig table's, base the
 	// header's bytes, ms was cleared by the entry point, no index stats are asked for)
 	int finish_on_device()
 	{
 		FinishPlan plan;
-		plan.index = host.with_bai; plan.bai_fd = host.bai_fd; plan.n_ref = host.n_ref; plan.mark = markdup; plan.ms = ms;
+		plan.index = host.with_bai; plan.bai_fd = host.bai_fd; plan.n_ref = host.n_ref; plan.mark = rq.mark; plan.ms = rq.mark ? rq.ms : nullptr;
 		int r = host.write_header(1, &plan.base);
 		if (!r) r = bam_devmerger_finish(dm, fd, &sd->dev, plan);
 		if (!r) { sd->n_records = sd->dev.n_records; sd->n_runs = sd->dev.n_runs; sd->merge_s = sd->dev.finish_s; }
@@ -317,7 +309,7 @@ struct DevSortedSink : Sink {
 struct SpillSortedSink : DevSortedSink {
 	bwahip_spill_t *sp; bool spilling = false;
 	int64_t spilled_raw = 0, longest = 0, all_rec = 0, all_tmpl = 0; int wp = 0;
-	SpillSortedSink(const char *h, bwahip_sort_dev_t *s, bwahip_spill_t *p) : DevSortedSink(h, s), sp(p) {}
+	SpillSortedSink(const char *h, const SortedDevReq &r) : DevSortedSink(h, r), sp(r.sp) {}
 	int open(bwahip_ctx *const *ctxs, int n_ctx) override
 	{
 		if (sp->host_budget < 0 || sp->window_pieces > 65536) return BWAHIP_EINVAL;
@@ -625,15 +617,29 @@ extern "C" int bwahip_stream_run_bam_dev(bwahip_ctx *const *ctxs, int n_ctx, con
 	return stream_run(ctxs, n_ctx, opt, pes0, fq1, fq2, out_fd, st, sink);
 }
 
+// One device-merged run as the request says (SortedDevReq): the stats structs it names are cleared, the sink is the spilling one when it names a store
+static int stream_run_sorted_dev(bwahip_ctx *const *ctxs, int n_ctx, const bwahip_opt_t *opt, const bwahip_pestat_t *pes0, const char *fq1, const char *fq2, int out_fd,
+                                 const char *hdr_line, bwahip_stream_t *st, const SortedDevReq &r)
+{
+	if (!r.sd) return BWAHIP_EINVAL;
+	if (r.ms) memset(r.ms, 0, sizeof *r.ms);
+	if (r.qs) memset(r.qs, 0, sizeof *r.qs);
+	if (r.ps) memset(r.ps, 0, sizeof *r.ps);
+	if (r.rs) memset(r.rs, 0, sizeof *r.rs);
+	if (r.sp) { SpillSortedSink sink(hdr_line, r); return stream_run(ctxs, n_ctx, opt, pes0, fq1, fq2, out_fd, st, sink); }
+	DevSortedSink sink(hdr_line, r);
+	return stream_run(ctxs, n_ctx, opt, pes0, fq1, fq2, out_fd, st, sink);
+}
+
 // FASTQ files in -> a coordinate-sorted BAM file out with the runs kept in HBM: every batch is sorted on its context as above, copied device
 // to device into buffers of its own and merged, gathered and deflated on ctxs[0]'s device after the last batch (k_bammerge.hip); when the
 // runs outgrow sd->hbm_budget the run ends as bwahip_stream_run_bam_sorted does, on the host
 extern "C" int bwahip_stream_run_bam_sorted_dev(bwahip_ctx *const *ctxs, int n_ctx, const bwahip_opt_t *opt, const bwahip_pestat_t *pes0,
                                                 const char *fq1, const char *fq2, int out_fd, const char *hdr_line, bwahip_stream_t *st, bwahip_sort_dev_t *sd)
 {
-	if (!sd) return BWAHIP_EINVAL;
-	DevSortedSink sink(hdr_line, sd);
-	return stream_run(ctxs, n_ctx, opt, pes0, fq1, fq2, out_fd, st, sink);
+	SortedDevReq r;
+	r.sd = sd; r.fall_back = true;
+	return stream_run_sorted_dev(ctxs, n_ctx, opt, pes0, fq1, fq2, out_fd, hdr_line, st, r);
 }
 
 // The two coordinate-sorted entry points with the BAI index of the file on bai_fd: the same sinks, which then count the header's member
@@ -650,10 +656,9 @@ extern "C" int bwahip_stream_run_bam_sorted_bai(bwahip_ctx *const *ctxs, int n_c
 extern "C" int bwahip_stream_run_bam_sorted_dev_bai(bwahip_ctx *const *ctxs, int n_ctx, const bwahip_opt_t *opt, const bwahip_pestat_t *pes0,
                                                     const char *fq1, const char *fq2, int out_fd, const char *hdr_line, bwahip_stream_t *st, bwahip_sort_dev_t *sd, int bai_fd)
 {
-	if (!sd) return BWAHIP_EINVAL;
-	DevSortedSink sink(hdr_line, sd);
-	sink.configure(bai_fd, false, nullptr, nullptr, -1, nullptr, false);
-	return stream_run(ctxs, n_ctx, opt, pes0, fq1, fq2, out_fd, st, sink);
+	SortedDevReq r;
+	r.sd = sd; r.fall_back = true; r.with_index(bai_fd);
+	return stream_run_sorted_dev(ctxs, n_ctx, opt, pes0, fq1, fq2, out_fd, hdr_line, st, r);
 }
 
 // bwahip_stream_run_bam_sorted_dev_bai with duplicate marking (k_markdup.hip): the batches leave their contexts with templates and descriptors,
@@ -662,11 +667,9 @@ extern "C" int bwahip_stream_run_bam_sorted_dev_markdup(bwahip_ctx *const *ctxs,
                                                         const char *fq1, const char *fq2, int out_fd, const char *hdr_line, bwahip_stream_t *st, bwahip_sort_dev_t *sd, int bai_fd,
                                                         bwahip_markdup_stats_t *ms)
 {
-	if (!sd) return BWAHIP_EINVAL;
-	if (ms) memset(ms, 0, sizeof *ms);
-	DevSortedSink sink(hdr_line, sd);
-	sink.configure(bai_fd, true, ms, nullptr, -1, nullptr, true);
-	return stream_run(ctxs, n_ctx, opt, pes0, fq1, fq2, out_fd, st, sink);
+	SortedDevReq r;
+	r.sd = sd; r.with_index(bai_fd); r.mark = true; r.ms = ms;
+	return stream_run_sorted_dev(ctxs, n_ctx, opt, pes0, fq1, fq2, out_fd, hdr_line, st, r);
 }
 
 // The two entry points above with the QC summary of the file on qc_fd (k_qc.hip): the merger is armed, so its finish runs the stage after the
@@ -676,28 +679,25 @@ extern "C" int bwahip_stream_run_bam_sorted_dev_qc(bwahip_ctx *const *ctxs, int 
                                                    bwahip_markdup_stats_t *ms, int markdup, const bwahip_qc_opt_t *qo, int qc_fd, bwahip_qc_stats_t *qs)
 {
 	if (!sd || !qo) return BWAHIP_EINVAL;
-	if (ms) memset(ms, 0, sizeof *ms);
-	if (qs) memset(qs, 0, sizeof *qs);
-	DevSortedSink sink(hdr_line, sd);
-	sink.configure(bai_fd, markdup != 0, ms, qo, qc_fd, qs, markdup != 0);   // unmarked, the run may end on the host: it always indexes
-	return stream_run(ctxs, n_ctx, opt, pes0, fq1, fq2, out_fd, st, sink);
+	SortedDevReq r;
+	r.sd = sd; r.fall_back = !markdup; r.with_index(bai_fd); r.mark = markdup != 0; r.ms = ms;
+	r.qc = qo; r.qc_fd = qc_fd; r.qs = qs;
+	return stream_run_sorted_dev(ctxs, n_ctx, opt, pes0, fq1, fq2, out_fd, hdr_line, st, r);
 }
 
-// The device-merged entry points with the pileup of the file on pu_fd (k_pileup.hip): the sink as _dev_markdup or _dev_qc configure it, without a
-// fall-back, its merger armed for the pileup over the contexts' reference
+// The device-merged entry points with the pileup of the file on pu_fd (k_pileup.hip), over the contexts' reference: marking, index and QC
+// summary as asked, never a fall-back
 extern "C" int bwahip_stream_run_bam_sorted_dev_pileup(bwahip_ctx *const *ctxs, int n_ctx, const bwahip_opt_t *opt, const bwahip_pestat_t *pes0,
                                                        const char *fq1, const char *fq2, int out_fd, const char *hdr_line, bwahip_stream_t *st, bwahip_sort_dev_t *sd, int bai_fd,
                                                        int mark, bwahip_markdup_stats_t *ms, const bwahip_qc_opt_t *qc, int qc_fd, bwahip_qc_stats_t *qs,
                                                        const bwahip_pileup_opt_t *pu, int pu_fd, bwahip_pileup_stats_t *ps)
 {
 	if (!sd || !pu) return BWAHIP_EINVAL;
-	if (ms) memset(ms, 0, sizeof *ms);
-	if (qs) memset(qs, 0, sizeof *qs);
-	if (ps) memset(ps, 0, sizeof *ps);
-	DevSortedSink sink(hdr_line, sd);
-	sink.configure(bai_fd, mark != 0, ms, qc, qc_fd, qs, true);
-	sink.configure_pileup(pu, pu_fd, ps);
-	return stream_run(ctxs, n_ctx, opt, pes0, fq1, fq2, out_fd, st, sink);
+	SortedDevReq r;
+	r.sd = sd; r.with_index(bai_fd); r.mark = mark != 0; r.ms = ms;
+	r.qc = qc; r.qc_fd = qc_fd; r.qs = qs;
+	r.pu = pu; r.pu_fd = pu_fd; r.ps = ps;
+	return stream_run_sorted_dev(ctxs, n_ctx, opt, pes0, fq1, fq2, out_fd, hdr_line, st, r);
 }
 
 // The device-merged entry points in one, for samples whose record bytes outgrow HBM: runs that do not fit sd->hbm_budget are held spilled
@@ -708,11 +708,10 @@ extern "C" int bwahip_stream_run_bam_sorted_dev_spill(bwahip_ctx *const *ctxs, i
                                                       int bai_fd, int mark, bwahip_markdup_stats_t *ms, const bwahip_qc_opt_t *qc, int qc_fd, bwahip_qc_stats_t *qs)
 {
 	if (!sd || !sp) return BWAHIP_EINVAL;
-	if (ms) memset(ms, 0, sizeof *ms);
-	if (qs) memset(qs, 0, sizeof *qs);
-	SpillSortedSink sink(hdr_line, sd, sp);
-	sink.configure(bai_fd, mark != 0, ms, qc, qc_fd, qs, true);
-	return stream_run(ctxs, n_ctx, opt, pes0, fq1, fq2, out_fd, st, sink);
+	SortedDevReq r;
+	r.sd = sd; r.sp = sp; r.with_index(bai_fd); r.mark = mark != 0; r.ms = ms;
+	r.qc = qc; r.qc_fd = qc_fd; r.qs = qs;
+	return stream_run_sorted_dev(ctxs, n_ctx, opt, pes0, fq1, fq2, out_fd, hdr_line, st, r);
 }
 
 // bwahip_stream_run_bam_sorted_dev_spill with the recalibration table of the file on rc_fd (k_recal.hip): the same sink, its merger armed for the
@@ -723,11 +722,9 @@ extern "C" int bwahip_stream_run_bam_sorted_dev_recal(bwahip_ctx *const *ctxs, i
                                                       const bwahip_recal_opt_t *rc, const uint8_t *mask, int rc_fd, bwahip_recal_stats_t *rs)
 {
 	if (!sd || !sp || !rc) return BWAHIP_EINVAL;
-	if (ms) memset(ms, 0, sizeof *ms);
-	if (qs) memset(qs, 0, sizeof *qs);
-	if (rs) memset(rs, 0, sizeof *rs);
-	SpillSortedSink sink(hdr_line, sd, sp);
-	sink.configure(bai_fd, mark != 0, ms, qc, qc_fd, qs, true);
-	sink.configure_recal(rc, mask, rc_fd, rs);
-	return stream_run(ctxs, n_ctx, opt, pes0, fq1, fq2, out_fd, st, sink);
+	SortedDevReq r;
+	r.sd = sd; r.sp = sp; r.with_index(bai_fd); r.mark = mark != 0; r.ms = ms;
+	r.qc = qc; r.qc_fd = qc_fd; r.qs = qs;
+	r.rc = rc; r.mask = mask; r.rc_fd = rc_fd; r.rs = rs;
+	return stream_run_sorted_dev(ctxs, n_ctx, opt, pes0, fq1, fq2, out_fd, hdr_line, st, r);
 }

@@ -328,14 +328,14 @@ def stream_case(built, tmp_path_factory):
     return dict(fq1=fqs[0], fq2=fqs[1])
 
 
-def _stream(fn, ctxs, sc, tmp_path, **kw):
+def _stream(fn, ctxs, sc, tmp_path, index=True, hbm_budget=8 << 30, **kw):
     opt = bw.default_opt()
     opt.n_threads = 4
     out = str(tmp_path / "o.bam")
     fd, fb, fq, fp = (os.open(out + x, os.O_WRONLY | os.O_CREAT | os.O_TRUNC, 0o644) for x in ("", ".bai", ".bqc", ".bpu"))
     try:
         extra = dict(pu_fd=fp) if "pileup" in kw else {}
-        res = fn(ctxs, sc["fq1"], sc["fq2"], fd, fb, fq, hdr_line=HDR, opt=opt, chunk_bases=K, reader_threads=2, hbm_budget=8 << 30, **extra, **kw)
+        res = fn(ctxs, sc["fq1"], sc["fq2"], fd, fb if index else -1, fq, hdr_line=HDR, opt=opt, chunk_bases=K, reader_threads=2, hbm_budget=hbm_budget, **extra, **kw)
     finally:
         for x in (fd, fb, fq, fp):
             os.close(x)
@@ -371,3 +371,27 @@ def test_stream_driver_writes_the_pileup_of_the_file(small_index, stream_case, t
         finally:
             for c in ctxs[1:]:
                 c.close()
+
+
+@pytest.mark.parametrize("with_index_and_qc", [False, True])
+def test_stream_driver_budget_counts_the_pileup_to_the_byte(small_index, stream_case, tmp_path, with_index_and_qc):
+    """The entry point's HBM budget at its boundary: the merger's need for all five runs plus bwahip_pileup_hbm_need of their records -- with
+    the index and the QC summary, their shares as well -- is a budget the run fits (no fall-back, every file that of the ample run); one
+    byte less and the last run is refused, as this entry point never falls back."""
+    qc_opt = (8, -1, 0) if with_index_and_qc else None
+    kw = dict(index=with_index_and_qc, qc=qc_opt, markdup=0, pileup=(20, 0, 0, 2))
+    with bw.Context(small_index["prefix"]) as c0:
+        bns = bw.lib().bwahip_bns(c0._h).contents
+        lens = [bns.anns[i].len for i in range(bns.n_seqs)]
+        files0, (st, sd, _, _, ps) = _stream(bw.stream_run_bam_sorted_dev_pileup, [c0], stream_case, tmp_path, **kw)
+        raw, n_rec, n_runs = sd.dev.raw_bytes, sd.dev.n_records, sd.dev.n_runs
+        assert sd.fell_back == 0 and n_runs == 5 and n_rec >= 2600 and files0[3] and bool(files0[1]) == bool(files0[2]) == with_index_and_qc
+        need = bw.bam_devmerge_hbm_need(raw, n_rec, n_runs, 1024) + bw.pileup_hbm_need(n_rec)
+        if with_index_and_qc:
+            need += bw.bam_devmerge_bai_hbm_need(n_rec, (raw + 65279) // 65280, len(lens), sum((n + 16383) >> 14 for n in lens))
+            need += bw.qc_hbm_need(len(lens), sum(lens), sum((n + 255) >> 8 for n in lens), 0)
+        print(f"index and QC {with_index_and_qc}: raw {raw}, records {n_rec}, runs {n_runs}, need {need}, of it the pileup's {bw.pileup_hbm_need(n_rec)}")
+        files, (_, sd, _, _, _) = _stream(bw.stream_run_bam_sorted_dev_pileup, [c0], stream_case, tmp_path, hbm_budget=need, **kw)
+        assert sd.fell_back == 0 and files == files0, "a budget of exactly the need"
+        with pytest.raises(bw.BwahipError, match="ECAPACITY"):
+            _stream(bw.stream_run_bam_sorted_dev_pileup, [c0], stream_case, tmp_path, hbm_budget=need - 1, **kw)

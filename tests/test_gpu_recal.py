@@ -431,14 +431,14 @@ def stream_case(built, tmp_path_factory):
     return dict(fq1=fqs[0], fq2=fqs[1])
 
 
-def _stream(fn, ctxs, sc, tmp_path, **kw):
+def _stream(fn, ctxs, sc, tmp_path, index=True, hbm_budget=8 << 30, **kw):
     opt = bw.default_opt()
     opt.n_threads = 4
     out = str(tmp_path / "o.bam")
     fd, fb, fq, fr = (os.open(out + x, os.O_WRONLY | os.O_CREAT | os.O_TRUNC, 0o644) for x in ("", ".bai", ".bqc", ".brc"))
     try:
         extra = dict(rc_fd=fr) if "recal" in kw else {}
-        res = fn(ctxs, sc["fq1"], sc["fq2"], fd, fb, fq, hdr_line=HDR, opt=opt, chunk_bases=K, reader_threads=2, hbm_budget=8 << 30, **extra, **kw)
+        res = fn(ctxs, sc["fq1"], sc["fq2"], fd, fb if index else -1, fq, hdr_line=HDR, opt=opt, chunk_bases=K, reader_threads=2, hbm_budget=hbm_budget, **extra, **kw)
     finally:
         for x in (fd, fb, fq, fr):
             os.close(x)
@@ -477,3 +477,27 @@ def test_stream_driver_writes_the_table_of_the_file(small_index, stream_case, tm
         finally:
             for c in ctxs[1:]:
                 c.close()
+
+
+@pytest.mark.parametrize("with_mask", [False, True])
+def test_stream_driver_budget_counts_the_table_to_the_byte(small_index, stream_case, tmp_path, with_mask):
+    """The spilling entry point's HBM budget at its boundary: the merger's need for all five runs resident, one window of staging reserved,
+    plus bwahip_recal_hbm_need -- the mask's bytes in it or not -- is a budget under which no run is spilled; one byte less and the last run
+    is held spilled, and the file and the table are still the resident run's."""
+    pb, wp = 1, 2
+    with bw.Context(small_index["prefix"]) as c0:
+        bns = bw.lib().bwahip_bns(c0._h).contents
+        l_pac = sum(bns.anns[i].len for i in range(bns.n_seqs))
+        assert l_pac == bns.l_pac
+        rng = random.Random(9)
+        mask = ref.make_mask(l_pac, {g for g in range(l_pac) if rng.random() < 0.01}) if with_mask else None
+        kw = dict(index=False, qc=None, markdup=0, recal=(20, 0, 0, 0), mask=mask, piece_blocks=pb, window_pieces=wp, host_budget=1 << 30)
+        files0, (st, sd, sp, _, _, rs) = _stream(bw.stream_run_bam_sorted_dev_recal, [c0], stream_case, tmp_path, **kw)
+        raw, n_rec, n_runs = sd.dev.raw_bytes, sd.dev.n_records, sd.dev.n_runs
+        assert sp.n_spilled_runs == 0 and n_runs == 5 and n_rec >= 2600 and files0[3] and files0[1] == files0[2] == b""
+        need = bw.bam_devmerge_spill_hbm_need(raw, wp * pb * 65280, 0, n_rec, n_runs, pb, wp) + bw.recal_hbm_need(l_pac, 0, with_mask)
+        print(f"mask {with_mask}: raw {raw}, records {n_rec}, runs {n_runs}, need {need}, of it the table's {bw.recal_hbm_need(l_pac, 0, with_mask)}")
+        files, (_, sd, sp, _, _, _) = _stream(bw.stream_run_bam_sorted_dev_recal, [c0], stream_case, tmp_path, hbm_budget=need, **kw)
+        assert sp.n_spilled_runs == 0 and sd.fell_back == 0 and files == files0, "a budget of exactly the need"
+        files, (_, sd, sp, _, _, _) = _stream(bw.stream_run_bam_sorted_dev_recal, [c0], stream_case, tmp_path, hbm_budget=need - 1, **kw)
+        assert sp.n_spilled_runs >= 1 and sd.fell_back == 0 and files == files0, "one byte less: the file or the table changed, or nothing was spilled"
